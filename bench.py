@@ -17,7 +17,11 @@ flight per launch sequence -- the way every keyframe is re-matched against the m
 pose_graph/graph.cpp:171-197.  Every call starts cold (no neighbour lists carried over).
 Map, kd-trees and scans are resident in HBM before the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (`--dump-outputs DIR`: and writes what the last timed step
+returned as DIR/<name>.npy).  Everything else -- the same steps through the other search modes, the grid sweep's tally step,
+the secondary legs, the CPU baseline and its parity check, the RCCL check -- runs with `--full` only.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes THIS process start N ranks
 (python -m torch.distributed.run, one per GPU) before it touches the GPU, and relay rank 0's line; under
@@ -25,11 +29,11 @@ a launcher (WORLD_SIZE set) the rank count must equal --gpus.  The map is replic
 its own scans (independent problems, no data-path collective: SURVEY.md 8e row 2), `value` is the
 whole-job aggregate.
 
-The LAST stdout line (rank 0) is one compact JSON object (< 6 KB: the contract's keys, `roofline`, `cpu_baseline`, one
-number per secondary leg); the full report goes to bench_report.json and, as one line, to stderr.  `roofline` prices the
+The LAST stdout line (rank 0) is one compact JSON object (< 6 KB: the contract's keys and `roofline`; with `--full` also
+`cpu_baseline` and one number per secondary leg that ran); the full report goes to bench_report.json and, as one line, to stderr.  `roofline` prices the
 sweep's dominant kernel -- SURVEY.md 8d's algorithmic flops (and, beside them, bytes) per point-residual over its average
 duration, measured with HIP events on the library's own stream inside the timed region -- next to what the committed
-rocprofv3 counter passes of this same command say bounds it.  `cpu_baseline` is the oracle (a port of the reference's single-threaded CPU path,
+rocprofv3 counter passes of this same command say bounds it.  `cpu_baseline` (`--full`) is the oracle (a port of the reference's single-threaded CPU path,
 including its per-call kd-tree rebuild) timed on this host on a sample of the same workload.
 """
 import argparse
@@ -87,12 +91,20 @@ def parse_args():
     ap.add_argument("--no-vlp16", action="store_true", help="skip the 16-ring x 1800 throughput leg")
     ap.add_argument("--no-mapping-frame", action="store_true", help="skip the per-frame mapping pipeline leg")
     ap.add_argument("--no-pipeline", action="store_true", help="skip the whole-chain (registration..mapping) leg")
-    ap.add_argument("--headline-only", action="store_true", help="only the timed region (profiling passes)")
+    ap.add_argument("--headline-only", action="store_true",
+                    help="with --full: the timed region, the grid sweep's tally step and the RCCL check only (the command the "
+                         "profiling passes wrap); implied without --full")
     ap.add_argument("--shard-points", action="store_true",
                     help="run the sharded-points leg even on one GPU (RCCL all-reduce over a world of 1)")
     ap.add_argument("--leg-timeout", type=int, default=1500, help="seconds the legs after the headline may take in all")
     ap.add_argument("--pg-iters", type=int, default=1000, help="LM iteration limit of the pose-graph leg")
     ap.add_argument("--cpu-scans", type=int, default=48, help="scans the single-core CPU baseline matches")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the other search modes, the secondary legs, the CPU baseline and its "
+                         "parity check, the grid sweep's tally step and the RCCL check (the --no-* options pick among them). "
+                         "Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (poses and per-scan statistics) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -113,6 +125,8 @@ def spawn_ranks(n):
 
 def main():
     args = parse_args()
+    if not args.full:  # a plain run: the timed region and its line only
+        args.headline_only = True
     if args.headline_only:
         args.no_cpu_baseline = args.no_joint_stereo = args.no_pose_graph = args.no_single = args.no_vlp16 = True
         args.no_mapping_frame = args.no_pipeline = True
@@ -331,7 +345,9 @@ def main():
                                     "loop_rounds_per_wavefront": section_ticks[11] / max(1, 64 * section_ticks[9]),
                                     "loop_lane_use": section_ticks[10] / max(1, section_ticks[11]),
                                     "share": {names[i]: section_ticks[i] / tot for i in range(9) if i != 6}}
-    if ctx.grid_launches() > 0:  # what share of the points the grid sweeps left to the tree search (one more step, counted; untimed)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, status, poses, sts, rank, world, np)
+    if args.full and ctx.grid_launches() > 0:  # what share of the points the grid sweeps left to the tree search (one more step, counted; untimed)
         import ctypes
         opts.debug_stats = 1
         g0 = (ctypes.c_uint64 * 3)()
@@ -456,7 +472,7 @@ def main():
         except Exception as e:
             out["final_feature_map"] = {"error": repr(e)}
     comm = None
-    if world == 1 and not args.shard_points and rank == 0:
+    if args.full and world == 1 and not args.shard_points and rank == 0:
         # a world of one: the line still says that librccl loads on this box and that the library's communicator answers
         # (ncclCommCount), with the version it found -- no collective is on the data path at N = 1
         try:
@@ -895,6 +911,24 @@ def make_comm(pkg, dist, torch, rank, local_rank, world):
         dist.broadcast(t, src=0)
         uid = t.cpu().numpy().astype(np.uint8)
     return pkg.Comm(local_rank, uid, rank, world)
+
+
+# the per-scan lslam_stats fields a caller of lslam_scanmatch_run_batch reads as results (the timings and the launch count are
+# measurements of the run, not outputs of it)
+DUMP_STATS = ("status", "iterations", "n_line", "n_plane", "n_rows", "degenerate", "converged", "delta_r", "delta_t", "score",
+              "percent", "point_residuals", "sweeps", "score2", "percent2")
+
+
+def dump_outputs(d, status, poses, sts, rank, world, np):
+    """--dump-outputs: what the last timed step returned -- the refined poses (float32, as the library writes them), the
+    batch's worst status and the per-scan statistics (float64; every integer field is exact in it) -- as d/<name>.npy.
+    About 140 KB at the default sizes.  With several ranks every rank writes its own files, suffixed _rank<r>."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"poses": np.ascontiguousarray(poses, np.float32), "batch_status": np.array([int(status)], np.float64)}
+    for f in DUMP_STATS:
+        arrays["stats_" + f] = np.array([getattr(s, f) for s in sts], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), a)
 
 
 def quiet_gc():

@@ -20,8 +20,10 @@ def _free_port():
 
 
 def _worker(rank, world, port, q):
+    # LSLAM_FORCE_DEVICE: on a box with a GPU, both ranks on device 0 -- what is tested is the process group, and the box may
+    # have fewer GPUs than ranks
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world),
-                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), LSLAM_FORCE_DEVICE="0")
     sys.path.insert(0, ROOT)
     d = importlib.import_module("the-cooper-mapper_amd.dist")
     dist = d.init(backend="gloo")
@@ -65,7 +67,8 @@ def _rs_worker(rank, world, port, q):
     """The exchange pattern of the library's row-sharded PCG (csrc/lslam_posegraph.hip, lslam_pg_set_row_shard) under a real
     process group, in numpy: own rows multiplied / updated / preconditioned locally, one scalar all-reduce (p . A p) and one
     all-reduce of the zero-padded z with r . z, r . r behind it per iteration, the direction recomputed by every rank."""
-    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                      LSLAM_FORCE_DEVICE="0")  # as in _worker
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import numpy as np
@@ -175,13 +178,14 @@ def test_row_shard_range_partitions(n, world):
 
 def test_bench_gpus_flag_starts_that_many_ranks():
     """`python bench.py --gpus 2` outside a launcher starts 2 ranks itself (before anything touches the GPU)
-    and rank 0 reports n_gpus == 2; under a launcher whose world size differs from --gpus it refuses."""
+    and rank 0 reports n_gpus == 2; under a launcher whose world size differs from --gpus it refuses.  The dry run prints a
+    line of the shape a --full run prints (every leg present), so that what is held to the 8 KB tail is the longest line."""
     import json
     import subprocess
-    env = dict(os.environ, LSLAM_BENCH_DRY_RUN="1")
+    env = dict(os.environ, LSLAM_BENCH_DRY_RUN="1", LSLAM_FORCE_DEVICE="0")  # (as in _worker)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full"],
                          env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

@@ -1,5 +1,7 @@
 """Loop-closure front end (pose_graph/loop_detector.hpp): the candidate gating on the CPU, a full
 detect -> scanMatchLocal -> Loop on the GPU."""
+import os
+
 import numpy as np
 import pytest
 
@@ -212,20 +214,42 @@ def test_cpp_graph_equals_python_graph(pkg, ctx, synth, small_problem, tmp_path)
     assert files[0] == files[1] and len(files[0]) >= 2  # the same cubes of the same types
 
 
-def test_trajectory_radius_search_matches_reference_nanoflann(pkg):
-    """LoopDetector.radius_search against the reference's own KdTreeFLANN::radiusSearch
-    (oracle/_ref/libref_nanoflann.so, nanoflann_pcl.h:164-186): same indices in the same order, same
-    squared distances, on a looping trajectory flattened to y = 0 as loop_detector.hpp:86-96 does."""
-    from oracle_lib import RefNanoflann, have_ref
-    if not have_ref():
-        pytest.skip("oracle/_ref not built (reference absent)")
+class StoredRadiusSearch:
+    """The reference's answers to radius_search_against's calls, in the order it makes them, as
+    tests/golden/make_ref_live_golden.py stored them in tests/golden/ref_live.npz (where oracle/_ref is not built)."""
+
+    def __init__(self, g, cloud):
+        assert np.array_equal(np.asarray(cloud, np.float32).view(np.uint32), g["radius_cloud"].view(np.uint32)), \
+            "the trajectory cloud is not the one the answers were stored for"
+        self.g, self.i, self.j = g, 0, 0
+
+    def _check_call(self, k, q, radius):
+        g = self.g
+        assert np.array_equal(np.asarray(q, np.float32).reshape(-1).view(np.uint32), g["radius_q"][k].view(np.uint32)) \
+            and np.float32(radius) == g["radius_r"][k], "call %d is not the stored one" % k
+
+    def radius(self, q, radius):
+        self._check_call(self.i, q, radius)
+        a, b = self.g["radius_off"][self.i], self.g["radius_off"][self.i + 1]
+        self.i += 1
+        return self.g["radius_idx"][a:b], self.g["radius_d2"][a:b]
+
+    def radius_as_wrapped(self, q, radius):
+        self._check_call(self.j, q, radius)
+        self.j += 1
+        return int(self.g["radius_nfound"][self.j - 1])
+
+
+def radius_search_against(pkg, make_ref):
+    """The comparison of test_trajectory_radius_search_matches_reference_nanoflann with the reference made by
+    make_ref(cloud) (the reference library itself, or its stored answers)."""
     rng = np.random.default_rng(3)
     s = np.linspace(0, 6 * np.pi, 900)
     xz = np.stack([40 * np.cos(s) + rng.normal(0, 0.3, len(s)), 40 * np.sin(s) + rng.normal(0, 0.3, len(s))], 1)
     kfs = [_kf(pkg, float(x), float(z), float(i), y=float(rng.normal(0, 2))) for i, (x, z) in enumerate(xz)]
     det = pkg.LoopDetector()
     det.update_trajectory(kfs)
-    ref = RefNanoflann(det._trajectory)  # x, 0, z, index: the cloud the reference builds its tree on
+    ref = make_ref(det._trajectory)  # x, 0, z, index: the cloud the reference builds its tree on
     hits = 0
     for k in range(0, len(kfs), 7):
         q = det._trajectory[k, :3] + rng.normal(0, 0.5, 3).astype(np.float32)
@@ -246,6 +270,19 @@ def test_trajectory_radius_search_matches_reference_nanoflann(pkg):
             else:
                 assert len(idx1) == 0  # the reference reports 1 and reads an empty vector here (UB)
     assert hits > 1000
+
+
+def test_trajectory_radius_search_matches_reference_nanoflann(pkg):
+    """LoopDetector.radius_search against the reference's own KdTreeFLANN::radiusSearch
+    (oracle/_ref/libref_nanoflann.so, nanoflann_pcl.h:164-186): same indices in the same order, same
+    squared distances, on a looping trajectory flattened to y = 0 as loop_detector.hpp:86-96 does.  Where
+    oracle/_ref is not built, against the reference's answers to the same calls (tests/golden/ref_live.npz)."""
+    from oracle_lib import RefNanoflann, have_ref
+    if have_ref():
+        radius_search_against(pkg, RefNanoflann)
+    else:
+        g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_live.npz"))
+        radius_search_against(pkg, lambda cloud: StoredRadiusSearch(g, cloud))
 
 
 @pytest.mark.gpu

@@ -1,11 +1,11 @@
 """Pins the oracle's pose-angle state to the reference's own lidar_slam::Angle
 (util/Angle.h): the cached std::sin / std::cos of the float radian and `a += x` == Angle(rad + x).
 Golden vector from the reference (tests/golden/angle_ref.npz, made by make_angle_golden.py); when
-oracle/_ref/libref_angle.so is present the same is checked live on fresh values."""
+oracle/_ref/libref_angle.so is present the same is checked live on fresh values, elsewhere on those values against the reference's
+states stored in tests/golden/ref_live.npz (tests/golden/make_ref_live_golden.py)."""
 import os
 
 import numpy as np
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -44,15 +44,22 @@ def test_angle_state_matches_reference_golden(oracle):
     assert same_bits(got, g["state"])
 
 
-def test_angle_state_matches_reference_live(oracle):
-    ref = os.path.join(ROOT, "oracle", "_ref", "libref_angle.so")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref not built (reference absent)")
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("make_angle_golden", os.path.join(ROOT, "tests", "golden", "make_angle_golden.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+def live_inputs():
     rng = np.random.default_rng(7)
-    rad = rng.uniform(-4, 4, 3000).astype(np.float32)
-    add = rng.normal(0, 0.1, 3000).astype(np.float32)
-    assert same_bits(oracle_states(oracle, rad, add), mod.ref_states(rad, add))
+    return rng.uniform(-4, 4, 3000).astype(np.float32), rng.normal(0, 0.1, 3000).astype(np.float32)
+
+
+def test_angle_state_matches_reference_live(oracle):
+    rad, add = live_inputs()
+    ref = os.path.join(ROOT, "oracle", "_ref", "libref_angle.so")
+    if os.path.exists(ref):
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("make_angle_golden", os.path.join(ROOT, "tests", "golden", "make_angle_golden.py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        want = mod.ref_states(rad, add)
+    else:
+        g = np.load(os.path.join(ROOT, "tests", "golden", "ref_live.npz"))
+        assert same_bits(rad, g["angle_rad"]) and same_bits(add, g["angle_add"]), "the seeded inputs are not the stored ones"
+        want = g["angle_state"]
+    assert same_bits(oracle_states(oracle, rad, add), want)

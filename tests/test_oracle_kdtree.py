@@ -1,10 +1,16 @@
 """Pins oracle/lslam_oracle.c's kd-tree (nanoflann v1.2.3 restatement) to the
 reference: committed golden vectors (generated from the reference's own
-nanoflann.hpp) and, where oracle/_ref was built, the reference library live."""
+nanoflann.hpp) and, where oracle/_ref was built, the reference library live; elsewhere the same queries against the
+reference's answers stored in tests/golden/ref_live.npz (tests/golden/make_ref_live_golden.py)."""
+import os
+import zlib
+
 import numpy as np
 import pytest
 
 from oracle_lib import RefNanoflann, have_ref
+
+REF_LIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_live.npz")
 
 
 def test_oracle_knn_matches_reference_goldens(oracle, goldens):
@@ -28,10 +34,9 @@ def test_goldens_are_sorted_and_exact(goldens):
             assert np.allclose(g["d2"][sub, 4], kth, rtol=1e-5, atol=1e-6), name
 
 
-@pytest.mark.skipif(not have_ref(), reason="oracle/_ref not built (reference absent)")
-@pytest.mark.parametrize("kind", ["uniform", "clustered", "lattice", "stride8"])
-def test_oracle_knn_matches_reference_live(oracle, kind):
-    rng = np.random.default_rng(hash(kind) % 1000)
+def live_inputs(kind, seed):
+    """(map, queries) of the live comparison: seeded clouds of four shapes."""
+    rng = np.random.default_rng(seed)
     if kind == "uniform":
         pts = rng.uniform(-50, 50, (50000, 3)).astype(np.float32)
         q = rng.uniform(-55, 55, (2000, 3)).astype(np.float32)
@@ -50,9 +55,27 @@ def test_oracle_knn_matches_reference_live(oracle, kind):
         pts[:, 4] = rng.uniform(0, 64, 20000)
         q = np.zeros((1000, 8), np.float32)
         q[:, :3] = rng.normal(0, 12, (1000, 3))
-    ref = RefNanoflann(pts)
+    return pts, q
+
+
+def inputs_crc(*arrays):
+    crc = 0
+    for a in arrays:
+        crc = zlib.crc32(np.ascontiguousarray(a).tobytes(), crc)
+    return crc
+
+
+@pytest.mark.parametrize("kind", ["uniform", "clustered", "lattice", "stride8"])
+def test_oracle_knn_matches_reference_live(oracle, kind):
+    if have_ref():
+        pts, q = live_inputs(kind, hash(kind) % 1000)
+        ri, rd = RefNanoflann(pts).knn(q, 5)
+    else:
+        g = np.load(REF_LIVE)
+        pts, q = live_inputs(kind, int(g["knn_%s_seed" % kind]))
+        assert inputs_crc(pts, q) == int(g["knn_%s_crc" % kind]), "the seeded inputs are not the ones the answers were stored for"
+        ri, rd = g["knn_%s_idx" % kind], g["knn_%s_d2" % kind]
     tree = oracle.kdtree(pts)
-    ri, rd = ref.knn(q, 5)
     oi, od = tree.knn(q, 5)
     assert np.array_equal(oi, ri)
     assert np.array_equal(od.view(np.int32), rd.view(np.int32))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # quick A/B of the headline + single-scan legs on the GPU box: tools/ab_bench.sh <tag> [env assignments...]
 tag=$1; shift
-F="--steps 5 --warmup 2 --no-cpu-baseline --no-mapping-frame --no-pipeline --no-joint-stereo --no-pose-graph --map-frames ${MAPF:-3000} ${EXTRA_FLAGS}"
+F="--full --steps 5 --warmup 2 --no-cpu-baseline --no-mapping-frame --no-pipeline --no-joint-stereo --no-pose-graph --map-frames ${MAPF:-3000} ${EXTRA_FLAGS}"
 env "$@" timeout 900 python bench.py $F > gpurun_out/ab_$tag.json 2> gpurun_out/ab_$tag.err || { echo "$tag FAILED"; tail -5 gpurun_out/ab_$tag.err; }
 python - <<PY
 import json

@@ -7,11 +7,11 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-H="$root/bench.py --headline-only --steps 6 --warmup 1 --map-cache /tmp/lslam_${tag}_map"
+H="$root/bench.py --full --headline-only --steps 6 --warmup 1 --map-cache /tmp/lslam_${tag}_map"
 timeout 600 python3 $H > $out/${tag}_headline.json 2> $out/${tag}_headline.err   # builds and saves the map once
-timeout 1500 python3 $root/bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout 1500 python3 $root/bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 cp $out/bench_report.json $out/${tag}_bench_report.json   # the full report of THIS run (later runs overwrite bench_report.json)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -o s -- python3 $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline --pg-iters 20 --map-cache /tmp/lslam_${tag}_map > $out/${tag}_stats.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -o s -- python3 $root/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --pg-iters 20 --map-cache /tmp/lslam_${tag}_map > $out/${tag}_stats.log 2>&1
 cp $out/${tag}_stats/s_kernel_stats.csv $out/${tag}_kernel_stats.csv
 # ... and of the headline command alone (the one the counter passes wrap): (sweep_kernel + sweep_queue_kernel + cert_plan_kernel
 # total) / sweep_kernel calls is the average sweep that roofline.avg_kernel_ms of <tag>_headline.json measures with its HIP events
@@ -29,7 +29,7 @@ for set in "FETCH_SIZE" "WRITE_SIZE" \
 done
 # the headline's sweep is the grid sweep (search AUTO): sweep_grid_kernel + its second pass, mean per sweep
 python3 $root/tools/summarize_pmc.py sweep_grid_kernel,sweep_queue_kernel,cert_plan_kernel $out/${tag}_pmc_sweep.csv $out/${tag}_pmc/p1 $out/${tag}_pmc/p2 $out/${tag}_pmc/p3 $out/${tag}_pmc/p4 $out/${tag}_pmc/p5 $out/${tag}_pmc/p6 $out/${tag}_pmc/p7 > /dev/null
-python3 $root/tools/summarize_pmc_by_name.py $out/${tag}_pmc_sweep_by_kernel.csv "rocprofv3 --kernel-trace --pmc <set> --output-format csv -- python3 bench.py --headline-only --steps 6 --warmup 1 (one pass per counter set): the dispatches of a sweep, per kernel; FETCH_SIZE / WRITE_SIZE in KiB as reported" sweep_grid_kernel,sweep_queue_kernel,cert_plan_kernel,sweep_kernel $out/${tag}_pmc/p1 $out/${tag}_pmc/p2 $out/${tag}_pmc/p3 $out/${tag}_pmc/p4 > /dev/null 2>&1
+python3 $root/tools/summarize_pmc_by_name.py $out/${tag}_pmc_sweep_by_kernel.csv "rocprofv3 --kernel-trace --pmc <set> --output-format csv -- python3 bench.py --full --headline-only --steps 6 --warmup 1 (one pass per counter set): the dispatches of a sweep, per kernel; FETCH_SIZE / WRITE_SIZE in KiB as reported" sweep_grid_kernel,sweep_queue_kernel,cert_plan_kernel,sweep_kernel $out/${tag}_pmc/p1 $out/${tag}_pmc/p2 $out/${tag}_pmc/p3 $out/${tag}_pmc/p4 > /dev/null 2>&1
 # the same command through the kd-tree walk (--search lane: round 3's kernel + certificate sweep): kernel stats and the
 # instruction / lane counters, for the before / after of the search
 HL="$H --search lane"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """README.md from tools/readme_template.md, the "Measured" table of DESIGN 4 and the numbered rows of profiles/README.md from the newest kept full report (profiles/rNN_bench_report.json -- what
-`python bench.py` wrote to bench_report.json on the GPU box), so that the README's numbers are the kept file's.
+`python bench.py --full` writes to bench_report.json on the GPU), so that the README's numbers are the kept file's.
     python tools/refresh_readme.py [report.json]"""
 import glob
 import json
