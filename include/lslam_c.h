@@ -721,10 +721,25 @@ void lslam_stereo_default_cam(lslam_stereo_cam *cam);
  * travel in the same 32-double all-reduce).  n = 0 removes the term. */
 int lslam_stereo_set(lslam_ctx *ctx, const float *landmarks_xyz, const float *obs, const float *inv_sigma2,
                      size_t n, const lslam_stereo_cam *cam);
+/* Removes the term, whichever form set it. */
 int lslam_stereo_clear(lslam_ctx *ctx);
 /* Parity tap: the stereo term alone at `pose`: sums32 = {21 upper-triangular A^T A, 6 A^T b,
- * rows, 0, 0, 0, observations used} (fp64 reduction of the per-block fp32 partials). */
+ * rows, 0, 0, 0, observations used} (fp64 reduction of the per-block fp32 partials).  A term of
+ * more than one set is refused: lslam_stereo_sums_batch. */
 int lslam_stereo_sums(lslam_ctx *ctx, const float pose[6], double sums32[32]);
+/* The joint system for a batch of resident scans (keyframe re-matching, loop candidates): K
+ * observation sets, one per resident scan, packed: set p is observations
+ * [offsets[p], offsets[p+1]) of landmarks_xyz[n][3] / obs[n][3] / inv_sigma2[n] (NULL: all 1),
+ * offsets[0] = 0, offsets[K] = n, non-decreasing.  One camera for all sets.  An empty set leaves
+ * its scan LiDAR-only.  n = 0 removes the term.  lslam_stereo_set is the case K = 1; setting one
+ * form replaces the other.  At run time K must equal the number of resident scans
+ * (lslam_scanmatch_run_batch; _run, _scan and _run_sharded take K = 1 only), otherwise the call
+ * returns LSLAM_ERR_INVALID and nothing changes.  Scan p of the batch gives, bit for bit, what it
+ * gives matched alone with set p through lslam_stereo_set. */
+int lslam_stereo_set_batch(lslam_ctx *ctx, int32_t n_sets, const float *landmarks_xyz, const float *obs,
+                           const float *inv_sigma2, const size_t *offsets, const lslam_stereo_cam *cam);
+/* Parity tap: each set's stereo term alone at its own pose -> sums32[K][32] (layout of lslam_stereo_sums). */
+int lslam_stereo_sums_batch(lslam_ctx *ctx, int32_t n_sets, const float *poses, double *sums32);
 
 int lslam_pg_create(int device, int32_t n_vertices, const double *poses7, int32_t n_edges,
                     const int32_t *ij, const double *meas7, const double *info36,

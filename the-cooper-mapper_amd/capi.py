@@ -159,6 +159,9 @@ SYMBOLS = {
     "lslam_stereo_set": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, C.c_size_t, C.POINTER(LslamStereoCam)]),
     "lslam_stereo_clear": (C.c_int, [C.c_void_p]),
     "lslam_stereo_sums": (C.c_int, [C.c_void_p, c_float_p, c_double_p]),
+    "lslam_stereo_set_batch": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_size_t),
+                                         C.POINTER(LslamStereoCam)]),
+    "lslam_stereo_sums_batch": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, c_double_p]),
     "lslam_scanmatch_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                        C.c_size_t, c_float_p, C.POINTER(LslamOpts), C.POINTER(LslamStats)]),
     "lslam_scanmatch_full": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,

@@ -237,11 +237,17 @@ struct lslam_ctx {
   DevBuf<float4> od_oc, od_os, od_q, od_sel;
   DevBuf<int32_t> od_ind;
   int od_iter_hint = 6;
-  // stereo term of the joint system (lslam_stereo_set)
+  // stereo term of the joint system (lslam_stereo_set_batch; lslam_stereo_set is its one-set case): one observation set per
+  // resident scan, each cut into whole blocks of its own
   DevBuf<float4> st_lm, st_obs;
-  DevBuf<float> st_partials;
-  DevBuf<ProbBlocks> st_noblocks;  // {0, 0}: a problem with no LiDAR blocks (lslam_stereo_sums)
-  int32_t n_stereo = 0;
+  DevBuf<float> st_partials;          // [n_st_blocks][NCOL]
+  DevBuf<StereoBlock> st_blocks;      // [n_st_blocks]
+  DevBuf<ProbBlocks> st_probs;        // [n_st_sets] block range of each set in st_blocks
+  std::vector<ProbBlocks> h_st_probs;
+  DevBuf<ProbBlocks> st_noblocks;     // [n_st_sets] {0, 0}: problems with no LiDAR blocks (lslam_stereo_sums_batch)
+  int32_t n_stereo = 0;               // observations of all sets (0: no term)
+  int32_t n_st_sets = 0;
+  int32_t n_st_blocks = 0;
   StereoCam st_cam{};
   uint64_t sweep_variants[SWEEP_N_VARIANTS] = {0};  // sweep launches per kernel instantiation (lslam_debug_sweep_launches)
   // cell grids over the whole-map trees (lslam_grid.hpp), built the first time the grid search is asked for on a map
@@ -1681,6 +1687,11 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
     set_err("batch size %d does not match the %d resident scans", n_scans, ctx->n_prob);
     return fail_all(LSLAM_ERR_INVALID);
   }
+  if (ctx->n_stereo > 0 && ctx->n_st_sets != n_scans) {
+    set_err("the stereo term holds %d observation set(s) and %d scan(s) are resident: one set per scan (lslam_stereo_set_batch)",
+            ctx->n_st_sets, n_scans);
+    return fail_all(LSLAM_ERR_INVALID);
+  }
   // ScanMatch.cpp:57-61 (variant C, FeatureMap::scanMatchScan, has no such guard)
   if (!ctx->cube_mode && (ctx->info.n_corner < 50 || ctx->info.n_surf < 100)) return fail_all(LSLAM_TOO_FEW_REF);
   const int max_it = o.max_iterations < 0 ? 0 : o.max_iterations;
@@ -1726,21 +1737,18 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
   so.min_rows = 50;        // ScanMatch.cpp:142
   so.too_few_continue = 0;
   so.nan_reset = 0;
-  // joint LiDAR + stereo system: the stereo blocks' records join the reduction of every iteration
+  // joint LiDAR + stereo system: each scan's stereo records join its reduction in every iteration (the set count was checked above)
   StereoArgs sta{};
   if (ctx->n_stereo > 0) {
-    if (n_scans != 1) {
-      set_err("the stereo term needs a single resident scan (%d resident)", n_scans);
-      return fail_all(LSLAM_ERR_INVALID);
-    }
     sta.landmarks = ctx->st_lm.p;
     sta.obs = ctx->st_obs.p;
-    sta.n = ctx->n_stereo;
+    sta.blocks = ctx->st_blocks.p;
+    sta.n_blocks = ctx->n_st_blocks;
     sta.cam = ctx->st_cam;
-    sta.state = ctx->d_state;
+    sta.states = ctx->d_state;
     sta.partials = ctx->st_partials.p;
     so.partials2 = ctx->st_partials.p;
-    so.n_blocks2 = stereo_blocks(ctx->n_stereo);
+    so.probs2 = ctx->st_probs.p;
   }
 
   auto sweep_events = [&](int launch, hipEvent_t *e0, hipEvent_t *e1) -> hipError_t {
@@ -2027,16 +2035,27 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
       soc.states = ctx->d_state + p0;
       soc.probs = ctx->probs.p + p0;
       soc.n_prob = p1 - p0;
+      StereoArgs stc = sta;  // the stereo blocks of this chunk's scans (their sets are consecutive)
+      if (so.probs2) {
+        soc.probs2 = so.probs2 + p0;
+        const int32_t sfb = ctx->h_st_probs[(size_t)p0].first_block;
+        stc.blocks = sta.blocks + sfb;
+        stc.partials = sta.partials + (size_t)sfb * NCOL;
+        stc.n_blocks = ctx->h_st_probs[(size_t)p1 - 1].first_block + ctx->h_st_probs[(size_t)p1 - 1].n_blocks - sfb;
+      }
       for (int b = 0; b < iters; ++b) {
         // the first sweep of a loop is bounded by the acceptance gate only, later ones also by the
         // neighbours the previous sweep of THIS loop found
         sc.prev_valid = (sc.bounded && done_iters[(size_t)c] > 0) ? 1 : 0;
-        hipEvent_t e0, e1;
-        HIP_TRY(sweep_events(n_launches, &e0, &e1));
         int variant = -1;
-        HIP_TRY(sweep_launch(ctx, sc, o.jtj_mode, e0, e1, &variant));
-        ++n_launches;
-        HIP_TRY(launch_stereo(sta, ctx->stream));
+        // (compacted: no LiDAR workgroup of a running scan is left -- only the stereo rows carry its loop -- nothing to sweep)
+        if (!(sc.active_blocks && sc.n_active <= 0)) {
+          hipEvent_t e0, e1;
+          HIP_TRY(sweep_events(n_launches, &e0, &e1));
+          HIP_TRY(sweep_launch(ctx, sc, o.jtj_mode, e0, e1, &variant));
+          ++n_launches;
+        }
+        HIP_TRY(launch_stereo(stc, ctx->stream));
         if (variant != SWEEP_VARIANT_DEEP_FUSED) HIP_TRY(launch_solve(soc, ctx->stream));
         ++done_iters[(size_t)c];
       }
@@ -2058,13 +2077,16 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
       // wait of ~30 us against sweeps of milliseconds): the next sweep is launched over THOSE, not over every workgroup of
       // every scan.  The states come back once, at the end.
       HIP_TRY(ctx->active_blocks.reserve((size_t)std::max(ctx->nb_total, 1)));
-      HIP_TRY(ctx->d_active_cnt.reserve((size_t)n_chunks));
-      if (ctx->h_active_cap < (size_t)n_chunks) {
+      // [n_chunks] workgroups left, then (stereo term) [n_chunks] whether a scan of the chunk still runs
+      const bool track_running = ctx->n_stereo > 0;
+      const size_t n_cnt = (size_t)n_chunks * (track_running ? 2 : 1);
+      HIP_TRY(ctx->d_active_cnt.reserve(n_cnt));
+      if (ctx->h_active_cap < n_cnt) {
         if (ctx->h_active) (void)hipHostFree(ctx->h_active);
         ctx->h_active = nullptr;
         ctx->h_active_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&ctx->h_active, sizeof(int32_t) * (size_t)n_chunks, hipHostMallocDefault));
-        ctx->h_active_cap = (size_t)n_chunks;
+        HIP_TRY(hipHostMalloc((void **)&ctx->h_active, sizeof(int32_t) * n_cnt, hipHostMallocDefault));
+        ctx->h_active_cap = n_cnt;
       }
       for (;;) {
         bool any = false;
@@ -2075,19 +2097,22 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
           if (rc) return rc;
           const int p0 = c * in_flight, p1 = std::min(n_scans, p0 + in_flight);
           const int32_t fb = ctx->h_probs[(size_t)p0].first_block;
-          HIP_TRY(launch_compact_active(ctx->d_state + p0, ctx->probs.p + p0, p1 - p0, fb, ctx->active_blocks.p + fb, ctx->d_active_cnt.p + c, ctx->stream));
+          HIP_TRY(launch_compact_active(ctx->d_state + p0, ctx->probs.p + p0, p1 - p0, fb, ctx->active_blocks.p + fb, ctx->d_active_cnt.p + c, ctx->stream,
+                                        track_running ? ctx->d_active_cnt.p + n_chunks + c : nullptr));
           any = true;
         }
         if (!any) break;
         launched = *std::max_element(done_iters.begin(), done_iters.end());
         HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->h_active, ctx->d_active_cnt.p, sizeof(int32_t) * (size_t)n_chunks, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->h_active, ctx->d_active_cnt.p, sizeof(int32_t) * n_cnt, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         bool all_done = true;
         for (int c = 0; c < n_chunks; ++c) {
           if (finished[(size_t)c]) continue;
           active_n[(size_t)c] = ctx->h_active[c];
-          if (active_n[(size_t)c] <= 0 || done_iters[(size_t)c] >= max_it) finished[(size_t)c] = 1;
+          // with the stereo term a running scan may have no LiDAR workgroup left to launch: the chunk is over when no scan runs
+          const bool over = track_running ? ctx->h_active[n_chunks + c] == 0 : active_n[(size_t)c] <= 0;
+          if (over || done_iters[(size_t)c] >= max_it) finished[(size_t)c] = 1;
           all_done = all_done && finished[(size_t)c];
         }
         if (all_done) break;
@@ -2173,7 +2198,7 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
         soc.reduce_only = 2;
         soc.ext_sums = nullptr;
         soc.partials2 = nullptr;  // LiDAR rows only
-        soc.n_blocks2 = 0;
+        soc.probs2 = nullptr;
         soc.sums_out = sharded ? xchg : nullptr;
         HIP_TRY(sweep_launch(ctx, sc, o.jtj_mode));
         HIP_TRY(launch_solve(soc, ctx->stream));
@@ -2300,13 +2325,29 @@ int lslam_stereo_clear(lslam_ctx *ctx) {
   int rc = check_ctx(ctx);
   if (rc) return rc;
   ctx->n_stereo = 0;
+  ctx->n_st_sets = 0;
+  ctx->n_st_blocks = 0;
   return LSLAM_OK;
 }
 
-int lslam_stereo_set(lslam_ctx *ctx, const float *landmarks_xyz, const float *obs, const float *inv_sigma2,
-                     size_t n, const lslam_stereo_cam *cam) {
+int lslam_stereo_set_batch(lslam_ctx *ctx, int32_t n_sets, const float *landmarks_xyz, const float *obs, const float *inv_sigma2,
+                           const size_t *offsets, const lslam_stereo_cam *cam) {
   int rc = check_ctx(ctx);
   if (rc) return rc;
+  if (n_sets <= 0 || !offsets) {
+    set_err("bad stereo arguments (at least one set and its offsets)");
+    return LSLAM_ERR_INVALID;
+  }
+  if (offsets[0] != 0) {
+    set_err("stereo offsets[0] must be 0");
+    return LSLAM_ERR_INVALID;
+  }
+  for (int32_t p = 0; p < n_sets; ++p)
+    if (offsets[p + 1] < offsets[p]) {
+      set_err("stereo offsets decrease at set %d", p);
+      return LSLAM_ERR_INVALID;
+    }
+  const size_t n = offsets[n_sets];
   if (n == 0) return lslam_stereo_clear(ctx);
   if (!landmarks_xyz || !obs || !cam || n >= (size_t)1 << 30) {
     set_err("bad stereo arguments");
@@ -2323,12 +2364,36 @@ int lslam_stereo_set(lslam_ctx *ctx, const float *landmarks_xyz, const float *ob
                         inv_sigma2 ? inv_sigma2[i] : 1.0f);
     ob[i] = make_float4(obs[3 * i], obs[3 * i + 1], obs[3 * i + 2], 0.0f);
   }
+  // every set in whole blocks of its own: block b of set p holds its observations [256 b, 256 b + 256)
+  std::vector<StereoBlock> blocks;
+  std::vector<ProbBlocks> probs((size_t)n_sets);
+  for (int32_t p = 0; p < n_sets; ++p) {
+    const size_t o0 = offsets[p], cnt = offsets[p + 1] - offsets[p];
+    probs[(size_t)p].first_block = (int32_t)blocks.size();
+    for (size_t k = 0; k < (size_t)stereo_blocks((int)cnt); ++k) {
+      StereoBlock b{};
+      b.prob = p;
+      b.first = (int32_t)(o0 + 256 * k);
+      b.count = (int32_t)std::min<size_t>(256, cnt - 256 * k);
+      blocks.push_back(b);
+    }
+    probs[(size_t)p].n_blocks = (int32_t)blocks.size() - probs[(size_t)p].first_block;
+  }
+  ctx->n_stereo = 0;  // (no term while the buffers change: a failed upload leaves none)
+  ctx->n_st_sets = 0;
+  ctx->n_st_blocks = 0;
   HIP_TRY(ctx->st_lm.reserve(n));
   HIP_TRY(ctx->st_obs.reserve(n));
-  HIP_TRY(ctx->st_partials.reserve((size_t)stereo_blocks((int)n) * NCOL));
+  HIP_TRY(ctx->st_partials.reserve(blocks.size() * NCOL));
+  HIP_TRY(ctx->st_blocks.reserve(blocks.size()));
+  HIP_TRY(ctx->st_probs.reserve((size_t)n_sets));
+  HIP_TRY(ctx->st_noblocks.reserve((size_t)n_sets));
   HIP_TRY(hipMemcpyAsync(ctx->st_lm.p, lm.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(ctx->st_obs.p, ob.data(), n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));  // lm, ob are locals
+  HIP_TRY(hipMemcpyAsync(ctx->st_blocks.p, blocks.data(), blocks.size() * sizeof(StereoBlock), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ctx->st_probs.p, probs.data(), probs.size() * sizeof(ProbBlocks), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->st_noblocks.p, 0, (size_t)n_sets * sizeof(ProbBlocks), ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));  // lm, ob, blocks, probs are locals
   StereoCam &c = ctx->st_cam;
   c.fx = cam->fx; c.fy = cam->fy; c.cx = cam->cx; c.cy = cam->cy; c.bf = cam->bf;
   std::memcpy(c.T_cl, cam->T_cl, sizeof(c.T_cl));
@@ -2337,43 +2402,75 @@ int lslam_stereo_set(lslam_ctx *ctx, const float *landmarks_xyz, const float *ob
   c.huber_mono = cam->huber_mono;
   c.gate_outliers = cam->gate_outliers;
   c.min_depth = cam->min_depth;
+  ctx->h_st_probs = std::move(probs);
+  ctx->n_st_blocks = (int32_t)blocks.size();
+  ctx->n_st_sets = n_sets;
   ctx->n_stereo = (int32_t)n;
   return LSLAM_OK;
 }
+
+int lslam_stereo_set(lslam_ctx *ctx, const float *landmarks_xyz, const float *obs, const float *inv_sigma2,
+                     size_t n, const lslam_stereo_cam *cam) {
+  const size_t offsets[2] = {0, n};
+  return lslam_stereo_set_batch(ctx, 1, landmarks_xyz, obs, inv_sigma2, offsets, cam);
+}
+
+namespace {
+// Each set's stereo term alone at its own pose: the stereo blocks, then the solve kernel's reduction over problems without
+// LiDAR blocks -- the order in which a scan's loop adds them.
+int stereo_sums_impl(lslam_ctx *ctx, int32_t n_sets, const float *poses, double *sums32) {
+  int rc = ensure_states(ctx, n_sets);
+  if (rc) return rc;
+  for (int32_t p = 0; p < n_sets; ++p) init_state(ctx->h_state[p], poses + 6 * p);
+  HIP_TRY(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(GNState) * (size_t)n_sets, hipMemcpyHostToDevice, ctx->stream));
+  StereoArgs sta{};
+  sta.landmarks = ctx->st_lm.p;
+  sta.obs = ctx->st_obs.p;
+  sta.blocks = ctx->st_blocks.p;
+  sta.n_blocks = ctx->n_st_blocks;
+  sta.cam = ctx->st_cam;
+  sta.states = ctx->d_state;
+  sta.partials = ctx->st_partials.p;
+  HIP_TRY(launch_stereo(sta, ctx->stream));
+  SolveArgs so{};
+  so.states = ctx->d_state;
+  so.partials = ctx->st_partials.p;  // unused: the problems have no LiDAR blocks
+  so.probs = ctx->st_noblocks.p;
+  so.n_prob = n_sets;
+  so.reduce_only = 1;
+  so.partials2 = ctx->st_partials.p;
+  so.probs2 = ctx->st_probs.p;
+  HIP_TRY(launch_solve(so, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState) * (size_t)n_sets, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  for (int32_t p = 0; p < n_sets; ++p)
+    for (int i = 0; i < NCOL; ++i) sums32[(size_t)p * NCOL + i] = ctx->h_state[p].sums[i];
+  return LSLAM_OK;
+}
+}  // namespace
 
 int lslam_stereo_sums(lslam_ctx *ctx, const float pose[6], double sums32[32]) {
   int rc = check_ctx(ctx);
   if (rc) return rc;
   if (!pose || !sums32) { set_err("null argument"); return LSLAM_ERR_INVALID; }
   if (ctx->n_stereo <= 0) { set_err("no stereo observations set"); return LSLAM_ERR_INVALID; }
-  rc = ensure_states(ctx, 1);
+  if (ctx->n_st_sets != 1) {
+    set_err("the stereo term holds %d observation sets: lslam_stereo_sums_batch", ctx->n_st_sets);
+    return LSLAM_ERR_INVALID;
+  }
+  return stereo_sums_impl(ctx, 1, pose, sums32);
+}
+
+int lslam_stereo_sums_batch(lslam_ctx *ctx, int32_t n_sets, const float *poses, double *sums32) {
+  int rc = check_ctx(ctx);
   if (rc) return rc;
-  init_state(*ctx->h_state, pose);
-  HIP_TRY(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx->st_noblocks.reserve(1));
-  const ProbBlocks none{0, 0};
-  HIP_TRY(hipMemcpyAsync(ctx->st_noblocks.p, &none, sizeof(none), hipMemcpyHostToDevice, ctx->stream));
-  StereoArgs sta{};
-  sta.landmarks = ctx->st_lm.p;
-  sta.obs = ctx->st_obs.p;
-  sta.n = ctx->n_stereo;
-  sta.cam = ctx->st_cam;
-  sta.state = ctx->d_state;
-  sta.partials = ctx->st_partials.p;
-  HIP_TRY(launch_stereo(sta, ctx->stream));
-  SolveArgs so{};
-  so.states = ctx->d_state;
-  so.partials = ctx->st_partials.p;  // unused: the problem has no LiDAR blocks
-  so.probs = ctx->st_noblocks.p;
-  so.n_prob = 1;
-  so.reduce_only = 1;
-  so.partials2 = ctx->st_partials.p;
-  so.n_blocks2 = stereo_blocks(ctx->n_stereo);
-  HIP_TRY(launch_solve(so, ctx->stream));
-  HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));  // `none` is a local too
-  for (int i = 0; i < NCOL; ++i) sums32[i] = ctx->h_state->sums[i];
-  return LSLAM_OK;
+  if (!poses || !sums32) { set_err("null argument"); return LSLAM_ERR_INVALID; }
+  if (ctx->n_stereo <= 0) { set_err("no stereo observations set"); return LSLAM_ERR_INVALID; }
+  if (n_sets != ctx->n_st_sets) {
+    set_err("%d poses for a stereo term of %d observation sets", n_sets, ctx->n_st_sets);
+    return LSLAM_ERR_INVALID;
+  }
+  return stereo_sums_impl(ctx, n_sets, poses, sums32);
 }
 
 int lslam_scanmatch_run_batch(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_opts *opts,
@@ -2412,6 +2509,10 @@ int lslam_scanmatch_run(lslam_ctx *ctx, float pose[6], const lslam_opts *opts, l
 int lslam_scanmatch_scan(lslam_ctx *ctx, const void *corner, size_t n_corner, const void *surf,
                          size_t n_surf, size_t stride_bytes, float pose[6],
                          const lslam_opts *opts, lslam_stats *stats) {
+  if (ctx && ctx->n_stereo > 0 && ctx->n_st_sets != 1) {  // refused before the resident scans change
+    set_err("the stereo term holds %d observation sets: lslam_scanmatch_scan matches one scan", ctx->n_st_sets);
+    return LSLAM_ERR_INVALID;
+  }
   int rc = lslam_scan_set(ctx, corner, n_corner, surf, n_surf, stride_bytes);
   if (rc) return rc;
   return lslam_scanmatch_run(ctx, pose, opts, stats);

@@ -213,8 +213,10 @@ struct SolveArgs {
   int32_t reduce_only;  // 1: only reduce partials into state->sums (tap; first half of a sharded iteration)
                         // 2: the same for the scans whose loop converged (the _fineScore re-sweep)
   const double *ext_sums;  // non-null: [n_prob][32] sums already reduced (and summed over ranks); skip the reduction
-  const float *partials2;  // non-null (single scan only): block records of the stereo term, added after the LiDAR ones
-  int32_t n_blocks2;
+  // non-null: block records of the stereo term (StereoArgs::partials of the whole term), scan p's records in
+  // [probs2[p].first_block, + n_blocks), added after its LiDAR ones
+  const float *partials2;
+  const ProbBlocks *probs2;  // [n_prob], like `probs`
   int32_t max_iterations;
   float delta_r_abort, delta_t_abort;
   float eig_thresh;  // 100 (ScanMatch.cpp:223); 10 in LaserOdometry.cpp:596
@@ -244,15 +246,24 @@ struct StereoCam {
   int32_t gate_outliers;
   float min_depth;
 };
-struct StereoArgs {
-  const float4 *landmarks;  // {X, Y, Z, inv_sigma2}, map frame
-  const float4 *obs;        // {uL, v, uR (< 0: monocular), -}
-  int32_t n;
-  StereoCam cam;
-  const GNState *state;
-  float *partials;          // [stereo_blocks(n)][NCOL]
+// One workgroup of stereo_kernel: up to 256 observations of ONE scan's set (each set is cut into whole blocks of its own, so
+// the lane of an observation and the block records are those of the set matched alone).
+struct StereoBlock {
+  int32_t prob;   // scan (an index into StereoArgs::states)
+  int32_t first;  // first observation of the block in landmarks / obs
+  int32_t count;  // observations in the block (<= 256)
+  int32_t pad;
 };
-int stereo_blocks(int n);
+struct StereoArgs {
+  const float4 *landmarks;     // {X, Y, Z, inv_sigma2}, map frame, all sets packed
+  const float4 *obs;           // {uL, v, uR (< 0: monocular), -}
+  const StereoBlock *blocks;   // [n_blocks] the blocks of this launch
+  int32_t n_blocks;
+  StereoCam cam;
+  const GNState *states;       // indexed by StereoBlock::prob; a block whose scan is done leaves at once
+  float *partials;             // [n_blocks][NCOL]: record b belongs to blocks[b]
+};
+int stereo_blocks(int n);  // blocks of a set of n observations
 hipError_t launch_stereo(const StereoArgs &a, hipStream_t s);
 
 // Variant B (LaserOdometry::scanMatch): one launch = one iteration over sharp + flat points.
@@ -331,7 +342,9 @@ struct GridDev {
 hipError_t grid_bbox2(const float4 *const pts[2], const int n[2], uint32_t *d_box12, float lo[2][3], float hi[2][3], hipStream_t s);
 hipError_t grid_unsort(const CellGrid &G, float4 *out, hipStream_t s);
 hipError_t launch_compact_active(const GNState *states, const ProbBlocks *probs, int n_prob, int32_t block_base, int32_t *active_blocks,
-                                 int32_t *count_out, hipStream_t s);
+                                 int32_t *count_out, hipStream_t s, int32_t *running_out = nullptr);
+// (running_out, or null: 1 when a scan of the chunk is still running, 0 otherwise -- with the stereo term a running scan may have
+// no LiDAR workgroups at all, so count_out = 0 does not mean that the chunk's loops are over)
 hipError_t launch_sweep_plan(const SweepArgs &a, hipStream_t s, const CertPlan &plan, int level, bool with_prefix);
 hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, int level = 0, bool planned = false);
 hipError_t launch_sweep_refill(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, const CertPlan &plan);

@@ -691,9 +691,11 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(SolveArgs a) {
     __syncthreads();
   } else {
     reduce_partials<SOLVE_THREADS, false>(partials, nb, red);
-    if (a.partials2) {  // stereo blocks of the joint system: same pattern, after the LiDAR blocks
+    if (a.partials2) {  // stereo blocks of the joint system: this scan's, same pattern, after its LiDAR blocks
+      const ProbBlocks sb = a.probs2[blockIdx.x];
+      const float *p2 = a.partials2 + (size_t)sb.first_block * NCOL;
       double s = red[grp][col];  // (this thread's own group)
-      for (int b = grp; b < a.n_blocks2; b += SOLVE_GROUPS) s += (double)a.partials2[(size_t)b * NCOL + col];
+      for (int b = grp; b < sb.n_blocks; b += SOLVE_GROUPS) s += (double)p2[(size_t)b * NCOL + col];
       red[grp][col] = s;
     }
     __syncthreads();
@@ -1501,14 +1503,21 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 
 // threads wrote their own scans' runs one entry after the other took 45 us per iteration for the bench's 430 000 entries.)
 constexpr int COMPACT_WGS = 64;
 __global__ __launch_bounds__(1024) void compact_active_kernel(const GNState *states, const ProbBlocks *probs, int n_prob, int32_t block_base,
-                                                              int32_t *active_blocks, int32_t *count_out) {
+                                                              int32_t *active_blocks, int32_t *count_out, int32_t *running_out) {
   __shared__ int incl[1024];
   __shared__ int wsum[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int per = (n_prob + 1023) / 1024;
   const int p0 = min(n_prob, tid * per), p1 = min(n_prob, p0 + per);
-  int sum = 0;
-  for (int p = p0; p < p1; ++p) sum += states[p].done ? 0 : probs[p].n_blocks;
+  int sum = 0, running = 0;
+  for (int p = p0; p < p1; ++p) {
+    sum += states[p].done ? 0 : probs[p].n_blocks;
+    running |= states[p].done ? 0 : 1;
+  }
+  if (running_out) {  // (uniform: a kernel argument)
+    running = __syncthreads_or(running);
+    if (blockIdx.x == 0 && tid == 0) *running_out = running ? 1 : 0;
+  }
   int run = sum;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
@@ -1546,8 +1555,9 @@ __global__ __launch_bounds__(1024) void compact_active_kernel(const GNState *sta
   if (blockIdx.x == 0 && tid == 0) *count_out = total;
 }
 hipError_t launch_compact_active(const GNState *states, const ProbBlocks *probs, int n_prob, int32_t block_base, int32_t *active_blocks,
-                                 int32_t *count_out, hipStream_t s) {
-  hipLaunchKernelGGL(compact_active_kernel, dim3(COMPACT_WGS), dim3(1024), 0, s, states, probs, n_prob, block_base, active_blocks, count_out);
+                                 int32_t *count_out, hipStream_t s, int32_t *running_out) {
+  hipLaunchKernelGGL(compact_active_kernel, dim3(COMPACT_WGS), dim3(1024), 0, s, states, probs, n_prob, block_base, active_blocks, count_out,
+                     running_out);
   return hipGetLastError();
 }
 

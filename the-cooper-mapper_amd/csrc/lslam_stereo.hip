@@ -12,6 +12,11 @@
 // record in the layout of the LiDAR sweep (lslam_internal.hpp COL_*), so that solve_kernel adds
 // both kinds of block into the same 6x6 system in a fixed order.
 //
+// A launch covers the observation sets of a chunk of resident scans (one set per scan, the joint batch): every set is cut into
+// blocks of its own (StereoBlock: no block straddles two sets), a block reads its scan's state and leaves when that scan's loop
+// is done, and solve_kernel adds scan p's records after its LiDAR ones.  Lane <-> observation and the records are those of the
+// set matched alone, so a batch and the single runs of its scans give the same bits.
+//
 // Bytes: 32 per observation ({X, inv_sigma2}, {uL, v, uR, -}) read once, coalesced; with 1e3-1e5
 // observations per frame the kernel is launch-latency bound (a few microseconds).
 #include <hip/hip_runtime.h>
@@ -32,19 +37,20 @@ __device__ __forceinline__ float st_wave_sum(float v) {
 }
 
 __global__ __launch_bounds__(ST_BLOCK) void stereo_kernel(StereoArgs a) {
-  const GNState *st = a.state;
-  if (st->done) return;
+  const StereoBlock sbk = a.blocks[blockIdx.x];
+  const GNState *st = a.states + sbk.prob;
+  if (st->done) return;  // this scan's loop already ended
   __shared__ float jr[ST_WAVES][3][8][64];  // [wave][component][column][lane]
   __shared__ float red[ST_WAVES][NCOL];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = blockIdx.x * ST_BLOCK + tid;
+  const int i = sbk.first + tid;  // lane tid <-> observation tid of the block, as in a set matched alone
   float rows[3][7];
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int c = 0; c < 7; ++c) rows[r][c] = 0.0f;
   float n_rows = 0.0f, used = 0.0f;
-  if (i < a.n) {
+  if (tid < sbk.count) {
     const float4 L = a.landmarks[i];  // X, Y, Z, inv_sigma2
     const float4 ob = a.obs[i];       // uL, v, uR, -
     const StereoCam &c = a.cam;
@@ -164,8 +170,8 @@ __global__ __launch_bounds__(ST_BLOCK) void stereo_kernel(StereoArgs a) {
 int stereo_blocks(int n) { return (n + ST_BLOCK - 1) / ST_BLOCK; }
 
 hipError_t launch_stereo(const StereoArgs &a, hipStream_t s) {
-  if (a.n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(stereo_kernel, dim3(stereo_blocks(a.n)), dim3(ST_BLOCK), 0, s, a);
+  if (a.n_blocks <= 0) return hipSuccess;
+  hipLaunchKernelGGL(stereo_kernel, dim3(a.n_blocks), dim3(ST_BLOCK), 0, s, a);
   return hipGetLastError();
 }
 

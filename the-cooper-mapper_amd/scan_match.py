@@ -308,6 +308,31 @@ class Context:
         self._check(self.lib.lslam_stereo_set(self.h, _fp(lm), _fp(ob), _fp(w) if w is not None else None,
                                               len(lm), C.byref(cam)))
 
+    def stereo_set_batch(self, sets, cam=None):
+        """lslam_stereo_set_batch: one observation set per resident scan of a batch, `sets` a list of
+        (landmarks (n_p,3), obs (n_p,3), inv_sigma2 (n_p,) or None).  run_batch then solves the joint
+        system of every scan with its own set (an empty set: LiDAR only).  No observations at all
+        removes the term; either form of the term replaces the other."""
+        if not sets:
+            raise ValueError("at least one observation set")
+        lms, obs, ws, offsets = [], [], [], [0]
+        for lm, ob, w in sets:
+            lm = np.asarray(lm, np.float32).reshape(-1, 3)
+            ob = np.asarray(ob, np.float32).reshape(-1, 3)
+            if len(lm) != len(ob):
+                raise ValueError("landmarks and observations differ in length")
+            lms.append(lm)
+            obs.append(ob)
+            ws.append(np.ones(len(lm), np.float32) if w is None else np.asarray(w, np.float32).reshape(len(lm)))
+            offsets.append(offsets[-1] + len(lm))
+        lm = np.ascontiguousarray(np.concatenate(lms), np.float32)
+        ob = np.ascontiguousarray(np.concatenate(obs), np.float32)
+        w = np.ascontiguousarray(np.concatenate(ws), np.float32)
+        off = np.ascontiguousarray(offsets, np.uintp)
+        cam = cam if cam is not None else self.default_stereo_cam()
+        self._check(self.lib.lslam_stereo_set_batch(self.h, len(sets), _fp(lm), _fp(ob), _fp(w),
+                                                    off.ctypes.data_as(C.POINTER(C.c_size_t)), C.byref(cam)))
+
     def stereo_clear(self):
         self._check(self.lib.lslam_stereo_clear(self.h))
 
@@ -317,6 +342,14 @@ class Context:
         p = np.array(pose, dtype=np.float32).reshape(6)
         out = np.zeros(32)
         self._check(self.lib.lslam_stereo_sums(self.h, _fp(p), out.ctypes.data_as(c_double_p)))
+        return out
+
+    def stereo_sums_batch(self, poses):
+        """Parity tap: each set's stereo term alone at its own pose -> (K, 32) sums."""
+        from .capi import c_double_p
+        p = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 6))
+        out = np.zeros((len(p), 32))
+        self._check(self.lib.lslam_stereo_sums_batch(self.h, len(p), _fp(p), out.ctypes.data_as(c_double_p)))
         return out
 
     def scanmatch_scan(self, corner, surf, pose, opts=None):
