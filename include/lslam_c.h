@@ -205,7 +205,8 @@ void lslam_default_opts(lslam_opts *opts);
 /* 5 (round 5): no struct changed; new entry points (lslam_debug_grid_stats, lslam_debug_knn5_wide, lslam_debug_sort_pairs), new bits (LSLAM_SWEEP_FIRST /
  * _CARRIED, LSLAM_AB_FIT_CACHE, LSLAM_AB_WIDE_NF_MARGIN) -- a program built against this header needs a library that has them. */
 /* 6 (round 6): no struct changed; new entry points (lslam_fset_*, lslam_extract_features_dev, lslam_odom_*, lslam_map_epoch). */
-#define LSLAM_ABI_VERSION 6
+/* 7: no struct changed; new entry points (lslam_lmap_*: the sliding-window local map). */
+#define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
 size_t lslam_sizeof_stats(void);
@@ -467,6 +468,58 @@ int lslam_fmap_load(lslam_fmap *fm, const char *directory);
 /* introspection: grid origin, _cubeValidInd, points held per type; any output may be NULL */
 int lslam_fmap_info(lslam_fmap *fm, int32_t origin[3], int32_t *n_valid, int32_t *valid_out, size_t cap,
                     size_t *n_corner_total, size_t *n_surf_total);
+/* ---- sliding-window local map (io_module/LocalFeatureMap.h, the container of odometry/LaserMappingLocal.cpp) ----------------
+ * The frames of the last `queue distance` metres of path, resident in HBM: addDataFrame (FrameUpdater's path length, push,
+ * clean() with its erase of n + 1 frames when n have fallen behind) and getSurroundFeature (the frames' clouds concatenated in
+ * queue order, pcl::VoxelGrid with leaf 0.2 over the corners and 0.4 over the surfaces), whose result becomes the ctx's map
+ * without leaving the device.  Point layouts as for lslam_fmap.  One in-flight call per ctx.
+ * THE ONE DIFFERENCE from the reference: its queue grows without bound (a sensor that stands still never advances the path
+ * length, so nothing is erased); device memory cannot.  The container is created with limits, and an add whose result would
+ * exceed one is refused with LSLAM_ERR_INVALID (the message says which) and changes nothing.  The limits apply to the window
+ * as it is after the add's clean(). */
+typedef struct lslam_lmap lslam_lmap;
+/* How the filtered surround is produced (same bits either way; 0 = the default, which is the measured winner: DESIGN). */
+#define LSLAM_LMAP_REFILTER 1      /* gather the window and sort + filter all of it, every sweep */
+#define LSLAM_LMAP_KEY_ORDERED 2   /* keep the window in voxel-key order: sort the new points only, merge them in */
+#define LSLAM_LMAP_ALWAYS_RESORT 4 /* key-ordered, but the ordered array is rebuilt from the ring every sweep (its fall-back, for tests) */
+/* max_points_per_type: 0 = 2^20 (30 m of path at 0.1 m per sweep: 300 VLP-16 frames of ~1000 corner / ~2500 surface points
+ * after the scan filter), at most 2^24; max_frames: 0 = 4096.  The memory is taken here: 112 bytes per point and type (the key-ordered
+ * filter's sort scratch, up to ~36 bytes per live point, grows with the window); all of it is returned by lslam_lmap_destroy. */
+int lslam_lmap_create(lslam_ctx *ctx, size_t max_points_per_type, int32_t max_frames, int32_t flags, lslam_lmap **out);
+void lslam_lmap_destroy(lslam_lmap *lm);
+/* queue_distance_threshold (LocalFeatureMap.h; default 30.0 m); must be positive. */
+int lslam_lmap_setup_queue_distance(lslam_lmap *lm, double metres);
+/* The leaves of the two surround filters.  The reference fixes them in its constructor (0.2 / 0.4: the defaults) and has no
+ * setter; this one is refused once a frame has been added (the key-ordered window is sorted by them) until lslam_lmap_clear. */
+int lslam_lmap_setup_filter_size(lslam_lmap *lm, float corner, float surf);
+/* featureMapUpdate + addDataFrame (LaserMappingLocal.cpp:68-83, LocalFeatureMap.h:62-82): the clouds are transformed by the
+ * row-major 4x4 T_map (p' = R p + t in fp32, intensity kept), FrameUpdater::update(T_map cast to double) advances the path
+ * length, the frame is pushed and clean() runs.  Both clouds go up behind one wait. */
+int lslam_lmap_add_data_frame(lslam_lmap *lm, const void *corner, size_t n_corner, const void *surf, size_t n_surf,
+                              size_t stride_bytes, const float T_map[16]);
+/* The same for clouds that are in the ctx's device memory already, packed {x, y, z, intensity} (16 bytes per point). */
+int lslam_lmap_add_data_frame_device(lslam_lmap *lm, const void *d_corner, size_t n_corner, const void *d_surf, size_t n_surf,
+                                     const float T_map[16]);
+/* getSurroundFeature (LocalFeatureMap.h:84-99) + ScanMatch's map set: the filtered window becomes the ctx's map (cell grids
+ * only under lslam_map_defer_trees); one wait for both types.  An empty window gives the empty map.  -> the two clouds' sizes */
+int lslam_lmap_surround_to_map_counts(lslam_lmap *lm, size_t *n_corner, size_t *n_surf);
+/* getSurroundFeature to the host: bit for bit lslam_voxel_grid over the concatenation of the window.  A null buffer: its
+ * count only. */
+int lslam_lmap_get_surround(lslam_lmap *lm, float *corner_xyzi, size_t cap_corner, size_t *n_corner, float *surf_xyzi,
+                            size_t cap_surf, size_t *n_surf);
+/* frames in the queue, FrameUpdater's accum_distance, points held per type, frames erased so far; any output may be NULL */
+int lslam_lmap_info(lslam_lmap *lm, int32_t *n_frames, double *accum_distance, size_t live_points[2], int64_t *frames_evicted);
+/* Debug tap: the queue as it is, oldest frame first -- per frame its accum_distance and its {corner, surf} point counts
+ * (counts[2 k], counts[2 k + 1]), and the frames' transformed points back to back per type.  Any output may be NULL. */
+int lslam_lmap_get_frames(lslam_lmap *lm, int32_t cap_frames, int32_t *n_frames, double *accum, int32_t *counts,
+                          float *corner_xyzi, size_t cap_corner, float *surf_xyzi, size_t cap_surf);
+/* How the surrounds were produced so far, per type and sweep: new points merged into the ordered array / ordered array sorted
+ * as a whole / window gathered and re-filtered. */
+int lslam_lmap_stats(lslam_lmap *lm, int64_t *merged, int64_t *resorted, int64_t *refiltered);
+/* Back to the state after create: no frames, path length 0, FrameUpdater's first-frame rule armed (limits, leaves and queue
+ * distance stay). */
+int lslam_lmap_clear(lslam_lmap *lm);
+
 /* pcl::VoxelGrid<PointXYZI>::filter with a cubic leaf on one cloud (LaserMatcher.cpp:289-301,
  * ScanMatch.cpp:362-398 scanMatchLocal): one centroid {x,y,z,intensity} per occupied voxel, in
  * ascending voxel index.  Points of a voxel are summed in input order (PCL: unspecified). */

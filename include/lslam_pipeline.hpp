@@ -8,6 +8,8 @@
 //                                        (odometry/LaserMatcher.cpp:289-354: prepareFeatureFrame,
 //                                        prepareFeatureSurround, optimizeTransform, transformMerge /
 //                                        transformUpdate, featureMapUpdate)
+//   lidar_slam::LaserMappingLocal::process  odometry/LaserMappingLocal.cpp:39-83: the same matcher over the sliding window of
+//                                        recent frames, io_module/LocalFeatureMap.h (lidar_slam::LocalFeatureMap below)
 //
 // ROS plumbing (topics, time-stamp matching, tf, frame skipping) is the host program's.  Clouds are any
 // type with `.points` (std::vector-like) of points with float x, y, z and `intensity` (= ring + relTime);
@@ -132,23 +134,88 @@ private:
   std::string _err;
 };
 
-// LaserMapping (BASELINE configs[1]): per sweep transformMerge (odometry prior), VoxelGrid of the frame's feature
-// clouds, FeatureMap::update + surround -> kd-trees (device), scanMatchScan with thresholds 0.1 / 0.1 and the
-// score gate off (its return value is ignored, LaserMatcher.cpp:327-331), transformUpdate, addFeatureCloud.
-class LaserMapping {
+namespace detail {
+// LaserMatcher (LaserMatcher.cpp:80-116, 289-347): the per-sweep steps the mapping nodes share -- transformMerge (odometry
+// prior), VoxelGrid of the frame's feature clouds, scanMatchScan with thresholds 0.1 / 0.1 and the score gate off (its return
+// value is ignored, :327-331), transformUpdate.  A node puts its map container's two steps between them.
+class LaserMatcherSteps {
 public:
-  // LaserMatcher.cpp:80-116 defaults (filter 1.0 / 1.0, map filters 1.0 / 1.0 / 2.0, 121 x 121 x 11 cubes)
-  explicit LaserMapping(lslam_ctx *ctx, int cubeX = 121, int cubeY = 121, int cubeZ = 11, float filterCorner = 1.0f,
-                        float filterSurf = 1.0f, float mapFilterCorner = 1.0f, float mapFilterSurf = 1.0f, float mapFilter = 2.0f)
-      : _ctx(ctx), _fm(nullptr), _filterCorner(filterCorner), _filterSurf(filterSurf) {
+  const float *lidarMapped() const { return _lidarMappedNew; }
+  const lslam_stats &lastStats() const { return _last; }
+  const std::string &lastError() const { return _err; }
+
+protected:
+  LaserMatcherSteps(lslam_ctx *ctx, float filterCorner, float filterSurf) : _ctx(ctx), _filterCorner(filterCorner), _filterSurf(filterSurf) {
     lslam_default_opts(&_opts);
     _opts.delta_t_abort = 0.1f;  // _scan_match.setConvergeThreshold(0.1, 0.1), LaserMatcher.cpp:94
     _opts.delta_r_abort = 0.1f;
     _opts.use_score = 0;         // setUseCore(false), :95
-    detail::identity4(_lidarOdomLast);
-    detail::identity4(_lidarMappedLast);
-    detail::identity4(_lidarMappedNew);
+    identity4(_lidarOdomLast);
+    identity4(_lidarMappedLast);
+    identity4(_lidarMappedNew);
     std::memset(&_last, 0, sizeof(_last));
+  }
+  // transformMerge, :333-340, and prepareFeatureFrame, :289-301
+  bool mergeAndPrepareFrame(const std::vector<float> &cornerLast, const std::vector<float> &surfLast, const float lidarOdomNew[16]) {
+    lslam_transform_associate(_lidarOdomLast, lidarOdomNew, _lidarMappedLast, _lidarMappedNew);
+    if (_filterCorner == _filterSurf) {  // the reference's defaults: both clouds in one pass (lslam_voxel_grid2: same bits)
+      _cornerDS.resize(cornerLast.size() + 4);
+      _surfDS.resize(surfLast.size() + 4);
+      size_t nc2 = 0, ns2 = 0;
+      if (lslam_voxel_grid2(_ctx, cornerLast.data(), cornerLast.size() / 4, surfLast.data(), surfLast.size() / 4, 16, _filterCorner,
+                            _cornerDS.data(), cornerLast.size() / 4, &nc2, _surfDS.data(), surfLast.size() / 4, &ns2) < 0)
+        return fail();
+      _cornerDS.resize(4 * nc2);
+      _surfDS.resize(4 * ns2);
+    } else if (!downsize(cornerLast, _filterCorner, _cornerDS) || !downsize(surfLast, _filterSurf, _surfDS)) {
+      return fail();
+    }
+    return true;
+  }
+  // optimizeTransform, :327-331, against the context's map (nc / ns: the sizes of the surround that became it), and
+  // transformUpdate, :342-347
+  bool optimizeAndUpdate(size_t nc, size_t ns, const float lidarOdomNew[16]) {
+    if (nc || ns) {
+      float pose[6];
+      lslam_isometry_to_pose(_lidarMappedNew, pose);
+      const int st = lslam_scanmatch_scan(_ctx, _cornerDS.data(), _cornerDS.size() / 4, _surfDS.data(), _surfDS.size() / 4, 16, pose,
+                                          &_opts, &_last);
+      if (st < 0) return fail();
+      if (st != LSLAM_TOO_FEW_REF) lslam_pose_to_isometry(pose, _lidarMappedNew);  // ScanMatch.cpp:57-61 leaves the pose untouched
+    }
+    std::memcpy(_lidarMappedLast, _lidarMappedNew, sizeof(_lidarMappedNew));
+    std::memcpy(_lidarOdomLast, lidarOdomNew, sizeof(_lidarOdomLast));
+    return true;
+  }
+  bool downsize(const std::vector<float> &in, float leaf, std::vector<float> &out) {
+    out.resize(in.size() + 4);
+    size_t n = 0;
+    const int st = lslam_voxel_grid(_ctx, in.data(), in.size() / 4, 16, leaf, out.data(), in.size() / 4, &n);
+    out.resize(4 * n);
+    return st >= 0;
+  }
+  bool fail() {
+    _err = lslam_last_error();
+    return false;
+  }
+  lslam_ctx *_ctx;
+  float _filterCorner, _filterSurf;
+  lslam_opts _opts;
+  float _lidarOdomLast[16], _lidarMappedLast[16], _lidarMappedNew[16];
+  std::vector<float> _cornerDS, _surfDS;
+  lslam_stats _last;
+  std::string _err;
+};
+}  // namespace detail
+
+// LaserMapping (BASELINE configs[1]): LaserMatcher's steps over the cube grid -- FeatureMap::update + surround -> the context's
+// map (device) before the match, addFeatureCloud after it.
+class LaserMapping : public detail::LaserMatcherSteps {
+public:
+  // LaserMatcher.cpp:80-116 defaults (filter 1.0 / 1.0, map filters 1.0 / 1.0 / 2.0, 121 x 121 x 11 cubes)
+  explicit LaserMapping(lslam_ctx *ctx, int cubeX = 121, int cubeY = 121, int cubeZ = 11, float filterCorner = 1.0f,
+                        float filterSurf = 1.0f, float mapFilterCorner = 1.0f, float mapFilterSurf = 1.0f, float mapFilter = 2.0f)
+      : detail::LaserMatcherSteps(ctx, filterCorner, filterSurf), _fm(nullptr) {
     if (lslam_fmap_create(ctx, cubeX, cubeY, cubeZ, &_fm) != LSLAM_OK) {
       _fm = nullptr;
       _err = lslam_last_error();
@@ -167,37 +234,13 @@ public:
   // lidarOdomNew: its _Tsum (row-major 4x4).  Returns false on a backend error; lidarMapped() is the sweep's pose in the map.
   bool process(const std::vector<float> &cornerLast, const std::vector<float> &surfLast, const float lidarOdomNew[16]) {
     if (!_fm) return false;
-    // transformMerge, :333-340
-    lslam_transform_associate(_lidarOdomLast, lidarOdomNew, _lidarMappedLast, _lidarMappedNew);
-    // prepareFeatureFrame, :289-301
-    if (_filterCorner == _filterSurf) {  // the reference's defaults: both clouds in one pass (lslam_voxel_grid2: same bits)
-      _cornerDS.resize(cornerLast.size() + 4);
-      _surfDS.resize(surfLast.size() + 4);
-      size_t nc2 = 0, ns2 = 0;
-      if (lslam_voxel_grid2(_ctx, cornerLast.data(), cornerLast.size() / 4, surfLast.data(), surfLast.size() / 4, 16, _filterCorner,
-                            _cornerDS.data(), cornerLast.size() / 4, &nc2, _surfDS.data(), surfLast.size() / 4, &ns2) < 0)
-        return fail();
-      _cornerDS.resize(4 * nc2);
-      _surfDS.resize(4 * ns2);
-    } else if (!downsize(cornerLast, _filterCorner, _cornerDS) || !downsize(surfLast, _filterSurf, _surfDS)) {
-      return fail();
-    }
+    if (!mergeAndPrepareFrame(cornerLast, surfLast, lidarOdomNew)) return false;
     // prepareFeatureSurround, :303-325
     const float pos[3] = {_lidarMappedNew[3], _lidarMappedNew[7], _lidarMappedNew[11]};
     if (lslam_fmap_update(_fm, pos) < 0) return fail();
     size_t nc = 0, ns = 0;
     if (lslam_fmap_surround_to_map_counts(_fm, &nc, &ns) < 0) return fail();  // the surround becomes the context's map
-    if (nc || ns) {  // optimizeTransform, :327-331
-      float pose[6];
-      lslam_isometry_to_pose(_lidarMappedNew, pose);
-      const int st = lslam_scanmatch_scan(_ctx, _cornerDS.data(), _cornerDS.size() / 4, _surfDS.data(), _surfDS.size() / 4, 16, pose,
-                                          &_opts, &_last);
-      if (st < 0) return fail();
-      if (st != LSLAM_TOO_FEW_REF) lslam_pose_to_isometry(pose, _lidarMappedNew);  // ScanMatch.cpp:57-61 leaves the pose untouched
-    }
-    // transformUpdate, :342-347
-    std::memcpy(_lidarMappedLast, _lidarMappedNew, sizeof(_lidarMappedNew));
-    std::memcpy(_lidarOdomLast, lidarOdomNew, sizeof(_lidarOdomLast));
+    if (!optimizeAndUpdate(nc, ns, lidarOdomNew)) return false;
     // featureMapUpdate, :349-354.  -DLSLAM_MAPPING_DEFER_ADD: enqueued, not waited for (lslam_fmap_add_feature_cloud_begin) -- the
     // map's rebuild then runs while the node takes up its next sweep and the next call on the map waits and commits first.  It pays
     // where the host idles between two sweeps (the Python mirror: 0.91 -> 0.82 ms per frame); with three nodes on three threads
@@ -212,31 +255,93 @@ public:
 #endif
     return true;
   }
-  const float *lidarMapped() const { return _lidarMappedNew; }
-  const lslam_stats &lastStats() const { return _last; }
-  const std::string &lastError() const { return _err; }
   lslam_fmap *featureMap() { return _fm; }
 
 private:
-  bool downsize(const std::vector<float> &in, float leaf, std::vector<float> &out) {
-    out.resize(in.size() + 4);
-    size_t n = 0;
-    const int st = lslam_voxel_grid(_ctx, in.data(), in.size() / 4, 16, leaf, out.data(), in.size() / 4, &n);
-    out.resize(4 * n);
-    return st >= 0;
+  lslam_fmap *_fm;
+};
+
+// LocalFeatureMap<PointT> (io_module/LocalFeatureMap.h) over lslam_lmap_*: the frames of the last `queue distance` metres of
+// path in HBM.  Clouds are packed {x, y, z, intensity} floats; tf is a row-major 4x4.
+class LocalFeatureMap {
+public:
+  explicit LocalFeatureMap(lslam_ctx *ctx, size_t maxPointsPerType = 0, int maxFrames = 0, int flags = 0) : _lm(nullptr) {
+    if (lslam_lmap_create(ctx, maxPointsPerType, maxFrames, flags, &_lm) != LSLAM_OK) {
+      _lm = nullptr;
+      _err = lslam_last_error();
+    }
   }
-  bool fail() {
-    _err = lslam_last_error();
+  ~LocalFeatureMap() { lslam_lmap_destroy(_lm); }
+  LocalFeatureMap(const LocalFeatureMap &) = delete;
+  LocalFeatureMap &operator=(const LocalFeatureMap &) = delete;
+  bool valid() const { return _lm != nullptr; }
+  bool setupQueueDistance(double metres) { return check(lslam_lmap_setup_queue_distance(_lm, metres)); }
+  // (not in the reference, whose leaves are fixed at 0.2 / 0.4; refused once a frame has been added)
+  bool setupFilterSize(float corner, float surf) { return check(lslam_lmap_setup_filter_size(_lm, corner, surf)); }
+  // LocalFeatureMap.h:62-69 behind LaserMappingLocal.cpp:68-83: the clouds are transformed by tf, pushed; clean() runs
+  bool addDataFrame(const std::vector<float> &cornerDS, const std::vector<float> &surfDS, const float tf[16]) {
+    return check(lslam_lmap_add_data_frame(_lm, cornerDS.data(), cornerDS.size() / 4, surfDS.data(), surfDS.size() / 4, 16, tf));
+  }
+  // :84-99, to the host
+  bool getSurroundFeature(std::vector<float> &surroundCorner, std::vector<float> &surroundSurf) {
+    size_t nc = 0, ns = 0;
+    if (!check(lslam_lmap_get_surround(_lm, nullptr, 0, &nc, nullptr, 0, &ns))) return false;
+    surroundCorner.resize(4 * nc + 4);
+    surroundSurf.resize(4 * ns + 4);
+    if (!check(lslam_lmap_get_surround(_lm, surroundCorner.data(), nc, &nc, surroundSurf.data(), ns, &ns))) return false;
+    surroundCorner.resize(4 * nc);
+    surroundSurf.resize(4 * ns);
+    return true;
+  }
+  // ... or as the scan matcher's map, without leaving the device
+  bool surroundToMap(size_t *nCorner, size_t *nSurf) { return check(lslam_lmap_surround_to_map_counts(_lm, nCorner, nSurf)); }
+  // :70-82 -- nothing to do: addDataFrame cleans, as the reference's does (n frames behind the threshold -> n + 1 erased)
+  void clean() {}
+  bool clear() { return check(lslam_lmap_clear(_lm)); }
+  const std::string &lastError() const { return _err; }
+  lslam_lmap *handle() { return _lm; }
+
+private:
+  bool check(int rc) {
+    if (rc < 0) _err = lslam_last_error();
+    return rc >= 0;
+  }
+  lslam_lmap *_lm;
+  std::string _err;
+};
+
+// LaserMappingLocal (odometry/LaserMappingLocal.cpp:39-83): LaserMatcher's steps over the sliding window -- its filtered
+// surround becomes the context's map before the match (prepareFeatureSurround, :61-66), the sweep's downsampled clouds are
+// added at the new map pose after it (featureMapUpdate, :68-83).
+class LaserMappingLocal : public detail::LaserMatcherSteps {
+public:
+  explicit LaserMappingLocal(lslam_ctx *ctx, float filterCorner = 1.0f, float filterSurf = 1.0f, double queueDistance = 30.0,
+                             size_t maxPointsPerType = 0, int maxFrames = 0, int flags = 0)
+      : detail::LaserMatcherSteps(ctx, filterCorner, filterSurf), _map(ctx, maxPointsPerType, maxFrames, flags) {
+    if (!_map.valid()) {
+      _err = _map.lastError();
+    } else {
+      _map.setupQueueDistance(queueDistance);
+      lslam_map_defer_trees(ctx, 1);  // (as LaserMapping: the per-sweep map is searched through its cell grids)
+    }
+  }
+  bool process(const std::vector<float> &cornerLast, const std::vector<float> &surfLast, const float lidarOdomNew[16]) {
+    if (!_map.valid()) return false;
+    if (!mergeAndPrepareFrame(cornerLast, surfLast, lidarOdomNew)) return false;
+    size_t nc = 0, ns = 0;
+    if (!_map.surroundToMap(&nc, &ns)) return failMap();
+    if (!optimizeAndUpdate(nc, ns, lidarOdomNew)) return false;
+    if (!_map.addDataFrame(_cornerDS, _surfDS, _lidarMappedNew)) return failMap();
+    return true;
+  }
+  LocalFeatureMap &featureMap() { return _map; }
+
+private:
+  bool failMap() {
+    _err = _map.lastError();
     return false;
   }
-  lslam_ctx *_ctx;
-  lslam_fmap *_fm;
-  float _filterCorner, _filterSurf;
-  lslam_opts _opts;
-  float _lidarOdomLast[16], _lidarMappedLast[16], _lidarMappedNew[16];
-  std::vector<float> _cornerDS, _surfDS;
-  lslam_stats _last;
-  std::string _err;
+  LocalFeatureMap _map;
 };
 
 }  // namespace lidar_slam

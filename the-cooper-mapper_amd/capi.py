@@ -229,6 +229,20 @@ SYMBOLS = {
     "lslam_fmap_load": (C.c_int, [C.c_void_p, C.c_char_p]),
     "lslam_fmap_info": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, C.c_size_t,
                                   C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lslam_lmap_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "lslam_lmap_destroy": (None, [C.c_void_p]),
+    "lslam_lmap_setup_queue_distance": (C.c_int, [C.c_void_p, C.c_double]),
+    "lslam_lmap_setup_filter_size": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
+    "lslam_lmap_add_data_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p]),
+    "lslam_lmap_add_data_frame_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_float_p]),
+    "lslam_lmap_surround_to_map_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lslam_lmap_get_surround": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, C.POINTER(C.c_size_t), c_float_p, C.c_size_t,
+                                          C.POINTER(C.c_size_t)]),
+    "lslam_lmap_info": (C.c_int, [C.c_void_p, c_int32_p, C.POINTER(C.c_double), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
+    "lslam_lmap_get_frames": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.POINTER(C.c_double), c_int32_p, c_float_p, C.c_size_t,
+                                        c_float_p, C.c_size_t]),
+    "lslam_lmap_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lslam_lmap_clear": (C.c_int, [C.c_void_p]),
     "lslam_voxel_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, c_float_p,
                                    C.c_size_t, C.POINTER(C.c_size_t)]),
     "lslam_voxel_grid2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, c_float_p,

@@ -1142,6 +1142,40 @@ int voxel_filter_segments(hipStream_t s, const float4 *in_pts, const int32_t *in
   }
   return rc;
 }
+
+// pcl::VoxelGrid of a window of points that its owner keeps in voxel-key order (lslam_lmap.hip, the sliding-window map): the
+// first n_sorted points of in_pts are in (absolute voxel of `leaf`, arrival) order already, the other n_total - n_sorted arrived
+// since -- only those are sorted, and merged in behind their equals (run_pipeline's n_sorted path, the one addFeatureCloud's
+// rebuilds take).  base0 / axis_bits: min_b and the key width of the window's extent, which the caller knows (it also evaluates
+// the "leaf too small" guard: this function always filters).  Nothing is waited for: {points out, key-range error, prefix not
+// in order} arrive in done[0..2] (pinned) behind everything else on the stream, *order is the sorted sequence as positions in
+// in_pts (device memory of `w`, valid until its next call) -- the caller permutes its points by it to keep them in order.
+struct WindowFilter {
+  Scratch sc;
+  Buf<int32_t> oc;
+};
+WindowFilter *window_filter_create() { return new WindowFilter(); }
+void window_filter_destroy(WindowFilter *w) {
+  if (!w) return;
+  w->sc.release();
+  w->oc.release();
+  delete w;
+}
+int voxel_filter_window(hipStream_t s, WindowFilter *w, const float4 *in_pts, size_t n_sorted, size_t n_total, float leaf,
+                        const int32_t base0[3], int axis_bits, float4 *out_pts, uint32_t *done, const uint32_t **order) {
+  KeyParams kp{};
+  kp.W = kp.H = kp.D = 1;
+  kp.cube_size = 1.0f;
+  kp.inv_leaf = 1.0f / leaf;
+  kp.single = 1;
+  kp.axis_bits = axis_bits;
+  for (int d = 0; d < 3; ++d) kp.base0[d] = base0[d];
+  FM_TRY(w->oc.reserve(n_total));
+  size_t m = 0;
+  const int rc = run_pipeline(s, w->sc, in_pts, nullptr, n_total, kp, 1, nullptr, out_pts, w->oc.p, &m, 0, done, n_sorted);
+  *order = w->sc.i1.p;
+  return rc;
+}
 }  // namespace lslam
 
 extern "C" {

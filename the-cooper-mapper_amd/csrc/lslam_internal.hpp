@@ -460,6 +460,13 @@ const char *debug_env(const char *name);  // nullptr unless the process runs wit
 int voxel_filter_segments(hipStream_t s, const float4 *in_pts, const int32_t *in_seg, size_t n, int nseg, float leaf,
                           float4 *out_pts, int32_t *out_seg, size_t *n_out, bool filter = true, uint32_t *done = nullptr);
 
+// lslam_fmap.hip: pcl::VoxelGrid of a window whose owner keeps its points in voxel-key order (see there)
+struct WindowFilter;  // the filter's scratch, owned by the caller
+WindowFilter *window_filter_create();
+void window_filter_destroy(WindowFilter *w);
+int voxel_filter_window(hipStream_t s, WindowFilter *w, const float4 *in_pts, size_t n_sorted, size_t n_total, float leaf,
+                        const int32_t base0[3], int axis_bits, float4 *out_pts, uint32_t *done, const uint32_t **order);
+
 // lslam_sort.hip: (64-bit key, 32-bit value) pairs ascending by key, equal keys by value -- the values must be distinct among
 // equal keys (every caller passes input positions: a stable sort by key).  For n <= SMALL_SORT_MAX; tmp: small_sort_tmp_bytes(n)
 // bytes of device memory (none for a single tile), in / out must not overlap

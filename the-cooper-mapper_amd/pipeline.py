@@ -10,12 +10,15 @@ the C ABI (clouds are (n, 4) float32 {x, y, z, intensity = ring + relTime}):
   (LaserMatcher.cpp:289-354): transformMerge (odometry prior), VoxelGrid of the frame's features,
   FeatureMap::update + surround, scanMatchScan (thresholds 0.1 / 0.1, score gate off, return value
   ignored), transformUpdate, addFeatureCloud.
+* :class:`LaserMappingLocal` -- ``LaserMappingLocal::process`` (LaserMappingLocal.cpp:39-83): the same matcher over
+  ``LocalFeatureMap``, the sliding window of recent frames (:mod:`.local_feature_map`), instead of the cube grid.
 
 ROS plumbing (topics, time-stamp checks, tf, frame skipping) is not mirrored.
 """
 import numpy as np
 
 from .feature_map import FeatureMap, voxel_grid, voxel_grid2
+from .local_feature_map import LocalFeatureMap
 
 
 class LaserOdometry:
@@ -122,18 +125,17 @@ class DeviceLaserOdometry:
             pass
 
 
-class LaserMapping:
-    def __init__(self, ctx, cube_dims=(121, 121, 11), filter_corner=1.0, filter_surf=1.0, map_filter_corner=1.0,
-                 map_filter_surf=1.0, map_filter=2.0, defer_trees=True, defer_add=False):
-        # LaserMatcher.cpp:80-116 defaults
+class _LaserMatcher:
+    """``LaserMatcher`` (LaserMatcher.cpp:80-116, 289-347): the per-sweep steps the mapping nodes share.  A node supplies its
+    map container through ``_prepare_feature_surround`` (-> the sizes of the two surround clouds, which have become the
+    context's map) and ``_feature_map_update``."""
+
+    def _init_matcher(self, ctx, filter_corner, filter_surf, defer_trees):
         self.ctx = ctx
-        self.defer_add = defer_add  # process() ends with lslam_fmap_add_feature_cloud_begin: pays where the host idles between sweeps
         # the per-frame surround map is searched through its cell grids; its kd-trees are built only if a frame needs them
         # (include/lslam_c.h lslam_map_defer_trees) -- same poses either way
         ctx.defer_trees(defer_trees)
         self.filter_corner, self.filter_surf = filter_corner, filter_surf
-        self.feature_map = FeatureMap(ctx, *cube_dims)
-        self.feature_map.setup_filter_size(map_filter_corner, map_filter_surf, map_filter)
         self.opts = ctx.default_opts()
         self.opts.delta_t_abort = 0.1   # _scan_match.setConvergeThreshold(0.1, 0.1), :94
         self.opts.delta_r_abort = 0.1
@@ -165,9 +167,8 @@ class LaserMapping:
         else:
             corner_ds = voxel_grid(self.ctx, corner_last, self.filter_corner)
             surf_ds = voxel_grid(self.ctx, surf_last, self.filter_surf)
-        # prepareFeatureSurround, :303-325
-        self.feature_map.update(self.lidar_mapped_new[:3, 3])
-        nc, ns = self.feature_map.surround_to_map_counts()  # (the surround becomes the context's map; its sizes come back with it)
+        # prepareFeatureSurround, :303-325 (the surround becomes the context's map; its sizes come back with it)
+        nc, ns = self._prepare_feature_surround()
         # optimizeTransform, :327-331 (return value ignored; pose written back unless "too few ref")
         if nc or ns:
             pose = self.ctx.isometry_to_pose(self.lidar_mapped_new)
@@ -178,7 +179,43 @@ class LaserMapping:
         # transformUpdate, :342-347
         self.lidar_mapped_last = self.lidar_mapped_new.copy()
         self.lidar_odom_last = odom_merged.copy()
-        # featureMapUpdate, :349-354 (defer_add: enqueued, not waited for -- the rebuild runs while the node takes up its next sweep,
-        # the next call on the map waits and commits first)
-        self.feature_map.add_feature_cloud(corner_ds, surf_ds, self.lidar_mapped_new, wait=not self.defer_add)
+        # featureMapUpdate, :349-354
+        self._feature_map_update(corner_ds, surf_ds)
         return self.lidar_mapped_new.copy()
+
+
+class LaserMapping(_LaserMatcher):
+    def __init__(self, ctx, cube_dims=(121, 121, 11), filter_corner=1.0, filter_surf=1.0, map_filter_corner=1.0,
+                 map_filter_surf=1.0, map_filter=2.0, defer_trees=True, defer_add=False):
+        # LaserMatcher.cpp:80-116 defaults
+        self._init_matcher(ctx, filter_corner, filter_surf, defer_trees)
+        self.defer_add = defer_add  # process() ends with lslam_fmap_add_feature_cloud_begin: pays where the host idles between sweeps
+        self.feature_map = FeatureMap(ctx, *cube_dims)
+        self.feature_map.setup_filter_size(map_filter_corner, map_filter_surf, map_filter)
+
+    def _prepare_feature_surround(self):
+        self.feature_map.update(self.lidar_mapped_new[:3, 3])
+        return self.feature_map.surround_to_map_counts()
+
+    def _feature_map_update(self, corner_ds, surf_ds):
+        # (defer_add: enqueued, not waited for -- the rebuild runs while the node takes up its next sweep, the next call on the
+        # map waits and commits first)
+        self.feature_map.add_feature_cloud(corner_ds, surf_ds, self.lidar_mapped_new, wait=not self.defer_add)
+
+
+class LaserMappingLocal(_LaserMatcher):
+    """``LaserMappingLocal`` (LaserMappingLocal.cpp:39-83): LaserMatcher's steps with the two overrides -- the surround is the
+    sliding window's (``LocalFeatureMap::getSurroundFeature``: every frame of the last ``queue_distance`` metres, VoxelGrid
+    0.2 / 0.4), and the sweep ends with ``addDataFrame`` of its downsampled clouds at the new map pose.  ``mode``:
+    :mod:`.local_feature_map` ``MODE_*`` (how the container produces the surround; same bits)."""
+
+    def __init__(self, ctx, filter_corner=1.0, filter_surf=1.0, queue_distance=30.0, map_filter_corner=0.2, map_filter_surf=0.4,
+                 max_points=0, max_frames=0, mode=0, defer_trees=True):
+        self._init_matcher(ctx, filter_corner, filter_surf, defer_trees)
+        self.feature_map = LocalFeatureMap(ctx, max_points, max_frames, mode, queue_distance, map_filter_corner, map_filter_surf)
+
+    def _prepare_feature_surround(self):  # LaserMappingLocal.cpp:61-66
+        return self.feature_map.surround_to_map_counts()
+
+    def _feature_map_update(self, corner_ds, surf_ds):  # :68-83
+        self.feature_map.add_data_frame(corner_ds, surf_ds, self.lidar_mapped_new)
