@@ -427,7 +427,7 @@ def test_destroy_releases_device_memory(pkg, ctx, frames):
         lm.close()
         return used
     free0 = torch.cuda.mem_get_info()[0]
-    cycle()  # (what the context and the per-stream filter cache keep is taken here)
+    cycle()  # (what the context keeps -- its filter scratch grows with the first container -- is taken here)
     free0 = torch.cuda.mem_get_info()[0]
     one = cycle()
     assert one > (1 << 20) * 16 * 4  # a container of 2^20 points per type is hundreds of megabytes

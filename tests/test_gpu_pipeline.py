@@ -224,7 +224,7 @@ def test_three_nodes_on_three_threads_equal_the_sequential_chain(pkg, synth, sma
     against the same calls from one thread.  The nodes share nothing but the device -- which is what this test is for: the
     library's per-device scratch caches (VoxelGrid, registration, extraction) were once handed to whichever context asked, and a
     no-wait caller on one thread had its scratch reused by another thread's context while its kernels ran (garbage ring ids, a
-    host segfault, a GPU memory fault).  They are per stream now; the two schedules must end at the same map pose."""
+    host segfault, a GPU memory fault).  Each context owns its scratch now; the two schedules must end at the same map pose."""
     import subprocess
     world = small_problem["world"]
     sweeps = 12

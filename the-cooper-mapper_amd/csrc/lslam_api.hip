@@ -52,36 +52,6 @@ double now_ms() {
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
-template <typename T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t cap = 0;
-  bool borrowed = false;  // p points into another allocation (adopt): never freed here, dropped by the next reserve
-  void adopt(T *ptr, size_t n) {
-    if (p && !borrowed) (void)hipFree(p);
-    p = ptr;
-    cap = n;
-    borrowed = true;
-  }
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p && !borrowed) (void)hipFree(p);
-    borrowed = false;
-    p = nullptr;
-    cap = 0;
-    size_t want = n + n / 8 + 64;
-    hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p && !borrowed) (void)hipFree(p);
-    borrowed = false;
-    p = nullptr;
-    cap = 0;
-  }
-};
-
 struct DevTree {
   DevBuf<KdNode> nodes;
   DevBuf<PNode> pn;  // packet-search nodes, same slots: made on demand (ensure_packet_nodes)
@@ -156,7 +126,8 @@ struct lslam_ctx {
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;  // the corner tree is built beside the surf tree; the corner map's cell grid beside the surf map's
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // ... forked from and joined to `stream` by these
-  ScanPrep *scanprep = nullptr;
+  CtxSlotEntry slots[CTX_N_SLOTS];  // scratch other translation units keep here (ctx_slot)
+  BuildPool build_pool[2];          // the tree build's scratch: of `stream`, of `stream2` (the worker's builds)
   Worker worker;  // builds the corner tree beside the surf tree
   int cube_sides_on_device = 0;  // cube-map sides built by the device forest builder (of the last set)
   DevTree tc, ts;
@@ -196,8 +167,7 @@ struct lslam_ctx {
   std::vector<int32_t> h_prob_group0;  // [n_prob + 1] first group of every scan
   uint64_t queue_launches = 0;
   DevBuf<int32_t> active_blocks;  // [nb_total] the grid sweep of a batch: block indices of the scans still running, per chunk at its block range
-  int32_t *h_active = nullptr;    // pinned: [n_chunks] how many
-  size_t h_active_cap = 0;
+  PinBuf<int32_t> h_active;       // [n_chunks] how many
   DevBuf<int32_t> d_active_cnt;
   DevBuf<int32_t> fit_ids;     // the grid sweep's fit cache (LSLAM_AB_FIT_CACHE): [5][n_points] neighbour positions ...
   DevBuf<float> fit_val;       // ... and [5][n_points] plane + verdict
@@ -206,9 +176,8 @@ struct lslam_ctx {
   bool grid_state_valid = false;  // prev_q holds what a grid-sweep run of the resident scan against the resident map left (LSLAM_SWEEP_CARRIED)
   lslam_comm *comm = nullptr;  // RCCL communicator of the sharded-points path (not owned)
   DevBuf<double> xchg;         // its exchange buffer
-  GNState *d_state = nullptr;   // [state_cap]
-  GNState *h_state = nullptr;   // pinned, [state_cap]
-  int32_t state_cap = 0;
+  DevBuf<GNState> d_state;     // one per resident scan (ensure_states)
+  PinBuf<GNState> h_state;
   // tap buffers
   DevBuf<int32_t> t_idx;
   DevBuf<float> t_d2;
@@ -227,12 +196,10 @@ struct lslam_ctx {
   bool gnp_ok = true;     // false once an exchange timed out: the launch loop from then on
   int gnp_runs = 0;
   // pinned staging area for the scan clouds a caller hands over (packed here, copied from here)
-  float4 *h_stage = nullptr;
-  size_t h_stage_cap = 0;
+  PinBuf<float4> h_stage;
   bool stage_busy = false;  // a copy out of h_stage was enqueued and no wait on the stream has happened since
   // ... and for the two map clouds of lslam_map_set (one per tree: they are packed on two threads)
-  float4 *h_map_stage[2] = {nullptr, nullptr};
-  size_t h_map_cap[2] = {0, 0};
+  PinBuf<float4> h_map_stage[2];
   // variant B (lslam_odometry_match): clouds, correspondences (grow-only, reused across sweeps)
   DevBuf<float4> od_oc, od_os, od_q, od_sel;
   DevBuf<int32_t> od_ind;
@@ -362,7 +329,7 @@ void fill_sweep_args(lslam_ctx *ctx, SweepArgs &a) {
   a.q = ctx->q.p;
   a.blocks = ctx->blocks.p;
   a.nb_total = ctx->nb_total;
-  a.states = ctx->d_state;
+  a.states = ctx->d_state.p;
   a.partials = ctx->partials.p;
   a.stack_ovf = nullptr;
   a.prev_nb = ctx->prev_nb.p;
@@ -533,15 +500,8 @@ hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, hipEve
 }
 
 int ensure_states(lslam_ctx *ctx, int32_t n) {
-  if (n <= ctx->state_cap) return LSLAM_OK;
-  if (ctx->d_state) (void)hipFree(ctx->d_state);
-  if (ctx->h_state) (void)hipHostFree(ctx->h_state);
-  ctx->d_state = nullptr;
-  ctx->h_state = nullptr;
-  ctx->state_cap = 0;
-  HIP_TRY(hipMalloc((void **)&ctx->d_state, sizeof(GNState) * (size_t)n));
-  HIP_TRY(hipHostMalloc((void **)&ctx->h_state, sizeof(GNState) * (size_t)n, hipHostMallocDefault));
-  ctx->state_cap = n;
+  HIP_TRY(ctx->d_state.reserve((size_t)n));
+  HIP_TRY(ctx->h_state.reserve((size_t)n));
   return LSLAM_OK;
 }
 
@@ -710,46 +670,19 @@ void lslam_ctx_destroy(lslam_ctx *ctx) {
   ctx->worker.stop();
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  lslam::odom_ctx_gone(ctx);  // the hidden odometry node of lslam_odometry_match (lslam_odom.hip)
-  ctx->tc.nodes.release(); ctx->tc.pts.release(); ctx->tc.pn.release(); ctx->tc.own_box.release();
-  ctx->ts.nodes.release(); ctx->ts.pts.release(); ctx->ts.pn.release(); ctx->ts.own_box.release();
-  ctx->cell_c.release(); ctx->cell_s.release(); ctx->views_c.release(); ctx->views_s.release();
-  ctx->prev_nb.release();
-  ctx->prev_q.release();
-  ctx->prev_lb.release();
-  ctx->need_list.release();
-  ctx->need_cnt.release();
-  ctx->need2_list.release();
-  ctx->need2_cnt.release();
-  ctx->groups.release();
-  ctx->scan_tables.release();
-  ctx->cert_work.release();
-  ctx->cert_count.release();
+  if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
+  // nothing is in flight any more: what other translation units kept here goes (the hidden odometry node, the filters' and
+  // the feature extraction's scratch), then the events and the streams; the context's own buffers go with `delete`
+  for (CtxSlotEntry &e : ctx->slots)
+    if (e.obj) e.drop(e.obj);
   ctx->kc.release();
   ctx->ks.release();
-  ctx->bbox6.release(); ctx->wide_p.release(); ctx->wide_d.release(); ctx->wide_off.release();
-  ctx->xchg.release();
-  ctx->active_blocks.release(); ctx->d_active_cnt.release(); ctx->fit_ids.release(); ctx->fit_val.release();
-  ctx->cert_stats.release();
-  ctx->gnp_slots.release(); ctx->gnp_bar.release();
-  ctx->q.release(); ctx->blocks.release(); ctx->probs.release(); ctx->partials.release(); ctx->stack_ovf.release();
-  ctx->t_idx.release(); ctx->t_d2.release(); ctx->t_coeff.release(); ctx->t_flags.release();
-  ctx->t_q.release(); ctx->t_small.release();
-  if (ctx->d_state) (void)hipFree(ctx->d_state);
-  if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-  for (int k = 0; k < 2; ++k)
-    if (ctx->h_map_stage[k]) (void)hipHostFree(ctx->h_map_stage[k]);
-  if (ctx->h_state) (void)hipHostFree(ctx->h_state);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   for (hipEvent_t e : ctx->sweep_ev) (void)hipEventDestroy(e);
-  scanprep_destroy(ctx->scanprep);
-  treebuild_release_scratch(ctx->stream);
-  if (ctx->stream2) treebuild_release_scratch(ctx->stream2);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-  if (ctx->h_active) (void)hipHostFree(ctx->h_active);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -839,7 +772,7 @@ int lslam_debug_tree_dump(lslam_ctx *ctx, int which, uint32_t *nodes_out, size_t
 
 // Profiling tap: phase stamps of the last solve kernel (100 MHz ticks).
 void lslam_debug_solve_clocks(lslam_ctx *ctx, uint64_t out[8]) {
-  for (int i = 0; i < 8; ++i) out[i] = ctx->h_state->clk[i];
+  for (int i = 0; i < 8; ++i) out[i] = ctx->h_state.p->clk[i];
 }
 
 // Profiling tap (not part of the drop-in surface): one sweep at `pose` with per-wave
@@ -849,8 +782,8 @@ int lslam_debug_sweep_clocks(lslam_ctx *ctx, const float pose[6], int32_t jtj_mo
   int rc = check_ctx(ctx);
   if (rc) return rc;
   if (!ctx->have_map || !ctx->have_scan || ctx->n_prob != 1) return LSLAM_ERR_NO_MAP;
-  init_state(*ctx->h_state, pose);
-  HIP_TRY(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
+  init_state(*ctx->h_state.p, pose);
+  HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
   SweepArgs sa;
   fill_sweep_args(ctx, sa);
   rc = ensure_stack_ovf(ctx, (size_t)sa.nb_total * SWEEP_BLOCK, &sa.stack_ovf);
@@ -931,16 +864,9 @@ int map_set_impl(lslam_ctx *ctx, const void *corner, size_t n_corner, const void
   // {x, y, z, bitcast(index)} of a host cloud packed straight into pinned memory, a chunk at a time, each chunk's DMA running
   // while the next one is packed
   auto upload_host = [&](int k, const void *host, size_t n, float4 *dst, hipStream_t st) -> hipError_t {
-    if (n > ctx->h_map_cap[k]) {
-      if (ctx->h_map_stage[k]) (void)hipHostFree(ctx->h_map_stage[k]);
-      ctx->h_map_stage[k] = nullptr;
-      ctx->h_map_cap[k] = 0;
-      const size_t want = n + n / 4 + 1024;
-      hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&ctx->h_map_stage[k]), want * sizeof(float4), hipHostMallocDefault);
-      if (e != hipSuccess) return e;
-      ctx->h_map_cap[k] = want;
-    }
-    float4 *stage = ctx->h_map_stage[k];
+    hipError_t e = ctx->h_map_stage[k].reserve(n);
+    if (e != hipSuccess) return e;
+    float4 *stage = ctx->h_map_stage[k].p;
     const char *sp = static_cast<const char *>(host);
     constexpr size_t CHUNK = 1u << 17;
     for (size_t off = 0; off < n; off += CHUNK) {
@@ -1047,7 +973,7 @@ int map_set_impl(lslam_ctx *ctx, const void *corner, size_t n_corner, const void
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     int fb[2] = {0, 0};
     hipError_t errs[2] = {hipSuccess, hipSuccess};
-    auto build_one = [&](int k, hipStream_t st) {
+    auto build_one = [&](int k, hipStream_t st, BuildPool &pool) {
       DevTree &dt = *trees[k];
       const size_t n = counts[k];
       (void)hipSetDevice(ctx->device);
@@ -1069,12 +995,12 @@ int map_set_impl(lslam_ctx *ctx, const void *corner, size_t n_corner, const void
         if (n && from_dev) {
           errs[k] = hipMemcpyAsync(dt.pts.p, dev_src[k], n * sizeof(float4), hipMemcpyDeviceToDevice, st);
         } else if (n && (attempt > dt.cap_attempt || host_uploaded)) {  // the packed cloud is in the pinned staging already
-          errs[k] = hipMemcpyAsync(dt.pts.p, ctx->h_map_stage[k], n * sizeof(float4), hipMemcpyHostToDevice, st);
+          errs[k] = hipMemcpyAsync(dt.pts.p, ctx->h_map_stage[k].p, n * sizeof(float4), hipMemcpyHostToDevice, st);
         } else if (n) {
           errs[k] = upload_host(k, host_src[k], n, dt.pts.p, st);
         }
         if (errs[k] != hipSuccess) return;
-        errs[k] = build_kdtree_device(dt.pts.p, (int32_t)n, dt.nodes.p, dt.own_box.p, (int32_t)cap, st, &dt.view, &dt.depth,
+        errs[k] = build_kdtree_device(pool, dt.pts.p, (int32_t)n, dt.nodes.p, dt.own_box.p, (int32_t)cap, st, &dt.view, &dt.depth,
                                       &n_leaves, &fallback);
         if (errs[k] != hipSuccess) return;
         if (fallback != 1) {
@@ -1087,8 +1013,8 @@ int map_set_impl(lslam_ctx *ctx, const void *corner, size_t n_corner, const void
     };
     {
       if (!ctx_stream2(ctx)) return LSLAM_ERR_HIP;
-      ctx->worker.submit([&] { build_one(0, ctx->stream2); });
-      build_one(1, ctx->stream);
+      ctx->worker.submit([&] { build_one(0, ctx->stream2, ctx->build_pool[1]); });
+      build_one(1, ctx->stream, ctx->build_pool[0]);
       ctx->worker.wait();
     }
     for (int k = 0; k < 2; ++k) {
@@ -1152,7 +1078,7 @@ int ensure_trees(lslam_ctx *ctx) {
       ET_TRY(dt.nodes.reserve(cap));
       ET_TRY(dt.own_box.reserve(cap * 6));
       ET_TRY(grid_unsort(gd[k]->view, dt.pts.p, ctx->stream));
-      ET_TRY(build_kdtree_device(dt.pts.p, (int32_t)n, dt.nodes.p, dt.own_box.p, (int32_t)cap, ctx->stream, &dt.view, &dt.depth,
+      ET_TRY(build_kdtree_device(ctx->build_pool[0], dt.pts.p, (int32_t)n, dt.nodes.p, dt.own_box.p, (int32_t)cap, ctx->stream, &dt.view, &dt.depth,
                                   &n_leaves, &fallback));
       if (fallback != 1) {
         if (!fallback) dt.cap_attempt = attempt;
@@ -1319,6 +1245,8 @@ int ctx_scratch(lslam_ctx *ctx, size_t n_float4, size_t n_double, float4 **pts, 
 }
 int ctx_stack_ovf_if_deep(lslam_ctx *ctx, size_t n_threads, uint32_t **out) { return ensure_stack_ovf(ctx, n_threads, out); }
 int ctx_device(const lslam_ctx *ctx) { return ctx ? ctx->device : -1; }
+BuildPool &ctx_build_pool(lslam_ctx *ctx, int which) { return ctx->build_pool[which]; }
+CtxSlotEntry &ctx_slot_entry(lslam_ctx *ctx, CtxSlot which) { return ctx->slots[which]; }
 bool ctx_alive(const lslam_ctx *ctx) {
   std::lock_guard<std::mutex> lk(g_live_mu);
   return g_live.count(ctx) != 0;
@@ -1358,7 +1286,7 @@ int build_cube_side_device(lslam_ctx *ctx, DevTree &dt, const float4 *src, bool 
     if (n_pts)
       HIP_TRY(hipMemcpyAsync(dt.pts.p, src, n_pts * sizeof(float4), src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                              ctx->stream));
-    HIP_TRY(build_kdforest_device(dt.pts.p, (int32_t)n_pts, roots_lr.data(), T, dt.nodes.p, nullptr, (int32_t)cap, ctx->stream,
+    HIP_TRY(build_kdforest_device(ctx->build_pool[0], dt.pts.p, (int32_t)n_pts, roots_lr.data(), T, dt.nodes.p, nullptr, (int32_t)cap, ctx->stream,
                                   views.data(), max_depth, &n_leaves, fallback));
     if (*fallback != 1) break;
   }
@@ -1508,15 +1436,8 @@ int lslam_scan_set_batch(lslam_ctx *ctx, int32_t n_scans, const void *const *cor
   }
   // the clouds are packed straight into pinned memory: one pass over the caller's points, and the
   // H2D copy is a real asynchronous DMA instead of a staged pageable copy
-  if (total > ctx->h_stage_cap) {
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    ctx->h_stage = nullptr;
-    ctx->h_stage_cap = 0;
-    const size_t cap = total + total / 4 + 1024;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_stage), cap * sizeof(float4), hipHostMallocDefault));
-    ctx->h_stage_cap = cap;
-  }
-  float4 *all = ctx->h_stage;
+  HIP_TRY(ctx->h_stage.reserve(total));
+  float4 *all = ctx->h_stage.p;
   size_t n_all = 0;
   ctx->h_blocks.clear();
   ctx->h_groups.clear();
@@ -1616,8 +1537,7 @@ int lslam_scan_set_batch(lslam_ctx *ctx, int32_t n_scans, const void *const *cor
   rc = ensure_states(ctx, n_scans);
   if (rc) return rc;
   if (total && dev_morton) {
-    if (!ctx->scanprep) ctx->scanprep = scanprep_create();
-    HIP_TRY(scanprep_order(ctx->scanprep, ctx->stream, all, total, seg_off.data(), (int)seg_off.size() - 1,
+    HIP_TRY(scanprep_order(ctx, all, total, seg_off.data(), (int)seg_off.size() - 1,
                            ctx->q.p));
   } else if (total) {
     HIP_TRY(hipMemcpyAsync(ctx->q.p, all, total * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
@@ -1702,10 +1622,10 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
   ctx->grid_state_valid = false;
 
   for (int32_t p = 0; p < n_scans; ++p) {
-    init_state(ctx->h_state[p], poses + 6 * p);
-    if (max_it == 0) ctx->h_state[p].done = 1;
+    init_state(ctx->h_state.p[p], poses + 6 * p);
+    if (max_it == 0) ctx->h_state.p[p].done = 1;
   }
-  HIP_TRY(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(GNState) * (size_t)n_scans,
+  HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState) * (size_t)n_scans,
                          hipMemcpyHostToDevice, ctx->stream));
   const int search = resolve_search_mode(ctx, o.search_mode);  // (may make the packet search's nodes: before the views are copied)
   SweepArgs sa;
@@ -1724,7 +1644,7 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
     }
   }
   SolveArgs so{};
-  so.states = ctx->d_state;
+  so.states = ctx->d_state.p;
   so.partials = ctx->partials.p;
   so.probs = ctx->probs.p;
   so.n_prob = n_scans;
@@ -1745,7 +1665,7 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
     sta.blocks = ctx->st_blocks.p;
     sta.n_blocks = ctx->n_st_blocks;
     sta.cam = ctx->st_cam;
-    sta.states = ctx->d_state;
+    sta.states = ctx->d_state.p;
     sta.partials = ctx->st_partials.p;
     so.partials2 = ctx->st_partials.p;
     so.probs2 = ctx->st_probs.p;
@@ -1821,9 +1741,9 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
         ++launched;
       }
       HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-      HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(hipStreamSynchronize(ctx->stream));
-      if (ctx->h_state[0].done) break;  // identical on every rank: same sums, same solve
+      if (ctx->h_state.p[0].done) break;  // identical on every rank: same sums, same solve
       batch = 2;
     }
   }
@@ -1861,7 +1781,7 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
         gl.slots = ctx->gnp_slots.p;
         gl.gslots = reinterpret_cast<double *>(ctx->gnp_slots.p + 2 * (size_t)sa.nb_total * NCOL);
         gl.bar = ctx->gnp_bar.p;
-        gl.state_out = ctx->d_state;
+        gl.state_out = ctx->d_state.p;
         gl.max_iterations = max_it;
         gl.min_rows = so.min_rows;
         gl.delta_r_abort = so.delta_r_abort;
@@ -1871,18 +1791,18 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
         ctx->sweep_variants[SWEEP_VARIANT_PERSISTENT]++;
         HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
         unsigned gbar[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipMemcpyAsync(gbar, ctx->gnp_bar.p, sizeof(gbar), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         if (gbar[1] == 0) {
           gnp_done = true;
           ctx->gnp_runs++;
-          launched = ctx->h_state[0].sweeps;
+          launched = ctx->h_state.p[0].sweeps;
         } else {  // an exchange ran into its spin limit (the workgroups were not all resident): the launch loop, from the start
           if (ctx->env_debug) fprintf(stderr, "[lslam] persistent GN kernel timed out in its grid exchange: launch loop from here on\n");
           ctx->gnp_ok = false;
-          init_state(ctx->h_state[0], poses);
-          HIP_TRY(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
+          init_state(ctx->h_state.p[0], poses);
+          HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
         }
       }
     }
@@ -2032,7 +1952,7 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
         sc.group_block_base = fb;
       }
       SolveArgs soc = so;
-      soc.states = ctx->d_state + p0;
+      soc.states = ctx->d_state.p + p0;
       soc.probs = ctx->probs.p + p0;
       soc.n_prob = p1 - p0;
       StereoArgs stc = sta;  // the stereo blocks of this chunk's scans (their sets are consecutive)
@@ -2081,13 +2001,7 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
       const bool track_running = ctx->n_stereo > 0;
       const size_t n_cnt = (size_t)n_chunks * (track_running ? 2 : 1);
       HIP_TRY(ctx->d_active_cnt.reserve(n_cnt));
-      if (ctx->h_active_cap < n_cnt) {
-        if (ctx->h_active) (void)hipHostFree(ctx->h_active);
-        ctx->h_active = nullptr;
-        ctx->h_active_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&ctx->h_active, sizeof(int32_t) * n_cnt, hipHostMallocDefault));
-        ctx->h_active_cap = n_cnt;
-      }
+      HIP_TRY(ctx->h_active.reserve(n_cnt));
       for (;;) {
         bool any = false;
         for (int c = 0; c < n_chunks; ++c) {
@@ -2097,27 +2011,27 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
           if (rc) return rc;
           const int p0 = c * in_flight, p1 = std::min(n_scans, p0 + in_flight);
           const int32_t fb = ctx->h_probs[(size_t)p0].first_block;
-          HIP_TRY(launch_compact_active(ctx->d_state + p0, ctx->probs.p + p0, p1 - p0, fb, ctx->active_blocks.p + fb, ctx->d_active_cnt.p + c, ctx->stream,
+          HIP_TRY(launch_compact_active(ctx->d_state.p + p0, ctx->probs.p + p0, p1 - p0, fb, ctx->active_blocks.p + fb, ctx->d_active_cnt.p + c, ctx->stream,
                                         track_running ? ctx->d_active_cnt.p + n_chunks + c : nullptr));
           any = true;
         }
         if (!any) break;
         launched = *std::max_element(done_iters.begin(), done_iters.end());
         HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->h_active, ctx->d_active_cnt.p, sizeof(int32_t) * n_cnt, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->h_active.p, ctx->d_active_cnt.p, sizeof(int32_t) * n_cnt, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         bool all_done = true;
         for (int c = 0; c < n_chunks; ++c) {
           if (finished[(size_t)c]) continue;
-          active_n[(size_t)c] = ctx->h_active[c];
+          active_n[(size_t)c] = ctx->h_active.p[c];
           // with the stereo term a running scan may have no LiDAR workgroup left to launch: the chunk is over when no scan runs
-          const bool over = track_running ? ctx->h_active[n_chunks + c] == 0 : active_n[(size_t)c] <= 0;
+          const bool over = track_running ? ctx->h_active.p[n_chunks + c] == 0 : active_n[(size_t)c] <= 0;
           if (over || done_iters[(size_t)c] >= max_it) finished[(size_t)c] = 1;
           all_done = all_done && finished[(size_t)c];
         }
         if (all_done) break;
       }
-      HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState) * (size_t)n_scans, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState) * (size_t)n_scans, hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(hipStreamSynchronize(ctx->stream));
     } else
     for (;;) {
@@ -2132,14 +2046,14 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
       }
       launched = *std::max_element(done_iters.begin(), done_iters.end());
       HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-      HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState) * (size_t)n_scans,
+      HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState) * (size_t)n_scans,
                              hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(hipStreamSynchronize(ctx->stream));
       bool all_done = true;
       for (int c = 0; c < n_chunks; ++c) {
         const int p0 = c * in_flight, p1 = std::min(n_scans, p0 + in_flight);
         bool cd = true;
-        for (int p = p0; p < p1; ++p) cd = cd && ctx->h_state[p].done;
+        for (int p = p0; p < p1; ++p) cd = cd && ctx->h_state.p[p].done;
         if (cd || done_iters[(size_t)c] >= max_it) finished[(size_t)c] = 1;
         all_done = all_done && finished[(size_t)c];
       }
@@ -2155,7 +2069,7 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
   std::vector<double> score2((size_t)n_scans, 0.0), match2((size_t)n_scans, 0.0);
   if (o.fine_score && o.use_score && max_it > 0) {
     bool any_conv = false;
-    for (int32_t p = 0; p < n_scans; ++p) any_conv = any_conv || ctx->h_state[p].converged;
+    for (int32_t p = 0; p < n_scans; ++p) any_conv = any_conv || ctx->h_state.p[p].converged;
     if (any_conv) {
       SweepArgs sf = sa;
       sf.tail = SweepTail{};  // this pass only reduces
@@ -2192,7 +2106,7 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
           }
         }
         SolveArgs soc = so;
-        soc.states = ctx->d_state + p0;
+        soc.states = ctx->d_state.p + p0;
         soc.probs = ctx->probs.p + p0;
         soc.n_prob = p1 - p0;
         soc.reduce_only = 2;
@@ -2210,11 +2124,11 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
         HIP_TRY(hipMemcpyAsync(xs, xchg, sizeof(xs), hipMemcpyDeviceToHost, ctx->stream));
       }
       HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-      HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState) * (size_t)n_scans, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState) * (size_t)n_scans, hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(hipStreamSynchronize(ctx->stream));
       for (int32_t p = 0; p < n_scans; ++p) {
-        if (!ctx->h_state[p].converged) continue;
-        const double *sm = sharded ? xs : ctx->h_state[p].sums;
+        if (!ctx->h_state.p[p].converged) continue;
+        const double *sm = sharded ? xs : ctx->h_state.p[p].sums;
         score2[(size_t)p] = sm[COL_SCORE];
         match2[(size_t)p] = sm[COL_LINE] + sm[COL_PLANE];
       }
@@ -2224,7 +2138,7 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
   ctx->stage_busy = false;  // the stream has been waited for since the scan was set
   if (lazy) {  // a point's answer needed nanoflann's visit order (sweep_wide_kernel): the trees after all, and the call again
     bool need_tree = false;
-    for (int32_t p = 0; p < n_scans; ++p) need_tree = need_tree || ctx->h_state[p].pad != 0;
+    for (int32_t p = 0; p < n_scans; ++p) need_tree = need_tree || ctx->h_state.p[p].pad != 0;
     if (need_tree) {
       rc = ensure_trees(ctx);
       if (rc) return rc;
@@ -2233,8 +2147,8 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
   }
   int max_sweeps = 0, max_iter = 0;
   for (int32_t p = 0; p < n_scans; ++p) {
-    max_sweeps = std::max(max_sweeps, ctx->h_state[p].sweeps);
-    max_iter = std::max(max_iter, ctx->h_state[p].iter);
+    max_sweeps = std::max(max_sweeps, ctx->h_state.p[p].sweeps);
+    max_iter = std::max(max_iter, ctx->h_state.p[p].iter);
   }
   // the spare iteration (five immediate exits of 4 - 5 us each on the grid path) is dropped once three calls in a row ran the
   // same number of iterations -- a mapping node's frames do; a loop that then needs one more costs one more round trip
@@ -2257,7 +2171,7 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
   }
   int worst = LSLAM_OK;
   for (int32_t p = 0; p < n_scans; ++p) {
-    const GNState &g = ctx->h_state[p];
+    const GNState &g = ctx->h_state.p[p];
     for (int i = 0; i < 6; ++i) poses[6 * p + i] = g.pose[i];  // always written back
     const size_t npts = (size_t)ctx->nqc[(size_t)p] + (size_t)ctx->nqs[(size_t)p];
     int status;
@@ -2421,19 +2335,19 @@ namespace {
 int stereo_sums_impl(lslam_ctx *ctx, int32_t n_sets, const float *poses, double *sums32) {
   int rc = ensure_states(ctx, n_sets);
   if (rc) return rc;
-  for (int32_t p = 0; p < n_sets; ++p) init_state(ctx->h_state[p], poses + 6 * p);
-  HIP_TRY(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(GNState) * (size_t)n_sets, hipMemcpyHostToDevice, ctx->stream));
+  for (int32_t p = 0; p < n_sets; ++p) init_state(ctx->h_state.p[p], poses + 6 * p);
+  HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState) * (size_t)n_sets, hipMemcpyHostToDevice, ctx->stream));
   StereoArgs sta{};
   sta.landmarks = ctx->st_lm.p;
   sta.obs = ctx->st_obs.p;
   sta.blocks = ctx->st_blocks.p;
   sta.n_blocks = ctx->n_st_blocks;
   sta.cam = ctx->st_cam;
-  sta.states = ctx->d_state;
+  sta.states = ctx->d_state.p;
   sta.partials = ctx->st_partials.p;
   HIP_TRY(launch_stereo(sta, ctx->stream));
   SolveArgs so{};
-  so.states = ctx->d_state;
+  so.states = ctx->d_state.p;
   so.partials = ctx->st_partials.p;  // unused: the problems have no LiDAR blocks
   so.probs = ctx->st_noblocks.p;
   so.n_prob = n_sets;
@@ -2441,10 +2355,10 @@ int stereo_sums_impl(lslam_ctx *ctx, int32_t n_sets, const float *poses, double 
   so.partials2 = ctx->st_partials.p;
   so.probs2 = ctx->st_probs.p;
   HIP_TRY(launch_solve(so, ctx->stream));
-  HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState) * (size_t)n_sets, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState) * (size_t)n_sets, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   for (int32_t p = 0; p < n_sets; ++p)
-    for (int i = 0; i < NCOL; ++i) sums32[(size_t)p * NCOL + i] = ctx->h_state[p].sums[i];
+    for (int i = 0; i < NCOL; ++i) sums32[(size_t)p * NCOL + i] = ctx->h_state.p[p].sums[i];
   return LSLAM_OK;
 }
 }  // namespace
@@ -2619,18 +2533,18 @@ int lslam::odometry_match_trees(lslam_ctx *ctx, const void *last_corner, size_t 
   oa.ind = d_ind.p;
   oa.sel = d_sel.p;
   oa.mode = 0;
-  oa.state = ctx->d_state;
+  oa.state = ctx->d_state.p;
   HIP_TRY(ctx->partials.reserve((size_t)(oa.nb_total ? oa.nb_total : 1) * NCOL));
   oa.partials = ctx->partials.p;
   ProbBlocks pb{0, oa.nb_total};
   HIP_TRY(ctx->probs.reserve(1));
   HIP_TRY(hipMemcpyAsync(ctx->probs.p, &pb, sizeof(pb), hipMemcpyHostToDevice, ctx->stream));
-  init_state(*ctx->h_state, pose);
+  init_state(*ctx->h_state.p, pose);
   const int max_it = max_iterations < 0 ? 0 : max_iterations;
-  if (max_it == 0 || oa.nb_total == 0) ctx->h_state->done = 1;
-  HIP_TRY(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
+  if (max_it == 0 || oa.nb_total == 0) ctx->h_state.p->done = 1;
+  HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
   SolveArgs so{};
-  so.states = ctx->d_state;
+  so.states = ctx->d_state.p;
   so.partials = ctx->partials.p;
   so.probs = ctx->probs.p;
   so.n_prob = 1;
@@ -2670,13 +2584,13 @@ int lslam::odometry_match_trees(lslam_ctx *ctx, const void *last_corner, size_t 
     }
     launched += batch;
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->h_state->done || launched >= max_it) break;
+    if (ctx->h_state.p->done || launched >= max_it) break;
     batch = 5;
   }
-  ctx->od_iter_hint = ctx->h_state->loop_iter + 1;
-  const GNState &g = *ctx->h_state;
+  ctx->od_iter_hint = ctx->h_state.p->loop_iter + 1;
+  const GNState &g = *ctx->h_state.p;
   for (int i = 0; i < 6; ++i) pose[i] = g.pose[i];
   st.iterations = g.iter;
   st.sweeps = g.sweeps;
@@ -2927,8 +2841,8 @@ int lslam_sweep_ex(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, int32_
   if (!pose) { set_err("null pose"); return LSLAM_ERR_INVALID; }
   if (ctx->n_prob != 1) { set_err("lslam_sweep is a single-scan tap"); return LSLAM_ERR_INVALID; }
   const size_t N = ctx->n_points;
-  init_state(*ctx->h_state, pose);
-  HIP_TRY(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
+  init_state(*ctx->h_state.p, pose);
+  HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
   SweepArgs sa;
   fill_sweep_args(ctx, sa);
   rc = ensure_stack_ovf(ctx, (size_t)sa.nb_total * SWEEP_BLOCK, &sa.stack_ovf);
@@ -2996,13 +2910,13 @@ int lslam_sweep_ex(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, int32_
   }
   HIP_TRY(sweep_launch(ctx, sa, jtj_mode));
   SolveArgs so{};
-  so.states = ctx->d_state;
+  so.states = ctx->d_state.p;
   so.partials = ctx->partials.p;
   so.probs = ctx->probs.p;
   so.n_prob = 1;
   so.reduce_only = 1;
   HIP_TRY(launch_solve(so, ctx->stream));
-  HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
   if (N) {
     if (idx_out) HIP_TRY(hipMemcpyAsync(idx_out, ctx->t_idx.p, N * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (d2_out) HIP_TRY(hipMemcpyAsync(d2_out, ctx->t_d2.p, N * 5 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -3011,7 +2925,7 @@ int lslam_sweep_ex(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, int32_
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (sums_out) {
-    const GNState &g = *ctx->h_state;
+    const GNState &g = *ctx->h_state.p;
     for (int i = 0; i < 27; ++i) sums_out[i] = (float)g.sums[i];
     sums_out[27] = (float)g.sums[COL_ROWS];
     sums_out[28] = (float)(g.sums[COL_LINE] + g.sums[COL_PLANE]);
@@ -3027,23 +2941,23 @@ int lslam_gn_step(lslam_ctx *ctx, const float AtA[36], const float Atb[6], int32
   int rc = check_ctx(ctx);
   if (rc) return rc;
   if (!AtA || !Atb || !pose || !matP || !degenerate) { set_err("null argument"); return LSLAM_ERR_INVALID; }
-  init_state(*ctx->h_state, pose);
-  ctx->h_state->iter = iter;
-  ctx->h_state->loop_iter = iter;
-  ctx->h_state->degenerate = *degenerate;
-  std::memcpy(ctx->h_state->matP, matP, sizeof(float) * 36);
+  init_state(*ctx->h_state.p, pose);
+  ctx->h_state.p->iter = iter;
+  ctx->h_state.p->loop_iter = iter;
+  ctx->h_state.p->degenerate = *degenerate;
+  std::memcpy(ctx->h_state.p->matP, matP, sizeof(float) * 36);
   HIP_TRY(ctx->t_small.reserve(64));
   float tmp[42];
   std::memcpy(tmp, AtA, sizeof(float) * 36);
   std::memcpy(tmp + 36, Atb, sizeof(float) * 6);
   HIP_TRY(hipMemcpyAsync(ctx->t_small.p, tmp, sizeof(tmp), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));  // tmp is a local
-  HIP_TRY(launch_gn_step_tap(ctx->d_state, ctx->t_small.p, ctx->t_small.p + 36, delta_r_abort,
+  HIP_TRY(launch_gn_step_tap(ctx->d_state.p, ctx->t_small.p, ctx->t_small.p + 36, delta_r_abort,
                              delta_t_abort, 100.0f, ctx->stream));
-  HIP_TRY(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  const GNState &g = *ctx->h_state;
+  const GNState &g = *ctx->h_state.p;
   for (int i = 0; i < 6; ++i) pose[i] = g.pose[i];
   std::memcpy(matP, g.matP, sizeof(float) * 36);
   *degenerate = g.degenerate;

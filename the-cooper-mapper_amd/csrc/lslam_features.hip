@@ -21,8 +21,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "lslam_device.hpp"
@@ -814,6 +812,16 @@ __global__ void ms_final_kernel(MsArgs a) {
   a.out[i] = make_float4(p.y, p.z, p.x, __fadd_rn((float)ring, rel));
 }
 
+// what the two entry points keep in their context between calls (lslam::ctx_slot); each blob is carved into the call's arrays
+struct FxCache {  // extract_features_impl
+  lslam::DevBuf<char> blob;
+  lslam::PinBuf<float4> pin, pout;
+};
+struct MsCache {  // lslam_multiscan_register
+  lslam::DevBuf<char> blob;
+  lslam::PinBuf<float4> pin;
+};
+
 }  // namespace
 
 extern "C" {
@@ -912,37 +920,15 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
   if (n_points == 0) return LSLAM_OK;
   FX_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = (hipStream_t)lslam_stream(ctx);
-  // device scratch and the pinned staging area of the input are kept per device between calls (a
-  // sweep arrives every 100 ms)
-  struct Cache { char *p = nullptr; size_t cap = 0; float4 *pin = nullptr; size_t pin_cap = 0; float4 *pout = nullptr; size_t pout_cap = 0; };
-  static std::map<hipStream_t, Cache> caches;  // per stream = per context: contexts of one device run on their own threads
-  static std::mutex mu;
-  Cache *cache_p;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    cache_p = &caches[s];
-  }
-  Cache &cache = *cache_p;
+  // device scratch and the pinned staging areas are the context's, kept between calls (a sweep arrives every 100 ms); the
+  // outputs are WRITTEN to pinned memory by the kernels that make them: sixteen header slots (totals, error), then a slice of
+  // n_points per list
+  FxCache &cache = *lslam::ctx_slot<FxCache>(ctx, lslam::CTX_SLOT_FEATURES);
   const size_t np4 = n_points * sizeof(float4);
-  if (n_points > cache.pin_cap) {
-    if (cache.pin) (void)hipHostFree(cache.pin);
-    cache.pin = nullptr;
-    cache.pin_cap = 0;
-    FX_TRY(hipHostMalloc((void **)&cache.pin, (n_points + n_points / 4) * sizeof(float4), hipHostMallocDefault));
-    cache.pin_cap = n_points + n_points / 4;
-  }
-  // the outputs are WRITTEN to pinned memory by the kernels that make them: sixteen header slots (totals, error), then a
-  // slice of n_points per list
-  if (4 * n_points + 16 > cache.pout_cap) {
-    if (cache.pout) (void)hipHostFree(cache.pout);
-    cache.pout = nullptr;
-    cache.pout_cap = 0;
-    const size_t want = 4 * (n_points + n_points / 4) + 16;
-    FX_TRY(hipHostMalloc((void **)&cache.pout, want * sizeof(float4), hipHostMallocDefault));
-    cache.pout_cap = want;
-  }
+  FX_TRY(cache.pin.reserve(n_points));
+  FX_TRY(cache.pout.reserve(4 * n_points + 16));
   // pack {x, y, z, intensity-to-copy} (toXYZI, util/pcl_util.h:30-37: the `curvature` field)
-  float4 *h = cache.pin;
+  float4 *h = cache.pin.p;
   const char *src = static_cast<const char *>(cloud);
   bool uploaded = false;
   if (stride_bytes == 16 && intensity_offset_bytes == 12) {
@@ -959,14 +945,8 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
   }
   const size_t bytes = 5 * np4 + 2 * n_scans * 4 + 4 * n_scans * 4 + n_points * 4 + 2 * n_points + (n_scans + 1) * 4 + np4 + n_points * 4 +
                        n_scans * 4 + 256 + 18 * 16;
-  if (bytes > cache.cap) {
-    if (cache.p) (void)hipFree(cache.p);
-    cache.p = nullptr;
-    cache.cap = 0;
-    FX_TRY(hipMalloc((void **)&cache.p, bytes + bytes / 4));
-    cache.cap = bytes + bytes / 4;
-  }
-  char *blob = cache.p;
+  FX_TRY(cache.blob.reserve(bytes));
+  char *blob = cache.blob.p;
   char *q = blob;
   auto take = [&](size_t b) { char *r = q; q += (b + 15) & ~(size_t)15; return r; };
   float4 *d_pts = (float4 *)take(np4);
@@ -1019,11 +999,11 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
   if (a.helpers > 0) FX_TRY2(hipMemsetAsync(d_ready, 0, n_scans * 4, s));
   hipLaunchKernelGGL(fx_ring_kernel, dim3((unsigned)n_scans * (unsigned)(1 + a.helpers)), dim3(FX_BLOCK), 0, s, a);
   // the four lists, on the device to the end (see fx_lists_block): nothing waits until everything is in pinned memory
-  uint32_t *hdr = reinterpret_cast<uint32_t *>(cache.pout);
+  uint32_t *hdr = reinterpret_cast<uint32_t *>(cache.pout.p);
   for (int k = 0; k < 8; ++k) hdr[k] = 0u;
   if (dev_out) {  // ... or in the feature set's slices in HBM: only the eight header words come back
     FX_TRY2(lslam::fset_reserve(dev_out, n_points));
-    FX_TRY2(hipMemsetAsync(dev_out->buf, 0, 8 * sizeof(uint32_t), s));
+    FX_TRY2(hipMemsetAsync(dev_out->buf.p, 0, 8 * sizeof(uint32_t), s));
   }
   FxOutArgs oa{};
   oa.pts = d_pts;
@@ -1035,8 +1015,8 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
   oa.inv_leaf = 1.0f / prm.less_flat_filter_size;
   oa.vox_stage = d_vox;
   oa.ring_out = d_ring_out;
-  oa.host = dev_out ? dev_out->buf : cache.pout;
-  oa.hdr = dev_out ? reinterpret_cast<uint32_t *>(dev_out->buf) : hdr;
+  oa.host = dev_out ? dev_out->buf.p : cache.pout.p;
+  oa.hdr = dev_out ? reinterpret_cast<uint32_t *>(dev_out->buf.p) : hdr;
   if (dev_out) oa.cap = (int32_t)dev_out->cap;
   hipLaunchKernelGGL(fx_ring_voxel_kernel, dim3((unsigned)n_scans + 3u), dim3(FX_BLOCK), 0, s, oa);
   hipLaunchKernelGGL(fx_lessflat_out_kernel, dim3((unsigned)n_scans), dim3(FX_BLOCK), 0, s, oa);
@@ -1044,7 +1024,7 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
   if (curvature_out) FX_TRY2(hipMemcpyAsync(curvature_out, d_curv, n_points * 4, hipMemcpyDeviceToHost, s));
   if (picked_out) FX_TRY2(hipMemcpyAsync(picked_out, d_picked, n_points, hipMemcpyDeviceToHost, s));
   if (label_out) FX_TRY2(hipMemcpyAsync(label_out, d_label, n_points, hipMemcpyDeviceToHost, s));
-  if (dev_out) FX_TRY2(hipMemcpyAsync(hdr, dev_out->buf, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (dev_out) FX_TRY2(hipMemcpyAsync(hdr, dev_out->buf.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   FX_TRY2(hipStreamSynchronize(s));
   if (hdr[4]) {
     lslam::set_error(hdr[4] == 1u ? "voxel index outside its range (non-finite point?)" : "a feature list overflowed its staging slice");
@@ -1054,7 +1034,7 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
   for (int k = 0; k < 4; ++k) {
     counts[k] = (size_t)hdr[k];
     if (dev_out) dev_out->counts[k] = counts[k];
-    if (!dev_out && outs[k] && hdr[k]) std::memcpy(outs[k], cache.pout + 16 + (size_t)k * n_points, (size_t)hdr[k] * sizeof(float4));
+    if (!dev_out && outs[k] && hdr[k]) std::memcpy(outs[k], cache.pout.p + 16 + (size_t)k * n_points, (size_t)hdr[k] * sizeof(float4));
   }
   return rc;
 }
@@ -1073,24 +1053,10 @@ int lslam_multiscan_register(lslam_ctx *ctx, const void *cloud, size_t n_points,
   if (n_points == 0) return LSLAM_OK;
   FX_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = (hipStream_t)lslam_stream(ctx);
-  struct Cache { char *p = nullptr; size_t cap = 0; float4 *pin = nullptr; size_t pin_cap = 0; };
-  static std::map<hipStream_t, Cache> caches;  // device scratch + pinned input staging kept per stream (= context) between sweeps
-  static std::mutex mu;
-  Cache *cache_p;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    cache_p = &caches[s];
-  }
-  Cache &cache = *cache_p;
+  MsCache &cache = *lslam::ctx_slot<MsCache>(ctx, lslam::CTX_SLOT_MULTISCAN);
   const size_t np4 = n_points * sizeof(float4);
-  if (n_points > cache.pin_cap) {
-    if (cache.pin) (void)hipHostFree(cache.pin);
-    cache.pin = nullptr;
-    cache.pin_cap = 0;
-    FX_TRY(hipHostMalloc((void **)&cache.pin, (n_points + n_points / 4) * sizeof(float4), hipHostMallocDefault));
-    cache.pin_cap = n_points + n_points / 4;
-  }
-  float4 *h = cache.pin;
+  FX_TRY(cache.pin.reserve(n_points));
+  float4 *h = cache.pin.p;
   const char *src = static_cast<const char *>(cloud);
   for (size_t i = 0; i < n_points; ++i) {
     float v[3];
@@ -1103,14 +1069,8 @@ int lslam_multiscan_register(lslam_ctx *ctx, const void *cloud, size_t n_points,
   if (end_ori - start_ori > 3 * M_PI) end_ori -= 2 * M_PI;
   else if (end_ori - start_ori < M_PI) end_ori += 2 * M_PI;
   const size_t bytes = 3 * np4 + 4 * n_points * 4 + 64;
-  if (bytes > cache.cap) {
-    if (cache.p) (void)hipFree(cache.p);
-    cache.p = nullptr;
-    cache.cap = 0;
-    FX_TRY(hipMalloc((void **)&cache.p, bytes + bytes / 4));
-    cache.cap = bytes + bytes / 4;
-  }
-  char *blob = cache.p;
+  FX_TRY(cache.blob.reserve(bytes));
+  char *blob = cache.blob.p;
   float4 *d_in = (float4 *)blob, *d_tmp = d_in + n_points, *d_out = d_tmp + n_points;
   int32_t *d_ring = (int32_t *)(d_out + n_points), *d_seg = d_ring + n_points;
   float *d_ori = (float *)(d_seg + n_points);
@@ -1136,7 +1096,7 @@ int lslam_multiscan_register(lslam_ctx *ctx, const void *cloud, size_t n_points,
   hipLaunchKernelGGL(ms_prep_kernel, grd, blk, 0, s, a);
   hipLaunchKernelGGL(ms_final_kernel, grd, blk, 0, s, a);
   size_t m = 0;  // per-ring clouds in arrival order (:178-190): a stable grouping by ring
-  int rc = lslam::voxel_filter_segments(s, d_tmp, d_ring, n_points, n_rings, 1.0f, d_out, d_seg, &m, false);
+  int rc = lslam::voxel_filter_segments(ctx, d_tmp, d_ring, n_points, n_rings, 1.0f, d_out, d_seg, &m, false);
   if (rc) return fail(rc);
   if (m > cap && out_xyzc) {
     lslam::set_error("registration output buffer too small");

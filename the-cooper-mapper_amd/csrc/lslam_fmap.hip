@@ -32,8 +32,6 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
-#include <map>
-#include <mutex>
 #include <sstream>
 #include <string>
 #include <chrono>
@@ -54,65 +52,8 @@ namespace {
     }                                                                                    \
   } while (0)
 
-template <typename T>
-struct Buf {
-  T *p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = n + n / 4 + 256;
-    hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  // grow, keeping the first `keep` elements
-  hipError_t grow(size_t n, size_t keep, hipStream_t s) {
-    if (n <= cap) return hipSuccess;
-    const size_t want = n + n / 4 + 256;
-    T *q = nullptr;
-    hipError_t e = hipMalloc((void **)&q, want * sizeof(T));
-    if (e != hipSuccess) return e;
-    if (keep && p) {
-      e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-// a pinned host block that lives as long as its owner: asynchronous copies to and from it need no wait to keep their host side
-// alive (a std::vector local does), and they run at the link's rate instead of through the runtime's staging
-template <typename T>
-struct Pin {
-  T *p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = n + n / 4 + 256;
-    hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
+using lslam::DevBuf;
+using lslam::PinBuf;
 
 constexpr uint64_t KEY_DROP = ~0ull;
 constexpr size_t MERGE_LIMIT = 1024 * 1024;  // rocprim::radix_sort_config<>::merge_sort_limit
@@ -599,16 +540,12 @@ int bits_for(double cells) {
 }
 
 struct Scratch {
-  Buf<uint64_t> k0, k1, kn;
-  Buf<uint32_t> i0, i1, in_, pos;
-  Buf<char> tmp;
-  Buf<int32_t> err;               // [0] points out, [1] key-range error, [2] the "sorted" prefix was not, [3] widest voxel extent of a filtered cube
-  Buf<int32_t> cmin, cmax, base;  // [ncube][3]
-  Buf<uint8_t> eff;               // [ncube] cubes this rebuild really filters
-  void release() {
-    k0.release(); k1.release(); kn.release(); i0.release(); i1.release(); in_.release(); pos.release(); tmp.release();
-    err.release(); cmin.release(); cmax.release(); base.release(); eff.release();
-  }
+  DevBuf<uint64_t> k0, k1, kn;
+  DevBuf<uint32_t> i0, i1, in_, pos;
+  DevBuf<char> tmp;
+  DevBuf<int32_t> err;               // [0] points out, [1] key-range error, [2] the "sorted" prefix was not, [3] widest voxel extent of a filtered cube
+  DevBuf<int32_t> cmin, cmax, base;  // [ncube][3]
+  DevBuf<uint8_t> eff;               // [ncube] cubes this rebuild really filters
 };
 
 }  // namespace
@@ -623,34 +560,34 @@ struct lslam_fmap {
   float leaf[3] = {0.2f, 0.2f, 0.6f};  // corner, surf, map (FeatureMap.h:64-66)
   std::vector<int32_t> valid;          // _cubeValidInd
   // per type
-  Buf<float4> pts[2], pts_alt[2];
-  Buf<int32_t> cube[2], cube_alt[2];
+  DevBuf<float4> pts[2], pts_alt[2];
+  DevBuf<int32_t> cube[2], cube_alt[2];
   size_t n[2] = {0, 0};
-  Buf<uint8_t> active;                 // per cube: 1 = in the active area (_cubeValidInd)
-  Buf<int32_t> seg_begin[2];            // [begin (seg_pad words) | end (seg_pad words)] of every cube's points in pts[t]
+  DevBuf<uint8_t> active;                 // per cube: 1 = in the active area (_cubeValidInd)
+  DevBuf<int32_t> seg_begin[2];            // [begin (seg_pad words) | end (seg_pad words)] of every cube's points in pts[t]
   std::vector<int32_t> h_begin[2];      // ... on the host: seg_b / seg_e
   bool seg_current[2] = {false, false};
   bool seg_dev_current[2] = {false, false};  // ... the device's table alone (what surround_to_map needs)
-  Buf<int32_t> d_valid;                 // the active cubes (fm->valid), uploaded when they change
+  DevBuf<int32_t> d_valid;                 // the active cubes (fm->valid), uploaded when they change
   std::vector<int32_t> valid_uploaded;  // ... what the device holds (flags in `active`, list in d_valid)
   bool valid_on_device = false;
-  Buf<uint32_t> sur_res;                // [2 types][8]: points gathered, bounding box (fm_gather_box_kernel)
-  Buf<float4> in_raw, in_tf;
-  Buf<int32_t> in_cube;
+  DevBuf<uint32_t> sur_res;                // [2 types][8]: points gathered, bounding box (fm_gather_box_kernel)
+  DevBuf<float4> in_raw, in_tf;
+  DevBuf<int32_t> in_cube;
   // addFeatureCloud runs both feature types behind ONE wait: per-type staging of the new points (pinned: the upload needs no
   // wait to keep its source alive), per-type transformed points, and the rebuilds' results {points out, error} in pinned slots
-  Pin<float4> in_pin[2];
-  Buf<float4> in_raw_t[2];
-  Buf<uint8_t> d_touched_t[2];
-  Pin<uint32_t> done;       // [2 types][2]
-  Pin<uint8_t> h_touched;   // [2 types][ncube]
-  Buf<int32_t> d_remap;
-  Buf<int32_t> g_src, g_dst;
+  PinBuf<float4> in_pin[2];
+  DevBuf<float4> in_raw_t[2];
+  DevBuf<uint8_t> d_touched_t[2];
+  PinBuf<uint32_t> done;       // [2 types][2]
+  PinBuf<uint8_t> h_touched;   // [2 types][ncube]
+  DevBuf<int32_t> d_remap;
+  DevBuf<int32_t> g_src, g_dst;
   // surround gather of the two feature types behind ONE wait: per-type tables, their host copies kept alive here until the
   // next gather (a pageable hipMemcpyAsync source must outlive the copy)
-  Buf<int32_t> g_src_t[2], g_dst_t[2];
+  DevBuf<int32_t> g_src_t[2], g_dst_t[2];
   std::vector<int32_t> h_gsrc[2], h_gdst[2];
-  Buf<float4> sur[2];
+  DevBuf<float4> sur[2];
   Scratch sc;
   // addFeatureCloud's two feature types are independent chains of a dozen small launches each: the surf chain runs on the
   // context's second stream beside the corner chain (fork / join by events on the context's stream; LSLAM_FMAP_ONE_STREAM=1: one after
@@ -669,9 +606,9 @@ struct lslam_fmap {
   // Trees built together share one node / point array ("generation"); a generation is freed when none of its trees
   // is current any more.
   struct Generation {
-    Buf<lslam::KdNode> nodes;
-    Buf<lslam::PNode> pn;
-    Buf<float4> pts;
+    DevBuf<lslam::KdNode> nodes;
+    DevBuf<lslam::PNode> pn;
+    DevBuf<float4> pts;
     int live = 0, depth = 0;
   };
   struct CubeTree {
@@ -682,9 +619,9 @@ struct lslam_fmap {
   std::vector<Generation *> spare;      // dead generations kept with their allocations: no hipMalloc / hipFree per frame
   std::vector<CubeTree> cube_tree[2];   // [ncube]
   std::vector<uint8_t> dirty[2];        // [ncube]
-  Buf<uint8_t> d_touched;               // [ncube] set by the insert kernel
-  Buf<int32_t> d_cells[2];
-  Buf<lslam::TreeView> d_views[2];
+  DevBuf<uint8_t> d_touched;               // [ncube] set by the insert kernel
+  DevBuf<int32_t> d_cells[2];
+  DevBuf<lslam::TreeView> d_views[2];
   bool cube_trees_used = false;               // lslam_fmap_to_cubemap has been called: addFeatureCloud keeps the cubes' marks
   int64_t trees_built = 0, trees_reused = 0;  // statistics of the last lslam_fmap_to_cubemap
   int64_t merged_rebuilds = 0, resorted_rebuilds = 0;  // addFeatureCloud rebuilds that merged the new points in / that had to sort everything after all
@@ -985,7 +922,7 @@ int upload_active(lslam_fmap *fm) {
 
 // host cloud -> pinned staging -> dst (device), no wait: `pin` lives as long as its owner and is not written again before
 // the owner's next wait.  mn / mx (optional): the cloud's bounding box, taken in the same pass.
-int pack_input(hipStream_t s, Pin<float4> &pin, Buf<float4> &dst, const void *src, size_t n, size_t stride_bytes,
+int pack_input(hipStream_t s, PinBuf<float4> &pin, DevBuf<float4> &dst, const void *src, size_t n, size_t stride_bytes,
                float *mn = nullptr, float *mx = nullptr) {
   // {x,y,z} at offset 0; intensity at offset 12 for 16-byte points, 16 for pcl::PointXYZI (32 bytes)
   FM_TRY(pin.reserve(n));
@@ -1072,7 +1009,7 @@ int gather_surround(lslam_fmap *fm, int t, int index_in_w, size_t *n_out, int mi
   *n_out = total;
   if (!total) return LSLAM_OK;
   hipStream_t s = fm->stream;
-  Buf<int32_t> &gs = no_wait ? fm->g_src_t[t] : fm->g_src, &gd = no_wait ? fm->g_dst_t[t] : fm->g_dst;
+  DevBuf<int32_t> &gs = no_wait ? fm->g_src_t[t] : fm->g_src, &gd = no_wait ? fm->g_dst_t[t] : fm->g_dst;
   FM_TRY(gs.reserve(src.size()));
   FM_TRY(gd.reserve(dst.size()));
   FM_TRY(fm->sur[t].reserve(total));
@@ -1084,36 +1021,41 @@ int gather_surround(lslam_fmap *fm, int t, int index_in_w, size_t *n_out, int mi
   return LSLAM_OK;
 }
 
+// what the entry points below keep in their context between calls (lslam::ctx_slot)
+struct SegFilterCache {  // voxel_filter_segments
+  Scratch sc;
+  DevBuf<uint8_t> all;
+  size_t all_set = 0;  // entries of `all` that hold their 1 already
+};
+struct VoxelGridCache {  // lslam_voxel_grid: staging and scratch are kept between calls (allocation costs more than the filter itself)
+  PinBuf<float4> in_pin, out_pin;
+  PinBuf<uint32_t> done;
+  DevBuf<float4> in_raw, out;
+  DevBuf<int32_t> oc;
+  Scratch sc;
+};
+struct VoxelGrid2Cache {  // lslam_voxel_grid2
+  PinBuf<float4> in_pin, out_pin;
+  PinBuf<int32_t> seg_pin;
+  PinBuf<uint32_t> done;
+  DevBuf<float4> in_raw;
+  DevBuf<int32_t> seg;
+};
 }  // namespace
 
 namespace lslam {
 // VoxelGrid per segment for other translation units (feature extraction: one segment per scan ring):
 // in_seg[i] is the segment of point i (ascending or not), every segment is filtered with `leaf`;
-// output ordered by segment, inside a segment in VoxelGrid order.  Scratch is cached per process.
+// output ordered by segment, inside a segment in VoxelGrid order.
 // done != nullptr (pinned, two words): nothing is waited for -- the widest voxel extent is not read back (the key gets every
 // bit the 63 allow: while the sort is a merge sort its width costs nothing) and {points out, key-range error} arrive in
 // done[0..1] behind everything else on the stream; on an error the caller calls again without `done`.
-int voxel_filter_segments(hipStream_t s, const float4 *in_pts, const int32_t *in_seg, size_t n, int nseg, float leaf,
+int voxel_filter_segments(lslam_ctx *ctx, const float4 *in_pts, const int32_t *in_seg, size_t n, int nseg, float leaf,
                           float4 *out_pts, int32_t *out_seg, size_t *n_out, bool filter, uint32_t *done) {
-  struct Cache {
-    Scratch sc;
-    Buf<uint8_t> all;
-    size_t all_set = 0;  // entries of `all` that hold their 1 already
-  };
-  // Scratch per STREAM (= per context), not per device: in the no-wait form (`done`) this function returns with its kernels
-  // still running, and a caller on another context of the same device -- the registration node beside the mapping node, each
-  // on its own thread -- would otherwise be handed the same scratch while they do.  (It was: garbage segment ids, a host
-  // segfault in the registration, "output buffer too small" in the map, found by tools/cpp/node_threads.cpp.)  Work on ONE
-  // stream is ordered by the stream.  The lock covers the table of caches only; a map's nodes do not move.
-  static std::map<hipStream_t, Cache> caches;
-  static std::mutex mu;
-  Cache *cache_p;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    cache_p = &caches[s];
-  }
+  hipStream_t s = ctx_stream(ctx);
+  SegFilterCache *cache_p = ctx_slot<SegFilterCache>(ctx, CTX_SLOT_SEG_FILTER);  // the scratch belongs to the context
   Scratch &sc = cache_p->sc;
-  Buf<uint8_t> &all = cache_p->all;
+  DevBuf<uint8_t> &all = cache_p->all;
   size_t &all_set = cache_p->all_set;
   {  // "every segment is filtered": ones, written when the array grows -- not once per call
     const uint8_t *before = all.p;
@@ -1121,7 +1063,7 @@ int voxel_filter_segments(hipStream_t s, const float4 *in_pts, const int32_t *in
     if (all.p != before) all_set = 0;
     if (all_set < (size_t)nseg) {
       FM_TRY(hipMemsetAsync(all.p, 1, all.cap, s));
-      FM_TRY(hipStreamSynchronize(s));  // (once per growth; the array is shared by the contexts of a device, whatever their streams)
+      FM_TRY(hipStreamSynchronize(s));  // (once per growth)
       all_set = all.cap;
     }
   }
@@ -1152,15 +1094,10 @@ int voxel_filter_segments(hipStream_t s, const float4 *in_pts, const int32_t *in
 // in_pts (device memory of `w`, valid until its next call) -- the caller permutes its points by it to keep them in order.
 struct WindowFilter {
   Scratch sc;
-  Buf<int32_t> oc;
+  DevBuf<int32_t> oc;
 };
 WindowFilter *window_filter_create() { return new WindowFilter(); }
-void window_filter_destroy(WindowFilter *w) {
-  if (!w) return;
-  w->sc.release();
-  w->oc.release();
-  delete w;
-}
+void window_filter_destroy(WindowFilter *w) { delete w; }
 int voxel_filter_window(hipStream_t s, WindowFilter *w, const float4 *in_pts, size_t n_sorted, size_t n_total, float leaf,
                         const int32_t base0[3], int axis_bits, float4 *out_pts, uint32_t *done, const uint32_t **order) {
   KeyParams kp{};
@@ -1209,28 +1146,9 @@ void lslam_fmap_destroy(lslam_fmap *fm) {
     (void)hipSetDevice(lslam::ctx_device(fm->ctx));
     (void)hipStreamSynchronize(fm->stream);
   }
-  for (int t = 0; t < 2; ++t) {
-    fm->pts[t].release(); fm->pts_alt[t].release(); fm->cube[t].release(); fm->cube_alt[t].release();
-    fm->seg_begin[t].release(); fm->sur[t].release();
-  }
-  for (lslam_fmap::Generation *g : fm->gens)
-    if (g) { g->nodes.release(); g->pn.release(); g->pts.release(); delete g; }
-  fm->gens.clear();
-  for (lslam_fmap::Generation *g : fm->spare) { g->nodes.release(); g->pn.release(); g->pts.release(); delete g; }
-  fm->spare.clear();
-  fm->d_touched.release();
+  for (lslam_fmap::Generation *g : fm->gens) delete g;
+  for (lslam_fmap::Generation *g : fm->spare) delete g;
   if (lslam::ctx_alive(fm->ctx)) lslam::cubemap_drop_views(fm->ctx);  // the context may still point at this map's trees
-  fm->active.release(); fm->in_raw.release(); fm->in_tf.release(); fm->in_cube.release();
-  fm->d_remap.release(); fm->g_src.release(); fm->g_dst.release();
-  for (int t = 0; t < 2; ++t) {
-    fm->g_src_t[t].release(); fm->g_dst_t[t].release();
-    fm->d_valid.release(); fm->sur_res.release();
-    fm->in_pin[t].release(); fm->in_raw_t[t].release();
-    fm->d_touched_t[t].release();
-  }
-  fm->done.release(); fm->h_touched.release();
-  fm->sc.release();
-  fm->sc2.release();
   if (fm->stream2 && lslam::ctx_alive(fm->ctx)) (void)hipStreamSynchronize(fm->stream2);  // (the context's: not ours to destroy)
   if (fm->ev_fork) (void)hipEventDestroy(fm->ev_fork);
   if (fm->ev_join) (void)hipEventDestroy(fm->ev_join);
@@ -1659,8 +1577,8 @@ int lslam_fmap_to_cubemap(lslam_fmap *fm) {
       const size_t cap = ((mult[attempt] * total / 3 + 64 + 8 * (size_t)T) + 7) & ~(size_t)7;
       FM_TRY(g->nodes.reserve(cap));
       if (attempt > first_attempt) FM_TRY(gather());  // the failed attempt permuted the points: gather them again
-      FM_TRY(lslam::build_kdforest_device(g->pts.p, (int32_t)total, roots_lr.data(), T, g->nodes.p, nullptr, (int32_t)cap, s,
-                                          built.data(), &max_depth, &n_leaves, &fallback));
+      FM_TRY(lslam::build_kdforest_device(lslam::ctx_build_pool(fm->ctx, 0), g->pts.p, (int32_t)total, roots_lr.data(), T, g->nodes.p, nullptr,
+                                          (int32_t)cap, s, built.data(), &max_depth, &n_leaves, &fallback));
       if (fallback != 1) {
         fm->forest_attempt0 = attempt;
         break;
@@ -1692,7 +1610,6 @@ int lslam_fmap_to_cubemap(lslam_fmap *fm) {
       if (fm->spare.size() < 8) {
         fm->spare.push_back(g);
       } else {
-        g->nodes.release(); g->pn.release(); g->pts.release();
         delete g;
       }
       gens[k] = nullptr;
@@ -1751,7 +1668,7 @@ int lslam_fmap_get_full_map(lslam_fmap *fm, float *out_xyzi, size_t cap, size_t 
   hipStream_t s = fm->stream;
   std::vector<float4> h[2];
   std::vector<int32_t> hc[2];
-  Buf<uint8_t> force;
+  DevBuf<uint8_t> force;
   FM_TRY(force.reserve(fm->ncube));
   FM_TRY(hipMemsetAsync(force.p, 1, fm->ncube, s));  // filter every cube
   for (int t = 0; t < 2; ++t) {
@@ -1763,7 +1680,7 @@ int lslam_fmap_get_full_map(lslam_fmap *fm, float *out_xyzi, size_t cap, size_t 
     size_t m = 0;
     rc = run_pipeline(s, fm->sc, fm->pts[t].p, fm->cube[t].p, n, kp, fm->ncube, force.p, fm->pts_alt[t].p,
                       fm->cube_alt[t].p, &m);
-    if (rc) { force.release(); return rc; }
+    if (rc) return rc;
     h[t].resize(m);
     hc[t].resize(m);
     if (m) {
@@ -1772,7 +1689,6 @@ int lslam_fmap_get_full_map(lslam_fmap *fm, float *out_xyzi, size_t cap, size_t 
     }
     FM_TRY(hipStreamSynchronize(s));
   }
-  force.release();
   const size_t total = h[0].size() + h[1].size();
   if (n_out) *n_out = total;
   if (!out_xyzi) return LSLAM_OK;
@@ -1935,7 +1851,7 @@ int lslam_fmap_load(lslam_fmap *fm, const char *directory) {
     cube[type].insert(cube[type].end(), cl.size(), c);
   }
   hipStream_t s = fm->stream;
-  Buf<uint8_t> d_flags;
+  DevBuf<uint8_t> d_flags;
   FM_TRY(d_flags.reserve(fm->ncube));
   for (int t = 0; t < 2 && rc == LSLAM_OK; ++t) {
     const size_t n = pts[t].size();
@@ -1955,7 +1871,6 @@ int lslam_fmap_load(lslam_fmap *fm, const char *directory) {
     rc = rebuild(fm, t, n, true, d_flags.p);
     if (rc == LSLAM_OK && hipStreamSynchronize(s) != hipSuccess) rc = LSLAM_ERR_HIP;
   }
-  d_flags.release();
   if (rc == LSLAM_ERR_HIP) lslam::set_error("HIP error while loading cube files");
   return rc;
 }
@@ -1979,24 +1894,9 @@ static int voxel_grid_impl(lslam_ctx *ctx, const void *cloud, size_t n, size_t s
   if (n == 0) return LSLAM_OK;
   FM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = (hipStream_t)lslam_stream(ctx);
-  // staging and scratch are kept between calls (allocation costs more than the filter itself)
-  struct Cache {
-    Pin<float4> in_pin, out_pin;
-    Pin<uint32_t> done;
-    Buf<float4> in_raw, out;
-    Buf<int32_t> oc;
-    Scratch sc;
-  };
-  static std::map<hipStream_t, Cache> caches;  // per stream = per context (see voxel_filter_segments)
-  static std::mutex mu;
-  Cache *cache_p;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    cache_p = &caches[s];
-  }
-  Cache &cache = *cache_p;
-  Buf<float4> &out = cache.out;
-  Buf<int32_t> &oc = cache.oc;
+  VoxelGridCache &cache = *lslam::ctx_slot<VoxelGridCache>(ctx, lslam::CTX_SLOT_VOXEL_GRID);
+  DevBuf<float4> &out = cache.out;
+  DevBuf<int32_t> &oc = cache.oc;
   Scratch &sc = cache.sc;
   // upload from pinned staging (no wait), min/max on the host in the same pass (VoxelGrid::applyFilter: getMinMax3D)
   const float inv = 1.0f / leaf;
@@ -2079,21 +1979,7 @@ static int voxel_grid2_impl(lslam_ctx *ctx, const void *a, size_t na, const void
   if (n == 0) return LSLAM_OK;
   FM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = (hipStream_t)lslam_stream(ctx);
-  struct Cache {
-    Pin<float4> in_pin, out_pin;
-    Pin<int32_t> seg_pin;
-    Pin<uint32_t> done;
-    Buf<float4> in_raw;
-    Buf<int32_t> seg;
-  };
-  static std::map<hipStream_t, Cache> caches;  // per stream = per context (see voxel_filter_segments)
-  static std::mutex mu;
-  Cache *cache_p;
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    cache_p = &caches[(hipStream_t)lslam_stream(ctx)];
-  }
-  Cache &c = *cache_p;
+  VoxelGrid2Cache &c = *lslam::ctx_slot<VoxelGrid2Cache>(ctx, lslam::CTX_SLOT_VOXEL_GRID2);
   FM_TRY(c.in_pin.reserve(n));
   FM_TRY(c.out_pin.reserve(n));
   FM_TRY(c.seg_pin.reserve(n));
@@ -2125,11 +2011,11 @@ static int voxel_grid2_impl(lslam_ctx *ctx, const void *a, size_t na, const void
   size_t m = 0;
   // the centroids and their segments are WRITTEN to pinned memory by the kernel that makes them (the m of them: the count is
   // not known on the host yet -- the copies this replaces moved all n slots, 0.8 MB for a sweep's 42 k points)
-  int rc = lslam::voxel_filter_segments(s, c.in_raw.p, c.seg.p, n, 2, leaf, c.out_pin.p, c.seg_pin.p, &m, true, c.done.p);
+  int rc = lslam::voxel_filter_segments(ctx, c.in_raw.p, c.seg.p, n, 2, leaf, c.out_pin.p, c.seg_pin.p, &m, true, c.done.p);
   if (rc) return rc;
   FM_TRY(hipStreamSynchronize(s));
   if (c.done.p[1]) {  // the wide key did not hold an extent: once more with the measured one (waits inside)
-    rc = lslam::voxel_filter_segments(s, c.in_raw.p, c.seg.p, n, 2, leaf, c.out_pin.p, c.seg_pin.p, &m, true, nullptr);
+    rc = lslam::voxel_filter_segments(ctx, c.in_raw.p, c.seg.p, n, 2, leaf, c.out_pin.p, c.seg_pin.p, &m, true, nullptr);
     if (rc) return rc;
     FM_TRY(hipStreamSynchronize(s));
   } else {

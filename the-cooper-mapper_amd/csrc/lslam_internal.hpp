@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "lslam_buf.hpp"
 #include "lslam_device.hpp"
 #include "lslam_grid.hpp"
 
@@ -371,15 +372,20 @@ hipError_t launch_gn_step_tap(GNState *st, const float *AtA, const float *Atb, f
 // device kd-tree builder (lslam_treebuild.hip): same tree, built in HBM
 // d_own_box (node_cap x 6 floats, or null): the tight box of every inner node's points, from which build_packet_nodes makes
 // the packet search's nodes when that search is asked for
-hipError_t build_kdtree_device(float4 *d_pts, int32_t n, KdNode *d_nodes, float *d_own_box, int32_t node_cap,
+// Scratch of a build, kept between builds (hipMalloc / hipFree of tens of MB per call cost more than a millisecond).  A
+// context owns one per stream (ctx_build_pool): its worker thread builds the corner tree on stream2 beside the surf tree.
+struct BuildPool {
+  DevBuf<char> blob, lv;
+  DevBuf<float> part;
+};
+hipError_t build_kdtree_device(BuildPool &pool, float4 *d_pts, int32_t n, KdNode *d_nodes, float *d_own_box, int32_t node_cap,
                                hipStream_t stream, TreeView *view, int *depth, size_t *n_leaves,
                                int *fallback);
 
 hipError_t build_packet_nodes(const TreeView &view, const float *d_own_box, PNode *d_pn, hipStream_t stream);
-hipError_t build_kdforest_device(float4 *d_pts, int32_t n_total, const int32_t *roots_lr, int T, KdNode *d_nodes,
+hipError_t build_kdforest_device(BuildPool &pool, float4 *d_pts, int32_t n_total, const int32_t *roots_lr, int T, KdNode *d_nodes,
                                  PNode *d_pn, int32_t node_cap, hipStream_t stream, TreeView *views, int *max_depth,
                                  size_t *n_leaves, int *fallback);
-void treebuild_release_scratch(hipStream_t s);  // frees the per-stream build scratch
 
 // lslam_api.hip internals used by lslam_fmap.hip (map maintenance)
 }  // namespace lslam
@@ -389,12 +395,11 @@ struct lslam_comm;
 // [0..3] the lists' sizes, [4] error), then four slices of `cap` points {x, y, z, intensity} -- sharp, less-sharp, flat, less-flat.
 struct lslam_fset {
   int device = 0;
-  float4 *buf = nullptr;
+  lslam::DevBuf<float4> buf;
   size_t cap = 0;  // points per slice
   size_t counts[4] = {0, 0, 0, 0};
-  float4 *h_stage = nullptr;  // page-locked staging of lslam_fset_upload (grow-only)
-  size_t h_stage_cap = 0;
-  float4 *list(int k) const { return buf + 16 + (size_t)k * cap; }
+  lslam::PinBuf<float4> h_stage;  // staging of lslam_fset_upload
+  float4 *list(int k) const { return buf.p + 16 + (size_t)k * cap; }
 };
 namespace lslam {
 hipError_t fset_reserve(lslam_fset *fs, size_t points_per_list);  // lslam_odom.hip: grows (contents are lost)
@@ -418,9 +423,6 @@ int cubemap_set_views(lslam_ctx *ctx, const std::vector<TreeView> &views_c, cons
                       float cube_size, const int32_t origin[3], const int32_t dims[3]);
 void cubemap_drop_views(lslam_ctx *ctx);  // the owner of such trees goes away
 void set_error(const char *msg);
-// lslam_odom.hip
-void odom_ctx_gone(lslam_ctx *ctx);
-
 // small accessors for translation units that work on a context (lslam_icp.hip)
 hipStream_t ctx_stream(lslam_ctx *ctx);
 hipStream_t ctx_stream2(lslam_ctx *ctx);  // made on first use; nullptr on failure
@@ -430,6 +432,34 @@ int ctx_scratch(lslam_ctx *ctx, size_t n_float4, size_t n_double, float4 **pts, 
 int ctx_stack_ovf_if_deep(lslam_ctx *ctx, size_t n_threads, uint32_t **out);  // null unless a tree is deeper than the LDS stack
 int ctx_device(const lslam_ctx *ctx);
 bool ctx_alive(const lslam_ctx *ctx);
+BuildPool &ctx_build_pool(lslam_ctx *ctx, int which);  // the tree build's scratch of `stream` (0) / `stream2` (1)
+
+// Scratch another translation unit keeps in a context: one typed object per slot, made on first use, deleted by
+// lslam_ctx_destroy (after the context's streams have been waited for).  A context is used by one thread at a time: no lock.
+enum CtxSlot : int {
+  CTX_SLOT_FEATURES,      // lslam_features.hip: extract_features_impl
+  CTX_SLOT_MULTISCAN,     // lslam_features.hip: lslam_multiscan_register
+  CTX_SLOT_SEG_FILTER,    // lslam_fmap.hip: voxel_filter_segments
+  CTX_SLOT_VOXEL_GRID,    // lslam_fmap.hip: lslam_voxel_grid
+  CTX_SLOT_VOXEL_GRID2,   // lslam_fmap.hip: lslam_voxel_grid2
+  CTX_SLOT_ODOM,          // lslam_odom.hip: the hidden node of lslam_odometry_match
+  CTX_SLOT_SCANPREP,      // lslam_scanprep.hip
+  CTX_N_SLOTS
+};
+struct CtxSlotEntry {
+  void *obj = nullptr;
+  void (*drop)(void *) = nullptr;
+};
+CtxSlotEntry &ctx_slot_entry(lslam_ctx *ctx, CtxSlot which);
+template <class T>
+T *ctx_slot(lslam_ctx *ctx, CtxSlot which) {
+  CtxSlotEntry &e = ctx_slot_entry(ctx, which);
+  if (!e.obj) {
+    e.obj = new T();
+    e.drop = [](void *p) { delete static_cast<T *>(p); };
+  }
+  return static_cast<T *>(e.obj);
+}
 
 // The process environment, read ONCE: when the first context (or pose graph) is created.  No entry point reads the
 // environment while it runs -- another thread's setenv would race with it.  A/B switches of measurements and the values tests
@@ -457,7 +487,7 @@ const EnvOnce &env_once();
 const char *debug_env(const char *name);  // nullptr unless the process runs with LSLAM_DEBUG_HOOKS=1 and `name` is set
 
 // lslam_fmap.hip: pcl::VoxelGrid per segment (see there)
-int voxel_filter_segments(hipStream_t s, const float4 *in_pts, const int32_t *in_seg, size_t n, int nseg, float leaf,
+int voxel_filter_segments(lslam_ctx *ctx, const float4 *in_pts, const int32_t *in_seg, size_t n, int nseg, float leaf,
                           float4 *out_pts, int32_t *out_seg, size_t *n_out, bool filter = true, uint32_t *done = nullptr);
 
 // lslam_fmap.hip: pcl::VoxelGrid of a window whose owner keeps its points in voxel-key order (see there)
@@ -477,9 +507,5 @@ hipError_t small_sort_pairs(hipStream_t s, const uint64_t *k_in, uint64_t *k_out
                             void *tmp);
 
 // lslam_scanprep.hip: Morton ordering of the resident scans on the device
-struct ScanPrep;
-ScanPrep *scanprep_create();
-void scanprep_destroy(ScanPrep *sp);
-hipError_t scanprep_order(ScanPrep *sp, hipStream_t s, const float4 *h_pts, size_t n, const int32_t *h_seg_off,
-                          int nseg, float4 *d_out);  // false once lslam_ctx_destroy ran
+hipError_t scanprep_order(lslam_ctx *ctx, const float4 *h_pts, size_t n, const int32_t *h_seg_off, int nseg, float4 *d_out);
 }  // namespace lslam

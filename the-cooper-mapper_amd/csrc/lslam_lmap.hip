@@ -287,9 +287,8 @@ struct lslam_lmap {
   uint64_t head[2] = {0, 0}, tail[2] = {0, 0};
   size_t live[2] = {0, 0};
   // add staging
-  float4 *h_stage[2] = {nullptr, nullptr};
-  float4 *d_raw[2] = {nullptr, nullptr}, *d_tf[2] = {nullptr, nullptr};
-  size_t stage_cap[2] = {0, 0};
+  lslam::PinBuf<float4> h_stage[2];
+  lslam::DevBuf<float4> d_raw[2], d_tf[2];
   // surround
   float4 *gath[2] = {nullptr, nullptr}, *filt[2] = {nullptr, nullptr}, *mapp[2] = {nullptr, nullptr};
   int32_t *seg[2] = {nullptr, nullptr}, *oseg[2] = {nullptr, nullptr};  // zeros (one segment) / the filter's segment output
@@ -332,10 +331,8 @@ int check_lm(lslam_lmap *lm, const char *what) {
 
 void free_all(lslam_lmap *lm) {
   for (int t = 0; t < 2; ++t) {
-    lm_free(lm->ring[t]); lm_free(lm->d_raw[t]); lm_free(lm->d_tf[t]); lm_free(lm->gath[t]); lm_free(lm->filt[t]); lm_free(lm->mapp[t]);
+    lm_free(lm->ring[t]); lm_free(lm->gath[t]); lm_free(lm->filt[t]); lm_free(lm->mapp[t]);
     lm_free(lm->seg[t]); lm_free(lm->oseg[t]); lm_free(lm->xs[t]); lm_free(lm->xs_alt[t]); lm_free(lm->xq[t]); lm_free(lm->xq_alt[t]);
-    if (lm->h_stage[t]) (void)hipHostFree(lm->h_stage[t]);
-    lm->h_stage[t] = nullptr;
     lslam::window_filter_destroy(lm->wf[t]);
     lm->wf[t] = nullptr;
   }
@@ -363,19 +360,9 @@ void reset_state(lslam_lmap *lm) {  // LocalFeatureMap as constructed (the leave
 }
 
 int reserve_stage(lslam_lmap *lm, int t, size_t n, bool host) {
-  if (n <= lm->stage_cap[t] && (!host || lm->h_stage[t])) return LSLAM_OK;
-  const size_t want = std::max(n + n / 4 + 256, lm->stage_cap[t]);
-  if (want > lm->stage_cap[t]) {
-    lm_free(lm->d_raw[t]);
-    lm_free(lm->d_tf[t]);
-    if (lm->h_stage[t]) (void)hipHostFree(lm->h_stage[t]);
-    lm->h_stage[t] = nullptr;
-    lm->stage_cap[t] = 0;
-    LM_TRY(lm_alloc(lm->d_raw[t], want));
-    LM_TRY(lm_alloc(lm->d_tf[t], want));
-    lm->stage_cap[t] = want;
-  }
-  if (host && !lm->h_stage[t]) LM_TRY(hipHostMalloc((void **)&lm->h_stage[t], lm->stage_cap[t] * sizeof(float4), hipHostMallocDefault));
+  LM_TRY(lm->d_raw[t].reserve(n));
+  LM_TRY(lm->d_tf[t].reserve(n));
+  if (host) LM_TRY(lm->h_stage[t].reserve(n));
   return LSLAM_OK;
 }
 
@@ -449,7 +436,7 @@ int add_impl(lslam_lmap *lm, const void *corner, size_t n_corner, const void *su
       rc = reserve_stage(lm, t, n_new[t], host);
       if (rc) return rc;
       if (host && n_new[t]) {
-        float4 *h = lm->h_stage[t];
+        float4 *h = lm->h_stage[t].p;
         const char *p = static_cast<const char *>(src[t]);
         if (stride_bytes == 16) {
           std::memcpy(h, p, n_new[t] * sizeof(float4));
@@ -461,10 +448,10 @@ int add_impl(lslam_lmap *lm, const void *corner, size_t n_corner, const void *su
             h[i] = make_float4(v[0], v[1], v[2], w);
           }
         }
-        LM_TRY(hipMemcpyAsync(lm->d_raw[t], h, n_new[t] * sizeof(float4), hipMemcpyHostToDevice, s));
+        LM_TRY(hipMemcpyAsync(lm->d_raw[t].p, h, n_new[t] * sizeof(float4), hipMemcpyHostToDevice, s));
       }
-      ta.in[t] = host ? lm->d_raw[t] : static_cast<const float4 *>(src[t]);
-      ta.out[t] = lm->d_tf[t];
+      ta.in[t] = host ? lm->d_raw[t].p : static_cast<const float4 *>(src[t]);
+      ta.out[t] = lm->d_tf[t].p;
       ta.n[t] = (int)n_new[t];
     }
     ta.nb0 = (int)((n_new[0] + 255) / 256);
@@ -526,7 +513,7 @@ int add_impl(lslam_lmap *lm, const void *corner, size_t n_corner, const void *su
   if (n_new[0] || n_new[1]) {
     AppendArgs aa{};
     for (int t = 0; t < 2; ++t) {
-      aa.in[t] = lm->d_tf[t];
+      aa.in[t] = lm->d_tf[t].p;
       aa.ring[t] = lm->ring[t];
       const bool x = lm->key_ordered && lm->x_valid[t];
       aa.xs[t] = x ? lm->xs[t] : nullptr;
@@ -592,7 +579,7 @@ int refilter(lslam_lmap *lm, int t, bool wait) {
   size_t m = 0;
   uint32_t *done = done_words(lm, t);
   done[0] = done[1] = done[2] = 0;
-  rc = lslam::voxel_filter_segments(lm->stream, lm->gath[t], lm->seg[t], lm->live[t], 1, lm->leaf[t], lm->filt[t], lm->oseg[t], &m, true,
+  rc = lslam::voxel_filter_segments(lm->ctx, lm->gath[t], lm->seg[t], lm->live[t], 1, lm->leaf[t], lm->filt[t], lm->oseg[t], &m, true,
                                     wait ? nullptr : done);
   if (rc) return rc;
   if (wait) done[0] = (uint32_t)m;

@@ -24,8 +24,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "lslam_internal.hpp"
@@ -801,31 +799,13 @@ __global__ __launch_bounds__(256) void odom_gn_kernel(GnSegArgs g) {
   }
 }
 
-template <typename T>
-struct Buf {
-  T *p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = n + n / 4 + 256;
-    hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
+using lslam::DevBuf;
+using lslam::PinBuf;
 
 // one generation of last clouds with its grids
 struct Side {
-  Buf<float4> org[2];
-  Buf<float4> sorted[4];  // [cloud * 2 + level]
+  DevBuf<float4> org[2];
+  DevBuf<float4> sorted[4];  // [cloud * 2 + level]
   uint32_t *start = nullptr;  // [4][OH_SIZE + 1]
   uint32_t *hdr = nullptr;    // [2] per cloud: bit 0 = not in ring order (odom_prep_kernel); behind it the ring table [2][OH_RINGS + 1]
   size_t n[2] = {0, 0};
@@ -847,31 +827,28 @@ struct lslam_odom {
   uint32_t *cnt = nullptr, *cursor = nullptr;  // [4][OH_SIZE]
   int32_t literal_window = 0;
   // odom_gn_kernel
-  Buf<float> slots;
+  DevBuf<float> slots;
   bool persistent = true;     // LSLAM_ODOM_PERSISTENT=0 (debug hook): the launch-per-step loop
   bool persistent_ok = true;  // false once an exchange ran into its spin limit
   uint32_t spin_limit = 1u << 18;
   uint64_t persistent_runs = 0, launch_runs = 0;
-  Buf<uint32_t> dbg;  // LSLAM_ODOM_SEARCH_TAP=1 (debug hook): per-query profile of the last search launch (lslam_debug_odom_search)
+  DevBuf<uint32_t> dbg;  // LSLAM_ODOM_SEARCH_TAP=1 (debug hook): per-query profile of the last search launch (lslam_debug_odom_search)
   bool dbg_on = false;
   size_t dbg_n = 0;
-  Buf<int32_t> ind;
-  Buf<float> partials;
+  DevBuf<int32_t> ind;
+  DevBuf<float> partials;
   ProbBlocks *d_probs = nullptr;
   GNState *d_state = nullptr, *h_state = nullptr;  // h_state pinned: [0] the state, then 64 bytes of flags, then the ProbBlocks going up
   int32_t nb_on_device = -1;
   uint32_t *d_flags = nullptr;
   float4 *h_last = nullptr;  // pinned staging of the last clouds going out (= h_own, or a buffer of the publishing ring)
-  float4 *h_own = nullptr;
-  size_t h_own_cap = 0;
+  PinBuf<float4> h_own;
   // lslam_odom_set_publish: a ring of pinned buffers the last clouds are copied to with every sweep, handed out as views
-  std::vector<float4 *> pub;
-  std::vector<size_t> pub_cap;
+  std::vector<PinBuf<float4>> pub;
   int pub_next = 0;
   const float4 *view_c = nullptr, *view_s = nullptr;
   size_t view_nc = 0, view_ns = 0;
-  float4 *h_up = nullptr;    // pinned staging of host clouds coming in (lslam_fset_upload, lslam_odometry_match)
-  size_t h_up_cap = 0;
+  PinBuf<float4> h_up;       // staging of host clouds coming in (lslam_odometry_match)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   int iter_hint = 6;
   uint64_t sweeps = 0;
@@ -887,26 +864,15 @@ void od_free(lslam_odom *od) {
   (void)hipSetDevice(od->device);
   if (od->stream && lslam::ctx_alive(od->ctx)) (void)hipStreamSynchronize(od->stream);
   for (Side &s : od->side) {
-    for (auto &b : s.org) b.release();
-    for (auto &b : s.sorted) b.release();
     if (s.start) (void)hipFree(s.start);
     if (s.hdr) (void)hipFree(s.hdr);
   }
-
   if (od->cnt) (void)hipFree(od->cnt);
   if (od->cursor) (void)hipFree(od->cursor);
-  od->ind.release();
-  od->partials.release();
-  od->slots.release();
-  od->dbg.release();
   if (od->d_probs) (void)hipFree(od->d_probs);
   if (od->d_state) (void)hipFree(od->d_state);
   if (od->d_flags) (void)hipFree(od->d_flags);
   if (od->h_state) (void)hipHostFree(od->h_state);
-  if (od->h_own) (void)hipHostFree(od->h_own);
-  for (float4 *b : od->pub)
-    if (b) (void)hipHostFree(b);
-  if (od->h_up) (void)hipHostFree(od->h_up);
   if (od->ev0) (void)hipEventDestroy(od->ev0);
   if (od->ev1) (void)hipEventDestroy(od->ev1);
   if (od->own_fs) lslam_fset_destroy(od->own_fs);
@@ -1227,17 +1193,6 @@ void pack_xyzi(const void *src, size_t n, size_t stride_bytes, float4 *out) {
   }
 }
 
-int reserve_pinned(float4 *&p, size_t &cap, size_t n) {
-  if (n <= cap) return LSLAM_OK;
-  if (p) (void)hipHostFree(p);
-  p = nullptr;
-  cap = 0;
-  const size_t want = n + n / 4 + 256;
-  OD_TRY(hipHostMalloc((void **)&p, want * sizeof(float4), hipHostMallocDefault));
-  cap = want;
-  return LSLAM_OK;
-}
-
 // host lists -> the feature set's slices, through `stage` (pinned, at least the four sizes together); enqueued on s
 int upload_lists(hipStream_t s, lslam_fset *fs, float4 *stage, const void *const src[4], const size_t n[4], size_t stride_bytes) {
   size_t most = 0;
@@ -1254,9 +1209,11 @@ int upload_lists(hipStream_t s, lslam_fset *fs, float4 *stage, const void *const
   return LSLAM_OK;
 }
 
-// the hidden node behind lslam_odometry_match, one per context
-std::mutex g_mu;
-std::map<lslam_ctx *, lslam_odom *> g_hidden;
+// the hidden node behind lslam_odometry_match, one per context: kept in the context (ctx_slot), gone with it
+struct HiddenOdom {
+  lslam_odom *od = nullptr;
+  ~HiddenOdom() { od_free(od); }
+};
 
 void mat4_mul(const float A[16], const float B[16], float C[16]) {
   for (int r = 0; r < 4; ++r)
@@ -1272,28 +1229,11 @@ void mat4_mul(const float A[16], const float B[16], float C[16]) {
 namespace lslam {
 
 hipError_t fset_reserve(lslam_fset *fs, size_t points_per_list) {
-  if (points_per_list <= fs->cap && fs->buf) return hipSuccess;
-  if (fs->buf) (void)hipFree(fs->buf);
-  fs->buf = nullptr;
+  if (points_per_list <= fs->cap && fs->buf.p) return hipSuccess;
   fs->cap = 0;
-  const size_t want = points_per_list + points_per_list / 4 + 256;
-  hipError_t e = hipMalloc((void **)&fs->buf, (16 + 4 * want) * sizeof(float4));
-  if (e == hipSuccess) fs->cap = want;
+  hipError_t e = fs->buf.reserve(16 + 4 * points_per_list);  // the slices share the slack
+  if (e == hipSuccess) fs->cap = (fs->buf.cap - 16) / 4;
   return e;
-}
-
-// lslam_ctx_destroy: the context's hidden odometry node goes with it
-void odom_ctx_gone(lslam_ctx *ctx) {
-  lslam_odom *od = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_hidden.find(ctx);
-    if (it != g_hidden.end()) {
-      od = it->second;
-      g_hidden.erase(it);
-    }
-  }
-  if (od) od_free(od);
 }
 
 }  // namespace lslam
@@ -1314,8 +1254,6 @@ int lslam_fset_create(lslam_ctx *ctx, lslam_fset **out) {
 void lslam_fset_destroy(lslam_fset *fs) {
   if (!fs) return;
   (void)hipSetDevice(fs->device);
-  if (fs->buf) (void)hipFree(fs->buf);
-  if (fs->h_stage) (void)hipHostFree(fs->h_stage);
   delete fs;
 }
 
@@ -1340,10 +1278,9 @@ int lslam_fset_upload(lslam_ctx *ctx, lslam_fset *fs, const void *sharp, size_t 
   const void *src[4] = {sharp, less_sharp, flat, less_flat};
   const size_t n[4] = {n_sharp, n_less_sharp, n_flat, n_less_flat};
   const size_t total = n_sharp + n_less_sharp + n_flat + n_less_flat;
-  int rc = reserve_pinned(fs->h_stage, fs->h_stage_cap, total + 1);
-  if (rc) return rc;
+  OD_TRY(fs->h_stage.reserve(total + 1));
   hipStream_t s = lslam::ctx_stream(ctx);
-  rc = upload_lists(s, fs, fs->h_stage, src, n, stride_bytes);
+  int rc = upload_lists(s, fs, fs->h_stage.p, src, n, stride_bytes);
   const hipError_t e = hipStreamSynchronize(s);
   if (rc) return rc;
   OD_TRY(e);
@@ -1385,10 +1322,8 @@ int lslam_odom_set_publish(lslam_odom *od, int32_t n_buffers) {
   }
   (void)hipSetDevice(od->device);
   if (lslam::ctx_alive(od->ctx)) (void)hipStreamSynchronize(od->stream);
-  for (float4 *b : od->pub)
-    if (b) (void)hipHostFree(b);
-  od->pub.assign((size_t)n_buffers, nullptr);
-  od->pub_cap.assign((size_t)n_buffers, 0);
+  od->pub.clear();
+  od->pub.resize((size_t)n_buffers);
   od->pub_next = 0;
   od->view_c = od->view_s = nullptr;
   od->view_nc = od->view_ns = 0;
@@ -1464,20 +1399,18 @@ int lslam_odom_process(lslam_odom *od, lslam_fset *fs, float transform[6], float
   const bool publish = !od->pub.empty();
   const bool want_out = last_corner || last_surf || publish;
   if (publish) {
-    if (od->pub_cap[od->pub_next] < n_ls + n_lf + 1) {
+    if (od->pub[od->pub_next].cap < n_ls + n_lf + 1) {
       // the whole ring at once (a page-locked allocation takes milliseconds: not one per sweep while the ring fills); the
       // buffers that are views right now keep their memory until their turn comes
       for (size_t k = 0; k < od->pub.size(); ++k) {
-        if (od->pub[k] && (int)k != od->pub_next) continue;
-        int rc = reserve_pinned(od->pub[k], od->pub_cap[k], 2 * (n_ls + n_lf) + 1);
-        if (rc) return rc;
+        if (od->pub[k].p && (int)k != od->pub_next) continue;
+        OD_TRY(od->pub[k].reserve(2 * (n_ls + n_lf) + 1));
       }
     }
-    od->h_last = od->pub[od->pub_next];
+    od->h_last = od->pub[od->pub_next].p;
   } else if (want_out) {
-    int rc = reserve_pinned(od->h_own, od->h_own_cap, n_ls + n_lf + 1);
-    if (rc) return rc;
-    od->h_last = od->h_own;
+    OD_TRY(od->h_own.reserve(n_ls + n_lf + 1));
+    od->h_last = od->h_own.p;
   }
   int status = LSLAM_TOO_FEW_REF;
   int32_t matched = 0, searches = 0;
@@ -1608,23 +1541,19 @@ int lslam_odometry_match(lslam_ctx *ctx, const void *last_corner, size_t n_lc, c
     st.status = LSLAM_TOO_FEW_REF;
     return LSLAM_TOO_FEW_REF;
   }
-  lslam_odom *od = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_hidden.find(ctx);
-    if (it != g_hidden.end()) od = it->second;
-  }
-  if (!od) {
-    int rc = od_create(ctx, max_iterations, delta_t_abort, delta_r_abort, &od);
+  HiddenOdom *hidden = lslam::ctx_slot<HiddenOdom>(ctx, lslam::CTX_SLOT_ODOM);
+  if (!hidden->od) {
+    lslam_odom *made = nullptr;
+    int rc = od_create(ctx, max_iterations, delta_t_abort, delta_r_abort, &made);
     if (rc) return rc;
-    rc = lslam_fset_create(ctx, &od->own_fs);
+    rc = lslam_fset_create(ctx, &made->own_fs);
     if (rc) {
-      od_free(od);
+      od_free(made);
       return rc;
     }
-    std::lock_guard<std::mutex> lk(g_mu);
-    g_hidden[ctx] = od;
+    hidden->od = made;
   }
+  lslam_odom *od = hidden->od;
   OD_TRY(hipSetDevice(od->device));
   od->max_it = max_iterations < 0 ? 0 : max_iterations;
   od->dt = delta_t_abort;
@@ -1632,9 +1561,8 @@ int lslam_odometry_match(lslam_ctx *ctx, const void *last_corner, size_t n_lc, c
   // the four clouds into the node's own feature set (the last clouds in the less-sharp / less-flat slices), grids, loop
   const void *src[4] = {sharp, last_corner, flat, last_surf};
   const size_t n[4] = {n_sharp, n_lc, n_flat, n_ls};
-  int rc = reserve_pinned(od->h_up, od->h_up_cap, n_sharp + n_lc + n_flat + n_ls + 1);
-  if (rc) return rc;
-  rc = upload_lists(od->stream, od->own_fs, od->h_up, src, n, stride_bytes);
+  OD_TRY(od->h_up.reserve(n_sharp + n_lc + n_flat + n_ls + 1));
+  int rc = upload_lists(od->stream, od->own_fs, od->h_up.p, src, n, stride_bytes);
   if (rc) return rc;
   lslam_fset *fs = od->own_fs;
   rc = enqueue_build(od, 0, fs->list(1), n_lc, fs->list(3), n_ls, false, false);

@@ -56,71 +56,44 @@ __global__ void sp_gather_kernel(const float4 *pts, const uint32_t *idx, const u
 
 }  // namespace
 
-struct ScanPrep {
-  void *keys0 = nullptr, *keys1 = nullptr, *idx0 = nullptr, *idx1 = nullptr, *tmp = nullptr, *raw = nullptr, *seg = nullptr;
-  size_t cap = 0, tmp_cap = 0, seg_cap = 0;
+struct ScanPrep {  // the context's (ctx_slot), grow-only
+  DevBuf<uint64_t> keys0, keys1;
+  DevBuf<uint32_t> idx0, idx1;
+  DevBuf<float4> raw;
+  DevBuf<int32_t> seg;
+  DevBuf<char> tmp;
 };
 
-ScanPrep *scanprep_create() { return new ScanPrep(); }
-void scanprep_destroy(ScanPrep *sp) {
-  if (!sp) return;
-  for (void *p : {sp->keys0, sp->keys1, sp->idx0, sp->idx1, sp->tmp, sp->raw, sp->seg})
-    if (p) (void)hipFree(p);
-  delete sp;
-}
-
 // h_pts: n packed points in caller order (cloud after cloud); h_seg_off: nseg + 1 offsets.
-// Writes the ordered points to d_out (n float4) on `s`, asynchronously: h_pts must stay untouched until `s` has been waited for.
-hipError_t scanprep_order(ScanPrep *sp, hipStream_t s, const float4 *h_pts, size_t n, const int32_t *h_seg_off,
-                          int nseg, float4 *d_out) {
+// Writes the ordered points to d_out (n float4) on the context's stream, asynchronously: h_pts must stay untouched until that
+// stream has been waited for.
+hipError_t scanprep_order(lslam_ctx *ctx, const float4 *h_pts, size_t n, const int32_t *h_seg_off, int nseg, float4 *d_out) {
   if (n == 0) return hipSuccess;
+  ScanPrep *sp = ctx_slot<ScanPrep>(ctx, CTX_SLOT_SCANPREP);
+  hipStream_t s = ctx_stream(ctx);
   hipError_t e;
-  if (n > sp->cap) {
-    for (void **p : {&sp->keys0, &sp->keys1, &sp->idx0, &sp->idx1, &sp->raw}) {
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
-    }
-    sp->cap = 0;
-    const size_t want = n + n / 4 + 1024;
-    if ((e = hipMalloc(&sp->keys0, want * 8)) != hipSuccess) return e;
-    if ((e = hipMalloc(&sp->keys1, want * 8)) != hipSuccess) return e;
-    if ((e = hipMalloc(&sp->idx0, want * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc(&sp->idx1, want * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc(&sp->raw, want * sizeof(float4))) != hipSuccess) return e;
-    sp->cap = want;
-  }
-  if ((size_t)nseg + 1 > sp->seg_cap) {
-    if (sp->seg) (void)hipFree(sp->seg);
-    sp->seg = nullptr;
-    sp->seg_cap = 0;
-    if ((e = hipMalloc(&sp->seg, ((size_t)nseg + 64) * 4)) != hipSuccess) return e;
-    sp->seg_cap = (size_t)nseg + 64;
-  }
-  if ((e = hipMemcpyAsync(sp->raw, h_pts, n * sizeof(float4), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-  if ((e = hipMemcpyAsync(sp->seg, h_seg_off, ((size_t)nseg + 1) * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  if ((e = sp->keys0.reserve(n)) != hipSuccess || (e = sp->keys1.reserve(n)) != hipSuccess || (e = sp->idx0.reserve(n)) != hipSuccess ||
+      (e = sp->idx1.reserve(n)) != hipSuccess || (e = sp->raw.reserve(n)) != hipSuccess || (e = sp->seg.reserve((size_t)nseg + 1)) != hipSuccess)
+    return e;
+  if ((e = hipMemcpyAsync(sp->raw.p, h_pts, n * sizeof(float4), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(sp->seg.p, h_seg_off, ((size_t)nseg + 1) * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
   int seg_bits = 1;
   while ((1 << seg_bits) < nseg) ++seg_bits;
   const unsigned end_bit = 30u + (unsigned)seg_bits;
-  uint64_t *k0 = (uint64_t *)sp->keys0, *k1 = (uint64_t *)sp->keys1;
-  uint32_t *i0 = (uint32_t *)sp->idx0, *i1 = (uint32_t *)sp->idx1;
+  uint64_t *k0 = sp->keys0.p, *k1 = sp->keys1.p;
+  uint32_t *i0 = sp->idx0.p, *i1 = sp->idx1.p;
   // the library's radix sort; LSLAM_SMALL_SORT=1 (A/B): lslam_sort.hip for a frame's scan (<= SMALL_SORT_MAX points)
   const bool small = n <= SMALL_SORT_MAX && env_once().small_sort;
   size_t tmp_bytes = 0;
   if (small) tmp_bytes = small_sort_tmp_bytes(n);
   else if ((e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, k0, k1, i0, i1, n, 0u, end_bit, s)) != hipSuccess) return e;
-  if (tmp_bytes > sp->tmp_cap) {
-    if (sp->tmp) (void)hipFree(sp->tmp);
-    sp->tmp = nullptr;
-    sp->tmp_cap = 0;
-    if ((e = hipMalloc(&sp->tmp, tmp_bytes + tmp_bytes / 4)) != hipSuccess) return e;
-    sp->tmp_cap = tmp_bytes + tmp_bytes / 4;
-  }
+  if ((e = sp->tmp.reserve(tmp_bytes)) != hipSuccess) return e;
   const dim3 blk(256), grd((unsigned)((n + 255) / 256));
-  hipLaunchKernelGGL(sp_key_kernel, grd, blk, 0, s, (const float4 *)sp->raw, (int)n, (const int32_t *)sp->seg, nseg, k0, i0);
-  if (small) e = small_sort_pairs(s, k0, k1, i0, i1, n, sp->tmp);
-  else e = rocprim::radix_sort_pairs(sp->tmp, tmp_bytes, k0, k1, i0, i1, n, 0u, end_bit, s);
+  hipLaunchKernelGGL(sp_key_kernel, grd, blk, 0, s, (const float4 *)sp->raw.p, (int)n, (const int32_t *)sp->seg.p, nseg, k0, i0);
+  if (small) e = small_sort_pairs(s, k0, k1, i0, i1, n, sp->tmp.p);
+  else e = rocprim::radix_sort_pairs(sp->tmp.p, tmp_bytes, k0, k1, i0, i1, n, 0u, end_bit, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(sp_gather_kernel, grd, blk, 0, s, (const float4 *)sp->raw, i1, k1, (const int32_t *)sp->seg, (int)n,
+  hipLaunchKernelGGL(sp_gather_kernel, grd, blk, 0, s, (const float4 *)sp->raw.p, i1, k1, (const int32_t *)sp->seg.p, (int)n,
                      d_out);
   // No wait: h_seg_off is pageable (consumed when hipMemcpyAsync returned), h_pts is the context's pinned staging area,
   // which the caller does not touch again before it has waited on `s` (lslam_ctx::stage_busy).

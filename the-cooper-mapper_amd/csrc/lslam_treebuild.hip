@@ -27,8 +27,6 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <vector>
 #include <chrono>
 #include <cstdio>
@@ -1796,45 +1794,6 @@ __global__ __launch_bounds__(256) void kd_pnode_kernel(const KdNode *nodes, int 
 // place).  d_nodes must hold node_cap nodes.  Returns hipSuccess and fills `view`/depth, or
 // sets *fallback when a structure limit was hit (the caller retries with more node slots or fails).
 namespace {
-// Scratch of a build, kept per stream between builds (hipMalloc/hipFree of tens of MB per call cost
-// more than a millisecond); released by treebuild_release_scratch.
-struct BuildPool {
-  void *blob = nullptr, *lv = nullptr, *part = nullptr;
-  size_t cap = 0, lv_cap = 0;
-};
-std::mutex g_pool_mu;
-std::map<hipStream_t, BuildPool> g_pool;
-
-hipError_t pool_get(hipStream_t s, bool lv, size_t bytes, void **out) {
-  std::lock_guard<std::mutex> lk(g_pool_mu);
-  BuildPool &p = g_pool[s];
-  void *&ptr = lv ? p.lv : p.blob;
-  size_t &cap = lv ? p.lv_cap : p.cap;
-  if (bytes > cap) {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    const size_t want = bytes + bytes / 4;
-    hipError_t e = hipMalloc(&ptr, want);
-    if (e != hipSuccess) return e;
-    cap = want;
-  }
-  *out = ptr;
-  return hipSuccess;
-}
-}  // namespace
-
-void treebuild_release_scratch(hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_pool_mu);
-  auto it = g_pool.find(s);
-  if (it == g_pool.end()) return;
-  if (it->second.blob) (void)hipFree(it->second.blob);
-  if (it->second.lv) (void)hipFree(it->second.lv);
-  if (it->second.part) (void)hipFree(it->second.part);
-  g_pool.erase(it);
-}
-
-namespace {
 // Phase 0 driver: processes `level` (every entry more than HUGE_MIN points) and the levels it
 // spawns; smaller children land in A.queue / A.sublist.  n = points the trees span in total.
 // n: points of all roots together (capacities); n_largest: of the largest root (how many levels the first batch enqueues)
@@ -1848,17 +1807,16 @@ namespace {
     return (err);                             \
   } while (0)
 
-hipError_t run_levels(const BuildArgs &A, std::vector<BuildItem> level, int32_t n, hipStream_t stream, int *fallback, const RootInit *root_init = nullptr,
+hipError_t run_levels(BuildPool &pool, const BuildArgs &A, std::vector<BuildItem> level, int32_t n, hipStream_t stream, int *fallback, const RootInit *root_init = nullptr,
                       int32_t n_largest = 0, const float *forest_part = nullptr) {
   if (n_largest <= 0) n_largest = n;
   hipError_t e;
-  void *lv_blob = nullptr;
   const int n_first = root_init ? 1 : (int)level.size();
   const int cap_nodes = n / A.huge_min * 2 + n_first + 8, cap_chunks = n / LV_CH + cap_nodes + 8;
   const size_t sz_items = (size_t)cap_nodes * sizeof(BuildItem), sz_stat = (size_t)cap_nodes * sizeof(LvStat),
                sz_ci = (size_t)cap_chunks * sizeof(int32_t), sz_ni = (size_t)cap_nodes * sizeof(int32_t);
-  if ((e = pool_get(stream, true, 2 * sz_items + 2 * sz_stat + 5 * sz_ci + sz_ni + (size_t)cap_chunks * sizeof(LvChunk) + 128, &lv_blob)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
-  char *q = static_cast<char *>(lv_blob);
+  if ((e = pool.lv.reserve(2 * sz_items + 2 * sz_stat + 5 * sz_ci + sz_ni + (size_t)cap_chunks * sizeof(LvChunk) + 128)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
+  char *q = pool.lv.p;
   BuildItem *d_items[2];
   d_items[0] = reinterpret_cast<BuildItem *>(q); q += sz_items;
   d_items[1] = reinterpret_cast<BuildItem *>(q); q += sz_items;
@@ -1971,7 +1929,7 @@ static int32_t reg_nodes_enabled() {
   return off ? 0 : 1;
 }
 
-hipError_t build_kdtree_device(float4 *d_pts, int32_t n, KdNode *d_nodes, float *d_own_box, int32_t node_cap,
+hipError_t build_kdtree_device(BuildPool &pool, float4 *d_pts, int32_t n, KdNode *d_nodes, float *d_own_box, int32_t node_cap,
                                hipStream_t stream, TreeView *view, int *depth, size_t *n_leaves,
                                int *fallback) {
   const bool dbg = env_once().debug;
@@ -1991,13 +1949,8 @@ hipError_t build_kdtree_device(float4 *d_pts, int32_t n, KdNode *d_nodes, float 
   hipError_t e;
   // bounding box
   constexpr int NB = 256;
-  float *d_part = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    BuildPool &bp = g_pool[stream];
-    if (!bp.part && (e = hipMalloc(&bp.part, NB * 6 * sizeof(float))) != hipSuccess) TB_RETURN_SETTLED(stream, e);
-    d_part = static_cast<float *>(bp.part);
-  }
+  if ((e = pool.part.reserve(NB * 6)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
+  float *d_part = pool.part.p;
   hipLaunchKernelGGL(kd_bbox_kernel, dim3(NB), dim3(256), 0, stream, d_pts, n, d_part);
   const int used = std::min(NB, (n + 255) / 256);
   if (n <= 10) {  // the root is a leaf: only the box is needed
@@ -2037,15 +1990,14 @@ hipError_t build_kdtree_device(float4 *d_pts, int32_t n, KdNode *d_nodes, float 
   A.reg_nodes = reg_nodes_enabled();
   A.spin_limit = 1u << 22;
   if (const char *sl = debug_env("LSLAM_DEBUG_SPIN_LIMIT")) A.spin_limit = (uint32_t)strtoul(sl, nullptr, 10);  // tests
-  void *blob = nullptr;
   A.sub_cap = sub_cap;
   const size_t sz_queue = (size_t)queue_cap * sizeof(BuildItem), sz_ready = (size_t)queue_cap * sizeof(int32_t),
                sz_tmp = (size_t)n * sizeof(int32_t), sz_ctl = 256, sz_sub = (size_t)sub_cap * sizeof(BuildItem);
   const bool tiny_phase = tiny_phase_enabled() && A.reg_nodes;
   const int32_t tiny_cap = tiny_phase ? n / 11 + 2 : 0;
   const size_t sz_tiny = tiny_phase ? ((size_t)tiny_cap * sizeof(BuildItem) + TINY_ACC * 128 + 127) & ~(size_t)127 : 0;
-  if ((e = pool_get(stream, false, sz_queue + sz_sub + sz_ready + 2 * sz_tmp + sz_ctl + sz_tiny + 128, &blob)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
-  char *p = static_cast<char *>(blob);
+  if ((e = pool.blob.reserve(sz_queue + sz_sub + sz_ready + 2 * sz_tmp + sz_ctl + sz_tiny + 128)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
+  char *p = pool.blob.p;
   A.queue = reinterpret_cast<BuildItem *>(p); p += sz_queue;
   A.sublist = reinterpret_cast<BuildItem *>(p); p += sz_sub;
   A.q_ready = reinterpret_cast<int32_t *>(p); p += sz_ready;
@@ -2077,7 +2029,7 @@ hipError_t build_kdtree_device(float4 *d_pts, int32_t n, KdNode *d_nodes, float 
   R.bbox_out = reinterpret_cast<float *>(reinterpret_cast<char *>(A.ctl) + 128);
   if (root_huge) {
     // ---- phase 0: level-synchronous processing of the nodes with more than HUGE_MIN points ----
-    if ((e = run_levels(A, std::vector<BuildItem>(), n, stream, fallback, &R)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
+    if ((e = run_levels(pool, A, std::vector<BuildItem>(), n, stream, fallback, &R)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
     if (*fallback) return hipSuccess;
   } else {
     R.mode = root_small ? 2 : 1;  // the whole tree is one phase-B subtree / the root enters the phase-A queue
@@ -2141,7 +2093,7 @@ hipError_t build_packet_nodes(const TreeView &view, const float *d_own_box, PNod
 // (host array), all trees share d_nodes; tree t's root sits in node group t.  Phase 0 takes every
 // root above HUGE_MIN points, phase B the rest; roots of at most 10 points are leaves.  views[t] is
 // filled for every root (nodes = d_nodes, pts = d_pts: references are absolute).
-hipError_t build_kdforest_device(float4 *d_pts, int32_t n_total, const int32_t *roots_lr, int T, KdNode *d_nodes,
+hipError_t build_kdforest_device(BuildPool &pool, float4 *d_pts, int32_t n_total, const int32_t *roots_lr, int T, KdNode *d_nodes,
                                  PNode *d_pn, int32_t node_cap, hipStream_t stream, TreeView *views, int *max_depth,
                                  size_t *n_leaves, int *fallback) {
   *fallback = 0;
@@ -2167,9 +2119,8 @@ hipError_t build_kdforest_device(float4 *d_pts, int32_t n_total, const int32_t *
   const bool tiny_phase = tiny_phase_enabled() && A.reg_nodes;
   const int32_t tiny_cap = tiny_phase ? n_total / 11 + 2 : 0;
   const size_t sz_tiny = tiny_phase ? ((size_t)tiny_cap * sizeof(BuildItem) + TINY_ACC * 128 + 127) & ~(size_t)127 : 0;
-  void *blob = nullptr;
-  if ((e = pool_get(stream, false, sz_queue + sz_sub + sz_ready + 2 * sz_tmp + sz_ctl + sz_rf + sz_lr + sz_bb + sz_tiny + sz_own + 128, &blob)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
-  char *p = static_cast<char *>(blob);
+  if ((e = pool.blob.reserve(sz_queue + sz_sub + sz_ready + 2 * sz_tmp + sz_ctl + sz_rf + sz_lr + sz_bb + sz_tiny + sz_own + 128)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
+  char *p = pool.blob.p;
   A.queue = reinterpret_cast<BuildItem *>(p); p += sz_queue;
   A.sublist = reinterpret_cast<BuildItem *>(p); p += sz_sub;
   A.q_ready = reinterpret_cast<int32_t *>(p); p += sz_ready;
@@ -2250,7 +2201,7 @@ hipError_t build_kdforest_device(float4 *d_pts, int32_t n_total, const int32_t *
   if (!level.empty()) {
     int32_t n_largest = 0;
     for (const BuildItem &it : level) n_largest = std::max(n_largest, it.r - it.l);
-    if ((e = run_levels(A, level, n_total, stream, fallback, nullptr, n_largest, d_part)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
+    if ((e = run_levels(pool, A, level, n_total, stream, fallback, nullptr, n_largest, d_part)) != hipSuccess) TB_RETURN_SETTLED(stream, e);
     if (*fallback) return hipSuccess;
   }
   int dev = 0, cus = 256;
