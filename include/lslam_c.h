@@ -206,6 +206,7 @@ void lslam_default_opts(lslam_opts *opts);
  * _CARRIED, LSLAM_AB_FIT_CACHE, LSLAM_AB_WIDE_NF_MARGIN) -- a program built against this header needs a library that has them. */
 /* 6 (round 6): no struct changed; new entry points (lslam_fset_*, lslam_extract_features_dev, lslam_odom_*, lslam_map_epoch). */
 /* 7: no struct changed; new entry points (lslam_lmap_*: the sliding-window local map). */
+/* still 7: no struct changed; new entry points (lslam_sreg_*: the registration node with the IMU de-skew branch). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -536,7 +537,7 @@ int lslam_voxel_grid2(lslam_ctx *ctx, const void *cloud_a, size_t n_a, const voi
  * setScanBuffersFor :471-531, setRegionBuffersFor :427-469, markAsPicked :533-555 and
  * pointClassify :557-687) on the ring-sorted full-resolution cloud MultiScanRegistration::process
  * builds (MultiScanRegistration.cpp:178-190).  Building that cloud from raw driver packets is the
- * caller's (ring from the vertical angle, IMU de-skew). */
+ * caller's here (ring from the vertical angle, IMU de-skew); lslam_sreg_* further down does all of it on the device. */
 typedef struct lslam_reg_params {     /* RegistrationParams, ScanRegistration.h:45-112 */
   int32_t n_feature_regions;          /* 6; 1 .. 512 (the device keeps the sort words of a ring's regions in LDS) */
   int32_t curvature_region;           /* 5 */
@@ -562,7 +563,7 @@ int lslam_extract_features(lslam_ctx *ctx, const void *cloud, size_t n_points, s
                            int8_t *label_out);
 
 /* MultiScanRegistration::process (odometry/MultiScanRegistration.cpp:94-190) without the IMU
- * branch: raw driver cloud {x,y,z} -> ring-sorted cloud {x', y', z', ring + relTime} in the
+ * branch (the registration node, lslam_sreg_*, has it): raw driver cloud {x,y,z} -> ring-sorted cloud {x', y', z', ring + relTime} in the
  * registration's swapped axes (x' = y, y' = z, z' = x) with its per-ring {first, last} ranges --
  * the input of lslam_extract_features (intensity offset 12).  Linear ring mapper
  * (MultiScanRegistration.h:57-87: VLP-16 = -15..15 deg / 16, HDL-32 = -30.67..10.67 / 32).  atan /
@@ -646,6 +647,64 @@ int lslam_odom_last_view(lslam_odom *od, const float **last_corner, size_t *n_co
 int lslam_debug_odom_search(lslam_odom *od, uint32_t *out, size_t cap_queries);
 /* Start again from the first sweep (keeps the buffers). */
 int lslam_odom_reset(lslam_odom *od);
+
+/* ---- the registration node resident on the device, with the IMU branch ------------------------------------------------
+ *
+ * MultiScanRegistration (odometry/MultiScanRegistration.cpp:78-200 on ScanRegistration.cpp:89-188, :684-707) as one object: the
+ * raw driver cloud goes up once, ring and relTime (as lslam_multiscan_register computes them, bit for bit), the projection of
+ * every point to the sweep start with the interpolated IMU state (setIMUTransformFor + transformToStartIMU, whenever an IMU
+ * has been heard), the grouping by ring, the per-ring ranges and the feature extraction all run on the device, the four lists
+ * stay in an lslam_fset for lslam_odom_process, and the host waits once.  Without an IMU state the lists, the cloud and the
+ * ranges are those of lslam_multiscan_register + lslam_extract_features_dev, bit for bit.
+ *
+ * IMU branch: the history lives on the host (lslam_sreg_imu_push = handleIMUMessage after getRPY: gravity removed in double,
+ * position and velocity integrated in float, the ring buffer overwriting its oldest state) and reaches the device with the
+ * sweep's upload.  The reference walks one index forward through the history while it visits the points in arrival order;
+ * with stamps that increase that index is f(the largest relTime among the kept points so far, at least 0), f(t) = the first
+ * state with (scanTime - stamp).toSec() + t <= 0 or the last state -- an inclusive prefix maximum and a binary search on the
+ * device.  THEREFORE a stamp that is not later than the previous state's is refused.  States used as they are (index 0, or
+ * a point later than the last state) keep the sine / cosine the host's C library cached when they were pushed; interpolated
+ * angles get sin / cos on the device as a double evaluation rounded once to float (the correctly rounded value except within
+ * ~1e-16 of a rounding boundary; glibc's sinf / cosf, which the reference calls, differ from that by one ulp for ~1.3 % of
+ * angles), so the de-skewed coordinates agree with a CPU restatement to a bound, not bit for bit: PARITY UNPINNED, as the
+ * reference's registration needs ROS and PCL to build (tests/scan_registration_ref.py is the CPU statement). */
+typedef struct lslam_sreg lslam_sreg;
+typedef struct lslam_sreg_stats {
+  uint64_t sweeps;     /* sweeps this node has registered */
+  size_t n_points;     /* points kept in this sweep's registered cloud */
+  int32_t imu_states;  /* IMU states sent with this sweep (0: none heard, no de-skew) */
+  int32_t launches;    /* kernels the node itself launches per sweep (7, 8 with the IMU branch), counted from the code; the
+                          grouping's sort and scan (the library's) and the memsets of the extraction are not in it */
+  size_t bytes_up;     /* host -> device, this sweep */
+  size_t bytes_down;   /* device -> host, this sweep: the result words, the ranges and the grouping's three words */
+} lslam_sreg_stats;
+/* params NULL: lslam_reg_default_params.  Ring mapper and scan period as lslam_multiscan_register; imu_history_size: the
+ * reference's imuHistorySize (200), 1 .. 512.  The node's buffers are its own and go with it; the grouping's scratch is the
+ * context's. */
+int lslam_sreg_create(lslam_ctx *ctx, const lslam_reg_params *params, float lower_deg, float upper_deg, int32_t n_rings,
+                      float scan_period, int32_t imu_history_size, lslam_sreg **out);
+void lslam_sreg_destroy(lslam_sreg *sr);
+/* handleIMUMessage (ScanRegistration.cpp:89-120) after tf's getRPY: stamp in nanoseconds, roll / pitch / yaw in radians,
+ * linear_acceleration {x, y, z} in the IMU's axes.  A stamp that is not later than the previous one is refused. */
+int lslam_sreg_imu_push(lslam_sreg *sr, int64_t stamp_ns, double roll, double pitch, double yaw, const double linear_acceleration[3]);
+/* States held, and the newest state's accumulated position / velocity (any pointer may be NULL). */
+int lslam_sreg_imu_info(const lslam_sreg *sr, int32_t *size, double last_position[3], double last_velocity[3]);
+/* Forget the history, _imuStart, _imuCur and the shift: the node is again one that has heard no IMU. */
+int lslam_sreg_imu_clear(lslam_sreg *sr);
+/* MultiScanRegistration::process(cloud, scanTime): cloud = n_points raw driver points {x,y,z} stride_bytes apart in arrival
+ * order, scan_time_ns the cloud's stamp.  out receives the four lists (counts[4] their sizes, may be NULL); imu_trans (may be
+ * NULL) the /imu_trans message: {start pitch, yaw, roll}, {current pitch, yaw, roll}, the shift and the velocity change in the
+ * start frame (all zero while no IMU has been heard).  A sweep without a kept point succeeds with empty lists and leaves
+ * _imuCur as it was.  Refused (LSLAM_ERR_INVALID, outputs zeroed, out reads empty): bad arguments and an empty cloud, found
+ * before anything is enqueued -- the node is exactly as before, the last sweep's cloud included; a ring of more than 2560
+ * points, found on the device and reported behind the same wait -- the IMU history, _imuStart, _imuCur and the shift are as
+ * before and the node is usable, but its scratch has been written: lslam_sreg_cloud has nothing to hand out until the next
+ * sweep succeeds. */
+int lslam_sreg_process(lslam_sreg *sr, const void *cloud, size_t n_points, size_t stride_bytes, int64_t scan_time_ns,
+                       lslam_fset *out, size_t counts[4], float imu_trans[12], lslam_sreg_stats *stats);
+/* The last sweep's registered cloud (/velodyne_cloud_2: {x', y', z', ring + relTime}, ring-sorted) and its n_rings x {first,
+ * last} ranges, on request (either pointer may be NULL; *n_out = the cloud's size). */
+int lslam_sreg_cloud(lslam_sreg *sr, float *out_xyzc, size_t cap, size_t *n_out, int32_t *ranges_out);
 
 /* ---- coarse alignment of a loop-closure candidate ------------------------------
  * Replaces LoopDetector::corseMatching (pose_graph/loop_detector.hpp:232-255), i.e.

@@ -1,6 +1,8 @@
-// lslam_pipeline.hpp -- header-only C++ mirrors of the two per-sweep state machines either side of the
+// lslam_pipeline.hpp -- header-only C++ mirrors of the per-sweep state machines either side of the
 // scan-match hot path, over the C ABI (lslam_c.h):
 //
+//   lidar_slam::MultiScanRegistration    odometry/MultiScanRegistration.cpp:78-200 on ScanRegistration.cpp:89-188, :684-707
+//                                        (handleIMUMessage, handleCloudMessage, process: the registration node, lslam_sreg_*)
 //   lidar_slam::LaserOdometry::process   /root/reference/L_SLAM/src/odometry/LaserOdometry.cpp:288-326
 //                                        (+ scanMatch :328-647 = lslam_odometry_match, transformToEnd
 //                                        :156-168 = lslam_transform_to_end, transformUpdate :649-653)
@@ -53,6 +55,98 @@ inline void identity4(float T[16]) {
   T[0] = T[5] = T[10] = T[15] = 1.f;
 }
 }  // namespace detail
+
+// MultiScanRegistration (the first node of the sweep chain): raw driver cloud in, the sweep's four feature lists in HBM out --
+// ring and relTime, the IMU de-skew, the grouping by ring and the feature extraction on the device behind one wait
+// (lslam_sreg_*, include/lslam_c.h).  The ROS side stays the host program's: handleIMUMessage takes the stamp in nanoseconds
+// and the roll / pitch / yaw tf's getRPY gave, handleCloudMessage / process the cloud (any type with `.points` of points with
+// float x, y, z first) and its stamp.  featureSet() is what LaserOdometry::processFeatureSet takes.
+class MultiScanRegistration {
+public:
+  explicit MultiScanRegistration(lslam_ctx *ctx, float lowerBound = -15.f, float upperBound = 15.f, int nScanRings = 16,
+                                 float scanPeriod = 0.1f, const lslam_reg_params *config = nullptr, int imuHistorySize = 200)
+      : _sr(nullptr), _fs(nullptr), _nScanRings(nScanRings), _systemDelay(SYSTEM_DELAY), _cloudReceiveCount(0) {
+    std::memset(_imuTrans, 0, sizeof(_imuTrans));
+    std::memset(_counts, 0, sizeof(_counts));
+    std::memset(&_stats, 0, sizeof(_stats));
+    if (lslam_abi_version() != LSLAM_ABI_VERSION || lslam_sizeof_opts() != sizeof(lslam_opts) || lslam_sizeof_stats() != sizeof(lslam_stats)) {
+      _err = "liblslam_hip was built from another include/lslam_c.h than this program (ABI version / struct sizes differ)";
+      return;
+    }
+    if (lslam_sreg_create(ctx, config, lowerBound, upperBound, nScanRings, scanPeriod, imuHistorySize, &_sr) != LSLAM_OK ||
+        lslam_fset_create(ctx, &_fs) != LSLAM_OK)
+      _err = lslam_last_error();
+  }
+  ~MultiScanRegistration() {
+    if (_sr) lslam_sreg_destroy(_sr);
+    if (_fs) lslam_fset_destroy(_fs);
+  }
+  MultiScanRegistration(const MultiScanRegistration &) = delete;
+  MultiScanRegistration &operator=(const MultiScanRegistration &) = delete;
+  enum { SYSTEM_DELAY = 2 };  // the first clouds of a session are skipped (MultiScanRegistration.cpp:82-85)
+  bool ok() const { return _sr && _fs; }
+  // ScanRegistration::handleIMUMessage after getRPY; false for a stamp that is not later than the previous one
+  bool handleIMUMessage(int64_t stampNs, double roll, double pitch, double yaw, const double linearAcceleration[3]) {
+    if (!ok()) return false;
+    return lslam_sreg_imu_push(_sr, stampNs, roll, pitch, yaw, linearAcceleration) == LSLAM_OK || fail();
+  }
+  bool hasIMUData() const {
+    int32_t n = 0;
+    return _sr && lslam_sreg_imu_info(_sr, &n, nullptr, nullptr) == LSLAM_OK && n > 0;
+  }
+  // false while the system delay lasts (nothing processed) and on a backend error
+  template <typename Cloud>
+  bool handleCloudMessage(const Cloud &laserCloudIn, int64_t stampNs) {
+    ++_cloudReceiveCount;
+    if (_systemDelay > 0) {
+      --_systemDelay;
+      return false;
+    }
+    return process(laserCloudIn, stampNs);
+  }
+  template <typename Cloud>
+  bool process(const Cloud &laserCloudIn, int64_t scanTimeNs) {
+    if (!ok()) return false;
+    const size_t n = laserCloudIn.points.size();
+    const void *p = n ? static_cast<const void *>(&laserCloudIn.points[0]) : nullptr;
+    if (lslam_sreg_process(_sr, p, n, sizeof(laserCloudIn.points[0]), scanTimeNs, _fs, _counts, _imuTrans, &_stats) < 0) return fail();
+    return true;
+  }
+  lslam_fset *featureSet() const { return _fs; }  // /laser_cloud_sharp, _less_sharp, _flat, _less_flat, in HBM
+  const size_t *counts() const { return _counts; }
+  const float *imuTrans() const { return _imuTrans; }  // /imu_trans: four points {x, y, z}
+  // /velodyne_cloud_2 on request: packed {x', y', z', ring + relTime}; ranges (optional): resized to nScanRings x {first, last}
+  bool laserCloud(std::vector<float> &cloud, std::vector<int32_t> *ranges = nullptr) {
+    if (!ok()) return false;
+    cloud.resize(4 * _stats.n_points);
+    if (ranges) ranges->assign(2 * (size_t)(_nScanRings > 0 ? _nScanRings : 0), 0);
+    size_t n = 0;
+    if (lslam_sreg_cloud(_sr, cloud.data(), _stats.n_points, &n, ranges ? ranges->data() : nullptr) < 0) {
+      cloud.clear();
+      return fail();
+    }
+    cloud.resize(4 * n);
+    return true;
+  }
+  const lslam_sreg_stats &nodeStats() const { return _stats; }
+  long cloudReceiveCount() const { return _cloudReceiveCount; }
+  const std::string &lastError() const { return _err; }
+
+private:
+  bool fail() {
+    _err = lslam_last_error();
+    return false;
+  }
+  lslam_sreg *_sr;
+  lslam_fset *_fs;
+  int _nScanRings;
+  int _systemDelay;
+  long _cloudReceiveCount;
+  size_t _counts[4];
+  float _imuTrans[12];
+  lslam_sreg_stats _stats;
+  std::string _err;
+};
 
 // LaserOdometry (variant B, BASELINE configs[0]): first sweep initialises the "last" clouds; afterwards
 // scanMatch against them with the persistent _transform as the initial guess, _Tsum = _Tsum * transform,

@@ -764,6 +764,7 @@ struct MsArgs {
   int32_t *ring;      // -1 = dropped
   float *ori_raw;
   int32_t *first_half;  // index of the first kept point at which halfPassed flips
+  float *rel_out;       // optional: relTime of every kept point on its own (the IMU branch interpolates with it)
 };
 
 __device__ __forceinline__ float ms_mode_a(float ori, float start_ori) {  // :150-156
@@ -810,7 +811,295 @@ __global__ void ms_final_kernel(MsArgs a) {
   }
   const float rel = __fdiv_rn(__fmul_rn(a.scan_period, __fsub_rn(ori, a.start_ori)), __fsub_rn(a.end_ori, a.start_ori));
   a.out[i] = make_float4(p.y, p.z, p.x, __fadd_rn((float)ring, rel));
+  if (a.rel_out) a.rel_out[i] = rel;
 }
+
+// ---- the registration node (lslam_sreg_*): the IMU branch of MultiScanRegistration::process and the ring ranges -----------
+// Per sweep, behind ms_prep_kernel / ms_final_kernel: sr_stats_kernel (points per ring, the workgroups' largest relTime, the
+// last kept point), with an IMU history sr_deskew_kernel (ScanRegistration::setIMUTransformFor + transformToStartIMU, in place
+// on the cloud in arrival order), the stable grouping by ring, sr_ranges_kernel (the IndexRange of every ring and the check of
+// the extraction's ring limit), then the extraction's three launches on the grouped cloud.
+constexpr int SR_BLOCK = 1024;
+constexpr int SR_MAX_HIST = 512;  // IMU states a sweep can see (their time offsets sit in LDS); the reference keeps 200
+struct SrState {    // an IMUState (ScanRegistration.h:122-170) as one sweep sees it
+  double tsec;      // (scanTime - stamp).toSec()
+  double dt_prev;   // (stamp - the previous state's stamp).toSec(); 0 for the oldest
+  float roll, pitch, yaw;
+  float sr, cr, sp, cp, sy, cy;  // what Angle cached on the host when the state was made
+  float pos[3], vel[3];
+  float pad;
+};
+static_assert(sizeof(SrState) == 80, "SrState is uploaded as it is");
+struct SrCtl {  // uploaded with the sweep: {INT32_MAX, -1, 0...}
+  int32_t first_half;  // ms_prep_kernel
+  int32_t last_kept;   // arrival index of the last kept point
+  int32_t pad[14];
+};
+// what comes back behind the node's one wait: the extraction's header, the last kept point's IMU state, the ranges
+constexpr int SR_RES_WORDS = 32;  // [0..15] FxOutArgs::hdr, [16..27] {roll, pitch, yaw, position, velocity, shift}, [28] points kept
+struct SrArgs {
+  float4 *pts;          // {x', y', z', ring + relTime} in arrival order (ms_final_kernel's output), de-skewed in place
+  const int32_t *ring;  // -1 = dropped
+  const float *rel;     // relTime of the kept points; nullptr without an IMU history
+  int n, n_rings;
+  SrCtl *ctl;
+  int32_t *hist;        // [n_rings] points per ring (zeroed by the upload)
+  float *bmax;          // [workgroups] max(0, relTime of the workgroup's kept points)
+  const SrState *states;
+  int n_states;
+  SrState start;        // _imuStart: interpolateIMUStateFor(0), made on the host
+  float *cur_out;       // 12 floats: the state and shift of the last kept point
+};
+
+__global__ __launch_bounds__(SR_BLOCK) void sr_stats_kernel(SrArgs a) {
+  __shared__ int32_t h[4096];
+  __shared__ float wmax[SR_BLOCK / 64];
+  __shared__ int wlast[SR_BLOCK / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int r = tid; r < a.n_rings; r += SR_BLOCK) h[r] = 0;
+  __syncthreads();
+  const int i = blockIdx.x * SR_BLOCK + tid;
+  const int ring = i < a.n ? a.ring[i] : -1;
+  float t = 0.0f;
+  int last = -1;
+  if (ring >= 0 && ring < a.n_rings) {
+    atomicAdd(&h[ring], 1);
+    if (a.rel) t = fmaxf(0.0f, a.rel[i]);
+    last = i;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    t = fmaxf(t, __shfl_xor(t, o, 64));
+    last = max(last, __shfl_xor(last, o, 64));
+  }
+  if (lane == 0) { wmax[wave] = t; wlast[wave] = last; }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int w = 1; w < SR_BLOCK / 64; ++w) { t = fmaxf(t, wmax[w]); last = max(last, wlast[w]); }
+    a.bmax[blockIdx.x] = t;
+    if (last >= 0) atomicMax(&a.ctl->last_kept, last);
+  }
+  for (int r = tid; r < a.n_rings; r += SR_BLOCK)
+    if (h[r]) atomicAdd(&a.hist[r], h[r]);
+}
+
+// sin / cos of a float angle as the correctly rounded float: a double evaluation (accurate to a few double ulp) rounded once --
+// off by a float ulp only where the exact value lies within ~1e-16 of a rounding boundary
+__device__ __forceinline__ float sr_sin(float x) { return (float)sin((double)x); }
+__device__ __forceinline__ float sr_cos(float x) { return (float)cos((double)x); }
+__device__ __forceinline__ void sr_rot(float c, float s, float &u, float &v) {  // u' = c u - s v, v' = s u + c v (rotZ on x, y)
+  const float u0 = u;
+  u = __fsub_rn(__fmul_rn(c, u0), __fmul_rn(s, v));
+  v = __fadd_rn(__fmul_rn(s, u0), __fmul_rn(c, v));
+}
+
+__global__ __launch_bounds__(SR_BLOCK) void sr_deskew_kernel(SrArgs a) {
+  __shared__ double tsec[SR_MAX_HIST];
+  __shared__ float wpart[SR_BLOCK / 64];
+  __shared__ float s_carry;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int k = tid; k < a.n_states; k += SR_BLOCK) tsec[k] = a.states[k].tsec;
+  // the walking index of interpolateIMUStateFor never goes back: it is f(the largest relTime among the kept points so far),
+  // f(t) = the first state with tsec + t <= 0 (or the last state).  The carry of the workgroups before this one ...
+  float c = 0.0f;
+  for (int b = tid; b < (int)blockIdx.x; b += SR_BLOCK) c = fmaxf(c, a.bmax[b]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c = fmaxf(c, __shfl_xor(c, o, 64));
+  if (lane == 0) wpart[wave] = c;
+  __syncthreads();
+  if (tid == 0) {
+    float m = wpart[0];
+#pragma unroll
+    for (int w = 1; w < SR_BLOCK / 64; ++w) m = fmaxf(m, wpart[w]);
+    s_carry = m;
+  }
+  __syncthreads();
+  const float carry = s_carry;
+  // ... and the inclusive prefix maximum inside it (a dropped point contributes the identity, 0)
+  const int i = blockIdx.x * SR_BLOCK + tid;
+  const int ring = i < a.n ? a.ring[i] : -1;
+  const bool kept = ring >= 0 && ring < a.n_rings;
+  const float rel = kept ? a.rel[i] : 0.0f;
+  float pm = kept ? fmaxf(0.0f, rel) : 0.0f;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float u = __shfl_up(pm, o, 64);
+    if (lane >= o) pm = fmaxf(pm, u);
+  }
+  __syncthreads();  // (wpart is read above)
+  if (lane == 63) wpart[wave] = pm;
+  __syncthreads();
+  pm = fmaxf(pm, carry);
+  for (int w = 0; w < wave; ++w) pm = fmaxf(pm, wpart[w]);
+  if (!kept) return;
+  int lo = 0, hi = a.n_states - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (__dadd_rn(tsec[mid], (double)pm) <= 0.0) hi = mid; else lo = mid + 1;
+  }
+  const int idx = lo;
+  const double time_diff = __dadd_rn(tsec[idx], (double)rel);
+  const SrState S = a.states[idx];
+  float roll = S.roll, pitch = S.pitch, yaw = S.yaw, sr = S.sr, cr = S.cr, sp = S.sp, cp = S.cp, sy = S.sy, cy = S.cy;
+  float pos[3] = {S.pos[0], S.pos[1], S.pos[2]}, vel[3] = {S.vel[0], S.vel[1], S.vel[2]};
+  if (!(idx == 0 || time_diff > 0.0)) {  // IMUState::interpolate(history[idx], history[idx - 1], ratio)
+    const SrState E = a.states[idx - 1];
+    const float ratio = (float)(-time_diff / S.dt_prev);
+    const float inv = __fsub_rn(1.0f, ratio);
+    roll = __fadd_rn(__fmul_rn(S.roll, inv), __fmul_rn(E.roll, ratio));
+    pitch = __fadd_rn(__fmul_rn(S.pitch, inv), __fmul_rn(E.pitch, ratio));
+    const double dyaw = (double)__fsub_rn(S.yaw, E.yaw);
+    if (dyaw > M_PI) yaw = (float)__dadd_rn((double)__fmul_rn(S.yaw, inv), __dmul_rn(__dadd_rn((double)E.yaw, 2 * M_PI), (double)ratio));
+    else if (dyaw < -M_PI) yaw = (float)__dadd_rn((double)__fmul_rn(S.yaw, inv), __dmul_rn(__dsub_rn((double)E.yaw, 2 * M_PI), (double)ratio));
+    else yaw = __fadd_rn(__fmul_rn(S.yaw, inv), __fmul_rn(E.yaw, ratio));
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      vel[d] = __fadd_rn(__fmul_rn(S.vel[d], inv), __fmul_rn(E.vel[d], ratio));
+      pos[d] = __fadd_rn(__fmul_rn(S.pos[d], inv), __fmul_rn(E.pos[d], ratio));
+    }
+    sr = sr_sin(roll); cr = sr_cos(roll);
+    sp = sr_sin(pitch); cp = sr_cos(pitch);
+    sy = sr_sin(yaw); cy = sr_cos(yaw);
+  }
+  // setIMUTransformFor: the sweep starts at the scan time, so relSweepTime is relTime
+  float shift[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) shift[d] = __fsub_rn(__fsub_rn(pos[d], a.start.pos[d]), __fmul_rn(a.start.vel[d], rel));
+  // transformToStartIMU: rotateZXY(p, roll, pitch, yaw), + shift, rotateYXZ(p, -start.yaw, -start.pitch, -start.roll)
+  float4 p = a.pts[i];
+  sr_rot(cr, sr, p.x, p.y);                    // rotZ
+  sr_rot(cp, sp, p.y, p.z);                    // rotX
+  sr_rot(cy, sy, p.z, p.x);                    // rotY: z' = c z - s x, x' = s z + c x
+  p.x = __fadd_rn(p.x, shift[0]);
+  p.y = __fadd_rn(p.y, shift[1]);
+  p.z = __fadd_rn(p.z, shift[2]);
+  sr_rot(a.start.cy, -a.start.sy, p.z, p.x);   // -angle: the sine negated, the cosine kept (Angle::operator-)
+  sr_rot(a.start.cp, -a.start.sp, p.y, p.z);
+  sr_rot(a.start.cr, -a.start.sr, p.x, p.y);
+  a.pts[i] = p;
+  if (i == a.ctl->last_kept) {  // _imuCur and _imuPositionShift as the sweep leaves them
+    a.cur_out[0] = roll; a.cur_out[1] = pitch; a.cur_out[2] = yaw;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { a.cur_out[3 + d] = pos[d]; a.cur_out[6 + d] = vel[d]; a.cur_out[9 + d] = shift[d]; }
+  }
+}
+
+// IndexRange(first, last) of every ring (MultiScanRegistration.cpp:184-189: an empty ring is {size, size - 1}, {0, 0} at the
+// front) from the points per ring; one workgroup.  ranges_fx is what the extraction reads: the same, or every ring empty when
+// nothing was kept or a ring has more points than the extraction holds in LDS (hdr[4] = 3: the call fails behind its wait)
+__global__ __launch_bounds__(FX_BLOCK) void sr_ranges_kernel(const int32_t *hist, int n_rings, int32_t *ranges_out, int32_t *ranges_fx,
+                                                             uint32_t *res) {
+  __shared__ int part[FX_BLOCK];
+  const int tid = threadIdx.x;
+  const int per = (n_rings + FX_BLOCK - 1) / FX_BLOCK;
+  const int r0 = min(n_rings, tid * per), r1 = min(n_rings, r0 + per);
+  int sum = 0, big = 0;
+  for (int r = r0; r < r1; ++r) {
+    sum += hist[r];
+    big |= hist[r] > MAXR ? 1 : 0;
+  }
+  int total;
+  int run = fx_block_scan(sum, part, &total);
+  const int bad = __syncthreads_or(big);
+  const bool none = bad || total == 0;
+  for (int r = r0; r < r1; ++r) {
+    const int first = run;
+    run += hist[r];
+    const int last = run > 0 ? run - 1 : 0;
+    ranges_out[2 * r] = first;
+    ranges_out[2 * r + 1] = last;
+    ranges_fx[2 * r] = none ? 0 : first;
+    ranges_fx[2 * r + 1] = none ? -1 : last;
+  }
+  if (tid == 0) {
+    res[28] = (uint32_t)total;
+    if (bad) res[4] = 3u;
+  }
+}
+
+// the launch sequence's device arrays, carved from one blob of fx_work_bytes
+struct FxWork {
+  float4 *pts;                // the ring-sorted cloud {x, y, z, intensity-to-copy}
+  int32_t *st[4];             // per list: cloud indices of the picks, ring r's from its first index on
+  int32_t *ranges, *counts;   // [n_scans][2] {first, last}, [n_scans][4]
+  float *curv;                // taps
+  int8_t *picked, *label;
+  int32_t *ring_out;          // centroids per ring (fx_ring_voxel_kernel)
+  float4 *vox;                // ... and the centroids, ring r's from its first index on
+  int32_t *cls, *ready;       // the classify helpers' (fx_ring_kernel)
+};
+size_t fx_work_bytes(size_t n_points, size_t n_scans) {
+  const size_t np4 = n_points * sizeof(float4);
+  return 5 * np4 + 2 * n_scans * 4 + 4 * n_scans * 4 + n_points * 4 + 2 * n_points + (n_scans + 1) * 4 + np4 + n_points * 4 +
+         n_scans * 4 + 256 + 18 * 16;
+}
+void fx_carve(char *blob, size_t n_points, size_t n_scans, FxWork &w) {
+  const size_t np4 = n_points * sizeof(float4);
+  char *q = blob;
+  auto take = [&](size_t b) { char *r = q; q += (b + 15) & ~(size_t)15; return r; };
+  w.pts = (float4 *)take(np4);
+  for (int k = 0; k < 4; ++k) w.st[k] = (int32_t *)take(np4);
+  w.ranges = (int32_t *)take(2 * n_scans * 4);
+  w.counts = (int32_t *)take(4 * n_scans * 4);
+  w.curv = (float *)take(n_points * 4);
+  w.picked = (int8_t *)take(n_points);
+  w.label = (int8_t *)take(n_points);
+  w.ring_out = (int32_t *)take((n_scans + 1) * 4);
+  w.vox = (float4 *)take(np4);
+  w.cls = (int32_t *)take(n_points * 4);
+  w.ready = (int32_t *)take(n_scans * 4);
+}
+// ScanRegistration::extractFeatures on the cloud and ranges in w (device memory both): the three launches every entry point
+// shares -- the host-cloud ones and the resident registration node.  out: sixteen header slots, then four slices of `cap`
+// points; hdr: [0..2] totals of the small lists, [3] less-flat points, [4] error (zeroed by the caller).  Nothing is waited for.
+hipError_t fx_enqueue(hipStream_t s, const lslam_reg_params &prm, const FxWork &w, size_t n_points, size_t n_scans, bool tap_curv,
+                      bool tap_picked, bool tap_label, float4 *out, uint32_t *hdr, size_t cap) {
+  hipError_t e;
+  if (tap_curv && (e = hipMemsetAsync(w.curv, 0, n_points * 4, s)) != hipSuccess) return e;
+  if (tap_picked && (e = hipMemsetAsync(w.picked, 0, n_points, s)) != hipSuccess) return e;
+  if (tap_label && (e = hipMemsetAsync(w.label, L_UNKNOW, n_points, s)) != hipSuccess) return e;
+  FxArgs a{};
+  a.pts = w.pts;
+  a.ranges = w.ranges;
+  a.n_scans = (int32_t)n_scans;
+  a.nf = prm.n_feature_regions;
+  a.cr = prm.curvature_region;
+  a.max_sharp = prm.max_corner_sharp;
+  a.max_flat = prm.max_surface_flat;
+  a.surf_thr = prm.surface_curvature_threshold;
+  a.blind_thr = prm.blind_threshold;
+  a.c175 = std::cos(175.0 * M_PI / 180.0);  // deg2rad(double), util/math_utils.h:29
+  a.c5 = std::cos(5.0 * M_PI / 180.0);
+  a.c135 = std::cos(135.0 * M_PI / 180.0);
+  a.c45 = std::cos(45.0 * M_PI / 180.0);
+  a.st_sharp = w.st[0]; a.st_less_sharp = w.st[1]; a.st_flat = w.st[2]; a.st_less_flat = w.st[3];
+  a.counts = w.counts;
+  a.curv_out = tap_curv ? w.curv : nullptr;
+  a.picked_out = tap_picked ? w.picked : nullptr;
+  a.label_out = tap_label ? w.label : nullptr;
+  a.helpers = lslam::env_once().fx_helpers;
+  a.cls_g = w.cls;
+  a.ready = w.ready;
+  if (a.helpers > 0 && (e = hipMemsetAsync(w.ready, 0, n_scans * 4, s)) != hipSuccess) return e;
+  hipLaunchKernelGGL(fx_ring_kernel, dim3((unsigned)n_scans * (unsigned)(1 + a.helpers)), dim3(FX_BLOCK), 0, s, a);
+  FxOutArgs oa{};
+  oa.pts = w.pts;
+  oa.ranges = w.ranges;
+  oa.counts = w.counts;
+  for (int k = 0; k < 4; ++k) oa.stage[k] = w.st[k];
+  oa.n_scans = (int32_t)n_scans;
+  oa.cap = (int32_t)cap;
+  oa.inv_leaf = 1.0f / prm.less_flat_filter_size;
+  oa.vox_stage = w.vox;
+  oa.ring_out = w.ring_out;
+  oa.host = out;
+  oa.hdr = hdr;
+  hipLaunchKernelGGL(fx_ring_voxel_kernel, dim3((unsigned)n_scans + 3u), dim3(FX_BLOCK), 0, s, oa);
+  hipLaunchKernelGGL(fx_lessflat_out_kernel, dim3((unsigned)n_scans), dim3(FX_BLOCK), 0, s, oa);
+  return hipGetLastError();
+}
+
 
 // what the two entry points keep in their context between calls (lslam::ctx_slot); each blob is carved into the call's arrays
 struct FxCache {  // extract_features_impl
@@ -943,20 +1232,13 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
       h[i] = make_float4(v[0], v[1], v[2], w);
     }
   }
-  const size_t bytes = 5 * np4 + 2 * n_scans * 4 + 4 * n_scans * 4 + n_points * 4 + 2 * n_points + (n_scans + 1) * 4 + np4 + n_points * 4 +
-                       n_scans * 4 + 256 + 18 * 16;
-  FX_TRY(cache.blob.reserve(bytes));
-  char *blob = cache.blob.p;
-  char *q = blob;
-  auto take = [&](size_t b) { char *r = q; q += (b + 15) & ~(size_t)15; return r; };
-  float4 *d_pts = (float4 *)take(np4);
-  int32_t *st0 = (int32_t *)take(np4), *st1 = (int32_t *)take(np4), *st2 = (int32_t *)take(np4), *st3 = (int32_t *)take(np4);
-  int32_t *d_ranges = (int32_t *)take(2 * n_scans * 4), *d_counts = (int32_t *)take(4 * n_scans * 4);
-  float *d_curv = (float *)take(n_points * 4);
-  int8_t *d_picked = (int8_t *)take(n_points), *d_label = (int8_t *)take(n_points);
-  int32_t *d_ring_out = (int32_t *)take((n_scans + 1) * 4);  // centroids per ring (fx_ring_voxel_kernel)
-  float4 *d_vox = (float4 *)take(np4);                       // ... and the centroids, ring r's from its first index on
-  int32_t *d_cls = (int32_t *)take(n_points * 4), *d_ready = (int32_t *)take(n_scans * 4);  // the classify helpers' (fx_ring_kernel)
+  FX_TRY(cache.blob.reserve(fx_work_bytes(n_points, n_scans)));
+  FxWork w;
+  fx_carve(cache.blob.p, n_points, n_scans, w);
+  float4 *d_pts = w.pts;
+  int32_t *d_ranges = w.ranges;
+  float *d_curv = w.curv;
+  int8_t *d_picked = w.picked, *d_label = w.label;
   int rc = LSLAM_OK;
   auto fail = [&](int code) { return code; };
 #define FX_TRY2(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { lslam::set_error(hipGetErrorString(_e)); return fail(LSLAM_ERR_HIP); } } while (0)
@@ -971,33 +1253,6 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
     FX_TRY2(hipMemcpyAsync(d_pts, h, np4, hipMemcpyHostToDevice, s));
   }
   FX_TRY2(hipMemcpyAsync(d_ranges, scan_ranges, 2 * n_scans * 4, hipMemcpyHostToDevice, s));
-  if (curvature_out) FX_TRY2(hipMemsetAsync(d_curv, 0, n_points * 4, s));
-  if (picked_out) FX_TRY2(hipMemsetAsync(d_picked, 0, n_points, s));
-  if (label_out) FX_TRY2(hipMemsetAsync(d_label, L_UNKNOW, n_points, s));
-  FxArgs a{};
-  a.pts = d_pts;
-  a.ranges = d_ranges;
-  a.n_scans = (int32_t)n_scans;
-  a.nf = prm.n_feature_regions;
-  a.cr = prm.curvature_region;
-  a.max_sharp = prm.max_corner_sharp;
-  a.max_flat = prm.max_surface_flat;
-  a.surf_thr = prm.surface_curvature_threshold;
-  a.blind_thr = prm.blind_threshold;
-  a.c175 = std::cos(175.0 * M_PI / 180.0);  // deg2rad(double), util/math_utils.h:29
-  a.c5 = std::cos(5.0 * M_PI / 180.0);
-  a.c135 = std::cos(135.0 * M_PI / 180.0);
-  a.c45 = std::cos(45.0 * M_PI / 180.0);
-  a.st_sharp = st0; a.st_less_sharp = st1; a.st_flat = st2; a.st_less_flat = st3;
-  a.counts = d_counts;
-  a.curv_out = curvature_out ? d_curv : nullptr;
-  a.picked_out = picked_out ? d_picked : nullptr;
-  a.label_out = label_out ? d_label : nullptr;
-  a.helpers = lslam::env_once().fx_helpers;
-  a.cls_g = d_cls;
-  a.ready = d_ready;
-  if (a.helpers > 0) FX_TRY2(hipMemsetAsync(d_ready, 0, n_scans * 4, s));
-  hipLaunchKernelGGL(fx_ring_kernel, dim3((unsigned)n_scans * (unsigned)(1 + a.helpers)), dim3(FX_BLOCK), 0, s, a);
   // the four lists, on the device to the end (see fx_lists_block): nothing waits until everything is in pinned memory
   uint32_t *hdr = reinterpret_cast<uint32_t *>(cache.pout.p);
   for (int k = 0; k < 8; ++k) hdr[k] = 0u;
@@ -1005,22 +1260,9 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
     FX_TRY2(lslam::fset_reserve(dev_out, n_points));
     FX_TRY2(hipMemsetAsync(dev_out->buf.p, 0, 8 * sizeof(uint32_t), s));
   }
-  FxOutArgs oa{};
-  oa.pts = d_pts;
-  oa.ranges = d_ranges;
-  oa.counts = d_counts;
-  oa.stage[0] = st0; oa.stage[1] = st1; oa.stage[2] = st2; oa.stage[3] = st3;
-  oa.n_scans = (int32_t)n_scans;
-  oa.cap = (int32_t)n_points;
-  oa.inv_leaf = 1.0f / prm.less_flat_filter_size;
-  oa.vox_stage = d_vox;
-  oa.ring_out = d_ring_out;
-  oa.host = dev_out ? dev_out->buf.p : cache.pout.p;
-  oa.hdr = dev_out ? reinterpret_cast<uint32_t *>(dev_out->buf.p) : hdr;
-  if (dev_out) oa.cap = (int32_t)dev_out->cap;
-  hipLaunchKernelGGL(fx_ring_voxel_kernel, dim3((unsigned)n_scans + 3u), dim3(FX_BLOCK), 0, s, oa);
-  hipLaunchKernelGGL(fx_lessflat_out_kernel, dim3((unsigned)n_scans), dim3(FX_BLOCK), 0, s, oa);
-  FX_TRY2(hipGetLastError());
+  FX_TRY2(fx_enqueue(s, prm, w, n_points, n_scans, curvature_out != nullptr, picked_out != nullptr, label_out != nullptr,
+                     dev_out ? dev_out->buf.p : cache.pout.p, dev_out ? reinterpret_cast<uint32_t *>(dev_out->buf.p) : hdr,
+                     dev_out ? dev_out->cap : n_points));
   if (curvature_out) FX_TRY2(hipMemcpyAsync(curvature_out, d_curv, n_points * 4, hipMemcpyDeviceToHost, s));
   if (picked_out) FX_TRY2(hipMemcpyAsync(picked_out, d_picked, n_points, hipMemcpyDeviceToHost, s));
   if (label_out) FX_TRY2(hipMemcpyAsync(label_out, d_label, n_points, hipMemcpyDeviceToHost, s));
@@ -1117,6 +1359,411 @@ int lslam_multiscan_register(lslam_ctx *ctx, const void *cloud, size_t n_points,
     ranges_out[2 * r + 1] = total > 0 ? (int32_t)total - 1 : 0;
   }
   *n_out = m;
+  return LSLAM_OK;
+}
+
+// ---- the registration node resident on the device (include/lslam_c.h lslam_sreg_*) ---------------------------------------
+}  // extern "C"
+
+namespace {
+#define SR_TRY(expr) FX_TRY(expr)
+struct SrImu {  // an IMUState on the host; the Angles with the sin / cos they cached when they were made (Angle(float))
+  int64_t stamp = 0;
+  float roll = 0.f, pitch = 0.f, yaw = 0.f;
+  float sr = 0.f, cr = 1.f, sp = 0.f, cp = 1.f, sy = 0.f, cy = 1.f;
+  float pos[3] = {0.f, 0.f, 0.f}, vel[3] = {0.f, 0.f, 0.f};
+};
+// ros::Duration::toSec() of an exact nanosecond difference: sec + 1e-9 * nsec with 0 <= nsec < 1e9
+double sr_to_sec(int64_t d) {
+  int64_t sec = d / 1000000000ll, nsec = d % 1000000000ll;
+  if (nsec < 0) { nsec += 1000000000ll; sec -= 1; }
+  return (double)sec + 1e-9 * (double)nsec;
+}
+void sr_rot_h(float c, float s, float &u, float &v) {
+  const float u0 = u;
+  u = c * u0 - s * v;
+  v = s * u0 + c * v;
+}
+void sr_set_angles(SrImu &st, float roll, float pitch, float yaw) {  // three Angle(float)
+  st.roll = roll; st.pitch = pitch; st.yaw = yaw;
+  st.sr = std::sin(roll); st.cr = std::cos(roll);
+  st.sp = std::sin(pitch); st.cp = std::cos(pitch);
+  st.sy = std::sin(yaw); st.cy = std::cos(yaw);
+}
+void sr_rotate_yxz_neg(const SrImu &st, float v[3]) {  // rotateYXZ(v, -yaw, -pitch, -roll)
+  sr_rot_h(st.cy, -st.sy, v[2], v[0]);
+  sr_rot_h(st.cp, -st.sp, v[1], v[2]);
+  sr_rot_h(st.cr, -st.sr, v[0], v[1]);
+}
+size_t sr_up16(size_t b) { return (b + 15) & ~(size_t)15; }
+}  // namespace
+
+struct lslam_sreg {
+  lslam_ctx *ctx = nullptr;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  lslam_reg_params prm;
+  float lower = 0.f, upper = 0.f, scan_period = 0.1f;
+  int32_t n_rings = 0;
+  // _imuHistory (CircularBuffer.h): `size` states from `first` on, the oldest overwritten when full
+  std::vector<SrImu> hist;
+  size_t first = 0, size = 0;
+  SrImu start, cur;             // _imuStart, _imuCur
+  float shift[3] = {0.f, 0.f, 0.f};  // _imuPositionShift
+  uint64_t sweeps = 0;
+  // the last sweep's registered cloud, for lslam_sreg_cloud
+  size_t last_m = 0;
+  bool last_valid = false;
+  float4 *d_sorted = nullptr;
+  lslam::PinBuf<char> h_in;        // what a sweep uploads in one copy: control words, result words, ranges, ring counts, IMU states, cloud
+  lslam::PinBuf<uint32_t> h_res;   // what comes back: SR_RES_WORDS, then the ranges
+  lslam::PinBuf<uint32_t> done;    // the grouping's {points out, key-range error, -}
+  lslam::DevBuf<char> d_in, d_work;
+  const SrImu &at(size_t k) const { return hist[(first + k) % hist.size()]; }
+};
+
+extern "C" {
+
+int lslam_sreg_create(lslam_ctx *ctx, const lslam_reg_params *params, float lower_deg, float upper_deg, int32_t n_rings,
+                      float scan_period, int32_t imu_history_size, lslam_sreg **out) {
+  if (out) *out = nullptr;
+  if (!ctx || !lslam::ctx_alive(ctx)) {
+    lslam::set_error("lslam_sreg_create: null context, or it was destroyed");
+    return LSLAM_ERR_INVALID;
+  }
+  lslam_reg_params prm;
+  if (params) prm = *params; else lslam_reg_default_params(&prm);
+  if (!out || n_rings <= 0 || n_rings > 4096 || !(upper_deg > lower_deg) || !(scan_period > 0.f) || imu_history_size < 1 ||
+      imu_history_size > SR_MAX_HIST || prm.curvature_region < 1 || prm.curvature_region > 16 || prm.n_feature_regions < 1 ||
+      prm.n_feature_regions > 512 || !(prm.less_flat_filter_size > 0.f)) {
+    lslam::set_error("lslam_sreg_create: bad registration arguments (rings 1..4096, upper > lower, IMU history 1..512)");
+    return LSLAM_ERR_INVALID;
+  }
+  lslam_sreg *sr = new lslam_sreg();
+  sr->ctx = ctx;
+  sr->device = lslam::ctx_device(ctx);
+  sr->stream = (hipStream_t)lslam_stream(ctx);
+  sr->prm = prm;
+  sr->lower = lower_deg; sr->upper = upper_deg; sr->n_rings = n_rings; sr->scan_period = scan_period;
+  sr->hist.resize((size_t)imu_history_size);
+  *out = sr;
+  return LSLAM_OK;
+}
+
+void lslam_sreg_destroy(lslam_sreg *sr) {
+  if (!sr) return;
+  if (lslam::ctx_alive(sr->ctx)) {  // a node may outlive its context; the stream is then gone (and was waited for)
+    (void)hipSetDevice(sr->device);
+    (void)hipStreamSynchronize(sr->stream);
+  }
+  delete sr;
+}
+
+int lslam_sreg_imu_push(lslam_sreg *sr, int64_t stamp_ns, double roll, double pitch, double yaw, const double linear_acceleration[3]) {
+  if (!sr) {
+    lslam::set_error("lslam_sreg_imu_push: null node");
+    return LSLAM_ERR_INVALID;
+  }
+  if (!linear_acceleration) {
+    lslam::set_error("lslam_sreg_imu_push: no acceleration");
+    return LSLAM_ERR_INVALID;
+  }
+  if (sr->size && stamp_ns <= sr->at(sr->size - 1).stamp) {
+    lslam::set_error("lslam_sreg_imu_push: the stamp is not later than the previous state's");
+    return LSLAM_ERR_INVALID;
+  }
+  const double *la = linear_acceleration;
+  // handleIMUMessage, ScanRegistration.cpp:96-117
+  float acc[3];
+  acc[0] = float(la[1] - std::sin(roll) * std::cos(pitch) * 9.81);
+  acc[1] = float(la[2] - std::cos(roll) * std::cos(pitch) * 9.81);
+  acc[2] = float(la[0] + std::sin(pitch) * 9.81);
+  SrImu st;
+  st.stamp = stamp_ns;
+  sr_set_angles(st, (float)roll, (float)pitch, (float)yaw);
+  if (sr->size) {
+    sr_rot_h(st.cr, st.sr, acc[0], acc[1]);  // rotateZXY(acc, roll, pitch, yaw)
+    sr_rot_h(st.cp, st.sp, acc[1], acc[2]);
+    sr_rot_h(st.cy, st.sy, acc[2], acc[0]);
+    const SrImu &prev = sr->at(sr->size - 1);
+    const float dt = float(sr_to_sec(stamp_ns - prev.stamp));
+    for (int d = 0; d < 3; ++d) {
+      st.pos[d] = (prev.pos[d] + prev.vel[d] * dt) + ((0.5f * acc[d]) * dt) * dt;
+      st.vel[d] = prev.vel[d] + acc[d] * dt;
+    }
+  }
+  const size_t cap = sr->hist.size();
+  if (sr->size < cap) {
+    sr->hist[(sr->first + sr->size) % cap] = st;
+    sr->size++;
+  } else {
+    sr->hist[sr->first] = st;
+    sr->first = (sr->first + 1) % cap;
+  }
+  return LSLAM_OK;
+}
+
+int lslam_sreg_imu_info(const lslam_sreg *sr, int32_t *size, double last_position[3], double last_velocity[3]) {
+  if (size) *size = 0;
+  for (int d = 0; d < 3; ++d) {
+    if (last_position) last_position[d] = 0.0;
+    if (last_velocity) last_velocity[d] = 0.0;
+  }
+  if (!sr) {
+    lslam::set_error("lslam_sreg_imu_info: null node");
+    return LSLAM_ERR_INVALID;
+  }
+  if (size) *size = (int32_t)sr->size;
+  if (sr->size) {
+    const SrImu &l = sr->at(sr->size - 1);
+    for (int d = 0; d < 3; ++d) {
+      if (last_position) last_position[d] = (double)l.pos[d];
+      if (last_velocity) last_velocity[d] = (double)l.vel[d];
+    }
+  }
+  return LSLAM_OK;
+}
+
+int lslam_sreg_imu_clear(lslam_sreg *sr) {
+  if (!sr) {
+    lslam::set_error("lslam_sreg_imu_clear: null node");
+    return LSLAM_ERR_INVALID;
+  }
+  sr->first = sr->size = 0;
+  sr->start = SrImu();
+  sr->cur = SrImu();
+  sr->shift[0] = sr->shift[1] = sr->shift[2] = 0.f;
+  return LSLAM_OK;
+}
+
+int lslam_sreg_process(lslam_sreg *sr, const void *cloud, size_t n_points, size_t stride_bytes, int64_t scan_time_ns, lslam_fset *out,
+                       size_t counts[4], float imu_trans[12], lslam_sreg_stats *stats) {
+  if (counts) for (int k = 0; k < 4; ++k) counts[k] = 0;
+  if (imu_trans) for (int k = 0; k < 12; ++k) imu_trans[k] = 0.f;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!sr) {
+    lslam::set_error("lslam_sreg_process: null node");
+    return LSLAM_ERR_INVALID;
+  }
+  if (!lslam::ctx_alive(sr->ctx)) {
+    lslam::set_error("lslam_sreg_process: the node's context was destroyed");
+    return LSLAM_ERR_INVALID;
+  }
+  if (!out || out->device != sr->device) {
+    lslam::set_error("lslam_sreg_process: no feature set, or it lives on another device");
+    return LSLAM_ERR_INVALID;
+  }
+  for (int k = 0; k < 4; ++k) out->counts[k] = 0;
+  if (!cloud || n_points == 0 || n_points > 0x3FFFFFFFu || stride_bytes < 12 || (stride_bytes & 3)) {
+    lslam::set_error("lslam_sreg_process: empty cloud or bad stride");
+    return LSLAM_ERR_INVALID;
+  }
+  SR_TRY(hipSetDevice(sr->device));
+  hipStream_t s = sr->stream;
+  sr->last_valid = false;
+  const size_t n = n_points, R = (size_t)sr->n_rings, K = sr->size;
+  const bool imu = K > 0;  // hasIMUData()
+  // ---- what goes up, in one block: [SrCtl][result words][ranges][points per ring][IMU states][cloud] --------------------------
+  const size_t o_res = sr_up16(sizeof(SrCtl)), o_ranges = o_res + SR_RES_WORDS * 4, o_hist = o_ranges + sr_up16(2 * R * 4),
+               o_states = o_hist + sr_up16(R * 4), o_cloud = o_states + sr_up16(K * sizeof(SrState)),
+               in_bytes = o_cloud + n * sizeof(float4);
+  SR_TRY(sr->h_in.reserve(in_bytes));
+  SR_TRY(sr->d_in.reserve(in_bytes));
+  SR_TRY(sr->h_res.reserve(SR_RES_WORDS + 2 * R));
+  SR_TRY(sr->done.reserve(4));
+  char *hb = sr->h_in.p;
+  std::memset(hb, 0, o_cloud);
+  SrCtl *hctl = reinterpret_cast<SrCtl *>(hb);
+  hctl->first_half = INT32_MAX;
+  hctl->last_kept = -1;
+  float4 *h = reinterpret_cast<float4 *>(hb + o_cloud);
+  const char *src = static_cast<const char *>(cloud);
+  if (stride_bytes == 16) {
+    std::memcpy(h, src, n * sizeof(float4));  // (the fourth float is never read)
+  } else {
+    for (size_t i = 0; i < n; ++i) {
+      float v[3];
+      std::memcpy(v, src + i * stride_bytes, 12);
+      h[i] = make_float4(v[0], v[1], v[2], 0.0f);
+    }
+  }
+  // sweep start / end orientation (MultiScanRegistration.cpp:101-109), on the host with the C library the reference uses
+  float start_ori = -std::atan2(h[0].y, h[0].x);
+  float end_ori = -std::atan2(h[n - 1].y, h[n - 1].x) + 2 * float(M_PI);
+  if (end_ori - start_ori > 3 * M_PI) end_ori -= 2 * M_PI;
+  else if (end_ori - start_ori < M_PI) end_ori += 2 * M_PI;
+  // ---- reset(scanTime): _imuIdx = 0, interpolateIMUStateFor(0, _imuStart) -- on the host, as the reference does it ---------
+  SrImu start = sr->start;
+  SrState dstart{};
+  if (imu) {
+    SrState *hs = reinterpret_cast<SrState *>(hb + o_states);
+    for (size_t k = 0; k < K; ++k) {
+      const SrImu &st = sr->at(k);
+      SrState &d = hs[k];
+      d.tsec = sr_to_sec(scan_time_ns - st.stamp);
+      d.dt_prev = k ? sr_to_sec(st.stamp - sr->at(k - 1).stamp) : 0.0;
+      d.roll = st.roll; d.pitch = st.pitch; d.yaw = st.yaw;
+      d.sr = st.sr; d.cr = st.cr; d.sp = st.sp; d.cp = st.cp; d.sy = st.sy; d.cy = st.cy;
+      for (int c = 0; c < 3; ++c) { d.pos[c] = st.pos[c]; d.vel[c] = st.vel[c]; }
+    }
+    size_t idx = 0;
+    double time_diff = hs[0].tsec + 0.0f;
+    while (idx < K - 1 && time_diff > 0) time_diff = hs[++idx].tsec + 0.0f;
+    const SrImu &S = sr->at(idx);
+    if (idx == 0 || time_diff > 0) {
+      start = S;
+    } else {
+      const SrImu &E = sr->at(idx - 1);
+      const float ratio = -time_diff / hs[idx].dt_prev;
+      const float inv = 1 - ratio;
+      float yaw;
+      if (S.yaw - E.yaw > M_PI) yaw = S.yaw * inv + (E.yaw + 2 * M_PI) * ratio;
+      else if (S.yaw - E.yaw < -M_PI) yaw = S.yaw * inv + (E.yaw - 2 * M_PI) * ratio;
+      else yaw = S.yaw * inv + E.yaw * ratio;
+      sr_set_angles(start, S.roll * inv + E.roll * ratio, S.pitch * inv + E.pitch * ratio, yaw);
+      for (int c = 0; c < 3; ++c) {
+        start.vel[c] = S.vel[c] * inv + E.vel[c] * ratio;
+        start.pos[c] = S.pos[c] * inv + E.pos[c] * ratio;
+      }
+    }
+    dstart.roll = start.roll; dstart.pitch = start.pitch; dstart.yaw = start.yaw;
+    dstart.sr = start.sr; dstart.cr = start.cr; dstart.sp = start.sp; dstart.cp = start.cp; dstart.sy = start.sy; dstart.cy = start.cy;
+    for (int c = 0; c < 3; ++c) { dstart.pos[c] = start.pos[c]; dstart.vel[c] = start.vel[c]; }
+  }
+  // ---- device arrays -----------------------------------------------------------------------------------------------------
+  const size_t nblk = (n + SR_BLOCK - 1) / SR_BLOCK;
+  const size_t np4 = n * sizeof(float4);
+  const size_t o_ring = sr_up16(np4), o_seg = o_ring + sr_up16(n * 4), o_ori = o_seg + sr_up16(n * 4), o_rel = o_ori + sr_up16(n * 4),
+               o_bmax = o_rel + sr_up16(n * 4), o_fx = o_bmax + sr_up16(nblk * 4);
+  SR_TRY(sr->d_work.reserve(o_fx + fx_work_bytes(n, R)));
+  char *wb = sr->d_work.p, *db = sr->d_in.p;
+  float4 *d_tmp = (float4 *)wb;
+  int32_t *d_ring = (int32_t *)(wb + o_ring), *d_seg = (int32_t *)(wb + o_seg);
+  float *d_ori = (float *)(wb + o_ori), *d_rel = (float *)(wb + o_rel), *d_bmax = (float *)(wb + o_bmax);
+  FxWork w;
+  fx_carve(wb + o_fx, n, R, w);
+  uint32_t *d_res = (uint32_t *)(db + o_res);
+  int32_t *d_ranges_out = (int32_t *)(db + o_ranges), *d_hist = (int32_t *)(db + o_hist);
+  SR_TRY(lslam::fset_reserve(out, n));
+  SR_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, s));
+  MsArgs a{};
+  a.in = (const float4 *)(db + o_cloud);
+  a.n = (int)n;
+  a.n_rings = sr->n_rings;
+  a.lower = sr->lower;
+  a.factor = (sr->n_rings - 1) / (sr->upper - sr->lower);  // MultiScanRegistration.h:63
+  a.scan_period = sr->scan_period;
+  a.start_ori = start_ori;
+  a.end_ori = end_ori;
+  a.out = d_tmp;
+  a.ring = d_ring;
+  a.ori_raw = d_ori;
+  a.first_half = &reinterpret_cast<SrCtl *>(db)->first_half;
+  a.rel_out = imu ? d_rel : nullptr;
+  const dim3 grd((unsigned)((n + 255) / 256)), blk(256);
+  hipLaunchKernelGGL(ms_prep_kernel, grd, blk, 0, s, a);
+  hipLaunchKernelGGL(ms_final_kernel, grd, blk, 0, s, a);
+  SrArgs sa{};
+  sa.pts = d_tmp;
+  sa.ring = d_ring;
+  sa.rel = imu ? d_rel : nullptr;
+  sa.n = (int)n;
+  sa.n_rings = sr->n_rings;
+  sa.ctl = reinterpret_cast<SrCtl *>(db);
+  sa.hist = d_hist;
+  sa.bmax = d_bmax;
+  sa.states = (const SrState *)(db + o_states);
+  sa.n_states = (int)K;
+  sa.start = dstart;
+  sa.cur_out = reinterpret_cast<float *>(d_res + 16);
+  hipLaunchKernelGGL(sr_stats_kernel, dim3((unsigned)nblk), dim3(SR_BLOCK), 0, s, sa);
+  if (imu) hipLaunchKernelGGL(sr_deskew_kernel, dim3((unsigned)nblk), dim3(SR_BLOCK), 0, s, sa);
+  // per-ring clouds in arrival order (:178-190): a stable grouping by ring; nothing is waited for
+  sr->done.p[0] = sr->done.p[1] = sr->done.p[2] = 0;
+  size_t m_unused = 0;
+  int rc = lslam::voxel_filter_segments(sr->ctx, d_tmp, d_ring, n, sr->n_rings, 1.0f, w.pts, d_seg, &m_unused, false, sr->done.p);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  hipLaunchKernelGGL(sr_ranges_kernel, dim3(1), dim3(FX_BLOCK), 0, s, d_hist, sr->n_rings, d_ranges_out, w.ranges, d_res);
+  hipError_t e = fx_enqueue(s, sr->prm, w, n, R, false, false, false, out->buf.p, d_res, out->cap);
+  if (e == hipSuccess) e = hipMemcpyAsync(sr->h_res.p, d_res, (SR_RES_WORDS + 2 * R) * 4, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);  // the node's one wait
+  if (e != hipSuccess || e2 != hipSuccess) {
+    lslam::set_error(hipGetErrorString(e != hipSuccess ? e : e2));
+    return LSLAM_ERR_HIP;
+  }
+  const uint32_t *res = sr->h_res.p;
+  if (res[4] || sr->done.p[1]) {
+    lslam::set_error(res[4] == 3u ? "lslam_sreg_process: a scan ring has more points than the extraction holds in LDS (2560)"
+                     : res[4] == 1u ? "voxel index outside its range (non-finite point?)"
+                     : res[4] == 2u ? "a feature list overflowed its staging slice" : "the grouping by ring failed");
+    return LSLAM_ERR_INVALID;
+  }
+  const size_t m = (size_t)res[28];
+  for (int k = 0; k < 4; ++k) {
+    out->counts[k] = (size_t)res[k];
+    if (counts) counts[k] = (size_t)res[k];
+  }
+  sr->last_m = m;
+  sr->last_valid = true;
+  sr->d_sorted = w.pts;
+  sr->sweeps++;
+  if (imu) {
+    sr->start = start;
+    if (m) {  // (a sweep without a kept point leaves _imuCur and _imuPositionShift as they were)
+      const float *c = reinterpret_cast<const float *>(res + 16);
+      sr->cur.roll = c[0]; sr->cur.pitch = c[1]; sr->cur.yaw = c[2];
+      for (int d = 0; d < 3; ++d) { sr->cur.pos[d] = c[3 + d]; sr->cur.vel[d] = c[6 + d]; sr->shift[d] = c[9 + d]; }
+    }
+  }
+  if (imu_trans) {  // publishResult, ScanRegistration.cpp:684-707
+    imu_trans[0] = sr->start.pitch; imu_trans[1] = sr->start.yaw; imu_trans[2] = sr->start.roll;
+    imu_trans[3] = sr->cur.pitch; imu_trans[4] = sr->cur.yaw; imu_trans[5] = sr->cur.roll;
+    float v[3] = {sr->shift[0], sr->shift[1], sr->shift[2]};
+    sr_rotate_yxz_neg(sr->start, v);
+    for (int d = 0; d < 3; ++d) imu_trans[6 + d] = v[d];
+    for (int d = 0; d < 3; ++d) v[d] = sr->cur.vel[d] - sr->start.vel[d];
+    sr_rotate_yxz_neg(sr->start, v);
+    for (int d = 0; d < 3; ++d) imu_trans[9 + d] = v[d];
+  }
+  if (stats) {
+    stats->sweeps = sr->sweeps;
+    stats->n_points = m;
+    stats->imu_states = (int32_t)K;
+    stats->launches = imu ? 8 : 7;
+    stats->bytes_up = in_bytes;
+    stats->bytes_down = (SR_RES_WORDS + 2 * R) * 4 + 12;
+  }
+  return LSLAM_OK;
+}
+
+int lslam_sreg_cloud(lslam_sreg *sr, float *out_xyzc, size_t cap, size_t *n_out, int32_t *ranges_out) {
+  if (n_out) *n_out = 0;
+  if (!sr) {
+    lslam::set_error("lslam_sreg_cloud: null node");
+    return LSLAM_ERR_INVALID;
+  }
+  if (ranges_out) for (int r = 0; r < 2 * sr->n_rings; ++r) ranges_out[r] = 0;
+  if (!n_out || !lslam::ctx_alive(sr->ctx)) {
+    lslam::set_error("lslam_sreg_cloud: no place for the size, or the node's context was destroyed");
+    return LSLAM_ERR_INVALID;
+  }
+  if (!sr->last_valid) {
+    lslam::set_error("lslam_sreg_cloud: no sweep has been registered (or the last one was refused)");
+    return LSLAM_ERR_INVALID;
+  }
+  *n_out = sr->last_m;
+  if (ranges_out) std::memcpy(ranges_out, sr->h_res.p + SR_RES_WORDS, 2 * (size_t)sr->n_rings * 4);
+  if (!out_xyzc || sr->last_m == 0) return LSLAM_OK;
+  if (cap < sr->last_m) {
+    lslam::set_error("lslam_sreg_cloud: output buffer too small");
+    return LSLAM_ERR_INVALID;
+  }
+  SR_TRY(hipSetDevice(sr->device));
+  SR_TRY(hipMemcpyAsync(out_xyzc, sr->d_sorted, sr->last_m * sizeof(float4), hipMemcpyDeviceToHost, sr->stream));
+  SR_TRY(hipStreamSynchronize(sr->stream));
   return LSLAM_OK;
 }
 

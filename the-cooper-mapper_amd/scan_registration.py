@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import LslamError, LslamRegParams, c_float_p, c_int32_p
+from .capi import LslamError, LslamRegParams, LslamSregStats, c_double_p, c_float_p, c_int32_p
 
 LISTS = ("sharp", "less_sharp", "flat", "less_flat")
 
@@ -127,3 +127,114 @@ def multiscan_register(ctx, cloud, lower_deg, upper_deg, n_rings, scan_period=0.
     if rc < 0:
         raise LslamError(rc, ctx.lib.lslam_last_error().decode())
     return out[:n.value].copy(), ranges
+
+
+def rpy_from_quaternion(x, y, z, w):
+    """tf::Matrix3x3(q).getRPY(roll, pitch, yaw) (solution_number 1, the default): of the two Euler triples of a rotation the
+    one with pitch in [-pi/2, pi/2]; at the gimbal lock (|m20| >= 1) yaw is 0."""
+    import math
+    n = x * x + y * y + z * z + w * w
+    s = 2.0 / n
+    m00, m10, m20 = 1.0 - s * (y * y + z * z), s * (x * y + w * z), s * (x * z - w * y)
+    m21, m22 = s * (y * z + w * x), 1.0 - s * (x * x + y * y)
+    if abs(m20) >= 1.0:  # gimbal lock: yaw = 0, roll = atan2(m21, m22) as tf forms it
+        return math.atan2(m21, m22), (math.pi / 2.0 if m20 < 0 else -math.pi / 2.0), 0.0
+    pitch = -math.asin(m20)
+    c = math.cos(pitch)
+    return math.atan2(m21 / c, m22 / c), pitch, math.atan2(m10 / c, m00 / c)
+
+
+class MultiScanRegistration:
+    """``lidar_slam::MultiScanRegistration`` as a node on the device (``lslam_sreg_*``): raw driver cloud in, the sweep's four
+    feature lists in a :class:`FeatureSet` out -- ring and relTime, the IMU de-skew (whenever :meth:`handle_imu_message` has
+    been called), the grouping by ring, the ranges and the extraction without a trip through the host, one wait per sweep."""
+    SYSTEM_DELAY = 2  # ScanRegistration.h: the first clouds of a session are skipped
+
+    def __init__(self, ctx, lower_deg=-15.0, upper_deg=15.0, n_rings=16, scan_period=0.1, params=None, imu_history_size=200):
+        self.ctx = ctx
+        self.n_rings = int(n_rings)
+        h = C.c_void_p()
+        rc = ctx.lib.lslam_sreg_create(ctx.h, C.byref(params) if params is not None else None, float(lower_deg), float(upper_deg),
+                                       self.n_rings, float(scan_period), int(imu_history_size), C.byref(h))
+        if rc < 0:
+            raise LslamError(rc, ctx.lib.lslam_last_error().decode())
+        self.h = h
+        self.system_delay = self.SYSTEM_DELAY
+        self.cloud_receive_count = 0
+        self.imu_trans = np.zeros((4, 3), np.float32)
+        self.last_stats = LslamSregStats()
+        self.fset = None
+
+    def _check(self, rc):
+        if rc < 0:
+            raise LslamError(rc, self.ctx.lib.lslam_last_error().decode())
+
+    def handle_imu_message(self, stamp_ns, rpy, linear_acceleration):
+        """handleIMUMessage after getRPY: ``rpy`` in radians, ``linear_acceleration`` {x, y, z} in the IMU's axes."""
+        la = (C.c_double * 3)(*[float(v) for v in linear_acceleration])
+        self._check(self.ctx.lib.lslam_sreg_imu_push(self.h, int(stamp_ns), float(rpy[0]), float(rpy[1]), float(rpy[2]), la))
+
+    def handle_imu_quaternion(self, stamp_ns, orientation_xyzw, linear_acceleration):
+        self.handle_imu_message(stamp_ns, rpy_from_quaternion(*[float(v) for v in orientation_xyzw]), linear_acceleration)
+
+    def has_imu_data(self):
+        return self.imu_info()[0] > 0
+
+    def imu_info(self):
+        n = C.c_int32()
+        pos, vel = (C.c_double * 3)(), (C.c_double * 3)()
+        self._check(self.ctx.lib.lslam_sreg_imu_info(self.h, C.byref(n), pos, vel))
+        return n.value, np.array(pos), np.array(vel)
+
+    def imu_clear(self):
+        self._check(self.ctx.lib.lslam_sreg_imu_clear(self.h))
+
+    def process(self, cloud, stamp_ns, fset):
+        """MultiScanRegistration::process: cloud (n, >=3) float32 in arrival order; returns the four lists' sizes."""
+        a = np.ascontiguousarray(cloud, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("cloud must be (n, >=3) float32")
+        counts = (C.c_size_t * 4)()
+        trans = np.zeros((4, 3), np.float32)
+        rc = self.ctx.lib.lslam_sreg_process(self.h, a.ctypes.data_as(C.c_void_p), len(a), a.shape[1] * 4, int(stamp_ns), fset.h, counts,
+                                             trans.ctypes.data_as(c_float_p), C.byref(self.last_stats))
+        self._check(rc)
+        self.imu_trans = trans
+        return dict(zip(LISTS, (int(v) for v in counts)))
+
+    def handle_cloud_message(self, cloud, stamp_ns, fset=None):
+        """handleCloudMessage: the first SYSTEM_DELAY clouds are dropped (returns None), the others processed into ``fset`` (or a
+        feature set of the node's own, ``self.fset``)."""
+        self.cloud_receive_count += 1
+        if self.system_delay > 0:
+            self.system_delay -= 1
+            return None
+        if fset is None:
+            if self.fset is None:
+                self.fset = FeatureSet(self.ctx)
+            fset = self.fset
+        return self.process(cloud, stamp_ns, fset)
+
+    def cloud(self):
+        """The last sweep's registered cloud (m, 4) {x', y', z', ring + relTime} and its (n_rings, 2) ranges."""
+        n = C.c_size_t()
+        ranges = np.zeros((self.n_rings, 2), np.int32)
+        self._check(self.ctx.lib.lslam_sreg_cloud(self.h, None, 0, C.byref(n), ranges.ctypes.data_as(c_int32_p)))
+        out = np.zeros((n.value, 4), np.float32)
+        if n.value:
+            self._check(self.ctx.lib.lslam_sreg_cloud(self.h, out.ctypes.data_as(c_float_p), len(out), C.byref(n), None))
+        return out, ranges
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lslam_sreg_destroy(self.h)
+            self.h = None
+        if self.fset is not None:
+            self.fset.close()
+            self.fset = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
