@@ -207,6 +207,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* 6 (round 6): no struct changed; new entry points (lslam_fset_*, lslam_extract_features_dev, lslam_odom_*, lslam_map_epoch). */
 /* 7: no struct changed; new entry points (lslam_lmap_*: the sliding-window local map). */
 /* still 7: no struct changed; new entry points (lslam_sreg_*: the registration node with the IMU de-skew branch). */
+/* still 7: no struct changed; new entry points and structs of their own (lslam_loc_*: the localisation node). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -953,6 +954,107 @@ void lslam_debug_grid_stats(lslam_ctx *ctx, uint64_t out[32]);
  * corner points, then its surf points (each in the library's own order).  Returns the number of points copied (at most
  * cap_points) or a negative status. */
 int lslam_debug_cert_state(lslam_ctx *ctx, float *q_xyz0, float *lb, size_t cap_points);
+
+/* ---- the localisation node resident on the device (odometry/LaserLocalization.cpp over util/FeatureMap.h) ------------------
+ * L_SLAM's second operating mode: a map built once (saveCloudToFiles / lslam_fmap_save) is loaded, every cube with at least five
+ * points of a type gets its kd-tree ONCE (loadCloudFromFiles, FeatureMap.h:415-462, builds them at :438,453), and every later
+ * sweep is matched against it by FeatureMap::scanMatchScan (:490-691): a scan point is searched in the tree of the cube it
+ * falls into, whichever loaded cube that is.  The node owns its map, its trees and its scratch; it never touches the
+ * context's resident map (lslam_map_set / lslam_cubemap_set on the same context in between change nothing for it, and it
+ * changes nothing for them).  One call in flight per ctx, like everything else on a ctx.
+ *
+ * The search.  What variant C fixes is the RESULT of nearestKSearch in the query's cube tree.  A cell grid over the cubes the
+ * sensor can reach (those within lidar-valid-distance of the sensor's cube, fewer if the cell tables would not hold them)
+ * proves, for most points, the five nearest among ALL points of those cubes with a margin to the sixth (csrc/lslam_grid.hpp);
+ * when the proven five all belong to the query's own cube they are the five nearest inside it, in the same order.  A point the
+ * probe cannot prove (a sparse neighbourhood, an exact tie among its six nearest), whose five are not all in its cube, or whose
+ * cube the grid does not cover is searched in its cube's tree.  A point farther than the sqrt(5) m gate from every grid point
+ * of a covered cube is rejected as the reference rejects it.  The grid is rebuilt only when the sensor's cube changes.
+ *
+ * Differences from the reference, on purpose:
+ *   - FeatureMap::update shifts the cube array when the sensor comes within 3 cubes of the grid's edge but leaves the kd-tree
+ *     arrays where they were (shift(), :353-376, swaps clouds only): what it then matches against is an accident.  A sweep
+ *     whose prior pose is that close to the edge is refused with LSLAM_ERR_INVALID and leaves the node as it was.  (With an
+ *     initial pose pending such a sweep is not matched -- its result would be discarded anyway -- and only takes the pose.)
+ *   - prepareFeatureSurround only feeds a publisher in this node: it is not run per sweep (lslam_loc_get_surround does it).
+ *   - the UKF (imu_que) is not part of the node: pose, velocity and stamp are what imu_que.correct would be handed. */
+typedef struct lslam_loc lslam_loc;
+/* lslam_loc_process flags */
+enum { LSLAM_LOC_DROPPED = 1,        /* no initial pose yet (LaserLocalization.cpp:169): nothing was done, nothing changed */
+       LSLAM_LOC_HAS_VELOCITY = 2,   /* velocity_out is valid (absent on the first processed sweep, :157) */
+       LSLAM_LOC_POSE_RESET = 4,     /* a pending initial pose replaced this sweep's match result (:142-145) */
+       LSLAM_LOC_VELOCITY_ZEROED = 8,/* |v| > 30 (:159-160) */
+       LSLAM_LOC_SECOND_WAIT = 16    /* the scan filter's key range did not hold: the sweep was run again behind a second wait */ };
+typedef struct {
+  int64_t cubes_loaded[2];      /* cubes that hold points, per type (corner, surf) */
+  int64_t cubes_with_tree[2];   /* ... of which have a kd-tree (>= 5 points) */
+  uint64_t n_points[2];
+  int64_t structure_builds;     /* forest builds since creation (one per map set / load) */
+  int64_t grid_builds;          /* cell-grid builds since creation (one per change of the sensor's cube, both types together) */
+  int32_t grid_cube[3];         /* the sensor cube the grids were built for */
+  int32_t grid_reach;           /* cubes on every side of it the grids cover */
+  int32_t grid_on[2];           /* 1 while the type has a grid (0: every point of the type goes to its cube tree) */
+  int32_t tree_depth;           /* of the deepest cube tree */
+  int32_t reserved;
+} lslam_loc_map_stats;
+typedef struct {                /* [0] the last sweep (all its Gauss-Newton iterations), [1] since creation */
+  uint64_t swept[2];            /* points looked at (points whose cube has no tree included) */
+  uint64_t grid_proven[2];      /* decided by the grid: five proven in the point's cube, or proven beyond the gate */
+  uint64_t cube_refused[2];     /* proven by the grid but refused by the cube check alone */
+  uint64_t to_trees[2];         /* searched in their cube's tree (cube_refused included) */
+  uint64_t fallback_sweeps[2];  /* sweeps that fell back to the trees entirely (0: a tie sends only its own point to its tree) */
+  uint64_t host_waits[2];
+  uint64_t bytes_up[2], bytes_down[2];
+} lslam_loc_search_counts;
+/* FeatureMap(cubeWidth, cubeHeight, cubeDepth) of LaserLocalization's _feature_map; defaults: origin round((size-1)/2), cube
+ * 50 m, valid distance 150 m, scan filters 1.0 / 1.0 (LaserMatcher.cpp:80-85), map filters 1.0 / 1.0 (:87-92,116). */
+int lslam_loc_create(lslam_ctx *ctx, int32_t cube_width, int32_t cube_height, int32_t cube_depth, lslam_loc **out);
+void lslam_loc_destroy(lslam_loc *loc);
+int lslam_loc_setup_scan_filter_size(lslam_loc *loc, float corner, float surf);
+int lslam_loc_setup_map_filter_size(lslam_loc *loc, float corner, float surf);   /* applied by lslam_loc_load / _set_map */
+int lslam_loc_setup_world_origin(lslam_loc *loc, int32_t ox, int32_t oy, int32_t oz);
+int lslam_loc_setup_world_cube_size(lslam_loc *loc, float size);
+int lslam_loc_setup_lidar_valid_distance(lslam_loc *loc, float dist);
+/* Debug switch: 0 = every point through its cube tree (the per-cube walk alone); 1 (default) = the grid path.  Same poses, bit for bit. */
+int lslam_loc_setup_search(lslam_loc *loc, int32_t use_grid);
+/* loadCloudFromFiles (FeatureMap.h:415-462) into an empty map: each listed cube through its type's VoxelGrid, a later entry
+ * for a cube replaces the earlier one, a missing PCD is skipped; then every tree, in one forest build. */
+int lslam_loc_load(lslam_loc *loc, const char *directory);
+/* The same from host clouds: points pushed into their cubes in input order (as lslam_cubemap_set); filter != 0: every cube
+ * through its type's VoxelGrid (the map filters) as the load does. */
+int lslam_loc_set_map(lslam_loc *loc, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
+                      int32_t filter);
+/* Adopt the map a mapping session has just built (same context, same cube-grid dimensions), device to device; cube size, origin
+ * and valid distance are taken from it; nothing is filtered. */
+int lslam_loc_set_map_from_fmap(lslam_loc *loc, lslam_fmap *fm);
+int lslam_loc_info(lslam_loc *loc, lslam_loc_map_stats *out);
+/* initialPoseHandler without its ROS sign conventions: T (row-major 4x4) becomes the pending pose and the node is initialised. */
+int lslam_loc_set_initial_pose(lslam_loc *loc, const float T[16]);
+/* LaserLocalization::process (:168-188) for one sweep: transformMerge on the host (lslam_transform_associate), both clouds
+ * voxel-filtered on the device (lslam_voxel_grid2's arithmetic), scanMatchScan with <= 10 iterations, 0.05 / 0.05 and no score
+ * gate, transformUpdate with its reset-after-match rule, the velocity (t_new - t_last) / dt in float.  One host wait.
+ * mapped_out: _lidarMappedNew; stats: the match's (may be NULL).  Returns the match's outcome (LSLAM_OK / LSLAM_NOT_CONVERGED /
+ * LSLAM_TOO_FEW_MATCHES; the pose is updated in every case, as the reference ignores scanMatchScan's result) or an error. */
+int lslam_loc_process(lslam_loc *loc, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
+                      const float odom[16], int64_t stamp_ns, float mapped_out[16], float velocity_out[3], int32_t *flags,
+                      lslam_stats *stats);
+/* The same for clouds in the context's device memory, packed {x, y, z, intensity} (lslam_odom_last_view's). */
+int lslam_loc_process_device(lslam_loc *loc, const void *d_corner, size_t n_corner, const void *d_surf, size_t n_surf,
+                             const float odom[16], int64_t stamp_ns, float mapped_out[16], float velocity_out[3], int32_t *flags,
+                             lslam_stats *stats);
+/* prepareFeatureFrame + optimizeTransform alone, from a given Twist (in/out); the node's pose state is not touched. */
+int lslam_loc_match(lslam_loc *loc, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
+                    float pose[6], lslam_stats *stats);
+/* prepareFeatureSurround on request: FeatureMap::update at the node's pose + getSurroundFeature.  A null buffer: its count only. */
+int lslam_loc_get_surround(lslam_loc *loc, float *corner_xyzi, size_t cap_corner, size_t *n_corner, float *surf_xyzi,
+                           size_t cap_surf, size_t *n_surf);
+int lslam_loc_search_stats(lslam_loc *loc, lslam_loc_search_counts *out);
+/* Parity tap of the search the Gauss-Newton loop runs (the same kernels): nq queries in the map frame against the corner
+ * (which = 0) or surf (1) structures -> the five neighbours' coordinates xyz_out[nq][5][3], their squared distances
+ * d2_out[nq][5] and how each query was decided, how_out[nq]: 0 skipped (no cube, or a cube with < 5 points: outputs zero),
+ * 1 grid, 2 cube tree.  Unlike the loop the tap has no gate: a query beyond sqrt(5) m of everything goes to its tree. */
+int lslam_loc_debug_knn5(lslam_loc *loc, int32_t which, const void *queries, size_t nq, size_t stride_bytes, float *xyz_out,
+                         float *d2_out, uint8_t *how_out);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,8 @@
 //                                        transformUpdate, featureMapUpdate)
 //   lidar_slam::LaserMappingLocal::process  odometry/LaserMappingLocal.cpp:39-83: the same matcher over the sliding window of
 //                                        recent frames, io_module/LocalFeatureMap.h (lidar_slam::LocalFeatureMap below)
+//   lidar_slam::LaserLocalization::process  odometry/LaserLocalization.cpp:140-188: localisation over a prebuilt map, the node
+//                                        resident on the device (lslam_loc_*)
 //
 // ROS plumbing (topics, time-stamp matching, tf, frame skipping) is the host program's.  Clouds are any
 // type with `.points` (std::vector-like) of points with float x, y, z and `intensity` (= ring + relTime);
@@ -436,6 +438,89 @@ private:
     return false;
   }
   LocalFeatureMap _map;
+};
+
+// LaserLocalization (odometry/LaserLocalization.cpp:140-188 over util/FeatureMap.h): the second operating mode -- a map built
+// once and saved with saveCloudToFiles is loaded at init, every cube's kd-tree is built once, and each sweep is matched against
+// it on the device behind one host wait (lslam_loc_*, include/lslam_c.h).  loadMap is _feature_map->loadCloudFromFiles,
+// handleInitialPose the pose initialPoseHandler ends with (its ROS sign conventions are the host program's), process the
+// sweep: transformMerge, prepareFeatureFrame, optimizeTransform, transformUpdate with its reset-after-match rule, the velocity.
+// The UKF (imu_que) is the host program's: lidarMapped(), velocity() and the stamp are what imu_que.correct is handed.
+class LaserLocalization {
+public:
+  explicit LaserLocalization(lslam_ctx *ctx, int cubeX = 121, int cubeY = 121, int cubeZ = 11, float filterCorner = 1.0f,
+                             float filterSurf = 1.0f, float mapFilterCorner = 1.0f, float mapFilterSurf = 1.0f)
+      : _loc(nullptr), _flags(0), _hasVelocity(false) {
+    detail::identity4(_lidarMappedNew);
+    std::memset(_velocity, 0, sizeof(_velocity));
+    std::memset(&_last, 0, sizeof(_last));
+    if (lslam_abi_version() != LSLAM_ABI_VERSION || lslam_sizeof_opts() != sizeof(lslam_opts) || lslam_sizeof_stats() != sizeof(lslam_stats)) {
+      _err = "liblslam_hip was built from another include/lslam_c.h than this program (ABI version / struct sizes differ)";
+      return;
+    }
+    if (lslam_loc_create(ctx, cubeX, cubeY, cubeZ, &_loc) != LSLAM_OK) {
+      _loc = nullptr;
+      _err = lslam_last_error();
+      return;
+    }
+    lslam_loc_setup_scan_filter_size(_loc, filterCorner, filterSurf);
+    lslam_loc_setup_map_filter_size(_loc, mapFilterCorner, mapFilterSurf);
+  }
+  ~LaserLocalization() { lslam_loc_destroy(_loc); }
+  LaserLocalization(const LaserLocalization &) = delete;
+  LaserLocalization &operator=(const LaserLocalization &) = delete;
+  bool ok() const { return _loc != nullptr; }
+  bool setupWorldOrigin(int ox, int oy, int oz) { return check(lslam_loc_setup_world_origin(_loc, ox, oy, oz)); }
+  bool setupWorldCubeSize(float size) { return check(lslam_loc_setup_world_cube_size(_loc, size)); }
+  bool setupLidarValidDistance(float dist) { return check(lslam_loc_setup_lidar_valid_distance(_loc, dist)); }
+  // init(): _feature_map->loadCloudFromFiles(map_file_path)
+  bool loadMap(const std::string &directory) { return check(lslam_loc_load(_loc, directory.c_str())); }
+  // ... or the map a mapping node of the same context has just built
+  bool adoptMap(lslam_fmap *fm) { return check(lslam_loc_set_map_from_fmap(_loc, fm)); }
+  bool handleInitialPose(const float T[16]) { return check(lslam_loc_set_initial_pose(_loc, T)); }
+  // cornerLast / surfLast: packed {x, y, z, intensity}; lidarOdomNew: the odometry node's _Tsum.  false: a backend error, or the
+  // sweep was dropped (dropped() says which); the match's own outcome (lastStats().status) never makes it false, as the
+  // reference ignores scanMatchScan's result.
+  bool process(const std::vector<float> &cornerLast, const std::vector<float> &surfLast, const float lidarOdomNew[16], int64_t stampNs) {
+    if (!_loc) return false;
+    return finish(lslam_loc_process(_loc, cornerLast.data(), cornerLast.size() / 4, surfLast.data(), surfLast.size() / 4, 16, lidarOdomNew,
+                                    stampNs, _lidarMappedNew, _velocity, &_flags, &_last));
+  }
+  // the same for clouds in the context's device memory (lslam_odom_last_view)
+  bool processDevice(const void *dCornerLast, size_t nCorner, const void *dSurfLast, size_t nSurf, const float lidarOdomNew[16],
+                     int64_t stampNs) {
+    if (!_loc) return false;
+    return finish(lslam_loc_process_device(_loc, dCornerLast, nCorner, dSurfLast, nSurf, lidarOdomNew, stampNs, _lidarMappedNew, _velocity,
+                                           &_flags, &_last));
+  }
+  const float *lidarMapped() const { return _lidarMappedNew; }
+  const float *velocity() const { return _velocity; }
+  bool hasVelocity() const { return _hasVelocity; }
+  bool dropped() const { return (_flags & LSLAM_LOC_DROPPED) != 0; }
+  int flags() const { return _flags; }
+  const lslam_stats &lastStats() const { return _last; }
+  const std::string &lastError() const { return _err; }
+  lslam_loc *handle() { return _loc; }
+
+private:
+  bool check(int rc) {
+    if (rc < 0) _err = lslam_last_error();
+    return rc >= 0;
+  }
+  bool finish(int rc) {
+    if (rc < 0) {
+      _err = lslam_last_error();
+      return false;
+    }
+    _hasVelocity = (_flags & LSLAM_LOC_HAS_VELOCITY) != 0;
+    return (_flags & LSLAM_LOC_DROPPED) == 0;
+  }
+  lslam_loc *_loc;
+  float _lidarMappedNew[16], _velocity[3];
+  int32_t _flags;
+  bool _hasVelocity;
+  lslam_stats _last;
+  std::string _err;
 };
 
 }  // namespace lidar_slam

@@ -135,6 +135,20 @@ class LslamSregStats(C.Structure):
                 ("bytes_up", C.c_size_t), ("bytes_down", C.c_size_t)]
 
 
+class LslamLocMapStats(C.Structure):
+    """lslam_loc_map_stats (include/lslam_c.h)."""
+    _fields_ = [("cubes_loaded", C.c_int64 * 2), ("cubes_with_tree", C.c_int64 * 2), ("n_points", C.c_uint64 * 2),
+                ("structure_builds", C.c_int64), ("grid_builds", C.c_int64), ("grid_cube", C.c_int32 * 3),
+                ("grid_reach", C.c_int32), ("grid_on", C.c_int32 * 2), ("tree_depth", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LslamLocSearchCounts(C.Structure):
+    """lslam_loc_search_counts (include/lslam_c.h): [0] the last sweep, [1] since creation."""
+    _fields_ = [("swept", C.c_uint64 * 2), ("grid_proven", C.c_uint64 * 2), ("cube_refused", C.c_uint64 * 2),
+                ("to_trees", C.c_uint64 * 2), ("fallback_sweeps", C.c_uint64 * 2), ("host_waits", C.c_uint64 * 2),
+                ("bytes_up", C.c_uint64 * 2), ("bytes_down", C.c_uint64 * 2)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLGATHERV_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32)
 c_double_p = C.POINTER(C.c_double)
@@ -288,6 +302,29 @@ SYMBOLS = {
     "lslam_sreg_process": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int64, C.c_void_p, C.POINTER(C.c_size_t),
                                      c_float_p, C.POINTER(LslamSregStats)]),
     "lslam_sreg_cloud": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, C.POINTER(C.c_size_t), c_int32_p]),
+    "lslam_loc_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "lslam_loc_destroy": (None, [C.c_void_p]),
+    "lslam_loc_setup_scan_filter_size": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
+    "lslam_loc_setup_map_filter_size": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
+    "lslam_loc_setup_world_origin": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "lslam_loc_setup_world_cube_size": (C.c_int, [C.c_void_p, C.c_float]),
+    "lslam_loc_setup_lidar_valid_distance": (C.c_int, [C.c_void_p, C.c_float]),
+    "lslam_loc_setup_search": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lslam_loc_load": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "lslam_loc_set_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32]),
+    "lslam_loc_set_map_from_fmap": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lslam_loc_info": (C.c_int, [C.c_void_p, C.POINTER(LslamLocMapStats)]),
+    "lslam_loc_set_initial_pose": (C.c_int, [C.c_void_p, c_float_p]),
+    "lslam_loc_process": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, C.c_int64,
+                                    c_float_p, c_float_p, c_int32_p, C.POINTER(LslamStats)]),
+    "lslam_loc_process_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_float_p, C.c_int64,
+                                           c_float_p, c_float_p, c_int32_p, C.POINTER(LslamStats)]),
+    "lslam_loc_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p,
+                                  C.POINTER(LslamStats)]),
+    "lslam_loc_get_surround": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, C.POINTER(C.c_size_t), c_float_p, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
+    "lslam_loc_search_stats": (C.c_int, [C.c_void_p, C.POINTER(LslamLocSearchCounts)]),
+    "lslam_loc_debug_knn5": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, c_float_p, c_uint8_p]),
     "lslam_pg_save_g2o": (C.c_int, [C.c_void_p, C.c_char_p]),
     "lslam_g2o_read": (C.c_int, [C.c_char_p, c_int32_p, c_double_p, c_int32_p, c_int32_p, c_double_p, c_double_p,
                                  c_int32_p]),

@@ -626,6 +626,7 @@ struct lslam_fmap {
   int64_t trees_built = 0, trees_reused = 0;  // statistics of the last lslam_fmap_to_cubemap
   int64_t merged_rebuilds = 0, resorted_rebuilds = 0;  // addFeatureCloud rebuilds that merged the new points in / that had to sort everything after all
   int forest_attempt0 = 0;                     // node-slot guess the last forest build succeeded with (lslam_fmap_to_cubemap)
+  bool private_store = false;                  // owned by a localisation node (lslam_loc.hip): never installed as the context's map
 };
 
 namespace {
@@ -1148,7 +1149,7 @@ void lslam_fmap_destroy(lslam_fmap *fm) {
   }
   for (lslam_fmap::Generation *g : fm->gens) delete g;
   for (lslam_fmap::Generation *g : fm->spare) delete g;
-  if (lslam::ctx_alive(fm->ctx)) lslam::cubemap_drop_views(fm->ctx);  // the context may still point at this map's trees
+  if (!fm->private_store && lslam::ctx_alive(fm->ctx)) lslam::cubemap_drop_views(fm->ctx);  // the context may still point at this map's trees
   if (fm->stream2 && lslam::ctx_alive(fm->ctx)) (void)hipStreamSynchronize(fm->stream2);  // (the context's: not ours to destroy)
   if (fm->ev_fork) (void)hipEventDestroy(fm->ev_fork);
   if (fm->ev_join) (void)hipEventDestroy(fm->ev_join);
@@ -2041,3 +2042,118 @@ int lslam_voxel_grid2(lslam_ctx *ctx, const void *a, size_t na, const void *b, s
 }
 
 }  // extern "C"
+
+// ---- what the localisation node (lslam_loc.hip) needs of the map store it owns -------------------------------------------
+namespace lslam {
+
+void fmap_set_private(lslam_fmap *fm) { fm->private_store = true; }
+
+// Replace the store's content by two host clouds: every point goes to the cube its coordinates give (worldToCube; points
+// outside the grid are dropped), input order kept inside a cube (pushCornerPoint / pushSurfPoint); filter: every cube then
+// goes through its type's VoxelGrid, as loadCloudFromFiles does with the cubes it reads.
+int fmap_set_clouds(lslam_fmap *fm, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
+                    bool filter) {
+  int rc = check_fm(fm);
+  if (rc) return rc;
+  hipStream_t s = fm->stream;
+  const void *src[2] = {corner, surf};
+  const size_t cnt[2] = {n_corner, n_surf};
+  DevBuf<uint8_t> d_flags;
+  if (filter) {
+    FM_TRY(d_flags.reserve(fm->ncube));
+    FM_TRY(hipMemsetAsync(d_flags.p, 1, fm->ncube, s));
+  }
+  for (int t = 0; t < 2; ++t) {
+    std::vector<float4> pts;
+    std::vector<int32_t> cube;
+    pts.reserve(cnt[t]);
+    cube.reserve(cnt[t]);
+    const char *p = static_cast<const char *>(src[t]);
+    const size_t ioff = stride_bytes == 16 ? 12 : 16;
+    for (size_t i = 0; i < cnt[t]; ++i) {
+      float v[3], w = 0.0f;
+      std::memcpy(v, p + i * stride_bytes, 12);
+      if (stride_bytes >= ioff + 4) std::memcpy(&w, p + i * stride_bytes + ioff, 4);
+      const int gi = (int)(std::round(v[0] / fm->cube_size) + (float)fm->origin[0]);
+      const int gj = (int)(std::round(v[1] / fm->cube_size) + (float)fm->origin[1]);
+      const int gk = (int)(std::round(v[2] / fm->cube_size) + (float)fm->origin[2]);
+      if (!idx_valid(fm, gi, gj, gk)) continue;
+      pts.push_back(make_float4(v[0], v[1], v[2], w));
+      cube.push_back(to_index(fm, gi, gj, gk));
+    }
+    const size_t n = pts.size();
+    fm->n[t] = 0;
+    fm->seg_current[t] = fm->seg_dev_current[t] = false;
+    if (n) {
+      FM_TRY(fm->in_tf.reserve(n));
+      FM_TRY(fm->in_cube.reserve(n));
+      FM_TRY(hipMemcpyAsync(fm->in_tf.p, pts.data(), n * sizeof(float4), hipMemcpyHostToDevice, s));
+      FM_TRY(hipMemcpyAsync(fm->in_cube.p, cube.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    rc = rebuild(fm, t, n, filter, filter ? d_flags.p : nullptr);
+    if (rc) return rc;
+    FM_TRY(hipStreamSynchronize(s));  // (pts / cube are locals)
+  }
+  return LSLAM_OK;
+}
+
+int fmap_clear(lslam_fmap *fm) {
+  int rc = check_fm(fm);
+  if (rc) return rc;
+  for (int t = 0; t < 2; ++t) {
+    fm->n[t] = 0;
+    fm->seg_current[t] = fm->seg_dev_current[t] = false;
+  }
+  return LSLAM_OK;
+}
+
+// dst becomes a copy of src (same context, same grid dimensions): the points and their cubes, device to device, and the geometry.
+int fmap_copy(lslam_fmap *dst, lslam_fmap *src) {
+  int rc = check_fm(dst);
+  if (rc) return rc;
+  rc = check_fm(src);
+  if (rc) return rc;
+  if (dst->ctx != src->ctx || dst->W != src->W || dst->H != src->H || dst->D != src->D) {
+    lslam::set_error("the two maps differ in context or cube-grid dimensions");
+    return LSLAM_ERR_INVALID;
+  }
+  hipStream_t s = dst->stream;
+  for (int d = 0; d < 3; ++d) { dst->origin[d] = src->origin[d]; dst->leaf[d] = src->leaf[d]; }
+  dst->cube_size = src->cube_size;
+  dst->valid_dist = src->valid_dist;
+  for (int t = 0; t < 2; ++t) {
+    const size_t n = src->n[t];
+    dst->n[t] = 0;
+    dst->seg_current[t] = dst->seg_dev_current[t] = false;
+    if (n) {
+      FM_TRY(dst->pts[t].reserve(n));
+      FM_TRY(dst->cube[t].reserve(n));
+      FM_TRY(hipMemcpyAsync(dst->pts[t].p, src->pts[t].p, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+      FM_TRY(hipMemcpyAsync(dst->cube[t].p, src->cube[t].p, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    }
+    dst->n[t] = n;
+  }
+  FM_TRY(hipStreamSynchronize(s));
+  return LSLAM_OK;
+}
+
+// the store as it is: per type the points (grouped by cube, ascending) and, on the host, every cube's [begin, end) in them
+int fmap_view(lslam_fmap *fm, FmapView *out) {
+  int rc = check_fm(fm);
+  if (rc) return rc;
+  for (int t = 0; t < 2; ++t) {
+    rc = refresh_segments(fm, t);
+    if (rc) return rc;
+    out->pts[t] = fm->pts[t].p;
+    out->n[t] = fm->n[t];
+    out->begin[t] = fm->h_begin[t].data();
+    out->end[t] = fm->h_begin[t].data() + seg_pad(fm);
+  }
+  out->W = fm->W; out->H = fm->H; out->D = fm->D;
+  for (int d = 0; d < 3; ++d) out->origin[d] = fm->origin[d];
+  out->cube_size = fm->cube_size;
+  out->valid_dist = fm->valid_dist;
+  return LSLAM_OK;
+}
+
+}  // namespace lslam

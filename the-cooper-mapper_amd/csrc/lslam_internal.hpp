@@ -391,6 +391,7 @@ hipError_t build_kdforest_device(BuildPool &pool, float4 *d_pts, int32_t n_total
 }  // namespace lslam
 struct lslam_ctx;
 struct lslam_comm;
+struct lslam_fmap;
 // A sweep's four feature lists in HBM (include/lslam_c.h lslam_fset_*): sixteen header slots (what the extraction kernels write:
 // [0..3] the lists' sizes, [4] error), then four slices of `cap` points {x, y, z, intensity} -- sharp, less-sharp, flat, less-flat.
 struct lslam_fset {
@@ -489,6 +490,22 @@ const char *debug_env(const char *name);  // nullptr unless the process runs wit
 // lslam_fmap.hip: pcl::VoxelGrid per segment (see there)
 int voxel_filter_segments(lslam_ctx *ctx, const float4 *in_pts, const int32_t *in_seg, size_t n, int nseg, float leaf,
                           float4 *out_pts, int32_t *out_seg, size_t *n_out, bool filter = true, uint32_t *done = nullptr);
+
+// lslam_fmap.hip: the map store of a localisation node (lslam_loc.hip owns an lslam_fmap it never installs in the context)
+struct FmapView {
+  const float4 *pts[2];         // device: the type's points, grouped by cube in ascending cube index
+  size_t n[2];
+  const int32_t *begin[2], *end[2];  // host: [ncube] every cube's range in pts[t]
+  int W, H, D;
+  int origin[3];
+  float cube_size, valid_dist;
+};
+void fmap_set_private(lslam_fmap *fm);
+int fmap_set_clouds(lslam_fmap *fm, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
+                    bool filter);
+int fmap_clear(lslam_fmap *fm);
+int fmap_copy(lslam_fmap *dst, lslam_fmap *src);
+int fmap_view(lslam_fmap *fm, FmapView *out);
 
 // lslam_fmap.hip: pcl::VoxelGrid of a window whose owner keeps its points in voxel-key order (see there)
 struct WindowFilter;  // the filter's scratch, owned by the caller

@@ -1,0 +1,155 @@
+"""Host-side mirror of ``lidar_slam::LaserLocalization`` (/root/reference/L_SLAM/src/odometry/LaserLocalization.cpp over
+util/FeatureMap.h) on the device-resident node ``lslam_loc`` (``csrc/lslam_loc.hip``, include/lslam_c.h): a prebuilt map is
+loaded once (``load_map`` / ``set_map`` / ``set_map_from``), every cube's kd-tree is built once, and each sweep runs
+transformMerge, the two scan filters, FeatureMap::scanMatchScan and transformUpdate behind one host wait.
+
+Poses are row-major 4x4 float32; clouds are ``(n, 4)`` float32 ``{x, y, z, intensity}`` (or ``(n, 8)`` pcl::PointXYZI).
+ROS plumbing, ``inputFrameSkip``, the UKF and ``DynamicFeatureMap`` are not mirrored.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .capi import LslamError, LslamLocMapStats, LslamLocSearchCounts, LslamStats, c_int32_p, c_uint8_p
+from .feature_map import _fp, _xyzi
+
+DROPPED, HAS_VELOCITY, POSE_RESET, VELOCITY_ZEROED, SECOND_WAIT = 1, 2, 4, 8, 16  # LSLAM_LOC_* flags
+HOW_SKIPPED, HOW_GRID, HOW_TREE = 0, 1, 2
+
+
+class LaserLocalization:
+    def __init__(self, ctx, cube_width=21, cube_height=11, cube_depth=21, filter_corner=None, filter_surf=None,
+                 map_filter_corner=None, map_filter_surf=None, cube_size=None, world_origin=None, lidar_valid_distance=None):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        rc = self.lib.lslam_loc_create(ctx.h, int(cube_width), int(cube_height), int(cube_depth), C.byref(h))
+        if rc != 0:
+            raise LslamError(rc, self.lib.lslam_last_error().decode())
+        self.h = h
+        if filter_corner is not None or filter_surf is not None:
+            self._check(self.lib.lslam_loc_setup_scan_filter_size(self.h, float(filter_corner or 1.0), float(filter_surf or 1.0)))
+        if map_filter_corner is not None or map_filter_surf is not None:
+            self._check(self.lib.lslam_loc_setup_map_filter_size(self.h, float(map_filter_corner or 1.0),
+                                                                 float(map_filter_surf or 1.0)))
+        if cube_size is not None:
+            self._check(self.lib.lslam_loc_setup_world_cube_size(self.h, float(cube_size)))
+        if world_origin is not None:
+            self._check(self.lib.lslam_loc_setup_world_origin(self.h, *[int(v) for v in world_origin]))
+        if lidar_valid_distance is not None:
+            self._check(self.lib.lslam_loc_setup_lidar_valid_distance(self.h, float(lidar_valid_distance)))
+        self.lidar_mapped = np.eye(4, dtype=np.float32)  # _lidarMappedNew after the last processed sweep
+        self.velocity = None                             # None until a sweep has one
+        self.last_stats = None
+        self.last_flags = 0
+        self.last_status = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.lslam_loc_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc < 0:
+            raise LslamError(rc, self.lib.lslam_last_error().decode())
+        return rc
+
+    # ---- the map, built once ------------------------------------------------------------------------------------------
+    def load_map(self, directory):
+        """loadCloudFromFiles: every listed cube through its type's VoxelGrid (the map filters), then every tree."""
+        self._check(self.lib.lslam_loc_load(self.h, str(directory).encode()))
+
+    def set_map(self, corner, surf, filter=False):
+        c, s = _xyzi(corner), _xyzi(surf)
+        if c.shape[1] != s.shape[1]:
+            raise ValueError("corner and surf clouds must share a point layout")
+        self._check(self.lib.lslam_loc_set_map(self.h, c.ctypes.data_as(C.c_void_p), len(c), s.ctypes.data_as(C.c_void_p), len(s),
+                                               c.shape[1] * 4, 1 if filter else 0))
+
+    def set_map_from(self, feature_map):
+        """Adopt the map of a :class:`~.feature_map.FeatureMap` on the same context, device to device."""
+        self._check(self.lib.lslam_loc_set_map_from_fmap(self.h, feature_map.h))
+
+    def set_search(self, use_grid):
+        self._check(self.lib.lslam_loc_setup_search(self.h, 1 if use_grid else 0))
+
+    def info(self):
+        o = LslamLocMapStats()
+        self._check(self.lib.lslam_loc_info(self.h, C.byref(o)))
+        return dict(cubes_loaded=tuple(o.cubes_loaded), cubes_with_tree=tuple(o.cubes_with_tree), n_points=tuple(o.n_points),
+                    structure_builds=o.structure_builds, grid_builds=o.grid_builds, grid_cube=tuple(o.grid_cube),
+                    grid_reach=o.grid_reach, grid_on=tuple(o.grid_on), tree_depth=o.tree_depth)
+
+    # ---- the sweep ----------------------------------------------------------------------------------------------------
+    def handle_initial_pose(self, T):
+        T = np.ascontiguousarray(T, dtype=np.float32).reshape(16)
+        self._check(self.lib.lslam_loc_set_initial_pose(self.h, _fp(T)))
+
+    def process(self, corner_last, surf_last, lidar_odom_new, stamp_ns):
+        """One sweep -> the 4x4 ``_lidarMappedNew``, or None when the sweep was dropped (no initial pose yet).  Two torch
+        tensors on the context's device ((n, 4) float32, contiguous) are taken where they are."""
+        odom = np.ascontiguousarray(lidar_odom_new, dtype=np.float32).reshape(16)
+        T = np.zeros(16, np.float32)
+        v = np.zeros(3, np.float32)
+        flags = C.c_int32()
+        st = LslamStats()
+        if hasattr(corner_last, "data_ptr") and hasattr(surf_last, "data_ptr"):
+            for x in (corner_last, surf_last):
+                if not (x.is_cuda and x.is_contiguous() and x.dim() == 2 and x.shape[1] == 4 and x.element_size() == 4):
+                    raise ValueError("device clouds must be contiguous (n, 4) float32 tensors on the GPU")
+            rc = self.lib.lslam_loc_process_device(self.h, C.c_void_p(corner_last.data_ptr()), corner_last.shape[0],
+                                                   C.c_void_p(surf_last.data_ptr()), surf_last.shape[0], _fp(odom), int(stamp_ns),
+                                                   _fp(T), _fp(v), C.byref(flags), C.byref(st))
+        else:
+            c, s = _xyzi(corner_last), _xyzi(surf_last)
+            if c.shape[1] != s.shape[1]:
+                raise ValueError("corner and surf clouds must share a point layout")
+            rc = self.lib.lslam_loc_process(self.h, c.ctypes.data_as(C.c_void_p), len(c), s.ctypes.data_as(C.c_void_p), len(s),
+                                            c.shape[1] * 4, _fp(odom), int(stamp_ns), _fp(T), _fp(v), C.byref(flags), C.byref(st))
+        self._check(rc)
+        self.last_status, self.last_flags = rc, flags.value
+        if flags.value & DROPPED:
+            return None
+        self.last_stats = st
+        self.lidar_mapped = T.reshape(4, 4).copy()
+        self.velocity = v.copy() if flags.value & HAS_VELOCITY else None
+        return self.lidar_mapped.copy()
+
+    process_device = process
+
+    def match(self, corner, surf, pose):
+        """prepareFeatureFrame + optimizeTransform from a Twist, the node's pose state untouched -> (status, pose, stats)."""
+        c, s = _xyzi(corner), _xyzi(surf)
+        p = np.array(pose, dtype=np.float32).reshape(6)
+        st = LslamStats()
+        rc = self._check(self.lib.lslam_loc_match(self.h, c.ctypes.data_as(C.c_void_p), len(c), s.ctypes.data_as(C.c_void_p), len(s),
+                                                  c.shape[1] * 4, _fp(p), C.byref(st)))
+        return rc, p, st
+
+    def get_surround(self):
+        """prepareFeatureSurround on request -> (corner (n, 4), surf (m, 4))."""
+        nc, ns = C.c_size_t(), C.c_size_t()
+        self._check(self.lib.lslam_loc_get_surround(self.h, None, 0, C.byref(nc), None, 0, C.byref(ns)))
+        c, s = np.zeros((nc.value, 4), np.float32), np.zeros((ns.value, 4), np.float32)
+        self._check(self.lib.lslam_loc_get_surround(self.h, _fp(c), len(c), C.byref(nc), _fp(s), len(s), C.byref(ns)))
+        return c, s
+
+    def search_stats(self):
+        o = LslamLocSearchCounts()
+        self._check(self.lib.lslam_loc_search_stats(self.h, C.byref(o)))
+        return {f: (int(getattr(o, f)[0]), int(getattr(o, f)[1])) for f, _ in LslamLocSearchCounts._fields_}
+
+    def debug_knn5(self, which, queries):
+        """The search's parity tap -> (xyz (nq, 5, 3), d2 (nq, 5), how (nq,))."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        nq = len(q)
+        xyz, d2, how = np.zeros((nq, 5, 3), np.float32), np.zeros((nq, 5), np.float32), np.zeros(nq, np.uint8)
+        self._check(self.lib.lslam_loc_debug_knn5(self.h, int(which), q.ctypes.data_as(C.c_void_p), nq, q.shape[1] * 4, _fp(xyz), _fp(d2),
+                                                  how.ctypes.data_as(c_uint8_p)))
+        return xyz, d2, how
