@@ -496,6 +496,29 @@ int pgo_linearize(int n_v, const double *poses, int n_e, const int32_t *ij, cons
   return 0;
 }
 
+/* off-diagonal blocks H(a, b) (rows of vertex a, columns of vertex b) for `n_pairs` vertex pairs, [n_pairs][36] row-major;
+ * a pair outside the envelope (no edge between the two and no fill between them) reads as zero */
+int pgo_linearize_blocks(int n_v, const double *poses, int n_e, const int32_t *ij, const double *meas, const double *info,
+                         int fixed, int n_pairs, const int32_t *pairs, double *off_out) {
+  env_t E;
+  env_build(&E, n_v, n_e, ij);
+  double *b = (double *)malloc(sizeof(double) * 6 * (size_t)n_v);
+  linearize(&E, n_v, poses, n_e, ij, meas, info, fixed, b);
+  for (int k = 0; k < n_pairs; ++k) {
+    const int pa = E.inv[pairs[2 * k]], pb = E.inv[pairs[2 * k + 1]];
+    const int hi = pa > pb ? pa : pb, lo = pa > pb ? pb : pa;
+    double *o = off_out + 36 * (size_t)k;
+    if (hi == lo || lo < E.first[hi]) { memset(o, 0, 36 * sizeof(double)); continue; }
+    const double *B = env_blk(&E, E.A, hi, lo); /* H(hi, lo) */
+    const size_t s = (size_t)6 * (size_t)E.width[hi];
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) o[r * 6 + c] = pa > pb ? B[(size_t)r * s + c] : B[(size_t)c * s + r];
+  }
+  free(b);
+  env_free(&E);
+  return 0;
+}
+
 /* one damped solve (H + lambda I) dx = b at `poses` */
 int pgo_solve(int n_v, const double *poses, int n_e, const int32_t *ij, const double *meas, const double *info, int fixed,
               double lambda, double *dx_out) {

@@ -56,10 +56,15 @@ def pose_inv(a):
     return np.concatenate([-qrot(qi, a[..., :3]), qi], axis=-1)
 
 
+dq_clamped = 0  # how many updates took the |dq| > 1 -> identity branch of from_vector_mqt (tests reset and read it)
+
+
 def from_vector_mqt(d):
     """g2o fromVectorMQT: delta (..., 6) -> pose [t, q]."""
+    global dq_clamped
     v = d[..., 3:]
     w2 = 1.0 - (v * v).sum(-1, keepdims=True)
+    dq_clamped += int((w2 < 0).sum())
     w = np.sqrt(np.maximum(w2, 0.0))
     q = np.where(w2 < 0, np.array([0.0, 0.0, 0.0, 1.0]), np.concatenate([v, w], axis=-1))
     return np.concatenate([d[..., :3], q], axis=-1)
@@ -156,8 +161,9 @@ def solve_damped(H, b, lam, fixed):
     return dx
 
 
-def optimize(poses, ij, meas, info, fixed=0, max_iters=50, verbose=False):
-    """g2o-style LM.  Returns (poses, history of dicts)."""
+def optimize(poses, ij, meas, info, fixed=0, max_iters=50, verbose=False, on_trial=None):
+    """g2o-style LM.  Returns (poses, history of dicts).  on_trial(H, b, lam, dx, accepted), when given, sees every damped
+    solve (tests derive error bounds of an iterative solver from it)."""
     poses = poses.copy()
     hist = []
     lam = None
@@ -171,6 +177,7 @@ def optimize(poses, ij, meas, info, fixed=0, max_iters=50, verbose=False):
         rho, qmax = 0.0, 0
         while True:
             dx = solve_damped(H, b, lam, fixed)
+            lam_used = lam
             trial = oplus(poses, dx, fixed)
             tmp = chi2(trial, ij, meas, info)
             scale = float(dx @ (lam * dx + b)) + 1e-3
@@ -187,6 +194,8 @@ def optimize(poses, ij, meas, info, fixed=0, max_iters=50, verbose=False):
                 ni *= 2.0
                 cur_new = cur
                 accepted = False
+            if on_trial is not None:
+                on_trial(H, b, lam_used, dx, accepted)
             qmax += 1
             if not (rho < 0 and qmax < 10):
                 break
@@ -244,3 +253,53 @@ def make_graph(n_kf=300, n_loop=1200, laps=3, radius=40.0, seed=7, odo_sigma=(0.
         init[k + 1] = pose_mul(init[k][None], odo[k][None])[0]
     init[:, 3:] /= np.linalg.norm(init[:, 3:], axis=1, keepdims=True)
     return dict(gt=gt, init=init, ij=ij, meas=meas, info=info, n_odo=n_kf - 1)
+
+
+def make_graph_se3(n, n_extra, seed, fixed=0, box=20.0, meas_sigma=(0.05, 0.02), init_sigma=(1.0, 0.15), isolated=False):
+    """General SE(3) graph, everything make_graph never produces: positions uniform in a cube of side `box`, uniformly random
+    unit quaternions, an odometry chain + `n_extra` random edges each reversed with probability 1/2 (so about half have
+    i > j), one parallel duplicate and one antiparallel copy of an edge (both share the original's off-diagonal block), one
+    extra edge at the fixed vertex, dense SPD information matrices A A^T + c I (exactly symmetric), a random sign on every
+    pose and measurement quaternion (both hemispheres of q_e), and -- `isolated` -- one vertex without edges.
+    meas_sigma / init_sigma: (translation, quaternion-vector) standard deviations of the measurement noise and of the
+    initial estimate's perturbation (the fixed vertex starts at its ground truth).  Same keys as make_graph, plus `fixed`
+    and `isolated` (vertex id or None)."""
+    assert n >= (3 if isolated else 2) and 0 <= fixed < n
+    rng = np.random.default_rng(seed)
+    q = rng.normal(size=(n, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    gt = np.concatenate([rng.uniform(-box / 2, box / 2, (n, 3)), q], 1)
+    iso = None
+    if isolated:
+        iso = n - 1 if fixed != n - 1 else n - 2
+    chain = np.array([v for v in range(n) if v != iso])
+    edges = [(int(a), int(b)) for a, b in zip(chain[:-1], chain[1:])]
+    n_odo = len(edges)
+    while len(edges) < n_odo + n_extra:
+        a, b = (int(v) for v in rng.choice(chain, 2, replace=False))
+        edges.append((a, b))
+    edges = [(b, a) if rng.random() < 0.5 else (a, b) for a, b in edges]
+    a, b = edges[int(rng.integers(0, len(edges)))]
+    edges.append((a, b))  # parallel duplicate
+    a, b = edges[int(rng.integers(0, len(edges) - 1))]
+    edges.append((b, a))  # antiparallel pair
+    other = int(rng.choice(chain[chain != fixed]))
+    edges.append((other, fixed) if rng.random() < 0.5 else (fixed, other))  # an extra edge at the fixed vertex
+    ij = np.array(edges, np.int32)
+    ne = len(ij)
+
+    def perturbed(p, sig):
+        d = np.concatenate([rng.normal(0, sig[0], (len(p), 3)), rng.normal(0, sig[1], (len(p), 3))], 1)
+        out = pose_mul(p, from_vector_mqt(d))
+        out[:, 3:] /= np.linalg.norm(out[:, 3:], axis=1, keepdims=True)
+        return out
+
+    meas = perturbed(pose_mul(pose_inv(gt[ij[:, 0]]), gt[ij[:, 1]]), meas_sigma)
+    init = perturbed(gt, init_sigma)
+    init[fixed] = gt[fixed]
+    meas[:, 3:] *= rng.choice([-1.0, 1.0], (ne, 1))
+    init[:, 3:] *= rng.choice([-1.0, 1.0], (n, 1))
+    A = rng.normal(size=(ne, 6, 6))
+    info = A @ np.transpose(A, (0, 2, 1)) + rng.uniform(0.5, 2.0, (ne, 1, 1)) * np.eye(6)
+    info = 0.5 * (info + np.transpose(info, (0, 2, 1)))  # exactly symmetric
+    return dict(gt=gt, init=init, ij=ij, meas=meas, info=info, n_odo=n_odo, fixed=fixed, isolated=iso)

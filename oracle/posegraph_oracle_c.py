@@ -33,6 +33,7 @@ def lib():
         L.pgo_chi2.restype = C.c_double
         L.pgo_chi2.argtypes = [C.c_int, dp, ip, dp, dp]
         L.pgo_linearize.argtypes = [C.c_int, dp, C.c_int, ip, dp, dp, C.c_int, dp, dp, dp]
+        L.pgo_linearize_blocks.argtypes = [C.c_int, dp, C.c_int, ip, dp, dp, C.c_int, C.c_int, ip, dp]
         L.pgo_solve.argtypes = [C.c_int, dp, C.c_int, ip, dp, dp, C.c_int, C.c_double, dp]
         L.pgo_optimize.argtypes = [C.c_int, dp, C.c_int, ip, dp, dp, C.c_int, C.c_int, C.POINTER(PgoStats)]
         _lib = L
@@ -61,6 +62,17 @@ def linearize(poses, ij, meas, info, fixed=0):
     lib().pgo_linearize(n_v, _d(poses), len(ij), ij.ctypes.data_as(C.POINTER(C.c_int32)), _d(meas), _d(info), fixed, _d(diag), _d(b),
                         C.byref(c2))
     return diag, b, c2.value
+
+
+def offdiag_blocks(poses, ij, meas, info, pairs, fixed=0):
+    """-> H(a, b) for every (a, b) of `pairs`, shape (len(pairs), 6, 6)"""
+    poses, ij, meas, info = _args(poses, ij, meas, info)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    out = np.zeros((len(pairs), 6, 6))
+    ip = C.POINTER(C.c_int32)
+    lib().pgo_linearize_blocks(len(poses), _d(poses), len(ij), ij.ctypes.data_as(ip), _d(meas), _d(info), fixed, len(pairs),
+                               pairs.ctypes.data_as(ip), _d(out))
+    return out
 
 
 def solve(poses, ij, meas, info, lam, fixed=0):

@@ -621,6 +621,11 @@ def _pg_oracle():
 
 
 def test_posegraph_linearize_matches_oracle(pkg):
+    """Planar laps against the numpy oracle (central differences).  The bound is ten times the oracle's own floor on this graph:
+    oracle/posegraph_oracle.c (analytic Jacobians) and the numpy oracle differ here by 4.3e-10 max|H| and 3.9e-10 max|b| --
+    the finite-difference error -- hence 4.3e-9 max|H| and 3.9e-9 max|b| (they were 2e-6).  chi2 is a sum of 649 positive fp64
+    terms in another order: within 649 eps = 1.4e-13 of it.  General rotations, i > j edges and fixed != 0:
+    tests/test_gpu_posegraph_se3.py."""
     po = _pg_oracle()
     g = po.make_graph(n_kf=150, n_loop=500, laps=3, radius=18.0)
     pg = pkg.PoseGraph(0)
@@ -630,14 +635,15 @@ def test_posegraph_linearize_matches_oracle(pkg):
     Hd = H.toarray()
     n = len(g["init"])
     scale = np.abs(Hd).max()
-    assert abs(s["chi2"] - c2) <= 1e-10 * c2
+    tol_h, tol_b = 4.3e-9, 3.9e-9
+    assert abs(s["chi2"] - c2) <= len(g["ij"]) * np.finfo(np.float64).eps * c2
     for v in range(1, n):  # vertex 0 is fixed: identity block, zero rhs
-        assert np.abs(s["diag"][v] - Hd[6 * v:6 * v + 6, 6 * v:6 * v + 6]).max() <= 2e-6 * scale
+        assert np.abs(s["diag"][v] - Hd[6 * v:6 * v + 6, 6 * v:6 * v + 6]).max() <= tol_h * scale
     assert np.array_equal(s["diag"][0], np.eye(6)) and not s["b"][:6].any()
-    assert np.abs(s["b"][6:] - b[6:]).max() <= 2e-6 * np.abs(b).max()
+    assert np.abs(s["b"][6:] - b[6:]).max() <= tol_b * np.abs(b).max()
     for (i, j), blk in zip(s["off_ij"], s["off"]):
         ref = Hd[6 * i:6 * i + 6, 6 * j:6 * j + 6] if i != 0 else np.zeros((6, 6))
-        assert i < j and np.abs(blk - ref).max() <= 2e-6 * scale
+        assert i < j and np.abs(blk - ref).max() <= tol_h * scale
     # one damped solve against scipy's sparse LU on the oracle system
     lam = 1e-5 * Hd.diagonal()[6:].max()
     dx, cg = pg.solve(lam)

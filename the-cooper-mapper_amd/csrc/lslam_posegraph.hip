@@ -1499,10 +1499,15 @@ __global__ __launch_bounds__(GJ_BLOCK) void pgc_gj_persistent_kernel(GjArgs g) {
 __global__ void pg_update_kernel(const double *src, const double *dx, int n_v, int fixed, double *dst) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n_v) return;
+  if (v == fixed) {  // g2o never touches a fixed vertex: copied, not renormalised (|q| = 1 +- 1 ulp would drift per accepted step)
+#pragma unroll
+    for (int k = 0; k < 7; ++k) dst[7 * v + k] = src[7 * v + k];
+    return;
+  }
   const Pose x = load_pose(src + 7 * v);
   double d[6];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) d[k] = (v == fixed) ? 0.0 : dx[v * 6 + k];
+  for (int k = 0; k < 6; ++k) d[k] = dx[v * 6 + k];
   const double w2 = 1.0 - (d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
   Q4 dq = {d[3], d[4], d[5], sqrt(w2 > 0 ? w2 : 0.0)};
   if (w2 < 0) dq = {0, 0, 0, 1};
@@ -2465,11 +2470,22 @@ int lslam_pg_linearize(lslam_pg *pg, double *diag_out, double *off_out, int32_t 
   return LSLAM_OK;
 }
 
+// The fixed vertex is no unknown (g2o removes it; here its row is the identity with a zero right-hand side and no coupling): its
+// step is exactly zero.  Block-Jacobi PCG keeps it so; the second preconditioner level prolongs an aggregate's correction onto
+// every member, the fixed one included, and PCG then only drives that row back to within its tolerance (~1e-9 seen).
+static int zero_fixed_step(lslam_pg *pg) {
+  if (pg->fixed < 0) return LSLAM_OK;
+  PG_TRY(hipMemsetAsync(pg->d_x + (size_t)pg->fixed * 6, 0, 6 * sizeof(double), pg->stream));
+  return LSLAM_OK;
+}
+
 int lslam_pg_solve(lslam_pg *pg, double lambda, double *dx_out, int32_t *cg_iters) {
   if (!pg) return LSLAM_ERR_INVALID;
   PG_TRY(hipSetDevice(pg->device));
   int it = 0;
   int rc = solve(pg, lambda, 4000, 1e-10, &it);
+  if (rc) return rc;
+  rc = zero_fixed_step(pg);
   if (rc) return rc;
   if (dx_out) {
     PG_TRY(hipMemcpyAsync(dx_out, pg->d_x, (size_t)pg->n_v * 6 * 8, hipMemcpyDeviceToHost, pg->stream));
@@ -2644,6 +2660,8 @@ int lslam_pg_optimize(lslam_pg *pg, int32_t max_iters, lslam_pg_stats *st_out) {
       const double cg_tol = pg->env_tol;
       pg->fell_back = false;
       rc = solve(pg, lambda, max_cg, cg_tol, &cg);
+      if (rc) return rc;
+      rc = zero_fixed_step(pg);
       if (rc) return rc;
       st.cg_iterations += cg;
       hipLaunchKernelGGL(pg_update_kernel, dim3((pg->n_v + 127) / 128), dim3(128), 0, pg->stream, pg->d_poses,

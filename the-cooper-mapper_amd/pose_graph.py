@@ -62,6 +62,7 @@ class PoseGraph:
         self._ij = []
         self._meas = []
         self._info = []
+        self.fixed = 0  # the vertex lslam_pg_create pins (g2o: setFixed); -1 pins none
         self.h = None
         self._cb = None
         self.last_stats = None
@@ -92,12 +93,16 @@ class PoseGraph:
         return st.iterations
 
     # ---- bulk construction / access ---------------------------------------------------
-    def set_graph(self, poses7, ij, meas7, info):
+    def set_graph(self, poses7, ij, meas7, info, fixed=0):
+        """Replace the graph; `fixed` is the vertex held at its estimate (default: the first, as add_se3_node)."""
         self._drop(keep_estimates=False)
         self._nodes = [p for p in np.asarray(poses7, np.float64).reshape(-1, 7)]
         self._ij = [tuple(int(v) for v in e) for e in np.asarray(ij).reshape(-1, 2)]
         self._meas = [m for m in np.asarray(meas7, np.float64).reshape(-1, 7)]
         self._info = [w for w in np.asarray(info, np.float64).reshape(-1, 6, 6)]
+        self.fixed = int(fixed)
+        if self.fixed >= len(self._nodes):
+            raise ValueError("fixed vertex %d of a graph with %d vertices" % (self.fixed, len(self._nodes)))
         self._drop()
 
     # ---- g2o text format (solver_g2o.cpp:97-100) -----------------------------------------
@@ -126,9 +131,10 @@ class PoseGraph:
         return dict(poses=poses, ij=ij, meas=meas, info=info, fixed=fx.value)
 
     def load(self, path):
-        """Replace the graph by the one in a .g2o file."""
+        """Replace the graph by the one in a .g2o file; the file's FIX vertex stays the fixed one (a file without FIX: the
+        first vertex, as add_se3_node)."""
         g = PoseGraph.read_g2o(path, self.lib)
-        self.set_graph(g["poses"], g["ij"], g["meas"], g["info"])
+        self.set_graph(g["poses"], g["ij"], g["meas"], g["info"], fixed=g["fixed"] if g["fixed"] >= 0 else 0)
         return g
 
     def poses(self):
@@ -259,7 +265,7 @@ class PoseGraph:
         info = np.ascontiguousarray(np.stack(self._info) if ne else np.zeros((0, 6, 6)), np.float64)
         h = C.c_void_p()
         rc = self.lib.lslam_pg_create(self.device, len(poses), _dp(poses), ne, ij.ctypes.data_as(c_int32_p),
-                                      _dp(meas), _dp(info), 0, C.byref(h))
+                                      _dp(meas), _dp(info), self.fixed, C.byref(h))
         if rc != 0:
             raise LslamError(rc, self.lib.lslam_pg_last_error().decode())
         self.h = h

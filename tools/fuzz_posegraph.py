@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Seeded fuzz of the pose-graph solver's two forms: random graphs (chains with random loop edges, sizes from 2
 keyframes up, hubs, disconnected pockets joined by one edge) solved by the persistent kernels and by the launch loop;
+every other block of seeds draws general SE(3) graphs instead (oracle/posegraph_oracle.make_graph_se3: random rotations,
+reversed and duplicated edges, both quaternion hemispheres, dense information matrices, a random fixed vertex);
 the damped steps must agree to the solves' tolerance, LM must land on the same chi2, and a persistent run repeated must
 give the same bits.  Run by tests/test_gpu_fuzz.py with a small budget."""
 import importlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 
 def random_graph(rng, n):
@@ -33,7 +36,16 @@ def random_graph(rng, n):
     info = np.tile(np.diag([0.8, 0.4, 0.8, 1.0, 2.0, 1.0]), (len(ij), 1, 1)) * rng.uniform(0.5, 2.0, (len(ij), 1, 1))
     init = gt.copy()
     init[1:, :3] += rng.normal(0, 0.3, (n - 1, 3))
-    return init, ij, meas, info
+    return init, ij, meas, info, 0
+
+
+def random_graph_se3(rng, n, seed):
+    """the general family, from a mild start (LM's accept / reject decisions must not hang on the solves' last digits)"""
+    po = importlib.import_module("posegraph_oracle")
+    fixed = int(rng.integers(0, n))
+    g = po.make_graph_se3(n, int(rng.integers(0, 3 * n + 1)), seed, fixed=fixed, init_sigma=(0.3, 0.05),
+                          isolated=bool(n >= 3 and rng.random() < 0.25))
+    return g["init"], g["ij"], g["meas"], g["info"], fixed
 
 
 def run(pkg, seeds, sizes):
@@ -41,13 +53,14 @@ def run(pkg, seeds, sizes):
     for seed in seeds:
         rng = np.random.default_rng(seed)
         n = int(sizes[seed % len(sizes)])
-        init, ij, meas, info = random_graph(rng, n)
+        se3 = (seed // len(sizes)) % 2 == 1  # seeds 0-9 planar, 10-19 SE(3), ...: both families meet every size
+        init, ij, meas, info, fixed = random_graph_se3(rng, n, seed) if se3 else random_graph(rng, n)
         out = {}
         for mode in ("1", "0", "1b"):
             os.environ["LSLAM_PG_PERSISTENT"] = mode[0]
             os.environ["LSLAM_PG_COARSE"] = str(seed % 2)
             pg = pkg.PoseGraph(0)
-            pg.set_graph(init, ij, meas, info)
+            pg.set_graph(init, ij, meas, info, fixed=fixed)
             pg.linearize()
             dx, it = pg.solve(1e-3)
             its = pg.optimize(8)
