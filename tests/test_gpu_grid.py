@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+import scanmatch_ref
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LANE, GRID = 1, 3          # LSLAM_SEARCH_LANE / _GRID
@@ -88,7 +90,7 @@ def test_grid_knn5_matches_oracle_on_synthetic_map(ctx, oracle, synth):
 
 def test_grid_sweep_taps_equal_tree_sweep(ctx, small_problem):
     """One sweep at the initial pose: per-point neighbours, distances, flags and coefficients of the grid sweep (both passes)
-    are the tree sweep's, bit for bit; the sums differ by summation order only."""
+    are the tree sweep's, bit for bit; the sums differ by summation order only -- each entry held to the float64 reference."""
     pr = small_problem
     ctx.map_set(pr["map_corner"], pr["map_surf"])
     ctx.scan_set(pr["corner"], pr["surf"])
@@ -100,7 +102,13 @@ def test_grid_sweep_taps_equal_tree_sweep(ctx, small_problem):
         assert np.array_equal(bits(a["d2"]), bits(b["d2"]))
         assert np.array_equal(bits(a["coeff"]), bits(b["coeff"]))
         assert a["sums"][27] == b["sums"][27] and a["sums"][28] == b["sums"][28]
-        assert np.allclose(a["sums"], b["sums"], rtol=2e-5, atol=1e-3)
+        # each sweep's 27 sums against the float64 reference of its taps, entry by entry; the two against each other within twice that
+        S, u = scanmatch_ref.reference_sums(pr["init_pose"], np.concatenate([pr["corner"], pr["surf"]]), a["coeff"], a["flags"])
+        ua, ub = scanmatch_ref.units(a["sums"], S, u), scanmatch_ref.units(b["sums"], S, u)
+        print("jtj_mode %d: tree sweep max %.2f units, grid sweep max %.2f units" % (jtj, ua.max(), ub.max()))
+        assert ua.max() <= scanmatch_ref.K and ub.max() <= scanmatch_ref.K, (ua.round(1).tolist(), ub.round(1).tolist())
+        assert (np.abs(a["sums"][:27].astype(np.float64) - b["sums"][:27].astype(np.float64)) <= 2 * scanmatch_ref.K * u).all()
+        assert np.allclose(a["sums"][27:], b["sums"][27:], rtol=2e-5, atol=1e-3)  # counters (equal, above) and the score sum
     assert ctx.grid_launches() >= 2
 
 

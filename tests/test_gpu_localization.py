@@ -163,6 +163,29 @@ def test_single_sweep_matches_the_oracle(pkg, ctx, synth, scene, refs, name):
     node.close()
 
 
+def test_single_sweep_at_a_tilted_pose_matches_the_oracle(pkg, ctx, synth, scene, refs):
+    """The body of test_single_sweep_matches_the_oracle at roll 0.9, pitch -0.7, yaw 2.4 rad: loc_fit_kernel shares
+    jacobian_row and block_accumulate with the sweep kernels, and every other frame of this file has roll, pitch ~ 0.01.
+    The sweep is re-expressed for the tilted pose (scanmatch_ref.reexpress), so its points land where they did."""
+    import scanmatch_ref
+    ref = refs["filtered"]["ref"]
+    node = _node(pkg, ctx, scene, filt=True)
+    c, s = scene["sweeps"][0]
+    p0 = synth.perturb_pose(scene["poses"][0], seed=99, dt=0.2, dr_deg=1.0)
+    pn = p0.copy()
+    pn[:3] = (0.9, -0.7, 2.4)
+    c, s = scanmatch_ref.reexpress(c, p0, pn), scanmatch_ref.reexpress(s, p0, pn)
+    ok, pr, st_r = ref.match(c, s, pn)
+    status, p, st = node.match(c, s, pn)
+    print("tilted: status %d iterations %d line %d plane %d rows %d |dt| %.2e |dr| %.2e" %
+          (status, st.iterations, st.n_line, st.n_plane, st.n_rows, np.abs(p[3:] - pr[3:]).max(), np.abs(p[:3] - pr[:3]).max()))
+    assert st_r.n_rows > 500 and st_r.iterations >= 2
+    assert (status == 0) == ok
+    assert (st.iterations, st.n_line, st.n_plane, st.n_rows) == (st_r.iterations, st_r.n_line, st_r.n_plane, st_r.n_rows)
+    assert np.abs(p[3:] - pr[3:]).max() <= TOL_T and np.abs(p[:3] - pr[:3]).max() <= TOL_R
+    node.close()
+
+
 def test_trajectory_from_the_three_map_inputs(pkg, ctx, scene, refs, oracle, tmp_path):
     """Host clouds (raw and filtered), a directory written by lslam_fmap_save (filtered at load), and a map adopted from an
     lslam_fmap: every sweep's pose within the tolerances of the restatement's run, velocity to tolerance / dt, the reset sweep

@@ -9,7 +9,8 @@ import threading
 import numpy as np
 import pytest
 
-from test_gpu_stereo import bits, gpu_cam
+from test_gpu_stereo import assert_stereo_sums_per_entry, bits, gpu_cam
+from test_scanmatch_ref import stereo_cases
 from test_oracle_stereo import default_cam
 
 pytestmark = pytest.mark.gpu
@@ -96,18 +97,21 @@ def test_stereo_sums_batch_matches_oracle_and_single_sets(ctx, oracle, small_pro
     got = ctx.stereo_sums_batch(poses)
     assert got.shape == (5, 32)
     assert not got[0].any()  # the empty set: all zeros
-    for k in range(1, len(sizes)):
-        ref = oracle.stereo_sums(*sets[k], ocam, poses[k])
-        g = got[k]
-        assert int(g[27]) == int(ref[27]) and int(g[31]) == int(ref[28]), k
-        assert g[28] == 0 and g[29] == 0 and g[30] == 0
-        scale = np.abs(ref[:21]).max()
-        assert np.abs(g[:21] - ref[:21]).max() <= 1e-4 * scale, k
-        assert np.abs(g[21:27] - ref[21:27]).max() <= 1e-4 * max(np.abs(ref[21:27]).max(), 1e-3 * scale), k
+    for k in range(1, len(sizes)):  # entry by entry against the float64 sum of the oracle's rows (tests/scanmatch_ref.py)
+        assert_stereo_sums_per_entry(got[k], oracle, *sets[k], ocam, poses[k], k)
     for k in range(1, len(sizes)):  # each set alone through the one-set form: the same bits
         ctx.stereo_set(*sets[k], cam)
         alone = ctx.stereo_sums(poses[k])
         assert np.array_equal(alone.view(np.uint64), got[k].view(np.uint64)), k
+    # the same at two tilted poses of the general family and the near-identity one in ONE batch: a set per pose, landmarks in
+    # the camera's view there, sizes 1500 / 257 / 63
+    cases = stereo_cases(small_problem)
+    tsets = [(lm[:n], ob[:n], w[:n]) for (_, lm, ob, w, _), n in zip(cases, (1500, 257, 63))]
+    tposes = np.stack([c[4] for c in cases])
+    ctx.stereo_set_batch(tsets, cam)
+    tgot = ctx.stereo_sums_batch(tposes)
+    for k in range(len(tsets)):
+        assert_stereo_sums_per_entry(tgot[k], oracle, *tsets[k], ocam, tposes[k], cases[k][0])
     ctx.stereo_clear()
 
 
