@@ -208,6 +208,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* 7: no struct changed; new entry points (lslam_lmap_*: the sliding-window local map). */
 /* still 7: no struct changed; new entry points (lslam_sreg_*: the registration node with the IMU de-skew branch). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_loc_*: the localisation node). */
+/* still 7: no struct changed; new entry points and a struct of their own (lslam_oreg_*: the registration node for organised clouds). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -538,7 +539,8 @@ int lslam_voxel_grid2(lslam_ctx *ctx, const void *cloud_a, size_t n_a, const voi
  * setScanBuffersFor :471-531, setRegionBuffersFor :427-469, markAsPicked :533-555 and
  * pointClassify :557-687) on the ring-sorted full-resolution cloud MultiScanRegistration::process
  * builds (MultiScanRegistration.cpp:178-190).  Building that cloud from raw driver packets is the
- * caller's here (ring from the vertical angle, IMU de-skew); lslam_sreg_* further down does all of it on the device. */
+ * caller's here (ring from the vertical angle, IMU de-skew); lslam_sreg_* further down does all of it on the device, and
+ * lslam_oreg_* the same for an organised cloud whose points carry their ring (OrganisedScanRegistration). */
 typedef struct lslam_reg_params {     /* RegistrationParams, ScanRegistration.h:45-112 */
   int32_t n_feature_regions;          /* 6; 1 .. 512 (the device keeps the sort words of a ring's regions in LDS) */
   int32_t curvature_region;           /* 5 */
@@ -706,6 +708,62 @@ int lslam_sreg_process(lslam_sreg *sr, const void *cloud, size_t n_points, size_
 /* The last sweep's registered cloud (/velodyne_cloud_2: {x', y', z', ring + relTime}, ring-sorted) and its n_rings x {first,
  * last} ranges, on request (either pointer may be NULL; *n_out = the cloud's size). */
 int lslam_sreg_cloud(lslam_sreg *sr, float *out_xyzc, size_t cap, size_t *n_out, int32_t *ranges_out);
+
+/* ---- the registration node for organised clouds, resident on the device ------------------------------------------------
+ *
+ * OrganisedScanRegistration (odometry/OrganizedScanRegistration.cpp:82-150 on ScanRegistration.cpp:89-188, :684-707) as one
+ * object: a height x width image whose points carry their own ring goes up once; the validity test (finite coordinates, then
+ * x*x + y*y + z*z < blind_radius^2 drops the point -- strictly less: a point on the radius stays), relTime = (float)(scan_period
+ * * (double)column / width), the 4th channel (float)ring + relTime -- the point's ring field, NOT its row --, the per-row clouds
+ * concatenated in row order (a stable compaction of the row-major image: no sort, no atan), the height x {first, last} ranges
+ * and the feature extraction all run on the device, the four lists stay in an lslam_fset for lslam_odom_process, and the host
+ * waits once.  x, y, z are copied unchanged: this node has no axis swap.  Every number of it is exact float arithmetic in the
+ * reference's order, so the cloud, the ranges and the lists equal a CPU restatement bit for bit
+ * (tests/organised_registration_ref.py).
+ *
+ * IMU: the class inherits the subscription (lslam_oreg_imu_push = lslam_sreg_imu_push, the same history type), but its
+ * process() never calls setIMUTransformFor / transformToStartIMU.  So with an IMU heard the points are NOT de-skewed, _imuCur
+ * and _imuPositionShift stay as constructed (zero) for the life of the node, and /imu_trans is {start pitch, yaw, roll}, zeros,
+ * the rotated zero shift, rotateYXZ(0 - _imuStart.velocity, -yaw, -pitch, -roll): host arithmetic on the history alone.  No IMU
+ * state reaches the device. */
+typedef struct lslam_oreg lslam_oreg;
+typedef struct lslam_oreg_stats {
+  uint64_t sweeps;     /* sweeps this node has registered */
+  size_t n_cells;      /* height * width of this sweep's image */
+  size_t n_points;     /* points kept in this sweep's registered cloud */
+  int32_t imu_states;  /* IMU states held when this sweep was processed (0: none heard) */
+  int32_t launches;    /* kernels the node itself launches per sweep (6: count, place, ranges, the extraction's three), counted
+                          from the code; the memsets of the extraction are not in it */
+  size_t bytes_up;     /* host -> device, this sweep: one block (result words, ranges, row counters, column times, cells) */
+  size_t bytes_down;   /* device -> host, this sweep: the result words and the ranges */
+} lslam_oreg_stats;
+/* params NULL: lslam_reg_default_params.  scan_period > 0 (the reference's 0.1), blind_radius finite and >= 0 (the reference's
+ * blindRaduis parameter, 2.5), imu_history_size 1 .. 512 (200).  The node's buffers are its own and go with it. */
+int lslam_oreg_create(lslam_ctx *ctx, const lslam_reg_params *params, float scan_period, float blind_radius,
+                      int32_t imu_history_size, lslam_oreg **out);
+void lslam_oreg_destroy(lslam_oreg *og);
+/* As lslam_sreg_imu_push / _imu_info / _imu_clear: a stamp that is not later than the previous one is refused. */
+int lslam_oreg_imu_push(lslam_oreg *og, int64_t stamp_ns, double roll, double pitch, double yaw, const double linear_acceleration[3]);
+int lslam_oreg_imu_info(const lslam_oreg *og, int32_t *size, double last_position[3], double last_velocity[3]);
+int lslam_oreg_imu_clear(lslam_oreg *og);
+/* OrganisedScanRegistration::process(cloud, scanTime): cloud = the row-major image, height * width points stride_bytes apart,
+ * {x, y, z} floats at byte 0 of each point and the ring as a uint16 at ring_offset_bytes (the reference's PointXYZIT: stride 32,
+ * ring at 26).  The device format is 16 bytes per cell, {x, y, z, word} with the ring in the low 16 bits of word (the upper 16
+ * are ignored): a caller who has that layout (stride 16, ring at 12) is uploaded as is, anything else is repacked on the host.
+ * out receives the four lists (counts[4] their sizes, may be NULL); imu_trans (may be NULL) the /imu_trans message described
+ * above (all zero while no IMU has been heard).  A sweep that keeps nothing succeeds with empty lists.  A width above 2560 is
+ * fine as long as no row KEEPS more than 2560 points.
+ * Refused (LSLAM_ERR_INVALID, outputs zeroed, out reads empty) before anything is enqueued, the node exactly as before, the last
+ * sweep's cloud included: null node, null cloud, a feature set on another device; height 0, width 0, height > 4096, height *
+ * width > 0x3FFFFFFF; stride_bytes < 12 or not a multiple of 4, ring_offset_bytes + 2 > stride_bytes.  Refused on the device,
+ * behind the same wait: a row that keeps more than 2560 points (the extraction's LDS limit) -- the node is usable, but
+ * lslam_oreg_cloud has nothing to hand out until the next sweep succeeds. */
+int lslam_oreg_process(lslam_oreg *og, const void *cloud, size_t height, size_t width, size_t stride_bytes, size_t ring_offset_bytes,
+                       int64_t scan_time_ns, lslam_fset *out, size_t counts[4], float imu_trans[12], lslam_oreg_stats *stats);
+/* The last sweep's registered cloud ({x, y, z, ring + relTime}, the rows concatenated) and its height x {first, last} ranges
+ * (height = that sweep's), on request (either pointer may be NULL; *n_out = the cloud's size).  ranges_out is written only on
+ * success. */
+int lslam_oreg_cloud(lslam_oreg *og, float *out_xyzc, size_t cap, size_t *n_out, int32_t *ranges_out);
 
 /* ---- coarse alignment of a loop-closure candidate ------------------------------
  * Replaces LoopDetector::corseMatching (pose_graph/loop_detector.hpp:232-255), i.e.

@@ -3,6 +3,8 @@
 //
 //   lidar_slam::MultiScanRegistration    odometry/MultiScanRegistration.cpp:78-200 on ScanRegistration.cpp:89-188, :684-707
 //                                        (handleIMUMessage, handleCloudMessage, process: the registration node, lslam_sreg_*)
+//   lidar_slam::OrganisedScanRegistration  odometry/OrganizedScanRegistration.cpp:82-150: the same node for a height x width cloud
+//                                        whose points carry their ring (lslam_oreg_*)
 //   lidar_slam::LaserOdometry::process   /root/reference/L_SLAM/src/odometry/LaserOdometry.cpp:288-326
 //                                        (+ scanMatch :328-647 = lslam_odometry_match, transformToEnd
 //                                        :156-168 = lslam_transform_to_end, transformUpdate :649-653)
@@ -147,6 +149,108 @@ private:
   size_t _counts[4];
   float _imuTrans[12];
   lslam_sreg_stats _stats;
+  std::string _err;
+};
+
+// OrganisedScanRegistration: the registration node for an organised cloud (the reference's Pandar / Ouster front end) -- any
+// type with `.height`, `.width` and `.points` (row-major, height * width of them) whose points have float x, y, z first and a
+// uint16_t member `ring`; sizeof(point) is the stride and the ring is read where the member lies.  Validity, relTime from the
+// column, ring + relTime, the rows concatenated, the ranges and the extraction run on the device behind one wait (lslam_oreg_*,
+// include/lslam_c.h).  As in the reference an IMU that has been heard changes /imu_trans only: the points are not de-skewed.
+class OrganisedScanRegistration {
+public:
+  explicit OrganisedScanRegistration(lslam_ctx *ctx, float scanPeriod = 0.1f, float blindRadius = 2.5f,
+                                     const lslam_reg_params *config = nullptr, int imuHistorySize = 200)
+      : _og(nullptr), _fs(nullptr), _height(0), _systemDelay(SYSTEM_DELAY), _cloudReceiveCount(0) {
+    std::memset(_imuTrans, 0, sizeof(_imuTrans));
+    std::memset(_counts, 0, sizeof(_counts));
+    std::memset(&_stats, 0, sizeof(_stats));
+    if (lslam_abi_version() != LSLAM_ABI_VERSION || lslam_sizeof_opts() != sizeof(lslam_opts) || lslam_sizeof_stats() != sizeof(lslam_stats)) {
+      _err = "liblslam_hip was built from another include/lslam_c.h than this program (ABI version / struct sizes differ)";
+      return;
+    }
+    if (lslam_oreg_create(ctx, config, scanPeriod, blindRadius, imuHistorySize, &_og) != LSLAM_OK || lslam_fset_create(ctx, &_fs) != LSLAM_OK)
+      _err = lslam_last_error();
+  }
+  ~OrganisedScanRegistration() {
+    if (_og) lslam_oreg_destroy(_og);
+    if (_fs) lslam_fset_destroy(_fs);
+  }
+  OrganisedScanRegistration(const OrganisedScanRegistration &) = delete;
+  OrganisedScanRegistration &operator=(const OrganisedScanRegistration &) = delete;
+  enum { SYSTEM_DELAY = 2 };  // the first clouds of a session are skipped (OrganizedScanRegistration.cpp:62-65)
+  bool ok() const { return _og && _fs; }
+  // ScanRegistration::handleIMUMessage after getRPY; false for a stamp that is not later than the previous one
+  bool handleIMUMessage(int64_t stampNs, double roll, double pitch, double yaw, const double linearAcceleration[3]) {
+    if (!ok()) return false;
+    return lslam_oreg_imu_push(_og, stampNs, roll, pitch, yaw, linearAcceleration) == LSLAM_OK || fail();
+  }
+  bool hasIMUData() const {
+    int32_t n = 0;
+    return _og && lslam_oreg_imu_info(_og, &n, nullptr, nullptr) == LSLAM_OK && n > 0;
+  }
+  // false while the system delay lasts (nothing processed) and on a backend error
+  template <typename Cloud>
+  bool handleCloudMessage(const Cloud &laserCloudIn, int64_t stampNs) {
+    ++_cloudReceiveCount;
+    if (_systemDelay > 0) {
+      --_systemDelay;
+      return false;
+    }
+    return process(laserCloudIn, stampNs);
+  }
+  template <typename Cloud>
+  bool process(const Cloud &laserCloudIn, int64_t scanTimeNs) {
+    if (!ok()) return false;
+    const size_t h = laserCloudIn.height, w = laserCloudIn.width;
+    if (laserCloudIn.points.size() != h * w) {
+      _err = "OrganisedScanRegistration::process: the cloud is not height x width";
+      return false;
+    }
+    const void *p = nullptr;
+    size_t ringOffset = 0;
+    if (h && w) {
+      p = static_cast<const void *>(&laserCloudIn.points[0]);
+      ringOffset = (size_t)(reinterpret_cast<const char *>(&laserCloudIn.points[0].ring) - static_cast<const char *>(p));
+    }
+    if (lslam_oreg_process(_og, p, h, w, sizeof(laserCloudIn.points[0]), ringOffset, scanTimeNs, _fs, _counts, _imuTrans, &_stats) < 0)
+      return fail();
+    _height = h;
+    return true;
+  }
+  lslam_fset *featureSet() const { return _fs; }  // /laser_cloud_sharp, _less_sharp, _flat, _less_flat, in HBM
+  const size_t *counts() const { return _counts; }
+  const float *imuTrans() const { return _imuTrans; }  // /imu_trans: four points {x, y, z}
+  // /velodyne_cloud_2 on request: packed {x, y, z, ring + relTime}; ranges (optional): resized to height x {first, last}
+  bool laserCloud(std::vector<float> &cloud, std::vector<int32_t> *ranges = nullptr) {
+    if (!ok()) return false;
+    cloud.resize(4 * _stats.n_points);
+    if (ranges) ranges->assign(2 * _height, 0);
+    size_t n = 0;
+    if (lslam_oreg_cloud(_og, cloud.data(), _stats.n_points, &n, ranges ? ranges->data() : nullptr) < 0) {
+      cloud.clear();
+      return fail();
+    }
+    cloud.resize(4 * n);
+    return true;
+  }
+  const lslam_oreg_stats &nodeStats() const { return _stats; }
+  long cloudReceiveCount() const { return _cloudReceiveCount; }
+  const std::string &lastError() const { return _err; }
+
+private:
+  bool fail() {
+    _err = lslam_last_error();
+    return false;
+  }
+  lslam_oreg *_og;
+  lslam_fset *_fs;
+  size_t _height;
+  int _systemDelay;
+  long _cloudReceiveCount;
+  size_t _counts[4];
+  float _imuTrans[12];
+  lslam_oreg_stats _stats;
   std::string _err;
 };
 

@@ -17,12 +17,12 @@ from .scan_match import Comm, Context, ScanMatch
 from .pose_graph import PoseGraph
 from .feature_map import FeatureMap, voxel_grid, voxel_grid2
 from . import scan_registration
-from .scan_registration import MultiScanRegistration
+from .scan_registration import MultiScanRegistration, OrganisedScanRegistration
 from .loop_closure import KeyFrame, Loop, LoopDetector
 from .graph import Graph, KeyframeUpdater
 from .local_feature_map import LocalFeatureMap
 from .pipeline import DeviceLaserOdometry, LaserOdometry, LaserMapping, LaserMappingLocal
 from .laser_localization import LaserLocalization
 
-__all__ = ["Comm", "Context", "ScanMatch", "PoseGraph", "FeatureMap", "voxel_grid", "voxel_grid2", "scan_registration", "MultiScanRegistration", "KeyFrame", "Loop", "LoopDetector", "Graph", "KeyframeUpdater", "LaserOdometry", "DeviceLaserOdometry", "LaserMapping", "LaserMappingLocal", "LaserLocalization", "LocalFeatureMap", "LslamError", "LslamOpts", "LslamStats", "LslamMapInfo", "LslamStereoCam",
+__all__ = ["Comm", "Context", "ScanMatch", "PoseGraph", "FeatureMap", "voxel_grid", "voxel_grid2", "scan_registration", "MultiScanRegistration", "OrganisedScanRegistration", "KeyFrame", "Loop", "LoopDetector", "Graph", "KeyframeUpdater", "LaserOdometry", "DeviceLaserOdometry", "LaserMapping", "LaserMappingLocal", "LaserLocalization", "LocalFeatureMap", "LslamError", "LslamOpts", "LslamStats", "LslamMapInfo", "LslamStereoCam",
            "Status", "lib_path", "load_library", "build_library"]

@@ -129,6 +129,12 @@ class LslamOdomStats(C.Structure):
                 ("sweeps", C.c_uint64), ("n_last_corner", C.c_size_t), ("n_last_surf", C.c_size_t)]
 
 
+class LslamOregStats(C.Structure):
+    """lslam_oreg_stats (include/lslam_c.h)."""
+    _fields_ = [("sweeps", C.c_uint64), ("n_cells", C.c_size_t), ("n_points", C.c_size_t), ("imu_states", C.c_int32),
+                ("launches", C.c_int32), ("bytes_up", C.c_size_t), ("bytes_down", C.c_size_t)]
+
+
 class LslamSregStats(C.Structure):
     """lslam_sreg_stats (include/lslam_c.h)."""
     _fields_ = [("sweeps", C.c_uint64), ("n_points", C.c_size_t), ("imu_states", C.c_int32), ("launches", C.c_int32),
@@ -302,6 +308,14 @@ SYMBOLS = {
     "lslam_sreg_process": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int64, C.c_void_p, C.POINTER(C.c_size_t),
                                      c_float_p, C.POINTER(LslamSregStats)]),
     "lslam_sreg_cloud": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, C.POINTER(C.c_size_t), c_int32_p]),
+    "lslam_oreg_create": (C.c_int, [C.c_void_p, C.POINTER(LslamRegParams), C.c_float, C.c_float, C.c_int32, C.POINTER(C.c_void_p)]),
+    "lslam_oreg_destroy": (None, [C.c_void_p]),
+    "lslam_oreg_imu_push": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, c_double_p]),
+    "lslam_oreg_imu_info": (C.c_int, [C.c_void_p, c_int32_p, c_double_p, c_double_p]),
+    "lslam_oreg_imu_clear": (C.c_int, [C.c_void_p]),
+    "lslam_oreg_process": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int64, C.c_void_p,
+                                     C.POINTER(C.c_size_t), c_float_p, C.POINTER(LslamOregStats)]),
+    "lslam_oreg_cloud": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, C.POINTER(C.c_size_t), c_int32_p]),
     "lslam_loc_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "lslam_loc_destroy": (None, [C.c_void_p]),
     "lslam_loc_setup_scan_filter_size": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),

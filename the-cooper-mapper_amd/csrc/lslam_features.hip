@@ -1396,6 +1396,76 @@ void sr_rotate_yxz_neg(const SrImu &st, float v[3]) {  // rotateYXZ(v, -yaw, -pi
   sr_rot_h(st.cr, -st.sr, v[0], v[1]);
 }
 size_t sr_up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// _imuHistory (CircularBuffer.h) with handleIMUMessage and interpolateIMUStateFor(0): host arithmetic on the history alone,
+// held by both registration nodes (lslam_sreg, lslam_oreg)
+struct SrImuHistory {
+  std::vector<SrImu> hist;  // `size` states from `first` on, the oldest overwritten when full
+  size_t first = 0, size = 0;
+  const SrImu &at(size_t k) const { return hist[(first + k) % hist.size()]; }
+  void clear() { first = size = 0; }
+  bool later_than_last(int64_t stamp_ns) const { return !size || stamp_ns > at(size - 1).stamp; }
+  // handleIMUMessage, ScanRegistration.cpp:96-117 (the stamp is later than the last state's: the caller has checked)
+  void push(int64_t stamp_ns, double roll, double pitch, double yaw, const double *la) {
+    float acc[3];
+    acc[0] = float(la[1] - std::sin(roll) * std::cos(pitch) * 9.81);
+    acc[1] = float(la[2] - std::cos(roll) * std::cos(pitch) * 9.81);
+    acc[2] = float(la[0] + std::sin(pitch) * 9.81);
+    SrImu st;
+    st.stamp = stamp_ns;
+    sr_set_angles(st, (float)roll, (float)pitch, (float)yaw);
+    if (size) {
+      sr_rot_h(st.cr, st.sr, acc[0], acc[1]);  // rotateZXY(acc, roll, pitch, yaw)
+      sr_rot_h(st.cp, st.sp, acc[1], acc[2]);
+      sr_rot_h(st.cy, st.sy, acc[2], acc[0]);
+      const SrImu &prev = at(size - 1);
+      const float dt = float(sr_to_sec(stamp_ns - prev.stamp));
+      for (int d = 0; d < 3; ++d) {
+        st.pos[d] = (prev.pos[d] + prev.vel[d] * dt) + ((0.5f * acc[d]) * dt) * dt;
+        st.vel[d] = prev.vel[d] + acc[d] * dt;
+      }
+    }
+    const size_t cap = hist.size();
+    if (size < cap) {
+      hist[(first + size) % cap] = st;
+      size++;
+    } else {
+      hist[first] = st;
+      first = (first + 1) % cap;
+    }
+  }
+  void info(int32_t *n, double last_position[3], double last_velocity[3]) const {
+    if (n) *n = (int32_t)size;
+    if (!size) return;
+    const SrImu &l = at(size - 1);
+    for (int d = 0; d < 3; ++d) {
+      if (last_position) last_position[d] = (double)l.pos[d];
+      if (last_velocity) last_velocity[d] = (double)l.vel[d];
+    }
+  }
+  // reset(scanTime): _imuIdx = 0, interpolateIMUStateFor(0, _imuStart) -- on the host, as the reference does it (size > 0)
+  SrImu start_for(int64_t scan_time_ns) const {
+    size_t idx = 0;
+    double time_diff = sr_to_sec(scan_time_ns - at(0).stamp) + 0.0f;
+    while (idx < size - 1 && time_diff > 0) time_diff = sr_to_sec(scan_time_ns - at(++idx).stamp) + 0.0f;
+    const SrImu &S = at(idx);
+    if (idx == 0 || time_diff > 0) return S;
+    SrImu start;
+    const SrImu &E = at(idx - 1);
+    const float ratio = -time_diff / sr_to_sec(S.stamp - E.stamp);
+    const float inv = 1 - ratio;
+    float yaw;
+    if (S.yaw - E.yaw > M_PI) yaw = S.yaw * inv + (E.yaw + 2 * M_PI) * ratio;
+    else if (S.yaw - E.yaw < -M_PI) yaw = S.yaw * inv + (E.yaw - 2 * M_PI) * ratio;
+    else yaw = S.yaw * inv + E.yaw * ratio;
+    sr_set_angles(start, S.roll * inv + E.roll * ratio, S.pitch * inv + E.pitch * ratio, yaw);
+    for (int c = 0; c < 3; ++c) {
+      start.vel[c] = S.vel[c] * inv + E.vel[c] * ratio;
+      start.pos[c] = S.pos[c] * inv + E.pos[c] * ratio;
+    }
+    return start;
+  }
+};
 }  // namespace
 
 struct lslam_sreg {
@@ -1405,9 +1475,7 @@ struct lslam_sreg {
   lslam_reg_params prm;
   float lower = 0.f, upper = 0.f, scan_period = 0.1f;
   int32_t n_rings = 0;
-  // _imuHistory (CircularBuffer.h): `size` states from `first` on, the oldest overwritten when full
-  std::vector<SrImu> hist;
-  size_t first = 0, size = 0;
+  SrImuHistory imu;             // _imuHistory
   SrImu start, cur;             // _imuStart, _imuCur
   float shift[3] = {0.f, 0.f, 0.f};  // _imuPositionShift
   uint64_t sweeps = 0;
@@ -1419,7 +1487,6 @@ struct lslam_sreg {
   lslam::PinBuf<uint32_t> h_res;   // what comes back: SR_RES_WORDS, then the ranges
   lslam::PinBuf<uint32_t> done;    // the grouping's {points out, key-range error, -}
   lslam::DevBuf<char> d_in, d_work;
-  const SrImu &at(size_t k) const { return hist[(first + k) % hist.size()]; }
 };
 
 extern "C" {
@@ -1445,7 +1512,7 @@ int lslam_sreg_create(lslam_ctx *ctx, const lslam_reg_params *params, float lowe
   sr->stream = (hipStream_t)lslam_stream(ctx);
   sr->prm = prm;
   sr->lower = lower_deg; sr->upper = upper_deg; sr->n_rings = n_rings; sr->scan_period = scan_period;
-  sr->hist.resize((size_t)imu_history_size);
+  sr->imu.hist.resize((size_t)imu_history_size);
   *out = sr;
   return LSLAM_OK;
 }
@@ -1468,38 +1535,11 @@ int lslam_sreg_imu_push(lslam_sreg *sr, int64_t stamp_ns, double roll, double pi
     lslam::set_error("lslam_sreg_imu_push: no acceleration");
     return LSLAM_ERR_INVALID;
   }
-  if (sr->size && stamp_ns <= sr->at(sr->size - 1).stamp) {
+  if (!sr->imu.later_than_last(stamp_ns)) {
     lslam::set_error("lslam_sreg_imu_push: the stamp is not later than the previous state's");
     return LSLAM_ERR_INVALID;
   }
-  const double *la = linear_acceleration;
-  // handleIMUMessage, ScanRegistration.cpp:96-117
-  float acc[3];
-  acc[0] = float(la[1] - std::sin(roll) * std::cos(pitch) * 9.81);
-  acc[1] = float(la[2] - std::cos(roll) * std::cos(pitch) * 9.81);
-  acc[2] = float(la[0] + std::sin(pitch) * 9.81);
-  SrImu st;
-  st.stamp = stamp_ns;
-  sr_set_angles(st, (float)roll, (float)pitch, (float)yaw);
-  if (sr->size) {
-    sr_rot_h(st.cr, st.sr, acc[0], acc[1]);  // rotateZXY(acc, roll, pitch, yaw)
-    sr_rot_h(st.cp, st.sp, acc[1], acc[2]);
-    sr_rot_h(st.cy, st.sy, acc[2], acc[0]);
-    const SrImu &prev = sr->at(sr->size - 1);
-    const float dt = float(sr_to_sec(stamp_ns - prev.stamp));
-    for (int d = 0; d < 3; ++d) {
-      st.pos[d] = (prev.pos[d] + prev.vel[d] * dt) + ((0.5f * acc[d]) * dt) * dt;
-      st.vel[d] = prev.vel[d] + acc[d] * dt;
-    }
-  }
-  const size_t cap = sr->hist.size();
-  if (sr->size < cap) {
-    sr->hist[(sr->first + sr->size) % cap] = st;
-    sr->size++;
-  } else {
-    sr->hist[sr->first] = st;
-    sr->first = (sr->first + 1) % cap;
-  }
+  sr->imu.push(stamp_ns, roll, pitch, yaw, linear_acceleration);
   return LSLAM_OK;
 }
 
@@ -1513,14 +1553,7 @@ int lslam_sreg_imu_info(const lslam_sreg *sr, int32_t *size, double last_positio
     lslam::set_error("lslam_sreg_imu_info: null node");
     return LSLAM_ERR_INVALID;
   }
-  if (size) *size = (int32_t)sr->size;
-  if (sr->size) {
-    const SrImu &l = sr->at(sr->size - 1);
-    for (int d = 0; d < 3; ++d) {
-      if (last_position) last_position[d] = (double)l.pos[d];
-      if (last_velocity) last_velocity[d] = (double)l.vel[d];
-    }
-  }
+  sr->imu.info(size, last_position, last_velocity);
   return LSLAM_OK;
 }
 
@@ -1529,7 +1562,7 @@ int lslam_sreg_imu_clear(lslam_sreg *sr) {
     lslam::set_error("lslam_sreg_imu_clear: null node");
     return LSLAM_ERR_INVALID;
   }
-  sr->first = sr->size = 0;
+  sr->imu.clear();
   sr->start = SrImu();
   sr->cur = SrImu();
   sr->shift[0] = sr->shift[1] = sr->shift[2] = 0.f;
@@ -1561,7 +1594,7 @@ int lslam_sreg_process(lslam_sreg *sr, const void *cloud, size_t n_points, size_
   SR_TRY(hipSetDevice(sr->device));
   hipStream_t s = sr->stream;
   sr->last_valid = false;
-  const size_t n = n_points, R = (size_t)sr->n_rings, K = sr->size;
+  const size_t n = n_points, R = (size_t)sr->n_rings, K = sr->imu.size;
   const bool imu = K > 0;  // hasIMUData()
   // ---- what goes up, in one block: [SrCtl][result words][ranges][points per ring][IMU states][cloud] --------------------------
   const size_t o_res = sr_up16(sizeof(SrCtl)), o_ranges = o_res + SR_RES_WORDS * 4, o_hist = o_ranges + sr_up16(2 * R * 4),
@@ -1598,34 +1631,15 @@ int lslam_sreg_process(lslam_sreg *sr, const void *cloud, size_t n_points, size_
   if (imu) {
     SrState *hs = reinterpret_cast<SrState *>(hb + o_states);
     for (size_t k = 0; k < K; ++k) {
-      const SrImu &st = sr->at(k);
+      const SrImu &st = sr->imu.at(k);
       SrState &d = hs[k];
       d.tsec = sr_to_sec(scan_time_ns - st.stamp);
-      d.dt_prev = k ? sr_to_sec(st.stamp - sr->at(k - 1).stamp) : 0.0;
+      d.dt_prev = k ? sr_to_sec(st.stamp - sr->imu.at(k - 1).stamp) : 0.0;
       d.roll = st.roll; d.pitch = st.pitch; d.yaw = st.yaw;
       d.sr = st.sr; d.cr = st.cr; d.sp = st.sp; d.cp = st.cp; d.sy = st.sy; d.cy = st.cy;
       for (int c = 0; c < 3; ++c) { d.pos[c] = st.pos[c]; d.vel[c] = st.vel[c]; }
     }
-    size_t idx = 0;
-    double time_diff = hs[0].tsec + 0.0f;
-    while (idx < K - 1 && time_diff > 0) time_diff = hs[++idx].tsec + 0.0f;
-    const SrImu &S = sr->at(idx);
-    if (idx == 0 || time_diff > 0) {
-      start = S;
-    } else {
-      const SrImu &E = sr->at(idx - 1);
-      const float ratio = -time_diff / hs[idx].dt_prev;
-      const float inv = 1 - ratio;
-      float yaw;
-      if (S.yaw - E.yaw > M_PI) yaw = S.yaw * inv + (E.yaw + 2 * M_PI) * ratio;
-      else if (S.yaw - E.yaw < -M_PI) yaw = S.yaw * inv + (E.yaw - 2 * M_PI) * ratio;
-      else yaw = S.yaw * inv + E.yaw * ratio;
-      sr_set_angles(start, S.roll * inv + E.roll * ratio, S.pitch * inv + E.pitch * ratio, yaw);
-      for (int c = 0; c < 3; ++c) {
-        start.vel[c] = S.vel[c] * inv + E.vel[c] * ratio;
-        start.pos[c] = S.pos[c] * inv + E.pos[c] * ratio;
-      }
-    }
+    start = sr->imu.start_for(scan_time_ns);
     dstart.roll = start.roll; dstart.pitch = start.pitch; dstart.yaw = start.yaw;
     dstart.sr = start.sr; dstart.cr = start.cr; dstart.sp = start.sp; dstart.cp = start.cp; dstart.sy = start.sy; dstart.cy = start.cy;
     for (int c = 0; c < 3; ++c) { dstart.pos[c] = start.pos[c]; dstart.vel[c] = start.vel[c]; }
@@ -1764,6 +1778,375 @@ int lslam_sreg_cloud(lslam_sreg *sr, float *out_xyzc, size_t cap, size_t *n_out,
   SR_TRY(hipSetDevice(sr->device));
   SR_TRY(hipMemcpyAsync(out_xyzc, sr->d_sorted, sr->last_m * sizeof(float4), hipMemcpyDeviceToHost, sr->stream));
   SR_TRY(hipStreamSynchronize(sr->stream));
+  return LSLAM_OK;
+}
+
+}  // extern "C"
+
+// ---- the registration node for organised clouds (include/lslam_c.h lslam_oreg_*) ---------------------------------------------
+// OrganisedScanRegistration::process (odometry/OrganizedScanRegistration.cpp:82-150): the rows of the height x width image are
+// visited in order and the columns in order, so "the per-row clouds concatenated" is a stable compaction of the row-major image:
+// no grouping sort, no atan.  Per sweep: or_count_kernel (kept cells per tile of OR_TILE, kept cells per row), or_place_kernel
+// (every workgroup sums the tiles before its own and writes {x, y, z, ring + relTime} where the extraction reads its cloud),
+// sr_ranges_kernel with n_rings = height, then the extraction's three launches: six kernels.  The memsets of the extraction
+// (its helpers' flags, when they are on) are not in that count.
+namespace {
+constexpr int OR_BLOCK = 256;
+constexpr int OR_TILE = 1024;  // cells per workgroup, OR_TILE / OR_BLOCK rounds of one cell per thread
+constexpr int OR_RES_WORDS = SR_RES_WORDS;  // the result words sr_ranges_kernel and the extraction write; the ranges follow them
+struct OrArgs {
+  const float4 *cells;  // row-major {x, y, z, word}: the ring in the low 16 bits of word
+  const float *rel;     // [width] relTime of every column, made on the host
+  int n, width;         // n = height * width
+  float blind2;         // _blindRaduis * _blindRaduis
+  int32_t *tile_count;  // [tiles] kept cells per tile
+  int32_t *hist;        // [height] kept cells per row (zeroed by the upload)
+  float4 *out;          // FxWork::pts
+};
+// :114-123: finite coordinates, then x*x + y*y + z*z < blind^2 drops the point (float, left to right, nothing contracted)
+__device__ __forceinline__ bool or_kept(const float4 &c, float blind2) {
+  const uint32_t e = 0x7f800000u;
+  if ((__float_as_uint(c.x) & e) == e || (__float_as_uint(c.y) & e) == e || (__float_as_uint(c.z) & e) == e) return false;
+  const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(c.x, c.x), __fmul_rn(c.y, c.y)), __fmul_rn(c.z, c.z));
+  return !(d2 < blind2);
+}
+
+// Pass 1: kept cells per tile (ballot + popcount, the wavefronts' counts through LDS) and per row.  A tile touches at most
+// OR_TILE rows (width 1); their counters sit in LDS and reach the global table with integer atomics, so the result does not
+// depend on the order the atomics ran in.  A wavefront whose 64 cells lie in one row adds its popcount once.
+__global__ __launch_bounds__(OR_BLOCK) void or_count_kernel(OrArgs a) {
+  __shared__ int32_t h[OR_TILE];
+  __shared__ int part[OR_BLOCK / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int base = blockIdx.x * OR_TILE, end = min(a.n, base + OR_TILE);
+  const int row0 = base / a.width, rows = (end - 1) / a.width - row0 + 1;
+  for (int r = tid; r < rows; r += OR_BLOCK) h[r] = 0;
+  __syncthreads();
+  int c = 0;
+#pragma unroll
+  for (int r = 0; r < OR_TILE / OR_BLOCK; ++r) {
+    const int i = base + r * OR_BLOCK + tid;
+    const bool in = i < end;
+    const bool kept = in && or_kept(a.cells[i], a.blind2);
+    const unsigned long long m = __ballot(kept);
+    const int row = in ? i / a.width - row0 : -1;
+    const int r_first = __shfl(row, 0, 64), r_last = __shfl(row, 63, 64);
+    if (r_first == r_last) {  // (a ragged wavefront has row -1 in lane 63: the other branch)
+      if (lane == 0 && m) atomicAdd(&h[r_first], __popcll(m));
+    } else if (kept) {
+      atomicAdd(&h[row], 1);
+    }
+    c += __popcll(m);
+  }
+  if (lane == 0) part[wave] = c;
+  __syncthreads();
+  if (tid == 0) {
+    int t = 0;
+#pragma unroll
+    for (int w = 0; w < OR_BLOCK / 64; ++w) t += part[w];
+    a.tile_count[blockIdx.x] = t;
+  }
+  for (int r = tid; r < rows; r += OR_BLOCK)
+    if (h[r]) atomicAdd(&a.hist[row0 + r], h[r]);
+}
+
+// Pass 2: the tiles before this one summed by the workgroup itself (a few hundred words: no scan launch between the passes),
+// then every kept cell placed in order -- ballot prefix inside a wavefront, the wavefronts' counts through LDS.  Validity is
+// computed again, not stored; the point goes straight into the extraction's input array.
+__global__ __launch_bounds__(OR_BLOCK) void or_place_kernel(OrArgs a) {
+  __shared__ int part[OR_BLOCK / 64];
+  __shared__ int wave_n[OR_BLOCK / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int before = 0;
+  for (int b = tid; b < (int)blockIdx.x; b += OR_BLOCK) before += a.tile_count[b];
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) before += __shfl_xor(before, d, 64);
+  if (lane == 0) part[wave] = before;
+  __syncthreads();
+  int offset = 0;
+#pragma unroll
+  for (int w = 0; w < OR_BLOCK / 64; ++w) offset += part[w];
+  const int base = blockIdx.x * OR_TILE, end = min(a.n, base + OR_TILE);
+  for (int r = 0; r < OR_TILE / OR_BLOCK; ++r) {
+    const int i = base + r * OR_BLOCK + tid;
+    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < end) c = a.cells[i];
+    const bool kept = i < end && or_kept(c, a.blind2);
+    const unsigned long long m = __ballot(kept);
+    __syncthreads();  // (wave_n of the previous round has been read)
+    if (lane == 0) wave_n[wave] = __popcll(m);
+    __syncthreads();
+    int w_before = 0, round_total = 0;
+#pragma unroll
+    for (int w = 0; w < OR_BLOCK / 64; ++w) {
+      if (w < wave) w_before += wave_n[w];
+      round_total += wave_n[w];
+    }
+    if (kept) {
+      const int dst = offset + w_before + __popcll(m & ((1ull << lane) - 1ull));
+      const int col = i % a.width;
+      const uint32_t ring = __float_as_uint(c.w) & 0xFFFFu;  // p.ring, a uint16: int -> float, one float add (:112)
+      if (dst < a.n) a.out[dst] = make_float4(c.x, c.y, c.z, __fadd_rn((float)ring, a.rel[col]));
+    }
+    offset += round_total;
+  }
+}
+}  // namespace
+
+struct lslam_oreg {
+  lslam_ctx *ctx = nullptr;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  lslam_reg_params prm;
+  float scan_period = 0.1f, blind_radius = 2.5f;
+  SrImuHistory imu;             // _imuHistory; _imuCur and _imuPositionShift stay as constructed (process never sets them)
+  SrImu start;                  // _imuStart
+  uint64_t sweeps = 0;
+  std::vector<float> rel;       // relTime of every column, for the width it was made for
+  // the last sweep's registered cloud, for lslam_oreg_cloud
+  size_t last_m = 0, last_h = 0;
+  bool last_valid = false;
+  float4 *d_sorted = nullptr;
+  lslam::PinBuf<char> h_in;       // what a sweep uploads in one copy: result words, ranges, row counters, column times, cells
+  lslam::PinBuf<uint32_t> h_res;  // what comes back: OR_RES_WORDS, then the ranges
+  lslam::DevBuf<char> d_in, d_work;
+};
+
+extern "C" {
+
+int lslam_oreg_create(lslam_ctx *ctx, const lslam_reg_params *params, float scan_period, float blind_radius, int32_t imu_history_size,
+                      lslam_oreg **out) {
+  if (out) *out = nullptr;
+  if (!ctx || !lslam::ctx_alive(ctx)) {
+    lslam::set_error("lslam_oreg_create: null context, or it was destroyed");
+    return LSLAM_ERR_INVALID;
+  }
+  lslam_reg_params prm;
+  if (params) prm = *params; else lslam_reg_default_params(&prm);
+  if (!out || !(scan_period > 0.f) || !std::isfinite(scan_period) || !(blind_radius >= 0.f) || !std::isfinite(blind_radius) ||
+      imu_history_size < 1 || imu_history_size > SR_MAX_HIST || prm.curvature_region < 1 || prm.curvature_region > 16 ||
+      prm.n_feature_regions < 1 || prm.n_feature_regions > 512 || !(prm.less_flat_filter_size > 0.f)) {
+    lslam::set_error("lslam_oreg_create: bad registration arguments (scan period > 0, finite blind radius >= 0, IMU history 1..512)");
+    return LSLAM_ERR_INVALID;
+  }
+  lslam_oreg *og = new lslam_oreg();
+  og->ctx = ctx;
+  og->device = lslam::ctx_device(ctx);
+  og->stream = (hipStream_t)lslam_stream(ctx);
+  og->prm = prm;
+  og->scan_period = scan_period;
+  og->blind_radius = blind_radius;
+  og->imu.hist.resize((size_t)imu_history_size);
+  *out = og;
+  return LSLAM_OK;
+}
+
+void lslam_oreg_destroy(lslam_oreg *og) {
+  if (!og) return;
+  if (lslam::ctx_alive(og->ctx)) {  // a node may outlive its context; the stream is then gone (and was waited for)
+    (void)hipSetDevice(og->device);
+    (void)hipStreamSynchronize(og->stream);
+  }
+  delete og;
+}
+
+int lslam_oreg_imu_push(lslam_oreg *og, int64_t stamp_ns, double roll, double pitch, double yaw, const double linear_acceleration[3]) {
+  if (!og) {
+    lslam::set_error("lslam_oreg_imu_push: null node");
+    return LSLAM_ERR_INVALID;
+  }
+  if (!linear_acceleration) {
+    lslam::set_error("lslam_oreg_imu_push: no acceleration");
+    return LSLAM_ERR_INVALID;
+  }
+  if (!og->imu.later_than_last(stamp_ns)) {
+    lslam::set_error("lslam_oreg_imu_push: the stamp is not later than the previous state's");
+    return LSLAM_ERR_INVALID;
+  }
+  og->imu.push(stamp_ns, roll, pitch, yaw, linear_acceleration);
+  return LSLAM_OK;
+}
+
+int lslam_oreg_imu_info(const lslam_oreg *og, int32_t *size, double last_position[3], double last_velocity[3]) {
+  if (size) *size = 0;
+  for (int d = 0; d < 3; ++d) {
+    if (last_position) last_position[d] = 0.0;
+    if (last_velocity) last_velocity[d] = 0.0;
+  }
+  if (!og) {
+    lslam::set_error("lslam_oreg_imu_info: null node");
+    return LSLAM_ERR_INVALID;
+  }
+  og->imu.info(size, last_position, last_velocity);
+  return LSLAM_OK;
+}
+
+int lslam_oreg_imu_clear(lslam_oreg *og) {
+  if (!og) {
+    lslam::set_error("lslam_oreg_imu_clear: null node");
+    return LSLAM_ERR_INVALID;
+  }
+  og->imu.clear();
+  og->start = SrImu();
+  return LSLAM_OK;
+}
+
+int lslam_oreg_process(lslam_oreg *og, const void *cloud, size_t height, size_t width, size_t stride_bytes, size_t ring_offset_bytes,
+                       int64_t scan_time_ns, lslam_fset *out, size_t counts[4], float imu_trans[12], lslam_oreg_stats *stats) {
+  if (counts) for (int k = 0; k < 4; ++k) counts[k] = 0;
+  if (imu_trans) for (int k = 0; k < 12; ++k) imu_trans[k] = 0.f;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!og) {
+    lslam::set_error("lslam_oreg_process: null node");
+    return LSLAM_ERR_INVALID;
+  }
+  if (!lslam::ctx_alive(og->ctx)) {
+    lslam::set_error("lslam_oreg_process: the node's context was destroyed");
+    return LSLAM_ERR_INVALID;
+  }
+  if (!out || out->device != og->device) {
+    lslam::set_error("lslam_oreg_process: no feature set, or it lives on another device");
+    return LSLAM_ERR_INVALID;
+  }
+  for (int k = 0; k < 4; ++k) out->counts[k] = 0;
+  if (!cloud) {
+    lslam::set_error("lslam_oreg_process: null cloud");
+    return LSLAM_ERR_INVALID;
+  }
+  if (height == 0 || width == 0 || height > 4096 || width > (size_t)0x3FFFFFFFu / height) {
+    lslam::set_error("lslam_oreg_process: bad image size (height 1..4096, width >= 1, height * width <= 0x3FFFFFFF)");
+    return LSLAM_ERR_INVALID;
+  }
+  if (stride_bytes < 12 || (stride_bytes & 3) || ring_offset_bytes > stride_bytes || ring_offset_bytes + 2 > stride_bytes) {
+    lslam::set_error("lslam_oreg_process: bad stride or ring offset");
+    return LSLAM_ERR_INVALID;
+  }
+  SR_TRY(hipSetDevice(og->device));
+  hipStream_t s = og->stream;
+  const size_t H = height, W = width, n = H * W, K = og->imu.size;
+  const size_t tiles = (n + OR_TILE - 1) / OR_TILE;
+  og->last_valid = false;  // from here on the node's buffers may move and its scratch is written
+  // ---- what goes up, in one block: [result words][ranges][kept cells per row][relTime per column][cells] -----------------------
+  const size_t o_ranges = OR_RES_WORDS * 4, o_hist = o_ranges + sr_up16(2 * H * 4), o_rel = o_hist + sr_up16(H * 4),
+               o_cloud = o_rel + sr_up16(W * 4), in_bytes = o_cloud + n * sizeof(float4);
+  SR_TRY(og->h_in.reserve(in_bytes));
+  SR_TRY(og->d_in.reserve(in_bytes));
+  SR_TRY(og->h_res.reserve(OR_RES_WORDS + 2 * H));
+  SR_TRY(og->d_work.reserve(sr_up16(tiles * 4) + fx_work_bytes(n, H)));
+  SR_TRY(lslam::fset_reserve(out, n));
+  char *hb = og->h_in.p;
+  std::memset(hb, 0, o_rel);
+  if (og->rel.size() != W) {  // float relTime = scanPeriod * static_cast<double>(col) / width (:111), rounded once
+    og->rel.resize(W);
+    for (size_t c = 0; c < W; ++c) og->rel[c] = (float)(((double)og->scan_period * (double)c) / (double)W);
+  }
+  std::memcpy(hb + o_rel, og->rel.data(), W * 4);
+  char *h = hb + o_cloud;
+  const char *src = static_cast<const char *>(cloud);
+  if (stride_bytes == 16 && ring_offset_bytes == 12) {
+    std::memcpy(h, src, n * 16);  // (the upper half of the fourth word is never read)
+  } else {
+    for (size_t i = 0; i < n; ++i) {
+      uint16_t ring;
+      std::memcpy(&ring, src + i * stride_bytes + ring_offset_bytes, 2);
+      const uint32_t word = ring;
+      std::memcpy(h + i * 16, src + i * stride_bytes, 12);
+      std::memcpy(h + i * 16 + 12, &word, 4);
+    }
+  }
+  // ---- reset(scanTime): interpolateIMUStateFor(0, _imuStart), on the host; nothing of it reaches the device ------------------
+  const bool imu = K > 0;
+  SrImu start = og->start;
+  if (imu) start = og->imu.start_for(scan_time_ns);
+  // ---- device arrays -----------------------------------------------------------------------------------------------------
+  char *db = og->d_in.p, *wb = og->d_work.p;
+  FxWork w;
+  fx_carve(wb + sr_up16(tiles * 4), n, H, w);
+  uint32_t *d_res = (uint32_t *)db;
+  int32_t *d_ranges_out = (int32_t *)(db + o_ranges);
+  SR_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, s));
+  OrArgs a{};
+  a.cells = (const float4 *)(db + o_cloud);
+  a.rel = (const float *)(db + o_rel);
+  a.n = (int)n;
+  a.width = (int)W;
+  a.blind2 = og->blind_radius * og->blind_radius;
+  a.tile_count = (int32_t *)wb;
+  a.hist = (int32_t *)(db + o_hist);
+  a.out = w.pts;
+  hipLaunchKernelGGL(or_count_kernel, dim3((unsigned)tiles), dim3(OR_BLOCK), 0, s, a);
+  hipLaunchKernelGGL(or_place_kernel, dim3((unsigned)tiles), dim3(OR_BLOCK), 0, s, a);
+  hipLaunchKernelGGL(sr_ranges_kernel, dim3(1), dim3(FX_BLOCK), 0, s, a.hist, (int)H, d_ranges_out, w.ranges, d_res);
+  hipError_t e = fx_enqueue(s, og->prm, w, n, H, false, false, false, out->buf.p, d_res, out->cap);
+  if (e == hipSuccess) e = hipMemcpyAsync(og->h_res.p, d_res, (OR_RES_WORDS + 2 * H) * 4, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);  // the node's one wait
+  if (e != hipSuccess || e2 != hipSuccess) {
+    lslam::set_error(hipGetErrorString(e != hipSuccess ? e : e2));
+    return LSLAM_ERR_HIP;
+  }
+  const uint32_t *res = og->h_res.p;
+  if (res[4]) {
+    lslam::set_error(res[4] == 3u ? "lslam_oreg_process: a row keeps more points than the extraction holds in LDS (2560)"
+                     : res[4] == 1u ? "lslam_oreg_process: voxel index outside its range"
+                                    : "lslam_oreg_process: a feature list overflowed its staging slice");
+    return LSLAM_ERR_INVALID;
+  }
+  const size_t m = (size_t)res[28];
+  for (int k = 0; k < 4; ++k) {
+    out->counts[k] = (size_t)res[k];
+    if (counts) counts[k] = (size_t)res[k];
+  }
+  og->last_m = m;
+  og->last_h = H;
+  og->last_valid = true;
+  og->d_sorted = w.pts;
+  og->sweeps++;
+  og->start = start;
+  if (imu_trans && imu) {  // publishResult, ScanRegistration.cpp:684-707, with _imuCur and _imuPositionShift as constructed
+    imu_trans[0] = start.pitch; imu_trans[1] = start.yaw; imu_trans[2] = start.roll;
+    float v[3] = {0.f, 0.f, 0.f};
+    sr_rotate_yxz_neg(start, v);
+    for (int d = 0; d < 3; ++d) imu_trans[6 + d] = v[d];
+    for (int d = 0; d < 3; ++d) v[d] = 0.f - start.vel[d];
+    sr_rotate_yxz_neg(start, v);
+    for (int d = 0; d < 3; ++d) imu_trans[9 + d] = v[d];
+  }
+  if (stats) {
+    stats->sweeps = og->sweeps;
+    stats->n_cells = n;
+    stats->n_points = m;
+    stats->imu_states = (int32_t)K;
+    stats->launches = 6;
+    stats->bytes_up = in_bytes;
+    stats->bytes_down = (OR_RES_WORDS + 2 * H) * 4;
+  }
+  return LSLAM_OK;
+}
+
+int lslam_oreg_cloud(lslam_oreg *og, float *out_xyzc, size_t cap, size_t *n_out, int32_t *ranges_out) {
+  if (n_out) *n_out = 0;
+  if (!og) {
+    lslam::set_error("lslam_oreg_cloud: null node");
+    return LSLAM_ERR_INVALID;
+  }
+  if (!n_out || !lslam::ctx_alive(og->ctx)) {
+    lslam::set_error("lslam_oreg_cloud: no place for the size, or the node's context was destroyed");
+    return LSLAM_ERR_INVALID;
+  }
+  if (!og->last_valid) {
+    lslam::set_error("lslam_oreg_cloud: no sweep has been registered (or the last one was refused on the device)");
+    return LSLAM_ERR_INVALID;
+  }
+  *n_out = og->last_m;
+  if (ranges_out) std::memcpy(ranges_out, og->h_res.p + OR_RES_WORDS, 2 * og->last_h * 4);
+  if (!out_xyzc || og->last_m == 0) return LSLAM_OK;
+  if (cap < og->last_m) {
+    lslam::set_error("lslam_oreg_cloud: output buffer too small");
+    return LSLAM_ERR_INVALID;
+  }
+  SR_TRY(hipSetDevice(og->device));
+  SR_TRY(hipMemcpyAsync(out_xyzc, og->d_sorted, og->last_m * sizeof(float4), hipMemcpyDeviceToHost, og->stream));
+  SR_TRY(hipStreamSynchronize(og->stream));
   return LSLAM_OK;
 }
 
