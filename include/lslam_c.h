@@ -1114,6 +1114,76 @@ int lslam_loc_search_stats(lslam_loc *loc, lslam_loc_search_counts *out);
 int lslam_loc_debug_knn5(lslam_loc *loc, int32_t which, const void *queries, size_t nq, size_t stride_bytes, float *xyz_out,
                          float *d2_out, uint8_t *how_out);
 
+/* ---- the paged mode of the localisation node (util/DynamicFeatureMap.h, the dynamicMode branch of LaserMatcher) --------------
+ * A second mode of lslam_loc, entered with lslam_pmap_open in place of lslam_loc_load / _set_map*: the cube_width x
+ * cube_height x cube_depth cubes of lslam_loc_create are a WINDOW addressed by GLOBAL cube index round(p / cube_size) that
+ * follows the sensor.  update(sensor position) loads exactly the listed cubes that enter the window (index2.txt plus
+ * <count>.pcd, each through its type's VoxelGrid with the map leaf, a kd-tree when at least five points remain); the cubes
+ * that stay are not touched, the ones that left give their room back.  The match is the static mode's (same kernels, same
+ * arithmetic) with the cube of a query looked up relative to the window centre.  The static mode is unchanged.  The entry
+ * points of the window carry the prefix lslam_pmap_ and take the node's handle; lslam_loc_process / _process_device / _match /
+ * _get_surround / _debug_knn5 / _info work in either mode (match updates the window at the Twist's translation first, the tap
+ * searches the window as it stands, get_surround updates at the node's pose).
+ *
+ * A step on the device: the entering files' points in one upload with their segment numbers, one VoxelGrid run per feature type
+ * over all entering cubes (lslam::voxel_filter_segments), their bounds and their placement into arena extents (pm_bounds_kernel,
+ * pm_place_kernel), one forest build over the entering cubes only, the window tables rewritten from pinned memory.  Work and
+ * bytes follow the entering cubes, not the window.  A step that is refused (capacity, LSLAM_ERR_TREE_DEPTH, a HIP error) has
+ * changed nothing live: the node answers the next call as it did before.
+ *
+ * Differences from the reference, on purpose:
+ *   - a query whose cube lies outside the window is skipped (the reference indexes _indexMap out of range);
+ *   - an even window dimension and ceil(valid distance / cube size) > min(W, H, D) / 2 are refused (same reason);
+ *   - the edge refusal of the static mode does not exist here;
+ *   - lslam_index_convert writes every input line once (the reference's eof() loop repeats the last one);
+ *   - addFeatureCloud / downsizeValidCloud / saveCloudToFiles / getFullMap are not built (DESIGN 8c says why). */
+typedef struct {
+  int32_t paged;                /* 1 once lslam_pmap_open succeeded */
+  int32_t have_window;          /* 1 after the first update */
+  int32_t centre[3];            /* sensorGloIdx of the last update */
+  int32_t dims[3];
+  int64_t steps;                /* updates that changed the window (the first included) */
+  int64_t refused_steps;
+  int64_t resident[2];          /* listed cubes in the window, per type (corner, surf) */
+  int64_t resident_with_tree[2];
+  int64_t staged[2];            /* cubes held in spare room by lslam_pmap_stage, not part of the window */
+  int64_t entered[2], left[2], adopted[2];   /* of the last step; adopted: entered from the staged set instead of from disk */
+  int64_t entered_total[2], left_total[2], adopted_total[2], staged_dropped_total[2];
+  int64_t files_read, files_read_total;      /* PCDs read by the last step / since open (lslam_pmap_stage's reads included in the total) */
+  int64_t files_missing, files_missing_total;/* listed but missing or unreadable: the cube stays empty */
+  int64_t trees_built, trees_built_total;    /* kd-trees built by the last step / since open; a surviving cube's tree is never rebuilt */
+  int64_t forest_builds_total;
+  uint64_t bytes_uploaded, bytes_uploaded_total;  /* by the last step / by all steps and stagings */
+  int32_t step_kernels;         /* of the last step: launches of its own kernels (bounds, placement) */
+  int32_t step_filter_runs;     /* ... VoxelGrid runs (each a fixed number of launches) */
+  int32_t step_forest_builds;   /* ... forest builds (1; more only when the node pool had to grow) */
+  int32_t step_host_waits;      /* ... host waits */
+  uint64_t arena_points_used, arena_points_capacity;  /* filtered points held (resident and staged) / room of the arena */
+  uint64_t arena_nodes_used, arena_nodes_capacity;
+  uint64_t active_cubes;        /* computeActiveAera of the last update */
+} lslam_loc_window_stats;
+/* setupFilesDirectory: reads directory/index2.txt (lines "count type i j k size"; type 0 corner, anything else surf; (i, j, k)
+ * the signed global cube index; a later line for the same (type, cube) replaces the earlier one).  Nothing is read from the
+ * PCDs until the first update.  Uses the cube size, valid distance and map filter sizes set before it.  A missing index2.txt:
+ * LSLAM_ERR_INVALID, the node as it was. */
+int lslam_pmap_open(lslam_loc *loc, const char *directory);
+/* Upper bound of the filtered points the node keeps per feature type (resident and staged together; 0: no bound, the arena
+ * grows).  A step that would need more is refused with LSLAM_ERR_INVALID after the staged cubes were dropped. */
+int lslam_pmap_setup_capacity(lslam_loc *loc, size_t max_points_per_type);
+/* DynamicFeatureMap::update: the window follows pos (a step if its cube changed), then computeActiveAera. */
+int lslam_pmap_update(lslam_loc *loc, const float pos[3]);
+/* Reads, filters and builds the cubes a window centred on pos's cube would need and the node does not hold, into spare room;
+ * no table changes.  A later step adopts a staged cube instead of reading it; results do not depend on staging.  Called by
+ * the host between sweeps with its predicted position; there is no library thread. */
+int lslam_pmap_stage(lslam_loc *loc, const float pos[3]);
+/* getSurroundFeature of the window as the last update left it (lslam_loc_get_surround updates at the node's pose first). */
+int lslam_pmap_get_surround(lslam_loc *loc, float *corner_xyzi, size_t cap_corner, size_t *n_corner, float *surf_xyzi,
+                                  size_t cap_surf, size_t *n_surf);
+int lslam_pmap_window_info(lslam_loc *loc, lslam_loc_window_stats *out);
+/* convertIndexFile: every line "count type i j k size" of in_path (an index.txt of lslam_fmap_save) written to out_path with
+ * i - ox, j - oy, k - oz, so that a map saved by the mapping node can be opened paged.  No device is needed. */
+int lslam_index_convert(const char *in_path, int32_t ox, int32_t oy, int32_t oz, const char *out_path);
+
 #ifdef __cplusplus
 }
 #endif

@@ -554,7 +554,7 @@ class LaserLocalization {
 public:
   explicit LaserLocalization(lslam_ctx *ctx, int cubeX = 121, int cubeY = 121, int cubeZ = 11, float filterCorner = 1.0f,
                              float filterSurf = 1.0f, float mapFilterCorner = 1.0f, float mapFilterSurf = 1.0f)
-      : _loc(nullptr), _flags(0), _hasVelocity(false) {
+      : _loc(nullptr), _flags(0), _hasVelocity(false), _dynamic(false) {
     detail::identity4(_lidarMappedNew);
     std::memset(_velocity, 0, sizeof(_velocity));
     std::memset(&_last, 0, sizeof(_last));
@@ -581,6 +581,23 @@ public:
   bool loadMap(const std::string &directory) { return check(lslam_loc_load(_loc, directory.c_str())); }
   // ... or the map a mapping node of the same context has just built
   bool adoptMap(lslam_fmap *fm) { return check(lslam_loc_set_map_from_fmap(_loc, fm)); }
+  // LaserMatcher's dynamicMode branch (LaserMatcher.cpp:100-104): the cubes become a window over the files of a directory
+  // (index2.txt plus <count>.pcd) that follows the sensor; setupFilesDirectory reads the index and enters the mode
+  bool setDynamicMode(bool on) {
+    _dynamic = on;
+    return true;
+  }
+  bool setupFilesDirectory(const std::string &directory) {
+    if (!_dynamic) {
+      _err = "setupFilesDirectory: the dynamic mode is off (setDynamicMode)";
+      return false;
+    }
+    return check(lslam_pmap_open(_loc, directory.c_str()));
+  }
+  bool setupPagedCapacity(size_t maxPointsPerType) { return check(lslam_pmap_setup_capacity(_loc, maxPointsPerType)); }
+  // between sweeps, with the host's predicted position: the cubes the next window would need are read ahead
+  bool stage(const float pos[3]) { return check(lslam_pmap_stage(_loc, pos)); }
+  bool windowInfo(lslam_loc_window_stats *out) { return check(lslam_pmap_window_info(_loc, out)); }
   bool handleInitialPose(const float T[16]) { return check(lslam_loc_set_initial_pose(_loc, T)); }
   // cornerLast / surfLast: packed {x, y, z, intensity}; lidarOdomNew: the odometry node's _Tsum.  false: a backend error, or the
   // sweep was dropped (dropped() says which); the match's own outcome (lastStats().status) never makes it false, as the
@@ -622,7 +639,7 @@ private:
   lslam_loc *_loc;
   float _lidarMappedNew[16], _velocity[3];
   int32_t _flags;
-  bool _hasVelocity;
+  bool _hasVelocity, _dynamic;
   lslam_stats _last;
   std::string _err;
 };

@@ -155,6 +155,21 @@ class LslamLocSearchCounts(C.Structure):
                 ("bytes_up", C.c_uint64 * 2), ("bytes_down", C.c_uint64 * 2)]
 
 
+class LslamLocWindowStats(C.Structure):
+    """lslam_loc_window_stats (include/lslam_c.h): the paged window of the localisation node."""
+    _fields_ = [("paged", C.c_int32), ("have_window", C.c_int32), ("centre", C.c_int32 * 3), ("dims", C.c_int32 * 3),
+                ("steps", C.c_int64), ("refused_steps", C.c_int64), ("resident", C.c_int64 * 2),
+                ("resident_with_tree", C.c_int64 * 2), ("staged", C.c_int64 * 2), ("entered", C.c_int64 * 2),
+                ("left", C.c_int64 * 2), ("adopted", C.c_int64 * 2), ("entered_total", C.c_int64 * 2),
+                ("left_total", C.c_int64 * 2), ("adopted_total", C.c_int64 * 2), ("staged_dropped_total", C.c_int64 * 2),
+                ("files_read", C.c_int64), ("files_read_total", C.c_int64), ("files_missing", C.c_int64),
+                ("files_missing_total", C.c_int64), ("trees_built", C.c_int64), ("trees_built_total", C.c_int64),
+                ("forest_builds_total", C.c_int64), ("bytes_uploaded", C.c_uint64), ("bytes_uploaded_total", C.c_uint64),
+                ("step_kernels", C.c_int32), ("step_filter_runs", C.c_int32), ("step_forest_builds", C.c_int32),
+                ("step_host_waits", C.c_int32), ("arena_points_used", C.c_uint64), ("arena_points_capacity", C.c_uint64),
+                ("arena_nodes_used", C.c_uint64), ("arena_nodes_capacity", C.c_uint64), ("active_cubes", C.c_uint64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLGATHERV_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32)
 c_double_p = C.POINTER(C.c_double)
@@ -339,6 +354,14 @@ SYMBOLS = {
                                          C.POINTER(C.c_size_t)]),
     "lslam_loc_search_stats": (C.c_int, [C.c_void_p, C.POINTER(LslamLocSearchCounts)]),
     "lslam_loc_debug_knn5": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, c_float_p, c_uint8_p]),
+    "lslam_pmap_open": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "lslam_pmap_setup_capacity": (C.c_int, [C.c_void_p, C.c_size_t]),
+    "lslam_pmap_update": (C.c_int, [C.c_void_p, c_float_p]),
+    "lslam_pmap_stage": (C.c_int, [C.c_void_p, c_float_p]),
+    "lslam_pmap_get_surround": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, C.POINTER(C.c_size_t), c_float_p, C.c_size_t,
+                                                C.POINTER(C.c_size_t)]),
+    "lslam_pmap_window_info": (C.c_int, [C.c_void_p, C.POINTER(LslamLocWindowStats)]),
+    "lslam_index_convert": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p]),
     "lslam_pg_save_g2o": (C.c_int, [C.c_void_p, C.c_char_p]),
     "lslam_g2o_read": (C.c_int, [C.c_char_p, c_int32_p, c_double_p, c_int32_p, c_int32_p, c_double_p, c_double_p,
                                  c_int32_p]),

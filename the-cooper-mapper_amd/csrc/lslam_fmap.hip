@@ -2156,4 +2156,7 @@ int fmap_view(lslam_fmap *fm, FmapView *out) {
   return LSLAM_OK;
 }
 
+// the PCD reader of lslam_fmap_load for the paged window of lslam_loc.hip, which reads single cube files
+bool fmap_read_pcd(const char *path, std::vector<float4> &out, std::string &err) { return read_pcd(std::string(path), out, err); }
+
 }  // namespace lslam

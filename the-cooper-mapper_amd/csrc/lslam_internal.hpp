@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 #include "lslam_buf.hpp"
@@ -506,6 +507,7 @@ int fmap_set_clouds(lslam_fmap *fm, const void *corner, size_t n_corner, const v
 int fmap_clear(lslam_fmap *fm);
 int fmap_copy(lslam_fmap *dst, lslam_fmap *src);
 int fmap_view(lslam_fmap *fm, FmapView *out);
+bool fmap_read_pcd(const char *path, std::vector<float4> &out, std::string &err);  // x y z intensity of an ascii or binary PCD
 
 // lslam_fmap.hip: pcl::VoxelGrid of a window whose owner keeps its points in voxel-key order (see there)
 struct WindowFilter;  // the filter's scratch, owned by the caller

@@ -18,9 +18,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <fstream>
+#include <map>
+#include <string>
 #include <vector>
 
 #include "lslam_internal.hpp"
@@ -282,6 +286,114 @@ __global__ void loc_gather_kernel(const float4 *pts, const int32_t *src_begin, c
   out[i] = p;
 }
 
+// ---- the paged window (util/DynamicFeatureMap.h) ----------------------------------------------------------------------------
+// [first, end) of every segment in a VoxelGrid run's output, which is grouped by segment: bounds[2 s], bounds[2 s + 1]; a segment
+// that left nothing keeps the zeros it was given.  done[0] (pinned) is the output's length, known to the device before the host;
+// n_in bounds it.
+__global__ __launch_bounds__(256) void pm_bounds_kernel(const int32_t *seg, const uint32_t *done, int n_in, int nseg, int32_t *bounds) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int m = min((int)done[0], n_in);
+  if (i >= m) return;
+  const int sg = seg[i];
+  if (sg < 0 || sg >= nseg) return;
+  if (i == 0 || seg[i - 1] != sg) bounds[2 * sg] = i;
+  if (i == m - 1 || seg[i + 1] != sg) bounds[2 * sg + 1] = i + 1;
+}
+
+// Every filtered point of the entering cubes to its cube's extent, in both arenas: fpts keeps the filter's order
+// (getSurroundFeature hands the clouds out as the filter left them), tpts is what the forest build permutes.  dst[s] < 0: the
+// segment's cube got no room (nothing is written for it).
+__global__ __launch_bounds__(256) void pm_place_kernel(const float4 *src, const int32_t *seg, const uint32_t *done, int n_in, int nseg,
+                                                      const int32_t *bounds, const int32_t *dst, float4 *fpts, float4 *tpts) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int m = min((int)done[0], n_in);
+  if (i >= m) return;
+  const int sg = seg[i];
+  if (sg < 0 || sg >= nseg) return;
+  const int base = dst[sg];
+  if (base < 0) return;
+  const int at = base + (i - bounds[2 * sg]);
+  const float4 v = src[i];
+  fpts[at] = v;
+  tpts[at] = v;
+}
+
+typedef std::array<int, 3> CubeKey;  // a global cube index (i, j, k)
+
+struct PmExtent {
+  int64_t off, len;
+};
+// first fit; the free list is kept in ascending order with neighbours merged
+bool ext_alloc(std::vector<PmExtent> &fl, int64_t len, int64_t *off) {
+  for (size_t k = 0; k < fl.size(); ++k)
+    if (fl[k].len >= len) {
+      *off = fl[k].off;
+      fl[k].off += len;
+      fl[k].len -= len;
+      if (!fl[k].len) fl.erase(fl.begin() + (long)k);
+      return true;
+    }
+  return false;
+}
+void ext_free(std::vector<PmExtent> &fl, int64_t off, int64_t len) {
+  if (len <= 0) return;
+  size_t k = 0;
+  while (k < fl.size() && fl[k].off < off) ++k;
+  fl.insert(fl.begin() + (long)k, PmExtent{off, len});
+  if (k + 1 < fl.size() && fl[k].off + fl[k].len == fl[k + 1].off) {
+    fl[k].len += fl[k + 1].len;
+    fl.erase(fl.begin() + (long)k + 1);
+  }
+  if (k > 0 && fl[k - 1].off + fl[k - 1].len == fl[k].off) {
+    fl[k - 1].len += fl[k].len;
+    fl.erase(fl.begin() + (long)k);
+  }
+}
+
+struct PagedCube {  // a listed cube of one type the node holds: in the window, or staged beside it
+  int32_t file = -1;
+  int64_t off = 0;     // its filtered points: [off, off + len) of both arenas
+  int32_t len = 0;
+  int32_t batch = -1;  // the forest build its tree came from (-1: fewer than five points, no tree)
+  TreeView view{};
+  bool staged = false;
+};
+struct NodeBatch {  // the node extent of one forest build; it goes back when the last of its trees has left
+  int64_t off = 0, cap = 0;
+  int32_t refs = 0, depth = 0;
+};
+
+struct Paged {
+  bool on = false, have_window = false;
+  std::string dir;
+  std::map<CubeKey, int32_t> index[2];  // setupPCDFileName: global cube -> <count> of its file
+  int centre[3] = {0, 0, 0};
+  std::map<CubeKey, PagedCube> cubes[2];
+  std::vector<NodeBatch> batches;
+  std::vector<CubeKey> active;          // computeActiveAera: global indices in its loop order
+  // the arenas: lslam_loc::tpts (the trees' points) and fpts (the same extents in the filter's order), lslam_loc::nodes
+  DevBuf<float4> fpts;
+  size_t cap_pts = 0, cap_nodes = 0;
+  std::vector<PmExtent> free_pts, free_nodes;
+  size_t limit = 0;                     // lslam_pmap_setup_capacity (0: none)
+  size_t used[2] = {0, 0};              // filtered points held per type, staged included
+  size_t nodes_used = 0;
+  bool tables_stale = false;            // an arena moved: the device tables point into the old one
+  // a step's staging
+  PinBuf<float4> in_pin;
+  PinBuf<int32_t> seg_pin, h_bounds[2], h_dst[2];
+  PinBuf<uint32_t> done;                // [2 types][4]
+  DevBuf<float4> in_raw, out[2];
+  DevBuf<int32_t> seg, oseg[2], bounds[2], dst[2];
+  // the window tables, two sets that alternate
+  int flip = 0;
+  PinBuf<int32_t> h_cells[2][2];
+  PinBuf<TreeView> h_views[2];
+  DevBuf<int32_t> d_cells[2][2];
+  DevBuf<TreeView> d_views[2];
+  lslam_loc_window_stats st{};
+};
+
 struct Result {  // what one sweep brings back (pinned)
   GNState st;
   unsigned long long stat[ST_N];
@@ -347,6 +459,9 @@ struct lslam_loc {
   int64_t stamp_last = 0;
   float velocity[3] = {0, 0, 0};
   lslam_loc_search_counts cnt{};
+  // ---- the paged mode (lslam_pmap_open) ----
+  float cfg_cube = 50.0f, cfg_valid = 150.0f;  // what the setup calls said (the store's own defaults)
+  Paged pg;
 };
 
 namespace {
@@ -725,6 +840,591 @@ void end_sweep_counts(lslam_loc *loc) {
   for (uint64_t *p : f) p[1] += p[0];
 }
 
+// ---- the paged window: host side -------------------------------------------------------------------------------------------
+bool pm_in_window(const lslam_loc *loc, const int c[3], const CubeKey &g) {
+  return std::abs(g[0] - c[0]) <= loc->W / 2 && std::abs(g[1] - c[1]) <= loc->H / 2 && std::abs(g[2] - c[2]) <= loc->D / 2;
+}
+
+void pm_release_cube(lslam_loc *loc, int t, const PagedCube &cu) {
+  Paged &pg = loc->pg;
+  ext_free(pg.free_pts, cu.off, cu.len);
+  pg.used[t] -= (size_t)cu.len;
+  if (cu.batch >= 0) {
+    NodeBatch &b = pg.batches[(size_t)cu.batch];
+    if (--b.refs == 0) {
+      ext_free(pg.free_nodes, b.off, b.cap);
+      pg.nodes_used -= (size_t)b.cap;
+      b.cap = 0;
+    }
+  }
+}
+
+// staged cubes a window centred on `keep` would not take: their room goes back
+void pm_drop_staged(lslam_loc *loc, const int keep[3]) {
+  Paged &pg = loc->pg;
+  for (int t = 0; t < 2; ++t)
+    for (auto it = pg.cubes[t].begin(); it != pg.cubes[t].end();) {
+      if (it->second.staged && !(keep && pm_in_window(loc, keep, it->first))) {
+        pm_release_cube(loc, t, it->second);
+        pg.st.staged_dropped_total[t]++;
+        it = pg.cubes[t].erase(it);
+      } else {
+        ++it;
+      }
+    }
+}
+
+void pm_reset(lslam_loc *loc) {  // every cube gone, the arenas empty (their memory is kept)
+  Paged &pg = loc->pg;
+  pg.cubes[0].clear();
+  pg.cubes[1].clear();
+  pg.batches.clear();
+  pg.active.clear();
+  pg.free_pts.clear();
+  pg.free_nodes.clear();
+  if (pg.cap_pts) pg.free_pts.push_back(PmExtent{0, (int64_t)pg.cap_pts});
+  if (pg.cap_nodes) pg.free_nodes.push_back(PmExtent{0, (int64_t)pg.cap_nodes});
+  pg.used[0] = pg.used[1] = 0;
+  pg.nodes_used = 0;
+  pg.have_window = false;
+  pg.tables_stale = false;
+}
+
+// Both point arenas to at least `want` points, contents kept; every view is moved along.  The device tables keep pointing into
+// the old arena until they are rewritten (tables_stale).
+int pm_grow_points(lslam_loc *loc, size_t want) {
+  Paged &pg = loc->pg;
+  hipStream_t s = loc->stream;
+  if (want > ((size_t)1 << 30)) return invalid("paged window", "more than 2^30 points");
+  const size_t old = pg.cap_pts;
+  const float4 *before = loc->tpts.p;
+  LOC_TRY(pg.fpts.grow(want + 16, old, s));
+  LOC_TRY(loc->tpts.grow(want + 16, old, s));
+  if (loc->tpts.p != before) {
+    for (int t = 0; t < 2; ++t)
+      for (auto &kv : pg.cubes[t])
+        if (kv.second.batch >= 0) kv.second.view.pts = loc->tpts.p;
+    pg.tables_stale = true;
+  }
+  const size_t cap = std::min(pg.fpts.cap, loc->tpts.cap) - 16;
+  if (cap > old) ext_free(pg.free_pts, (int64_t)old, (int64_t)(cap - old));
+  pg.cap_pts = std::max(cap, old);
+  return LSLAM_OK;
+}
+int pm_grow_nodes(lslam_loc *loc, size_t want) {
+  Paged &pg = loc->pg;
+  const size_t old = pg.cap_nodes;
+  const KdNode *before = loc->nodes.p;
+  LOC_TRY(loc->nodes.grow(want, old, loc->stream));
+  if (loc->nodes.p != before) {
+    for (int t = 0; t < 2; ++t)
+      for (auto &kv : pg.cubes[t])
+        if (kv.second.batch >= 0) kv.second.view.nodes = loc->nodes.p + pg.batches[(size_t)kv.second.batch].off;
+    pg.tables_stale = true;
+  }
+  const size_t cap = loc->nodes.cap & ~(size_t)7;
+  if (cap > old) ext_free(pg.free_nodes, (int64_t)old, (int64_t)(cap - old));
+  pg.cap_nodes = std::max(cap, old);
+  return LSLAM_OK;
+}
+
+// The window tables for centre c from the cubes the node holds: per type cell_tree over W x H x D and the TreeViews, in ascending
+// window-cell order; CubeGridDev.origin = (W/2, H/2, D/2) - c.  Written into the set of buffers the kernels are not reading.
+int pm_write_tables(lslam_loc *loc, const int c[3]) {
+  Paged &pg = loc->pg;
+  hipStream_t s = loc->stream;
+  const int W = loc->W, H = loc->H, D = loc->D;
+  const size_t ncell = (size_t)W * H * D;
+  const int f = pg.flip ^ 1;
+  size_t n_tree[2] = {0, 0};
+  int depth = 0;
+  for (int t = 0; t < 2; ++t) {
+    LOC_TRY(pg.h_cells[f][t].reserve(ncell));
+    LOC_TRY(pg.d_cells[f][t].reserve(ncell));
+    for (const auto &kv : pg.cubes[t])
+      if (!kv.second.staged && kv.second.batch >= 0 && pm_in_window(loc, c, kv.first)) n_tree[t]++;
+  }
+  LOC_TRY(pg.h_views[f].reserve(n_tree[0] + n_tree[1] + 1));
+  LOC_TRY(pg.d_views[f].reserve(n_tree[0] + n_tree[1] + 1));
+  size_t at = 0;
+  for (int t = 0; t < 2; ++t) {
+    loc->tree_cube[t].clear();
+    loc->tree_l[t].clear();
+    loc->tree_r[t].clear();
+    loc->cubes_loaded[t] = 0;
+    size_t n_pts = 0;
+    int32_t *cells = pg.h_cells[f][t].p;
+    for (int k = 0; k < D; ++k)
+      for (int j = 0; j < H; ++j)
+        for (int i = 0; i < W; ++i) {
+          const size_t cell = (size_t)i + (size_t)j * W + (size_t)k * W * H;
+          cells[cell] = -1;
+          const CubeKey g = {c[0] + i - W / 2, c[1] + j - H / 2, c[2] + k - D / 2};
+          const auto it = pg.cubes[t].find(g);
+          if (it == pg.cubes[t].end() || it->second.staged) continue;
+          const PagedCube &cu = it->second;
+          if (cu.len > 0) loc->cubes_loaded[t]++;
+          n_pts += (size_t)cu.len;
+          if (cu.batch < 0) continue;  // DynamicFeatureMap.h: a cube with fewer than five points is skipped by the match
+          cells[cell] = (int32_t)loc->tree_cube[t].size();
+          loc->tree_cube[t].push_back((int32_t)cell);
+          loc->tree_l[t].push_back((int32_t)cu.off);
+          loc->tree_r[t].push_back((int32_t)(cu.off + cu.len));
+          pg.h_views[f].p[at++] = cu.view;
+          depth = std::max(depth, pg.batches[(size_t)cu.batch].depth);
+        }
+    loc->view.n[t] = n_pts;
+    LOC_TRY(hipMemcpyAsync(pg.d_cells[f][t].p, cells, ncell * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  }
+  if (at) LOC_TRY(hipMemcpyAsync(pg.d_views[f].p, pg.h_views[f].p, at * sizeof(TreeView), hipMemcpyHostToDevice, s));
+  LOC_TRY(hipStreamSynchronize(s));  // (this set of pinned tables is written again two steps from now)
+  pg.st.step_host_waits++;
+  pg.flip = f;
+  FmapView &v = loc->view;
+  v.W = W; v.H = H; v.D = D;
+  v.origin[0] = W / 2 - c[0]; v.origin[1] = H / 2 - c[1]; v.origin[2] = D / 2 - c[2];
+  v.cube_size = loc->cfg_cube;
+  v.valid_dist = loc->cfg_valid;
+  for (int t = 0; t < 2; ++t) {
+    CubeGridDev &g = loc->cg[t];
+    g.cube_size = v.cube_size;
+    for (int d = 0; d < 3; ++d) g.origin[d] = v.origin[d];
+    g.dims[0] = W; g.dims[1] = H; g.dims[2] = D;
+    g.cell_tree = pg.d_cells[f][t].p;
+    g.trees = pg.d_views[f].p + (t ? n_tree[0] : 0);
+  }
+  loc->tree_depth = depth;
+  loc->grid_valid = false;  // the cell grids are rebuilt from the arena for the new centre (ensure_grids)
+  loc->have_map = true;
+  pg.tables_stale = false;
+  return LSLAM_OK;
+}
+
+struct PmEnter {  // a cube that a step (or a staging) brings in
+  int t, seg;
+  CubeKey g;
+  int32_t file;
+  size_t first, n_raw;  // its file's points in the upload
+  PagedCube cu;
+};
+struct PmTxn {  // what a step has taken and must give back when it is refused
+  std::vector<PmExtent> pts;
+  PmExtent nodes = {0, 0};
+};
+
+int pm_filter_type(lslam_loc *loc, int t, size_t first, size_t n, int nseg, bool no_wait) {
+  Paged &pg = loc->pg;
+  hipStream_t s = loc->stream;
+  uint32_t *done = pg.done.p + 4 * t;
+  size_t m = 0;
+  int rc = lslam::voxel_filter_segments(loc->ctx, pg.in_raw.p + first, pg.seg.p + first, n, nseg, loc->map_leaf[t], pg.out[t].p, pg.oseg[t].p, &m,
+                                        true, no_wait ? done : nullptr);
+  if (rc) return rc;
+  if (!no_wait) {
+    done[0] = (uint32_t)m;
+    done[1] = 0;
+  }
+  pg.st.step_filter_runs++;
+  LOC_TRY(hipMemsetAsync(pg.bounds[t].p, 0, 2 * (size_t)nseg * sizeof(int32_t), s));
+  hipLaunchKernelGGL(pm_bounds_kernel, dim3(((unsigned)n + 255) / 256), dim3(256), 0, s, (const int32_t *)pg.oseg[t].p, (const uint32_t *)done, (int)n,
+                     nseg, pg.bounds[t].p);
+  LOC_TRY(hipGetLastError());
+  pg.st.step_kernels++;
+  LOC_TRY(hipMemcpyAsync(pg.h_bounds[t].p, pg.bounds[t].p, 2 * (size_t)nseg * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  return LSLAM_OK;
+}
+
+int pm_place_type(lslam_loc *loc, int t, size_t n, int nseg) {
+  Paged &pg = loc->pg;
+  hipLaunchKernelGGL(pm_place_kernel, dim3(((unsigned)n + 255) / 256), dim3(256), 0, loc->stream, (const float4 *)pg.out[t].p,
+                     (const int32_t *)pg.oseg[t].p, (const uint32_t *)(pg.done.p + 4 * t), (int)n, nseg, (const int32_t *)pg.bounds[t].p,
+                     (const int32_t *)pg.dst[t].p, pg.fpts.p, loc->tpts.p);
+  LOC_TRY(hipGetLastError());
+  pg.st.step_kernels++;
+  return LSLAM_OK;
+}
+
+// Bring in the listed cubes of the window centred on c that the node does not hold.  stage: into spare room only -- no table
+// changes, nothing leaves.  Otherwise the step: staged cubes of the new window are adopted, the others are read, the cubes
+// outside the new window leave, the tables are rewritten.  Nothing live changes before the commit at the end.
+int pm_bring_body(lslam_loc *loc, const int c[3], bool stage, PmTxn &txn) {
+  Paged &pg = loc->pg;
+  hipStream_t s = loc->stream;
+  lslam_loc_window_stats &st = pg.st;
+  const int W = loc->W, H = loc->H, D = loc->D;
+  // 1. who enters
+  std::vector<PmEnter> enter;
+  int nseg[2] = {0, 0};
+  int64_t adopted[2] = {0, 0};
+  for (int t = 0; t < 2; ++t)
+    for (int k = -D / 2; k <= D / 2; ++k)
+      for (int j = -H / 2; j <= H / 2; ++j)
+        for (int i = -W / 2; i <= W / 2; ++i) {
+          const CubeKey g = {c[0] + i, c[1] + j, c[2] + k};
+          const auto li = pg.index[t].find(g);
+          if (li == pg.index[t].end()) continue;
+          const auto cu = pg.cubes[t].find(g);
+          if (cu != pg.cubes[t].end()) {
+            if (cu->second.staged && !stage) adopted[t]++;
+            continue;
+          }
+          PmEnter e{};
+          e.t = t;
+          e.seg = nseg[t]++;
+          e.g = g;
+          e.file = li->second;
+          e.cu.file = li->second;
+          e.cu.staged = stage;
+          enter.push_back(e);
+        }
+  // 2. their files, into one pinned block [corner cubes | surf cubes] with the segment of every point
+  std::vector<std::vector<float4>> raw(enter.size());
+  size_t n_in[2] = {0, 0};
+  int64_t files_read = 0, files_missing = 0;
+  for (size_t k = 0; k < enter.size(); ++k) {
+    std::string err;
+    const std::string path = pg.dir + "/" + std::to_string(enter[k].file) + ".pcd";
+    if (!lslam::fmap_read_pcd(path.c_str(), raw[k], err)) {  // reference: `if(!file) continue;` -- the cube stays empty
+      raw[k].clear();
+      files_missing++;
+    } else {
+      files_read++;
+    }
+    enter[k].n_raw = raw[k].size();
+    n_in[enter[k].t] += raw[k].size();
+  }
+  const size_t n = n_in[0] + n_in[1];
+  if (n > ((size_t)1 << 27)) return invalid("paged window", "too many points in the entering files");
+  uint64_t bytes = 0;
+  int waits = 0;
+  if (n) {
+    LOC_TRY(pg.in_pin.reserve(n));
+    LOC_TRY(pg.seg_pin.reserve(n));
+    LOC_TRY(pg.in_raw.reserve(n));
+    LOC_TRY(pg.seg.reserve(n));
+    LOC_TRY(pg.done.reserve(8));
+    size_t at = 0;
+    for (size_t k = 0; k < enter.size(); ++k) {
+      enter[k].first = at;
+      if (!raw[k].empty()) std::memcpy(pg.in_pin.p + at, raw[k].data(), raw[k].size() * sizeof(float4));
+      for (size_t i = 0; i < raw[k].size(); ++i) pg.seg_pin.p[at + i] = enter[k].seg;
+      at += raw[k].size();
+    }
+    LOC_TRY(hipMemcpyAsync(pg.in_raw.p, pg.in_pin.p, n * sizeof(float4), hipMemcpyHostToDevice, s));
+    LOC_TRY(hipMemcpyAsync(pg.seg.p, pg.seg_pin.p, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    bytes += n * (sizeof(float4) + sizeof(int32_t));
+    for (int k = 0; k < 8; ++k) pg.done.p[k] = 0;
+    // 3. pcl::VoxelGrid of every entering cube, one run per type over all of them; the runs' segment bounds
+    for (int t = 0; t < 2; ++t) {
+      if (!n_in[t]) continue;
+      LOC_TRY(pg.out[t].reserve(n_in[t]));
+      LOC_TRY(pg.oseg[t].reserve(n_in[t]));
+      LOC_TRY(pg.bounds[t].reserve(2 * (size_t)nseg[t]));
+      LOC_TRY(pg.h_bounds[t].reserve(2 * (size_t)nseg[t]));
+      LOC_TRY(pg.h_dst[t].reserve((size_t)nseg[t]));
+      LOC_TRY(pg.dst[t].reserve((size_t)nseg[t]));
+      int rc = pm_filter_type(loc, t, t ? n_in[0] : 0, n_in[t], nseg[t], true);
+      if (rc) return rc;
+    }
+    LOC_TRY(hipStreamSynchronize(s));  // the step's wait: how many points every cube keeps
+    waits++;
+    for (int t = 0; t < 2; ++t) {
+      if (!n_in[t] || !pg.done.p[4 * t + 1]) continue;
+      // the filter's wide key did not hold a voxel extent: this type once more, with the filter measuring it (waits inside)
+      int rc = pm_filter_type(loc, t, t ? n_in[0] : 0, n_in[t], nseg[t], false);
+      if (rc) return rc;
+      LOC_TRY(hipStreamSynchronize(s));
+      waits += 2;
+    }
+  }
+  // 4. room: the counts against the capacity, then an extent per cube
+  size_t n_new[2] = {0, 0};
+  for (PmEnter &e : enter) {
+    if (!e.n_raw) continue;
+    const int32_t *hb = pg.h_bounds[e.t].p;
+    e.cu.len = hb[2 * e.seg + 1] - hb[2 * e.seg];
+    n_new[e.t] += (size_t)e.cu.len;
+  }
+  if (pg.limit)
+    for (int t = 0; t < 2; ++t)
+      if (pg.used[t] + n_new[t] > pg.limit) {
+        if (!stage) pm_drop_staged(loc, c);  // staged cubes the window does not reach make room
+        if (pg.used[t] + n_new[t] > pg.limit) {
+          char b[200];
+          std::snprintf(b, sizeof(b), "%zu + %zu %s points exceed the capacity of %zu per type (lslam_pmap_setup_capacity)", pg.used[t],
+                        n_new[t], t ? "surf" : "corner", pg.limit);
+          return invalid(stage ? "lslam_pmap_stage" : "paged window step", b);
+        }
+      }
+  for (PmEnter &e : enter) {
+    if (e.cu.len <= 0) continue;
+    if (!ext_alloc(pg.free_pts, e.cu.len, &e.cu.off)) {
+      // (the arena at least doubles, and holds everything held and entering even if its free room were all fragments)
+      int rc = pm_grow_points(loc, std::max(2 * pg.cap_pts, pg.cap_pts + n_new[0] + n_new[1] + 1024));
+      if (rc) return rc;
+      if (!ext_alloc(pg.free_pts, e.cu.len, &e.cu.off)) return invalid("paged window", "no room in the point arena");
+    }
+    txn.pts.push_back(PmExtent{e.cu.off, e.cu.len});
+  }
+  // 5. placement
+  std::vector<int32_t> roots_lr;
+  std::vector<size_t> root_of;
+  int64_t n_total = 0;
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < nseg[t]; ++k)
+      if (n_in[t]) pg.h_dst[t].p[k] = -1;
+  for (size_t k = 0; k < enter.size(); ++k) {
+    const PmEnter &e = enter[k];
+    if (e.cu.len <= 0) continue;
+    pg.h_dst[e.t].p[e.seg] = (int32_t)e.cu.off;
+    if (e.cu.len >= 5) {
+      roots_lr.push_back((int32_t)e.cu.off);
+      roots_lr.push_back((int32_t)(e.cu.off + e.cu.len));
+      root_of.push_back(k);
+      n_total = std::max(n_total, e.cu.off + e.cu.len);
+    }
+  }
+  for (int t = 0; t < 2; ++t) {
+    if (!n_new[t]) continue;
+    LOC_TRY(hipMemcpyAsync(pg.dst[t].p, pg.h_dst[t].p, (size_t)nseg[t] * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    bytes += (size_t)nseg[t] * sizeof(int32_t);
+    int rc = pm_place_type(loc, t, n_in[t], nseg[t]);
+    if (rc) return rc;
+  }
+  // 6. ONE forest build over the entering cubes, into a node extent of its own
+  const int T = (int)root_of.size();
+  int batch = -1, forest_builds = 0;
+  NodeBatch nb{};
+  if (T > 0) {
+    std::vector<TreeView> views((size_t)T);
+    size_t n_root_pts = 0;
+    for (int r = 0; r < T; ++r) n_root_pts += (size_t)(roots_lr[2 * (size_t)r + 1] - roots_lr[2 * (size_t)r]);
+    int max_depth = 0, fallback = 0;
+    size_t n_leaves = 0;
+    for (int attempt = 0; attempt < 3; ++attempt) {
+      // (generous at once: a step waits for its build, a second build costs more than the room, and what the trees do not use goes back below)
+      const size_t mult[3] = {6, 12, 24};
+      const size_t cap = ((mult[attempt] * n_root_pts / 3 + 64 + 8 * (size_t)T) + 7) & ~(size_t)7;
+      if (txn.nodes.len) {
+        ext_free(pg.free_nodes, txn.nodes.off, txn.nodes.len);
+        txn.nodes = PmExtent{0, 0};
+      }
+      int64_t off = 0;
+      if (!ext_alloc(pg.free_nodes, (int64_t)cap, &off)) {
+        int rc = pm_grow_nodes(loc, std::max(2 * pg.cap_nodes, pg.cap_nodes + cap + 1024));
+        if (rc) return rc;
+        if (!ext_alloc(pg.free_nodes, (int64_t)cap, &off)) return invalid("paged window", "no room in the node arena");
+      }
+      txn.nodes = PmExtent{off, (int64_t)cap};
+      if (attempt > 0)  // the failed attempt permuted the points
+        for (int t = 0; t < 2; ++t)
+          if (n_new[t]) {
+            int rc = pm_place_type(loc, t, n_in[t], nseg[t]);
+            if (rc) return rc;
+          }
+      LOC_TRY(lslam::build_kdforest_device(lslam::ctx_build_pool(loc->ctx, 0), loc->tpts.p, (int32_t)n_total, roots_lr.data(), T, loc->nodes.p + off,
+                                           nullptr, (int32_t)cap, s, views.data(), &max_depth, &n_leaves, &fallback));
+      forest_builds++;
+      waits++;
+      if (fallback != 1) break;
+    }
+    if (fallback) {
+      lslam::set_error("paged window: the device cube-tree build hit a structure limit");
+      return fallback == 1 || fallback == 2 ? LSLAM_ERR_TREE_BUILD : LSLAM_ERR_TREE_DEPTH;
+    }
+    if (max_depth > KD_STACK_LDS + 1) {
+      lslam::set_error("paged window: a cube tree is deeper than the device traversal stack");
+      return LSLAM_ERR_TREE_DEPTH;
+    }
+    const int64_t n_used = std::max<int64_t>(8, ((int64_t)views[0].n_nodes + 7) & ~(int64_t)7);  // node groups the build took, all trees together
+    if (n_used < txn.nodes.len) {
+      ext_free(pg.free_nodes, txn.nodes.off + n_used, txn.nodes.len - n_used);
+      txn.nodes.len = n_used;
+    }
+    nb.off = txn.nodes.off;
+    nb.cap = txn.nodes.len;
+    nb.refs = T;
+    nb.depth = max_depth;
+    batch = (int)pg.batches.size();
+    for (int r = 0; r < T; ++r) {
+      enter[root_of[(size_t)r]].cu.view = views[(size_t)r];
+      enter[root_of[(size_t)r]].cu.batch = batch;
+    }
+  }
+  // 7. the commit
+  if (T > 0) {
+    pg.batches.push_back(nb);
+    pg.nodes_used += (size_t)nb.cap;
+  }
+  txn = PmTxn{};
+  int64_t entered[2] = {0, 0}, left[2] = {0, 0};
+  for (const PmEnter &e : enter) {
+    pg.cubes[e.t][e.g] = e.cu;
+    pg.used[e.t] += (size_t)e.cu.len;
+    entered[e.t]++;
+  }
+  st.files_read_total += files_read;
+  st.files_missing_total += files_missing;
+  st.trees_built_total += T;
+  st.forest_builds_total += forest_builds;
+  st.bytes_uploaded_total += bytes;
+  if (stage) return LSLAM_OK;
+  for (int t = 0; t < 2; ++t)
+    for (auto it = pg.cubes[t].begin(); it != pg.cubes[t].end();) {
+      if (pm_in_window(loc, c, it->first)) {
+        it->second.staged = false;
+        ++it;
+      } else if (!it->second.staged) {
+        pm_release_cube(loc, t, it->second);
+        left[t]++;
+        it = pg.cubes[t].erase(it);
+      } else {
+        ++it;
+      }
+    }
+  for (int t = 0; t < 2; ++t) {
+    st.entered[t] = entered[t] + adopted[t];
+    st.adopted[t] = adopted[t];
+    st.left[t] = left[t];
+    st.entered_total[t] += entered[t] + adopted[t];
+    st.adopted_total[t] += adopted[t];
+    st.left_total[t] += left[t];
+  }
+  st.files_read = files_read;
+  st.files_missing = files_missing;
+  st.trees_built = T;
+  st.bytes_uploaded = bytes;
+  st.step_forest_builds = forest_builds;
+  st.step_host_waits = waits;
+  st.steps++;
+  for (int d = 0; d < 3; ++d) pg.centre[d] = c[d];
+  pg.have_window = true;
+  return pm_write_tables(loc, c);
+}
+
+int pm_bring(lslam_loc *loc, const int c[3], bool stage) {
+  Paged &pg = loc->pg;
+  const lslam_loc_window_stats last = pg.st;  // (a staging leaves the last step's counters as they are)
+  pg.st.step_kernels = pg.st.step_filter_runs = pg.st.step_forest_builds = pg.st.step_host_waits = 0;
+  PmTxn txn;
+  const int rc = pm_bring_body(loc, c, stage, txn);
+  if (stage) {
+    pg.st.step_kernels = last.step_kernels;
+    pg.st.step_filter_runs = last.step_filter_runs;
+    pg.st.step_forest_builds = last.step_forest_builds;
+    pg.st.step_host_waits = last.step_host_waits;
+  }
+  if (rc == LSLAM_OK) {
+    // (a staging that moved an arena: the same tables once more, pointing into the new one)
+    if (stage && pg.tables_stale && pg.have_window) return pm_write_tables(loc, pg.centre);
+    return rc;
+  }
+  // refused: what the step took goes back, and the node answers the next call as it did before
+  (void)hipStreamSynchronize(loc->stream);
+  for (const PmExtent &x : txn.pts) ext_free(pg.free_pts, x.off, x.len);
+  ext_free(pg.free_nodes, txn.nodes.off, txn.nodes.len);
+  if (!stage) pg.st.refused_steps++;
+  if (pg.tables_stale && pg.have_window) {  // an arena moved before the refusal: the old window's tables, for where it is now
+    const std::string msg = lslam_last_error();
+    (void)pm_write_tables(loc, pg.centre);
+    lslam::set_error(msg.c_str());
+  }
+  return rc;
+}
+
+// computeActiveAera + InVerticalFov (DynamicFeatureMap.h:748-804): the offsets within ws cubes, loops i, j, k, that are listed
+// and -- the centre apart -- have one of their eight corners within the valid distance of the sensor's fractional position
+void pm_active_area(lslam_loc *loc, const float pos[3]) {
+  Paged &pg = loc->pg;
+  pg.active.clear();
+  const float cs = loc->cfg_cube, valid = loc->cfg_valid;
+  const int *c = pg.centre;
+  const double real[3] = {(double)(pos[0] / cs - (float)c[0]), (double)(pos[1] / cs - (float)c[1]), (double)(pos[2] / cs - (float)c[2])};
+  const int ws = (int)std::ceil(valid / cs);
+  const double d[2] = {-0.5, 0.5};
+  for (int i = -ws; i <= ws; ++i)
+    for (int j = -ws; j <= ws; ++j)
+      for (int k = -ws; k <= ws; ++k) {
+        const CubeKey g = {c[0] + i, c[1] + j, c[2] + k};
+        if (!pg.index[0].count(g) && !pg.index[1].count(g)) continue;
+        bool in = !i && !j && !k;
+        if (!in) {
+          double min_dis = -1.0;
+          for (int dx = 0; dx < 2; ++dx)
+            for (int dy = 0; dy < 2; ++dy)
+              for (int dz = 0; dz < 2; ++dz) {
+                const double x = i + d[dx] - real[0], y = j + d[dy] - real[1], z = k + d[dz] - real[2];
+                const double dis = std::sqrt(std::pow(x * cs, 2) + std::pow(y * cs, 2) + std::pow(z * cs, 2));
+                min_dis = min_dis == -1.0 ? dis : std::min(min_dis, dis);
+              }
+          in = !(min_dis > (double)valid);
+        }
+        if (in) pg.active.push_back(g);
+      }
+  pg.st.active_cubes = pg.active.size();
+}
+
+// DynamicFeatureMap::update
+int pm_update(lslam_loc *loc, const float pos[3]) {
+  Paged &pg = loc->pg;
+  int c[3];
+  for (int d = 0; d < 3; ++d) {
+    if (!std::isfinite(pos[d])) return invalid("paged window", "the sensor position is not finite");
+    c[d] = (int)std::round(pos[d] / loc->cfg_cube);  // Glo2GloIdx: a float quotient
+  }
+  if (!pg.have_window || c[0] != pg.centre[0] || c[1] != pg.centre[1] || c[2] != pg.centre[2]) {
+    const int rc = pm_bring(loc, c, false);
+    if (rc) return rc;
+  }
+  pm_active_area(loc, pos);
+  return LSLAM_OK;
+}
+
+int pm_surround(lslam_loc *loc, const char *fn, float *corner_xyzi, size_t cap_corner, size_t *n_corner, float *surf_xyzi, size_t cap_surf,
+                size_t *n_surf) {
+  Paged &pg = loc->pg;
+  size_t cnt[2] = {0, 0};
+  for (int t = 0; t < 2; ++t)
+    for (const CubeKey &g : pg.active) {
+      const auto it = pg.cubes[t].find(g);
+      if (it != pg.cubes[t].end() && !it->second.staged) cnt[t] += (size_t)it->second.len;
+    }
+  *n_corner = cnt[0];
+  *n_surf = cnt[1];
+  if (!corner_xyzi && !surf_xyzi) return LSLAM_OK;
+  if ((corner_xyzi && cap_corner < cnt[0]) || (surf_xyzi && cap_surf < cnt[1]) || !corner_xyzi || !surf_xyzi)
+    return invalid(fn, "both buffers are needed, each with room for its cloud");
+  float *out[2] = {corner_xyzi, surf_xyzi};
+  for (int t = 0; t < 2; ++t) {
+    size_t at = 0;
+    for (const CubeKey &g : pg.active) {
+      const auto it = pg.cubes[t].find(g);
+      if (it == pg.cubes[t].end() || it->second.staged || it->second.len <= 0) continue;
+      LOC_TRY(hipMemcpyAsync(out[t] + 4 * at, pg.fpts.p + it->second.off, (size_t)it->second.len * sizeof(float4), hipMemcpyDeviceToHost, loc->stream));
+      at += (size_t)it->second.len;
+    }
+  }
+  LOC_TRY(hipStreamSynchronize(loc->stream));
+  return LSLAM_OK;
+}
+
+int paged_only(lslam_loc *loc, const char *fn) {
+  int rc = check_loc(loc, fn);
+  if (rc) return rc;
+  if (!loc->pg.on) return invalid(fn, "the node is not in the paged mode (lslam_pmap_open)");
+  return LSLAM_OK;
+}
+void pm_leave(lslam_loc *loc) {  // a static map replaces the window: the arenas' memory is the static structures' again
+  if (!loc->pg.on) return;
+  (void)hipStreamSynchronize(loc->stream);
+  pm_reset(loc);
+  loc->pg.cap_pts = loc->pg.cap_nodes = 0;
+  loc->pg.free_pts.clear();
+  loc->pg.free_nodes.clear();
+  loc->pg.on = false;
+  loc->have_map = false;
+}
+
 int process_impl(lslam_loc *loc, const char *fn, const void *corner, size_t n_corner, const void *surf, size_t n_surf,
                  size_t stride_bytes, bool from_device, const float odom[16], int64_t stamp_ns, float mapped_out[16],
                  float velocity_out[3], int32_t *flags, lslam_stats *stats) {
@@ -737,7 +1437,7 @@ int process_impl(lslam_loc *loc, const char *fn, const void *corner, size_t n_co
     *flags = LSLAM_LOC_DROPPED;
     return LSLAM_OK;
   }
-  if (!loc->have_map) {
+  if (!loc->pg.on && !loc->have_map) {
     lslam::set_error("localisation node: no map (lslam_loc_load / _set_map / _set_map_from_fmap)");
     return LSLAM_ERR_NO_MAP;
   }
@@ -745,7 +1445,12 @@ int process_impl(lslam_loc *loc, const char *fn, const void *corner, size_t n_co
   float Wnew[16];
   lslam_transform_associate(loc->odom_last, odom, loc->mapped_last, Wnew);
   bool at_edge = false;
-  {
+  if (loc->pg.on) {
+    // LaserMatcher.cpp:310-316: the window follows the merged prior (with a pose pending too: the quirk is kept); no edge here
+    const float pos[3] = {Wnew[3], Wnew[7], Wnew[11]};
+    rc = pm_update(loc, pos);
+    if (rc) return rc;
+  } else {
     const float pos[3] = {Wnew[3], Wnew[7], Wnew[11]};
     int g[3];
     cube_of(loc, pos, g);
@@ -849,6 +1554,7 @@ int lslam_loc_setup_map_filter_size(lslam_loc *loc, float corner, float surf) {
   int rc = check_loc(loc, "lslam_loc_setup_map_filter_size");
   if (rc) return rc;
   if (!(corner > 0.f) || !(surf > 0.f)) return invalid("lslam_loc_setup_map_filter_size", "a leaf must be positive");
+  if (loc->pg.on) return invalid("lslam_loc_setup_map_filter_size", "set before lslam_pmap_open: the window's cubes were filtered with the old leaves");
   loc->map_leaf[0] = corner;
   loc->map_leaf[1] = surf;
   return lslam_fmap_setup_filter_size(loc->fm, corner, surf, 0.6f);
@@ -856,6 +1562,7 @@ int lslam_loc_setup_map_filter_size(lslam_loc *loc, float corner, float surf) {
 int lslam_loc_setup_world_origin(lslam_loc *loc, int32_t ox, int32_t oy, int32_t oz) {
   int rc = check_loc(loc, "lslam_loc_setup_world_origin");
   if (rc) return rc;
+  if (loc->pg.on) return invalid("lslam_loc_setup_world_origin", "the paged window is addressed by global cube index: it has no origin to set");
   loc->have_map = false;  // the cubes of a map that is there were cut with the old origin
   return lslam_fmap_setup_world_origin(loc->fm, ox, oy, oz);
 }
@@ -863,12 +1570,17 @@ int lslam_loc_setup_world_cube_size(lslam_loc *loc, float size) {
   int rc = check_loc(loc, "lslam_loc_setup_world_cube_size");
   if (rc) return rc;
   if (!(size > 0.f)) return invalid("lslam_loc_setup_world_cube_size", "the cube size must be positive");
+  if (loc->pg.on) return invalid("lslam_loc_setup_world_cube_size", "set before lslam_pmap_open: the index is in cubes of the old size");
+  loc->cfg_cube = size;
   loc->have_map = false;
   return lslam_fmap_setup_world_cube_size(loc->fm, size);
 }
 int lslam_loc_setup_lidar_valid_distance(lslam_loc *loc, float dist) {
   int rc = check_loc(loc, "lslam_loc_setup_lidar_valid_distance");
   if (rc) return rc;
+  if (loc->pg.on && (!(dist >= 0.f) || (int)std::ceil(dist / loc->cfg_cube) > std::min(loc->W, std::min(loc->H, loc->D)) / 2))
+    return invalid("lslam_loc_setup_lidar_valid_distance", "the active area would reach beyond the paged window");
+  loc->cfg_valid = dist;
   loc->view.valid_dist = dist;
   loc->grid_valid = false;
   return lslam_fmap_setup_lidar_valid_distance(loc->fm, dist);
@@ -884,6 +1596,7 @@ int lslam_loc_load(lslam_loc *loc, const char *directory) {
   int rc = check_loc(loc, "lslam_loc_load");
   if (rc) return rc;
   if (!directory) return invalid("lslam_loc_load", "null directory");
+  pm_leave(loc);
   loc->have_map = false;
   rc = lslam::fmap_clear(loc->fm);
   if (rc) return rc;
@@ -898,6 +1611,7 @@ int lslam_loc_set_map(lslam_loc *loc, const void *corner, size_t n_corner, const
   int rc = check_loc(loc, "lslam_loc_set_map");
   if (rc) return rc;
   if ((n_corner && !corner) || (n_surf && !surf) || stride_bytes < 12 || (stride_bytes & 3)) return invalid("lslam_loc_set_map", "bad arguments");
+  pm_leave(loc);
   loc->have_map = false;
   rc = lslam::fmap_set_clouds(loc->fm, corner, n_corner, surf, n_surf, stride_bytes, filter != 0);
   if (rc) return rc;
@@ -909,9 +1623,17 @@ int lslam_loc_set_map_from_fmap(lslam_loc *loc, lslam_fmap *fm) {
   int rc = check_loc(loc, "lslam_loc_set_map_from_fmap");
   if (rc) return rc;
   if (!fm) return invalid("lslam_loc_set_map_from_fmap", "null feature map");
+  pm_leave(loc);
   loc->have_map = false;
   rc = lslam::fmap_copy(loc->fm, fm);
   if (rc) return rc;
+  {  // cube size and valid distance are the adopted map's
+    FmapView v{};
+    if (lslam::fmap_view(loc->fm, &v) == LSLAM_OK) {
+      loc->cfg_cube = v.cube_size;
+      loc->cfg_valid = v.valid_dist;
+    }
+  }
   lslam_fmap_setup_filter_size(loc->fm, loc->map_leaf[0], loc->map_leaf[1], 0.6f);
   set_grid_cells(loc, false);
   return install(loc);
@@ -969,6 +1691,11 @@ int lslam_loc_match(lslam_loc *loc, const void *corner, size_t n_corner, const v
   int rc = check_loc(loc, "lslam_loc_match");
   if (rc) return rc;
   if (!pose || (n_corner && !corner) || (n_surf && !surf) || stride_bytes < 12 || (stride_bytes & 3)) return invalid("lslam_loc_match", "bad arguments");
+  if (loc->pg.on) {
+    const float pos[3] = {pose[3], pose[4], pose[5]};
+    rc = pm_update(loc, pos);
+    if (rc) return rc;
+  }
   if (!loc->have_map) {
     lslam::set_error("localisation node: no map (lslam_loc_load / _set_map / _set_map_from_fmap)");
     return LSLAM_ERR_NO_MAP;
@@ -987,6 +1714,12 @@ int lslam_loc_get_surround(lslam_loc *loc, float *corner_xyzi, size_t cap_corner
   int rc = check_loc(loc, "lslam_loc_get_surround");
   if (rc) return rc;
   if (!n_corner || !n_surf) return invalid("lslam_loc_get_surround", "null count outputs");
+  if (loc->pg.on) {
+    const float at[3] = {loc->mapped_last[3], loc->mapped_last[7], loc->mapped_last[11]};
+    rc = pm_update(loc, at);
+    if (rc) return rc;
+    return pm_surround(loc, "lslam_loc_get_surround", corner_xyzi, cap_corner, n_corner, surf_xyzi, cap_surf, n_surf);
+  }
   if (!loc->have_map) {
     lslam::set_error("localisation node: no map (lslam_loc_load / _set_map / _set_map_from_fmap)");
     return LSLAM_ERR_NO_MAP;
@@ -1046,6 +1779,9 @@ int lslam_loc_debug_knn5(lslam_loc *loc, int32_t which, const void *queries, siz
     const float pos[3] = {h[0].x, h[0].y, h[0].z};
     int g[3];
     cube_of(loc, pos, g);
+    if (loc->pg.on) {  // the window's grids go around its centre, as a sweep's do
+      g[0] = loc->W / 2; g[1] = loc->H / 2; g[2] = loc->D / 2;
+    }
     rc = ensure_grids(loc, g);
     if (rc) return rc;
   }
@@ -1080,6 +1816,126 @@ int lslam_loc_debug_knn5(lslam_loc *loc, int32_t which, const void *queries, siz
   LOC_TRY(hipMemcpyAsync(how_out, d_how.p, nq, hipMemcpyDeviceToHost, s));
   LOC_TRY(hipStreamSynchronize(s));
   return LSLAM_OK;
+}
+
+// ---- the paged mode --------------------------------------------------------------------------------------------------------
+int lslam_pmap_open(lslam_loc *loc, const char *directory) {
+  int rc = check_loc(loc, "lslam_pmap_open");
+  if (rc) return rc;
+  if (!directory) return invalid("lslam_pmap_open", "null directory");
+  if (!(loc->W & 1) || !(loc->H & 1) || !(loc->D & 1))
+    return invalid("lslam_pmap_open", "an even window dimension: the window has no centre cube (the reference would index out of range)");
+  if (!(loc->cfg_valid >= 0.f) || (int)std::ceil(loc->cfg_valid / loc->cfg_cube) > std::min(loc->W, std::min(loc->H, loc->D)) / 2)
+    return invalid("lslam_pmap_open", "ceil(valid distance / cube size) exceeds half the smallest window dimension: the active area would "
+                                           "reach beyond the window");
+  const std::string dir(directory);
+  std::ifstream fin(dir + "/index2.txt");
+  if (!fin) {
+    lslam::set_error("no index2.txt in the directory");
+    return LSLAM_ERR_INVALID;  // the reference prints "Fail to open index.txt!" and goes on without a map
+  }
+  std::map<CubeKey, int32_t> index[2];
+  int count, type, i, j, k, size;
+  while (fin >> count >> type >> i >> j >> k >> size) index[type ? 1 : 0][CubeKey{i, j, k}] = count;  // a later line replaces an earlier one
+  (void)hipStreamSynchronize(loc->stream);
+  Paged &pg = loc->pg;
+  if (!pg.on) {  // the arenas share lslam_loc::tpts / nodes with the static structures, which end here
+    pg.cap_pts = pg.cap_nodes = 0;
+  }
+  pm_reset(loc);
+  pg.on = true;
+  pg.dir = dir;
+  pg.index[0].swap(index[0]);
+  pg.index[1].swap(index[1]);
+  pg.st = lslam_loc_window_stats{};
+  loc->have_map = false;
+  loc->grid_valid = false;
+  set_grid_cells(loc, true);
+  return LSLAM_OK;
+}
+
+int lslam_pmap_setup_capacity(lslam_loc *loc, size_t max_points_per_type) {
+  int rc = check_loc(loc, "lslam_pmap_setup_capacity");
+  if (rc) return rc;
+  if (max_points_per_type > ((size_t)1 << 29)) return invalid("lslam_pmap_setup_capacity", "more than 2^29 points per type");
+  loc->pg.limit = max_points_per_type;
+  return LSLAM_OK;
+}
+
+int lslam_pmap_update(lslam_loc *loc, const float pos[3]) {
+  int rc = paged_only(loc, "lslam_pmap_update");
+  if (rc) return rc;
+  if (!pos) return invalid("lslam_pmap_update", "null position");
+  return pm_update(loc, pos);
+}
+
+int lslam_pmap_stage(lslam_loc *loc, const float pos[3]) {
+  int rc = paged_only(loc, "lslam_pmap_stage");
+  if (rc) return rc;
+  if (!pos) return invalid("lslam_pmap_stage", "null position");
+  int c[3];
+  for (int d = 0; d < 3; ++d) {
+    if (!std::isfinite(pos[d])) return invalid("lslam_pmap_stage", "the position is not finite");
+    c[d] = (int)std::round(pos[d] / loc->cfg_cube);
+  }
+  return pm_bring(loc, c, true);
+}
+
+int lslam_pmap_get_surround(lslam_loc *loc, float *corner_xyzi, size_t cap_corner, size_t *n_corner, float *surf_xyzi,
+                                  size_t cap_surf, size_t *n_surf) {
+  if (n_corner) *n_corner = 0;
+  if (n_surf) *n_surf = 0;
+  int rc = paged_only(loc, "lslam_pmap_get_surround");
+  if (rc) return rc;
+  if (!n_corner || !n_surf) return invalid("lslam_pmap_get_surround", "null count outputs");
+  if (!loc->pg.have_window) {
+    lslam::set_error("paged window: no update yet");
+    return LSLAM_ERR_NO_MAP;
+  }
+  return pm_surround(loc, "lslam_pmap_get_surround", corner_xyzi, cap_corner, n_corner, surf_xyzi, cap_surf, n_surf);
+}
+
+int lslam_pmap_window_info(lslam_loc *loc, lslam_loc_window_stats *out) {
+  if (out) std::memset(out, 0, sizeof(*out));
+  int rc = check_loc(loc, "lslam_pmap_window_info");
+  if (rc) return rc;
+  if (!out) return invalid("lslam_pmap_window_info", "null output");
+  Paged &pg = loc->pg;
+  *out = pg.st;
+  out->paged = pg.on ? 1 : 0;
+  out->have_window = pg.have_window ? 1 : 0;
+  out->dims[0] = loc->W; out->dims[1] = loc->H; out->dims[2] = loc->D;
+  for (int d = 0; d < 3; ++d) out->centre[d] = pg.centre[d];
+  for (int t = 0; t < 2; ++t) {
+    out->resident[t] = out->resident_with_tree[t] = out->staged[t] = 0;
+    for (const auto &kv : pg.cubes[t]) {
+      if (kv.second.staged) {
+        out->staged[t]++;
+      } else {
+        out->resident[t]++;
+        if (kv.second.batch >= 0) out->resident_with_tree[t]++;
+      }
+    }
+  }
+  out->arena_points_used = pg.used[0] + pg.used[1];
+  out->arena_points_capacity = pg.cap_pts;
+  out->arena_nodes_used = pg.nodes_used;
+  out->arena_nodes_capacity = pg.cap_nodes;
+  return LSLAM_OK;
+}
+
+int lslam_index_convert(const char *in_path, int32_t ox, int32_t oy, int32_t oz, const char *out_path) {
+  if (!in_path || !out_path) return invalid("lslam_index_convert", "null path");
+  std::ifstream fin(in_path);
+  if (!fin) return invalid("lslam_index_convert", "input file error!");
+  std::vector<std::array<long long, 6>> lines;
+  long long count, type, i, j, k, size;
+  while (fin >> count >> type >> i >> j >> k >> size) lines.push_back({count, type, i - ox, j - oy, k - oz, size});
+  fin.close();  // (read whole before writing: out_path may be in_path)
+  std::ofstream fout(out_path);
+  if (!fout) return invalid("lslam_index_convert", "save file error!");
+  for (const auto &l : lines) fout << l[0] << " " << l[1] << " " << l[2] << " " << l[3] << " " << l[4] << " " << l[5] << std::endl;
+  return fout ? LSLAM_OK : invalid("lslam_index_convert", "save file error!");
 }
 
 }  // extern "C"

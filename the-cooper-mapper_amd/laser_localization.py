@@ -4,13 +4,15 @@ loaded once (``load_map`` / ``set_map`` / ``set_map_from``), every cube's kd-tre
 transformMerge, the two scan filters, FeatureMap::scanMatchScan and transformUpdate behind one host wait.
 
 Poses are row-major 4x4 float32; clouds are ``(n, 4)`` float32 ``{x, y, z, intensity}`` (or ``(n, 8)`` pcl::PointXYZI).
-ROS plumbing, ``inputFrameSkip``, the UKF and ``DynamicFeatureMap`` are not mirrored.
+``dynamic_mode=True`` is LaserMatcher's ``dynamicMode`` branch: the cubes are a window over ``files_directory``
+(``index2.txt`` plus ``<count>.pcd``) that follows the sensor (``lslam_pmap_open``; :mod:`.dynamic_feature_map`).
+ROS plumbing, ``inputFrameSkip`` and the UKF are not mirrored.
 """
 import ctypes as C
 
 import numpy as np
 
-from .capi import LslamError, LslamLocMapStats, LslamLocSearchCounts, LslamStats, c_int32_p, c_uint8_p
+from .capi import LslamError, LslamLocMapStats, LslamLocSearchCounts, LslamLocWindowStats, LslamStats, c_int32_p, c_uint8_p
 from .feature_map import _fp, _xyzi
 
 DROPPED, HAS_VELOCITY, POSE_RESET, VELOCITY_ZEROED, SECOND_WAIT = 1, 2, 4, 8, 16  # LSLAM_LOC_* flags
@@ -19,7 +21,8 @@ HOW_SKIPPED, HOW_GRID, HOW_TREE = 0, 1, 2
 
 class LaserLocalization:
     def __init__(self, ctx, cube_width=21, cube_height=11, cube_depth=21, filter_corner=None, filter_surf=None,
-                 map_filter_corner=None, map_filter_surf=None, cube_size=None, world_origin=None, lidar_valid_distance=None):
+                 map_filter_corner=None, map_filter_surf=None, cube_size=None, world_origin=None, lidar_valid_distance=None,
+                 dynamic_mode=False, files_directory=None, paged_capacity=None):
         self.ctx = ctx
         self.lib = ctx.lib
         h = C.c_void_p()
@@ -38,6 +41,11 @@ class LaserLocalization:
             self._check(self.lib.lslam_loc_setup_world_origin(self.h, *[int(v) for v in world_origin]))
         if lidar_valid_distance is not None:
             self._check(self.lib.lslam_loc_setup_lidar_valid_distance(self.h, float(lidar_valid_distance)))
+        self.dynamic_mode = bool(dynamic_mode)
+        if paged_capacity is not None:
+            self._check(self.lib.lslam_pmap_setup_capacity(self.h, int(paged_capacity)))
+        if self.dynamic_mode and files_directory is not None:  # LaserMatcher.cpp:100-104
+            self.setup_files_directory(files_directory)
         self.lidar_mapped = np.eye(4, dtype=np.float32)  # _lidarMappedNew after the last processed sweep
         self.velocity = None                             # None until a sweep has one
         self.last_stats = None
@@ -75,6 +83,42 @@ class LaserLocalization:
     def set_map_from(self, feature_map):
         """Adopt the map of a :class:`~.feature_map.FeatureMap` on the same context, device to device."""
         self._check(self.lib.lslam_loc_set_map_from_fmap(self.h, feature_map.h))
+
+    # ---- the dynamic mode: a window of cubes paged in from files ------------------------------------------------------
+    def setup_files_directory(self, directory):
+        """setupFilesDirectory: index2.txt is read; no PCD is touched before the first sweep."""
+        self._check(self.lib.lslam_pmap_open(self.h, str(directory).encode()))
+        self.dynamic_mode = True
+
+    def setup_paged_capacity(self, max_points_per_type):
+        self._check(self.lib.lslam_pmap_setup_capacity(self.h, int(max_points_per_type)))
+
+    def update(self, position):
+        """DynamicFeatureMap::update at a sensor position (the window follows it, then the active area)."""
+        p = np.ascontiguousarray(position, dtype=np.float32).reshape(3)
+        self._check(self.lib.lslam_pmap_update(self.h, _fp(p)))
+
+    def stage(self, position):
+        """Read, filter and build the cubes a window around ``position`` would need, ahead of the step that takes them."""
+        p = np.ascontiguousarray(position, dtype=np.float32).reshape(3)
+        self._check(self.lib.lslam_pmap_stage(self.h, _fp(p)))
+
+    def get_window_surround(self):
+        """getSurroundFeature of the window as the last update left it -> (corner (n, 4), surf (m, 4))."""
+        nc, ns = C.c_size_t(), C.c_size_t()
+        self._check(self.lib.lslam_pmap_get_surround(self.h, None, 0, C.byref(nc), None, 0, C.byref(ns)))
+        c, s = np.zeros((nc.value, 4), np.float32), np.zeros((ns.value, 4), np.float32)
+        self._check(self.lib.lslam_pmap_get_surround(self.h, _fp(c), len(c), C.byref(nc), _fp(s), len(s), C.byref(ns)))
+        return c, s
+
+    def window_info(self):
+        o = LslamLocWindowStats()
+        self._check(self.lib.lslam_pmap_window_info(self.h, C.byref(o)))
+        out = {}
+        for f, ty in LslamLocWindowStats._fields_:
+            v = getattr(o, f)
+            out[f] = tuple(int(x) for x in v) if hasattr(v, "__len__") else int(v)
+        return out
 
     def set_search(self, use_grid):
         self._check(self.lib.lslam_loc_setup_search(self.h, 1 if use_grid else 0))

@@ -1,0 +1,230 @@
+#!/usr/bin/env python3
+"""Paged against static localisation on a drive through a map of 50 m cubes (not bench.py: the headline workload is untouched).
+
+The scene of tests/test_gpu_paged_localization.py enlarged to the reference's defaults: a 600 m world, the map binned into 50 m
+cubes, one PCD per (type, cube); a straight drive from x = -270 m to +270 m that crosses ten cube faces; 16 x 900 sweeps cut to
+30 m.  Three variants of the node, through the C ABI, take the same sweeps in turn:
+
+  A  the static node: a 21 x 21 x 11 cube array that holds the whole map, loaded at once (lslam_loc_load);
+  B  the paged node: a 21 x 11 x 21 window that follows the sensor (lslam_pmap_open);
+  C  the paged node with lslam_pmap_stage called between sweeps at the next sweep's odometry position.
+
+Every repetition runs A, B, C one after the other on fresh nodes (alternating, so that a drift of the machine hits all three);
+the first repetition warms up and is dropped.  A sweep's time is the host clock around lslam_loc_process, which ends in the
+sweep's device wait; a staging call is timed on its own (it happens between sweeps).  Reported: median and worst ms per sweep for
+sweeps with and without a window step, ms per step against the cubes that entered, resident device bytes, time to first pose
+(create + open / load + first sweep).  The claim under test: a paged sweep WITHOUT a step costs no more than A's, the margin
+being A's own spread between repetitions.  Exits non-zero unless A, B and C give the same poses in every bit."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+F = np.float32
+
+CUBE, VALID = 50.0, 100.0
+WINDOW = (21, 11, 21)
+STATIC_DIMS, STATIC_ORIGIN = (21, 21, 11), (10, 10, 5)
+LEAVES = (1.0, 1.0)
+RANGE_CUT = 30.0
+
+
+def glo_idx(p, cube):
+    q = np.asarray(p, F)[:, :3] / F(cube)
+    return np.where(q >= 0, np.floor(q + F(0.5)), np.ceil(q - F(0.5))).astype(np.int64)
+
+
+def write_pcd(path, pts):
+    with open(path, "wb") as f:
+        f.write(("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\n"
+                 "COUNT 1 1 1 1\nWIDTH %d\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %d\nDATA binary\n" % (len(pts), len(pts))).encode())
+        f.write(np.ascontiguousarray(pts, F).tobytes())
+
+
+def write_map(directory, map_corner, map_surf):
+    """One PCD per (type, cube), input order kept inside a cube; index2.txt with global indices, index.txt with the static
+    array's.  -> files per type."""
+    count, n_files = 0, [0, 0]
+    with open(os.path.join(directory, "index2.txt"), "w") as f2, open(os.path.join(directory, "index.txt"), "w") as f1:
+        for t, cloud in enumerate((map_corner, map_surf)):
+            cloud = np.ascontiguousarray(cloud, F)[:, :4]
+            g = glo_idx(cloud, CUBE)
+            key = (g[:, 0] + 1000) * 4000000 + (g[:, 1] + 1000) * 2000 + (g[:, 2] + 1000)
+            order = np.argsort(key, kind="stable")
+            bounds = np.flatnonzero(np.diff(key[order])) + 1
+            for part in np.split(order, bounds):
+                i, j, k = (int(v) for v in g[part[0]])
+                write_pcd(os.path.join(directory, "%d.pcd" % count), cloud[part])
+                f2.write("%d %d %d %d %d %d\n" % (count, t, i, j, k, len(part)))
+                f1.write("%d %d %d %d %d %d\n" % (count, t, i + STATIC_ORIGIN[0], j + STATIC_ORIGIN[1], k + STATIC_ORIGIN[2], len(part)))
+                count += 1
+                n_files[t] += 1
+    return n_files
+
+
+def make_scene(synth, n_sweeps, half, sweep_cache=None):
+    """sweep_cache: an .npz the ray-cast sweeps are kept in between runs (the CPU ray caster takes seconds per sweep in a world
+    of this size; everything else is regenerated from its seeds)."""
+    world = synth.World(half_extent=half, wall_half=half - 5.0)
+    map_c, map_s = synth.make_map(world, 0.2, 0.4, seed=77)
+    xs = np.linspace(-(half - 30.0), half - 30.0, n_sweeps)
+    poses = [(0.01, -0.015, 0.05, float(x), 3.0 + 0.01 * float(x), 1.8) for x in xs]
+    sweeps = []
+    tag = np.asarray([n_sweeps, half, RANGE_CUT], np.float64)
+    if sweep_cache and os.path.exists(sweep_cache):
+        z = np.load(sweep_cache)
+        if np.array_equal(z["tag"], tag):
+            sweeps = [(z["c%d" % k], z["s%d" % k]) for k in range(n_sweeps)]
+    for k, gt in enumerate(poses if not sweeps else []):
+        c, s, _ = synth.make_scan(world, 16, 900, gt_pose=gt, seed=1234 + k)
+        c, s = np.ascontiguousarray(c, F), np.ascontiguousarray(s, F)
+        sweeps.append((c[np.linalg.norm(c[:, :3], axis=1) <= RANGE_CUT], s[np.linalg.norm(s[:, :3], axis=1) <= RANGE_CUT]))
+    if sweep_cache and not os.path.exists(sweep_cache):
+        arrays = dict(tag=tag)
+        for k, (c, s) in enumerate(sweeps):
+            arrays["c%d" % k], arrays["s%d" % k] = c, s
+        np.savez_compressed(sweep_cache, **arrays)
+    return dict(map_corner=map_c, map_surf=map_s, poses=poses, sweeps=sweeps, start=synth.perturb_pose(poses[0], dt=0.2, dr_deg=1.0))
+
+
+def run_variant(pkg, ctx, torch, variant, scene, directory):
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    t0 = time.perf_counter()
+    if variant == "A":
+        node = pkg.LaserLocalization(ctx, *STATIC_DIMS, map_filter_corner=LEAVES[0], map_filter_surf=LEAVES[1], cube_size=CUBE,
+                                     world_origin=STATIC_ORIGIN, lidar_valid_distance=VALID)
+        node.load_map(directory)
+    else:
+        node = pkg.LaserLocalization(ctx, *WINDOW, map_filter_corner=LEAVES[0], map_filter_surf=LEAVES[1], cube_size=CUBE,
+                                     lidar_valid_distance=VALID, dynamic_mode=True, files_directory=directory)
+    node.handle_initial_pose(ctx.pose_to_isometry(scene["start"]))
+    rows, poses, first_pose_ms = [], [], None
+    steps_before = 0
+    for k, (c, s) in enumerate(scene["sweeps"]):
+        stage_ms = 0.0
+        if variant == "C" and k > 0:
+            ts = time.perf_counter()
+            node.stage(np.asarray(scene["poses"][k][3:6], F))
+            stage_ms = (time.perf_counter() - ts) * 1e3
+        odom = ctx.pose_to_isometry(np.asarray(scene["poses"][k], F))
+        ts = time.perf_counter()
+        T = node.process(c, s, odom, 1_000_000_000 + k * 100_000_000)
+        ms = (time.perf_counter() - ts) * 1e3
+        if first_pose_ms is None:
+            first_pose_ms = (time.perf_counter() - t0) * 1e3
+        stepped, entered, read = False, 0, 0
+        if variant != "A":
+            info = node.window_info()
+            stepped = info["steps"] != steps_before
+            steps_before = info["steps"]
+            if stepped:
+                entered, read = sum(info["entered"]), info["files_read"]
+        poses.append(np.concatenate([T.reshape(16), np.zeros(3, F) if node.velocity is None else node.velocity, [node.last_flags, node.last_status]]).astype(F))
+        rows.append((k, ms, stage_ms, stepped, entered, read))
+    torch.cuda.synchronize()
+    resident = free0 - torch.cuda.mem_get_info()[0]
+    info = node.window_info() if variant != "A" else None
+    node.close()
+    return dict(rows=rows, poses=np.asarray(poses), first_pose_ms=first_pose_ms, resident=resident, info=info)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sweeps", type=int, default=91)
+    ap.add_argument("--half", type=float, default=300.0, help="half extent of the world [m]")
+    ap.add_argument("--reps", type=int, default=6, help="repetitions of A, B, C in turn; the first is dropped")
+    ap.add_argument("--out", default=None, help="also write the report here")
+    ap.add_argument("--sweep-cache", default=None, help=".npz that keeps the ray-cast sweeps between runs")
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        print("no GPU: this tool measures on the device and has no fall-back", file=sys.stderr)
+        return 2
+    pkg = importlib.import_module("the-cooper-mapper_amd")
+    synth = importlib.import_module("the-cooper-mapper_amd.synth")
+    scene = make_scene(synth, a.sweeps, a.half, a.sweep_cache)
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+    with tempfile.TemporaryDirectory() as d:
+        n_files = write_map(d, scene["map_corner"], scene["map_surf"])
+        xs = [p[3] for p in scene["poses"]]
+        faces = sum(1 for x0, x1 in zip(xs, xs[1:]) if glo_idx(np.asarray([[x0, 0, 0]]), CUBE)[0, 0] != glo_idx(np.asarray([[x1, 0, 0]]), CUBE)[0, 0])
+        say("paged localisation: %d sweeps over %.0f m, %d cube faces crossed; map %d corner + %d surf points in %d + %d files of %.0f m cubes; "
+            "window %s, static array %s; %d repetitions kept" % (a.sweeps, xs[-1] - xs[0], faces, len(scene["map_corner"]), len(scene["map_surf"]),
+                                                                   n_files[0], n_files[1], CUBE, WINDOW, STATIC_DIMS, a.reps - 1))
+        ctx = pkg.Context(0)
+        runs = {v: [] for v in "ABC"}
+        for rep in range(a.reps):
+            for v in "ABC":
+                r = run_variant(pkg, ctx, torch, v, scene, d)
+                if rep > 0:
+                    runs[v].append(r)
+        ctx.close()
+    same = all(np.array_equal(r["poses"].view(np.uint32), runs["A"][0]["poses"].view(np.uint32)) for v in "ABC" for r in runs[v])
+    say("poses, velocities, flags and statuses of A, B and C in every bit: %s" % ("EQUAL" if same else "DIFFERENT"))
+
+    def stats(v, pick):
+        per_rep = [np.asarray([row[1] for row in r["rows"][1:] if pick(row)]) for r in runs[v]]  # (sweep 0 is the first pose's)
+        per_rep = [x for x in per_rep if len(x)]
+        if not per_rep:
+            return None
+        med = [float(np.median(x)) for x in per_rep]
+        return dict(n=len(per_rep[0]), median=float(np.median(med)), med_lo=min(med), med_hi=max(med), worst=max(float(x.max()) for x in per_rep))
+    say()
+    say("| variant | sweeps | n | median ms (min .. max of the repetitions' medians) | worst ms |")
+    say("|---|---|---|---|---|")
+    table = {}
+    for v, label, pick in (("A", "all", lambda r: True), ("B", "without a step", lambda r: not r[3]), ("B", "with a step", lambda r: r[3]),
+                           ("C", "without a step", lambda r: not r[3]), ("C", "with a step", lambda r: r[3])):
+        st = stats(v, pick)
+        table[(v, label)] = st
+        if st:
+            say("| %s | %s | %d | %.3f (%.3f .. %.3f) | %.3f |" % (v, label, st["n"], st["median"], st["med_lo"], st["med_hi"], st["worst"]))
+    stage_all = np.asarray([row[2] for r in runs["C"] for row in r["rows"][1:]])
+    stage_step = np.asarray([row[2] for r in runs["C"] for row in r["rows"][1:] if row[3]])
+    say("| C | lslam_pmap_stage before a sweep without a step | %d | %.3f | %.3f |" %
+        (len(stage_all) - len(stage_step), float(np.median(stage_all)), float(np.max(stage_all))))
+    if len(stage_step):
+        say("| C | lslam_pmap_stage before a sweep with a step | %d | %.3f | %.3f |" %
+            (len(stage_step), float(np.median(stage_step)), float(np.max(stage_step))))
+    say()
+    say("| variant | time to first pose ms (median) | resident device bytes |")
+    say("|---|---|---|")
+    for v in "ABC":
+        say("| %s | %.1f | %d |" % (v, float(np.median([r["first_pose_ms"] for r in runs[v]])), int(np.median([r["resident"] for r in runs[v]]))))
+    say()
+    say("steps of B (last repetition): sweep, cubes entered, files read, sweep ms")
+    for row in runs["B"][-1]["rows"]:
+        if row[3]:
+            say("  sweep %3d: %4d cubes, %4d files, %8.3f ms  (%.4f ms per entering cube)" % (row[0], row[4], row[5], row[1], row[1] / max(row[4], 1)))
+    say("steps of C (last repetition): sweep, cubes entered, files read, sweep ms, the staging call before it ms")
+    for row in runs["C"][-1]["rows"]:
+        if row[3]:
+            say("  sweep %3d: %4d cubes, %4d files, %8.3f ms, staged in %8.3f ms" % (row[0], row[4], row[5], row[1], row[2]))
+    sa, sb = table[("A", "all")], table[("B", "without a step")]
+    spread = sa["med_hi"] - sa["med_lo"]
+    verdict = sb["median"] <= sa["median"] + spread
+    say()
+    say("claim: a paged sweep without a step costs no more than the static node's: B %.3f ms against A %.3f ms + A's spread %.3f ms: %s" %
+        (sb["median"], sa["median"], spread, "HOLDS" if verdict else "DOES NOT HOLD"))
+    say(json.dumps(dict(equal=bool(same), a_ms=sa["median"], b_no_step_ms=sb["median"], a_spread_ms=spread, claim_holds=bool(verdict))))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
