@@ -1184,6 +1184,92 @@ int lslam_pmap_window_info(lslam_loc *loc, lslam_loc_window_stats *out);
  * i - ox, j - oy, k - oz, so that a map saved by the mapping node can be opened paged.  No device is needed. */
 int lslam_index_convert(const char *in_path, int32_t ox, int32_t oy, int32_t oz, const char *out_path);
 
+/* ---- Survey-cloud feature map extractor (io_module/feature_extracter.cpp:43-130 over util/pcl_util.h:39-62,107-182 and
+ * util/voxel_grid_partition.hpp:80-330): a dense survey cloud -> the corner / surf cube map the localisation node loads.
+ * Per partition block: VoxelGrid with a minimum point count, radius-search PCA normals over the block, a K-nearest graph,
+ * region growing, the angle-gap boundary test, VoxelGrid again, the axis permutation (x, y, z) <- (y, z, x) and worldToCube.
+ * PCL is not part of the parity here: the yardstick is the numpy restatement tests/survey_map_ref.py, and where PCL's answer
+ * is version dependent or unspecified the choice is fixed by this library (DESIGN "Survey-cloud extractor").  In short:
+ *   - blocks in ascending partition cell, input order inside a block, processed one after another (device memory follows the
+ *     largest block); non-finite points dropped; the "leaf too small" guard of the partition gives an empty result;
+ *   - a neighbour of q is p with fp32 dx*dx + dy*dy + dz*dz < (float)((double)r * r); mean and covariance in fp64 over
+ *     (double)p - (double)q, summed in ascending (search-grid cell (z, y, x), index) order; the eigenvector of the smallest
+ *     eigenvalue by a fixed cyclic Jacobi iteration in fp64; flipped towards (0, 0, 0); curvature l0 / (l0 + l1 + l2); one
+ *     rounding to fp32.  Fewer than 3 neighbours: the normal is undefined, the point leaves the later stages (counted);
+ *   - neighbour lists: the K nearest by (fp32 squared distance, index), the point itself included;
+ *   - region growing as the min-ancestor fixpoint of label[j] = min(label[j], label[i]) over the edges i -> j
+ *     (j in i's list, fabsf(ni . nj) >= cosf-threshold), labels starting as (curvature, index) ranks;
+ *   - the largest angle gap in fp64 with Eigen's unitOrthogonal basis. */
+typedef struct lslam_survey lslam_survey;
+typedef struct lslam_survey_params {
+  double boundary_angle;         /* 3.14159 / 2.0 * 0.9 (the literal, not pi): a point is a boundary point iff its gap is larger */
+  float partition_leaf;          /* 50.0   voxelPartition */
+  int32_t partition_min_points;  /* 1000 */
+  float filter_leaf;             /* 0.05   voxelFilter of a block */
+  int32_t filter_min_points;     /* 3 */
+  float normal_radius;           /* 0.05   normalEstimate, search surface = the block */
+  int32_t knn_k;                 /* 60     RegionGrowing::setNumberOfNeighbours; 1 .. 64 */
+  float smoothness_angle;        /* (float)(3.0 / 180.0 * M_PI); the edge threshold is (float)cos((double)smoothness_angle) */
+  float curvature_threshold;     /* 1.0    above every curvature: each reached point grows on.  Values below 1/3 are refused */
+  int32_t cluster_min;           /* 50 */
+  int32_t cluster_max;           /* 1000000 */
+  float boundary_radius;         /* 0.1 */
+  float feature_leaf;            /* 0.2    voxelFilter of the planar and the boundary cloud */
+  int32_t feature_min_points;    /* 3 */
+  float cube_size;               /* 50.0   FeatureMap(21, 21, 21), setupWorldOrigin(10, 5, 10), setupWorldCubeSize(50.0) */
+  int32_t cube_dims[3];
+  int32_t cube_origin[3];
+  float knn_cell;                /* cell of the K-nearest search grid [m]; 0: 4 * filter_leaf.  Results do not depend on it */
+  int32_t reserved;
+} lslam_survey_params;
+typedef struct lslam_survey_stats {
+  int64_t points_in;           /* finite points of the cloud */
+  int64_t points_nonfinite;    /* dropped before the partition */
+  int64_t blocks_kept;         /* partition cells with at least partition_min_points points */
+  int64_t blocks_dropped;      /* occupied cells below it */
+  int64_t max_block_points;
+  int64_t filtered_points;     /* after the first filter, all blocks */
+  int64_t undefined_normals;   /* of those: fewer than 3 neighbours */
+  int64_t clusters_kept;       /* regions inside [cluster_min, cluster_max] */
+  int64_t clusters_dropped;
+  int64_t label_sweeps;        /* launches of the label sweep, all blocks (depends on scheduling: not part of the parity) */
+  int64_t planar_points;       /* before the second filter */
+  int64_t boundary_points;
+  int64_t n_corner;            /* the result: boundary points in the cubes */
+  int64_t n_surf;              /* ... planar points */
+} lslam_survey_stats;
+/* Writes every byte of *p (the reference's literals above). */
+void lslam_survey_default_params(lslam_survey_params *p);
+/* The whole extraction of a host cloud (x, y, z floats at the head of every stride_bytes record).  The result stays on the
+ * device in *out (which owns it; lslam_survey_destroy frees it; scratch of the call is freed before it returns).  An empty
+ * cloud and a cloud whose cells are all below the minimum give an empty result and LSLAM_OK. */
+int lslam_survey_extract(lslam_ctx *ctx, const void *cloud, size_t n, size_t stride_bytes, const lslam_survey_params *params,
+                         lslam_survey **out);
+/* The same from a PCD file, read by the reader of lslam_fmap_load (DATA ascii or binary; binary_compressed and a missing file
+ * are refused with LSLAM_ERR_INVALID, lslam_last_error says which). */
+int lslam_survey_extract_file(lslam_ctx *ctx, const char *pcd_path, const lslam_survey_params *params, lslam_survey **out);
+int lslam_survey_info(lslam_survey *sv, lslam_survey_stats *out);
+/* Both clouds {x, y, z, intensity = 0} in block order (a null buffer is skipped; cap in points, at least the stats' count). */
+int lslam_survey_get(lslam_survey *sv, float *corner_xyzi, size_t cap_corner, float *surf_xyzi, size_t cap_surf);
+/* saveCloudToFiles: directory/index.txt and <count>.pcd in the layout lslam_fmap_save writes, points of a cube in block order. */
+int lslam_survey_save(lslam_survey *sv, const char *directory);
+void lslam_survey_destroy(lslam_survey *sv);
+/* pcl::VoxelGrid with setMinimumPointsNumberPerVoxel(min_points): lslam_voxel_grid's arithmetic, voxels with fewer points
+ * give no output.  min_points = 1: bit for bit lslam_voxel_grid. */
+int lslam_voxel_grid_min(lslam_ctx *ctx, const void *cloud, size_t n, size_t stride_bytes, float leaf, int32_t min_points,
+                         float *out_xyzi, size_t cap, size_t *n_out);
+/* Stage taps (tests): each works on caller-supplied host arrays of packed {x, y, z, w} float records.
+ * normals: out_normal[q] = {nx, ny, nz, curvature} (NaN when undefined), out_count[q] = neighbours in radius. */
+int lslam_debug_survey_normals(lslam_ctx *ctx, const float *surface_xyzw, size_t n_surface, const float *query_xyzw, size_t n_query,
+                               float radius, float *out_normal, int32_t *out_count);
+/* out_lists[i * k + t]: the t-th nearest point of i (itself included), -1 past the cloud's size.  cell <= 0: chosen here. */
+int lslam_debug_survey_knn(lslam_ctx *ctx, const float *pts_xyzw, size_t n, int32_t k, float cell, int32_t *out_lists);
+/* normals_curv = {nx, ny, nz, curvature}; out_labels[i] = the index of the seed point whose region i joins; sweeps_out: launches. */
+int lslam_debug_survey_region(lslam_ctx *ctx, const float *normals_curv, size_t n, const int32_t *lists, int32_t k, float cos_threshold,
+                              int32_t *out_labels, int32_t *sweeps_out);
+int lslam_debug_survey_boundary(lslam_ctx *ctx, const float *pts_xyzw, const float *normals_xyzw, size_t n, float radius,
+                                double angle_threshold, uint8_t *out_flags, double *out_gaps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,8 @@ from .local_feature_map import LocalFeatureMap
 from .pipeline import DeviceLaserOdometry, LaserOdometry, LaserMapping, LaserMappingLocal
 from .laser_localization import LaserLocalization
 from .dynamic_feature_map import DynamicFeatureMap
+from . import survey_map
+from .survey_map import SurveyMap
 
-__all__ = ["Comm", "Context", "ScanMatch", "PoseGraph", "FeatureMap", "voxel_grid", "voxel_grid2", "scan_registration", "MultiScanRegistration", "OrganisedScanRegistration", "KeyFrame", "Loop", "LoopDetector", "Graph", "KeyframeUpdater", "LaserOdometry", "DeviceLaserOdometry", "LaserMapping", "LaserMappingLocal", "LaserLocalization", "DynamicFeatureMap", "LocalFeatureMap", "LslamError", "LslamOpts", "LslamStats", "LslamMapInfo", "LslamStereoCam",
+__all__ = ["Comm", "Context", "ScanMatch", "PoseGraph", "FeatureMap", "voxel_grid", "voxel_grid2", "scan_registration", "MultiScanRegistration", "OrganisedScanRegistration", "KeyFrame", "Loop", "LoopDetector", "Graph", "KeyframeUpdater", "LaserOdometry", "DeviceLaserOdometry", "LaserMapping", "LaserMappingLocal", "LaserLocalization", "DynamicFeatureMap", "LocalFeatureMap", "survey_map", "SurveyMap", "LslamError", "LslamOpts", "LslamStats", "LslamMapInfo", "LslamStereoCam",
            "Status", "lib_path", "load_library", "build_library"]

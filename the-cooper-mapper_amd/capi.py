@@ -170,6 +170,23 @@ class LslamLocWindowStats(C.Structure):
                 ("arena_nodes_used", C.c_uint64), ("arena_nodes_capacity", C.c_uint64), ("active_cubes", C.c_uint64)]
 
 
+class LslamSurveyParams(C.Structure):
+    """lslam_survey_params (include/lslam_c.h)."""
+    _fields_ = [("boundary_angle", C.c_double), ("partition_leaf", C.c_float), ("partition_min_points", C.c_int32),
+                ("filter_leaf", C.c_float), ("filter_min_points", C.c_int32), ("normal_radius", C.c_float), ("knn_k", C.c_int32),
+                ("smoothness_angle", C.c_float), ("curvature_threshold", C.c_float), ("cluster_min", C.c_int32),
+                ("cluster_max", C.c_int32), ("boundary_radius", C.c_float), ("feature_leaf", C.c_float),
+                ("feature_min_points", C.c_int32), ("cube_size", C.c_float), ("cube_dims", C.c_int32 * 3),
+                ("cube_origin", C.c_int32 * 3), ("knn_cell", C.c_float), ("reserved", C.c_int32)]
+
+
+class LslamSurveyStats(C.Structure):
+    """lslam_survey_stats (include/lslam_c.h)."""
+    _fields_ = [(k, C.c_int64) for k in ("points_in", "points_nonfinite", "blocks_kept", "blocks_dropped", "max_block_points",
+                                         "filtered_points", "undefined_normals", "clusters_kept", "clusters_dropped",
+                                         "label_sweeps", "planar_points", "boundary_points", "n_corner", "n_surf")]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLGATHERV_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32)
 c_double_p = C.POINTER(C.c_double)
@@ -362,6 +379,23 @@ SYMBOLS = {
                                                 C.POINTER(C.c_size_t)]),
     "lslam_pmap_window_info": (C.c_int, [C.c_void_p, C.POINTER(LslamLocWindowStats)]),
     "lslam_index_convert": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p]),
+    "lslam_survey_default_params": (None, [C.POINTER(LslamSurveyParams)]),
+    "lslam_survey_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(LslamSurveyParams),
+                                       C.POINTER(C.c_void_p)]),
+    "lslam_survey_extract_file": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(LslamSurveyParams), C.POINTER(C.c_void_p)]),
+    "lslam_survey_info": (C.c_int, [C.c_void_p, C.POINTER(LslamSurveyStats)]),
+    "lslam_survey_get": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p, C.c_size_t]),
+    "lslam_survey_save": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "lslam_survey_destroy": (None, [C.c_void_p]),
+    "lslam_voxel_grid_min": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, C.c_int32, c_float_p,
+                                       C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lslam_debug_survey_normals": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p, C.c_size_t, C.c_float, c_float_p,
+                                             c_int32_p]),
+    "lslam_debug_survey_knn": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, C.c_int32, C.c_float, c_int32_p]),
+    "lslam_debug_survey_region": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_int32_p, C.c_int32, C.c_float, c_int32_p,
+                                            c_int32_p]),
+    "lslam_debug_survey_boundary": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t, C.c_float, C.c_double, c_uint8_p,
+                                              C.POINTER(C.c_double)]),
     "lslam_pg_save_g2o": (C.c_int, [C.c_void_p, C.c_char_p]),
     "lslam_g2o_read": (C.c_int, [C.c_char_p, c_int32_p, c_double_p, c_int32_p, c_int32_p, c_double_p, c_double_p,
                                  c_int32_p]),

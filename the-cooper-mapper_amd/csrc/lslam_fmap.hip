@@ -2158,5 +2158,7 @@ int fmap_view(lslam_fmap *fm, FmapView *out) {
 
 // the PCD reader of lslam_fmap_load for the paged window of lslam_loc.hip, which reads single cube files
 bool fmap_read_pcd(const char *path, std::vector<float4> &out, std::string &err) { return read_pcd(std::string(path), out, err); }
+// ... and the cube-file writer of lslam_fmap_save for lslam_survey.hip, which saves a map it extracted in the same layout
+bool fmap_write_pcd(const char *path, const float4 *p, size_t n) { return write_pcd_binary(std::string(path), p, n); }
 
 }  // namespace lslam

@@ -508,6 +508,7 @@ int fmap_clear(lslam_fmap *fm);
 int fmap_copy(lslam_fmap *dst, lslam_fmap *src);
 int fmap_view(lslam_fmap *fm, FmapView *out);
 bool fmap_read_pcd(const char *path, std::vector<float4> &out, std::string &err);  // x y z intensity of an ascii or binary PCD
+bool fmap_write_pcd(const char *path, const float4 *p, size_t n);  // one cube file as lslam_fmap_save writes it
 
 // lslam_fmap.hip: pcl::VoxelGrid of a window whose owner keeps its points in voxel-key order (see there)
 struct WindowFilter;  // the filter's scratch, owned by the caller
