@@ -648,6 +648,31 @@ int lslam_odom_last_view(lslam_odom *od, const float **last_corner, size_t *n_co
  * search launch four words -- 10 ns ticks, candidates looked at for the nearest neighbour, for the ring categories, bit 0 / 1 a
  * coarse-level pass in the former / the latter.  Returns the number of queries copied (0: tap off). */
 int lslam_debug_odom_search(lslam_odom *od, uint32_t *out, size_t cap_queries);
+/* Parity tap: ONE iteration of the loop of :328-647 -- the odometry counterpart of lslam_sweep_ex.  The sharp / flat lists of
+ * fs are matched against the last clouds the node holds (after at least one lslam_odom_process), from `pose`, as iteration
+ * `iter` of the loop (iter decides the weights of feature_utils.h; the correspondences are refreshed when iter % 5 == 0 or
+ * refresh != 0 -- without a refresh the ones the previous call of this tap left for the same clouds are used).
+ *   path 0  the launch loop's step: search (if refreshing), residual pass, solve
+ *   path 1  the persistent kernel: search, then one generation -- iter must be 4, 9, ... or max_iterations - 1, so that the
+ *           kernel leaves after one iteration by its own rule; at most 64 blocks; no per-point taps
+ * The launch arguments are the ones lslam_odom_process builds.  Neither the last clouds nor the node's _transform change.
+ * Any output but `out` may be NULL.  n = sharp + flat queries, sharp first:
+ *   ind_out[3][n]   closest / second / third point (-1: none)      sel_out[n][3]   pointSel of the residual pass
+ *   coeff_out[n][4] the coefficients as the row takes them (zeros where no second / third point)
+ *   kept_out[n]     1: the row was kept                            sums_out[32]    the reduced sums the solve consumed
+ * Returns LSLAM_TOO_FEW_REF when the node would not match (:337). */
+typedef struct lslam_odom_step {
+  float pose[6], x[6];  /* after the solve */
+  int32_t n_rows, n_line, n_plane, degenerate, converged, done, loop_iter, solves;
+  int32_t tie;        /* a nearest neighbour needed nanoflann's visit order */
+  int32_t refreshed;  /* the search ran */
+} lslam_odom_step;
+int lslam_debug_odom_step(lslam_odom *od, lslam_fset *fs, const float pose[6], int32_t iter, int32_t refresh, int32_t path,
+                          int32_t *ind_out, float *sel_out, float *coeff_out, uint8_t *kept_out, double sums_out[32],
+                          lslam_odom_step *out);
+/* How many matches of the node ran their loop in the persistent kernel and how many by one launch per step (more than 64
+ * blocks of queries, LSLAM_ODOM_PERSISTENT=0, or after an exchange gave up).  Either pointer may be NULL. */
+int lslam_debug_odom_runs(const lslam_odom *od, uint64_t *persistent_runs, uint64_t *launch_runs);
 /* Start again from the first sweep (keeps the buffers). */
 int lslam_odom_reset(lslam_odom *od);
 

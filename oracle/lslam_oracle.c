@@ -1508,6 +1508,92 @@ static int odom_surf_coeff(const float *A, const float *B, const float *C, const
   return ((double)weight > 0.1 && distance != 0);
 }
 
+/* LaserOdometry.cpp:358-408 (sharp) / :424-483 (flat): the correspondences of one de-skewed query against a last cloud --
+ * nearestKSearch(pointSel, 1) inside the 5 m gate, then the two walks over the ring window from the closest point.
+ * n_queries is the walk's upper bound (quirk Q5: the QUERY count, :370 / :434).  out = {closest, min2, min3}, -1: none
+ * (min3 stays -1 for a sharp query). */
+static void odom_corr_one(const oracle_kdtree *tree, const float *cloud, size_t n_cloud, size_t stride, const float sel[3],
+                          size_t n_queries, int is_flat, int out[3]) {
+  int32_t idx;
+  float d2;
+  oracle_kdtree_knn(tree, sel, 1, &idx, &d2);
+  int closest = -1, min2 = -1, min3 = -1;
+  if (d2 < 25) {
+    closest = idx;
+    int scan = (int)cloud[(size_t)closest * stride + 3];
+    float minD2 = 25, minD3 = 25;
+    /* quirk Q5: the loop bound is the QUERY count; never read past the cloud */
+    for (int j = closest + 1; j < (int)n_queries && j < (int)n_cloud; j++) {
+      const int ring = (int)cloud[(size_t)j * stride + 3];
+      if (ring > scan + 2.5) break;
+      float d = sq_diff(cloud + (size_t)j * stride, sel);
+      if (!is_flat) {
+        if (ring > scan) {
+          if (d < minD2) { minD2 = d; min2 = j; }
+        }
+      } else if (ring <= scan) {
+        if (d < minD2) { minD2 = d; min2 = j; }
+      } else {
+        if (d < minD3) { minD3 = d; min3 = j; }
+      }
+    }
+    for (int j = closest - 1; j >= 0; j--) {
+      const int ring = (int)cloud[(size_t)j * stride + 3];
+      if (ring < scan - 2.5) break;
+      float d = sq_diff(cloud + (size_t)j * stride, sel);
+      if (!is_flat) {
+        if (ring < scan) {
+          if (d < minD2) { minD2 = d; min2 = j; }
+        }
+      } else if (ring >= scan) {
+        if (d < minD2) { minD2 = d; min2 = j; }
+      } else {
+        if (d < minD3) { minD3 = d; min3 = j; }
+      }
+    }
+  }
+  out[0] = closest;
+  out[1] = min2;
+  out[2] = min3;
+}
+
+/* Parity taps of the pieces above (tests/odom_ref.py holds them to independent references). */
+void oracle_odom_to_start(const float pose[6], const float *pts, size_t n, size_t stride, float *sel_out) {
+  for (size_t i = 0; i < n; ++i) odom_transform_to_start(pose, pts + i * stride, sel_out + 3 * i);
+}
+
+/* ind_out[3][n]: the correspondences of n de-skewed queries sel[n][3] against `cloud`; n_queries: the Q5 bound. */
+void oracle_odom_corr(const float *cloud, size_t n_cloud, size_t stride, const float *sel, size_t n, size_t n_queries,
+                      int is_flat, int32_t *ind_out) {
+  oracle_kdtree *tree = oracle_kdtree_build(cloud, n_cloud, stride);
+  for (size_t i = 0; i < n; ++i) {
+    int o[3];
+    odom_corr_one(tree, cloud, n_cloud, stride, sel + 3 * i, n_queries, is_flat, o);
+    ind_out[i] = o[0];
+    ind_out[n + i] = o[1];
+    ind_out[2 * n + i] = o[2];
+  }
+  oracle_kdtree_free(tree);
+}
+
+/* coeff_out[n][4], kept_out[n]: odom_corner_coeff (is_flat 0; ind[2][n]) / odom_surf_coeff (ind[3][n]) per query at sel[n][3];
+ * a query without its second (third) point gets zeros and kept 0. */
+void oracle_odom_coeff(const float *cloud, size_t stride, const float *sel, size_t n, const int32_t *ind, int is_flat,
+                       int iter, float *coeff_out, uint8_t *kept_out) {
+  for (size_t i = 0; i < n; ++i) {
+    float *c = coeff_out + 4 * i;
+    c[0] = c[1] = c[2] = c[3] = 0.0f;
+    kept_out[i] = 0;
+    const int32_t i1 = ind[i], i2 = ind[n + i], i3 = is_flat ? ind[2 * n + i] : 0;
+    if (i1 < 0 || i2 < 0 || i3 < 0) continue;
+    if (!is_flat)
+      kept_out[i] = (uint8_t)odom_corner_coeff(cloud + (size_t)i1 * stride, cloud + (size_t)i2 * stride, sel + 3 * i, iter, c);
+    else
+      kept_out[i] = (uint8_t)odom_surf_coeff(cloud + (size_t)i1 * stride, cloud + (size_t)i2 * stride,
+                                             cloud + (size_t)i3 * stride, sel + 3 * i, iter, c);
+  }
+}
+
 int oracle_odometry_match(const float *lc, size_t n_lc, const float *ls, size_t n_ls, const float *sharp,
                           size_t n_sharp, const float *flat, size_t n_flat, size_t stride, float pose[6],
                           const oracle_odom_opts *opts, oracle_stats *st) {
@@ -1534,32 +1620,10 @@ int oracle_odometry_match(const float *lc, size_t n_lc, const float *ls, size_t 
       float sel[3];
       odom_transform_to_start(pose, pi, sel);
       if (iter % 5 == 0) { /* :358-408 */
-        int32_t idx;
-        float d2;
-        oracle_kdtree_knn(tc, sel, 1, &idx, &d2);
-        int closest = -1, min2 = -1;
-        if (d2 < 25) {
-          closest = idx;
-          int scan = (int)lc[(size_t)closest * stride + 3];
-          float minD2 = 25;
-          /* quirk Q5: the loop bound is the QUERY count (:370); never read past the cloud */
-          for (int j = closest + 1; j < (int)n_sharp && j < (int)n_lc; j++) {
-            if ((int)lc[(size_t)j * stride + 3] > scan + 2.5) break;
-            float d = sq_diff(lc + (size_t)j * stride, sel);
-            if ((int)lc[(size_t)j * stride + 3] > scan) {
-              if (d < minD2) { minD2 = d; min2 = j; }
-            }
-          }
-          for (int j = closest - 1; j >= 0; j--) {
-            if ((int)lc[(size_t)j * stride + 3] < scan - 2.5) break;
-            float d = sq_diff(lc + (size_t)j * stride, sel);
-            if ((int)lc[(size_t)j * stride + 3] < scan) {
-              if (d < minD2) { minD2 = d; min2 = j; }
-            }
-          }
-        }
-        c1[i] = closest;
-        c2[i] = min2;
+        int o[3];
+        odom_corr_one(tc, lc, n_lc, stride, sel, n_sharp, 0, o);
+        c1[i] = o[0];
+        c2[i] = o[1];
       }
       if (c2[i] >= 0) { /* :409-418 */
         float coeff[4];
@@ -1579,36 +1643,11 @@ int oracle_odometry_match(const float *lc, size_t n_lc, const float *ls, size_t 
       float sel[3];
       odom_transform_to_start(pose, pi, sel);
       if (iter % 5 == 0) { /* :424-483 */
-        int32_t idx;
-        float d2;
-        oracle_kdtree_knn(ts, sel, 1, &idx, &d2);
-        int closest = -1, min2 = -1, min3 = -1;
-        if (d2 < 25) {
-          closest = idx;
-          int scan = (int)ls[(size_t)closest * stride + 3];
-          float minD2 = 25, minD3 = 25;
-          for (int j = closest + 1; j < (int)n_flat && j < (int)n_ls; j++) { /* Q5: :434 */
-            if ((int)ls[(size_t)j * stride + 3] > scan + 2.5) break;
-            float d = sq_diff(ls + (size_t)j * stride, sel);
-            if ((int)ls[(size_t)j * stride + 3] <= scan) {
-              if (d < minD2) { minD2 = d; min2 = j; }
-            } else {
-              if (d < minD3) { minD3 = d; min3 = j; }
-            }
-          }
-          for (int j = closest - 1; j >= 0; j--) {
-            if ((int)ls[(size_t)j * stride + 3] < scan - 2.5) break;
-            float d = sq_diff(ls + (size_t)j * stride, sel);
-            if ((int)ls[(size_t)j * stride + 3] >= scan) {
-              if (d < minD2) { minD2 = d; min2 = j; }
-            } else {
-              if (d < minD3) { minD3 = d; min3 = j; }
-            }
-          }
-        }
-        s1[i] = closest;
-        s2[i] = min2;
-        s3[i] = min3;
+        int o[3];
+        odom_corr_one(ts, ls, n_ls, stride, sel, n_flat, 1, o);
+        s1[i] = o[0];
+        s2[i] = o[1];
+        s3[i] = o[2];
       }
       if (s2[i] >= 0 && s3[i] >= 0) { /* :485-496 */
         float coeff[4];

@@ -185,6 +185,18 @@ int oracle_odometry_match(const float *last_corner, size_t n_lc, const float *la
 /* LaserOdometry::transformToEnd (odometry/LaserOdometry.cpp:156-168): cloud {x,y,z,intensity}
  * in place. */
 void oracle_transform_to_end(float *cloud, size_t n, size_t stride_floats, const float pose[6]);
+/* Taps of the pieces oracle_odometry_match is made of (it calls the same functions):
+ *   oracle_odom_to_start  transformToStart (:135-142) of n points {x,y,z,intensity,...} -> sel_out[n][3]
+ *   oracle_odom_corr      :358-408 (is_flat 0) / :424-483 (1) for n de-skewed queries sel[n][3] against `cloud`;
+ *                         n_queries is the walks' upper bound (quirk Q5) -> ind_out[3][n] {closest, second, third}, -1: none
+ *   oracle_odom_coeff     getCornerFeatureCoefficients / getSurfaceFeatureCoefficients of iteration `iter` at sel[n][3] and
+ *                         ind[3][n] (the third row is not read for is_flat 0) -> coeff_out[n][4], kept_out[n]; zeros and 0
+ *                         where a point is missing */
+void oracle_odom_to_start(const float pose[6], const float *pts, size_t n, size_t stride, float *sel_out);
+void oracle_odom_corr(const float *cloud, size_t n_cloud, size_t stride, const float *sel, size_t n, size_t n_queries,
+                      int is_flat, int32_t *ind_out);
+void oracle_odom_coeff(const float *cloud, size_t stride, const float *sel, size_t n, const int32_t *ind, int is_flat,
+                       int iter, float *coeff_out, uint8_t *kept_out);
 
 /* One GN solve step given sums (ScanMatch.cpp:206-260).  iter==0 computes the
  * degeneracy projector into matP/degenerate (in/out state). Returns converged. */

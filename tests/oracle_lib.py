@@ -163,6 +163,13 @@ class Oracle:
                                             c_float_p, C.c_size_t, C.c_size_t, c_float_p,
                                             C.POINTER(OracleOdomOpts), C.POINTER(OracleStats)]
         L.oracle_transform_to_end.argtypes = [c_float_p, C.c_size_t, C.c_size_t, c_float_p]
+        L.oracle_odom_to_start.restype = None
+        L.oracle_odom_to_start.argtypes = [c_float_p, c_float_p, C.c_size_t, C.c_size_t, c_float_p]
+        L.oracle_odom_corr.restype = None
+        L.oracle_odom_corr.argtypes = [c_float_p, C.c_size_t, C.c_size_t, c_float_p, C.c_size_t, C.c_size_t, C.c_int, c_int32_p]
+        L.oracle_odom_coeff.restype = None
+        L.oracle_odom_coeff.argtypes = [c_float_p, C.c_size_t, c_float_p, C.c_size_t, c_int32_p, C.c_int, C.c_int, c_float_p,
+                                        c_uint8_p]
         L.oracle_gn_step.restype = C.c_int
         L.oracle_gn_step.argtypes = [c_float_p, c_float_p, C.c_int, c_float_p, c_float_p,
                                      C.POINTER(C.c_int), C.c_float, C.c_float, C.c_float,
@@ -432,6 +439,35 @@ class Oracle:
         n = self.lib.oracle_odometry_match(_fp(lc), len(lc), _fp(ls), len(ls), _fp(sh), len(sh), _fp(fl), len(fl),
                                            s, _fp(pose), C.byref(op), C.byref(st))
         return n, pose, st
+
+    def odom_to_start(self, pose, pts):
+        """transformToStart (:135-142) of every point -> (n, 3) float32."""
+        a, s = as_cloud(pts)
+        assert s >= 4
+        p = np.ascontiguousarray(pose, np.float32).reshape(6)
+        out = np.zeros((len(a), 3), np.float32)
+        self.lib.oracle_odom_to_start(_fp(p), _fp(a), len(a), s, _fp(out))
+        return out
+
+    def odom_corr(self, cloud, sel, n_queries, is_flat):
+        """The correspondences of :357-483 for the de-skewed queries sel (n, 3) -> (3, n) int32."""
+        a, s = as_cloud(cloud)
+        assert s >= 4
+        q = np.ascontiguousarray(sel, np.float32).reshape(-1, 3)
+        out = np.full((3, len(q)), -1, np.int32)
+        self.lib.oracle_odom_corr(_fp(a), len(a), s, _fp(q), len(q), int(n_queries), int(bool(is_flat)), _ip(out))
+        return out
+
+    def odom_coeff(self, cloud, sel, ind, is_flat, it):
+        """The coefficients of iteration `it` at sel (n, 3) and ind (3, n) -> coeff (n, 4) float32, kept (n,) bool."""
+        a, s = as_cloud(cloud)
+        q = np.ascontiguousarray(sel, np.float32).reshape(-1, 3)
+        ind = np.ascontiguousarray(ind, np.int32).reshape(3, len(q))
+        coeff = np.zeros((len(q), 4), np.float32)
+        kept = np.zeros(len(q), np.uint8)
+        self.lib.oracle_odom_coeff(_fp(a), s, _fp(q), len(q), _ip(ind), int(bool(is_flat)), int(it), _fp(coeff),
+                                   kept.ctypes.data_as(c_uint8_p))
+        return coeff, kept.astype(bool)
 
     def transform_to_end(self, cloud, pose):
         a = np.array(cloud, dtype=np.float32, order="C")

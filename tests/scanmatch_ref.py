@@ -103,14 +103,20 @@ def sums64(J, b, keep, Jh=None, bh=None, variant=None):
     return S, M
 
 
-def reference_sums(pose32, q, coeff, flags, variant=None):
+def reference_sums(pose32, q, coeff, flags=None, variant=None, keep=None, b=None):
     """(S[27], u[27]) of one sweep from its taps: q (n, >=3) the scan points in tap order (corner then surf), coeff (n, 4)
-    and flags (n,) the tap's; kept rows are those with flags & 4."""
+    and flags (n,) the tap's; kept rows are those with flags & 4.  keep (n,) bool: the kept rows given directly (a tap
+    without flag bits).  b (n,): the right-hand side where it is not -coeff[3] (variant B scales it, tests/odom_ref.py); its
+    majorant is |b|."""
     rv = variant if variant in ROW_VARIANTS else None
     sv = variant if variant in SUM_VARIANTS else None
-    J, b = rows64(pose32, q, coeff, rv)
+    J, b0 = rows64(pose32, q, coeff, rv)
     Jh, bh = majorant(pose32, q, coeff)
-    S, M = sums64(J, b, (np.asarray(flags) & 4) != 0, Jh, bh, sv)
+    if b is not None:
+        b0 = np.asarray(b, np.float64)
+        bh = np.abs(b0)
+    keep = (np.asarray(flags) & 4) != 0 if keep is None else np.asarray(keep, bool)
+    S, M = sums64(J, b0, keep, Jh, bh, sv)
     return S, EPS32 * M
 
 
@@ -124,9 +130,10 @@ def units(got, S, u):
     return out
 
 
-def rows32_pairwise_sums(pose32, q, coeff, flags):
+def rows32_pairwise_sums(pose32, q, coeff, flags=None, keep=None, b=None):
     """Floor (a): the same formula in numpy float32 (float32 sin/cos, float32 rows and products), summed with numpy's pairwise
-    float32 sum -> S32[27].  What a careful fp32 implementation gives; reference side only."""
+    float32 sum -> S32[27].  What a careful fp32 implementation gives; reference side only.  keep / b as in reference_sums
+    (b float32)."""
     a = np.asarray(pose32, np.float32)
     sc = np.array([np.sin(a[0]), np.cos(a[0]), np.sin(a[1]), np.cos(a[1]), np.sin(a[2]), np.cos(a[2])], np.float32)
     q = np.asarray(q, np.float32)[:, :3]
@@ -144,8 +151,8 @@ def rows32_pairwise_sums(pose32, q, coeff, flags):
            + (crz * cry * px + (crz * sry * srx - srz * crx) * py + crz * sry * crx + srz * srx * pz) * cy)
     J = np.stack([arx, ary, arz, cx, cy, cz], 1)
     assert J.dtype == np.float32
-    keep = (np.asarray(flags) & 4) != 0
-    J, b = J[keep], -c[keep, 3]
+    keep = (np.asarray(flags) & 4) != 0 if keep is None else np.asarray(keep, bool)
+    J, b = J[keep], (-c[keep, 3] if b is None else np.asarray(b, np.float32)[keep])
     S = np.zeros(27, np.float32)
     for k, (i, j) in enumerate(PAIRS):
         S[k] = np.sum(J[:, i] * J[:, j], dtype=np.float32)

@@ -72,14 +72,37 @@ class OracleChain:
         return new
 
 
-def test_chain_through_a_velocity_reversal(pkg, ctx, oracle, synth, small_problem):
+class _DeviceOdometry:
+    """The device-resident node (the one bench.py times) behind the host-pointer node's interface: a sweep's host lists go up
+    into a feature set, lslam_odom_process runs on it."""
+
+    def __init__(self, pkg, ctx):
+        self.node = pkg.DeviceLaserOdometry(ctx)
+        self.fs = pkg.scan_registration.FeatureSet(ctx)
+
+    def process(self, sharp, less_sharp, flat, less_flat):
+        T = self.node.process(self.fs.upload(sharp, less_sharp, flat, less_flat))
+        self.last_stats, self.last_corner, self.last_surf = self.node.last_stats, self.node.last_corner, self.node.last_surf
+        return T
+
+    def close(self):
+        self.node.close()
+        self.fs.close()
+
+
+def _odometry_node(pkg, ctx, kind):
+    return pkg.LaserOdometry(ctx) if kind == "host" else _DeviceOdometry(pkg, ctx)
+
+
+@pytest.mark.parametrize("node", ["host", "device"])
+def test_chain_through_a_velocity_reversal(pkg, ctx, oracle, synth, small_problem, node):
     """The same chain over sweeps that go out and come back (0 1 2 3 2 1 0): at the turn the odometry's
     initial guess (the previous sweep's motion, LaserOdometry.cpp:288-326) points the wrong way by 0.8 m,
     so its Gauss-Newton loop starts far from the answer and runs long.  Device and oracle chains must stay
     together through that as well (the paths a smooth drive never takes)."""
     world = small_problem["world"]
     dims = (21, 21, 11)
-    odo = pkg.LaserOdometry(ctx)
+    odo = _odometry_node(pkg, ctx, node)
     mapper = pkg.LaserMapping(ctx, cube_dims=dims)
     chain = OracleChain(oracle, ctx, dims)
     sr = pkg.scan_registration
@@ -102,9 +125,12 @@ def test_chain_through_a_velocity_reversal(pkg, ctx, oracle, synth, small_proble
         assert np.abs(M_g - M_o).max() <= 2e-3, (step, np.abs(M_g - M_o).max())
     assert max(iters) == 25  # some loops run to the iteration limit (LaserOdometry.cpp: 25) without converging
     mapper.feature_map.close()
+    if node == "device":
+        odo.close()
 
 
-def test_registration_to_mapping_chain(pkg, ctx, oracle, synth, small_problem):
+@pytest.mark.parametrize("node", ["host", "device"])
+def test_registration_to_mapping_chain(pkg, ctx, oracle, synth, small_problem, node):
     """Five consecutive VLP-16 sweeps of a drive through the synthetic world, raw driver clouds in:
     the device chain and the oracle chain agree on every intermediate product (feature clouds bit for
     bit) and on the odometry and map poses to 1e-4 m (the chain passes through per-point sin/cos and
@@ -112,7 +138,7 @@ def test_registration_to_mapping_chain(pkg, ctx, oracle, synth, small_problem):
     from test_oracle_features import _raw_sweep  # noqa: F401  (same raw-sweep construction)
     world = small_problem["world"]
     dims = (21, 21, 11)
-    odo = pkg.LaserOdometry(ctx)
+    odo = _odometry_node(pkg, ctx, node)
     mapper = pkg.LaserMapping(ctx, cube_dims=dims)
     chain = OracleChain(oracle, ctx, dims)
     sr = pkg.scan_registration
@@ -145,6 +171,8 @@ def test_registration_to_mapping_chain(pkg, ctx, oracle, synth, small_problem):
     assert abs(np.linalg.norm(M_g[:3, 3]) - np.hypot(1.6, 0.6)) < 0.1
     print("chain worst |device - oracle| = %.3g (bar %.0e)" % (worst, CHAIN_TOL))
     mapper.feature_map.close()
+    if node == "device":
+        odo.close()
 
 
 def test_laser_mapping_default_grid(pkg, ctx, oracle, synth, small_problem):

@@ -129,6 +129,13 @@ class LslamOdomStats(C.Structure):
                 ("sweeps", C.c_uint64), ("n_last_corner", C.c_size_t), ("n_last_surf", C.c_size_t)]
 
 
+class LslamOdomStep(C.Structure):
+    """lslam_odom_step (include/lslam_c.h)."""
+    _fields_ = [("pose", C.c_float * 6), ("x", C.c_float * 6), ("n_rows", C.c_int32), ("n_line", C.c_int32), ("n_plane", C.c_int32),
+                ("degenerate", C.c_int32), ("converged", C.c_int32), ("done", C.c_int32), ("loop_iter", C.c_int32),
+                ("solves", C.c_int32), ("tie", C.c_int32), ("refreshed", C.c_int32)]
+
+
 class LslamOregStats(C.Structure):
     """lslam_oreg_stats (include/lslam_c.h)."""
     _fields_ = [("sweeps", C.c_uint64), ("n_cells", C.c_size_t), ("n_points", C.c_size_t), ("imu_states", C.c_int32),
@@ -328,6 +335,9 @@ SYMBOLS = {
     "lslam_odom_last_clouds": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p, C.c_size_t]),
     "lslam_odom_reset": (C.c_int, [C.c_void_p]),
     "lslam_debug_odom_search": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t]),
+    "lslam_debug_odom_step": (C.c_int, [C.c_void_p, C.c_void_p, c_float_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_float_p,
+                                        c_float_p, C.POINTER(C.c_uint8), c_double_p, C.POINTER(LslamOdomStep)]),
+    "lslam_debug_odom_runs": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lslam_odom_set_publish": (C.c_int, [C.c_void_p, C.c_int32]),
     "lslam_odom_last_view": (C.c_int, [C.c_void_p, C.POINTER(c_float_p), C.POINTER(C.c_size_t), C.POINTER(c_float_p),
                                        C.POINTER(C.c_size_t)]),

@@ -282,6 +282,8 @@ struct OdomArgs {
                                 // it and the de-skewed query; 2: cached correspondences only
   const GNState *state;
   float *partials;
+  float4 *coeff;                // (or null) parity tap of the residual pass: per query {coeff[0..3]} as the row takes them, with
+                                // sel[] = {pointSel, kept ? 1 : 0} of THIS pass beside it (lslam_debug_odom_step)
 };
 hipError_t launch_odom_sweep(const OdomArgs &a, hipStream_t s);
 hipError_t launch_odom_window(const OdomArgs &a, hipStream_t s);

@@ -1946,6 +1946,11 @@ __global__ __launch_bounds__(256, 2) void odom_sweep_kernel(OdomArgs a) {
       rb = (float)(-0.05 * (double)coeff[3]);  // :575
       kept = 1.0f;
     }
+    if (a.coeff) {  // parity tap (uniform): what this pass saw, zeros where no coefficient was formed
+      const bool fit = is_flat ? (i2 >= 0 && i3 >= 0) : i2 >= 0;
+      a.sel[qi] = make_float4(sel[0], sel[1], sel[2], kept);
+      a.coeff[qi] = fit ? make_float4(coeff[0], coeff[1], coeff[2], coeff[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
   }
   if (a.mode == 1) return;  // correspondence refresh only; the residual pass follows as its own launch
   float v[NCOL];

@@ -835,6 +835,8 @@ struct lslam_odom {
   DevBuf<uint32_t> dbg;  // LSLAM_ODOM_SEARCH_TAP=1 (debug hook): per-query profile of the last search launch (lslam_debug_odom_search)
   bool dbg_on = false;
   size_t dbg_n = 0;
+  DevBuf<float4> tap_sel, tap_coeff;  // lslam_debug_odom_step
+  uint64_t tap_ind_key[3] = {~0ull, 0, 0};  // (sweeps, n_sharp, n_flat) the tap's last refresh left `ind` valid for
   DevBuf<int32_t> ind;
   DevBuf<float> partials;
   ProbBlocks *d_probs = nullptr;
@@ -998,15 +1000,21 @@ int enqueue_tail(lslam_odom *od, const TailSpec &t, bool gated) {
   return LSLAM_OK;
 }
 
-// LaserOdometry::scanMatch (:328-647) of the queries sharp / flat (device) against side `from`; pose in/out.  The tail (the
-// next last clouds) is enqueued behind every batch of iterations, acting only once the loop has ended: in the common case the
-// host waits once per sweep.  *tie: a nearest neighbour needed nanoflann's visit order (the result is then not to be used).
-int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, const float4 *flat, size_t n_flat, float pose[6],
-               lslam_stats &st, int32_t *searches, bool *tie, const TailSpec &tail) {
+// The launch arguments of one match: what the search, the residual pass, the solve and the persistent kernel take for the
+// queries sharp / flat (device) against side `from`.  Reserves the node's buffers they point into (not the exchange slots:
+// loop_slots) and puts the block range on the device.  Shared by match_loop and the parity tap lslam_debug_odom_step.
+struct LoopSetup {
+  OdomArgs oa{};
+  SearchArgs sa{};
+  SolveArgs so{};
+  GnSegArgs ga{};
+};
+
+int loop_setup(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, const float4 *flat, size_t n_flat, LoopSetup &L) {
   const Side &S = od->side[from];
   const size_t nq = n_sharp + n_flat;
   OD_TRY(od->ind.reserve(3 * nq + 1));
-  OdomArgs oa{};
+  OdomArgs &oa = L.oa;
   oa.oc = S.org[0].p;
   oa.os = S.org[1].p;
   oa.n_oc = (int32_t)S.n[0];
@@ -1019,11 +1027,12 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   oa.nb_total = oa.nb_sharp + (int32_t)((n_flat + 255) / 256);
   oa.ind = od->ind.p;
   oa.sel = nullptr;
+  oa.coeff = nullptr;
   oa.mode = 2;
   oa.state = od->d_state;
   OD_TRY(od->partials.reserve((size_t)(oa.nb_total ? oa.nb_total : 1) * NCOL));
   oa.partials = od->partials.p;
-  SearchArgs sa{};
+  SearchArgs &sa = L.sa;
   for (int c = 0; c < 2; ++c) {
     sa.h[c].start = S.start + (size_t)(2 * c) * (OH_SIZE + 1);
     sa.h[c].pts[0] = S.sorted[2 * c].p;
@@ -1048,12 +1057,6 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
     od->dbg_n = nq;
   }
   sa.nf_slack = od->nf_slack;
-  GNState *hs = od->h_state;
-  std::memset(hs, 0, sizeof(GNState));
-  for (int i = 0; i < 6; ++i) hs->pose[i] = pose[i];
-  pose_to_Rt_sc(pose, hs->R, hs->t, hs->sc, HostSinCosF());
-  const int max_it = od->max_it;
-  if (max_it == 0 || oa.nb_total == 0) hs->done = 1;
   if (od->nb_on_device != oa.nb_total) {
     ProbBlocks *pb = reinterpret_cast<ProbBlocks *>(h_flags_of(od) + 16);  // pinned
     pb->first_block = 0;
@@ -1061,21 +1064,74 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
     OD_TRY(hipMemcpyAsync(od->d_probs, pb, sizeof(ProbBlocks), hipMemcpyHostToDevice, od->stream));
     od->nb_on_device = oa.nb_total;
   }
-  OD_TRY(hipMemcpyAsync(od->d_state, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
-  OD_TRY(hipMemsetAsync(od->d_flags, 0, 64, od->stream));
-  if (nq) OD_TRY(hipMemsetAsync(od->ind.p, 0xFF, 3 * nq * sizeof(int32_t), od->stream));
-  SolveArgs so{};
+  SolveArgs &so = L.so;
   so.states = od->d_state;
   so.partials = od->partials.p;
   so.probs = od->d_probs;
   so.n_prob = 1;
-  so.max_iterations = max_it;
+  so.max_iterations = od->max_it;
   so.delta_r_abort = od->dr;
   so.delta_t_abort = od->dt;
   so.eig_thresh = 10.0f;  // :596
   so.min_rows = 10;       // :501
   so.too_few_continue = 1;
   so.nan_reset = 1;
+  GnSegArgs &ga = L.ga;
+  ga.oa = oa;
+  ga.slots = nullptr;  // loop_slots
+  ga.abort = od->d_flags + 1;
+  ga.state = od->d_state;
+  ga.sp.max_iterations = so.max_iterations;
+  ga.sp.min_rows = so.min_rows;
+  ga.sp.too_few_continue = so.too_few_continue;
+  ga.sp.nan_reset = so.nan_reset;
+  ga.sp.delta_r_abort = so.delta_r_abort;
+  ga.sp.delta_t_abort = so.delta_t_abort;
+  ga.sp.eig_thresh = so.eig_thresh;
+  ga.spin_limit = od->spin_limit;
+  return LSLAM_OK;
+}
+
+// the persistent kernel's exchange slots, every generation filled with the sentinel; enqueued in front of each of its launches
+int loop_slots(lslam_odom *od, LoopSetup &L) {
+  const size_t n = (size_t)OGN_GENERATIONS * L.oa.nb_total * NCOL;
+  OD_TRY(od->slots.reserve(n));
+  L.ga.slots = od->slots.p;
+  OD_TRY(hipMemsetD32Async((hipDeviceptr_t)od->slots.p, (int)OGN_SENT, n, od->stream));
+  return LSLAM_OK;
+}
+
+// the loop's state as the reference enters an iteration with `pose`: into h_state, and from there to the device
+int loop_state_up(lslam_odom *od, const float pose[6], int32_t loop_iter, bool done) {
+  GNState *hs = od->h_state;
+  std::memset(hs, 0, sizeof(GNState));
+  for (int i = 0; i < 6; ++i) hs->pose[i] = pose[i];
+  pose_to_Rt_sc(pose, hs->R, hs->t, hs->sc, HostSinCosF());
+  hs->loop_iter = loop_iter;
+  hs->done = done ? 1 : 0;
+  OD_TRY(hipMemcpyAsync(od->d_state, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
+  OD_TRY(hipMemsetAsync(od->d_flags, 0, 64, od->stream));
+  return LSLAM_OK;
+}
+
+// LaserOdometry::scanMatch (:328-647) of the queries sharp / flat (device) against side `from`; pose in/out.  The tail (the
+// next last clouds) is enqueued behind every batch of iterations, acting only once the loop has ended: in the common case the
+// host waits once per sweep.  *tie: a nearest neighbour needed nanoflann's visit order (the result is then not to be used).
+int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, const float4 *flat, size_t n_flat, float pose[6],
+               lslam_stats &st, int32_t *searches, bool *tie, const TailSpec &tail) {
+  const size_t nq = n_sharp + n_flat;
+  LoopSetup L;
+  int rc0 = loop_setup(od, from, sharp, n_sharp, flat, n_flat, L);
+  if (rc0) return rc0;
+  const OdomArgs &oa = L.oa;
+  const SearchArgs &sa = L.sa;
+  const SolveArgs &so = L.so;
+  GnSegArgs &ga = L.ga;
+  GNState *hs = od->h_state;
+  const int max_it = od->max_it;
+  rc0 = loop_state_up(od, pose, 0, max_it == 0 || oa.nb_total == 0);
+  if (rc0) return rc0;
+  if (nq) OD_TRY(hipMemsetAsync(od->ind.p, 0xFF, 3 * nq * sizeof(int32_t), od->stream));
   OD_TRY(hipEventRecord(od->ev0, od->stream));
   // loop_iter advances by one per solve until the loop is done, so the host knows which iterations refresh the
   // correspondences (every fifth, :357,:423); launches behind the end of the loop exit at once
@@ -1083,20 +1139,6 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   const bool persistent = od->persistent && od->persistent_ok && oa.nb_total >= 1 && oa.nb_total <= OGN_MAX_BLOCKS && max_it > 0;
   if (persistent) {
     // segments of a refresh + up to five iterations in ONE launch (odom_gn_kernel)
-    OD_TRY(od->slots.reserve((size_t)OGN_GENERATIONS * oa.nb_total * NCOL));
-    GnSegArgs ga{};
-    ga.oa = oa;
-    ga.slots = od->slots.p;
-    ga.abort = od->d_flags + 1;
-    ga.state = od->d_state;
-    ga.sp.max_iterations = so.max_iterations;
-    ga.sp.min_rows = so.min_rows;
-    ga.sp.too_few_continue = so.too_few_continue;
-    ga.sp.nan_reset = so.nan_reset;
-    ga.sp.delta_r_abort = so.delta_r_abort;
-    ga.sp.delta_t_abort = so.delta_t_abort;
-    ga.sp.eig_thresh = so.eig_thresh;
-    ga.spin_limit = od->spin_limit;
     const int n_seg = (max_it + 4) / 5;
     int seg_done = 0;
     int batch = (od->iter_hint + 4) / 5;
@@ -1104,7 +1146,8 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
     for (;;) {
       if (batch > n_seg - seg_done) batch = n_seg - seg_done;
       for (int b = 0; b < batch; ++b) {
-        OD_TRY(hipMemsetD32Async((hipDeviceptr_t)od->slots.p, (int)OGN_SENT, (size_t)OGN_GENERATIONS * oa.nb_total * NCOL, od->stream));
+        int rs = loop_slots(od, L);
+        if (rs) return rs;
         if (nq) {
           hipLaunchKernelGGL(odom_search_kernel, dim3((unsigned)nq), dim3(64), 0, od->stream, sa);
           ++n_search;
@@ -1348,6 +1391,117 @@ int lslam_debug_odom_search(lslam_odom *od, uint32_t *out, size_t cap_queries) {
   if (n == 0) return 0;
   if (hipMemcpy(out, od->dbg.p, n * 16, hipMemcpyDeviceToHost) != hipSuccess) return LSLAM_ERR_HIP;
   return (int)n;
+}
+
+// One step of the loop at a given pose and loop counter, with everything the step saw; include/lslam_c.h.
+int lslam_debug_odom_step(lslam_odom *od, lslam_fset *fs, const float pose[6], int32_t iter, int32_t refresh, int32_t path,
+                          int32_t *ind_out, float *sel_out, float *coeff_out, uint8_t *kept_out, double sums_out[32],
+                          lslam_odom_step *out) {
+  if (!od || !lslam::ctx_alive(od->ctx) || !fs || fs->device != od->device || !pose || !out || (path != 0 && path != 1)) {
+    lslam::set_error("bad odometry-step arguments (node, feature set on the node's device, pose, out, path 0 | 1)");
+    return LSLAM_ERR_INVALID;
+  }
+  const Side &S = od->side[od->cur];
+  if (!od->inited || !(S.n[0] > 10 && S.n[1] > 100)) {  // :337
+    lslam::set_error("the node holds no last clouds to match against");
+    return LSLAM_TOO_FEW_REF;
+  }
+  const size_t n_sharp = fs->counts[0], n_flat = fs->counts[2], nq = n_sharp + n_flat;
+  if (nq == 0 || iter < 0 || iter >= od->max_it) {
+    lslam::set_error("bad odometry-step arguments (no queries, or iter outside [0, max_iterations))");
+    return LSLAM_ERR_INVALID;
+  }
+  OD_TRY(hipSetDevice(od->device));
+  LoopSetup L;
+  int rc = loop_setup(od, od->cur, fs->list(0), n_sharp, fs->list(2), n_flat, L);
+  if (rc) return rc;
+  const uint64_t key[3] = {od->sweeps, (uint64_t)n_sharp, (uint64_t)n_flat};
+  const bool search = path == 1 || refresh != 0 || iter % 5 == 0;
+  if (!search && std::memcmp(key, od->tap_ind_key, sizeof(key)) != 0) {
+    lslam::set_error("no correspondences of these clouds to reuse: ask for a refresh");
+    return LSLAM_ERR_INVALID;
+  }
+  if (path == 1) {
+    // one generation only: the kernel leaves after an iteration when the next one refreshes, or when the loop ends
+    if (L.oa.nb_total > OGN_MAX_BLOCKS || !((iter + 1) % 5 == 0 || iter + 1 >= od->max_it)) {
+      lslam::set_error("path 1 takes at most 64 blocks and an iter in front of a refresh (4, 9, ...) or the last one");
+      return LSLAM_ERR_INVALID;
+    }
+    if (sel_out || coeff_out || kept_out) {
+      lslam::set_error("path 1 has no per-point taps");
+      return LSLAM_ERR_INVALID;
+    }
+  }
+  rc = loop_state_up(od, pose, iter, false);
+  if (rc) return rc;
+  if (search) {
+    OD_TRY(hipMemsetAsync(od->ind.p, 0xFF, 3 * nq * sizeof(int32_t), od->stream));
+    hipLaunchKernelGGL(odom_search_kernel, dim3((unsigned)nq), dim3(64), 0, od->stream, L.sa);
+  }
+  if (path == 1) {
+    rc = loop_slots(od, L);
+    if (rc) return rc;
+    hipLaunchKernelGGL(odom_gn_kernel, dim3((unsigned)L.oa.nb_total), dim3(256), 0, od->stream, L.ga);
+  } else {
+    OD_TRY(od->tap_sel.reserve(nq));
+    OD_TRY(od->tap_coeff.reserve(nq));
+    L.oa.sel = od->tap_sel.p;
+    L.oa.coeff = od->tap_coeff.p;
+    OD_TRY(launch_odom_sweep(L.oa, od->stream));
+    OD_TRY(launch_solve(L.so, od->stream));
+  }
+  OD_TRY(hipGetLastError());
+  GNState *hs = od->h_state;
+  OD_TRY(hipMemcpyAsync(hs, od->d_state, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
+  OD_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags, 64, hipMemcpyDeviceToHost, od->stream));
+  if (ind_out) OD_TRY(hipMemcpyAsync(ind_out, od->ind.p, 3 * nq * sizeof(int32_t), hipMemcpyDeviceToHost, od->stream));
+  std::vector<float4> hsel, hco;
+  if (path == 0 && (sel_out || kept_out)) {
+    hsel.resize(nq);
+    OD_TRY(hipMemcpyAsync(hsel.data(), od->tap_sel.p, nq * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+  }
+  if (path == 0 && coeff_out) OD_TRY(hipMemcpyAsync(coeff_out, od->tap_coeff.p, nq * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+  od->tap_ind_key[0] = ~0ull;
+  OD_TRY(hipStreamSynchronize(od->stream));
+  if (path == 1 && h_flags_of(od)[1] != 0u) {
+    lslam::set_error("the persistent kernel's exchange gave up");
+    return LSLAM_ERR_HIP;
+  }
+  std::memcpy(od->tap_ind_key, key, sizeof(key));  // `ind` holds the correspondences of these clouds
+  for (size_t i = 0; i < hsel.size(); ++i) {
+    if (sel_out) {
+      sel_out[3 * i] = hsel[i].x; sel_out[3 * i + 1] = hsel[i].y; sel_out[3 * i + 2] = hsel[i].z;
+    }
+    if (kept_out) kept_out[i] = hsel[i].w != 0.0f ? 1 : 0;
+  }
+  if (sums_out)
+    for (int k = 0; k < NCOL; ++k) sums_out[k] = hs->sums[k];
+  std::memset(out, 0, sizeof(*out));
+  for (int i = 0; i < 6; ++i) {
+    out->pose[i] = hs->pose[i];
+    out->x[i] = hs->x[i];
+  }
+  out->n_rows = hs->n_rows;
+  out->n_line = hs->n_line;
+  out->n_plane = hs->n_plane;
+  out->degenerate = hs->degenerate;
+  out->converged = hs->converged;
+  out->done = hs->done;
+  out->loop_iter = hs->loop_iter;
+  out->solves = hs->iter;
+  out->tie = (h_flags_of(od)[0] & 1u) ? 1 : 0;
+  out->refreshed = search ? 1 : 0;
+  return LSLAM_OK;
+}
+
+int lslam_debug_odom_runs(const lslam_odom *od, uint64_t *persistent_runs, uint64_t *launch_runs) {
+  if (!od) {
+    lslam::set_error("no odometry node");
+    return LSLAM_ERR_INVALID;
+  }
+  if (persistent_runs) *persistent_runs = od->persistent_runs;
+  if (launch_runs) *launch_runs = od->launch_runs;
+  return LSLAM_OK;
 }
 
 int lslam_odom_reset(lslam_odom *od) {

@@ -113,6 +113,59 @@ class DeviceLaserOdometry:
             raise LslamError(rc, self.ctx.lib.lslam_last_error().decode())
         return oc, os_
 
+    def debug_step(self, fset, pose, it, path=0, refresh=False):
+        """Parity tap (``lslam_debug_odom_step``): one iteration of the loop from ``pose`` as iteration ``it`` against the last
+        clouds the node holds, through the launch loop (``path`` 0) or the persistent kernel (1).  Changes neither the last
+        clouds nor ``transform``.  -> dict: ind (3, n), sums (32,) float64, the state after the solve (pose, x, n_rows, n_line,
+        n_plane, degenerate, converged, done, loop_iter, solves), tie, refreshed; path 0 also sel (n, 3), coeff (n, 4), kept (n,)."""
+        import ctypes as C
+        from .capi import LslamError, LslamOdomStep, c_double_p, c_float_p, c_int32_p
+        cnt = fset.counts()
+        n = cnt["sharp"] + cnt["flat"]
+        ind = np.full((3, n), -1, np.int32)
+        sums = np.zeros(32, np.float64)
+        out = LslamOdomStep()
+        p = np.ascontiguousarray(pose, np.float32).reshape(6)
+        sel = coeff = kept = None
+        a_sel = a_coeff = a_kept = None
+        if path == 0:
+            sel, coeff, kept = np.zeros((n, 3), np.float32), np.zeros((n, 4), np.float32), np.zeros(n, np.uint8)
+            a_sel, a_coeff, a_kept = sel.ctypes.data_as(c_float_p), coeff.ctypes.data_as(c_float_p), kept.ctypes.data_as(C.POINTER(C.c_uint8))
+        rc = self.ctx.lib.lslam_debug_odom_step(self.h, fset.h, p.ctypes.data_as(c_float_p), int(it), int(bool(refresh)), int(path),
+                                                ind.ctypes.data_as(c_int32_p), a_sel, a_coeff, a_kept, sums.ctypes.data_as(c_double_p),
+                                                C.byref(out))
+        if rc != 0:
+            raise LslamError(rc, self.ctx.lib.lslam_last_error().decode())
+        res = dict(ind=ind, sums=sums, pose=np.array(out.pose, np.float32), x=np.array(out.x, np.float32), tie=bool(out.tie),
+                   refreshed=bool(out.refreshed))
+        for k in ("n_rows", "n_line", "n_plane", "degenerate", "converged", "done", "loop_iter", "solves"):
+            res[k] = int(getattr(out, k))
+        if path == 0:
+            res.update(sel=sel, coeff=coeff, kept=kept.astype(bool))
+        return res
+
+    def run_counts(self):
+        """(matches whose loop ran in the persistent kernel, matches that ran one launch per step)."""
+        import ctypes as C
+        from .capi import LslamError
+        a, b = C.c_uint64(), C.c_uint64()
+        rc = self.ctx.lib.lslam_debug_odom_runs(self.h, C.byref(a), C.byref(b))
+        if rc < 0:
+            raise LslamError(rc, self.ctx.lib.lslam_last_error().decode())
+        return int(a.value), int(b.value)
+
+    def search_profile(self, n):
+        """The per-query profile of the node's last search launch (``lslam_debug_odom_search``; a node made with
+        LSLAM_ODOM_SEARCH_TAP=1) -> (m, 4) uint32: ticks, candidates of the nearest-neighbour passes, of the category passes,
+        flags (bit 0 a coarse-level nearest-neighbour pass, bit 1 the ring-table fallback)."""
+        import ctypes as C
+        from .capi import LslamError
+        out = np.zeros((n, 4), np.uint32)
+        m = self.ctx.lib.lslam_debug_odom_search(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n)
+        if m < 0:
+            raise LslamError(m, self.ctx.lib.lslam_last_error().decode())
+        return out[:m]
+
     def close(self):
         if self.h:
             self.ctx.lib.lslam_odom_destroy(self.h)
