@@ -675,8 +675,6 @@ void lslam_ctx_destroy(lslam_ctx *ctx) {
   // the feature extraction's scratch), then the events and the streams; the context's own buffers go with `delete`
   for (CtxSlotEntry &e : ctx->slots)
     if (e.obj) e.drop(e.obj);
-  ctx->kc.release();
-  ctx->ks.release();
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   for (hipEvent_t e : ctx->sweep_ev) (void)hipEventDestroy(e);
@@ -790,23 +788,22 @@ int lslam_debug_sweep_clocks(lslam_ctx *ctx, const float pose[6], int32_t jtj_mo
   if (rc) return rc;
   const size_t nw = (size_t)sa.nb_total * (SWEEP_BLOCK / 64);
   if (nw > out_cap_waves) return LSLAM_ERR_INVALID;
-  uint64_t *d = nullptr;
+  DevBuf<uint64_t> d;
   size_t words = nw * 4;
 #ifdef LSLAM_TRAVERSAL_STATS
   words += (size_t)sa.nb_total * SWEEP_BLOCK * 8;  // per-lane traversal statistics follow
   if (nw * 4 + (size_t)sa.nb_total * SWEEP_BLOCK * 8 > out_cap_waves * 4) return LSLAM_ERR_INVALID;
 #endif
-  HIP_TRY(hipMalloc((void **)&d, words * sizeof(uint64_t)));
-  HIP_TRY(hipMemsetAsync(d, 0, words * sizeof(uint64_t), ctx->stream));
-  sa.dbg = d;
+  HIP_TRY(d.alloc(words));
+  HIP_TRY(hipMemsetAsync(d.p, 0, words * sizeof(uint64_t), ctx->stream));
+  sa.dbg = d.p;
   const bool unbounded_dbg = env_once().unbounded_knn;
   sa.bounded = unbounded_dbg ? 0 : 1;
   sa.prev_valid = ctx->prev_valid ? 1 : 0;
   if (sa.bounded) ctx->prev_valid = true;
   HIP_TRY(sweep_launch(ctx, sa, jtj_mode));
-  HIP_TRY(hipMemcpyAsync(out, d, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(out, d.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  (void)hipFree(d);
   return (int)nw;
 }
 

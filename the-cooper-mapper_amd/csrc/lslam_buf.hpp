@@ -2,6 +2,8 @@
 // (PinBuf).  A buffer belongs to the object it is a member of and is released by its destructor: a context, a map, an odometry
 // node frees what it allocated when it is destroyed -- once nothing enqueued on its streams can still touch the memory (the
 // owner waits for them first).  One growth rule for every buffer: n + n / 4 + 256 elements.
+// reserve(n) is for what grows and applies that rule; alloc(n) is for what is sized once, when its owner is made (a map's rings,
+// a pose graph's arrays, hash tables): exactly n elements, so a container the user sized keeps the footprint they asked for.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,16 +37,17 @@ struct DevBuf {
     cap = n;
     borrowed = true;
   }
-  // room for n elements; the contents are lost when the buffer grows
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
+  // exactly max(n, 1) elements, whatever was held before
+  hipError_t alloc(size_t n) {
     release();
-    const size_t want = buf_grown(n);
+    const size_t want = n ? n : 1;
     hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
     if (e == hipSuccess) cap = want;
     else p = nullptr;
     return e;
   }
+  // room for n elements; the contents are lost when the buffer grows
+  hipError_t reserve(size_t n) { return n <= cap ? hipSuccess : alloc(buf_grown(n)); }
   // grow, keeping the first `keep` elements (copied on `s`, waited for)
   hipError_t grow(size_t n, size_t keep, hipStream_t s) {
     if (n <= cap) return hipSuccess;
@@ -90,15 +93,15 @@ struct PinBuf {
     return *this;
   }
   ~PinBuf() { release(); }
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
+  hipError_t alloc(size_t n) {
     release();
-    const size_t want = buf_grown(n);
+    const size_t want = n ? n : 1;
     hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
     if (e == hipSuccess) cap = want;
     else p = nullptr;
     return e;
   }
+  hipError_t reserve(size_t n) { return n <= cap ? hipSuccess : alloc(buf_grown(n)); }
   void release() {
     if (p) (void)hipHostFree(p);
     p = nullptr;

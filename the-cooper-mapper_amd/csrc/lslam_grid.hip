@@ -268,29 +268,29 @@ hipError_t GridDev::build(const float4 *src, int n_src, const float lo[3], const
 #define G_TRY(x) do { e = (x); if (e != hipSuccess) return e; } while (0)
   // An allocation that fails is "no grid" (status 3), not a failed call: the tree search needs none of these arrays.
 #define G_ALLOC(x) do { e = (x); if (e != hipSuccess) { (void)hipGetLastError(); release(); *status = 3; return hipSuccess; } } while (0)
-  G_ALLOC(reserve(pts, cap_pts, (size_t)n + 16));
-  G_ALLOC(reserve(tmp_pts, cap_tmp, (size_t)n + 16));
-  G_ALLOC(reserve(cell_start, cap_cell, ncell + 1));
+  G_ALLOC(pts.reserve((size_t)n + 16));
+  G_ALLOC(tmp_pts.reserve((size_t)n + 16));
+  G_ALLOC(cell_start.reserve(ncell + 1));
   const size_t n_coarse = (ncell + CS_CELLS - 1) / CS_CELLS;
   // the coarse counts and, right behind them (at a 16-byte boundary), the "point outside the table" counter: zeroed by ONE fill
   const size_t n_coarse_pad = (n_coarse + 3) & ~(size_t)3;
-  G_ALLOC(reserve(coarse, cap_coarse, n_coarse_pad + 4));
-  err = reinterpret_cast<int32_t *>(coarse + n_coarse_pad);
+  G_ALLOC(coarse.reserve(n_coarse_pad + 4));
+  err = reinterpret_cast<int32_t *>(coarse.p + n_coarse_pad);
   {
     // the count table is left zeroed by every build (the scatter counts it down); only a new allocation is cleared
-    const size_t before = cap_count;
-    G_ALLOC(reserve(count, cap_count, ncell + 16));
-    if (cap_count != before || !count_clean) G_TRY(hipMemsetAsync(count, 0, cap_count * sizeof(uint32_t), s));
+    const size_t before = count.cap;
+    G_ALLOC(count.reserve(ncell + 16));
+    if (count.cap != before || !count_clean) G_TRY(hipMemsetAsync(count.p, 0, count.cap * sizeof(uint32_t), s));
     count_clean = false;
   }
-  G_TRY(hipMemsetAsync(coarse, 0, (n_coarse_pad + 4) * sizeof(uint32_t), s));
+  G_TRY(hipMemsetAsync(coarse.p, 0, (n_coarse_pad + 4) * sizeof(uint32_t), s));
   const dim3 blk(256), grd((n + 255) / 256);
-  hipLaunchKernelGGL(grid_count_kernel, grd, blk, 0, s, G, src, count, coarse, err);
-  hipLaunchKernelGGL(grid_scan_kernel, dim3((unsigned)((ncell + 1 + CS_CELLS - 1) / CS_CELLS)), blk, 0, s, (const uint32_t *)count,
-                     (const uint32_t *)coarse, (uint32_t)(ncell + 1), (uint32_t)n, cell_start);
-  hipLaunchKernelGGL(grid_scatter_kernel, grd, blk, 0, s, G, src, (const uint32_t *)cell_start, count, tmp_pts);
-  G.cell_start = cell_start;  // (the rank kernel reads the table through the view)
-  hipLaunchKernelGGL(grid_rank_kernel, grd, blk, 0, s, G, (const float4 *)tmp_pts, (const uint32_t *)cell_start, pts);
+  hipLaunchKernelGGL(grid_count_kernel, grd, blk, 0, s, G, src, count.p, coarse.p, err);
+  hipLaunchKernelGGL(grid_scan_kernel, dim3((unsigned)((ncell + 1 + CS_CELLS - 1) / CS_CELLS)), blk, 0, s, (const uint32_t *)count.p,
+                     (const uint32_t *)coarse.p, (uint32_t)(ncell + 1), (uint32_t)n, cell_start.p);
+  hipLaunchKernelGGL(grid_scatter_kernel, grd, blk, 0, s, G, src, (const uint32_t *)cell_start.p, count.p, tmp_pts.p);
+  G.cell_start = cell_start.p;  // (the rank kernel reads the table through the view)
+  hipLaunchKernelGGL(grid_rank_kernel, grd, blk, 0, s, G, (const float4 *)tmp_pts.p, (const uint32_t *)cell_start.p, pts.p);
   G_TRY(hipGetLastError());
   count_clean = true;  // once the stream gets there
   // the candidate loop loads pts[cur] for lanes that have run out of candidates at index 0: nothing to pad; a leaf-style
@@ -303,18 +303,16 @@ hipError_t GridDev::build(const float4 *src, int n_src, const float lo[3], const
 #undef G_TRY
 #undef G_ALLOC
   if (h_err) { *status = 1; return hipSuccess; }
-  G.cell_start = cell_start;
-  G.pts = pts;
+  G.cell_start = cell_start.p;
+  G.pts = pts.p;
   view = G;
   n_cells = ncell;
   return hipSuccess;
 }
 
 void GridDev::release() {
-  for (void *q : {(void *)pts, (void *)tmp_pts, (void *)cell_start, (void *)count, (void *)coarse})  // (err lives behind coarse)
-    if (q) (void)hipFree(q);
-  pts = tmp_pts = nullptr; cell_start = count = coarse = nullptr; err = nullptr;
-  cap_pts = cap_tmp = cap_cell = cap_count = cap_coarse = cap_err = 0;
+  pts.release(); tmp_pts.release(); cell_start.release(); count.release(); coarse.release();
+  err = nullptr;
   count_clean = false;
   view = CellGrid{};
   n_cells = 0;

@@ -321,22 +321,10 @@ hipError_t launch_knn5_grid(const CellGrid &G, const TreeView &T, const float4 *
 struct GridDev {
   CellGrid view{};
   size_t n_cells = 0;
-  float4 *pts = nullptr, *tmp_pts = nullptr;
-  int32_t *err = nullptr;
-  uint32_t *cell_start = nullptr, *count = nullptr, *coarse = nullptr;
-  size_t cap_pts = 0, cap_tmp = 0, cap_cell = 0, cap_count = 0, cap_coarse = 0, cap_err = 0;
+  DevBuf<float4> pts, tmp_pts;
+  DevBuf<uint32_t> cell_start, count, coarse;
+  int32_t *err = nullptr;    // the "point outside the table" counter: lives behind the coarse counts
   bool count_clean = false;  // every cell of `count` is zero (each build leaves it so)
-  template <typename T>
-  static hipError_t reserve(T *&p, size_t &cap, size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = n + n / 8 + 64;
-    hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
   // status: 0 built (or nothing to build: view.cell_start stays null), 1 non-finite point, 2 map too large for the grid
   hipError_t build(const TreeView &T, float cell, hipStream_t s, int *status);
   // ... from n points {x, y, z, bitcast(original index)} in any order and their bounding box (a map whose trees are deferred)

@@ -252,17 +252,6 @@ struct LFrame {
   float lo[2][3], hi[2][3];  // the transformed clouds' boxes
 };
 
-template <typename T>
-hipError_t lm_alloc(T *&p, size_t n) {
-  p = nullptr;
-  return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T));
-}
-template <typename T>
-void lm_free(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
 }  // namespace
 
 struct lslam_lmap {
@@ -283,24 +272,24 @@ struct lslam_lmap {
   int64_t evicted = 0;
   bool has_frames_ever = false;  // the leaves are fixed from the first frame on
   // rings
-  float4 *ring[2] = {nullptr, nullptr};
+  lslam::DevBuf<float4> ring[2];
   uint64_t head[2] = {0, 0}, tail[2] = {0, 0};
   size_t live[2] = {0, 0};
   // add staging
   lslam::PinBuf<float4> h_stage[2];
   lslam::DevBuf<float4> d_raw[2], d_tf[2];
   // surround
-  float4 *gath[2] = {nullptr, nullptr}, *filt[2] = {nullptr, nullptr}, *mapp[2] = {nullptr, nullptr};
-  int32_t *seg[2] = {nullptr, nullptr}, *oseg[2] = {nullptr, nullptr};  // zeros (one segment) / the filter's segment output
-  uint32_t *d_res = nullptr;  // [2][8] add boxes, [2][8] surround counts and boxes
-  uint32_t *h_pin = nullptr;  // pinned: [2][4] done words, [2][8] add boxes, [2][8] surround results
+  lslam::DevBuf<float4> gath[2], filt[2], mapp[2];
+  lslam::DevBuf<int32_t> seg[2], oseg[2];  // zeros (one segment) / the filter's segment output
+  lslam::DevBuf<uint32_t> d_res;  // [2][8] add boxes, [2][8] surround counts and boxes
+  lslam::PinBuf<uint32_t> h_pin;  // pinned: [2][4] done words, [2][8] add boxes, [2][8] surround results
   bool sur_valid = false;
   size_t n_sur[2] = {0, 0};
   float sur_lo[2][3], sur_hi[2][3];
   // key-ordered window
-  float4 *xs[2] = {nullptr, nullptr}, *xs_alt[2] = {nullptr, nullptr};
-  uint32_t *xq[2] = {nullptr, nullptr}, *xq_alt[2] = {nullptr, nullptr};
-  int32_t *tile_count = nullptr;
+  lslam::DevBuf<float4> xs[2], xs_alt[2];
+  lslam::DevBuf<uint32_t> xq[2], xq_alt[2];
+  lslam::DevBuf<int32_t> tile_count;
   size_t nx[2] = {0, 0}, nx_sorted[2] = {0, 0};  // entries of xs / of its prefix that is in key order (evicted ones included until compacted)
   uint32_t pend_seq[2] = {0, 0};                 // frames from this sequence number on are behind the prefix
   bool x_valid[2] = {true, true}, x_dead[2] = {false, false};
@@ -310,9 +299,9 @@ struct lslam_lmap {
 
 namespace {
 
-uint32_t *done_words(lslam_lmap *lm, int t) { return lm->h_pin + 4 * t; }
-uint32_t *h_addbox(lslam_lmap *lm) { return lm->h_pin + 8; }
-uint32_t *h_surres(lslam_lmap *lm) { return lm->h_pin + 24; }
+uint32_t *done_words(lslam_lmap *lm, int t) { return lm->h_pin.p + 4 * t; }
+uint32_t *h_addbox(lslam_lmap *lm) { return lm->h_pin.p + 8; }
+uint32_t *h_surres(lslam_lmap *lm) { return lm->h_pin.p + 24; }
 
 int check_lm(lslam_lmap *lm, const char *what) {
   if (!lm) {
@@ -329,17 +318,11 @@ int check_lm(lslam_lmap *lm, const char *what) {
   return LSLAM_OK;
 }
 
-void free_all(lslam_lmap *lm) {
+void free_all(lslam_lmap *lm) {  // what no member's destructor releases
   for (int t = 0; t < 2; ++t) {
-    lm_free(lm->ring[t]); lm_free(lm->gath[t]); lm_free(lm->filt[t]); lm_free(lm->mapp[t]);
-    lm_free(lm->seg[t]); lm_free(lm->oseg[t]); lm_free(lm->xs[t]); lm_free(lm->xs_alt[t]); lm_free(lm->xq[t]); lm_free(lm->xq_alt[t]);
     lslam::window_filter_destroy(lm->wf[t]);
     lm->wf[t] = nullptr;
   }
-  lm_free(lm->d_res);
-  lm_free(lm->tile_count);
-  if (lm->h_pin) (void)hipHostFree(lm->h_pin);
-  lm->h_pin = nullptr;
 }
 
 void reset_state(lslam_lmap *lm) {  // LocalFeatureMap as constructed (the leaves and the queue distance stay)
@@ -455,13 +438,13 @@ int add_impl(lslam_lmap *lm, const void *corner, size_t n_corner, const void *su
       ta.n[t] = (int)n_new[t];
     }
     ta.nb0 = (int)((n_new[0] + 255) / 256);
-    ta.res = lm->d_res;
+    ta.res = lm->d_res.p;
     Rigid12 Tm;
     for (int k = 0; k < 12; ++k) Tm.m[k] = T_map[k];
-    LM_TRY(hipMemsetAsync(lm->d_res, 0, 16 * sizeof(uint32_t), s));
+    LM_TRY(hipMemsetAsync(lm->d_res.p, 0, 16 * sizeof(uint32_t), s));
     hipLaunchKernelGGL(lm_transform_kernel, dim3((unsigned)(ta.nb0 + (int)((n_new[1] + 255) / 256))), dim3(256), 0, s, ta, Tm);
     LM_TRY(hipGetLastError());
-    LM_TRY(hipMemcpyAsync(h_addbox(lm), lm->d_res, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LM_TRY(hipMemcpyAsync(h_addbox(lm), lm->d_res.p, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     LM_TRY(hipStreamSynchronize(s));
     for (int t = 0; t < 2; ++t)
       for (int a = 0; a < 3; ++a) {
@@ -514,10 +497,10 @@ int add_impl(lslam_lmap *lm, const void *corner, size_t n_corner, const void *su
     AppendArgs aa{};
     for (int t = 0; t < 2; ++t) {
       aa.in[t] = lm->d_tf[t].p;
-      aa.ring[t] = lm->ring[t];
+      aa.ring[t] = lm->ring[t].p;
       const bool x = lm->key_ordered && lm->x_valid[t];
-      aa.xs[t] = x ? lm->xs[t] : nullptr;
-      aa.xq[t] = x ? lm->xq[t] : nullptr;
+      aa.xs[t] = x ? lm->xs[t].p : nullptr;
+      aa.xq[t] = x ? lm->xq[t].p : nullptr;
       aa.n[t] = (int)n_new[t];
       aa.tail[t] = (uint32_t)(lm->tail[t] % lm->cap);
       aa.nx[t] = (uint32_t)lm->nx[t];
@@ -557,8 +540,8 @@ void window_box(const lslam_lmap *lm, int t, float mn[3], float mx[3]) {
 
 int index_box(lslam_lmap *lm, int t, const uint32_t *n_ptr) {
   const unsigned blocks = (unsigned)std::min<size_t>(512, (lm->live[t] + 255) / 256);
-  hipLaunchKernelGGL(lm_index_box_kernel, dim3(blocks), dim3(256), 0, lm->stream, (const float4 *)lm->filt[t], n_ptr, (uint32_t)lm->cap,
-                     lm->mapp[t], lm->d_res + 16 + 8 * t);
+  hipLaunchKernelGGL(lm_index_box_kernel, dim3(blocks), dim3(256), 0, lm->stream, (const float4 *)lm->filt[t].p, n_ptr, (uint32_t)lm->cap,
+                     lm->mapp[t].p, lm->d_res.p + 16 + 8 * t);
   LM_TRY(hipGetLastError());
   return LSLAM_OK;
 }
@@ -566,7 +549,7 @@ int index_box(lslam_lmap *lm, int t, const uint32_t *n_ptr) {
 int gather_ring(lslam_lmap *lm, int t, float4 *out) {
   const int n = (int)lm->live[t];
   if (!n) return LSLAM_OK;
-  hipLaunchKernelGGL(lm_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lm->stream, (const float4 *)lm->ring[t],
+  hipLaunchKernelGGL(lm_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lm->stream, (const float4 *)lm->ring[t].p,
                      (uint32_t)lm->cap, (uint32_t)(lm->head[t] % lm->cap), n, out);
   LM_TRY(hipGetLastError());
   return LSLAM_OK;
@@ -574,12 +557,12 @@ int gather_ring(lslam_lmap *lm, int t, float4 *out) {
 
 // (a): gather + voxel_filter_segments over one segment.  wait: the filter's blocking form (the retry after a key-range error)
 int refilter(lslam_lmap *lm, int t, bool wait) {
-  int rc = gather_ring(lm, t, lm->gath[t]);
+  int rc = gather_ring(lm, t, lm->gath[t].p);
   if (rc) return rc;
   size_t m = 0;
   uint32_t *done = done_words(lm, t);
   done[0] = done[1] = done[2] = 0;
-  rc = lslam::voxel_filter_segments(lm->ctx, lm->gath[t], lm->seg[t], lm->live[t], 1, lm->leaf[t], lm->filt[t], lm->oseg[t], &m, true,
+  rc = lslam::voxel_filter_segments(lm->ctx, lm->gath[t].p, lm->seg[t].p, lm->live[t], 1, lm->leaf[t], lm->filt[t].p, lm->oseg[t].p, &m, true,
                                     wait ? nullptr : done);
   if (rc) return rc;
   if (wait) done[0] = (uint32_t)m;
@@ -612,11 +595,11 @@ int ordered_filter(lslam_lmap *lm, int t, bool *took) {
   const uint32_t min_seq = lm->frames.front().seq;
   if (lm->always_resort) lm->x_valid[t] = false;
   if (!lm->x_valid[t]) {  // rebuild from the ring: everything is "new"
-    int rc = gather_ring(lm, t, lm->xs[t]);
+    int rc = gather_ring(lm, t, lm->xs[t].p);
     if (rc) return rc;
     size_t at = 0;
     for (const LFrame &f : lm->frames) {  // (the fall-back path: one fill per frame)
-      if (f.count[t]) LM_TRY(hipMemsetD32Async((hipDeviceptr_t)(lm->xq[t] + at), (int)f.seq, f.count[t], s));
+      if (f.count[t]) LM_TRY(hipMemsetD32Async((hipDeviceptr_t)(lm->xq[t].p + at), (int)f.seq, f.count[t], s));
       at += f.count[t];
     }
     lm->nx[t] = lm->live[t];
@@ -626,9 +609,9 @@ int ordered_filter(lslam_lmap *lm, int t, bool *took) {
   } else if (lm->x_dead[t] && lm->nx[t]) {  // evictions since the last sweep: stable compaction by frame sequence
     const int n = (int)lm->nx[t];
     const unsigned tiles = (unsigned)((n + LM_TILE - 1) / LM_TILE);
-    hipLaunchKernelGGL(lm_live_count_kernel, dim3(tiles), dim3(256), 0, s, (const uint32_t *)lm->xq[t], n, min_seq, lm->tile_count);
-    hipLaunchKernelGGL(lm_compact_kernel, dim3(tiles), dim3(256), 0, s, (const float4 *)lm->xs[t], (const uint32_t *)lm->xq[t], n, min_seq,
-                       (const int32_t *)lm->tile_count, lm->xs_alt[t], lm->xq_alt[t], (uint32_t)lm->cap);
+    hipLaunchKernelGGL(lm_live_count_kernel, dim3(tiles), dim3(256), 0, s, (const uint32_t *)lm->xq[t].p, n, min_seq, lm->tile_count.p);
+    hipLaunchKernelGGL(lm_compact_kernel, dim3(tiles), dim3(256), 0, s, (const float4 *)lm->xs[t].p, (const uint32_t *)lm->xq[t].p, n, min_seq,
+                       (const int32_t *)lm->tile_count.p, lm->xs_alt[t].p, lm->xq_alt[t].p, (uint32_t)lm->cap);
     LM_TRY(hipGetLastError());
     std::swap(lm->xs[t], lm->xs_alt[t]);
     std::swap(lm->xq[t], lm->xq_alt[t]);
@@ -642,12 +625,12 @@ int ordered_filter(lslam_lmap *lm, int t, bool *took) {
   uint32_t *done = done_words(lm, t);
   done[0] = done[1] = done[2] = 0;
   const uint32_t *order = nullptr;
-  int rc = lslam::voxel_filter_window(s, lm->wf[t], lm->xs[t], lm->nx_sorted[t], lm->nx[t], lm->leaf[t], base0, bits, lm->filt[t], done, &order);
+  int rc = lslam::voxel_filter_window(s, lm->wf[t], lm->xs[t].p, lm->nx_sorted[t], lm->nx[t], lm->leaf[t], base0, bits, lm->filt[t].p, done, &order);
   if (rc) return rc;
   if (lm->nx_sorted[t] > 0 && lm->nx_sorted[t] < lm->nx[t]) lm->n_merged++; else lm->n_resorted++;
   const int n = (int)lm->nx[t];
-  hipLaunchKernelGGL(lm_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float4 *)lm->xs[t], (const uint32_t *)lm->xq[t],
-                     order, n, lm->xs_alt[t], lm->xq_alt[t]);
+  hipLaunchKernelGGL(lm_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float4 *)lm->xs[t].p, (const uint32_t *)lm->xq[t].p,
+                     order, n, lm->xs_alt[t].p, lm->xq_alt[t].p);
   LM_TRY(hipGetLastError());
   std::swap(lm->xs[t], lm->xs_alt[t]);
   std::swap(lm->xq[t], lm->xq_alt[t]);
@@ -664,7 +647,7 @@ int ensure_surround(lslam_lmap *lm) {
   bool any = false, ordered[2] = {false, false};
   uint32_t *h = h_surres(lm);
   for (int k = 0; k < 16; ++k) h[k] = 0u;
-  LM_TRY(hipMemsetAsync(lm->d_res + 16, 0, 16 * sizeof(uint32_t), s));
+  LM_TRY(hipMemsetAsync(lm->d_res.p + 16, 0, 16 * sizeof(uint32_t), s));
   for (int t = 0; t < 2; ++t) {
     if (!lm->live[t]) continue;
     int rc = LSLAM_OK;
@@ -678,7 +661,7 @@ int ensure_surround(lslam_lmap *lm) {
     any = true;
   }
   if (any) {
-    LM_TRY(hipMemcpyAsync(h, lm->d_res + 16, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LM_TRY(hipMemcpyAsync(h, lm->d_res.p + 16, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     LM_TRY(hipStreamSynchronize(s));
     for (int t = 0; t < 2; ++t) {
       if (!lm->live[t]) continue;
@@ -687,10 +670,10 @@ int ensure_surround(lslam_lmap *lm) {
         // the key did not hold the points after all, or the ordered array was not in order: the blocking full re-filter
         // decides, and the ordered array is rebuilt from the ring at the next sweep
         if (ordered[t]) lm->x_valid[t] = false;
-        LM_TRY(hipMemsetAsync(lm->d_res + 16 + 8 * t, 0, 8 * sizeof(uint32_t), s));
+        LM_TRY(hipMemsetAsync(lm->d_res.p + 16 + 8 * t, 0, 8 * sizeof(uint32_t), s));
         const int rc = refilter(lm, t, true);
         if (rc) return rc == LSLAM_ERR_HIP ? fail_reset(lm, rc) : rc;
-        LM_TRY(hipMemcpyAsync(h + 8 * t, lm->d_res + 16 + 8 * t, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        LM_TRY(hipMemcpyAsync(h + 8 * t, lm->d_res.p + 16 + 8 * t, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         LM_TRY(hipStreamSynchronize(s));
       }
     }
@@ -734,24 +717,24 @@ int lslam_lmap_create(lslam_ctx *ctx, size_t max_points_per_type, int32_t max_fr
   const size_t cap = lm->cap;
   hipError_t e = hipSuccess;
   for (int t = 0; t < 2 && e == hipSuccess; ++t) {
-    if (e == hipSuccess) e = lm_alloc(lm->ring[t], cap);
-    if (e == hipSuccess) e = lm_alloc(lm->gath[t], cap);
-    if (e == hipSuccess) e = lm_alloc(lm->filt[t], cap);
-    if (e == hipSuccess) e = lm_alloc(lm->mapp[t], cap);
-    if (e == hipSuccess) e = lm_alloc(lm->seg[t], cap);
-    if (e == hipSuccess) e = lm_alloc(lm->oseg[t], cap);
-    if (e == hipSuccess) e = hipMemsetAsync(lm->seg[t], 0, cap * sizeof(int32_t), lm->stream);
+    if (e == hipSuccess) e = lm->ring[t].alloc(cap);
+    if (e == hipSuccess) e = lm->gath[t].alloc(cap);
+    if (e == hipSuccess) e = lm->filt[t].alloc(cap);
+    if (e == hipSuccess) e = lm->mapp[t].alloc(cap);
+    if (e == hipSuccess) e = lm->seg[t].alloc(cap);
+    if (e == hipSuccess) e = lm->oseg[t].alloc(cap);
+    if (e == hipSuccess) e = hipMemsetAsync(lm->seg[t].p, 0, cap * sizeof(int32_t), lm->stream);
     if (lm->key_ordered) {
-      if (e == hipSuccess) e = lm_alloc(lm->xs[t], cap);
-      if (e == hipSuccess) e = lm_alloc(lm->xs_alt[t], cap);
-      if (e == hipSuccess) e = lm_alloc(lm->xq[t], cap);
-      if (e == hipSuccess) e = lm_alloc(lm->xq_alt[t], cap);
+      if (e == hipSuccess) e = lm->xs[t].alloc(cap);
+      if (e == hipSuccess) e = lm->xs_alt[t].alloc(cap);
+      if (e == hipSuccess) e = lm->xq[t].alloc(cap);
+      if (e == hipSuccess) e = lm->xq_alt[t].alloc(cap);
       if (e == hipSuccess) lm->wf[t] = lslam::window_filter_create();
     }
   }
-  if (e == hipSuccess) e = lm_alloc(lm->d_res, 32);
-  if (e == hipSuccess && lm->key_ordered) e = lm_alloc(lm->tile_count, (cap + LM_TILE - 1) / LM_TILE);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&lm->h_pin, 40 * sizeof(uint32_t), hipHostMallocDefault);
+  if (e == hipSuccess) e = lm->d_res.alloc(32);
+  if (e == hipSuccess && lm->key_ordered) e = lm->tile_count.alloc((cap + LM_TILE - 1) / LM_TILE);
+  if (e == hipSuccess) e = lm->h_pin.alloc(40);
   if (e == hipSuccess) e = hipStreamSynchronize(lm->stream);
   if (e != hipSuccess) {
     char b[200];
@@ -761,7 +744,7 @@ int lslam_lmap_create(lslam_ctx *ctx, size_t max_points_per_type, int32_t max_fr
     delete lm;
     return LSLAM_ERR_HIP;
   }
-  std::memset(lm->h_pin, 0, 40 * sizeof(uint32_t));
+  std::memset(lm->h_pin.p, 0, 40 * sizeof(uint32_t));
   reset_state(lm);
   *out = lm;
   return LSLAM_OK;
@@ -825,7 +808,7 @@ int lslam_lmap_surround_to_map_counts(lslam_lmap *lm, size_t *n_corner, size_t *
   if (n_corner) *n_corner = lm->n_sur[0];
   if (n_surf) *n_surf = lm->n_sur[1];
   if (lm->n_sur[0] == 0 && lm->n_sur[1] == 0) return lslam_map_set(lm->ctx, nullptr, 0, nullptr, 0, 16);
-  return lslam::map_set_device(lm->ctx, lm->mapp[0], lm->n_sur[0], lm->mapp[1], lm->n_sur[1], lm->sur_lo, lm->sur_hi);
+  return lslam::map_set_device(lm->ctx, lm->mapp[0].p, lm->n_sur[0], lm->mapp[1].p, lm->n_sur[1], lm->sur_lo, lm->sur_hi);
 }
 
 int lslam_lmap_get_surround(lslam_lmap *lm, float *corner_xyzi, size_t cap_c, size_t *n_c, float *surf_xyzi, size_t cap_s, size_t *n_s) {
@@ -847,7 +830,7 @@ int lslam_lmap_get_surround(lslam_lmap *lm, float *corner_xyzi, size_t cap_c, si
       return LSLAM_ERR_INVALID;
     }
     if (lm->n_sur[t]) {
-      LM_TRY(hipMemcpyAsync(dst[t], lm->filt[t], lm->n_sur[t] * sizeof(float4), hipMemcpyDeviceToHost, lm->stream));
+      LM_TRY(hipMemcpyAsync(dst[t], lm->filt[t].p, lm->n_sur[t] * sizeof(float4), hipMemcpyDeviceToHost, lm->stream));
       any = true;
     }
   }
@@ -888,9 +871,9 @@ int lslam_lmap_get_frames(lslam_lmap *lm, int32_t cap_frames, int32_t *n_frames,
   bool any = false;
   for (int t = 0; t < 2; ++t) {
     if (!dst[t] || !lm->live[t]) continue;
-    rc = gather_ring(lm, t, lm->gath[t]);
+    rc = gather_ring(lm, t, lm->gath[t].p);
     if (rc) return rc;
-    LM_TRY(hipMemcpyAsync(dst[t], lm->gath[t], lm->live[t] * sizeof(float4), hipMemcpyDeviceToHost, lm->stream));
+    LM_TRY(hipMemcpyAsync(dst[t], lm->gath[t].p, lm->live[t] * sizeof(float4), hipMemcpyDeviceToHost, lm->stream));
     any = true;
   }
   if (any) LM_TRY(hipStreamSynchronize(lm->stream));

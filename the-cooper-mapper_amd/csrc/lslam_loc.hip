@@ -1537,8 +1537,6 @@ void lslam_loc_destroy(lslam_loc *loc) {
     (void)hipStreamSynchronize(loc->stream);
   }
   lslam_fmap_destroy(loc->fm);
-  loc->grid[0].release();
-  loc->grid[1].release();
   delete loc;
 }
 

@@ -806,10 +806,19 @@ using lslam::PinBuf;
 struct Side {
   DevBuf<float4> org[2];
   DevBuf<float4> sorted[4];  // [cloud * 2 + level]
-  uint32_t *start = nullptr;  // [4][OH_SIZE + 1]
-  uint32_t *hdr = nullptr;    // [2] per cloud: bit 0 = not in ring order (odom_prep_kernel); behind it the ring table [2][OH_RINGS + 1]
+  DevBuf<uint32_t> start;  // [4][OH_SIZE + 1]
+  DevBuf<uint32_t> hdr;    // [2] per cloud: bit 0 = not in ring order (odom_prep_kernel); behind it the ring table [2][OH_RINGS + 1]
   size_t n[2] = {0, 0};
 };
+
+// the node's pinned block: the state coming down, the flags coming down, the ProbBlocks going up
+struct HostState {
+  GNState state;
+  uint32_t flags[16];
+  ProbBlocks probs;
+  unsigned char pad[64 - sizeof(ProbBlocks)];
+};
+static_assert(sizeof(HostState) == sizeof(GNState) + 128, "HostState: a GNState and 128 bytes behind it");
 
 }  // namespace
 
@@ -824,7 +833,7 @@ struct lslam_odom {
   float Tsum[16];
   Side side[2];
   int cur = 0;
-  uint32_t *cnt = nullptr, *cursor = nullptr;  // [4][OH_SIZE]
+  DevBuf<uint32_t> cnt, cursor;  // [4][OH_SIZE]
   int32_t literal_window = 0;
   // odom_gn_kernel
   DevBuf<float> slots;
@@ -839,10 +848,11 @@ struct lslam_odom {
   uint64_t tap_ind_key[3] = {~0ull, 0, 0};  // (sweeps, n_sharp, n_flat) the tap's last refresh left `ind` valid for
   DevBuf<int32_t> ind;
   DevBuf<float> partials;
-  ProbBlocks *d_probs = nullptr;
-  GNState *d_state = nullptr, *h_state = nullptr;  // h_state pinned: [0] the state, then 64 bytes of flags, then the ProbBlocks going up
+  DevBuf<ProbBlocks> d_probs;
+  DevBuf<GNState> d_state;
+  PinBuf<HostState> h_state;
   int32_t nb_on_device = -1;
-  uint32_t *d_flags = nullptr;
+  DevBuf<uint32_t> d_flags;  // [16]
   float4 *h_last = nullptr;  // pinned staging of the last clouds going out (= h_own, or a buffer of the publishing ring)
   PinBuf<float4> h_own;
   // lslam_odom_set_publish: a ring of pinned buffers the last clouds are copied to with every sweep, handed out as views
@@ -865,16 +875,6 @@ void od_free(lslam_odom *od) {
   if (!od) return;
   (void)hipSetDevice(od->device);
   if (od->stream && lslam::ctx_alive(od->ctx)) (void)hipStreamSynchronize(od->stream);
-  for (Side &s : od->side) {
-    if (s.start) (void)hipFree(s.start);
-    if (s.hdr) (void)hipFree(s.hdr);
-  }
-  if (od->cnt) (void)hipFree(od->cnt);
-  if (od->cursor) (void)hipFree(od->cursor);
-  if (od->d_probs) (void)hipFree(od->d_probs);
-  if (od->d_state) (void)hipFree(od->d_state);
-  if (od->d_flags) (void)hipFree(od->d_flags);
-  if (od->h_state) (void)hipHostFree(od->h_state);
   if (od->ev0) (void)hipEventDestroy(od->ev0);
   if (od->ev1) (void)hipEventDestroy(od->ev1);
   if (od->own_fs) lslam_fset_destroy(od->own_fs);
@@ -899,17 +899,16 @@ int od_create(lslam_ctx *ctx, int32_t max_iterations, float dt, float dr, lslam_
   hipError_t e;
   if ((e = hipSetDevice(od->device)) != hipSuccess) return fail(e);
   for (Side &s : od->side) {
-    if ((e = hipMalloc((void **)&s.start, 4 * (size_t)(OH_SIZE + 1) * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc((void **)&s.hdr, 64 + 2 * (OH_RINGS + 1) * 4)) != hipSuccess) return fail(e);
+    if ((e = s.start.alloc(4 * (size_t)(OH_SIZE + 1))) != hipSuccess) return fail(e);
+    if ((e = s.hdr.alloc(16 + 2 * (OH_RINGS + 1))) != hipSuccess) return fail(e);
   }
-
-  if ((e = hipMalloc((void **)&od->cnt, 4 * (size_t)OH_SIZE * 4)) != hipSuccess) return fail(e);
-  if ((e = hipMalloc((void **)&od->cursor, 4 * (size_t)OH_SIZE * 4)) != hipSuccess) return fail(e);
-  if ((e = hipMemsetAsync(od->cnt, 0, 4 * (size_t)OH_SIZE * 4, od->stream)) != hipSuccess) return fail(e);
-  if ((e = hipMalloc((void **)&od->d_probs, sizeof(ProbBlocks))) != hipSuccess) return fail(e);
-  if ((e = hipMalloc((void **)&od->d_state, sizeof(GNState))) != hipSuccess) return fail(e);
-  if ((e = hipMalloc((void **)&od->d_flags, 64)) != hipSuccess) return fail(e);
-  if ((e = hipHostMalloc((void **)&od->h_state, sizeof(GNState) + 128, hipHostMallocDefault)) != hipSuccess) return fail(e);
+  if ((e = od->cnt.alloc(4 * (size_t)OH_SIZE)) != hipSuccess) return fail(e);
+  if ((e = od->cursor.alloc(4 * (size_t)OH_SIZE)) != hipSuccess) return fail(e);
+  if ((e = hipMemsetAsync(od->cnt.p, 0, 4 * (size_t)OH_SIZE * 4, od->stream)) != hipSuccess) return fail(e);
+  if ((e = od->d_probs.alloc(1)) != hipSuccess) return fail(e);
+  if ((e = od->d_state.alloc(1)) != hipSuccess) return fail(e);
+  if ((e = od->d_flags.alloc(16)) != hipSuccess) return fail(e);
+  if ((e = od->h_state.alloc(1)) != hipSuccess) return fail(e);
   if ((e = hipEventCreate(&od->ev0)) != hipSuccess) return fail(e);
   if ((e = hipEventCreate(&od->ev1)) != hipSuccess) return fail(e);
   if ((e = hipStreamSynchronize(od->stream)) != hipSuccess) return fail(e);
@@ -934,7 +933,7 @@ struct HostSinCosF {
   }
 };
 
-uint32_t *h_flags_of(lslam_odom *od) { return reinterpret_cast<uint32_t *>(od->h_state + 1); }
+uint32_t *h_flags_of(lslam_odom *od) { return od->h_state.p->flags; }
 
 // K1-K3: src lists -> side `to`'s clouds (moved to the sweep end with the pose of d_state when to_end) and their grids.
 // gate: the launches only act once the loop of d_state has ended.
@@ -954,25 +953,25 @@ int enqueue_build(lslam_odom *od, int to, const float4 *less_sharp, size_t n_ls,
   pa.src[0] = less_sharp; pa.src[1] = less_flat;
   pa.n[0] = (int32_t)n_ls; pa.n[1] = (int32_t)n_lf;
   pa.org[0] = S.org[0].p; pa.org[1] = S.org[1].p;
-  pa.cnt = od->cnt;
-  pa.hdr = S.hdr;
-  pa.ring_start = reinterpret_cast<int32_t *>(S.hdr + 16);
+  pa.cnt = od->cnt.p;
+  pa.hdr = S.hdr.p;
+  pa.ring_start = reinterpret_cast<int32_t *>(S.hdr.p + 16);
   if (n_ls >= (1u << OH_IDX_BITS) || n_lf >= (1u << OH_IDX_BITS)) {
     lslam::set_error("a last cloud of more than 16 777 215 points");
     return LSLAM_ERR_INVALID;
   }
-  OD_TRY(hipMemsetAsync(S.hdr, 0, 8, od->stream));
-  OD_TRY(hipMemsetAsync(od->cnt, 0, 4 * (size_t)OH_SIZE * 4, od->stream));
-  pa.gate = (gated || to_end) ? od->d_state : nullptr;
+  OD_TRY(hipMemsetAsync(S.hdr.p, 0, 8, od->stream));
+  OD_TRY(hipMemsetAsync(od->cnt.p, 0, 4 * (size_t)OH_SIZE * 4, od->stream));
+  pa.gate = (gated || to_end) ? od->d_state.p : nullptr;
   pa.to_end = to_end ? 1 : 0;
   // (an ungated move to the end still reads the pose from d_state: the caller has put it there and marked it done)
   const unsigned nb = (unsigned)((n + 255) / 256);
   if (nb) hipLaunchKernelGGL(odom_prep_kernel, dim3(nb), dim3(256), 0, od->stream, pa);
-  hipLaunchKernelGGL(odom_scan_kernel, dim3(16, 4), dim3(256), 0, od->stream, od->cnt, S.start, od->cursor, pa.gate);
+  hipLaunchKernelGGL(odom_scan_kernel, dim3(16, 4), dim3(256), 0, od->stream, od->cnt.p, S.start.p, od->cursor.p, pa.gate);
   ScatterArgs sa{};
   sa.org[0] = S.org[0].p; sa.org[1] = S.org[1].p;
   sa.n[0] = (int32_t)n_ls; sa.n[1] = (int32_t)n_lf;
-  sa.cursor = od->cursor;
+  sa.cursor = od->cursor.p;
   for (int k = 0; k < 4; ++k) sa.sorted[k] = S.sorted[k].p;
   sa.gate = pa.gate;
   if (nb) hipLaunchKernelGGL(odom_scatter_kernel, dim3(nb), dim3(256), 0, od->stream, sa);
@@ -1029,12 +1028,12 @@ int loop_setup(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   oa.sel = nullptr;
   oa.coeff = nullptr;
   oa.mode = 2;
-  oa.state = od->d_state;
+  oa.state = od->d_state.p;
   OD_TRY(od->partials.reserve((size_t)(oa.nb_total ? oa.nb_total : 1) * NCOL));
   oa.partials = od->partials.p;
   SearchArgs &sa = L.sa;
   for (int c = 0; c < 2; ++c) {
-    sa.h[c].start = S.start + (size_t)(2 * c) * (OH_SIZE + 1);
+    sa.h[c].start = S.start.p + (size_t)(2 * c) * (OH_SIZE + 1);
     sa.h[c].pts[0] = S.sorted[2 * c].p;
     sa.h[c].pts[1] = S.sorted[2 * c + 1].p;
     sa.h[c].n = (int32_t)S.n[c];
@@ -1044,10 +1043,10 @@ int loop_setup(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   sa.q[0] = sharp; sa.q[1] = flat;
   sa.nq[0] = (int32_t)n_sharp; sa.nq[1] = (int32_t)n_flat;
   sa.ind = od->ind.p;
-  sa.state = od->d_state;
-  sa.flags = od->d_flags;
-  sa.hdr = S.hdr;
-  sa.ring_start = reinterpret_cast<const int32_t *>(S.hdr + 16);
+  sa.state = od->d_state.p;
+  sa.flags = od->d_flags.p;
+  sa.hdr = S.hdr.p;
+  sa.ring_start = reinterpret_cast<const int32_t *>(S.hdr.p + 16);
   sa.literal_window = od->literal_window;
   sa.dbg = nullptr;
   if (od->dbg_on) {
@@ -1058,16 +1057,16 @@ int loop_setup(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   }
   sa.nf_slack = od->nf_slack;
   if (od->nb_on_device != oa.nb_total) {
-    ProbBlocks *pb = reinterpret_cast<ProbBlocks *>(h_flags_of(od) + 16);  // pinned
+    ProbBlocks *pb = &od->h_state.p->probs;  // pinned
     pb->first_block = 0;
     pb->n_blocks = oa.nb_total;
-    OD_TRY(hipMemcpyAsync(od->d_probs, pb, sizeof(ProbBlocks), hipMemcpyHostToDevice, od->stream));
+    OD_TRY(hipMemcpyAsync(od->d_probs.p, pb, sizeof(ProbBlocks), hipMemcpyHostToDevice, od->stream));
     od->nb_on_device = oa.nb_total;
   }
   SolveArgs &so = L.so;
-  so.states = od->d_state;
+  so.states = od->d_state.p;
   so.partials = od->partials.p;
-  so.probs = od->d_probs;
+  so.probs = od->d_probs.p;
   so.n_prob = 1;
   so.max_iterations = od->max_it;
   so.delta_r_abort = od->dr;
@@ -1079,8 +1078,8 @@ int loop_setup(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   GnSegArgs &ga = L.ga;
   ga.oa = oa;
   ga.slots = nullptr;  // loop_slots
-  ga.abort = od->d_flags + 1;
-  ga.state = od->d_state;
+  ga.abort = od->d_flags.p + 1;
+  ga.state = od->d_state.p;
   ga.sp.max_iterations = so.max_iterations;
   ga.sp.min_rows = so.min_rows;
   ga.sp.too_few_continue = so.too_few_continue;
@@ -1103,14 +1102,14 @@ int loop_slots(lslam_odom *od, LoopSetup &L) {
 
 // the loop's state as the reference enters an iteration with `pose`: into h_state, and from there to the device
 int loop_state_up(lslam_odom *od, const float pose[6], int32_t loop_iter, bool done) {
-  GNState *hs = od->h_state;
+  GNState *hs = &od->h_state.p->state;
   std::memset(hs, 0, sizeof(GNState));
   for (int i = 0; i < 6; ++i) hs->pose[i] = pose[i];
   pose_to_Rt_sc(pose, hs->R, hs->t, hs->sc, HostSinCosF());
   hs->loop_iter = loop_iter;
   hs->done = done ? 1 : 0;
-  OD_TRY(hipMemcpyAsync(od->d_state, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
-  OD_TRY(hipMemsetAsync(od->d_flags, 0, 64, od->stream));
+  OD_TRY(hipMemcpyAsync(od->d_state.p, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
+  OD_TRY(hipMemsetAsync(od->d_flags.p, 0, 64, od->stream));
   return LSLAM_OK;
 }
 
@@ -1127,7 +1126,7 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   const SearchArgs &sa = L.sa;
   const SolveArgs &so = L.so;
   GnSegArgs &ga = L.ga;
-  GNState *hs = od->h_state;
+  GNState *hs = &od->h_state.p->state;
   const int max_it = od->max_it;
   rc0 = loop_state_up(od, pose, 0, max_it == 0 || oa.nb_total == 0);
   if (rc0) return rc0;
@@ -1160,8 +1159,8 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
       OD_TRY(hipEventRecord(od->ev1, od->stream));
       int rc = enqueue_tail(od, tail, true);
       if (rc) return rc;
-      OD_TRY(hipMemcpyAsync(hs, od->d_state, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
-      OD_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags, 64, hipMemcpyDeviceToHost, od->stream));
+      OD_TRY(hipMemcpyAsync(hs, od->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
+      OD_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags.p, 64, hipMemcpyDeviceToHost, od->stream));
       OD_TRY(hipStreamSynchronize(od->stream));
       if (h_flags_of(od)[1] != 0u) {  // an exchange gave up: this match again by launches, and launches from now on
         od->persistent_ok = false;
@@ -1189,8 +1188,8 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
     OD_TRY(hipEventRecord(od->ev1, od->stream));
     int rc = enqueue_tail(od, tail, true);
     if (rc) return rc;
-    OD_TRY(hipMemcpyAsync(hs, od->d_state, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
-    OD_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags, 64, hipMemcpyDeviceToHost, od->stream));
+    OD_TRY(hipMemcpyAsync(hs, od->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
+    OD_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags.p, 64, hipMemcpyDeviceToHost, od->stream));
     OD_TRY(hipStreamSynchronize(od->stream));
     if (hs->done || launched >= max_it) break;
     batch = 10;
@@ -1451,9 +1450,9 @@ int lslam_debug_odom_step(lslam_odom *od, lslam_fset *fs, const float pose[6], i
     OD_TRY(launch_solve(L.so, od->stream));
   }
   OD_TRY(hipGetLastError());
-  GNState *hs = od->h_state;
-  OD_TRY(hipMemcpyAsync(hs, od->d_state, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
-  OD_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags, 64, hipMemcpyDeviceToHost, od->stream));
+  GNState *hs = &od->h_state.p->state;
+  OD_TRY(hipMemcpyAsync(hs, od->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
+  OD_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags.p, 64, hipMemcpyDeviceToHost, od->stream));
   if (ind_out) OD_TRY(hipMemcpyAsync(ind_out, od->ind.p, 3 * nq * sizeof(int32_t), hipMemcpyDeviceToHost, od->stream));
   std::vector<float4> hsel, hco;
   if (path == 0 && (sel_out || kept_out)) {
@@ -1609,11 +1608,11 @@ int lslam_odom_process(lslam_odom *od, lslam_fset *fs, float transform[6], float
         if (rc < 0) return rc;
         od->tree_fallbacks++;
         // the next last clouds with THAT pose
-        GNState *hs = od->h_state;
+        GNState *hs = &od->h_state.p->state;
         std::memset(hs, 0, sizeof(GNState));
         for (int i = 0; i < 6; ++i) hs->pose[i] = pose[i];
         hs->done = 1;
-        OD_TRY(hipMemcpyAsync(od->d_state, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
+        OD_TRY(hipMemcpyAsync(od->d_state.p, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
         rc = enqueue_tail(od, tail, false);
         if (rc) return rc;
         OD_TRY(hipStreamSynchronize(od->stream));
@@ -1622,11 +1621,11 @@ int lslam_odom_process(lslam_odom *od, lslam_fset *fs, float transform[6], float
       status = st.status;
       matched = 1;
     } else {  // nothing to match against: _transform stays, the clouds still move on (:305-316)
-      GNState *hs = od->h_state;
+      GNState *hs = &od->h_state.p->state;
       std::memset(hs, 0, sizeof(GNState));
       for (int i = 0; i < 6; ++i) hs->pose[i] = od->transform[i];
       hs->done = 1;
-      OD_TRY(hipMemcpyAsync(od->d_state, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
+      OD_TRY(hipMemcpyAsync(od->d_state.p, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
       int rc = enqueue_tail(od, tail, false);
       if (rc) return rc;
       OD_TRY(hipStreamSynchronize(od->stream));

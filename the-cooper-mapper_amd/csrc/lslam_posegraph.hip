@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/lslam_c.h"
+#include "lslam_buf.hpp"
 
 namespace lslam {  // lslam_comm.hip
 hipError_t comm_allreduce_f64(lslam_comm *comm, double *buf, size_t count, hipStream_t s);
@@ -1557,10 +1558,10 @@ thread_local std::string g_pg_err;
   } while (0)
 
 template <typename T>
-hipError_t dev_upload(T **d, const std::vector<T> &h) {
-  hipError_t e = hipMalloc((void **)d, std::max<size_t>(1, h.size()) * sizeof(T));
+hipError_t dev_upload(lslam::DevBuf<T> &d, const std::vector<T> &h) {
+  hipError_t e = d.alloc(h.size());
   if (e != hipSuccess) return e;
-  if (!h.empty()) e = hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+  if (!h.empty()) e = hipMemcpy(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
   return e;
 }
 
@@ -1607,29 +1608,28 @@ struct lslam_pg {
     return lslam::comm_allgatherv_f64(comm, n_lists, bufs, offs, stream) == hipSuccess ? LSLAM_OK : LSLAM_ERR_COMM;
   }
   // graph
-  double *d_poses = nullptr, *d_trial = nullptr, *d_meas = nullptr, *d_info = nullptr;
-  int32_t *d_ij = nullptr;
+  lslam::DevBuf<double> d_poses, d_trial, d_meas, d_info;
+  lslam::DevBuf<int32_t> d_ij;
   std::vector<int32_t> h_ij;
   std::vector<int32_t> edge_block;  // per edge: off-diagonal block id
   std::vector<int32_t> off_pairs;   // [n_off][2]
   // shard structures
-  double *d_rec = nullptr, *d_chi = nullptr;
-  int32_t *d_vptr = nullptr, *d_vadj = nullptr, *d_optr = nullptr, *d_oadj = nullptr;
-  // system buffer [diag | off | b | chi2]; owned unless supplied by the caller
-  double *d_sys = nullptr;
-  bool own_sys = true;
+  lslam::DevBuf<double> d_rec, d_chi;
+  lslam::DevBuf<int32_t> d_vptr, d_vadj, d_optr, d_oadj;
+  // system buffer [diag | off | b | chi2]; owned unless supplied by the caller (adopted)
+  lslam::DevBuf<double> d_sys;
   // solver
-  int32_t *d_row_ptr = nullptr, *d_row_col = nullptr, *d_row_src = nullptr, *d_row_of = nullptr;
-  double *d_vals = nullptr, *d_minv = nullptr;
-  double *d_x = nullptr, *d_r = nullptr, *d_z = nullptr, *d_p = nullptr, *d_q = nullptr;
-  double *d_part = nullptr, *d_scal = nullptr, *d_tmp = nullptr;
+  lslam::DevBuf<int32_t> d_row_ptr, d_row_col, d_row_src, d_row_of;
+  lslam::DevBuf<double> d_vals, d_minv;
+  lslam::DevBuf<double> d_x, d_r, d_z, d_p, d_q;
+  lslam::DevBuf<double> d_part, d_scal, d_tmp;
   int n_cg_blocks = 0;
   // second level of the preconditioner (rigid motions of graph aggregates of at most `agg` keyframes)
   std::vector<int32_t> h_row_of, h_row_col;
   int agg = 64, n_agg = 0, n_c = 0, n_cb = 0, n_cblk = 0, n_parts = 0;
-  int32_t *d_agg_of = nullptr, *d_agg_ptr = nullptr, *d_agg_mem = nullptr;
-  double *d_P = nullptr, *d_Ac = nullptr, *d_rc = nullptr, *d_yc = nullptr, *d_gj = nullptr;
-  int32_t *d_cb_ptr = nullptr, *d_cb_ent = nullptr, *d_cb_ab = nullptr;
+  lslam::DevBuf<int32_t> d_agg_of, d_agg_ptr, d_agg_mem;
+  lslam::DevBuf<double> d_P, d_Ac, d_rc, d_yc, d_gj;
+  lslam::DevBuf<int32_t> d_cb_ptr, d_cb_ent, d_cb_ab;
   // environment switches, read when the graph is created (lslam_pg_create) -- never while it is optimised
   bool env_no_reuse = false, env_persistent_off = false, env_debug = false;
   int env_max_cg = 20000;
@@ -1646,12 +1646,12 @@ struct lslam_pg {
   int coarse_fresh_iters = 0, coarse_last_iters = 0;
   int coarse_setups = 0;
   // persistent PCG kernel (pg_pcg_persistent_kernel): per-aggregate entry / column lists, its buffers, whether the graph fits
-  int32_t *d_bent_ptr = nullptr, *d_bent = nullptr, *d_blc = nullptr, *d_bmptr = nullptr, *d_bcol_ptr = nullptr, *d_bcol = nullptr;
-  double *d_pk = nullptr;      // [rc0 | rc1] then the exchange slots of pg_pcg_persistent_kernel
-  unsigned *d_bar = nullptr;
+  lslam::DevBuf<int32_t> d_bent_ptr, d_bent, d_blc, d_bmptr, d_bcol_ptr, d_bcol;
+  lslam::DevBuf<double> d_pk;      // [rc0 | rc1] then the exchange slots of pg_pcg_persistent_kernel
+  lslam::DevBuf<unsigned> d_bar;
   int pk_lds_cols = 0, pk_lds_items = 0;
   size_t pk_lds_bytes = 0;
-  double *d_gjslots = nullptr; // pgc_gj_persistent_kernel's pivot-row slots [n_agg][6][n_c]
+  lslam::DevBuf<double> d_gjslots; // pgc_gj_persistent_kernel's pivot-row slots [n_agg][6][n_c]
   int gj_fit = -1;             // as pk_fit, for the coarse inverse
   int pk_fit = -1;             // -1 not decided yet, 0 the multi-launch loop, 1 the persistent kernel
   int fused_solves = 0, total_solves = 0, pk_timeouts = 0;
@@ -1665,21 +1665,16 @@ struct lslam_pg {
   size_t core_doubles() const { return (size_t)n_v * 36 + (size_t)n_off * 36 + (size_t)n_v * 6 + 2; }
   static constexpr int RS_MAX_WORLD = 64;  // ranks whose partial sums the exchange area has room for (gather mode)
   size_t sys_doubles() const { return core_doubles() + (size_t)n_v * 6 + 8 + 2 * RS_MAX_WORLD; }
-  double *xchg() const { return d_sys + core_doubles(); }
-  double *diag() const { return d_sys; }
-  double *off() const { return d_sys + (size_t)n_v * 36; }
-  double *b() const { return d_sys + (size_t)n_v * 36 + (size_t)n_off * 36; }
+  double *xchg() const { return d_sys.p + core_doubles(); }
+  double *diag() const { return d_sys.p; }
+  double *off() const { return d_sys.p + (size_t)n_v * 36; }
+  double *b() const { return d_sys.p + (size_t)n_v * 36 + (size_t)n_off * 36; }
   double *chi() const { return b() + (size_t)n_v * 6; }
 };
 
 namespace {
 
 int build_shard(lslam_pg *pg, int e_begin, int e_end) {
-  for (void *p : {(void *)pg->d_rec, (void *)pg->d_chi, (void *)pg->d_vptr, (void *)pg->d_vadj,
-                  (void *)pg->d_optr, (void *)pg->d_oadj})
-    if (p) (void)hipFree(p);
-  pg->d_rec = pg->d_chi = nullptr;
-  pg->d_vptr = pg->d_vadj = pg->d_optr = pg->d_oadj = nullptr;
   pg->e_begin = e_begin;
   pg->e_end = e_end;
   const int ne = e_end - e_begin;
@@ -1699,31 +1694,31 @@ int build_shard(lslam_pg *pg, int e_begin, int e_end) {
     vadj[vc[pg->h_ij[2 * e + 1]]++] = (le << 1) | 1;
     oadj[oc[pg->edge_block[e]]++] = le;
   }
-  PG_TRY(hipMalloc((void **)&pg->d_rec, std::max<size_t>(1, (size_t)ne) * REC * sizeof(double)));
-  PG_TRY(hipMalloc((void **)&pg->d_chi, std::max<size_t>(1, (size_t)ne) * sizeof(double)));
-  PG_TRY(dev_upload(&pg->d_vptr, vptr));
-  PG_TRY(dev_upload(&pg->d_vadj, vadj));
-  PG_TRY(dev_upload(&pg->d_optr, optr));
-  PG_TRY(dev_upload(&pg->d_oadj, oadj));
+  PG_TRY(pg->d_rec.alloc(std::max<size_t>(1, (size_t)ne) * REC));
+  PG_TRY(pg->d_chi.alloc((size_t)ne));
+  PG_TRY(dev_upload(pg->d_vptr, vptr));
+  PG_TRY(dev_upload(pg->d_vadj, vadj));
+  PG_TRY(dev_upload(pg->d_optr, optr));
+  PG_TRY(dev_upload(pg->d_oadj, oadj));
   return LSLAM_OK;
 }
 
-// system of this shard's edges into pg->d_sys, then the all-reduce over ranks
+// system of this shard's edges into pg->d_sys.p, then the all-reduce over ranks
 int linearize(lslam_pg *pg, const double *poses) {
   const int ne = pg->e_end - pg->e_begin;
   if (ne > 0)
-    hipLaunchKernelGGL(pg_edge_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij,
-                       pg->d_meas, pg->d_info, pg->e_begin, pg->e_end, pg->fixed, pg->d_rec, pg->d_chi);
+    hipLaunchKernelGGL(pg_edge_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij.p,
+                       pg->d_meas.p, pg->d_info.p, pg->e_begin, pg->e_end, pg->fixed, pg->d_rec.p, pg->d_chi.p);
   hipLaunchKernelGGL(pg_assemble_vertex_kernel, dim3((pg->n_v * 42 + 255) / 256), dim3(256), 0, pg->stream,
-                     pg->d_rec, pg->d_vptr, pg->d_vadj, pg->n_v, pg->sharded() ? -1 : pg->fixed,
+                     pg->d_rec.p, pg->d_vptr.p, pg->d_vadj.p, pg->n_v, pg->sharded() ? -1 : pg->fixed,
                      pg->diag(), pg->b());
   if (pg->n_off > 0)
     hipLaunchKernelGGL(pg_assemble_off_kernel, dim3((pg->n_off * 36 + 255) / 256), dim3(256), 0, pg->stream,
-                       pg->d_rec, pg->d_optr, pg->d_oadj, pg->n_off, pg->off());
-  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi, ne, 1, pg->chi());
+                       pg->d_rec.p, pg->d_optr.p, pg->d_oadj.p, pg->n_off, pg->off());
+  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne, 1, pg->chi());
   PG_TRY(hipGetLastError());
   if (pg->sharded()) {
-    const int rc = pg->reduce(pg->d_sys, pg->core_doubles());
+    const int rc = pg->reduce(pg->d_sys.p, pg->core_doubles());
     if (rc) return rc;
     // identity block of the fixed vertex after the sum over ranks
     static const double I[36] = {1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0,
@@ -1739,9 +1734,9 @@ int eval_chi2(lslam_pg *pg, const double *poses, double *out) {
   // back, and it lives in the buffer the all-reduce hook knows how to address
   const int ne = pg->e_end - pg->e_begin;
   if (ne > 0)
-    hipLaunchKernelGGL(pg_chi2_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij,
-                       pg->d_meas, pg->d_info, pg->e_begin, pg->e_end, pg->d_chi);
-  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi, ne, 1, pg->chi());
+    hipLaunchKernelGGL(pg_chi2_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij.p,
+                       pg->d_meas.p, pg->d_info.p, pg->e_begin, pg->e_end, pg->d_chi.p);
+  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne, 1, pg->chi());
   PG_TRY(hipGetLastError());
   if (pg->sharded()) {
     // chi2 and, next to it, whether this rank's persistent kernels gave way to their launch loops in the solve before:
@@ -1763,28 +1758,28 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
   const int n6 = pg->n_v * 6;
   const size_t n_items = (size_t)pg->n_entries * 6;
   hipLaunchKernelGGL(pg_expand_kernel, dim3((unsigned)((n_items * 6 + 255) / 256)), dim3(256), 0, pg->stream,
-                     pg->d_sys, pg->d_row_src, pg->n_entries, lambda, pg->d_vals);
-  hipLaunchKernelGGL(pg_precond_kernel, dim3((pg->n_v + 63) / 64), dim3(64), 0, pg->stream, pg->d_vals,
-                     pg->d_row_ptr, pg->n_v, n_items, pg->d_minv);
+                     pg->d_sys.p, pg->d_row_src.p, pg->n_entries, lambda, pg->d_vals.p);
+  hipLaunchKernelGGL(pg_precond_kernel, dim3((pg->n_v + 63) / 64), dim3(64), 0, pg->stream, pg->d_vals.p,
+                     pg->d_row_ptr.p, pg->n_v, n_items, pg->d_minv.p);
   CgArgs a;
-  a.vals = pg->d_vals;
-  a.row_ptr = pg->d_row_ptr;
-  a.row_col = pg->d_row_col;
-  a.row_of = pg->d_row_of;
-  a.minv = pg->d_minv;
+  a.vals = pg->d_vals.p;
+  a.row_ptr = pg->d_row_ptr.p;
+  a.row_col = pg->d_row_col.p;
+  a.row_of = pg->d_row_of.p;
+  a.minv = pg->d_minv.p;
   a.b = pg->b();
-  a.x = pg->d_x; a.r = pg->d_r; a.z = pg->d_z; a.d = pg->d_q;
-  a.p[0] = pg->d_p;
-  a.p[1] = pg->d_p + n6;
-  a.part_rz[0] = pg->d_part;
-  a.part_rz[1] = pg->d_part + pg->n_parts;
-  a.part_rr = pg->d_part + 2 * pg->n_parts;
-  a.part_pq = pg->d_part + 3 * pg->n_parts;
+  a.x = pg->d_x.p; a.r = pg->d_r.p; a.z = pg->d_z.p; a.d = pg->d_q.p;
+  a.p[0] = pg->d_p.p;
+  a.p[1] = pg->d_p.p + n6;
+  a.part_rz[0] = pg->d_part.p;
+  a.part_rz[1] = pg->d_part.p + pg->n_parts;
+  a.part_rr = pg->d_part.p + 2 * pg->n_parts;
+  a.part_pq = pg->d_part.p + 3 * pg->n_parts;
   a.n_parts = pg->n_parts;
-  PG_TRY(hipMemsetAsync(pg->d_part, 0, 3 * (size_t)pg->n_parts * sizeof(double), pg->stream));  // the coarse level's slots
+  PG_TRY(hipMemsetAsync(pg->d_part.p, 0, 3 * (size_t)pg->n_parts * sizeof(double), pg->stream));  // the coarse level's slots
   a.n_items = (int)n_items;
   a.n_pblocks = (int)((n_items + PROD_BLOCK - 1) / PROD_BLOCK);
-  a.scal = pg->d_scal;
+  a.scal = pg->d_scal.p;
   a.n6 = n6;
   a.n_blocks = pg->n_cg_blocks;
   a.tol2 = tol * tol;
@@ -1794,11 +1789,11 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
   bool fresh_inverse = false;
   CoarseArgs c{};
   if (coarse) {
-    c.poses = pg->d_poses;
-    c.P = pg->d_P; c.Ac = pg->d_Ac; c.rc = pg->d_rc; c.yc = pg->d_yc;
-    c.Rbuf = pg->d_gj; c.Cbuf = pg->d_gj + (size_t)6 * pg->n_c; c.Bbuf = pg->d_gj + (size_t)12 * pg->n_c;
-    c.cb_ptr = pg->d_cb_ptr; c.cb_ent = pg->d_cb_ent; c.cb_ab = pg->d_cb_ab;
-    c.agg_of = pg->d_agg_of; c.agg_ptr = pg->d_agg_ptr; c.agg_mem = pg->d_agg_mem;
+    c.poses = pg->d_poses.p;
+    c.P = pg->d_P.p; c.Ac = pg->d_Ac.p; c.rc = pg->d_rc.p; c.yc = pg->d_yc.p;
+    c.Rbuf = pg->d_gj.p; c.Cbuf = pg->d_gj.p + (size_t)6 * pg->n_c; c.Bbuf = pg->d_gj.p + (size_t)12 * pg->n_c;
+    c.cb_ptr = pg->d_cb_ptr.p; c.cb_ent = pg->d_cb_ent.p; c.cb_ab = pg->d_cb_ab.p;
+    c.agg_of = pg->d_agg_of.p; c.agg_ptr = pg->d_agg_ptr.p; c.agg_mem = pg->d_agg_mem.p;
     c.n_v = pg->n_v; c.G = pg->agg; c.na = pg->n_agg; c.n_c = pg->n_c; c.n_cb = pg->n_cb; c.n_cblk = pg->n_cblk;
     const size_t nn = (size_t)c.n_c * c.n_c;
     const bool no_reuse = pg->env_no_reuse;  // A/B switch (LSLAM_PG_NO_REUSE, read when the graph was created)
@@ -1808,16 +1803,16 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
       rebuild = !(ratio <= 10.0) || (pg->coarse_fresh_iters > 0 && 10 * pg->coarse_last_iters > 13 * pg->coarse_fresh_iters);
     }
     fresh_inverse = rebuild;
-    if (!pg->d_Ac) {  // first solve with the second level: its dense matrix and scratch
-      PG_TRY(hipMalloc((void **)&pg->d_Ac, nn * sizeof(double)));
-      PG_TRY(hipMalloc((void **)&pg->d_gj, ((size_t)12 * pg->n_c + 36) * sizeof(double)));
-      c.Ac = pg->d_Ac;
-      c.Rbuf = pg->d_gj; c.Cbuf = pg->d_gj + (size_t)6 * pg->n_c; c.Bbuf = pg->d_gj + (size_t)12 * pg->n_c;
+    if (!pg->d_Ac.p) {  // first solve with the second level: its dense matrix and scratch
+      PG_TRY(pg->d_Ac.alloc(nn));
+      PG_TRY(pg->d_gj.alloc((size_t)12 * pg->n_c + 36));
+      c.Ac = pg->d_Ac.p;
+      c.Rbuf = pg->d_gj.p; c.Cbuf = pg->d_gj.p + (size_t)6 * pg->n_c; c.Bbuf = pg->d_gj.p + (size_t)12 * pg->n_c;
     }
     if (rebuild) {
     hipLaunchKernelGGL(pgc_P_kernel, dim3((pg->n_v + 127) / 128), dim3(128), 0, pg->stream, c);
     PG_TRY(hipMemsetAsync(c.Ac, 0, nn * sizeof(double), pg->stream));
-    hipLaunchKernelGGL(pgc_assemble_kernel, dim3(c.n_cb), dim3(64), 0, pg->stream, c, pg->d_vals, pg->d_row_of, pg->d_row_col, n_items);
+    hipLaunchKernelGGL(pgc_assemble_kernel, dim3(c.n_cb), dim3(64), 0, pg->stream, c, pg->d_vals.p, pg->d_row_of.p, pg->d_row_col.p, n_items);
     if (pg->gj_fit < 0) {  // the persistent inverse when a workgroup per aggregate is co-resident and the row fits its registers
       pg->gj_fit = 0;
       const bool off = pg->env_persistent_off;
@@ -1826,19 +1821,19 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
       if (!off && c.n_c <= GJ_CREG * GJ_BLOCK && hipGetDeviceProperties(&prop, pg->device) == hipSuccess &&
           hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pgc_gj_persistent_kernel, GJ_BLOCK, 0) == hipSuccess &&
           (long)per_cu * prop.multiProcessorCount >= c.na &&
-          hipMalloc((void **)&pg->d_gjslots, (size_t)c.na * 6 * c.n_c * sizeof(double)) == hipSuccess)
+          pg->d_gjslots.alloc((size_t)c.na * 6 * c.n_c) == hipSuccess)
         pg->gj_fit = 1;
       (void)hipGetLastError();
     }
     if (pg->gj_fit == 1) {
       GjArgs gj;
-      gj.Ac = c.Ac; gj.slots = pg->d_gjslots; gj.bar = pg->d_bar; gj.n_c = c.n_c; gj.na = c.na;
+      gj.Ac = c.Ac; gj.slots = pg->d_gjslots.p; gj.bar = pg->d_bar.p; gj.n_c = c.n_c; gj.na = c.na;
       {
         const char *da = lslam::debug_env("LSLAM_DEBUG_GJ_ABORT");  // test hook (LSLAM_DEBUG_HOOKS=1)
         gj.debug_abort = da ? std::atoi(da) : -1;
       }
-      PG_TRY(hipMemsetAsync(pg->d_bar, 0, 2 * sizeof(unsigned), pg->stream));
-      PG_TRY(hipMemsetD32Async((hipDeviceptr_t)pg->d_gjslots, (int)PK_SENT32, (size_t)c.na * 6 * c.n_c * 2, pg->stream));
+      PG_TRY(hipMemsetAsync(pg->d_bar.p, 0, 2 * sizeof(unsigned), pg->stream));
+      PG_TRY(hipMemsetD32Async((hipDeviceptr_t)pg->d_gjslots.p, (int)PK_SENT32, (size_t)c.na * 6 * c.n_c * 2, pg->stream));
       void *gargs[] = {(void *)&gj};
       unsigned gbar[2] = {0, 0};
       if (hipLaunchCooperativeKernel((const void *)pgc_gj_persistent_kernel, dim3((unsigned)c.na), dim3(GJ_BLOCK), gargs, 0, pg->stream) != hipSuccess) {
@@ -1847,7 +1842,7 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
         (void)hipGetLastError();
         gbar[1] = 1;
       } else {
-        PG_TRY(hipMemcpyAsync(gbar, pg->d_bar, sizeof(gbar), hipMemcpyDeviceToHost, pg->stream));
+        PG_TRY(hipMemcpyAsync(gbar, pg->d_bar.p, sizeof(gbar), hipMemcpyDeviceToHost, pg->stream));
         PG_TRY(hipStreamSynchronize(pg->stream));
       }
       if (gbar[1] != 0) {  // not all workgroups resident at once (see the PCG kernel's fallback): the launch loop inverts A_c,
@@ -1857,7 +1852,7 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
         pg->pk_timeouts++;
         pg->fell_back = true;
         PG_TRY(hipMemsetAsync(c.Ac, 0, nn * sizeof(double), pg->stream));
-        hipLaunchKernelGGL(pgc_assemble_kernel, dim3(c.n_cb), dim3(64), 0, pg->stream, c, pg->d_vals, pg->d_row_of, pg->d_row_col, n_items);
+        hipLaunchKernelGGL(pgc_assemble_kernel, dim3(c.n_cb), dim3(64), 0, pg->stream, c, pg->d_vals.p, pg->d_row_of.p, pg->d_row_col.p, n_items);
       }
     }
     if (pg->gj_fit != 1) {
@@ -1972,17 +1967,17 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
       }
       it += chunk;
       hipLaunchKernelGGL(pg_cg_check_kernel, dim3(1), blk, 0, pg->stream, a, it);
-      PG_TRY(hipMemcpyAsync(scal, pg->d_scal, sizeof(scal), hipMemcpyDeviceToHost, pg->stream));
+      PG_TRY(hipMemcpyAsync(scal, pg->d_scal.p, sizeof(scal), hipMemcpyDeviceToHost, pg->stream));
       PG_TRY(hipStreamSynchronize(pg->stream));
       done_iters = (int)scal[6];
       if (scal[5] != 0.0) break;
     }
     // the solution: every rank's rows, gathered the same way
-    hipLaunchKernelGGL(pg_rs_pack_kernel, gall, b256, 0, pg->stream, (const double *)pg->d_x, X, n6, r0, r1);
+    hipLaunchKernelGGL(pg_rs_pack_kernel, gall, b256, 0, pg->stream, (const double *)pg->d_x.p, X, n6, r0, r1);
     PG_TRY(hipGetLastError());
     int rc = gather ? pg->gather(1, g_bufs, g_offs, g_world) : pg->reduce(X, (size_t)n6);
     if (rc) return rc;
-    PG_TRY(hipMemcpyAsync(pg->d_x, X, (size_t)n6 * sizeof(double), hipMemcpyDeviceToDevice, pg->stream));
+    PG_TRY(hipMemcpyAsync(pg->d_x.p, X, (size_t)n6 * sizeof(double), hipMemcpyDeviceToDevice, pg->stream));
     *iters_out = done_iters;
     pg->total_solves++;
     pg->rs_solves++;
@@ -2007,18 +2002,18 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
   pg->total_solves++;
   if (pg->pk_fit == 1) {
     PkArgs k;
-    k.vals = pg->d_vals; k.minv = pg->d_minv; k.b = pg->b();
-    k.x = pg->d_x; k.p0 = pg->d_p; k.p1 = pg->d_p + n6;
-    k.agg_ptr = pg->d_agg_ptr; k.agg_mem = pg->d_agg_mem;
-    k.bent_ptr = pg->d_bent_ptr; k.bent = pg->d_bent; k.blc = pg->d_blc; k.bmptr = pg->d_bmptr;
-    k.bcol_ptr = pg->d_bcol_ptr; k.bcol = pg->d_bcol;
-    k.P = pg->d_P; k.Ainv = pg->d_Ac;
-    k.rc0 = pg->d_pk; k.rc1 = pg->d_pk + pg->n_c;
-    double *slots = pg->d_pk + 2 * (size_t)pg->n_c;
+    k.vals = pg->d_vals.p; k.minv = pg->d_minv.p; k.b = pg->b();
+    k.x = pg->d_x.p; k.p0 = pg->d_p.p; k.p1 = pg->d_p.p + n6;
+    k.agg_ptr = pg->d_agg_ptr.p; k.agg_mem = pg->d_agg_mem.p;
+    k.bent_ptr = pg->d_bent_ptr.p; k.bent = pg->d_bent.p; k.blc = pg->d_blc.p; k.bmptr = pg->d_bmptr.p;
+    k.bcol_ptr = pg->d_bcol_ptr.p; k.bcol = pg->d_bcol.p;
+    k.P = pg->d_P.p; k.Ainv = pg->d_Ac.p;
+    k.rc0 = pg->d_pk.p; k.rc1 = pg->d_pk.p + pg->n_c;
+    double *slots = pg->d_pk.p + 2 * (size_t)pg->n_c;
     const size_t n_slots = 2 * (size_t)n6 + 6 * (size_t)pg->n_agg + 2 * (size_t)pg->n_c;
     k.zA = slots; k.rzA = k.zA + 2 * (size_t)n6; k.rrA = k.rzA + 2 * pg->n_agg; k.pqB = k.rrA + 2 * pg->n_agg;
     k.qcB = k.pqB + 2 * pg->n_agg;
-    k.scal = pg->d_scal; k.bar = pg->d_bar;
+    k.scal = pg->d_scal.p; k.bar = pg->d_bar.p;
     k.n_items = n_items;
     k.n6 = n6; k.n_agg = pg->n_agg; k.n_c = pg->n_c; k.coarse = coarse ? 1 : 0; k.max_iter = max_cg;
     k.lds_cols = pg->pk_lds_cols; k.lds_items = pg->pk_lds_items;
@@ -2027,7 +2022,7 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
       const char *da = lslam::debug_env("LSLAM_DEBUG_PG_ABORT");  // test hook (LSLAM_DEBUG_HOOKS=1)
       k.debug_abort = da ? std::atoi(da) : -1;
     }
-    PG_TRY(hipMemsetAsync(pg->d_bar, 0, 2 * sizeof(unsigned), pg->stream));
+    PG_TRY(hipMemsetAsync(pg->d_bar.p, 0, 2 * sizeof(unsigned), pg->stream));
     PG_TRY(hipMemsetD32Async((hipDeviceptr_t)slots, (int)PK_SENT32, 2 * n_slots, pg->stream));
     void *kargs[] = {(void *)&k};
     double scal[8] = {0};
@@ -2037,8 +2032,8 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
       (void)hipGetLastError();  // as for the coarse inverse: a refused cooperative launch means the launch loop, not a failed solve
       bar[1] = 1;
     } else {
-      PG_TRY(hipMemcpyAsync(scal, pg->d_scal, sizeof(scal), hipMemcpyDeviceToHost, pg->stream));
-      PG_TRY(hipMemcpyAsync(bar, pg->d_bar, sizeof(bar), hipMemcpyDeviceToHost, pg->stream));
+      PG_TRY(hipMemcpyAsync(scal, pg->d_scal.p, sizeof(scal), hipMemcpyDeviceToHost, pg->stream));
+      PG_TRY(hipMemcpyAsync(bar, pg->d_bar.p, sizeof(bar), hipMemcpyDeviceToHost, pg->stream));
       PG_TRY(hipStreamSynchronize(pg->stream));
     }
     if (bar[1] == 0) {
@@ -2079,7 +2074,7 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
     }
     it += chunk;
     hipLaunchKernelGGL(pg_cg_check_kernel, dim3(1), blk, 0, pg->stream, a, it);
-    PG_TRY(hipMemcpyAsync(scal, pg->d_scal, sizeof(scal), hipMemcpyDeviceToHost, pg->stream));
+    PG_TRY(hipMemcpyAsync(scal, pg->d_scal.p, sizeof(scal), hipMemcpyDeviceToHost, pg->stream));
     PG_TRY(hipStreamSynchronize(pg->stream));
     done_iters = (int)scal[6];
     if (scal[5] != 0.0) break;
@@ -2242,9 +2237,9 @@ int lslam_pg_create(int device, int32_t n_v, const double *poses7, int32_t n_e, 
     pg->n_agg = (int)agg_ptr.size() - 1;
     pg->n_c = 6 * pg->n_agg;
     pg->n_cblk = pg->n_agg;  // partial-sum slots of the coarse level: one per aggregate (pgc_mvp_kernel)
-    PG_TRY(dev_upload(&pg->d_agg_of, agg_of));
-    PG_TRY(dev_upload(&pg->d_agg_ptr, agg_ptr));
-    PG_TRY(dev_upload(&pg->d_agg_mem, agg_mem));
+    PG_TRY(dev_upload(pg->d_agg_of, agg_of));
+    PG_TRY(dev_upload(pg->d_agg_ptr, agg_ptr));
+    PG_TRY(dev_upload(pg->d_agg_mem, agg_mem));
     std::map<std::pair<int, int>, std::vector<int32_t>> cb;
     for (int e = 0; e < pg->n_entries; ++e) cb[{agg_of[(size_t)rof[(size_t)e]], agg_of[(size_t)rcol[(size_t)e]]}].push_back(e);
     std::vector<int32_t> cptr(1, 0), cent, cab;
@@ -2255,12 +2250,12 @@ int lslam_pg_create(int device, int32_t n_v, const double *poses7, int32_t n_e, 
       cptr.push_back((int32_t)cent.size());
     }
     pg->n_cb = (int)cb.size();
-    PG_TRY(dev_upload(&pg->d_cb_ptr, cptr));
-    PG_TRY(dev_upload(&pg->d_cb_ent, cent));
-    PG_TRY(dev_upload(&pg->d_cb_ab, cab));
-    PG_TRY(hipMalloc((void **)&pg->d_P, (size_t)n_v * 36 * sizeof(double)));
-    PG_TRY(hipMalloc((void **)&pg->d_rc, (size_t)pg->n_c * sizeof(double)));
-    PG_TRY(hipMalloc((void **)&pg->d_yc, (size_t)pg->n_c * sizeof(double)));
+    PG_TRY(dev_upload(pg->d_cb_ptr, cptr));
+    PG_TRY(dev_upload(pg->d_cb_ent, cent));
+    PG_TRY(dev_upload(pg->d_cb_ab, cab));
+    PG_TRY(pg->d_P.alloc((size_t)n_v * 36));
+    PG_TRY(pg->d_rc.alloc((size_t)pg->n_c));
+    PG_TRY(pg->d_yc.alloc((size_t)pg->n_c));
     // the dense coarse matrix (n_c^2 doubles) and the Gauss-Jordan scratch are allocated by the first solve that takes the
     // second level (solve()); graphs whose coarse matrix would exceed PG_COARSE_MAX unknowns never take it
     if (pg->n_c > PG_COARSE_MAX) {
@@ -2308,42 +2303,42 @@ int lslam_pg_create(int device, int32_t n_v, const double *poses7, int32_t n_e, 
       if (std::getenv("LSLAM_DEBUG"))
         fprintf(stderr, "[lslam pg] %d aggregates, widest: %d columns, %d items; persistent-kernel LDS %zu bytes\n", pg->n_agg,
                 max_cols, max_items, pg->pk_lds_bytes);
-      PG_TRY(dev_upload(&pg->d_bent_ptr, bent_ptr));
-      PG_TRY(dev_upload(&pg->d_bent, bent));
-      PG_TRY(dev_upload(&pg->d_blc, blc));
-      PG_TRY(dev_upload(&pg->d_bmptr, bmptr));
-      PG_TRY(dev_upload(&pg->d_bcol_ptr, bcol_ptr));
-      PG_TRY(dev_upload(&pg->d_bcol, bcol));
+      PG_TRY(dev_upload(pg->d_bent_ptr, bent_ptr));
+      PG_TRY(dev_upload(pg->d_bent, bent));
+      PG_TRY(dev_upload(pg->d_blc, blc));
+      PG_TRY(dev_upload(pg->d_bmptr, bmptr));
+      PG_TRY(dev_upload(pg->d_bcol_ptr, bcol_ptr));
+      PG_TRY(dev_upload(pg->d_bcol, bcol));
       // [rc0 | rc1] then the sentinel-initialised slots [zA 2 n6 | rzA 2 n_agg | rrA 2 n_agg | pqB 2 n_agg | qcB 2 n_c]
-      PG_TRY(hipMalloc((void **)&pg->d_pk, (4 * (size_t)pg->n_c + 6 * (size_t)pg->n_agg + 12 * (size_t)n_v) * sizeof(double)));
-      PG_TRY(hipMalloc((void **)&pg->d_bar, 2 * sizeof(unsigned)));
+      PG_TRY(pg->d_pk.alloc(4 * (size_t)pg->n_c + 6 * (size_t)pg->n_agg + 12 * (size_t)n_v));
+      PG_TRY(pg->d_bar.alloc(2));
     }
   }
   std::vector<double> hp(poses7, poses7 + 7 * (size_t)n_v), hm(meas7, meas7 + 7 * (size_t)n_e),
       hi(info36, info36 + 36 * (size_t)n_e);
-  PG_TRY(dev_upload(&pg->d_poses, hp));
-  PG_TRY(dev_upload(&pg->d_trial, hp));
-  PG_TRY(dev_upload(&pg->d_meas, hm));
-  PG_TRY(dev_upload(&pg->d_info, hi));
-  PG_TRY(dev_upload(&pg->d_ij, pg->h_ij));
-  PG_TRY(dev_upload(&pg->d_row_ptr, rptr));
-  PG_TRY(dev_upload(&pg->d_row_col, rcol));
-  PG_TRY(dev_upload(&pg->d_row_src, rsrc));
-  PG_TRY(dev_upload(&pg->d_row_of, rof));
+  PG_TRY(dev_upload(pg->d_poses, hp));
+  PG_TRY(dev_upload(pg->d_trial, hp));
+  PG_TRY(dev_upload(pg->d_meas, hm));
+  PG_TRY(dev_upload(pg->d_info, hi));
+  PG_TRY(dev_upload(pg->d_ij, pg->h_ij));
+  PG_TRY(dev_upload(pg->d_row_ptr, rptr));
+  PG_TRY(dev_upload(pg->d_row_col, rcol));
+  PG_TRY(dev_upload(pg->d_row_src, rsrc));
+  PG_TRY(dev_upload(pg->d_row_of, rof));
   const size_t n6 = (size_t)n_v * 6;
   pg->n_cg_blocks = (int)((n6 + CG_ROWS - 1) / CG_ROWS);
   pg->n_parts = pg->n_cg_blocks + pg->n_cblk;
-  PG_TRY(hipMalloc((void **)&pg->d_sys, pg->sys_doubles() * sizeof(double)));
-  PG_TRY(hipMalloc((void **)&pg->d_vals, (size_t)pg->n_entries * 36 * sizeof(double)));
-  PG_TRY(hipMalloc((void **)&pg->d_minv, (size_t)n_v * 36 * sizeof(double)));
-  for (double **p : {&pg->d_x, &pg->d_r, &pg->d_z})
-    PG_TRY(hipMalloc((void **)p, n6 * sizeof(double)));
-  PG_TRY(hipMalloc((void **)&pg->d_q, (size_t)pg->n_entries * 6 * sizeof(double)));
-  PG_TRY(hipMalloc((void **)&pg->d_p, 2 * n6 * sizeof(double)));
-  PG_TRY(hipMalloc((void **)&pg->d_part, (3 * (size_t)pg->n_parts + ((size_t)pg->n_entries * 6 + PROD_BLOCK - 1) / PROD_BLOCK) * sizeof(double)));
-  PG_TRY(hipMalloc((void **)&pg->d_scal, 32 * sizeof(double)));
-  PG_TRY(hipMemset(pg->d_scal, 0, 32 * sizeof(double)));
-  PG_TRY(hipMalloc((void **)&pg->d_tmp, 8 * sizeof(double)));
+  PG_TRY(pg->d_sys.alloc(pg->sys_doubles()));
+  PG_TRY(pg->d_vals.alloc((size_t)pg->n_entries * 36));
+  PG_TRY(pg->d_minv.alloc((size_t)n_v * 36));
+  for (lslam::DevBuf<double> *p : {&pg->d_x, &pg->d_r, &pg->d_z})
+    PG_TRY(p->alloc(n6));
+  PG_TRY(pg->d_q.alloc((size_t)pg->n_entries * 6));
+  PG_TRY(pg->d_p.alloc(2 * n6));
+  PG_TRY(pg->d_part.alloc(3 * (size_t)pg->n_parts + ((size_t)pg->n_entries * 6 + PROD_BLOCK - 1) / PROD_BLOCK));
+  PG_TRY(pg->d_scal.alloc(32));
+  PG_TRY(hipMemset(pg->d_scal.p, 0, 32 * sizeof(double)));
+  PG_TRY(pg->d_tmp.alloc(8));
   int rc = build_shard(pg, 0, n_e);
   if (rc) return rc;
   guard.p = nullptr;
@@ -2355,18 +2350,6 @@ void lslam_pg_destroy(lslam_pg *pg) {
   if (!pg) return;
   (void)hipSetDevice(pg->device);
   if (pg->stream) (void)hipStreamSynchronize(pg->stream);
-  for (void *p : {(void *)pg->d_poses, (void *)pg->d_trial, (void *)pg->d_meas, (void *)pg->d_info,
-                  (void *)pg->d_ij, (void *)pg->d_rec, (void *)pg->d_chi, (void *)pg->d_vptr,
-                  (void *)pg->d_vadj, (void *)pg->d_optr, (void *)pg->d_oadj, (void *)pg->d_row_ptr,
-                  (void *)pg->d_row_col, (void *)pg->d_row_src, (void *)pg->d_row_of, (void *)pg->d_vals, (void *)pg->d_minv,
-                  (void *)pg->d_P, (void *)pg->d_Ac, (void *)pg->d_rc, (void *)pg->d_yc, (void *)pg->d_gj, (void *)pg->d_cb_ptr,
-                  (void *)pg->d_cb_ent, (void *)pg->d_cb_ab, (void *)pg->d_agg_of, (void *)pg->d_agg_ptr, (void *)pg->d_agg_mem,
-                  (void *)pg->d_x, (void *)pg->d_r, (void *)pg->d_z, (void *)pg->d_p, (void *)pg->d_q,
-                  (void *)pg->d_part, (void *)pg->d_scal, (void *)pg->d_tmp, (void *)pg->d_bent_ptr, (void *)pg->d_bent,
-                  (void *)pg->d_blc, (void *)pg->d_bmptr, (void *)pg->d_bcol_ptr, (void *)pg->d_bcol, (void *)pg->d_pk,
-                  (void *)pg->d_bar, (void *)pg->d_gjslots})
-    if (p) (void)hipFree(p);
-  if (pg->own_sys && pg->d_sys) (void)hipFree(pg->d_sys);
   if (pg->stream) (void)hipStreamDestroy(pg->stream);
   delete pg;
 }
@@ -2448,9 +2431,7 @@ int lslam_pg_set_shard(lslam_pg *pg, int32_t e_begin, int32_t e_end, lslam_allre
   pg->allreduce = fn;
   pg->allreduce_user = user;
   if (system_buf) {
-    if (pg->own_sys && pg->d_sys) (void)hipFree(pg->d_sys);
-    pg->d_sys = system_buf;
-    pg->own_sys = false;
+    pg->d_sys.adopt(system_buf, pg->sys_doubles());
   }
   return build_shard(pg, e_begin, e_end);
 }
@@ -2459,7 +2440,7 @@ int lslam_pg_linearize(lslam_pg *pg, double *diag_out, double *off_out, int32_t 
                        double *chi2_out) {
   if (!pg) return LSLAM_ERR_INVALID;
   PG_TRY(hipSetDevice(pg->device));
-  int rc = linearize(pg, pg->d_poses);
+  int rc = linearize(pg, pg->d_poses.p);
   if (rc) return rc;
   if (diag_out) PG_TRY(hipMemcpyAsync(diag_out, pg->diag(), (size_t)pg->n_v * 36 * 8, hipMemcpyDeviceToHost, pg->stream));
   if (off_out) PG_TRY(hipMemcpyAsync(off_out, pg->off(), (size_t)pg->n_off * 36 * 8, hipMemcpyDeviceToHost, pg->stream));
@@ -2475,7 +2456,7 @@ int lslam_pg_linearize(lslam_pg *pg, double *diag_out, double *off_out, int32_t 
 // every member, the fixed one included, and PCG then only drives that row back to within its tolerance (~1e-9 seen).
 static int zero_fixed_step(lslam_pg *pg) {
   if (pg->fixed < 0) return LSLAM_OK;
-  PG_TRY(hipMemsetAsync(pg->d_x + (size_t)pg->fixed * 6, 0, 6 * sizeof(double), pg->stream));
+  PG_TRY(hipMemsetAsync(pg->d_x.p + (size_t)pg->fixed * 6, 0, 6 * sizeof(double), pg->stream));
   return LSLAM_OK;
 }
 
@@ -2488,7 +2469,7 @@ int lslam_pg_solve(lslam_pg *pg, double lambda, double *dx_out, int32_t *cg_iter
   rc = zero_fixed_step(pg);
   if (rc) return rc;
   if (dx_out) {
-    PG_TRY(hipMemcpyAsync(dx_out, pg->d_x, (size_t)pg->n_v * 6 * 8, hipMemcpyDeviceToHost, pg->stream));
+    PG_TRY(hipMemcpyAsync(dx_out, pg->d_x.p, (size_t)pg->n_v * 6 * 8, hipMemcpyDeviceToHost, pg->stream));
     PG_TRY(hipStreamSynchronize(pg->stream));
   }
   if (cg_iters) *cg_iters = it;
@@ -2499,14 +2480,14 @@ int lslam_pg_solve(lslam_pg *pg, double lambda, double *dx_out, int32_t *cg_iter
 int lslam_pg_debug_clocks(lslam_pg *pg, double out[12]) {
   if (!pg || !out) return LSLAM_ERR_INVALID;
   PG_TRY(hipSetDevice(pg->device));
-  PG_TRY(hipMemcpy(out, pg->d_scal + 8, 12 * sizeof(double), hipMemcpyDeviceToHost));
+  PG_TRY(hipMemcpy(out, pg->d_scal.p + 8, 12 * sizeof(double), hipMemcpyDeviceToHost));
   return LSLAM_OK;
 }
 
 int lslam_pg_get_poses(lslam_pg *pg, double *poses7) {
   if (!pg || !poses7) return LSLAM_ERR_INVALID;
   PG_TRY(hipSetDevice(pg->device));
-  PG_TRY(hipMemcpyAsync(poses7, pg->d_poses, (size_t)pg->n_v * 7 * 8, hipMemcpyDeviceToHost, pg->stream));
+  PG_TRY(hipMemcpyAsync(poses7, pg->d_poses.p, (size_t)pg->n_v * 7 * 8, hipMemcpyDeviceToHost, pg->stream));
   PG_TRY(hipStreamSynchronize(pg->stream));
   return LSLAM_OK;
 }
@@ -2519,10 +2500,10 @@ int lslam_pg_save_g2o(lslam_pg *pg, const char *path) {
   if (!pg || !path) return LSLAM_ERR_INVALID;
   PG_TRY(hipSetDevice(pg->device));
   std::vector<double> poses((size_t)pg->n_v * 7), meas((size_t)pg->n_e * 7), info((size_t)pg->n_e * 36);
-  PG_TRY(hipMemcpyAsync(poses.data(), pg->d_poses, poses.size() * 8, hipMemcpyDeviceToHost, pg->stream));
+  PG_TRY(hipMemcpyAsync(poses.data(), pg->d_poses.p, poses.size() * 8, hipMemcpyDeviceToHost, pg->stream));
   if (pg->n_e) {
-    PG_TRY(hipMemcpyAsync(meas.data(), pg->d_meas, meas.size() * 8, hipMemcpyDeviceToHost, pg->stream));
-    PG_TRY(hipMemcpyAsync(info.data(), pg->d_info, info.size() * 8, hipMemcpyDeviceToHost, pg->stream));
+    PG_TRY(hipMemcpyAsync(meas.data(), pg->d_meas.p, meas.size() * 8, hipMemcpyDeviceToHost, pg->stream));
+    PG_TRY(hipMemcpyAsync(info.data(), pg->d_info.p, info.size() * 8, hipMemcpyDeviceToHost, pg->stream));
   }
   PG_TRY(hipStreamSynchronize(pg->stream));
   std::ofstream ofs(path);
@@ -2631,15 +2612,15 @@ int lslam_pg_optimize(lslam_pg *pg, int32_t max_iters, lslam_pg_stats *st_out) {
   const int fused0 = pg->fused_solves;
   double lambda = -1.0, ni = 2.0;
   for (int it = 0; it < max_iters; ++it) {
-    int rc = linearize(pg, pg->d_poses);
+    int rc = linearize(pg, pg->d_poses.p);
     if (rc) return rc;
     double cur;
     PG_TRY(hipMemcpyAsync(&cur, pg->chi(), 8, hipMemcpyDeviceToHost, pg->stream));
     if (lambda < 0) {
-      hipLaunchKernelGGL(pg_maxdiag_kernel, dim3(1), dim3(256), 0, pg->stream, pg->diag(), pg->n_v, pg->fixed, pg->d_tmp + 1);
+      hipLaunchKernelGGL(pg_maxdiag_kernel, dim3(1), dim3(256), 0, pg->stream, pg->diag(), pg->n_v, pg->fixed, pg->d_tmp.p + 1);
       PG_TRY(hipGetLastError());
       double md;
-      PG_TRY(hipMemcpyAsync(&md, pg->d_tmp + 1, 8, hipMemcpyDeviceToHost, pg->stream));
+      PG_TRY(hipMemcpyAsync(&md, pg->d_tmp.p + 1, 8, hipMemcpyDeviceToHost, pg->stream));
       PG_TRY(hipStreamSynchronize(pg->stream));
       lambda = 1e-5 * md;
     }
@@ -2664,20 +2645,20 @@ int lslam_pg_optimize(lslam_pg *pg, int32_t max_iters, lslam_pg_stats *st_out) {
       rc = zero_fixed_step(pg);
       if (rc) return rc;
       st.cg_iterations += cg;
-      hipLaunchKernelGGL(pg_update_kernel, dim3((pg->n_v + 127) / 128), dim3(128), 0, pg->stream, pg->d_poses,
-                         pg->d_x, pg->n_v, pg->fixed, pg->d_trial);
+      hipLaunchKernelGGL(pg_update_kernel, dim3((pg->n_v + 127) / 128), dim3(128), 0, pg->stream, pg->d_poses.p,
+                         pg->d_x.p, pg->n_v, pg->fixed, pg->d_trial.p);
       PG_TRY(hipGetLastError());
       // the trial's chi2 and the gain denominator are enqueued together and read back after ONE wait
       double tmp, scale;
-      rc = eval_chi2(pg, pg->d_trial, nullptr);  // enqueue only
+      rc = eval_chi2(pg, pg->d_trial.p, nullptr);  // enqueue only
       if (rc) return rc;
-      hipLaunchKernelGGL(pg_dot_scale_kernel, dim3(pg->n_cg_blocks), dim3(CG_BLOCK), 0, pg->stream, pg->d_x,
-                         pg->b(), n6, lambda, pg->d_part);
-      hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_part, pg->n_cg_blocks, 1, pg->d_tmp + 2);
+      hipLaunchKernelGGL(pg_dot_scale_kernel, dim3(pg->n_cg_blocks), dim3(CG_BLOCK), 0, pg->stream, pg->d_x.p,
+                         pg->b(), n6, lambda, pg->d_part.p);
+      hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_part.p, pg->n_cg_blocks, 1, pg->d_tmp.p + 2);
       PG_TRY(hipGetLastError());  // a failed launch must not turn into a stale read below
       double chi_flag[2] = {0.0, 0.0};
       PG_TRY(hipMemcpyAsync(chi_flag, pg->chi(), pg->sharded() ? 16 : 8, hipMemcpyDeviceToHost, pg->stream));
-      PG_TRY(hipMemcpyAsync(&scale, pg->d_tmp + 2, 8, hipMemcpyDeviceToHost, pg->stream));
+      PG_TRY(hipMemcpyAsync(&scale, pg->d_tmp.p + 2, 8, hipMemcpyDeviceToHost, pg->stream));
       PG_TRY(hipStreamSynchronize(pg->stream));
       tmp = chi_flag[0];
       if (pg->sharded() && chi_flag[1] > 0.0) {
