@@ -209,6 +209,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed; new entry points (lslam_sreg_*: the registration node with the IMU de-skew branch). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_loc_*: the localisation node). */
 /* still 7: no struct changed; new entry points and a struct of their own (lslam_oreg_*: the registration node for organised clouds). */
+/* still 7: no struct changed; new entry points and a struct of their own (lslam_kfs_*: the keyframe store). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -522,6 +523,77 @@ int lslam_lmap_stats(lslam_lmap *lm, int64_t *merged, int64_t *resorted, int64_t
 /* Back to the state after create: no frames, path length 0, FrameUpdater's first-frame rule armed (limits, leaves and queue
  * distance stay). */
 int lslam_lmap_clear(lslam_lmap *lm);
+
+/* ---- keyframe store (pose_graph/keyframe.h's clouds; pose_graph::Graph, LoopDetector) --------------------------------------
+ * The corner and surface clouds of the pose graph's keyframes, resident in HBM, and the steps of the pose-graph node that read
+ * them there: a keyframe is uploaded once (lslam_kfs_add) and every later use -- the loop detector's coarse and fine alignment,
+ * Graph::getFinalFeatureMap's filter, match and addFeatureCloud -- names it by its id and moves no point over PCIe in either
+ * direction.  Points are packed {x, y, z, intensity}, 16 bytes; ids are 0, 1, 2, ... in order of insertion (the order of the
+ * reference's `keyframes` vector).  An empty cloud (0 points) is a legal keyframe cloud.  One in-flight call per ctx.
+ * Memory is slabs of slab_points points (16 bytes each) taken as the store grows.  A cloud never straddles a slab, a cloud
+ * larger than a slab gets a slab of its own, and slabs are never moved: a device pointer handed out by lslam_kfs_view stays
+ * valid until lslam_kfs_clear / lslam_kfs_destroy, and growing the store copies nothing.
+ * As for lslam_lmap_*, the reference's container grows without bound and device memory cannot: the store has limits, and an
+ * add that would exceed one is refused with LSLAM_ERR_INVALID (the message names the limit) and changes nothing.
+ * LIFETIME: the rule of every per-ctx object (lslam_fmap, lslam_lmap, ...): lslam_ctx_destroy waits for the ctx's streams and
+ * frees what the ctx owns, NOT the store; a store that outlives its ctx keeps its memory, refuses every call with
+ * LSLAM_ERR_INVALID ("its ctx was destroyed") and is freed by lslam_kfs_destroy, which is valid before and after. */
+typedef struct lslam_kfs lslam_kfs;
+typedef struct lslam_kfs_stats {
+  int64_t n_keyframes;
+  uint64_t n_points[2];             /* corner, surf points held */
+  int64_t n_slabs;
+  uint64_t bytes_held;              /* device memory of the slabs */
+  uint64_t cloud_bytes_uploaded;    /* point data this store's entry points moved host -> device (lslam_kfs_add) ... */
+  uint64_t cloud_bytes_downloaded;  /* ... and device -> host (lslam_kfs_get, the debug tap), since creation */
+} lslam_kfs_stats;
+/* max_points_per_type: 0 = 2^26 (1 GiB per type), at most 2^30; max_keyframes: 0 = 65536; slab_points: 0 = 2^20 (16 MiB). */
+int lslam_kfs_create(lslam_ctx *ctx, size_t max_points_per_type, int32_t max_keyframes, size_t slab_points, lslam_kfs **out);
+void lslam_kfs_destroy(lslam_kfs *kfs);
+/* Empties the store and frees its slabs (pointers handed out become invalid); ids start at 0 again.  Limits and byte counters stay. */
+int lslam_kfs_clear(lslam_kfs *kfs);
+/* A new keyframe from host clouds (stride_bytes >= 16: {x, y, z} at 0, the intensity at byte 12 of a 16-byte point, at byte 16
+ * of a longer one, as pcl::PointXYZI keeps it); both clouds go up behind one wait.  -> *id */
+int lslam_kfs_add(lslam_kfs *kfs, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
+                  int32_t *id);
+/* The same for clouds that are in the ctx's device memory already, packed (lslam_odom_last_view's, a torch tensor's): copied
+ * device to device, waited for -- the caller's buffers are free when the call returns. */
+int lslam_kfs_add_device(lslam_kfs *kfs, const void *d_corner, size_t n_corner, const void *d_surf, size_t n_surf, int32_t *id);
+int lslam_kfs_counts(lslam_kfs *kfs, int32_t id, size_t *n_corner, size_t *n_surf);
+/* A cloud back on the host; which: 0 corner, 1 surf.  out_xyzi NULL: the count only. */
+int lslam_kfs_get(lslam_kfs *kfs, int32_t id, int32_t which, float *out_xyzi, size_t cap, size_t *n_out);
+/* The clouds where they are (device pointers, NULL for an empty cloud); any output may be NULL. */
+int lslam_kfs_view(lslam_kfs *kfs, int32_t id, const float **d_corner, size_t *n_corner, const float **d_surf, size_t *n_surf);
+int lslam_kfs_info(lslam_kfs *kfs, lslam_kfs_stats *stats);
+/* Debug tap of the loop detector's reference clouds (loop_detector.hpp:166-200), downloaded: candidate ids[0]'s clouds as
+ * they are (bit for bit), those of ids[1 .. n_cand-1] transformed by the row-major 4x4 rel_T[k] -- (estimate_0^-1 *
+ * estimate_k).cast<float>(); rel_T[0] is not read -- as pcl::transformPointCloud does (x' = ((T0 x + T1 y) + T2 z) + T3 in
+ * fp32, no FMA) and appended in candidate order.  1 <= n_cand <= 6; an id may repeat.  A NULL buffer: its count only. */
+int lslam_kfs_debug_local_clouds(lslam_kfs *kfs, int32_t n_cand, const int32_t *ids, const float *rel_T, float *corner_out,
+                                 size_t cap_corner, size_t *n_corner, float *surf_out, size_t cap_surf, size_t *n_surf);
+/* LoopDetector::matching_nearest behind its gating (loop_detector.hpp:166-255), on the device: the candidates' local clouds
+ * (above); stop if the surface one is empty; lslam_icp_align (transformation epsilon 0, no correspondence gate) of keyframe
+ * new_id's surface cloud onto it from `guess`; stop if it did not converge; ScanMatch::scanMatchLocal -- lslam_voxel_grid
+ * with leaf 0.2 / 0.4 / 0.2 / 0.4 over the local corner, local surface, new corner, new surface clouds, then
+ * lslam_scanmatch_full -- from the ICP's result.  Same kernels in the same order as those calls: same bits.
+ * *stage says where the call ended; guess holds the ICP's result from LSLAM_KFS_ICP_REJECTED on and the scan match's pose
+ * (lslam_pose_to_isometry of it; where the filtered reference was too small for a match, of the ICP's result as a twist: what
+ * ScanMatch::scanMatchLocal's mirrors hand back then) from LSLAM_KFS_MATCH_FAILED on.  fitness / icp_iterations: the ICP's; stats: the scan match's.  The ctx's map and resident
+ * scan belong to the call afterwards.  Returns LSLAM_OK whatever the stage, < 0 on an error. */
+#define LSLAM_KFS_EMPTY_REFERENCE 0
+#define LSLAM_KFS_ICP_REJECTED 1
+#define LSLAM_KFS_MATCH_FAILED 2
+#define LSLAM_KFS_LOOP_ACCEPTED 3
+int lslam_kfs_loop_match(lslam_kfs *kfs, int32_t n_cand, const int32_t *ids, const float *rel_T, int32_t new_id, float guess[16],
+                         int32_t icp_max_iterations, const lslam_opts *opts, int32_t *stage, double *fitness,
+                         int32_t *icp_iterations, lslam_stats *stats);
+/* Graph::getFinalFeatureMap's match of one keyframe (graph.cpp:171-185): the keyframe's clouds through lslam_voxel_grid with
+ * the two leaves, on the device; they become the ctx's resident scan and are matched against the resident map.  Return codes
+ * and the pose write-back rule of lslam_scanmatch_scan. */
+int lslam_kfs_scanmatch(lslam_kfs *kfs, int32_t id, float leaf_corner, float leaf_surf, float pose[6], const lslam_opts *opts,
+                        lslam_stats *stats);
+/* lslam_fmap_add_feature_cloud with the keyframe's clouds taken from the store (fm: a feature map of the store's ctx). */
+int lslam_kfs_add_to_fmap(lslam_kfs *kfs, int32_t id, lslam_fmap *fm, const float T[16]);
 
 /* pcl::VoxelGrid<PointXYZI>::filter with a cubic leaf on one cloud (LaserMatcher.cpp:289-301,
  * ScanMatch.cpp:362-398 scanMatchLocal): one centroid {x,y,z,intensity} per occupied voxel, in

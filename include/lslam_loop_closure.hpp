@@ -8,6 +8,11 @@
 //   pose_graph::Graph             pose_graph/graph.cpp:230-385 (keyframe queue, odometry / loop edges with the
 //                                 reference's information matrices, optimise when a loop was found, odom -> graph)
 //
+//   KeyframeStore                 RAII wrapper of lslam_kfs_*: the keyframes' clouds resident in HBM.  A Graph made with
+//                                 resident = true owns one: add_frame uploads a keyframe's clouds once, LoopDetector and
+//                                 getFinalFeatureMap then name them by id and no cloud crosses PCIe again.  Same ABI
+//                                 kernels in the same order as the host-cloud path: same results.
+//
 // ROS topics, threads and tf are the host program's.  Poses are row-major 4x4 doubles (Mat4d); clouds are packed
 // {x, y, z, intensity} floats.  Nothing here throws; backend failures end up in lastError() and a false / empty
 // result, the way the reference's nodes report a failed match.
@@ -20,6 +25,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <deque>
 #include <memory>
@@ -91,6 +97,51 @@ inline Mat4d pose7_to_mat(const double p[7]) {
   return T;
 }
 
+// The keyframes' clouds in device memory (lslam_kfs_*).  Not copyable; the store may outlive its ctx (every call is then
+// refused), the destructor frees it either way.
+class KeyframeStore {
+public:
+  explicit KeyframeStore(lslam_ctx *ctx, size_t max_points_per_type = 0, int32_t max_keyframes = 0, size_t slab_points = 0) {
+    if (lslam_kfs_create(ctx, max_points_per_type, max_keyframes, slab_points, &_h) != LSLAM_OK) _err = lslam_last_error();
+  }
+  ~KeyframeStore() { lslam_kfs_destroy(_h); }
+  KeyframeStore(const KeyframeStore &) = delete;
+  KeyframeStore &operator=(const KeyframeStore &) = delete;
+  bool ok() const { return _h != nullptr; }
+  lslam_kfs *handle() const { return _h; }
+  // -> the keyframe's id, -1 when the add was refused (lastError says why)
+  int add(const std::vector<float> &corner, const std::vector<float> &surf) {
+    int32_t id = -1;
+    if (lslam_kfs_add(_h, corner.data(), corner.size() / 4, surf.data(), surf.size() / 4, 16, &id) != LSLAM_OK) {
+      _err = lslam_last_error();
+      return -1;
+    }
+    return id;
+  }
+  bool get(int id, int which, std::vector<float> &out) {
+    size_t n = 0;
+    if (lslam_kfs_get(_h, id, which, nullptr, 0, &n) != LSLAM_OK) { _err = lslam_last_error(); return false; }
+    out.resize(4 * n);
+    if (lslam_kfs_get(_h, id, which, out.data(), n, &n) != LSLAM_OK) { _err = lslam_last_error(); return false; }
+    return true;
+  }
+  bool info(lslam_kfs_stats &st) {
+    if (lslam_kfs_info(_h, &st) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  bool clear() {
+    if (lslam_kfs_clear(_h) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  const std::string &lastError() const { return _err; }
+
+private:
+  lslam_kfs *_h = nullptr;
+  std::string _err;
+};
+
 // pose_graph/keyframe.h
 struct KeyFrame {
   typedef std::shared_ptr<KeyFrame> Ptr;
@@ -99,6 +150,8 @@ struct KeyFrame {
   std::vector<float> cornerCloud, surfCloud;  // {x,y,z,intensity} in the keyframe's own frame
   int node = -1;                 // vertex id in the solver
   int frame_id = 0;
+  lslam_kfs *store = nullptr;    // the store that holds the clouds on the device (a resident Graph's), and the id there;
+  int store_id = -1;             // cornerCloud / surfCloud are then empty unless the graph keeps host copies
 };
 
 // loop_detector.hpp:18-48
@@ -200,6 +253,9 @@ public:
   Loop::Ptr matching_nearest(const std::vector<KeyFrame::Ptr> &candidates, const KeyFrame::Ptr &nk) {
     if (candidates.empty()) return nullptr;
     const Mat4d inv = inverse(candidates[0]->estimate);
+    bool stored = nk->store != nullptr && candidates.size() <= 6;
+    for (const auto &c : candidates) stored = stored && c->store == nk->store;
+    if (stored) return matching_nearest_stored(candidates, nk, inv);
     std::vector<float> cornerLocal = candidates[0]->cornerCloud, surfLocal = candidates[0]->surfCloud;
     for (size_t i = 1; i < candidates.size(); ++i) {
       float rel[16];
@@ -252,6 +308,32 @@ public:
          fitness_score_thresh = 0.5;
 
 private:
+  // the same for keyframes whose clouds are in a KeyframeStore: one call, no cloud crosses PCIe (lslam_kfs_loop_match)
+  Loop::Ptr matching_nearest_stored(const std::vector<KeyFrame::Ptr> &candidates, const KeyFrame::Ptr &nk, const Mat4d &inv) {
+    std::vector<int32_t> ids;
+    std::vector<float> rel(16 * candidates.size());
+    for (size_t i = 0; i < candidates.size(); ++i) {
+      ids.push_back(candidates[i]->store_id);
+      to_float16(inv * candidates[i]->estimate, &rel[16 * i]);
+    }
+    float guess[16];
+    to_float16(inv * nk->estimate, guess);
+    int32_t stage = 0, its = 0;
+    double fit = 0;
+    lslam_stats st;
+    if (lslam_kfs_loop_match(nk->store, (int32_t)ids.size(), ids.data(), rel.data(), nk->store_id, guess, 10, &_opts, &stage, &fit,
+                             &its, &st) < 0) {
+      _err = lslam_last_error();
+      return nullptr;
+    }
+    if (stage != LSLAM_KFS_LOOP_ACCEPTED) return nullptr;
+    last_loop_accum_distance = nk->accum_distance;
+    Loop::Ptr lp = std::make_shared<Loop>();
+    lp->key1 = candidates[0];
+    lp->key2 = nk;
+    lp->relative_pose = from_float16(guess);
+    return lp;
+  }
   static void append_transformed(const std::vector<float> &c, const float T[16], std::vector<float> &out) {
     for (size_t i = 0; i + 3 < c.size(); i += 4) {  // pcl::transformPointCloud, fp32
       const float x = c[i], y = c[i + 1], z = c[i + 2];
@@ -273,8 +355,16 @@ private:
 // kept on the host and handed to lslam_pg_* when an optimisation is due.
 class Graph {
 public:
-  explicit Graph(lslam_ctx *ctx, int device = 0, int max_keyframes_per_update = 10)
-      : loop_detector(ctx), _device(device), _max_per_update(max_keyframes_per_update) {}
+  // resident: the keyframes' clouds live in a KeyframeStore on `ctx` (add_frame uploads them once); keep_host_clouds = false
+  // then leaves KeyFrame::cornerCloud / surfCloud empty (KeyframeStore::get fetches a cloud when one is wanted)
+  explicit Graph(lslam_ctx *ctx, int device = 0, int max_keyframes_per_update = 10, bool resident = false,
+                 bool keep_host_clouds = true)
+      : loop_detector(ctx), _ctx(ctx), _device(device), _max_per_update(max_keyframes_per_update), _keep_host(keep_host_clouds) {
+    if (resident) {
+      store.reset(new KeyframeStore(ctx));
+      if (!store->ok()) _err = store->lastError();
+    }
+  }
 
   // graph.cpp:230-246: returns the queued keyframe, or null when the pose did not move enough
   KeyFrame::Ptr add_frame(const Mat4d &odom, const std::vector<float> &corner, const std::vector<float> &surf) {
@@ -282,8 +372,18 @@ public:
     KeyFrame::Ptr kf = std::make_shared<KeyFrame>();
     kf->odom = odom;
     kf->accum_distance = keyframe_updater.get_accum_distance();
-    kf->cornerCloud = corner;
-    kf->surfCloud = surf;
+    if (store) {
+      kf->store_id = store->add(corner, surf);
+      if (kf->store_id < 0) {  // (a full store: the message names the limit)
+        _err = store->lastError();
+        return nullptr;
+      }
+      kf->store = store->handle();
+    }
+    if (!store || _keep_host) {
+      kf->cornerCloud = corner;
+      kf->surfCloud = surf;
+    }
     kf->frame_id = keyframe_updater.get_unique_id();
     keyframe_queue.push_back(kf);
     return kf;
@@ -355,12 +455,16 @@ public:
       if (lslam_fmap_update(fm, pos) < 0) return fail_final(fm);
       size_t nc = 0, ns = 0;
       if (lslam_fmap_surround_counts(fm, &nc, &ns) < 0) return fail_final(fm);
+      // a stored keyframe is filtered, matched and added where it is (lslam_kfs_scanmatch, lslam_kfs_add_to_fmap)
+      const bool stored = kf->store != nullptr && ctx == _ctx;
       const size_t kc = kf->cornerCloud.size() / 4, ks = kf->surfCloud.size() / 4;
-      cc.resize(4 * kc + 4);
-      cs.resize(4 * ks + 4);
       size_t mc = 0, ms = 0;
-      if (lslam_voxel_grid(ctx, kf->cornerCloud.data(), kc, 16, 0.2f, cc.data(), kc, &mc) < 0) return fail_final(fm);
-      if (lslam_voxel_grid(ctx, kf->surfCloud.data(), ks, 16, 0.3f, cs.data(), ks, &ms) < 0) return fail_final(fm);
+      if (!stored) {
+        cc.resize(4 * kc + 4);
+        cs.resize(4 * ks + 4);
+        if (lslam_voxel_grid(ctx, kf->cornerCloud.data(), kc, 16, 0.2f, cc.data(), kc, &mc) < 0) return fail_final(fm);
+        if (lslam_voxel_grid(ctx, kf->surfCloud.data(), ks, 16, 0.3f, cs.data(), ks, &ms) < 0) return fail_final(fm);
+      }
       bool ok = false;
       const bool enough = nc >= 50 && ns >= 100;
       if (enough) {
@@ -368,13 +472,16 @@ public:
         float pose[6];
         lslam_isometry_to_pose(T, pose);
         lslam_stats st;
-        const int rc = lslam_scanmatch_scan(ctx, cc.data(), mc, cs.data(), ms, 16, pose, &opts, &st);
+        const int rc = stored ? lslam_kfs_scanmatch(kf->store, kf->store_id, 0.2f, 0.3f, pose, &opts, &st)
+                              : lslam_scanmatch_scan(ctx, cc.data(), mc, cs.data(), ms, 16, pose, &opts, &st);
         if (rc < 0) return fail_final(fm);
         if (rc != LSLAM_TOO_FEW_REF) lslam_pose_to_isometry(pose, T);  // written back also when the match failed (:342-346)
         ok = rc == LSLAM_OK;
       }
       if (ok || (bootstrap && !enough)) {
-        if (lslam_fmap_add_feature_cloud(fm, kf->cornerCloud.data(), kc, kf->surfCloud.data(), ks, 16, T) < 0) return fail_final(fm);
+        if ((stored ? lslam_kfs_add_to_fmap(kf->store, kf->store_id, fm, T)
+                    : lslam_fmap_add_feature_cloud(fm, kf->cornerCloud.data(), kc, kf->surfCloud.data(), ks, 16, T)) < 0)
+          return fail_final(fm);
         ++added;
       }
       matched.push_back(ok ? 1 : 0);
@@ -386,8 +493,59 @@ public:
     return added;
   }
 
+  // Graph::save (graph.cpp:106-147) with the reference's hard-coded paths replaced by `directory` (which must exist, with its
+  // subdirectories graph/ and graph2/: saveCloudToFiles writes into an existing directory): graph_before.g2o, a final
+  // optimisation, graph_end.g2o, the keyframes' estimates and tf_odom2graph refreshed, the map of all keyframes at their
+  // optimised poses (FeatureMap(121, 111, 121) with its default filter sizes: update + addFeatureCloud per keyframe, no match)
+  // into directory/graph, traj_graph.pcd and traj_odom.pcd (ASCII; x y z intensity normal_x normal_y normal_z curvature =
+  // translation, quaternion w, quaternion x y z of the float-cast rotation, index), then getFinalFeatureMap into directory/graph2.
+  bool save(const std::string &directory, bool bootstrap = false, int max_iterations = 1000) {
+    if (keyframes.empty()) { _err = "Graph::save: no keyframes"; return false; }
+    lslam_pg *pg = nullptr;
+    if (lslam_pg_create(_device, (int)(_poses.size() / 7), _poses.data(), (int)(_ij.size() / 2), _ij.data(), _meas.data(), _info.data(),
+                        0, &pg) != LSLAM_OK) {
+      _err = lslam_pg_last_error();
+      return false;
+    }
+    lslam_pg_stats st;
+    int rc = lslam_pg_save_g2o(pg, (directory + "/graph_before.g2o").c_str());
+    if (rc >= 0) rc = lslam_pg_optimize(pg, max_iterations, &st);
+    if (rc >= 0) rc = lslam_pg_save_g2o(pg, (directory + "/graph_end.g2o").c_str());
+    if (rc >= 0) rc = lslam_pg_get_poses(pg, _poses.data());
+    lslam_pg_destroy(pg);
+    if (rc < 0) {
+      _err = lslam_pg_last_error();
+      return false;
+    }
+    last_iterations = st.iterations;
+    for (auto &kf : keyframes) kf->estimate = pose7_to_mat(&_poses[7 * (size_t)kf->node]);
+    tf_odom2graph = keyframes.back()->estimate * inverse(keyframes.back()->odom);
+    lslam_fmap *fm = nullptr;
+    if (lslam_fmap_create(_ctx, 121, 111, 121, &fm) != LSLAM_OK) return fail_final(nullptr) >= 0;
+    for (const auto &kf : keyframes) {
+      float T[16];
+      to_float16(kf->estimate, T);
+      const float pos[3] = {T[3], T[7], T[11]};
+      if (lslam_fmap_update(fm, pos) < 0) return fail_final(fm) >= 0;
+      if ((kf->store ? lslam_kfs_add_to_fmap(kf->store, kf->store_id, fm, T)
+                     : lslam_fmap_add_feature_cloud(fm, kf->cornerCloud.data(), kf->cornerCloud.size() / 4, kf->surfCloud.data(),
+                                                    kf->surfCloud.size() / 4, 16, T)) < 0)
+        return fail_final(fm) >= 0;
+    }
+    if (lslam_fmap_save(fm, (directory + "/graph").c_str()) < 0) return fail_final(fm) >= 0;
+    lslam_fmap_destroy(fm);
+    if (!save_trajectory_cloud(directory + "/traj_graph.pcd", false) || !save_trajectory_cloud(directory + "/traj_odom.pcd", true)) {
+      _err = "Graph::save: cannot write the trajectory clouds";
+      return false;
+    }
+    std::vector<char> matched;
+    std::vector<Mat4d> poses;
+    return getFinalFeatureMap(_ctx, directory + "/graph2", bootstrap, matched, poses, nullptr) >= 0;
+  }
+
   LoopDetector loop_detector;
   KeyframeUpdater keyframe_updater;
+  std::unique_ptr<KeyframeStore> store;  // resident graphs only
   std::vector<KeyFrame::Ptr> keyframes, new_keyframes;
   std::deque<KeyFrame::Ptr> keyframe_queue;
   std::vector<Loop::Ptr> loops;
@@ -396,6 +554,23 @@ public:
   const std::string &lastError() const { return _err; }
 
 private:
+  // generateGraphTrajectoryCloud / generateOdomTrajectoryCloud + saveTrajectoryCloud
+  bool save_trajectory_cloud(const std::string &path, bool odom) const {
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return false;
+    std::fprintf(f, "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity normal_x normal_y normal_z curvature\n"
+                    "SIZE 4 4 4 4 4 4 4 4\nTYPE F F F F F F F F\nCOUNT 1 1 1 1 1 1 1 1\nWIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\n"
+                    "POINTS %zu\nDATA ascii\n", keyframes.size(), keyframes.size());
+    for (size_t i = 0; i < keyframes.size(); ++i) {
+      float Tf[16];
+      to_float16(odom ? keyframes[i]->odom : keyframes[i]->estimate, Tf);
+      double p7[7];
+      mat_to_pose7(from_float16(Tf), p7);
+      std::fprintf(f, "%.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", Tf[3], Tf[7], Tf[11], (float)p7[6], (float)p7[3], (float)p7[4],
+                   (float)p7[5], (float)i);
+    }
+    return std::fclose(f) == 0;
+  }
   int fail_final(lslam_fmap *fm) {
     _err = lslam_last_error();
     if (fm) lslam_fmap_destroy(fm);
@@ -431,7 +606,9 @@ private:
     for (int r = 0; r < 6; ++r)
       for (int c = 0; c < 6; ++c) _info.push_back(r == c ? diag_info[r] : 0.0);
   }
+  lslam_ctx *_ctx;
   int _device, _max_per_update;
+  bool _keep_host;
   std::vector<double> _poses, _meas, _info;
   std::vector<int32_t> _ij;
   std::string _err;

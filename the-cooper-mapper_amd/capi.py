@@ -194,6 +194,12 @@ class LslamSurveyStats(C.Structure):
                                          "label_sweeps", "planar_points", "boundary_points", "n_corner", "n_surf")]
 
 
+class LslamKfsStats(C.Structure):
+    """lslam_kfs_stats (include/lslam_c.h)."""
+    _fields_ = [("n_keyframes", C.c_int64), ("n_points", C.c_uint64 * 2), ("n_slabs", C.c_int64), ("bytes_held", C.c_uint64),
+                ("cloud_bytes_uploaded", C.c_uint64), ("cloud_bytes_downloaded", C.c_uint64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLGATHERV_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32)
 c_double_p = C.POINTER(C.c_double)
@@ -308,6 +314,23 @@ SYMBOLS = {
                                         c_float_p, C.c_size_t]),
     "lslam_lmap_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "lslam_lmap_clear": (C.c_int, [C.c_void_p]),
+    "lslam_kfs_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "lslam_kfs_destroy": (None, [C.c_void_p]),
+    "lslam_kfs_clear": (C.c_int, [C.c_void_p]),
+    "lslam_kfs_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_int32_p]),
+    "lslam_kfs_add_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_int32_p]),
+    "lslam_kfs_counts": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lslam_kfs_get": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_float_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lslam_kfs_view": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_size_t)]),
+    "lslam_kfs_info": (C.c_int, [C.c_void_p, C.POINTER(LslamKfsStats)]),
+    "lslam_kfs_debug_local_clouds": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, c_float_p, C.c_size_t,
+                                               C.POINTER(C.c_size_t), c_float_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lslam_kfs_loop_match": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, C.c_int32, c_float_p, C.c_int32,
+                                       C.POINTER(LslamOpts), c_int32_p, C.POINTER(C.c_double), c_int32_p, C.POINTER(LslamStats)]),
+    "lslam_kfs_scanmatch": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, c_float_p, C.POINTER(LslamOpts),
+                                      C.POINTER(LslamStats)]),
+    "lslam_kfs_add_to_fmap": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, c_float_p]),
     "lslam_voxel_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, c_float_p,
                                    C.c_size_t, C.POINTER(C.c_size_t)]),
     "lslam_voxel_grid2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, c_float_p,

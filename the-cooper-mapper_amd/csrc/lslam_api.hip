@@ -1404,9 +1404,17 @@ int lslam_map_info_get(const lslam_ctx *ctx, lslam_map_info *info) {
   return LSLAM_OK;
 }
 
+static int scan_set_batch_impl(lslam_ctx *ctx, int32_t n_scans, const void *const *corner, const size_t *n_corner,
+                               const void *const *surf, const size_t *n_surf, size_t stride_bytes, bool from_dev);
 int lslam_scan_set_batch(lslam_ctx *ctx, int32_t n_scans, const void *const *corner,
                          const size_t *n_corner, const void *const *surf, const size_t *n_surf,
                          size_t stride_bytes) {
+  return scan_set_batch_impl(ctx, n_scans, corner, n_corner, surf, n_surf, stride_bytes, false);
+}
+// from_dev: the clouds are packed float4 in the context's device memory (lslam::scan_set_device) -- nothing is packed or
+// uploaded, the ordering kernels read them where they are
+static int scan_set_batch_impl(lslam_ctx *ctx, int32_t n_scans, const void *const *corner, const size_t *n_corner,
+                               const void *const *surf, const size_t *n_surf, size_t stride_bytes, bool from_dev) {
   int rc = check_ctx(ctx, true);
   if (rc) return rc;
   if (n_scans <= 0 || !corner || !n_corner || !surf || !n_surf || stride_bytes < 12 ||
@@ -1433,7 +1441,7 @@ int lslam_scan_set_batch(lslam_ctx *ctx, int32_t n_scans, const void *const *cor
   }
   // the clouds are packed straight into pinned memory: one pass over the caller's points, and the
   // H2D copy is a real asynchronous DMA instead of a staged pageable copy
-  HIP_TRY(ctx->h_stage.reserve(total));
+  if (!from_dev) HIP_TRY(ctx->h_stage.reserve(total));
   float4 *all = ctx->h_stage.p;
   size_t n_all = 0;
   ctx->h_blocks.clear();
@@ -1448,6 +1456,11 @@ int lslam_scan_set_batch(lslam_ctx *ctx, int32_t n_scans, const void *const *cor
   const bool no_morton = env_once().no_morton;
   const bool host_morton = env_once().host_morton;
   const bool dev_morton = !no_morton && !host_morton;
+  if (from_dev && !dev_morton) {
+    set_err("a scan in device memory is ordered on the device: not with LSLAM_NO_MORTON / LSLAM_HOST_MORTON");
+    return LSLAM_ERR_INVALID;
+  }
+  std::vector<const float4 *> dev_clouds;
   std::vector<int32_t> seg_off;
   int32_t out_base = 0;
   for (int32_t p = 0; p < n_scans; ++p) {
@@ -1457,7 +1470,9 @@ int lslam_scan_set_batch(lslam_ctx *ctx, int32_t n_scans, const void *const *cor
       const size_t cnt = type ? n_surf[p] : n_corner[p];
       const int32_t base = (int32_t)n_all;
       float4 *dst = all + n_all;
-      if (host_morton && !no_morton) {
+      if (from_dev) {
+        dev_clouds.push_back(static_cast<const float4 *>(src));
+      } else if (host_morton && !no_morton) {
         pack_cloud(src, cnt, stride_bytes, tmp);
         morton_order(tmp);
         std::copy(tmp.begin(), tmp.end(), dst);
@@ -1533,7 +1548,9 @@ int lslam_scan_set_batch(lslam_ctx *ctx, int32_t n_scans, const void *const *cor
   ctx->grid_state_valid = false;
   rc = ensure_states(ctx, n_scans);
   if (rc) return rc;
-  if (total && dev_morton) {
+  if (total && from_dev) {
+    HIP_TRY(scanprep_order_device(ctx, dev_clouds.data(), total, seg_off.data(), (int)seg_off.size() - 1, ctx->q.p));
+  } else if (total && dev_morton) {
     HIP_TRY(scanprep_order(ctx, all, total, seg_off.data(), (int)seg_off.size() - 1,
                            ctx->q.p));
   } else if (total) {
@@ -2447,11 +2464,34 @@ int lslam_scanmatch_full(lslam_ctx *ctx, const void *ref_corner, size_t n_ref_co
   return lslam_scanmatch_scan(ctx, corner, n_corner, surf, n_surf, stride_bytes, pose, opts, stats);
 }
 
+}  // extern "C"
+
+// lslam_scan_set and lslam_scanmatch_scan for clouds that are in the context's device memory (the keyframe store, lslam_kfs.hip)
+namespace lslam {
+int scan_set_device(lslam_ctx *ctx, const float4 *d_corner, size_t n_corner, const float4 *d_surf, size_t n_surf) {
+  if ((n_corner && !d_corner) || (n_surf && !d_surf)) {
+    set_err("bad scan arguments");
+    return LSLAM_ERR_INVALID;
+  }
+  const void *c = d_corner, *sf = d_surf;
+  return scan_set_batch_impl(ctx, 1, &c, &n_corner, &sf, &n_surf, sizeof(float4), true);
+}
+int scanmatch_scan_device(lslam_ctx *ctx, const float4 *d_corner, size_t n_corner, const float4 *d_surf, size_t n_surf, float pose[6],
+                          const lslam_opts *opts, lslam_stats *stats) {
+  if (ctx && ctx->n_stereo > 0 && ctx->n_st_sets != 1) {  // as lslam_scanmatch_scan: refused before the resident scans change
+    set_err("the stereo term holds %d observation sets: lslam_scanmatch_scan matches one scan", ctx->n_st_sets);
+    return LSLAM_ERR_INVALID;
+  }
+  const int rc = scan_set_device(ctx, d_corner, n_corner, d_surf, n_surf);
+  if (rc) return rc;
+  return lslam_scanmatch_run(ctx, pose, opts, stats);
+}
+}  // namespace lslam
+
 // Variant B: LaserOdometry::scanMatch (odometry/LaserOdometry.cpp:328-647) through kd-trees of the last clouds, one launch per
 // step: the implementation of rounds 1-5.  lslam_odometry_match (lslam_odom.hip) searches hashed cell grids instead and comes
 // here only for a sweep with an exact distance tie, where nanoflann's visit order decides (and under LSLAM_ODOM_TREES=1, the A/B
 // switch of the two).
-}  // extern "C"
 namespace lslam {
 int odometry_match_trees(lslam_ctx *ctx, const void *last_corner, size_t n_lc, const void *last_surf, size_t n_ls, const void *sharp,
                          size_t n_sharp, const void *flat, size_t n_flat, size_t stride_bytes, float pose[6], int32_t max_iterations,

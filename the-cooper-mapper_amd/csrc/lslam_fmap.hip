@@ -1226,7 +1226,7 @@ int lslam_fmap_update(lslam_fmap *fm, const float pos[3]) {
 }
 
 static int add_feature_cloud_impl(lslam_fmap *fm, const void *corner, size_t n_corner, const void *surf, size_t n_surf,
-                                  size_t stride_bytes, const float T[16]);
+                                  size_t stride_bytes, const float T[16], bool on_device);
 static int add_settle(lslam_fmap *fm, int rc) {
   // a failure half way leaves copies out of the pinned staging in flight: nothing may reuse it before they are done
   if (rc != LSLAM_OK && fm && lslam::ctx_alive(fm->ctx)) {
@@ -1238,17 +1238,17 @@ static int add_settle(lslam_fmap *fm, int rc) {
 }
 int lslam_fmap_add_feature_cloud_begin(lslam_fmap *fm, const void *corner, size_t n_corner, const void *surf,
                                        size_t n_surf, size_t stride_bytes, const float T[16]) {
-  return add_settle(fm, add_feature_cloud_impl(fm, corner, n_corner, surf, n_surf, stride_bytes, T));
+  return add_settle(fm, add_feature_cloud_impl(fm, corner, n_corner, surf, n_surf, stride_bytes, T, false));
 }
 int lslam_fmap_add_feature_cloud(lslam_fmap *fm, const void *corner, size_t n_corner, const void *surf,
                                  size_t n_surf, size_t stride_bytes, const float T[16]) {
-  int rc = add_feature_cloud_impl(fm, corner, n_corner, surf, n_surf, stride_bytes, T);
+  int rc = add_feature_cloud_impl(fm, corner, n_corner, surf, n_surf, stride_bytes, T, false);
   if (rc == LSLAM_OK) rc = finish_add(fm);
   return add_settle(fm, rc);
 }
 int lslam_fmap_wait(lslam_fmap *fm) { return add_settle(fm, check_fm(fm)); }
 static int add_feature_cloud_impl(lslam_fmap *fm, const void *corner, size_t n_corner, const void *surf, size_t n_surf,
-                                  size_t stride_bytes, const float T[16]) {
+                                  size_t stride_bytes, const float T[16], bool on_device) {
   int rc = check_fm(fm);
   if (rc) return rc;
   if (!T || stride_bytes < 12 || (stride_bytes & 3) || (n_corner && !corner) || (n_surf && !surf)) {
@@ -1284,8 +1284,12 @@ static int add_feature_cloud_impl(lslam_fmap *fm, const void *corner, size_t n_c
     const size_t n = cnt[t];
     hipStream_t st = (two && t == 1) ? fm->stream2 : s;
     if (n) {
-      rc = pack_input(st, fm->in_pin[t], fm->in_raw_t[t], src[t], n, stride_bytes);
-      if (rc) return rc;
+      // on_device: packed {x, y, z, intensity} in the context's device memory (the keyframe store's clouds) -- read where they are
+      if (!on_device) {
+        rc = pack_input(st, fm->in_pin[t], fm->in_raw_t[t], src[t], n, stride_bytes);
+        if (rc) return rc;
+      }
+      const float4 *raw = on_device ? static_cast<const float4 *>(src[t]) : fm->in_raw_t[t].p;
       // the transformed points go straight behind the type's current points, where the rebuild wants them (was: a staging
       // array of their own and two device-to-device copies per type)
       FM_TRY(fm->pts[t].grow(fm->n[t] + n, fm->n[t], st));
@@ -1295,7 +1299,7 @@ static int add_feature_cloud_impl(lslam_fmap *fm, const void *corner, size_t n_c
         FM_TRY(fm->d_touched_t[t].reserve(((size_t)fm->ncube + 15) & ~(size_t)15));
         FM_TRY(hipMemsetAsync(fm->d_touched_t[t].p, 0, ((size_t)fm->ncube + 15) & ~(size_t)15, st));  // (a whole number of 16-byte words: one fill launch, no tail)
       }
-      hipLaunchKernelGGL(fm_transform_kernel, dim3(((int)n + 255) / 256), dim3(256), 0, st, fm->in_raw_t[t].p, (int)n,
+      hipLaunchKernelGGL(fm_transform_kernel, dim3(((int)n + 255) / 256), dim3(256), 0, st, raw, (int)n,
                          Tm, kp, fm->pts[t].p + fm->n[t], fm->cube[t].p + fm->n[t], track ? fm->d_touched_t[t].p : (uint8_t *)nullptr);
       if (track) FM_TRY(hipMemcpyAsync(fm->h_touched.p + (size_t)t * fm->ncube, fm->d_touched_t[t].p, fm->ncube, hipMemcpyDeviceToHost, st));
     }
@@ -2047,6 +2051,68 @@ int lslam_voxel_grid2(lslam_ctx *ctx, const void *a, size_t na, const void *b, s
 namespace lslam {
 
 void fmap_set_private(lslam_fmap *fm) { fm->private_store = true; }
+
+// ---- device-input forms of lslam_fmap_add_feature_cloud and lslam_voxel_grid (the keyframe store, lslam_kfs.hip) ----------------
+// The kernels and their order are those of the host-pointer entry points: only the upload (and, for the filter, the download)
+// is gone.  Clouds are packed {x, y, z, intensity} in the context's device memory and nothing enqueued may still write them.
+int fmap_add_feature_cloud_device(lslam_fmap *fm, const float4 *d_corner, size_t n_corner, const float4 *d_surf, size_t n_surf,
+                                  const float T[16]) {
+  int rc = add_feature_cloud_impl(fm, d_corner, n_corner, d_surf, n_surf, sizeof(float4), T, true);
+  if (rc == LSLAM_OK) rc = finish_add(fm);
+  return add_settle(fm, rc);
+}
+
+// lslam_voxel_grid of n device points whose bounding box (getMinMax3D) the caller has: lo / hi.  d_out: room for n points.
+int voxel_grid_device(lslam_ctx *ctx, const float4 *d_in, size_t n, const float lo[3], const float hi[3], float leaf, float4 *d_out,
+                      size_t *n_out) {
+  *n_out = 0;
+  if (n == 0) return LSLAM_OK;
+  if (!ctx || !d_in || !d_out || !(leaf > 0.f)) {
+    lslam::set_error("bad voxel-grid arguments");
+    return LSLAM_ERR_INVALID;
+  }
+  FM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  hipStream_t s = lslam::ctx_stream(ctx);
+  VoxelGridCache &cache = *lslam::ctx_slot<VoxelGridCache>(ctx, lslam::CTX_SLOT_VOXEL_GRID);
+  const float inv = 1.0f / leaf;
+  KeyParams kp{};
+  kp.W = kp.H = kp.D = 1;
+  kp.cube_size = 1.0f;
+  kp.inv_leaf = inv;
+  kp.single = 1;
+  double cells = 1.0;
+  long long vol = 1;
+  for (int d = 0; d < 3; ++d) {
+    kp.base0[d] = (int32_t)std::floor(lo[d] * inv);
+    const double c = (double)((int32_t)std::floor(hi[d] * inv) - kp.base0[d] + 1);
+    cells = c > cells ? c : cells;
+    vol *= (long long)((hi[d] - lo[d]) * inv) + 1;
+  }
+  kp.axis_bits = bits_for(cells + 1.0);
+  if (!(vol <= (long long)INT32_MAX)) {  // "Leaf size is too small for the input dataset": the input, unfiltered
+    FM_TRY(hipMemcpyAsync(d_out, d_in, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    *n_out = n;
+    return LSLAM_OK;
+  }
+  FM_TRY(cache.oc.reserve(n));
+  FM_TRY(cache.done.reserve(4));
+  size_t m = 0;
+  if (n * sizeof(float4) <= (size_t)1 << 20) {  // (lslam_voxel_grid's two forms of the same pipeline)
+    const int rc = run_pipeline(s, cache.sc, d_in, nullptr, n, kp, 1, nullptr, d_out, cache.oc.p, &m, 0, cache.done.p);
+    if (rc) return rc;
+    FM_TRY(hipStreamSynchronize(s));
+    if (cache.done.p[1]) {
+      lslam::set_error("voxel index outside its key range (non-finite point?)");
+      return LSLAM_ERR_INVALID;
+    }
+    m = cache.done.p[0];
+  } else {
+    const int rc = run_pipeline(s, cache.sc, d_in, nullptr, n, kp, 1, nullptr, d_out, cache.oc.p, &m);
+    if (rc) return rc;
+  }
+  *n_out = m;
+  return LSLAM_OK;
+}
 
 // Replace the store's content by two host clouds: every point goes to the cube its coordinates give (worldToCube; points
 // outside the grid are dropped), input order kept inside a cube (pushCornerPoint / pushSurfPoint); filter: every cube then

@@ -160,10 +160,29 @@ double det3(const double M[9]) {
 
 using namespace lslam;
 
+// on_device: target is {x, y, z, bitcast(index)} and source any float4 cloud, both in the context's device memory -- the
+// target goes to the map slot device to device, the source is read where it is (the kernel reads x, y, z only)
+static int icp_align_impl(lslam_ctx *ctx, const void *target, size_t n_target, const void *source, size_t n_source,
+                          size_t stride_bytes, float T_io[16], int32_t max_iterations, double transformation_epsilon,
+                          double max_correspondence_distance, double *fitness_out, int32_t *converged_out,
+                          int32_t *iterations_out, bool on_device);
 extern "C" int lslam_icp_align(lslam_ctx *ctx, const void *target, size_t n_target, const void *source, size_t n_source,
                                size_t stride_bytes, float T_io[16], int32_t max_iterations, double transformation_epsilon,
                                double max_correspondence_distance, double *fitness_out, int32_t *converged_out,
                                int32_t *iterations_out) {
+  return icp_align_impl(ctx, target, n_target, source, n_source, stride_bytes, T_io, max_iterations, transformation_epsilon,
+                        max_correspondence_distance, fitness_out, converged_out, iterations_out, false);
+}
+int lslam::icp_align_device(lslam_ctx *ctx, const float4 *d_target, size_t n_target, const float4 *d_source, size_t n_source, float T_io[16],
+                            int32_t max_iterations, double transformation_epsilon, double max_correspondence_distance,
+                            double *fitness_out, int32_t *converged_out, int32_t *iterations_out) {
+  return icp_align_impl(ctx, d_target, n_target, d_source, n_source, sizeof(float4), T_io, max_iterations, transformation_epsilon,
+                        max_correspondence_distance, fitness_out, converged_out, iterations_out, true);
+}
+static int icp_align_impl(lslam_ctx *ctx, const void *target, size_t n_target, const void *source, size_t n_source,
+                          size_t stride_bytes, float T_io[16], int32_t max_iterations, double transformation_epsilon,
+                          double max_correspondence_distance, double *fitness_out, int32_t *converged_out,
+                          int32_t *iterations_out, bool on_device) {
   if (converged_out) *converged_out = 0;
   if (iterations_out) *iterations_out = 0;
   if (fitness_out) *fitness_out = 0.0;
@@ -173,7 +192,8 @@ extern "C" int lslam_icp_align(lslam_ctx *ctx, const void *target, size_t n_targ
   }
   if (n_target == 0) return LSLAM_OK;  // loop_detector.hpp:233-235: empty reference -> not matched
   // the target's kd-tree takes the surf slot of the context's map (the map belongs to this call afterwards)
-  int rc = lslam_map_set(ctx, nullptr, 0, target, n_target, stride_bytes);
+  int rc = on_device ? map_set_device(ctx, nullptr, 0, static_cast<const float4 *>(target), n_target)
+                     : lslam_map_set(ctx, nullptr, 0, target, n_target, stride_bytes);
   if (rc) return rc;
   ctx_invalidate_map(ctx);
   hipStream_t s = ctx_stream(ctx);
@@ -181,9 +201,11 @@ extern "C" int lslam_icp_align(lslam_ctx *ctx, const void *target, size_t n_targ
   float4 *d_src = nullptr;
   double *d_part = nullptr;
   const int blocks = (int)((n_source + ICP_BLOCK - 1) / ICP_BLOCK);
-  rc = ctx_scratch(ctx, n_source, (size_t)std::max(blocks, 1) * ICP_SUMS, &d_src, &d_part);
+  rc = ctx_scratch(ctx, on_device ? 1 : n_source, (size_t)std::max(blocks, 1) * ICP_SUMS, &d_src, &d_part);
   if (rc) return rc;
-  {
+  if (on_device) {
+    d_src = const_cast<float4 *>(static_cast<const float4 *>(source));
+  } else {
     std::vector<float4> h(n_source);
     const char *p = static_cast<const char *>(source);
     for (size_t i = 0; i < n_source; ++i) {

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/lslam_c.h"
 #include "lslam_buf.hpp"
 #include "lslam_device.hpp"
 #include "lslam_grid.hpp"
@@ -499,6 +500,22 @@ int fmap_copy(lslam_fmap *dst, lslam_fmap *src);
 int fmap_view(lslam_fmap *fm, FmapView *out);
 bool fmap_read_pcd(const char *path, std::vector<float4> &out, std::string &err);  // x y z intensity of an ascii or binary PCD
 bool fmap_write_pcd(const char *path, const float4 *p, size_t n);  // one cube file as lslam_fmap_save writes it
+
+// Device-input forms of steps that exist for host clouds, for the keyframe store (lslam_kfs.hip).  Same kernels in the same order
+// as the host-pointer entry points named; clouds are packed float4 in the context's device memory.
+int fmap_add_feature_cloud_device(lslam_fmap *fm, const float4 *d_corner, size_t n_corner, const float4 *d_surf, size_t n_surf,
+                                  const float T[16]);  // lslam_fmap_add_feature_cloud ({x, y, z, intensity})
+int voxel_grid_device(lslam_ctx *ctx, const float4 *d_in, size_t n, const float lo[3], const float hi[3], float leaf, float4 *d_out,
+                      size_t *n_out);  // lslam_voxel_grid; lo / hi: the input's bounding box; d_out: room for n points
+int scan_set_device(lslam_ctx *ctx, const float4 *d_corner, size_t n_corner, const float4 *d_surf, size_t n_surf);  // lslam_scan_set (.w is ignored)
+int scanmatch_scan_device(lslam_ctx *ctx, const float4 *d_corner, size_t n_corner, const float4 *d_surf, size_t n_surf, float pose[6],
+                          const lslam_opts *opts, lslam_stats *stats);  // lslam_scanmatch_scan
+// lslam_icp_align; d_target: {x, y, z, bitcast(index)} as map_set_device takes a cloud, d_source: .w is ignored
+int icp_align_device(lslam_ctx *ctx, const float4 *d_target, size_t n_target, const float4 *d_source, size_t n_source, float T_io[16],
+                     int32_t max_iterations, double transformation_epsilon, double max_correspondence_distance, double *fitness_out,
+                     int32_t *converged_out, int32_t *iterations_out);
+// lslam_scanprep.hip: scanprep_order over clouds that are on the device (nseg of them, d_clouds[k] with h_seg_off[k + 1] - h_seg_off[k] points)
+hipError_t scanprep_order_device(lslam_ctx *ctx, const float4 *const *d_clouds, size_t n, const int32_t *h_seg_off, int nseg, float4 *d_out);
 
 // lslam_fmap.hip: pcl::VoxelGrid of a window whose owner keeps its points in voxel-key order (see there)
 struct WindowFilter;  // the filter's scratch, owned by the caller

@@ -100,13 +100,7 @@ __global__ __launch_bounds__(256) void lm_transform_kernel(const TransformArgs a
   const bool in = i < a.n[t];
   uint32_t mm[6] = {0u, 0u, 0u, 0u, 0u, 0u};
   if (in) {
-    const float *T = Tm.m;
-    const float4 p = a.in[t][i];
-    float4 q;
-    q.x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p.x), __fmul_rn(T[1], p.y)), __fmul_rn(T[2], p.z)), T[3]);
-    q.y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], p.x), __fmul_rn(T[5], p.y)), __fmul_rn(T[6], p.z)), T[7]);
-    q.z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], p.x), __fmul_rn(T[9], p.y)), __fmul_rn(T[10], p.z)), T[11]);
-    q.w = p.w;
+    const float4 q = lslam::rigid_transform_point(Tm.m, a.in[t][i]);
     a.out[t][i] = q;
     const uint32_t o[3] = {lm_ordered_u32(q.x), lm_ordered_u32(q.y), lm_ordered_u32(q.z)};
 #pragma unroll

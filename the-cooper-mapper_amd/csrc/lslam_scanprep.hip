@@ -67,7 +67,18 @@ struct ScanPrep {  // the context's (ctx_slot), grow-only
 // h_pts: n packed points in caller order (cloud after cloud); h_seg_off: nseg + 1 offsets.
 // Writes the ordered points to d_out (n float4) on the context's stream, asynchronously: h_pts must stay untouched until that
 // stream has been waited for.
+static hipError_t order_impl(lslam_ctx *ctx, const float4 *h_pts, const float4 *const *d_clouds, size_t n, const int32_t *h_seg_off, int nseg,
+                             float4 *d_out);
 hipError_t scanprep_order(lslam_ctx *ctx, const float4 *h_pts, size_t n, const int32_t *h_seg_off, int nseg, float4 *d_out) {
+  return order_impl(ctx, h_pts, nullptr, n, h_seg_off, nseg, d_out);
+}
+// The same for clouds that are in device memory already: they are copied into the staging array device to device (the
+// original index is recomputed by the gather: .w of the input is not read), the kernels are the same.
+hipError_t scanprep_order_device(lslam_ctx *ctx, const float4 *const *d_clouds, size_t n, const int32_t *h_seg_off, int nseg, float4 *d_out) {
+  return order_impl(ctx, nullptr, d_clouds, n, h_seg_off, nseg, d_out);
+}
+static hipError_t order_impl(lslam_ctx *ctx, const float4 *h_pts, const float4 *const *d_clouds, size_t n, const int32_t *h_seg_off, int nseg,
+                             float4 *d_out) {
   if (n == 0) return hipSuccess;
   ScanPrep *sp = ctx_slot<ScanPrep>(ctx, CTX_SLOT_SCANPREP);
   hipStream_t s = ctx_stream(ctx);
@@ -75,7 +86,14 @@ hipError_t scanprep_order(lslam_ctx *ctx, const float4 *h_pts, size_t n, const i
   if ((e = sp->keys0.reserve(n)) != hipSuccess || (e = sp->keys1.reserve(n)) != hipSuccess || (e = sp->idx0.reserve(n)) != hipSuccess ||
       (e = sp->idx1.reserve(n)) != hipSuccess || (e = sp->raw.reserve(n)) != hipSuccess || (e = sp->seg.reserve((size_t)nseg + 1)) != hipSuccess)
     return e;
-  if ((e = hipMemcpyAsync(sp->raw.p, h_pts, n * sizeof(float4), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  if (h_pts) {
+    if ((e = hipMemcpyAsync(sp->raw.p, h_pts, n * sizeof(float4), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  } else {
+    for (int k = 0; k < nseg; ++k) {
+      const size_t cnt = (size_t)(h_seg_off[k + 1] - h_seg_off[k]);
+      if (cnt && (e = hipMemcpyAsync(sp->raw.p + h_seg_off[k], d_clouds[k], cnt * sizeof(float4), hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
+    }
+  }
   if ((e = hipMemcpyAsync(sp->seg.p, h_seg_off, ((size_t)nseg + 1) * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
   int seg_bits = 1;
   while ((1 << seg_bits) < nseg) ++seg_bits;

@@ -59,9 +59,19 @@ LOOP_INFORMATION = 2.0 * np.eye(6)
 
 
 class Graph:
-    def __init__(self, device=0, ctx=None, loop_detector=None, max_keyframes_per_update=10):
+    def __init__(self, device=0, ctx=None, loop_detector=None, max_keyframes_per_update=10, resident=False,
+                 keep_host_clouds=True, store_max_points=0, store_max_keyframes=0, store_slab_points=0):
+        """``resident=True``: the keyframes' clouds live in a :class:`KeyframeStore` on the loop detector's context --
+        ``add_frame`` uploads them once (``kf.store_id``), loop closure and ``get_final_feature_map`` read them there;
+        ``keep_host_clouds=False`` then drops the host copies (``kf.corner_cloud`` / ``kf.surf_cloud`` fetch on demand).
+        The ``store_*`` limits are :class:`KeyframeStore`'s (0: its defaults).  Without ``resident`` nothing changes."""
         self.solver = PoseGraph(device)
         self.loop_detector = loop_detector or LoopDetector(device=device, ctx=ctx)
+        self.store = None
+        self.keep_host_clouds = bool(keep_host_clouds)
+        if resident:
+            from .keyframe_store import KeyframeStore
+            self.store = KeyframeStore(self.loop_detector.scan_match.ctx, store_max_points, store_max_keyframes, store_slab_points)
         self.keyframe_updater = KeyframeUpdater()
         self.keyframes = []
         self.new_keyframes = []
@@ -79,6 +89,8 @@ class Graph:
                       frame_id=self.keyframe_updater.get_unique_id())
         kf.odom = odom.copy()
         kf.node = None
+        if self.store is not None:
+            kf.put_in_store(self.store, self.keep_host_clouds)
         self.keyframe_queue.append(kf)
         return kf
 
@@ -150,21 +162,101 @@ class Graph:
             est = np.asarray(kf.estimate, np.float64).astype(np.float32).reshape(4, 4)  # node->estimate().cast<float>()
             fm.update(est[:3, 3])
             nc, ns = fm.surround_counts()
-            corner = voxel_grid(ctx, kf.corner_cloud, 0.2)
-            surf = voxel_grid(ctx, kf.surf_cloud, 0.3)
+            # a stored keyframe (resident=True) is filtered, matched and added where it is: no cloud crosses PCIe
+            stored = getattr(kf, "store", None) is not None and kf.store.ctx is ctx
+            if not stored:
+                corner = voxel_grid(ctx, kf.corner_cloud, 0.2)
+                surf = voxel_grid(ctx, kf.surf_cloud, 0.3)
             ok = False
             if nc >= 50 and ns >= 100:  # else scanMatchScan says "reference cloud points too few" and leaves the pose alone
                 fm.surround_to_map()
-                status, pose, st = ctx.scanmatch_scan(corner, surf, ctx.isometry_to_pose(est), opts)
+                if stored:
+                    status, pose, st = kf.store.scanmatch(kf.store_id, 0.2, 0.3, ctx.isometry_to_pose(est), opts)
+                else:
+                    status, pose, st = ctx.scanmatch_scan(corner, surf, ctx.isometry_to_pose(est), opts)
                 last = st
                 if int(status) != 1:
                     est = ctx.pose_to_isometry(pose)  # written back also when the match failed (ScanMatch.cpp:342-346)
                 ok = int(status) == 0
             if ok or (bootstrap and not (nc >= 50 and ns >= 100)):
-                fm.add_feature_cloud(kf.corner_cloud, kf.surf_cloud, est)
+                if stored:
+                    kf.store.add_to_fmap(kf.store_id, fm, est)
+                else:
+                    fm.add_feature_cloud(kf.corner_cloud, kf.surf_cloud, est)
                 added += 1
             matched.append(ok)
             poses.append(np.array(est, np.float32))
         if directory is not None:
             fm.save_cloud_to_files(directory)
         return {"map": fm, "matched": matched, "poses": poses, "added": added, "stats": last}
+
+    # graph.cpp:106-147
+    def save(self, directory, bootstrap=False, max_iterations=1000):
+        """``Graph::save`` with the reference's hard-coded paths replaced by ``directory``: ``graph_before.g2o``, a final
+        optimisation, ``graph_end.g2o``, the keyframes' estimates and ``tf_odom2graph`` refreshed, the map of all keyframes at
+        their optimised poses (a ``FeatureMap(121, 111, 121)`` with its default filter sizes: ``update`` + ``addFeatureCloud``
+        per keyframe, no match) saved into ``directory/graph``, the trajectory clouds ``traj_graph.pcd`` / ``traj_odom.pcd``,
+        then :meth:`get_final_feature_map` into ``directory/graph2``.  Works with and without ``resident``.  -> the dict of
+        :meth:`get_final_feature_map` (its map closed), with ``iterations`` of the final optimisation."""
+        import os
+        from .feature_map import FeatureMap
+        from .pose_graph import pose7_to_mat
+        if not self.keyframes:
+            raise ValueError("Graph.save: the graph holds no keyframes")
+        os.makedirs(directory, exist_ok=True)
+        self.solver.save(os.path.join(directory, "graph_before.g2o"))
+        iterations = self.solver.optimize(max_iterations)
+        self.solver.save(os.path.join(directory, "graph_end.g2o"))
+        poses = self.solver.poses()
+        for kf in self.keyframes:
+            kf.estimate = pose7_to_mat(poses[kf.node])
+        last = self.keyframes[-1]
+        self.tf_odom2graph = last.estimate @ np.linalg.inv(last.odom)
+        ctx = self.loop_detector.scan_match.ctx
+        fm = FeatureMap(ctx, 121, 111, 121)
+        try:
+            for kf in self.keyframes:
+                est = np.asarray(kf.estimate, np.float64).astype(np.float32)
+                fm.update(est[:3, 3])
+                if getattr(kf, "store", None) is not None and kf.store.ctx is ctx:
+                    kf.store.add_to_fmap(kf.store_id, fm, est)
+                else:
+                    fm.add_feature_cloud(kf.corner_cloud, kf.surf_cloud, est)
+            os.makedirs(os.path.join(directory, "graph"), exist_ok=True)
+            fm.save_cloud_to_files(os.path.join(directory, "graph"))
+        finally:
+            fm.close()
+        save_trajectory_cloud(os.path.join(directory, "traj_graph.pcd"), [kf.estimate for kf in self.keyframes])
+        save_trajectory_cloud(os.path.join(directory, "traj_odom.pcd"), [kf.odom for kf in self.keyframes])
+        os.makedirs(os.path.join(directory, "graph2"), exist_ok=True)
+        out = self.get_final_feature_map(ctx=ctx, directory=os.path.join(directory, "graph2"), bootstrap=bootstrap)
+        out["map"].close()
+        out["iterations"] = iterations
+        return out
+
+
+def trajectory_rows(poses):
+    """generateGraphTrajectoryCloud / generateOdomTrajectoryCloud: one PointXYZINormal per pose -- position = translation,
+    normal = the quaternion's x, y, z, intensity = its w (the quaternion of the float-cast rotation), curvature = index."""
+    from .pose_graph import mat_to_pose7
+    rows = np.zeros((len(poses), 8), np.float32)
+    for i, T in enumerate(poses):
+        Tf = np.asarray(T, np.float64).astype(np.float32)
+        p = mat_to_pose7(Tf.astype(np.float64))
+        q = p[3:]
+        rows[i, :3] = Tf[:3, 3]
+        rows[i, 3] = q[3]
+        rows[i, 4:7] = q[:3]
+        rows[i, 7] = i
+    return rows
+
+
+def save_trajectory_cloud(path, poses):
+    """ASCII PCD, fields ``x y z intensity normal_x normal_y normal_z curvature``."""
+    rows = trajectory_rows(poses)
+    with open(path, "w") as f:
+        f.write("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\n"
+                "FIELDS x y z intensity normal_x normal_y normal_z curvature\nSIZE 4 4 4 4 4 4 4 4\nTYPE F F F F F F F F\n"
+                "COUNT 1 1 1 1 1 1 1 1\nWIDTH %d\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %d\nDATA ascii\n" % (len(rows), len(rows)))
+        for r in rows:
+            f.write(" ".join(repr(float(v)) for v in r) + "\n")

@@ -1,0 +1,142 @@
+"""The pose graph's keyframe clouds resident in HBM (``csrc/lslam_kfs.hip``, ``lslam_kfs_*`` of include/lslam_c.h): a
+keyframe's corner and surface cloud are uploaded once, and the steps of ``pose_graph::Graph`` / ``LoopDetector`` that use
+them -- the loop detector's coarse and fine alignment, ``getFinalFeatureMap``'s filter, match and ``addFeatureCloud`` -- name
+them by id and move no point between host and device.  Clouds are ``(n, 4)`` float32 ``{x, y, z, intensity}``; ids are
+0, 1, 2, ... in order of insertion.
+
+Like :class:`LocalFeatureMap`, the store has limits where the reference's vector grows without bound: an add past
+``max_points`` per type or ``max_keyframes`` raises :class:`LslamError` and changes nothing.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .capi import LslamError, LslamKfsStats, LslamStats, c_int32_p
+from .feature_map import _fp, _xyzi
+
+# lslam_kfs_loop_match's *stage (include/lslam_c.h LSLAM_KFS_*)
+EMPTY_REFERENCE, ICP_REJECTED, MATCH_FAILED, LOOP_ACCEPTED = 0, 1, 2, 3
+MAX_CANDIDATES = 6  # loop_detector.hpp:141
+
+
+class KeyframeStore:
+    def __init__(self, ctx, max_points=0, max_keyframes=0, slab_points=0):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        rc = self.lib.lslam_kfs_create(ctx.h, int(max_points), int(max_keyframes), int(slab_points), C.byref(h))
+        if rc != 0:
+            raise LslamError(rc, self.lib.lslam_last_error().decode())
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.lslam_kfs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc < 0:
+            raise LslamError(rc, self.lib.lslam_last_error().decode())
+        return rc
+
+    def __len__(self):
+        return self.info()["n_keyframes"]
+
+    def add(self, corner, surf):
+        """-> the new keyframe's id.  Two torch tensors on the context's device ((n, 4) float32, contiguous) are copied
+        device to device (``lslam_kfs_add_device``); anything else is uploaded, both clouds behind one wait."""
+        kid = C.c_int32(-1)
+        if hasattr(corner, "data_ptr") and hasattr(surf, "data_ptr"):
+            for x in (corner, surf):
+                if not (x.is_cuda and x.is_contiguous() and x.dim() == 2 and x.shape[1] == 4 and x.element_size() == 4):
+                    raise ValueError("device clouds must be contiguous (n, 4) float32 tensors on the GPU")
+            self._check(self.lib.lslam_kfs_add_device(self.h, C.c_void_p(corner.data_ptr()), corner.shape[0],
+                                                      C.c_void_p(surf.data_ptr()), surf.shape[0], C.byref(kid)))
+            return kid.value
+        c, s = _xyzi(corner), _xyzi(surf)
+        if c.shape[1] != s.shape[1]:
+            raise ValueError("corner and surf clouds must share a point layout")
+        self._check(self.lib.lslam_kfs_add(self.h, c.ctypes.data_as(C.c_void_p), len(c), s.ctypes.data_as(C.c_void_p), len(s),
+                                           c.shape[1] * 4, C.byref(kid)))
+        return kid.value
+
+    def counts(self, kid):
+        nc, ns = C.c_size_t(), C.c_size_t()
+        self._check(self.lib.lslam_kfs_counts(self.h, int(kid), C.byref(nc), C.byref(ns)))
+        return nc.value, ns.value
+
+    def get(self, kid, which):
+        """One cloud back on the host; ``which``: 0 corner, 1 surf -> (n, 4) float32."""
+        n = self.counts(kid)[int(which)]
+        out = np.zeros((n, 4), np.float32)
+        got = C.c_size_t()
+        self._check(self.lib.lslam_kfs_get(self.h, int(kid), int(which), _fp(out), n, C.byref(got)))
+        return out
+
+    def view(self, kid):
+        """-> (corner device pointer, n_corner, surf device pointer, n_surf); the pointers stay valid until clear / close."""
+        pc, ps = C.c_void_p(), C.c_void_p()
+        nc, ns = C.c_size_t(), C.c_size_t()
+        self._check(self.lib.lslam_kfs_view(self.h, int(kid), C.byref(pc), C.byref(nc), C.byref(ps), C.byref(ns)))
+        return pc.value or 0, nc.value, ps.value or 0, ns.value
+
+    def info(self):
+        st = LslamKfsStats()
+        self._check(self.lib.lslam_kfs_info(self.h, C.byref(st)))
+        return dict(n_keyframes=st.n_keyframes, n_corner=st.n_points[0], n_surf=st.n_points[1], n_slabs=st.n_slabs,
+                    bytes_held=st.bytes_held, cloud_bytes_uploaded=st.cloud_bytes_uploaded,
+                    cloud_bytes_downloaded=st.cloud_bytes_downloaded)
+
+    def clear(self):
+        self._check(self.lib.lslam_kfs_clear(self.h))
+
+    @staticmethod
+    def _candidates(ids, rel_T):
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        T = np.ascontiguousarray(rel_T, np.float32).reshape(len(ids), 16)
+        return ids, T
+
+    def debug_local_clouds(self, ids, rel_T):
+        """The loop detector's reference clouds (debug tap): candidate ``ids[0]``'s clouds as they are, the others transformed
+        by ``rel_T[k]`` (4x4 float32; ``rel_T[0]`` is not read) and appended -> (corner (n, 4), surf (m, 4))."""
+        ids, T = self._candidates(ids, rel_T)
+        nc, ns = C.c_size_t(), C.c_size_t()
+        self._check(self.lib.lslam_kfs_debug_local_clouds(self.h, len(ids), ids.ctypes.data_as(c_int32_p), _fp(T), None, 0,
+                                                          C.byref(nc), None, 0, C.byref(ns)))
+        c, s = np.zeros((nc.value, 4), np.float32), np.zeros((ns.value, 4), np.float32)
+        self._check(self.lib.lslam_kfs_debug_local_clouds(self.h, len(ids), ids.ctypes.data_as(c_int32_p), _fp(T), _fp(c), len(c),
+                                                          C.byref(nc), _fp(s), len(s), C.byref(ns)))
+        return c, s
+
+    def loop_match(self, ids, rel_T, new_id, guess, opts=None, icp_max_iterations=10):
+        """``LoopDetector::matching_nearest`` behind its gating, on the device (``lslam_kfs_loop_match``) -> dict: ``stage``
+        (EMPTY_REFERENCE / ICP_REJECTED / MATCH_FAILED / LOOP_ACCEPTED), ``guess`` (4x4 float32), ``fitness``,
+        ``icp_iterations``, ``stats`` (the scan match's lslam_stats)."""
+        ids, T = self._candidates(ids, rel_T)
+        g = np.array(guess, dtype=np.float32).reshape(16)
+        stage, its, fit, st = C.c_int32(), C.c_int32(), C.c_double(), LslamStats()
+        self._check(self.lib.lslam_kfs_loop_match(self.h, len(ids), ids.ctypes.data_as(c_int32_p), _fp(T), int(new_id), _fp(g),
+                                                  int(icp_max_iterations), C.byref(opts) if opts is not None else None,
+                                                  C.byref(stage), C.byref(fit), C.byref(its), C.byref(st)))
+        return dict(stage=stage.value, guess=g.reshape(4, 4), fitness=fit.value, icp_iterations=its.value, stats=st)
+
+    def scanmatch(self, kid, leaf_corner, leaf_surf, pose, opts=None):
+        """The keyframe's clouds filtered on the device, matched against the context's resident map
+        (``lslam_kfs_scanmatch``) -> (status, pose (6,), stats), as ``Context.scanmatch_scan``."""
+        from .capi import Status
+        p = np.array(pose, dtype=np.float32).reshape(6)
+        st = LslamStats()
+        rc = self._check(self.lib.lslam_kfs_scanmatch(self.h, int(kid), float(leaf_corner), float(leaf_surf), _fp(p),
+                                                      C.byref(opts) if opts is not None else None, C.byref(st)))
+        return Status(rc), p, st
+
+    def add_to_fmap(self, kid, fmap, tf):
+        """``FeatureMap.add_feature_cloud`` with the keyframe's clouds taken from the store."""
+        T = np.ascontiguousarray(tf, dtype=np.float32).reshape(16)
+        self._check(self.lib.lslam_kfs_add_to_fmap(self.h, int(kid), fmap.h, _fp(T)))

@@ -37,9 +37,34 @@ class KeyFrame:
     def __init__(self, estimate, accum_distance, corner_cloud, surf_cloud, frame_id=0):
         self.estimate = np.asarray(estimate, np.float64).reshape(4, 4)
         self.accum_distance = float(accum_distance)
+        self.store, self.store_id = None, None  # a KeyframeStore that holds the clouds on the device, and the id there
         self.corner_cloud = np.ascontiguousarray(corner_cloud, np.float32)
         self.surf_cloud = np.ascontiguousarray(surf_cloud, np.float32)
         self.frame_id = frame_id
+
+    # the clouds on the host; a stored keyframe whose host copies were dropped (Graph(keep_host_clouds=False)) fetches them
+    @property
+    def corner_cloud(self):
+        return self._corner if self._corner is not None else self.store.get(self.store_id, 0)
+
+    @corner_cloud.setter
+    def corner_cloud(self, cloud):
+        self._corner = cloud
+
+    @property
+    def surf_cloud(self):
+        return self._surf if self._surf is not None else self.store.get(self.store_id, 1)
+
+    @surf_cloud.setter
+    def surf_cloud(self, cloud):
+        self._surf = cloud
+
+    def put_in_store(self, store, keep_host_clouds=True):
+        """Upload the clouds once into ``store`` (a :class:`KeyframeStore`) and remember the id."""
+        self.store_id = store.add(self._corner, self._surf)
+        self.store = store
+        if not keep_host_clouds:
+            self._corner = self._surf = None
 
 
 class Loop:
@@ -163,6 +188,10 @@ class LoopDetector:
             return None
         candidate_tf = candidate_keyframes[0].estimate
         inv = np.linalg.inv(candidate_tf)
+        store = new_keyframe.store
+        if store is not None and all(k.store is store for k in candidate_keyframes) and \
+                self.coarse_matcher == self._icp_coarse_matcher and store.ctx is self.scan_match.ctx:
+            return self._matching_nearest_stored(store, candidate_keyframes, new_keyframe, inv)
         corner_local = [candidate_keyframes[0].corner_cloud]
         surf_local = [candidate_keyframes[0].surf_cloud]
         for k in candidate_keyframes[1:]:
@@ -182,3 +211,20 @@ class LoopDetector:
             return None
         self.last_loop_accum_distance = new_keyframe.accum_distance
         return Loop(candidate_keyframes[0], new_keyframe, guess2)
+
+    def _matching_nearest_stored(self, store, candidate_keyframes, new_keyframe, inv):
+        """The rest of :meth:`matching_nearest` for keyframes whose clouds are in a KeyframeStore: one call
+        (``lslam_kfs_loop_match``), no cloud crosses PCIe.  Same kernels in the same order as the host path: same result."""
+        from .capi import Status
+        from .keyframe_store import MATCH_FAILED, LOOP_ACCEPTED
+        rel = np.stack([(inv @ k.estimate).astype(np.float32) for k in candidate_keyframes])
+        new_relative = (inv @ new_keyframe.estimate).astype(np.float32)
+        sm = self.scan_match
+        r = store.loop_match([k.store_id for k in candidate_keyframes], rel, new_keyframe.store_id, new_relative, sm.opts)
+        if r["stage"] >= MATCH_FAILED:  # scanMatchScan ran: ScanMatch's counters move as they do on the host path
+            sm._resident, sm._resident_map = None, 0
+            sm._finish(Status(r["stats"].status), r["stats"])
+        if r["stage"] != LOOP_ACCEPTED:
+            return None
+        self.last_loop_accum_distance = new_keyframe.accum_distance
+        return Loop(candidate_keyframes[0], new_keyframe, r["guess"])
