@@ -412,16 +412,22 @@ int resolve_stack_mode(const lslam_ctx *ctx, int32_t search_mode) {
   return (search_mode & LSLAM_STACK_SHALLOW) ? SWEEP_STACK_SHALLOW : ((search_mode & LSLAM_STACK_DEEP) ? SWEEP_STACK_DEEP : SWEEP_STACK_AUTO);
 }
 
-// launch_sweep + the per-context count of the instantiation it took
-hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
-                        int *variant = nullptr) {
-  int v = -1;
+// the pass-2 plan of the next queue launch: the two counter sets alternate per launched plan (ctx->queue_launches)
+CertPlan make_cert_plan(const lslam_ctx *ctx) {
   CertPlan plan;
   plan.work = ctx->cert_work.p;
   plan.count = ctx->cert_count.p + (ctx->queue_launches & 1);
   plan.count_next = ctx->cert_count.p + ((ctx->queue_launches + 1) & 1);
   plan.ticket = plan.count + 2;
   plan.ticket_next = plan.count_next + 2;
+  return plan;
+}
+
+// launch_sweep + the per-context count of the instantiation it took
+hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
+                        int *variant = nullptr) {
+  int v = -1;
+  CertPlan plan = make_cert_plan(ctx);
   plan.ticket2 = plan.count + 4;
   plan.ticket2_next = plan.count_next + 4;
   if (a.grid) {  // the grid sweep: probe + proof for every point, then the tree search for the points it listed; timed as one
@@ -453,13 +459,7 @@ hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, hipEve
       e = launch_sweep_queue(a, jtj_mode, ctx->stream, nullptr, pass2, plan, 0);
       ctx->queue_launches++;
       if (e != hipSuccess) return e;
-      CertPlan plan2;
-      plan2.work = ctx->cert_work.p;
-      plan2.count = ctx->cert_count.p + (ctx->queue_launches & 1);
-      plan2.count_next = ctx->cert_count.p + ((ctx->queue_launches + 1) & 1);
-      plan2.ticket = plan2.count + 2;
-      plan2.ticket_next = plan2.count_next + 2;
-      e = launch_sweep_queue(a, jtj_mode, ctx->stream, e1, pass2, plan2, 1);
+      e = launch_sweep_queue(a, jtj_mode, ctx->stream, e1, pass2, make_cert_plan(ctx), 1);  // (no second consumer: no ticket2)
       ctx->queue_launches++;
       return e;
     }
@@ -1582,53 +1582,203 @@ int lslam_scan_set(lslam_ctx *ctx, const void *corner, size_t n_corner, const vo
 }
 
 namespace {
-// Shared body of lslam_scanmatch_run_batch and lslam_scanmatch_run_sharded.  With `fn` set the
-// resident scan is this rank's shard of ONE scan's points: every iteration reduces the local
-// partials, hands the 32 fp64 sums to `fn` (sum over ranks, in place, on `xchg`) and then
-// every rank runs the same solve on the same numbers (SURVEY 8e row 1).
-int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_opts *opts_in,
-                   lslam_stats *stats, lslam_allreduce_fn fn, void *user, double *xchg, bool use_comm = false) {
+// One call of run_batch_impl: what its stages share.  Built once at the top; the stages below take (ctx, call).
+struct RunCall {
+  // the caller's arguments as given (the lazy path's re-entry hands them on unchanged)
+  int32_t n_scans;
+  float *poses;
+  const lslam_opts *opts_in;
+  lslam_stats *stats;
+  lslam_allreduce_fn fn;
+  void *user;
+  double *xchg;  // sharded: the exchange buffer (the caller's; upload_states puts the library's own here when there is none)
+  bool use_comm;
+  lslam_opts o{};  // the resolved options
+  int ab = 0;      // o.ab_switches | ctx->env_ab
+  int max_it = 0, search = 0;
+  bool sharded = false, unbounded = false, lazy = false;
+  int in_flight = 1, n_chunks = 1;  // the resident scans are matched `in_flight` at a time
+  // running counters
+  int launched = 0, n_launches = 0, batch = 1;
+  double total_points = -1.0;  // sharded: points of the whole scan (sum over ranks)
+  bool gnp_done = false;
+  uint64_t grid_launches_before = 0;
+  SweepArgs sa;
+  SolveArgs so{};
+  StereoArgs sta{};
+  // the chunked loops (configure_search)
+  bool compact = false, force_cert = false, no_probe2 = true, cert_counters_reset = false;
+  std::vector<int> done_iters;  // iterations enqueued per chunk
+  std::vector<char> finished;
+  std::vector<int32_t> active_n;
+  std::vector<double> score2, match2;  // fine_score_pass
+};
+
+int fail_all(const RunCall &call, int code) {
+  if (call.stats) for (int32_t p = 0; p < call.n_scans; ++p) call.stats[p].status = code;
+  return code;
+}
+
+// the pair of events around sweep launch `launch` of a profiled call (null otherwise); made on first use, kept by the context
+hipError_t sweep_events(lslam_ctx *ctx, const RunCall &call, int launch, hipEvent_t *e0, hipEvent_t *e1) {
+  *e0 = *e1 = nullptr;
+  if (!call.o.profile) return hipSuccess;
+  while ((int)ctx->sweep_ev.size() < 2 * (launch + 1)) {
+    hipEvent_t e;
+    hipError_t rc_e = hipEventCreate(&e);
+    if (rc_e != hipSuccess) return rc_e;
+    ctx->sweep_ev.push_back(e);
+  }
+  *e0 = ctx->sweep_ev[2 * launch];
+  *e1 = ctx->sweep_ev[2 * launch + 1];
+  return hipSuccess;
+}
+
+int exchange_sums(lslam_ctx *ctx, const RunCall &call) {  // sharded: sum xchg[0..32) over the ranks; ordered on the library's stream
+  if (call.fn) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    call.fn(call.user, call.xchg, NCOL);  // returns with the sum visible to this stream
+  } else {
+    if (comm_allreduce_f64(ctx->comm, call.xchg, NCOL, ctx->stream) != hipSuccess) return LSLAM_ERR_COMM;
+  }
+  return LSLAM_OK;
+}
+
+// ---- chunks: scans [p0, p1) of the resident batch, blocks [fb, lb) ------------------------------------------------
+struct ChunkRange { int p0, p1; int32_t fb, lb; };
+ChunkRange chunk_range(const lslam_ctx *ctx, const RunCall &call, int c) {
+  const int p0 = c * call.in_flight, p1 = std::min<int>(call.n_scans, p0 + call.in_flight);
+  const ProbBlocks &last = ctx->h_probs[(size_t)p1 - 1];
+  return {p0, p1, ctx->h_probs[(size_t)p0].first_block, last.first_block + last.n_blocks};
+}
+int32_t max_chunk_blocks(const lslam_ctx *ctx, const RunCall &call) {
+  int32_t max_nb = 0;
+  for (int c = 0; c < call.n_chunks; ++c) {
+    const ChunkRange r = chunk_range(ctx, call, c);
+    max_nb = std::max(max_nb, r.lb - r.fb);
+  }
+  return max_nb;
+}
+// overflow area of the shallow LDS stack: sized for the largest chunk
+int reserve_chunk_stack_ovf(lslam_ctx *ctx, const RunCall &call, SweepArgs &a) {
+  const int32_t max_nb = std::max(max_chunk_blocks(ctx, call), 1);
+  HIP_TRY(ctx->stack_ovf.reserve(stack_ovf_words((size_t)max_nb * SWEEP_BLOCK, std::max(ctx->tc.depth, ctx->ts.depth))));
+  a.stack_ovf = ctx->stack_ovf.p;
+  return LSLAM_OK;
+}
+
+// `base` (the call's SweepArgs, or the fine-score pass's copy of them), call.so and call.sta cut down to chunk c.  The
+// fine-score pass (`fine`) only reduces the LiDAR rows: no second probe lists, no stereo slice, reduce_only = 2, the sums
+// to the exchange buffer of a sharded run -- and, sharded, no grid.
+struct ChunkArgs { SweepArgs sc; SolveArgs soc; StereoArgs stc; };
+int slice_chunk(lslam_ctx *ctx, RunCall &call, const SweepArgs &base, int c, bool fine, ChunkArgs &out) {
+  const ChunkRange r = chunk_range(ctx, call, c);
+  SweepArgs &sc = out.sc;
+  sc = base;
+  sc.blocks = ctx->blocks.p + r.fb;
+  sc.nb_total = r.lb - r.fb;
+  sc.partials = ctx->partials.p + (size_t)r.fb * NCOL;
+  if (!fine && call.compact && call.done_iters[(size_t)c] > 0) {  // only the workgroups of the scans still running (compact_active_kernel, below)
+    sc.active_blocks = ctx->active_blocks.p + r.fb;
+    sc.n_active = call.active_n[(size_t)c];
+  }
+  // throughput-bound launches only (launch_sweep's own test: more wavefronts than two per SIMD): a launch that fits the
+  // device at once ends when its slowest wavefront does, certificates or not, and the second pass is two launches more
+  // per iteration (measured on single scans: 0.29 against 0.26 ms per loop).  LSLAM_KNN_CERT=2 takes it regardless (tests)
+  // (the fine-score pass: the grid sweep's second pass alone)
+  const bool pass2 = fine ? sc.grid != 0
+                          : (sc.grid || sc.prev_q) && !sc.tail.count && (sc.grid || call.force_cert || (long)sc.nb_total * (SWEEP_BLOCK / 64) > 2 * 1024);
+  if (pass2 && fine && call.sharded) {
+    sc.grid = 0;
+  } else if (pass2) {
+    if (!fine && !call.cert_counters_reset) {  // once per call: whatever an earlier call that ended in an error left in the plan's counters
+      HIP_TRY(hipMemsetAsync(ctx->cert_count.p, 0, 6 * sizeof(int32_t), ctx->stream));
+      call.cert_counters_reset = true;
+    }
+    sc.need_list = ctx->need_list.p + (size_t)r.fb * SWEEP_BLOCK;
+    sc.need_cnt = ctx->need_cnt.p + r.fb;
+    if (!fine && sc.grid == 1 && !call.no_probe2) {
+      sc.need2_list = ctx->need2_list.p + (size_t)r.fb * SWEEP_BLOCK;
+      sc.need2_cnt = ctx->need2_cnt.p + r.fb;
+    }
+    sc.groups = ctx->groups.p + ctx->h_prob_group0[(size_t)r.p0];
+    sc.n_groups = ctx->h_prob_group0[(size_t)r.p1] - ctx->h_prob_group0[(size_t)r.p0];
+    sc.group_block_base = r.fb;
+  }
+  SolveArgs &soc = out.soc;
+  soc = call.so;
+  soc.states = ctx->d_state.p + r.p0;
+  soc.probs = ctx->probs.p + r.p0;
+  soc.n_prob = r.p1 - r.p0;
+  out.stc = call.sta;  // the stereo blocks of this chunk's scans (their sets are consecutive)
+  if (fine) {
+    soc.reduce_only = 2;
+    soc.ext_sums = nullptr;
+    soc.partials2 = nullptr;  // LiDAR rows only
+    soc.probs2 = nullptr;
+    soc.sums_out = call.sharded ? call.xchg : nullptr;
+  } else if (call.so.probs2) {
+    soc.probs2 = call.so.probs2 + r.p0;
+    const int32_t sfb = ctx->h_st_probs[(size_t)r.p0].first_block;
+    out.stc.blocks = call.sta.blocks + sfb;
+    out.stc.partials = call.sta.partials + (size_t)sfb * NCOL;
+    out.stc.n_blocks = ctx->h_st_probs[(size_t)r.p1 - 1].first_block + ctx->h_st_probs[(size_t)r.p1 - 1].n_blocks - sfb;
+  }
+  return LSLAM_OK;
+}
+
+// ---- stages of run_batch_impl, in the order it calls them ---------------------------------------------------------
+// Argument checks, and whether a map with deferred trees is matched without them.
+int validate_call(lslam_ctx *ctx, RunCall &call) {
   int rc = check_ctx(ctx, true);
   if (rc) return rc;
+  const int32_t n_scans = call.n_scans;
   // A map whose kd-trees are deferred (lslam_map_defer_trees) is matched through its cell grids alone when the call is a
   // latency-bound one on the plain loop -- a mapping frame: one scan of a few thousand points; anything else builds the trees now.
-  bool lazy = false;
   if (ctx->trees_pending) {
-    const lslam_opts *oi = opts_in;
+    const lslam_opts *oi = call.opts_in;
     const int sm = ctx->env_search >= 0 ? ctx->env_search : (oi ? (oi->search_mode & 0xFF) : LSLAM_SEARCH_AUTO);
-    lazy = ctx->have_map && ctx->have_scan && !ctx->cube_mode && !fn && !use_comm && n_scans == ctx->n_prob &&
-           (sm == LSLAM_SEARCH_AUTO || sm == LSLAM_SEARCH_GRID) && !(oi && oi->fine_score && oi->use_score) &&
-           (long)ctx->nb_total * (SWEEP_BLOCK / 64) <= 2 * 1024 && ctx->kc.view.cell_start && ctx->ks.view.cell_start;
-    if (!lazy) {
+    call.lazy = ctx->have_map && ctx->have_scan && !ctx->cube_mode && !call.fn && !call.use_comm && n_scans == ctx->n_prob &&
+                (sm == LSLAM_SEARCH_AUTO || sm == LSLAM_SEARCH_GRID) && !(oi && oi->fine_score && oi->use_score) &&
+                (long)ctx->nb_total * (SWEEP_BLOCK / 64) <= 2 * 1024 && ctx->kc.view.cell_start && ctx->ks.view.cell_start;
+    if (!call.lazy) {
       rc = ensure_trees(ctx);
       if (rc) return rc;
     }
   }
-  if (!poses || n_scans <= 0) {
+  if (!call.poses || n_scans <= 0) {
     set_err("null poses");
     return LSLAM_ERR_INVALID;
   }
-  lslam_opts o;
-  if (opts_in) o = *opts_in; else lslam_default_opts(&o);
-  if (stats) std::memset(stats, 0, sizeof(lslam_stats) * (size_t)n_scans);
-  auto fail_all = [&](int code) {
-    if (stats) for (int32_t p = 0; p < n_scans; ++p) stats[p].status = code;
-    return code;
-  };
-  if (!ctx->have_map) { set_err("no map set"); return fail_all(LSLAM_ERR_NO_MAP); }
-  if (!ctx->have_scan) { set_err("no scan set"); return fail_all(LSLAM_ERR_NO_SCAN); }
+  if (call.opts_in) call.o = *call.opts_in; else lslam_default_opts(&call.o);
+  if (call.stats) std::memset(call.stats, 0, sizeof(lslam_stats) * (size_t)n_scans);
+  if (!ctx->have_map) { set_err("no map set"); return fail_all(call, LSLAM_ERR_NO_MAP); }
+  if (!ctx->have_scan) { set_err("no scan set"); return fail_all(call, LSLAM_ERR_NO_SCAN); }
   if (n_scans != ctx->n_prob) {
     set_err("batch size %d does not match the %d resident scans", n_scans, ctx->n_prob);
-    return fail_all(LSLAM_ERR_INVALID);
+    return fail_all(call, LSLAM_ERR_INVALID);
   }
   if (ctx->n_stereo > 0 && ctx->n_st_sets != n_scans) {
     set_err("the stereo term holds %d observation set(s) and %d scan(s) are resident: one set per scan (lslam_stereo_set_batch)",
             ctx->n_st_sets, n_scans);
-    return fail_all(LSLAM_ERR_INVALID);
+    return fail_all(call, LSLAM_ERR_INVALID);
   }
   // ScanMatch.cpp:57-61 (variant C, FeatureMap::scanMatchScan, has no such guard)
-  if (!ctx->cube_mode && (ctx->info.n_corner < 50 || ctx->info.n_surf < 100)) return fail_all(LSLAM_TOO_FEW_REF);
-  const int max_it = o.max_iterations < 0 ? 0 : o.max_iterations;
+  if (!ctx->cube_mode && (ctx->info.n_corner < 50 || ctx->info.n_surf < 100)) return fail_all(call, LSLAM_TOO_FEW_REF);
+  const lslam_opts &o = call.o;
+  call.ab = o.ab_switches | ctx->env_ab;
+  call.max_it = o.max_iterations < 0 ? 0 : o.max_iterations;
+  call.sharded = call.fn != nullptr || call.use_comm;
+  call.unbounded = env_once().unbounded_knn;  // A/B switch
+  call.in_flight = call.sharded ? n_scans : (o.scans_in_flight > 0 ? std::min<int>(o.scans_in_flight, n_scans) : std::min<int>(n_scans, 128));
+  call.n_chunks = (n_scans + call.in_flight - 1) / call.in_flight;
+  return LSLAM_OK;
+}
+
+// The start states go up; the SweepArgs / SolveArgs / StereoArgs every path starts from.
+int upload_states(lslam_ctx *ctx, RunCall &call) {
+  const lslam_opts &o = call.o;
+  const int32_t n_scans = call.n_scans;
   // Every call starts cold: the neighbour lists a previous call left behind belong to another pose (or
   // another scan) and must not bound this call's first sweep -- a real call on a new scan has none.
   // From the second sweep on the bound comes from the first sweep of THIS loop.
@@ -1636,44 +1786,43 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
   ctx->grid_state_valid = false;
 
   for (int32_t p = 0; p < n_scans; ++p) {
-    init_state(ctx->h_state.p[p], poses + 6 * p);
-    if (max_it == 0) ctx->h_state.p[p].done = 1;
+    init_state(ctx->h_state.p[p], call.poses + 6 * p);
+    if (call.max_it == 0) ctx->h_state.p[p].done = 1;
   }
   HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState) * (size_t)n_scans,
                          hipMemcpyHostToDevice, ctx->stream));
-  const int search = resolve_search_mode(ctx, o.search_mode);  // (may make the packet search's nodes: before the views are copied)
-  SweepArgs sa;
+  call.search = resolve_search_mode(ctx, o.search_mode);  // (may make the packet search's nodes: before the views are copied)
+  SweepArgs &sa = call.sa;
   fill_sweep_args(ctx, sa);
-  sa.packet = search == LSLAM_SEARCH_PACKET ? 1 : 0;
+  sa.packet = call.search == LSLAM_SEARCH_PACKET ? 1 : 0;
   sa.stack_mode = resolve_stack_mode(ctx, o.search_mode);
   // the production sweep keeps a shallow stack in LDS: it always gets the overflow area (sized per
-  // chunk below; the sharded path has one resident scan)
-  const bool sharded = fn != nullptr || use_comm;
-  if (sharded) {
+  // chunk by configure_search; the sharded path has one resident scan)
+  if (call.sharded) {
     HIP_TRY(ctx->stack_ovf.reserve(stack_ovf_words((size_t)sa.nb_total * SWEEP_BLOCK)));
     sa.stack_ovf = ctx->stack_ovf.p;
-    if (!xchg) {  // the library's own exchange buffer
+    if (!call.xchg) {  // the library's own exchange buffer
       HIP_TRY(ctx->xchg.reserve(NCOL));
-      xchg = ctx->xchg.p;
+      call.xchg = ctx->xchg.p;
     }
   }
-  SolveArgs so{};
+  SolveArgs &so = call.so;
   so.states = ctx->d_state.p;
   so.partials = ctx->partials.p;
   so.probs = ctx->probs.p;
   so.n_prob = n_scans;
   so.reduce_only = 0;
   so.ext_sums = nullptr;
-  so.max_iterations = max_it;
+  so.max_iterations = call.max_it;
   so.delta_r_abort = o.delta_r_abort;
   so.delta_t_abort = o.delta_t_abort;
   so.eig_thresh = 100.0f;  // ScanMatch.cpp:223
   so.min_rows = 50;        // ScanMatch.cpp:142
   so.too_few_continue = 0;
   so.nan_reset = 0;
-  // joint LiDAR + stereo system: each scan's stereo records join its reduction in every iteration (the set count was checked above)
-  StereoArgs sta{};
+  // joint LiDAR + stereo system: each scan's stereo records join its reduction in every iteration (the set count was checked by validate_call)
   if (ctx->n_stereo > 0) {
+    StereoArgs &sta = call.sta;
     sta.landmarks = ctx->st_lm.p;
     sta.obs = ctx->st_obs.p;
     sta.blocks = ctx->st_blocks.p;
@@ -1684,499 +1833,418 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
     so.partials2 = ctx->st_partials.p;
     so.probs2 = ctx->st_probs.p;
   }
-
-  auto sweep_events = [&](int launch, hipEvent_t *e0, hipEvent_t *e1) -> hipError_t {
-    *e0 = *e1 = nullptr;
-    if (!o.profile) return hipSuccess;
-    while ((int)ctx->sweep_ev.size() < 2 * (launch + 1)) {
-      hipEvent_t e;
-      hipError_t rc_e = hipEventCreate(&e);
-      if (rc_e != hipSuccess) return rc_e;
-      ctx->sweep_ev.push_back(e);
-    }
-    *e0 = ctx->sweep_ev[2 * launch];
-    *e1 = ctx->sweep_ev[2 * launch + 1];
-    return hipSuccess;
-  };
   // The loop is device-resident: sweep/solve pairs are enqueued back to back and a
   // finished loop turns the remaining launches into immediate exits.  To avoid paying
   // for many such exits the first batch is sized from the previous call's iteration
   // count (+1 spare); only if a loop is still running after it does the host look at
   // the states (one round trip) and enqueue two more iterations at a time.
   HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-  const uint64_t grid_launches_before = ctx->sweep_variants[SWEEP_VARIANT_GRID];
-  int launched = 0;
-  int batch = ctx->iter_hint < 1 ? 1 : ctx->iter_hint;
-  double total_points = -1.0;  // sharded: points of the whole scan (sum over ranks)
-  auto exchange = [&]() -> int {  // sharded: sum xchg[0..32) over the ranks; ordered on the library's stream
-    if (fn) {
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      fn(user, xchg, NCOL);  // returns with the sum visible to this stream
-    } else {
-      if (comm_allreduce_f64(ctx->comm, xchg, NCOL, ctx->stream) != hipSuccess) return LSLAM_ERR_COMM;
-    }
-    return LSLAM_OK;
-  };
-  if (sharded) {
-    // xchg[32]: the local point count first (one exchange per call), then the sums per iteration
-    const bool unbounded = env_once().unbounded_knn;
-    sa.bounded = (ctx->cube_mode || unbounded) ? 0 : 1;
-    double cnt[NCOL] = {0};
-    cnt[0] = (double)ctx->nqc[0] + (double)ctx->nqs[0];
-    HIP_TRY(hipMemcpyAsync(xchg, cnt, sizeof(cnt), hipMemcpyHostToDevice, ctx->stream));
-    rc = exchange();
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(cnt, xchg, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    total_points = cnt[0];
-    // With the library's communicator the loop is device-resident like the single-GPU one: sweep ->
-    // per-rank reduction straight into the exchange buffer -> ncclAllReduce -> replicated solve, `batch`
-    // iterations enqueued before the host looks.  Every rank sees the same sums, hence the same `done`
-    // flag, hence enqueues the same number of collectives.  A callback transport (fn) needs the host
-    // between the two halves of every iteration.
-    while (launched < max_it) {
-      const int todo = fn ? 1 : std::min(batch, max_it - launched);
-      for (int b = 0; b < todo; ++b) {
-        sa.prev_valid = (sa.bounded && launched > 0) ? 1 : 0;
-        hipEvent_t e0, e1;
-        HIP_TRY(sweep_events(launched, &e0, &e1));
-        HIP_TRY(sweep_launch(ctx, sa, o.jtj_mode, e0, e1));
-        HIP_TRY(launch_stereo(sta, ctx->stream));
-        so.reduce_only = 1;
-        so.ext_sums = nullptr;
-        so.sums_out = xchg;
-        HIP_TRY(launch_solve(so, ctx->stream));
-        rc = exchange();
-        if (rc) return rc;
-        so.reduce_only = 0;
-        so.ext_sums = xchg;
-        so.sums_out = nullptr;
-        HIP_TRY(launch_solve(so, ctx->stream));
-        ++launched;
-      }
-      HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-      HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      if (ctx->h_state.p[0].done) break;  // identical on every rank: same sums, same solve
-      batch = 2;
-    }
-  }
-  // ---- device-resident loops -----------------------------------------------------------------------
-  // The resident scans are matched `in_flight` at a time (a keyframe re-matching pass holds hundreds
-  // of scans, pose_graph/graph.cpp:171-197): every chunk is its own sequence of sweep/solve launches
-  // over its block range, so the traversal-stack overflow area and the wavefront count of a launch stay
-  // bounded.  All chunks' first `batch` iterations are enqueued back to back before the host looks once.
-  int n_launches = 0;
-  // One resident scan: the whole loop in ONE persistent launch (gn_persistent_kernel) when every block of the sweep can
-  // be resident at once and nothing needs the launches in between (per-launch profiling, the stereo term, the exchange of
-  // a sharded run, per-cube trees, the packet search, trees deeper than the LDS stack).  OFF by default
-  // (lslam_opts.ab_switches & LSLAM_AB_PERSISTENT_GN turns it on): bit-identical results, but measured no faster than the launch loop -- 327 us
-  // against 315 us of device time per four-iteration scanMatchScan of 115 200 points; the two grid exchanges and the
-  // replicated solve of an iteration cost what the solve launch and its two gaps do.
-  bool gnp_done = false;
-  {
-    const bool gnp_off = !((o.ab_switches | ctx->env_ab) & LSLAM_AB_PERSISTENT_GN);
-    const bool unbounded = env_once().unbounded_knn;
-    if (!sharded && !lazy && n_scans == 1 && !gnp_off && ctx->gnp_ok && !o.profile && ctx->n_stereo == 0 && !ctx->cube_mode &&
-        !sa.packet && sa.stack_mode != SWEEP_STACK_SHALLOW && max_it > 0 && ctx->tc.depth <= KD_STACK_LDS + 1 && ctx->ts.depth <= KD_STACK_LDS + 1 &&
-        sa.nb_total > 0 && sa.nb_total <= 512) {
-      if (ctx->gnp_cap < 0) ctx->gnp_cap = gn_persistent_capacity(ctx->device);
-      if (sa.nb_total <= ctx->gnp_cap) {
-        // [2][nb][32] floats, then [3][32][32] doubles (8-byte aligned: the float part is a multiple of 64 words)
-        const size_t n_slot = 2 * (size_t)sa.nb_total * NCOL + 2 * 3 * 32 * NCOL;
-        HIP_TRY(ctx->gnp_slots.reserve(n_slot));
-        HIP_TRY(ctx->gnp_bar.reserve(2));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ctx->gnp_slots.p, (int)0xFFF8DEADu, n_slot, ctx->stream));
-        HIP_TRY(hipMemsetAsync(ctx->gnp_bar.p, 0, 2 * sizeof(unsigned), ctx->stream));
-        SweepArgs sp = sa;
-        sp.bounded = unbounded ? 0 : 1;
-        sp.stack_ovf = nullptr;
-        GnLoopArgs gl{};
-        gl.slots = ctx->gnp_slots.p;
-        gl.gslots = reinterpret_cast<double *>(ctx->gnp_slots.p + 2 * (size_t)sa.nb_total * NCOL);
-        gl.bar = ctx->gnp_bar.p;
-        gl.state_out = ctx->d_state.p;
-        gl.max_iterations = max_it;
-        gl.min_rows = so.min_rows;
-        gl.delta_r_abort = so.delta_r_abort;
-        gl.delta_t_abort = so.delta_t_abort;
-        gl.eig_thresh = so.eig_thresh;
-        HIP_TRY(launch_gn_persistent(sp, o.jtj_mode, gl, ctx->stream));
-        ctx->sweep_variants[SWEEP_VARIANT_PERSISTENT]++;
-        HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-        unsigned gbar[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(gbar, ctx->gnp_bar.p, sizeof(gbar), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (gbar[1] == 0) {
-          gnp_done = true;
-          ctx->gnp_runs++;
-          launched = ctx->h_state.p[0].sweeps;
-        } else {  // an exchange ran into its spin limit (the workgroups were not all resident): the launch loop, from the start
-          if (ctx->env_debug) fprintf(stderr, "[lslam] persistent GN kernel timed out in its grid exchange: launch loop from here on\n");
-          ctx->gnp_ok = false;
-          init_state(ctx->h_state.p[0], poses);
-          HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
-        }
-      }
-    }
-  }
-  if (!sharded && !gnp_done) {
-    const int in_flight = o.scans_in_flight > 0 ? std::min<int>(o.scans_in_flight, n_scans) : std::min<int>(n_scans, 128);
-    const int n_chunks = (n_scans + in_flight - 1) / in_flight;
-    const bool unbounded = env_once().unbounded_knn;  // A/B switch
-    sa.bounded = (ctx->cube_mode || unbounded) ? 0 : 1;  // per-cube positions are tree-relative
-    // The grid sweep (LSLAM_SEARCH_GRID): cell grids over the resident trees, made on first use.  A map the grid cannot take
-    // (non-finite points, an extent beyond the grid's limits) is searched by the tree as before.
-    // AUTO takes it for throughput-bound batches (launch_sweep's own test: more than two wavefronts per SIMD in a launch of
-    // the first chunk): a launch that fits the device at once is latency-bound, and the grid sweep is two launches more
-    bool want_grid = search == LSLAM_SEARCH_GRID;
-    if (!want_grid && ctx->env_search < 0 && (o.search_mode & 0xFF) == LSLAM_SEARCH_AUTO && !ctx->cube_mode && !sa.packet) {
-      const int p1 = std::min(n_scans, in_flight);
-      const long nb0 = (long)ctx->h_probs[(size_t)p1 - 1].first_block + ctx->h_probs[(size_t)p1 - 1].n_blocks;
-      want_grid = nb0 * (SWEEP_BLOCK / 64) > 2 * 1024;
-    }
-    if (lazy && !sa.bounded) {  // (LSLAM_UNBOUNDED_KNN: an A/B switch of the tree search)
-      rc = ensure_trees(ctx);
+  call.grid_launches_before = ctx->sweep_variants[SWEEP_VARIANT_GRID];
+  call.batch = ctx->iter_hint < 1 ? 1 : ctx->iter_hint;
+  return LSLAM_OK;
+}
+
+// The resident scan is this rank's shard of one scan: every iteration's sums go through the exchange.
+int run_sharded_loop(lslam_ctx *ctx, RunCall &call) {
+  SweepArgs &sa = call.sa;
+  SolveArgs &so = call.so;
+  // xchg[32]: the local point count first (one exchange per call), then the sums per iteration
+  sa.bounded = (ctx->cube_mode || call.unbounded) ? 0 : 1;
+  double cnt[NCOL] = {0};
+  cnt[0] = (double)ctx->nqc[0] + (double)ctx->nqs[0];
+  HIP_TRY(hipMemcpyAsync(call.xchg, cnt, sizeof(cnt), hipMemcpyHostToDevice, ctx->stream));
+  int rc = exchange_sums(ctx, call);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(cnt, call.xchg, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  call.total_points = cnt[0];
+  // With the library's communicator the loop is device-resident like the single-GPU one: sweep ->
+  // per-rank reduction straight into the exchange buffer -> ncclAllReduce -> replicated solve, `batch`
+  // iterations enqueued before the host looks.  Every rank sees the same sums, hence the same `done`
+  // flag, hence enqueues the same number of collectives.  A callback transport (fn) needs the host
+  // between the two halves of every iteration.
+  while (call.launched < call.max_it) {
+    const int todo = call.fn ? 1 : std::min(call.batch, call.max_it - call.launched);
+    for (int b = 0; b < todo; ++b) {
+      sa.prev_valid = (sa.bounded && call.launched > 0) ? 1 : 0;
+      hipEvent_t e0, e1;
+      HIP_TRY(sweep_events(ctx, call, call.launched, &e0, &e1));
+      HIP_TRY(sweep_launch(ctx, sa, call.o.jtj_mode, e0, e1));
+      HIP_TRY(launch_stereo(call.sta, ctx->stream));
+      so.reduce_only = 1;
+      so.ext_sums = nullptr;
+      so.sums_out = call.xchg;
+      HIP_TRY(launch_solve(so, ctx->stream));
+      rc = exchange_sums(ctx, call);
       if (rc) return rc;
-      lazy = false;
+      so.reduce_only = 0;
+      so.ext_sums = call.xchg;
+      so.sums_out = nullptr;
+      HIP_TRY(launch_solve(so, ctx->stream));
+      ++call.launched;
     }
-    if (lazy) {  // the grids the map was set with; no trees: the listed points go through the wide probe
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->h_state.p[0].done) break;  // identical on every rank: same sums, same solve
+    call.batch = 2;
+  }
+  return LSLAM_OK;
+}
+
+// One resident scan: the whole loop in ONE persistent launch (gn_persistent_kernel) when every block of the sweep can
+// be resident at once and nothing needs the launches in between (per-launch profiling, the stereo term, the exchange of
+// a sharded run, per-cube trees, the packet search, trees deeper than the LDS stack).  OFF by default
+// (lslam_opts.ab_switches & LSLAM_AB_PERSISTENT_GN turns it on): bit-identical results, but measured no faster than the launch loop -- 327 us
+// against 315 us of device time per four-iteration scanMatchScan of 115 200 points; the two grid exchanges and the
+// replicated solve of an iteration cost what the solve launch and its two gaps do.
+// Sets call.gnp_done when the launch carried the loop; otherwise the chunked loop runs it.
+int run_persistent(lslam_ctx *ctx, RunCall &call) {
+  const SweepArgs &sa = call.sa;
+  const SolveArgs &so = call.so;
+  const bool gnp_off = !(call.ab & LSLAM_AB_PERSISTENT_GN);
+  if (!(!call.sharded && !call.lazy && call.n_scans == 1 && !gnp_off && ctx->gnp_ok && !call.o.profile && ctx->n_stereo == 0 && !ctx->cube_mode &&
+        !sa.packet && sa.stack_mode != SWEEP_STACK_SHALLOW && call.max_it > 0 && ctx->tc.depth <= KD_STACK_LDS + 1 && ctx->ts.depth <= KD_STACK_LDS + 1 &&
+        sa.nb_total > 0 && sa.nb_total <= 512))
+    return LSLAM_OK;
+  if (ctx->gnp_cap < 0) ctx->gnp_cap = gn_persistent_capacity(ctx->device);
+  if (sa.nb_total > ctx->gnp_cap) return LSLAM_OK;
+  // [2][nb][32] floats, then [3][32][32] doubles (8-byte aligned: the float part is a multiple of 64 words)
+  const size_t n_slot = 2 * (size_t)sa.nb_total * NCOL + 2 * 3 * 32 * NCOL;
+  HIP_TRY(ctx->gnp_slots.reserve(n_slot));
+  HIP_TRY(ctx->gnp_bar.reserve(2));
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ctx->gnp_slots.p, (int)0xFFF8DEADu, n_slot, ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->gnp_bar.p, 0, 2 * sizeof(unsigned), ctx->stream));
+  SweepArgs sp = sa;
+  sp.bounded = call.unbounded ? 0 : 1;
+  sp.stack_ovf = nullptr;
+  GnLoopArgs gl{};
+  gl.slots = ctx->gnp_slots.p;
+  gl.gslots = reinterpret_cast<double *>(ctx->gnp_slots.p + 2 * (size_t)sa.nb_total * NCOL);
+  gl.bar = ctx->gnp_bar.p;
+  gl.state_out = ctx->d_state.p;
+  gl.max_iterations = call.max_it;
+  gl.min_rows = so.min_rows;
+  gl.delta_r_abort = so.delta_r_abort;
+  gl.delta_t_abort = so.delta_t_abort;
+  gl.eig_thresh = so.eig_thresh;
+  HIP_TRY(launch_gn_persistent(sp, call.o.jtj_mode, gl, ctx->stream));
+  ctx->sweep_variants[SWEEP_VARIANT_PERSISTENT]++;
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  unsigned gbar[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(gbar, ctx->gnp_bar.p, sizeof(gbar), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (gbar[1] == 0) {
+    call.gnp_done = true;
+    ctx->gnp_runs++;
+    call.launched = ctx->h_state.p[0].sweeps;
+  } else {  // an exchange ran into its spin limit (the workgroups were not all resident): the launch loop, from the start
+    if (ctx->env_debug) fprintf(stderr, "[lslam] persistent GN kernel timed out in its grid exchange: launch loop from here on\n");
+    ctx->gnp_ok = false;
+    init_state(ctx->h_state.p[0], call.poses);
+    HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
+  }
+  return LSLAM_OK;
+}
+
+// lslam_opts.ab_switches & LSLAM_AB_FUSED_SOLVE: the solve rides in the tail of the sweep launch whenever that
+// launch is a latency-bound one (launch_sweep takes the whole-stack kernel: single scans, small batches) -- the block that
+// retires a scan's last record reduces and solves, one launch per Gauss-Newton iteration.  Bit-identical to the solve
+// kernel as its own launch (tests/test_gpu_stack_shapes.py) and MEASURED NO FASTER, so off by default: per working
+// iteration of a 115 200-point scan 83 us against 47 + 13 us of kernels plus a ~3 us gap (rocprofv3 --kernel-trace);
+// 0.270 against 0.237 ms of device time per three-iteration loop, 0.244 against 0.229 ms for a 4 835-point scan.  The
+// tail is the solve's own dependent chain (reduction round trip, 6 x 6 QR, pose update: ~13 us) run by ONE workgroup
+// that first had to finish its share of the sweep, reading the records through the coherence point; the launch it saves
+// costs less than that.  Not with the stereo term (its records come from a launch of their own).
+int configure_fused_tail(lslam_ctx *ctx, RunCall &call) {
+  SweepArgs &sa = call.sa;
+  const SolveArgs &so = call.so;
+  const bool no_fuse = !(call.ab & LSLAM_AB_FUSED_SOLVE);
+  if (no_fuse || ctx->n_stereo != 0 || sa.grid) return LSLAM_OK;
+  // the ticket counters: zero between launches (the last block of a launch resets its scan's); once per call here, in case
+  // an earlier call ended in an error half way
+  HIP_TRY(hipMemsetAsync(ctx->tail_count.p, 0, sizeof(int32_t) * (size_t)call.n_scans, ctx->stream));
+  sa.tail.count = ctx->tail_count.p;
+  sa.tail.probs = ctx->probs.p;
+  sa.tail.partials_abs = ctx->partials.p;
+  sa.tail.sp.max_iterations = so.max_iterations;
+  sa.tail.sp.min_rows = so.min_rows;
+  sa.tail.sp.too_few_continue = so.too_few_continue;
+  sa.tail.sp.nan_reset = so.nan_reset;
+  sa.tail.sp.delta_r_abort = so.delta_r_abort;
+  sa.tail.sp.delta_t_abort = so.delta_t_abort;
+  sa.tail.sp.eig_thresh = so.eig_thresh;
+  return LSLAM_OK;
+}
+
+// What the chunked loops search with: grid or trees, the lazy wide probe, certificates, the fit cache, the fused tail.
+int configure_search(lslam_ctx *ctx, RunCall &call) {
+  const lslam_opts &o = call.o;
+  const int32_t n_scans = call.n_scans;
+  SweepArgs &sa = call.sa;
+  int rc;
+  sa.bounded = (ctx->cube_mode || call.unbounded) ? 0 : 1;  // per-cube positions are tree-relative
+  // The grid sweep (LSLAM_SEARCH_GRID): cell grids over the resident trees, made on first use.  A map the grid cannot take
+  // (non-finite points, an extent beyond the grid's limits) is searched by the tree as before.
+  // AUTO takes it for throughput-bound batches (launch_sweep's own test: more than two wavefronts per SIMD in a launch of
+  // the first chunk): a launch that fits the device at once is latency-bound, and the grid sweep is two launches more
+  bool want_grid = call.search == LSLAM_SEARCH_GRID;
+  if (!want_grid && ctx->env_search < 0 && (o.search_mode & 0xFF) == LSLAM_SEARCH_AUTO && !ctx->cube_mode && !sa.packet) {
+    const long nb0 = chunk_range(ctx, call, 0).lb;
+    want_grid = nb0 * (SWEEP_BLOCK / 64) > 2 * 1024;
+  }
+  if (call.lazy && !sa.bounded) {  // (LSLAM_UNBOUNDED_KNN: an A/B switch of the tree search)
+    rc = ensure_trees(ctx);
+    if (rc) return rc;
+    call.lazy = false;
+  }
+  if (call.lazy) {  // the grids the map was set with; no trees: the listed points go through the wide probe
+    sa.kc = ctx->kc.view;
+    sa.ks = ctx->ks.view;
+    sa.grid = 2;
+    sa.grid_clip_margin = GRID_CLIP_MARGIN_MIN;
+    sa.wide_nf_slack = (call.ab & LSLAM_AB_WIDE_NF_MARGIN) ? GRID_NF_PRUNE_SLACK_WIDE : 0.0f;
+    HIP_TRY(ctx->wide_d.reserve(std::max<size_t>(ctx->n_points, 1) * 5));
+    HIP_TRY(ctx->wide_p.reserve(std::max<size_t>(ctx->n_points, 1) * 5));
+    HIP_TRY(ctx->wide_off.reserve((size_t)std::max(ctx->nb_total, 1) + 2));
+    sa.wide_d = ctx->wide_d.p;
+    sa.wide_p = ctx->wide_p.p;
+    sa.wide_off = ctx->wide_off.p;
+  } else if (want_grid && sa.bounded) {
+    rc = ensure_grid(ctx, ctx->env_grid_cell > 0.0f ? ctx->env_grid_cell : o.grid_cell);
+    if (rc) return rc;
+    if (ctx->kc.view.cell_start && ctx->ks.view.cell_start) {
       sa.kc = ctx->kc.view;
       sa.ks = ctx->ks.view;
-      sa.grid = 2;
+      sa.grid = 1;
+      if (call.ab & LSLAM_AB_REFILL) {  // A/B (off): the second pass's two-launch form -- the five of every listed point between its launches
+        HIP_TRY(ctx->wide_d.reserve(std::max<size_t>(ctx->n_points, 1) * 5));
+        HIP_TRY(ctx->wide_p.reserve(std::max<size_t>(ctx->n_points, 1) * 5));
+        sa.wide_d = ctx->wide_d.p;
+        sa.wide_p = ctx->wide_p.p;
+      }
       sa.grid_clip_margin = GRID_CLIP_MARGIN_MIN;
-      sa.wide_nf_slack = ((o.ab_switches | ctx->env_ab) & LSLAM_AB_WIDE_NF_MARGIN) ? GRID_NF_PRUNE_SLACK_WIDE : 0.0f;
-      HIP_TRY(ctx->wide_d.reserve(std::max<size_t>(ctx->n_points, 1) * 5));
-      HIP_TRY(ctx->wide_p.reserve(std::max<size_t>(ctx->n_points, 1) * 5));
-      HIP_TRY(ctx->wide_off.reserve((size_t)std::max(ctx->nb_total, 1) + 2));
-      sa.wide_d = ctx->wide_d.p;
-      sa.wide_p = ctx->wide_p.p;
-      sa.wide_off = ctx->wide_off.p;
-    } else if (want_grid && sa.bounded) {
-      rc = ensure_grid(ctx, ctx->env_grid_cell > 0.0f ? ctx->env_grid_cell : o.grid_cell);
+    }
+  }
+  ctx->ab_now = call.ab;
+  const bool grid_on = sa.grid != 0;
+  call.no_probe2 = (call.ab & LSLAM_AB_SECOND_PROBE) == 0;  // A/B (off): a second, wider probe before the tree search
+  // neighbour lists carried from sweep to sweep by certificate where a point has hardly moved (sweep_body): lslam_opts.knn_cert
+  // = 0 searches every point in every sweep, 2 takes the certificate sweep whatever the size of the launch (tests); the
+  // environment's LSLAM_KNN_CERT / LSLAM_CERT_TRY_M / LSLAM_CERT_TRACK_M, read when the context was made, override the options
+  const int cert_mode = ctx->env_knn_cert >= 0 ? ctx->env_knn_cert : o.knn_cert;
+  const bool no_cert = cert_mode == 0 || sa.grid;
+  call.force_cert = cert_mode == 2;
+  sa.prev_q = (sa.bounded && !no_cert && !sa.packet) ? ctx->prev_q.p : nullptr;
+  if (sa.prev_q) {
+    sa.prev_lb = ctx->prev_lb.p;
+    sa.cert_try_m = ctx->env_cert_try_m >= 0.0f ? ctx->env_cert_try_m : (o.cert_try_m > 0.0f ? o.cert_try_m : CERT_TRY_M_DEFAULT);
+    sa.cert_track_m = ctx->env_cert_track_m >= 0.0f ? ctx->env_cert_track_m : (o.cert_track_m > 0.0f ? o.cert_track_m : CERT_TRACK_M_DEFAULT);
+  }
+  if (grid_on) {  // the grid sweep carries (position, fifth distance) per point in prev_q; no certificates
+    sa.prev_q = ctx->prev_q.p;
+    sa.prev_lb = nullptr;
+    sa.grid_hint = ctx->prev_lb.p;  // (the certificate sweep's per-point array, free in this mode)
+    if (sa.grid == 1 && (call.ab & LSLAM_AB_FIT_CACHE)) {  // the fit cache (sweep_grid_kernel)
+      const size_t nf = std::max<size_t>(ctx->n_points, 1);
+      HIP_TRY(ctx->fit_ids.reserve(5 * nf));
+      HIP_TRY(ctx->fit_val.reserve(5 * nf));
+      sa.fit_ids = ctx->fit_ids.p;
+      sa.fit_val = ctx->fit_val.p;
+      sa.n_fit = (int32_t)nf;
+      sa.fit_from_sweep = ctx->env_fit_from_sweep > 0 ? ctx->env_fit_from_sweep : 3;
+    }
+  }
+  if ((sa.prev_q || sa.grid) && (ctx->env_debug_cert_stats || o.debug_stats)) {
+    if (!ctx->cert_stats.p) {
+      HIP_TRY(ctx->cert_stats.reserve(CERT_STATS_WORDS));
+      HIP_TRY(hipMemsetAsync(ctx->cert_stats.p, 0, CERT_STATS_WORDS * sizeof(unsigned long long), ctx->stream));
+    }
+    sa.cert_stats = ctx->cert_stats.p;
+  }
+  rc = configure_fused_tail(ctx, call);
+  if (rc) return rc;
+  // a batch through the grid sweep launches, from a loop's second sweep on, only the workgroups of the scans still running
+  call.compact = sa.grid == 1 && n_scans >= 4 && !(call.ab & LSLAM_AB_NO_COMPACT);
+  call.done_iters.assign((size_t)call.n_chunks, 0);
+  call.finished.assign((size_t)call.n_chunks, 0);
+  call.active_n.assign((size_t)call.n_chunks, 0);
+  return reserve_chunk_stack_ovf(ctx, call, sa);
+}
+
+// `iters` more Gauss-Newton iterations of chunk c: sweep (+ stereo rows) and solve, back to back on the stream
+int enqueue_chunk(lslam_ctx *ctx, RunCall &call, int c, int iters) {
+  ChunkArgs ch;
+  int rc = slice_chunk(ctx, call, call.sa, c, false, ch);
+  if (rc) return rc;
+  for (int b = 0; b < iters; ++b) {
+    // the first sweep of a loop is bounded by the acceptance gate only, later ones also by the
+    // neighbours the previous sweep of THIS loop found
+    ch.sc.prev_valid = (ch.sc.bounded && call.done_iters[(size_t)c] > 0) ? 1 : 0;
+    int variant = -1;
+    // (compacted: no LiDAR workgroup of a running scan is left -- only the stereo rows carry its loop -- nothing to sweep)
+    if (!(ch.sc.active_blocks && ch.sc.n_active <= 0)) {
+      hipEvent_t e0, e1;
+      HIP_TRY(sweep_events(ctx, call, call.n_launches, &e0, &e1));
+      HIP_TRY(sweep_launch(ctx, ch.sc, call.o.jtj_mode, e0, e1, &variant));
+      ++call.n_launches;
+    }
+    HIP_TRY(launch_stereo(ch.stc, ctx->stream));
+    if (variant != SWEEP_VARIANT_DEEP_FUSED) HIP_TRY(launch_solve(ch.soc, ctx->stream));
+    ++call.done_iters[(size_t)c];
+  }
+  return LSLAM_OK;
+}
+
+// ---- device-resident loops -----------------------------------------------------------------------
+// The resident scans are matched `in_flight` at a time (a keyframe re-matching pass holds hundreds
+// of scans, pose_graph/graph.cpp:171-197): every chunk is its own sequence of sweep/solve launches
+// over its block range, so the traversal-stack overflow area and the wavefront count of a launch stay
+// bounded.  All chunks' first `batch` iterations are enqueued back to back before the host looks once.
+int run_chunks_batched(lslam_ctx *ctx, RunCall &call) {
+  const int n_chunks = call.n_chunks;
+  for (;;) {
+    bool any = false;
+    for (int c = 0; c < n_chunks; ++c) {
+      if (call.finished[(size_t)c]) continue;
+      const int iters = std::min(call.batch, call.max_it - call.done_iters[(size_t)c]);
+      if (iters <= 0) { call.finished[(size_t)c] = 1; continue; }
+      const int rc = enqueue_chunk(ctx, call, c, iters);
       if (rc) return rc;
-      if (ctx->kc.view.cell_start && ctx->ks.view.cell_start) {
-        sa.kc = ctx->kc.view;
-        sa.ks = ctx->ks.view;
-        sa.grid = 1;
-        if ((o.ab_switches | ctx->env_ab) & LSLAM_AB_REFILL) {  // A/B (off): the second pass's two-launch form -- the five of every listed point between its launches
-          HIP_TRY(ctx->wide_d.reserve(std::max<size_t>(ctx->n_points, 1) * 5));
-          HIP_TRY(ctx->wide_p.reserve(std::max<size_t>(ctx->n_points, 1) * 5));
-          sa.wide_d = ctx->wide_d.p;
-          sa.wide_p = ctx->wide_p.p;
-        }
-        sa.grid_clip_margin = GRID_CLIP_MARGIN_MIN;
-      }
+      any = true;
     }
-    ctx->ab_now = o.ab_switches | ctx->env_ab;
-    const bool grid_on = sa.grid != 0;
-    const bool no_probe2 = ((o.ab_switches | ctx->env_ab) & LSLAM_AB_SECOND_PROBE) == 0;  // A/B (off): a second, wider probe before the tree search
-    // neighbour lists carried from sweep to sweep by certificate where a point has hardly moved (sweep_body): lslam_opts.knn_cert
-    // = 0 searches every point in every sweep, 2 takes the certificate sweep whatever the size of the launch (tests); the
-    // environment's LSLAM_KNN_CERT / LSLAM_CERT_TRY_M / LSLAM_CERT_TRACK_M, read when the context was made, override the options
-    const int cert_mode = ctx->env_knn_cert >= 0 ? ctx->env_knn_cert : o.knn_cert;
-    const bool no_cert = cert_mode == 0 || sa.grid, force_cert = cert_mode == 2;
-    sa.prev_q = (sa.bounded && !no_cert && !sa.packet) ? ctx->prev_q.p : nullptr;
-    if (sa.prev_q) {
-      sa.prev_lb = ctx->prev_lb.p;
-      sa.cert_try_m = ctx->env_cert_try_m >= 0.0f ? ctx->env_cert_try_m : (o.cert_try_m > 0.0f ? o.cert_try_m : CERT_TRY_M_DEFAULT);
-      sa.cert_track_m = ctx->env_cert_track_m >= 0.0f ? ctx->env_cert_track_m : (o.cert_track_m > 0.0f ? o.cert_track_m : CERT_TRACK_M_DEFAULT);
+    call.launched = *std::max_element(call.done_iters.begin(), call.done_iters.end());
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState) * (size_t)call.n_scans,
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    bool all_done = true;
+    for (int c = 0; c < n_chunks; ++c) {
+      const ChunkRange r = chunk_range(ctx, call, c);
+      bool cd = true;
+      for (int p = r.p0; p < r.p1; ++p) cd = cd && ctx->h_state.p[p].done;
+      if (cd || call.done_iters[(size_t)c] >= call.max_it) call.finished[(size_t)c] = 1;
+      all_done = all_done && call.finished[(size_t)c];
     }
-    if (grid_on) {  // the grid sweep carries (position, fifth distance) per point in prev_q; no certificates
-      sa.prev_q = ctx->prev_q.p;
-      sa.prev_lb = nullptr;
-      sa.grid_hint = ctx->prev_lb.p;  // (the certificate sweep's per-point array, free in this mode)
-      if (sa.grid == 1 && ((o.ab_switches | ctx->env_ab) & LSLAM_AB_FIT_CACHE)) {  // the fit cache (sweep_grid_kernel)
-        const size_t nf = std::max<size_t>(ctx->n_points, 1);
-        HIP_TRY(ctx->fit_ids.reserve(5 * nf));
-        HIP_TRY(ctx->fit_val.reserve(5 * nf));
-        sa.fit_ids = ctx->fit_ids.p;
-        sa.fit_val = ctx->fit_val.p;
-        sa.n_fit = (int32_t)nf;
-        sa.fit_from_sweep = ctx->env_fit_from_sweep > 0 ? ctx->env_fit_from_sweep : 3;
-      }
-    }
-    if ((sa.prev_q || sa.grid) && (ctx->env_debug_cert_stats || o.debug_stats)) {
-      if (!ctx->cert_stats.p) {
-        HIP_TRY(ctx->cert_stats.reserve(CERT_STATS_WORDS));
-        HIP_TRY(hipMemsetAsync(ctx->cert_stats.p, 0, CERT_STATS_WORDS * sizeof(unsigned long long), ctx->stream));
-      }
-      sa.cert_stats = ctx->cert_stats.p;
-    }
-    std::vector<int> done_iters((size_t)n_chunks, 0);    // iterations enqueued per chunk
-    std::vector<char> finished((size_t)n_chunks, 0);
-    // lslam_opts.ab_switches & LSLAM_AB_FUSED_SOLVE: the solve rides in the tail of the sweep launch whenever that
-    // launch is a latency-bound one (launch_sweep takes the whole-stack kernel: single scans, small batches) -- the block that
-    // retires a scan's last record reduces and solves, one launch per Gauss-Newton iteration.  Bit-identical to the solve
-    // kernel as its own launch (tests/test_gpu_stack_shapes.py) and MEASURED NO FASTER, so off by default: per working
-    // iteration of a 115 200-point scan 83 us against 47 + 13 us of kernels plus a ~3 us gap (rocprofv3 --kernel-trace);
-    // 0.270 against 0.237 ms of device time per three-iteration loop, 0.244 against 0.229 ms for a 4 835-point scan.  The
-    // tail is the solve's own dependent chain (reduction round trip, 6 x 6 QR, pose update: ~13 us) run by ONE workgroup
-    // that first had to finish its share of the sweep, reading the records through the coherence point; the launch it saves
-    // costs less than that.  Not with the stereo term (its records come from a launch of their own).
-    const bool no_fuse = !((o.ab_switches | ctx->env_ab) & LSLAM_AB_FUSED_SOLVE);
-    if (!no_fuse && ctx->n_stereo == 0 && !sa.grid) {
-      // the ticket counters: zero between launches (the last block of a launch resets its scan's); once per call here, in case
-      // an earlier call ended in an error half way
-      HIP_TRY(hipMemsetAsync(ctx->tail_count.p, 0, sizeof(int32_t) * (size_t)n_scans, ctx->stream));
-      sa.tail.count = ctx->tail_count.p;
-      sa.tail.probs = ctx->probs.p;
-      sa.tail.partials_abs = ctx->partials.p;
-      sa.tail.sp.max_iterations = so.max_iterations;
-      sa.tail.sp.min_rows = so.min_rows;
-      sa.tail.sp.too_few_continue = so.too_few_continue;
-      sa.tail.sp.nan_reset = so.nan_reset;
-      sa.tail.sp.delta_r_abort = so.delta_r_abort;
-      sa.tail.sp.delta_t_abort = so.delta_t_abort;
-      sa.tail.sp.eig_thresh = so.eig_thresh;
-    }
-    bool cert_counters_reset = false;
-    // a batch through the grid sweep launches, from a loop's second sweep on, only the workgroups of the scans still running
-    const bool compact = sa.grid == 1 && n_scans >= 4 && !(((o.ab_switches | ctx->env_ab) & LSLAM_AB_NO_COMPACT));
-    std::vector<int32_t> active_n((size_t)n_chunks, 0);
-    auto enqueue = [&](int c, int iters) -> int {
-      const int p0 = c * in_flight, p1 = std::min(n_scans, p0 + in_flight);
-      const int32_t fb = ctx->h_probs[(size_t)p0].first_block;
-      const int32_t lb = ctx->h_probs[(size_t)p1 - 1].first_block + ctx->h_probs[(size_t)p1 - 1].n_blocks;
-      SweepArgs sc = sa;
-      sc.blocks = ctx->blocks.p + fb;
-      sc.nb_total = lb - fb;
-      sc.partials = ctx->partials.p + (size_t)fb * NCOL;
-      if (compact && done_iters[(size_t)c] > 0) {  // only the workgroups of the scans still running (compact_active_kernel, below)
-        sc.active_blocks = ctx->active_blocks.p + fb;
-        sc.n_active = active_n[(size_t)c];
-      }
-      // throughput-bound launches only (launch_sweep's own test: more wavefronts than two per SIMD): a launch that fits the
-      // device at once ends when its slowest wavefront does, certificates or not, and the second pass is two launches more
-      // per iteration (measured on single scans: 0.29 against 0.26 ms per loop).  LSLAM_KNN_CERT=2 takes it regardless (tests)
-      if ((sc.grid || sc.prev_q) && !sc.tail.count && (sc.grid || force_cert || (long)sc.nb_total * (SWEEP_BLOCK / 64) > 2 * 1024)) {
-        if (!cert_counters_reset) {  // once per call: whatever an earlier call that ended in an error left in the plan's counters
-          HIP_TRY(hipMemsetAsync(ctx->cert_count.p, 0, 6 * sizeof(int32_t), ctx->stream));
-          cert_counters_reset = true;
-        }
-        sc.need_list = ctx->need_list.p + (size_t)fb * SWEEP_BLOCK;
-        sc.need_cnt = ctx->need_cnt.p + fb;
-        if (sc.grid == 1 && !no_probe2) {
-          sc.need2_list = ctx->need2_list.p + (size_t)fb * SWEEP_BLOCK;
-          sc.need2_cnt = ctx->need2_cnt.p + fb;
-        }
-        sc.groups = ctx->groups.p + ctx->h_prob_group0[(size_t)p0];
-        sc.n_groups = ctx->h_prob_group0[(size_t)p1] - ctx->h_prob_group0[(size_t)p0];
-        sc.group_block_base = fb;
-      }
-      SolveArgs soc = so;
-      soc.states = ctx->d_state.p + p0;
-      soc.probs = ctx->probs.p + p0;
-      soc.n_prob = p1 - p0;
-      StereoArgs stc = sta;  // the stereo blocks of this chunk's scans (their sets are consecutive)
-      if (so.probs2) {
-        soc.probs2 = so.probs2 + p0;
-        const int32_t sfb = ctx->h_st_probs[(size_t)p0].first_block;
-        stc.blocks = sta.blocks + sfb;
-        stc.partials = sta.partials + (size_t)sfb * NCOL;
-        stc.n_blocks = ctx->h_st_probs[(size_t)p1 - 1].first_block + ctx->h_st_probs[(size_t)p1 - 1].n_blocks - sfb;
-      }
-      for (int b = 0; b < iters; ++b) {
-        // the first sweep of a loop is bounded by the acceptance gate only, later ones also by the
-        // neighbours the previous sweep of THIS loop found
-        sc.prev_valid = (sc.bounded && done_iters[(size_t)c] > 0) ? 1 : 0;
-        int variant = -1;
-        // (compacted: no LiDAR workgroup of a running scan is left -- only the stereo rows carry its loop -- nothing to sweep)
-        if (!(sc.active_blocks && sc.n_active <= 0)) {
-          hipEvent_t e0, e1;
-          HIP_TRY(sweep_events(n_launches, &e0, &e1));
-          HIP_TRY(sweep_launch(ctx, sc, o.jtj_mode, e0, e1, &variant));
-          ++n_launches;
-        }
-        HIP_TRY(launch_stereo(stc, ctx->stream));
-        if (variant != SWEEP_VARIANT_DEEP_FUSED) HIP_TRY(launch_solve(soc, ctx->stream));
-        ++done_iters[(size_t)c];
-      }
-      return LSLAM_OK;
-    };
-    // overflow area of the shallow LDS stack: sized for the largest chunk
-    {
-      int32_t max_nb = 0;
-      for (int c = 0; c < n_chunks; ++c) {
-        const int p0 = c * in_flight, p1 = std::min(n_scans, p0 + in_flight);
-        max_nb = std::max(max_nb, ctx->h_probs[(size_t)p1 - 1].first_block + ctx->h_probs[(size_t)p1 - 1].n_blocks -
-                                      ctx->h_probs[(size_t)p0].first_block);
-      }
-      HIP_TRY(ctx->stack_ovf.reserve(stack_ovf_words((size_t)std::max(max_nb, 1) * SWEEP_BLOCK, std::max(ctx->tc.depth, ctx->ts.depth))));
-      sa.stack_ovf = ctx->stack_ovf.p;
-    }
-    if (compact) {
-      // One iteration at a time, and between two of them the host learns how many workgroups are left (4 bytes per chunk, one
-      // wait of ~30 us against sweeps of milliseconds): the next sweep is launched over THOSE, not over every workgroup of
-      // every scan.  The states come back once, at the end.
-      HIP_TRY(ctx->active_blocks.reserve((size_t)std::max(ctx->nb_total, 1)));
-      // [n_chunks] workgroups left, then (stereo term) [n_chunks] whether a scan of the chunk still runs
-      const bool track_running = ctx->n_stereo > 0;
-      const size_t n_cnt = (size_t)n_chunks * (track_running ? 2 : 1);
-      HIP_TRY(ctx->d_active_cnt.reserve(n_cnt));
-      HIP_TRY(ctx->h_active.reserve(n_cnt));
-      for (;;) {
-        bool any = false;
-        for (int c = 0; c < n_chunks; ++c) {
-          if (finished[(size_t)c]) continue;
-          if (done_iters[(size_t)c] >= max_it) { finished[(size_t)c] = 1; continue; }
-          rc = enqueue(c, 1);
-          if (rc) return rc;
-          const int p0 = c * in_flight, p1 = std::min(n_scans, p0 + in_flight);
-          const int32_t fb = ctx->h_probs[(size_t)p0].first_block;
-          HIP_TRY(launch_compact_active(ctx->d_state.p + p0, ctx->probs.p + p0, p1 - p0, fb, ctx->active_blocks.p + fb, ctx->d_active_cnt.p + c, ctx->stream,
-                                        track_running ? ctx->d_active_cnt.p + n_chunks + c : nullptr));
-          any = true;
-        }
-        if (!any) break;
-        launched = *std::max_element(done_iters.begin(), done_iters.end());
-        HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->h_active.p, ctx->d_active_cnt.p, sizeof(int32_t) * n_cnt, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        bool all_done = true;
-        for (int c = 0; c < n_chunks; ++c) {
-          if (finished[(size_t)c]) continue;
-          active_n[(size_t)c] = ctx->h_active.p[c];
-          // with the stereo term a running scan may have no LiDAR workgroup left to launch: the chunk is over when no scan runs
-          const bool over = track_running ? ctx->h_active.p[n_chunks + c] == 0 : active_n[(size_t)c] <= 0;
-          if (over || done_iters[(size_t)c] >= max_it) finished[(size_t)c] = 1;
-          all_done = all_done && finished[(size_t)c];
-        }
-        if (all_done) break;
-      }
-      HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState) * (size_t)n_scans, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-    } else
-    for (;;) {
-      bool any = false;
-      for (int c = 0; c < n_chunks; ++c) {
-        if (finished[(size_t)c]) continue;
-        const int iters = std::min(batch, max_it - done_iters[(size_t)c]);
-        if (iters <= 0) { finished[(size_t)c] = 1; continue; }
-        rc = enqueue(c, iters);
-        if (rc) return rc;
-        any = true;
-      }
-      launched = *std::max_element(done_iters.begin(), done_iters.end());
-      HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-      HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState) * (size_t)n_scans,
-                             hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      bool all_done = true;
-      for (int c = 0; c < n_chunks; ++c) {
-        const int p0 = c * in_flight, p1 = std::min(n_scans, p0 + in_flight);
-        bool cd = true;
-        for (int p = p0; p < p1; ++p) cd = cd && ctx->h_state.p[p].done;
-        if (cd || done_iters[(size_t)c] >= max_it) finished[(size_t)c] = 1;
-        all_done = all_done && finished[(size_t)c];
-      }
-      if (all_done || !any) break;
-      batch = 2;
-    }
+    if (all_done || !any) break;
+    call.batch = 2;
   }
-  // ---- _fineScore (ScanMatch.cpp:272-321) ---------------------------------------------------------------------------
-  // After a converged loop with the score gate on, the reference sweeps once more at the FINAL pose, accepting a point when
-  // its nearest neighbour is within sqrt(0.02) m (corner) / sqrt(0.05) m (surf) instead of the fifth within sqrt(5) m, and
-  // prints score2 / percent2; neither enters the return value.  One more launch over the converged scans (unbounded search:
-  // the bound of the loop's sweeps assumes the d2[4] < 5 gate), their sums reduced by the solve kernel's first half.
-  std::vector<double> score2((size_t)n_scans, 0.0), match2((size_t)n_scans, 0.0);
-  if (o.fine_score && o.use_score && max_it > 0) {
-    bool any_conv = false;
-    for (int32_t p = 0; p < n_scans; ++p) any_conv = any_conv || ctx->h_state.p[p].converged;
-    if (any_conv) {
-      SweepArgs sf = sa;
-      sf.tail = SweepTail{};  // this pass only reduces
-      sf.bounded = 0;
-      sf.prev_valid = 0;
-      sf.fine_gate_c = 0.02f;  // :282
-      sf.fine_gate_s = 0.05f;  // :302
-      const int in_flight = sharded ? n_scans : (o.scans_in_flight > 0 ? std::min<int>(o.scans_in_flight, n_scans) : std::min<int>(n_scans, 128));
-      const int n_chunks = (n_scans + in_flight - 1) / in_flight;
-      int32_t max_nb = 1;
-      for (int c = 0; c < n_chunks; ++c) {
-        const int p0 = c * in_flight, p1 = std::min(n_scans, p0 + in_flight);
-        max_nb = std::max(max_nb, ctx->h_probs[(size_t)p1 - 1].first_block + ctx->h_probs[(size_t)p1 - 1].n_blocks - ctx->h_probs[(size_t)p0].first_block);
-      }
-      HIP_TRY(ctx->stack_ovf.reserve(stack_ovf_words((size_t)max_nb * SWEEP_BLOCK, std::max(ctx->tc.depth, ctx->ts.depth))));
-      sf.stack_ovf = ctx->stack_ovf.p;
-      for (int c = 0; c < n_chunks; ++c) {
-        const int p0 = c * in_flight, p1 = std::min(n_scans, p0 + in_flight);
-        const int32_t fb = ctx->h_probs[(size_t)p0].first_block;
-        const int32_t lb = ctx->h_probs[(size_t)p1 - 1].first_block + ctx->h_probs[(size_t)p1 - 1].n_blocks;
-        SweepArgs sc = sf;
-        sc.blocks = ctx->blocks.p + fb;
-        sc.nb_total = lb - fb;
-        sc.partials = ctx->partials.p + (size_t)fb * NCOL;
-        if (sc.grid) {  // the grid sweep's second pass (as enqueue() sets it up)
-          if (sharded) {
-            sc.grid = 0;
-          } else {
-            sc.need_list = ctx->need_list.p + (size_t)fb * SWEEP_BLOCK;
-            sc.need_cnt = ctx->need_cnt.p + fb;
-            sc.groups = ctx->groups.p + ctx->h_prob_group0[(size_t)p0];
-            sc.n_groups = ctx->h_prob_group0[(size_t)p1] - ctx->h_prob_group0[(size_t)p0];
-            sc.group_block_base = fb;
-          }
-        }
-        SolveArgs soc = so;
-        soc.states = ctx->d_state.p + p0;
-        soc.probs = ctx->probs.p + p0;
-        soc.n_prob = p1 - p0;
-        soc.reduce_only = 2;
-        soc.ext_sums = nullptr;
-        soc.partials2 = nullptr;  // LiDAR rows only
-        soc.probs2 = nullptr;
-        soc.sums_out = sharded ? xchg : nullptr;
-        HIP_TRY(sweep_launch(ctx, sc, o.jtj_mode));
-        HIP_TRY(launch_solve(soc, ctx->stream));
-      }
-      double xs[NCOL] = {0};
-      if (sharded) {  // every rank converged together (same sums, same solve): every rank is here
-        rc = exchange();
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(xs, xchg, sizeof(xs), hipMemcpyDeviceToHost, ctx->stream));
-      }
-      HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-      HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState) * (size_t)n_scans, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      for (int32_t p = 0; p < n_scans; ++p) {
-        if (!ctx->h_state.p[p].converged) continue;
-        const double *sm = sharded ? xs : ctx->h_state.p[p].sums;
-        score2[(size_t)p] = sm[COL_SCORE];
-        match2[(size_t)p] = sm[COL_LINE] + sm[COL_PLANE];
-      }
-    }
-  }
-  ctx->grid_state_valid = !sharded && !gnp_done && ctx->sweep_variants[SWEEP_VARIANT_GRID] > grid_launches_before && n_scans == 1;
-  ctx->stage_busy = false;  // the stream has been waited for since the scan was set
-  if (lazy) {  // a point's answer needed nanoflann's visit order (sweep_wide_kernel): the trees after all, and the call again
-    bool need_tree = false;
-    for (int32_t p = 0; p < n_scans; ++p) need_tree = need_tree || ctx->h_state.p[p].pad != 0;
-    if (need_tree) {
-      rc = ensure_trees(ctx);
+  return LSLAM_OK;
+}
+
+// One iteration at a time, and between two of them the host learns how many workgroups are left (4 bytes per chunk, one
+// wait of ~30 us against sweeps of milliseconds): the next sweep is launched over THOSE, not over every workgroup of
+// every scan.  The states come back once, at the end.
+int run_chunks_compact(lslam_ctx *ctx, RunCall &call) {
+  const int n_chunks = call.n_chunks;
+  HIP_TRY(ctx->active_blocks.reserve((size_t)std::max(ctx->nb_total, 1)));
+  // [n_chunks] workgroups left, then (stereo term) [n_chunks] whether a scan of the chunk still runs
+  const bool track_running = ctx->n_stereo > 0;
+  const size_t n_cnt = (size_t)n_chunks * (track_running ? 2 : 1);
+  HIP_TRY(ctx->d_active_cnt.reserve(n_cnt));
+  HIP_TRY(ctx->h_active.reserve(n_cnt));
+  for (;;) {
+    bool any = false;
+    for (int c = 0; c < n_chunks; ++c) {
+      if (call.finished[(size_t)c]) continue;
+      if (call.done_iters[(size_t)c] >= call.max_it) { call.finished[(size_t)c] = 1; continue; }
+      const int rc = enqueue_chunk(ctx, call, c, 1);
       if (rc) return rc;
-      return run_batch_impl(ctx, n_scans, poses, opts_in, stats, fn, user, xchg, use_comm);
+      const ChunkRange r = chunk_range(ctx, call, c);
+      HIP_TRY(launch_compact_active(ctx->d_state.p + r.p0, ctx->probs.p + r.p0, r.p1 - r.p0, r.fb, ctx->active_blocks.p + r.fb, ctx->d_active_cnt.p + c, ctx->stream,
+                                    track_running ? ctx->d_active_cnt.p + n_chunks + c : nullptr));
+      any = true;
     }
+    if (!any) break;
+    call.launched = *std::max_element(call.done_iters.begin(), call.done_iters.end());
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_active.p, ctx->d_active_cnt.p, sizeof(int32_t) * n_cnt, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    bool all_done = true;
+    for (int c = 0; c < n_chunks; ++c) {
+      if (call.finished[(size_t)c]) continue;
+      call.active_n[(size_t)c] = ctx->h_active.p[c];
+      // with the stereo term a running scan may have no LiDAR workgroup left to launch: the chunk is over when no scan runs
+      const bool over = track_running ? ctx->h_active.p[n_chunks + c] == 0 : call.active_n[(size_t)c] <= 0;
+      if (over || call.done_iters[(size_t)c] >= call.max_it) call.finished[(size_t)c] = 1;
+      all_done = all_done && call.finished[(size_t)c];
+    }
+    if (all_done) break;
   }
-  int max_sweeps = 0, max_iter = 0;
+  HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState) * (size_t)call.n_scans, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return LSLAM_OK;
+}
+
+// ---- _fineScore (ScanMatch.cpp:272-321) ---------------------------------------------------------------------------
+// After a converged loop with the score gate on, the reference sweeps once more at the FINAL pose, accepting a point when
+// its nearest neighbour is within sqrt(0.02) m (corner) / sqrt(0.05) m (surf) instead of the fifth within sqrt(5) m, and
+// prints score2 / percent2; neither enters the return value.  One more launch over the converged scans (unbounded search:
+// the bound of the loop's sweeps assumes the d2[4] < 5 gate), their sums reduced by the solve kernel's first half.
+int fine_score_pass(lslam_ctx *ctx, RunCall &call) {
+  const int32_t n_scans = call.n_scans;
+  call.score2.assign((size_t)n_scans, 0.0);
+  call.match2.assign((size_t)n_scans, 0.0);
+  if (!(call.o.fine_score && call.o.use_score && call.max_it > 0)) return LSLAM_OK;
+  bool any_conv = false;
+  for (int32_t p = 0; p < n_scans; ++p) any_conv = any_conv || ctx->h_state.p[p].converged;
+  if (!any_conv) return LSLAM_OK;
+  SweepArgs sf = call.sa;
+  sf.tail = SweepTail{};  // this pass only reduces
+  sf.bounded = 0;
+  sf.prev_valid = 0;
+  sf.fine_gate_c = 0.02f;  // :282
+  sf.fine_gate_s = 0.05f;  // :302
+  int rc = reserve_chunk_stack_ovf(ctx, call, sf);
+  if (rc) return rc;
+  for (int c = 0; c < call.n_chunks; ++c) {
+    ChunkArgs ch;
+    rc = slice_chunk(ctx, call, sf, c, true, ch);
+    if (rc) return rc;
+    HIP_TRY(sweep_launch(ctx, ch.sc, call.o.jtj_mode));
+    HIP_TRY(launch_solve(ch.soc, ctx->stream));
+  }
+  double xs[NCOL] = {0};
+  if (call.sharded) {  // every rank converged together (same sums, same solve): every rank is here
+    rc = exchange_sums(ctx, call);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(xs, call.xchg, sizeof(xs), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState) * (size_t)n_scans, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   for (int32_t p = 0; p < n_scans; ++p) {
-    max_sweeps = std::max(max_sweeps, ctx->h_state.p[p].sweeps);
-    max_iter = std::max(max_iter, ctx->h_state.p[p].iter);
+    if (!ctx->h_state.p[p].converged) continue;
+    const double *sm = call.sharded ? xs : ctx->h_state.p[p].sums;
+    call.score2[(size_t)p] = sm[COL_SCORE];
+    call.match2[(size_t)p] = sm[COL_LINE] + sm[COL_PLANE];
   }
+  return LSLAM_OK;
+}
+
+// the size of the next call's first batch of iterations
+void update_iter_hint(lslam_ctx *ctx, const RunCall &call) {
+  int max_iter = 0;
+  for (int32_t p = 0; p < call.n_scans; ++p) max_iter = std::max(max_iter, ctx->h_state.p[p].iter);
   // the spare iteration (five immediate exits of 4 - 5 us each on the grid path) is dropped once three calls in a row ran the
   // same number of iterations -- a mapping node's frames do; a loop that then needs one more costs one more round trip
   ctx->iter_same = (max_iter == ctx->iter_last) ? std::min(ctx->iter_same + 1, 1000) : 0;
   ctx->iter_last = max_iter;
   ctx->iter_hint = max_iter + (ctx->iter_same >= 2 ? 0 : 1);
+}
 
+// Timing, the poses, per-scan status and stats; the call's return value.
+int write_results(lslam_ctx *ctx, const RunCall &call) {
+  const lslam_opts &o = call.o;
+  const int32_t n_scans = call.n_scans;
   float gpu_ms_total = 0.f, gpu_ms_sweep = 0.f;
   int sweep_launches = 0;
   HIP_TRY(hipEventElapsedTime(&gpu_ms_total, ctx->ev0, ctx->ev1));
   if (o.profile) {
     // every sweep launch of this call, the trailing ones that found all scans converged included
     // (a few microseconds each): the same population rocprofv3's per-kernel average is taken over
-    for (int it = 0; it < (sharded ? launched : n_launches); ++it) {
+    for (int it = 0; it < (call.sharded ? call.launched : call.n_launches); ++it) {
       float ms = 0.f;
       HIP_TRY(hipEventElapsedTime(&ms, ctx->sweep_ev[2 * it], ctx->sweep_ev[2 * it + 1]));
       gpu_ms_sweep += ms;
@@ -2186,17 +2254,18 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
   int worst = LSLAM_OK;
   for (int32_t p = 0; p < n_scans; ++p) {
     const GNState &g = ctx->h_state.p[p];
-    for (int i = 0; i < 6; ++i) poses[6 * p + i] = g.pose[i];  // always written back
+    for (int i = 0; i < 6; ++i) call.poses[6 * p + i] = g.pose[i];  // always written back
     const size_t npts = (size_t)ctx->nqc[(size_t)p] + (size_t)ctx->nqs[(size_t)p];
+    const double total_points = call.total_points >= 0.0 ? call.total_points : (double)npts;
     int status;
     double score = 0.0, percent = 0.0, s2 = 0.0, pc2 = 0.0;
     if (g.converged && o.use_score) {  // ScanMatch.cpp:263-341
       score = g.score;
       const double match_count = (double)g.n_line + (double)g.n_plane;
-      percent = (float)(match_count / (total_points >= 0.0 ? total_points : (double)npts));
+      percent = (float)(match_count / total_points);
       if (o.fine_score) {  // :317-319
-        s2 = score2[(size_t)p];
-        pc2 = (float)(match2[(size_t)p] / (total_points >= 0.0 ? total_points : (double)npts));
+        s2 = call.score2[(size_t)p];
+        pc2 = (float)(call.match2[(size_t)p] / total_points);
       }
       if (score < o.score_threshold) status = LSLAM_LOW_SCORE;
       else if (percent < o.match_percentage_threshold) status = LSLAM_LOW_PERCENT;
@@ -2207,8 +2276,8 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
       status = LSLAM_NOT_CONVERGED;
     }
     if (status != LSLAM_OK && worst == LSLAM_OK) worst = status;
-    if (stats) {
-      lslam_stats &st = stats[p];
+    if (call.stats) {
+      lslam_stats &st = call.stats[p];
       st.status = status;
       st.iterations = g.iter;
       st.n_line = g.n_line;
@@ -2229,7 +2298,39 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
       st.sweep_launches = sweep_launches;
     }
   }
-  return n_scans == 1 ? (stats ? stats[0].status : worst) : worst;
+  return n_scans == 1 ? (call.stats ? call.stats[0].status : worst) : worst;
+}
+
+// Shared body of lslam_scanmatch_run_batch and lslam_scanmatch_run_sharded.  With `fn` set the
+// resident scan is this rank's shard of ONE scan's points: every iteration reduces the local
+// partials, hands the 32 fp64 sums to `fn` (sum over ranks, in place, on `xchg`) and then
+// every rank runs the same solve on the same numbers (SURVEY 8e row 1).
+int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_opts *opts_in,
+                   lslam_stats *stats, lslam_allreduce_fn fn, void *user, double *xchg, bool use_comm = false) {
+  RunCall call{n_scans, poses, opts_in, stats, fn, user, xchg, use_comm};
+  int rc = validate_call(ctx, call);
+  if (!rc) rc = upload_states(ctx, call);
+  if (!rc && call.sharded) rc = run_sharded_loop(ctx, call);
+  if (!rc && !call.sharded) rc = run_persistent(ctx, call);
+  if (!rc && !call.sharded && !call.gnp_done) {
+    rc = configure_search(ctx, call);
+    if (!rc) rc = call.compact ? run_chunks_compact(ctx, call) : run_chunks_batched(ctx, call);
+  }
+  if (!rc) rc = fine_score_pass(ctx, call);
+  if (rc) return rc;
+  ctx->grid_state_valid = !call.sharded && !call.gnp_done && ctx->sweep_variants[SWEEP_VARIANT_GRID] > call.grid_launches_before && n_scans == 1;
+  ctx->stage_busy = false;  // the stream has been waited for since the scan was set
+  if (call.lazy) {  // a point's answer needed nanoflann's visit order (sweep_wide_kernel): the trees after all, and the call again
+    bool need_tree = false;
+    for (int32_t p = 0; p < n_scans; ++p) need_tree = need_tree || ctx->h_state.p[p].pad != 0;
+    if (need_tree) {
+      rc = ensure_trees(ctx);
+      if (rc) return rc;
+      return run_batch_impl(ctx, n_scans, poses, opts_in, stats, fn, user, xchg, use_comm);
+    }
+  }
+  update_iter_hint(ctx, call);
+  return write_results(ctx, call);
 }
 }  // namespace
 
