@@ -385,6 +385,32 @@ int lslam_debug_knn5_wide(lslam_ctx *ctx, int which_map, const void *queries, si
 int lslam_debug_sort_pairs(lslam_ctx *ctx, const uint64_t *keys, const uint32_t *values, size_t n, uint64_t *keys_out,
                            uint32_t *values_out);
 
+/* Parity taps of the coarse alignment (lslam_icp_align, csrc/lslam_icp.hip).
+ *
+ * lslam_debug_icp_step: ONE correspondence pass of the alignment's loop at the transform T (row-major 4x4, source -> target),
+ * through the code the loop runs: the target's kd-tree is built as lslam_icp_align builds it (the context's resident map is
+ * replaced), the kernel is launched with the loop's arguments plus two tap pointers, and the fit is the loop's.  Clouds and
+ * stride_bytes as lslam_icp_align takes them; max_correspondence_distance <= 0: no gate.  n_target == 0 is refused.
+ *   idx_out[n_source]  the target point each source point was paired with (index into `target`), -1: beyond the gate
+ *   d2_out[n_source]   fp32 squared distance of the transformed source point from its nearest target point (gated out or not)
+ *   sums_out[18]       n | sum d2 | sum s (3) | sum t (3) | sum s t^T (9, row-major) | 0, s = the transformed source point
+ * idx_out, d2_out and sums_out may be NULL.  out->fitted = 1 when n >= 3: R, t, W and det_sign are then what the loop would
+ * compose into T (lslam_debug_icp_fit of the sums). */
+typedef struct lslam_icp_step {
+  double R[9], t[3], W[3]; /* the increment (row-major R) and the singular values of the cross-covariance, descending */
+  int32_t det_sign;        /* sign of det(V U^T): -1 where the reflection fix was applied */
+  int32_t fitted;          /* 0: fewer than 3 correspondences, the loop would stop (R, t, W are zero) */
+  int32_t overflow_stack;  /* 1: icp_corr_kernel<true> ran (target tree deeper than the LDS stack), 0: icp_corr_kernel<false> */
+  int32_t blocks;          /* blocks of 128 source points launched */
+} lslam_icp_step;
+int lslam_debug_icp_step(lslam_ctx *ctx, const void *target, size_t n_target, const void *source, size_t n_source,
+                         size_t stride_bytes, const float T[16], double max_correspondence_distance, int32_t *idx_out,
+                         float *d2_out, double sums_out[18], lslam_icp_step *out);
+/* The rigid fit of the loop on 18 sums laid out as sums_out above (sums[0] >= 1): centroids, cross-covariance
+ * H = sum s t^T - n cs ct^T, its SVD H = U diag(W) V^T with orthonormal U and V for every H (H = 0 included), R = V diag(1, 1,
+ * det(V U^T)) U^T, t = ct - R cs.  Host code: needs no context and no device.  det_sign may be NULL. */
+int lslam_debug_icp_fit(const double sums[18], double R[9], double t[3], double W[3], int32_t *det_sign);
+
 /* The names SURVEY.md 8(b) gave these entry points before they were built, kept as exported aliases:
  *   lslam_residuals        = lslam_sweep with the MFMA contraction: coeff_out[N*4], valid_out[N] (the flag bits of
  *                            lslam_sweep), JtJ27_out[27] = the 21 upper-triangular A^T A sums then the 6 A^T b sums
@@ -869,8 +895,12 @@ int lslam_oreg_cloud(lslam_oreg *og, float *out_xyzc, size_t cap, size_t *n_out,
  * part of the reference tree: PARITY UNPINNED (csrc/lslam_icp.hip states the restated defaults;
  * oracle/icp_oracle.py is the independent CPU statement).  max_iterations <= 0: 10; transformation_epsilon
  * 0 and max_correspondence_distance <= 0 (unlimited) are PCL's defaults.  *converged = hasConverged(),
- * *fitness = getFitnessScore().  An empty target returns converged = 0 (:233-235).  The context's resident
- * map is replaced by the target's kd-tree (like lslam_odometry_match). */
+ * *fitness = getFitnessScore().  An empty target returns converged = 0 (:233-235), fitness 0.  Fewer than 3
+ * correspondences at the guess (a source of 0, 1 or 2 points, a gate that leaves as few): converged = 0,
+ * iterations = 0, T untouched, and the fitness of the guess -- DBL_MAX when no source point has a correspondence
+ * (an empty source included), which is what getFitnessScore() returns then.  A target of any rank gives a rigid
+ * T (one point, two points, a line: the SVD's factors are completed to orthonormal ones, as Eigen's are).  The
+ * context's resident map is replaced by the target's kd-tree (like lslam_odometry_match). */
 int lslam_icp_align(lslam_ctx *ctx, const void *target, size_t n_target, const void *source, size_t n_source,
                     size_t stride_bytes, float T[16], int32_t max_iterations, double transformation_epsilon,
                     double max_correspondence_distance, double *fitness, int32_t *converged, int32_t *iterations);

@@ -136,6 +136,12 @@ class LslamOdomStep(C.Structure):
                 ("solves", C.c_int32), ("tie", C.c_int32), ("refreshed", C.c_int32)]
 
 
+class LslamIcpStep(C.Structure):
+    """lslam_icp_step (include/lslam_c.h)."""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("W", C.c_double * 3), ("det_sign", C.c_int32), ("fitted", C.c_int32),
+                ("overflow_stack", C.c_int32), ("blocks", C.c_int32)]
+
+
 class LslamOregStats(C.Structure):
     """lslam_oreg_stats (include/lslam_c.h)."""
     _fields_ = [("sweeps", C.c_uint64), ("n_cells", C.c_size_t), ("n_points", C.c_size_t), ("imu_states", C.c_int32),
@@ -447,6 +453,9 @@ SYMBOLS = {
     "lslam_pg_solve": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_int32_p]),
     "lslam_icp_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, C.c_int32,
                                   C.c_double, C.c_double, c_double_p, c_int32_p, c_int32_p]),
+    "lslam_debug_icp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, C.c_double,
+                                       c_int32_p, c_float_p, c_double_p, C.POINTER(LslamIcpStep)]),
+    "lslam_debug_icp_fit": (C.c_int, [c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]),
     "lslam_comm_unique_id": (C.c_int, [c_uint8_p]),
     "lslam_comm_create": (C.c_int, [C.c_int, c_uint8_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "lslam_comm_destroy": (None, [C.c_void_p]),

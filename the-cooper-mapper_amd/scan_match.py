@@ -419,6 +419,26 @@ class Context:
         return T.reshape(4, 4), bool(conv.value), its.value, fit.value
 
     # -- parity taps -------------------------------------------------------------
+    def icp_step(self, target, source, T, max_correspondence_distance=0.0):
+        """lslam_debug_icp_step: one correspondence pass of lslam_icp_align's loop at ``T`` and the fit the loop would make.
+        -> dict(idx (n,) int32 -- -1: gated out, d2 (n,) float32, sums (18,) float64, R (3, 3), t (3,), W (3,), det_sign, fitted,
+        overflow_stack, blocks)."""
+        from .capi import LslamIcpStep, c_double_p
+        t, st = _cloud(target)
+        s, ss = _cloud(source)
+        if st != ss:
+            raise ValueError("target/source strides differ")
+        Tm = np.array(T, dtype=np.float32).reshape(16)
+        idx = np.zeros(len(s), np.int32)
+        d2 = np.zeros(len(s), np.float32)
+        sums = np.zeros(18, np.float64)
+        out = LslamIcpStep()
+        self._check(self.lib.lslam_debug_icp_step(self.h, _vp(t), len(t), _vp(s), len(s), st, _fp(Tm),
+                                                  float(max_correspondence_distance), idx.ctypes.data_as(c_int32_p), _fp(d2),
+                                                  sums.ctypes.data_as(c_double_p), C.byref(out)))
+        return dict(idx=idx, d2=d2, sums=sums, R=np.array(out.R).reshape(3, 3), t=np.array(out.t), W=np.array(out.W),
+                    det_sign=out.det_sign, fitted=bool(out.fitted), overflow_stack=bool(out.overflow_stack), blocks=out.blocks)
+
     def knn5(self, which_map, queries, search_mode=1, want_ties=False):
         """lslam_knn5_ex; search_mode 1 = one query per lane (nanoflann's traversal), 2 = packet search."""
         q, sq = _cloud(queries)
@@ -492,6 +512,22 @@ class Context:
         T = np.zeros(16, np.float32)
         self.lib.lslam_pose_to_isometry(_fp(p), _fp(T))
         return T.reshape(4, 4)
+
+
+
+def icp_fit(sums):
+    """lslam_debug_icp_fit: the rigid fit lslam_icp_align's loop makes from the 18 sums of one correspondence pass -- host code,
+    no context and no device.  -> dict(R (3, 3), t (3,), W (3,), det_sign)."""
+    from .capi import c_double_p
+    lib = load_library()
+    s = np.ascontiguousarray(sums, np.float64).reshape(18)
+    R, t, W = np.zeros(9), np.zeros(3), np.zeros(3)
+    sign = C.c_int32(0)
+    rc = lib.lslam_debug_icp_fit(s.ctypes.data_as(c_double_p), R.ctypes.data_as(c_double_p), t.ctypes.data_as(c_double_p),
+                                 W.ctypes.data_as(c_double_p), C.byref(sign))
+    if rc != 0:
+        raise LslamError(rc, "lslam_debug_icp_fit")
+    return dict(R=R.reshape(3, 3), t=t, W=W, det_sign=sign.value)
 
 
 class ScanMatch:
