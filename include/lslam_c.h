@@ -1311,6 +1311,114 @@ int lslam_pmap_window_info(lslam_loc *loc, lslam_loc_window_stats *out);
  * i - ox, j - oy, k - oz, so that a map saved by the mapping node can be opened paged.  No device is needed. */
 int lslam_index_convert(const char *in_path, int32_t ox, int32_t oy, int32_t oz, const char *out_path);
 
+/* ---- global re-localisation of the localisation node: a pose without an initial pose -----------------------------------------
+ * lslam_loc_process drops every sweep until somebody gives the node a pose (a click in RViz or a GPS fix in the reference, whose
+ * README names a "Re-Localization module" that was never written).  This stage finds the pose from one sweep and the loaded
+ * map alone: very many pose hypotheses are scored against an occupancy set of the map, the best few are refined with the
+ * node's own matcher, and the verdict says whether the answer is unambiguous.  The entry points take the node's handle and
+ * carry the prefix lslam_reloc_.  Static maps only: a node in the paged mode answers LSLAM_ERR_INVALID, as does a node
+ * without a map.  This comment is the specification; tests/relocalization_ref.py restates it in numpy.
+ *
+ * Occupancy sets.  Per feature type (0 corner, 1 surf) the set of voxels that hold at least one point the node holds after
+ * lslam_loc_load / _set_map / _set_map_from_fmap (map filter included, cubes with fewer than five points too).  Voxel edge
+ * `voxel` metres (0: 2.0); inv = 1.0f / voxel (one fp32 division on the host); the voxel of a point is
+ * (int)floorf(x * inv) per axis, one fp32 multiply, then floor.  A point one of whose three floors is not finite, or not in
+ * [-2^20, 2^20), has no voxel: it is not in the set and as a query it is not occupied.  The sets are exact (an open-addressing
+ * table of packed 64-bit keys at a load of at most 1/2, filled with 64-bit compare-and-swap), built at the first use and
+ * again when the map or `voxel` changes.
+ *
+ * Hypotheses.  h = r * n_pos + j for rotation r < n_rot and position j < n_pos; n_rot <= 4096, n_rot * n_pos <= 2^26.  A
+ * rotation is a Twist angle triplet (rx, ry, rz); its matrix R is the rotation block of lslam_pose_to_isometry for
+ * (rx, ry, rz, 0, 0, 0).  A position is float[3].
+ *
+ * Scan.  Both clouds through the node's scan filters (prepareFeatureFrame, the device step of lslam_loc_match).  With
+ * max_points > 0 and n > max_points filtered points of a type, the points 0, s, 2 s, ... with s = ceil(n / max_points) are
+ * scored, in the filter's order.
+ *
+ * Score.  q = R p + t in fp32 as ((r0 * x + r1 * y) + r2 * z) + t, every operation rounded on its own (no contraction).  A
+ * point of type T counts when q has a voxel and that voxel is in set T.  score(h) = corner hits + surf hits.  A hypothesis
+ * whose position's cube (round(p / cube_size) + origin, lslam_loc_process's rule) lies within 3 cubes of the cube array's edge
+ * on any axis scores -1 and is counted in `skipped`.
+ *
+ * Selection.  On the device: the top_m (0: 256; <= 1024) hypotheses by score descending, then index ascending; -1 is never
+ * selected; only this list comes back, behind the one host wait of the coarse stage.  On the host: greedy non-maximum
+ * suppression in that order -- a hypothesis is dropped when a kept one has max|dpos| <= nms_m (0: 2.0) and a rotation index
+ * within nms_rot (0: 2; negative: the same index only), compared cyclically modulo n_rot when rot_cyclic is set.  The first
+ * max_candidates (0: 8; <= 64) survivors are refined.
+ *
+ * Refinement and verdict.  Each candidate runs lslam_loc_match's arithmetic (the same kernels over the scan prepared once)
+ * from the hypothesis' Twist, again from its own result while it returns LSLAM_NOT_CONVERGED, at most refine_rounds (0: 3)
+ * times: bit for bit what that many lslam_loc_match calls by hand return.  Candidates are visited in the order of their
+ * sensor cube, so the cell grids are rebuilt once per distinct cube; afterwards the node's grids, counters of lslam_loc_info
+ * and pose state are as they were.  The winner is the candidate whose last match returned LSLAM_OK with the largest n_rows
+ * (ties: the better coarse rank); fraction = n_rows / (filtered corner + surf points, before subsampling); accepted when
+ * fraction >= min_fraction (0: 0.4, the reference's match_percentage_threshold).  runner_up is the best such candidate
+ * whose refined position is farther than nms_m (max|dpos|) from the winner's, or -1.
+ * Returns LSLAM_OK with accepted = 1, LSLAM_NOT_CONVERGED when no candidate converged (winner = -1), LSLAM_TOO_FEW_MATCHES
+ * when the winner is below min_fraction; the result is filled in all three.  With apply != 0 an accepted result is handed to
+ * the node exactly as lslam_loc_set_initial_pose(T) would be; otherwise the node is left as it was. */
+typedef struct {
+  float voxel;             /* m; 0: 2.0 */
+  int32_t max_points;      /* per type; 0: every filtered point */
+  int32_t top_m;           /* 0: 256; <= 1024 */
+  int32_t max_candidates;  /* 0: 8; <= 64 */
+  float nms_m;             /* 0: 2.0 */
+  int32_t nms_rot;         /* 0: 2; negative: the same rotation index only */
+  int32_t rot_cyclic;      /* rotation indices wrap around (a full yaw sweep) */
+  int32_t refine_rounds;   /* 0: 3 */
+  float min_fraction;      /* 0: 0.4 */
+  int32_t apply;
+} lslam_reloc_opts;
+typedef struct {
+  int32_t hypothesis;      /* r * n_pos + j */
+  int32_t coarse_score;
+  int32_t status;          /* of the last match */
+  int32_t rounds;          /* matches run */
+  int32_t n_rows;
+  float pose[6];           /* the refined Twist */
+} lslam_reloc_candidate;
+typedef struct {
+  int32_t accepted;
+  int32_t winner, runner_up;    /* indices into candidates, -1: none */
+  float fraction;
+  float T[16];                  /* the winner's pose, row-major 4x4 (identity without a winner) */
+  int64_t n_hypotheses, skipped;
+  int32_t n_points[2];          /* filtered scan points per type, before subsampling */
+  int32_t n_scored[2];          /* ... of which were scored */
+  int64_t occupied_voxels[2];
+  int32_t n_selected;           /* length of the downloaded top list */
+  int32_t n_candidates;
+  lslam_reloc_candidate candidates[64];  /* in coarse rank order */
+  float ms_coarse, ms_refine;   /* host wall clock of the two stages */
+} lslam_reloc_result;
+typedef struct {
+  int64_t occupied_voxels[2];   /* of the sets as last built (0 before the first build) */
+  uint64_t table_slots;         /* 64-bit slots of both tables together */
+  int64_t builds;               /* set builds since creation */
+  float voxel;                  /* the edge they were built with */
+  int32_t valid;                /* 1 while they match the loaded map */
+} lslam_reloc_map_stats;
+/* Kernel shape, for tests that have to straddle it: positions per workgroup and scan points per LDS chunk. */
+#define LSLAM_RELOC_POS_TILE 32
+#define LSLAM_RELOC_CHUNK 1024
+int lslam_reloc_relocalize(lslam_loc *loc, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
+                           const float *rot_xyz, size_t n_rot, const float *pos_xyz, size_t n_pos, const lslam_reloc_opts *opts,
+                           lslam_reloc_result *result);
+/* Parity tap: the same kernels up to the selection, no refinement; scores_out[n_rot * n_pos].  top_idx / top_score (room for
+ * top_m each, may both be NULL) receive the downloaded list, *n_top its length; result (may be NULL) is filled up to
+ * n_selected. */
+int lslam_reloc_scores(lslam_loc *loc, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
+                       const float *rot_xyz, size_t n_rot, const float *pos_xyz, size_t n_pos, const lslam_reloc_opts *opts,
+                       int32_t *scores_out, int32_t *top_idx, int32_t *top_score, int32_t *n_top, lslam_reloc_result *result);
+/* The host half of the selection alone (no device needed): greedy NMS over a top list -> keep_out[<= max_candidates] (positions
+ * in the list), returns their number or a negative status. */
+int lslam_reloc_nms(const int32_t *top_idx, int32_t n_top, const float *pos_xyz, size_t n_rot, size_t n_pos,
+                    const lslam_reloc_opts *opts, int32_t *keep_out);
+/* Tap of the occupancy sets: out[i] = 1 when query point i (map frame) has a voxel and it is in set `which`. */
+int lslam_reloc_occupied(lslam_loc *loc, int32_t which, float voxel, const void *queries, size_t nq, size_t stride_bytes,
+                         uint8_t *out);
+int lslam_reloc_info(lslam_loc *loc, lslam_reloc_map_stats *out);
+
 /* ---- Survey-cloud feature map extractor (io_module/feature_extracter.cpp:43-130 over util/pcl_util.h:39-62,107-182 and
  * util/voxel_grid_partition.hpp:80-330): a dense survey cloud -> the corner / surf cube map the localisation node loads.
  * Per partition block: VoxelGrid with a minimum point count, radius-search PCA normals over the block, a K-nearest graph,

@@ -554,10 +554,11 @@ class LaserLocalization {
 public:
   explicit LaserLocalization(lslam_ctx *ctx, int cubeX = 121, int cubeY = 121, int cubeZ = 11, float filterCorner = 1.0f,
                              float filterSurf = 1.0f, float mapFilterCorner = 1.0f, float mapFilterSurf = 1.0f)
-      : _loc(nullptr), _flags(0), _hasVelocity(false), _dynamic(false) {
+      : _loc(nullptr), _flags(0), _hasVelocity(false), _dynamic(false), _relocStatus(0) {
     detail::identity4(_lidarMappedNew);
     std::memset(_velocity, 0, sizeof(_velocity));
     std::memset(&_last, 0, sizeof(_last));
+    std::memset(&_reloc, 0, sizeof(_reloc));
     if (lslam_abi_version() != LSLAM_ABI_VERSION || lslam_sizeof_opts() != sizeof(lslam_opts) || lslam_sizeof_stats() != sizeof(lslam_stats)) {
       _err = "liblslam_hip was built from another include/lslam_c.h than this program (ABI version / struct sizes differ)";
       return;
@@ -599,6 +600,25 @@ public:
   bool stage(const float pos[3]) { return check(lslam_pmap_stage(_loc, pos)); }
   bool windowInfo(lslam_loc_window_stats *out) { return check(lslam_pmap_window_info(_loc, out)); }
   bool handleInitialPose(const float T[16]) { return check(lslam_loc_set_initial_pose(_loc, T)); }
+  // the map from host clouds (packed {x, y, z, intensity}); filter: every cube through the map filters, as loadMap does
+  bool setMap(const std::vector<float> &corner, const std::vector<float> &surf, bool filter) {
+    return check(lslam_loc_set_map(_loc, corner.data(), corner.size() / 4, surf.data(), surf.size() / 4, 16, filter ? 1 : 0));
+  }
+  // Global re-localisation (lslam_reloc_*, include/lslam_c.h): the pose of one sweep in the loaded map without an initial pose,
+  // where the reference waits for a click in RViz or a GPS fix.  rotXyz: Twist angle triplets, posXyz: positions, every pair is
+  // a hypothesis; opts may be null (the defaults).  true: accepted -- with opts->apply the node then holds the pose as after
+  // handleInitialPose(relocResult().T).  false: relocStatus() says why (LSLAM_NOT_CONVERGED, LSLAM_TOO_FEW_MATCHES: the result is
+  // filled in all the same; negative: a backend error, lastError()).
+  bool relocalize(const std::vector<float> &corner, const std::vector<float> &surf, const std::vector<float> &rotXyz,
+                  const std::vector<float> &posXyz, const lslam_reloc_opts *opts = nullptr) {
+    if (!_loc) return false;
+    _relocStatus = lslam_reloc_relocalize(_loc, corner.data(), corner.size() / 4, surf.data(), surf.size() / 4, 16, rotXyz.data(),
+                                          rotXyz.size() / 3, posXyz.data(), posXyz.size() / 3, opts, &_reloc);
+    if (_relocStatus < 0) _err = lslam_last_error();
+    return _relocStatus == LSLAM_OK && _reloc.accepted != 0;
+  }
+  const lslam_reloc_result &relocResult() const { return _reloc; }
+  int relocStatus() const { return _relocStatus; }
   // cornerLast / surfLast: packed {x, y, z, intensity}; lidarOdomNew: the odometry node's _Tsum.  false: a backend error, or the
   // sweep was dropped (dropped() says which); the match's own outcome (lastStats().status) never makes it false, as the
   // reference ignores scanMatchScan's result.
@@ -641,6 +661,8 @@ private:
   int32_t _flags;
   bool _hasVelocity, _dynamic;
   lslam_stats _last;
+  lslam_reloc_result _reloc;
+  int _relocStatus;
   std::string _err;
 };
 

@@ -168,6 +168,34 @@ class LslamLocSearchCounts(C.Structure):
                 ("bytes_up", C.c_uint64 * 2), ("bytes_down", C.c_uint64 * 2)]
 
 
+class LslamRelocOpts(C.Structure):
+    """lslam_reloc_opts (include/lslam_c.h)."""
+    _fields_ = [("voxel", C.c_float), ("max_points", C.c_int32), ("top_m", C.c_int32), ("max_candidates", C.c_int32),
+                ("nms_m", C.c_float), ("nms_rot", C.c_int32), ("rot_cyclic", C.c_int32), ("refine_rounds", C.c_int32),
+                ("min_fraction", C.c_float), ("apply", C.c_int32)]
+
+
+class LslamRelocCandidate(C.Structure):
+    """lslam_reloc_candidate (include/lslam_c.h)."""
+    _fields_ = [("hypothesis", C.c_int32), ("coarse_score", C.c_int32), ("status", C.c_int32), ("rounds", C.c_int32),
+                ("n_rows", C.c_int32), ("pose", C.c_float * 6)]
+
+
+class LslamRelocResult(C.Structure):
+    """lslam_reloc_result (include/lslam_c.h)."""
+    _fields_ = [("accepted", C.c_int32), ("winner", C.c_int32), ("runner_up", C.c_int32), ("fraction", C.c_float),
+                ("T", C.c_float * 16), ("n_hypotheses", C.c_int64), ("skipped", C.c_int64), ("n_points", C.c_int32 * 2),
+                ("n_scored", C.c_int32 * 2), ("occupied_voxels", C.c_int64 * 2), ("n_selected", C.c_int32),
+                ("n_candidates", C.c_int32), ("candidates", LslamRelocCandidate * 64), ("ms_coarse", C.c_float),
+                ("ms_refine", C.c_float)]
+
+
+class LslamRelocMapStats(C.Structure):
+    """lslam_reloc_map_stats (include/lslam_c.h)."""
+    _fields_ = [("occupied_voxels", C.c_int64 * 2), ("table_slots", C.c_uint64), ("builds", C.c_int64), ("voxel", C.c_float),
+                ("valid", C.c_int32)]
+
+
 class LslamLocWindowStats(C.Structure):
     """lslam_loc_window_stats (include/lslam_c.h): the paged window of the localisation node."""
     _fields_ = [("paged", C.c_int32), ("have_window", C.c_int32), ("centre", C.c_int32 * 3), ("dims", C.c_int32 * 3),
@@ -410,6 +438,14 @@ SYMBOLS = {
                                          C.POINTER(C.c_size_t)]),
     "lslam_loc_search_stats": (C.c_int, [C.c_void_p, C.POINTER(LslamLocSearchCounts)]),
     "lslam_loc_debug_knn5": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, c_float_p, c_uint8_p]),
+    "lslam_reloc_relocalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, C.c_size_t,
+                                         c_float_p, C.c_size_t, C.POINTER(LslamRelocOpts), C.POINTER(LslamRelocResult)]),
+    "lslam_reloc_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, C.c_size_t,
+                                     c_float_p, C.c_size_t, C.POINTER(LslamRelocOpts), c_int32_p, c_int32_p, c_int32_p, c_int32_p,
+                                     C.POINTER(LslamRelocResult)]),
+    "lslam_reloc_nms": (C.c_int, [c_int32_p, C.c_int32, c_float_p, C.c_size_t, C.c_size_t, C.POINTER(LslamRelocOpts), c_int32_p]),
+    "lslam_reloc_occupied": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_size_t, C.c_size_t, c_uint8_p]),
+    "lslam_reloc_info": (C.c_int, [C.c_void_p, C.POINTER(LslamRelocMapStats)]),
     "lslam_pmap_open": (C.c_int, [C.c_void_p, C.c_char_p]),
     "lslam_pmap_setup_capacity": (C.c_int, [C.c_void_p, C.c_size_t]),
     "lslam_pmap_update": (C.c_int, [C.c_void_p, c_float_p]),

@@ -462,6 +462,21 @@ struct lslam_loc {
   // ---- the paged mode (lslam_pmap_open) ----
   float cfg_cube = 50.0f, cfg_valid = 150.0f;  // what the setup calls said (the store's own defaults)
   Paged pg;
+  // ---- re-localisation (lslam_reloc_*): the map's occupancy sets and the coarse stage's scratch ----
+  DevBuf<unsigned long long> occ_tab;  // [2 types][occ_cap] packed voxel keys, RL_EMPTY: free
+  DevBuf<unsigned long long> occ_cnt;  // [2]
+  size_t occ_cap = 0;
+  float occ_voxel = 0.0f;
+  int64_t occ_epoch = -1;              // structure_builds when the sets were built
+  int64_t occ_builds = 0, occ_voxels[2] = {0, 0};
+  DevBuf<float4> rl_scan, rl_pos;
+  DevBuf<float> rl_R;
+  DevBuf<int32_t> rl_meta, rl_scores, rl_blk, rl_sel, rl_out;
+  DevBuf<uint32_t> rl_hist;
+  DevBuf<unsigned long long> rl_keys;
+  PinBuf<float4> rl_pos_pin;
+  PinBuf<float> rl_R_pin;
+  PinBuf<int32_t> rl_out_pin;
 };
 
 namespace {
@@ -686,27 +701,18 @@ void launch_search(const LocArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(loc_tree_kernel, dim3(tree_blocks), dim3(LOC_TREE_BLOCK), 0, s, a);
 }
 
-// prepareFeatureFrame + optimizeTransform.  The clouds are in in_raw already ([corner | surf], packed) when from_device, else
-// they are packed and uploaded here.  sync_filter: the filter waits for its own result (the fall-back of a key-range error).
-int match_impl(lslam_loc *loc, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
-               bool from_device, float pose[6], lslam_stats *stats, bool sync_filter, int32_t *flags) {
+// prepareFeatureFrame: the clouds are in in_raw already ([corner | surf], packed) when from_device, else they are packed and
+// uploaded here; both go through the scan filters, and counts (device) says where the filtered clouds lie.  Nothing is waited
+// for unless sync_filter: then the filter waits for its own result (the fall-back of a key-range error).
+int prepare_scan(lslam_loc *loc, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
+                 bool from_device, bool sync_filter) {
   hipStream_t s = loc->stream;
   const size_t n = n_corner + n_surf;
   if (n > ((size_t)1 << 27)) return invalid("lslam_loc_process", "too many scan points");
   const int nbc = (int)((n_corner + LOC_BLOCK - 1) / LOC_BLOCK), nbs = (int)((n_surf + LOC_BLOCK - 1) / LOC_BLOCK);
-  const int nb_total = nbc + nbs;
-  int rc = reserve_search(loc, nb_total);
+  int rc = reserve_search(loc, nbc + nbs);
   if (rc) return rc;
-  {
-    float pos[3] = {pose[3], pose[4], pose[5]};
-    int g[3];
-    cube_of(loc, pos, g);
-    rc = ensure_grids(loc, g);
-    if (rc) return rc;
-  }
   LOC_TRY(hipMemsetAsync(loc->counts.p, 0, 4 * sizeof(int32_t), s));
-  LOC_TRY(hipMemsetAsync(loc->ctr.p, 0, (LOC_MAX_ITER + 2) * sizeof(int32_t), s));
-  LOC_TRY(hipMemsetAsync(loc->stat.p, 0, ST_N * sizeof(unsigned long long), s));
   for (int k = 0; k < 8; ++k) loc->done.p[k] = 0;
   const bool two_runs = loc->scan_leaf[0] != loc->scan_leaf[1];
   if (n) {
@@ -761,6 +767,29 @@ int match_impl(lslam_loc *loc, const void *corner, size_t n_corner, const void *
     hipLaunchKernelGGL(loc_counts_kernel, dim3(1), dim3(64), 0, s, (const int32_t *)loc->out_seg[0].p, (const uint32_t *)loc->done.p,
                        (const int32_t *)loc->out_seg[kb].p, (const uint32_t *)(loc->done.p + 4 * kb), loc->counts.p);
   }
+  return LSLAM_OK;
+}
+
+// the filter's wide key did not hold a voxel extent (known after a wait): prepare_scan has to run again with sync_filter
+bool scan_filter_overflowed(const lslam_loc *loc) { return loc->done.p[1] || loc->done.p[5]; }
+
+// optimizeTransform over the scan prepare_scan left (n_corner / n_surf as given there), from a Twist (in/out): one host wait.
+// *refilter: the wait showed that the scan has to be prepared again (nothing was written).
+int solve_scan(lslam_loc *loc, size_t n_corner, size_t n_surf, float pose[6], lslam_stats *stats, bool *refilter) {
+  hipStream_t s = loc->stream;
+  *refilter = false;
+  const int nbc = (int)((n_corner + LOC_BLOCK - 1) / LOC_BLOCK), nbs = (int)((n_surf + LOC_BLOCK - 1) / LOC_BLOCK);
+  const int nb_total = nbc + nbs;
+  const bool two_runs = loc->scan_leaf[0] != loc->scan_leaf[1];
+  {
+    float pos[3] = {pose[3], pose[4], pose[5]};
+    int g[3];
+    cube_of(loc, pos, g);
+    int rc = ensure_grids(loc, g);
+    if (rc) return rc;
+  }
+  LOC_TRY(hipMemsetAsync(loc->ctr.p, 0, (LOC_MAX_ITER + 2) * sizeof(int32_t), s));
+  LOC_TRY(hipMemsetAsync(loc->stat.p, 0, ST_N * sizeof(unsigned long long), s));
   // the Gauss-Newton loop, enqueued whole: a launch whose loop has ended leaves at once (GNState::done)
   GNState &h = *loc->h_state.p;
   std::memset(&h, 0, sizeof(h));
@@ -800,10 +829,9 @@ int match_impl(lslam_loc *loc, const void *corner, size_t n_corner, const void *
   loc->cnt.host_waits[0]++;
   loc->cnt.bytes_down[0] += sizeof(Result);
   loc->cnt.bytes_up[0] += sizeof(GNState) + sizeof(ProbBlocks);
-  if (!sync_filter && (loc->done.p[1] || loc->done.p[5])) {
-    // the filter's wide key did not hold a voxel extent: once more, with the filter measuring it (waits inside)
-    if (flags) *flags |= LSLAM_LOC_SECOND_WAIT;
-    return match_impl(loc, corner, n_corner, surf, n_surf, stride_bytes, from_device, pose, stats, true, flags);
+  if (scan_filter_overflowed(loc)) {
+    *refilter = true;
+    return LSLAM_OK;
   }
   const GNState &g = res.st;
   for (int i = 0; i < 6; ++i) pose[i] = g.pose[i];  // transformf = transform: always written back
@@ -827,6 +855,21 @@ int match_impl(lslam_loc *loc, const void *corner, size_t n_corner, const void *
     stats->point_residuals = (int64_t)res.stat[ST_SWEPT];
   }
   return status;
+}
+
+// prepareFeatureFrame + optimizeTransform
+int match_impl(lslam_loc *loc, const void *corner, size_t n_corner, const void *surf, size_t n_surf, size_t stride_bytes,
+               bool from_device, float pose[6], lslam_stats *stats, bool sync_filter, int32_t *flags) {
+  int rc = prepare_scan(loc, corner, n_corner, surf, n_surf, stride_bytes, from_device, sync_filter);
+  if (rc) return rc;
+  bool refilter = false;
+  rc = solve_scan(loc, n_corner, n_surf, pose, stats, &refilter);
+  if (refilter && !sync_filter) {
+    // the filter's wide key did not hold a voxel extent: once more, with the filter measuring it (waits inside)
+    if (flags) *flags |= LSLAM_LOC_SECOND_WAIT;
+    return match_impl(loc, corner, n_corner, surf, n_surf, stride_bytes, from_device, pose, stats, true, flags);
+  }
+  return rc;
 }
 
 void begin_sweep_counts(lslam_loc *loc) {
@@ -1937,3 +1980,5 @@ int lslam_index_convert(const char *in_path, int32_t ox, int32_t oy, int32_t oz,
 }
 
 }  // extern "C"
+
+#include "lslam_reloc_impl.hpp"

@@ -12,11 +12,48 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import LslamError, LslamLocMapStats, LslamLocSearchCounts, LslamLocWindowStats, LslamStats, c_int32_p, c_uint8_p
+from collections import namedtuple
+
+from .capi import (LslamError, LslamLocMapStats, LslamLocSearchCounts, LslamLocWindowStats, LslamRelocMapStats, LslamRelocOpts,
+                   LslamRelocResult, LslamStats, c_int32_p, c_uint8_p)
 from .feature_map import _fp, _xyzi
 
 DROPPED, HAS_VELOCITY, POSE_RESET, VELOCITY_ZEROED, SECOND_WAIT = 1, 2, 4, 8, 16  # LSLAM_LOC_* flags
 HOW_SKIPPED, HOW_GRID, HOW_TREE = 0, 1, 2
+RELOC_POS_TILE, RELOC_CHUNK = 32, 1024  # LSLAM_RELOC_POS_TILE / LSLAM_RELOC_CHUNK: the scoring kernel's shape
+
+RelocCandidate = namedtuple("RelocCandidate", "hypothesis coarse_score status rounds n_rows pose")
+RelocResult = namedtuple("RelocResult", "status accepted winner runner_up fraction T n_hypotheses skipped n_points n_scored "
+                                        "occupied_voxels n_selected candidates ms_coarse ms_refine")
+
+
+class YawSweep(np.ndarray):
+    """(n, 3) float32 Twist angle triplets of a full turn; ``rot_cyclic`` tells relocalize that the indices wrap around."""
+    rot_cyclic = True
+
+
+def yaw_sweep(step_deg, axis, tilt=(0.0, 0.0)):
+    """Angle triplets (rx, ry, rz) of a full turn about ``axis`` every ``step_deg`` degrees: axis 1 for the reference's y-up
+    sensor frame, 2 for z-up (as ``synth``).  ``tilt`` fills the other two angles, in ascending axis order.  Needs no device."""
+    if axis not in (0, 1, 2):
+        raise ValueError("axis must be 0, 1 or 2")
+    n = int(round(360.0 / float(step_deg)))
+    if n < 1 or abs(n * float(step_deg) - 360.0) > 1e-6:
+        raise ValueError("step_deg must divide 360")
+    out = np.zeros((n, 3), np.float32)
+    others = [a for a in range(3) if a != axis]
+    out[:, others[0]], out[:, others[1]] = np.float32(tilt[0]), np.float32(tilt[1])
+    out[:, axis] = (np.arange(n, dtype=np.float64) * (2.0 * np.pi / n)).astype(np.float32)
+    return out.view(YawSweep)
+
+
+def grid_positions(center, half_extent, step, height):
+    """(n, 3) float32 positions on a square grid: center[0] + i * step, center[1] + j * step for |i|, |j| <= half_extent / step,
+    first coordinate slowest, every one at ``height`` (the third coordinate).  Needs no device."""
+    k = int(np.floor(float(half_extent) / float(step) + 1e-9))
+    off = np.arange(-k, k + 1, dtype=np.float64) * float(step)
+    xs, ys = np.meshgrid(float(center[0]) + off, float(center[1]) + off, indexing="ij")
+    return np.stack([xs.ravel(), ys.ravel(), np.full(xs.size, float(height))], 1).astype(np.float32)
 
 
 class LaserLocalization:
@@ -197,3 +234,85 @@ class LaserLocalization:
         self._check(self.lib.lslam_loc_debug_knn5(self.h, int(which), q.ctypes.data_as(C.c_void_p), nq, q.shape[1] * 4, _fp(xyz), _fp(d2),
                                                   how.ctypes.data_as(c_uint8_p)))
         return xyz, d2, how
+
+    # ---- global re-localisation (lslam_reloc_*) -------------------------------------------------------------------------
+    @staticmethod
+    def _reloc_opts(rotations, opts):
+        o = LslamRelocOpts()
+        names = {f for f, _ in LslamRelocOpts._fields_}
+        for k, v in opts.items():
+            if k not in names:
+                raise TypeError("unknown relocalisation option %r" % k)
+            setattr(o, k, v)
+        if "rot_cyclic" not in opts and getattr(rotations, "rot_cyclic", False):
+            o.rot_cyclic = 1
+        return o
+
+    @staticmethod
+    def _reloc_inputs(corner, surf, rotations, positions):
+        c, s = _xyzi(corner), _xyzi(surf)
+        if c.shape[1] != s.shape[1]:
+            raise ValueError("corner and surf clouds must share a point layout")
+        r = np.ascontiguousarray(np.asarray(rotations), dtype=np.float32).reshape(-1, 3)
+        p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        return c, s, r, p
+
+    @staticmethod
+    def _reloc_result(rc, res):
+        cands = [RelocCandidate(int(c.hypothesis), int(c.coarse_score), int(c.status), int(c.rounds), int(c.n_rows),
+                                np.array(c.pose, np.float32)) for c in res.candidates[:res.n_candidates]]
+        return RelocResult(rc, bool(res.accepted), int(res.winner), int(res.runner_up), float(res.fraction),
+                           np.array(res.T, np.float32).reshape(4, 4), int(res.n_hypotheses), int(res.skipped), tuple(res.n_points),
+                           tuple(res.n_scored), tuple(res.occupied_voxels), int(res.n_selected), cands, float(res.ms_coarse),
+                           float(res.ms_refine))
+
+    def relocalize(self, corner, surf, rotations, positions, **opts):
+        """A pose from one sweep and the map alone: every (rotation, position) hypothesis scored on the device, the best few
+        refined with the node's matcher -> :class:`RelocResult` (``status``: 0 accepted, NOT_CONVERGED, TOO_FEW_MATCHES).
+        ``apply=1`` hands an accepted pose to the node as ``handle_initial_pose`` would.  Options: lslam_reloc_opts."""
+        c, s, r, p = self._reloc_inputs(corner, surf, rotations, positions)
+        o = self._reloc_opts(rotations, opts)
+        res = LslamRelocResult()
+        rc = self._check(self.lib.lslam_reloc_relocalize(self.h, c.ctypes.data_as(C.c_void_p), len(c), s.ctypes.data_as(C.c_void_p),
+                                                         len(s), c.shape[1] * 4, _fp(r), len(r), _fp(p), len(p), C.byref(o),
+                                                         C.byref(res)))
+        return self._reloc_result(rc, res)
+
+    def reloc_scores(self, corner, surf, rotations, positions, **opts):
+        """The coarse stage alone (the same kernels) -> (scores (n_rot, n_pos) int32, top_idx, top_score, RelocResult)."""
+        c, s, r, p = self._reloc_inputs(corner, surf, rotations, positions)
+        o = self._reloc_opts(rotations, opts)
+        res = LslamRelocResult()
+        scores = np.zeros(len(r) * len(p), np.int32)
+        ti, ts = np.zeros(1024, np.int32), np.zeros(1024, np.int32)
+        nt = C.c_int32()
+        rc = self._check(self.lib.lslam_reloc_scores(self.h, c.ctypes.data_as(C.c_void_p), len(c), s.ctypes.data_as(C.c_void_p), len(s),
+                                                     c.shape[1] * 4, _fp(r), len(r), _fp(p), len(p), C.byref(o),
+                                                     scores.ctypes.data_as(c_int32_p), ti.ctypes.data_as(c_int32_p),
+                                                     ts.ctypes.data_as(c_int32_p), C.byref(nt), C.byref(res)))
+        return scores.reshape(len(r), len(p)), ti[:nt.value].copy(), ts[:nt.value].copy(), self._reloc_result(rc, res)
+
+    def reloc_nms(self, top_idx, rotations, positions, **opts):
+        """The host half of the selection: positions in ``top_idx`` of the NMS survivors (no device work)."""
+        r = np.asarray(rotations, dtype=np.float32).reshape(-1, 3)
+        p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        ti = np.ascontiguousarray(top_idx, dtype=np.int32)
+        o = self._reloc_opts(rotations, opts)
+        keep = np.zeros(64, np.int32)
+        n = self._check(self.lib.lslam_reloc_nms(ti.ctypes.data_as(c_int32_p), len(ti), _fp(p), len(r), len(p), C.byref(o),
+                                                 keep.ctypes.data_as(c_int32_p)))
+        return keep[:n].copy()
+
+    def reloc_occupied(self, which, queries, voxel=0.0):
+        """Tap of the occupancy sets: 1 where the query point's voxel holds a map point of type ``which``."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        out = np.zeros(len(q), np.uint8)
+        self._check(self.lib.lslam_reloc_occupied(self.h, int(which), float(voxel), q.ctypes.data_as(C.c_void_p), len(q), q.shape[1] * 4,
+                                                  out.ctypes.data_as(c_uint8_p)))
+        return out
+
+    def reloc_info(self):
+        o = LslamRelocMapStats()
+        self._check(self.lib.lslam_reloc_info(self.h, C.byref(o)))
+        return dict(occupied_voxels=tuple(o.occupied_voxels), table_slots=int(o.table_slots), builds=int(o.builds),
+                    voxel=float(o.voxel), valid=int(o.valid))
