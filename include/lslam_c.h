@@ -210,6 +210,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed; new entry points and structs of their own (lslam_loc_*: the localisation node). */
 /* still 7: no struct changed; new entry points and a struct of their own (lslam_oreg_*: the registration node for organised clouds). */
 /* still 7: no struct changed; new entry points and a struct of their own (lslam_kfs_*: the keyframe store). */
+/* still 7: no struct changed; new entry points and structs of their own (lslam_sc_*: loop candidates by appearance). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -620,6 +621,80 @@ int lslam_kfs_scanmatch(lslam_kfs *kfs, int32_t id, float leaf_corner, float lea
                         lslam_stats *stats);
 /* lslam_fmap_add_feature_cloud with the keyframe's clouds taken from the store (fm: a feature map of the store's ctx). */
 int lslam_kfs_add_to_fmap(lslam_kfs *kfs, int32_t id, lslam_fmap *fm, const float T[16]);
+
+/* ---- loop candidates by appearance: scan context over the keyframe store ----------------------------------------------------
+ * Not in the reference: its LoopDetector only looks where the drifted estimate puts the vehicle (a sqrt(5) m radius search), so
+ * a loop whose drift exceeds that is never tried.  These entry points find candidates from what a keyframe looks like: a Scan
+ * Context descriptor (Kim & Kim, IROS 2018) per keyframe, built from the clouds where they lie in the store, and an exhaustive
+ * comparison of a query keyframe with all earlier ones.  This comment is the specification (restated in numpy by
+ * tests/place_recognition_ref.py).
+ *
+ * DESCRIPTOR of a keyframe: D[ring][sector], fp32, row-major, n_ring x n_sector, over the corner cloud followed by the surf
+ * cloud.  up_axis 1 (y up: LOAM's frame, the reference's): (a, b, h) = (z, x, y); up_axis 2 (z up): (a, b, h) = (x, y, z); the
+ * azimuth runs from +a towards +b, a right-handed rotation about the up axis.  Per point, in fp32, every operation rounded on
+ * its own (no FMA):
+ *   d2 = a*a + b*b;  rho = sqrtf(d2) (correctly rounded);  ring = (int)(rho * ring_scale), ring_scale = (float)n_ring / max_range
+ *   (one fp32 division, on the host).  The point is dropped when a coordinate is not finite, rho == 0, !(rho < max_range) or
+ *   ring >= n_ring.
+ *   In fp64: ang = atan2((double)b, (double)a); if (ang < 0) ang += 2 pi; sector = min((int)(ang * sector_scale), n_sector - 1),
+ *   sector_scale = n_sector / (2 pi) (fp64, on the host).
+ *   v = h + height_offset (one fp32 add); a point with v <= 0 leaves its cell alone.
+ * A cell holds the maximum v of its points, 0 without one.  A maximum does not depend on order: descriptors are bit-reproducible.
+ *
+ * DISTANCE of query Q to candidate C at shift s: over the columns j with |Q[:, j]| > 0 and |C[:, (j + s) mod n_sector]| > 0 the
+ * mean of the cosines of the two columns; d(s) = max(0, 1 - mean), and 1 without such a column.  The pair's distance is
+ * min_s d(s), its shift the smallest s that attains the minimum the kernel computed.  Every term is non-negative (no
+ * cancellation); the order of summation is the kernel's (a column's dot over ascending rings, the columns ascending), and the
+ * result is held to a float64 evaluation within (n_ring + n_sector + 8) * 2^-23: the (n - 1) u bound of the dot, the norms, the
+ * quotient and the mean, with a factor of two to spare.
+ * DETERMINISM: the distance and shift of a pair depend on the two descriptors only -- not on where the candidate sits in the
+ * store, in a tile or in a batch -- and the same query asked twice gives the same bits.
+ * SHIFT: if the query sensor is rotated by psi about the up axis relative to the candidate at the same place, the best shift is
+ * round(psi / (2 pi / n_sector)) mod n_sector; the pose of the query in the candidate's frame (p_c = T p_q) is the rotation by
+ * shift * 2 pi / n_sector about the up axis with zero translation -- what lslam_kfs_loop_match takes as `guess`.
+ *
+ * Descriptors live in device slabs that grow with the store, are never moved and are freed by lslam_kfs_clear /
+ * lslam_kfs_destroy (the store's lifetime rule).  They are built lazily: a call that needs them first describes every keyframe
+ * that has none, in one launch.  A store on which lslam_sc_setup was never called allocates nothing for them. */
+typedef struct lslam_sc_params {
+  int32_t n_ring;       /* 20    2 .. 32 */
+  int32_t n_sector;     /* 60    4 .. 128 */
+  float max_range;      /* 80.0  > 0 [m] */
+  float height_offset;  /* 2.0   added to the height: the sensor's height above the lowest surface that should count */
+  int32_t up_axis;      /* 1     1: y up, 2: z up */
+} lslam_sc_params;
+typedef struct lslam_sc_stats {
+  lslam_sc_params params;     /* in force (zero before lslam_sc_setup) */
+  int32_t is_set;             /* 1 once lslam_sc_setup succeeded */
+  int64_t n_described;        /* keyframes that have their descriptor */
+  uint64_t descriptor_bytes;  /* device memory of the descriptor slabs */
+  int64_t describe_launches;  /* launches of the describe kernel ... */
+  int64_t query_launches;     /* ... and of the query kernel, since creation */
+} lslam_sc_stats;
+/* Kernel shape, for tests that have to straddle it: points a workgroup takes per pass of the describe kernel, candidates per
+ * workgroup of the query kernel. */
+#define LSLAM_SC_POINT_CHUNK 256
+#define LSLAM_SC_CAND_TILE 64
+#define LSLAM_SC_MAX_TOP_K 32
+/* Writes every byte of *p (the defaults above). */
+void lslam_sc_default_params(lslam_sc_params *p);
+/* Validates (LSLAM_ERR_INVALID, the message names the field) and installs the parameters; NULL: the defaults.  Parameters that
+ * differ from those in force drop the descriptors held. */
+int lslam_sc_setup(lslam_kfs *kfs, const lslam_sc_params *params);
+/* Parity tap: keyframe id's descriptor (the raw maxima), downloaded; out[n_ring * n_sector]. */
+int lslam_sc_descriptor(lslam_kfs *kfs, int32_t id, float *out);
+/* Query q (keyframe query_ids[q]) against every keyframe 0 .. max_cand_id[q], inclusive; max_cand_id NULL: query_ids[q] - 1; a
+ * value below 0: no candidate, n_out[q] = 0; a value >= n_keyframes is refused.  The top_k (1 .. 32) best are selected on the
+ * device by distance ascending, then id ascending; only the lists come back, behind one host wait for the whole call:
+ * ids_out / shift_out / dist_out [n_query * top_k], list q at q * top_k, n_out[q] = min(top_k, eligible) entries of it valid.
+ * n_query: 0 (nothing happens) .. 65535.  The entry points are lslam_sc_*, not lslam_kfs_sc_*: the set of lslam_kfs_* names is
+ * pinned by the keyframe store's own ABI test. */
+int lslam_sc_query(lslam_kfs *kfs, int32_t n_query, const int32_t *query_ids, const int32_t *max_cand_id, int32_t top_k,
+                       int32_t *ids_out, int32_t *shift_out, float *dist_out, int32_t *n_out);
+/* Parity tap: the query kernel's distance and shift of keyframe query_id against every keyframe, itself included, without
+ * selection; dist_out / shift_out [n_keyframes]. */
+int lslam_sc_distances(lslam_kfs *kfs, int32_t query_id, float *dist_out, int32_t *shift_out);
+int lslam_sc_info(lslam_kfs *kfs, lslam_sc_stats *out);
 
 /* pcl::VoxelGrid<PointXYZI>::filter with a cubic leaf on one cloud (LaserMatcher.cpp:289-301,
  * ScanMatch.cpp:362-398 scanMatchLocal): one centroid {x,y,z,intensity} per occupied voxel, in

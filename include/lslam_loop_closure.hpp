@@ -13,6 +13,10 @@
 //                                 getFinalFeatureMap then name them by id and no cloud crosses PCIe again.  Same ABI
 //                                 kernels in the same order as the host-cloud path: same results.
 //
+// Not in the reference: KeyframeStore::sc_* (lslam_sc_*: scan-context descriptors over the store),
+// LoopDetector::detect_appearance (loop candidates from what a keyframe looks like, verified by lslam_kfs_loop_match) and
+// Graph's appearance_loops switch (off by default: nothing changes without it).
+//
 // ROS topics, threads and tf are the host program's.  Poses are row-major 4x4 doubles (Mat4d); clouds are packed
 // {x, y, z, intensity} floats.  Nothing here throws; backend failures end up in lastError() and a false / empty
 // result, the way the reference's nodes report a failed match.
@@ -135,6 +139,53 @@ public:
     _err = lslam_last_error();
     return false;
   }
+  // ---- loop candidates by appearance: scan context (lslam_sc_*) ----
+  // params == nullptr: the defaults.  Other parameters than those in force drop the descriptors held.
+  bool sc_setup(const lslam_sc_params *params = nullptr) {
+    if (lslam_sc_setup(_h, params) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  bool sc_info(lslam_sc_stats &st) {
+    if (lslam_sc_info(_h, &st) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // keyframe id's descriptor, n_ring x n_sector row-major (parity tap)
+  bool sc_descriptor(int id, std::vector<float> &out) {
+    lslam_sc_stats st;
+    if (!sc_info(st)) return false;
+    out.assign((size_t)std::max(st.params.n_ring, 1) * (size_t)std::max(st.params.n_sector, 1), 0.0f);
+    if (lslam_sc_descriptor(_h, id, out.data()) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // One list per query, best first (distance, then id), top_k entries apart in the outputs; n_out[q] of them are valid.
+  // max_cand_id == nullptr: query_ids[q] - 1.
+  bool sc_query(const std::vector<int32_t> &query_ids, const std::vector<int32_t> *max_cand_id, int top_k, std::vector<int32_t> &ids,
+                std::vector<int32_t> &shifts, std::vector<float> &dists, std::vector<int32_t> &n_out) {
+    const size_t nq = query_ids.size(), k = (size_t)std::max(top_k, 1);
+    ids.assign(nq * k, -1);
+    shifts.assign(nq * k, 0);
+    dists.assign(nq * k, 1.0f);
+    n_out.assign(nq, 0);
+    if (max_cand_id && max_cand_id->size() != nq) { _err = "sc_query: one max_cand_id per query"; return false; }
+    if (lslam_sc_query(_h, (int32_t)nq, query_ids.data(), max_cand_id ? max_cand_id->data() : nullptr, top_k, ids.data(),
+                           shifts.data(), dists.data(), n_out.data()) == LSLAM_OK)
+      return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // the query kernel's distance and shift of query_id against every keyframe (parity tap)
+  bool sc_distances(int query_id, std::vector<float> &dists, std::vector<int32_t> &shifts) {
+    lslam_kfs_stats st;
+    if (!info(st)) return false;
+    dists.assign((size_t)st.n_keyframes, 0.0f);
+    shifts.assign((size_t)st.n_keyframes, 0);
+    if (lslam_sc_distances(_h, query_id, dists.data(), shifts.data()) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
   const std::string &lastError() const { return _err; }
 
 private:
@@ -216,6 +267,98 @@ public:
       }
     }
     return loop_found;
+  }
+
+  // ---- not in the reference: candidates by appearance (lslam_sc_*) ----
+  // The scan-context candidate list of one new keyframe, in its store's ids, best first: empty when the interval rule skips the
+  // keyframe or no keyframe is accum_distance_thresh of travel behind it.  No gate on the estimated distance: that is the point.
+  // false: a backend error (lastError()).
+  bool appearance_candidates(const std::vector<KeyFrame::Ptr> &keyframes, const KeyFrame::Ptr &nk, std::vector<int32_t> &ids,
+                             std::vector<int32_t> &shifts, std::vector<float> &dists) {
+    ids.clear();
+    shifts.clear();
+    dists.clear();
+    if (!nk->store) { _err = "detect_appearance: the new keyframe is not in a KeyframeStore"; return false; }
+    if (nk->accum_distance - last_loop_accum_distance < last_loop_interval_thresh) return true;
+    int32_t max_cand = -1;  // accumulated distance is monotone in the id: the eligible candidates are the ids up to one limit
+    for (const auto &k : keyframes)
+      if (k->store == nk->store && k->store_id < nk->store_id && k->store_id > max_cand &&
+          nk->accum_distance - k->accum_distance >= accum_distance_thresh)
+        max_cand = k->store_id;
+    if (max_cand < 0) return true;
+    lslam_sc_stats st;
+    if (lslam_sc_info(nk->store, &st) < 0 || (!st.is_set && lslam_sc_setup(nk->store, nullptr) < 0)) {
+      _err = lslam_last_error();
+      return false;
+    }
+    const int32_t q = nk->store_id;
+    int32_t n = 0;
+    ids.assign((size_t)sc_top_k, -1);
+    shifts.assign((size_t)sc_top_k, 0);
+    dists.assign((size_t)sc_top_k, 1.0f);
+    if (lslam_sc_query(nk->store, 1, &q, &max_cand, sc_top_k, ids.data(), shifts.data(), dists.data(), &n) < 0) {
+      _err = lslam_last_error();
+      ids.clear(); shifts.clear(); dists.clear();
+      return false;
+    }
+    ids.resize((size_t)n);
+    shifts.resize((size_t)n);
+    dists.resize((size_t)n);
+    return true;
+  }
+
+  // Loops found from what the new keyframes look like: per new keyframe the sc_top_k nearest scan-context descriptors among the
+  // keyframes at least accum_distance_thresh of travel back; those below sc_distance_thresh are verified in list order by
+  // lslam_kfs_loop_match (one candidate, started from the rotation the descriptor shift stands for); the first accepted one is
+  // the Loop.  All keyframes involved are in one KeyframeStore on this detector's ctx.
+  bool detect_appearance(const std::vector<KeyFrame::Ptr> &keyframes, const std::deque<KeyFrame::Ptr> &new_keyframes,
+                         std::vector<Loop::Ptr> &detected_loops) {
+    bool loop_found = false;
+    for (const auto &nk : new_keyframes) {
+      std::vector<int32_t> ids, shifts;
+      std::vector<float> dists;
+      if (!appearance_candidates(keyframes, nk, ids, shifts, dists) || ids.empty()) continue;
+      lslam_sc_stats sc;
+      if (lslam_sc_info(nk->store, &sc) < 0) { _err = lslam_last_error(); continue; }
+      for (size_t i = 0; i < ids.size(); ++i) {
+        if (!(dists[i] < (float)sc_distance_thresh)) break;  // the list is sorted
+        KeyFrame::Ptr cand;
+        for (const auto &k : keyframes)
+          if (k->store == nk->store && k->store_id == ids[i]) { cand = k; break; }
+        if (!cand) continue;
+        float guess[16];
+        sc_shift_guess(shifts[i], sc.params.n_sector, sc.params.up_axis, guess);
+        float rel[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        int32_t stage = 0, its = 0;
+        double fit = 0;
+        lslam_stats st;
+        if (lslam_kfs_loop_match(nk->store, 1, &ids[i], rel, nk->store_id, guess, 10, &_opts, &stage, &fit, &its, &st) < 0) {
+          _err = lslam_last_error();
+          continue;
+        }
+        if (stage != LSLAM_KFS_LOOP_ACCEPTED) continue;
+        last_loop_accum_distance = nk->accum_distance;
+        Loop::Ptr lp = std::make_shared<Loop>();
+        lp->key1 = cand;
+        lp->key2 = nk;
+        lp->relative_pose = from_float16(guess);
+        detected_loops.push_back(lp);
+        loop_count++;
+        loop_found = true;
+        break;
+      }
+    }
+    return loop_found;
+  }
+
+  // The pose of the query in the candidate's frame that a scan-context shift stands for: the rotation by shift * 2 pi / n_sector
+  // about the up axis, zero translation (lslam_c.h, SHIFT) -- lslam_kfs_loop_match's guess.
+  static void sc_shift_guess(int32_t shift, int32_t n_sector, int32_t up_axis, float T[16]) {
+    const double psi = (double)shift * (6.283185307179586 / (double)n_sector);
+    const float c = (float)std::cos(psi), s = (float)std::sin(psi);
+    for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    if (up_axis == 1) { T[0] = c; T[2] = s; T[8] = -s; T[10] = c; }   // about +y: z -> x
+    else { T[0] = c; T[1] = -s; T[4] = s; T[5] = c; }                 // about +z: x -> y
   }
 
   // :93-106
@@ -306,6 +449,9 @@ public:
 
   double estimated_distance_thresh = 25.0, accum_distance_thresh = 30.0, last_loop_interval_thresh = 3.0,
          fitness_score_thresh = 0.5;
+  // detect_appearance.  0.2 is the upper end of the range the descriptor's authors use; not tuned on this project's data
+  double sc_distance_thresh = 0.2;
+  int sc_top_k = 4;
 
 private:
   // the same for keyframes whose clouds are in a KeyframeStore: one call, no cloud crosses PCIe (lslam_kfs_loop_match)
@@ -357,12 +503,17 @@ class Graph {
 public:
   // resident: the keyframes' clouds live in a KeyframeStore on `ctx` (add_frame uploads them once); keep_host_clouds = false
   // then leaves KeyFrame::cornerCloud / surfCloud empty (KeyframeStore::get fetches a cloud when one is wanted)
+  // appearance_loops (not in the reference; implies resident): optimize also runs LoopDetector::detect_appearance -- scan-context
+  // candidates over the store, sc_params being lslam_sc_setup's (nullptr: the defaults) -- for the new keyframes for which
+  // detect_nearest found no loop
   explicit Graph(lslam_ctx *ctx, int device = 0, int max_keyframes_per_update = 10, bool resident = false,
-                 bool keep_host_clouds = true)
-      : loop_detector(ctx), _ctx(ctx), _device(device), _max_per_update(max_keyframes_per_update), _keep_host(keep_host_clouds) {
-    if (resident) {
+                 bool keep_host_clouds = true, bool appearance_loops = false, const lslam_sc_params *sc_params = nullptr)
+      : loop_detector(ctx), _ctx(ctx), _device(device), _max_per_update(max_keyframes_per_update), _keep_host(keep_host_clouds),
+        _appearance(appearance_loops) {
+    if (resident || appearance_loops) {
       store.reset(new KeyframeStore(ctx));
       if (!store->ok()) _err = store->lastError();
+      else if (appearance_loops && !store->sc_setup(sc_params)) _err = store->lastError();
     }
   }
 
@@ -397,6 +548,15 @@ public:
     std::vector<Loop::Ptr> found;
     std::deque<KeyFrame::Ptr> nk(new_keyframes.begin(), new_keyframes.end());
     loop_detector.detect_nearest(keyframes, nk, found);
+    if (_appearance) {
+      std::deque<KeyFrame::Ptr> open;
+      for (const auto &k : nk) {
+        bool closed = false;
+        for (const auto &lp : found) closed = closed || lp->key2 == k;
+        if (!closed) open.push_back(k);
+      }
+      loop_detector.detect_appearance(keyframes, open, found);
+    }
     static const double LOOP_INFO[6] = {2, 2, 2, 2, 2, 2};  // graph.cpp:333-339
     for (const auto &lp : found) add_edge(lp->key1->node, lp->key2->node, lp->relative_pose, LOOP_INFO);
     loops.insert(loops.end(), found.begin(), found.end());
@@ -608,7 +768,7 @@ private:
   }
   lslam_ctx *_ctx;
   int _device, _max_per_update;
-  bool _keep_host;
+  bool _keep_host, _appearance;
   std::vector<double> _poses, _meas, _info;
   std::vector<int32_t> _ij;
   std::string _err;

@@ -234,6 +234,18 @@ class LslamKfsStats(C.Structure):
                 ("cloud_bytes_uploaded", C.c_uint64), ("cloud_bytes_downloaded", C.c_uint64)]
 
 
+class LslamScParams(C.Structure):
+    """lslam_sc_params (include/lslam_c.h)."""
+    _fields_ = [("n_ring", C.c_int32), ("n_sector", C.c_int32), ("max_range", C.c_float), ("height_offset", C.c_float),
+                ("up_axis", C.c_int32)]
+
+
+class LslamScStats(C.Structure):
+    """lslam_sc_stats (include/lslam_c.h)."""
+    _fields_ = [("params", LslamScParams), ("is_set", C.c_int32), ("n_described", C.c_int64), ("descriptor_bytes", C.c_uint64),
+                ("describe_launches", C.c_int64), ("query_launches", C.c_int64)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLGATHERV_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32)
 c_double_p = C.POINTER(C.c_double)
@@ -365,6 +377,13 @@ SYMBOLS = {
     "lslam_kfs_scanmatch": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, c_float_p, C.POINTER(LslamOpts),
                                       C.POINTER(LslamStats)]),
     "lslam_kfs_add_to_fmap": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, c_float_p]),
+    "lslam_sc_default_params": (None, [C.POINTER(LslamScParams)]),
+    "lslam_sc_setup": (C.c_int, [C.c_void_p, C.POINTER(LslamScParams)]),
+    "lslam_sc_descriptor": (C.c_int, [C.c_void_p, C.c_int32, c_float_p]),
+    "lslam_sc_query": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, C.c_int32, c_int32_p, c_int32_p, c_float_p,
+                                     c_int32_p]),
+    "lslam_sc_distances": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, c_int32_p]),
+    "lslam_sc_info": (C.c_int, [C.c_void_p, C.POINTER(LslamScStats)]),
     "lslam_voxel_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, c_float_p,
                                    C.c_size_t, C.POINTER(C.c_size_t)]),
     "lslam_voxel_grid2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, c_float_p,
@@ -508,6 +527,7 @@ SYMBOLS = {
 }
 
 COMM_ID_BYTES = 128
+SC_POINT_CHUNK, SC_CAND_TILE, SC_MAX_TOP_K = 256, 64, 32  # LSLAM_SC_* of include/lslam_c.h: the scan-context kernels' shape
 SEARCH_AUTO, SEARCH_LANE, SEARCH_PACKET, SEARCH_GRID = 0, 1, 2, 3
 AB_PERSISTENT_GN, AB_FUSED_SOLVE, AB_SECOND_PROBE, AB_WIDE_IN_PLACE = 1, 2, 4, 8  # lslam_opts.ab_switches (LSLAM_AB_*)
 AB_REFILL = 128

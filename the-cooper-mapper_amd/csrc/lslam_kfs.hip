@@ -22,19 +22,9 @@
 #include <vector>
 
 #include "lslam_internal.hpp"
+#include "lslam_kfs_impl.hpp"
 
 namespace {
-
-#define KFS_TRY(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      char _b[400];                                                                      \
-      snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      lslam::set_error(_b);                                                              \
-      return LSLAM_ERR_HIP;                                                              \
-    }                                                                                    \
-  } while (0)
 
 constexpr size_t KFS_DEFAULT_SLAB = (size_t)1 << 20;     // 16 MiB: ~300 VLP-16 keyframes' surface clouds
 constexpr size_t KFS_DEFAULT_POINTS = (size_t)1 << 26;   // per type: 1 GiB, taken slab by slab as the store grows
@@ -72,61 +62,10 @@ __global__ __launch_bounds__(256) void kfs_index_kernel(const float4 *in, int n,
   out[i] = p;
 }
 
-struct Slab {
-  lslam::DevBuf<float4> buf;
-  size_t used = 0;
-};
-struct KeyframeClouds {
-  float4 *p[2];
-  size_t n[2];
-  float lo[2][3], hi[2][3];  // getMinMax3D of each cloud (not read for an empty one)
-};
-
-}  // namespace
-
-struct lslam_kfs {
-  lslam_ctx *ctx = nullptr;
-  hipStream_t stream = nullptr;
-  size_t max_points = 0, slab_points = 0;
-  int32_t max_keyframes = 0;
-  std::vector<std::unique_ptr<Slab>> slabs;
-  std::vector<KeyframeClouds> kfs;
-  size_t total[2] = {0, 0};
-  size_t held_points = 0;
-  uint64_t bytes_up = 0, bytes_down = 0;
-  lslam::PinBuf<float4> h_stage;
-  lslam::DevBuf<uint32_t> d_box;  // [12] grid_bbox2's scratch
-  // loop match: the assembled clouds, their {x, y, z, index} forms, the four filtered clouds
-  lslam::DevBuf<float4> local[2], indexed[2], filt[4];
-  size_t n_local[2] = {0, 0};
-};
-
-namespace {
-
-int check_kfs(lslam_kfs *k, const char *what) {
-  if (!k) {
-    char b[160];
-    snprintf(b, sizeof(b), "%s: null keyframe store", what);
-    lslam::set_error(b);
-    return LSLAM_ERR_INVALID;
-  }
-  if (!lslam::ctx_alive(k->ctx)) {
-    lslam::set_error("keyframe store: its ctx was destroyed");
-    return LSLAM_ERR_INVALID;
-  }
-  KFS_TRY(hipSetDevice(lslam::ctx_device(k->ctx)));
-  return LSLAM_OK;
-}
-
-int check_id(const lslam_kfs *k, const char *what, int32_t id) {
-  if (id < 0 || (size_t)id >= k->kfs.size()) {
-    char b[200];
-    snprintf(b, sizeof(b), "%s: keyframe id %d out of range (the store holds %zu)", what, id, k->kfs.size());
-    lslam::set_error(b);
-    return LSLAM_ERR_INVALID;
-  }
-  return LSLAM_OK;
-}
+using lslam::check_kfs;
+using lslam::check_id;
+using lslam::Slab;
+using lslam::KeyframeClouds;
 
 // Room for two clouds.  Nothing is committed: the caller commits (slab `used` counters) once the points are there; slabs
 // opened here are dropped again by rollback().
@@ -347,6 +286,7 @@ int lslam_kfs_clear(lslam_kfs *k) {
   k->total[0] = k->total[1] = 0;
   k->held_points = 0;
   k->n_local[0] = k->n_local[1] = 0;
+  k->sc.drop();  // the descriptors go with the keyframes; the scan-context parameters stay
   return LSLAM_OK;
 }
 

@@ -1,0 +1,126 @@
+// lslam_kfs_impl.hpp -- the keyframe store's state, shared by the files that implement lslam_kfs_* entry points: lslam_kfs.hip
+// (the clouds and the pose-graph steps that read them) and lslam_sc.hip (the scan-context descriptors over them).  Host side only.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <memory>
+#include <vector>
+
+#include "lslam_internal.hpp"
+
+#define KFS_TRY(expr)                                                                    \
+  do {                                                                                   \
+    hipError_t _e = (expr);                                                              \
+    if (_e != hipSuccess) {                                                              \
+      char _b[400];                                                                      \
+      snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+      lslam::set_error(_b);                                                              \
+      return LSLAM_ERR_HIP;                                                              \
+    }                                                                                    \
+  } while (0)
+
+namespace lslam {
+
+struct Slab {
+  DevBuf<float4> buf;
+  size_t used = 0;
+};
+struct KeyframeClouds {
+  float4 *p[2];
+  size_t n[2];
+  float lo[2][3], hi[2][3];  // getMinMax3D of each cloud (not read for an empty one)
+};
+
+// What the describe kernel reads per keyframe (uploaded for the keyframes that have no descriptor yet)
+struct ScJob {
+  const float4 *p[2];
+  uint32_t n[2];
+};
+
+// Scan-context state of a store (lslam_sc_*, lslam_sc.hip).  Empty -- no allocation -- until lslam_sc_setup.
+// Keyframe i's record lives in slab i / SC_SLAB_KEYFRAMES at (i % SC_SLAB_KEYFRAMES) * stride floats: the raw maxima D[ring][sector],
+// then the query form -- the columns divided by their norms, [ring][sector], and one more row of 1.0 / 0.0: the column's norm is > 0.
+// A slab is never moved or freed before drop(), so records stay where the describe kernel wrote them.
+struct ScState {
+  static constexpr size_t SC_SLAB_KEYFRAMES = 1024;
+  bool set = false;
+  lslam_sc_params params{};
+  float ring_scale = 0.0f;      // (float)n_ring / max_range
+  double sector_scale = 0.0;    // n_sector / (2 pi)
+  size_t stride = 0;            // floats per keyframe record: (2 * n_ring + 1) * n_sector
+  size_t described = 0;         // keyframes 0 .. described-1 have their record
+  std::vector<std::unique_ptr<DevBuf<float>>> slabs;
+  DevBuf<float *> d_slabs;      // the slabs' base pointers, for the kernels
+  size_t slabs_uploaded = 0;
+  PinBuf<ScJob> h_jobs;
+  DevBuf<ScJob> d_jobs;
+  // a query call's scratch: ids and limits up, tile lists, the merged lists down
+  PinBuf<int32_t> h_io;
+  DevBuf<int32_t> d_in, d_out, d_tile_shift;
+  DevBuf<uint64_t> d_tile_key;
+  DevBuf<float> d_tap;
+  int64_t describe_launches = 0, query_launches = 0;
+
+  size_t bytes_held() const {
+    size_t b = 0;
+    for (const auto &s : slabs) b += s->cap * sizeof(float);
+    return b;
+  }
+  // the descriptors go (their slabs are freed); parameters, scratch and counters stay.  The caller has waited for the stream.
+  void drop() {
+    slabs.clear();
+    slabs_uploaded = 0;
+    described = 0;
+  }
+};
+
+}  // namespace lslam
+
+struct lslam_kfs {
+  lslam_ctx *ctx = nullptr;
+  hipStream_t stream = nullptr;
+  size_t max_points = 0, slab_points = 0;
+  int32_t max_keyframes = 0;
+  std::vector<std::unique_ptr<lslam::Slab>> slabs;
+  std::vector<lslam::KeyframeClouds> kfs;
+  size_t total[2] = {0, 0};
+  size_t held_points = 0;
+  uint64_t bytes_up = 0, bytes_down = 0;
+  lslam::PinBuf<float4> h_stage;
+  lslam::DevBuf<uint32_t> d_box;  // [12] grid_bbox2's scratch
+  // loop match: the assembled clouds, their {x, y, z, index} forms, the four filtered clouds
+  lslam::DevBuf<float4> local[2], indexed[2], filt[4];
+  size_t n_local[2] = {0, 0};
+  lslam::ScState sc;
+};
+
+namespace lslam {
+
+inline int check_kfs(lslam_kfs *k, const char *what) {
+  if (!k) {
+    char b[160];
+    snprintf(b, sizeof(b), "%s: null keyframe store", what);
+    set_error(b);
+    return LSLAM_ERR_INVALID;
+  }
+  if (!ctx_alive(k->ctx)) {
+    set_error("keyframe store: its ctx was destroyed");
+    return LSLAM_ERR_INVALID;
+  }
+  KFS_TRY(hipSetDevice(ctx_device(k->ctx)));
+  return LSLAM_OK;
+}
+
+inline int check_id(const lslam_kfs *k, const char *what, int32_t id) {
+  if (id < 0 || (size_t)id >= k->kfs.size()) {
+    char b[200];
+    snprintf(b, sizeof(b), "%s: keyframe id %d out of range (the store holds %zu)", what, id, k->kfs.size());
+    set_error(b);
+    return LSLAM_ERR_INVALID;
+  }
+  return LSLAM_OK;
+}
+
+}  // namespace lslam

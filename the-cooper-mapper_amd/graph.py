@@ -60,18 +60,25 @@ LOOP_INFORMATION = 2.0 * np.eye(6)
 
 class Graph:
     def __init__(self, device=0, ctx=None, loop_detector=None, max_keyframes_per_update=10, resident=False,
-                 keep_host_clouds=True, store_max_points=0, store_max_keyframes=0, store_slab_points=0):
+                 keep_host_clouds=True, store_max_points=0, store_max_keyframes=0, store_slab_points=0, appearance_loops=False,
+                 sc_params=None):
         """``resident=True``: the keyframes' clouds live in a :class:`KeyframeStore` on the loop detector's context --
         ``add_frame`` uploads them once (``kf.store_id``), loop closure and ``get_final_feature_map`` read them there;
         ``keep_host_clouds=False`` then drops the host copies (``kf.corner_cloud`` / ``kf.surf_cloud`` fetch on demand).
-        The ``store_*`` limits are :class:`KeyframeStore`'s (0: its defaults).  Without ``resident`` nothing changes."""
+        The ``store_*`` limits are :class:`KeyframeStore`'s (0: its defaults).  Without ``resident`` nothing changes.
+        ``appearance_loops=True`` (not in the reference; implies ``resident``): ``optimize`` also runs
+        ``LoopDetector.detect_appearance`` -- scan-context candidates over the store, ``sc_params`` being
+        ``KeyframeStore.sc_setup``'s keywords -- for the new keyframes for which ``detect_nearest`` found no loop."""
         self.solver = PoseGraph(device)
         self.loop_detector = loop_detector or LoopDetector(device=device, ctx=ctx)
         self.store = None
         self.keep_host_clouds = bool(keep_host_clouds)
-        if resident:
+        self.appearance_loops = bool(appearance_loops)
+        if resident or self.appearance_loops:
             from .keyframe_store import KeyframeStore
             self.store = KeyframeStore(self.loop_detector.scan_match.ctx, store_max_points, store_max_keyframes, store_slab_points)
+            if self.appearance_loops:
+                self.store.sc_setup(**(sc_params or {}))
         self.keyframe_updater = KeyframeUpdater()
         self.keyframes = []
         self.new_keyframes = []
@@ -119,6 +126,10 @@ class Graph:
         if not self.flush_keyframe_queue():
             return [], 0
         loops = self.loop_detector.detect_nearest(self.keyframes, self.new_keyframes)
+        if self.appearance_loops:
+            closed = set(id(lp.key2) for lp in loops)
+            loops = loops + self.loop_detector.detect_appearance(self.keyframes,
+                                                                 [k for k in self.new_keyframes if id(k) not in closed])
         for lp in loops:
             self.solver.add_se3_edge(lp.key1.node, lp.key2.node, lp.relative_pose.astype(np.float64), LOOP_INFORMATION)
         self.loops.extend(loops)

@@ -11,12 +11,26 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import LslamError, LslamKfsStats, LslamStats, c_int32_p
+from .capi import LslamError, LslamKfsStats, LslamScParams, LslamScStats, LslamStats, c_int32_p
 from .feature_map import _fp, _xyzi
 
 # lslam_kfs_loop_match's *stage (include/lslam_c.h LSLAM_KFS_*)
 EMPTY_REFERENCE, ICP_REJECTED, MATCH_FAILED, LOOP_ACCEPTED = 0, 1, 2, 3
 MAX_CANDIDATES = 6  # loop_detector.hpp:141
+SC_PARAM_FIELDS = ("n_ring", "n_sector", "max_range", "height_offset", "up_axis")
+
+
+def sc_shift_guess(shift, n_sector, up_axis):
+    """The pose of the query in the candidate's frame that a scan-context shift stands for (include/lslam_c.h, SHIFT): the
+    rotation by ``shift * 2 pi / n_sector`` about the up axis, zero translation -> 4x4 float32, ``loop_match``'s ``guess``."""
+    psi = float(shift) * (2.0 * np.pi / float(n_sector))
+    c, s = np.cos(psi), np.sin(psi)
+    T = np.eye(4)
+    if int(up_axis) == 1:  # about +y: z -> x
+        T[0, 0], T[0, 2], T[2, 0], T[2, 2] = c, s, -s, c
+    else:  # about +z: x -> y
+        T[0, 0], T[0, 1], T[1, 0], T[1, 1] = c, -s, s, c
+    return T.astype(np.float32)
 
 
 class KeyframeStore:
@@ -140,3 +154,53 @@ class KeyframeStore:
         """``FeatureMap.add_feature_cloud`` with the keyframe's clouds taken from the store."""
         T = np.ascontiguousarray(tf, dtype=np.float32).reshape(16)
         self._check(self.lib.lslam_kfs_add_to_fmap(self.h, int(kid), fmap.h, _fp(T)))
+
+    # ---- loop candidates by appearance: scan context (lslam_sc_*) ---------------------------------------------------------
+    def sc_setup(self, **params):
+        """Install the scan-context parameters (``n_ring``, ``n_sector``, ``max_range``, ``height_offset``, ``up_axis``;
+        what is not named keeps its default).  Other parameters than those in force drop the descriptors held."""
+        p = LslamScParams()
+        self.lib.lslam_sc_default_params(C.byref(p))
+        for k, v in params.items():
+            if k not in SC_PARAM_FIELDS:
+                raise TypeError("sc_setup: unknown parameter %r" % k)
+            setattr(p, k, v)
+        self._check(self.lib.lslam_sc_setup(self.h, C.byref(p)))
+
+    def sc_info(self):
+        st = LslamScStats()
+        self._check(self.lib.lslam_sc_info(self.h, C.byref(st)))
+        out = {k: getattr(st.params, k) for k in SC_PARAM_FIELDS}
+        out.update(is_set=bool(st.is_set), n_described=st.n_described, descriptor_bytes=st.descriptor_bytes,
+                   describe_launches=st.describe_launches, query_launches=st.query_launches)
+        return out
+
+    def sc_descriptor(self, kid):
+        """Keyframe ``kid``'s descriptor (parity tap) -> (n_ring, n_sector) float32."""
+        i = self.sc_info()
+        out = np.zeros((max(i["n_ring"], 1), max(i["n_sector"], 1)), np.float32)
+        self._check(self.lib.lslam_sc_descriptor(self.h, int(kid), _fp(out)))
+        return out
+
+    def sc_query(self, query_ids, max_cand_id=None, top_k=4):
+        """Each query keyframe against the keyframes ``0 .. max_cand_id[q]`` (None: ``query_ids[q] - 1``) -> one
+        ``(ids, shifts, dists)`` triple of arrays per query, best first (distance, then id), at most ``top_k`` long."""
+        q = np.ascontiguousarray(query_ids, np.int32).reshape(-1)
+        lim = None if max_cand_id is None else np.ascontiguousarray(max_cand_id, np.int32).reshape(-1)
+        if lim is not None and len(lim) != len(q):
+            raise ValueError("sc_query: one max_cand_id per query")
+        k = max(int(top_k), 1)
+        ids, sh = np.full((len(q), k), -1, np.int32), np.zeros((len(q), k), np.int32)
+        d, n = np.ones((len(q), k), np.float32), np.zeros(len(q), np.int32)
+        self._check(self.lib.lslam_sc_query(self.h, len(q), q.ctypes.data_as(c_int32_p),
+                                                lim.ctypes.data_as(c_int32_p) if lim is not None else None, int(top_k),
+                                                ids.ctypes.data_as(c_int32_p), sh.ctypes.data_as(c_int32_p), _fp(d),
+                                                n.ctypes.data_as(c_int32_p)))
+        return [(ids[i, :n[i]].copy(), sh[i, :n[i]].copy(), d[i, :n[i]].copy()) for i in range(len(q))]
+
+    def sc_distances(self, query_id):
+        """The query kernel's distance and shift of ``query_id`` against every keyframe (parity tap) -> (dist, shift)."""
+        n = len(self)
+        d, sh = np.zeros(n, np.float32), np.zeros(n, np.int32)
+        self._check(self.lib.lslam_sc_distances(self.h, int(query_id), _fp(d), sh.ctypes.data_as(c_int32_p)))
+        return d, sh

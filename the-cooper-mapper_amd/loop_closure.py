@@ -94,6 +94,10 @@ class LoopDetector:
         self.accum_distance_thresh = 30.0
         self.last_loop_interval_thresh = 3.0
         self.fitness_score_thresh = 0.5
+        # detect_appearance (not in the reference).  0.2 is the upper end of the range the descriptor's authors use; it was not
+        # tuned on this project's data
+        self.sc_distance_thresh = 0.2
+        self.sc_top_k = 4
         self.loop_count = 0
         self.last_loop_accum_distance = 0.0
         self._trajectory = np.zeros((0, 4), np.float32)
@@ -132,6 +136,69 @@ class LoopDetector:
                 if loop is not None:
                     loops.append(loop)
                     self.loop_count += 1
+        return loops
+
+    # ---- not in the reference: candidates by appearance (lslam_sc_*) --------------------------------
+    def appearance_candidates(self, keyframes, new_keyframe):
+        """The scan-context candidate list of one new keyframe -> (ids, shifts, dists) in the store's ids, best first; empty
+        when the interval rule skips the keyframe or no keyframe is ``accum_distance_thresh`` of travel behind it.  No gate
+        on the estimated distance: that is the point."""
+        none = (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32))
+        store = new_keyframe.store
+        if store is None:
+            raise ValueError("detect_appearance: the new keyframe is not in a KeyframeStore")
+        if new_keyframe.accum_distance - self.last_loop_accum_distance < self.last_loop_interval_thresh:
+            return none
+        # accumulated distance is monotone in the id: the eligible candidates are the ids up to one limit
+        max_cand = -1
+        for k in keyframes:
+            if k.store is store and k.store_id < new_keyframe.store_id and k.store_id > max_cand and \
+                    new_keyframe.accum_distance - k.accum_distance >= self.accum_distance_thresh:
+                max_cand = k.store_id
+        if max_cand < 0:
+            return none
+        if not store.sc_info()["is_set"]:
+            store.sc_setup()
+        return store.sc_query([new_keyframe.store_id], [max_cand], self.sc_top_k)[0]
+
+    def detect_appearance(self, keyframes, new_keyframes):
+        """Loops found from what the new keyframes look like, not from where their estimates put them: per new keyframe the
+        ``sc_top_k`` nearest scan-context descriptors among the keyframes at least ``accum_distance_thresh`` of travel back;
+        those below ``sc_distance_thresh`` are verified in list order by ``lslam_kfs_loop_match`` (one candidate, started from
+        the rotation the descriptor shift stands for); the first accepted one is the Loop.  All keyframes involved must be in
+        one :class:`KeyframeStore` on this detector's context.  -> list of Loop."""
+        from .capi import Status
+        from .keyframe_store import LOOP_ACCEPTED, MATCH_FAILED, sc_shift_guess
+        by_id = {}
+        for k in keyframes:
+            if k.store is not None:
+                by_id[(id(k.store), k.store_id)] = k
+        loops = []
+        for nk in new_keyframes:
+            ids, shifts, dists = self.appearance_candidates(keyframes, nk)
+            if not len(ids):
+                continue
+            store, sm = nk.store, self.scan_match
+            if store.ctx is not sm.ctx:
+                raise ValueError("detect_appearance: the keyframe store is not on the detector's context")
+            info = store.sc_info()
+            for cid, shift, dist in zip(ids, shifts, dists):
+                if not dist < self.sc_distance_thresh:
+                    break  # the list is sorted
+                cand = by_id.get((id(store), int(cid)))
+                if cand is None:
+                    continue
+                guess = sc_shift_guess(shift, info["n_sector"], info["up_axis"])
+                r = store.loop_match([int(cid)], np.eye(4, dtype=np.float32)[None], nk.store_id, guess, sm.opts)
+                if r["stage"] >= MATCH_FAILED:
+                    sm._resident, sm._resident_map = None, 0
+                    sm._finish(Status(r["stats"].status), r["stats"])
+                if r["stage"] != LOOP_ACCEPTED:
+                    continue
+                self.last_loop_accum_distance = nk.accum_distance
+                loops.append(Loop(cand, nk, r["guess"]))
+                self.loop_count += 1
+                break
         return loops
 
     # ---- :93-106 ----------------------------------------------------------------------------------
