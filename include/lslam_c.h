@@ -211,6 +211,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed; new entry points and a struct of their own (lslam_oreg_*: the registration node for organised clouds). */
 /* still 7: no struct changed; new entry points and a struct of their own (lslam_kfs_*: the keyframe store). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_sc_*: loop candidates by appearance). */
+/* still 7: no struct changed; new entry points and an enum (lslam_pg_set_robust_kernels, _edge_robust, _robust_info, _kernel_from_name: robust kernels on pose-graph edges; lslam_pg_stream). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -1183,6 +1184,38 @@ int lslam_g2o_read(const char *path, int32_t *n_vertices, double *poses7, int32_
 int lslam_pg_linearize(lslam_pg *pg, double *diag_out, double *off_out, int32_t *off_ij_out,
                        double *b_out, double *chi2_out);
 int lslam_pg_solve(lslam_pg *pg, double lambda, double *dx_out, int32_t *cg_iters);
+
+/* ---- robust kernels on pose-graph edges ------------------------------------------------------------------------------
+ * The reference only shows the intent (pose_graph/solver_g2o.h:25-26 includes g2o's robust-kernel headers, solver_g2o.cpp:27-28
+ * fills and prints the kernel factory, information_estimator.hpp has a weight() nobody calls): no edge there carries a kernel,
+ * and g2o itself is not pinned by it, so PARITY IS UNPINNED like the rest of this solver.  The semantics are g2o's published
+ * ones (BaseBinaryEdge::constructQuadraticForm, robust_kernel_impl.cpp).  With e2 = e^T Omega e and the kernel parameter delta,
+ * rho = (rho0, rho1):
+ *   NONE    (e2, 1)
+ *   HUBER   e2 <= delta^2: (e2, 1), else (2 delta sqrt(e2) - delta^2, delta / sqrt(e2))
+ *   CAUCHY  a = e2 / delta^2 + 1: (delta^2 ln a, 1 / a)
+ *   DCS     s = 2 delta / (delta + e2): s >= 1: (e2, 1), else (s^2 e2, s^2)   -- rho1 is g2o's, not d rho0 / d e2
+ * The edge adds rho1 J^T Omega J to H, -rho1 J^T Omega e to b and rho0 to chi2 (the second-order rho2 term is dropped, as g2o
+ * drops it).  lslam_pg_optimize then runs its unchanged schedule on the sum of rho0 (g2o's activeRobustChi2): chi2_initial,
+ * chi2_final and every accept / reject decision; lslam_pg_linearize returns the weighted system and that sum.  A sharded run
+ * needs nothing more: each rank weights its own edges (every rank sets the same arrays, indexed by global edge id).
+ * Huber is convex: it bounds an outlier's pull but cannot reject it.  Cauchy and DCS can (DESIGN, pose-graph section).
+ * While no edge carries a kernel -- the default -- the solver launches exactly the kernels it launched before these entry points
+ * existed.  The .g2o text format has no place for a kernel: lslam_pg_save_g2o writes none, a graph read back has plain edges. */
+enum { LSLAM_PG_KERNEL_NONE = 0, LSLAM_PG_KERNEL_HUBER = 1, LSLAM_PG_KERNEL_CAUCHY = 2, LSLAM_PG_KERNEL_DCS = 3 };
+/* "NONE" / "Huber" / "Cauchy" / "DCS" (the names the C++ mirrors take) -> LSLAM_PG_KERNEL_*; anything else -1. */
+int lslam_pg_kernel_from_name(const char *name);
+/* kind[n_edges], delta[n_edges] (delta ignored where kind is NONE); (NULL, NULL) clears: the plain solver again.  A delta that
+ * is not finite and > 0, an unknown kind, or one array without the other: LSLAM_ERR_INVALID, lslam_pg_last_error says which,
+ * and nothing has changed. */
+int lslam_pg_set_robust_kernels(lslam_pg *pg, const int32_t *kind, const double *delta);
+/* per edge at poses7 (NULL: the current estimate); any output may be NULL: e2[n_edges], rho[n_edges] = rho0, weight[n_edges] = rho1 */
+int lslam_pg_edge_robust(lslam_pg *pg, const double *poses7, double *e2, double *rho, double *weight);
+/* edges carrying a kernel; of those, edges with weight < 1 at the current estimate; the plain sum of e2 */
+int lslam_pg_robust_info(lslam_pg *pg, int32_t *n_robust, int32_t *n_downweighted, double *chi2_plain);
+/* Device handle tap, as lslam_stream: the stream every kernel of this graph runs on (hipStream_t), for harnesses that time a
+ * linearisation with events (tools/bench_robust_linearize.py). */
+void *lslam_pg_stream(lslam_pg *pg);
 
 /* Device handle taps for harnesses that time on the library's stream. */
 void *lslam_stream(lslam_ctx *ctx); /* hipStream_t */

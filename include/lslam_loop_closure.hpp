@@ -32,6 +32,7 @@
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -544,11 +545,21 @@ public:
   // among the new keyframes, add loop edges, optimise if a loop was found, update odom -> graph.
   // Returns the number of loops found (-1 on a backend error).
   int optimize(int max_iterations = 1000) {
+    const int loop_kind = lslam_pg_kernel_from_name(loop_robust_kernel.c_str());
+    if (loop_kind < 0) {  // both checked before anything is added: a refused kernel must not leave edges behind
+      _err = "Graph: unknown loop_robust_kernel " + loop_robust_kernel + " (NONE, Huber, Cauchy, DCS)";
+      return -1;
+    }
+    if (loop_kind != LSLAM_PG_KERNEL_NONE && !(std::isfinite(loop_robust_kernel_size) && loop_robust_kernel_size > 0.0)) {
+      _err = "Graph: loop_robust_kernel_size must be finite and > 0";
+      return -1;
+    }
     if (!flush_keyframe_queue()) return 0;
     std::vector<Loop::Ptr> found;
     std::deque<KeyFrame::Ptr> nk(new_keyframes.begin(), new_keyframes.end());
-    loop_detector.detect_nearest(keyframes, nk, found);
-    if (_appearance) {
+    if (loop_source) loop_source(keyframes, nk, found);
+    else loop_detector.detect_nearest(keyframes, nk, found);
+    if (_appearance && !loop_source) {
       std::deque<KeyFrame::Ptr> open;
       for (const auto &k : nk) {
         bool closed = false;
@@ -558,29 +569,16 @@ public:
       loop_detector.detect_appearance(keyframes, open, found);
     }
     static const double LOOP_INFO[6] = {2, 2, 2, 2, 2, 2};  // graph.cpp:333-339
-    for (const auto &lp : found) add_edge(lp->key1->node, lp->key2->node, lp->relative_pose, LOOP_INFO);
+    for (const auto &lp : found) {
+      _loop_edges.push_back((int)(_ij.size() / 2));
+      add_edge(lp->key1->node, lp->key2->node, lp->relative_pose, LOOP_INFO, loop_kind, loop_robust_kernel_size);
+    }
     loops.insert(loops.end(), found.begin(), found.end());
     keyframes.insert(keyframes.end(), new_keyframes.begin(), new_keyframes.end());
     new_keyframes.clear();
     last_iterations = 0;
     if (!found.empty()) {
-      lslam_pg *pg = nullptr;
-      const int ne = (int)(_ij.size() / 2);
-      if (lslam_pg_create(_device, (int)(_poses.size() / 7), _poses.data(), ne, _ij.data(), _meas.data(), _info.data(), 0, &pg) !=
-          LSLAM_OK) {
-        _err = lslam_pg_last_error();
-        return -1;
-      }
-      lslam_pg_stats st;
-      const int rc = lslam_pg_optimize(pg, max_iterations, &st);
-      if (rc >= 0) lslam_pg_get_poses(pg, _poses.data());
-      lslam_pg_destroy(pg);
-      if (rc < 0) {
-        _err = lslam_pg_last_error();
-        return -1;
-      }
-      last_iterations = st.iterations;
-      for (auto &kf : keyframes) kf->estimate = pose7_to_mat(&_poses[7 * (size_t)kf->node]);
+      if (!solve_graph(max_iterations, nullptr, nullptr)) return -1;
     }
     const KeyFrame::Ptr &last = keyframes.back();
     tf_odom2graph = last->estimate * inverse(last->odom);
@@ -661,24 +659,9 @@ public:
   // translation, quaternion w, quaternion x y z of the float-cast rotation, index), then getFinalFeatureMap into directory/graph2.
   bool save(const std::string &directory, bool bootstrap = false, int max_iterations = 1000) {
     if (keyframes.empty()) { _err = "Graph::save: no keyframes"; return false; }
-    lslam_pg *pg = nullptr;
-    if (lslam_pg_create(_device, (int)(_poses.size() / 7), _poses.data(), (int)(_ij.size() / 2), _ij.data(), _meas.data(), _info.data(),
-                        0, &pg) != LSLAM_OK) {
-      _err = lslam_pg_last_error();
-      return false;
-    }
-    lslam_pg_stats st;
-    int rc = lslam_pg_save_g2o(pg, (directory + "/graph_before.g2o").c_str());
-    if (rc >= 0) rc = lslam_pg_optimize(pg, max_iterations, &st);
-    if (rc >= 0) rc = lslam_pg_save_g2o(pg, (directory + "/graph_end.g2o").c_str());
-    if (rc >= 0) rc = lslam_pg_get_poses(pg, _poses.data());
-    lslam_pg_destroy(pg);
-    if (rc < 0) {
-      _err = lslam_pg_last_error();
-      return false;
-    }
-    last_iterations = st.iterations;
-    for (auto &kf : keyframes) kf->estimate = pose7_to_mat(&_poses[7 * (size_t)kf->node]);
+    // (the .g2o files carry no kernel: the text format has no place for one)
+    const std::string before = directory + "/graph_before.g2o", end = directory + "/graph_end.g2o";
+    if (!solve_graph(max_iterations, before.c_str(), end.c_str())) return false;
     tf_odom2graph = keyframes.back()->estimate * inverse(keyframes.back()->odom);
     lslam_fmap *fm = nullptr;
     if (lslam_fmap_create(_ctx, 121, 111, 121, &fm) != LSLAM_OK) return fail_final(nullptr) >= 0;
@@ -709,6 +692,18 @@ public:
   std::vector<KeyFrame::Ptr> keyframes, new_keyframes;
   std::deque<KeyFrame::Ptr> keyframe_queue;
   std::vector<Loop::Ptr> loops;
+  // A robust kernel on every LOOP edge added from now on (not in the reference, which includes g2o's robust-kernel headers and
+  // uses none): "NONE" (default: every edge at full weight), "Huber", "Cauchy" or "DCS" with delta loop_robust_kernel_size;
+  // semantics in lslam_c.h.  Odometry edges never carry one.  Huber is convex: it bounds a false loop's pull but cannot
+  // reject it; Cauchy (0.1) and DCS (1) can.  Reporting only: nothing is removed from the graph.
+  std::string loop_robust_kernel = "NONE";
+  double loop_robust_kernel_size = 1.0;
+  // the robust weight of every entry of `loops` after the last optimisation (all 1 without a kernel)
+  const std::vector<double> &loopWeights() const { return _loop_weights; }
+  // Where the loops come from, when set: called by optimize() instead of loop_detector's detect_nearest / detect_appearance
+  // with (keyframes, new keyframes, loops out).  The counterpart of the Python Graph's loop_detector argument: a node that has
+  // its own place recognition, or a test with prepared loops, hands them over here.
+  std::function<void(const std::vector<KeyFrame::Ptr> &, const std::deque<KeyFrame::Ptr> &, std::vector<Loop::Ptr> &)> loop_source;
   Mat4d tf_odom2graph;
   int last_iterations = 0;
   const std::string &lastError() const { return _err; }
@@ -757,7 +752,47 @@ private:
     keyframe_queue.erase(keyframe_queue.begin(), keyframe_queue.begin() + n);
     return true;
   }
-  void add_edge(int a, int b, const Mat4d &rel, const double diag_info[6]) {
+  // the graph as it stands through the solver: kernels on, [save,] optimise, [save,] estimates and loop weights back --
+  // optimize() and save() share it
+  bool solve_graph(int max_iterations, const char *g2o_before, const char *g2o_end) {
+    lslam_pg *pg = nullptr;
+    if (lslam_pg_create(_device, (int)(_poses.size() / 7), _poses.data(), (int)(_ij.size() / 2), _ij.data(), _meas.data(), _info.data(),
+                        0, &pg) != LSLAM_OK) {
+      _err = lslam_pg_last_error();
+      return false;
+    }
+    lslam_pg_stats st;
+    int rc = apply_kernels(pg);
+    if (rc >= 0 && g2o_before) rc = lslam_pg_save_g2o(pg, g2o_before);
+    if (rc >= 0) rc = lslam_pg_optimize(pg, max_iterations, &st);
+    if (rc >= 0 && g2o_end) rc = lslam_pg_save_g2o(pg, g2o_end);
+    if (rc >= 0) rc = lslam_pg_get_poses(pg, _poses.data());
+    if (rc >= 0) rc = read_loop_weights(pg);
+    lslam_pg_destroy(pg);
+    if (rc < 0) {
+      _err = lslam_pg_last_error();
+      return false;
+    }
+    last_iterations = st.iterations;
+    for (auto &kf : keyframes) kf->estimate = pose7_to_mat(&_poses[7 * (size_t)kf->node]);
+    return true;
+  }
+  int apply_kernels(lslam_pg *pg) {
+    bool any = false;
+    for (size_t e = 0; e < _kind.size(); ++e) any = any || _kind[e] != LSLAM_PG_KERNEL_NONE;
+    return any ? lslam_pg_set_robust_kernels(pg, _kind.data(), _delta.data()) : LSLAM_OK;
+  }
+  int read_loop_weights(lslam_pg *pg) {
+    std::vector<double> w(_ij.size() / 2);
+    const int rc = lslam_pg_edge_robust(pg, nullptr, nullptr, nullptr, w.data());
+    if (rc < 0) return rc;
+    _loop_weights.clear();
+    for (size_t k = 0; k < _loop_edges.size(); ++k) _loop_weights.push_back(w[(size_t)_loop_edges[k]]);
+    return LSLAM_OK;
+  }
+  void add_edge(int a, int b, const Mat4d &rel, const double diag_info[6], int kind = LSLAM_PG_KERNEL_NONE, double delta = 1.0) {
+    _kind.push_back(kind);
+    _delta.push_back(delta);
     _ij.push_back(a);
     _ij.push_back(b);
     double p7[7];
@@ -771,6 +806,10 @@ private:
   bool _keep_host, _appearance;
   std::vector<double> _poses, _meas, _info;
   std::vector<int32_t> _ij;
+  std::vector<int32_t> _kind;  // per edge: LSLAM_PG_KERNEL_* and its delta
+  std::vector<double> _delta;
+  std::vector<int> _loop_edges;  // edge index of every entry of `loops`
+  std::vector<double> _loop_weights;
   std::string _err;
 };
 

@@ -58,7 +58,32 @@ public:
     for (int r = 0; r < 6; ++r)
       for (int c = 0; c < 6; ++c) _info.push_back(information_matrix(r, c));
     _edges.push_back(EdgeSE3{(int)_edges.size()});
+    _kind.push_back(LSLAM_PG_KERNEL_NONE);
+    _delta.push_back(1.0);
     return &_edges.back();
+  }
+  // A robust kernel on one edge, with the signature of the solver this one descends from (the reference itself only includes
+  // g2o's robust-kernel headers, solver_g2o.h:25-26, and prints the factory's kernels, solver_g2o.cpp:27-28).  kernel_type is
+  // "NONE", "Huber", "Cauchy" or "DCS" -- anything else throws -- and kernel_size its delta (g2o: setDelta); semantics in
+  // lslam_c.h.  Applied when the device graph is built; kept across add_se3_node / add_se3_edge.
+  void add_robust_kernel(EdgeSE3 *edge, const std::string &kernel_type, double kernel_size) {
+    if (!edge || edge->index < 0 || edge->index >= (int)_edges.size()) throw std::invalid_argument("add_robust_kernel: no such edge");
+    const int kind = lslam_pg_kernel_from_name(kernel_type.c_str());
+    if (kind < 0) throw std::invalid_argument("add_robust_kernel: unknown kernel type " + kernel_type);
+    // checked here, before anything changes: the library would refuse it only when the device graph is built
+    if (kind != LSLAM_PG_KERNEL_NONE && !(std::isfinite(kernel_size) && kernel_size > 0.0))
+      throw std::invalid_argument("add_robust_kernel: kernel_size must be finite and > 0");
+    _kind[(size_t)edge->index] = kind;
+    _delta[(size_t)edge->index] = kernel_size;
+    if (_pg) apply_kernels();
+  }
+  // the robust weight (rho1) of every edge at the current estimate, by edge index; all 1 without kernels
+  std::vector<double> edgeWeights() {
+    build();
+    std::vector<double> w(_edges.size());
+    if (lslam_pg_edge_robust(_pg, nullptr, nullptr, nullptr, w.data()) < 0)
+      throw std::runtime_error(std::string("lslam_pg_edge_robust: ") + lslam_pg_last_error());
+    return w;
   }
   // solver_g2o.cpp:79-95: graph->optimize(1000) with "lm_var"
   void optimize() {
@@ -135,6 +160,17 @@ private:
                         _info.data(), 0, &_pg) != LSLAM_OK)
       throw std::runtime_error(std::string("lslam_pg_create: ") + lslam_pg_last_error());
     if (_solve_tol > 0.0) (void)lslam_pg_set_solve_tolerance(_pg, _solve_tol);
+    apply_kernels();
+  }
+  void apply_kernels() {
+    bool any = false;
+    for (size_t e = 0; e < _kind.size(); ++e) any = any || _kind[e] != LSLAM_PG_KERNEL_NONE;
+    if (lslam_pg_set_robust_kernels(_pg, any ? _kind.data() : nullptr, any ? _delta.data() : nullptr) < 0) {
+      const std::string why = lslam_pg_last_error();
+      lslam_pg_destroy(_pg);  // never a device graph without the kernels it was asked to carry
+      _pg = nullptr;
+      throw std::runtime_error("lslam_pg_set_robust_kernels: " + why);
+    }
   }
   void pull_keep() {  // current estimates into _poses, device graph kept
     if (_pg) lslam_pg_get_poses(_pg, _poses.data());
@@ -154,6 +190,8 @@ private:
   std::deque<EdgeSE3> _edges;
   std::vector<double> _poses, _meas, _info;
   std::vector<int32_t> _ij;
+  std::vector<int32_t> _kind;  // per edge: LSLAM_PG_KERNEL_* and its delta
+  std::vector<double> _delta;
 };
 
 }  // namespace pose_graph

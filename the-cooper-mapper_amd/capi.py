@@ -506,6 +506,11 @@ SYMBOLS = {
     "lslam_pg_get_poses": (C.c_int, [C.c_void_p, c_double_p]),
     "lslam_pg_linearize": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p]),
     "lslam_pg_solve": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_int32_p]),
+    "lslam_pg_set_robust_kernels": (C.c_int, [C.c_void_p, c_int32_p, c_double_p]),
+    "lslam_pg_edge_robust": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "lslam_pg_robust_info": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_double_p]),
+    "lslam_pg_stream": (C.c_void_p, [C.c_void_p]),
+    "lslam_pg_kernel_from_name": (C.c_int, [C.c_char_p]),
     "lslam_icp_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, C.c_int32,
                                   C.c_double, C.c_double, c_double_p, c_int32_p, c_int32_p]),
     "lslam_debug_icp_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, C.c_double,

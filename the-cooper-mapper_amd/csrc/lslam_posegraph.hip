@@ -151,8 +151,50 @@ PG_DEV void edge_error(const Pose &xi, const Pose &xj, const Pose &z, double e[6
 // Per-edge record: [Hii(36) bi(6) | Hjj(36) bj(6) | Hoff(36) | chi2] = 121 doubles
 constexpr int REC = 121;
 
-__global__ void pg_edge_kernel(const double *poses, const int32_t *ij, const double *meas,
-                               const double *info, int e_begin, int e_end, int fixed, double *rec, double *chi) {
+// Robust kernels on edges, g2o's semantics (BaseBinaryEdge::constructQuadraticForm with robust_kernel_impl.cpp; g2o is not
+// pinned by the reference, see the head of this file): rho = (rho0, rho1) of e2 = e^T Omega e.  The edge adds rho1 J^T Omega J
+// to H, -rho1 J^T Omega e to b and rho0 to chi2; the second-order rho2 term is dropped, as g2o drops it.  DCS's rho1 is
+// g2o's s^2, NOT d rho0 / d e2.
+PG_DEV void robustify(int kind, double delta, double e2, double &rho0, double &rho1) {
+  rho0 = e2;
+  rho1 = 1.0;
+  if (kind == LSLAM_PG_KERNEL_HUBER) {
+    if (e2 > delta * delta) {
+      const double sq = sqrt(e2);
+      rho0 = 2.0 * delta * sq - delta * delta;
+      rho1 = delta / sq;
+    }
+  } else if (kind == LSLAM_PG_KERNEL_CAUCHY) {
+    const double d2 = delta * delta, a = e2 / d2 + 1.0;
+    rho0 = d2 * log(a);
+    rho1 = 1.0 / a;
+  } else if (kind == LSLAM_PG_KERNEL_DCS) {
+    const double s = 2.0 * delta / (delta + e2);
+    if (!(s >= 1.0)) {
+      rho0 = s * s * e2;
+      rho1 = s * s;
+    }
+  }
+}
+
+PG_DEV double edge_e2(const double *info_e, const double er[6]) {
+  double c2 = 0.0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) s += info_e[r * 6 + c] * er[c];
+    c2 += er[r] * s;
+  }
+  return c2;
+}
+
+// ROBUST = false is the plain solver: no kernel arrays are read and the record is e^T Omega e's.  ROBUST = true scales the
+// record's 120 system entries by rho1 as they are written and stores rho0 in both chi2 slots, so assembly, the all-reduce of
+// a sharded run, the PCG and the coarse level read a weighted system without knowing it.
+template <bool ROBUST>
+PG_DEV void edge_record(const double *poses, const int32_t *ij, const double *meas, const double *info, int e_begin,
+                        int e_end, int fixed, const int32_t *kind, const double *delta, double *rec, double *chi) {
   const int e = e_begin + blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= e_end) return;
   const int i = ij[2 * e], j = ij[2 * e + 1];
@@ -162,6 +204,11 @@ __global__ void pg_edge_kernel(const double *poses, const int32_t *ij, const dou
 #pragma unroll
   for (int k = 0; k < 36; ++k) Om[k] = info[(size_t)e * 36 + k];
   double *o = rec + (size_t)(e - e_begin) * REC;
+  double c2 = 0.0, w = 1.0;
+  if (ROBUST) {  // the weight is needed before the record is written; the plain instantiation computes chi2 where it always did
+    const int kd = kind[e];
+    robustify(kd, kd != LSLAM_PG_KERNEL_NONE ? delta[e] : 1.0, edge_e2(Om, er), c2, w);
+  }
   // A = J^T Omega
   double Ai[36], Aj[36];
 #pragma unroll
@@ -189,6 +236,7 @@ __global__ void pg_edge_kernel(const double *poses, const int32_t *ij, const dou
         hjj += Aj[r * 6 + k] * Jj[k * 6 + c];
         hij += Ai[r * 6 + k] * Jj[k * 6 + c];
       }
+      if (ROBUST) { hii *= w; hjj *= w; hij *= w; }
       o[r * 6 + c] = fi ? 0.0 : hii;
       o[42 + r * 6 + c] = fj ? 0.0 : hjj;
       // off-diagonal block is stored for the pair (min,max): transposed when i > j
@@ -201,19 +249,32 @@ __global__ void pg_edge_kernel(const double *poses, const int32_t *ij, const dou
       bi += Ai[r * 6 + k] * er[k];
       bj += Aj[r * 6 + k] * er[k];
     }
+    if (ROBUST) { bi *= w; bj *= w; }
     o[36 + r] = fi ? 0.0 : -bi;
     o[42 + 36 + r] = fj ? 0.0 : -bj;
   }
-  double c2 = 0.0;
+  if (!ROBUST) {
 #pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    double s = 0.0;
+    for (int r = 0; r < 6; ++r) {
+      double s = 0.0;
 #pragma unroll
-    for (int c = 0; c < 6; ++c) s += Om[r * 6 + c] * er[c];
-    c2 += er[r] * s;
+      for (int c = 0; c < 6; ++c) s += Om[r * 6 + c] * er[c];
+      c2 += er[r] * s;
+    }
   }
   o[120] = c2;
   chi[e - e_begin] = c2;  // also compact: the sum over the edges then reads consecutive doubles instead of one per record
+}
+
+__global__ void pg_edge_kernel(const double *poses, const int32_t *ij, const double *meas,
+                               const double *info, int e_begin, int e_end, int fixed, double *rec, double *chi) {
+  edge_record<false>(poses, ij, meas, info, e_begin, e_end, fixed, nullptr, nullptr, rec, chi);
+}
+// the same with per-edge kernels: kind / delta are indexed by GLOBAL edge id, like ij / meas / info
+__global__ void pg_edge_robust_kernel(const double *poses, const int32_t *ij, const double *meas, const double *info,
+                                      int e_begin, int e_end, int fixed, const int32_t *kind, const double *delta,
+                                      double *rec, double *chi) {
+  edge_record<true>(poses, ij, meas, info, e_begin, e_end, fixed, kind, delta, rec, chi);
 }
 
 // chi2 only (trial evaluation): per-edge value
@@ -234,6 +295,39 @@ __global__ void pg_chi2_kernel(const double *poses, const int32_t *ij, const dou
     c2 += er[r] * s;
   }
   out[e - e_begin] = c2;
+}
+// trial evaluation with kernels: per-edge rho0
+__global__ void pg_chi2_robust_kernel(const double *poses, const int32_t *ij, const double *meas, const double *info,
+                                      int e_begin, int e_end, const int32_t *kind, const double *delta, double *out) {
+  const int e = e_begin + blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= e_end) return;
+  const int i = ij[2 * e], j = ij[2 * e + 1];
+  const Pose xi = load_pose(poses + 7 * i), xj = load_pose(poses + 7 * j), z = load_pose(meas + 7 * e);
+  double er[6];
+  edge_error<false>(xi, xj, z, er, nullptr, nullptr);
+  const double e2 = edge_e2(info + (size_t)e * 36, er);
+  const int kd = kind[e];
+  double rho0, rho1;
+  robustify(kd, kd != LSLAM_PG_KERNEL_NONE ? delta[e] : 1.0, e2, rho0, rho1);
+  out[e - e_begin] = rho0;
+}
+// Tap: per edge of the WHOLE graph (not the shard) e2, rho0 and rho1 at `poses`; kind == nullptr: no kernels, (e2, e2, 1)
+__global__ void pg_edge_robust_tap_kernel(const double *poses, const int32_t *ij, const double *meas, const double *info,
+                                          int n_e, const int32_t *kind, const double *delta, double *e2_out,
+                                          double *rho_out, double *w_out) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_e) return;
+  const int i = ij[2 * e], j = ij[2 * e + 1];
+  const Pose xi = load_pose(poses + 7 * i), xj = load_pose(poses + 7 * j), z = load_pose(meas + 7 * e);
+  double er[6];
+  edge_error<false>(xi, xj, z, er, nullptr, nullptr);
+  const double e2 = edge_e2(info + (size_t)e * 36, er);
+  const int kd = kind ? kind[e] : LSLAM_PG_KERNEL_NONE;
+  double rho0, rho1;
+  robustify(kd, kd != LSLAM_PG_KERNEL_NONE ? delta[e] : 1.0, e2, rho0, rho1);
+  e2_out[e] = e2;
+  rho_out[e] = rho0;
+  w_out[e] = rho1;
 }
 
 // fixed-order sum of n doubles into *dst, single block of 1024 (four independent accumulators per thread keep four
@@ -1613,6 +1707,13 @@ struct lslam_pg {
   std::vector<int32_t> h_ij;
   std::vector<int32_t> edge_block;  // per edge: off-diagonal block id
   std::vector<int32_t> off_pairs;   // [n_off][2]
+  // robust kernels (lslam_pg_set_robust_kernels): per GLOBAL edge id; `robust` selects the robust instantiations of the edge
+  // and chi2 kernels, and is false while no edge carries a kernel -- the plain solver then launches what it always launched
+  lslam::DevBuf<int32_t> d_kind;
+  lslam::DevBuf<double> d_delta;
+  std::vector<int32_t> h_kind;
+  bool robust = false;
+  lslam::DevBuf<double> d_tap, d_tap_poses;  // lslam_pg_edge_robust: [e2 | rho0 | rho1] of n_e each; caller-supplied poses
   // shard structures
   lslam::DevBuf<double> d_rec, d_chi;
   lslam::DevBuf<int32_t> d_vptr, d_vadj, d_optr, d_oadj;
@@ -1706,7 +1807,11 @@ int build_shard(lslam_pg *pg, int e_begin, int e_end) {
 // system of this shard's edges into pg->d_sys.p, then the all-reduce over ranks
 int linearize(lslam_pg *pg, const double *poses) {
   const int ne = pg->e_end - pg->e_begin;
-  if (ne > 0)
+  if (ne > 0 && pg->robust)
+    hipLaunchKernelGGL(pg_edge_robust_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij.p,
+                       pg->d_meas.p, pg->d_info.p, pg->e_begin, pg->e_end, pg->fixed, pg->d_kind.p, pg->d_delta.p,
+                       pg->d_rec.p, pg->d_chi.p);
+  else if (ne > 0)
     hipLaunchKernelGGL(pg_edge_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij.p,
                        pg->d_meas.p, pg->d_info.p, pg->e_begin, pg->e_end, pg->fixed, pg->d_rec.p, pg->d_chi.p);
   hipLaunchKernelGGL(pg_assemble_vertex_kernel, dim3((pg->n_v * 42 + 255) / 256), dim3(256), 0, pg->stream,
@@ -1733,7 +1838,10 @@ int eval_chi2(lslam_pg *pg, const double *poses, double *out) {
   // the chi2 slot of the system buffer is free again once the current chi2 has been read
   // back, and it lives in the buffer the all-reduce hook knows how to address
   const int ne = pg->e_end - pg->e_begin;
-  if (ne > 0)
+  if (ne > 0 && pg->robust)  // the sum below is then the sum of rho0 (g2o's activeRobustChi2)
+    hipLaunchKernelGGL(pg_chi2_robust_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij.p,
+                       pg->d_meas.p, pg->d_info.p, pg->e_begin, pg->e_end, pg->d_kind.p, pg->d_delta.p, pg->d_chi.p);
+  else if (ne > 0)
     hipLaunchKernelGGL(pg_chi2_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij.p,
                        pg->d_meas.p, pg->d_info.p, pg->e_begin, pg->e_end, pg->d_chi.p);
   hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne, 1, pg->chi());
@@ -2420,6 +2528,7 @@ int lslam_pg_set_comm(lslam_pg *pg, lslam_comm *comm) {
   return LSLAM_OK;
 }
 int32_t lslam_pg_num_offdiag(const lslam_pg *pg) { return pg ? pg->n_off : 0; }
+void *lslam_pg_stream(lslam_pg *pg) { return pg ? (void *)pg->stream : nullptr; }
 
 int lslam_pg_set_shard(lslam_pg *pg, int32_t e_begin, int32_t e_end, lslam_allreduce_fn fn, void *user,
                        double *system_buf) {
@@ -2448,6 +2557,113 @@ int lslam_pg_linearize(lslam_pg *pg, double *diag_out, double *off_out, int32_t 
   if (chi2_out) PG_TRY(hipMemcpyAsync(chi2_out, pg->chi(), 8, hipMemcpyDeviceToHost, pg->stream));
   PG_TRY(hipStreamSynchronize(pg->stream));
   if (off_ij_out) std::memcpy(off_ij_out, pg->off_pairs.data(), pg->off_pairs.size() * sizeof(int32_t));
+  return LSLAM_OK;
+}
+
+// ---- robust kernels on edges -------------------------------------------------------------------------------------------
+int lslam_pg_kernel_from_name(const char *name) {
+  static const char *const names[4] = {"NONE", "Huber", "Cauchy", "DCS"};
+  if (!name) return -1;
+  for (int k = 0; k < 4; ++k)
+    if (std::strcmp(names[k], name) == 0) return k;
+  return -1;
+}
+int lslam_pg_set_robust_kernels(lslam_pg *pg, const int32_t *kind, const double *delta) {
+  if (!pg) return LSLAM_ERR_INVALID;
+  if ((kind == nullptr) != (delta == nullptr)) {
+    g_pg_err = "robust kernels: kind and delta are given together, or both NULL to clear";
+    return LSLAM_ERR_INVALID;
+  }
+  PG_TRY(hipSetDevice(pg->device));
+  if (!kind) {  // the plain solver again
+    pg->robust = false;
+    pg->h_kind.clear();
+    return LSLAM_OK;
+  }
+  bool any = false;
+  for (int e = 0; e < pg->n_e; ++e) {  // everything is checked before anything changes
+    if (kind[e] < LSLAM_PG_KERNEL_NONE || kind[e] > LSLAM_PG_KERNEL_DCS) {
+      g_pg_err = "robust kernels: unknown kind " + std::to_string(kind[e]) + " on edge " + std::to_string(e);
+      return LSLAM_ERR_INVALID;
+    }
+    if (kind[e] == LSLAM_PG_KERNEL_NONE) continue;
+    any = true;
+    if (!std::isfinite(delta[e]) || !(delta[e] > 0.0)) {
+      g_pg_err = "robust kernels: delta must be finite and > 0 (edge " + std::to_string(e) + ")";
+      return LSLAM_ERR_INVALID;
+    }
+  }
+  if (!any) {  // every edge NONE: nothing to weight
+    pg->robust = false;
+    pg->h_kind.clear();
+    return LSLAM_OK;
+  }
+  std::vector<int32_t> hk(kind, kind + pg->n_e);
+  std::vector<double> hd(delta, delta + pg->n_e);
+  for (int e = 0; e < pg->n_e; ++e)
+    if (hk[e] == LSLAM_PG_KERNEL_NONE) hd[e] = 1.0;  // ignored; never a NaN in device memory
+  PG_TRY(hipStreamSynchronize(pg->stream));  // nothing in flight still reads the arrays replaced here
+  PG_TRY(dev_upload(pg->d_kind, hk));
+  PG_TRY(dev_upload(pg->d_delta, hd));
+  pg->h_kind.swap(hk);
+  pg->robust = true;
+  return LSLAM_OK;
+}
+
+// e2 / rho0 / rho1 of every edge into pg->d_tap, at `poses7` (host; NULL: the current estimate), and back to `host` [3 n_e]
+static int robust_tap(lslam_pg *pg, const double *poses7, std::vector<double> &host) {
+  host.assign(3 * (size_t)pg->n_e, 0.0);
+  if (pg->n_e == 0) return LSLAM_OK;
+  const double *poses = pg->d_poses.p;
+  if (poses7) {
+    PG_TRY(pg->d_tap_poses.alloc((size_t)pg->n_v * 7));
+    PG_TRY(hipMemcpyAsync(pg->d_tap_poses.p, poses7, (size_t)pg->n_v * 7 * 8, hipMemcpyHostToDevice, pg->stream));
+    poses = pg->d_tap_poses.p;
+  }
+  const size_t ne = (size_t)pg->n_e;
+  PG_TRY(pg->d_tap.alloc(3 * ne));
+  hipLaunchKernelGGL(pg_edge_robust_tap_kernel, dim3((pg->n_e + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij.p,
+                     pg->d_meas.p, pg->d_info.p, pg->n_e, pg->robust ? pg->d_kind.p : (const int32_t *)nullptr,
+                     pg->robust ? pg->d_delta.p : (const double *)nullptr, pg->d_tap.p, pg->d_tap.p + ne,
+                     pg->d_tap.p + 2 * ne);
+  PG_TRY(hipGetLastError());
+  PG_TRY(hipMemcpyAsync(host.data(), pg->d_tap.p, 3 * ne * 8, hipMemcpyDeviceToHost, pg->stream));
+  PG_TRY(hipStreamSynchronize(pg->stream));
+  return LSLAM_OK;
+}
+
+int lslam_pg_edge_robust(lslam_pg *pg, const double *poses7, double *e2, double *rho, double *weight) {
+  if (!pg) return LSLAM_ERR_INVALID;
+  PG_TRY(hipSetDevice(pg->device));
+  std::vector<double> h;
+  const int rc = robust_tap(pg, poses7, h);
+  if (rc) return rc;
+  const size_t ne = (size_t)pg->n_e;
+  if (e2 && ne) std::memcpy(e2, h.data(), ne * 8);
+  if (rho && ne) std::memcpy(rho, h.data() + ne, ne * 8);
+  if (weight && ne) std::memcpy(weight, h.data() + 2 * ne, ne * 8);
+  return LSLAM_OK;
+}
+
+int lslam_pg_robust_info(lslam_pg *pg, int32_t *n_robust, int32_t *n_downweighted, double *chi2_plain) {
+  if (!pg) return LSLAM_ERR_INVALID;
+  PG_TRY(hipSetDevice(pg->device));
+  std::vector<double> h;
+  const int rc = robust_tap(pg, nullptr, h);
+  if (rc) return rc;
+  const size_t ne = (size_t)pg->n_e;
+  int nr = 0, nd = 0;
+  double sum = 0.0;
+  for (size_t e = 0; e < ne; ++e) {  // edge order
+    sum += h[e];
+    if (pg->robust && pg->h_kind[e] != LSLAM_PG_KERNEL_NONE) {
+      ++nr;
+      if (h[2 * ne + e] < 1.0) ++nd;
+    }
+  }
+  if (n_robust) *n_robust = nr;
+  if (n_downweighted) *n_downweighted = nd;
+  if (chi2_plain) *chi2_plain = sum;
   return LSLAM_OK;
 }
 

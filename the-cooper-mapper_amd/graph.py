@@ -8,7 +8,7 @@ ROS plumbing (topics, threads, tf) is not mirrored; the arithmetic runs on the d
 import numpy as np
 
 from .loop_closure import KeyFrame, LoopDetector
-from .pose_graph import PoseGraph
+from .pose_graph import PoseGraph, kernel_kind
 
 
 def _angle_of(R):
@@ -61,14 +61,23 @@ LOOP_INFORMATION = 2.0 * np.eye(6)
 class Graph:
     def __init__(self, device=0, ctx=None, loop_detector=None, max_keyframes_per_update=10, resident=False,
                  keep_host_clouds=True, store_max_points=0, store_max_keyframes=0, store_slab_points=0, appearance_loops=False,
-                 sc_params=None):
+                 sc_params=None, loop_robust_kernel=None, loop_robust_delta=1.0):
         """``resident=True``: the keyframes' clouds live in a :class:`KeyframeStore` on the loop detector's context --
         ``add_frame`` uploads them once (``kf.store_id``), loop closure and ``get_final_feature_map`` read them there;
         ``keep_host_clouds=False`` then drops the host copies (``kf.corner_cloud`` / ``kf.surf_cloud`` fetch on demand).
         The ``store_*`` limits are :class:`KeyframeStore`'s (0: its defaults).  Without ``resident`` nothing changes.
         ``appearance_loops=True`` (not in the reference; implies ``resident``): ``optimize`` also runs
         ``LoopDetector.detect_appearance`` -- scan-context candidates over the store, ``sc_params`` being
-        ``KeyframeStore.sc_setup``'s keywords -- for the new keyframes for which ``detect_nearest`` found no loop."""
+        ``KeyframeStore.sc_setup``'s keywords -- for the new keyframes for which ``detect_nearest`` found no loop.
+        ``loop_robust_kernel`` (not in the reference, which includes g2o's robust-kernel headers and uses none): "Huber",
+        "Cauchy" or "DCS" with parameter ``loop_robust_delta`` on every LOOP edge, whichever detector found it; odometry edges
+        never carry one.  A false loop -- two places that look alike -- then loses its weight instead of bending the map:
+        :meth:`loop_weights`, :meth:`rejected_loops`.  The default stays None (every edge at full weight, the reference's
+        behaviour); switching a kernel on is the caller's decision.  Huber is convex and CANNOT reject an outlier, it only
+        bounds its pull: on graphs with this node's weak odometry information the trajectory still bends to meet a false loop
+        (DESIGN, pose-graph section); Cauchy (0.1) and DCS (1) do reject."""
+        self.loop_robust_kernel = loop_robust_kernel if kernel_kind(loop_robust_kernel) else None
+        self.loop_robust_delta = float(loop_robust_delta)
         self.solver = PoseGraph(device)
         self.loop_detector = loop_detector or LoopDetector(device=device, ctx=ctx)
         self.store = None
@@ -86,6 +95,7 @@ class Graph:
         self.max_keyframes_per_update = max_keyframes_per_update
         self.tf_odom2graph = np.eye(4)
         self.loops = []
+        self.loop_edges = []  # solver edge index of every entry of self.loops
 
     # graph.cpp:230-246
     def add_frame(self, odom, corner_cloud, surf_cloud):
@@ -131,7 +141,9 @@ class Graph:
             loops = loops + self.loop_detector.detect_appearance(self.keyframes,
                                                                  [k for k in self.new_keyframes if id(k) not in closed])
         for lp in loops:
-            self.solver.add_se3_edge(lp.key1.node, lp.key2.node, lp.relative_pose.astype(np.float64), LOOP_INFORMATION)
+            self.loop_edges.append(self.solver.add_se3_edge(lp.key1.node, lp.key2.node, lp.relative_pose.astype(np.float64),
+                                                            LOOP_INFORMATION, robust_kernel=self.loop_robust_kernel,
+                                                            robust_delta=self.loop_robust_delta))
         self.loops.extend(loops)
         self.keyframes.extend(self.new_keyframes)
         self.new_keyframes = []
@@ -145,6 +157,18 @@ class Graph:
         last = self.keyframes[-1]
         self.tf_odom2graph = last.estimate @ np.linalg.inv(last.odom)
         return loops, iterations
+
+    def loop_weights(self):
+        """The robust weight (rho1) of every entry of ``self.loops`` at the solver's current estimate, i.e. after the last
+        optimise; all 1 without ``loop_robust_kernel``."""
+        if not self.loops:
+            return np.zeros(0)
+        return self.solver.edge_robust()["weight"][np.asarray(self.loop_edges, np.int64)]
+
+    def rejected_loops(self, threshold=0.1):
+        """The loops whose weight is below ``threshold``.  Reporting only: nothing is removed from the graph."""
+        w = self.loop_weights()
+        return [lp for lp, wk in zip(self.loops, w) if wk < threshold]
 
     # graph.cpp:150-199 (driven by Graph::save, :106-147)
     def get_final_feature_map(self, ctx=None, directory=None, cube_dims=(121, 111, 121), bootstrap=False, keyframes=None):

@@ -17,6 +17,23 @@ def _dp(a):
     return a.ctypes.data_as(c_double_p)
 
 
+# include/lslam_c.h: LSLAM_PG_KERNEL_*
+KERNEL_NONE, KERNEL_HUBER, KERNEL_CAUCHY, KERNEL_DCS = 0, 1, 2, 3
+_KERNEL_NAMES = {"none": KERNEL_NONE, "huber": KERNEL_HUBER, "cauchy": KERNEL_CAUCHY, "dcs": KERNEL_DCS}
+
+
+def kernel_kind(k):
+    """None / "NONE" / "Huber" / "Cauchy" / "DCS" (any case) or an LSLAM_PG_KERNEL_* integer -> the integer.  An integer is
+    passed through as it is: the library decides whether it names a kernel."""
+    if k is None:
+        return KERNEL_NONE
+    if isinstance(k, str):
+        if k.lower() not in _KERNEL_NAMES:
+            raise ValueError("unknown robust kernel %r (NONE, Huber, Cauchy, DCS)" % (k,))
+        return _KERNEL_NAMES[k.lower()]
+    return int(k)
+
+
 def mat_to_pose7(T):
     """4x4 -> {t, q_xyzw} (Eigen Quaterniond(R), Shepperd's method)."""
     T = np.asarray(T, np.float64)
@@ -62,6 +79,8 @@ class PoseGraph:
         self._ij = []
         self._meas = []
         self._info = []
+        self._kind = []   # per edge: LSLAM_PG_KERNEL_* and its delta; applied by _build, so they survive a topology change
+        self._delta = []
         self.fixed = 0  # the vertex lslam_pg_create pins (g2o: setFixed); -1 pins none
         self.h = None
         self._cb = None
@@ -75,10 +94,14 @@ class PoseGraph:
         self._nodes.append(mat_to_pose7(p) if p.shape == (4, 4) else p.reshape(7).copy())
         return len(self._nodes) - 1
 
-    def add_se3_edge(self, v1, v2, relative_pose, information_matrix):
-        """solver_g2o.cpp:65-77."""
+    def add_se3_edge(self, v1, v2, relative_pose, information_matrix, robust_kernel=None, robust_delta=1.0):
+        """solver_g2o.cpp:65-77.  ``robust_kernel`` (not in the reference, which only includes g2o's kernel headers): None /
+        "NONE", "Huber", "Cauchy" or "DCS" with parameter ``robust_delta`` on this edge, g2o's semantics (lslam_c.h)."""
         z = np.asarray(relative_pose, np.float64)
+        kind = kernel_kind(robust_kernel)
         self._drop()
+        self._kind.append(kind)
+        self._delta.append(float(robust_delta))
         self._ij.append((int(v1), int(v2)))
         self._meas.append(mat_to_pose7(z) if z.shape == (4, 4) else z.reshape(7).copy())
         self._info.append(np.asarray(information_matrix, np.float64).reshape(6, 6).copy())
@@ -93,9 +116,14 @@ class PoseGraph:
         return st.iterations
 
     # ---- bulk construction / access ---------------------------------------------------
-    def set_graph(self, poses7, ij, meas7, info, fixed=0):
-        """Replace the graph; `fixed` is the vertex held at its estimate (default: the first, as add_se3_node)."""
+    def set_graph(self, poses7, ij, meas7, info, fixed=0, kernels=None, deltas=None):
+        """Replace the graph; `fixed` is the vertex held at its estimate (default: the first, as add_se3_node).  `kernels` /
+        `deltas`: per edge, as set_robust_kernels (None: plain edges)."""
+        kind, delta = self._kernel_lists(kernels, deltas, len(np.asarray(ij).reshape(-1, 2)))  # raises before anything is dropped
+        if int(fixed) >= len(np.asarray(poses7).reshape(-1, 7)):
+            raise ValueError("fixed vertex %d of a graph with %d vertices" % (int(fixed), len(np.asarray(poses7).reshape(-1, 7))))
         self._drop(keep_estimates=False)
+        self._kind, self._delta = kind, delta
         self._nodes = [p for p in np.asarray(poses7, np.float64).reshape(-1, 7)]
         self._ij = [tuple(int(v) for v in e) for e in np.asarray(ij).reshape(-1, 2)]
         self._meas = [m for m in np.asarray(meas7, np.float64).reshape(-1, 7)]
@@ -105,9 +133,61 @@ class PoseGraph:
             raise ValueError("fixed vertex %d of a graph with %d vertices" % (self.fixed, len(self._nodes)))
         self._drop()
 
+    # ---- robust kernels on edges (lslam_pg_set_robust_kernels) ------------------------------
+    @staticmethod
+    def _kernel_lists(kinds, deltas, ne):
+        if kinds is None:
+            return [KERNEL_NONE] * ne, [1.0] * ne
+        kinds = [kernel_kind(k) for k in (kinds.tolist() if isinstance(kinds, np.ndarray) else kinds)]
+        deltas = np.broadcast_to(np.asarray(1.0 if deltas is None else deltas, np.float64), (ne,)).tolist()
+        if len(kinds) != ne:
+            raise ValueError("%d kernels for %d edges" % (len(kinds), ne))
+        return kinds, deltas
+
+    def set_robust_kernels(self, kinds, deltas):
+        """One kernel per edge: `kinds` names or LSLAM_PG_KERNEL_* integers, `deltas` a scalar or one per edge (ignored where
+        the kind is NONE).  Checked by the library: on an error (delta not finite and > 0, unknown kind) nothing changes."""
+        kinds, deltas = self._kernel_lists(kinds, deltas, len(self._ij))
+        if self.h:
+            self._upload_kernels(kinds, deltas)
+        self._kind, self._delta = kinds, deltas
+
+    def clear_robust_kernels(self):
+        """The plain solver again."""
+        if self.h:
+            self._check(self.lib.lslam_pg_set_robust_kernels(self.h, None, None))
+        self._kind, self._delta = self._kernel_lists(None, None, len(self._ij))
+
+    def edge_robust(self, poses=None):
+        """Per edge at `poses` ((n, 7); None: the current estimate): dict(e2 = e^T Omega e, rho = rho0, weight = rho1)."""
+        self._build()
+        ne = len(self._ij)
+        e2, rho, w = np.zeros(ne), np.zeros(ne), np.zeros(ne)
+        p = None
+        if poses is not None:
+            p = np.ascontiguousarray(poses, np.float64)
+            if p.shape != (len(self._nodes), 7):
+                raise ValueError("poses must be (%d, 7)" % len(self._nodes))
+        self._check(self.lib.lslam_pg_edge_robust(self.h, _dp(p) if p is not None else None, _dp(e2), _dp(rho), _dp(w)))
+        return dict(e2=e2, rho=rho, weight=w)
+
+    def robust_info(self):
+        """dict(n_robust: edges carrying a kernel, n_downweighted: of those, edges with weight < 1 at the current estimate,
+        chi2_plain: the plain sum of e^T Omega e)."""
+        self._build()
+        nr, nd, c2 = C.c_int32(), C.c_int32(), C.c_double()
+        self._check(self.lib.lslam_pg_robust_info(self.h, C.byref(nr), C.byref(nd), C.byref(c2)))
+        return dict(n_robust=nr.value, n_downweighted=nd.value, chi2_plain=c2.value)
+
+    def _upload_kernels(self, kinds, deltas):
+        k = np.ascontiguousarray(kinds, np.int32)
+        d = np.ascontiguousarray(deltas, np.float64)
+        self._check(self.lib.lslam_pg_set_robust_kernels(self.h, k.ctypes.data_as(c_int32_p), _dp(d)))
+
     # ---- g2o text format (solver_g2o.cpp:97-100) -----------------------------------------
     def save(self, path):
-        """SolverG2O::save: the graph with its current estimates as a .g2o file."""
+        """SolverG2O::save: the graph with its current estimates as a .g2o file.  The format has no place for a robust kernel:
+        none is written, and a graph loaded back has plain edges."""
         self._build()
         self._check(self.lib.lslam_pg_save_g2o(self.h, str(path).encode()))
 
@@ -269,6 +349,12 @@ class PoseGraph:
         if rc != 0:
             raise LslamError(rc, self.lib.lslam_pg_last_error().decode())
         self.h = h
+        if any(k != KERNEL_NONE for k in self._kind):
+            try:
+                self._upload_kernels(self._kind, self._delta)
+            except Exception:
+                self._drop(keep_estimates=False)
+                raise
 
     def close(self):
         self._drop(keep_estimates=False)
