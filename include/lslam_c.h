@@ -118,6 +118,14 @@ enum { LSLAM_AB_PERSISTENT_GN = 1, /* one resident scan: the whole Gauss-Newton 
                                       slower: 1.405e10 against 1.461e10, no faster even in a loop's first sweep, where work is
                                       plentiful -- the lanes a wavefront loses are lost inside every round of the walk (descents
                                       and stack pops of different lengths), not at its end */
+       LSLAM_AB_GRID_GENERAL = 256, /* grid sweep: the production loop's launches through the general instantiation of
+                                      sweep_grid_kernel instead of the lean one (the same statements with the shuffle sums, the
+                                      taps, the _fineScore gate, the unbounded search, the counters and the fit cache folded away
+                                      at compile time, and the five neighbours' points handed from the search to the fit instead
+                                      of gathered twice: 61 VGPRs and no scratch at eight wavefronts per SIMD against 72 + 36 B at
+                                      seven).  Same bits.  Measured on the headline, the two taken in turn in one session: 1.466 -
+                                      1.475e10 with this switch or the library before it, 1.512 - 1.517e10 without: +3.0 %
+                                      (profiles/r14_grid_lean.txt) */
        LSLAM_AB_WIDE_NF_MARGIN = 16 /* a map without kd-trees: a point whose fifth and sixth distances are within 8 ulps of each
                                       other counts as undecidable too (as an exact tie does): the trees are built and the call
                                       repeated.  Off: such a pair is ordered by its exact fp32 distances -- nanoflann's order
@@ -1226,6 +1234,8 @@ void *lslam_stream(lslam_ctx *ctx); /* hipStream_t */
 void lslam_debug_sweep_launches(lslam_ctx *ctx, uint64_t counts[8]);
 /* ... and of the grid sweep (sweep_grid_kernel; LSLAM_SEARCH_GRID) */
 uint64_t lslam_debug_grid_launches(lslam_ctx *ctx);
+/* ... of which those that took the lean instantiation (sweep_grid_kernel<256, false, false, true>: the production loop's launch) */
+uint64_t lslam_debug_grid_lean_launches(lslam_ctx *ctx);
 /* ... of which the single-launch form for a map without trees (sweep_grid_kernel<256, true>) */
 uint64_t lslam_debug_grid_wide_launches(lslam_ctx *ctx);
 /* cells of the resident map's two cell tables (corner, surf); 0 while a type has no grid */

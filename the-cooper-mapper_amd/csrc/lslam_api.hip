@@ -217,6 +217,7 @@ struct lslam_ctx {
   int32_t n_st_blocks = 0;
   StereoCam st_cam{};
   uint64_t sweep_variants[SWEEP_N_VARIANTS] = {0};  // sweep launches per kernel instantiation (lslam_debug_sweep_launches)
+  uint64_t grid_lean_launches = 0;                  // ... of SWEEP_VARIANT_GRID's, those that took the lean instantiation (lslam_debug_grid_lean_launches)
   // cell grids over the whole-map trees (lslam_grid.hpp), built the first time the grid search is asked for on a map
   GridDev kc, ks;
   uint64_t map_epoch = 0;      // bumped whenever the resident trees change
@@ -441,9 +442,12 @@ hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, hipEve
       if (variant) *variant = SWEEP_VARIANT_GRID_WIDE;
       return e1w;
     }
-    hipError_t e = launch_sweep_grid(a, jtj_mode, ctx->stream, e0, nullptr);
+    // the production loop's launch takes the lean instantiation (A/B: lslam_opts.ab_switches & LSLAM_AB_GRID_GENERAL keeps the general one)
+    const bool lean = grid_sweep_lean_ok(a, jtj_mode) && !(ctx->ab_now & LSLAM_AB_GRID_GENERAL);
+    hipError_t e = launch_sweep_grid(a, jtj_mode, ctx->stream, e0, nullptr, false, lean);
     v = SWEEP_VARIANT_GRID;
     ctx->sweep_variants[v]++;
+    if (lean) ctx->grid_lean_launches++;
     if (variant) *variant = v;
     if (e != hipSuccess) return e;
     bool planned = false;
@@ -732,6 +736,7 @@ void lslam_debug_lazy_trees(lslam_ctx *ctx, uint64_t out[3]) {
 }
 
 uint64_t lslam_debug_grid_launches(lslam_ctx *ctx) { return ctx ? ctx->sweep_variants[SWEEP_VARIANT_GRID] + ctx->sweep_variants[SWEEP_VARIANT_GRID_WIDE] : 0; }
+uint64_t lslam_debug_grid_lean_launches(lslam_ctx *ctx) { return ctx ? ctx->grid_lean_launches : 0; }
 uint64_t lslam_debug_grid_wide_launches(lslam_ctx *ctx) { return ctx ? ctx->sweep_variants[SWEEP_VARIANT_GRID_WIDE] : 0; }
 void lslam_debug_grid_cells(lslam_ctx *ctx, uint64_t out[2]) {
   out[0] = ctx && ctx->kc.view.cell_start ? (uint64_t)ctx->kc.n_cells : 0;

@@ -129,9 +129,15 @@ enum : int {
 // (twenty-five runs of five), for the points the 27-cell probe could not prove: guaranteed radius c (2 + wall) instead of
 // c (1 + wall), rows clipped to the BALL of the caller's bound (which such a point always has: the fifth distance the first
 // probe saw).  rows: 2 (2R + 1)^2 words per lane.
-template <int BLOCK, int R = 1>
+//
+// KEEP: also hand out what was fetched: (*five)[3 j ..] = x, y, z of G.pts[p[j]], the points of the five returned, when
+// *five_valid -- wave-uniform: no lane of the wavefront took the re-sort branch, so every lane's five are its first five
+// survivors.  A caller that goes on to fit them (the lean grid sweep) need not gather them a second time.  (Plain floats: an
+// array of float4 handed through stays in scratch memory.)
+template <int BLOCK, int R = 1, bool KEEP = false>
 LSLAM_DEV int knn5_grid(const CellGrid &G, const bool on, const float qx, const float qy, const float qz, const float bound,
-                        const float clip_margin, lds_u32 *rows, float (&d)[5], int (&p)[5], float &lb6 LSLAM_SEC_PARAM) {
+                        const float clip_margin, lds_u32 *rows, float (&d)[5], int (&p)[5], float &lb6 LSLAM_SEC_PARAM,
+                        float (*five)[15] = nullptr, bool *five_valid = nullptr) {
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     d[i] = FLT_MAX;
@@ -450,6 +456,15 @@ LSLAM_DEV int knn5_grid(const CellGrid &G, const bool on, const float qx, const 
     p[j] = (ks[j] != 0xFFFFFFFFu) ? (int)pos[j] : -1;
   }
   const bool ascending = e[0] <= e[1] && e[1] <= e[2] && e[2] <= e[3] && e[3] <= e[4] && e[4] <= e[5];
+  if constexpr (KEEP) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      (*five)[3 * j] = sp[j].x;
+      (*five)[3 * j + 1] = sp[j].y;
+      (*five)[3 * j + 2] = sp[j].z;
+    }
+    *five_valid = __builtin_amdgcn_ballot_w64(!ascending) == 0ull;
+  }
   if (__builtin_amdgcn_ballot_w64(!ascending) != 0ull) {
 #pragma unroll
     for (int j = 0; j < 5; ++j) {

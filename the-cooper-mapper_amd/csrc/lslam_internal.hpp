@@ -312,7 +312,14 @@ enum : int {
   SWEEP_VARIANT_GRID_WIDE = 9,  // sweep_grid_kernel<256, true>: a map without trees, a small launch -- unproven points resolved in place
   SWEEP_N_VARIANTS = 10
 };
-hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool resolve_in_place = false);
+// A grid sweep the lean instantiation sweep_grid_kernel<256, false, false, true> computes as the general one does: the production
+// loop's launch -- MFMA sums, no taps, the acceptance gate on the fifth distance, the bounded search, no counters, no fit cache.
+// launch_sweep_grid takes the lean kernel when `lean` is set, which only such a launch may be given (and not resolve_in_place).
+inline bool grid_sweep_lean_ok(const SweepArgs &a, int jtj_mode) {
+  return jtj_mode == 1 && !a.flags_out && !a.coeff_out && !a.idx_out && a.fine_gate_c < 0.0f && a.bounded && !a.cert_stats && !a.fit_ids;
+}
+hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool resolve_in_place = false,
+                             bool lean = false);
 hipError_t launch_sweep_wide(const SweepArgs &a, hipStream_t s);  // sweep_wide_kernel (its prefix: launch_sweep_plan with_prefix)
 hipError_t launch_knn5_wide(const CellGrid &G, const float4 *q, int nq, float nf_slack, int32_t *idx, float *d2, uint8_t *undecided, hipStream_t s);
 hipError_t launch_knn5_grid(const CellGrid &G, const TreeView &T, const float4 *q, int nq, int32_t *idx, float *d2,

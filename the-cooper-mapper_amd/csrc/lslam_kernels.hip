@@ -1015,6 +1015,9 @@ hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, h
 #ifndef LSLAM_GRID_OCC
 #define LSLAM_GRID_OCC 7  // wavefronts per SIMD the grid sweep is compiled for: 72 VGPRs + 36 B of scratch (6: 80 VGPRs + 8 B, 1.6 % slower since round 6 -- it had been the faster one before the loop was hand-scheduled; 5: 88 VGPRs, 5 % slower; 8: 64 VGPRs + 96 B of scratch, 8 % slower)
 #endif
+#ifndef LSLAM_GRID_LEAN_OCC
+#define LSLAM_GRID_LEAN_OCC 8  // ... and the lean instantiation (below): 61 VGPRs without scratch at 8, 7 and 6 alike, so eight wavefronts run whatever is asked for (the attribute is a floor) -- 1.4821 / 1.4822 / 1.4826e10 for 8 / 7 / 6: no difference
+#endif
 #ifndef LSLAM_STAGE_PAD
 #define LSLAM_STAGE_PAD 0
 #endif
@@ -1033,8 +1036,26 @@ LSLAM_DEV void wide_probe(const CellGrid &G, const float (&sel)[3], float r2, in
 // SIMD is a chain of latencies of which the loop is only one.)
 // FITC: the instantiation with the fit cache (LSLAM_AB_FIT_CACHE) -- a template argument, not a run-time branch: with the cache's
 // code in it the kernel everybody runs was 3.5 % slower (16 bytes of scratch, twelve more scalar registers, a longer program)
-template <int BLOCK, bool WIDE = false, bool FITC = false>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : LSLAM_GRID_OCC))) void sweep_grid_kernel(SweepArgs a, int jtj_mode) {
+// LEAN: the instantiation of the production sweep (grid_sweep_lean_ok: MFMA sums, no taps, no _fineScore gate, the bounded
+// search, no counters, no fit cache, not WIDE) -- the same statements with what such a launch never does folded away at compile
+// time, so that the register allocator does not budget for it: the general kernel carries the shuffle path's 31 accumulators
+// (all of its scratch) and the taps' live values through the whole program.  With the registers that frees the five
+// neighbours' points go from the search (which has fetched them for their exact distances) straight to the fit, not gathered a
+// second time (knn5_grid<.., true>, point_residual<true>).  Same operations on the same values: same bits; +3.0 % on the
+// headline (LSLAM_AB_GRID_GENERAL brings the general kernel back; DESIGN 4 has the numbers).
+template <int BLOCK, bool WIDE = false, bool FITC = false, bool LEAN = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : (LEAN ? LSLAM_GRID_LEAN_OCC : LSLAM_GRID_OCC)))) void sweep_grid_kernel(SweepArgs a, int jtj_mode) {
+  static_assert(!LEAN || (!WIDE && !FITC), "the lean grid sweep has neither the wide probe nor the fit cache");
+  if constexpr (LEAN) {  // what launch_sweep_grid has checked, as constants
+    jtj_mode = 1;
+    a.flags_out = nullptr;
+    a.coeff_out = nullptr;
+    a.idx_out = nullptr;
+    a.fine_gate_c = -1.0f;
+    a.bounded = 1;
+    a.cert_stats = nullptr;
+    a.fit_ids = nullptr;
+  }
   constexpr int NWAVE = BLOCK / 64;
   const int lb = a.active_blocks ? a.active_blocks[xcd_remap(blockIdx.x, a.n_active)] : xcd_remap(blockIdx.x, a.nb_total);
   const BlockDesc bd = a.blocks[lb];
@@ -1126,7 +1147,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 
   __builtin_amdgcn_s_sleep(LSLAM_EXP_SLEEP);
 #endif
   LSLAM_TICK_P(scp, 0);  // block and state fetched, the point, its transform, the carried bound
-  int verdict = knn5_grid<BLOCK>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG);
+  float five[15];  // LEAN: the five neighbours' points as the search fetched them, handed on to the residual chain
+  bool five_valid = false;
+  int verdict;
+  if constexpr (LEAN) verdict = knn5_grid<BLOCK, 1, true>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG, &five, &five_valid);
+  else verdict = knn5_grid<BLOCK>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG);
   LSLAM_TICK_P(scp, 3);  // the six survivors fetched again, exact distances, order, proof
   // beyond the gate nothing is looked up (ScanMatch.cpp:102,120); the taps and the _fineScore re-sweep want nanoflann's answer
   if (verdict == GRID_FAR && !a.bounded) verdict = GRID_UNPROVEN;
@@ -1288,7 +1313,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 
     }
   }
   LSLAM_TICK_P(scp, 4);  // the list of pass 2 (one workgroup barrier), the carried state written
-  if (has && !fit_done) point_residual(a, bd, is_surf, G.pts, q, sel, d, p, sc, row, rb, kept, matched, score);
+  if (has && !fit_done) {
+    if constexpr (LEAN) point_residual<true>(a, bd, is_surf, G.pts, q, sel, d, p, sc, row, rb, kept, matched, score, &five, five_valid);
+    else point_residual(a, bd, is_surf, G.pts, q, sel, d, p, sc, row, rb, kept, matched, score);
+  }
   LSLAM_TICK_P(scp, 5);  // the residual chain: five neighbours fetched, findLine / findPlane, coefficient, Jacobian row, score
   __syncthreads();  // every wavefront is done with its row table: the staging rows may be written
   LSLAM_TICK_P(scp, 7);  // waiting for the workgroup's slowest wavefront
@@ -1373,15 +1401,18 @@ hipError_t launch_compact_active(const GNState *states, const ProbBlocks *probs,
   return hipGetLastError();
 }
 
-hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool resolve_in_place) {
+hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool resolve_in_place, bool lean) {
   if (a.nb_total <= 0) return hipSuccess;
+  if (lean && (resolve_in_place || !grid_sweep_lean_ok(a, jtj_mode))) return hipErrorInvalidValue;  // (the lean kernel would compute something else)
   if (a.active_blocks && !resolve_in_place) {  // the batch's grid sweep over the running scans' workgroups only
     if (a.n_active <= 0) return hipSuccess;
-    if (a.fit_ids) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, true>), dim3(a.n_active), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
+    if (lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, false, true>), dim3(a.n_active), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
+    else if (a.fit_ids) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, true>), dim3(a.n_active), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
     else hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK>), dim3(a.n_active), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
     return hipGetLastError();
   }
   if (resolve_in_place) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, true>), dim3(a.nb_total), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
+  else if (lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, false, true>), dim3(a.nb_total), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
   else if (a.fit_ids) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, true>), dim3(a.nb_total), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
   else hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK>), dim3(a.nb_total), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
   return hipGetLastError();

@@ -31,9 +31,13 @@ LSLAM_DEV int cube_tree_of(const CubeGridDev &g, float x, float y, float z) {
 // ScanMatch.cpp:102-139 for one point whose five neighbours are known: the acceptance gate, findLine / findPlane on the five
 // (fetched from P, the array the neighbour ids p[] index), the coefficient, the Jacobian row; the optional per-point taps.
 // Shared by the tree sweep (P = the tree's permuted points) and the grid sweep (P = the cell-sorted points).
+// GIVEN (the lean grid sweep): the search has the five points in registers already -- (*given)[3 j ..] = x, y, z of P[p[j]]
+// when `use_given` (wave-uniform; knn5_grid<.., true>) -- and they are not gathered again (findLine / findPlane read x, y, z only).
+template <bool GIVEN = false>
 LSLAM_DEV void point_residual(const SweepArgs &a, const BlockDesc &bd, const bool is_surf, const float4 *P, const float4 &q,
                               const float (&sel)[3], const float (&d)[5], const int (&p)[5], const float (&sc)[6],
-                              float (&row)[6], float &rb, float &kept, float &matched, float &score) {
+                              float (&row)[6], float &rb, float &kept, float &matched, float &score,
+                              const float (*given)[15] = nullptr, const bool use_given = false) {
   float coeff[4] = {0, 0, 0, 0};
   unsigned flag = 0;
   float4 nb[5];
@@ -41,8 +45,24 @@ LSLAM_DEV void point_residual(const SweepArgs &a, const BlockDesc &bd, const boo
   const bool gate = a.fine_gate_c >= 0.0f ? d[0] < (is_surf ? a.fine_gate_s : a.fine_gate_c) : d[4] < 5.0f;
   if (gate) {
     flag |= 1u;
+    bool fetch = true;
+    if constexpr (GIVEN) {
+      if (use_given) {
+        fetch = false;
 #pragma unroll
-    for (int j = 0; j < 5; ++j) nb[j] = P[p[j]];
+        for (int j = 0; j < 5; ++j) {
+          // (through an empty asm: two arms that both end in plain loads are merged into ONE load through a pointer chosen
+          // between `given` and P -- and `given` then lives in scratch memory instead of registers)
+          float gx = (*given)[3 * j], gy = (*given)[3 * j + 1], gz = (*given)[3 * j + 2];
+          asm("" : "+v"(gx), "+v"(gy), "+v"(gz));
+          nb[j] = make_float4(gx, gy, gz, 0.0f);
+        }
+      }
+    }
+    if (!GIVEN || fetch) {
+#pragma unroll
+      for (int j = 0; j < 5; ++j) nb[j] = P[p[j]];
+    }
     if (!is_surf) {
       float A[3], B[3];
       if (find_line(nb, A, B)) {  // ScanMatch.cpp:105-112

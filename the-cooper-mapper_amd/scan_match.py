@@ -144,6 +144,10 @@ class Context:
         """lslam_debug_grid_launches: grid sweeps (sweep_grid_kernel) this context has launched so far."""
         return int(self.lib.lslam_debug_grid_launches(self.h))
 
+    def grid_lean_launches(self):
+        """lslam_debug_grid_lean_launches: ... of which with the lean instantiation (the production loop's launch)."""
+        return int(self.lib.lslam_debug_grid_lean_launches(self.h))
+
     def grid_wide_launches(self):
         """lslam_debug_grid_wide_launches: ... of which in the single-launch form of a map without trees."""
         return int(self.lib.lslam_debug_grid_wide_launches(self.h))
