@@ -220,6 +220,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed; new entry points and a struct of their own (lslam_kfs_*: the keyframe store). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_sc_*: loop candidates by appearance). */
 /* still 7: no struct changed; new entry points and an enum (lslam_pg_set_robust_kernels, _edge_robust, _robust_info, _kernel_from_name: robust kernels on pose-graph edges; lslam_pg_stream). */
+/* still 7: no struct changed; new entry points and a struct of their own (lslam_match_information, lslam_keyframe_edge_information, lslam_sizeof_edge_info: the match Hessian of a pose-graph edge). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -630,6 +631,61 @@ int lslam_kfs_scanmatch(lslam_kfs *kfs, int32_t id, float leaf_corner, float lea
                         lslam_stats *stats);
 /* lslam_fmap_add_feature_cloud with the keyframe's clouds taken from the store (fm: a feature map of the store's ctx). */
 int lslam_kfs_add_to_fmap(lslam_kfs *kfs, int32_t id, lslam_fmap *fm, const float T[16]);
+
+/* ---- edge information: the match Hessian of a pose-graph edge, in fp64 --------------------------------------------------------
+ * Not in the reference: pose_graph/information_estimator.hpp returns the identity (its //@ todo), and graph.cpp:279-288,333-339
+ * weight every edge with a constant.  These entry points give the Gauss-Newton normal matrix of a scan match at the pose it
+ * returned, in the coordinates of the pose graph's edge error, so that an edge can be trusted in the directions its match
+ * observed.  This comment is the specification (restated in numpy by tests/edge_information_ref.py).
+ *
+ * INPUT.  One sweep (lslam_sweep_ex with the search of `search_mode`, LSLAM_SEARCH_* without the LSLAM_SWEEP_* bits) over the
+ * resident single scan at `pose` leaves, per scan point k (corner points, then surf points), coeff_k = (w*n | w*d) and flags_k
+ * on the device.  p_k is the scan point in the sensor frame, R[i][j] = (double)T[4*i + j] of lslam_pose_to_isometry(pose, T).
+ *
+ * ROW, for every k with flags_k & 4 (row kept), in fp64 from the fp32 inputs, every product and sum rounded on its own (no FMA)
+ * in the order written:
+ *   c = (double)coeff_k.xyz          m_j = (R[0][j]*c_0 + R[1][j]*c_1) + R[2][j]*c_2          (m = R^T c)
+ *   x = p_k x m:  x_0 = p_1*m_2 - p_2*m_1,  x_1 = p_2*m_0 - p_0*m_2,  x_2 = p_0*m_1 - p_1*m_0
+ *   J_k = [ m_0 m_1 m_2 | 2 x_0  2 x_1  2 x_2 ]     order [t, q]          b_k = (double)coeff_k.w
+ * J_k is the derivative at delta = 0 of the weighted residual c . (T * fromVectorMQT(delta) * p_k): the perturbation on the
+ * RIGHT, delta_q the vector part of the unit quaternion (hence the 2).  With the measurement Z = T the error of an lslam_pg_*
+ * edge, toVectorMQT(Z^-1 X_i^-1 X_j), is delta itself: H = sum_k J_k^T J_k is the information of that error up to the noise
+ * scale (H / sigma^2 for residuals of standard deviation sigma).  No Euler Jacobian: nothing is singular at ry = +-90 degrees.
+ *
+ * SUMS.  H (21 upper-triangular entries, mirrored into the 36), sum_b2 = sum_k b_k^2, n_rows = rows kept, n_line / n_plane =
+ * corner / surf points with flags_k & 2 (a line / plane was fitted: the sweep's own counters).  All accumulation is fp64 in a
+ * FIXED order -- each lane serially over its points (point i of the context's ordered scan belongs to lane i mod (lanes of the
+ * launch)), a butterfly over the wavefront, the wavefronts of a workgroup in order, the workgroups' partials in workgroup order
+ * by one final workgroup; no floating-point atomics -- so two calls give the same bits.  Each entry lies within
+ * (n_rows + 2) * 2^-53 * sum_k |J_ka J_kb| of the exact sum.
+ *
+ * EIGEN-DECOMPOSITION, on the host: cyclic Jacobi in fp64 on the symmetric 6x6.  eig ascending; evec row i is the unit
+ * eigenvector of eig[i].
+ *
+ * lslam_match_information: the resident map and the resident single scan; one sweep with the taps left on the device (no
+ * per-point data crosses PCIe), the reduction, one download of 25 numbers.  Errors as lslam_sweep_ex (LSLAM_ERR_NO_MAP,
+ * _NO_SCAN, _INVALID for a NULL argument, a batch of scans or an unknown search mode); *out is zeroed first.  No kept rows
+ * (an empty scan included): LSLAM_OK with H = 0, eig = 0, evec = identity. */
+typedef struct {
+  double H[36];        /* row-major, symmetric, order [t, q] */
+  double eig[6];       /* ascending */
+  double evec[36];     /* row i = eigenvector of eig[i] */
+  double sum_b2;
+  int32_t n_rows, n_line, n_plane;
+} lslam_edge_info;
+size_t lslam_sizeof_edge_info(void);
+int lslam_match_information(lslam_ctx *ctx, const float pose[6], int32_t search_mode, lslam_edge_info *out);
+/* The information of an edge between stored keyframes.  The reference is built exactly as lslam_kfs_loop_match builds it: the
+ * local clouds of keyframes ref_ids under rel_T (1 <= n_ref <= 6; lslam_kfs_debug_local_clouds), lslam_voxel_grid with
+ * leaf_ref_corner / leaf_ref_surf over them and leaf_corner / leaf_surf over keyframe new_id's clouds, lslam_map_set and
+ * lslam_scan_set on the device, then lslam_match_information(lslam_isometry_to_pose(T), LSLAM_SEARCH_AUTO): same kernels in
+ * the same order as those calls, same bits.  T: new_id's pose in ref_ids[0]'s frame (row-major 4x4), the edge's measurement.
+ * A filtered reference with no corner or no surf point: LSLAM_OK with *out zero (nothing to match against).  The ctx's map and
+ * resident scan belong to the call afterwards.  (Named apart from lslam_kfs_*: that prefix is the store's own, closed set of
+ * entry points -- this one is a consumer of the store, as lslam_sc_* are.) */
+int lslam_keyframe_edge_information(lslam_kfs *kfs, int32_t n_ref, const int32_t *ref_ids, const float *rel_T, int32_t new_id,
+                               const float T[16], float leaf_ref_corner, float leaf_ref_surf, float leaf_corner, float leaf_surf,
+                               lslam_edge_info *out);
 
 /* ---- loop candidates by appearance: scan context over the keyframe store ----------------------------------------------------
  * Not in the reference: its LoopDetector only looks where the drifted estimate puts the vehicle (a sqrt(5) m radius search), so

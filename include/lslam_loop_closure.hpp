@@ -211,6 +211,10 @@ struct Loop {
   typedef std::shared_ptr<Loop> Ptr;
   KeyFrame::Ptr key1, key2;
   Mat4d relative_pose;
+  // the store ids and transforms (16 floats each) of the keyframes whose local clouds the verification matched against; empty
+  // where the keyframes are not in a store -- what Graph::edge_information = "hessian" builds the edge's match Hessian from
+  std::vector<int32_t> ref_ids;
+  std::vector<float> rel_T;
 };
 
 // keyframe_updater.hpp:10-60
@@ -343,6 +347,8 @@ public:
         lp->key1 = cand;
         lp->key2 = nk;
         lp->relative_pose = from_float16(guess);
+        lp->ref_ids.assign(1, ids[i]);
+        lp->rel_T.assign(rel, rel + 16);
         detected_loops.push_back(lp);
         loop_count++;
         loop_found = true;
@@ -479,6 +485,8 @@ private:
     lp->key1 = candidates[0];
     lp->key2 = nk;
     lp->relative_pose = from_float16(guess);
+    lp->ref_ids = ids;
+    lp->rel_T = rel;
     return lp;
   }
   static void append_transformed(const std::vector<float> &c, const float T[16], std::vector<float> &out) {
@@ -554,7 +562,23 @@ public:
       _err = "Graph: loop_robust_kernel_size must be finite and > 0";
       return -1;
     }
-    if (!flush_keyframe_queue()) return 0;
+    const bool hessian = edge_information == "hessian";
+    if (!hessian && edge_information != "NONE") {
+      _err = "Graph: unknown edge_information " + edge_information + " (NONE, hessian)";
+      return -1;
+    }
+    if (hessian && !(std::isfinite(range_sigma) && range_sigma > 0.0)) {
+      _err = "Graph: edge_information = hessian needs range_sigma, the sensor's range noise [m]";
+      return -1;
+    }
+    if (hessian && !store) {
+      _err = "Graph: edge_information = hessian needs a resident graph";
+      return -1;
+    }
+    _edge_failed = false;
+    const bool flushed = flush_keyframe_queue();
+    if (_edge_failed) return -1;
+    if (!flushed) return 0;
     std::vector<Loop::Ptr> found;
     std::deque<KeyFrame::Ptr> nk(new_keyframes.begin(), new_keyframes.end());
     if (loop_source) loop_source(keyframes, nk, found);
@@ -570,8 +594,16 @@ public:
     }
     static const double LOOP_INFO[6] = {2, 2, 2, 2, 2, 2};  // graph.cpp:333-339
     for (const auto &lp : found) {
+      double full[36];
+      if (hessian) {
+        if (lp->ref_ids.empty()) {
+          _err = "Graph: edge_information = hessian needs loops verified in the keyframe store";
+          return -1;
+        }
+        if (!hessian_information(LOOP_INFO, lp->ref_ids, lp->rel_T, lp->key2->store_id, lp->relative_pose, full)) return -1;
+      }
       _loop_edges.push_back((int)(_ij.size() / 2));
-      add_edge(lp->key1->node, lp->key2->node, lp->relative_pose, LOOP_INFO, loop_kind, loop_robust_kernel_size);
+      add_edge(lp->key1->node, lp->key2->node, lp->relative_pose, LOOP_INFO, loop_kind, loop_robust_kernel_size, hessian ? full : nullptr);
     }
     loops.insert(loops.end(), found.begin(), found.end());
     keyframes.insert(keyframes.end(), new_keyframes.begin(), new_keyframes.end());
@@ -700,6 +732,19 @@ public:
   double loop_robust_kernel_size = 1.0;
   // the robust weight of every entry of `loops` after the last optimisation (all 1 without a kernel)
   const std::vector<double> &loopWeights() const { return _loop_weights; }
+  // Data-driven edge information (not in the reference, whose InformationEstimator returns the identity): "NONE" (default:
+  // graph.cpp's constants) or "hessian" -- every edge added from now on gets
+  //   Omega = Omega_ref + H / max(sum_b2 / (n_rows - 6), range_sigma^2),        Omega_ref alone below 50 rows (ScanMatch.cpp:142)
+  // with H, sum_b2, n_rows the fp64 match Hessian of the edge's two keyframes at its measurement (lslam_keyframe_edge_information:
+  // odometry edges against the previous keyframe, loop edges against the keyframes their verification used; leaves 0.2 / 0.4 /
+  // 0.2 / 0.4 as scanMatchLocal) and Omega_ref graph.cpp's constant for the edge type, a weak prior: Omega stays positive
+  // definite, and a direction the match did not observe keeps exactly the reference's weight.  Needs a resident graph and
+  // range_sigma [m], the range noise of the caller's sensor -- no default: the library does not guess it.
+  std::string edge_information = "NONE";
+  double range_sigma = 0.0;
+  // the lslam_edge_info of every edge in edge order (edge_information = "hessian" only), and every edge's 6x6 information
+  const std::vector<lslam_edge_info> &edgeInformations() const { return _edge_infos; }
+  const std::vector<double> &informationMatrices() const { return _info; }
   // Where the loops come from, when set: called by optimize() instead of loop_detector's detect_nearest / detect_appearance
   // with (keyframes, new keyframes, loops out).  The counterpart of the Python Graph's loop_detector argument: a node that has
   // its own place recognition, or a test with prepared loops, hands them over here.
@@ -747,7 +792,16 @@ private:
       _poses.insert(_poses.end(), p7, p7 + 7);
       if (i == 0 && keyframes.empty()) continue;
       const KeyFrame::Ptr &prev = i == 0 ? keyframes.back() : keyframe_queue[(size_t)i - 1];
-      add_edge(prev->node, kf->node, inverse(prev->odom) * kf->odom, ODOM_INFO);
+      const Mat4d relative = inverse(prev->odom) * kf->odom;
+      double full[36];
+      const bool hessian = edge_information == "hessian";
+      if (hessian) {  // the previous keyframe is the reference, the edge's measurement the pose
+        static const float EYE[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        if (!hessian_information(ODOM_INFO, std::vector<int32_t>(1, prev->store_id), std::vector<float>(EYE, EYE + 16), kf->store_id,
+                                 relative, full))
+          _edge_failed = true;
+      }
+      add_edge(prev->node, kf->node, relative, ODOM_INFO, LSLAM_PG_KERNEL_NONE, 1.0, hessian && !_edge_failed ? full : nullptr);
     }
     keyframe_queue.erase(keyframe_queue.begin(), keyframe_queue.begin() + n);
     return true;
@@ -790,7 +844,31 @@ private:
     for (size_t k = 0; k < _loop_edges.size(); ++k) _loop_weights.push_back(w[(size_t)_loop_edges[k]]);
     return LSLAM_OK;
   }
-  void add_edge(int a, int b, const Mat4d &rel, const double diag_info[6], int kind = LSLAM_PG_KERNEL_NONE, double delta = 1.0) {
+  // One edge's information under edge_information = "hessian" (the formula at that member; sums that are not finite -- a scan
+  // point exactly on its line is a 0 / 0 in the reference's coefficient -- count as no match); its lslam_edge_info is kept.
+  bool hessian_information(const double diag_ref[6], const std::vector<int32_t> &ref_ids, const std::vector<float> &rel_T, int new_id,
+                           const Mat4d &T, double out[36]) {
+    float Tf[16];
+    to_float16(T, Tf);
+    lslam_edge_info ei;
+    if (lslam_keyframe_edge_information(store->handle(), (int32_t)ref_ids.size(), ref_ids.data(), rel_T.data(), new_id, Tf, 0.2f, 0.4f, 0.2f,
+                                   0.4f, &ei) < 0) {
+      _err = lslam_last_error();
+      return false;
+    }
+    _edge_infos.push_back(ei);
+    bool use = ei.n_rows >= 50 && std::isfinite(ei.sum_b2);
+    for (int k = 0; k < 36; ++k) use = use && std::isfinite(ei.H[k]);
+    const double s2 = use ? std::max(ei.sum_b2 / (double)(ei.n_rows - 6), range_sigma * range_sigma) : 1.0;
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) {
+        const double ref = r == c ? diag_ref[r] : 0.0;
+        out[r * 6 + c] = use ? ref + ei.H[r * 6 + c] / s2 : ref;
+      }
+    return true;
+  }
+  void add_edge(int a, int b, const Mat4d &rel, const double diag_info[6], int kind = LSLAM_PG_KERNEL_NONE, double delta = 1.0,
+                const double *full_info = nullptr) {
     _kind.push_back(kind);
     _delta.push_back(delta);
     _ij.push_back(a);
@@ -799,7 +877,7 @@ private:
     mat_to_pose7(rel, p7);
     _meas.insert(_meas.end(), p7, p7 + 7);
     for (int r = 0; r < 6; ++r)
-      for (int c = 0; c < 6; ++c) _info.push_back(r == c ? diag_info[r] : 0.0);
+      for (int c = 0; c < 6; ++c) _info.push_back(full_info ? full_info[r * 6 + c] : (r == c ? diag_info[r] : 0.0));
   }
   lslam_ctx *_ctx;
   int _device, _max_per_update;
@@ -810,6 +888,8 @@ private:
   std::vector<double> _delta;
   std::vector<int> _loop_edges;  // edge index of every entry of `loops`
   std::vector<double> _loop_weights;
+  std::vector<lslam_edge_info> _edge_infos;
+  bool _edge_failed = false;
   std::string _err;
 };
 

@@ -228,6 +228,18 @@ class LslamSurveyStats(C.Structure):
                                          "label_sweeps", "planar_points", "boundary_points", "n_corner", "n_surf")]
 
 
+class LslamEdgeInfo(C.Structure):
+    """lslam_edge_info (include/lslam_c.h): the match Hessian of a pose-graph edge, order [t, q]."""
+    _fields_ = [("H", C.c_double * 36), ("eig", C.c_double * 6), ("evec", C.c_double * 36), ("sum_b2", C.c_double),
+                ("n_rows", C.c_int32), ("n_line", C.c_int32), ("n_plane", C.c_int32)]
+
+    def as_dict(self):
+        import numpy as np
+        return dict(H=np.array(self.H, np.float64).reshape(6, 6), eig=np.array(self.eig, np.float64),
+                    evec=np.array(self.evec, np.float64).reshape(6, 6), sum_b2=float(self.sum_b2), n_rows=int(self.n_rows),
+                    n_line=int(self.n_line), n_plane=int(self.n_plane))
+
+
 class LslamKfsStats(C.Structure):
     """lslam_kfs_stats (include/lslam_c.h)."""
     _fields_ = [("n_keyframes", C.c_int64), ("n_points", C.c_uint64 * 2), ("n_slabs", C.c_int64), ("bytes_held", C.c_uint64),
@@ -377,6 +389,10 @@ SYMBOLS = {
     "lslam_kfs_scanmatch": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, c_float_p, C.POINTER(LslamOpts),
                                       C.POINTER(LslamStats)]),
     "lslam_kfs_add_to_fmap": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, c_float_p]),
+    "lslam_sizeof_edge_info": (C.c_size_t, []),
+    "lslam_match_information": (C.c_int, [C.c_void_p, c_float_p, C.c_int32, C.POINTER(LslamEdgeInfo)]),
+    "lslam_keyframe_edge_information": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, C.c_int32, c_float_p, C.c_float, C.c_float,
+                                             C.c_float, C.c_float, C.POINTER(LslamEdgeInfo)]),
     "lslam_sc_default_params": (None, [C.POINTER(LslamScParams)]),
     "lslam_sc_setup": (C.c_int, [C.c_void_p, C.POINTER(LslamScParams)]),
     "lslam_sc_descriptor": (C.c_int, [C.c_void_p, C.c_int32, c_float_p]),

@@ -185,6 +185,8 @@ struct lslam_ctx {
   DevBuf<uint8_t> t_flags;
   DevBuf<float4> t_q;
   DevBuf<float> t_small;  // AtA/Atb upload for the gn_step tap
+  DevBuf<double> info_sums;  // lslam_match_information: [workgroup partials | the 25 sums]
+  PinBuf<double> h_info;     // ... the sums on the host
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> sweep_ev;
   int iter_hint = 4;  // size of the first batch of enqueued GN iterations
@@ -2975,8 +2977,10 @@ int lslam_scanmatch_batch(lslam_ctx *ctx, int32_t n_problems, float *poses, cons
   return lslam_scanmatch_run_batch(ctx, n_problems, poses, opts, stats);
 }
 
-int lslam_sweep_ex(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, int32_t search_mode, int32_t *idx_out,
-                   float *d2_out, float *coeff_out, uint8_t *flags_out, float *sums_out) {
+// lslam_sweep_ex; keep_taps: the taps are written (ctx->t_idx / t_d2 / t_coeff / t_flags) also when no output asks for them --
+// lslam_match_information reads them where they are
+static int sweep_ex_impl(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, int32_t search_mode, int32_t *idx_out,
+                         float *d2_out, float *coeff_out, uint8_t *flags_out, float *sums_out, bool keep_taps) {
   int rc = check_ctx(ctx);
   if (rc) return rc;
   if (!ctx->have_map) { set_err("no map set"); return LSLAM_ERR_NO_MAP; }
@@ -3040,7 +3044,7 @@ int lslam_sweep_ex(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, int32_
       ctx->grid_state_valid = true;  // what this sweep leaves is the state the next sweep of the loop would find
     }
   }
-  const bool taps = idx_out || d2_out || coeff_out || flags_out;
+  const bool taps = keep_taps || idx_out || d2_out || coeff_out || flags_out;
   if (taps) {
     HIP_TRY(ctx->t_idx.reserve(N * 5 + 1));
     HIP_TRY(ctx->t_d2.reserve(N * 5 + 1));
@@ -3074,6 +3078,98 @@ int lslam_sweep_ex(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, int32_
     sums_out[28] = (float)(g.sums[COL_LINE] + g.sums[COL_PLANE]);
     sums_out[29] = (float)g.sums[COL_SCORE];
   }
+  return LSLAM_OK;
+}
+
+int lslam_sweep_ex(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, int32_t search_mode, int32_t *idx_out,
+                   float *d2_out, float *coeff_out, uint8_t *flags_out, float *sums_out) {
+  return sweep_ex_impl(ctx, pose, jtj_mode, search_mode, idx_out, d2_out, coeff_out, flags_out, sums_out, false);
+}
+
+size_t lslam_sizeof_edge_info(void) { return sizeof(lslam_edge_info); }
+
+// Cyclic Jacobi on a symmetric 6x6 in fp64 (include/lslam_c.h, "edge information"): eig ascending, evec row i its eigenvector.
+static void jacobi6(const double H[36], double eig[6], double evec[36]) {
+  double A[6][6], V[6][6];
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j) {
+      A[i][j] = H[i * 6 + j];
+      V[i][j] = i == j ? 1.0 : 0.0;
+    }
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    double off = 0.0, diag = 0.0;
+    for (int i = 0; i < 6; ++i) {
+      diag += A[i][i] * A[i][i];
+      for (int j = i + 1; j < 6; ++j) off += A[i][j] * A[i][j];
+    }
+    if (off == 0.0 || off <= 1e-40 * diag) break;
+    for (int p = 0; p < 5; ++p)
+      for (int q = p + 1; q < 6; ++q) {
+        if (A[p][q] == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < 6; ++k) {  // A <- A G
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq;
+          A[k][q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < 6; ++k) {  // A <- G^T A
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - s * aqk;
+          A[q][k] = s * apk + c * aqk;
+        }
+        A[p][q] = A[q][p] = 0.0;
+        for (int k = 0; k < 6; ++k) {  // V <- V G: the columns are the eigenvectors
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq;
+          V[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+  int order[6] = {0, 1, 2, 3, 4, 5};
+  std::stable_sort(order, order + 6, [&](int a, int b) { return A[a][a] < A[b][b]; });
+  for (int i = 0; i < 6; ++i) {
+    eig[i] = A[order[i]][order[i]];
+    for (int k = 0; k < 6; ++k) evec[i * 6 + k] = V[k][order[i]];
+  }
+}
+
+int lslam_match_information(lslam_ctx *ctx, const float pose[6], int32_t search_mode, lslam_edge_info *out) {
+  if (out) std::memset(out, 0, sizeof(*out));
+  if (!ctx || !pose || !out) {
+    set_err("lslam_match_information: null ctx, pose or out");
+    return LSLAM_ERR_INVALID;
+  }
+  if ((search_mode & ~(0xFF | LSLAM_STACK_DEEP | LSLAM_STACK_SHALLOW)) || (search_mode & 0xFF) > LSLAM_SEARCH_GRID) {
+    set_err("lslam_match_information: search_mode is LSLAM_SEARCH_* ORed with LSLAM_STACK_*");
+    return LSLAM_ERR_INVALID;
+  }
+  int rc = sweep_ex_impl(ctx, pose, 1, search_mode, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+  if (rc) return rc;
+  const size_t N = ctx->n_points;
+  float T[16];
+  lslam_pose_to_isometry(pose, T);
+  double R[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) R[i * 3 + j] = (double)T[i * 4 + j];
+  // [partials | the 25 sums] in the exchange buffer's place: doubles, grow-only
+  const size_t n_part = info_partial_doubles(N);
+  HIP_TRY(ctx->info_sums.reserve(n_part + INFO_NOUT));
+  double *d_out = ctx->info_sums.p + n_part;
+  HIP_TRY(launch_match_information(ctx->q.p, (int)N, ctx->nqc[0], ctx->t_coeff.p, ctx->t_flags.p, R, ctx->info_sums.p, d_out, ctx->stream));
+  HIP_TRY(ctx->h_info.reserve(INFO_NOUT));
+  HIP_TRY(hipMemcpyAsync(ctx->h_info.p, d_out, INFO_NOUT * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const double *h = ctx->h_info.p;
+  int k = 0;
+  for (int r = 0; r < 6; ++r)
+    for (int c = r; c < 6; ++c, ++k) out->H[r * 6 + c] = out->H[c * 6 + r] = h[k];
+  out->sum_b2 = h[21];
+  out->n_rows = (int32_t)h[22];
+  out->n_line = (int32_t)h[23];
+  out->n_plane = (int32_t)h[24];
+  jacobi6(out->H, out->eig, out->evec);
   return LSLAM_OK;
 }
 

@@ -540,6 +540,15 @@ size_t small_sort_tmp_bytes(size_t n);
 hipError_t small_sort_pairs(hipStream_t s, const uint64_t *k_in, uint64_t *k_out, const uint32_t *v_in, uint32_t *v_out, size_t n,
                             void *tmp);
 
+// lslam_info.hip: the tangent-space normal matrix of a match in fp64 (include/lslam_c.h, "edge information").  q: the ordered
+// single resident scan (n points, the first n_corner of them corner points, .w the caller's index within its type), coeff /
+// flags: a sweep's taps in the caller's order, R: row-major rotation.  partials: info_partial_doubles(n) doubles of scratch;
+// out25: [21 upper-triangular H | sum_b2 | n_rows | n_line | n_plane] (the counts as doubles, exact).  Enqueued, not waited for.
+constexpr int INFO_NOUT = 25;
+size_t info_partial_doubles(size_t n);
+hipError_t launch_match_information(const float4 *q, int n, int n_corner, const float4 *coeff, const uint8_t *flags, const double R[9],
+                                    double *partials, double *out25, hipStream_t s);
+
 // lslam_scanprep.hip: Morton ordering of the resident scans on the device
 hipError_t scanprep_order(lslam_ctx *ctx, const float4 *h_pts, size_t n, const int32_t *h_seg_off, int nseg, float4 *d_out);
 }  // namespace lslam

@@ -482,6 +482,66 @@ int lslam_kfs_loop_match(lslam_kfs *k, int32_t n_cand, const int32_t *ids, const
   return LSLAM_OK;
 }
 
+int lslam_keyframe_edge_information(lslam_kfs *k, int32_t n_ref, const int32_t *ref_ids, const float *rel_T, int32_t new_id,
+                               const float T[16], float leaf_ref_corner, float leaf_ref_surf, float leaf_corner, float leaf_surf,
+                               lslam_edge_info *out) {
+  if (out) std::memset(out, 0, sizeof(*out));
+  if (!k || !out || !T) {
+    lslam::set_error("lslam_keyframe_edge_information: null store, pose or out");
+    return LSLAM_ERR_INVALID;
+  }
+  const float leaf[4] = {leaf_ref_corner, leaf_ref_surf, leaf_corner, leaf_surf};
+  for (int c = 0; c < 4; ++c)
+    if (!(leaf[c] > 0.0f)) {
+      lslam::set_error("lslam_keyframe_edge_information: a leaf that is not positive");
+      return LSLAM_ERR_INVALID;
+    }
+  int rc = check_kfs(k, "lslam_keyframe_edge_information");
+  if (rc) return rc;
+  rc = check_id(k, "lslam_keyframe_edge_information", new_id);
+  if (rc) return rc;
+  rc = assemble(k, "lslam_keyframe_edge_information", n_ref, ref_ids, rel_T);
+  if (rc) {
+    (void)hipStreamSynchronize(k->stream);
+    return rc;
+  }
+  const KeyframeClouds nk = k->kfs[(size_t)new_id];
+  // ---- the reference and the scan as lslam_kfs_loop_match's scanMatchLocal makes them ----------------------------------------
+  float lo[2][3], hi[2][3];
+  {
+    const float4 *bp[2] = {k->local[0].p, k->local[1].p};
+    const int bn[2] = {(int)k->n_local[0], (int)k->n_local[1]};
+    KFS_TRY(lslam::grid_bbox2(bp, bn, k->d_box.p, lo, hi, k->stream));
+  }
+  const float4 *in[4] = {k->local[0].p, k->local[1].p, nk.p[0], nk.p[1]};
+  const size_t n_in[4] = {k->n_local[0], k->n_local[1], nk.n[0], nk.n[1]};
+  const float *blo[4] = {lo[0], lo[1], nk.lo[0], nk.lo[1]}, *bhi[4] = {hi[0], hi[1], nk.hi[0], nk.hi[1]};
+  size_t m[4] = {0, 0, 0, 0};
+  for (int c = 0; c < 4; ++c) {
+    KFS_TRY(k->filt[c].reserve(n_in[c] ? n_in[c] : 1));
+    rc = lslam::voxel_grid_device(k->ctx, in[c], n_in[c], blo[c], bhi[c], leaf[c], k->filt[c].p, &m[c]);
+    if (rc) {
+      (void)hipStreamSynchronize(k->stream);
+      return rc;
+    }
+  }
+  if (m[0] == 0 || m[1] == 0) {  // nothing to match against: *out stays zero
+    KFS_TRY(hipStreamSynchronize(k->stream));
+    return LSLAM_OK;
+  }
+  for (int t = 0; t < 2; ++t) {
+    rc = index_cloud(k, k->filt[t].p, m[t], k->indexed[t]);
+    if (rc) return rc;
+  }
+  rc = lslam::map_set_device(k->ctx, k->indexed[0].p, m[0], k->indexed[1].p, m[1]);
+  if (rc) return rc;
+  rc = lslam::scan_set_device(k->ctx, k->filt[2].p, m[2], k->filt[3].p, m[3]);
+  if (rc) return rc;
+  float pose[6];
+  lslam_isometry_to_pose(T, pose);
+  return lslam_match_information(k->ctx, pose, LSLAM_SEARCH_AUTO, out);
+}
+
 int lslam_kfs_scanmatch(lslam_kfs *k, int32_t id, float leaf_corner, float leaf_surf, float pose[6], const lslam_opts *opts,
                         lslam_stats *stats) {
   if (stats) std::memset(stats, 0, sizeof(*stats));

@@ -56,12 +56,30 @@ class KeyframeUpdater:
 # graph.cpp:279-288 and :333-339
 ODOMETRY_INFORMATION = np.diag([0.8, 0.4, 0.8, 1.0, 2.0, 1.0])
 LOOP_INFORMATION = 2.0 * np.eye(6)
+# ScanMatch.cpp:142: the reference's floor for a usable match; below it an edge keeps the reference's constant
+EDGE_INFORMATION_MIN_ROWS = 50
+# scanMatchLocal's leaves (ScanMatch.cpp:29-30): reference corner / surf, new corner / surf
+EDGE_INFORMATION_LEAVES = (0.2, 0.4, 0.2, 0.4)
+
+
+def hessian_information(omega_ref, H, sum_b2, n_rows, range_sigma):
+    """The information of an edge from its match Hessian (``lslam_edge_info``; DESIGN, pose-graph section):
+    ``omega_ref + H / max(sum_b2 / (n_rows - 6), range_sigma^2)``, and ``omega_ref`` alone below 50 rows.  ``omega_ref`` --
+    the reference's constant for the edge type -- acts as a weak prior: the result is positive definite whatever the match
+    saw, and a direction the match did not observe keeps exactly the reference's weight."""
+    omega_ref = np.asarray(omega_ref, np.float64)
+    H = np.asarray(H, np.float64).reshape(6, 6)
+    # (a scan point exactly on its line gives the reference's coefficient a 0 / 0, ScanMatch.cpp:160-170: such sums say nothing)
+    if n_rows < EDGE_INFORMATION_MIN_ROWS or not (np.isfinite(H).all() and np.isfinite(sum_b2)):
+        return omega_ref.copy()
+    s2 = max(float(sum_b2) / float(n_rows - 6), float(range_sigma) * float(range_sigma))
+    return omega_ref + H / s2
 
 
 class Graph:
     def __init__(self, device=0, ctx=None, loop_detector=None, max_keyframes_per_update=10, resident=False,
                  keep_host_clouds=True, store_max_points=0, store_max_keyframes=0, store_slab_points=0, appearance_loops=False,
-                 sc_params=None, loop_robust_kernel=None, loop_robust_delta=1.0):
+                 sc_params=None, loop_robust_kernel=None, loop_robust_delta=1.0, edge_information=None, range_sigma=None):
         """``resident=True``: the keyframes' clouds live in a :class:`KeyframeStore` on the loop detector's context --
         ``add_frame`` uploads them once (``kf.store_id``), loop closure and ``get_final_feature_map`` read them there;
         ``keep_host_clouds=False`` then drops the host copies (``kf.corner_cloud`` / ``kf.surf_cloud`` fetch on demand).
@@ -75,7 +93,22 @@ class Graph:
         :meth:`loop_weights`, :meth:`rejected_loops`.  The default stays None (every edge at full weight, the reference's
         behaviour); switching a kernel on is the caller's decision.  Huber is convex and CANNOT reject an outlier, it only
         bounds its pull: on graphs with this node's weak odometry information the trajectory still bends to meet a false loop
-        (DESIGN, pose-graph section); Cauchy (0.1) and DCS (1) do reject."""
+        (DESIGN, pose-graph section); Cauchy (0.1) and DCS (1) do reject.
+        ``edge_information="hessian"`` (not in the reference, whose InformationEstimator returns the identity; needs
+        ``resident=True`` and ``range_sigma``): every edge's information is the reference's constant plus the fp64 match Hessian
+        of the two keyframes at the edge's measurement (``lslam_keyframe_edge_information``) over the residual variance, floored at
+        ``range_sigma``^2 -- :func:`hessian_information`.  ``range_sigma`` [m] is the range noise of the caller's sensor and
+        has no default: the library does not guess it.  None (the default) changes nothing."""
+        if edge_information not in (None, "hessian"):
+            raise ValueError("Graph: edge_information is None or \"hessian\"")
+        if edge_information == "hessian":
+            if range_sigma is None or not float(range_sigma) > 0.0:
+                raise ValueError("Graph: edge_information=\"hessian\" needs range_sigma, the sensor's range noise [m]")
+            if not (resident or appearance_loops):
+                raise ValueError("Graph: edge_information=\"hessian\" needs resident=True")
+        self.edge_information = edge_information
+        self.range_sigma = None if range_sigma is None else float(range_sigma)
+        self.edge_infos = []  # the lslam_edge_info of every solver edge, in edge order (edge_information="hessian" only)
         self.loop_robust_kernel = loop_robust_kernel if kernel_kind(loop_robust_kernel) else None
         self.loop_robust_delta = float(loop_robust_delta)
         self.solver = PoseGraph(device)
@@ -126,9 +159,26 @@ class Graph:
                 continue
             prev = self.keyframes[-1] if i == 0 else self.keyframe_queue[i - 1]
             relative = np.linalg.inv(prev.odom) @ kf.odom
-            self.solver.add_se3_edge(prev.node, kf.node, relative, ODOMETRY_INFORMATION)
+            info = ODOMETRY_INFORMATION
+            if self.edge_information == "hessian":  # the previous keyframe is the reference, the edge's measurement the pose
+                info = self._hessian_information(ODOMETRY_INFORMATION, [prev.store_id], np.eye(4, dtype=np.float32)[None],
+                                                 kf.store_id, relative.astype(np.float32))
+            self.solver.add_se3_edge(prev.node, kf.node, relative, info)
         del self.keyframe_queue[:n]
         return True
+
+    def _hessian_information(self, omega_ref, ref_ids, rel_T, new_id, T):
+        """One edge's information under ``edge_information="hessian"``; its lslam_edge_info is kept for reporting."""
+        sm = self.loop_detector.scan_match
+        ei = self.store.edge_information(ref_ids, rel_T, new_id, T, EDGE_INFORMATION_LEAVES)
+        sm._resident, sm._resident_map = None, 0  # the context's map and scan belong to that call now
+        self.edge_infos.append(ei)
+        return hessian_information(omega_ref, np.array(ei.H, np.float64), ei.sum_b2, ei.n_rows, self.range_sigma)
+
+    def edge_informations(self):
+        """The ``lslam_edge_info`` (:class:`LslamEdgeInfo`) of every edge, in the solver's edge order, for reporting; empty
+        without ``edge_information="hessian"``."""
+        return list(self.edge_infos)
 
     # one pass of the loop in graph.cpp:313-383
     def optimize(self, max_iterations=1000):
@@ -141,8 +191,13 @@ class Graph:
             loops = loops + self.loop_detector.detect_appearance(self.keyframes,
                                                                  [k for k in self.new_keyframes if id(k) not in closed])
         for lp in loops:
+            info = LOOP_INFORMATION
+            if self.edge_information == "hessian":
+                if lp.ref_ids is None:
+                    raise ValueError("Graph: edge_information=\"hessian\" needs loops verified in the keyframe store")
+                info = self._hessian_information(LOOP_INFORMATION, lp.ref_ids, lp.rel_T, lp.key2.store_id, lp.relative_pose)
             self.loop_edges.append(self.solver.add_se3_edge(lp.key1.node, lp.key2.node, lp.relative_pose.astype(np.float64),
-                                                            LOOP_INFORMATION, robust_kernel=self.loop_robust_kernel,
+                                                            info, robust_kernel=self.loop_robust_kernel,
                                                             robust_delta=self.loop_robust_delta))
         self.loops.extend(loops)
         self.keyframes.extend(self.new_keyframes)

@@ -150,6 +150,19 @@ class KeyframeStore:
                                                       C.byref(opts) if opts is not None else None, C.byref(st)))
         return Status(rc), p, st
 
+    def edge_information(self, ref_ids, rel_T, new_id, T, leaves=(0.2, 0.4, 0.2, 0.4)):
+        """``lslam_keyframe_edge_information``: the match Hessian of keyframe ``new_id`` at pose ``T`` (4x4, in ``ref_ids[0]``'s
+        frame) against the local clouds of ``ref_ids`` under ``rel_T`` -> :class:`LslamEdgeInfo`.  ``leaves``: reference
+        corner / surf, new corner / surf (scanMatchLocal's by default)."""
+        from .capi import LslamEdgeInfo
+        ids, R = self._candidates(ref_ids, rel_T)
+        Tf = np.ascontiguousarray(T, dtype=np.float32).reshape(16)
+        out = LslamEdgeInfo()
+        self._check(self.lib.lslam_keyframe_edge_information(self.h, len(ids), ids.ctypes.data_as(c_int32_p), _fp(R), int(new_id), _fp(Tf),
+                                                        float(leaves[0]), float(leaves[1]), float(leaves[2]), float(leaves[3]),
+                                                        C.byref(out)))
+        return out
+
     def add_to_fmap(self, kid, fmap, tf):
         """``FeatureMap.add_feature_cloud`` with the keyframe's clouds taken from the store."""
         T = np.ascontiguousarray(tf, dtype=np.float32).reshape(16)

@@ -70,9 +70,14 @@ class KeyFrame:
 class Loop:
     """loop_detector.hpp:18-48."""
 
-    def __init__(self, key1, key2, relative_pose):
+    def __init__(self, key1, key2, relative_pose, ref_ids=None, rel_T=None):
+        """``ref_ids`` / ``rel_T``: the store ids and transforms of the keyframes whose local clouds the verification matched
+        against (None where the keyframes are not in a store) -- what ``Graph(edge_information="hessian")`` builds the edge's
+        match Hessian from."""
         self.key1, self.key2 = key1, key2
         self.relative_pose = np.asarray(relative_pose, np.float32).reshape(4, 4)
+        self.ref_ids = None if ref_ids is None else [int(i) for i in ref_ids]
+        self.rel_T = None if rel_T is None else np.ascontiguousarray(rel_T, np.float32).reshape(-1, 4, 4)
 
 
 def transform_cloud(cloud, tf):
@@ -196,7 +201,7 @@ class LoopDetector:
                 if r["stage"] != LOOP_ACCEPTED:
                     continue
                 self.last_loop_accum_distance = nk.accum_distance
-                loops.append(Loop(cand, nk, r["guess"]))
+                loops.append(Loop(cand, nk, r["guess"], [int(cid)], np.eye(4, dtype=np.float32)[None]))
                 self.loop_count += 1
                 break
         return loops
@@ -294,4 +299,4 @@ class LoopDetector:
         if r["stage"] != LOOP_ACCEPTED:
             return None
         self.last_loop_accum_distance = new_keyframe.accum_distance
-        return Loop(candidate_keyframes[0], new_keyframe, r["guess"])
+        return Loop(candidate_keyframes[0], new_keyframe, r["guess"], [k.store_id for k in candidate_keyframes], rel)

@@ -490,6 +490,15 @@ class Context:
         self._check(self.lib.lslam_sweep_ex(self.h, _fp(p), jtj_mode, int(search_mode), None, None, None, None, _fp(sums)))
         return dict(sums=sums)
 
+    def match_information(self, pose, search_mode=0):
+        """``lslam_match_information``: the fp64 Gauss-Newton normal matrix of the resident scan against the resident map at
+        ``pose``, in the pose graph's edge coordinates ``[t, q]`` -> :class:`LslamEdgeInfo`."""
+        from .capi import LslamEdgeInfo
+        p = np.array(pose, dtype=np.float32).reshape(6)
+        out = LslamEdgeInfo()
+        self._check(self.lib.lslam_match_information(self.h, _fp(p), int(search_mode), C.byref(out)))
+        return out
+
     def gn_step(self, AtA, Atb, it, pose, matP, degenerate, dr=0.05, dt=0.05):
         AtA = np.ascontiguousarray(AtA, np.float32).reshape(36)
         Atb = np.ascontiguousarray(Atb, np.float32).reshape(6)
