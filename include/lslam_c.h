@@ -126,6 +126,14 @@ enum { LSLAM_AB_PERSISTENT_GN = 1, /* one resident scan: the whole Gauss-Newton 
                                       seven).  Same bits.  Measured on the headline, the two taken in turn in one session: 1.466 -
                                       1.475e10 with this switch or the library before it, 1.512 - 1.517e10 without: +3.0 %
                                       (profiles/r14_grid_lean.txt) */
+       LSLAM_AB_GRID_CUBIC = 512,  /* grid sweep: the first pass of a throughput-bound batch that AUTO sent to the grid sweep keeps
+                                      the cubic cell table instead of the x-subdivided one (each 0.6 m cell cut into S sub-cells
+                                      along x, the axis the rows run along, so that a bounded probe's rows are clipped to
+                                      2 rb + c / S instead of 2 rb + c; built once per map on first use, with its own
+                                      cell-sorted points).  Same five neighbours; a rare near-tie point may change passes, which
+                                      moves the last bits of the sums.  S: LSLAM_GRID_XSUB in the environment the context was
+                                      made in (1: off; above 1 explicit LSLAM_SEARCH_GRID calls take the fine tables too -- for
+                                      tests), default LSLAM_GRID_XSUB_DEFAULT of the build (profiles/r16_grid_xsub.txt) */
        LSLAM_AB_WIDE_NF_MARGIN = 16 /* a map without kd-trees: a point whose fifth and sixth distances are within 8 ulps of each
                                       other counts as undecidable too (as an exact tie does): the trees are built and the call
                                       repeated.  Off: such a pair is ordered by its exact fp32 distances -- nanoflann's order
@@ -1292,6 +1300,18 @@ void lslam_debug_sweep_launches(lslam_ctx *ctx, uint64_t counts[8]);
 uint64_t lslam_debug_grid_launches(lslam_ctx *ctx);
 /* ... of which those that took the lean instantiation (sweep_grid_kernel<256, false, false, true>: the production loop's launch) */
 uint64_t lslam_debug_grid_lean_launches(lslam_ctx *ctx);
+/* ... of which those whose first pass read the x-subdivided cell tables (LSLAM_AB_GRID_CUBIC), lean or general */
+uint64_t lslam_debug_grid_fine_launches(lslam_ctx *ctx);
+/* the x-subdivided tables of the resident map: out[0], out[1] sub-cells per cell used (corner, surf; lowered where the table's
+ * limits ask for it), out[2], out[3] their cells; build_ms (or null): host time of their one build.  All 0 while there are none
+ * (no call has wanted them, the trees are deferred, the switch is off). */
+void lslam_debug_grid_fine_info(lslam_ctx *ctx, uint64_t out[4], float *build_ms);
+/* Debug export of one of them (which_map 0: corner, 1: surf), after building it once more when `rebuild` is set: dims_out =
+ * {nx (sub-cells), ny, nz, sub-cells per cell}, geom_out = {org x, y, z, cell edge, inv_cx}, the first cap_cells words of
+ * cell_start[nx ny nz + 1], the first cap_pts cell-sorted points {x, y, z, bitcast(original index)}.  Any output may be null.
+ * Returns the number of points, or a negative LSLAM_ERR_* (LSLAM_ERR_INVALID: the map has no such table). */
+int lslam_debug_grid_fine_table(lslam_ctx *ctx, int which_map, int32_t rebuild, int32_t dims_out[4], float geom_out[5],
+                                uint32_t *cell_start_out, size_t cap_cells, float *pts_out, size_t cap_pts);
 /* ... of which the single-launch form for a map without trees (sweep_grid_kernel<256, true>) */
 uint64_t lslam_debug_grid_wide_launches(lslam_ctx *ctx);
 /* cells of the resident map's two cell tables (corner, surf); 0 while a type has no grid */

@@ -226,6 +226,16 @@ struct lslam_ctx {
   uint64_t grid_epoch = ~0ull; // the map the grids were built from
   float grid_cell = 0.0f;      // ... and their cell size
   int grid_status = 0;         // why they could not be built (GridDev::build), 0: fine
+  // ... and the x-subdivided tables (CellGrid::xsub > 1, their own cell-sorted points) that the plain first pass of a
+  // throughput-bound grid sweep takes instead: built once per map on the first call that wants them (ensure_grid_fine),
+  // dropped by the first call after the map changed.  A map with deferred trees never has them.
+  GridDev kfc, kfs;
+  uint64_t fine_epoch = ~0ull;
+  float fine_cell = 0.0f;
+  int fine_xsub_asked = 0;
+  float fine_build_ms = 0.0f;       // host time of their one build, stream drained
+  uint64_t grid_fine_launches = 0;  // first-pass launches over them (lslam_debug_grid_fine_launches)
+  int env_grid_xsub = -1;           // LSLAM_GRID_XSUB (-1: not set -> LSLAM_GRID_XSUB_DEFAULT; 1: off; > 1: explicit GRID calls take them too)
   // deferred kd-trees (lslam_map_defer_trees): a map handed over on the device gets its cell grids at once and its trees on
   // first need -- a tap, the lane search, a query whose neighbours need nanoflann's visit order (an exact distance tie)
   bool defer_trees = false;    // the caller's wish
@@ -396,6 +406,43 @@ int ensure_grid(lslam_ctx *ctx, float cell) {
   return LSLAM_OK;
 }
 
+void drop_grid_fine(lslam_ctx *ctx) {
+  ctx->kfc.release();
+  ctx->kfs.release();
+  ctx->fine_epoch = ~0ull;
+}
+
+// The x-subdivided tables of the resident whole-map trees.  true in *ok: both exist for this map, cell size and xsub.
+int ensure_grid_fine(lslam_ctx *ctx, float cell, int xsub, bool *ok) {
+  *ok = false;
+  if (!ctx->have_map || ctx->cube_mode || ctx->trees_pending || xsub <= 1) return LSLAM_OK;
+  if (!(cell > 0.0f)) cell = GRID_CELL_DEFAULT;
+  if (!(ctx->fine_epoch == ctx->map_epoch && ctx->fine_cell == cell && ctx->fine_xsub_asked == xsub)) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    drop_grid_fine(ctx);
+    ctx->fine_epoch = ctx->map_epoch;
+    ctx->fine_cell = cell;
+    ctx->fine_xsub_asked = xsub;
+    int st_c = 0, st_s = 0;
+    HIP_TRY(ctx->kfc.build(ctx->tc.view, ctx->env_grid_cell_corner > 0.0f ? ctx->env_grid_cell_corner : cell, ctx->stream, &st_c, xsub));
+    HIP_TRY(ctx->kfs.build(ctx->ts.view, cell, ctx->stream, &st_s, xsub));
+    if (st_c || st_s || !ctx->kfc.view.cell_start || !ctx->kfs.view.cell_start) {  // both or none
+      ctx->kfc.release();
+      ctx->kfs.release();
+    } else {  // built once: the build's scratch goes (both builds have waited for the stream)
+      for (GridDev *g : {&ctx->kfc, &ctx->kfs}) {
+        g->tmp_pts.release(); g->count.release(); g->coarse.release();
+        g->err = nullptr;
+        g->count_clean = false;
+      }
+    }
+    ctx->fine_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  *ok = ctx->kfc.view.cell_start && ctx->kfs.view.cell_start;
+  return LSLAM_OK;
+}
+
 int resolve_search_mode(const lslam_ctx *ctx, int32_t requested) {
   if (ctx->env_search >= 0) requested = ctx->env_search;
   requested &= 0xFF;  // the LSLAM_STACK_* bits are resolve_stack_mode's
@@ -427,8 +474,10 @@ CertPlan make_cert_plan(const lslam_ctx *ctx) {
 }
 
 // launch_sweep + the per-context count of the instantiation it took
+// fine: the grid sweep's first pass reads the x-subdivided tables (ctx->kfc / kfs, which the caller has ensured); every other
+// launch of the sweep -- the second pass, its probes -- keeps a's cubic tables
 hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
-                        int *variant = nullptr) {
+                        int *variant = nullptr, bool fine = false) {
   int v = -1;
   CertPlan plan = make_cert_plan(ctx);
   plan.ticket2 = plan.count + 4;
@@ -446,7 +495,16 @@ hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, hipEve
     }
     // the production loop's launch takes the lean instantiation (A/B: lslam_opts.ab_switches & LSLAM_AB_GRID_GENERAL keeps the general one)
     const bool lean = grid_sweep_lean_ok(a, jtj_mode) && !(ctx->ab_now & LSLAM_AB_GRID_GENERAL);
-    hipError_t e = launch_sweep_grid(a, jtj_mode, ctx->stream, e0, nullptr, false, lean);
+    hipError_t e;
+    if (fine && a.grid == 1 && !a.fit_ids && !a.need2_cnt && !a.wide_d && ctx->kfc.view.cell_start && ctx->kfs.view.cell_start) {
+      SweepArgs af = a;
+      af.kc = ctx->kfc.view;
+      af.ks = ctx->kfs.view;
+      e = launch_sweep_grid(af, jtj_mode, ctx->stream, e0, nullptr, false, lean, true);
+      ctx->grid_fine_launches++;
+    } else {
+      e = launch_sweep_grid(a, jtj_mode, ctx->stream, e0, nullptr, false, lean);
+    }
     v = SWEEP_VARIANT_GRID;
     ctx->sweep_variants[v]++;
     if (lean) ctx->grid_lean_launches++;
@@ -643,6 +701,7 @@ int lslam_ctx_create(int device, lslam_ctx **out) {
   if (const char *v = std::getenv("LSLAM_CERT_TRACK_M")) ctx->env_cert_track_m = (float)std::atof(v);
   if (const char *v = std::getenv("LSLAM_GRID_CELL")) ctx->env_grid_cell = (float)std::atof(v);
   if (const char *v = std::getenv("LSLAM_GRID_CELL_CORNER")) ctx->env_grid_cell_corner = (float)std::atof(v);
+  if (const char *v = std::getenv("LSLAM_GRID_XSUB")) ctx->env_grid_xsub = std::max(1, std::min(std::atoi(v), GRID_MAX_XSUB));
   if (const char *v = std::getenv("LSLAM_FIT_FROM_SWEEP")) ctx->env_fit_from_sweep = std::atoi(v);
   if (const char *v = std::getenv("LSLAM_DEBUG_CERT_STATS")) ctx->env_debug_cert_stats = std::atoi(v);
   if (const char *v = std::getenv("LSLAM_FORCE_STACK")) {
@@ -739,6 +798,15 @@ void lslam_debug_lazy_trees(lslam_ctx *ctx, uint64_t out[3]) {
 
 uint64_t lslam_debug_grid_launches(lslam_ctx *ctx) { return ctx ? ctx->sweep_variants[SWEEP_VARIANT_GRID] + ctx->sweep_variants[SWEEP_VARIANT_GRID_WIDE] : 0; }
 uint64_t lslam_debug_grid_lean_launches(lslam_ctx *ctx) { return ctx ? ctx->grid_lean_launches : 0; }
+uint64_t lslam_debug_grid_fine_launches(lslam_ctx *ctx) { return ctx ? ctx->grid_fine_launches : 0; }
+void lslam_debug_grid_fine_info(lslam_ctx *ctx, uint64_t out[4], float *build_ms) {
+  const bool have = ctx && ctx->kfc.view.cell_start && ctx->kfs.view.cell_start;
+  out[0] = have ? (uint64_t)ctx->kfc.view.xsub : 0;
+  out[1] = have ? (uint64_t)ctx->kfs.view.xsub : 0;
+  out[2] = have ? (uint64_t)ctx->kfc.n_cells : 0;
+  out[3] = have ? (uint64_t)ctx->kfs.n_cells : 0;
+  if (build_ms) *build_ms = have ? ctx->fine_build_ms : 0.0f;
+}
 uint64_t lslam_debug_grid_wide_launches(lslam_ctx *ctx) { return ctx ? ctx->sweep_variants[SWEEP_VARIANT_GRID_WIDE] : 0; }
 void lslam_debug_grid_cells(lslam_ctx *ctx, uint64_t out[2]) {
   out[0] = ctx && ctx->kc.view.cell_start ? (uint64_t)ctx->kc.n_cells : 0;
@@ -1615,6 +1683,7 @@ struct RunCall {
   StereoArgs sta{};
   // the chunked loops (configure_search)
   bool compact = false, force_cert = false, no_probe2 = true, cert_counters_reset = false;
+  bool fine = false;  // the loops' first pass reads the x-subdivided tables (configure_search)
   std::vector<int> done_iters;  // iterations enqueued per chunk
   std::vector<char> finished;
   std::vector<int32_t> active_n;
@@ -2032,8 +2101,19 @@ int configure_search(lslam_ctx *ctx, RunCall &call) {
         sa.wide_p = ctx->wide_p.p;
       }
       sa.grid_clip_margin = GRID_CLIP_MARGIN_MIN;
+      // The x-subdivided tables for the plain first pass: where AUTO chose the grid sweep (an explicit LSLAM_SEARCH_GRID keeps
+      // the cubic table -- its pose bytes are pinned -- unless LSLAM_GRID_XSUB forces them, for tests), not for the A/B forms of
+      // the sweep (refill, fit cache, second probe), not with LSLAM_AB_GRID_CUBIC.
+      const int xsub = ctx->env_grid_xsub >= 1 ? ctx->env_grid_xsub : LSLAM_GRID_XSUB_DEFAULT;
+      const bool by_auto = call.search != LSLAM_SEARCH_GRID;
+      if (xsub > 1 && (by_auto || ctx->env_grid_xsub > 1) && !ctx->defer_trees &&  // (a deferred-trees map whose trees a tie forced: the mapping frame)
+          !(call.ab & (LSLAM_AB_GRID_CUBIC | LSLAM_AB_REFILL | LSLAM_AB_FIT_CACHE | LSLAM_AB_SECOND_PROBE))) {
+        rc = ensure_grid_fine(ctx, ctx->env_grid_cell > 0.0f ? ctx->env_grid_cell : o.grid_cell, xsub, &call.fine);
+        if (rc) return rc;
+      }
     }
   }
+  if (!call.fine && ctx->fine_epoch != ctx->map_epoch && (ctx->kfc.pts.p || ctx->kfs.pts.p)) drop_grid_fine(ctx);  // another map's
   ctx->ab_now = call.ab;
   const bool grid_on = sa.grid != 0;
   call.no_probe2 = (call.ab & LSLAM_AB_SECOND_PROBE) == 0;  // A/B (off): a second, wider probe before the tree search
@@ -2094,7 +2174,7 @@ int enqueue_chunk(lslam_ctx *ctx, RunCall &call, int c, int iters) {
     if (!(ch.sc.active_blocks && ch.sc.n_active <= 0)) {
       hipEvent_t e0, e1;
       HIP_TRY(sweep_events(ctx, call, call.n_launches, &e0, &e1));
-      HIP_TRY(sweep_launch(ctx, ch.sc, call.o.jtj_mode, e0, e1, &variant));
+      HIP_TRY(sweep_launch(ctx, ch.sc, call.o.jtj_mode, e0, e1, &variant, call.fine));
       ++call.n_launches;
     }
     HIP_TRY(launch_stereo(ch.stc, ctx->stream));
@@ -2886,6 +2966,29 @@ int lslam_knn5_ex(lslam_ctx *ctx, int which_map, const void *queries, size_t nq,
   return LSLAM_OK;
 }
 
+// Debug export of an x-subdivided cell table (include/lslam_c.h)
+int lslam_debug_grid_fine_table(lslam_ctx *ctx, int which_map, int32_t rebuild, int32_t dims_out[4], float geom_out[5], uint32_t *cell_start_out,
+                                size_t cap_cells, float *pts_out, size_t cap_pts) {
+  int rc = check_ctx(ctx, true);
+  if (rc) return rc;
+  if (which_map != 0 && which_map != 1) { set_err("bad map"); return LSLAM_ERR_INVALID; }
+  if (rebuild && ctx->fine_epoch == ctx->map_epoch) {
+    bool ok = false;
+    ctx->fine_epoch = ~0ull;
+    rc = ensure_grid_fine(ctx, ctx->fine_cell, ctx->fine_xsub_asked, &ok);
+    if (rc) return rc;
+  }
+  const GridDev &g = which_map ? ctx->kfs : ctx->kfc;
+  if (ctx->fine_epoch != ctx->map_epoch || !g.view.cell_start) { set_err("this map has no x-subdivided cell table"); return LSLAM_ERR_INVALID; }
+  const CellGrid &G = g.view;
+  if (dims_out) { dims_out[0] = G.nx; dims_out[1] = G.ny; dims_out[2] = G.nz; dims_out[3] = G.xsub; }
+  if (geom_out) { geom_out[0] = G.org[0]; geom_out[1] = G.org[1]; geom_out[2] = G.org[2]; geom_out[3] = G.c; geom_out[4] = G.inv_cx; }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (cell_start_out) HIP_TRY(hipMemcpy(cell_start_out, G.cell_start, std::min(cap_cells, g.n_cells + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (pts_out) HIP_TRY(hipMemcpy(pts_out, G.pts, std::min(cap_pts, (size_t)G.n_pts) * sizeof(float4), hipMemcpyDeviceToHost));
+  return G.n_pts;
+}
+
 // Parity tap of the search a map WITHOUT kd-trees is matched through (include/lslam_c.h): the wide probe on the resident cell
 // grids, every cell within the acceptance gate, one wavefront per query.  Builds no tree.
 int lslam_debug_knn5_wide(lslam_ctx *ctx, int which_map, const void *queries, size_t nq, size_t stride_bytes, int32_t nf_margin,
@@ -3055,7 +3158,12 @@ static int sweep_ex_impl(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, 
     sa.coeff_out = ctx->t_coeff.p;
     sa.flags_out = ctx->t_flags.p;
   }
-  HIP_TRY(sweep_launch(ctx, sa, jtj_mode));
+  bool fine = false;  // LSLAM_GRID_XSUB forced: the general kernel's taps over the x-subdivided tables
+  if (sa.grid == 1 && ctx->env_grid_xsub > 1 && !(ctx->env_ab & LSLAM_AB_GRID_CUBIC)) {
+    rc = ensure_grid_fine(ctx, ctx->env_grid_cell > 0.0f ? ctx->env_grid_cell : 0.0f, ctx->env_grid_xsub, &fine);
+    if (rc) return rc;
+  }
+  HIP_TRY(sweep_launch(ctx, sa, jtj_mode, nullptr, nullptr, nullptr, fine));
   SolveArgs so{};
   so.states = ctx->d_state.p;
   so.partials = ctx->partials.p;

@@ -20,7 +20,7 @@ namespace lslam {
 namespace {
 
 LSLAM_DEV int cell_of(const CellGrid &G, const float4 &p, bool &ok) {
-  const float ux = __fmul_rn(__fsub_rn(p.x, G.org[0]), G.inv_c);
+  const float ux = __fmul_rn(__fsub_rn(p.x, G.org[0]), G.inv_cx);  // x in sub-cells (xsub == 1: inv_cx is inv_c)
   const float uy = __fmul_rn(__fsub_rn(p.y, G.org[1]), G.inv_c);
   const float uz = __fmul_rn(__fsub_rn(p.z, G.org[2]), G.inv_c);
   ok = ux >= 0.0f && ux < (float)G.nx && uy >= 0.0f && uy < (float)G.ny && uz >= 0.0f && uz < (float)G.nz;
@@ -233,14 +233,17 @@ hipError_t grid_bbox2(const float4 *const pts[2], const int n[2], uint32_t *d_bo
 }
 
 // Host side of a grid (one per map type): owns the device arrays.
-hipError_t GridDev::build(const TreeView &T, float cell, hipStream_t s, int *status) {
-  return build(T.pts, T.n_pts, T.bb_lo, T.bb_hi, cell, s, status, true);
+hipError_t GridDev::build(const TreeView &T, float cell, hipStream_t s, int *status, int xsub) {
+  return build(T.pts, T.n_pts, T.bb_lo, T.bb_hi, cell, s, status, true, xsub);
 }
 
 // src: n points {x, y, z, bitcast(original index)} in any order; lo / hi: their bounding box
 // wait: read the "point outside the table" counter back (one host round trip).  A caller whose box was reduced from these very
 // points a moment ago has nothing to learn from it (a non-finite coordinate shows in the box) and passes false: stream-ordered, no wait.
-hipError_t GridDev::build(const float4 *src, int n_src, const float lo[3], const float hi[3], float cell, hipStream_t s, int *status, bool wait) {
+// xsub: x sub-cells per cell asked for (CellGrid::xsub); lowered until the table keeps its limits -- nx <= GRID_MAX_DIM (the
+// rounding slack is sized for coordinates below it), GRID_MAX_CELLS, 4 096 cells per point -- view.xsub is the value used.
+hipError_t GridDev::build(const float4 *src, int n_src, const float lo[3], const float hi[3], float cell, hipStream_t s, int *status, bool wait,
+                          int xsub) {
   *status = 0;
   view = CellGrid{};
   if (n_src <= 0 || !(cell > 0.05f) || !(cell < 1.45f)) return hipSuccess;  // rg <= 1.5 c must stay inside the sqrt(5) m gate
@@ -256,7 +259,13 @@ hipError_t GridDev::build(const float4 *src, int n_src, const float lo[3], const
     dims[a] = (int)std::floor((hi[a] - G.org[a]) * G.inv_c) + 1 + margin;
     if (dims[a] > GRID_MAX_DIM) { *status = 2; return hipSuccess; }  // the map is larger than the grid's rounding slack allows
   }
-  G.nx = dims[0]; G.ny = dims[1]; G.nz = dims[2];
+  const size_t cell_cap = std::min(GRID_MAX_CELLS, (size_t)4096 * (size_t)std::max(n_src, 4096));
+  xsub = std::max(1, std::min(xsub, GRID_MAX_XSUB));
+  while (xsub > 1 && (dims[0] * xsub > GRID_MAX_DIM || (size_t)dims[0] * xsub * dims[1] * dims[2] > cell_cap)) --xsub;
+  G.xsub = xsub;
+  G.inv_cx = xsub == 1 ? G.inv_c : (float)xsub / cell;
+  G.inv_s = 1.0f / (float)xsub;
+  G.nx = dims[0] * xsub; G.ny = dims[1]; G.nz = dims[2];
   const size_t ncell = (size_t)G.nx * G.ny * G.nz;
   // The two dense tables (count, cell_start: 8 bytes per cell) are memset / rewritten in full by every build: a map that is wide
   // but sparse must not cost gigabytes of both.  GRID_MAX_CELLS cells (512 MB per type; the bench surround has 16 M), or 4 096

@@ -17,7 +17,8 @@
 //   pts[n]            the map points sorted by cell, {x, y, z, bitcast(original index)}
 //   cell_start[N + 1] cell -> first point, cells numbered x-fastest: cell = ix + nx (iy + ny iz); the three x-neighbours of a
 //                     cell row are ONE contiguous run of pts, so the 27 cells are nine runs (two loads each)
-// Cell of a coordinate v on axis a: floor(fl(fl(v - org[a]) * inv_c)), the same two fp32 operations for map points and queries.
+// Cell of a coordinate v on axis a: floor(fl(fl(v - org[a]) * inv_c)), the same two fp32 operations for map points and queries
+// (x: inv_cx, sub-cells -- see CellGrid).
 // The grid covers the map's bounding box plus GRID_MARGIN_CELLS(c) empty cells on every side, so that a query whose cell is
 // not an interior one is farther than sqrt(5) m from every map point (the acceptance gate of ScanMatch.cpp:102,120).
 #pragma once
@@ -31,8 +32,14 @@ struct CellGrid {
   const float4 *pts;
   float org[3];
   float inv_c, c;
-  int32_t nx, ny, nz;
+  int32_t nx, ny, nz;  // nx counts x SUB-cells (xsub per cell)
   int32_t n_pts;
+  // The x axis cut into xsub (>= 1) sub-cells per cell: the x index of a point or a query is floor(fl(fl(v - org[0]) * inv_cx)),
+  // inv_cx = xsub / c, and its (coarse) x cell is BY DEFINITION that index div xsub -- the two can never disagree.  A row of
+  // three cells is still one contiguous run of pts; a bounded probe clips it to sub-cells (knn5_grid<.., FINE>).  xsub == 1:
+  // inv_cx == inv_c, the cubic table.
+  int32_t xsub;
+  float inv_cx, inv_s;  // inv_s = 1 / xsub
 };
 
 #ifndef LSLAM_GRID_BALL
@@ -44,6 +51,10 @@ struct CellGrid {
 constexpr float GRID_CELL_DEFAULT = 0.6f;
 constexpr int GRID_MAX_DIM = 2048;        // cells per axis (the rounding slack below is sized for it)
 constexpr size_t GRID_MAX_CELLS = (size_t)1 << 26;  // cells per table: two dense 4-byte tables rewritten by every build (lslam_grid.hip)
+constexpr int GRID_MAX_XSUB = 8;          // x sub-cells per cell (CellGrid::xsub)
+#ifndef LSLAM_GRID_XSUB_DEFAULT
+#define LSLAM_GRID_XSUB_DEFAULT 2  // sub-cells of the fine tables the production grid sweep's first pass takes (1: none); DESIGN 4 has the numbers
+#endif
 // Rounding of the cell coordinate u(v) = fl(fl(v - o) * inv_c): relative error <= 2^-23 on a value < GRID_MAX_DIM, so two
 // points whose cell coordinates differ by w are at least (w - GRID_U_SLACK) cells apart on that axis.
 constexpr float GRID_U_SLACK = 2.0e-3f;
@@ -134,7 +145,14 @@ enum : int {
 // *five_valid -- wave-uniform: no lane of the wavefront took the re-sort branch, so every lane's five are its first five
 // survivors.  A caller that goes on to fit them (the lean grid sweep) need not gather them a second time.  (Plain floats: an
 // array of float4 handed through stays in scratch memory.)
-template <int BLOCK, int R = 1, bool KEEP = false>
+//
+// FINE: G's x axis is cut into G.xsub sub-cells per cell.  The interior test, wall, rg and the y / z clip work on coarse
+// coordinates as before (coarse x = fine x / xsub); the x-extent of the nine runs is counted in sub-cells,
+//   max(xsub (fxc - 1), floor(ux - rbc xsub)) .. min(xsub (fxc + 1) + xsub - 1, floor(ux + rbc xsub)):
+// unclipped exactly the three coarse cells, clipped to 2 rb + c / xsub instead of 2 rb + c.  A point left out differs by
+// more than rbc xsub less the rounding slack in SUB-cell units, i.e. by at least rb - GRID_U_SLACK c / xsub metres: cl and
+// clip_lo2 keep their values and their claim.  The loop, the survivors and the proof are the same text.
+template <int BLOCK, int R = 1, bool KEEP = false, bool FINE = false>
 LSLAM_DEV int knn5_grid(const CellGrid &G, const bool on, const float qx, const float qy, const float qz, const float bound,
                         const float clip_margin, lds_u32 *rows, float (&d)[5], int (&p)[5], float &lb6 LSLAM_SEC_PARAM,
                         float (*five)[15] = nullptr, bool *five_valid = nullptr) {
@@ -143,7 +161,8 @@ LSLAM_DEV int knn5_grid(const CellGrid &G, const bool on, const float qx, const 
     d[i] = FLT_MAX;
     p[i] = -1;
   }
-  const float ux = __fmul_rn(__fsub_rn(qx, G.org[0]), G.inv_c);
+  static_assert(!FINE || (R == 1 && !LSLAM_GRID_BALL), "the sub-cell clip is the 27-cell probe's box clip");
+  const float ux = __fmul_rn(__fsub_rn(qx, G.org[0]), FINE ? G.inv_cx : G.inv_c);  // FINE: in sub-cells
   const float uy = __fmul_rn(__fsub_rn(qy, G.org[1]), G.inv_c);
   const float uz = __fmul_rn(__fsub_rn(qz, G.org[2]), G.inv_c);
   // interior cell: 1 <= i <= n - 2 on every axis (NaN fails every comparison)
@@ -151,20 +170,24 @@ LSLAM_DEV int knn5_grid(const CellGrid &G, const bool on, const float qx, const 
   constexpr uint32_t IDB = R == 1 ? GRID_ID_BITS : GRID_ID_BITS + 1;  // id = (row slot << GRID_ROW_BITS) | offset in the row
   constexpr uint32_t IDM = (1u << IDB) - 1u;
   static_assert(NR - 1 <= (int)(IDM >> GRID_ROW_BITS), "row slots must fit the id");
-  const bool inr = ux >= (float)R && ux < (float)(G.nx - R) && uy >= (float)R && uy < (float)(G.ny - R) && uz >= (float)R && uz < (float)(G.nz - R);
+  const float sx = FINE ? (float)G.xsub : 1.0f;
+  const bool inr = (FINE ? ux >= sx && ux < (float)G.nx - sx : ux >= (float)R && ux < (float)(G.nx - R)) && uy >= (float)R && uy < (float)(G.ny - R) && uz >= (float)R && uz < (float)(G.nz - R);
   const bool alive0 = on && inr;
-  const float fx0 = floorf(ux), fy0 = floorf(uy), fz0 = floorf(uz);
-  const float ex = ux - fx0, ey = uy - fy0, ez = uz - fz0;  // position inside the cell, [0, 1)
+  // FINE: the coarse cell is the sub-cell's index div xsub (the half keeps the product clear of the integers whatever the
+  // rounding of inv_s); the position inside it to the coordinate's own rounding, which GRID_U_SLACK covers
+  const float fx0 = FINE ? floorf((floorf(ux) + 0.5f) * G.inv_s) : floorf(ux), fy0 = floorf(uy), fz0 = floorf(uz);
+  const float ex = FINE ? fminf(fmaxf(ux * G.inv_s - fx0, 0.0f), 1.0f) : ux - fx0, ey = uy - fy0, ez = uz - fz0;  // position inside the cell, [0, 1)
   const float wall = fminf(fminf(fminf(ex, 1.0f - ex), fminf(ey, 1.0f - ey)), fminf(ez, 1.0f - ez));
   const float rg = G.c * (((float)R - GRID_U_SLACK) + wall);
   const float rg2 = (rg * rg) * (1.0f - (1.0e-5f + GRID_NF_PRUNE_SLACK));
   // clip box in cell coordinates
   float clip_lo2 = FLT_MAX;
-  float xlo = fx0 - (float)R, xhi = fx0 + (float)R, ylo = fy0 - (float)R, yhi = fy0 + (float)R, zlo = fz0 - (float)R, zhi = fz0 + (float)R;
+  float xlo = FINE ? sx * (fx0 - 1.0f) : fx0 - (float)R, xhi = FINE ? sx * (fx0 + 1.0f) + (sx - 1.0f) : fx0 + (float)R, ylo = fy0 - (float)R, yhi = fy0 + (float)R, zlo = fz0 - (float)R, zhi = fz0 + (float)R;
   if (bound < 1.0e30f) {
     const float rb = sqrtf(bound) * (1.0f + 1.0e-5f) + clip_margin;
     const float rbc = rb * G.inv_c;
-    xlo = fmaxf(xlo, floorf(ux - rbc)); xhi = fminf(xhi, floorf(ux + rbc));
+    const float rbx = FINE ? rbc * sx : rbc;
+    xlo = fmaxf(xlo, floorf(ux - rbx)); xhi = fminf(xhi, floorf(ux + rbx));
     ylo = fmaxf(ylo, floorf(uy - rbc)); yhi = fminf(yhi, floorf(uy + rbc));
     zlo = fmaxf(zlo, floorf(uz - rbc)); zhi = fminf(zhi, floorf(uz + rbc));
     const float cl = rb - GRID_U_SLACK * G.c;  // a clipped point is at least this far away

@@ -318,8 +318,9 @@ enum : int {
 inline bool grid_sweep_lean_ok(const SweepArgs &a, int jtj_mode) {
   return jtj_mode == 1 && !a.flags_out && !a.coeff_out && !a.idx_out && a.fine_gate_c < 0.0f && a.bounded && !a.cert_stats && !a.fit_ids;
 }
+// fine: a.kc / a.ks are x-subdivided tables (CellGrid::xsub); sweep_grid_kernel<.., FINE>, lean or general
 hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool resolve_in_place = false,
-                             bool lean = false);
+                             bool lean = false, bool fine = false);
 hipError_t launch_sweep_wide(const SweepArgs &a, hipStream_t s);  // sweep_wide_kernel (its prefix: launch_sweep_plan with_prefix)
 hipError_t launch_knn5_wide(const CellGrid &G, const float4 *q, int nq, float nf_slack, int32_t *idx, float *d2, uint8_t *undecided, hipStream_t s);
 hipError_t launch_knn5_grid(const CellGrid &G, const TreeView &T, const float4 *q, int nq, int32_t *idx, float *d2,
@@ -334,9 +335,11 @@ struct GridDev {
   int32_t *err = nullptr;    // the "point outside the table" counter: lives behind the coarse counts
   bool count_clean = false;  // every cell of `count` is zero (each build leaves it so)
   // status: 0 built (or nothing to build: view.cell_start stays null), 1 non-finite point, 2 map too large for the grid
-  hipError_t build(const TreeView &T, float cell, hipStream_t s, int *status);
+  // xsub: x sub-cells per cell asked for; view.xsub is what the table's limits allowed (lslam_grid.hip)
+  hipError_t build(const TreeView &T, float cell, hipStream_t s, int *status, int xsub = 1);
   // ... from n points {x, y, z, bitcast(original index)} in any order and their bounding box (a map whose trees are deferred)
-  hipError_t build(const float4 *src, int n, const float lo[3], const float hi[3], float cell, hipStream_t s, int *status, bool wait = true);
+  hipError_t build(const float4 *src, int n, const float lo[3], const float hi[3], float cell, hipStream_t s, int *status, bool wait = true,
+                   int xsub = 1);
   void release();
 };
 hipError_t grid_bbox2(const float4 *const pts[2], const int n[2], uint32_t *d_box12, float lo[2][3], float hi[2][3], hipStream_t s);

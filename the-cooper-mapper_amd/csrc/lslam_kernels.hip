@@ -1043,9 +1043,12 @@ LSLAM_DEV void wide_probe(const CellGrid &G, const float (&sel)[3], float r2, in
 // neighbours' points go from the search (which has fetched them for their exact distances) straight to the fit, not gathered a
 // second time (knn5_grid<.., true>, point_residual<true>).  Same operations on the same values: same bits; +3.0 % on the
 // headline (LSLAM_AB_GRID_GENERAL brings the general kernel back; DESIGN 4 has the numbers).
-template <int BLOCK, bool WIDE = false, bool FITC = false, bool LEAN = false>
+// FINE: a.kc / a.ks are the x-subdivided tables (CellGrid::xsub > 1, their own cell-sorted points): knn5_grid<.., FINE> clips the
+// bounded probe's rows to sub-cells.  The plain first pass only -- positions in these tables never leave the launch.
+template <int BLOCK, bool WIDE = false, bool FITC = false, bool LEAN = false, bool FINE = false>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : (LEAN ? LSLAM_GRID_LEAN_OCC : LSLAM_GRID_OCC)))) void sweep_grid_kernel(SweepArgs a, int jtj_mode) {
   static_assert(!LEAN || (!WIDE && !FITC), "the lean grid sweep has neither the wide probe nor the fit cache");
+  static_assert(!FINE || (!WIDE && !FITC), "the fine tables serve the plain first pass only");
   if constexpr (LEAN) {  // what launch_sweep_grid has checked, as constants
     jtj_mode = 1;
     a.flags_out = nullptr;
@@ -1113,6 +1116,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 
   G.ny = is_surf ? a.ks.ny : a.kc.ny;
   G.nz = is_surf ? a.ks.nz : a.kc.nz;
   G.n_pts = is_surf ? a.ks.n_pts : a.kc.n_pts;
+  if constexpr (FINE) {
+    G.xsub = is_surf ? a.ks.xsub : a.kc.xsub;
+    G.inv_cx = is_surf ? a.ks.inv_cx : a.kc.inv_cx;
+    G.inv_s = is_surf ? a.ks.inv_s : a.kc.inv_s;
+  }
 
   float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
   if (active) q = a.q[qi];
@@ -1150,8 +1158,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 
   float five[15];  // LEAN: the five neighbours' points as the search fetched them, handed on to the residual chain
   bool five_valid = false;
   int verdict;
-  if constexpr (LEAN) verdict = knn5_grid<BLOCK, 1, true>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG, &five, &five_valid);
-  else verdict = knn5_grid<BLOCK>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG);
+  if constexpr (LEAN) verdict = knn5_grid<BLOCK, 1, true, FINE>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG, &five, &five_valid);
+  else verdict = knn5_grid<BLOCK, 1, false, FINE>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG);
   LSLAM_TICK_P(scp, 3);  // the six survivors fetched again, exact distances, order, proof
   // beyond the gate nothing is looked up (ScanMatch.cpp:102,120); the taps and the _fineScore re-sweep want nanoflann's answer
   if (verdict == GRID_FAR && !a.bounded) verdict = GRID_UNPROVEN;
@@ -1401,9 +1409,19 @@ hipError_t launch_compact_active(const GNState *states, const ProbBlocks *probs,
   return hipGetLastError();
 }
 
-hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool resolve_in_place, bool lean) {
+hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool resolve_in_place, bool lean,
+                             bool fine) {
   if (a.nb_total <= 0) return hipSuccess;
   if (lean && (resolve_in_place || !grid_sweep_lean_ok(a, jtj_mode))) return hipErrorInvalidValue;  // (the lean kernel would compute something else)
+  if (fine) {  // a.kc / a.ks are x-subdivided tables: the plain first pass, lean or general -- the same table for both
+    if (resolve_in_place || a.fit_ids || a.kc.xsub < 1 || a.ks.xsub < 1) return hipErrorInvalidValue;
+    const dim3 grd(a.active_blocks ? a.n_active : a.nb_total);
+    if (a.active_blocks && a.n_active <= 0) return hipSuccess;
+    if (lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, false, true, true>), grd, dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
+    else hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, false, false, true>), grd, dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
+    return hipGetLastError();
+  }
+  if (a.kc.xsub > 1 || a.ks.xsub > 1) return hipErrorInvalidValue;  // (these kernels read x in whole cells)
   if (a.active_blocks && !resolve_in_place) {  // the batch's grid sweep over the running scans' workgroups only
     if (a.n_active <= 0) return hipSuccess;
     if (lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, false, true>), dim3(a.n_active), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);

@@ -148,6 +148,34 @@ class Context:
         """lslam_debug_grid_lean_launches: ... of which with the lean instantiation (the production loop's launch)."""
         return int(self.lib.lslam_debug_grid_lean_launches(self.h))
 
+    def grid_fine_launches(self):
+        """lslam_debug_grid_fine_launches: ... of which with the first pass over the x-subdivided cell tables."""
+        return int(self.lib.lslam_debug_grid_fine_launches(self.h))
+
+    def grid_fine_info(self):
+        """lslam_debug_grid_fine_info: dict(xsub=(corner, surf), cells=(corner, surf), build_ms) of the resident map's
+        x-subdivided cell tables; zeros while there are none."""
+        out = (C.c_uint64 * 4)()
+        ms = C.c_float(0.0)
+        self.lib.lslam_debug_grid_fine_info(self.h, out, C.byref(ms))
+        return dict(xsub=(int(out[0]), int(out[1])), cells=(int(out[2]), int(out[3])), build_ms=float(ms.value))
+
+    def grid_fine_table(self, which_map, rebuild=False):
+        """lslam_debug_grid_fine_table: (dims {nx, ny, nz, xsub}, geom {org, c, inv_cx}, cell_start, pts (n, 4) float32) of
+        an x-subdivided table, or None when the map has none."""
+        dims = (C.c_int32 * 4)()
+        geom = (C.c_float * 5)()
+        n = self.lib.lslam_debug_grid_fine_table(self.h, which_map, 1 if rebuild else 0, dims, geom, None, 0, None, 0)
+        if n < 0:
+            return None
+        ncell = int(dims[0]) * int(dims[1]) * int(dims[2])
+        cs = np.empty(ncell + 1, np.uint32)
+        pts = np.empty((n, 4), np.float32)
+        n2 = self.lib.lslam_debug_grid_fine_table(self.h, which_map, 0, dims, geom, cs.ctypes.data_as(C.POINTER(C.c_uint32)), cs.size,
+                                                  pts.ctypes.data_as(C.POINTER(C.c_float)), n)
+        assert n2 == n
+        return np.array(dims[:]), np.array(geom[:], np.float32), cs, pts
+
     def grid_wide_launches(self):
         """lslam_debug_grid_wide_launches: ... of which in the single-launch form of a map without trees."""
         return int(self.lib.lslam_debug_grid_wide_launches(self.h))
