@@ -7,13 +7,22 @@
 // LM schedule of OptimizationAlgorithmLevenberg -- see oracle/posegraph_oracle.py.
 //
 // Data parallel structure
-//   pg_edge_kernel      one lane per edge of this rank's shard: error, analytic Jacobians,
+//   pg_edge_kernel, pg_edge_robust_kernel (edges with robust kernels; pg_edge_robust_tap_kernel: their e2 / rho for the host)
+//                       one lane per edge of this rank's shard: error, analytic Jacobians,
 //                       J^T Omega J blocks, J^T Omega e, chi2 -> per-edge records
-//   pg_assemble_kernel  deterministic gather of the records into the block system
+//   pg_assemble_vertex_kernel, pg_assemble_off_kernel, pg_sum_kernel
+//                       deterministic gather of the records into the block system
 //                       [diag blocks | off-diagonal blocks | b | chi2]  (fixed order, no atomics)
-//   (all-reduce of that buffer across ranks: callback, RCCL via torch.distributed)
-//   pg_expand / pg_precond / pg_spmv / pg_cg_*   replicated block-Jacobi PCG on (H + lambda I)
-//   pg_update_kernel    X <- X * fromVectorMQT(dx)
+//   (all-reduce of that buffer across ranks: callback, or the library's RCCL communicator)
+//   pg_expand_kernel, pg_precond_kernel          block rows of H + lambda I, inverses of its diagonal blocks
+//   pg_cg_init / init2 / prod / update / check_kernel   replicated block-Jacobi PCG, a launch per step
+//   pg_rs_*_kernel      what the row-sharded form of that loop adds (several GPUs share one solve)
+//   pgc_*_kernel        second preconditioner level: rigid motions of graph aggregates, dense inverse by Gauss-Jordan
+//                       (pgc_gj_pivot / update_kernel per pivot, or pgc_gj_persistent_kernel in one launch)
+//   pg_pcg_persistent_kernel   the whole PCG loop, second level included, in one cooperative launch
+//   pg_update_kernel    X <- X * fromVectorMQT(dx);  pg_chi2_kernel, pg_chi2_robust_kernel: chi2 of a trial
+//   pg_dot_scale_kernel, pg_maxdiag_kernel       LM's gain denominator and first damping
+// The host side is cut into named stages: solve(), lslam_pg_create() and lslam_pg_optimize() each read as their list.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1685,8 +1694,6 @@ struct lslam_pg {
   void *gatherv_user = nullptr;
   int gatherv_rank = -1, gatherv_world = 0;
   int rs_gathered = 0;
-  int rs_agree_v0 = -2, rs_agree_v1 = -2, rs_agree_world = -1;  // the setting the ranks last agreed on ...
-  bool rs_agree_gather = false;                                  // ... and what they agreed: every rank's rows are the canonical partition
   // rank / world of whichever transport can gather; false: only the all-reduce is available
   bool gather_transport(int *rank, int *world) const {
     if (gatherv) { *rank = gatherv_rank; *world = gatherv_world; return true; }
@@ -1732,7 +1739,7 @@ struct lslam_pg {
   lslam::DevBuf<double> d_P, d_Ac, d_rc, d_yc, d_gj;
   lslam::DevBuf<int32_t> d_cb_ptr, d_cb_ent, d_cb_ab;
   // environment switches, read when the graph is created (lslam_pg_create) -- never while it is optimised
-  bool env_no_reuse = false, env_persistent_off = false, env_debug = false;
+  bool env_no_reuse = false, env_no_merge = false, env_persistent_off = false, env_debug = false;
   int env_max_cg = 20000;
   double env_tol = 1e-8;
   int coarse_mode = -1;     // -1 automatic (switched on by a solve that needed many iterations), 0 off, 1 on
@@ -1861,15 +1868,33 @@ int eval_chi2(lslam_pg *pg, const double *poses, double *out) {
   return LSLAM_OK;
 }
 
-// (H + lambda I) dx = b by block-Jacobi PCG; returns iterations
-int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
-  const int n6 = pg->n_v * 6;
-  const size_t n_items = (size_t)pg->n_entries * 6;
-  hipLaunchKernelGGL(pg_expand_kernel, dim3((unsigned)((n_items * 6 + 255) / 256)), dim3(256), 0, pg->stream,
-                     pg->d_sys.p, pg->d_row_src.p, pg->n_entries, lambda, pg->d_vals.p);
+// ---- the host driver of the solve: solve() at the end of this section is the list of its stages ------------
+
+// What one call of solve() works on.
+struct SolveCall {
+  CgArgs a{};
+  CoarseArgs c{};
+  bool coarse = false;         // the second level of the preconditioner takes part in this solve ...
+  bool fresh_inverse = false;  // ... with an inverse built by this call
+  size_t n_items = 0;
+  double lambda = 0.0;
+  int max_cg = 0;
+  double tol = 0.0;
+};
+
+// vals = the block rows of H + lambda I, minv = the inverses of its diagonal blocks, and the coarse level's partial-sum slots
+int expand_and_precondition(lslam_pg *pg, const SolveCall &s) {
+  hipLaunchKernelGGL(pg_expand_kernel, dim3((unsigned)((s.n_items * 6 + 255) / 256)), dim3(256), 0, pg->stream,
+                     pg->d_sys.p, pg->d_row_src.p, pg->n_entries, s.lambda, pg->d_vals.p);
   hipLaunchKernelGGL(pg_precond_kernel, dim3((pg->n_v + 63) / 64), dim3(64), 0, pg->stream, pg->d_vals.p,
-                     pg->d_row_ptr.p, pg->n_v, n_items, pg->d_minv.p);
-  CgArgs a;
+                     pg->d_row_ptr.p, pg->n_v, s.n_items, pg->d_minv.p);
+  PG_TRY(hipMemsetAsync(pg->d_part.p, 0, 3 * (size_t)pg->n_parts * sizeof(double), pg->stream));  // the coarse level's slots
+  return LSLAM_OK;
+}
+
+void make_cg_args(const lslam_pg *pg, SolveCall &s) {
+  const int n6 = pg->n_v * 6;
+  CgArgs &a = s.a;
   a.vals = pg->d_vals.p;
   a.row_ptr = pg->d_row_ptr.p;
   a.row_col = pg->d_row_col.p;
@@ -1884,316 +1909,639 @@ int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
   a.part_rr = pg->d_part.p + 2 * pg->n_parts;
   a.part_pq = pg->d_part.p + 3 * pg->n_parts;
   a.n_parts = pg->n_parts;
-  PG_TRY(hipMemsetAsync(pg->d_part.p, 0, 3 * (size_t)pg->n_parts * sizeof(double), pg->stream));  // the coarse level's slots
-  a.n_items = (int)n_items;
-  a.n_pblocks = (int)((n_items + PROD_BLOCK - 1) / PROD_BLOCK);
+  a.n_items = (int)s.n_items;
+  a.n_pblocks = (int)((s.n_items + PROD_BLOCK - 1) / PROD_BLOCK);
   a.scal = pg->d_scal.p;
   a.n6 = n6;
   a.n_blocks = pg->n_cg_blocks;
-  a.tol2 = tol * tol;
-  const dim3 g(pg->n_cg_blocks), blk(CG_BLOCK);
-  // second level (see pgc_P_kernel): on when forced, or -- automatic -- once a solve of this graph needed many iterations
-  const bool coarse = pg->coarse_mode == 1 || (pg->coarse_mode < 0 && pg->coarse_on);
-  bool fresh_inverse = false;
-  CoarseArgs c{};
-  if (coarse) {
-    c.poses = pg->d_poses.p;
-    c.P = pg->d_P.p; c.Ac = pg->d_Ac.p; c.rc = pg->d_rc.p; c.yc = pg->d_yc.p;
-    c.Rbuf = pg->d_gj.p; c.Cbuf = pg->d_gj.p + (size_t)6 * pg->n_c; c.Bbuf = pg->d_gj.p + (size_t)12 * pg->n_c;
-    c.cb_ptr = pg->d_cb_ptr.p; c.cb_ent = pg->d_cb_ent.p; c.cb_ab = pg->d_cb_ab.p;
-    c.agg_of = pg->d_agg_of.p; c.agg_ptr = pg->d_agg_ptr.p; c.agg_mem = pg->d_agg_mem.p;
-    c.n_v = pg->n_v; c.G = pg->agg; c.na = pg->n_agg; c.n_c = pg->n_c; c.n_cb = pg->n_cb; c.n_cblk = pg->n_cblk;
+  a.tol2 = s.tol * s.tol;
+  a.item_begin = 0;
+  a.item_end = (int)s.n_items;
+  a.block_begin = 0;
+}
+
+// The second level's arguments (see pgc_P_kernel).  Its dense matrix and the Gauss-Jordan scratch are allocated by the first
+// solve that takes the second level; the pointers into them are assigned here, after that.
+int make_coarse_args(lslam_pg *pg, SolveCall &s) {
+  if (!pg->d_Ac.p) {
+    PG_TRY(pg->d_Ac.alloc((size_t)pg->n_c * pg->n_c));
+    PG_TRY(pg->d_gj.alloc((size_t)12 * pg->n_c + 36));
+  }
+  CoarseArgs &c = s.c;
+  c.poses = pg->d_poses.p;
+  c.P = pg->d_P.p; c.Ac = pg->d_Ac.p; c.rc = pg->d_rc.p; c.yc = pg->d_yc.p;
+  c.Rbuf = pg->d_gj.p; c.Cbuf = pg->d_gj.p + (size_t)6 * pg->n_c; c.Bbuf = pg->d_gj.p + (size_t)12 * pg->n_c;
+  c.cb_ptr = pg->d_cb_ptr.p; c.cb_ent = pg->d_cb_ent.p; c.cb_ab = pg->d_cb_ab.p;
+  c.agg_of = pg->d_agg_of.p; c.agg_ptr = pg->d_agg_ptr.p; c.agg_mem = pg->d_agg_mem.p;
+  c.n_v = pg->n_v; c.G = pg->agg; c.na = pg->n_agg; c.n_c = pg->n_c; c.n_cb = pg->n_cb; c.n_cblk = pg->n_cblk;
+  return LSLAM_OK;
+}
+
+// The reuse rule of the coarse inverse (see lslam_pg::coarse_valid): a function of lambda and iteration counts only, which
+// are identical on every rank of a sharded run.
+bool coarse_needs_rebuild(const lslam_pg *pg, double lambda) {
+  if (!pg->coarse_valid || pg->env_no_reuse) return true;  // (A/B switch LSLAM_PG_NO_REUSE, read when the graph was created)
+  const double ratio = lambda > pg->coarse_lambda ? lambda / pg->coarse_lambda : pg->coarse_lambda / lambda;
+  return !(ratio <= 10.0) || (pg->coarse_fresh_iters > 0 && 10 * pg->coarse_last_iters > 13 * pg->coarse_fresh_iters);
+}
+
+// Do `n_groups` workgroups of `kernel` (this block size, this much dynamic LDS) fit on the device at once?  What a
+// cooperative launch needs; the caller adds the conditions of its own kernel.
+bool fits_co_resident(const lslam_pg *pg, const void *kernel, int block, size_t lds_bytes, int n_groups) {
+  hipDeviceProp_t prop;
+  int per_cu = 0;
+  return hipGetDeviceProperties(&prop, pg->device) == hipSuccess &&
+         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds_bytes) == hipSuccess &&
+         (long)per_cu * prop.multiProcessorCount >= n_groups;
+}
+
+// One persistent kernel, a workgroup per aggregate: the barrier words zeroed, the exchange slots set to the sentinel, the
+// cooperative launch, and the abort word (with `scal_out`, the PCG's eight scalars too) read back behind ONE wait.
+// *aborted: an exchange ran into its spin limit, i.e. the workgroups were not all resident at once (another process's
+// persistent kernel on the same device can do that -- cooperative launches are not coordinated across processes) -- or the
+// launch was refused: no cooperative launch on this device / partition mode, or the runtime's residency count differs from
+// the occupancy query.  Neither is an error of the solve: the caller's launch loop does the work.
+int launch_persistent(lslam_pg *pg, const void *kernel, int block, size_t lds_bytes, void *args, double *slots,
+                      size_t n_slot_doubles, double *scal_out, bool *aborted) {
+  PG_TRY(hipMemsetAsync(pg->d_bar.p, 0, 2 * sizeof(unsigned), pg->stream));
+  PG_TRY(hipMemsetD32Async((hipDeviceptr_t)slots, (int)PK_SENT32, 2 * n_slot_doubles, pg->stream));
+  void *kargs[] = {args};
+  unsigned bar[2] = {0, 0};
+  if (hipLaunchCooperativeKernel(kernel, dim3((unsigned)pg->n_agg), dim3(block), kargs, (unsigned)lds_bytes, pg->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    bar[1] = 1;
+  } else {
+    if (scal_out) PG_TRY(hipMemcpyAsync(scal_out, pg->d_scal.p, 8 * sizeof(double), hipMemcpyDeviceToHost, pg->stream));
+    PG_TRY(hipMemcpyAsync(bar, pg->d_bar.p, sizeof(bar), hipMemcpyDeviceToHost, pg->stream));
+    PG_TRY(hipStreamSynchronize(pg->stream));
+  }
+  *aborted = bar[1] != 0;
+  return LSLAM_OK;
+}
+
+// A persistent kernel gave way to its launch loop: the graph stays on that loop (*fit = 0), and in a sharded run every rank
+// must follow (fell_back, see eval_chi2 and lm_trial).
+void record_fallback(lslam_pg *pg, int *fit, const char *what) {
+  if (pg->env_debug) fprintf(stderr, "[lslam pg] persistent %s: launch loop from here on\n", what);
+  *fit = 0;
+  pg->pk_timeouts++;
+  pg->fell_back = true;
+}
+
+int assemble_coarse(lslam_pg *pg, const SolveCall &s) {
+  PG_TRY(hipMemsetAsync(s.c.Ac, 0, (size_t)s.c.n_c * s.c.n_c * sizeof(double), pg->stream));
+  hipLaunchKernelGGL(pgc_assemble_kernel, dim3(s.c.n_cb), dim3(64), 0, pg->stream, s.c, pg->d_vals.p, pg->d_row_of.p, pg->d_row_col.p, s.n_items);
+  return LSLAM_OK;
+}
+
+// P at the current poses, A_c = P^T (H + lambda I) P, and its inverse in place: by the persistent Gauss-Jordan kernel when
+// it fits, else (or after it gave up) by the pivot / update launch loop.
+int build_coarse_inverse(lslam_pg *pg, const SolveCall &s) {
+  const CoarseArgs &c = s.c;
+  hipLaunchKernelGGL(pgc_P_kernel, dim3((pg->n_v + 127) / 128), dim3(128), 0, pg->stream, c);
+  int rc = assemble_coarse(pg, s);
+  if (rc) return rc;
+  if (pg->gj_fit < 0) {  // the persistent inverse when a workgroup per aggregate is co-resident and the row fits its registers
+    pg->gj_fit = 0;
+    if (!pg->env_persistent_off && c.n_c <= GJ_CREG * GJ_BLOCK &&
+        fits_co_resident(pg, (const void *)pgc_gj_persistent_kernel, GJ_BLOCK, 0, c.na) &&
+        pg->d_gjslots.alloc((size_t)c.na * 6 * c.n_c) == hipSuccess)
+      pg->gj_fit = 1;
+    (void)hipGetLastError();
+  }
+  if (pg->gj_fit == 1) {
+    GjArgs gj;
+    gj.Ac = c.Ac; gj.slots = pg->d_gjslots.p; gj.bar = pg->d_bar.p; gj.n_c = c.n_c; gj.na = c.na;
+    const char *da = lslam::debug_env("LSLAM_DEBUG_GJ_ABORT");  // test hook (LSLAM_DEBUG_HOOKS=1)
+    gj.debug_abort = da ? std::atoi(da) : -1;
+    bool aborted = false;
+    rc = launch_persistent(pg, (const void *)pgc_gj_persistent_kernel, GJ_BLOCK, 0, &gj, pg->d_gjslots.p,
+                           (size_t)c.na * 6 * c.n_c, nullptr, &aborted);
+    if (rc) return rc;
+    if (aborted) {  // the launch loop inverts A_c, assembled once more (a kernel that timed out wrote nothing back, but
+                    // nothing here relies on that)
+      record_fallback(pg, &pg->gj_fit, "Gauss-Jordan kernel timed out");
+      rc = assemble_coarse(pg, s);
+      if (rc) return rc;
+    }
+  }
+  if (pg->gj_fit != 1) {
     const size_t nn = (size_t)c.n_c * c.n_c;
-    const bool no_reuse = pg->env_no_reuse;  // A/B switch (LSLAM_PG_NO_REUSE, read when the graph was created)
-    bool rebuild = !pg->coarse_valid || no_reuse;
-    if (!rebuild) {
-      const double ratio = lambda > pg->coarse_lambda ? lambda / pg->coarse_lambda : pg->coarse_lambda / lambda;
-      rebuild = !(ratio <= 10.0) || (pg->coarse_fresh_iters > 0 && 10 * pg->coarse_last_iters > 13 * pg->coarse_fresh_iters);
-    }
-    fresh_inverse = rebuild;
-    if (!pg->d_Ac.p) {  // first solve with the second level: its dense matrix and scratch
-      PG_TRY(pg->d_Ac.alloc(nn));
-      PG_TRY(pg->d_gj.alloc((size_t)12 * pg->n_c + 36));
-      c.Ac = pg->d_Ac.p;
-      c.Rbuf = pg->d_gj.p; c.Cbuf = pg->d_gj.p + (size_t)6 * pg->n_c; c.Bbuf = pg->d_gj.p + (size_t)12 * pg->n_c;
-    }
-    if (rebuild) {
-    hipLaunchKernelGGL(pgc_P_kernel, dim3((pg->n_v + 127) / 128), dim3(128), 0, pg->stream, c);
-    PG_TRY(hipMemsetAsync(c.Ac, 0, nn * sizeof(double), pg->stream));
-    hipLaunchKernelGGL(pgc_assemble_kernel, dim3(c.n_cb), dim3(64), 0, pg->stream, c, pg->d_vals.p, pg->d_row_of.p, pg->d_row_col.p, n_items);
-    if (pg->gj_fit < 0) {  // the persistent inverse when a workgroup per aggregate is co-resident and the row fits its registers
-      pg->gj_fit = 0;
-      const bool off = pg->env_persistent_off;
-      hipDeviceProp_t prop;
-      int per_cu = 0;
-      if (!off && c.n_c <= GJ_CREG * GJ_BLOCK && hipGetDeviceProperties(&prop, pg->device) == hipSuccess &&
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pgc_gj_persistent_kernel, GJ_BLOCK, 0) == hipSuccess &&
-          (long)per_cu * prop.multiProcessorCount >= c.na &&
-          pg->d_gjslots.alloc((size_t)c.na * 6 * c.n_c) == hipSuccess)
-        pg->gj_fit = 1;
-      (void)hipGetLastError();
-    }
-    if (pg->gj_fit == 1) {
-      GjArgs gj;
-      gj.Ac = c.Ac; gj.slots = pg->d_gjslots.p; gj.bar = pg->d_bar.p; gj.n_c = c.n_c; gj.na = c.na;
-      {
-        const char *da = lslam::debug_env("LSLAM_DEBUG_GJ_ABORT");  // test hook (LSLAM_DEBUG_HOOKS=1)
-        gj.debug_abort = da ? std::atoi(da) : -1;
-      }
-      PG_TRY(hipMemsetAsync(pg->d_bar.p, 0, 2 * sizeof(unsigned), pg->stream));
-      PG_TRY(hipMemsetD32Async((hipDeviceptr_t)pg->d_gjslots.p, (int)PK_SENT32, (size_t)c.na * 6 * c.n_c * 2, pg->stream));
-      void *gargs[] = {(void *)&gj};
-      unsigned gbar[2] = {0, 0};
-      if (hipLaunchCooperativeKernel((const void *)pgc_gj_persistent_kernel, dim3((unsigned)c.na), dim3(GJ_BLOCK), gargs, 0, pg->stream) != hipSuccess) {
-        // no cooperative launch on this device / partition mode, or the runtime's residency count differs from the occupancy
-        // query: not an error of the solve -- the launch loop inverts A_c (which is untouched)
-        (void)hipGetLastError();
-        gbar[1] = 1;
-      } else {
-        PG_TRY(hipMemcpyAsync(gbar, pg->d_bar.p, sizeof(gbar), hipMemcpyDeviceToHost, pg->stream));
-        PG_TRY(hipStreamSynchronize(pg->stream));
-      }
-      if (gbar[1] != 0) {  // not all workgroups resident at once (see the PCG kernel's fallback): the launch loop inverts A_c,
-                           // assembled once more (a kernel that timed out wrote nothing back, but nothing here relies on that)
-        if (pg->env_debug) fprintf(stderr, "[lslam pg] persistent Gauss-Jordan kernel timed out: launch loop from here on\n");
-        pg->gj_fit = 0;
-        pg->pk_timeouts++;
-        pg->fell_back = true;
-        PG_TRY(hipMemsetAsync(c.Ac, 0, nn * sizeof(double), pg->stream));
-        hipLaunchKernelGGL(pgc_assemble_kernel, dim3(c.n_cb), dim3(64), 0, pg->stream, c, pg->d_vals.p, pg->d_row_of.p, pg->d_row_col.p, n_items);
-      }
-    }
-    if (pg->gj_fit != 1) {
     for (int k = 0; k < c.na; ++k) {
       hipLaunchKernelGGL(pgc_gj_pivot_kernel, dim3(1), dim3(256), 0, pg->stream, c, k);
       hipLaunchKernelGGL(pgc_gj_update_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, pg->stream, c, k);
     }
-    }
-    PG_TRY(hipGetLastError());
-    pg->coarse_valid = true;
-    pg->coarse_lambda = lambda;
-    pg->coarse_fresh_iters = 0;
-    pg->coarse_setups++;
-    }
-    pg->coarse_solves++;
   }
-  a.item_begin = 0;
-  a.item_end = (int)n_items;
-  a.block_begin = 0;
-  // ---- row-sharded solve: several GPUs share ONE solve of a large graph (beyond "replicated solve") ----------
-  // Block-Jacobi PCG only (the dense second level is a single-device structure), launch per step; see pg_rs_direction_kernel.
-  if (pg->sharded() && pg->row_v0 >= 0 && !coarse) {
-    const int v0 = pg->row_v0, v1 = pg->row_v1;
-    const int r0 = v0 * 6, r1 = v1 * 6;
-    a.item_begin = pg->h_row_ptr[(size_t)v0] * 6;
-    a.item_end = pg->h_row_ptr[(size_t)v1] * 6;
-    a.block_begin = r0 / CG_ROWS;
-    const int nb_rows = (r1 - a.block_begin * CG_ROWS + CG_ROWS - 1) / CG_ROWS;   // row blocks of this rank
-    const int nb_items = (a.item_end - a.item_begin + PROD_BLOCK - 1) / PROD_BLOCK;  // item blocks of this rank
-    double *X = pg->xchg();  // [z (6 n_v) | rz | rr | pq | ... (8) | per rank: its part of rz, rr]
-    double *z_own = a.z;     // init runs replicated on the ordinary z
-    // The exchange: an all-gather of the owned segments when the transport has one and the ranks' rows are the canonical
-    // partition (every rank can then name every segment without asking); else the zero-padded all-reduce.
-    int g_rank = 0, g_world = 1;
-    bool gather = pg->gather_transport(&g_rank, &g_world) && g_world >= 1 && g_world <= lslam_pg::RS_MAX_WORLD;
-    std::vector<int64_t> z_offs, s_offs;
-    {
-      // Gather or all-reduce is ONE decision of all ranks: a rank that gathered (grouped broadcasts) while another all-reduced
-      // would hang the solve.  lslam_pg_set_row_shard accepts any whole-block range and a rank may have no gather transport at
-      // all, so no rank can tell from what it holds what the others will do: EVERY rank of EVERY row-sharded solve sums a
-      // "not from me" flag through the linearisation's transport -- 1 without a gather transport or with a range that is not
-      // the canonical one -- and the ranks gather only if nobody raised it.  (Cached per rank this was itself a collective
-      // that some ranks could skip: a rank whose setting had not changed did not enter it.  One scalar all-reduce per solve of
-      // ~100 iterations with two collectives each costs nothing.)
-      int cb = -1, ce = -1;
-      if (gather) lslam_pg_row_shard_range(pg->n_v, g_rank, g_world, &cb, &ce);
-      double flag = (gather && cb == v0 && ce == v1) ? 0.0 : 1.0;
-      PG_TRY(hipMemcpyAsync(X + n6 + 7, &flag, sizeof(double), hipMemcpyHostToDevice, pg->stream));
-      PG_TRY(hipStreamSynchronize(pg->stream));  // (flag is a local)
-      int rc_a = pg->reduce(X + n6 + 7, 1);
-      if (rc_a) return rc_a;
-      PG_TRY(hipMemcpyAsync(&flag, X + n6 + 7, sizeof(double), hipMemcpyDeviceToHost, pg->stream));
-      PG_TRY(hipStreamSynchronize(pg->stream));
-      pg->rs_agree_gather = flag == 0.0;
+  PG_TRY(hipGetLastError());
+  pg->coarse_valid = true;
+  pg->coarse_lambda = s.lambda;
+  pg->coarse_fresh_iters = 0;
+  pg->coarse_setups++;
+  return LSLAM_OK;
+}
+
+// The launch-per-step PCG loops' common form: 50 iterations enqueued by step(k), then pg_cg_check_kernel and one read-back
+// of the scalars (converged? iterations done) -- one host wait per 50 iterations.
+template <typename Step>
+int run_cg_chunks(lslam_pg *pg, const CgArgs &a, int max_cg, Step step, int *done_iters) {
+  double scal[8] = {0};
+  *done_iters = 0;
+  for (int it = 0; it < max_cg;) {
+    const int chunk = std::min(50, max_cg - it);
+    for (int k = it; k < it + chunk; ++k) {
+      const int rc = step(k);
+      if (rc) return rc;
     }
-    if (gather) {
-      gather = pg->rs_agree_gather;
-      z_offs.resize((size_t)g_world + 1);
-      s_offs.resize((size_t)g_world + 1);
-      for (int r = 0; r <= g_world; ++r) {
-        int b = pg->n_v, e = pg->n_v;
-        if (r < g_world) lslam_pg_row_shard_range(pg->n_v, r, g_world, &b, &e);
-        z_offs[(size_t)r] = (int64_t)b * 6;
-        s_offs[(size_t)r] = 2 * (int64_t)r;
-      }
+    it += chunk;
+    hipLaunchKernelGGL(pg_cg_check_kernel, dim3(1), dim3(CG_BLOCK), 0, pg->stream, a, it);
+    PG_TRY(hipMemcpyAsync(scal, pg->d_scal.p, sizeof(scal), hipMemcpyDeviceToHost, pg->stream));
+    PG_TRY(hipStreamSynchronize(pg->stream));
+    *done_iters = (int)scal[6];
+    if (scal[5] != 0.0) break;
+  }
+  return LSLAM_OK;
+}
+
+// Gather or all-reduce is ONE decision of all ranks: a rank that gathered (grouped broadcasts) while another all-reduced
+// would hang the solve.  lslam_pg_set_row_shard accepts any whole-block range and a rank may have no gather transport at
+// all, so no rank can tell from what it holds what the others will do: EVERY rank of EVERY row-sharded solve sums a
+// "not from me" flag through the linearisation's transport -- 1 without a gather transport or with a range that is not
+// the canonical one -- and the ranks gather only if nobody raised it.  (Cached per rank this was itself a collective
+// that some ranks could skip: a rank whose setting had not changed did not enter it.  One scalar all-reduce per solve of
+// ~100 iterations with two collectives each costs nothing.)
+int agree_on_gather(lslam_pg *pg, bool can_gather, double *slot, bool *agreed) {
+  double flag = can_gather ? 0.0 : 1.0;
+  PG_TRY(hipMemcpyAsync(slot, &flag, sizeof(double), hipMemcpyHostToDevice, pg->stream));
+  PG_TRY(hipStreamSynchronize(pg->stream));  // (flag is a local)
+  const int rc = pg->reduce(slot, 1);
+  if (rc) return rc;
+  PG_TRY(hipMemcpyAsync(&flag, slot, sizeof(double), hipMemcpyDeviceToHost, pg->stream));
+  PG_TRY(hipStreamSynchronize(pg->stream));
+  *agreed = flag == 0.0;
+  return LSLAM_OK;
+}
+
+// ---- row-sharded solve: several GPUs share ONE solve of a large graph (beyond "replicated solve") ----------
+// Block-Jacobi PCG only (the dense second level is a single-device structure), launch per step; see pg_rs_direction_kernel.
+int solve_row_sharded(lslam_pg *pg, SolveCall &s, int *iters_out) {
+  CgArgs &a = s.a;
+  const int n6 = a.n6;
+  const int v0 = pg->row_v0, v1 = pg->row_v1;
+  const int r0 = v0 * 6, r1 = v1 * 6;
+  a.item_begin = pg->h_row_ptr[(size_t)v0] * 6;
+  a.item_end = pg->h_row_ptr[(size_t)v1] * 6;
+  a.block_begin = r0 / CG_ROWS;
+  const int nb_rows = (r1 - a.block_begin * CG_ROWS + CG_ROWS - 1) / CG_ROWS;   // row blocks of this rank
+  const int nb_items = (a.item_end - a.item_begin + PROD_BLOCK - 1) / PROD_BLOCK;  // item blocks of this rank
+  double *X = pg->xchg();  // [z (6 n_v) | rz | rr | pq | ... (8) | per rank: its part of rz, rr]
+  double *z_own = a.z;     // init runs replicated on the ordinary z
+  // The exchange: an all-gather of the owned segments when the transport has one and the ranks' rows are the canonical
+  // partition (every rank can then name every segment without asking); else the zero-padded all-reduce.
+  int g_rank = 0, g_world = 1;
+  bool gather = pg->gather_transport(&g_rank, &g_world) && g_world >= 1 && g_world <= lslam_pg::RS_MAX_WORLD;
+  int cb = -1, ce = -1;
+  if (gather) lslam_pg_row_shard_range(pg->n_v, g_rank, g_world, &cb, &ce);
+  bool agreed = false;
+  int rc = agree_on_gather(pg, gather && cb == v0 && ce == v1, X + n6 + 7, &agreed);
+  if (rc) return rc;
+  std::vector<int64_t> z_offs, s_offs;
+  if (gather) {
+    gather = agreed;
+    z_offs.resize((size_t)g_world + 1);
+    s_offs.resize((size_t)g_world + 1);
+    for (int r = 0; r <= g_world; ++r) {
+      int b = pg->n_v, e = pg->n_v;
+      if (r < g_world) lslam_pg_row_shard_range(pg->n_v, r, g_world, &b, &e);
+      z_offs[(size_t)r] = (int64_t)b * 6;
+      s_offs[(size_t)r] = 2 * (int64_t)r;
     }
-    double *tail = X + n6 + 8;
-    double *const g_bufs[2] = {X, tail};
-    const int64_t *const g_offs[2] = {z_offs.data(), s_offs.data()};
-    // x = 0, r = b, z = M^-1 b and their sums, on every row by every rank: b is complete everywhere after the linearisation's
-    // all-reduce, so this needs no exchange
-    hipLaunchKernelGGL(pg_cg_init_kernel, g, blk, 0, pg->stream, a);
-    hipLaunchKernelGGL(pg_cg_init2_kernel, dim3(1), blk, 0, pg->stream, a);
-    hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rz[0], pg->n_cg_blocks, 1, X + n6);
-    hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rr, pg->n_cg_blocks, 1, X + n6 + 1);
-    hipLaunchKernelGGL(pg_rs_copy_kernel, dim3(1), dim3(64), 0, pg->stream, (const double *)(X + n6), a.part_rz[0], a.part_rr, (double *)nullptr);
-    PG_TRY(hipMemcpyAsync(X, z_own, (size_t)n6 * sizeof(double), hipMemcpyDeviceToDevice, pg->stream));
-    a.z = X;  // from here on z lives in the exchange area: own rows written by the update, the others arrive by the all-reduce
-    a.n_parts = 1;
-    a.n_pblocks = 1;
-    const dim3 gall((n6 + 255) / 256), b256(256);
-    double scal[8] = {0};
-    int done_iters = 0;
-    for (int it = 0; it < max_cg;) {
-      const int chunk = std::min(50, max_cg - it);
-      for (int k = it; k < it + chunk; ++k) {
-        hipLaunchKernelGGL(pg_rs_direction_kernel, gall, b256, 0, pg->stream, a, k);
-        a.n_pblocks = 1;
-        hipLaunchKernelGGL(pg_cg_prod_kernel, dim3(std::max(nb_items, 1)), dim3(PROD_BLOCK), 0, pg->stream, a, k);
-        hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_pq, nb_items, 1, X + n6 + 2);
-        PG_TRY(hipGetLastError());
-        int rc = pg->reduce(X + n6 + 2, 1);  // p . A p
-        if (rc) return rc;
-        hipLaunchKernelGGL(pg_rs_copy_kernel, dim3(1), dim3(64), 0, pg->stream, (const double *)(X + n6 + 2), a.part_pq, (double *)nullptr, (double *)nullptr);
-        hipLaunchKernelGGL(pg_cg_update_kernel, dim3(std::max(nb_rows, 1)), blk, 0, pg->stream, a, k);
-        if (gather) {  // own rows of z are in place; own parts of r . z and r . r go to this rank's slot behind them
-          hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rz[(k + 1) & 1], nb_rows, 1, tail + 2 * g_rank);
-          hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rr, nb_rows, 1, tail + 2 * g_rank + 1);
-          PG_TRY(hipGetLastError());
-          rc = pg->gather(2, g_bufs, g_offs, g_world);
-          if (rc) return rc;
-          hipLaunchKernelGGL(pg_rs_tail_sum_kernel, dim3(1), dim3(64), 0, pg->stream, X + n6, (const double *)tail, g_world);
-        } else {
-          hipLaunchKernelGGL(pg_rs_zero_others_kernel, gall, b256, 0, pg->stream, X, n6, r0, r1);
-          hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rz[(k + 1) & 1], nb_rows, 1, X + n6);
-          hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rr, nb_rows, 1, X + n6 + 1);
-          PG_TRY(hipGetLastError());
-          rc = pg->reduce(X, (size_t)n6 + 2);  // z gathered, r . z and r . r summed
-          if (rc) return rc;
-        }
-        hipLaunchKernelGGL(pg_rs_copy_kernel, dim3(1), dim3(64), 0, pg->stream, (const double *)(X + n6), a.part_rz[(k + 1) & 1], a.part_rr, (double *)nullptr);
-      }
-      it += chunk;
-      hipLaunchKernelGGL(pg_cg_check_kernel, dim3(1), blk, 0, pg->stream, a, it);
-      PG_TRY(hipMemcpyAsync(scal, pg->d_scal.p, sizeof(scal), hipMemcpyDeviceToHost, pg->stream));
-      PG_TRY(hipStreamSynchronize(pg->stream));
-      done_iters = (int)scal[6];
-      if (scal[5] != 0.0) break;
-    }
-    // the solution: every rank's rows, gathered the same way
-    hipLaunchKernelGGL(pg_rs_pack_kernel, gall, b256, 0, pg->stream, (const double *)pg->d_x.p, X, n6, r0, r1);
+  }
+  double *tail = X + n6 + 8;
+  double *const g_bufs[2] = {X, tail};
+  const int64_t *const g_offs[2] = {z_offs.data(), s_offs.data()};
+  const dim3 blk(CG_BLOCK), gall((n6 + 255) / 256), b256(256);
+  // x = 0, r = b, z = M^-1 b and their sums, on every row by every rank: b is complete everywhere after the linearisation's
+  // all-reduce, so this needs no exchange
+  hipLaunchKernelGGL(pg_cg_init_kernel, dim3(pg->n_cg_blocks), blk, 0, pg->stream, a);
+  hipLaunchKernelGGL(pg_cg_init2_kernel, dim3(1), blk, 0, pg->stream, a);
+  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rz[0], pg->n_cg_blocks, 1, X + n6);
+  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rr, pg->n_cg_blocks, 1, X + n6 + 1);
+  hipLaunchKernelGGL(pg_rs_copy_kernel, dim3(1), dim3(64), 0, pg->stream, (const double *)(X + n6), a.part_rz[0], a.part_rr, (double *)nullptr);
+  PG_TRY(hipMemcpyAsync(X, z_own, (size_t)n6 * sizeof(double), hipMemcpyDeviceToDevice, pg->stream));
+  a.z = X;  // from here on z lives in the exchange area: own rows written by the update, the others arrive by the all-reduce
+  a.n_parts = 1;
+  a.n_pblocks = 1;
+  int done_iters = 0;
+  rc = run_cg_chunks(pg, a, s.max_cg, [&](int k) -> int {
+    hipLaunchKernelGGL(pg_rs_direction_kernel, gall, b256, 0, pg->stream, a, k);
+    hipLaunchKernelGGL(pg_cg_prod_kernel, dim3(std::max(nb_items, 1)), dim3(PROD_BLOCK), 0, pg->stream, a, k);
+    hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_pq, nb_items, 1, X + n6 + 2);
     PG_TRY(hipGetLastError());
-    int rc = gather ? pg->gather(1, g_bufs, g_offs, g_world) : pg->reduce(X, (size_t)n6);
+    int rc = pg->reduce(X + n6 + 2, 1);  // p . A p
     if (rc) return rc;
-    PG_TRY(hipMemcpyAsync(pg->d_x.p, X, (size_t)n6 * sizeof(double), hipMemcpyDeviceToDevice, pg->stream));
-    *iters_out = done_iters;
-    pg->total_solves++;
-    pg->rs_solves++;
-    pg->rs_gathered += gather ? 1 : 0;
+    hipLaunchKernelGGL(pg_rs_copy_kernel, dim3(1), dim3(64), 0, pg->stream, (const double *)(X + n6 + 2), a.part_pq, (double *)nullptr, (double *)nullptr);
+    hipLaunchKernelGGL(pg_cg_update_kernel, dim3(std::max(nb_rows, 1)), blk, 0, pg->stream, a, k);
+    if (gather) {  // own rows of z are in place; own parts of r . z and r . r go to this rank's slot behind them
+      hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rz[(k + 1) & 1], nb_rows, 1, tail + 2 * g_rank);
+      hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rr, nb_rows, 1, tail + 2 * g_rank + 1);
+      PG_TRY(hipGetLastError());
+      rc = pg->gather(2, g_bufs, g_offs, g_world);
+      if (rc) return rc;
+      hipLaunchKernelGGL(pg_rs_tail_sum_kernel, dim3(1), dim3(64), 0, pg->stream, X + n6, (const double *)tail, g_world);
+    } else {
+      hipLaunchKernelGGL(pg_rs_zero_others_kernel, gall, b256, 0, pg->stream, X, n6, r0, r1);
+      hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rz[(k + 1) & 1], nb_rows, 1, X + n6);
+      hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, a.part_rr, nb_rows, 1, X + n6 + 1);
+      PG_TRY(hipGetLastError());
+      rc = pg->reduce(X, (size_t)n6 + 2);  // z gathered, r . z and r . r summed
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL(pg_rs_copy_kernel, dim3(1), dim3(64), 0, pg->stream, (const double *)(X + n6), a.part_rz[(k + 1) & 1], a.part_rr, (double *)nullptr);
+    return LSLAM_OK;
+  }, &done_iters);
+  if (rc) return rc;
+  // the solution: every rank's rows, gathered the same way
+  hipLaunchKernelGGL(pg_rs_pack_kernel, gall, b256, 0, pg->stream, (const double *)pg->d_x.p, X, n6, r0, r1);
+  PG_TRY(hipGetLastError());
+  rc = gather ? pg->gather(1, g_bufs, g_offs, g_world) : pg->reduce(X, (size_t)n6);
+  if (rc) return rc;
+  PG_TRY(hipMemcpyAsync(pg->d_x.p, X, (size_t)n6 * sizeof(double), hipMemcpyDeviceToDevice, pg->stream));
+  // this path's own accounting: it never runs with the second level, and finish_solve's rules about it do not apply
+  *iters_out = done_iters;
+  pg->total_solves++;
+  pg->rs_solves++;
+  pg->rs_gathered += gather ? 1 : 0;
+  return LSLAM_OK;
+}
+
+// The persistent kernel when the graph fits: one workgroup per aggregate, all co-resident, LDS for its columns / items.
+void decide_pk_fit(lslam_pg *pg) {
+  if (pg->pk_fit >= 0) return;
+  pg->pk_fit = 0;
+  if (!pg->env_persistent_off && pg->n_agg <= PK_BLOCK /* one thread per aggregate sums the partials */ &&
+      pg->pk_lds_bytes <= 150 * 1024 &&
+      hipFuncSetAttribute((const void *)pg_pcg_persistent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)pg->pk_lds_bytes) == hipSuccess &&
+      fits_co_resident(pg, (const void *)pg_pcg_persistent_kernel, PK_BLOCK, pg->pk_lds_bytes, pg->n_agg))
+    pg->pk_fit = 1;
+  (void)hipGetLastError();
+}
+
+// The whole PCG loop in one launch.  *finished: it ran to its end and *done_iters counts; else nothing was written that
+// the launch-per-step loop reads, and this graph stays on that loop from here on.
+int solve_persistent(lslam_pg *pg, const SolveCall &s, bool *finished, int *done_iters) {
+  const int n6 = s.a.n6;
+  PkArgs k;
+  k.vals = pg->d_vals.p; k.minv = pg->d_minv.p; k.b = pg->b();
+  k.x = pg->d_x.p; k.p0 = pg->d_p.p; k.p1 = pg->d_p.p + n6;
+  k.agg_ptr = pg->d_agg_ptr.p; k.agg_mem = pg->d_agg_mem.p;
+  k.bent_ptr = pg->d_bent_ptr.p; k.bent = pg->d_bent.p; k.blc = pg->d_blc.p; k.bmptr = pg->d_bmptr.p;
+  k.bcol_ptr = pg->d_bcol_ptr.p; k.bcol = pg->d_bcol.p;
+  k.P = pg->d_P.p; k.Ainv = pg->d_Ac.p;
+  k.rc0 = pg->d_pk.p; k.rc1 = pg->d_pk.p + pg->n_c;
+  double *slots = pg->d_pk.p + 2 * (size_t)pg->n_c;
+  const size_t n_slots = 2 * (size_t)n6 + 6 * (size_t)pg->n_agg + 2 * (size_t)pg->n_c;
+  k.zA = slots; k.rzA = k.zA + 2 * (size_t)n6; k.rrA = k.rzA + 2 * pg->n_agg; k.pqB = k.rrA + 2 * pg->n_agg;
+  k.qcB = k.pqB + 2 * pg->n_agg;
+  k.scal = pg->d_scal.p; k.bar = pg->d_bar.p;
+  k.n_items = s.n_items;
+  k.n6 = n6; k.n_agg = pg->n_agg; k.n_c = pg->n_c; k.coarse = s.coarse ? 1 : 0; k.max_iter = s.max_cg;
+  k.lds_cols = pg->pk_lds_cols; k.lds_items = pg->pk_lds_items;
+  k.tol2 = s.tol * s.tol;
+  const char *da = lslam::debug_env("LSLAM_DEBUG_PG_ABORT");  // test hook (LSLAM_DEBUG_HOOKS=1)
+  k.debug_abort = da ? std::atoi(da) : -1;
+  double scal[8] = {0};
+  bool aborted = false;
+  const int rc = launch_persistent(pg, (const void *)pg_pcg_persistent_kernel, PK_BLOCK, pg->pk_lds_bytes, &k, slots, n_slots,
+                                   scal, &aborted);
+  if (rc) return rc;
+  *finished = !aborted;
+  if (aborted) {
+    record_fallback(pg, &pg->pk_fit, "PCG kernel timed out in a grid exchange");
     return LSLAM_OK;
   }
-  // The persistent kernel when the graph fits: one workgroup per aggregate, all co-resident, LDS for its columns / items.
-  if (pg->pk_fit < 0) {
-    pg->pk_fit = 0;
-    const bool off = pg->env_persistent_off;
-    hipDeviceProp_t prop;
-    int per_cu = 0;
-    if (!off && pg->n_agg <= PK_BLOCK /* one thread per aggregate sums the partials */ && pg->pk_lds_bytes <= 150 * 1024 &&
-        hipGetDeviceProperties(&prop, pg->device) == hipSuccess &&
-        hipFuncSetAttribute((const void *)pg_pcg_persistent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)pg->pk_lds_bytes) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pg_pcg_persistent_kernel, PK_BLOCK, pg->pk_lds_bytes) == hipSuccess &&
-        (long)per_cu * prop.multiProcessorCount >= pg->n_agg)
-      pg->pk_fit = 1;
-    (void)hipGetLastError();
-  }
-  pg->total_solves++;
-  if (pg->pk_fit == 1) {
-    PkArgs k;
-    k.vals = pg->d_vals.p; k.minv = pg->d_minv.p; k.b = pg->b();
-    k.x = pg->d_x.p; k.p0 = pg->d_p.p; k.p1 = pg->d_p.p + n6;
-    k.agg_ptr = pg->d_agg_ptr.p; k.agg_mem = pg->d_agg_mem.p;
-    k.bent_ptr = pg->d_bent_ptr.p; k.bent = pg->d_bent.p; k.blc = pg->d_blc.p; k.bmptr = pg->d_bmptr.p;
-    k.bcol_ptr = pg->d_bcol_ptr.p; k.bcol = pg->d_bcol.p;
-    k.P = pg->d_P.p; k.Ainv = pg->d_Ac.p;
-    k.rc0 = pg->d_pk.p; k.rc1 = pg->d_pk.p + pg->n_c;
-    double *slots = pg->d_pk.p + 2 * (size_t)pg->n_c;
-    const size_t n_slots = 2 * (size_t)n6 + 6 * (size_t)pg->n_agg + 2 * (size_t)pg->n_c;
-    k.zA = slots; k.rzA = k.zA + 2 * (size_t)n6; k.rrA = k.rzA + 2 * pg->n_agg; k.pqB = k.rrA + 2 * pg->n_agg;
-    k.qcB = k.pqB + 2 * pg->n_agg;
-    k.scal = pg->d_scal.p; k.bar = pg->d_bar.p;
-    k.n_items = n_items;
-    k.n6 = n6; k.n_agg = pg->n_agg; k.n_c = pg->n_c; k.coarse = coarse ? 1 : 0; k.max_iter = max_cg;
-    k.lds_cols = pg->pk_lds_cols; k.lds_items = pg->pk_lds_items;
-    k.tol2 = tol * tol;
-    {
-      const char *da = lslam::debug_env("LSLAM_DEBUG_PG_ABORT");  // test hook (LSLAM_DEBUG_HOOKS=1)
-      k.debug_abort = da ? std::atoi(da) : -1;
-    }
-    PG_TRY(hipMemsetAsync(pg->d_bar.p, 0, 2 * sizeof(unsigned), pg->stream));
-    PG_TRY(hipMemsetD32Async((hipDeviceptr_t)slots, (int)PK_SENT32, 2 * n_slots, pg->stream));
-    void *kargs[] = {(void *)&k};
-    double scal[8] = {0};
-    unsigned bar[2] = {0, 0};
-    if (hipLaunchCooperativeKernel((const void *)pg_pcg_persistent_kernel, dim3((unsigned)pg->n_agg), dim3(PK_BLOCK), kargs,
-                                   (unsigned)pg->pk_lds_bytes, pg->stream) != hipSuccess) {
-      (void)hipGetLastError();  // as for the coarse inverse: a refused cooperative launch means the launch loop, not a failed solve
-      bar[1] = 1;
-    } else {
-      PG_TRY(hipMemcpyAsync(scal, pg->d_scal.p, sizeof(scal), hipMemcpyDeviceToHost, pg->stream));
-      PG_TRY(hipMemcpyAsync(bar, pg->d_bar.p, sizeof(bar), hipMemcpyDeviceToHost, pg->stream));
-      PG_TRY(hipStreamSynchronize(pg->stream));
-    }
-    if (bar[1] == 0) {
-      const int done_iters = (int)scal[6];
-      *iters_out = done_iters;
-      pg->fused_solves++;
-      if (done_iters > 300) pg->coarse_on = true;
-      if (coarse) {
-        if (fresh_inverse) pg->coarse_fresh_iters = done_iters;
-        pg->coarse_last_iters = done_iters;
-      }
-      return LSLAM_OK;
-    }
-    // An exchange ran into its spin limit: the workgroups were not all resident at once (another process's persistent
-    // kernel on the same device can do that -- cooperative launches are not coordinated across processes).  Nothing was
-    // written that the launch-per-step loop below reads; this graph stays on that loop from here on.
-    if (pg->env_debug) fprintf(stderr, "[lslam pg] persistent PCG kernel timed out in a grid exchange: launch loop from here on\n");
-    pg->pk_fit = 0;
-    pg->pk_timeouts++;
-    pg->fell_back = true;
-  }
+  *done_iters = (int)scal[6];
+  pg->fused_solves++;
+  return LSLAM_OK;
+}
+
+// The same PCG, a launch per step (graphs that do not fit the persistent kernel, and after a fallback).
+int solve_launch_loop(lslam_pg *pg, const SolveCall &s, int *done_iters) {
+  const CgArgs &a = s.a;
+  const CoarseArgs &c = s.c;
+  const dim3 g(pg->n_cg_blocks), blk(CG_BLOCK);
   auto coarse_correct = [&](int k) {  // z += P A_c^-1 P^T r and the matching share of r.z, entering iteration k + 1
-    if (!coarse) return;
+    if (!s.coarse) return;
     hipLaunchKernelGGL(pgc_restrict_kernel, dim3(c.na), dim3(64), 0, pg->stream, c, (const double *)a.r);
     hipLaunchKernelGGL(pgc_mvp_kernel, dim3(c.na), dim3(256), 0, pg->stream, c, a.z, a.part_rz[(k + 1) & 1] + pg->n_cg_blocks);
   };
   hipLaunchKernelGGL(pg_cg_init_kernel, g, blk, 0, pg->stream, a);
   hipLaunchKernelGGL(pg_cg_init2_kernel, dim3(1), blk, 0, pg->stream, a);
   coarse_correct(-1);
-  double scal[8] = {0};
-  int done_iters = 0;
-  for (int it = 0; it < max_cg;) {
-    const int chunk = std::min(50, max_cg - it);
-    for (int k = it; k < it + chunk; ++k) {
-      hipLaunchKernelGGL(pg_cg_prod_kernel, dim3(a.n_pblocks), dim3(PROD_BLOCK), 0, pg->stream, a, k);
-      hipLaunchKernelGGL(pg_cg_update_kernel, g, blk, 0, pg->stream, a, k);
-      coarse_correct(k);
-    }
-    it += chunk;
-    hipLaunchKernelGGL(pg_cg_check_kernel, dim3(1), blk, 0, pg->stream, a, it);
-    PG_TRY(hipMemcpyAsync(scal, pg->d_scal.p, sizeof(scal), hipMemcpyDeviceToHost, pg->stream));
-    PG_TRY(hipStreamSynchronize(pg->stream));
-    done_iters = (int)scal[6];
-    if (scal[5] != 0.0) break;
-  }
+  const int rc = run_cg_chunks(pg, a, s.max_cg, [&](int k) -> int {
+    hipLaunchKernelGGL(pg_cg_prod_kernel, dim3(a.n_pblocks), dim3(PROD_BLOCK), 0, pg->stream, a, k);
+    hipLaunchKernelGGL(pg_cg_update_kernel, g, blk, 0, pg->stream, a, k);
+    coarse_correct(k);
+    return LSLAM_OK;
+  }, done_iters);
+  if (rc) return rc;
   PG_TRY(hipGetLastError());
+  return LSLAM_OK;
+}
+
+// What a finished replicated solve leaves for the next one.
+void finish_solve(lslam_pg *pg, const SolveCall &s, int done_iters, int *iters_out) {
   *iters_out = done_iters;
   if (done_iters > 300) pg->coarse_on = true;  // ill-conditioned from here on: later solves of this graph take the second level
-  if (coarse) {
-    if (fresh_inverse) pg->coarse_fresh_iters = done_iters;
+  if (s.coarse) {
+    if (s.fresh_inverse) pg->coarse_fresh_iters = done_iters;
     pg->coarse_last_iters = done_iters;
   }
+}
+
+// (H + lambda I) dx = b by block-Jacobi PCG, with the second level when it is on; returns iterations
+int solve(lslam_pg *pg, double lambda, int max_cg, double tol, int *iters_out) {
+  SolveCall s;
+  s.n_items = (size_t)pg->n_entries * 6;
+  s.lambda = lambda;
+  s.max_cg = max_cg;
+  s.tol = tol;
+  // second level (see pgc_P_kernel): on when forced, or -- automatic -- once a solve of this graph needed many iterations
+  s.coarse = pg->coarse_mode == 1 || (pg->coarse_mode < 0 && pg->coarse_on);
+  int rc = expand_and_precondition(pg, s);
+  if (rc) return rc;
+  make_cg_args(pg, s);
+  if (s.coarse) {
+    rc = make_coarse_args(pg, s);
+    if (rc) return rc;
+    s.fresh_inverse = coarse_needs_rebuild(pg, lambda);
+    if (s.fresh_inverse) rc = build_coarse_inverse(pg, s);
+    if (rc) return rc;
+    pg->coarse_solves++;
+  }
+  if (pg->sharded() && pg->row_v0 >= 0 && !s.coarse) return solve_row_sharded(pg, s, iters_out);
+  decide_pk_fit(pg);
+  pg->total_solves++;
+  int done_iters = 0;
+  bool finished = false;
+  if (pg->pk_fit == 1) rc = solve_persistent(pg, s, &finished, &done_iters);
+  if (rc) return rc;
+  if (!finished) rc = solve_launch_loop(pg, s, &done_iters);
+  if (rc) return rc;
+  finish_solve(pg, s, done_iters, iters_out);
+  return LSLAM_OK;
+}
+
+// ---- what lslam_pg_create builds on the host, before anything is uploaded: the builders below make no HIP call ------------
+struct GraphLayout {
+  int n_v = 0, n_e = 0;
+  const int32_t *ij = nullptr;
+  std::vector<int32_t> off_pairs, edge_block;                        // number_offdiag_blocks
+  std::vector<int32_t> rptr, rcol, rsrc, rof;                        // build_solver_rows
+  std::vector<int32_t> agg_of, agg_ptr, agg_mem;                     // grow_aggregates, merge_pockets
+  std::vector<int32_t> cptr, cent, cab;                              // build_coarse_blocks
+  std::vector<int32_t> bent_ptr, bent, blc, bmptr, bcol_ptr, bcol;   // build_persistent_view
+  int max_cols = 0, max_items = 0;                                   // ... its widest aggregate
+  int n_off() const { return (int)(off_pairs.size() / 2); }
+  int n_agg() const { return (int)agg_ptr.size() - 1; }
+};
+
+// off-diagonal block ids: distinct (min,max) pairs in first-appearance order of a sorted map
+void number_offdiag_blocks(GraphLayout &L) {
+  const int32_t *ij = L.ij;
+  std::map<std::pair<int, int>, int> ids;
+  for (int e = 0; e < L.n_e; ++e) ids.emplace(std::minmax(ij[2 * e], ij[2 * e + 1]), 0);
+  int nid = 0;
+  for (auto &kv : ids) kv.second = nid++;
+  L.off_pairs.resize(2 * (size_t)nid);
+  for (auto &kv : ids) {
+    L.off_pairs[2 * kv.second] = kv.first.first;
+    L.off_pairs[2 * kv.second + 1] = kv.first.second;
+  }
+  L.edge_block.resize(L.n_e);
+  for (int e = 0; e < L.n_e; ++e) L.edge_block[e] = ids[std::minmax(ij[2 * e], ij[2 * e + 1])];
+}
+
+// solver block-CSR: row v = [diag, then neighbours in block-id order]
+void build_solver_rows(GraphLayout &L) {
+  const int n_v = L.n_v, nid = L.n_off();
+  std::vector<std::vector<std::pair<int, int>>> rows(n_v);  // (col, code)
+  for (int v = 0; v < n_v; ++v) rows[v].push_back({v, (v << 2) | 1});
+  for (int k = 0; k < nid; ++k) {
+    const int a = L.off_pairs[2 * k], b = L.off_pairs[2 * k + 1];
+    rows[a].push_back({b, ((n_v + k) << 2) | 0});
+    rows[b].push_back({a, ((n_v + k) << 2) | 2});
+  }
+  L.rptr.assign(n_v + 1, 0);
+  for (int v = 0; v < n_v; ++v) {
+    L.rptr[v + 1] = L.rptr[v] + (int)rows[v].size();
+    for (auto &pr : rows[v]) {
+      L.rcol.push_back(pr.first);
+      L.rsrc.push_back(pr.second);
+      L.rof.push_back(v);
+    }
+  }
+}
+
+// aggregates: breadth-first from the lowest unassigned vertex over the solver rows (neighbours in block-id order,
+// i.e. deterministic), at most `limit` members each
+void grow_aggregates(GraphLayout &L, int limit) {
+  const std::vector<int32_t> &rptr = L.rptr, &rcol = L.rcol;
+  std::vector<int32_t> &agg_of = L.agg_of, &agg_ptr = L.agg_ptr, &agg_mem = L.agg_mem;
+  agg_of.assign((size_t)L.n_v, -1);
+  agg_ptr.assign(1, 0);
+  for (int seed = 0; seed < L.n_v; ++seed) {
+    if (agg_of[(size_t)seed] >= 0) continue;
+    const int a = (int)agg_ptr.size() - 1;
+    const size_t first = agg_mem.size();
+    agg_of[(size_t)seed] = a;
+    agg_mem.push_back(seed);
+    for (size_t head = first; head < agg_mem.size() && (int)(agg_mem.size() - first) < limit; ++head) {
+      const int u = agg_mem[head];
+      for (int e = rptr[(size_t)u]; e < rptr[(size_t)u + 1] && (int)(agg_mem.size() - first) < limit; ++e) {
+        const int v = rcol[(size_t)e];
+        if (agg_of[(size_t)v] < 0) {
+          agg_of[(size_t)v] = a;
+          agg_mem.push_back(v);
+        }
+      }
+    }
+    agg_ptr.push_back((int32_t)agg_mem.size());
+  }
+}
+
+// Breadth-first growth leaves pockets: a handful of keyframes cut off between two full aggregates (59 of the bench
+// graph's 136 aggregates had fewer than eight members).  Each would be a workgroup of the persistent solver, a
+// participant of every grid exchange and six coarse unknowns of little use: a pocket joins the smallest adjacent
+// aggregate that has room for it (the growth stops at 7/8 of the limit G to leave that room).
+void merge_pockets(GraphLayout &L, int G) {
+  const std::vector<int32_t> &rptr = L.rptr, &rcol = L.rcol;
+  std::vector<int32_t> &agg_of = L.agg_of, &agg_ptr = L.agg_ptr, &agg_mem = L.agg_mem;
+  const int n0 = (int)agg_ptr.size() - 1;
+  std::vector<int> size(n0), into(n0);
+  for (int a = 0; a < n0; ++a) { size[a] = agg_ptr[(size_t)a + 1] - agg_ptr[(size_t)a]; into[a] = a; }
+  for (int a = 0; a < n0; ++a) {
+    if (size[a] > std::max(1, G / 8)) continue;
+    int best = -1;
+    for (int m = agg_ptr[(size_t)a]; m < agg_ptr[(size_t)a + 1]; ++m) {
+      const int u = agg_mem[(size_t)m];
+      for (int e = rptr[(size_t)u]; e < rptr[(size_t)u + 1]; ++e) {
+        int b = agg_of[(size_t)rcol[(size_t)e]];
+        while (into[b] != b) b = into[b];
+        if (b != a && size[b] + size[a] <= G && (best < 0 || size[b] < size[best] || (size[b] == size[best] && b < best))) best = b;
+      }
+    }
+    if (best >= 0) { into[a] = best; size[best] += size[a]; size[a] = 0; }
+  }
+  std::vector<int> newid(n0, -1);
+  int nn = 0;
+  for (int a = 0; a < n0; ++a) if (into[a] == a) newid[a] = nn++;
+  std::vector<std::vector<int32_t>> mem((size_t)nn);
+  for (int a = 0; a < n0; ++a) {  // the receiving aggregate's members first (its first member stays its origin), pockets after them in order
+    int b = a;
+    while (into[b] != b) b = into[b];
+    if (b == a)
+      for (int m = agg_ptr[(size_t)a]; m < agg_ptr[(size_t)a + 1]; ++m) mem[(size_t)newid[a]].push_back(agg_mem[(size_t)m]);
+  }
+  for (int a = 0; a < n0; ++a) {
+    int b = a;
+    while (into[b] != b) b = into[b];
+    if (b != a)
+      for (int m = agg_ptr[(size_t)a]; m < agg_ptr[(size_t)a + 1]; ++m) mem[(size_t)newid[b]].push_back(agg_mem[(size_t)m]);
+  }
+  agg_ptr.assign(1, 0);
+  agg_mem.clear();
+  for (int a = 0; a < nn; ++a) {
+    for (int32_t u : mem[(size_t)a]) { agg_of[(size_t)u] = a; agg_mem.push_back(u); }
+    agg_ptr.push_back((int32_t)agg_mem.size());
+  }
+}
+
+// coarse blocks: fine entries grouped by (aggregate of the row, aggregate of the column), in entry order
+void build_coarse_blocks(GraphLayout &L) {
+  std::map<std::pair<int, int>, std::vector<int32_t>> cb;
+  for (int e = 0; e < (int)L.rcol.size(); ++e) cb[{L.agg_of[(size_t)L.rof[(size_t)e]], L.agg_of[(size_t)L.rcol[(size_t)e]]}].push_back(e);
+  L.cptr.assign(1, 0);
+  for (auto &kv : cb) {
+    L.cab.push_back(kv.first.first);
+    L.cab.push_back(kv.first.second);
+    L.cent.insert(L.cent.end(), kv.second.begin(), kv.second.end());
+    L.cptr.push_back((int32_t)L.cent.size());
+  }
+}
+
+// the persistent PCG kernel's view: per aggregate its rows' entries member by member, and a local numbering of
+// the column vertices those entries refer to (first appearance order)
+void build_persistent_view(GraphLayout &L) {
+  const std::vector<int32_t> &rptr = L.rptr, &rcol = L.rcol, &agg_ptr = L.agg_ptr, &agg_mem = L.agg_mem;
+  std::vector<int32_t> &bent = L.bent, &blc = L.blc, &bmptr = L.bmptr, &bcol = L.bcol;
+  L.bent_ptr.assign(1, 0);
+  L.bcol_ptr.assign(1, 0);
+  std::vector<int32_t> local((size_t)L.n_v, -1);
+  for (int a = 0; a < L.n_agg(); ++a) {
+    const size_t cfirst = bcol.size();
+    const size_t efirst = bent.size();
+    for (int m = agg_ptr[(size_t)a]; m < agg_ptr[(size_t)a + 1]; ++m) {
+      const int u = agg_mem[(size_t)m];
+      bmptr.push_back((int32_t)(bent.size() - efirst));
+      for (int e = rptr[(size_t)u]; e < rptr[(size_t)u + 1]; ++e) {
+        const int cv = rcol[(size_t)e];
+        if (local[(size_t)cv] < 0) {
+          local[(size_t)cv] = (int32_t)(bcol.size() - cfirst);
+          bcol.push_back(cv);
+        }
+        bent.push_back(e);
+        blc.push_back(local[(size_t)cv]);
+      }
+    }
+    bmptr.push_back((int32_t)(bent.size() - efirst));
+    for (size_t c = cfirst; c < bcol.size(); ++c) local[(size_t)bcol[c]] = -1;
+    L.bent_ptr.push_back((int32_t)bent.size());
+    L.bcol_ptr.push_back((int32_t)bcol.size());
+    L.max_cols = std::max(L.max_cols, (int)(bcol.size() - cfirst));
+    L.max_items = std::max(L.max_items, 6 * (int)(bent.size() - efirst));
+  }
+}
+
+// The layout's sizes into the graph, and what LSLAM_DEBUG says about it.
+void adopt_layout_sizes(lslam_pg *pg, const GraphLayout &L) {
+  pg->n_off = L.n_off();
+  pg->n_entries = (int)L.rcol.size();
+  pg->n_agg = L.n_agg();
+  pg->n_c = 6 * pg->n_agg;
+  pg->n_cblk = pg->n_agg;  // partial-sum slots of the coarse level: one per aggregate (pgc_mvp_kernel)
+  pg->n_cb = (int)L.cptr.size() - 1;
+  // the dense coarse matrix (n_c^2 doubles) and the Gauss-Jordan scratch are allocated by the first solve that takes the
+  // second level (make_coarse_args); graphs whose coarse matrix would exceed PG_COARSE_MAX unknowns never take it
+  if (pg->n_c > PG_COARSE_MAX) {
+    if (pg->env_debug)
+      fprintf(stderr, "[lslam pg] %d coarse unknowns > %d: the dense second level is not used for this graph (block-Jacobi PCG)\n", pg->n_c, PG_COARSE_MAX);
+    pg->coarse_mode = 0;
+  }
+  pg->pk_lds_cols = L.max_cols;
+  pg->pk_lds_items = L.max_items;
+  pg->pk_lds_bytes = ((size_t)L.max_cols * 6 + (size_t)L.max_items + PK_ROWS + 7 * (size_t)pg->n_c + 8 * PK_W) * sizeof(double);
+  const size_t n6 = (size_t)pg->n_v * 6;
+  pg->n_cg_blocks = (int)((n6 + CG_ROWS - 1) / CG_ROWS);
+  pg->n_parts = pg->n_cg_blocks + pg->n_cblk;
+  if (pg->env_debug) {
+    int hist[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int a = 0; a < pg->n_agg; ++a) hist[std::min(8, (L.agg_ptr[(size_t)a + 1] - L.agg_ptr[(size_t)a]) / 8)]++;
+    fprintf(stderr, "[lslam pg] aggregate sizes (members / 8): %d %d %d %d %d %d %d %d %d\n", hist[0], hist[1], hist[2], hist[3],
+            hist[4], hist[5], hist[6], hist[7], hist[8]);
+    fprintf(stderr, "[lslam pg] %d aggregates, widest: %d columns, %d items; persistent-kernel LDS %zu bytes\n", pg->n_agg,
+            L.max_cols, L.max_items, pg->pk_lds_bytes);
+  }
+}
+
+// the second level and the persistent kernels' structures
+int upload_aggregates(lslam_pg *pg, const GraphLayout &L) {
+  PG_TRY(dev_upload(pg->d_agg_of, L.agg_of));
+  PG_TRY(dev_upload(pg->d_agg_ptr, L.agg_ptr));
+  PG_TRY(dev_upload(pg->d_agg_mem, L.agg_mem));
+  PG_TRY(dev_upload(pg->d_cb_ptr, L.cptr));
+  PG_TRY(dev_upload(pg->d_cb_ent, L.cent));
+  PG_TRY(dev_upload(pg->d_cb_ab, L.cab));
+  PG_TRY(pg->d_P.alloc((size_t)pg->n_v * 36));
+  PG_TRY(pg->d_rc.alloc((size_t)pg->n_c));
+  PG_TRY(pg->d_yc.alloc((size_t)pg->n_c));
+  PG_TRY(dev_upload(pg->d_bent_ptr, L.bent_ptr));
+  PG_TRY(dev_upload(pg->d_bent, L.bent));
+  PG_TRY(dev_upload(pg->d_blc, L.blc));
+  PG_TRY(dev_upload(pg->d_bmptr, L.bmptr));
+  PG_TRY(dev_upload(pg->d_bcol_ptr, L.bcol_ptr));
+  PG_TRY(dev_upload(pg->d_bcol, L.bcol));
+  // [rc0 | rc1] then the sentinel-initialised slots [zA 2 n6 | rzA 2 n_agg | rrA 2 n_agg | pqB 2 n_agg | qcB 2 n_c]
+  PG_TRY(pg->d_pk.alloc(4 * (size_t)pg->n_c + 6 * (size_t)pg->n_agg + 12 * (size_t)pg->n_v));
+  PG_TRY(pg->d_bar.alloc(2));
+  return LSLAM_OK;
+}
+
+// the graph, the solver rows, and the solver's vectors
+int upload_graph_and_solver(lslam_pg *pg, const GraphLayout &L, const double *poses7, const double *meas7, const double *info36) {
+  const size_t n_v = (size_t)pg->n_v, n_e = (size_t)pg->n_e;
+  std::vector<double> hp(poses7, poses7 + 7 * n_v), hm(meas7, meas7 + 7 * n_e), hi(info36, info36 + 36 * n_e);
+  PG_TRY(dev_upload(pg->d_poses, hp));
+  PG_TRY(dev_upload(pg->d_trial, hp));
+  PG_TRY(dev_upload(pg->d_meas, hm));
+  PG_TRY(dev_upload(pg->d_info, hi));
+  PG_TRY(dev_upload(pg->d_ij, pg->h_ij));
+  PG_TRY(dev_upload(pg->d_row_ptr, L.rptr));
+  PG_TRY(dev_upload(pg->d_row_col, L.rcol));
+  PG_TRY(dev_upload(pg->d_row_src, L.rsrc));
+  PG_TRY(dev_upload(pg->d_row_of, L.rof));
+  const size_t n6 = n_v * 6;
+  PG_TRY(pg->d_sys.alloc(pg->sys_doubles()));
+  PG_TRY(pg->d_vals.alloc((size_t)pg->n_entries * 36));
+  PG_TRY(pg->d_minv.alloc(n_v * 36));
+  for (lslam::DevBuf<double> *p : {&pg->d_x, &pg->d_r, &pg->d_z})
+    PG_TRY(p->alloc(n6));
+  PG_TRY(pg->d_q.alloc((size_t)pg->n_entries * 6));
+  PG_TRY(pg->d_p.alloc(2 * n6));
+  PG_TRY(pg->d_part.alloc(3 * (size_t)pg->n_parts + ((size_t)pg->n_entries * 6 + PROD_BLOCK - 1) / PROD_BLOCK));
+  PG_TRY(pg->d_scal.alloc(32));
+  PG_TRY(hipMemset(pg->d_scal.p, 0, 32 * sizeof(double)));
+  PG_TRY(pg->d_tmp.alloc(8));
   return LSLAM_OK;
 }
 
@@ -2229,225 +2577,45 @@ int lslam_pg_create(int device, int32_t n_v, const double *poses7, int32_t n_e, 
   pg->device = device;
   pg->n_v = n_v;
   pg->n_e = n_e;
-  (void)lslam::debug_env("LSLAM_DEBUG_HOOKS");  // (the process-wide snapshot of the environment is taken no later than here)
-  pg->env_no_reuse = std::getenv("LSLAM_PG_NO_REUSE") != nullptr;
-  pg->env_persistent_off = std::getenv("LSLAM_PG_PERSISTENT") && std::atoi(std::getenv("LSLAM_PG_PERSISTENT")) == 0;
-  pg->env_debug = std::getenv("LSLAM_DEBUG") != nullptr;
-  if (const char *v = std::getenv("LSLAM_PG_MAX_CG")) pg->env_max_cg = std::atoi(v);
-  if (const char *v = std::getenv("LSLAM_PG_TOL")) pg->env_tol = std::atof(v);
   pg->fixed = fixed_vertex;
+  // The one place where a pose graph reads the environment -- when it is created, never while it is optimised.  It stays
+  // inside this function: tests/test_abi.py holds every getenv of this file to the text of lslam_pg_create.
+  const auto read_env = [](lslam_pg *pg) {
+    (void)lslam::debug_env("LSLAM_DEBUG_HOOKS");  // (the process-wide snapshot of the environment is taken no later than here)
+    pg->env_no_reuse = std::getenv("LSLAM_PG_NO_REUSE") != nullptr;
+    pg->env_no_merge = std::getenv("LSLAM_PG_NO_MERGE") != nullptr;
+    pg->env_debug = std::getenv("LSLAM_DEBUG") != nullptr;
+    if (const char *v = std::getenv("LSLAM_PG_PERSISTENT")) pg->env_persistent_off = std::atoi(v) == 0;
+    if (const char *v = std::getenv("LSLAM_PG_MAX_CG")) pg->env_max_cg = std::atoi(v);
+    if (const char *v = std::getenv("LSLAM_PG_TOL")) pg->env_tol = std::atof(v);
+    if (const char *v = std::getenv("LSLAM_PG_AGG")) pg->agg = std::max(2, std::min(PG_AGG_MAX, std::atoi(v)));
+    if (const char *v = std::getenv("LSLAM_PG_COARSE")) pg->coarse_mode = std::atoi(v);
+  };
+  read_env(pg);
   PG_TRY(hipStreamCreateWithFlags(&pg->stream, hipStreamNonBlocking));
+  GraphLayout L;
+  L.n_v = n_v;
+  L.n_e = n_e;
+  L.ij = ij;
+  number_offdiag_blocks(L);
+  build_solver_rows(L);
+  // (the growth stops at 7/8 of the limit: the merge fills up to it)
+  grow_aggregates(L, pg->env_no_merge ? pg->agg : std::max(2, pg->agg - pg->agg / 8));
+  if (!pg->env_no_merge) merge_pockets(L, pg->agg);
+  build_coarse_blocks(L);
+  build_persistent_view(L);
+  adopt_layout_sizes(pg, L);
+  int rc = upload_aggregates(pg, L);
+  if (rc) return rc;
   pg->h_ij.assign(ij, ij + 2 * (size_t)n_e);
-  // off-diagonal block ids: distinct (min,max) pairs in first-appearance order of a sorted map
-  std::map<std::pair<int, int>, int> ids;
-  for (int e = 0; e < n_e; ++e) ids.emplace(std::minmax(ij[2 * e], ij[2 * e + 1]), 0);
-  int nid = 0;
-  for (auto &kv : ids) kv.second = nid++;
-  pg->n_off = nid;
-  pg->off_pairs.resize(2 * (size_t)nid);
-  for (auto &kv : ids) {
-    pg->off_pairs[2 * kv.second] = kv.first.first;
-    pg->off_pairs[2 * kv.second + 1] = kv.first.second;
-  }
-  pg->edge_block.resize(n_e);
-  for (int e = 0; e < n_e; ++e) pg->edge_block[e] = ids[std::minmax(ij[2 * e], ij[2 * e + 1])];
-  // solver block-CSR: row v = [diag, then neighbours in block-id order]
-  std::vector<std::vector<std::pair<int, int>>> rows(n_v);  // (col, code)
-  for (int v = 0; v < n_v; ++v) rows[v].push_back({v, (v << 2) | 1});
-  for (int k = 0; k < nid; ++k) {
-    const int a = pg->off_pairs[2 * k], b = pg->off_pairs[2 * k + 1];
-    rows[a].push_back({b, ((n_v + k) << 2) | 0});
-    rows[b].push_back({a, ((n_v + k) << 2) | 2});
-  }
-  std::vector<int32_t> rptr(n_v + 1, 0), rcol, rsrc, rof;
-  for (int v = 0; v < n_v; ++v) {
-    rptr[v + 1] = rptr[v] + (int)rows[v].size();
-    for (auto &pr : rows[v]) {
-      rcol.push_back(pr.first);
-      rsrc.push_back(pr.second);
-      rof.push_back(v);
-    }
-  }
-  pg->n_entries = (int)rcol.size();
-  pg->h_row_ptr = rptr;
-  pg->h_row_of = rof;
-  pg->h_row_col = rcol;
-  {  // coarse blocks: fine entries grouped by (aggregate of the row, aggregate of the column), in entry order
-    if (const char *g = std::getenv("LSLAM_PG_AGG")) pg->agg = std::max(2, std::min(PG_AGG_MAX, std::atoi(g)));
-    if (const char *m = std::getenv("LSLAM_PG_COARSE")) pg->coarse_mode = std::atoi(m);
-    const int G = pg->agg;
-    // aggregates: breadth-first from the lowest unassigned vertex over the solver rows (neighbours in block-id order,
-    // i.e. deterministic), at most G members each
-    std::vector<int32_t> agg_of((size_t)n_v, -1), agg_ptr(1, 0), agg_mem;
-    const int Gg = std::getenv("LSLAM_PG_NO_MERGE") ? G : std::max(2, G - G / 8);  // growth limit (the merge below fills up to G)
-    for (int seed = 0; seed < n_v; ++seed) {
-      if (agg_of[(size_t)seed] >= 0) continue;
-      const int a = (int)agg_ptr.size() - 1;
-      const size_t first = agg_mem.size();
-      agg_of[(size_t)seed] = a;
-      agg_mem.push_back(seed);
-      for (size_t head = first; head < agg_mem.size() && (int)(agg_mem.size() - first) < Gg; ++head) {
-        const int u = agg_mem[head];
-        for (int e = rptr[(size_t)u]; e < rptr[(size_t)u + 1] && (int)(agg_mem.size() - first) < Gg; ++e) {
-          const int v = rcol[(size_t)e];
-          if (agg_of[(size_t)v] < 0) {
-            agg_of[(size_t)v] = a;
-            agg_mem.push_back(v);
-          }
-        }
-      }
-      agg_ptr.push_back((int32_t)agg_mem.size());
-    }
-    // Breadth-first growth leaves pockets: a handful of keyframes cut off between two full aggregates (59 of the bench
-    // graph's 136 aggregates had fewer than eight members).  Each would be a workgroup of the persistent solver, a
-    // participant of every grid exchange and six coarse unknowns of little use: a pocket joins the smallest adjacent
-    // aggregate that has room for it (the growth above stops at 7/8 of the limit to leave that room).
-    if (!std::getenv("LSLAM_PG_NO_MERGE")) {
-      const int n0 = (int)agg_ptr.size() - 1;
-      std::vector<int> size(n0), into(n0);
-      for (int a = 0; a < n0; ++a) { size[a] = agg_ptr[(size_t)a + 1] - agg_ptr[(size_t)a]; into[a] = a; }
-      for (int a = 0; a < n0; ++a) {
-        if (size[a] > std::max(1, G / 8)) continue;
-        int best = -1;
-        for (int m = agg_ptr[(size_t)a]; m < agg_ptr[(size_t)a + 1]; ++m) {
-          const int u = agg_mem[(size_t)m];
-          for (int e = rptr[(size_t)u]; e < rptr[(size_t)u + 1]; ++e) {
-            int b = agg_of[(size_t)rcol[(size_t)e]];
-            while (into[b] != b) b = into[b];
-            if (b != a && size[b] + size[a] <= G && (best < 0 || size[b] < size[best] || (size[b] == size[best] && b < best))) best = b;
-          }
-        }
-        if (best >= 0) { into[a] = best; size[best] += size[a]; size[a] = 0; }
-      }
-      std::vector<int> newid(n0, -1);
-      int nn = 0;
-      for (int a = 0; a < n0; ++a) if (into[a] == a) newid[a] = nn++;
-      std::vector<std::vector<int32_t>> mem((size_t)nn);
-      for (int a = 0; a < n0; ++a) {  // the receiving aggregate's members first (its first member stays its origin), pockets after them in order
-        int b = a;
-        while (into[b] != b) b = into[b];
-        if (b == a)
-          for (int m = agg_ptr[(size_t)a]; m < agg_ptr[(size_t)a + 1]; ++m) mem[(size_t)newid[a]].push_back(agg_mem[(size_t)m]);
-      }
-      for (int a = 0; a < n0; ++a) {
-        int b = a;
-        while (into[b] != b) b = into[b];
-        if (b != a)
-          for (int m = agg_ptr[(size_t)a]; m < agg_ptr[(size_t)a + 1]; ++m) mem[(size_t)newid[b]].push_back(agg_mem[(size_t)m]);
-      }
-      agg_ptr.assign(1, 0);
-      agg_mem.clear();
-      for (int a = 0; a < nn; ++a) {
-        for (int32_t u : mem[(size_t)a]) { agg_of[(size_t)u] = a; agg_mem.push_back(u); }
-        agg_ptr.push_back((int32_t)agg_mem.size());
-      }
-    }
-    pg->n_agg = (int)agg_ptr.size() - 1;
-    pg->n_c = 6 * pg->n_agg;
-    pg->n_cblk = pg->n_agg;  // partial-sum slots of the coarse level: one per aggregate (pgc_mvp_kernel)
-    PG_TRY(dev_upload(pg->d_agg_of, agg_of));
-    PG_TRY(dev_upload(pg->d_agg_ptr, agg_ptr));
-    PG_TRY(dev_upload(pg->d_agg_mem, agg_mem));
-    std::map<std::pair<int, int>, std::vector<int32_t>> cb;
-    for (int e = 0; e < pg->n_entries; ++e) cb[{agg_of[(size_t)rof[(size_t)e]], agg_of[(size_t)rcol[(size_t)e]]}].push_back(e);
-    std::vector<int32_t> cptr(1, 0), cent, cab;
-    for (auto &kv : cb) {
-      cab.push_back(kv.first.first);
-      cab.push_back(kv.first.second);
-      cent.insert(cent.end(), kv.second.begin(), kv.second.end());
-      cptr.push_back((int32_t)cent.size());
-    }
-    pg->n_cb = (int)cb.size();
-    PG_TRY(dev_upload(pg->d_cb_ptr, cptr));
-    PG_TRY(dev_upload(pg->d_cb_ent, cent));
-    PG_TRY(dev_upload(pg->d_cb_ab, cab));
-    PG_TRY(pg->d_P.alloc((size_t)n_v * 36));
-    PG_TRY(pg->d_rc.alloc((size_t)pg->n_c));
-    PG_TRY(pg->d_yc.alloc((size_t)pg->n_c));
-    // the dense coarse matrix (n_c^2 doubles) and the Gauss-Jordan scratch are allocated by the first solve that takes the
-    // second level (solve()); graphs whose coarse matrix would exceed PG_COARSE_MAX unknowns never take it
-    if (pg->n_c > PG_COARSE_MAX) {
-      if (std::getenv("LSLAM_DEBUG"))
-        fprintf(stderr, "[lslam pg] %d coarse unknowns > %d: the dense second level is not used for this graph (block-Jacobi PCG)\n", pg->n_c, PG_COARSE_MAX);
-      pg->coarse_mode = 0;
-    }
-    {  // the persistent PCG kernel's view: per aggregate its rows' entries member by member, and a local numbering of
-       // the column vertices those entries refer to (first appearance order)
-      std::vector<int32_t> bent_ptr(1, 0), bent, blc, bmptr, bcol_ptr(1, 0), bcol;
-      std::vector<int32_t> local((size_t)n_v, -1);
-      int max_cols = 0, max_items = 0;
-      for (int a = 0; a < pg->n_agg; ++a) {
-        const size_t cfirst = bcol.size();
-        const size_t efirst = bent.size();
-        for (int m = agg_ptr[(size_t)a]; m < agg_ptr[(size_t)a + 1]; ++m) {
-          const int u = agg_mem[(size_t)m];
-          bmptr.push_back((int32_t)(bent.size() - efirst));
-          for (int e = rptr[(size_t)u]; e < rptr[(size_t)u + 1]; ++e) {
-            const int cv = rcol[(size_t)e];
-            if (local[(size_t)cv] < 0) {
-              local[(size_t)cv] = (int32_t)(bcol.size() - cfirst);
-              bcol.push_back(cv);
-            }
-            bent.push_back(e);
-            blc.push_back(local[(size_t)cv]);
-          }
-        }
-        bmptr.push_back((int32_t)(bent.size() - efirst));
-        for (size_t c = cfirst; c < bcol.size(); ++c) local[(size_t)bcol[c]] = -1;
-        bent_ptr.push_back((int32_t)bent.size());
-        bcol_ptr.push_back((int32_t)bcol.size());
-        max_cols = std::max(max_cols, (int)(bcol.size() - cfirst));
-        max_items = std::max(max_items, 6 * (int)(bent.size() - efirst));
-      }
-      pg->pk_lds_cols = max_cols;
-      pg->pk_lds_items = max_items;
-      pg->pk_lds_bytes = ((size_t)max_cols * 6 + (size_t)max_items + PK_ROWS + 7 * (size_t)pg->n_c + 8 * PK_W) * sizeof(double);
-      if (std::getenv("LSLAM_DEBUG")) {
-        int hist[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int a = 0; a < pg->n_agg; ++a) hist[std::min(8, (agg_ptr[(size_t)a + 1] - agg_ptr[(size_t)a]) / 8)]++;
-        fprintf(stderr, "[lslam pg] aggregate sizes (members / 8): %d %d %d %d %d %d %d %d %d\n", hist[0], hist[1], hist[2], hist[3],
-                hist[4], hist[5], hist[6], hist[7], hist[8]);
-      }
-      if (std::getenv("LSLAM_DEBUG"))
-        fprintf(stderr, "[lslam pg] %d aggregates, widest: %d columns, %d items; persistent-kernel LDS %zu bytes\n", pg->n_agg,
-                max_cols, max_items, pg->pk_lds_bytes);
-      PG_TRY(dev_upload(pg->d_bent_ptr, bent_ptr));
-      PG_TRY(dev_upload(pg->d_bent, bent));
-      PG_TRY(dev_upload(pg->d_blc, blc));
-      PG_TRY(dev_upload(pg->d_bmptr, bmptr));
-      PG_TRY(dev_upload(pg->d_bcol_ptr, bcol_ptr));
-      PG_TRY(dev_upload(pg->d_bcol, bcol));
-      // [rc0 | rc1] then the sentinel-initialised slots [zA 2 n6 | rzA 2 n_agg | rrA 2 n_agg | pqB 2 n_agg | qcB 2 n_c]
-      PG_TRY(pg->d_pk.alloc(4 * (size_t)pg->n_c + 6 * (size_t)pg->n_agg + 12 * (size_t)n_v));
-      PG_TRY(pg->d_bar.alloc(2));
-    }
-  }
-  std::vector<double> hp(poses7, poses7 + 7 * (size_t)n_v), hm(meas7, meas7 + 7 * (size_t)n_e),
-      hi(info36, info36 + 36 * (size_t)n_e);
-  PG_TRY(dev_upload(pg->d_poses, hp));
-  PG_TRY(dev_upload(pg->d_trial, hp));
-  PG_TRY(dev_upload(pg->d_meas, hm));
-  PG_TRY(dev_upload(pg->d_info, hi));
-  PG_TRY(dev_upload(pg->d_ij, pg->h_ij));
-  PG_TRY(dev_upload(pg->d_row_ptr, rptr));
-  PG_TRY(dev_upload(pg->d_row_col, rcol));
-  PG_TRY(dev_upload(pg->d_row_src, rsrc));
-  PG_TRY(dev_upload(pg->d_row_of, rof));
-  const size_t n6 = (size_t)n_v * 6;
-  pg->n_cg_blocks = (int)((n6 + CG_ROWS - 1) / CG_ROWS);
-  pg->n_parts = pg->n_cg_blocks + pg->n_cblk;
-  PG_TRY(pg->d_sys.alloc(pg->sys_doubles()));
-  PG_TRY(pg->d_vals.alloc((size_t)pg->n_entries * 36));
-  PG_TRY(pg->d_minv.alloc((size_t)n_v * 36));
-  for (lslam::DevBuf<double> *p : {&pg->d_x, &pg->d_r, &pg->d_z})
-    PG_TRY(p->alloc(n6));
-  PG_TRY(pg->d_q.alloc((size_t)pg->n_entries * 6));
-  PG_TRY(pg->d_p.alloc(2 * n6));
-  PG_TRY(pg->d_part.alloc(3 * (size_t)pg->n_parts + ((size_t)pg->n_entries * 6 + PROD_BLOCK - 1) / PROD_BLOCK));
-  PG_TRY(pg->d_scal.alloc(32));
-  PG_TRY(hipMemset(pg->d_scal.p, 0, 32 * sizeof(double)));
-  PG_TRY(pg->d_tmp.alloc(8));
-  int rc = build_shard(pg, 0, n_e);
+  rc = upload_graph_and_solver(pg, L, poses7, meas7, info36);
+  if (rc) return rc;
+  pg->off_pairs = std::move(L.off_pairs);
+  pg->edge_block = std::move(L.edge_block);
+  pg->h_row_ptr = std::move(L.rptr);
+  pg->h_row_of = std::move(L.rof);
+  pg->h_row_col = std::move(L.rcol);
+  rc = build_shard(pg, 0, n_e);
   if (rc) return rc;
   guard.p = nullptr;
   *out = pg;
@@ -2513,7 +2681,6 @@ int lslam_pg_set_row_gather(lslam_pg *pg, lslam_allgatherv_fn fn, void *user, in
     g_pg_err = "bad rank / world for the row gather";
     return LSLAM_ERR_INVALID;
   }
-  pg->rs_agree_world = -1;  // another transport: the ranks agree again
   pg->gatherv = fn;
   pg->gatherv_user = user;
   pg->gatherv_rank = fn ? rank : -1;
@@ -2524,7 +2691,6 @@ int lslam_pg_set_row_gather(lslam_pg *pg, lslam_allgatherv_fn fn, void *user, in
 int lslam_pg_set_comm(lslam_pg *pg, lslam_comm *comm) {
   if (!pg) return LSLAM_ERR_INVALID;
   pg->comm = comm;
-  pg->rs_agree_world = -1;  // another transport: the ranks agree again
   return LSLAM_OK;
 }
 int32_t lslam_pg_num_offdiag(const lslam_pg *pg) { return pg ? pg->n_off : 0; }
@@ -2813,6 +2979,87 @@ struct EventPair {  // destroyed on every exit path
     if (b) (void)hipEventDestroy(b);
   }
 };
+
+struct LmState {
+  double lambda = -1.0, ni = 2.0;  // damping (< 0: not chosen yet) and the factor a rejected trial raises it by
+  double cur = 0.0;                // chi2 at the current estimate
+  double rho = 0.0;                // gain ratio of the last trial
+  int qmax = 0;                    // trials of this iteration
+};
+
+// the first iteration's damping: 1e-5 of the largest diagonal entry of H (behind the linearisation on the stream)
+int initial_lambda(lslam_pg *pg, double *lambda) {
+  hipLaunchKernelGGL(pg_maxdiag_kernel, dim3(1), dim3(256), 0, pg->stream, pg->diag(), pg->n_v, pg->fixed, pg->d_tmp.p + 1);
+  PG_TRY(hipGetLastError());
+  double md;
+  PG_TRY(hipMemcpyAsync(&md, pg->d_tmp.p + 1, 8, hipMemcpyDeviceToHost, pg->stream));
+  PG_TRY(hipStreamSynchronize(pg->stream));
+  *lambda = 1e-5 * md;
+  return LSLAM_OK;
+}
+
+// One LM trial at lm.lambda: solve, step, the trial's chi2 and the gain ratio, accept or reject.  *again: another trial of
+// this iteration follows (the step was rejected and fewer than ten were tried -- or, sharded, the trial has to be repeated).
+int lm_trial(lslam_pg *pg, LmState &lm, lslam_pg_stats &st, bool *again) {
+  *again = true;
+  int cg = 0;
+  // Every damped system is solved to a relative residual of 1e-8 (1e-10 until the PCG was fused; 1e-8 leaves every parity
+  // and convergence test unchanged, 1e-6 -- g2o's own PCG default -- shows in the sharded-against-full comparison at 3e-8 m;
+  // LSLAM_PG_TOL overrides), however many PCG iterations that takes: near the
+  // optimum lambda shrinks, the system of a 5 000-keyframe chain reaches a condition number of ~1e7 and block-Jacobi
+  // PCG needs thousands of iterations -- but a TRUNCATED solve leaves exactly the slow (global bending) modes
+  // unresolved, and LM then crawls (measured: capped at 800 iterations the 5 k / 25 k graph is still 5 m from its
+  // optimum after 2 000 LM iterations; uncapped it arrives in 342).  LSLAM_PG_MAX_CG overrides the cap for A/B runs.
+  pg->fell_back = false;
+  int rc = solve(pg, lm.lambda, pg->env_max_cg, pg->env_tol, &cg);
+  if (rc) return rc;
+  rc = zero_fixed_step(pg);
+  if (rc) return rc;
+  st.cg_iterations += cg;
+  hipLaunchKernelGGL(pg_update_kernel, dim3((pg->n_v + 127) / 128), dim3(128), 0, pg->stream, pg->d_poses.p,
+                     pg->d_x.p, pg->n_v, pg->fixed, pg->d_trial.p);
+  PG_TRY(hipGetLastError());
+  // the trial's chi2 and the gain denominator are enqueued together and read back after ONE wait
+  double scale;
+  rc = eval_chi2(pg, pg->d_trial.p, nullptr);  // enqueue only
+  if (rc) return rc;
+  hipLaunchKernelGGL(pg_dot_scale_kernel, dim3(pg->n_cg_blocks), dim3(CG_BLOCK), 0, pg->stream, pg->d_x.p,
+                     pg->b(), pg->n_v * 6, lm.lambda, pg->d_part.p);
+  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_part.p, pg->n_cg_blocks, 1, pg->d_tmp.p + 2);
+  PG_TRY(hipGetLastError());  // a failed launch must not turn into a stale read below
+  double chi_flag[2] = {0.0, 0.0};
+  PG_TRY(hipMemcpyAsync(chi_flag, pg->chi(), pg->sharded() ? 16 : 8, hipMemcpyDeviceToHost, pg->stream));
+  PG_TRY(hipMemcpyAsync(&scale, pg->d_tmp.p + 2, 8, hipMemcpyDeviceToHost, pg->stream));
+  PG_TRY(hipStreamSynchronize(pg->stream));
+  const double tmp = chi_flag[0];
+  if (pg->sharded() && chi_flag[1] > 0.0) {
+    // Some rank's persistent kernel timed out (or was refused) in this trial and that rank solved with the launch loop: a
+    // different summation order, dx equal to ~1e-8 instead of bit for bit -- and the replicated solve is only useful while
+    // every rank takes the same LM decisions.  Every rank switches to the launch loops for good and repeats the trial
+    // (one more chi2 all-reduce on every rank: the collectives stay matched).
+    pg->pk_fit = 0;
+    if (pg->gj_fit == 1) pg->gj_fit = 0;
+    pg->coarse_valid = false;
+    return LSLAM_OK;
+  }
+  scale += 1e-3;
+  lm.rho = (lm.cur - tmp) / scale;
+  st.lm_trials++;
+  if (lm.rho > 0 && std::isfinite(tmp)) {
+    double alpha = 1.0 - std::pow(2 * lm.rho - 1, 3);
+    alpha = std::min(alpha, 2.0 / 3.0);
+    lm.lambda *= std::max(1.0 / 3.0, alpha);
+    lm.ni = 2.0;
+    std::swap(pg->d_poses, pg->d_trial);  // accept
+    lm.cur = tmp;
+  } else {
+    lm.lambda *= lm.ni;
+    lm.ni *= 2.0;
+  }
+  lm.qmax++;
+  *again = lm.rho < 0 && lm.qmax < 10;
+  return LSLAM_OK;
+}
 }  // namespace
 
 int lslam_pg_optimize(lslam_pg *pg, int32_t max_iters, lslam_pg_stats *st_out) {
@@ -2824,90 +3071,26 @@ int lslam_pg_optimize(lslam_pg *pg, int32_t max_iters, lslam_pg_stats *st_out) {
   PG_TRY(hipEventCreate(&ev.a));
   PG_TRY(hipEventCreate(&ev.b));
   PG_TRY(hipEventRecord(ev.a, pg->stream));
-  const int n6 = pg->n_v * 6;
   const int fused0 = pg->fused_solves;
-  double lambda = -1.0, ni = 2.0;
+  LmState lm;
   for (int it = 0; it < max_iters; ++it) {
     int rc = linearize(pg, pg->d_poses.p);
     if (rc) return rc;
-    double cur;
-    PG_TRY(hipMemcpyAsync(&cur, pg->chi(), 8, hipMemcpyDeviceToHost, pg->stream));
-    if (lambda < 0) {
-      hipLaunchKernelGGL(pg_maxdiag_kernel, dim3(1), dim3(256), 0, pg->stream, pg->diag(), pg->n_v, pg->fixed, pg->d_tmp.p + 1);
-      PG_TRY(hipGetLastError());
-      double md;
-      PG_TRY(hipMemcpyAsync(&md, pg->d_tmp.p + 1, 8, hipMemcpyDeviceToHost, pg->stream));
-      PG_TRY(hipStreamSynchronize(pg->stream));
-      lambda = 1e-5 * md;
-    }
+    PG_TRY(hipMemcpyAsync(&lm.cur, pg->chi(), 8, hipMemcpyDeviceToHost, pg->stream));
+    if (lm.lambda < 0) rc = initial_lambda(pg, &lm.lambda);
+    if (rc) return rc;
     PG_TRY(hipStreamSynchronize(pg->stream));
-    if (it == 0) st.chi2_initial = cur;
-    double rho = 0.0;
-    int qmax = 0;
-    for (;;) {
-      int cg = 0;
-      // Every damped system is solved to a relative residual of 1e-8 (1e-10 until the PCG was fused; 1e-8 leaves every parity
-      // and convergence test unchanged, 1e-6 -- g2o's own PCG default -- shows in the sharded-against-full comparison at 3e-8 m;
-      // LSLAM_PG_TOL overrides), however many PCG iterations that takes: near the
-      // optimum lambda shrinks, the system of a 5 000-keyframe chain reaches a condition number of ~1e7 and block-Jacobi
-      // PCG needs thousands of iterations -- but a TRUNCATED solve leaves exactly the slow (global bending) modes
-      // unresolved, and LM then crawls (measured: capped at 800 iterations the 5 k / 25 k graph is still 5 m from its
-      // optimum after 2 000 LM iterations; uncapped it arrives in 342).  LSLAM_PG_MAX_CG overrides the cap for A/B runs.
-      const int max_cg = pg->env_max_cg;
-      const double cg_tol = pg->env_tol;
-      pg->fell_back = false;
-      rc = solve(pg, lambda, max_cg, cg_tol, &cg);
+    if (it == 0) st.chi2_initial = lm.cur;
+    lm.rho = 0.0;
+    lm.qmax = 0;
+    for (bool again = true; again;) {
+      rc = lm_trial(pg, lm, st, &again);
       if (rc) return rc;
-      rc = zero_fixed_step(pg);
-      if (rc) return rc;
-      st.cg_iterations += cg;
-      hipLaunchKernelGGL(pg_update_kernel, dim3((pg->n_v + 127) / 128), dim3(128), 0, pg->stream, pg->d_poses.p,
-                         pg->d_x.p, pg->n_v, pg->fixed, pg->d_trial.p);
-      PG_TRY(hipGetLastError());
-      // the trial's chi2 and the gain denominator are enqueued together and read back after ONE wait
-      double tmp, scale;
-      rc = eval_chi2(pg, pg->d_trial.p, nullptr);  // enqueue only
-      if (rc) return rc;
-      hipLaunchKernelGGL(pg_dot_scale_kernel, dim3(pg->n_cg_blocks), dim3(CG_BLOCK), 0, pg->stream, pg->d_x.p,
-                         pg->b(), n6, lambda, pg->d_part.p);
-      hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_part.p, pg->n_cg_blocks, 1, pg->d_tmp.p + 2);
-      PG_TRY(hipGetLastError());  // a failed launch must not turn into a stale read below
-      double chi_flag[2] = {0.0, 0.0};
-      PG_TRY(hipMemcpyAsync(chi_flag, pg->chi(), pg->sharded() ? 16 : 8, hipMemcpyDeviceToHost, pg->stream));
-      PG_TRY(hipMemcpyAsync(&scale, pg->d_tmp.p + 2, 8, hipMemcpyDeviceToHost, pg->stream));
-      PG_TRY(hipStreamSynchronize(pg->stream));
-      tmp = chi_flag[0];
-      if (pg->sharded() && chi_flag[1] > 0.0) {
-        // Some rank's persistent kernel timed out (or was refused) in this trial and that rank solved with the launch loop: a
-        // different summation order, dx equal to ~1e-8 instead of bit for bit -- and the replicated solve is only useful while
-        // every rank takes the same LM decisions.  Every rank switches to the launch loops for good and repeats the trial
-        // (one more chi2 all-reduce on every rank: the collectives stay matched).
-        pg->pk_fit = 0;
-        if (pg->gj_fit == 1) pg->gj_fit = 0;
-        pg->coarse_valid = false;
-        continue;
-      }
-      scale += 1e-3;
-      rho = (cur - tmp) / scale;
-      st.lm_trials++;
-      if (rho > 0 && std::isfinite(tmp)) {
-        double alpha = 1.0 - std::pow(2 * rho - 1, 3);
-        alpha = std::min(alpha, 2.0 / 3.0);
-        lambda *= std::max(1.0 / 3.0, alpha);
-        ni = 2.0;
-        std::swap(pg->d_poses, pg->d_trial);  // accept
-        cur = tmp;
-      } else {
-        lambda *= ni;
-        ni *= 2.0;
-      }
-      qmax++;
-      if (!(rho < 0 && qmax < 10)) break;
     }
     st.iterations = it + 1;
-    st.chi2_final = cur;
-    st.lambda = lambda;
-    if (qmax == 10 || rho == 0) break;
+    st.chi2_final = lm.cur;
+    st.lambda = lm.lambda;
+    if (lm.qmax == 10 || lm.rho == 0) break;
   }
   PG_TRY(hipEventRecord(ev.b, pg->stream));
   PG_TRY(hipStreamSynchronize(pg->stream));
