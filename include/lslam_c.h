@@ -84,43 +84,27 @@ typedef struct {
   float cert_track_m;      /* ... and its searches keep the bound a certificate needs when by less than this [m] (1.0) */
   float grid_cell;         /* LSLAM_SEARCH_GRID: edge of a grid cell [m]; 0 = the default (0.6) */
   int32_t debug_stats;     /* 1: count the points the certificate / grid sweeps leave to their second pass (lslam_debug_cert_stats) */
-  int32_t ab_switches;     /* LSLAM_AB_*: measured-and-kept alternatives, off by default (DESIGN.md has the numbers) */
+  int32_t ab_switches;     /* LSLAM_AB_*: measured-and-kept alternatives, off by default (DESIGN.md has the numbers); a bit
+                              that is none of them is refused with LSLAM_ERR_INVALID before anything is enqueued */
 } lslam_opts;
 /* Environment overrides of the fields above -- LSLAM_KNN_CERT, LSLAM_CERT_TRY_M, LSLAM_CERT_TRACK_M, LSLAM_GRID_CELL,
- * LSLAM_SEARCH=lane|packet|grid, LSLAM_FORCE_STACK=deep|shallow|auto, LSLAM_PERSISTENT_GN=1, LSLAM_FUSED_SOLVE=1,
+ * LSLAM_SEARCH=lane|packet|grid, LSLAM_FORCE_STACK=deep|shallow|auto, LSLAM_AB_SWITCHES=<LSLAM_AB_* bits>,
  * LSLAM_DEBUG_CERT_STATS=1 -- are read ONCE per context, in lslam_ctx_create; the A/B switches of the builders and the loop
  * (LSLAM_UNBOUNDED_KNN, LSLAM_NO_MORTON, LSLAM_HOST_MORTON, LSLAM_TINY_PHASE, LSLAM_NO_REG_NODES, LSLAM_NO_LEVEL_BUILD, ...)
  * once per process, when the first context is created; a pose graph's (LSLAM_PG_*) when it is created.  No entry point reads
  * the environment while it runs.  The hooks tests use to force failure paths (LSLAM_DEBUG_NODE_CAP_DIV,
  * LSLAM_DEBUG_SPIN_LIMIT, LSLAM_DEBUG_PG_ABORT, LSLAM_DEBUG_GJ_ABORT, LSLAM_HUGE_MIN) are the exception, and exist only in a
  * process started with LSLAM_DEBUG_HOOKS=1 (tests/conftest.py sets it); without it they are never looked at. */
-enum { LSLAM_AB_PERSISTENT_GN = 1, /* one resident scan: the whole Gauss-Newton loop as one persistent launch */
-       LSLAM_AB_FUSED_SOLVE = 2,   /* latency-bound launches: the 6x6 solve in the tail of the sweep launch */
-       LSLAM_AB_SECOND_PROBE = 4,  /* grid sweep: the points the 27-cell probe cannot prove get a second, 125-cell probe (clipped to
-                                      the ball of what the first saw) before the tree search -- exact, measured slower
-                                      (1.16e10 against 1.25e10 point-residuals/s: the points that need more than the first probe
-                                      are the ones a wide probe is slow for too) */
-       LSLAM_AB_WIDE_IN_PLACE = 8, /* a map without kd-trees (lslam_map_defer_trees), a launch of at most two wavefronts per SIMD:
-                                      the points the probe cannot prove are resolved inside the probe's own launch, wavefront by
-                                      wavefront (one launch per sweep instead of five; the sums are then formed exactly as the
-                                      lane search's sweep forms them).  Exact, measured slower: a frame's scan match 0.84 ms
-                                      against 0.49 -- a wavefront works its unproven points off one after the other, the
-                                      separate wide-probe launch gives each its own wavefront */
-       LSLAM_AB_FIT_CACHE = 32,    /* grid sweep of a batch: from a loop's third sweep on a surf point whose five neighbours are the
-                                      ones of the sweep before reuses that sweep's plane (findPlane is a pure function of the five
-                                      in order); the points whose five changed are compacted through LDS so that the fit runs on as
-                                      few wavefronts as they fill.  Same bits.  DESIGN 4 has the measurement */
-       LSLAM_AB_NO_COMPACT = 64,   /* a batch through the grid sweep: launch every workgroup of every scan in every sweep (round 4's
+/* Bits 1, 2, 4, 8, 32 and 128 named six alternatives that measured slower than what ships (the Gauss-Newton loop as one
+ * persistent launch, the solve in the sweep's tail, a second probe, unproven points resolved in place, the fit cache, the
+ * second pass by persistent lanes).  They are retired -- HISTORY.md keeps their numbers and the commit that last had them --
+ * and, like any bit this enum does not name, are REFUSED: a run call whose ab_switches has one returns LSLAM_ERR_INVALID
+ * with the pose untouched, lslam_ctx_create does under such an LSLAM_AB_SWITCHES (lslam_last_error names the bits). */
+enum { LSLAM_AB_NO_COMPACT = 64,   /* a batch through the grid sweep: launch every workgroup of every scan in every sweep (round 4's
                                       form) instead of only those of the scans whose loop is still running */
-       LSLAM_AB_REFILL = 128,      /* grid sweep of a batch: the second pass as two launches -- the listed points searched by persistent
-                                      lanes (a lane whose tree walk has ended hands its five in and takes the next point of a
-                                      pool of four workgroups' worth), their residual chain in the next.  Same bits.  Measured
-                                      slower: 1.405e10 against 1.461e10, no faster even in a loop's first sweep, where work is
-                                      plentiful -- the lanes a wavefront loses are lost inside every round of the walk (descents
-                                      and stack pops of different lengths), not at its end */
        LSLAM_AB_GRID_GENERAL = 256, /* grid sweep: the production loop's launches through the general instantiation of
                                       sweep_grid_kernel instead of the lean one (the same statements with the shuffle sums, the
-                                      taps, the _fineScore gate, the unbounded search, the counters and the fit cache folded away
+                                      taps, the _fineScore gate, the unbounded search and the counters folded away
                                       at compile time, and the five neighbours' points handed from the search to the fit instead
                                       of gathered twice: 61 VGPRs and no scratch at eight wavefronts per SIMD against 72 + 36 B at
                                       seven).  Same bits.  Measured on the headline, the two taken in turn in one session: 1.466 -
@@ -219,7 +203,7 @@ void lslam_default_opts(lslam_opts *opts);
  *   assert(lslam_abi_version() == LSLAM_ABI_VERSION && lslam_sizeof_opts() == sizeof(lslam_opts));
  * (the C++ mirrors do, and refuse to start otherwise). */
 /* 5 (round 5): no struct changed; new entry points (lslam_debug_grid_stats, lslam_debug_knn5_wide, lslam_debug_sort_pairs), new bits (LSLAM_SWEEP_FIRST /
- * _CARRIED, LSLAM_AB_FIT_CACHE, LSLAM_AB_WIDE_NF_MARGIN) -- a program built against this header needs a library that has them. */
+ * _CARRIED, LSLAM_AB_WIDE_NF_MARGIN, the fit cache's bit -- since retired) -- a program built against this header needs a library that has them. */
 /* 6 (round 6): no struct changed; new entry points (lslam_fset_*, lslam_extract_features_dev, lslam_odom_*, lslam_map_epoch). */
 /* 7: no struct changed; new entry points (lslam_lmap_*: the sliding-window local map). */
 /* still 7: no struct changed; new entry points (lslam_sreg_*: the registration node with the IMU de-skew branch). */
@@ -229,6 +213,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed; new entry points and structs of their own (lslam_sc_*: loop candidates by appearance). */
 /* still 7: no struct changed; new entry points and an enum (lslam_pg_set_robust_kernels, _edge_robust, _robust_info, _kernel_from_name: robust kernels on pose-graph edges; lslam_pg_stream). */
 /* still 7: no struct changed; new entry points and a struct of their own (lslam_match_information, lslam_keyframe_edge_information, lslam_sizeof_edge_info: the match Hessian of a pose-graph edge). */
+/* still 7: no struct changed, no entry point gone; six LSLAM_AB_* names retired (bits 1, 2, 4, 8, 32, 128: refused from here on, see lslam_opts.ab_switches). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -1293,8 +1278,8 @@ void *lslam_pg_stream(lslam_pg *pg);
 void *lslam_stream(lslam_ctx *ctx); /* hipStream_t */
 /* Sweep launches of this context so far, per kernel instantiation: [0] whole stack in LDS, [1] the same with the HBM
  * overflow (trees deeper than 33 levels), [2] the shallow-stack batch kernel sweep_kernel<256,true,false,12>, [3] per-cube
- * trees, [4] per-cube trees with overflow, [5] packet search, [6] persistent Gauss-Newton kernel, [7] the whole-stack kernel with
- * the 6x6 solve fused into its tail (the Gauss-Newton loop of single scans: one launch per iteration). */
+ * trees, [4] per-cube trees with overflow, [5] packet search.  [6] and [7] counted two retired kernels (the persistent
+ * Gauss-Newton loop, the solve fused into the sweep's tail): the slots keep their places and always read 0. */
 void lslam_debug_sweep_launches(lslam_ctx *ctx, uint64_t counts[8]);
 /* ... and of the grid sweep (sweep_grid_kernel; LSLAM_SEARCH_GRID) */
 uint64_t lslam_debug_grid_launches(lslam_ctx *ctx);
@@ -1312,7 +1297,7 @@ void lslam_debug_grid_fine_info(lslam_ctx *ctx, uint64_t out[4], float *build_ms
  * Returns the number of points, or a negative LSLAM_ERR_* (LSLAM_ERR_INVALID: the map has no such table). */
 int lslam_debug_grid_fine_table(lslam_ctx *ctx, int which_map, int32_t rebuild, int32_t dims_out[4], float geom_out[5],
                                 uint32_t *cell_start_out, size_t cap_cells, float *pts_out, size_t cap_pts);
-/* ... of which the single-launch form for a map without trees (sweep_grid_kernel<256, true>) */
+/* (counted a retired single-launch form for a map without trees: always 0) */
 uint64_t lslam_debug_grid_wide_launches(lslam_ctx *ctx);
 /* cells of the resident map's two cell tables (corner, surf); 0 while a type has no grid */
 void lslam_debug_grid_cells(lslam_ctx *ctx, uint64_t out[2]);

@@ -164,14 +164,6 @@ def test_grid_batch_equals_lane_batch(ctx, synth):
         assert np.abs(p_lane - p_grid).max() <= 2e-6
         _, p_again, _ = ctx.run_batch(inits, o)
         assert np.array_equal(p_again, p_grid)  # fixed places, fixed order: the same bits in every run
-        # the A/B switch "second probe" (125 cells for the points the 27-cell probe cannot prove, tree search only for what
-        # that leaves): another grouping of the same terms
-        o.ab_switches = 4
-        _, p_2, s_2 = ctx.run_batch(inits, o)
-        o.ab_switches = 0
-        for a, b in zip(s_lane, s_2):
-            assert (a.iterations, a.n_rows, a.n_line, a.n_plane, a.converged) == (b.iterations, b.n_rows, b.n_line, b.n_plane, b.converged)
-        assert np.abs(p_lane - p_2).max() <= 2e-6
 
 
 def test_grid_fine_score_resweep(ctx, small_problem):
@@ -209,10 +201,9 @@ def test_grid_run_does_not_read_what_an_earlier_call_left(ctx, small_problem):
         assert np.array_equal(bits(pose), bits(ref)) and (st.iterations, st.n_rows) == (st_ref.iterations, st_ref.n_rows)
 
 
-def _mapping_frames(pkg, ctx, synth, world, defer, n=4, lattice=False, ab_switches=0):
+def _mapping_frames(pkg, ctx, synth, world, defer, n=4, lattice=False):
     """A few LaserMapping frames (the device chain of tests/test_gpu_pipeline.py, mapping half only) -> poses, stats."""
     mapper = pkg.LaserMapping(ctx, cube_dims=(21, 21, 11), defer_trees=defer)
-    mapper.opts.ab_switches = ab_switches
     out = []
     for k in range(n):
         gt = (0.0, 0.0, 0.3 + 0.01 * k, 3.0 + 0.4 * k, -2.0 + 0.15 * k, synth.SENSOR_HEIGHT)
@@ -253,20 +244,6 @@ def test_deferred_trees_mapping_frames_equal_eager(pkg, synth, small_problem):
     for (Ma, sa), (Mb, sb) in zip(res[False], res[True]):
         assert sa == sb
         assert np.abs(Ma - Mb).max() <= 2e-6
-    # the A/B form of the deferred sweep (LSLAM_AB_WIDE_IN_PLACE: unproven points resolved inside the probe's launch, one
-    # launch per sweep) -- it forms a workgroup's sums the way the lane search's sweep does, so against the EAGER frames
-    # (trees, lane search: what AUTO takes for a single scan) it is the same bits
-    c = pkg.Context(0)
-    try:
-        inplace = _mapping_frames(pkg, c, synth, world, True, ab_switches=8)  # LSLAM_AB_WIDE_IN_PLACE
-        sets, builds, pending = c.lazy_trees()
-        assert sets >= 3 and builds == 0 and pending
-        assert c.grid_wide_launches() > 0 and c.grid_wide_launches() == c.grid_launches()
-    finally:
-        c.close()
-    for (Ma, sa), (Mb, sb) in zip(res[False], inplace):
-        assert sa == sb
-        assert np.array_equal(bits(Ma), bits(Mb))
 
 
 def test_deferred_trees_for_a_host_map(pkg, small_problem):
@@ -564,42 +541,6 @@ def test_wide_probe_near_tie_margin_is_an_option(pkg):
     assert np.array_equal(bits(res["deferred+margin"][1]), bits(res["eager"][1]))
 
 
-@pytest.mark.parametrize("from_sweep", [0, 1, 2])
-def test_grid_fit_cache_gives_the_same_bits(pkg, synth, monkeypatch, from_sweep):
-    """LSLAM_AB_FIT_CACHE: surf points whose five neighbours did not change reuse the previous sweep's plane, the others are
-    compacted through LDS and fitted by as few wavefronts as they fill.  findPlane is a pure function of the five in order and
-    every lane still forms its own row, so the loop is the SAME BITS as without the cache -- with the cache used from the
-    default sweep (0 = the library's: the fourth) and, forced through the environment, from a loop's second and third sweep
-    (where most points' neighbours DID change: both the compacted and the everybody-fits form run)."""
-    if from_sweep:
-        monkeypatch.setenv("LSLAM_FIT_FROM_SWEEP", str(from_sweep))
-    c = pkg.Context(0)
-    try:
-        pr0 = synth.make_problem(rings=16, azimuth_steps=900, world_half=60.0)
-        c.map_set(pr0["map_corner"], pr0["map_surf"])
-        scans, inits = [], []
-        for k in range(6):
-            pr = synth.make_problem(rings=16, azimuth_steps=900, world_half=60.0, seed=k)
-            scans.append((pr["corner"], pr["surf"]))
-            inits.append(synth.perturb_pose(pr["gt_pose"], seed=40 + k, dt=0.4, dr_deg=2.5))  # far enough for loops of 4+ sweeps
-        c.scan_set_batch(scans)
-        inits = np.stack(inits)
-        o = c.default_opts()
-        o.search_mode = GRID
-        res = {}
-        for ab in (0, 32, 0, 32):
-            o.ab_switches = ab
-            _, p, st = c.run_batch(inits, o)
-            key = (ab, len([k for k in res if k[0] == ab]))
-            res[key] = (p.copy(), [(s.status, s.iterations, s.n_rows, s.n_line, s.n_plane, s.converged, s.sweeps) for s in st])
-        assert max(s[6] for s in res[(0, 0)][1]) >= 4  # loops long enough for cached fits to be used
-        for key in ((32, 0), (0, 1), (32, 1)):
-            assert res[key][1] == res[(0, 0)][1], key
-            assert np.array_equal(bits(res[key][0]), bits(res[(0, 0)][0])), key
-    finally:
-        c.close()
-
-
 def test_grid_batch_over_the_running_scans_only_gives_the_same_bits(ctx, synth):
     """A batch through the grid sweep launches, from a loop's second sweep on, only the workgroups of the scans still running
     (compact_active_kernel; one 4-byte read-back per iteration) instead of every workgroup of every scan.  Every workgroup writes
@@ -622,7 +563,7 @@ def test_grid_batch_over_the_running_scans_only_gives_the_same_bits(ctx, synth):
     ref = None
     for in_flight in (0, 4):
         o.scans_in_flight = in_flight
-        for ab in (64, 0, 128):                         # LSLAM_AB_NO_COMPACT first; LSLAM_AB_REFILL: the second pass's two-launch form
+        for ab in (64, 0):                              # LSLAM_AB_NO_COMPACT first
             o.ab_switches = ab
             _, p, st = ctx.run_batch(inits, o)
             cur = (p.copy(), [(s.status, s.iterations, s.n_rows, s.n_line, s.n_plane, s.converged, s.sweeps) for s in st])

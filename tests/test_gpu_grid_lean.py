@@ -1,5 +1,5 @@
-"""The lean instantiation of the grid sweep's first pass (sweep_grid_kernel<256, false, false, true>): the production loop's
-launches -- MFMA sums, no taps, the fifth-distance gate, the bounded search, no counters, no fit cache -- run a kernel with
+"""The lean instantiation of the grid sweep's first pass (sweep_grid_kernel<256, true>): the production loop's
+launches -- MFMA sums, no taps, the fifth-distance gate, the bounded search, no counters -- run a kernel with
 everything else folded away at compile time.  Same statements on the same values: the SAME BITS as the general
 instantiation, which lslam_opts.ab_switches & LSLAM_AB_GRID_GENERAL (256) brings back; every launch that needs one of the
 folded paths still takes the general kernel (lslam_debug_grid_lean_launches counts the lean ones)."""
@@ -9,7 +9,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 LANE, GRID = 1, 3
-AB_FIT_CACHE, AB_GRID_GENERAL = 32, 256
+AB_GRID_GENERAL = 256
 TOO_FEW_MATCHES = 5
 TIMES = ("gpu_ms_total", "gpu_ms_sweep")
 
@@ -105,9 +105,9 @@ def test_loops_cut_short(ctx, six, max_iterations):
     assert all(s.iterations <= max_iterations for s in st) and any(s.iterations == max_iterations for s in st)
 
 
-@pytest.mark.parametrize("what", ["jtj_mode", "debug_stats", "fit_cache"])
+@pytest.mark.parametrize("what", ["jtj_mode", "debug_stats"])
 def test_launches_that_need_a_folded_path_take_the_general_kernel(ctx, six, what):
-    """The shuffle sums, the counters and the fit cache: no lean launch, and the results the lean loop gives (the shuffle
+    """The shuffle sums and the counters: no lean launch, and the results the lean loop gives (the shuffle
     sums are another order of the same terms: its counts, its pose to rounding)."""
     ctx.map_set(*six["map"])
     ctx.scan_set_batch(six["scans"])
@@ -117,10 +117,8 @@ def test_launches_that_need_a_folded_path_take_the_general_kernel(ctx, six, what
     p_ref = p_ref.copy()
     if what == "jtj_mode":
         o.jtj_mode = 0
-    elif what == "debug_stats":
-        o.debug_stats = 1
     else:
-        o.ab_switches = AB_FIT_CACHE
+        o.debug_stats = 1
     lean0, grid0 = ctx.grid_lean_launches(), ctx.grid_launches()
     _, p, st = ctx.run_batch(six["inits"], o)
     assert ctx.grid_launches() > grid0 and ctx.grid_lean_launches() == lean0

@@ -1,5 +1,5 @@
 """The x-subdivided cell tables of the grid sweep's first pass (csrc/lslam_grid.hpp CellGrid::xsub, knn5_grid<.., FINE>,
-sweep_grid_kernel<256, false, false, LEAN, true>; include/lslam_c.h LSLAM_AB_GRID_CUBIC): each 0.6 m cell cut into S sub-cells
+sweep_grid_kernel<256, LEAN, true>; include/lslam_c.h LSLAM_AB_GRID_CUBIC): each 0.6 m cell cut into S sub-cells
 along x, the rows of a bounded probe clipped to sub-cells.  The same five neighbours as the cubic table's probe and the
 kd-tree walk -- held to the oracle tap by tap -- from tables that are the same bytes build after build.
 

@@ -1,6 +1,6 @@
 """The launch schedule of the scan-match driver (run_batch_impl and its stages in csrc/lslam_api.hip), not only its results.
 
-Every configuration below runs on a context of its own -- the iteration hint, the persistent kernel's fallback flag and the
+Every configuration below runs on a context of its own -- the iteration hint and the
 parity of the queue-launch counter carry over from call to call -- and issues the same call three times, so that the
 iteration-hint rule (the spare iteration is dropped after three equal runs) is part of what is pinned.  Per call the return
 status, every field of lslam_stats but the two times, the poses' bytes, and what the call added to the eight sweep-launch
@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "run_schedule.json")
 LANE, PACKET, GRID = 1, 2, 3  # LSLAM_SEARCH_*
 # lslam_opts.ab_switches (include/lslam_c.h)
-AB_PERSISTENT_GN, AB_FUSED_SOLVE, AB_SECOND_PROBE, AB_FIT_CACHE, AB_NO_COMPACT, AB_REFILL = 1, 2, 4, 32, 64, 128
+AB_NO_COMPACT = 64
 N_CALLS = 3
 STEREO_SHAPES = ((16, 900), (16, 450), (8, 300), (16, 1200))  # as tests/test_gpu_stereo_batch.py
 STEREO_SET_SIZES = (1500, 300, 63, 800)
@@ -33,20 +33,15 @@ CONFIGS = {
     "one_default": ("trees", 1, "batch", {}),
     "one_profile": ("trees", 1, "batch", dict(profile=1)),
     "one_no_iterations": ("trees", 1, "batch", dict(max_iterations=0)),
-    "one_persistent": ("trees", 1, "batch", dict(ab_switches=AB_PERSISTENT_GN)),
-    "one_fused_solve": ("trees", 1, "batch", dict(ab_switches=AB_FUSED_SOLVE)),
     "one_cert_forced": ("trees", 1, "batch", dict(knn_cert=2)),
     "one_cert_off": ("trees", 1, "batch", dict(knn_cert=0)),
     "one_grid": ("trees", 1, "batch", dict(search_mode=GRID)),
     "one_grid_fine_score": ("trees", 1, "batch", dict(search_mode=GRID, fine_score=1, use_score=1)),
-    "one_grid_fit_cache": ("trees", 1, "batch", dict(search_mode=GRID, ab_switches=AB_FIT_CACHE)),
     "one_packet": ("trees", 1, "batch", dict(search_mode=PACKET)),
     "one_deferred_trees": ("deferred", 1, "batch", {}),
     "seven_trees": ("trees", 7, "batch", dict(scans_in_flight=3, search_mode=LANE)),
     "seven_grid": ("trees", 7, "batch", dict(scans_in_flight=3, search_mode=GRID)),
     "seven_grid_no_compact": ("trees", 7, "batch", dict(scans_in_flight=3, search_mode=GRID, ab_switches=AB_NO_COMPACT)),
-    "seven_grid_refill": ("trees", 7, "batch", dict(scans_in_flight=3, search_mode=GRID, ab_switches=AB_REFILL)),
-    "seven_grid_second_probe": ("trees", 7, "batch", dict(scans_in_flight=3, search_mode=GRID, ab_switches=AB_SECOND_PROBE)),
     "four_stereo_grid": ("trees", "stereo", "batch", dict(scans_in_flight=2, search_mode=GRID)),
     "one_cubes": ("cubes", 1, "batch", {}),
     "sharded": ("trees", 1, "sharded", {}),

@@ -143,26 +143,6 @@ def test_full_loop_matches_oracle_from_every_family_pose(ctx, oracle, fam, small
     assert abs(st.score - ost.score) <= 1e-5 * ost.score and abs(st.percent - ost.percent) <= 1e-6
 
 
-def test_persistent_gn_loop_equals_launch_loop_at_a_tilted_pose(ctx, fam, small_problem):
-    """lslam_opts.ab_switches & LSLAM_AB_PERSISTENT_GN at a tilted pose: the launch loop's pose, counters and sweeps, bit for
-    bit (the form of test_gpu_parity.test_persistent_gn_loop_equals_launch_loop)."""
-    pr = small_problem
-    m = fam["members"][R.TILTED]
-    ctx.map_set(pr["map_corner"], pr["map_surf"])
-    ctx.scan_set(m["corner"], m["surf"])
-    out = {}
-    for mode in (0, 1):
-        opts = ctx.default_opts()
-        opts.ab_switches = mode  # LSLAM_AB_PERSISTENT_GN
-        before = ctx.sweep_launches()
-        status, pose, st = ctx.run(m["pose"], opts)
-        after = ctx.sweep_launches()
-        assert (after["persistent"] - before["persistent"] == 1) == (mode == 1)
-        out[mode] = (int(status), bits(pose).tolist(), st.iterations, st.n_rows, st.n_line, st.n_plane, st.converged, st.sweeps)
-    assert out[0] == out[1]
-    assert out[1][6] == 1 and out[1][2] >= 2
-
-
 def test_batch_equals_single_runs_at_tilted_poses(ctx, fam, small_problem):
     """Two tilted members and the near-identity one matched together give, bit for bit, what each gives alone (the form of
     test_gpu_parity.test_batch_equals_individual_runs)."""

@@ -461,47 +461,6 @@ def test_voxel_map_batch_of_48_full_scans_properties(voxel_map_problem, pkg, syn
     assert np.array_equal(bits(p4), bits(p1[:24]))
 
 
-def test_fused_solve_equals_the_solve_launch(ctx, synth, small_problem, monkeypatch):
-    """The 6 x 6 solve in the tail of the sweep launch (the block that retires the scan's last record reduces and solves) against
-    the solve kernel as its own launch: same reduction order, same solve -- same bits; single scan, a small batch with a scan
-    that ends early, and the mapping node's settings.  (Measured no faster: lslam_opts.ab_switches & LSLAM_AB_FUSED_SOLVE is an A/B switch, off by default.)"""
-    pr = small_problem
-    ctx.map_set(pr["map_corner"], pr["map_surf"])
-    world = pr["world"]
-    scans, inits = [(pr["corner"], pr["surf"])], [pr["init_pose"]]
-    for k in range(3):
-        gt = (0.0, 0.01 * k, 0.2 + 0.3 * k, 2.0 - 1.5 * k, -1.0 + k, synth.SENSOR_HEIGHT)
-        qc, qs, gt = synth.make_scan(world, 16, 450, gt_pose=gt, seed=500 + k)
-        scans.append((qc, qs))
-        inits.append(synth.perturb_pose(gt, seed=600 + k))
-    inits[2][3] += 400.0
-    opts = ctx.default_opts()
-    mopts = ctx.default_opts()
-    mopts.delta_t_abort = mopts.delta_r_abort = 0.1
-    mopts.use_score = 0
-    res = {}
-    # the fused tail rides on the one-launch sweep: the certificate sweep (two launches, the same terms summed in another
-    # grouping) is held against it and the oracle by test_certificate_sweep_equals_searching_every_point
-    opts.knn_cert = mopts.knn_cert = 0
-    for fused in (True, False):
-        opts.ab_switches = mopts.ab_switches = 2 if fused else 0  # LSLAM_AB_FUSED_SOLVE
-        before = ctx.sweep_launches()
-        ctx.scan_set(*scans[0])
-        a = ctx.run(inits[0], opts)
-        b = ctx.run(inits[0], mopts)
-        ctx.scan_set_batch(scans)
-        c = ctx.run_batch(np.stack(inits), opts)
-        assert set(_ran(before, ctx.sweep_launches())) == {"deep_fused" if fused else "deep"}
-        res[fused] = (a, b, c)
-    for x, y in ((res[True][0], res[False][0]), (res[True][1], res[False][1])):
-        assert np.array_equal(bits(x[1]), bits(y[1])) and x[2].iterations == y[2].iterations and x[2].n_rows == y[2].n_rows
-        assert x[2].score == y[2].score and int(x[0]) == int(y[0]) and x[2].sweeps == y[2].sweeps
-    (_, pf, sf), (_, pu, su) = res[True][2], res[False][2]
-    assert np.array_equal(bits(pf), bits(pu))
-    assert [(s.status, s.iterations, s.n_rows, s.sweeps) for s in sf] == [(s.status, s.iterations, s.n_rows, s.sweeps) for s in su]
-    assert sf[2].status == 5 and len({s.iterations for s in sf}) > 1
-
-
 def test_vlp16_mapping_frames_against_the_voxel_map_match_oracle(voxel_map_problem, pkg, oracle, synth):
     """BASELINE configs[1] at its own shape: VLP-16 sweeps of 16 x 1800 points through LaserMapping::process
     (LaserMapping.cpp:39-59 over LaserMatcher.cpp:289-354: transformMerge, VoxelGrid of the frame's features, update +

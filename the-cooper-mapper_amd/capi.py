@@ -555,12 +555,11 @@ SYMBOLS = {
 COMM_ID_BYTES = 128
 SC_POINT_CHUNK, SC_CAND_TILE, SC_MAX_TOP_K = 256, 64, 32  # LSLAM_SC_* of include/lslam_c.h: the scan-context kernels' shape
 SEARCH_AUTO, SEARCH_LANE, SEARCH_PACKET, SEARCH_GRID = 0, 1, 2, 3
-AB_PERSISTENT_GN, AB_FUSED_SOLVE, AB_SECOND_PROBE, AB_WIDE_IN_PLACE = 1, 2, 4, 8  # lslam_opts.ab_switches (LSLAM_AB_*)
-AB_REFILL = 128
+AB_WIDE_NF_MARGIN, AB_NO_COMPACT = 16, 64  # lslam_opts.ab_switches (LSLAM_AB_*); any other bit is refused
 AB_GRID_GENERAL = 256
 AB_GRID_CUBIC = 512
 STACK_AUTO, STACK_DEEP, STACK_SHALLOW = 0, 0x100, 0x200  # ORed into a search mode (LSLAM_STACK_*)
-# lslam_debug_sweep_launches: index of each sweep-kernel instantiation
+# lslam_debug_sweep_launches: index of each sweep-kernel instantiation ("persistent", "deep_fused": retired, always 0)
 SWEEP_VARIANTS = ("deep", "deep_ovf", "shallow", "cubes", "cubes_ovf", "packet", "persistent", "deep_fused")
 
 

@@ -152,14 +152,12 @@ struct lslam_ctx {
   DevBuf<float> partials;
   DevBuf<char> scan_tables;    // [blocks | probs | groups] of the resident scans: blocks / probs / groups point into it
   std::vector<char> h_tables;  // ... its host image
-  DevBuf<int32_t> tail_count;  // per resident scan: the fused solve's ticket counter (zero between launches)
   DevBuf<uint32_t> stack_ovf;  // only allocated for trees deeper than KD_STACK_LDS+1
   DevBuf<int32_t> prev_nb;     // neighbours of the previous sweep, per resident scan point
   DevBuf<float4> prev_q;       // ... and where the point was then,
   DevBuf<float> prev_lb;       // ... with the bound the certificate needs (sweep_body)
   DevBuf<uint8_t> need_list;   // certificate sweep: the points pass 1 leaves to pass 2 (SweepArgs)
   DevBuf<uint16_t> need_cnt;
-  DevBuf<uint16_t> need2_list, need2_cnt;  // grid sweep: what its second probe leaves to the tree search (SweepArgs)
   DevBuf<GroupDesc> groups;
   DevBuf<int32_t> cert_work;   // [blocks] work list of pass 2 (CertPlan)
   DevBuf<int32_t> cert_count;  // [2] items + [2] tickets
@@ -169,8 +167,6 @@ struct lslam_ctx {
   DevBuf<int32_t> active_blocks;  // [nb_total] the grid sweep of a batch: block indices of the scans still running, per chunk at its block range
   PinBuf<int32_t> h_active;       // [n_chunks] how many
   DevBuf<int32_t> d_active_cnt;
-  DevBuf<int32_t> fit_ids;     // the grid sweep's fit cache (LSLAM_AB_FIT_CACHE): [5][n_points] neighbour positions ...
-  DevBuf<float> fit_val;       // ... and [5][n_points] plane + verdict
   DevBuf<unsigned long long> cert_stats;  // LSLAM_DEBUG_CERT_STATS=1: [searched, swept] counters of the certificate path
   bool prev_valid = false;
   bool grid_state_valid = false;  // prev_q holds what a grid-sweep run of the resident scan against the resident map left (LSLAM_SWEEP_CARRIED)
@@ -191,12 +187,6 @@ struct lslam_ctx {
   std::vector<hipEvent_t> sweep_ev;
   int iter_hint = 4;  // size of the first batch of enqueued GN iterations
   int iter_last = -1, iter_same = 0;  // the last call's iteration count, and for how many calls in a row it has been that
-  // gn_persistent_kernel (one resident scan: the whole loop in one cooperative launch)
-  DevBuf<float> gnp_slots;
-  DevBuf<unsigned> gnp_bar;
-  int gnp_cap = -1;       // workgroups the device holds at once (-1: not asked yet)
-  bool gnp_ok = true;     // false once an exchange timed out: the launch loop from then on
-  int gnp_runs = 0;
   // pinned staging area for the scan clouds a caller hands over (packed here, copied from here)
   PinBuf<float4> h_stage;
   bool stage_busy = false;  // a copy out of h_stage was enqueued and no wait on the stream has happened since
@@ -248,13 +238,11 @@ struct lslam_ctx {
   // environment overrides of lslam_opts fields, read ONCE when the context is made (never inside a call)
   int env_knn_cert = -1;       // LSLAM_KNN_CERT (-1: not set)
   float env_cert_try_m = -1.0f, env_cert_track_m = -1.0f, env_grid_cell = -1.0f;  // LSLAM_CERT_TRY_M, LSLAM_CERT_TRACK_M, LSLAM_GRID_CELL
-  int env_fit_from_sweep = 0;  // LSLAM_FIT_FROM_SWEEP: A/B -- the sweep of a loop from which cached fits are used (default 3)
   float env_grid_cell_corner = -1.0f;  // LSLAM_GRID_CELL_CORNER: A/B switch -- another cell edge for the corner map's grid (the line-like cloud)
   int env_search = -1;         // LSLAM_SEARCH=lane|packet|grid
   int env_debug_cert_stats = 0;  // LSLAM_DEBUG_CERT_STATS
   int env_force_stack = -1;    // LSLAM_FORCE_STACK=deep|shallow|auto -> SWEEP_STACK_*
-  int env_ab = 0;              // LSLAM_PERSISTENT_GN=1, LSLAM_FUSED_SOLVE=1 -> LSLAM_AB_* bits
-  int ab_now = 0;              // lslam_opts.ab_switches | env_ab of the call that is running (sweep_launch has no options at hand)
+  int env_ab = 0;              // LSLAM_AB_SWITCHES: LSLAM_AB_* bits for every call of the context
   bool env_debug = false;      // LSLAM_DEBUG
 };
 
@@ -329,13 +317,8 @@ void fill_sweep_args(lslam_ctx *ctx, SweepArgs &a) {
   a.wide_nf_slack = 0.0f;
   a.active_blocks = nullptr;
   a.n_active = 0;
-  a.fit_ids = nullptr;
-  a.fit_val = nullptr;
-  a.n_fit = 0;
-  a.fit_from_sweep = 0;
   a.grid_hint = nullptr;
-  a.need2_list = nullptr;
-  a.need2_cnt = nullptr;
+  a.spare0 = a.spare1 = nullptr;
   a.wide_d = nullptr;
   a.wide_p = nullptr;
   a.wide_off = nullptr;
@@ -354,7 +337,6 @@ void fill_sweep_args(lslam_ctx *ctx, SweepArgs &a) {
   a.packet = 0;
   a.stack_mode = SWEEP_STACK_AUTO;
   a.fine_gate_c = a.fine_gate_s = -1.0f;
-  a.tail = SweepTail{};
   a.cert_stats = nullptr;
   a.need_list = nullptr;
   a.need_cnt = nullptr;
@@ -473,73 +455,55 @@ CertPlan make_cert_plan(const lslam_ctx *ctx) {
   return plan;
 }
 
+// lslam_opts.ab_switches and LSLAM_AB_SWITCHES are input from outside: a bit this library has no variant for -- a retired one,
+// a newer header's -- is refused, not ignored (a caller that asks for a variant must not be handed the production path's
+// numbers under its name).  false: g_err names the bits.
+constexpr int32_t AB_KNOWN = LSLAM_AB_WIDE_NF_MARGIN | LSLAM_AB_NO_COMPACT | LSLAM_AB_GRID_GENERAL | LSLAM_AB_GRID_CUBIC;
+bool ab_switches_known(int32_t ab, const char *where) {
+  const uint32_t unknown = (uint32_t)ab & ~(uint32_t)AB_KNOWN;
+  if (!unknown) return true;
+  set_err("%s = %d: bit(s) 0x%x name no variant of this library (known LSLAM_AB_* bits: 0x%x; 1, 2, 4, 8, 32 and 128 are retired)",
+          where, (int)ab, unknown, (unsigned)AB_KNOWN);
+  return false;
+}
+
 // launch_sweep + the per-context count of the instantiation it took
 // fine: the grid sweep's first pass reads the x-subdivided tables (ctx->kfc / kfs, which the caller has ensured); every other
 // launch of the sweep -- the second pass, its probes -- keeps a's cubic tables
-hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
-                        int *variant = nullptr, bool fine = false) {
-  int v = -1;
-  CertPlan plan = make_cert_plan(ctx);
-  plan.ticket2 = plan.count + 4;
-  plan.ticket2_next = plan.count_next + 4;
+// general: the grid sweep's first pass through the general instantiation even where the lean one would do (LSLAM_AB_GRID_GENERAL)
+hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, bool general, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
+                        bool fine = false) {
+  const CertPlan plan = make_cert_plan(ctx);
   if (a.grid) {  // the grid sweep: probe + proof for every point, then the tree search for the points it listed; timed as one
     if (a.nb_total <= 0 || a.n_groups <= 0 || !a.need_cnt) return a.nb_total <= 0 ? hipSuccess : hipErrorInvalidValue;
-    // A/B (off; lslam_opts.ab_switches & LSLAM_AB_WIDE_IN_PLACE): a map without trees and a launch of at most two wavefronts per
-    // SIMD as ONE launch -- each wavefront resolves its own unproven points by the wide probe before the residual chain
-    // (sweep_grid_kernel<.., true>).  Measured slower than the five launches below: see include/lslam_c.h.
-    if (a.grid == 2 && (long)a.nb_total * (SWEEP_BLOCK / 64) <= 2 * 1024 && (ctx->ab_now & LSLAM_AB_WIDE_IN_PLACE)) {
-      hipError_t e1w = launch_sweep_grid(a, jtj_mode, ctx->stream, e0, e1, true);
-      ctx->sweep_variants[SWEEP_VARIANT_GRID_WIDE]++;
-      if (variant) *variant = SWEEP_VARIANT_GRID_WIDE;
-      return e1w;
-    }
-    // the production loop's launch takes the lean instantiation (A/B: lslam_opts.ab_switches & LSLAM_AB_GRID_GENERAL keeps the general one)
-    const bool lean = grid_sweep_lean_ok(a, jtj_mode) && !(ctx->ab_now & LSLAM_AB_GRID_GENERAL);
+    const bool lean = grid_sweep_lean_ok(a, jtj_mode) && !general;  // the production loop's launch takes the lean instantiation
     hipError_t e;
-    if (fine && a.grid == 1 && !a.fit_ids && !a.need2_cnt && !a.wide_d && ctx->kfc.view.cell_start && ctx->kfs.view.cell_start) {
+    if (fine && a.grid == 1 && ctx->kfc.view.cell_start && ctx->kfs.view.cell_start) {
       SweepArgs af = a;
       af.kc = ctx->kfc.view;
       af.ks = ctx->kfs.view;
-      e = launch_sweep_grid(af, jtj_mode, ctx->stream, e0, nullptr, false, lean, true);
+      e = launch_sweep_grid(af, jtj_mode, ctx->stream, e0, nullptr, lean, true);
       ctx->grid_fine_launches++;
     } else {
-      e = launch_sweep_grid(a, jtj_mode, ctx->stream, e0, nullptr, false, lean);
+      e = launch_sweep_grid(a, jtj_mode, ctx->stream, e0, nullptr, lean);
     }
-    v = SWEEP_VARIANT_GRID;
-    ctx->sweep_variants[v]++;
+    ctx->sweep_variants[SWEEP_VARIANT_GRID]++;
     if (lean) ctx->grid_lean_launches++;
-    if (variant) *variant = v;
     if (e != hipSuccess) return e;
     bool planned = false;
     if (a.grid == 2) {  // no trees: the listed points' neighbours come from the wide probe, the queue only runs their residual chain
-      e = launch_sweep_plan(a, ctx->stream, plan, 0, true);  // the second pass's plan and the wide probe's prefix in one launch
+      e = launch_sweep_plan(a, ctx->stream, plan, true);  // the second pass's plan and the wide probe's prefix in one launch
       if (e != hipSuccess) return e;
       planned = true;
       e = launch_sweep_wide(a, ctx->stream);
       if (e != hipSuccess) return e;
     }
     const int pass2 = a.stack_ovf ? (a.deep_tree ? SWEEP_VARIANT_DEEP_OVF : SWEEP_VARIANT_SHALLOW) : SWEEP_VARIANT_DEEP;
-    if (a.grid == 1 && a.need2_cnt) {  // second probe, then the tree search of what IT could not prove: two plans, two queues
-      e = launch_sweep_queue(a, jtj_mode, ctx->stream, nullptr, pass2, plan, 0);
-      ctx->queue_launches++;
-      if (e != hipSuccess) return e;
-      e = launch_sweep_queue(a, jtj_mode, ctx->stream, e1, pass2, make_cert_plan(ctx), 1);  // (no second consumer: no ticket2)
-      ctx->queue_launches++;
-      return e;
-    }
 #ifdef LSLAM_EXP_NO_PASS2  // TIMING EXPERIMENT ONLY (wrong results): the listed points are dropped -- what the second pass costs
     if (e1) return hipEventRecord(e1, ctx->stream);
     return hipSuccess;
 #endif
-    // A/B (off; lslam_opts.ab_switches & LSLAM_AB_REFILL sets wide_d / wide_p): whole-map trees, the bounded production sweep of a
-    // throughput-bound batch -- the listed points are searched by persistent lanes in a launch of their own, their residual
-    // chain runs in the next (sweep_refill_kernel).  Same bits, measured slower
-    if (a.grid == 1 && pass2 == SWEEP_VARIANT_SHALLOW && a.bounded && a.wide_d && a.wide_p && !a.flags_out && a.fine_gate_c < 0.0f && !planned) {
-      e = launch_sweep_refill(a, jtj_mode, ctx->stream, e1, plan);
-      ctx->queue_launches++;
-      return e;
-    }
-    e = launch_sweep_queue(a, jtj_mode, ctx->stream, e1, pass2, plan, 0, planned);
+    e = launch_sweep_queue(a, jtj_mode, ctx->stream, e1, pass2, plan, planned);
     ctx->queue_launches++;
     return e;
   }
@@ -547,11 +511,11 @@ hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, hipEve
   // pair is timed as one
   // (n_groups > 0: the two counter pairs of the plan alternate per LAUNCHED plan -- each zeroes the other's -- so a sweep
   // with nothing to plan must not advance them)
+  int v = -1;
   bool cert_launched = false;
-  const bool two_pass = a.prev_q && a.need_cnt && a.bounded && a.prev_valid && !a.tail.count && !a.gc.trees && a.n_groups > 0 && a.nb_total > 0;
+  const bool two_pass = a.prev_q && a.need_cnt && a.bounded && a.prev_valid && !a.gc.trees && a.n_groups > 0 && a.nb_total > 0;
   hipError_t e = launch_sweep(a, jtj_mode, ctx->stream, e0, two_pass ? nullptr : e1, &v, &cert_launched);
   if (v >= 0 && v < SWEEP_N_VARIANTS) ctx->sweep_variants[v]++;
-  if (variant) *variant = v;
   if (e == hipSuccess && two_pass) {
     if (cert_launched) {  // (a build whose launch_sweep never takes the certificate instantiation lists nothing)
       e = launch_sweep_queue(a, jtj_mode, ctx->stream, e1, v, plan);
@@ -608,7 +572,6 @@ const EnvOnce &env_once() {
     v.host_morton = on("LSLAM_HOST_MORTON");
     v.odom_inline = on("LSLAM_ODOM_INLINE_SEARCH");
     v.odom_trees = on("LSLAM_ODOM_TREES");
-    v.gnp_coop = on("LSLAM_GNP_COOPERATIVE");
     v.tiny_phase_off = on("LSLAM_TINY_PHASE") && num("LSLAM_TINY_PHASE", 1) == 0;
     v.no_reg_nodes = on("LSLAM_NO_REG_NODES");
     v.no_level_build = on("LSLAM_NO_LEVEL_BUILD");
@@ -679,9 +642,15 @@ int lslam_ctx_create(int device, lslam_ctx **out) {
     set_err("device %d out of range [0,%d)", device, count);
     return LSLAM_ERR_INVALID;
   }
+  // Environment overrides of lslam_opts fields (A/B runs of a binary one cannot pass options to): read here, once per
+  // context -- never inside a call, where another thread's setenv would race with it.  (The process-wide switches: env_once.)
+  int32_t env_ab = 0;
+  if (const char *v = std::getenv("LSLAM_AB_SWITCHES")) env_ab = std::atoi(v);  // any LSLAM_AB_* bits, for A/B runs of unmodified programs
+  if (!ab_switches_known(env_ab, "LSLAM_AB_SWITCHES")) return LSLAM_ERR_INVALID;
   HIP_TRY(hipSetDevice(device));
   lslam_ctx *ctx = new lslam_ctx();
   ctx->device = device;
+  ctx->env_ab = env_ab;
   HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   // (stream2 is made when something first forks onto it -- ctx_stream2: a context that only registers sweeps or runs the odometry
   // node never does, and every stream is one more claimant of the device's few hardware queues)
@@ -693,8 +662,6 @@ int lslam_ctx_create(int device, lslam_ctx **out) {
   }
   HIP_TRY(hipEventCreate(&ctx->ev0));
   HIP_TRY(hipEventCreate(&ctx->ev1));
-  // Environment overrides of lslam_opts fields (A/B runs of a binary one cannot pass options to): read here, once per
-  // context -- never inside a call, where another thread's setenv would race with it.  (The process-wide switches: env_once.)
   (void)lslam::env_once();
   if (const char *v = std::getenv("LSLAM_KNN_CERT")) ctx->env_knn_cert = std::atoi(v);
   if (const char *v = std::getenv("LSLAM_CERT_TRY_M")) ctx->env_cert_try_m = (float)std::atof(v);
@@ -702,16 +669,12 @@ int lslam_ctx_create(int device, lslam_ctx **out) {
   if (const char *v = std::getenv("LSLAM_GRID_CELL")) ctx->env_grid_cell = (float)std::atof(v);
   if (const char *v = std::getenv("LSLAM_GRID_CELL_CORNER")) ctx->env_grid_cell_corner = (float)std::atof(v);
   if (const char *v = std::getenv("LSLAM_GRID_XSUB")) ctx->env_grid_xsub = std::max(1, std::min(std::atoi(v), GRID_MAX_XSUB));
-  if (const char *v = std::getenv("LSLAM_FIT_FROM_SWEEP")) ctx->env_fit_from_sweep = std::atoi(v);
   if (const char *v = std::getenv("LSLAM_DEBUG_CERT_STATS")) ctx->env_debug_cert_stats = std::atoi(v);
   if (const char *v = std::getenv("LSLAM_FORCE_STACK")) {
     if (!std::strcmp(v, "deep")) ctx->env_force_stack = SWEEP_STACK_DEEP;
     else if (!std::strcmp(v, "shallow")) ctx->env_force_stack = SWEEP_STACK_SHALLOW;
     else if (!std::strcmp(v, "auto")) ctx->env_force_stack = SWEEP_STACK_AUTO;
   }
-  if (const char *v = std::getenv("LSLAM_PERSISTENT_GN")) ctx->env_ab |= std::atoi(v) == 1 ? LSLAM_AB_PERSISTENT_GN : 0;
-  if (const char *v = std::getenv("LSLAM_FUSED_SOLVE")) ctx->env_ab |= std::atoi(v) == 1 ? LSLAM_AB_FUSED_SOLVE : 0;
-  if (const char *v = std::getenv("LSLAM_AB_SWITCHES")) ctx->env_ab |= std::atoi(v);  // any LSLAM_AB_* bits, for A/B runs of unmodified programs
   ctx->env_debug = lslam::env_once().debug;
   if (const char *v = std::getenv("LSLAM_SEARCH")) {
     if (!std::strcmp(v, "lane")) ctx->env_search = LSLAM_SEARCH_LANE;
@@ -796,7 +759,7 @@ void lslam_debug_lazy_trees(lslam_ctx *ctx, uint64_t out[3]) {
   out[2] = ctx ? (ctx->trees_pending ? 1 : 0) : 0;
 }
 
-uint64_t lslam_debug_grid_launches(lslam_ctx *ctx) { return ctx ? ctx->sweep_variants[SWEEP_VARIANT_GRID] + ctx->sweep_variants[SWEEP_VARIANT_GRID_WIDE] : 0; }
+uint64_t lslam_debug_grid_launches(lslam_ctx *ctx) { return ctx ? ctx->sweep_variants[SWEEP_VARIANT_GRID] : 0; }
 uint64_t lslam_debug_grid_lean_launches(lslam_ctx *ctx) { return ctx ? ctx->grid_lean_launches : 0; }
 uint64_t lslam_debug_grid_fine_launches(lslam_ctx *ctx) { return ctx ? ctx->grid_fine_launches : 0; }
 void lslam_debug_grid_fine_info(lslam_ctx *ctx, uint64_t out[4], float *build_ms) {
@@ -807,7 +770,7 @@ void lslam_debug_grid_fine_info(lslam_ctx *ctx, uint64_t out[4], float *build_ms
   out[3] = have ? (uint64_t)ctx->kfs.n_cells : 0;
   if (build_ms) *build_ms = have ? ctx->fine_build_ms : 0.0f;
 }
-uint64_t lslam_debug_grid_wide_launches(lslam_ctx *ctx) { return ctx ? ctx->sweep_variants[SWEEP_VARIANT_GRID_WIDE] : 0; }
+uint64_t lslam_debug_grid_wide_launches(lslam_ctx *) { return 0; }  // (the instantiation it counted is retired; the entry point stays)
 void lslam_debug_grid_cells(lslam_ctx *ctx, uint64_t out[2]) {
   out[0] = ctx && ctx->kc.view.cell_start ? (uint64_t)ctx->kc.n_cells : 0;
   out[1] = ctx && ctx->ks.view.cell_start ? (uint64_t)ctx->ks.n_cells : 0;
@@ -876,7 +839,7 @@ int lslam_debug_sweep_clocks(lslam_ctx *ctx, const float pose[6], int32_t jtj_mo
   sa.bounded = unbounded_dbg ? 0 : 1;
   sa.prev_valid = ctx->prev_valid ? 1 : 0;
   if (sa.bounded) ctx->prev_valid = true;
-  HIP_TRY(sweep_launch(ctx, sa, jtj_mode));
+  HIP_TRY(sweep_launch(ctx, sa, jtj_mode, false));  // (a tree sweep)
   HIP_TRY(hipMemcpyAsync(out, d.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return (int)nw;
@@ -1611,14 +1574,11 @@ static int scan_set_batch_impl(lslam_ctx *ctx, int32_t n_scans, const void *cons
   HIP_TRY(ctx->prev_lb.reserve(total ? total : 1));
   HIP_TRY(ctx->need_list.reserve((nb ? nb : 1) * SWEEP_BLOCK));
   HIP_TRY(ctx->need_cnt.reserve(nb ? nb : 1));
-  HIP_TRY(ctx->need2_list.reserve((nb ? nb : 1) * SWEEP_BLOCK));
-  HIP_TRY(ctx->need2_cnt.reserve(nb ? nb : 1));
   HIP_TRY(ctx->cert_work.reserve(nb ? nb : 1));
   if (!ctx->cert_count.p) {
-    HIP_TRY(ctx->cert_count.reserve(6));  // items [2], tickets [2], the refill search's tickets [2]
-    HIP_TRY(hipMemsetAsync(ctx->cert_count.p, 0, 6 * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx->cert_count.reserve(4));  // items [2], tickets [2]
+    HIP_TRY(hipMemsetAsync(ctx->cert_count.p, 0, 4 * sizeof(int32_t), ctx->stream));
   }
-  HIP_TRY(ctx->tail_count.reserve((size_t)n_scans));  // (zeroed where the fused solve is switched on: run_batch_impl)
   ctx->prev_valid = false;
   ctx->grid_state_valid = false;
   rc = ensure_states(ctx, n_scans);
@@ -1676,13 +1636,12 @@ struct RunCall {
   // running counters
   int launched = 0, n_launches = 0, batch = 1;
   double total_points = -1.0;  // sharded: points of the whole scan (sum over ranks)
-  bool gnp_done = false;
   uint64_t grid_launches_before = 0;
   SweepArgs sa;
   SolveArgs so{};
   StereoArgs sta{};
   // the chunked loops (configure_search)
-  bool compact = false, force_cert = false, no_probe2 = true, cert_counters_reset = false;
+  bool compact = false, force_cert = false, cert_counters_reset = false;
   bool fine = false;  // the loops' first pass reads the x-subdivided tables (configure_search)
   std::vector<int> done_iters;  // iterations enqueued per chunk
   std::vector<char> finished;
@@ -1744,7 +1703,7 @@ int reserve_chunk_stack_ovf(lslam_ctx *ctx, const RunCall &call, SweepArgs &a) {
 }
 
 // `base` (the call's SweepArgs, or the fine-score pass's copy of them), call.so and call.sta cut down to chunk c.  The
-// fine-score pass (`fine`) only reduces the LiDAR rows: no second probe lists, no stereo slice, reduce_only = 2, the sums
+// fine-score pass (`fine`) only reduces the LiDAR rows: no stereo slice, reduce_only = 2, the sums
 // to the exchange buffer of a sharded run -- and, sharded, no grid.
 struct ChunkArgs { SweepArgs sc; SolveArgs soc; StereoArgs stc; };
 int slice_chunk(lslam_ctx *ctx, RunCall &call, const SweepArgs &base, int c, bool fine, ChunkArgs &out) {
@@ -1763,20 +1722,16 @@ int slice_chunk(lslam_ctx *ctx, RunCall &call, const SweepArgs &base, int c, boo
   // per iteration (measured on single scans: 0.29 against 0.26 ms per loop).  LSLAM_KNN_CERT=2 takes it regardless (tests)
   // (the fine-score pass: the grid sweep's second pass alone)
   const bool pass2 = fine ? sc.grid != 0
-                          : (sc.grid || sc.prev_q) && !sc.tail.count && (sc.grid || call.force_cert || (long)sc.nb_total * (SWEEP_BLOCK / 64) > 2 * 1024);
+                          : (sc.grid || sc.prev_q) && (sc.grid || call.force_cert || (long)sc.nb_total * (SWEEP_BLOCK / 64) > 2 * 1024);
   if (pass2 && fine && call.sharded) {
     sc.grid = 0;
   } else if (pass2) {
     if (!fine && !call.cert_counters_reset) {  // once per call: whatever an earlier call that ended in an error left in the plan's counters
-      HIP_TRY(hipMemsetAsync(ctx->cert_count.p, 0, 6 * sizeof(int32_t), ctx->stream));
+      HIP_TRY(hipMemsetAsync(ctx->cert_count.p, 0, 4 * sizeof(int32_t), ctx->stream));
       call.cert_counters_reset = true;
     }
     sc.need_list = ctx->need_list.p + (size_t)r.fb * SWEEP_BLOCK;
     sc.need_cnt = ctx->need_cnt.p + r.fb;
-    if (!fine && sc.grid == 1 && !call.no_probe2) {
-      sc.need2_list = ctx->need2_list.p + (size_t)r.fb * SWEEP_BLOCK;
-      sc.need2_cnt = ctx->need2_cnt.p + r.fb;
-    }
     sc.groups = ctx->groups.p + ctx->h_prob_group0[(size_t)r.p0];
     sc.n_groups = ctx->h_prob_group0[(size_t)r.p1] - ctx->h_prob_group0[(size_t)r.p0];
     sc.group_block_base = r.fb;
@@ -1809,6 +1764,7 @@ int validate_call(lslam_ctx *ctx, RunCall &call) {
   int rc = check_ctx(ctx, true);
   if (rc) return rc;
   const int32_t n_scans = call.n_scans;
+  if (call.opts_in && !ab_switches_known(call.opts_in->ab_switches, "lslam_opts.ab_switches")) return LSLAM_ERR_INVALID;  // (before anything is enqueued)
   // A map whose kd-trees are deferred (lslam_map_defer_trees) is matched through its cell grids alone when the call is a
   // latency-bound one on the plain loop -- a mapping frame: one scan of a few thousand points; anything else builds the trees now.
   if (ctx->trees_pending) {
@@ -1945,7 +1901,7 @@ int run_sharded_loop(lslam_ctx *ctx, RunCall &call) {
       sa.prev_valid = (sa.bounded && call.launched > 0) ? 1 : 0;
       hipEvent_t e0, e1;
       HIP_TRY(sweep_events(ctx, call, call.launched, &e0, &e1));
-      HIP_TRY(sweep_launch(ctx, sa, call.o.jtj_mode, e0, e1));
+      HIP_TRY(sweep_launch(ctx, sa, call.o.jtj_mode, false, e0, e1));  // (no grid sweep on this path)
       HIP_TRY(launch_stereo(call.sta, ctx->stream));
       so.reduce_only = 1;
       so.ext_sums = nullptr;
@@ -1968,93 +1924,7 @@ int run_sharded_loop(lslam_ctx *ctx, RunCall &call) {
   return LSLAM_OK;
 }
 
-// One resident scan: the whole loop in ONE persistent launch (gn_persistent_kernel) when every block of the sweep can
-// be resident at once and nothing needs the launches in between (per-launch profiling, the stereo term, the exchange of
-// a sharded run, per-cube trees, the packet search, trees deeper than the LDS stack).  OFF by default
-// (lslam_opts.ab_switches & LSLAM_AB_PERSISTENT_GN turns it on): bit-identical results, but measured no faster than the launch loop -- 327 us
-// against 315 us of device time per four-iteration scanMatchScan of 115 200 points; the two grid exchanges and the
-// replicated solve of an iteration cost what the solve launch and its two gaps do.
-// Sets call.gnp_done when the launch carried the loop; otherwise the chunked loop runs it.
-int run_persistent(lslam_ctx *ctx, RunCall &call) {
-  const SweepArgs &sa = call.sa;
-  const SolveArgs &so = call.so;
-  const bool gnp_off = !(call.ab & LSLAM_AB_PERSISTENT_GN);
-  if (!(!call.sharded && !call.lazy && call.n_scans == 1 && !gnp_off && ctx->gnp_ok && !call.o.profile && ctx->n_stereo == 0 && !ctx->cube_mode &&
-        !sa.packet && sa.stack_mode != SWEEP_STACK_SHALLOW && call.max_it > 0 && ctx->tc.depth <= KD_STACK_LDS + 1 && ctx->ts.depth <= KD_STACK_LDS + 1 &&
-        sa.nb_total > 0 && sa.nb_total <= 512))
-    return LSLAM_OK;
-  if (ctx->gnp_cap < 0) ctx->gnp_cap = gn_persistent_capacity(ctx->device);
-  if (sa.nb_total > ctx->gnp_cap) return LSLAM_OK;
-  // [2][nb][32] floats, then [3][32][32] doubles (8-byte aligned: the float part is a multiple of 64 words)
-  const size_t n_slot = 2 * (size_t)sa.nb_total * NCOL + 2 * 3 * 32 * NCOL;
-  HIP_TRY(ctx->gnp_slots.reserve(n_slot));
-  HIP_TRY(ctx->gnp_bar.reserve(2));
-  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ctx->gnp_slots.p, (int)0xFFF8DEADu, n_slot, ctx->stream));
-  HIP_TRY(hipMemsetAsync(ctx->gnp_bar.p, 0, 2 * sizeof(unsigned), ctx->stream));
-  SweepArgs sp = sa;
-  sp.bounded = call.unbounded ? 0 : 1;
-  sp.stack_ovf = nullptr;
-  GnLoopArgs gl{};
-  gl.slots = ctx->gnp_slots.p;
-  gl.gslots = reinterpret_cast<double *>(ctx->gnp_slots.p + 2 * (size_t)sa.nb_total * NCOL);
-  gl.bar = ctx->gnp_bar.p;
-  gl.state_out = ctx->d_state.p;
-  gl.max_iterations = call.max_it;
-  gl.min_rows = so.min_rows;
-  gl.delta_r_abort = so.delta_r_abort;
-  gl.delta_t_abort = so.delta_t_abort;
-  gl.eig_thresh = so.eig_thresh;
-  HIP_TRY(launch_gn_persistent(sp, call.o.jtj_mode, gl, ctx->stream));
-  ctx->sweep_variants[SWEEP_VARIANT_PERSISTENT]++;
-  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-  unsigned gbar[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(ctx->h_state.p, ctx->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipMemcpyAsync(gbar, ctx->gnp_bar.p, sizeof(gbar), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (gbar[1] == 0) {
-    call.gnp_done = true;
-    ctx->gnp_runs++;
-    call.launched = ctx->h_state.p[0].sweeps;
-  } else {  // an exchange ran into its spin limit (the workgroups were not all resident): the launch loop, from the start
-    if (ctx->env_debug) fprintf(stderr, "[lslam] persistent GN kernel timed out in its grid exchange: launch loop from here on\n");
-    ctx->gnp_ok = false;
-    init_state(ctx->h_state.p[0], call.poses);
-    HIP_TRY(hipMemcpyAsync(ctx->d_state.p, ctx->h_state.p, sizeof(GNState), hipMemcpyHostToDevice, ctx->stream));
-  }
-  return LSLAM_OK;
-}
-
-// lslam_opts.ab_switches & LSLAM_AB_FUSED_SOLVE: the solve rides in the tail of the sweep launch whenever that
-// launch is a latency-bound one (launch_sweep takes the whole-stack kernel: single scans, small batches) -- the block that
-// retires a scan's last record reduces and solves, one launch per Gauss-Newton iteration.  Bit-identical to the solve
-// kernel as its own launch (tests/test_gpu_stack_shapes.py) and MEASURED NO FASTER, so off by default: per working
-// iteration of a 115 200-point scan 83 us against 47 + 13 us of kernels plus a ~3 us gap (rocprofv3 --kernel-trace);
-// 0.270 against 0.237 ms of device time per three-iteration loop, 0.244 against 0.229 ms for a 4 835-point scan.  The
-// tail is the solve's own dependent chain (reduction round trip, 6 x 6 QR, pose update: ~13 us) run by ONE workgroup
-// that first had to finish its share of the sweep, reading the records through the coherence point; the launch it saves
-// costs less than that.  Not with the stereo term (its records come from a launch of their own).
-int configure_fused_tail(lslam_ctx *ctx, RunCall &call) {
-  SweepArgs &sa = call.sa;
-  const SolveArgs &so = call.so;
-  const bool no_fuse = !(call.ab & LSLAM_AB_FUSED_SOLVE);
-  if (no_fuse || ctx->n_stereo != 0 || sa.grid) return LSLAM_OK;
-  // the ticket counters: zero between launches (the last block of a launch resets its scan's); once per call here, in case
-  // an earlier call ended in an error half way
-  HIP_TRY(hipMemsetAsync(ctx->tail_count.p, 0, sizeof(int32_t) * (size_t)call.n_scans, ctx->stream));
-  sa.tail.count = ctx->tail_count.p;
-  sa.tail.probs = ctx->probs.p;
-  sa.tail.partials_abs = ctx->partials.p;
-  sa.tail.sp.max_iterations = so.max_iterations;
-  sa.tail.sp.min_rows = so.min_rows;
-  sa.tail.sp.too_few_continue = so.too_few_continue;
-  sa.tail.sp.nan_reset = so.nan_reset;
-  sa.tail.sp.delta_r_abort = so.delta_r_abort;
-  sa.tail.sp.delta_t_abort = so.delta_t_abort;
-  sa.tail.sp.eig_thresh = so.eig_thresh;
-  return LSLAM_OK;
-}
-
-// What the chunked loops search with: grid or trees, the lazy wide probe, certificates, the fit cache, the fused tail.
+// What the chunked loops search with: grid or trees, the lazy wide probe, certificates.
 int configure_search(lslam_ctx *ctx, RunCall &call) {
   const lslam_opts &o = call.o;
   const int32_t n_scans = call.n_scans;
@@ -2094,29 +1964,20 @@ int configure_search(lslam_ctx *ctx, RunCall &call) {
       sa.kc = ctx->kc.view;
       sa.ks = ctx->ks.view;
       sa.grid = 1;
-      if (call.ab & LSLAM_AB_REFILL) {  // A/B (off): the second pass's two-launch form -- the five of every listed point between its launches
-        HIP_TRY(ctx->wide_d.reserve(std::max<size_t>(ctx->n_points, 1) * 5));
-        HIP_TRY(ctx->wide_p.reserve(std::max<size_t>(ctx->n_points, 1) * 5));
-        sa.wide_d = ctx->wide_d.p;
-        sa.wide_p = ctx->wide_p.p;
-      }
       sa.grid_clip_margin = GRID_CLIP_MARGIN_MIN;
       // The x-subdivided tables for the plain first pass: where AUTO chose the grid sweep (an explicit LSLAM_SEARCH_GRID keeps
-      // the cubic table -- its pose bytes are pinned -- unless LSLAM_GRID_XSUB forces them, for tests), not for the A/B forms of
-      // the sweep (refill, fit cache, second probe), not with LSLAM_AB_GRID_CUBIC.
+      // the cubic table -- its pose bytes are pinned -- unless LSLAM_GRID_XSUB forces them, for tests), not with LSLAM_AB_GRID_CUBIC.
       const int xsub = ctx->env_grid_xsub >= 1 ? ctx->env_grid_xsub : LSLAM_GRID_XSUB_DEFAULT;
       const bool by_auto = call.search != LSLAM_SEARCH_GRID;
       if (xsub > 1 && (by_auto || ctx->env_grid_xsub > 1) && !ctx->defer_trees &&  // (a deferred-trees map whose trees a tie forced: the mapping frame)
-          !(call.ab & (LSLAM_AB_GRID_CUBIC | LSLAM_AB_REFILL | LSLAM_AB_FIT_CACHE | LSLAM_AB_SECOND_PROBE))) {
+          !(call.ab & LSLAM_AB_GRID_CUBIC)) {
         rc = ensure_grid_fine(ctx, ctx->env_grid_cell > 0.0f ? ctx->env_grid_cell : o.grid_cell, xsub, &call.fine);
         if (rc) return rc;
       }
     }
   }
   if (!call.fine && ctx->fine_epoch != ctx->map_epoch && (ctx->kfc.pts.p || ctx->kfs.pts.p)) drop_grid_fine(ctx);  // another map's
-  ctx->ab_now = call.ab;
   const bool grid_on = sa.grid != 0;
-  call.no_probe2 = (call.ab & LSLAM_AB_SECOND_PROBE) == 0;  // A/B (off): a second, wider probe before the tree search
   // neighbour lists carried from sweep to sweep by certificate where a point has hardly moved (sweep_body): lslam_opts.knn_cert
   // = 0 searches every point in every sweep, 2 takes the certificate sweep whatever the size of the launch (tests); the
   // environment's LSLAM_KNN_CERT / LSLAM_CERT_TRY_M / LSLAM_CERT_TRACK_M, read when the context was made, override the options
@@ -2133,15 +1994,6 @@ int configure_search(lslam_ctx *ctx, RunCall &call) {
     sa.prev_q = ctx->prev_q.p;
     sa.prev_lb = nullptr;
     sa.grid_hint = ctx->prev_lb.p;  // (the certificate sweep's per-point array, free in this mode)
-    if (sa.grid == 1 && (call.ab & LSLAM_AB_FIT_CACHE)) {  // the fit cache (sweep_grid_kernel)
-      const size_t nf = std::max<size_t>(ctx->n_points, 1);
-      HIP_TRY(ctx->fit_ids.reserve(5 * nf));
-      HIP_TRY(ctx->fit_val.reserve(5 * nf));
-      sa.fit_ids = ctx->fit_ids.p;
-      sa.fit_val = ctx->fit_val.p;
-      sa.n_fit = (int32_t)nf;
-      sa.fit_from_sweep = ctx->env_fit_from_sweep > 0 ? ctx->env_fit_from_sweep : 3;
-    }
   }
   if ((sa.prev_q || sa.grid) && (ctx->env_debug_cert_stats || o.debug_stats)) {
     if (!ctx->cert_stats.p) {
@@ -2150,8 +2002,6 @@ int configure_search(lslam_ctx *ctx, RunCall &call) {
     }
     sa.cert_stats = ctx->cert_stats.p;
   }
-  rc = configure_fused_tail(ctx, call);
-  if (rc) return rc;
   // a batch through the grid sweep launches, from a loop's second sweep on, only the workgroups of the scans still running
   call.compact = sa.grid == 1 && n_scans >= 4 && !(call.ab & LSLAM_AB_NO_COMPACT);
   call.done_iters.assign((size_t)call.n_chunks, 0);
@@ -2169,16 +2019,15 @@ int enqueue_chunk(lslam_ctx *ctx, RunCall &call, int c, int iters) {
     // the first sweep of a loop is bounded by the acceptance gate only, later ones also by the
     // neighbours the previous sweep of THIS loop found
     ch.sc.prev_valid = (ch.sc.bounded && call.done_iters[(size_t)c] > 0) ? 1 : 0;
-    int variant = -1;
     // (compacted: no LiDAR workgroup of a running scan is left -- only the stereo rows carry its loop -- nothing to sweep)
     if (!(ch.sc.active_blocks && ch.sc.n_active <= 0)) {
       hipEvent_t e0, e1;
       HIP_TRY(sweep_events(ctx, call, call.n_launches, &e0, &e1));
-      HIP_TRY(sweep_launch(ctx, ch.sc, call.o.jtj_mode, e0, e1, &variant, call.fine));
+      HIP_TRY(sweep_launch(ctx, ch.sc, call.o.jtj_mode, (call.ab & LSLAM_AB_GRID_GENERAL) != 0, e0, e1, call.fine));
       ++call.n_launches;
     }
     HIP_TRY(launch_stereo(ch.stc, ctx->stream));
-    if (variant != SWEEP_VARIANT_DEEP_FUSED) HIP_TRY(launch_solve(ch.soc, ctx->stream));
+    HIP_TRY(launch_solve(ch.soc, ctx->stream));
     ++call.done_iters[(size_t)c];
   }
   return LSLAM_OK;
@@ -2278,7 +2127,6 @@ int fine_score_pass(lslam_ctx *ctx, RunCall &call) {
   for (int32_t p = 0; p < n_scans; ++p) any_conv = any_conv || ctx->h_state.p[p].converged;
   if (!any_conv) return LSLAM_OK;
   SweepArgs sf = call.sa;
-  sf.tail = SweepTail{};  // this pass only reduces
   sf.bounded = 0;
   sf.prev_valid = 0;
   sf.fine_gate_c = 0.02f;  // :282
@@ -2289,7 +2137,7 @@ int fine_score_pass(lslam_ctx *ctx, RunCall &call) {
     ChunkArgs ch;
     rc = slice_chunk(ctx, call, sf, c, true, ch);
     if (rc) return rc;
-    HIP_TRY(sweep_launch(ctx, ch.sc, call.o.jtj_mode));
+    HIP_TRY(sweep_launch(ctx, ch.sc, call.o.jtj_mode, true));  // (the gate on the nearest neighbour: the general kernel's)
     HIP_TRY(launch_solve(ch.soc, ctx->stream));
   }
   double xs[NCOL] = {0};
@@ -2398,14 +2246,13 @@ int run_batch_impl(lslam_ctx *ctx, int32_t n_scans, float *poses, const lslam_op
   int rc = validate_call(ctx, call);
   if (!rc) rc = upload_states(ctx, call);
   if (!rc && call.sharded) rc = run_sharded_loop(ctx, call);
-  if (!rc && !call.sharded) rc = run_persistent(ctx, call);
-  if (!rc && !call.sharded && !call.gnp_done) {
+  if (!rc && !call.sharded) {
     rc = configure_search(ctx, call);
     if (!rc) rc = call.compact ? run_chunks_compact(ctx, call) : run_chunks_batched(ctx, call);
   }
   if (!rc) rc = fine_score_pass(ctx, call);
   if (rc) return rc;
-  ctx->grid_state_valid = !call.sharded && !call.gnp_done && ctx->sweep_variants[SWEEP_VARIANT_GRID] > call.grid_launches_before && n_scans == 1;
+  ctx->grid_state_valid = !call.sharded && ctx->sweep_variants[SWEEP_VARIANT_GRID] > call.grid_launches_before && n_scans == 1;
   ctx->stage_busy = false;  // the stream has been waited for since the scan was set
   if (call.lazy) {  // a point's answer needed nanoflann's visit order (sweep_wide_kernel): the trees after all, and the call again
     bool need_tree = false;
@@ -3137,7 +2984,7 @@ static int sweep_ex_impl(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, 
     sa.groups = ctx->groups.p;
     sa.n_groups = (int32_t)ctx->h_groups.size();
     sa.group_block_base = 0;
-    HIP_TRY(hipMemsetAsync(ctx->cert_count.p, 0, 6 * sizeof(int32_t), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->cert_count.p, 0, 4 * sizeof(int32_t), ctx->stream));
     if (carried || first) {  // a sweep of the production loop, kernel for kernel (include/lslam_c.h LSLAM_SWEEP_CARRIED / _FIRST)
       HIP_TRY(ctx->prev_q.reserve(std::max<size_t>(N, 1)));
       sa.bounded = 1;
@@ -3163,7 +3010,7 @@ static int sweep_ex_impl(lslam_ctx *ctx, const float pose[6], int32_t jtj_mode, 
     rc = ensure_grid_fine(ctx, ctx->env_grid_cell > 0.0f ? ctx->env_grid_cell : 0.0f, ctx->env_grid_xsub, &fine);
     if (rc) return rc;
   }
-  HIP_TRY(sweep_launch(ctx, sa, jtj_mode, nullptr, nullptr, nullptr, fine));
+  HIP_TRY(sweep_launch(ctx, sa, jtj_mode, (ctx->env_ab & LSLAM_AB_GRID_GENERAL) != 0, nullptr, nullptr, fine));
   SolveArgs so{};
   so.states = ctx->d_state.p;
   so.partials = ctx->partials.p;

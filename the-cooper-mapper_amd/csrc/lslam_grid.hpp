@@ -136,11 +136,6 @@ enum : int {
 //   * points in rows or cells that were clipped are farther than sqrt(bound) (padded), hence farther than five known points;
 //   * d[0] < d[1] < ... < d[4] < (sixth smallest candidate distance) (1 - GRID_NF_PRUNE_SLACK): no tie that nanoflann's visit
 //     order would have decided, and no sixth point close enough for the rounding of nanoflann's pruning bound to matter.
-// R: rings of cells around the query's cell -- 1: the 27-cell probe of pass 1 (nine runs of three cells); 2: 125 cells
-// (twenty-five runs of five), for the points the 27-cell probe could not prove: guaranteed radius c (2 + wall) instead of
-// c (1 + wall), rows clipped to the BALL of the caller's bound (which such a point always has: the fifth distance the first
-// probe saw).  rows: 2 (2R + 1)^2 words per lane.
-//
 // KEEP: also hand out what was fetched: (*five)[3 j ..] = x, y, z of G.pts[p[j]], the points of the five returned, when
 // *five_valid -- wave-uniform: no lane of the wavefront took the re-sort branch, so every lane's five are its first five
 // survivors.  A caller that goes on to fit them (the lean grid sweep) need not gather them a second time.  (Plain floats: an
@@ -152,7 +147,7 @@ enum : int {
 // unclipped exactly the three coarse cells, clipped to 2 rb + c / xsub instead of 2 rb + c.  A point left out differs by
 // more than rbc xsub less the rounding slack in SUB-cell units, i.e. by at least rb - GRID_U_SLACK c / xsub metres: cl and
 // clip_lo2 keep their values and their claim.  The loop, the survivors and the proof are the same text.
-template <int BLOCK, int R = 1, bool KEEP = false, bool FINE = false>
+template <int BLOCK, bool KEEP = false, bool FINE = false>
 LSLAM_DEV int knn5_grid(const CellGrid &G, const bool on, const float qx, const float qy, const float qz, const float bound,
                         const float clip_margin, lds_u32 *rows, float (&d)[5], int (&p)[5], float &lb6 LSLAM_SEC_PARAM,
                         float (*five)[15] = nullptr, bool *five_valid = nullptr) {
@@ -161,13 +156,13 @@ LSLAM_DEV int knn5_grid(const CellGrid &G, const bool on, const float qx, const 
     d[i] = FLT_MAX;
     p[i] = -1;
   }
-  static_assert(!FINE || (R == 1 && !LSLAM_GRID_BALL), "the sub-cell clip is the 27-cell probe's box clip");
+  static_assert(!FINE || !LSLAM_GRID_BALL, "the sub-cell clip is the probe's box clip");
   const float ux = __fmul_rn(__fsub_rn(qx, G.org[0]), FINE ? G.inv_cx : G.inv_c);  // FINE: in sub-cells
   const float uy = __fmul_rn(__fsub_rn(qy, G.org[1]), G.inv_c);
   const float uz = __fmul_rn(__fsub_rn(qz, G.org[2]), G.inv_c);
   // interior cell: 1 <= i <= n - 2 on every axis (NaN fails every comparison)
-  constexpr int W = 2 * R + 1, NR = W * W;          // rows per probe
-  constexpr uint32_t IDB = R == 1 ? GRID_ID_BITS : GRID_ID_BITS + 1;  // id = (row slot << GRID_ROW_BITS) | offset in the row
+  constexpr int R = 1, W = 2 * R + 1, NR = W * W;   // one ring of cells around the query's cell: nine rows of three cells
+  constexpr uint32_t IDB = GRID_ID_BITS;            // id = (row slot << GRID_ROW_BITS) | offset in the row
   constexpr uint32_t IDM = (1u << IDB) - 1u;
   static_assert(NR - 1 <= (int)(IDM >> GRID_ROW_BITS), "row slots must fit the id");
   const float sx = FINE ? (float)G.xsub : 1.0f;
@@ -197,7 +192,7 @@ LSLAM_DEV int knn5_grid(const CellGrid &G, const bool on, const float qx, const 
   // BALL of radius rb, not its box: a row whose nearest wall is g cells away (in y and z) is scanned over
   // [ux - w, ux + w], w = sqrt(rbc^2 - g^2), and not at all when g > rbc.  g is taken a rounding slack short and w a hair
   // long, so a point outside the scanned cells is still farther than rb - GRID_U_SLACK c (the box version's claim).
-  const bool ball = (R > 1 || LSLAM_GRID_BALL) && bound < 1.0e30f;
+  const bool ball = LSLAM_GRID_BALL && bound < 1.0e30f;
   const float rbc2 = ball ? (sqrtf(bound) * (1.0f + 1.0e-5f) + clip_margin) * G.inv_c : 0.0f;
   const float rbcs = rbc2 * rbc2;
   const int iy = alive0 ? (int)fy0 : R, iz = alive0 ? (int)fz0 : R;

@@ -90,7 +90,6 @@ struct CertPlan {
   int32_t *work;
   int32_t *count, *count_next;
   int32_t *ticket, *ticket_next;  // the next item to deal (sweep_queue_kernel)
-  int32_t *ticket2 = nullptr, *ticket2_next = nullptr;  // ... of a second consumer of the same list (sweep_refill_kernel), or null
 };
 #ifndef LSLAM_CERT_GROUP
 #define LSLAM_CERT_GROUP 256
@@ -116,10 +115,7 @@ struct CubeGridDev {
   const TreeView *trees;
 };
 
-// The solve fused into the tail of a sweep launch (ScanMatch.cpp:206-260 right behind :97-204): the block that retires a
-// scan's LAST partial record runs the cross-block reduction, the 6x6 solve and the pose update for that scan, so a
-// Gauss-Newton iteration of a latency-bound (single-scan) launch is ONE launch instead of a sweep, a 13 us solve launch and
-// the gap between them.  count == nullptr: no fusion (the solve kernel follows as its own launch).
+// What solve_finish (lslam_solve_dev.hpp) needs besides the sums: the solve kernel's and the odometry node's persistent loop's.
 struct SolveParams {
   int32_t max_iterations;
   int32_t min_rows;          // 50 (ScanMatch.cpp:142); 10 in LaserOdometry.cpp:501
@@ -127,12 +123,6 @@ struct SolveParams {
   int32_t nan_reset;         // variant B: LaserOdometry.cpp:622-634
   float delta_r_abort, delta_t_abort;
   float eig_thresh;          // 100 (ScanMatch.cpp:223); 10 in LaserOdometry.cpp:596
-};
-struct SweepTail {
-  int32_t *count;            // [n_prob] blocks of the scan that have stored their record in this launch (zero between launches)
-  const ProbBlocks *probs;   // [n_prob] absolute block range of each scan
-  float *partials_abs;       // the records of block 0 (SweepArgs::partials is the chunk's base)
-  SolveParams sp;
 };
 
 struct SweepArgs {
@@ -149,21 +139,14 @@ struct SweepArgs {
   // neighbours in wide_d / wide_p (positions in kc.pts / ks.pts); sweep_queue_kernel then only runs their residual chain.  A
   // point whose answer needs nanoflann's visit order (an exact distance tie) raises GNState::pad of its scan: the caller builds
   // the trees and runs the call again through them.
-  // the fit cache of the grid sweep (sweep_grid_kernel; null: off): per scan point the five neighbours its last fit was made
-  // from (positions in ks.pts, -1: none) and the plane with its verdict, both as five planes of n_fit words
-  int32_t *fit_ids;        // [5][n_fit]
-  float *fit_val;          // [5][n_fit]  plane[0..3], found (0 / 1)
-  int32_t n_fit;
-  int32_t fit_from_sweep;  // sweep index (0 = a loop's first) from which cached fits are used; they are stored one sweep earlier
   float wide_nf_slack;     // relative margin of the wide probe's fifth-against-sixth test (lslam_grid.hpp GRID_NF_PRUNE_SLACK_WIDE, or 0)
   float *wide_d;           // [points][5]
   int32_t *wide_p;         // [points][5]
   int32_t *wide_off;       // [nb_total + 1] exclusive prefix of the listed points per pass-1 workgroup (grid_prefix_kernel)
-  // the grid sweep's second level: the points pass 1 listed get a second, wider probe (125 cells, clipped to the ball of what
-  // the first probe saw) by sweep_queue_kernel<..., 3>; what THAT cannot prove is listed again -- same shape as the first
-  // lists, entries = point offset from the group's first point -- and only those few go to the tree search
-  uint16_t *need2_list;    // [nb_total][SWEEP_BLOCK]
-  uint16_t *need2_cnt;     // [nb_total]
+  // Two pointers nothing reads (always null; a retired second probe's lists lived here).  sweep_queue_kernel launders them
+  // beside grid_hint in one empty asm, and with a shorter operand list its register allocation comes out differently (same
+  // VGPRs, scratch and occupancy, a few per cent other instructions).  Taking them out is a change to measure on its own.
+  void *spare0, *spare1;
   float *grid_hint;        // [points] grid sweep, pass 1 -> pass 2: an upper bound of the fifth neighbour's squared distance of a
                            // point the probe could not prove (the fifth smallest distance it saw, FLT_MAX if it saw fewer than five)
   const float4 *q;  // scan points of all scans, sensor frame, Morton order within a scan
@@ -190,7 +173,6 @@ struct SweepArgs {
   // fine_gate_s (surf blocks) instead of d2[4] < 5, and the launch works on the scans whose loop CONVERGED (their `done`
   // flag is set) instead of the ones still running
   float fine_gate_c, fine_gate_s;
-  SweepTail tail;
   // the certificate sweep's second pass (sweep_body, sweep_queue_kernel); need_cnt null: no certificates
   uint8_t *need_list;              // [nb_total][SWEEP_BLOCK] lanes of pass-1 workgroup b whose point is left to pass 2
   uint16_t *need_cnt;              // [nb_total] how many
@@ -228,18 +210,6 @@ struct SolveArgs {
   int32_t nan_reset;         // variant B: LaserOdometry.cpp:622-634
   double *sums_out;          // reduce_only: also write the [n_prob][32] sums here (the all-reduce buffer)
 };
-
-// gn_persistent_kernel: the whole Gauss-Newton loop of one resident scan in one cooperative launch (lslam_kernels.hip)
-struct GnLoopArgs {
-  float *slots;       // [2][nb_total][NCOL] the blocks' sums; exchange slots, filled with the sentinel 0xFFF8DEAD before the launch
-  double *gslots;     // [3][32][NCOL] the 32 row groups' sums (same sentinel in both halves)
-  unsigned *bar;      // [1] abort flag
-  GNState *state_out; // where workgroup 0 leaves the final state (SweepArgs::states holds the initial one)
-  int32_t max_iterations, min_rows;
-  float delta_r_abort, delta_t_abort, eig_thresh;
-};
-int gn_persistent_capacity(int device);
-hipError_t launch_gn_persistent(const SweepArgs &a, int jtj_mode, const GnLoopArgs &g, hipStream_t s);
 
 // Stereo reprojection rows of the joint system (lslam_stereo.hip; include/lslam_c.h lslam_stereo_cam).
 struct StereoCam {
@@ -306,21 +276,18 @@ enum : int {
   SWEEP_VARIANT_CUBES = 3,      // sweep_kernel<256, false, true, 32>
   SWEEP_VARIANT_CUBES_OVF = 4,  // sweep_kernel<256, true, true, 32>
   SWEEP_VARIANT_PACKET = 5,     // sweep_kernel<256, true, false, 4, true>
-  SWEEP_VARIANT_PERSISTENT = 6, // gn_persistent_kernel
-  SWEEP_VARIANT_DEEP_FUSED = 7, // sweep_kernel<256, *, false, 32> with the solve in its tail (single scans)
+  // 6, 7: two retired instantiations; the slots stay so that lslam_debug_sweep_launches keeps its indices (they read 0)
   SWEEP_VARIANT_GRID = 8,       // sweep_grid_kernel<256> (+ sweep_queue_kernel for the points it could not prove)
-  SWEEP_VARIANT_GRID_WIDE = 9,  // sweep_grid_kernel<256, true>: a map without trees, a small launch -- unproven points resolved in place
-  SWEEP_N_VARIANTS = 10
+  SWEEP_N_VARIANTS = 9
 };
-// A grid sweep the lean instantiation sweep_grid_kernel<256, false, false, true> computes as the general one does: the production
-// loop's launch -- MFMA sums, no taps, the acceptance gate on the fifth distance, the bounded search, no counters, no fit cache.
-// launch_sweep_grid takes the lean kernel when `lean` is set, which only such a launch may be given (and not resolve_in_place).
+// A grid sweep the lean instantiation sweep_grid_kernel<256, true> computes as the general one does: the production loop's
+// launch -- MFMA sums, no taps, the acceptance gate on the fifth distance, the bounded search, no counters.
+// launch_sweep_grid takes the lean kernel when `lean` is set, which only such a launch may be given.
 inline bool grid_sweep_lean_ok(const SweepArgs &a, int jtj_mode) {
-  return jtj_mode == 1 && !a.flags_out && !a.coeff_out && !a.idx_out && a.fine_gate_c < 0.0f && a.bounded && !a.cert_stats && !a.fit_ids;
+  return jtj_mode == 1 && !a.flags_out && !a.coeff_out && !a.idx_out && a.fine_gate_c < 0.0f && a.bounded && !a.cert_stats;
 }
 // fine: a.kc / a.ks are x-subdivided tables (CellGrid::xsub); sweep_grid_kernel<.., FINE>, lean or general
-hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool resolve_in_place = false,
-                             bool lean = false, bool fine = false);
+hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool lean = false, bool fine = false);
 hipError_t launch_sweep_wide(const SweepArgs &a, hipStream_t s);  // sweep_wide_kernel (its prefix: launch_sweep_plan with_prefix)
 hipError_t launch_knn5_wide(const CellGrid &G, const float4 *q, int nq, float nf_slack, int32_t *idx, float *d2, uint8_t *undecided, hipStream_t s);
 hipError_t launch_knn5_grid(const CellGrid &G, const TreeView &T, const float4 *q, int nq, int32_t *idx, float *d2,
@@ -348,9 +315,8 @@ hipError_t launch_compact_active(const GNState *states, const ProbBlocks *probs,
                                  int32_t *count_out, hipStream_t s, int32_t *running_out = nullptr);
 // (running_out, or null: 1 when a scan of the chunk is still running, 0 otherwise -- with the stereo term a running scan may have
 // no LiDAR workgroups at all, so count_out = 0 does not mean that the chunk's loops are over)
-hipError_t launch_sweep_plan(const SweepArgs &a, hipStream_t s, const CertPlan &plan, int level, bool with_prefix);
-hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, int level = 0, bool planned = false);
-hipError_t launch_sweep_refill(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, const CertPlan &plan);
+hipError_t launch_sweep_plan(const SweepArgs &a, hipStream_t s, const CertPlan &plan, bool with_prefix);
+hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, bool planned = false);
 hipError_t launch_sweep(const SweepArgs &a, int jtj_mode, hipStream_t s,
                         hipEvent_t start = nullptr, hipEvent_t stop = nullptr, int *variant = nullptr, bool *cert_launched = nullptr);
 hipError_t launch_solve(const SolveArgs &a, hipStream_t s);
@@ -475,7 +441,6 @@ struct EnvOnce {
   bool no_morton = false, host_morton = false;  // LSLAM_NO_MORTON, LSLAM_HOST_MORTON
   bool odom_inline = false;      // LSLAM_ODOM_INLINE_SEARCH
   bool odom_trees = false;       // LSLAM_ODOM_TREES=1: A/B switch -- lslam_odometry_match through kd-trees, one launch per step (rounds 1-5)
-  bool gnp_coop = false;         // LSLAM_GNP_COOPERATIVE
   bool tiny_phase_off = false;   // LSLAM_TINY_PHASE=0
   bool no_reg_nodes = false;     // LSLAM_NO_REG_NODES
   bool no_level_build = false;   // LSLAM_NO_LEVEL_BUILD

@@ -55,9 +55,8 @@ __device__ unsigned long long g_pass2_hist[8];  // listed points by the bound th
 // PACKET: the 5-NN search is the wave-cooperative one of lslam_packet.hpp (scalar loads, no per-lane
 // traversal stack: LDS_DEPTH = 4 only provides the eight staging rows of the MFMA contraction); lanes
 // that see an exact distance tie redo their search with nanoflann's traversal (stack in HBM).
-// One block of one sweep: the body of sweep_kernel, and of an iteration of gn_persistent_kernel.  `st` is the scan's
-// state -- in HBM (STATE_LDS = false: R, t, sc arrive by scalar loads) or a workgroup's LDS copy (true); `red` and
-// `stack_lds` are the caller's LDS; the block's 32 sums go to partial_out[0..32).
+// One block of one sweep: the body of sweep_kernel and of sweep_queue_kernel.  `st` is the scan's state in HBM (R, t, sc
+// arrive by scalar loads); `red` and `stack_lds` are the caller's LDS; the block's 32 sums go to partial_out[0..32).
 // CERT (the bounded production sweep over whole-map trees, two launches): 1 = the pass over every point, which carries the
 // neighbour lists of points that have hardly moved over by certificate and lists the others; 2 = the pass over the listed
 // points (sweep_queue_kernel: `q_item` is this lane's point or -1, the sums are ADDED to partial_out).  See below.
@@ -65,7 +64,7 @@ __device__ unsigned long long g_pass2_hist[8];  // listed points by the bound th
 // hands over, no certificate bookkeeping); 2 = the grid sweep's on a map without trees (neighbours given by sweep_wide_kernel).
 // A template argument, not a run-time flag: each second pass is compiled without the others' search code (the one kernel for
 // all three needed 96 VGPRs + 92 bytes of scratch per lane).
-template <int BLOCK, bool OVF, bool CUBES, int LDS_DEPTH, bool PACKET, bool STATE_LDS, bool FUSE = false, int CERT = 0, int GRIDQ = 0>
+template <int BLOCK, bool OVF, bool CUBES, int LDS_DEPTH, bool PACKET, int CERT = 0, int GRIDQ = 0>
 LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, const BlockDesc &bd, const GNState *st,
                           uint32_t *stack_lds, float (*red)[NCOL], float *partial_out, const int prev_valid, const int q_item = -1) {
   constexpr int NWAVE = BLOCK / 64;
@@ -83,14 +82,7 @@ LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, 
   // state invariant (the solve kernel writes it between launches) and would fetch it with vector loads into 18 VGPRs
   // that then sit in the register file through the whole search: fetched with scalar loads they live in SGPRs.
   float R[9], t[3], sc[6];
-  if (STATE_LDS) {  // the workgroup's own copy: wave-uniform values, moved to SGPRs
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(st->R[i])));
-#pragma unroll
-    for (int i = 0; i < 3; ++i) t[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(st->t[i])));
-#pragma unroll
-    for (int i = 0; i < 6; ++i) sc[i] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(st->sc[i])));
-  } else {
+  {
     static_assert(offsetof(GNState, R) == 24 && offsetof(GNState, t) == 60 && offsetof(GNState, sc) == 72, "GNState layout");
     typedef uint32_t u32x16_t __attribute__((ext_vector_type(16)));
     typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
@@ -190,68 +182,8 @@ LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, 
   static_assert(GRIDQ == 0 || CERT == 2, "GRIDQ is a mode of the second pass");
   constexpr bool grid = GRIDQ != 0;
   bool track = CERT == 2 && !grid && a.prev_q != nullptr;  // ... which keeps the bound the next sweep's certificate needs
-  if (GRIDQ == 3) {
-    // The grid sweep's SECOND probe: this lane's point is one the 27-cell probe could not prove (q_item).  125 cells now --
-    // guaranteed radius c (2 + wall) -- clipped to the ball of what is known about the point: the fifth distance the first probe
-    // saw, the carried bound, the gate.  Proven: the residual chain below.  Still unproven (a sparser neighbourhood yet, an
-    // exact tie): listed once more, at this work item's fixed place, for the tree search.
-    static_assert(GRIDQ != 3 || (2 * LDS_DEPTH >= 50 && BLOCK == 256), "the second probe's row table: 25 runs per lane");
-    __shared__ int wave_needy2[NWAVE];
-    CellGrid G;
-    G.cell_start = is_surf ? a.ks.cell_start : a.kc.cell_start;
-    G.pts = is_surf ? a.ks.pts : a.kc.pts;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) G.org[i] = is_surf ? a.ks.org[i] : a.kc.org[i];
-    G.inv_c = is_surf ? a.ks.inv_c : a.kc.inv_c;
-    G.c = is_surf ? a.ks.c : a.kc.c;
-    G.nx = is_surf ? a.ks.nx : a.kc.nx;
-    G.ny = is_surf ? a.ks.ny : a.kc.ny;
-    G.nz = is_surf ? a.ks.nz : a.kc.nz;
-    G.n_pts = is_surf ? a.ks.n_pts : a.kc.n_pts;
-    if (active) q = a.q[qi];
-    sel[0] = ((R[0] * q.x + R[1] * q.y) + R[2] * q.z) + t[0];
-    sel[1] = ((R[3] * q.x + R[4] * q.y) + R[5] * q.z) + t[1];
-    sel[2] = ((R[6] * q.x + R[7] * q.y) + R[8] * q.z) + t[2];
-    float bound2 = a.bounded ? 5.0f * (1.0f + 1e-5f) : FLT_MAX;
-    if (active) {
-      if (a.bounded && prev_valid) bound2 = fminf(bound2, grid_carried_bound(a.prev_q[qi], sel));
-      if (a.grid_hint) bound2 = fminf(bound2, a.grid_hint[qi]);
-    }
-    // A point that is known to have five neighbours within two cells is worth the wider probe (the ball it scans is no
-    // bigger than the first probe's block); one that is not -- the first probe saw fewer than five, or its fifth far out --
-    // would scan all 125 cells, hundreds of candidates, with its wavefront waiting: the tree search is the tool for those.
-    const float worth = (2.0f * G.c) * (2.0f * G.c);
-    const bool probe = active && bound2 < worth;
-    float lb6u;
-    int verdict = knn5_grid<BLOCK, 2>(G, probe, sel[0], sel[1], sel[2], bound2, a.grid_clip_margin, (lds_u32 *)(stack_lds + tid), d, p, lb6u);
-    if (verdict == GRID_FAR && !a.bounded) verdict = GRID_UNPROVEN;
-    const bool needy2 = active && (!probe || verdict == GRID_UNPROVEN);
-    const unsigned long long m2 = __ballot(needy2);
-    if (lane == 0) wave_needy2[wave] = __popcll(m2);
-    __syncthreads();
-    int off2 = 0, total2 = 0;
-#pragma unroll
-    for (int w = 0; w < NWAVE; ++w) {
-      const int c2 = wave_needy2[w];
-      off2 += w < wave ? c2 : 0;
-      total2 += c2;
-    }
-    if (needy2) {
-      a.need2_list[(size_t)lb * BLOCK + off2 + __popcll(m2 & ((1ull << lane) - 1ull))] = (uint16_t)(qi - bd.first);
-      if (a.grid_hint && probe && d[4] < 1.0e30f) a.grid_hint[qi] = fminf(a.grid_hint[qi], d[4] * (1.0f + 1e-5f) + 1e-12f);
-    }
-    if (tid == 0) {
-      a.need2_cnt[lb] = (uint16_t)total2;
-      if (a.cert_stats) atomicAdd(a.cert_stats + 2, (unsigned long long)total2);  // debug tap: points left to the tree search
-    }
-    if (active && !needy2 && a.bounded)
-      a.prev_q[qi] = make_float4(sel[0], sel[1], sel[2], (verdict == GRID_PROVEN && d[4] < 5.0f) ? d[4] : FLT_MAX);
-    active = active && !needy2;
-    do_search = false;
-    __syncthreads();  // the row table is dead: its words become the staging rows of the contraction
-  }
   if (CERT == 1) {
-    static_assert(CERT != 1 || (!PACKET && !CUBES && !STATE_LDS && BLOCK <= 256), "certificate pass: whole-map lane search, byte lists");
+    static_assert(CERT != 1 || (!PACKET && !CUBES && BLOCK <= 256), "certificate pass: whole-map lane search, byte lists");
     // the last update of this scan, as the largest displacement of a point within CERT_RANGE_M of the sensor [m]
     const float dr_deg = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(st->delta_r)));
     const float dt_cm = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(st->delta_t)));
@@ -334,7 +266,7 @@ LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, 
   }
 
   if (active) {
-    if (!PACKET && do_search && GRIDQ != 3) {
+    if (!PACKET && do_search) {
     q = a.q[qi];
     // util/transform_utils.h:476-482 pointAssociateToMap: it * p
     sel[0] = ((R[0] * q.x + R[1] * q.y) + R[2] * q.z) + t[0];
@@ -375,7 +307,7 @@ LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, 
       sel[2] = ((R[6] * q.x + R[7] * q.y) + R[8] * q.z) + t[2];
       if (a.bounded) a.prev_q[qi] = make_float4(sel[0], sel[1], sel[2], (p[4] >= 0 && d[4] < 5.0f) ? d[4] : FLT_MAX);
     }
-    if (GRIDQ != 2 && GRIDQ != 3 && do_search) {
+    if (GRIDQ != 2 && do_search) {
     KdStack<BLOCK, OVF, LDS_DEPTH> stk;
     stk.lds = (lds_u32 *)(stack_lds + tid);
     stk.ovf = OVF ? a.stack_ovf + ((size_t)lb * BLOCK + tid) : nullptr;  // lb: unique per workgroup of a launch, < nb_total
@@ -467,12 +399,12 @@ LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, 
     (void)searched;
     if (a.dbg) dbg_t1 = __builtin_readcyclecounter();
 
-    // (GRIDQ == 2 with trees -- a.grid == 1: the neighbours sweep_refill_kernel left are positions in the tree's point array)
-    point_residual(a, bd, is_surf, ((GRIDQ == 2 && a.grid == 2) || GRIDQ == 3) ? (is_surf ? a.ks.pts : a.kc.pts) : T.pts, q, sel, d, p, sc, row, rb, kept, matched, score);
+    // (GRIDQ == 2 is launched for a.grid == 2 only: the wide probe's neighbours are positions in the cell-sorted points)
+    point_residual(a, bd, is_surf, (GRIDQ == 2 && a.grid == 2) ? (is_surf ? a.ks.pts : a.kc.pts) : T.pts, q, sel, d, p, sc, row, rb, kept, matched, score);
   }
 
   if (a.dbg) dbg_t2 = __builtin_readcyclecounter();
-  block_accumulate<BLOCK, FUSE, CERT == 2>(jtj_mode, is_surf, row, rb, kept, matched, score, stack_lds, red, partial_out);
+  block_accumulate<BLOCK, CERT == 2>(jtj_mode, is_surf, row, rb, kept, matched, score, stack_lds, red, partial_out);
   if (a.dbg && lane == 0) {  // per-wave phase stamps (shader clock)
     uint64_t *o = a.dbg + ((size_t)lb * NWAVE + wave) * 4;
     o[0] = dbg_t0;
@@ -502,7 +434,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(SolveArgs a) {
     }
     __syncthreads();
   } else {
-    reduce_partials<SOLVE_THREADS, false>(partials, nb, red);
+    reduce_partials<SOLVE_THREADS>(partials, nb, red);
     if (a.partials2) {  // stereo blocks of the joint system: this scan's, same pattern, after its LiDAR blocks
       const ProbBlocks sb = a.probs2[blockIdx.x];
       const float *p2 = a.partials2 + (size_t)sb.first_block * NCOL;
@@ -534,9 +466,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(SolveArgs a) {
 }
 
 // PACKET: the 5-NN search is the wave-cooperative one of lslam_packet.hpp (see sweep_body).
-// FUSE: the block that retires a scan's last record of the launch runs that scan's reduction + solve (SweepTail).
 // CERT = 1: pass 1 of the certificate sweep (sweep_body); sweep_queue_kernel is pass 2.
-template <int BLOCK, bool OVF, bool CUBES, int LDS_DEPTH, bool PACKET = false, bool FUSE = false, int CERT = 0>
+template <int BLOCK, bool OVF, bool CUBES, int LDS_DEPTH, bool PACKET = false, int CERT = 0>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LDS_DEPTH <= 16 ? LSLAM_SHALLOW_OCC : 2))) void sweep_kernel(SweepArgs a, int jtj_mode) {
   const int lb = xcd_remap(blockIdx.x, a.nb_total);
   const BlockDesc bd = a.blocks[lb];
@@ -548,51 +479,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LDS_DEPTH
   // slots -- word row c, lane slot p -- which are dead once its 5-NN searches are over: no extra LDS,
   // no cross-wavefront hazard (the shallow variant then fits six workgroups per CU instead of four).
   __shared__ uint32_t stack_lds[2 * LDS_DEPTH * BLOCK];
-  sweep_body<BLOCK, OVF, CUBES, LDS_DEPTH, PACKET, false, FUSE, CERT>(a, jtj_mode, lb, bd, st, stack_lds, red, a.partials + (size_t)lb * NCOL, a.prev_valid);
-  if (FUSE) {
-    static_assert(!FUSE || (2 * LDS_DEPTH * BLOCK * 4 >= (int)((SOLVE_GROUPS + 1) * NCOL * sizeof(double) + sizeof(GnShared) + 16)), "the tail's LDS lives in the stack");
-    __shared__ int last;
-    // every wavefront's record stores are at the coherence point before the ticket is taken
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-    const ProbBlocks pb = a.tail.probs[bd.prob];
-    if (threadIdx.x == 0) {
-      // acq_rel: the records published above are ordered before the ticket, and the last block's reads of the others' after it
-      const int ticket = __hip_atomic_fetch_add(a.tail.count + bd.prob, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-      last = ticket == pb.n_blocks - 1;
-      if (last) __hip_atomic_store(a.tail.count + bd.prob, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
-    }
-    __syncthreads();
-    if (!last) return;
-    // the traversal stack is dead: the reduction's 32 x 32 doubles, the totals and the solve's 6 x 6 system live in it
-    double (*redd)[NCOL] = reinterpret_cast<double (*)[NCOL]>(stack_lds);
-    double *tot = &redd[SOLVE_GROUPS][0];
-    GnShared &sh = *reinterpret_cast<GnShared *>(tot + NCOL);
-    int &go = *reinterpret_cast<int *>(reinterpret_cast<char *>(&sh) + sizeof(GnShared));
-    const int tid = threadIdx.x;
-    if (tid == 0) st->clk[0] = wall_clock64();
-    reduce_partials<BLOCK, true>(a.tail.partials_abs + (size_t)pb.first_block * NCOL, pb.n_blocks, redd);
-    __syncthreads();
-    if (tid < NCOL) {
-      double v = 0.0;
-#pragma unroll
-      for (int g = 0; g < SOLVE_GROUPS; ++g) v += redd[g][tid];
-      tot[tid] = v;
-      st->sums[tid] = v;
-    }
-    __syncthreads();
-    solve_finish(st, tot, sh, go, a.tail.sp);
-  }
+  sweep_body<BLOCK, OVF, CUBES, LDS_DEPTH, PACKET, CERT>(a, jtj_mode, lb, bd, st, stack_lds, red, a.partials + (size_t)lb * NCOL, a.prev_valid);
 }
 
 // Pass 2 of the certificate sweep (sweep_body), in two launches.
 // cert_plan_kernel, one wavefront per group: how many chunks of BLOCK listed points the group's pass-1 workgroups left (none for
 // a scan whose loop has ended), and that many work items (group, chunk) appended to the work list.  The order of the list
 // depends on the order of the atomics; nothing else does -- an item's sums go to a place of its own.
-// level 0: the first-level lists (need_cnt); when second-level lists exist their counts are zeroed here, so that a block no
-// work item of the second probe is made for reads as empty.  level 1: the second-level lists (need2_cnt).
 LSLAM_DEV void grid_prefix_block(const SweepArgs &a, int *part);
-__global__ __launch_bounds__(256) void cert_plan_kernel(SweepArgs a, CertPlan plan, int level, int with_prefix) {
+__global__ __launch_bounds__(256) void cert_plan_kernel(SweepArgs a, CertPlan plan, int with_prefix) {
   // a map without trees (a.grid == 2): the exclusive prefix of the list lengths that sweep_wide_kernel needs rides in one more
   // workgroup of this launch instead of a launch of its own (grid_prefix_kernel: five launches per sweep of a mapping frame)
   if (with_prefix && blockIdx.x == gridDim.x - 1) {
@@ -606,12 +501,11 @@ __global__ __launch_bounds__(256) void cert_plan_kernel(SweepArgs a, CertPlan pl
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // the counters of the NEXT plan (they alternate)
     *plan.count_next = 0;
     *plan.ticket_next = 0;
-    if (plan.ticket2_next) *plan.ticket2_next = 0;
   }
   // debug tap of the grid sweep (lslam_opts.debug_stats): points listed for pass 2 / points swept, in total and by feature type
   // and sweep of the loop.  Counted HERE, from the counts pass 1 left -- per workgroup of this (tiny) launch a histogram in
   // LDS, then one atomic per non-empty slot -- so that a run with the tap on times the same sweep kernel as one without
-  const bool tap = a.cert_stats != nullptr && a.grid && !level;  // launch-uniform
+  const bool tap = a.cert_stats != nullptr && a.grid;  // launch-uniform
   __shared__ unsigned int hist[CERT_STATS_WORDS];
   if (tap) {
     if (threadIdx.x < CERT_STATS_WORDS) hist[threadIdx.x] = 0;
@@ -628,8 +522,7 @@ __global__ __launch_bounds__(256) void cert_plan_kernel(SweepArgs a, CertPlan pl
     const int fb = gd.first_block - a.group_block_base;
     int total = 0, swept = 0;
     for (int k = lane; k < gd.n_blocks; k += 64) {
-      total += level ? (int)a.need2_cnt[fb + k] : (int)a.need_cnt[fb + k];
-      if (!level && a.need2_cnt) a.need2_cnt[fb + k] = 0;
+      total += (int)a.need_cnt[fb + k];
       if (tap) swept += a.blocks[fb + k].count;
     }
 #pragma unroll
@@ -664,9 +557,8 @@ __global__ __launch_bounds__(256) void cert_plan_kernel(SweepArgs a, CertPlan pl
 // -- as many as the sweep itself has, nearly all of them leaving at once -- cost 0.25 ms per launch, more than the last
 // sweeps of a batch themselves.  The argument block is re-read through a laundered pointer in every turn: left to itself the
 // compiler carries the sweep's invariants across the loop in registers it does not have (124 bytes of scratch per lane).
-// LIST2: the work items are chunks of the SECOND-level lists (need2_list: point offsets from the group's first point).
-template <int BLOCK, bool OVF, int LDS_DEPTH, int GRIDQ = 0, bool LIST2 = false>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(GRIDQ == 3 ? 3 : (LDS_DEPTH <= 16 ? LSLAM_SHALLOW_OCC : 2)))) void sweep_queue_kernel(const SweepArgs a_in, const int jtj_mode_in, const CertPlan plan) {
+template <int BLOCK, bool OVF, int LDS_DEPTH, int GRIDQ = 0>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LDS_DEPTH <= 16 ? LSLAM_SHALLOW_OCC : 2))) void sweep_queue_kernel(const SweepArgs a_in, const int jtj_mode_in, const CertPlan plan) {
   __shared__ float red[BLOCK / 64][NCOL];
   __shared__ uint32_t stack_lds[2 * LDS_DEPTH * BLOCK];
   __shared__ int next_w;
@@ -683,7 +575,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(GRIDQ == 
     int jtj_mode = jtj_mode_in;
     asm volatile("" : "+s"(a.q), "+s"(a.blocks), "+s"(a.states), "+s"(a.partials), "+s"(a.prev_nb), "+s"(a.prev_q), "+s"(a.prev_lb), "+s"(jtj_mode));
     asm volatile("" : "+s"(a.tc.nodes), "+s"(a.tc.pts), "+s"(a.ts.nodes), "+s"(a.ts.pts), "+s"(a.stack_ovf), "+s"(a.need_list), "+s"(a.need_cnt), "+s"(a.groups));
-    asm volatile("" : "+s"(a.need2_list), "+s"(a.need2_cnt), "+s"(a.grid_hint));
+    asm volatile("" : "+s"(a.spare0), "+s"(a.spare1), "+s"(a.grid_hint));  // (spare0 / spare1: see SweepArgs)
     const int item_id = __builtin_amdgcn_readfirstlane(plan.work[w]);
     const int g = item_id / CERT_GROUP, c = item_id % CERT_GROUP;
     GroupDesc gd = a.groups[g];
@@ -697,7 +589,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(GRIDQ == 
     static_assert(CERT_GROUP <= BLOCK && (CERT_GROUP & (CERT_GROUP - 1)) == 0, "one list length per thread; the search below halves");
     {
       const int k = (int)threadIdx.x, ln = k & 63, wv = k >> 6;
-      int run = k < gd.n_blocks ? (LIST2 ? (int)a.need2_cnt[fb + k] : (int)a.need_cnt[fb + k]) : 0;
+      int run = k < gd.n_blocks ? (int)a.need_cnt[fb + k] : 0;
 #pragma unroll
       for (int o = 1; o < 64; o <<= 1) {
         const int u = __shfl_up(run, o, 64);
@@ -727,147 +619,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(GRIDQ == 
       for (int step = CERT_GROUP / 2; step >= 1; step >>= 1)
         if (pre_lds[k + step] <= i) k += step;
       const int p0 = pre_lds[k];
-      if (LIST2) item = a.blocks[fb].first + (int)a.need2_list[(size_t)(fb + k) * BLOCK + (i - p0)];
-      else item = a.blocks[fb + k].first + (int)a.need_list[(size_t)(fb + k) * BLOCK + (i - p0)];
+      item = a.blocks[fb + k].first + (int)a.need_list[(size_t)(fb + k) * BLOCK + (i - p0)];
     }
-    sweep_body<BLOCK, OVF, false, LDS_DEPTH, false, false, false, 2, GRIDQ>(a, jtj_mode, fb + c, bd, st, stack_lds, red, a.partials + (size_t)(fb + c) * NCOL, a.prev_valid, item);  // (the certificate sweep's second pass only runs with prev_valid set; the grid sweep's runs in a loop's first sweep too)
+    sweep_body<BLOCK, OVF, false, LDS_DEPTH, false, 2, GRIDQ>(a, jtj_mode, fb + c, bd, st, stack_lds, red, a.partials + (size_t)(fb + c) * NCOL, a.prev_valid, item);  // (the certificate sweep's second pass only runs with prev_valid set; the grid sweep's runs in a loop's first sweep too)
     __syncthreads();  // red and the stack columns are free again
-  }
-}
-
-// The grid sweep's second pass as TWO launches (throughput-bound batches on whole-map trees): this one only SEARCHES -- with
-// persistent lanes (knn5_search_refill): a workgroup takes REFILL_CHUNKS consecutive items of the plan, i.e. up to that many
-// workgroups' worth of one group's listed points, as one pool; a lane whose walk has ended hands its five in (wide_d / wide_p,
-// by point) and takes the pool's next point, so a wavefront is no longer as slow as the longest of its first 64 walks with the
-// lanes that drew short ones idle.  sweep_queue_kernel<.., 2> then runs the residual chain of the same items, chunk by chunk,
-// its sums where the one-launch form puts them: same bits.
-#ifndef LSLAM_REFILL_CHUNKS
-#define LSLAM_REFILL_CHUNKS 4
-#endif
-#ifndef LSLAM_REFILL_OCC
-#define LSLAM_REFILL_OCC LSLAM_SHALLOW_OCC
-#endif
-constexpr int REFILL_CHUNKS = LSLAM_REFILL_CHUNKS;
-template <int BLOCK, bool OVF, int LDS_DEPTH>
-struct RefillSrc {
-  const SweepArgs &a;
-  const float (&R)[9];
-  const float (&t)[3];
-  const TreeView &T;
-  const int *pre;   // LDS: where the lists of the group's workgroups begin
-  int *pool_next;   // LDS
-  int fb, i1, prev_valid, qi;
-  LSLAM_DEV bool next(float &qx, float &qy, float &qz, float &bound) {
-    const int i = atomicAdd(pool_next, 1);
-    if (i >= i1) return false;
-    int k = 0;
-#pragma unroll
-    for (int step = CERT_GROUP / 2; step >= 1; step >>= 1)
-      if (pre[k + step] <= i) k += step;
-    qi = a.blocks[fb + k].first + (int)a.need_list[(size_t)(fb + k) * BLOCK + (i - pre[k])];
-    const float4 q = a.q[qi];
-    // util/transform_utils.h:476-482 pointAssociateToMap (sweep_body's statement)
-    qx = ((R[0] * q.x + R[1] * q.y) + R[2] * q.z) + t[0];
-    qy = ((R[3] * q.x + R[4] * q.y) + R[5] * q.z) + t[1];
-    qz = ((R[6] * q.x + R[7] * q.y) + R[8] * q.z) + t[2];
-    bound = 5.0f * (1.0f + 1e-5f);  // (this kernel runs the bounded production sweep only)
-    if (prev_valid && T.n_pts > 0) {
-      const float sel[3] = {qx, qy, qz};
-      bound = fminf(bound, grid_carried_bound(a.prev_q[qi], sel));
-    }
-    if (a.grid_hint) bound = fminf(bound, a.grid_hint[qi]);
-    return true;
-  }
-  LSLAM_DEV void emit(const float (&d)[5], const int (&p)[5]) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      a.wide_d[(size_t)qi * 5 + j] = d[j];
-      a.wide_p[(size_t)qi * 5 + j] = p[j];
-    }
-  }
-};
-template <int BLOCK, bool OVF, int LDS_DEPTH>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LSLAM_REFILL_OCC))) void sweep_refill_kernel(const SweepArgs a, const CertPlan plan) {
-  __shared__ uint32_t stack_lds[2 * LDS_DEPTH * BLOCK];
-  __shared__ int next_w, pool_next;
-  __shared__ int pre_lds[CERT_GROUP + 1];
-  __shared__ int pre_wave[BLOCK / 64];
-  const int n_work = *plan.count;
-  for (;;) {
-    if (threadIdx.x == 0) next_w = atomicAdd(plan.ticket2, REFILL_CHUNKS);
-    __syncthreads();
-    int w = __builtin_amdgcn_readfirstlane(next_w);
-    if (w >= n_work) break;
-    const int w_end = min(w + REFILL_CHUNKS, n_work);
-    while (w < w_end) {  // (wave-uniform) runs of consecutive chunks of one group: nearly always all of them
-      const int id0 = __builtin_amdgcn_readfirstlane(plan.work[w]);
-      int run = 1;
-      while (w + run < w_end && __builtin_amdgcn_readfirstlane(plan.work[w + run]) == id0 + run) ++run;
-      const int g = id0 / CERT_GROUP, c0 = id0 % CERT_GROUP;
-      GroupDesc gd = a.groups[g];
-      gd.first_block = __builtin_amdgcn_readfirstlane(gd.first_block);
-      gd.n_blocks = __builtin_amdgcn_readfirstlane(gd.n_blocks);
-      gd.prob = __builtin_amdgcn_readfirstlane(gd.prob);
-      const int fb = gd.first_block - a.group_block_base;
-      {  // where the group's lists begin (sweep_queue_kernel's scan)
-        const int k = (int)threadIdx.x, ln = k & 63, wv = k >> 6;
-        int sum = k < gd.n_blocks ? (int)a.need_cnt[fb + k] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const int u = __shfl_up(sum, o, 64);
-          if (ln >= o) sum += u;
-        }
-        if (CERT_GROUP > 64) {
-          if (ln == 63) pre_wave[wv] = sum;
-          __syncthreads();
-#pragma unroll
-          for (int ww = 0; ww < BLOCK / 64; ++ww) sum += ww < wv ? pre_wave[ww] : 0;
-        }
-        if (k < CERT_GROUP) pre_lds[k + 1] = sum;
-        if (k == 0) {
-          pre_lds[0] = 0;
-          pool_next = c0 * BLOCK;
-        }
-      }
-      __syncthreads();
-      const int total = pre_lds[CERT_GROUP];
-      const bool is_surf = __builtin_amdgcn_readfirstlane(a.blocks[fb].is_surf) != 0;
-      const GNState *st = a.states + gd.prob;
-      float R[9], t[3];
-      {
-        static_assert(offsetof(GNState, R) == 24 && offsetof(GNState, t) == 60, "GNState layout");
-        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-        typedef uint32_t u32x8_t __attribute__((ext_vector_type(8)));
-        u32x8_t w8;
-        u32x4_t w4;
-        asm volatile("s_load_dwordx8 %0, %2, 0x18\n\ts_load_dwordx4 %1, %2, 0x38\n\ts_waitcnt lgkmcnt(0)" : "=&s"(w8), "=&s"(w4) : "s"(st) : "memory");
-#pragma unroll
-        for (int i = 0; i < 8; ++i) R[i] = __uint_as_float(w8[i]);
-        R[8] = __uint_as_float(w4[0]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) t[i] = __uint_as_float(w4[1 + i]);
-      }
-      TreeView T;
-      T.nodes = is_surf ? a.ts.nodes : a.tc.nodes;
-      T.pn = is_surf ? a.ts.pn : a.tc.pn;
-      T.pts = is_surf ? a.ts.pts : a.tc.pts;
-      T.n_pts = is_surf ? a.ts.n_pts : a.tc.n_pts;
-      T.n_nodes = is_surf ? a.ts.n_nodes : a.tc.n_nodes;
-      T.root_ref = is_surf ? a.ts.root_ref : a.tc.root_ref;
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        T.bb_lo[i] = is_surf ? a.ts.bb_lo[i] : a.tc.bb_lo[i];
-        T.bb_hi[i] = is_surf ? a.ts.bb_hi[i] : a.tc.bb_hi[i];
-      }
-      KdStack<BLOCK, OVF, LDS_DEPTH> stk;
-      stk.lds = (lds_u32 *)(stack_lds + threadIdx.x);
-      stk.ovf = OVF ? a.stack_ovf + ((size_t)(fb + c0) * BLOCK + threadIdx.x) : nullptr;  // (fb + c0: this workgroup's alone while it runs)
-      stk.ovf_stride = (size_t)a.nb_total * BLOCK;
-      RefillSrc<BLOCK, OVF, LDS_DEPTH> src{a, R, t, T, pre_lds, &pool_next, fb, min((c0 + run) * BLOCK, total), a.prev_valid, 0};
-      knn5_search_refill<BLOCK, OVF, LDS_DEPTH>(T, stk, src);
-      __syncthreads();  // pre_lds, pool_next and the stack columns are free again
-      w += run;
-    }
   }
 }
 
@@ -908,7 +663,7 @@ hipError_t launch_sweep(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEven
     hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, true, false, 4, true>), g, b, 0, s, start, stop, 0, a, jtj_mode);
   } else if (shallow) {
     v = SWEEP_VARIANT_SHALLOW;
-    if (cert) hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, true, false, SHALLOW, false, false, 1>), g, b, 0, s, start, stop, 0, a, jtj_mode);
+    if (cert) hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, true, false, SHALLOW, false, 1>), g, b, 0, s, start, stop, 0, a, jtj_mode);
     else hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, true, false, SHALLOW>), g, b, 0, s, start, stop, 0, a, jtj_mode);
   } else if (cubes && a.stack_ovf && deep_tree) {
     v = SWEEP_VARIANT_CUBES_OVF;
@@ -917,20 +672,12 @@ hipError_t launch_sweep(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEven
     v = SWEEP_VARIANT_CUBES;
     hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, false, true, KD_STACK_LDS>), g, b, 0, s, start, stop, 0, a, jtj_mode);
   } else if (a.stack_ovf && deep_tree) {
-    if (a.tail.count) {
-      v = SWEEP_VARIANT_DEEP_FUSED;
-      hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, true, false, KD_STACK_LDS, false, true>), g, b, 0, s, start, stop, 0, a, jtj_mode);
-    } else {
-      v = SWEEP_VARIANT_DEEP_OVF;
-      if (cert) hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, true, false, KD_STACK_LDS, false, false, 1>), g, b, 0, s, start, stop, 0, a, jtj_mode);
-      else hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, true, false, KD_STACK_LDS>), g, b, 0, s, start, stop, 0, a, jtj_mode);
-    }
-  } else if (a.tail.count) {  // latency-bound launch: the solve rides in its tail
-    v = SWEEP_VARIANT_DEEP_FUSED;
-    hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, false, false, KD_STACK_LDS, false, true>), g, b, 0, s, start, stop, 0, a, jtj_mode);
+    v = SWEEP_VARIANT_DEEP_OVF;
+    if (cert) hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, true, false, KD_STACK_LDS, false, 1>), g, b, 0, s, start, stop, 0, a, jtj_mode);
+    else hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, true, false, KD_STACK_LDS>), g, b, 0, s, start, stop, 0, a, jtj_mode);
   } else {
     v = SWEEP_VARIANT_DEEP;
-    if (cert) hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, false, false, KD_STACK_LDS, false, false, 1>), g, b, 0, s, start, stop, 0, a, jtj_mode);
+    if (cert) hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, false, false, KD_STACK_LDS, false, 1>), g, b, 0, s, start, stop, 0, a, jtj_mode);
     else hipExtLaunchKernelGGL((sweep_kernel<SWEEP_BLOCK, false, false, KD_STACK_LDS>), g, b, 0, s, start, stop, 0, a, jtj_mode);
   }
   if (variant) *variant = v;
@@ -940,49 +687,19 @@ hipError_t launch_sweep(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEven
 }
 
 // the planner of a second pass on its own (a map without trees plans BEFORE the wide probe, whose prefix rides in the same launch)
-hipError_t launch_sweep_plan(const SweepArgs &a, hipStream_t s, const CertPlan &plan, int level, bool with_prefix) {
+hipError_t launch_sweep_plan(const SweepArgs &a, hipStream_t s, const CertPlan &plan, bool with_prefix) {
   if (a.n_groups <= 0) return hipSuccess;
-  hipLaunchKernelGGL(cert_plan_kernel, dim3((a.n_groups + 3) / 4 + (with_prefix ? 1 : 0)), dim3(256), 0, s, a, plan, level, with_prefix ? 1 : 0);
+  hipLaunchKernelGGL(cert_plan_kernel, dim3((a.n_groups + 3) / 4 + (with_prefix ? 1 : 0)), dim3(256), 0, s, a, plan, with_prefix ? 1 : 0);
   return hipGetLastError();
 }
 
-// the grid sweep's second pass in its two-launch form (sweep_refill_kernel, then the residual chain of the same items): the
-// shallow-stack shape on whole-map trees only
-hipError_t launch_sweep_refill(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, const CertPlan &plan) {
+hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, bool planned) {
   if (a.n_groups <= 0) return hipSuccess;
-  constexpr int SHALLOW = LSLAM_SHALLOW_DEPTH;
-  hipLaunchKernelGGL(cert_plan_kernel, dim3((a.n_groups + 3) / 4), dim3(256), 0, s, a, plan, 0, 0);
-  const long possible = a.active_blocks ? std::max<long>(a.n_active, 1) : (long)a.nb_total;
-  const dim3 b(SWEEP_BLOCK);
-  hipLaunchKernelGGL((sweep_refill_kernel<SWEEP_BLOCK, true, SHALLOW>), dim3((unsigned)std::min<long>((possible + REFILL_CHUNKS - 1) / REFILL_CHUNKS, 256 * LSLAM_REFILL_OCC)), b, 0, s, a, plan);
-  hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 2>), dim3((unsigned)std::min<long>(possible, 256 * 5)), b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
-  return hipGetLastError();
-}
-
-hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, int level, bool planned) {
-  if (a.n_groups <= 0) return hipSuccess;
-  if (!planned) hipLaunchKernelGGL(cert_plan_kernel, dim3((a.n_groups + 3) / 4), dim3(256), 0, s, a, plan, level, 0);
+  if (!planned) hipLaunchKernelGGL(cert_plan_kernel, dim3((a.n_groups + 3) / 4), dim3(256), 0, s, a, plan, 0);
   // as many workgroups as stay resident (256 CUs x five of the shallow kernel, two of the deep ones), never more than items possible
   constexpr int SHALLOW = LSLAM_SHALLOW_DEPTH;
   const long possible = a.active_blocks ? std::max<long>(a.n_active, 1) : (long)a.nb_total;  // (a work item is at most one per pass-1 workgroup that ran)
   const dim3 b(SWEEP_BLOCK);
-  if (a.grid == 1 && a.need2_cnt && level == 0) {  // the grid sweep's second probe (no tree search in it: its LDS is the 25-run row table)
-    const dim3 g((unsigned)std::min<long>(possible, 256 * 3));
-    hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, 25, 3>), g, b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
-    return hipGetLastError();
-  }
-  if (a.grid == 1 && a.need2_cnt && level == 1) {  // ... and the tree search of what it listed
-    if (variant == SWEEP_VARIANT_SHALLOW) {
-      hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 1, true>), dim3((unsigned)std::min<long>(possible, 256 * 5)), b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
-    } else if (variant == SWEEP_VARIANT_DEEP_OVF) {
-      hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, KD_STACK_LDS, 1, true>), dim3((unsigned)std::min<long>(possible, 256 * 2)), b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
-    } else if (variant == SWEEP_VARIANT_DEEP) {
-      hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, false, KD_STACK_LDS, 1, true>), dim3((unsigned)std::min<long>(possible, 256 * 2)), b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
-    } else {
-      return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
   if (a.grid == 2) {  // neighbours given (a map without trees): no search, no stack -- the shallow shape's LDS is plenty
     const dim3 g((unsigned)std::min<long>(possible, 256 * 5));
     hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 2>), g, b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
@@ -1024,31 +741,17 @@ hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, h
 #ifdef LSLAM_EXP_SECTION_CLOCK
 __device__ unsigned long long g_section_clock[12 * 64];  // [section][place]: s_memtime ticks; 9 = wavefronts reporting, 10 / 11 = candidates, 64 x rounds
 #endif
-LSLAM_DEV void wide_probe(const CellGrid &G, const float (&sel)[3], float r2, int lane, float nf_slack, float (&d)[5], int (&p)[5], bool &num, bool &bad);
 
-// WIDE (A/B, LSLAM_AB_WIDE_IN_PLACE; a map without kd-trees, a launch too small to fill the chip -- the mapping node's frame):
-// a point the probe cannot prove is resolved on the spot by its own wavefront (wide_probe: every cell within the fifth
-// distance the probe saw), and the residual chain then runs ONCE for all 64 lanes.  One launch per sweep instead of five, no
-// lists; the workgroup's sums are formed exactly as the lane search's sweep forms them.  Slower all the same (0.84 ms against
-// 0.49 per scan match of a frame): the wavefront's unproven points are probed one after the other, ~15 us each.
-// (Tried for single-scan launches and dropped: the candidate loop row after row with four points in flight instead of the
-// lock-step one-candidate-per-round loop -- same bits, no faster, 27 - 32 us against 23 - 31: a launch of one wavefront per
-// SIMD is a chain of latencies of which the loop is only one.)
-// FITC: the instantiation with the fit cache (LSLAM_AB_FIT_CACHE) -- a template argument, not a run-time branch: with the cache's
-// code in it the kernel everybody runs was 3.5 % slower (16 bytes of scratch, twelve more scalar registers, a longer program)
 // LEAN: the instantiation of the production sweep (grid_sweep_lean_ok: MFMA sums, no taps, no _fineScore gate, the bounded
-// search, no counters, no fit cache, not WIDE) -- the same statements with what such a launch never does folded away at compile
-// time, so that the register allocator does not budget for it: the general kernel carries the shuffle path's 31 accumulators
+// search, no counters) -- the same statements with what such a launch never does folded away at compile time, so that the register allocator does not budget for it: the general kernel carries the shuffle path's 31 accumulators
 // (all of its scratch) and the taps' live values through the whole program.  With the registers that frees the five
 // neighbours' points go from the search (which has fetched them for their exact distances) straight to the fit, not gathered a
 // second time (knn5_grid<.., true>, point_residual<true>).  Same operations on the same values: same bits; +3.0 % on the
 // headline (LSLAM_AB_GRID_GENERAL brings the general kernel back; DESIGN 4 has the numbers).
 // FINE: a.kc / a.ks are the x-subdivided tables (CellGrid::xsub > 1, their own cell-sorted points): knn5_grid<.., FINE> clips the
 // bounded probe's rows to sub-cells.  The plain first pass only -- positions in these tables never leave the launch.
-template <int BLOCK, bool WIDE = false, bool FITC = false, bool LEAN = false, bool FINE = false>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : (LEAN ? LSLAM_GRID_LEAN_OCC : LSLAM_GRID_OCC)))) void sweep_grid_kernel(SweepArgs a, int jtj_mode) {
-  static_assert(!LEAN || (!WIDE && !FITC), "the lean grid sweep has neither the wide probe nor the fit cache");
-  static_assert(!FINE || (!WIDE && !FITC), "the fine tables serve the plain first pass only");
+template <int BLOCK, bool LEAN = false, bool FINE = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LEAN ? LSLAM_GRID_LEAN_OCC : LSLAM_GRID_OCC))) void sweep_grid_kernel(SweepArgs a, int jtj_mode) {
   if constexpr (LEAN) {  // what launch_sweep_grid has checked, as constants
     jtj_mode = 1;
     a.flags_out = nullptr;
@@ -1057,7 +760,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 
     a.fine_gate_c = -1.0f;
     a.bounded = 1;
     a.cert_stats = nullptr;
-    a.fit_ids = nullptr;
   }
   constexpr int NWAVE = BLOCK / 64;
   const int lb = a.active_blocks ? a.active_blocks[xcd_remap(blockIdx.x, a.n_active)] : xcd_remap(blockIdx.x, a.nb_total);
@@ -1158,40 +860,13 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 
   float five[15];  // LEAN: the five neighbours' points as the search fetched them, handed on to the residual chain
   bool five_valid = false;
   int verdict;
-  if constexpr (LEAN) verdict = knn5_grid<BLOCK, 1, true, FINE>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG, &five, &five_valid);
-  else verdict = knn5_grid<BLOCK, 1, false, FINE>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG);
+  if constexpr (LEAN) verdict = knn5_grid<BLOCK, true, FINE>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG, &five, &five_valid);
+  else verdict = knn5_grid<BLOCK, false, FINE>(G, active, sel[0], sel[1], sel[2], bound, a.grid_clip_margin, (lds_u32 *)(rows_lds + tid), d, p, lb6 LSLAM_SEC_ARG);
   LSLAM_TICK_P(scp, 3);  // the six survivors fetched again, exact distances, order, proof
   // beyond the gate nothing is looked up (ScanMatch.cpp:102,120); the taps and the _fineScore re-sweep want nanoflann's answer
   if (verdict == GRID_FAR && !a.bounded) verdict = GRID_UNPROVEN;
-  bool needy = active && verdict == GRID_UNPROVEN;
-  bool resolved_wide = false;
-  if (WIDE) {
-    unsigned long long todo = __ballot(needy);
-    if (a.cert_stats && lane == 0) atomicAdd(a.cert_stats, (unsigned long long)__popcll(todo));
-    if (a.cert_stats && tid == 0) atomicAdd(a.cert_stats + 1, (unsigned long long)bd.count);
-    const float my_hint = d[4] < 1.0e30f ? d[4] * (1.0f + 1e-5f) + 1e-12f : FLT_MAX;  // five map points the probe SAW lie within this
-    bool any_bad = false;
-    while (todo) {  // wave-uniform
-      const int L = __builtin_ctzll(todo);
-      todo &= todo - 1;
-      const float s3[3] = {__shfl(sel[0], L, 64), __shfl(sel[1], L, 64), __shfl(sel[2], L, 64)};
-      const float r2 = fminf(5.0f * (1.0f + 1e-5f), __shfl(my_hint, L, 64));
-      float wd[5];
-      int wp[5];
-      bool num, bad;
-      wide_probe(G, s3, r2, lane, a.wide_nf_slack, wd, wp, num, bad);
-      any_bad = any_bad || bad;
-      if (lane == L) {
-#pragma unroll
-        for (int j = 0; j < 5; ++j) { d[j] = wd[j]; p[j] = wp[j]; }
-      }
-    }
-    // an exact tie (only nanoflann's traversal can order it): the host builds the trees and repeats the call
-    if (any_bad && lane == 0) atomicOr(&const_cast<GNState *>(st)->pad, 1);
-    resolved_wide = needy;
-    needy = false;
-  }
-  if (!WIDE) {  // the list of pass 2 (as the certificate sweep's pass 1 writes it)
+  const bool needy = active && verdict == GRID_UNPROVEN;
+  {  // the list of pass 2 (as the certificate sweep's pass 1 writes it)
     const unsigned long long m = __ballot(needy);
     if (lane == 0) wave_needy[wave] = __popcll(m);
     __syncthreads();
@@ -1218,117 +893,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 
   float rb = 0.0f, kept = 0.0f, matched = 0.0f, score = 0.0f;
   if (has) {
     // what the next sweep's bound is taken from: where the point is now and how far its fifth neighbour
-    const bool fifth_known = resolved_wide ? (p[4] >= 0 && d[4] < 5.0f) : (verdict == GRID_PROVEN && d[4] < 5.0f);
+    bool fifth_known = false;
+    if (verdict == GRID_PROVEN) fifth_known = d[4] < 5.0f;
     if (a.bounded) a.prev_q[qi] = make_float4(sel[0], sel[1], sel[2], fifth_known ? d[4] : FLT_MAX);
   }
-  // ---- the plane fit of a surf block, with the fit cache (lslam_opts.ab_switches & LSLAM_AB_FIT_CACHE) ---------------------
-  // findPlane is a pure function of the five neighbours IN ORDER (feature_utils.h:157-204), and late in a Gauss-Newton loop
-  // most points keep theirs from one sweep to the next (84 % from the third to the fourth sweep of the bench's loops, 97 % to
-  // the fifth; 1 % and 23 % before: tools/nb_change_stats.py).  From the sweep with index fit_from_sweep - 1 on, a proven point
-  // stores its five neighbours (positions in the cell-sorted map) and its plane; from fit_from_sweep on it compares, and the
-  // workgroup runs the fit only for the points whose five changed -- COMPACTED through LDS into as few wavefronts as they
-  // fill, because a lone changed lane would otherwise cost its wavefront the whole fit (917 instructions).  Same bits: a
-  // cached plane is the plane the same five points gave.
-  bool fit_done = false;
-  if (FITC && !WIDE && a.fit_ids != nullptr && is_surf && a.bounded && a.fine_gate_c < 0.0f && a.flags_out == nullptr) {  // block-uniform
-    const int sweep_ix = st->sweeps;
-    const bool fc_store = sweep_ix >= a.fit_from_sweep - 1, fc_use = sweep_ix >= a.fit_from_sweep && a.prev_valid;
-    if (fc_store) {
-      fit_done = true;
-      const size_t nf = (size_t)a.n_fit;
-      const bool gate = has && d[4] < 5.0f;  // ScanMatch.cpp:120
-      bool same = false;
-      if (fc_use && gate) {
-        same = true;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) same = same && a.fit_ids[j * nf + qi] == p[j];
-      }
-      const bool need_fit = gate && !same;
-      float plane[4] = {0.f, 0.f, 0.f, 0.f};
-      bool plane_ok = false;
-      // slots of the points that need a fit, in lane order
-      const unsigned long long mf = __ballot(need_fit);
-      __syncthreads();  // (the list's counters above have been read by everybody: wave_needy is free again)
-      if (lane == 0) wave_needy[wave] = __popcll(mf);
-      __syncthreads();
-      int foff = 0, ftotal = 0;
-#pragma unroll
-      for (int w = 0; w < NWAVE; ++w) {
-        const int c = wave_needy[w];
-        foff += w < wave ? c : 0;
-        ftotal += c;
-      }
-      if (fc_use && ftotal <= BLOCK / 2) {  // block-uniform: few enough to pay for the detour
-        int32_t *slot_p = reinterpret_cast<int32_t *>(rows_lds);               // [BLOCK][6]: five positions, the owner's thread
-        float *slot_f = reinterpret_cast<float *>(rows_lds) + 6 * BLOCK;       // [BLOCK][5]: the plane, found
-        const int myslot = foff + __popcll(mf & ((1ull << lane) - 1ull));
-        if (need_fit) {
-#pragma unroll
-          for (int j = 0; j < 5; ++j) slot_p[myslot * 6 + j] = p[j];
-          slot_p[myslot * 6 + 5] = tid;
-        }
-        __syncthreads();
-        if (tid < ftotal) {  // the first ceil(ftotal / 64) wavefronts
-          float4 nb5[5];
-#pragma unroll
-          for (int j = 0; j < 5; ++j) nb5[j] = G.pts[slot_p[tid * 6 + j]];
-          float pl[4];
-          const bool ok = find_plane(nb5, 0.2f, pl);
-          const int owner_q = bd.first + slot_p[tid * 6 + 5];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            slot_f[tid * 5 + j] = pl[j];
-            a.fit_val[j * nf + owner_q] = pl[j];
-          }
-          slot_f[tid * 5 + 4] = ok ? 1.0f : 0.0f;
-          a.fit_val[4 * nf + owner_q] = ok ? 1.0f : 0.0f;
-        }
-        if (same) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) plane[j] = a.fit_val[j * nf + qi];
-          plane_ok = a.fit_val[4 * nf + qi] != 0.0f;
-        }
-        __syncthreads();
-        if (need_fit) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) plane[j] = slot_f[myslot * 5 + j];
-          plane_ok = slot_f[myslot * 5 + 4] != 0.0f;
-        }
-      } else if (gate) {  // everybody fits for itself (the sweep that fills the cache; a sweep after a large step)
-        float4 nb5[5];
-#pragma unroll
-        for (int j = 0; j < 5; ++j) nb5[j] = G.pts[p[j]];
-        plane_ok = find_plane(nb5, 0.2f, plane);
-        if (!same) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) a.fit_val[j * nf + qi] = plane[j];
-          a.fit_val[4 * nf + qi] = plane_ok ? 1.0f : 0.0f;
-        }
-      }
-      if (active && !same) {  // what the next sweep compares with: the five of a proven point inside the gate, else "none"
-#pragma unroll
-        for (int j = 0; j < 5; ++j) a.fit_ids[j * nf + qi] = gate ? p[j] : -1;
-      }
-      if (gate && plane_ok) {  // ScanMatch.cpp:122-139
-        matched = 1.0f;
-        float coeff[4];
-        if (surf_coeff(plane, sel, coeff)) {
-          jacobian_row(sc, q.x, q.y, q.z, coeff, row, rb);
-          kept = 1.0f;
-          score = expf(-fabsf(coeff[3]));
-        }
-      }
-    }
-  }
   LSLAM_TICK_P(scp, 4);  // the list of pass 2 (one workgroup barrier), the carried state written
-  if (has && !fit_done) {
+  if (has) {
     if constexpr (LEAN) point_residual<true>(a, bd, is_surf, G.pts, q, sel, d, p, sc, row, rb, kept, matched, score, &five, five_valid);
     else point_residual(a, bd, is_surf, G.pts, q, sel, d, p, sc, row, rb, kept, matched, score);
   }
   LSLAM_TICK_P(scp, 5);  // the residual chain: five neighbours fetched, findLine / findPlane, coefficient, Jacobian row, score
   __syncthreads();  // every wavefront is done with its row table: the staging rows may be written
   LSLAM_TICK_P(scp, 7);  // waiting for the workgroup's slowest wavefront
-  block_accumulate<BLOCK, false, false, LSLAM_STAGE_PAD>(jtj_mode, is_surf, row, rb, kept, matched, score, rows_lds, red, a.partials + (size_t)lb * NCOL);
+  block_accumulate<BLOCK, false, LSLAM_STAGE_PAD>(jtj_mode, is_surf, row, rb, kept, matched, score, rows_lds, red, a.partials + (size_t)lb * NCOL);
 #ifdef LSLAM_EXP_SECTION_CLOCK
   LSLAM_TICK_P(scp, 8);  // staging, the MFMA contraction, the workgroup's record
   if ((lb & 15) == 0 && lane == 0) {  // one workgroup in sixteen reports (atomics on 64 places per section)
@@ -1409,30 +986,18 @@ hipError_t launch_compact_active(const GNState *states, const ProbBlocks *probs,
   return hipGetLastError();
 }
 
-hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool resolve_in_place, bool lean,
-                             bool fine) {
+hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool lean, bool fine) {
   if (a.nb_total <= 0) return hipSuccess;
-  if (lean && (resolve_in_place || !grid_sweep_lean_ok(a, jtj_mode))) return hipErrorInvalidValue;  // (the lean kernel would compute something else)
-  if (fine) {  // a.kc / a.ks are x-subdivided tables: the plain first pass, lean or general -- the same table for both
-    if (resolve_in_place || a.fit_ids || a.kc.xsub < 1 || a.ks.xsub < 1) return hipErrorInvalidValue;
-    const dim3 grd(a.active_blocks ? a.n_active : a.nb_total);
-    if (a.active_blocks && a.n_active <= 0) return hipSuccess;
-    if (lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, false, true, true>), grd, dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
-    else hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, false, false, true>), grd, dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
-    return hipGetLastError();
-  }
-  if (a.kc.xsub > 1 || a.ks.xsub > 1) return hipErrorInvalidValue;  // (these kernels read x in whole cells)
-  if (a.active_blocks && !resolve_in_place) {  // the batch's grid sweep over the running scans' workgroups only
-    if (a.n_active <= 0) return hipSuccess;
-    if (lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, false, true>), dim3(a.n_active), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
-    else if (a.fit_ids) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, true>), dim3(a.n_active), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
-    else hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK>), dim3(a.n_active), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
-    return hipGetLastError();
-  }
-  if (resolve_in_place) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, true>), dim3(a.nb_total), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
-  else if (lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, false, true>), dim3(a.nb_total), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
-  else if (a.fit_ids) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, true>), dim3(a.nb_total), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
-  else hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK>), dim3(a.nb_total), dim3(SWEEP_BLOCK), 0, s, start, stop, 0, a, jtj_mode);
+  if (lean && !grid_sweep_lean_ok(a, jtj_mode)) return hipErrorInvalidValue;  // (the lean kernel would compute something else)
+  // fine: a.kc / a.ks are x-subdivided tables, the same table for the lean and the general kernel; otherwise x is read in whole cells
+  if (fine ? (a.kc.xsub < 1 || a.ks.xsub < 1) : (a.kc.xsub > 1 || a.ks.xsub > 1)) return hipErrorInvalidValue;
+  if (a.active_blocks && a.n_active <= 0) return hipSuccess;
+  // (active_blocks: the batch's grid sweep over the running scans' workgroups only)
+  const dim3 grd(a.active_blocks ? a.n_active : a.nb_total), blk(SWEEP_BLOCK);
+  if (fine && lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, true, true>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);
+  else if (fine) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, true>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);
+  else if (lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, true>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);
+  else hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);
   return hipGetLastError();
 }
 
@@ -1680,178 +1245,6 @@ hipError_t launch_sweep_wide(const SweepArgs &a, hipStream_t s) {  // (after lau
   if (a.nb_total <= 0) return hipSuccess;
   // one wavefront per point that CAN be listed (every point of the launch): the ones beyond the listed total leave at once
   hipLaunchKernelGGL(sweep_wide_kernel, dim3((unsigned)a.nb_total * (SWEEP_BLOCK / 4)), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// The whole Gauss-Newton loop of ONE scan in one persistent launch.  As launches an iteration is a sweep
-// (44-55 us for 115 200 points), a solve launch (13 us: 1024 threads ramp up to reduce 450 x 32 partials
-// and run a 6 x 6 QR), two launch-to-launch gaps and, after the last iteration, a spare pair that finds
-// the loop ended: ~79 us per iteration, 0.32 ms of device time per scanMatchScan of four.  Here every workgroup of the
-// sweep stays resident (450 of them at two per CU), keeps ITS OWN copy of the scan's state in LDS and,
-// after its block of the sweep, takes part in one grid-wide exchange of the blocks' 32 sums -- slots that
-// hold a sentinel until their owner stores them, polled by the readers themselves (the mechanism of
-// pg_pcg_persistent_kernel, lslam_posegraph.hip; three generations, a slot is reset one exchange after
-// everybody has read it) -- reduces them in the solve kernel's order and runs the solve REPLICATED: every
-// workgroup computes the same next pose from the same numbers, nothing travels back.  Bit for bit the
-// launch loop's result (same sums in the same order, same solve; tests/test_gpu_parity.py holds the two
-// against each other).  For a single resident scan against shallow trees without the stereo term,
-// the sharded exchange or per-launch profiling; a spin limit raises an abort flag instead of hanging
-// and the caller falls back to the launch loop.  MEASURED NO FASTER than the launch loop (327 us against
-// 315 us per four-iteration loop: the exchanges and the replicated solve cost what the solve launch and
-// its gaps do) and therefore off unless LSLAM_PERSISTENT_GN=1; kept as the A/B switch of that result.
-// ---------------------------------------------------------------------------
-constexpr uint32_t GNP_SENT = 0xFFF8DEADu;  // a NaN payload no sum produces
-constexpr long long GNP_SENT64 = (long long)(((unsigned long long)GNP_SENT << 32) | GNP_SENT);
-constexpr unsigned GNP_SPIN_LIMIT = 1u << 20;
-LSLAM_DEV float gnp_ld(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-LSLAM_DEV void gnp_st(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__global__ __launch_bounds__(SWEEP_BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void gn_persistent_kernel(SweepArgs a, int jtj_mode, GnLoopArgs g) {
-  constexpr int BLOCK = SWEEP_BLOCK, LDS_DEPTH = KD_STACK_LDS;
-  __shared__ float red[BLOCK / 64][NCOL];
-  __shared__ uint32_t stack_lds[2 * LDS_DEPTH * BLOCK];
-  __shared__ GNState lst;       // this workgroup's copy of the scan's state
-  __shared__ float part[NCOL];
-  __shared__ double tot[NCOL];
-  __shared__ GnShared sh;
-  __shared__ int go;
-  __shared__ double redd[32][NCOL];
-  const int tid = threadIdx.x;
-  const int lb = xcd_remap(blockIdx.x, a.nb_total);
-  const BlockDesc bd = a.blocks[lb];
-  const int nb = a.nb_total;
-  {
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(a.states);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(&lst);
-    for (int i = tid; i < (int)(sizeof(GNState) / 4); i += BLOCK) dst[i] = src[i];
-  }
-  __syncthreads();
-  for (int it = 0; it < g.max_iterations && !lst.done; ++it) {
-    sweep_body<BLOCK, false, false, LDS_DEPTH, false, true>(a, jtj_mode, lb, bd, &lst, stack_lds, red, part, (a.bounded && it > 0) ? 1 : 0);
-    __syncthreads();
-    // Exchange in two stages, the solve kernel's summation order kept: the blocks' 32 sums go to slots (two generations);
-    // workgroup `grp` < 32 adds rows grp, grp + 32, ... of them in fp64 and publishes the group's sums (three generations);
-    // every workgroup adds the 32 groups in order.  (One stage -- every workgroup reading all 450 x 32 sums through the
-    // coherence point, 26 MB per iteration -- cost more than the launches it replaced.)
-    float *slot = g.slots + (size_t)(it & 1) * nb * NCOL;
-    double *gsl = g.gslots + (size_t)(it % 3) * 32 * NCOL;
-    if (tid < NCOL) gnp_st(slot + (size_t)lb * NCOL + tid, part[tid]);
-    if (lb < 32) {
-      float *pv = reinterpret_cast<float *>(stack_lds);  // [<= 16][NCOL] this group's rows (the traversal stack is dead by now)
-      const int nrow = lb < nb ? (nb - lb + 31) / 32 : 0;
-      for (unsigned spins = 0;; ++spins) {
-        int bad = 0;
-        for (int i = tid; i < nrow * NCOL; i += BLOCK) {
-          const float v = gnp_ld(slot + (size_t)(lb + 32 * (i / NCOL)) * NCOL + (i % NCOL));
-          pv[i] = v;
-          bad |= (__float_as_uint(v) == GNP_SENT) ? 1 : 0;
-        }
-        if (!__syncthreads_or(bad)) break;
-        if ((spins & 255u) == 255u &&
-            (spins > GNP_SPIN_LIMIT || __hip_atomic_load(g.bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-          __hip_atomic_store(g.bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          return;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      if (tid < NCOL) {
-        double sgrp = 0.0;
-        for (int r = 0; r < nrow; ++r) sgrp += (double)pv[r * NCOL + tid];
-        __hip_atomic_store(gsl + lb * NCOL + tid, sgrp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    for (unsigned spins = 0;; ++spins) {
-      int bad = 0;
-#pragma unroll 4
-      for (int i = tid; i < 32 * NCOL; i += BLOCK) {
-        const double v = __hip_atomic_load(gsl + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        (&redd[0][0])[i] = v;
-        bad |= (__double_as_longlong(v) == GNP_SENT64) ? 1 : 0;
-      }
-      if (!__syncthreads_or(bad)) break;
-      if ((spins & 255u) == 255u &&
-          (spins > GNP_SPIN_LIMIT || __hip_atomic_load(g.bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-        __hip_atomic_store(g.bar + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    // all 32 group sums are there: every reducer has read every block's sums of this iteration, and every workgroup
-    // has finished reading the group sums of the iteration before the last
-    if (tid < NCOL) gnp_st(slot + (size_t)lb * NCOL + tid, __uint_as_float(GNP_SENT));
-    if (it > 0 && lb < 32 && tid < NCOL)
-      __hip_atomic_store(g.gslots + (size_t)((it - 1) % 3) * 32 * NCOL + lb * NCOL + tid, __longlong_as_double(GNP_SENT64),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < NCOL) {
-      double v = 0.0;
-#pragma unroll 8
-      for (int gi = 0; gi < 32; ++gi) v += redd[gi][tid];
-      tot[tid] = v;
-      lst.sums[tid] = v;
-    }
-    __syncthreads();
-    if (tid == 0) {  // solve_kernel's bookkeeping (ScanMatch.cpp:141-145)
-      lst.sweeps += 1;
-      const int n_rows = (int)tot[COL_ROWS];
-      lst.n_rows = n_rows;
-      lst.n_line = (int)tot[COL_LINE];
-      lst.n_plane = (int)tot[COL_PLANE];
-      lst.score = tot[COL_SCORE];
-      go = 1;
-      if (n_rows < g.min_rows) {
-        go = 0;
-        lst.too_few = 1;
-        lst.done = 1;
-      }
-    }
-    if (tid < 36) {
-      const int r = tid / 6, c = tid % 6;
-      const int i = r < c ? r : c, j = r < c ? c : r;
-      sh.A[tid] = (float)tot[COL_ATA + (i * 6 - (i * (i - 1)) / 2) + (j - i)];
-    }
-    if (tid < 6) sh.b[tid] = (float)tot[COL_ATB + tid];
-    __syncthreads();
-    if (go) {
-      gn_step_block(&lst, sh, g.eig_thresh, g.delta_r_abort, g.delta_t_abort, false);
-      if (tid == 0) {
-        lst.loop_iter += 1;
-        if (lst.loop_iter >= g.max_iterations) lst.done = 1;
-      }
-    }
-    __syncthreads();
-  }
-  if (blockIdx.x == 0) {
-    uint32_t *dst = reinterpret_cast<uint32_t *>(g.state_out);
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(&lst);
-    for (int i = tid; i < (int)(sizeof(GNState) / 4); i += BLOCK) dst[i] = src[i];
-  }
-}
-
-int gn_persistent_capacity(int device) {  // workgroups of gn_persistent_kernel the device holds at once
-  hipDeviceProp_t prop;
-  int per_cu = 0;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gn_persistent_kernel, SWEEP_BLOCK, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  return per_cu * prop.multiProcessorCount;
-}
-
-hipError_t launch_gn_persistent(const SweepArgs &a, int jtj_mode, const GnLoopArgs &g, hipStream_t s) {
-  // An ordinary launch: the caller has checked that the grid fits the device at once, and the kernel's spin limit turns
-  // the case it does not (another process on the device) into a fallback instead of a hang.  hipLaunchCooperativeKernel
-  // adds tens of microseconds per launch on this runtime -- more than the launches this kernel saves.
-  const bool coop = env_once().gnp_coop;  // A/B switch
-  if (coop) {
-    SweepArgs aa = a;
-    int jm = jtj_mode;
-    GnLoopArgs gg = g;
-    void *args[] = {(void *)&aa, (void *)&jm, (void *)&gg};
-    return hipLaunchCooperativeKernel((const void *)gn_persistent_kernel, dim3((unsigned)a.nb_total), dim3(SWEEP_BLOCK), args, 0, s);
-  }
-  hipLaunchKernelGGL(gn_persistent_kernel, dim3((unsigned)a.nb_total), dim3(SWEEP_BLOCK), 0, s, a, jtj_mode, g);
   return hipGetLastError();
 }
 

@@ -12,7 +12,7 @@
 // rejected there, every other point is listed for loc_tree_kernel, which walks the tree of ITS CUBE.  Both leave the five
 // neighbours per point (distances, positions in the cell-sorted array or in the trees' array); loc_fit_kernel then runs the
 // residual chain and the block sums over all points in their fixed places, so the sums -- and the poses -- do not depend on
-// which search decided a point.  The carried-neighbour certificates, the second probe and the fit cache are not used here.
+// which search decided a point.  The carried-neighbour certificates are not used here.
 #include "../../include/lslam_c.h"
 
 #include <hip/hip_runtime.h>
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(LOC_BLOCK) void loc_fit_kernel(const LocArgs a, con
     const float4 *P = how == HOW_GRID ? (is_surf ? a.G[1].pts : a.G[0].pts) : a.tpts;
     point_residual(sa, bd, is_surf, P, q, sel, d, p, sc, row, rb, kept, matched, score);
   }
-  block_accumulate<LOC_BLOCK, false, false>(jtj_mode, is_surf, row, rb, kept, matched, score, stage, red, a.partials + (size_t)blockIdx.x * NCOL);
+  block_accumulate<LOC_BLOCK, false>(jtj_mode, is_surf, row, rb, kept, matched, score, stage, red, a.partials + (size_t)blockIdx.x * NCOL);
 }
 
 // the tap's outputs: coordinates of the five, their distances, how

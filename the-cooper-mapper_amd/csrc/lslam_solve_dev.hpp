@@ -1,7 +1,7 @@
 // lslam_solve_dev.hpp -- the solve half of a Gauss-Newton iteration as device functions (ScanMatch.cpp:141-145, 206-260;
 // LaserOdometry.cpp:501-503, 580-646): the deterministic cross-block reduction, the 6x6 solve, the degeneracy projection, the
-// pose update and the convergence test.  Shared by the solve kernel and the persistent loops of lslam_kernels.hip and by the
-// odometry node's persistent loop (lslam_odom.hip): one copy of the arithmetic.
+// pose update and the convergence test.  Shared by the solve kernel of lslam_kernels.hip and by the odometry node's
+// persistent loop (lslam_odom.hip): one copy of the arithmetic.
 #pragma once
 
 #include "lslam_internal.hpp"
@@ -368,13 +368,11 @@ constexpr int SOLVE_GROUPS = 32;  // 32 row groups x 32 columns: the summation o
 // Deterministic cross-block reduction in fp64 of one scan's block records: the thread that owns (group grp, column col)
 // adds rows grp, grp + 32, ... in order (32 independent loads in flight per pass, so up to 1024 sweep blocks cost a single
 // memory round trip); red[grp][col] receives the group's sum.  Called by THREADS = 32 * G threads, each owning 32 / G groups:
-// the order inside a group -- the only order that matters -- does not depend on G (the solve kernel: 1024 threads, the fused
-// tail of a sweep block: 256).  COHERENT: the records were written by other workgroups of the same launch (relaxed
-// agent-scope atomic loads, served by the coherence point).
-template <int THREADS, bool COHERENT>
+// the order inside a group -- the only order that matters -- does not depend on G (the solve kernel: 1024 threads).
+template <int THREADS>
 LSLAM_DEV void reduce_partials(const float *partials, int nb, double (*red)[NCOL]) {
   constexpr int G = THREADS / NCOL;       // groups worked on at a time
-  constexpr int NG = SOLVE_GROUPS / G;    // groups per thread (1 for the solve kernel, 4 for a sweep block)
+  constexpr int NG = SOLVE_GROUPS / G;    // groups per thread (1 for the solve kernel)
   constexpr int CH = NG == 1 ? 32 : 16;   // rows of a group fetched together: NG * CH loads in flight per thread
   const int tid = threadIdx.x, col = tid & 31, g0 = tid >> 5;
   double s[NG];
@@ -387,8 +385,7 @@ LSLAM_DEV void reduce_partials(const float *partials, int nb, double (*red)[NCOL
 #pragma unroll
       for (int u = 0; u < CH; ++u) {
         const int b = b0 + (g0 + G * gg) + u * SOLVE_GROUPS;
-        if (COHERENT) v[gg][u] = b < nb ? __hip_atomic_load(partials + (size_t)b * NCOL + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-        else v[gg][u] = b < nb ? partials[(size_t)b * NCOL + col] : 0.0f;
+        v[gg][u] = b < nb ? partials[(size_t)b * NCOL + col] : 0.0f;
       }
 #pragma unroll
     for (int gg = 0; gg < NG; ++gg)

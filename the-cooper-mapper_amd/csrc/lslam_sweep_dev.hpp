@@ -129,7 +129,7 @@ LSLAM_DEV void point_residual(const SweepArgs &a, const BlockDesc &bd, const boo
 // with PAD = 4 the 32 words of a step lie in 32 banks.  Same words to the same lanes: same bits.  Only for a caller whose `stage`
 // is free of other wavefronts' data (a padded row reaches into the neighbouring wavefronts' columns): the grid sweep, behind
 // its workgroup barrier; the tree sweeps stage in the columns of their own traversal stacks, without one.
-template <int BLOCK, bool FUSE, bool ADD, int PAD = 0>
+template <int BLOCK, bool ADD, int PAD = 0>
 LSLAM_DEV void block_accumulate(const int jtj_mode, const bool is_surf, const float (&row)[6], const float rb, const float kept,
                                 const float matched, const float score, uint32_t *stage, float (*red)[NCOL], float *partial_out) {
   constexpr int NWAVE = BLOCK / 64;
@@ -209,10 +209,7 @@ LSLAM_DEV void block_accumulate(const int jtj_mode, const bool is_surf, const fl
     float s = red[0][tid];
 #pragma unroll
     for (int w = 1; w < NWAVE; ++w) s += red[w][tid];
-    // fused solve: the record is read by another workgroup of THIS launch (possibly on another XCD) -- written through to
-    // the device's coherence point; otherwise by the next launch
-    if (FUSE) __hip_atomic_store(partial_out + tid, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else if (ADD) partial_out[tid] += s;  // onto the record pass 1 left (this thread alone touches the word)
+    if (ADD) partial_out[tid] += s;  // onto the record pass 1 left (this thread alone touches the word)
     else partial_out[tid] = s;
   }
 }

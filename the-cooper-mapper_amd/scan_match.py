@@ -177,7 +177,7 @@ class Context:
         return np.array(dims[:]), np.array(geom[:], np.float32), cs, pts
 
     def grid_wide_launches(self):
-        """lslam_debug_grid_wide_launches: ... of which in the single-launch form of a map without trees."""
+        """lslam_debug_grid_wide_launches: always 0 (the single-launch form of a map without trees is retired)."""
         return int(self.lib.lslam_debug_grid_wide_launches(self.h))
 
     def scratch(self, name, rows, cols, dtype=np.float32):

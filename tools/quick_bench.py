@@ -27,8 +27,7 @@ print("last solve kernel (us): reduce %.2f  qr %.2f  rest %.2f  total %.2f" % ((
 print("%-40s sweep_us median %.1f min %.1f | loop_us median %.1f | iters %d pose %s" % (
     os.path.basename(os.environ.get("LSLAM_LIB", "default")), 1e3 * np.median(sw), 1e3 * min(sw), 1e3 * np.median(lp),
     st.iterations, np.array2string(pose, precision=5)))
-# the same loop without per-launch events (a single resident scan then runs as ONE persistent launch unless
-# LSLAM_PERSISTENT_GN=0): device time of the whole loop and wall time of the call
+# the same loop without per-launch events: device time of the whole loop and wall time of the call
 import time
 opts.profile = 0
 for _ in range(3):
