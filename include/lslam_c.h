@@ -214,6 +214,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed; new entry points and an enum (lslam_pg_set_robust_kernels, _edge_robust, _robust_info, _kernel_from_name: robust kernels on pose-graph edges; lslam_pg_stream). */
 /* still 7: no struct changed; new entry points and a struct of their own (lslam_match_information, lslam_keyframe_edge_information, lslam_sizeof_edge_info: the match Hessian of a pose-graph edge). */
 /* still 7: no struct changed, no entry point gone; six LSLAM_AB_* names retired (bits 1, 2, 4, 8, 32, 128: refused from here on, see lslam_opts.ab_switches). */
+/* still 7: no struct changed; new entry points and an enum (lslam_pg_set_priors, _num_priors, _prior_robust, lslam_g2o_read_priors: unary constraints on pose-graph vertices). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -1178,7 +1179,9 @@ int lslam_pg_create(int device, int32_t n_vertices, const double *poses7, int32_
 void lslam_pg_destroy(lslam_pg *pg);
 const char *lslam_pg_last_error(void);
 /* Edge shard [e_begin, e_end) of this rank; fn == NULL: single GPU.  system_buf: optional
- * caller-owned DEVICE buffer of lslam_pg_system_doubles() doubles to assemble into. */
+ * caller-owned DEVICE buffer of lslam_pg_system_doubles() doubles to assemble into.
+ * Unary constraints (lslam_pg_set_priors, further down) are not sharded: the rank whose range starts at 0 and is not empty
+ * carries all of them, every other rank none, so the sum over the ranks counts each once. */
 int lslam_pg_set_shard(lslam_pg *pg, int32_t e_begin, int32_t e_end, lslam_allreduce_fn fn,
                        void *user, double *system_buf);
 /* The same with the library's own RCCL communicator instead of a callback (NULL detaches). */
@@ -1270,6 +1273,55 @@ int lslam_pg_set_robust_kernels(lslam_pg *pg, const int32_t *kind, const double 
 int lslam_pg_edge_robust(lslam_pg *pg, const double *poses7, double *e2, double *rho, double *weight);
 /* edges carrying a kernel; of those, edges with weight < 1 at the current estimate; the plain sum of e2 */
 int lslam_pg_robust_info(lslam_pg *pg, int32_t *n_robust, int32_t *n_downweighted, double *chi2_plain);
+
+/* ---- unary constraints on keyframes: GPS position and absolute-pose priors --------------------------------------------
+ * The reference shows the intent and stops there: pose_graph/keyframe.h:40-41 gives every keyframe an optional utm_coord ("UTM
+ * coord obtained by GPS") and imu_quat, kf_fusion/fpdReceiver.cpp and utmProjection.cpp produce the fixes,
+ * map_evaluation/Evaluation.cpp scores the lidar pose against them -- and nothing consumes the two keyframe fields.  The module
+ * is modelled on hdl_graph_slam, where they become unary edges (EdgeSE3PriorXYZ, EdgeSE3PriorQuat).  Neither hdl_graph_slam nor
+ * g2o is under the reference, so PARITY IS UNPINNED like the rest of this solver; the semantics are their published ones, in
+ * this solver's conventions (update X <- X * fromVectorMQT(d), error in toVectorMQT coordinates).  A prior sits on one vertex v
+ * with estimate X = (t, q):
+ *   LSLAM_PG_PRIOR_XYZ   a GPS fix: e = t - z in the graph frame (3 rows), J = [R(q) | 0]; the information is the upper-left
+ *                        3x3 of info36, the rest is ignored; of meas7 only x, y, z are read
+ *   LSLAM_PG_PRIOR_POSE  an absolute pose: e = toVectorMQT(Z^-1 X) (6 rows), the binary edge's error with Xi = identity, 6x6
+ *                        information.  Positive SEMI-definite information is legal: a zero translation block makes it an
+ *                        orientation prior (keyframe.h:41's imu_quat), only z / roll / pitch entries a ground-plane prior.
+ * A prior adds J^T Omega J to its vertex's diagonal block, -J^T Omega e to its segment of b and e^T Omega e to chi2: the
+ * sparsity pattern, the PCG, the coarse level and the sharded layouts do not change.  With a robust kernel (kind / delta, the
+ * LSLAM_PG_KERNEL_* semantics above: rho1 scales H and b, rho0 goes to chi2) an outlying fix -- GPS multipath -- can be
+ * rejected.  Several priors on one vertex are legal; they are summed in prior order behind the vertex's edges (one fixed order,
+ * no atomics).  A prior on the fixed vertex adds its rho0 to chi2 and nothing to H or b (g2o's behaviour for an active edge on
+ * a fixed vertex).  Priors can fix the gauge: a graph created with fixed_vertex = -1 holds no vertex, and is well posed once its
+ * priors pin all six degrees of freedom.
+ * lslam_pg_linearize and lslam_pg_optimize include the priors; lslam_pg_robust_info and lslam_pg_edge_robust keep their meaning
+ * (edges only).  While a graph has no priors -- the default -- the solver launches exactly the kernels it launched before these
+ * entry points existed.
+ * SHARDED RUNS (lslam_pg_set_shard): the system is summed over the ranks, so every prior must be counted once.  Every rank sets
+ * the same priors; the rank whose edge range starts at 0 and is not empty linearises all of them, every other rank none.  No
+ * new transport is needed.  (A graph without edges has nothing to shard: its one range [0, 0) carries the priors.) */
+enum { LSLAM_PG_PRIOR_XYZ = 0, LSLAM_PG_PRIOR_POSE = 1 };
+/* Replaces the whole set; n_priors = 0 clears.  vertex[n], type[n], meas7[n][7] = {x, y, z, qx, qy, qz, qw}, info36[n][36]
+ * row-major; kind[n] / delta[n] as lslam_pg_set_robust_kernels, both NULL: no kernels.  Everything is checked before anything
+ * changes -- LSLAM_ERR_INVALID, lslam_pg_last_error names the cause, for: a vertex out of range, an unknown type, a non-finite
+ * measurement, a zero-norm quaternion on a POSE prior, a used information block that is not finite, not symmetric (beyond 1e-12
+ * of its largest entry) or has a negative diagonal entry, kind without delta or the reverse, an unknown kind, a delta that is
+ * not finite and > 0.  A POSE prior's quaternion need not be unit: it is normalised before it reaches the device (the file
+ * lslam_pg_save_g2o writes carries it as given).  A device error (LSLAM_ERR_HIP) while the new set is uploaded leaves the graph
+ * with no priors. */
+int lslam_pg_set_priors(lslam_pg *pg, int32_t n_priors, const int32_t *vertex, const int32_t *type, const double *meas7,
+                        const double *info36, const int32_t *kind, const double *delta);
+int32_t lslam_pg_num_priors(const lslam_pg *pg);
+/* per prior at poses7 (NULL: the current estimate); any output may be NULL: e2[n_priors], rho[n_priors] = rho0, weight[n_priors] = rho1 */
+int lslam_pg_prior_robust(lslam_pg *pg, const double *poses7, double *e2, double *rho, double *weight);
+/* lslam_pg_save_g2o writes the priors behind the edges: one "PARAMS_SE3OFFSET 0 0 0 0 0 0 0 1" line when a POSE prior exists,
+ * "EDGE_SE3_PRIOR v 0 <meas7> <21 upper-triangular>" per POSE prior (g2o's own tag) and "EDGE_SE3_PRIORXYZ v x y z <6
+ * upper-triangular>" per XYZ prior (hdl_graph_slam's tag); robust kernels have no place in the format.  lslam_g2o_read ignores
+ * these lines; this reader returns them, in file order (host only).  *n_priors: in = capacity of the arrays, out = what the file
+ * holds (call with NULL arrays to size them); vertices are numbered as lslam_g2o_read numbers them. */
+int lslam_g2o_read_priors(const char *path, int32_t *n_priors, int32_t *vertex, int32_t *type, double *meas7,
+                          double *info36);
+
 /* Device handle tap, as lslam_stream: the stream every kernel of this graph runs on (hipStream_t), for harnesses that time a
  * linearisation with events (tools/bench_robust_linearize.py). */
 void *lslam_pg_stream(lslam_pg *pg);

@@ -204,6 +204,10 @@ struct KeyFrame {
   int frame_id = 0;
   lslam_kfs *store = nullptr;    // the store that holds the clouds on the device (a resident Graph's), and the id there;
   int store_id = -1;             // cornerCloud / surfCloud are then empty unless the graph keeps host copies
+  // keyframe.h:40-41's optional fields (boost::optional there): a projected GPS fix and an IMU orientation (x, y, z, w); used
+  // only by a Graph with gps_sigma_xy / imu_orientation_sigma set.  gps_local = utm_coord - the graph's utm_origin (fp64).
+  bool has_utm_coord = false, has_imu_quat = false, has_gps_local = false;
+  double utm_coord[3] = {0.0, 0.0, 0.0}, imu_quat[4] = {0.0, 0.0, 0.0, 1.0}, gps_local[3] = {0.0, 0.0, 0.0};
 };
 
 // loop_detector.hpp:18-48
@@ -548,6 +552,23 @@ public:
     keyframe_queue.push_back(kf);
     return kf;
   }
+  // ... with keyframe.h:40-41's optional fields: utm_coord[3] (x, y, z [m], projected -- what kf_fusion/fpdReceiver.cpp makes of
+  // a fix) and imu_quat[4] (x, y, z, w); either may be null.  Stored on the keyframe; used only with gps_sigma_xy /
+  // imu_orientation_sigma.
+  KeyFrame::Ptr add_frame(const Mat4d &odom, const std::vector<float> &corner, const std::vector<float> &surf, const double *utm_coord,
+                          const double *imu_quat) {
+    KeyFrame::Ptr kf = add_frame(odom, corner, surf);
+    if (!kf) return kf;
+    if (utm_coord) {
+      kf->has_utm_coord = true;
+      for (int k = 0; k < 3; ++k) kf->utm_coord[k] = utm_coord[k];
+    }
+    if (imu_quat) {
+      kf->has_imu_quat = true;
+      for (int k = 0; k < 4; ++k) kf->imu_quat[k] = imu_quat[k];
+    }
+    return kf;
+  }
 
   // one pass of the optimisation loop, graph.cpp:313-383: flush the queue (vertices + odometry edges), detect loops
   // among the new keyframes, add loop edges, optimise if a loop was found, update odom -> graph.
@@ -573,6 +594,16 @@ public:
     }
     if (hessian && !store) {
       _err = "Graph: edge_information = hessian needs a resident graph";
+      return -1;
+    }
+    const int gps_kind = lslam_pg_kernel_from_name(gps_robust_kernel.c_str());
+    if (gps_kind < 0 || (gps_kind != LSLAM_PG_KERNEL_NONE && !(std::isfinite(gps_robust_kernel_size) && gps_robust_kernel_size > 0.0))) {
+      _err = "Graph: gps_robust_kernel is NONE, Huber, Cauchy or DCS with a finite gps_robust_kernel_size > 0";
+      return -1;
+    }
+    if (!(gps_sigma_xy >= 0.0 && gps_sigma_z >= 0.0 && std::isfinite(gps_sigma_xy) && std::isfinite(gps_sigma_z)) ||
+        ((gps_sigma_xy > 0.0) != (gps_sigma_z > 0.0)) || !(imu_orientation_sigma >= 0.0) || !(gps_min_spread >= 0.0)) {
+      _err = "Graph: gps_sigma_xy and gps_sigma_z [m] are set together, both > 0; imu_orientation_sigma [rad] and gps_min_spread [m] >= 0";
       return -1;
     }
     _edge_failed = false;
@@ -607,9 +638,10 @@ public:
     }
     loops.insert(loops.end(), found.begin(), found.end());
     keyframes.insert(keyframes.end(), new_keyframes.begin(), new_keyframes.end());
+    const bool added_priors = add_priors(new_keyframes, gps_kind);
     new_keyframes.clear();
     last_iterations = 0;
-    if (!found.empty()) {
+    if (!found.empty() || added_priors) {
       if (!solve_graph(max_iterations, nullptr, nullptr)) return -1;
     }
     const KeyFrame::Ptr &last = keyframes.back();
@@ -749,6 +781,49 @@ public:
   // with (keyframes, new keyframes, loops out).  The counterpart of the Python Graph's loop_detector argument: a node that has
   // its own place recognition, or a test with prepared loops, hands them over here.
   std::function<void(const std::vector<KeyFrame::Ptr> &, const std::deque<KeyFrame::Ptr> &, std::vector<Loop::Ptr> &)> loop_source;
+  // GPS fixes and IMU orientations as unary constraints (not in the reference, whose keyframes only carry the two fields;
+  // lslam_pg_set_priors, semantics in lslam_c.h).  All off by default (0).
+  //   gps_sigma_xy / gps_sigma_z [m]: the fixes handed to add_frame become XYZ priors with information diag(1/sxy^2, 1/sxy^2,
+  //     1/sz^2) and gps_robust_kernel / gps_robust_kernel_size on each (multipath: "Cauchy" rejects an outlying fix).  No
+  //     default: the library does not guess a receiver's noise.  utm_origin is the first keyframe fix, kept in fp64 on the host
+  //     and subtracted before anything reaches the solver (UTM coordinates are ~1e6 m).
+  //   GAUGE: the graph frame starts as the first lidar pose, not ENU; priors under a fixed, misaligned first vertex would bend
+  //     the map.  Until the fixes span a plane -- the second singular value of the centred fix positions >= gps_min_spread
+  //     (0: 10 * gps_sigma_xy) -- priors are queued and the first vertex stays fixed (the reference's behaviour); then the
+  //     keyframe estimates and tf_odom2graph are moved by the rigid fit of estimate positions to fixes (lslam_debug_icp_fit),
+  //     all queued priors are added and the solver runs with no fixed vertex from there on.
+  //   imu_orientation_sigma [rad]: a keyframe's imu_quat (in the frame the fixes are in) becomes a POSE prior with a zero
+  //     translation block and (2 / sigma)^2 on the quaternion vector; queued with the fixes when the GPS switch is on.
+  // optimize() then runs the solver when a pass added loops OR priors.
+  double gps_sigma_xy = 0.0, gps_sigma_z = 0.0;
+  std::string gps_robust_kernel = "NONE";
+  double gps_robust_kernel_size = 1.0;
+  double gps_min_spread = 0.0;
+  double imu_orientation_sigma = 0.0;
+  bool gps_aligned = false;
+  bool has_utm_origin = false;
+  double utm_origin[3] = {0.0, 0.0, 0.0};
+  // the keyframe of every GPS prior in the solver; its robust weight after the last optimisation (all 1 without a kernel);
+  // the keyframes whose fix has a weight below `threshold` (reporting only: nothing is removed)
+  std::vector<KeyFrame::Ptr> gps_fixes;
+  const std::vector<double> &gpsWeights() const { return _gps_weights; }
+  std::vector<KeyFrame::Ptr> rejectedFixes(double threshold = 0.1) const {
+    std::vector<KeyFrame::Ptr> out;
+    for (size_t k = 0; k < gps_fixes.size() && k < _gps_weights.size(); ++k)
+      if (_gps_weights[k] < threshold) out.push_back(gps_fixes[k]);
+    return out;
+  }
+  size_t numPriors() const { return _pv.size(); }
+  // the second singular value of the centred fix positions of the keyframes in the graph [m]: 0 on a line
+  double gpsSpread() const {
+    double S[18] = {0.0};
+    for (const auto &kf : keyframes)
+      if (kf->has_gps_local) accumulate_pair(S, kf->gps_local, kf->gps_local);
+    if (S[0] < 3.0) return 0.0;
+    double R[9], t[3], W[3];
+    if (lslam_debug_icp_fit(S, R, t, W, nullptr) < 0) return 0.0;
+    return std::sqrt(W[1] > 0.0 ? W[1] : 0.0);  // F^T F of the centred fixes F: its singular values are those of F, squared
+  }
   Mat4d tf_odom2graph;
   int last_iterations = 0;
   const std::string &lastError() const { return _err; }
@@ -775,6 +850,90 @@ private:
     _err = lslam_last_error();
     if (fm) lslam_fmap_destroy(fm);
     return -1;
+  }
+  static void accumulate_pair(double S[18], const double s[3], const double t[3]) {  // lslam_debug_icp_fit's sums
+    S[0] += 1.0;
+    for (int r = 0; r < 3; ++r) {
+      S[2 + r] += s[r];
+      S[5 + r] += t[r];
+      for (int c = 0; c < 3; ++c) S[8 + r * 3 + c] += s[r] * t[c];
+    }
+  }
+  // The priors of a pass's new keyframes: queued until the fixes span a plane, then added -- all of them, after the graph frame
+  // has been moved onto the fixes.  -> whether any prior reached the solver.
+  bool add_priors(const std::vector<KeyFrame::Ptr> &fresh, int gps_kind) {
+    const bool gps = gps_sigma_xy > 0.0, imu = imu_orientation_sigma > 0.0;
+    if (!gps && !imu) return false;
+    for (const auto &kf : fresh) {
+      if (gps && kf->has_utm_coord) {
+        if (!has_utm_origin) {
+          has_utm_origin = true;
+          for (int k = 0; k < 3; ++k) utm_origin[k] = kf->utm_coord[k];
+        }
+        kf->has_gps_local = true;
+        for (int k = 0; k < 3; ++k) kf->gps_local[k] = kf->utm_coord[k] - utm_origin[k];  // fp64, before anything reaches the solver
+      }
+      if (kf->has_gps_local || (imu && kf->has_imu_quat)) _prior_queue.push_back(kf);
+    }
+    if (gps && !gps_aligned && !align_to_fixes()) return false;
+    bool added = false;
+    for (const auto &kf : _prior_queue) {
+      if (kf->has_gps_local) {
+        double w[36] = {0.0};
+        w[0] = w[7] = 1.0 / (gps_sigma_xy * gps_sigma_xy);
+        w[14] = 1.0 / (gps_sigma_z * gps_sigma_z);
+        const double z[7] = {kf->gps_local[0], kf->gps_local[1], kf->gps_local[2], 0.0, 0.0, 0.0, 1.0};
+        _gps_priors.push_back((int)_pv.size());
+        gps_fixes.push_back(kf);
+        add_prior(kf->node, LSLAM_PG_PRIOR_XYZ, z, w, gps_kind, gps_robust_kernel_size);
+        added = true;
+      }
+      if (imu && kf->has_imu_quat) {
+        const double *q = kf->imu_quat;
+        const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        const double z[7] = {0.0, 0.0, 0.0, q[0] / n, q[1] / n, q[2] / n, q[3] / n};
+        double w[36] = {0.0};
+        w[21] = w[28] = w[35] = (2.0 / imu_orientation_sigma) * (2.0 / imu_orientation_sigma);
+        add_prior(kf->node, LSLAM_PG_PRIOR_POSE, z, w, LSLAM_PG_KERNEL_NONE, 1.0);
+        added = true;
+      }
+    }
+    _prior_queue.clear();
+    return added;
+  }
+  void add_prior(int v, int type, const double z[7], const double w[36], int kind, double delta) {
+    _pv.push_back(v);
+    _ptype.push_back(type);
+    _pmeas.insert(_pmeas.end(), z, z + 7);
+    _pinfo.insert(_pinfo.end(), w, w + 36);
+    _pkind.push_back(kind);
+    _pdelta.push_back(delta);
+  }
+  // Once the fixes span a plane: the rigid fit of the keyframes' estimate positions to their fixes moves every estimate and
+  // tf_odom2graph, and no vertex is fixed from here on.  -> whether that has happened.
+  bool align_to_fixes() {
+    const double need = gps_min_spread > 0.0 ? gps_min_spread : 10.0 * gps_sigma_xy;
+    if (!(gpsSpread() >= need)) return false;
+    double S[18] = {0.0};
+    for (const auto &kf : keyframes)
+      if (kf->has_gps_local) {
+        const double s[3] = {kf->estimate(0, 3), kf->estimate(1, 3), kf->estimate(2, 3)};
+        accumulate_pair(S, s, kf->gps_local);
+      }
+    double R[9], t[3], W[3];
+    if (lslam_debug_icp_fit(S, R, t, W, nullptr) < 0) return false;
+    Mat4d T;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) T.m[r * 4 + c] = R[r * 3 + c];
+      T.m[r * 4 + 3] = t[r];
+    }
+    for (auto &kf : keyframes) {
+      kf->estimate = T * kf->estimate;
+      mat_to_pose7(kf->estimate, &_poses[7 * (size_t)kf->node]);
+    }
+    tf_odom2graph = T * tf_odom2graph;
+    gps_aligned = true;
+    return true;
   }
   // graph.cpp:248-297
   bool flush_keyframe_queue() {
@@ -811,17 +970,29 @@ private:
   bool solve_graph(int max_iterations, const char *g2o_before, const char *g2o_end) {
     lslam_pg *pg = nullptr;
     if (lslam_pg_create(_device, (int)(_poses.size() / 7), _poses.data(), (int)(_ij.size() / 2), _ij.data(), _meas.data(), _info.data(),
-                        0, &pg) != LSLAM_OK) {
+                        gps_aligned ? -1 : 0, &pg) != LSLAM_OK) {  // (aligned: the priors hold the gauge, no vertex is fixed)
       _err = lslam_pg_last_error();
       return false;
     }
     lslam_pg_stats st;
     int rc = apply_kernels(pg);
+    if (rc >= 0 && !_pv.empty()) {
+      bool any = false;
+      for (size_t p = 0; p < _pkind.size(); ++p) any = any || _pkind[p] != LSLAM_PG_KERNEL_NONE;
+      rc = lslam_pg_set_priors(pg, (int32_t)_pv.size(), _pv.data(), _ptype.data(), _pmeas.data(), _pinfo.data(),
+                               any ? _pkind.data() : nullptr, any ? _pdelta.data() : nullptr);
+    }
     if (rc >= 0 && g2o_before) rc = lslam_pg_save_g2o(pg, g2o_before);
     if (rc >= 0) rc = lslam_pg_optimize(pg, max_iterations, &st);
     if (rc >= 0 && g2o_end) rc = lslam_pg_save_g2o(pg, g2o_end);
     if (rc >= 0) rc = lslam_pg_get_poses(pg, _poses.data());
     if (rc >= 0) rc = read_loop_weights(pg);
+    if (rc >= 0 && !_pv.empty()) {
+      std::vector<double> w(_pv.size());
+      rc = lslam_pg_prior_robust(pg, nullptr, nullptr, nullptr, w.data());
+      _gps_weights.clear();
+      for (size_t k = 0; rc >= 0 && k < _gps_priors.size(); ++k) _gps_weights.push_back(w[(size_t)_gps_priors[k]]);
+    }
     lslam_pg_destroy(pg);
     if (rc < 0) {
       _err = lslam_pg_last_error();
@@ -890,6 +1061,13 @@ private:
   std::vector<double> _loop_weights;
   std::vector<lslam_edge_info> _edge_infos;
   bool _edge_failed = false;
+  // unary constraints: vertex, LSLAM_PG_PRIOR_*, measurement, information, kernel; the keyframes whose priors wait for the
+  // alignment; the prior index of every entry of gps_fixes and its weight
+  std::vector<int32_t> _pv, _ptype, _pkind;
+  std::vector<double> _pmeas, _pinfo, _pdelta;
+  std::vector<KeyFrame::Ptr> _prior_queue;
+  std::vector<int> _gps_priors;
+  std::vector<double> _gps_weights;
   std::string _err;
 };
 

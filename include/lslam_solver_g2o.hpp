@@ -31,6 +31,7 @@ public:
     SolverG2OT *_owner;
   };
   struct EdgeSE3 { int index; };
+  struct EdgeSE3Prior { int index; };  // a unary constraint (lslam_pg_set_priors), by prior index
 
   explicit SolverG2OT(int device = 0) : is_first(true), _device(device), _pg(nullptr) {}
   ~SolverG2OT() { lslam_pg_destroy(_pg); }
@@ -77,6 +78,90 @@ public:
     _delta[(size_t)edge->index] = kernel_size;
     if (_pg) apply_kernels();
   }
+  // ---- unary constraints (not in the reference, whose keyframes only carry the utm_coord / imu_quat fields, keyframe.h:40-41;
+  // names and meaning of hdl_graph_slam's GraphSLAM, semantics in lslam_c.h).  Vec3: (i) read access; Mat3: (r, c) read access
+  // to a 3x3; Quat: .x() .y() .z() .w() (Eigen::Vector3d / Eigen::MatrixXd / Eigen::Quaterniond work).
+  // A position fix in the graph frame (GPS): EdgeSE3PriorXYZ.
+  template <typename Vec3, typename Mat3>
+  EdgeSE3Prior *add_se3_prior_xyz_edge(VertexSE3 *v, const Vec3 &xyz, const Mat3 &information_matrix) {
+    double z[7] = {xyz(0), xyz(1), xyz(2), 0.0, 0.0, 0.0, 1.0}, w[36] = {0.0};
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) w[r * 6 + c] = information_matrix(r, c);
+    return add_prior(v, LSLAM_PG_PRIOR_XYZ, z, w);
+  }
+  // An absolute orientation (IMU): EdgeSE3PriorQuat -- a pose prior whose translation block is zero.
+  template <typename Quat, typename Mat3>
+  EdgeSE3Prior *add_se3_prior_quat_edge(VertexSE3 *v, const Quat &quat, const Mat3 &information_matrix) {
+    double z[7] = {0.0, 0.0, 0.0, quat.x(), quat.y(), quat.z(), quat.w()}, w[36] = {0.0};
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) w[(3 + r) * 6 + 3 + c] = information_matrix(r, c);
+    return add_prior(v, LSLAM_PG_PRIOR_POSE, z, w);
+  }
+  // The full form: an absolute pose with a 6x6 information over [translation, rotation] (g2o's EdgeSE3Prior, zero offset).
+  EdgeSE3Prior *add_se3_prior_pose_edge(VertexSE3 *v, const Isometry &pose, const Matrix &information_matrix) {
+    double z[7], w[36];
+    to_pose7(pose, z);
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) w[r * 6 + c] = information_matrix(r, c);
+    return add_prior(v, LSLAM_PG_PRIOR_POSE, z, w);
+  }
+  // add_robust_kernel for a prior: GPS multipath is the outlier case
+  void add_robust_kernel(EdgeSE3Prior *prior, const std::string &kernel_type, double kernel_size) {
+    if (!prior || prior->index < 0 || prior->index >= (int)_priors.size()) throw std::invalid_argument("add_robust_kernel: no such prior");
+    const int kind = lslam_pg_kernel_from_name(kernel_type.c_str());
+    if (kind < 0) throw std::invalid_argument("add_robust_kernel: unknown kernel type " + kernel_type);
+    if (kind != LSLAM_PG_KERNEL_NONE && !(std::isfinite(kernel_size) && kernel_size > 0.0))
+      throw std::invalid_argument("add_robust_kernel: kernel_size must be finite and > 0");
+    _pkind[(size_t)prior->index] = kind;
+    _pdelta[(size_t)prior->index] = kernel_size;
+    if (_pg) apply_priors();
+  }
+  // the robust weight (rho1) of every prior at the current estimate, by prior index; all 1 without kernels
+  std::vector<double> priorWeights() {
+    build();
+    std::vector<double> w(_priors.size());
+    if (lslam_pg_prior_robust(_pg, nullptr, nullptr, nullptr, w.data()) < 0)
+      throw std::runtime_error(std::string("lslam_pg_prior_robust: ") + lslam_pg_last_error());
+    return w;
+  }
+  // true (default, solver_g2o.cpp:55-59): the first vertex is held fixed; false: no vertex is -- for graphs whose priors fix
+  // the gauge.  Takes effect when the device graph is next built.
+  void setFixFirstNode(bool fix) {
+    if (fix == _fix_first) return;
+    pull();
+    _fix_first = fix;
+  }
+  // Replaces the graph by the one in a .g2o file written by save(): vertices, edges, priors and whether a vertex is fixed
+  // (lslam_g2o_read / lslam_g2o_read_priors).  Vertex and edge pointers handed out before are invalid afterwards.
+  void load(const std::string &filename) {
+    int32_t nv = 0, ne = 0, np = 0, fixed = -1;
+    if (lslam_g2o_read(filename.c_str(), &nv, nullptr, &ne, nullptr, nullptr, nullptr, &fixed) < 0 ||
+        lslam_g2o_read_priors(filename.c_str(), &np, nullptr, nullptr, nullptr, nullptr) < 0)
+      throw std::runtime_error(std::string("load: ") + lslam_pg_last_error());
+    std::vector<double> poses((size_t)nv * 7), meas((size_t)ne * 7), info((size_t)ne * 36), pmeas((size_t)np * 7), pinfo((size_t)np * 36);
+    std::vector<int32_t> ij((size_t)ne * 2), pv((size_t)np), pt((size_t)np);
+    if (lslam_g2o_read(filename.c_str(), &nv, poses.data(), &ne, ij.data(), meas.data(), info.data(), &fixed) < 0 ||
+        lslam_g2o_read_priors(filename.c_str(), &np, pv.data(), pt.data(), pmeas.data(), pinfo.data()) < 0)
+      throw std::runtime_error(std::string("load: ") + lslam_pg_last_error());
+    if (fixed > 0) throw std::runtime_error("load: only the first vertex can be the fixed one");
+    lslam_pg_destroy(_pg);
+    _pg = nullptr;
+    _vertices.clear();
+    _edges.clear();
+    _priors.clear();
+    for (int k = 0; k < nv; ++k) _vertices.push_back(VertexSE3{k, this});
+    for (int k = 0; k < ne; ++k) _edges.push_back(EdgeSE3{k});
+    for (int k = 0; k < np; ++k) _priors.push_back(EdgeSE3Prior{k});
+    _poses.swap(poses); _meas.swap(meas); _info.swap(info); _ij.swap(ij);
+    _pv.swap(pv); _ptype.swap(pt); _pmeas.swap(pmeas); _pinfo.swap(pinfo);
+    _kind.assign((size_t)ne, LSLAM_PG_KERNEL_NONE);
+    _delta.assign((size_t)ne, 1.0);
+    _pkind.assign((size_t)np, LSLAM_PG_KERNEL_NONE);
+    _pdelta.assign((size_t)np, 1.0);
+    _fix_first = fixed == 0;
+    is_first = nv == 0;
+  }
+  size_t numPriors() const { return _priors.size(); }
   // the robust weight (rho1) of every edge at the current estimate, by edge index; all 1 without kernels
   std::vector<double> edgeWeights() {
     build();
@@ -157,10 +242,34 @@ private:
     if (_pg) return;
     if (_vertices.empty()) throw std::runtime_error("empty pose graph");
     if (lslam_pg_create(_device, (int32_t)_vertices.size(), _poses.data(), (int32_t)_edges.size(), _ij.data(), _meas.data(),
-                        _info.data(), 0, &_pg) != LSLAM_OK)
+                        _info.data(), _fix_first ? 0 : -1, &_pg) != LSLAM_OK)
       throw std::runtime_error(std::string("lslam_pg_create: ") + lslam_pg_last_error());
     if (_solve_tol > 0.0) (void)lslam_pg_set_solve_tolerance(_pg, _solve_tol);
     apply_kernels();
+    if (!_priors.empty()) apply_priors();
+  }
+  EdgeSE3Prior *add_prior(VertexSE3 *v, int type, const double z[7], const double w[36]) {
+    if (!v) throw std::invalid_argument("prior: no vertex");
+    pull();
+    _pv.push_back(v->id());
+    _ptype.push_back(type);
+    _pmeas.insert(_pmeas.end(), z, z + 7);
+    _pinfo.insert(_pinfo.end(), w, w + 36);
+    _pkind.push_back(LSLAM_PG_KERNEL_NONE);
+    _pdelta.push_back(1.0);
+    _priors.push_back(EdgeSE3Prior{(int)_priors.size()});
+    return &_priors.back();
+  }
+  void apply_priors() {
+    bool any = false;
+    for (size_t p = 0; p < _pkind.size(); ++p) any = any || _pkind[p] != LSLAM_PG_KERNEL_NONE;
+    if (lslam_pg_set_priors(_pg, (int32_t)_priors.size(), _pv.data(), _ptype.data(), _pmeas.data(), _pinfo.data(),
+                            any ? _pkind.data() : nullptr, any ? _pdelta.data() : nullptr) < 0) {
+      const std::string why = lslam_pg_last_error();
+      lslam_pg_destroy(_pg);  // never a device graph without the priors it was asked to carry
+      _pg = nullptr;
+      throw std::runtime_error("lslam_pg_set_priors: " + why);
+    }
   }
   void apply_kernels() {
     bool any = false;
@@ -192,6 +301,10 @@ private:
   std::vector<int32_t> _ij;
   std::vector<int32_t> _kind;  // per edge: LSLAM_PG_KERNEL_* and its delta
   std::vector<double> _delta;
+  bool _fix_first = true;
+  std::deque<EdgeSE3Prior> _priors;  // unary constraints: vertex, LSLAM_PG_PRIOR_*, measurement, information, kernel
+  std::vector<int32_t> _pv, _ptype, _pkind;
+  std::vector<double> _pmeas, _pinfo, _pdelta;
 };
 
 }  // namespace pose_graph

@@ -525,6 +525,11 @@ SYMBOLS = {
     "lslam_pg_set_robust_kernels": (C.c_int, [C.c_void_p, c_int32_p, c_double_p]),
     "lslam_pg_edge_robust": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "lslam_pg_robust_info": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_double_p]),
+    "lslam_pg_set_priors": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_double_p, c_double_p, c_int32_p,
+                                      c_double_p]),
+    "lslam_pg_num_priors": (C.c_int32, [C.c_void_p]),
+    "lslam_pg_prior_robust": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "lslam_g2o_read_priors": (C.c_int, [C.c_char_p, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p]),
     "lslam_pg_stream": (C.c_void_p, [C.c_void_p]),
     "lslam_pg_kernel_from_name": (C.c_int, [C.c_char_p]),
     "lslam_icp_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, C.c_int32,

@@ -167,7 +167,11 @@ void svd3(const double A[9], double U[9], double S[3], double V[9]) {
     nw = std::sqrt(nw);  // >= sqrt(2/3): |e_k . u0| <= 1/sqrt(3)
     for (int r = 0; r < 3; ++r) U[r * 3 + 1] = w[r] / nw;
   }
-  if (!(S[2] > 1e-300) || S[2] <= 1e-300 * (S[0] + 1e-300)) {
+  // (relative to the largest: a source EXACTLY in a plane -- a ground vehicle's odometry positions, z = 0 -- leaves a row of A
+  // exactly zero; the rotations then leave a third column of ~1e-154, whose squares underflow: S[2] is above any absolute floor
+  // and B / S[2] is no unit vector.  1e-100 S[0] is far below what rounding leaves of a merely near-planar cloud (~1e-17 S[0]),
+  // whose bits stay as they were)
+  if (!(S[2] > 1e-300) || S[2] <= 1e-100 * S[0]) {
     U[2] = U[3] * U[7] - U[6] * U[4];
     U[5] = U[6] * U[1] - U[0] * U[7];
     U[8] = U[0] * U[4] - U[3] * U[1];

@@ -10,7 +10,9 @@
 //   pg_edge_kernel, pg_edge_robust_kernel (edges with robust kernels; pg_edge_robust_tap_kernel: their e2 / rho for the host)
 //                       one lane per edge of this rank's shard: error, analytic Jacobians,
 //                       J^T Omega J blocks, J^T Omega e, chi2 -> per-edge records
-//   pg_assemble_vertex_kernel, pg_assemble_off_kernel, pg_sum_kernel
+//   pg_prior_kernel     one lane per unary constraint (GPS position / absolute pose on one vertex; pg_prior_chi2_kernel,
+//                       pg_prior_tap_kernel: the trial's and the host's values) -- launched only while a graph has priors
+//   pg_assemble_vertex_kernel (pg_assemble_vertex_prior_kernel with priors), pg_assemble_off_kernel, pg_sum_kernel
 //                       deterministic gather of the records into the block system
 //                       [diag blocks | off-diagonal blocks | b | chi2]  (fixed order, no atomics)
 //   (all-reduce of that buffer across ranks: callback, or the library's RCCL communicator)
@@ -339,6 +341,127 @@ __global__ void pg_edge_robust_tap_kernel(const double *poses, const int32_t *ij
   w_out[e] = rho1;
 }
 
+// ---- unary constraints (lslam_pg_set_priors): a GPS position or an absolute pose on one vertex ------------------------------
+// hdl_graph_slam's EdgeSE3PriorXYZ and g2o's EdgeSE3Prior (zero offset); neither is pinned by the reference, like the rest of
+// this solver: the semantics are their published ones, in this file's conventions (update X <- X * fromVectorMQT(d)).
+//   XYZ   e = t - z in the graph frame (rows 3..5 of the 6-row form below are zero), J = [R(q) | 0], Omega = the upper-left
+//         3x3 of info36 (the host zeroes the rest before it is uploaded, so one code path serves both types)
+//   POSE  e = toVectorMQT(Z^-1 X): the binary edge's error with Xi = identity, J = its Jj
+// Per-prior record: [H(36) b(6) chi2] = 43 doubles
+constexpr int PREC = 43;
+
+template <bool JAC>
+PG_DEV void prior_error(int type, const Pose &x, const Pose &z, double e[6], double *J) {
+  if (type == LSLAM_PG_PRIOR_POSE) {
+    const Pose id = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};
+    double Ji[36];  // of the identity "vertex": never used
+    edge_error<JAC>(id, x, z, e, JAC ? Ji : nullptr, J);
+    return;
+  }
+  e[0] = x.t.x - z.t.x; e[1] = x.t.y - z.t.y; e[2] = x.t.z - z.t.z;
+  e[3] = 0.0; e[4] = 0.0; e[5] = 0.0;
+  if (!JAC) return;
+  double R[9];
+  qrotmat(x.q, R);
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) J[r * 6 + c] = (r < 3 && c < 3) ? R[r * 3 + c] : 0.0;
+}
+
+// One lane per prior.  ROBUST as in edge_record: rho1 scales H and b, rho0 goes to chi2.  A prior on the fixed vertex adds its
+// rho0 to chi2 and nothing to H or b (g2o: an active edge on a fixed vertex).  chi: this rank's compact per-constraint values,
+// the priors' behind the edges'.
+template <bool ROBUST>
+PG_DEV void prior_record(const double *poses, const int32_t *pv, const int32_t *ptype, const double *pmeas,
+                         const double *pinfo, int n_p, int fixed, const int32_t *kind, const double *delta, double *rec,
+                         double *chi) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_p) return;
+  const int v = pv[p];
+  const Pose x = load_pose(poses + 7 * v), z = load_pose(pmeas + 7 * p);
+  double er[6], J[36], Om[36];
+  prior_error<true>(ptype[p], x, z, er, J);
+#pragma unroll
+  for (int k = 0; k < 36; ++k) Om[k] = pinfo[(size_t)p * 36 + k];
+  double c2 = edge_e2(Om, er), w = 1.0;
+  if (ROBUST) {
+    const int kd = kind[p];
+    robustify(kd, kd != LSLAM_PG_KERNEL_NONE ? delta[p] : 1.0, c2, c2, w);
+  }
+  double A[36];  // J^T Omega
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s += J[k * 6 + r] * Om[k * 6 + c];
+      A[r * 6 + c] = s;
+    }
+  const bool fx = (v == fixed);
+  double *o = rec + (size_t)p * PREC;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double h = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) h += A[r * 6 + k] * J[k * 6 + c];
+      if (ROBUST) h *= w;
+      o[r * 6 + c] = fx ? 0.0 : h;
+    }
+    double bv = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) bv += A[r * 6 + k] * er[k];
+    if (ROBUST) bv *= w;
+    o[36 + r] = fx ? 0.0 : -bv;
+  }
+  o[42] = c2;
+  chi[p] = c2;
+}
+
+template <bool ROBUST>
+__global__ void pg_prior_kernel(const double *poses, const int32_t *pv, const int32_t *ptype, const double *pmeas,
+                                const double *pinfo, int n_p, int fixed, const int32_t *kind, const double *delta,
+                                double *rec, double *chi) {
+  prior_record<ROBUST>(poses, pv, ptype, pmeas, pinfo, n_p, fixed, kind, delta, rec, chi);
+}
+
+// trial evaluation: per-prior chi2 (ROBUST: rho0)
+template <bool ROBUST>
+__global__ void pg_prior_chi2_kernel(const double *poses, const int32_t *pv, const int32_t *ptype, const double *pmeas,
+                                     const double *pinfo, int n_p, const int32_t *kind, const double *delta, double *out) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_p) return;
+  const Pose x = load_pose(poses + 7 * pv[p]), z = load_pose(pmeas + 7 * p);
+  double er[6];
+  prior_error<false>(ptype[p], x, z, er, nullptr);
+  double c2 = edge_e2(pinfo + (size_t)p * 36, er), w = 1.0;
+  if (ROBUST) {
+    const int kd = kind[p];
+    robustify(kd, kd != LSLAM_PG_KERNEL_NONE ? delta[p] : 1.0, c2, c2, w);
+  }
+  out[p] = c2;
+}
+// Tap: per prior e2, rho0 and rho1 at `poses`; kind == nullptr: no kernels, (e2, e2, 1)
+__global__ void pg_prior_tap_kernel(const double *poses, const int32_t *pv, const int32_t *ptype, const double *pmeas,
+                                    const double *pinfo, int n_p, const int32_t *kind, const double *delta, double *e2_out,
+                                    double *rho_out, double *w_out) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_p) return;
+  const Pose x = load_pose(poses + 7 * pv[p]), z = load_pose(pmeas + 7 * p);
+  double er[6];
+  prior_error<false>(ptype[p], x, z, er, nullptr);
+  const double e2 = edge_e2(pinfo + (size_t)p * 36, er);
+  const int kd = kind ? kind[p] : LSLAM_PG_KERNEL_NONE;
+  double rho0, rho1;
+  robustify(kd, kd != LSLAM_PG_KERNEL_NONE ? delta[p] : 1.0, e2, rho0, rho1);
+  e2_out[p] = e2;
+  rho_out[p] = rho0;
+  w_out[p] = rho1;
+}
+
 // fixed-order sum of n doubles into *dst, single block of 1024 (four independent accumulators per thread keep four
 // loads in flight: with one, the 25 000-edge chi2 sum was a 36 us chain of dependent strided loads)
 constexpr int SUM_BLOCK = 1024;
@@ -374,6 +497,23 @@ __global__ void pg_assemble_vertex_kernel(const double *rec, const int32_t *v_pt
     s += rec[(size_t)(code >> 1) * REC + (code & 1) * 42 + k];
   }
   if (v == fixed) s = (k < 36 && (k / 6 == k % 6)) ? 1.0 : 0.0;  // identity row: dx_fixed = 0
+  if (k < 36) diag[(size_t)v * 36 + k] = s; else b[(size_t)v * 6 + (k - 36)] = s;
+}
+// The same for a graph with priors: the edge records in their order, then the vertex's prior records in prior order through
+// a second CSR (p_ptr / p_adj) -- still one fixed summation order, no atomics.
+__global__ void pg_assemble_vertex_prior_kernel(const double *rec, const int32_t *v_ptr, const int32_t *v_adj,
+                                                const double *prec, const int32_t *p_ptr, const int32_t *p_adj, int n_v,
+                                                int fixed, double *diag, double *b) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int v = t / 42, k = t % 42;
+  if (v >= n_v) return;
+  double s = 0.0;
+  for (int a = v_ptr[v]; a < v_ptr[v + 1]; ++a) {
+    const int code = v_adj[a];
+    s += rec[(size_t)(code >> 1) * REC + (code & 1) * 42 + k];
+  }
+  for (int a = p_ptr[v]; a < p_ptr[v + 1]; ++a) s += prec[(size_t)p_adj[a] * PREC + k];
+  if (v == fixed) s = (k < 36 && (k / 6 == k % 6)) ? 1.0 : 0.0;
   if (k < 36) diag[(size_t)v * 36 + k] = s; else b[(size_t)v * 6 + (k - 36)] = s;
 }
 __global__ void pg_assemble_off_kernel(const double *rec, const int32_t *o_ptr, const int32_t *o_adj,
@@ -1721,6 +1861,18 @@ struct lslam_pg {
   std::vector<int32_t> h_kind;
   bool robust = false;
   lslam::DevBuf<double> d_tap, d_tap_poses;  // lslam_pg_edge_robust: [e2 | rho0 | rho1] of n_e each; caller-supplied poses
+  // unary constraints (lslam_pg_set_priors).  n_p == 0 -- the default -- launches exactly what a graph without them launches.
+  // The host copies are what the caller gave (save_g2o writes them); the device's info has everything outside an XYZ
+  // prior's 3x3 zeroed and its measurement quaternion set to the identity.
+  int n_p = 0;
+  bool prior_robust = false;  // some prior carries a kernel: the robust instantiations of the prior kernels
+  std::vector<int32_t> h_pv, h_ptype, h_pkind;
+  std::vector<double> h_pmeas, h_pinfo, h_pdelta;
+  lslam::DevBuf<int32_t> d_pv, d_ptype, d_pkind, d_pptr, d_padj;
+  lslam::DevBuf<double> d_pmeas, d_pinfo, d_pdelta, d_prec, d_ptap;
+  // In a sharded run the system is summed over the ranks, so every prior must be counted once: the rank whose edge range
+  // starts at 0 and is not empty carries all of them (a graph without edges: its one range [0, 0) does).
+  int local_priors() const { return (e_begin == 0 && (e_end > 0 || n_e == 0)) ? n_p : 0; }
   // shard structures
   lslam::DevBuf<double> d_rec, d_chi;
   lslam::DevBuf<int32_t> d_vptr, d_vadj, d_optr, d_oadj;
@@ -1803,7 +1955,7 @@ int build_shard(lslam_pg *pg, int e_begin, int e_end) {
     oadj[oc[pg->edge_block[e]]++] = le;
   }
   PG_TRY(pg->d_rec.alloc(std::max<size_t>(1, (size_t)ne) * REC));
-  PG_TRY(pg->d_chi.alloc((size_t)ne));
+  PG_TRY(pg->d_chi.alloc((size_t)ne + (size_t)pg->n_p));  // the priors' values sit behind the edges' (linearize)
   PG_TRY(dev_upload(pg->d_vptr, vptr));
   PG_TRY(dev_upload(pg->d_vadj, vadj));
   PG_TRY(dev_upload(pg->d_optr, optr));
@@ -1821,13 +1973,25 @@ int linearize(lslam_pg *pg, const double *poses) {
   else if (ne > 0)
     hipLaunchKernelGGL(pg_edge_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij.p,
                        pg->d_meas.p, pg->d_info.p, pg->e_begin, pg->e_end, pg->fixed, pg->d_rec.p, pg->d_chi.p);
-  hipLaunchKernelGGL(pg_assemble_vertex_kernel, dim3((pg->n_v * 42 + 255) / 256), dim3(256), 0, pg->stream,
-                     pg->d_rec.p, pg->d_vptr.p, pg->d_vadj.p, pg->n_v, pg->sharded() ? -1 : pg->fixed,
-                     pg->diag(), pg->b());
+  const int np = pg->local_priors();
+  if (np > 0) {
+    const int32_t *kind = pg->prior_robust ? pg->d_pkind.p : nullptr;
+    const double *delta = pg->prior_robust ? pg->d_pdelta.p : nullptr;
+    hipLaunchKernelGGL(pg->prior_robust ? pg_prior_kernel<true> : pg_prior_kernel<false>, dim3((np + 127) / 128), dim3(128),
+                       0, pg->stream, poses, pg->d_pv.p, pg->d_ptype.p, pg->d_pmeas.p, pg->d_pinfo.p, np, pg->fixed, kind,
+                       delta, pg->d_prec.p, pg->d_chi.p + ne);
+    hipLaunchKernelGGL(pg_assemble_vertex_prior_kernel, dim3((pg->n_v * 42 + 255) / 256), dim3(256), 0, pg->stream,
+                       pg->d_rec.p, pg->d_vptr.p, pg->d_vadj.p, pg->d_prec.p, pg->d_pptr.p, pg->d_padj.p, pg->n_v,
+                       pg->sharded() ? -1 : pg->fixed, pg->diag(), pg->b());
+  } else {  // no priors: exactly the launches of a graph that never had any
+    hipLaunchKernelGGL(pg_assemble_vertex_kernel, dim3((pg->n_v * 42 + 255) / 256), dim3(256), 0, pg->stream,
+                       pg->d_rec.p, pg->d_vptr.p, pg->d_vadj.p, pg->n_v, pg->sharded() ? -1 : pg->fixed,
+                       pg->diag(), pg->b());
+  }
   if (pg->n_off > 0)
     hipLaunchKernelGGL(pg_assemble_off_kernel, dim3((pg->n_off * 36 + 255) / 256), dim3(256), 0, pg->stream,
                        pg->d_rec.p, pg->d_optr.p, pg->d_oadj.p, pg->n_off, pg->off());
-  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne, 1, pg->chi());
+  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne + np, 1, pg->chi());
   PG_TRY(hipGetLastError());
   if (pg->sharded()) {
     const int rc = pg->reduce(pg->d_sys.p, pg->core_doubles());
@@ -1851,7 +2015,13 @@ int eval_chi2(lslam_pg *pg, const double *poses, double *out) {
   else if (ne > 0)
     hipLaunchKernelGGL(pg_chi2_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij.p,
                        pg->d_meas.p, pg->d_info.p, pg->e_begin, pg->e_end, pg->d_chi.p);
-  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne, 1, pg->chi());
+  const int np = pg->local_priors();
+  if (np > 0)
+    hipLaunchKernelGGL(pg->prior_robust ? pg_prior_chi2_kernel<true> : pg_prior_chi2_kernel<false>, dim3((np + 127) / 128),
+                       dim3(128), 0, pg->stream, poses, pg->d_pv.p, pg->d_ptype.p, pg->d_pmeas.p, pg->d_pinfo.p, np,
+                       pg->prior_robust ? pg->d_pkind.p : (const int32_t *)nullptr,
+                       pg->prior_robust ? pg->d_pdelta.p : (const double *)nullptr, pg->d_chi.p + ne);
+  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne + np, 1, pg->chi());
   PG_TRY(hipGetLastError());
   if (pg->sharded()) {
     // chi2 and, next to it, whether this rank's persistent kernels gave way to their launch loops in the solve before:
@@ -2833,6 +3003,152 @@ int lslam_pg_robust_info(lslam_pg *pg, int32_t *n_robust, int32_t *n_downweighte
   return LSLAM_OK;
 }
 
+// ---- unary constraints ----------------------------------------------------------------------------------------------------
+int lslam_pg_set_priors(lslam_pg *pg, int32_t n_priors, const int32_t *vertex, const int32_t *type, const double *meas7,
+                        const double *info36, const int32_t *kind, const double *delta) {
+  if (!pg || n_priors < 0 || (n_priors > 0 && (!vertex || !type || !meas7 || !info36))) {
+    g_pg_err = "priors: bad arguments";
+    return LSLAM_ERR_INVALID;
+  }
+  if ((kind == nullptr) != (delta == nullptr)) {
+    g_pg_err = "priors: kind and delta are given together, or both NULL";
+    return LSLAM_ERR_INVALID;
+  }
+  PG_TRY(hipSetDevice(pg->device));
+  const size_t n = (size_t)n_priors;
+  std::vector<double> dm(7 * n), di(36 * n, 0.0), dd(n, 1.0);
+  bool any_kernel = false;
+  for (size_t p = 0; p < n; ++p) {  // everything is checked before anything changes
+    const std::string at = " (prior " + std::to_string(p) + ")";
+    if (vertex[p] < 0 || vertex[p] >= pg->n_v) {
+      g_pg_err = "priors: vertex out of range" + at;
+      return LSLAM_ERR_INVALID;
+    }
+    if (type[p] != LSLAM_PG_PRIOR_XYZ && type[p] != LSLAM_PG_PRIOR_POSE) {
+      g_pg_err = "priors: unknown type " + std::to_string(type[p]) + at;
+      return LSLAM_ERR_INVALID;
+    }
+    const bool pose = type[p] == LSLAM_PG_PRIOR_POSE;
+    const double *m = meas7 + 7 * p, *w = info36 + 36 * p;
+    for (int k = 0; k < (pose ? 7 : 3); ++k)
+      if (!std::isfinite(m[k])) {
+        g_pg_err = "priors: measurement is not finite" + at;
+        return LSLAM_ERR_INVALID;
+      }
+    if (pose && !(m[3] * m[3] + m[4] * m[4] + m[5] * m[5] + m[6] * m[6] > 0.0)) {
+      g_pg_err = "priors: zero-norm quaternion" + at;
+      return LSLAM_ERR_INVALID;
+    }
+    const int d = pose ? 6 : 3;  // the block that is used
+    double big = 0.0;
+    for (int r = 0; r < d; ++r)
+      for (int c = 0; c < d; ++c) {
+        if (!std::isfinite(w[r * 6 + c])) {
+          g_pg_err = "priors: information is not finite" + at;
+          return LSLAM_ERR_INVALID;
+        }
+        big = std::max(big, std::fabs(w[r * 6 + c]));
+      }
+    for (int r = 0; r < d; ++r) {
+      if (w[r * 6 + r] < 0.0) {
+        g_pg_err = "priors: information has a negative diagonal entry" + at;
+        return LSLAM_ERR_INVALID;
+      }
+      for (int c = r + 1; c < d; ++c)
+        if (std::fabs(w[r * 6 + c] - w[c * 6 + r]) > 1e-12 * big) {  // (rounding of a product A A^T is far below this)
+          g_pg_err = "priors: information is not symmetric" + at;
+          return LSLAM_ERR_INVALID;
+        }
+    }
+    if (kind) {
+      if (kind[p] < LSLAM_PG_KERNEL_NONE || kind[p] > LSLAM_PG_KERNEL_DCS) {
+        g_pg_err = "priors: unknown robust kernel " + std::to_string(kind[p]) + at;
+        return LSLAM_ERR_INVALID;
+      }
+      if (kind[p] != LSLAM_PG_KERNEL_NONE) {
+        if (!std::isfinite(delta[p]) || !(delta[p] > 0.0)) {
+          g_pg_err = "priors: delta must be finite and > 0" + at;
+          return LSLAM_ERR_INVALID;
+        }
+        any_kernel = true;
+        dd[p] = delta[p];
+      }
+    }
+    // the device's copy: what the kernels read, nothing else (never a NaN in device memory)
+    for (int k = 0; k < 3; ++k) dm[7 * p + k] = m[k];
+    // (a POSE prior's quaternion normalised: edge_error takes the measurement's as a unit quaternion)
+    const double qn = pose ? std::sqrt(m[3] * m[3] + m[4] * m[4] + m[5] * m[5] + m[6] * m[6]) : 1.0;
+    for (int k = 3; k < 7; ++k) dm[7 * p + k] = pose ? m[k] / qn : (k == 6 ? 1.0 : 0.0);
+    for (int r = 0; r < d; ++r)
+      for (int c = 0; c < d; ++c) di[36 * p + r * 6 + c] = w[r * 6 + c];
+  }
+  PG_TRY(hipStreamSynchronize(pg->stream));  // nothing in flight still reads the arrays replaced here
+  std::vector<int32_t> hv(vertex, vertex + n), ht(type, type + n), hk(n, LSLAM_PG_KERNEL_NONE);
+  if (kind) hk.assign(kind, kind + n);
+  // From here on only a device error can stop the call: the graph then has NO priors (n_p = 0 until every array of the new
+  // set is in place), never a mixture of the old set's sizes and the new set's arrays.
+  pg->n_p = 0;
+  pg->prior_robust = false;
+  pg->h_pv.clear();
+  pg->h_ptype.clear();
+  if (n > 0) {
+    std::vector<int32_t> pptr((size_t)pg->n_v + 1, 0), padj(n);
+    for (size_t p = 0; p < n; ++p) pptr[(size_t)hv[p] + 1]++;
+    for (int v = 0; v < pg->n_v; ++v) pptr[(size_t)v + 1] += pptr[v];
+    std::vector<int32_t> pc(pptr.begin(), pptr.end() - 1);
+    for (size_t p = 0; p < n; ++p) padj[pc[hv[p]]++] = (int32_t)p;  // prior order = summation order
+    PG_TRY(dev_upload(pg->d_pv, hv));
+    PG_TRY(dev_upload(pg->d_ptype, ht));
+    PG_TRY(dev_upload(pg->d_pmeas, dm));
+    PG_TRY(dev_upload(pg->d_pinfo, di));
+    PG_TRY(dev_upload(pg->d_pkind, hk));
+    PG_TRY(dev_upload(pg->d_pdelta, dd));
+    PG_TRY(dev_upload(pg->d_pptr, pptr));
+    PG_TRY(dev_upload(pg->d_padj, padj));
+    PG_TRY(pg->d_prec.alloc(n * PREC));
+  }
+  if ((size_t)(pg->e_end - pg->e_begin) + n > pg->d_chi.cap)  // the priors' chi2 values sit behind the edges'
+    PG_TRY(pg->d_chi.alloc((size_t)(pg->e_end - pg->e_begin) + n));
+  pg->n_p = (int)n;
+  pg->prior_robust = any_kernel;
+  pg->h_pv.swap(hv);
+  pg->h_ptype.swap(ht);
+  pg->h_pkind.swap(hk);
+  pg->h_pmeas.assign(meas7, meas7 + 7 * n);
+  pg->h_pinfo.assign(info36, info36 + 36 * n);
+  pg->h_pdelta.swap(dd);
+  return LSLAM_OK;
+}
+
+int32_t lslam_pg_num_priors(const lslam_pg *pg) { return pg ? pg->n_p : 0; }
+
+int lslam_pg_prior_robust(lslam_pg *pg, const double *poses7, double *e2, double *rho, double *weight) {
+  if (!pg) return LSLAM_ERR_INVALID;
+  PG_TRY(hipSetDevice(pg->device));
+  const size_t n = (size_t)pg->n_p;
+  if (n == 0) return LSLAM_OK;
+  const double *poses = pg->d_poses.p;
+  if (poses7) {
+    PG_TRY(pg->d_tap_poses.alloc((size_t)pg->n_v * 7));
+    PG_TRY(hipMemcpyAsync(pg->d_tap_poses.p, poses7, (size_t)pg->n_v * 7 * 8, hipMemcpyHostToDevice, pg->stream));
+    poses = pg->d_tap_poses.p;
+  }
+  PG_TRY(pg->d_ptap.alloc(3 * n));
+  hipLaunchKernelGGL(pg_prior_tap_kernel, dim3((pg->n_p + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_pv.p,
+                     pg->d_ptype.p, pg->d_pmeas.p, pg->d_pinfo.p, pg->n_p,
+                     pg->prior_robust ? pg->d_pkind.p : (const int32_t *)nullptr,
+                     pg->prior_robust ? pg->d_pdelta.p : (const double *)nullptr, pg->d_ptap.p, pg->d_ptap.p + n,
+                     pg->d_ptap.p + 2 * n);
+  PG_TRY(hipGetLastError());
+  std::vector<double> h(3 * n);
+  PG_TRY(hipMemcpyAsync(h.data(), pg->d_ptap.p, 3 * n * 8, hipMemcpyDeviceToHost, pg->stream));
+  PG_TRY(hipStreamSynchronize(pg->stream));
+  if (e2) std::memcpy(e2, h.data(), n * 8);
+  if (rho) std::memcpy(rho, h.data() + n, n * 8);
+  if (weight) std::memcpy(weight, h.data() + 2 * n, n * 8);
+  return LSLAM_OK;
+}
+
 // The fixed vertex is no unknown (g2o removes it; here its row is the identity with a zero right-hand side and no coupling): its
 // step is exactly zero.  Block-Jacobi PCG keeps it so; the second preconditioner level prolongs an aggregate's correction onto
 // every member, the fixed one included, and PCG then only drives that row back to within its tolerance (~1e-9 seen).
@@ -2907,7 +3223,76 @@ int lslam_pg_save_g2o(lslam_pg *pg, const char *path) {
       for (int c = r; c < 6; ++c) ofs << ' ' << info[(size_t)e * 36 + r * 6 + c];
     ofs << '\n';
   }
+  // Unary constraints: g2o's own EDGE_SE3_PRIOR (vertex, offset parameter id, measurement, 21 upper-triangular entries) with
+  // one zero offset parameter in front, and hdl_graph_slam's EDGE_SE3_PRIORXYZ (vertex, x y z, 6 upper-triangular entries).
+  // Like an edge's, a prior's robust kernel has no place in the format.
+  if (std::find(pg->h_ptype.begin(), pg->h_ptype.end(), (int32_t)LSLAM_PG_PRIOR_POSE) != pg->h_ptype.end())
+    ofs << "PARAMS_SE3OFFSET 0 0 0 0 0 0 0 1\n";
+  for (int p = 0; p < pg->n_p; ++p) {
+    const bool pose = pg->h_ptype[p] == LSLAM_PG_PRIOR_POSE;
+    const int d = pose ? 6 : 3;
+    ofs << (pose ? "EDGE_SE3_PRIOR " : "EDGE_SE3_PRIORXYZ ") << pg->h_pv[p];
+    if (pose) ofs << " 0";
+    for (int k = 0; k < (pose ? 7 : 3); ++k) ofs << ' ' << pg->h_pmeas[(size_t)p * 7 + k];
+    for (int r = 0; r < d; ++r)
+      for (int c = r; c < d; ++c) ofs << ' ' << pg->h_pinfo[(size_t)p * 36 + r * 6 + c];
+    ofs << '\n';
+  }
   return ofs.good() ? LSLAM_OK : LSLAM_ERR_INVALID;
+}
+
+// The unary constraints of such a file (host only), in file order.  *n_priors: in = capacity, out = what the file holds;
+// vertices are numbered as lslam_g2o_read numbers them (order of appearance of the VERTEX_SE3:QUAT lines).
+int lslam_g2o_read_priors(const char *path, int32_t *n_priors, int32_t *vertex, int32_t *type, double *meas7,
+                          double *info36) {
+  if (!path || !n_priors) return LSLAM_ERR_INVALID;
+  std::ifstream ifs(path);
+  if (!ifs) {
+    g_pg_err = std::string("cannot open ") + path;
+    return LSLAM_ERR_INVALID;
+  }
+  std::map<long, int> ids;
+  int nv = 0, np = 0;
+  const int cap = *n_priors;
+  std::string line, tag;
+  while (std::getline(ifs, line)) {
+    std::istringstream ls(line);
+    if (!(ls >> tag)) continue;
+    if (tag == "VERTEX_SE3:QUAT") {
+      long id;
+      if (ls >> id) ids[id] = nv++;
+    } else if (tag == "EDGE_SE3_PRIOR" || tag == "EDGE_SE3_PRIORXYZ") {
+      const bool pose = tag == "EDGE_SE3_PRIOR";
+      const int d = pose ? 6 : 3, nm = pose ? 7 : 3, nu = pose ? 21 : 6;
+      long v, param;
+      double m[7] = {0, 0, 0, 0, 0, 0, 1}, u[21];
+      ls >> v;
+      if (pose) ls >> param;  // the offset parameter: lslam_pg_save_g2o writes one, the identity
+      for (int k = 0; k < nm; ++k) ls >> m[k];
+      for (int k = 0; k < nu; ++k) ls >> u[k];
+      if (!ls) { g_pg_err = "malformed " + tag + " line"; return LSLAM_ERR_INVALID; }
+      auto iv = ids.find(v);
+      if (iv == ids.end()) { g_pg_err = "prior refers to an unknown vertex"; return LSLAM_ERR_INVALID; }
+      if (np < cap) {
+        if (vertex) vertex[np] = iv->second;
+        if (type) type[np] = pose ? LSLAM_PG_PRIOR_POSE : LSLAM_PG_PRIOR_XYZ;
+        if (meas7) for (int k = 0; k < 7; ++k) meas7[(size_t)np * 7 + k] = m[k];
+        if (info36) {
+          for (int k = 0; k < 36; ++k) info36[(size_t)np * 36 + k] = 0.0;
+          int q = 0;
+          for (int r = 0; r < d; ++r)
+            for (int c = r; c < d; ++c) {
+              info36[(size_t)np * 36 + r * 6 + c] = u[q];
+              info36[(size_t)np * 36 + c * 6 + r] = u[q];
+              ++q;
+            }
+        }
+      }
+      ++np;
+    }
+  }
+  *n_priors = np;
+  return LSLAM_OK;
 }
 
 // Reader for the same format (host only, no device needed).  Two-call pattern: with NULL arrays it

@@ -76,10 +76,23 @@ def hessian_information(omega_ref, H, sum_b2, n_rows, range_sigma):
     return omega_ref + H / s2
 
 
+def rigid_fit(source, target):
+    """The rigid transform (4x4) that moves `source` onto `target` in the least-squares sense (Kabsch / Umeyama without
+    scale): the library's host fit ``lslam_debug_icp_fit`` on the 18 sums ``n | 0 | sum s | sum t | sum s t^T | 0`` -- no
+    device needed."""
+    from .scan_match import icp_fit
+    s, t = np.asarray(source, np.float64).reshape(-1, 3), np.asarray(target, np.float64).reshape(-1, 3)
+    fit = icp_fit(np.r_[float(len(s)), 0.0, s.sum(0), t.sum(0), (s.T @ t).reshape(-1), 0.0])
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = fit["R"], fit["t"]
+    return T
+
+
 class Graph:
     def __init__(self, device=0, ctx=None, loop_detector=None, max_keyframes_per_update=10, resident=False,
                  keep_host_clouds=True, store_max_points=0, store_max_keyframes=0, store_slab_points=0, appearance_loops=False,
-                 sc_params=None, loop_robust_kernel=None, loop_robust_delta=1.0, edge_information=None, range_sigma=None):
+                 sc_params=None, loop_robust_kernel=None, loop_robust_delta=1.0, edge_information=None, range_sigma=None,
+                 gps_sigma=None, gps_robust_kernel=None, gps_robust_delta=1.0, gps_min_spread=None, imu_orientation_sigma=None):
         """``resident=True``: the keyframes' clouds live in a :class:`KeyframeStore` on the loop detector's context --
         ``add_frame`` uploads them once (``kf.store_id``), loop closure and ``get_final_feature_map`` read them there;
         ``keep_host_clouds=False`` then drops the host copies (``kf.corner_cloud`` / ``kf.surf_cloud`` fetch on demand).
@@ -98,7 +111,39 @@ class Graph:
         ``resident=True`` and ``range_sigma``): every edge's information is the reference's constant plus the fp64 match Hessian
         of the two keyframes at the edge's measurement (``lslam_keyframe_edge_information``) over the residual variance, floored at
         ``range_sigma``^2 -- :func:`hessian_information`.  ``range_sigma`` [m] is the range noise of the caller's sensor and
-        has no default: the library does not guess it.  None (the default) changes nothing."""
+        has no default: the library does not guess it.  None (the default) changes nothing.
+        ``gps_sigma=(sigma_xy, sigma_z)`` [m] (not in the reference, whose keyframes only carry the ``utm_coord`` / ``imu_quat``
+        fields, keyframe.h:40-41): the fixes handed to ``add_frame(utm_coord=...)`` become XYZ priors with information
+        ``diag(1/sxy^2, 1/sxy^2, 1/sz^2)`` (``lslam_pg_set_priors``), with ``gps_robust_kernel`` / ``gps_robust_delta`` on each
+        (GPS multipath: "Cauchy" rejects an outlying fix; :meth:`gps_weights`, :meth:`rejected_fixes`).  Like ``range_sigma`` it
+        has no default: the library does not guess a receiver's noise.  ``utm_origin`` is the first keyframe fix, kept in fp64
+        on the host and subtracted before anything reaches the solver (UTM coordinates are ~1e6 m).  GAUGE: the graph frame
+        starts as the first lidar pose, not ENU, and priors under a fixed, misaligned first vertex would bend the map -- so
+        until the fixes span a plane (second singular value of the centred fix positions >= ``gps_min_spread``, default
+        ``10 * sigma_xy``: the heading is then observable well above the noise) the priors are queued and the first vertex
+        stays fixed, the reference's behaviour; once they do, the keyframe estimates and ``tf_odom2graph`` are moved by the
+        rigid fit of estimate positions to fixes (:func:`rigid_fit`), all queued priors are added and the solver is
+        rebuilt with no fixed vertex.  ``imu_orientation_sigma`` [rad]: ``add_frame(imu_quat=...)`` (x, y, z, w, in the frame
+        the fixes are in) becomes a POSE prior with a zero translation block and ``(2 / sigma)^2`` on the quaternion vector
+        (half the angle); queued with the fixes when ``gps_sigma`` is set.  ``optimize`` then runs the solver when a pass
+        added loops OR priors.  All of it is off by default."""
+        self.gps_sigma = None
+        if gps_sigma is not None:
+            sxy, sz = (float(v) for v in gps_sigma)
+            if not (sxy > 0.0 and sz > 0.0 and np.isfinite(sxy) and np.isfinite(sz)):
+                raise ValueError("Graph: gps_sigma is (sigma_xy, sigma_z) in metres, both > 0")
+            self.gps_sigma = (sxy, sz)
+        self.gps_robust_kernel = gps_robust_kernel if kernel_kind(gps_robust_kernel) else None
+        self.gps_robust_delta = float(gps_robust_delta)
+        self.gps_min_spread = None if self.gps_sigma is None else (10.0 * self.gps_sigma[0] if gps_min_spread is None else float(gps_min_spread))
+        self.imu_orientation_sigma = None if imu_orientation_sigma is None else float(imu_orientation_sigma)
+        if self.imu_orientation_sigma is not None and not self.imu_orientation_sigma > 0.0:
+            raise ValueError("Graph: imu_orientation_sigma [rad] must be > 0")
+        self.utm_origin = None      # the first keyframe fix (fp64, host)
+        self.gps_aligned = False    # the graph frame has been moved onto the fixes and no vertex is fixed any more
+        self.gps_fixes = []         # (keyframe, prior index in the solver) of every GPS prior added
+        self._prior_queue = []      # keyframes whose priors wait for the alignment
+        self._bookkeeping_only = False  # tests: optimize() adds keyframes, edges and priors but never runs the solver
         if edge_information not in (None, "hessian"):
             raise ValueError("Graph: edge_information is None or \"hessian\"")
         if edge_information == "hessian":
@@ -131,7 +176,9 @@ class Graph:
         self.loop_edges = []  # solver edge index of every entry of self.loops
 
     # graph.cpp:230-246
-    def add_frame(self, odom, corner_cloud, surf_cloud):
+    def add_frame(self, odom, corner_cloud, surf_cloud, utm_coord=None, imu_quat=None):
+        """``utm_coord`` (x, y, z [m], projected -- what kf_fusion/fpdReceiver.cpp makes of a fix) and ``imu_quat`` (x, y, z, w)
+        are keyframe.h:40-41's optional fields: stored on the keyframe, used only with ``gps_sigma`` / ``imu_orientation_sigma``."""
         odom = np.asarray(odom, np.float64).reshape(4, 4)
         if not self.keyframe_updater.update(odom):
             return None
@@ -139,6 +186,8 @@ class Graph:
                       frame_id=self.keyframe_updater.get_unique_id())
         kf.odom = odom.copy()
         kf.node = None
+        kf.utm_coord = None if utm_coord is None else np.array(utm_coord, np.float64).reshape(3)
+        kf.imu_quat = None if imu_quat is None else np.array(imu_quat, np.float64).reshape(4)
         if self.store is not None:
             kf.put_in_store(self.store, self.keep_host_clouds)
         self.keyframe_queue.append(kf)
@@ -201,9 +250,10 @@ class Graph:
                                                             robust_delta=self.loop_robust_delta))
         self.loops.extend(loops)
         self.keyframes.extend(self.new_keyframes)
+        added_priors = self._add_priors(self.new_keyframes)
         self.new_keyframes = []
         iterations = 0
-        if loops:
+        if (loops or added_priors) and not self._bookkeeping_only:
             iterations = self.solver.optimize(max_iterations)
             poses = self.solver.poses()
             from .pose_graph import pose7_to_mat
@@ -212,6 +262,72 @@ class Graph:
         last = self.keyframes[-1]
         self.tf_odom2graph = last.estimate @ np.linalg.inv(last.odom)
         return loops, iterations
+
+    # ---- GPS fixes and IMU orientations as unary constraints (not in the reference) ------------------------------------------
+    def _add_priors(self, new_keyframes):
+        """The priors of a pass's new keyframes: queued until the fixes span a plane, then added -- all of them, after the graph
+        frame has been moved onto the fixes.  -> whether any prior reached the solver."""
+        if self.gps_sigma is None and self.imu_orientation_sigma is None:
+            return False
+        for kf in new_keyframes:
+            kf.gps_local = None
+            if self.gps_sigma is not None and kf.utm_coord is not None:
+                if self.utm_origin is None:
+                    self.utm_origin = kf.utm_coord.copy()
+                kf.gps_local = kf.utm_coord - self.utm_origin  # fp64, before anything reaches the solver
+            if kf.gps_local is not None or (self.imu_orientation_sigma is not None and kf.imu_quat is not None):
+                self._prior_queue.append(kf)
+        if self.gps_sigma is not None and not self.gps_aligned and not self._align_to_fixes():
+            return False
+        added = False
+        for kf in self._prior_queue:
+            if kf.gps_local is not None:
+                sxy, sz = self.gps_sigma
+                self.gps_fixes.append((kf, self.solver.add_se3_prior_xyz_edge(
+                    kf.node, kf.gps_local, np.diag([1.0 / (sxy * sxy), 1.0 / (sxy * sxy), 1.0 / (sz * sz)]),
+                    robust_kernel=self.gps_robust_kernel, robust_delta=self.gps_robust_delta)))
+                added = True
+            if self.imu_orientation_sigma is not None and kf.imu_quat is not None:
+                w = np.zeros((6, 6))
+                w[3:, 3:] = np.eye(3) * (2.0 / self.imu_orientation_sigma) ** 2
+                q = kf.imu_quat / np.linalg.norm(kf.imu_quat)
+                self.solver.add_se3_prior_pose_edge(kf.node, np.r_[0.0, 0.0, 0.0, q], w)
+                added = True
+        self._prior_queue = []
+        return added
+
+    def gps_spread(self):
+        """The second singular value of the centred fix positions of the keyframes in the graph [m]: 0 on a line."""
+        fixes = np.array([kf.gps_local for kf in self.keyframes if getattr(kf, "gps_local", None) is not None]).reshape(-1, 3)
+        if len(fixes) < 3:
+            return 0.0
+        return float(np.linalg.svd(fixes - fixes.mean(0), compute_uv=False)[1])
+
+    def _align_to_fixes(self):
+        """Once the fixes span a plane: the rigid fit of the keyframes' estimate positions to their fixes moves every estimate
+        and tf_odom2graph, and the solver is rebuilt with no fixed vertex.  -> whether that has happened."""
+        if not self.gps_spread() >= self.gps_min_spread:
+            return False
+        pairs = [(kf.estimate[:3, 3], kf.gps_local) for kf in self.keyframes if getattr(kf, "gps_local", None) is not None]
+        s, t = np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs])
+        T = rigid_fit(s, t)
+        for kf in self.keyframes:
+            kf.estimate = T @ kf.estimate
+        self.tf_odom2graph = T @ self.tf_odom2graph
+        self.solver.set_estimates([kf.estimate for kf in sorted(self.keyframes, key=lambda k: k.node)], fixed=-1)
+        self.gps_aligned = True
+        return True
+
+    def gps_weights(self):
+        """The robust weight (rho1) of every GPS prior in ``self.gps_fixes`` at the solver's current estimate; all 1 without
+        ``gps_robust_kernel``."""
+        if not self.gps_fixes:
+            return np.zeros(0)
+        return self.solver.prior_robust()["weight"][np.asarray([p for _, p in self.gps_fixes], np.int64)]
+
+    def rejected_fixes(self, threshold=0.1):
+        """The keyframes whose fix has a weight below ``threshold``.  Reporting only: nothing is removed from the graph."""
+        return [kf for (kf, _), w in zip(self.gps_fixes, self.gps_weights()) if w < threshold]
 
     def loop_weights(self):
         """The robust weight (rho1) of every entry of ``self.loops`` at the solver's current estimate, i.e. after the last

@@ -20,6 +20,8 @@ def _dp(a):
 # include/lslam_c.h: LSLAM_PG_KERNEL_*
 KERNEL_NONE, KERNEL_HUBER, KERNEL_CAUCHY, KERNEL_DCS = 0, 1, 2, 3
 _KERNEL_NAMES = {"none": KERNEL_NONE, "huber": KERNEL_HUBER, "cauchy": KERNEL_CAUCHY, "dcs": KERNEL_DCS}
+# include/lslam_c.h: LSLAM_PG_PRIOR_*
+PRIOR_XYZ, PRIOR_POSE = 0, 1
 
 
 def kernel_kind(k):
@@ -72,7 +74,9 @@ def pose7_to_mat(p):
 
 
 class PoseGraph:
-    def __init__(self, device=0):
+    def __init__(self, device=0, fixed=0):
+        """`fixed`: the vertex held at its estimate (the first, as the reference's add_se3_node); -1 holds none -- for graphs
+        whose priors fix the gauge."""
         self.lib = load_library()
         self.device = device
         self._nodes = []
@@ -81,7 +85,8 @@ class PoseGraph:
         self._info = []
         self._kind = []   # per edge: LSLAM_PG_KERNEL_* and its delta; applied by _build, so they survive a topology change
         self._delta = []
-        self.fixed = 0  # the vertex lslam_pg_create pins (g2o: setFixed); -1 pins none
+        self._priors = []  # unary constraints: dicts (vertex, type, meas (7), info (6, 6), kind, delta); applied by _build
+        self.fixed = int(fixed)  # the vertex lslam_pg_create pins (g2o: setFixed); -1 pins none
         self.h = None
         self._cb = None
         self.last_stats = None
@@ -107,6 +112,84 @@ class PoseGraph:
         self._info.append(np.asarray(information_matrix, np.float64).reshape(6, 6).copy())
         return len(self._ij) - 1
 
+    def add_se3_prior_xyz_edge(self, v, xyz, information3, robust_kernel=None, robust_delta=1.0):
+        """hdl_graph_slam's add_se3_prior_xyz_edge (not in the reference, whose keyframes only carry the utm_coord field): a
+        position fix `xyz` in the graph frame on vertex `v` with a 3x3 information matrix.  Returns the prior's index."""
+        info = np.zeros((6, 6))
+        info[:3, :3] = np.asarray(information3, np.float64).reshape(3, 3)
+        meas = np.array([*np.asarray(xyz, np.float64).reshape(3), 0.0, 0.0, 0.0, 1.0])
+        return self._add_prior(v, PRIOR_XYZ, meas, info, robust_kernel, robust_delta)
+
+    def add_se3_prior_pose_edge(self, v, pose, information6, robust_kernel=None, robust_delta=1.0):
+        """An absolute pose (4x4 or 7-vector) on vertex `v` with a 6x6 information matrix over [translation, rotation]; it
+        may be positive semi-definite only (a zero translation block: an orientation prior)."""
+        z = np.asarray(pose, np.float64)
+        meas = mat_to_pose7(z) if z.shape == (4, 4) else z.reshape(7).copy()
+        return self._add_prior(v, PRIOR_POSE, meas, np.asarray(information6, np.float64).reshape(6, 6).copy(), robust_kernel,
+                               robust_delta)
+
+    def _add_prior(self, v, type_, meas, info, robust_kernel, robust_delta):
+        kind = kernel_kind(robust_kernel)
+        self._drop()
+        self._priors.append(dict(vertex=int(v), type=int(type_), meas=meas, info=info, kind=kind, delta=float(robust_delta)))
+        return len(self._priors) - 1
+
+    @property
+    def num_priors(self):
+        return int(self.lib.lslam_pg_num_priors(self.h)) if self.h else len(self._priors)
+
+    @staticmethod
+    def _prior_list(priors):
+        """dict(vertex (n), type (n), meas (n, 7), info (n, 6, 6)[, kernels (n), deltas (n or scalar)]) or None -> list"""
+        if priors is None:
+            return []
+        vertex = np.asarray(priors["vertex"]).reshape(-1)
+        n = len(vertex)
+        type_ = np.asarray(priors["type"]).reshape(-1)
+        meas = np.asarray(priors["meas"], np.float64).reshape(n, 7)
+        info = np.asarray(priors["info"], np.float64).reshape(n, 6, 6)
+        kind, delta = PoseGraph._kernel_lists(priors.get("kernels"), priors.get("deltas"), n)
+        if len(type_) != n:
+            raise ValueError("%d prior types for %d priors" % (len(type_), n))
+        return [dict(vertex=int(vertex[p]), type=int(type_[p]), meas=meas[p].copy(), info=info[p].copy(), kind=kind[p],
+                     delta=float(delta[p])) for p in range(n)]
+
+    def set_priors(self, priors):
+        """Replace the whole set of unary constraints (lslam_pg_set_priors); None or an empty set clears.  `priors`: the dict
+        of set_graph.  Checked by the library: on an error nothing changes."""
+        new = self._prior_list(priors)
+        if self.h:
+            self._upload_priors(new)
+        self._priors = new
+
+    def prior_robust(self, poses=None):
+        """Per prior at `poses` ((n, 7); None: the current estimate): dict(e2 = e^T Omega e, rho = rho0, weight = rho1)."""
+        self._build()
+        n = len(self._priors)
+        e2, rho, w = np.zeros(n), np.zeros(n), np.zeros(n)
+        p = None
+        if poses is not None:
+            p = np.ascontiguousarray(poses, np.float64)
+            if p.shape != (len(self._nodes), 7):
+                raise ValueError("poses must be (%d, 7)" % len(self._nodes))
+        self._check(self.lib.lslam_pg_prior_robust(self.h, _dp(p) if p is not None else None, _dp(e2), _dp(rho), _dp(w)))
+        return dict(e2=e2, rho=rho, weight=w)
+
+    def _upload_priors(self, priors):
+        n = len(priors)
+        if n == 0:
+            self._check(self.lib.lslam_pg_set_priors(self.h, 0, None, None, None, None, None, None))
+            return
+        v = np.ascontiguousarray([q["vertex"] for q in priors], np.int32)
+        t = np.ascontiguousarray([q["type"] for q in priors], np.int32)
+        m = np.ascontiguousarray(np.stack([q["meas"] for q in priors]), np.float64)
+        w = np.ascontiguousarray(np.stack([q["info"] for q in priors]), np.float64)
+        k = np.ascontiguousarray([q["kind"] for q in priors], np.int32)
+        d = np.ascontiguousarray([q["delta"] for q in priors], np.float64)
+        robust = bool((k != KERNEL_NONE).any())
+        self._check(self.lib.lslam_pg_set_priors(self.h, n, v.ctypes.data_as(c_int32_p), t.ctypes.data_as(c_int32_p), _dp(m), _dp(w),
+                                                 k.ctypes.data_as(c_int32_p) if robust else None, _dp(d) if robust else None))
+
     def optimize(self, max_iterations=1000):
         """solver_g2o.cpp:79-95: graph->optimize(1000).  Returns the iteration count."""
         self._build()
@@ -116,14 +199,17 @@ class PoseGraph:
         return st.iterations
 
     # ---- bulk construction / access ---------------------------------------------------
-    def set_graph(self, poses7, ij, meas7, info, fixed=0, kernels=None, deltas=None):
-        """Replace the graph; `fixed` is the vertex held at its estimate (default: the first, as add_se3_node).  `kernels` /
-        `deltas`: per edge, as set_robust_kernels (None: plain edges)."""
+    def set_graph(self, poses7, ij, meas7, info, fixed=0, kernels=None, deltas=None, priors=None):
+        """Replace the graph; `fixed` is the vertex held at its estimate (default: the first, as add_se3_node; -1: none, for
+        graphs whose priors fix the gauge).  `kernels` / `deltas`: per edge, as set_robust_kernels (None: plain edges).
+        `priors`: None or dict(vertex (n), type (n) of PRIOR_XYZ / PRIOR_POSE, meas (n, 7), info (n, 6, 6)[, kernels, deltas])."""
+        new_priors = self._prior_list(priors)
         kind, delta = self._kernel_lists(kernels, deltas, len(np.asarray(ij).reshape(-1, 2)))  # raises before anything is dropped
         if int(fixed) >= len(np.asarray(poses7).reshape(-1, 7)):
             raise ValueError("fixed vertex %d of a graph with %d vertices" % (int(fixed), len(np.asarray(poses7).reshape(-1, 7))))
         self._drop(keep_estimates=False)
         self._kind, self._delta = kind, delta
+        self._priors = new_priors
         self._nodes = [p for p in np.asarray(poses7, np.float64).reshape(-1, 7)]
         self._ij = [tuple(int(v) for v in e) for e in np.asarray(ij).reshape(-1, 2)]
         self._meas = [m for m in np.asarray(meas7, np.float64).reshape(-1, 7)]
@@ -186,14 +272,16 @@ class PoseGraph:
 
     # ---- g2o text format (solver_g2o.cpp:97-100) -----------------------------------------
     def save(self, path):
-        """SolverG2O::save: the graph with its current estimates as a .g2o file.  The format has no place for a robust kernel:
-        none is written, and a graph loaded back has plain edges."""
+        """SolverG2O::save: the graph with its current estimates as a .g2o file, priors included (EDGE_SE3_PRIOR /
+        EDGE_SE3_PRIORXYZ lines).  The format has no place for a robust kernel: none is written, and a graph loaded back has
+        plain edges and priors."""
         self._build()
         self._check(self.lib.lslam_pg_save_g2o(self.h, str(path).encode()))
 
     @staticmethod
     def read_g2o(path, lib=None):
-        """-> dict(poses (n,7), ij (m,2), meas (m,7), info (m,6,6), fixed) from a .g2o file (host only)."""
+        """-> dict(poses (n,7), ij (m,2), meas (m,7), info (m,6,6), fixed, priors) from a .g2o file (host only); `priors` is
+        the dict set_graph takes (vertex, type, meas, info), empty arrays for a file without any."""
         from .capi import load_library
         lib = lib or load_library()
         nv, ne, fx = C.c_int32(0), C.c_int32(0), C.c_int32(-1)
@@ -208,13 +296,25 @@ class PoseGraph:
                                 ij.ctypes.data_as(c_int32_p), _dp(meas), _dp(info), C.byref(fx))
         if rc < 0:
             raise LslamError(rc, lib.lslam_pg_last_error().decode())
-        return dict(poses=poses, ij=ij, meas=meas, info=info, fixed=fx.value)
+        npr = C.c_int32(0)
+        rc = lib.lslam_g2o_read_priors(str(path).encode(), C.byref(npr), None, None, None, None)
+        if rc < 0:
+            raise LslamError(rc, lib.lslam_pg_last_error().decode())
+        pv, pt = np.zeros(npr.value, np.int32), np.zeros(npr.value, np.int32)
+        pm, pw = np.zeros((npr.value, 7)), np.zeros((npr.value, 6, 6))
+        rc = lib.lslam_g2o_read_priors(str(path).encode(), C.byref(npr), pv.ctypes.data_as(c_int32_p), pt.ctypes.data_as(c_int32_p),
+                                       _dp(pm), _dp(pw))
+        if rc < 0:
+            raise LslamError(rc, lib.lslam_pg_last_error().decode())
+        return dict(poses=poses, ij=ij, meas=meas, info=info, fixed=fx.value, priors=dict(vertex=pv, type=pt, meas=pm, info=pw))
 
     def load(self, path):
-        """Replace the graph by the one in a .g2o file; the file's FIX vertex stays the fixed one (a file without FIX: the
-        first vertex, as add_se3_node)."""
+        """Replace the graph by the one in a .g2o file, its priors included; the file's FIX vertex stays the fixed one.  A
+        file without FIX: the first vertex, as add_se3_node -- unless the file holds priors, which then fix the gauge (-1)."""
         g = PoseGraph.read_g2o(path, self.lib)
-        self.set_graph(g["poses"], g["ij"], g["meas"], g["info"], fixed=g["fixed"] if g["fixed"] >= 0 else 0)
+        has_priors = len(g["priors"]["vertex"]) > 0
+        self.set_graph(g["poses"], g["ij"], g["meas"], g["info"], fixed=g["fixed"] if g["fixed"] >= 0 or has_priors else 0,
+                       priors=g["priors"] if has_priors else None)
         return g
 
     def poses(self):
@@ -225,6 +325,19 @@ class PoseGraph:
 
     def estimate(self, v):
         return pose7_to_mat(self.poses()[v])
+
+    def set_estimates(self, poses, fixed=None):
+        """Replace every vertex's estimate (n 7-vectors or n 4x4 matrices) and, with `fixed`, the vertex held fixed (-1:
+        none); edges, kernels and priors stay.  The device graph is rebuilt by the next call that needs it."""
+        poses = [np.asarray(p, np.float64) for p in poses]
+        if len(poses) != len(self._nodes):
+            raise ValueError("%d estimates for %d vertices" % (len(poses), len(self._nodes)))
+        if fixed is not None and int(fixed) >= len(self._nodes):
+            raise ValueError("fixed vertex %d of a graph with %d vertices" % (int(fixed), len(self._nodes)))
+        self._drop(keep_estimates=False)
+        self._nodes = [mat_to_pose7(p) if p.shape == (4, 4) else p.reshape(7).copy() for p in poses]
+        if fixed is not None:
+            self.fixed = int(fixed)
 
     # ---- multi-GPU ------------------------------------------------------------------------
     def set_shard(self, e_begin, e_end, allreduce=None, system_tensor=None):
@@ -349,12 +462,14 @@ class PoseGraph:
         if rc != 0:
             raise LslamError(rc, self.lib.lslam_pg_last_error().decode())
         self.h = h
-        if any(k != KERNEL_NONE for k in self._kind):
-            try:
+        try:
+            if any(k != KERNEL_NONE for k in self._kind):
                 self._upload_kernels(self._kind, self._delta)
-            except Exception:
-                self._drop(keep_estimates=False)
-                raise
+            if self._priors:
+                self._upload_priors(self._priors)
+        except Exception:
+            self._drop(keep_estimates=False)
+            raise
 
     def close(self):
         self._drop(keep_estimates=False)
