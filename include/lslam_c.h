@@ -109,7 +109,10 @@ enum { LSLAM_AB_NO_COMPACT = 64,   /* a batch through the grid sweep: launch eve
                                       of gathered twice: 61 VGPRs and no scratch at eight wavefronts per SIMD against 72 + 36 B at
                                       seven).  Same bits.  Measured on the headline, the two taken in turn in one session: 1.466 -
                                       1.475e10 with this switch or the library before it, 1.512 - 1.517e10 without: +3.0 %
-                                      (profiles/r14_grid_lean.txt) */
+                                      (profiles/r14_grid_lean.txt).  The switch also keeps the general instantiation of the
+                                      sweep's SECOND pass (sweep_queue_kernel; the lean one: the same folding, 12-byte leaf
+                                      fetches, nothing carried in registers from work item to work item -- 80 VGPRs and no scratch at
+                                      six wavefronts per SIMD against 96 + 68 B at five; same bits, +2.5 %: profiles/r20_queue_lean.txt) */
        LSLAM_AB_GRID_CUBIC = 512,  /* grid sweep: the first pass of a throughput-bound batch that AUTO sent to the grid sweep keeps
                                       the cubic cell table instead of the x-subdivided one (each 0.6 m cell cut into S sub-cells
                                       along x, the axis the rows run along, so that a bounded probe's rows are clipped to
@@ -1337,6 +1340,9 @@ void lslam_debug_sweep_launches(lslam_ctx *ctx, uint64_t counts[8]);
 uint64_t lslam_debug_grid_launches(lslam_ctx *ctx);
 /* ... of which those that took the lean instantiation (sweep_grid_kernel<256, false, false, true>: the production loop's launch) */
 uint64_t lslam_debug_grid_lean_launches(lslam_ctx *ctx);
+/* ... of which those whose second pass took ITS lean instantiation (sweep_queue_kernel<256, true, 12, 1, true>; LSLAM_QUEUE_LEAN=0
+   in the environment a context is made in keeps the general one) */
+uint64_t lslam_debug_queue_lean_launches(lslam_ctx *ctx);
 /* ... of which those whose first pass read the x-subdivided cell tables (LSLAM_AB_GRID_CUBIC), lean or general */
 uint64_t lslam_debug_grid_fine_launches(lslam_ctx *ctx);
 /* the x-subdivided tables of the resident map: out[0], out[1] sub-cells per cell used (corner, surf; lowered where the table's

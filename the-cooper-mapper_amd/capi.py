@@ -544,6 +544,7 @@ SYMBOLS = {
     "lslam_comm_info": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),
     "lslam_debug_grid_launches": (C.c_uint64, [C.c_void_p]),
     "lslam_debug_grid_lean_launches": (C.c_uint64, [C.c_void_p]),
+    "lslam_debug_queue_lean_launches": (C.c_uint64, [C.c_void_p]),
     "lslam_debug_grid_fine_launches": (C.c_uint64, [C.c_void_p]),
     "lslam_debug_grid_fine_info": (None, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     "lslam_debug_grid_fine_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, c_int32_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32),

@@ -210,6 +210,8 @@ struct lslam_ctx {
   StereoCam st_cam{};
   uint64_t sweep_variants[SWEEP_N_VARIANTS] = {0};  // sweep launches per kernel instantiation (lslam_debug_sweep_launches)
   uint64_t grid_lean_launches = 0;                  // ... of SWEEP_VARIANT_GRID's, those that took the lean instantiation (lslam_debug_grid_lean_launches)
+  uint64_t queue_lean_launches = 0;                 // ... and those whose second pass took its lean instantiation (lslam_debug_queue_lean_launches)
+  bool env_queue_lean = true;                       // LSLAM_QUEUE_LEAN=0: the second pass keeps the general kernel where the first is lean (to measure it alone)
   // cell grids over the whole-map trees (lslam_grid.hpp), built the first time the grid search is asked for on a map
   GridDev kc, ks;
   uint64_t map_epoch = 0;      // bumped whenever the resident trees change
@@ -470,7 +472,7 @@ bool ab_switches_known(int32_t ab, const char *where) {
 // launch_sweep + the per-context count of the instantiation it took
 // fine: the grid sweep's first pass reads the x-subdivided tables (ctx->kfc / kfs, which the caller has ensured); every other
 // launch of the sweep -- the second pass, its probes -- keeps a's cubic tables
-// general: the grid sweep's first pass through the general instantiation even where the lean one would do (LSLAM_AB_GRID_GENERAL)
+// general: both passes of the grid sweep through the general instantiations even where the lean ones would do (LSLAM_AB_GRID_GENERAL)
 hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, bool general, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
                         bool fine = false) {
   const CertPlan plan = make_cert_plan(ctx);
@@ -499,12 +501,15 @@ hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, bool g
       if (e != hipSuccess) return e;
     }
     const int pass2 = a.stack_ovf ? (a.deep_tree ? SWEEP_VARIANT_DEEP_OVF : SWEEP_VARIANT_SHALLOW) : SWEEP_VARIANT_DEEP;
+    // the sweep's one decision holds for its second pass: lean where the first was, over the shallow stack (the production loop's)
+    const bool lean2 = lean && ctx->env_queue_lean && pass2 == SWEEP_VARIANT_SHALLOW && grid_queue_lean_ok(a, jtj_mode);
 #ifdef LSLAM_EXP_NO_PASS2  // TIMING EXPERIMENT ONLY (wrong results): the listed points are dropped -- what the second pass costs
     if (e1) return hipEventRecord(e1, ctx->stream);
     return hipSuccess;
 #endif
-    e = launch_sweep_queue(a, jtj_mode, ctx->stream, e1, pass2, plan, planned);
+    e = launch_sweep_queue(a, jtj_mode, ctx->stream, e1, pass2, plan, planned, lean2);
     ctx->queue_launches++;
+    if (lean2) ctx->queue_lean_launches++;
     return e;
   }
   // certificate sweep: from the second sweep of a loop a second launch searches the points pass 1 listed (sweep_body); the
@@ -669,6 +674,7 @@ int lslam_ctx_create(int device, lslam_ctx **out) {
   if (const char *v = std::getenv("LSLAM_GRID_CELL")) ctx->env_grid_cell = (float)std::atof(v);
   if (const char *v = std::getenv("LSLAM_GRID_CELL_CORNER")) ctx->env_grid_cell_corner = (float)std::atof(v);
   if (const char *v = std::getenv("LSLAM_GRID_XSUB")) ctx->env_grid_xsub = std::max(1, std::min(std::atoi(v), GRID_MAX_XSUB));
+  if (const char *v = std::getenv("LSLAM_QUEUE_LEAN")) ctx->env_queue_lean = std::atoi(v) != 0;
   if (const char *v = std::getenv("LSLAM_DEBUG_CERT_STATS")) ctx->env_debug_cert_stats = std::atoi(v);
   if (const char *v = std::getenv("LSLAM_FORCE_STACK")) {
     if (!std::strcmp(v, "deep")) ctx->env_force_stack = SWEEP_STACK_DEEP;
@@ -761,6 +767,7 @@ void lslam_debug_lazy_trees(lslam_ctx *ctx, uint64_t out[3]) {
 
 uint64_t lslam_debug_grid_launches(lslam_ctx *ctx) { return ctx ? ctx->sweep_variants[SWEEP_VARIANT_GRID] : 0; }
 uint64_t lslam_debug_grid_lean_launches(lslam_ctx *ctx) { return ctx ? ctx->grid_lean_launches : 0; }
+uint64_t lslam_debug_queue_lean_launches(lslam_ctx *ctx) { return ctx ? ctx->queue_lean_launches : 0; }
 uint64_t lslam_debug_grid_fine_launches(lslam_ctx *ctx) { return ctx ? ctx->grid_fine_launches : 0; }
 void lslam_debug_grid_fine_info(lslam_ctx *ctx, uint64_t out[4], float *build_ms) {
   const bool have = ctx && ctx->kfc.view.cell_start && ctx->kfs.view.cell_start;

@@ -72,6 +72,7 @@ constexpr int KD_STACK_MAX = 64;  // host refuses deeper trees (LSLAM_ERR_TREE_D
 #define LSLAM_PK_DIST 0  // 1: x / y differences and squares as packed fp32 operations -- measured no faster (A/B switch)
 #endif
 typedef float lslam_f2 __attribute__((ext_vector_type(2)));
+struct alignas(16) f32x3_ld { float x, y, z; };  // the first twelve bytes of a float4 (one global_load_dwordx3)
 LSLAM_DEV float dist2_xyz(float qx, float qy, float qz, const float4 &p) {
 #if LSLAM_PK_DIST
   // the x and y differences and squares as PACKED fp32 operations (v_pk_add_f32 / v_pk_mul_f32: two IEEE fp32 results
@@ -231,7 +232,9 @@ struct TravStats { unsigned long long t_desc, t_leaf, t_pop, t_take; unsigned n_
 #endif
 // POPW_SET: stack entries examined per pop round, 0 = by the stack's shape (below).  The grid sweep's second pass asks for one:
 // its searches start from a bound and seldom pop more (1.403 -> 1.417e10, round 6).
-template <int BLOCK, bool OVF, int LDS_DEPTH, bool TRACK = false, int POPW_SET = 0>
+// XYZ: the leaf fetches 12 bytes per slot, not 16 -- the distances read x, y and z, the w word (the point's original index) is
+// for the caller's taps: thirty registers in flight per leaf instead of forty.  Same loads of the same words otherwise.
+template <int BLOCK, bool OVF, int LDS_DEPTH, bool TRACK = false, int POPW_SET = 0, bool XYZ = false>
 LSLAM_DEV void knn5_search(const TreeView &T, float qx, float qy, float qz, float (&d)[5],
                            int (&p)[5], KdStack<BLOCK, OVF, LDS_DEPTH> &stk,
 #ifdef LSLAM_TRAVERSAL_STATS
@@ -305,8 +308,16 @@ LSLAM_DEV void knn5_search(const TreeView &T, float qx, float qy, float qz, floa
       const float worst = fminf(d[4], bound);  // worst_dist cached once per leaf
       // all of the leaf's loads are issued before any distance is evaluated
       float4 pt[10];
+      if constexpr (XYZ) {
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+          const f32x3_ld v = *reinterpret_cast<const f32x3_ld *>(T.pts + l + j);
+          pt[j] = make_float4(v.x, v.y, v.z, 0.0f);
+        }
+      } else {
 #pragma unroll
       for (int j = 0; j < 10; ++j) pt[j] = T.pts[l + j];
+      }
 #if LSLAM_LEAF_COMPACT
       // A/B switch (round 3): the cheap accept test on all ten slots first, then the sorted insert only for the ACCEPTED
       // candidates -- a lane accepts 5-8 of the ~44 candidates it is offered in a sweep, the straight-line form below pays

@@ -286,6 +286,16 @@ enum : int {
 inline bool grid_sweep_lean_ok(const SweepArgs &a, int jtj_mode) {
   return jtj_mode == 1 && !a.flags_out && !a.coeff_out && !a.idx_out && a.fine_gate_c < 0.0f && a.bounded && !a.cert_stats;
 }
+// ... and its second pass over the trees, sweep_queue_kernel<256, true, 12, 1, true>: the same launch, with no clocks asked for
+// and no prev_lb (a grid sweep never has one: the array is its grid_hint; the lean kernel has no store to it).  The profiling
+// build with traversal counters keeps the general kernel, whose search it instruments.
+inline bool grid_queue_lean_ok(const SweepArgs &a, int jtj_mode) {
+#ifdef LSLAM_TRAVERSAL_STATS
+  return false;
+#else
+  return grid_sweep_lean_ok(a, jtj_mode) && a.grid == 1 && !a.dbg && !a.prev_lb && a.stack_ovf && !a.deep_tree;
+#endif
+}
 // fine: a.kc / a.ks are x-subdivided tables (CellGrid::xsub); sweep_grid_kernel<.., FINE>, lean or general
 hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool lean = false, bool fine = false);
 hipError_t launch_sweep_wide(const SweepArgs &a, hipStream_t s);  // sweep_wide_kernel (its prefix: launch_sweep_plan with_prefix)
@@ -316,7 +326,8 @@ hipError_t launch_compact_active(const GNState *states, const ProbBlocks *probs,
 // (running_out, or null: 1 when a scan of the chunk is still running, 0 otherwise -- with the stereo term a running scan may have
 // no LiDAR workgroups at all, so count_out = 0 does not mean that the chunk's loops are over)
 hipError_t launch_sweep_plan(const SweepArgs &a, hipStream_t s, const CertPlan &plan, bool with_prefix);
-hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, bool planned = false);
+hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, bool planned = false,
+                              bool lean = false);  // lean: the grid sweep's second pass through its lean instantiation (grid_queue_lean_ok)
 hipError_t launch_sweep(const SweepArgs &a, int jtj_mode, hipStream_t s,
                         hipEvent_t start = nullptr, hipEvent_t stop = nullptr, int *variant = nullptr, bool *cert_launched = nullptr);
 hipError_t launch_solve(const SolveArgs &a, hipStream_t s);

@@ -64,13 +64,18 @@ __device__ unsigned long long g_pass2_hist[8];  // listed points by the bound th
 // hands over, no certificate bookkeeping); 2 = the grid sweep's on a map without trees (neighbours given by sweep_wide_kernel).
 // A template argument, not a run-time flag: each second pass is compiled without the others' search code (the one kernel for
 // all three needed 96 VGPRs + 92 bytes of scratch per lane).
-template <int BLOCK, bool OVF, bool CUBES, int LDS_DEPTH, bool PACKET, int CERT = 0, int GRIDQ = 0>
+// LEAN (with GRIDQ = 1): the production loop's second pass (sweep_queue_kernel<.., LEAN>) -- the caller hands over `a` and
+// jtj_mode with what such a launch never does as constants; here the search reads 12 bytes per leaf slot and nothing is clocked.
+template <int BLOCK, bool OVF, bool CUBES, int LDS_DEPTH, bool PACKET, int CERT = 0, int GRIDQ = 0, bool LEAN = false>
 LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, const BlockDesc &bd, const GNState *st,
                           uint32_t *stack_lds, float (*red)[NCOL], float *partial_out, const int prev_valid, const int q_item = -1) {
   constexpr int NWAVE = BLOCK / 64;
   static_assert(2 * LDS_DEPTH >= 8, "staging needs eight word rows of the stack");
+  static_assert(!LEAN || (CERT == 2 && GRIDQ == 1 && !PACKET && !CUBES), "LEAN is the grid sweep's second pass over whole-map trees");
 
-  const int tid = threadIdx.x;
+  int tid_v = threadIdx.x;
+  if constexpr (LEAN) asm volatile("" : "+v"(tid_v));  // (see sweep_queue_kernel)
+  const int tid = tid_v;
   const int lane = tid & 63, wave = tid >> 6;
   const uint64_t dbg_t0 = a.dbg ? __builtin_readcyclecounter() : 0;
   uint64_t dbg_t1 = 0, dbg_t2 = 0;
@@ -382,10 +387,11 @@ LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, 
           knn5_search<BLOCK, OVF, LDS_DEPTH>(T, sel[0], sel[1], sel[2], d, p, stk, bound);
       } else
 #endif
-      knn5_search<BLOCK, OVF, LDS_DEPTH, false, (GRIDQ == 1 && LDS_DEPTH <= 16) ? 1 : 0>(T, sel[0], sel[1], sel[2], d, p, stk, bound);
+      knn5_search<BLOCK, OVF, LDS_DEPTH, false, (GRIDQ == 1 && LDS_DEPTH <= 16) ? 1 : 0, LEAN>(T, sel[0], sel[1], sel[2], d, p, stk, bound);
       // no bound kept: no certificate for this point in the next sweep (the first sweep of a certificate loop is this kernel
       // WITHOUT the certificate code -- launch_sweep -- which is 4 % faster at searching than the one with it)
-      if ((CERT || !CUBES) && a.prev_lb) a.prev_lb[qi] = 0.0f;
+      // (LEAN: a grid sweep is launched with prev_lb null -- the array is its grid_hint -- which launch_sweep_queue checks)
+      if (!LEAN && (CERT || !CUBES) && a.prev_lb) a.prev_lb[qi] = 0.0f;
     }
     if (grid) {
       if (a.bounded) a.prev_q[qi] = make_float4(sel[0], sel[1], sel[2], (p[4] >= 0 && d[4] < 5.0f) ? d[4] : FLT_MAX);
@@ -404,7 +410,7 @@ LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, 
   }
 
   if (a.dbg) dbg_t2 = __builtin_readcyclecounter();
-  block_accumulate<BLOCK, CERT == 2>(jtj_mode, is_surf, row, rb, kept, matched, score, stack_lds, red, partial_out);
+  block_accumulate<BLOCK, CERT == 2, 0, LEAN>(jtj_mode, is_surf, row, rb, kept, matched, score, stack_lds, red, partial_out);
   if (a.dbg && lane == 0) {  // per-wave phase stamps (shader clock)
     uint64_t *o = a.dbg + ((size_t)lb * NWAVE + wave) * 4;
     o[0] = dbg_t0;
@@ -557,8 +563,18 @@ __global__ __launch_bounds__(256) void cert_plan_kernel(SweepArgs a, CertPlan pl
 // -- as many as the sweep itself has, nearly all of them leaving at once -- cost 0.25 ms per launch, more than the last
 // sweeps of a batch themselves.  The argument block is re-read through a laundered pointer in every turn: left to itself the
 // compiler carries the sweep's invariants across the loop in registers it does not have (124 bytes of scratch per lane).
-template <int BLOCK, bool OVF, int LDS_DEPTH, int GRIDQ = 0>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LDS_DEPTH <= 16 ? LSLAM_SHALLOW_OCC : 2))) void sweep_queue_kernel(const SweepArgs a_in, const int jtj_mode_in, const CertPlan plan) {
+// LEAN: the instantiation of the production loop's grid sweep (grid_queue_lean_ok: what grid_sweep_lean_ok asks of pass 1, no
+// clocks, no prev_lb) -- the same statements with what such a launch never does folded away at compile time, as
+// sweep_grid_kernel<.., LEAN> has it: the general kernel budgets registers for the shuffle path's 31 accumulators, the taps, the
+// _fineScore gate and the clocks through the whole item loop (68 bytes of scratch per lane, 107 scalar registers spilled).
+// Same operations on the same values: same bits (LSLAM_AB_GRID_GENERAL or LSLAM_QUEUE_LEAN=0 bring the general kernel back;
+// DESIGN 4 has the numbers).
+#ifndef LSLAM_QUEUE_LEAN_OCC
+#define LSLAM_QUEUE_LEAN_OCC 6  // wavefronts per SIMD the lean second pass is compiled for, and workgroups per CU its launch asks for: 80 VGPRs without scratch (5: 82 VGPRs, none either; six workgroups of 26 144 B fit a CU's 160 KB of LDS, seven do not).  The headline, the parent / 5 / 6 taken in turn five times: 1.525 - 1.546 / 1.549 - 1.564 / 1.569 - 1.585e10, medians +1.1 % and +2.5 % ("The lean instantiation of pass 2")
+#endif
+template <int BLOCK, bool OVF, int LDS_DEPTH, int GRIDQ = 0, bool LEAN = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LEAN ? LSLAM_QUEUE_LEAN_OCC : (LDS_DEPTH <= 16 ? LSLAM_SHALLOW_OCC : 2)))) void sweep_queue_kernel(const SweepArgs a_in, const int jtj_mode_in, const CertPlan plan) {
+  static_assert(!LEAN || GRIDQ == 1, "LEAN is an instantiation of the grid sweep's second pass over trees");
   __shared__ float red[BLOCK / 64][NCOL];
   __shared__ uint32_t stack_lds[2 * LDS_DEPTH * BLOCK];
   __shared__ int next_w;
@@ -571,11 +587,31 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LDS_DEPTH
     __syncthreads();
     const int w = __builtin_amdgcn_readfirstlane(next_w);
     if (w >= n_work) break;
+    // LEAN: the thread's number is laundered in every turn, here and where sweep_body and block_accumulate take it: what depends
+    // on nothing else -- the scan's and the sums' shuffle lanes, the MFMA scatter's places -- is then worked out where it is
+    // used, not once before the loop and kept in (or spilled from) registers through every search
+    int tid_k = (int)threadIdx.x;
+    if constexpr (LEAN) asm volatile("" : "+v"(tid_k));
     SweepArgs a = a_in;
     int jtj_mode = jtj_mode_in;
+    if constexpr (LEAN) {  // what launch_sweep_queue has checked, as constants; the fields the item touches laundered as below
+      jtj_mode = 1;
+      a.flags_out = nullptr;
+      a.coeff_out = nullptr;
+      a.idx_out = nullptr;
+      a.fine_gate_c = -1.0f;
+      a.bounded = 1;
+      a.cert_stats = nullptr;
+      a.dbg = nullptr;
+      a.prev_lb = nullptr;
+      asm volatile("" : "+s"(a.q), "+s"(a.blocks), "+s"(a.states), "+s"(a.partials), "+s"(a.prev_q));
+      asm volatile("" : "+s"(a.tc.nodes), "+s"(a.tc.pts), "+s"(a.ts.nodes), "+s"(a.ts.pts), "+s"(a.stack_ovf), "+s"(a.need_list), "+s"(a.need_cnt), "+s"(a.groups));
+      asm volatile("" : "+s"(a.grid_hint));
+    } else {
     asm volatile("" : "+s"(a.q), "+s"(a.blocks), "+s"(a.states), "+s"(a.partials), "+s"(a.prev_nb), "+s"(a.prev_q), "+s"(a.prev_lb), "+s"(jtj_mode));
     asm volatile("" : "+s"(a.tc.nodes), "+s"(a.tc.pts), "+s"(a.ts.nodes), "+s"(a.ts.pts), "+s"(a.stack_ovf), "+s"(a.need_list), "+s"(a.need_cnt), "+s"(a.groups));
     asm volatile("" : "+s"(a.spare0), "+s"(a.spare1), "+s"(a.grid_hint));  // (spare0 / spare1: see SweepArgs)
+    }
     const int item_id = __builtin_amdgcn_readfirstlane(plan.work[w]);
     const int g = item_id / CERT_GROUP, c = item_id % CERT_GROUP;
     GroupDesc gd = a.groups[g];
@@ -588,7 +624,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LDS_DEPTH
     // sixty-four -- the grid sweep lists 1 - 3 % of a workgroup's points, and an item is a workgroup's worth of lanes -- it is not)
     static_assert(CERT_GROUP <= BLOCK && (CERT_GROUP & (CERT_GROUP - 1)) == 0, "one list length per thread; the search below halves");
     {
-      const int k = (int)threadIdx.x, ln = k & 63, wv = k >> 6;
+      const int k = tid_k, ln = k & 63, wv = k >> 6;
       int run = k < gd.n_blocks ? (int)a.need_cnt[fb + k] : 0;
 #pragma unroll
       for (int o = 1; o < 64; o <<= 1) {
@@ -611,7 +647,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LDS_DEPTH
     bd.is_surf = __builtin_amdgcn_readfirstlane(bd.is_surf);
     bd.out_base = __builtin_amdgcn_readfirstlane(bd.out_base);
     GNState *st = const_cast<GNState *>(a.states) + gd.prob;
-    const int i = c * BLOCK + (int)threadIdx.x;
+    const int i = c * BLOCK + tid_k;
     int item = -1;
     if (i < total) {
       int k = 0;  // the last workgroup whose list begins at or before entry i
@@ -621,7 +657,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LDS_DEPTH
       const int p0 = pre_lds[k];
       item = a.blocks[fb + k].first + (int)a.need_list[(size_t)(fb + k) * BLOCK + (i - p0)];
     }
-    sweep_body<BLOCK, OVF, false, LDS_DEPTH, false, 2, GRIDQ>(a, jtj_mode, fb + c, bd, st, stack_lds, red, a.partials + (size_t)(fb + c) * NCOL, a.prev_valid, item);  // (the certificate sweep's second pass only runs with prev_valid set; the grid sweep's runs in a loop's first sweep too)
+    sweep_body<BLOCK, OVF, false, LDS_DEPTH, false, 2, GRIDQ, LEAN>(a, jtj_mode, fb + c, bd, st, stack_lds, red, a.partials + (size_t)(fb + c) * NCOL, a.prev_valid, item);  // (the certificate sweep's second pass only runs with prev_valid set; the grid sweep's runs in a loop's first sweep too)
     __syncthreads();  // red and the stack columns are free again
   }
 }
@@ -693,16 +729,21 @@ hipError_t launch_sweep_plan(const SweepArgs &a, hipStream_t s, const CertPlan &
   return hipGetLastError();
 }
 
-hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, bool planned) {
+hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, bool planned, bool lean) {
   if (a.n_groups <= 0) return hipSuccess;
+  // (the lean kernel would compute something else; it exists for the shallow stack, the production loop's, only)
+  if (lean && !(grid_queue_lean_ok(a, jtj_mode) && variant == SWEEP_VARIANT_SHALLOW)) return hipErrorInvalidValue;
   if (!planned) hipLaunchKernelGGL(cert_plan_kernel, dim3((a.n_groups + 3) / 4), dim3(256), 0, s, a, plan, 0);
-  // as many workgroups as stay resident (256 CUs x five of the shallow kernel, two of the deep ones), never more than items possible
+  // as many workgroups as stay resident (256 CUs x five of the shallow kernel, six of its lean instantiation, two of the deep ones), never more than items possible
   constexpr int SHALLOW = LSLAM_SHALLOW_DEPTH;
   const long possible = a.active_blocks ? std::max<long>(a.n_active, 1) : (long)a.nb_total;  // (a work item is at most one per pass-1 workgroup that ran)
   const dim3 b(SWEEP_BLOCK);
   if (a.grid == 2) {  // neighbours given (a map without trees): no search, no stack -- the shallow shape's LDS is plenty
     const dim3 g((unsigned)std::min<long>(possible, 256 * 5));
     hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 2>), g, b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
+  } else if (lean) {
+    const dim3 g((unsigned)std::min<long>(possible, 256 * LSLAM_QUEUE_LEAN_OCC));
+    hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 1, true>), g, b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
   } else if (variant == SWEEP_VARIANT_SHALLOW) {
     const dim3 g((unsigned)std::min<long>(possible, 256 * 5));
     if (a.grid) hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 1>), g, b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);

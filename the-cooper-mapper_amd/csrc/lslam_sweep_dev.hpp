@@ -129,11 +129,15 @@ LSLAM_DEV void point_residual(const SweepArgs &a, const BlockDesc &bd, const boo
 // with PAD = 4 the 32 words of a step lie in 32 banks.  Same words to the same lanes: same bits.  Only for a caller whose `stage`
 // is free of other wavefronts' data (a padded row reaches into the neighbouring wavefronts' columns): the grid sweep, behind
 // its workgroup barrier; the tree sweeps stage in the columns of their own traversal stacks, without one.
-template <int BLOCK, bool ADD, int PAD = 0>
+// FRESH_TID: the thread's number is laundered here, so that nothing worked out from it alone is hoisted out of a caller's loop
+// over work items and kept in registers through the searches (sweep_queue_kernel<.., LEAN>).
+template <int BLOCK, bool ADD, int PAD = 0, bool FRESH_TID = false>
 LSLAM_DEV void block_accumulate(const int jtj_mode, const bool is_surf, const float (&row)[6], const float rb, const float kept,
                                 const float matched, const float score, uint32_t *stage, float (*red)[NCOL], float *partial_out) {
   constexpr int NWAVE = BLOCK / 64;
-  const int tid = threadIdx.x;
+  int tid_v = threadIdx.x;
+  if constexpr (FRESH_TID) asm volatile("" : "+v"(tid_v));
+  const int tid = tid_v;
   const int lane = tid & 63, wave = tid >> 6;
   // ---- normal equations: per-wave reduction --------------------------------
   float v[NCOL];

@@ -148,6 +148,10 @@ class Context:
         """lslam_debug_grid_lean_launches: ... of which with the lean instantiation (the production loop's launch)."""
         return int(self.lib.lslam_debug_grid_lean_launches(self.h))
 
+    def queue_lean_launches(self):
+        """lslam_debug_queue_lean_launches: ... of which with the lean instantiation of the second pass as well."""
+        return int(self.lib.lslam_debug_queue_lean_launches(self.h))
+
     def grid_fine_launches(self):
         """lslam_debug_grid_fine_launches: ... of which with the first pass over the x-subdivided cell tables."""
         return int(self.lib.lslam_debug_grid_fine_launches(self.h))
