@@ -14,14 +14,17 @@ Per step of a family (launch loop, path 0):
                    4 x the family's conditioning (odom_ref.COEFF_COND) of coeff64
   sums             each of the 27 within K_ODOM = 34 units of sums64_odom built from the device's taps; the three counters exact
   solve            pose and x after the step bit for bit oracle.gn_step's on the device's sums rounded to float32 (the solve
-                   consumes the float64 totals through exactly that rounding: solve_finish's (float)tot[k])
+                   consumes the float64 totals through exactly that rounding: solve_finish's (float)tot[k]); on a step the
+                   eigenvalue test (threshold 10) calls degenerate -- the first step of seven families, DEGENERATE_AT_0 -- x
+                   and the pose within K_X units of the plain solve's error (tests/degenerate_ref.py) and converged equal
 and, where the persistent kernel can be held to one generation (iter 4, 9, 24; at most 64 blocks), path 1's indices, sums and
 state bit for bit path 0's.
 
 Measured on an MI355X, largest over the 26 families and their iterations (each test prints its own): no index and no tie flag
 differs; sel 3.21 units (bound 29); coefficients and kept flags equal the oracle's bits everywhere, and lie within the
 family's recorded conditioning of coeff64 (bar: 4 x that); sums 3.15 units (the single flat row of ragged_0_1; 0.2 - 1.8
-on the families with sums of many rows; K_ODOM = 34); pose and x equal oracle.gn_step's bits on every non-degenerate step.
+on the families with sums of many rows; K_ODOM = 34); pose and x equal oracle.gn_step's bits on every non-degenerate step,
+and differ from them by 0 on the seven degenerate first steps as well (bar: K_X = 17.45 units).
 The ring-table fallback ran on 100 % of the sparse family's queries, the coarse level on 51 % of the large pose's and on all
 of the 10 km family's; at 50 km no query saw a grid candidate.  Loop level, 16 and 64 rings x 1800: two sweeps converge (1 and
 6 iterations) and four run to 25 iterations per ring count; counts equal, |dt| <= 4.8e-7 m and |dr| <= 1.4e-8 rad on every
@@ -33,6 +36,7 @@ import os
 import numpy as np
 import pytest
 
+import degenerate_ref as D
 import odom_ref as O
 import scanmatch_ref as R
 
@@ -52,6 +56,13 @@ FAMILY_NAMES = ["ragged_%d_%d" % c for c in O.RAGGED] + [
     "q5_few_sharp", "q5_more_sharp_than_cloud", "guard_edge", "pose_zero", "pose_drive", "pose_large", "reltime_0", "reltime_0999",
     "rings_64", "empty_rings", "rings_0_to_255", "not_ring_order", "rings_above_255", "sparse_2_to_4.9m", "walk_ties", "far_3km",
     "far_10km", "far_50km"]
+
+
+# families whose first step has an eigenvalue below 10 (tests/odom_ref.py's references say so without a device: few or thin
+# clouds, the lattice of walk_ties, and the far families, whose float32 sums are singular) -- where check_step holds the
+# projected step
+DEGENERATE_AT_0 = {"q5_few_sharp", "guard_edge", "not_ring_order", "walk_ties", "far_3km", "far_10km", "far_50km"}
+DEGENERATE_STEPS = {}
 
 
 class Node:
@@ -120,6 +131,7 @@ def check_step(oracle, f, it, st, label):
     un = R.units(sums, S, u)
     assert un.max() <= O.K_ODOM, (label, "entry %d: %.1f units > %.0f" % (un.argmax(), un.max(), O.K_ODOM), un.round(1).tolist())
     # solve
+    degenerate, deg_units = False, 0.0
     if n_rows < 10:  # :501-503: the iteration is skipped, the counter moves on
         assert np.array_equal(bits(st["pose"]), bits(f["pose"])) and st["loop_iter"] == it + 1 and st["solves"] == 0
     else:
@@ -134,7 +146,22 @@ def check_step(oracle, f, it, st, label):
             assert np.array_equal(bits(st["x"]), bits(g["x"])), (label, st["x"], g["x"])
             assert np.array_equal(bits(st["pose"]), bits(g["pose"])), (label, st["pose"], g["pose"])
             assert bool(st["converged"]) == g["converged"]
-    return dict(sel=su, coeff=cd, sums=un.max(), rows=n_rows)
+        elif it == 0:
+            # the projected step (LaserOdometry.cpp:583-614, threshold 10): nothing pins the device's eigenvectors to the
+            # oracle's bit for bit, so x and the pose are held within K_X units of the plain solve's error
+            # (tests/degenerate_ref.py; measured: no difference at all); the pose is one float32 addition more.  The unit
+            # grows with cond(A): on the far families, whose float32 sums are singular, only the decision and converged bind
+            degenerate = True
+            ux = D.unit_x_of(AtA, s32[21:27])
+            dx = float(np.abs(st["x"].astype(np.float64) - g["x"]).max())
+            dp = float(np.abs(st["pose"].astype(np.float64) - g["pose"]).max())
+            deg_units = dx / ux if ux > 0 else (0.0 if dx == 0 else np.inf)
+            print("%s: degenerate step, |x - oracle| %.3g = %.3g units (K_X %.2f, cond %.3g)" % (
+                label, dx, deg_units, D.K_X, np.linalg.cond(AtA.astype(np.float64))))
+            assert dx <= D.K_X * ux, (label, st["x"], g["x"], ux)
+            assert dp <= D.K_X * ux + 2 * D.EPS32 * float(np.abs(g["pose"]).max()), (label, st["pose"], g["pose"], ux)
+            assert bool(st["converged"]) == g["converged"], label
+    return dict(sel=su, coeff=cd, sums=un.max(), rows=n_rows, degenerate=degenerate, deg_units=deg_units)
 
 
 @pytest.mark.parametrize("name", FAMILY_NAMES)
@@ -153,6 +180,12 @@ def test_one_step_against_the_references(pkg, ctx, oracle, fams, name):
         label = "%s iter %d" % (name, it)
         st = dev.debug_step(node.fs, f["pose"], it, path=0, refresh=True)
         m = check_step(oracle, f, it, st, label)
+        if it == 0:
+            DEGENERATE_STEPS[name] = m["degenerate"]
+            print("degenerate first steps so far: %d of %d families (%s)" % (sum(DEGENERATE_STEPS.values()), len(DEGENERATE_STEPS),
+                                                                          ", ".join(k for k, v in DEGENERATE_STEPS.items() if v)))
+            # (reference side: the oracle's decision on the device's sums) the families whose first step is projected
+            assert m["degenerate"] == (name in DEGENERATE_AT_0), (name, m["degenerate"])
         prof = dev.search_profile(ns + nf)
         assert len(prof) == ns + nf
         print("%-32s rows %5d  sel %.2f units  coeff %.3g (bar %.3g)  sums %.2f units (K %.0f)  coarse %.0f%%  ring table %.0f%%" % (

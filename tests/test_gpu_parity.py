@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+import degenerate_ref as D
 import scanmatch_ref
 
 pytestmark = pytest.mark.gpu
@@ -332,6 +333,19 @@ def test_gn_step_degenerate_projection(ctx, oracle):
     assert o["degenerate"] and g["degenerate"]
     assert np.abs(g["matP"] - o["matP"]).max() < 1e-4
     assert np.abs(g["x"] - o["x"]).max() < 1e-5 + 1e-4 * np.abs(o["x"]).max()
+    # matP against its float64 statement (tests/degenerate_ref.py): one of the 32 sign variants of V^T diag(0, 1..1) V, the one
+    # the oracle's is nearest to, within K_P units; the next variant is more than ten times K_P away, so the reading is unambiguous
+    s = D.step64(AtA, Atb, 0, pose, g["matP"], False, 100.0)
+    so = D.step64(AtA, Atb, 0, pose, o["matP"], False, 100.0)
+    unit = D.unit_P(s["E"])
+    print("matP: %.3f units from the nearest member (oracle %.3f), the next one %.0f units away" % (s["dist"][0] / unit, so["dist"][0] / unit, s["dist"][1] / unit))
+    assert s["k"] == 1 and s["dist"][1] >= 10 * D.K_P * unit
+    assert s["dist"][0] <= D.K_P * unit and so["dist"][0] <= D.K_P * unit and s["member"] == so["member"]
+    # x is matP times the plain solve's bits, to the bound of a six-term float32 dot product per component
+    plain = ctx.gn_step(AtA, Atb, 1, pose, np.zeros(36), False)
+    assert not plain["degenerate"]
+    want, bound = D.dot6_bound(g["matP"], plain["x"])
+    assert (np.abs(g["x"] - want) <= bound).all(), (g["x"], want, bound)
 
 
 @pytest.mark.parametrize("search", ["lane", "lane_shallow", "packet"])

@@ -324,8 +324,10 @@ __device__ static void gn_step_block(GNState *st, GnShared &sh, float eig_thresh
   const float dR = (float)sqrt(r0 * r0 + r1 * r1 + r2 * r2);
   const double t0 = (double)(x[3] * 100), t1 = (double)(x[4] * 100), t2 = (double)(x[5] * 100);
   const float dT = (float)sqrt(t0 * t0 + t1 * t1 + t2 * t2);
-  // next rotation: lanes 0..2 half angles, 3..5 full angles (the host uses
-  // std::sin/std::cos(float); the double-precision functions rounded to float agree)
+  // next rotation: lanes 0..2 half angles, 3..5 full angles (the host uses std::sin/std::cos(float), which are good to
+  // 0.56 ulp and not correctly rounded: the double-precision functions rounded to float are the other neighbour of the exact
+  // value at a few angles in a thousand, so a tap at a pose the loop returned may sweep with a rotation one ulp off the
+  // loop's own -- tests/test_gpu_degenerate.py says which poses)
   const int ai = lane < 3 ? lane : (lane < 6 ? lane - 3 : 0);
   float ang = ai == 0 ? pose[0] : (ai == 1 ? pose[1] : pose[2]);
   if (lane < 3) ang = 0.5f * ang;
