@@ -218,6 +218,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed; new entry points and a struct of their own (lslam_match_information, lslam_keyframe_edge_information, lslam_sizeof_edge_info: the match Hessian of a pose-graph edge). */
 /* still 7: no struct changed, no entry point gone; six LSLAM_AB_* names retired (bits 1, 2, 4, 8, 32, 128: refused from here on, see lslam_opts.ab_switches). */
 /* still 7: no struct changed; new entry points and an enum (lslam_pg_set_priors, _num_priors, _prior_robust, lslam_g2o_read_priors: unary constraints on pose-graph vertices). */
+/* still 7: no struct changed; new entry points and structs of their own (lslam_floor_*, lslam_debug_floor_hypotheses: floor detection; lslam_pg_set_plane_priors, _num_plane_priors, _plane_prior_robust, lslam_g2o_read_plane_priors: plane priors). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -628,6 +629,85 @@ int lslam_kfs_scanmatch(lslam_kfs *kfs, int32_t id, float leaf_corner, float lea
                         lslam_stats *stats);
 /* lslam_fmap_add_feature_cloud with the keyframe's clouds taken from the store (fm: a feature map of the store's ctx). */
 int lslam_kfs_add_to_fmap(lslam_kfs *kfs, int32_t id, lslam_fmap *fm, const float T[16]);
+
+/* ---- floor detection: the ground plane of a cloud, found on the device --------------------------------------------------------
+ * The reference shows the intent and stops there: pose_graph/solver_g2o.h:61-65 has add_plane_node commented out, :92 a
+ * commented floor_plane_node, :42 includes g2o's plane types, and graph.cpp:321 speaks of "floor coeffs in the queues" -- nothing
+ * there detects a floor.  The module is modelled on hdl_graph_slam, whose floor detector is a height clip and a PCL RANSAC.
+ * Neither hdl_graph_slam nor PCL is under the reference, so PARITY IS UNPINNED like the rest of the pose-graph node; the
+ * semantics below are this project's own, stated completely, so that an independent reference reproduces every integer
+ * decision exactly.  All fp32 expressions are evaluated as written, without FMA contraction (the convention of
+ * lslam_kfs_debug_local_clouds).  u is `up` normalised in fp64; where fp32 is named, u rounded to fp32.
+ *  1 CANDIDATES  h = ((ux x + uy y) + uz z) in fp32.  Point k is a candidate iff x, y, z are finite,
+ *    -(sensor_height + height_clip_range) <= h <= -(sensor_height - height_clip_range) (the bounds in fp32) and, with
+ *    max_range > 0, (x x + y y) + z z <= max_range * max_range (fp32).  The candidate list keeps the input order; K entries.
+ *  2 HYPOTHESES  hypothesis h in [0, H) draws three candidate slots, slot j = (uint64(fmix32(seed + 0x9E3779B9 (3 h + j + 1))) K)
+ *    >> 32, fmix32 MurmurHash3's 32-bit finaliser, arithmetic mod 2^32.  With a, b, c the slots' points: DEGENERATE if two slots
+ *    coincide or, in fp64 from the fp32 points, n = (b - a) x (c - a) has |n|^2 <= 1e-12 |b - a|^2 |c - a|^2.  Otherwise n is
+ *    normalised, flipped so that n.u >= 0, d = -n.a; STEEP, and out of the vote, if n.u < cos(max_normal_angle_deg).  The plane
+ *    is rounded to fp32.
+ *  3 SCORING     count_h = the candidates with fabsf(((nx x + ny y) + nz z) + d) <= inlier_threshold in fp32: integers, exact.
+ *  4 BEST        the largest count; among equals the lowest index.
+ *  5 REFIT       refit_iterations times: the inliers of the current plane (the test of 3 against the plane rounded to fp32);
+ *    sum p, sum p p^T and the count in fp64 in one fixed order (per-tile records, a fixed tree, no floating-point atomics); on
+ *    the host the centroid c, the covariance, the eigenvector of its smallest eigenvalue by 3x3 Jacobi, oriented to u, d = -n.c.
+ *  6 RESULT      plane (unit normal, n.u >= 0, n.p + d = 0), n_candidates, n_inliers and rms_distance (fp64, of the inliers'
+ *    distances) under the final plane, best_hypothesis, best_count, status.
+ *  7 STATUS      the first that applies: FEW_CANDIDATES (K < 3 or K < min_inliers; plane zero, best_hypothesis -1),
+ *    NO_HYPOTHESIS (all degenerate or steep; plane zero, best_hypothesis -1), FEW_INLIERS (a pass over the inliers -- before a
+ *    refit, or the final one -- found fewer than max(3, min_inliers); the plane is the last one fitted), STEEP (a refitted normal
+ *    is beyond the angle; the plane is that fit), else OK.  The calls return LSLAM_OK whatever the status (as
+ *    lslam_kfs_loop_match does with its stage), < 0 on an error.
+ * Everything is checked before anything runs -- LSLAM_ERR_INVALID, lslam_last_error names the cause, nothing has changed (the
+ * caller's result structs included), for: a null ctx, store, cloud or result, a keyframe id out of range, an
+ * up that is zero or not finite, an inlier_threshold that is not positive and finite, n_hypotheses not a multiple of 64 in
+ * [64, 4096], a negative min_inliers or refit_iterations, a sensor_height that is not finite, a height_clip_range or max_range
+ * that is negative or not finite, a max_normal_angle_deg outside [0, 180].  params NULL: the defaults. */
+typedef struct lslam_floor_params {
+  float up[3];                /* the sensor frame's up direction (any length)   (0, 0, 1) */
+  float sensor_height;        /* of the sensor above the floor [m]              1.8 */
+  float height_clip_range;    /* half width of the candidates' height band [m]  1.0 */
+  float max_range;            /* candidates' range gate [m], 0 = off            0 */
+  int32_t n_hypotheses;       /* H                                              512 */
+  float inlier_threshold;     /* [m]                                            0.1 */
+  int32_t min_inliers;        /*                                                512 */
+  float max_normal_angle_deg; /* of a floor normal from up                      10 */
+  int32_t refit_iterations;   /*                                                1 */
+  uint32_t seed;              /*                                                1 */
+} lslam_floor_params;
+enum { LSLAM_FLOOR_OK = 0, LSLAM_FLOOR_FEW_CANDIDATES = 1, LSLAM_FLOOR_NO_HYPOTHESIS = 2, LSLAM_FLOOR_FEW_INLIERS = 3, LSLAM_FLOOR_STEEP = 4 };
+typedef struct lslam_floor_result {
+  double plane[4];
+  double rms_distance;
+  int32_t n_candidates, n_inliers, best_hypothesis, best_count, status, reserved;
+} lslam_floor_result;
+void lslam_floor_default_params(lslam_floor_params *params); /* writes every byte */
+size_t lslam_sizeof_floor_params(void);
+size_t lslam_sizeof_floor_result(void);
+/* A host cloud (stride_bytes >= 16, {x, y, z} at 0 as elsewhere; the intensity is not read): uploaded, then as below. */
+int lslam_floor_detect(lslam_ctx *ctx, const void *points, size_t n, size_t stride_bytes, const lslam_floor_params *params,
+                       lslam_floor_result *result);
+/* A cloud that is in the ctx's device memory already, packed {x, y, z, -}: read where it is. */
+int lslam_floor_detect_device(lslam_ctx *ctx, const float *d_xyzi, size_t n, const lslam_floor_params *params,
+                              lslam_floor_result *result);
+/* The floor of each named keyframe's SURFACE cloud, where it lies in the store: results[n_ids], 0 <= n_ids <= 65535, an id may
+ * repeat.  Every keyframe of the call goes through each stage in one launch (workgroups indexed by tile and keyframe); the host
+ * reads one small record per keyframe and pass over the inliers (refit_iterations + 1 of them) and writes back one plane per
+ * keyframe and refit.  No cloud moves in either direction: the store's byte counters stay.  Per-keyframe arithmetic does not
+ * depend on the batch: the results are, bit for bit, those of lslam_floor_detect_device on each cloud.  (Named apart from
+ * lslam_kfs_*: that prefix is the store's own, closed set of names.) */
+int lslam_floor_detect_keyframes(lslam_kfs *kfs, int32_t n_ids, const int32_t *ids, const lslam_floor_params *params,
+                                 lslam_floor_result *results);
+/* Measurement tap (tools/bench_floor.py): enqueues `launches` launches of the scoring kernel alone, in the shape of the store's
+ * last lslam_floor_detect_keyframes call and on its candidates and hypotheses, counting into counters of its own; not waited for
+ * (time it with events on lslam_stream).  LSLAM_ERR_INVALID before such a call has run. */
+int lslam_debug_floor_score(lslam_kfs *kfs, int32_t launches);
+/* Debug tap of the ctx's last single-cloud detection (lslam_floor_detect, _device): the candidates' input indices
+ * cand_idx[K], and per hypothesis the three slots triples[H][3] (positions in the candidate list), the fp32 plane planes[H][4]
+ * (zero for a degenerate one) and counts[H] (-1 degenerate, -2 steep).  *n_candidates = K, *n_hypotheses = H; any array may be
+ * NULL (call with all NULL to size them); the capacities are in entries (candidates, hypotheses). */
+int lslam_debug_floor_hypotheses(lslam_ctx *ctx, int32_t *cand_idx, size_t cap_candidates, size_t *n_candidates, int32_t *triples,
+                                 float *planes, int32_t *counts, size_t cap_hypotheses, size_t *n_hypotheses);
 
 /* ---- edge information: the match Hessian of a pose-graph edge, in fp64 --------------------------------------------------------
  * Not in the reference: pose_graph/information_estimator.hpp returns the identity (its //@ todo), and graph.cpp:279-288,333-339
@@ -1324,6 +1404,44 @@ int lslam_pg_prior_robust(lslam_pg *pg, const double *poses7, double *e2, double
  * holds (call with NULL arrays to size them); vertices are numbered as lslam_g2o_read numbers them. */
 int lslam_g2o_read_priors(const char *path, int32_t *n_priors, int32_t *vertex, int32_t *type, double *meas7,
                           double *info36);
+
+/* ---- plane priors: a plane known in the graph frame, measured in a keyframe's sensor frame ------------------------------------
+ * The reference shows the intent and stops there (pose_graph/solver_g2o.h:61-65 add_plane_node commented out, :92 the floor
+ * plane node, :42 g2o's plane types; graph.cpp:321 "floor coeffs").  The module is modelled on hdl_graph_slam's floor
+ * constraint.  Neither hdl_graph_slam nor g2o is under the reference, so PARITY IS UNPINNED like the rest of this solver; the
+ * semantics are this project's own, in this solver's conventions (update X <- X * fromVectorMQT(d)).  A POSE prior with only
+ * z / roll / pitch information is NOT this constraint: its error's coordinates turn with yaw, a plane seen from the sensor does not.
+ * A plane prior sits on one vertex v with estimate X = (t, R), R sensor -> graph.  world4 = (n_w, d_w) is the plane in the graph
+ * frame, meas4 = (n_m, d_m) the plane measured in the sensor frame (n.p + d = 0; both are scaled to unit normals before they
+ * reach the device).  The world plane in the sensor frame: n_l = R^T n_w, d_l = d_w + n_w.t.  Tangent basis of n_m: a = the unit
+ * axis of the smallest |n_m| component (the lowest index among equals), b1 = normalise(n_m x a), b2 = n_m x b1.
+ *   e = (b1.n_l, b2.n_l, d_l - d_m)          3 rows
+ *   J = rows 0, 1: [0 | 2 (b_k x n_l)^T], row 2: [n_l^T | 0]
+ *   Omega = info9, 3x3 row-major in (tangent 1, tangent 2, distance) coordinates; positive SEMI-definite is legal
+ * It adds rho1 J^T Omega J to its vertex's diagonal block, -rho1 J^T Omega e to its segment of b and rho0 to chi2 (kind / delta:
+ * the LSLAM_PG_KERNEL_* semantics): the sparsity pattern, the PCG and the sharded layouts do not change.  In the per-vertex sum
+ * the plane priors follow the vertex's edges and its POSE / XYZ priors, in plane-prior order (one fixed order, no atomics).  On
+ * the fixed vertex a plane prior adds its rho0 to chi2 only.  lslam_pg_linearize and lslam_pg_optimize include them; sharded runs
+ * follow the priors' rule (every rank sets the same set, the rank whose edge range starts at 0 linearises all of it).  This set
+ * is separate from lslam_pg_set_priors': lslam_pg_num_priors, lslam_pg_prior_robust and lslam_g2o_read_priors keep their meaning.
+ * While a graph has no plane priors -- the default -- the solver launches exactly the kernels it launched before. */
+/* Replaces the whole set; n_priors = 0 clears.  vertex[n], world4[n][4], meas4[n][4], info9[n][9]; kind[n] / delta[n] as
+ * lslam_pg_set_priors.  Everything is checked before anything changes -- LSLAM_ERR_INVALID, lslam_pg_last_error names the
+ * cause, for: a vertex out of range, a plane that is not finite or has a zero normal, information that is not finite, not
+ * symmetric (beyond 1e-12 of its largest entry) or has a negative diagonal entry, kind without delta or the reverse, an unknown
+ * kind, a delta that is not finite and > 0, and a pair whose normals lie in opposite hemispheres at the vertex's current
+ * estimate (n_l.n_m < 0: one of the planes is given upside down).  A device error while the new set is uploaded leaves the
+ * graph with no plane priors. */
+int lslam_pg_set_plane_priors(lslam_pg *pg, int32_t n_priors, const int32_t *vertex, const double *world4, const double *meas4,
+                              const double *info9, const int32_t *kind, const double *delta);
+int32_t lslam_pg_num_plane_priors(const lslam_pg *pg);
+/* per plane prior at poses7 (NULL: the current estimate); any output may be NULL: e2[n], rho[n] = rho0, weight[n] = rho1 */
+int lslam_pg_plane_prior_robust(lslam_pg *pg, const double *poses7, double *e2, double *rho, double *weight);
+/* lslam_pg_save_g2o writes the plane priors behind the other priors, one line each with THIS PROJECT'S OWN tag (no g2o or
+ * hdl_graph_slam type reads it): "EDGE_SE3_PRIOR_PLANE v <world4> <meas4> <6 upper-triangular>", the planes as given.
+ * lslam_g2o_read and lslam_g2o_read_priors skip these lines; this reader returns them, in file order (host only), with the
+ * two-call pattern and the vertex numbering of lslam_g2o_read_priors. */
+int lslam_g2o_read_plane_priors(const char *path, int32_t *n_priors, int32_t *vertex, double *world4, double *meas4, double *info9);
 
 /* Device handle tap, as lslam_stream: the stream every kernel of this graph runs on (hipStream_t), for harnesses that time a
  * linearisation with events (tools/bench_robust_linearize.py). */

@@ -140,6 +140,14 @@ public:
     _err = lslam_last_error();
     return false;
   }
+  // The floor of each named keyframe's SURFACE cloud, where it lies (lslam_floor_detect_keyframes: every keyframe through each
+  // stage in one launch, no cloud moved); params == nullptr: the defaults.  results[k] belongs to ids[k].
+  bool floorDetect(const std::vector<int32_t> &ids, const lslam_floor_params *params, std::vector<lslam_floor_result> &results) {
+    results.assign(ids.size(), lslam_floor_result());
+    if (lslam_floor_detect_keyframes(_h, (int32_t)ids.size(), ids.data(), params, results.data()) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
   // ---- loop candidates by appearance: scan context (lslam_sc_*) ----
   // params == nullptr: the defaults.  Other parameters than those in force drop the descriptors held.
   bool sc_setup(const lslam_sc_params *params = nullptr) {
@@ -208,6 +216,11 @@ struct KeyFrame {
   // only by a Graph with gps_sigma_xy / imu_orientation_sigma set.  gps_local = utm_coord - the graph's utm_origin (fp64).
   bool has_utm_coord = false, has_imu_quat = false, has_gps_local = false;
   double utm_coord[3] = {0.0, 0.0, 0.0}, imu_quat[4] = {0.0, 0.0, 0.0, 1.0}, gps_local[3] = {0.0, 0.0, 0.0};
+  // the floor found in the surface cloud by a Graph with floor_sigma_normal / floor_sigma_distance set: (n, d) in the sensor
+  // frame when has_floor_coeffs; floor_status is the detection's LSLAM_FLOOR_* (-1: not looked for)
+  bool has_floor_coeffs = false;
+  double floor_coeffs[4] = {0.0, 0.0, 0.0, 0.0};
+  int floor_status = -1;
 };
 
 // loop_detector.hpp:18-48
@@ -523,6 +536,7 @@ public:
                  bool keep_host_clouds = true, bool appearance_loops = false, const lslam_sc_params *sc_params = nullptr)
       : loop_detector(ctx), _ctx(ctx), _device(device), _max_per_update(max_keyframes_per_update), _keep_host(keep_host_clouds),
         _appearance(appearance_loops) {
+    lslam_floor_default_params(&floor_params);
     if (resident || appearance_loops) {
       store.reset(new KeyframeStore(ctx));
       if (!store->ok()) _err = store->lastError();
@@ -606,6 +620,16 @@ public:
       _err = "Graph: gps_sigma_xy and gps_sigma_z [m] are set together, both > 0; imu_orientation_sigma [rad] and gps_min_spread [m] >= 0";
       return -1;
     }
+    const int floor_kind = lslam_pg_kernel_from_name(floor_robust_kernel.c_str());
+    if (floor_kind < 0 || (floor_kind != LSLAM_PG_KERNEL_NONE && !(std::isfinite(floor_robust_kernel_size) && floor_robust_kernel_size > 0.0))) {
+      _err = "Graph: floor_robust_kernel is NONE, Huber, Cauchy or DCS with a finite floor_robust_kernel_size > 0";
+      return -1;
+    }
+    if (!(floor_sigma_normal >= 0.0 && floor_sigma_distance >= 0.0 && std::isfinite(floor_sigma_normal) && std::isfinite(floor_sigma_distance)) ||
+        ((floor_sigma_normal > 0.0) != (floor_sigma_distance > 0.0))) {
+      _err = "Graph: floor_sigma_normal [rad] and floor_sigma_distance [m] are set together, both > 0";
+      return -1;
+    }
     _edge_failed = false;
     const bool flushed = flush_keyframe_queue();
     if (_edge_failed) return -1;
@@ -639,9 +663,11 @@ public:
     loops.insert(loops.end(), found.begin(), found.end());
     keyframes.insert(keyframes.end(), new_keyframes.begin(), new_keyframes.end());
     const bool added_priors = add_priors(new_keyframes, gps_kind);
+    bool added_floors = false;
+    if (!add_floors(new_keyframes, floor_kind, &added_floors)) return -1;
     new_keyframes.clear();
     last_iterations = 0;
-    if (!found.empty() || added_priors) {
+    if (!found.empty() || added_priors || added_floors) {
       if (!solve_graph(max_iterations, nullptr, nullptr)) return -1;
     }
     const KeyFrame::Ptr &last = keyframes.back();
@@ -795,6 +821,36 @@ public:
   //   imu_orientation_sigma [rad]: a keyframe's imu_quat (in the frame the fixes are in) becomes a POSE prior with a zero
   //     translation block and (2 / sigma)^2 on the quaternion vector; queued with the fixes when the GPS switch is on.
   // optimize() then runs the solver when a pass added loops OR priors.
+  // Floor planes as plane priors (not in the reference, which only shows the intent: solver_g2o.h:61-65, :92, graph.cpp:321;
+  // lslam_floor_detect*, lslam_pg_set_plane_priors, semantics in lslam_c.h).  Off by default (0).
+  //   floor_sigma_normal [rad] / floor_sigma_distance [m]: on each pass the floor of every new keyframe's surface cloud is
+  //     detected on the device with floor_params (the defaults unless changed) -- one KeyframeStore::floorDetect call over the
+  //     store of a resident graph, one lslam_floor_detect per cloud otherwise.  An accepted floor becomes the keyframe's
+  //     floor_coeffs and a plane prior against floor_world_plane -- the floor in the GRAPH frame, z = 0 by default; a graph frame
+  //     that starts at the first sensor pose has its floor at (0, 0, 1, sensor_height) -- with information diag(1/sn^2, 1/sn^2,
+  //     1/sd^2) and floor_robust_kernel / floor_robust_kernel_size.  A keyframe whose floor was not found adds nothing and is
+  //     counted (floorsNotFound).  No default: the library does not guess the detection's noise.
+  //   LIMIT: with the reference's constant odometry information (sigma about 1 m / 0.7 rad) bending the trajectory onto an
+  //     outlying floor costs less than any kernel charges for rejecting it: a kernel rejects only when the edges are worth
+  //     something -- odometry_information below, or edge_information = "hessian".
+  double floor_sigma_normal = 0.0, floor_sigma_distance = 0.0;
+  lslam_floor_params floor_params;
+  std::string floor_robust_kernel = "NONE";
+  double floor_robust_kernel_size = 1.0;
+  double floor_world_plane[4] = {0.0, 0.0, 1.0, 0.0};
+  std::vector<KeyFrame::Ptr> floors;           // the keyframes whose floor became a plane prior, in plane-prior order
+  std::vector<KeyFrame::Ptr> floorsNotFound;   // ... and those whose floor was not found (KeyFrame::floor_status says why)
+  const std::vector<double> &floorWeights() const { return _floor_weights; }
+  std::vector<KeyFrame::Ptr> rejectedFloors(double threshold = 0.1) const {
+    std::vector<KeyFrame::Ptr> out;
+    for (size_t k = 0; k < floors.size() && k < _floor_weights.size(); ++k)
+      if (_floor_weights[k] < threshold) out.push_back(floors[k]);
+    return out;
+  }
+  size_t numPlanePriors() const { return _qv.size(); }
+  // The diagonal of every odometry edge's information over [translation, rotation]; the reference's constant (graph.cpp:279-288)
+  // unless the caller knows its odometry better.
+  double odometry_information[6] = {0.8, 0.4, 0.8, 1.0, 2.0, 1.0};
   double gps_sigma_xy = 0.0, gps_sigma_z = 0.0;
   std::string gps_robust_kernel = "NONE";
   double gps_robust_kernel_size = 1.0;
@@ -901,6 +957,48 @@ private:
     _prior_queue.clear();
     return added;
   }
+  // The floors of a pass's new keyframes: detected in one call over the store (resident) or per cloud; the accepted ones become
+  // plane priors.  -> false on a backend error; *added: whether any reached the solver.
+  bool add_floors(const std::vector<KeyFrame::Ptr> &fresh, int floor_kind, bool *added) {
+    *added = false;
+    if (!(floor_sigma_normal > 0.0) || fresh.empty()) return true;
+    std::vector<lslam_floor_result> res(fresh.size());
+    if (store) {
+      std::vector<int32_t> ids;
+      for (const auto &kf : fresh) ids.push_back(kf->store_id);
+      if (!store->floorDetect(ids, &floor_params, res)) {
+        _err = store->lastError();
+        return false;
+      }
+    } else {
+      for (size_t k = 0; k < fresh.size(); ++k)
+        if (lslam_floor_detect(_ctx, fresh[k]->surfCloud.data(), fresh[k]->surfCloud.size() / 4, 16, &floor_params, &res[k]) < 0) {
+          _err = lslam_last_error();
+          return false;
+        }
+    }
+    const double wn = 1.0 / (floor_sigma_normal * floor_sigma_normal), wd = 1.0 / (floor_sigma_distance * floor_sigma_distance);
+    for (size_t k = 0; k < fresh.size(); ++k) {
+      const KeyFrame::Ptr &kf = fresh[k];
+      kf->floor_status = res[k].status;
+      if (res[k].status != LSLAM_FLOOR_OK) {
+        floorsNotFound.push_back(kf);
+        continue;
+      }
+      kf->has_floor_coeffs = true;
+      for (int c = 0; c < 4; ++c) kf->floor_coeffs[c] = res[k].plane[c];
+      _qv.push_back(kf->node);
+      _qworld.insert(_qworld.end(), floor_world_plane, floor_world_plane + 4);
+      _qmeas.insert(_qmeas.end(), kf->floor_coeffs, kf->floor_coeffs + 4);
+      const double w[9] = {wn, 0.0, 0.0, 0.0, wn, 0.0, 0.0, 0.0, wd};
+      _qinfo.insert(_qinfo.end(), w, w + 9);
+      _qkind.push_back(floor_kind);
+      _qdelta.push_back(floor_robust_kernel_size);
+      floors.push_back(kf);
+      *added = true;
+    }
+    return true;
+  }
   void add_prior(int v, int type, const double z[7], const double w[36], int kind, double delta) {
     _pv.push_back(v);
     _ptype.push_back(type);
@@ -940,7 +1038,7 @@ private:
     if (keyframe_queue.empty()) return false;
     const Mat4d odom2map = tf_odom2graph;
     const int n = std::min<int>((int)keyframe_queue.size(), _max_per_update);
-    static const double ODOM_INFO[6] = {0.8, 0.4, 0.8, 1.0, 2.0, 1.0};  // graph.cpp:279-288
+    const double *ODOM_INFO = odometry_information;  // graph.cpp:279-288 by default
     for (int i = 0; i < n; ++i) {
       KeyFrame::Ptr kf = keyframe_queue[(size_t)i];
       new_keyframes.push_back(kf);
@@ -982,6 +1080,12 @@ private:
       rc = lslam_pg_set_priors(pg, (int32_t)_pv.size(), _pv.data(), _ptype.data(), _pmeas.data(), _pinfo.data(),
                                any ? _pkind.data() : nullptr, any ? _pdelta.data() : nullptr);
     }
+    if (rc >= 0 && !_qv.empty()) {
+      bool any = false;
+      for (size_t p = 0; p < _qkind.size(); ++p) any = any || _qkind[p] != LSLAM_PG_KERNEL_NONE;
+      rc = lslam_pg_set_plane_priors(pg, (int32_t)_qv.size(), _qv.data(), _qworld.data(), _qmeas.data(), _qinfo.data(),
+                                     any ? _qkind.data() : nullptr, any ? _qdelta.data() : nullptr);
+    }
     if (rc >= 0 && g2o_before) rc = lslam_pg_save_g2o(pg, g2o_before);
     if (rc >= 0) rc = lslam_pg_optimize(pg, max_iterations, &st);
     if (rc >= 0 && g2o_end) rc = lslam_pg_save_g2o(pg, g2o_end);
@@ -992,6 +1096,10 @@ private:
       rc = lslam_pg_prior_robust(pg, nullptr, nullptr, nullptr, w.data());
       _gps_weights.clear();
       for (size_t k = 0; rc >= 0 && k < _gps_priors.size(); ++k) _gps_weights.push_back(w[(size_t)_gps_priors[k]]);
+    }
+    if (rc >= 0 && !_qv.empty()) {
+      _floor_weights.assign(_qv.size(), 1.0);
+      rc = lslam_pg_plane_prior_robust(pg, nullptr, nullptr, nullptr, _floor_weights.data());
     }
     lslam_pg_destroy(pg);
     if (rc < 0) {
@@ -1068,6 +1176,9 @@ private:
   std::vector<KeyFrame::Ptr> _prior_queue;
   std::vector<int> _gps_priors;
   std::vector<double> _gps_weights;
+  // plane priors: vertex, world plane, measured plane, 3x3 information, kernel; the weight of every entry of `floors`
+  std::vector<int32_t> _qv, _qkind;
+  std::vector<double> _qworld, _qmeas, _qinfo, _qdelta, _floor_weights;
   std::string _err;
 };
 

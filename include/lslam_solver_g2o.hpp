@@ -32,6 +32,7 @@ public:
   };
   struct EdgeSE3 { int index; };
   struct EdgeSE3Prior { int index; };  // a unary constraint (lslam_pg_set_priors), by prior index
+  struct EdgeSE3Plane { int index; };  // a plane prior (lslam_pg_set_plane_priors), by plane-prior index
 
   explicit SolverG2OT(int device = 0) : is_first(true), _device(device), _pg(nullptr) {}
   ~SolverG2OT() { lslam_pg_destroy(_pg); }
@@ -124,6 +125,53 @@ public:
       throw std::runtime_error(std::string("lslam_pg_prior_robust: ") + lslam_pg_last_error());
     return w;
   }
+  // ---- plane priors (the reference's add_plane_node is commented out, solver_g2o.h:61-65; hdl_graph_slam's floor constraint,
+  // semantics in lslam_c.h "plane priors").  The plane `world_plane` = (n, d) of the graph frame was measured as `measured_plane`
+  // in v's sensor frame; Vec4: (i) read access (Eigen::Vector4d works); the information is 3x3 over (tangent 1, tangent 2, distance).
+  template <typename Vec4, typename Mat3, typename World4>
+  EdgeSE3Plane *add_se3_prior_plane_edge(VertexSE3 *v, const Vec4 &measured_plane, const Mat3 &information_matrix,
+                                         const World4 &world_plane) {
+    if (!v) throw std::invalid_argument("plane prior: no vertex");
+    pull();
+    _qv.push_back(v->id());
+    for (int k = 0; k < 4; ++k) {
+      _qworld.push_back(world_plane(k));
+      _qmeas.push_back(measured_plane(k));
+    }
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) _qinfo.push_back(information_matrix(r, c));
+    _qkind.push_back(LSLAM_PG_KERNEL_NONE);
+    _qdelta.push_back(1.0);
+    _planes.push_back(EdgeSE3Plane{(int)_planes.size()});
+    return &_planes.back();
+  }
+  // ... against the floor z = 0 of the graph frame, (0, 0, 1, 0)
+  struct FloorZ0 {
+    double operator()(int k) const { return k == 2 ? 1.0 : 0.0; }
+  };
+  template <typename Vec4, typename Mat3>
+  EdgeSE3Plane *add_se3_prior_plane_edge(VertexSE3 *v, const Vec4 &measured_plane, const Mat3 &information_matrix) {
+    return add_se3_prior_plane_edge(v, measured_plane, information_matrix, FloorZ0());
+  }
+  void add_robust_kernel(EdgeSE3Plane *plane, const std::string &kernel_type, double kernel_size) {
+    if (!plane || plane->index < 0 || plane->index >= (int)_planes.size()) throw std::invalid_argument("add_robust_kernel: no such plane prior");
+    const int kind = lslam_pg_kernel_from_name(kernel_type.c_str());
+    if (kind < 0) throw std::invalid_argument("add_robust_kernel: unknown kernel type " + kernel_type);
+    if (kind != LSLAM_PG_KERNEL_NONE && !(std::isfinite(kernel_size) && kernel_size > 0.0))
+      throw std::invalid_argument("add_robust_kernel: kernel_size must be finite and > 0");
+    _qkind[(size_t)plane->index] = kind;
+    _qdelta[(size_t)plane->index] = kernel_size;
+    if (_pg) apply_plane_priors();
+  }
+  // the robust weight (rho1) of every plane prior at the current estimate, by plane-prior index; all 1 without kernels
+  std::vector<double> planePriorWeights() {
+    build();
+    std::vector<double> w(_planes.size());
+    if (lslam_pg_plane_prior_robust(_pg, nullptr, nullptr, nullptr, w.data()) < 0)
+      throw std::runtime_error(std::string("lslam_pg_plane_prior_robust: ") + lslam_pg_last_error());
+    return w;
+  }
+  size_t numPlanePriors() const { return _planes.size(); }
   // true (default, solver_g2o.cpp:55-59): the first vertex is held fixed; false: no vertex is -- for graphs whose priors fix
   // the gauge.  Takes effect when the device graph is next built.
   void setFixFirstNode(bool fix) {
@@ -134,9 +182,14 @@ public:
   // Replaces the graph by the one in a .g2o file written by save(): vertices, edges, priors and whether a vertex is fixed
   // (lslam_g2o_read / lslam_g2o_read_priors).  Vertex and edge pointers handed out before are invalid afterwards.
   void load(const std::string &filename) {
-    int32_t nv = 0, ne = 0, np = 0, fixed = -1;
+    int32_t nv = 0, ne = 0, np = 0, nq = 0, fixed = -1;
     if (lslam_g2o_read(filename.c_str(), &nv, nullptr, &ne, nullptr, nullptr, nullptr, &fixed) < 0 ||
-        lslam_g2o_read_priors(filename.c_str(), &np, nullptr, nullptr, nullptr, nullptr) < 0)
+        lslam_g2o_read_priors(filename.c_str(), &np, nullptr, nullptr, nullptr, nullptr) < 0 ||
+        lslam_g2o_read_plane_priors(filename.c_str(), &nq, nullptr, nullptr, nullptr, nullptr) < 0)
+      throw std::runtime_error(std::string("load: ") + lslam_pg_last_error());
+    std::vector<int32_t> qv((size_t)nq);
+    std::vector<double> qworld((size_t)nq * 4), qmeas((size_t)nq * 4), qinfo((size_t)nq * 9);
+    if (lslam_g2o_read_plane_priors(filename.c_str(), &nq, qv.data(), qworld.data(), qmeas.data(), qinfo.data()) < 0)
       throw std::runtime_error(std::string("load: ") + lslam_pg_last_error());
     std::vector<double> poses((size_t)nv * 7), meas((size_t)ne * 7), info((size_t)ne * 36), pmeas((size_t)np * 7), pinfo((size_t)np * 36);
     std::vector<int32_t> ij((size_t)ne * 2), pv((size_t)np), pt((size_t)np);
@@ -158,6 +211,11 @@ public:
     _delta.assign((size_t)ne, 1.0);
     _pkind.assign((size_t)np, LSLAM_PG_KERNEL_NONE);
     _pdelta.assign((size_t)np, 1.0);
+    _planes.clear();
+    for (int k = 0; k < nq; ++k) _planes.push_back(EdgeSE3Plane{k});
+    _qv.swap(qv); _qworld.swap(qworld); _qmeas.swap(qmeas); _qinfo.swap(qinfo);
+    _qkind.assign((size_t)nq, LSLAM_PG_KERNEL_NONE);
+    _qdelta.assign((size_t)nq, 1.0);
     _fix_first = fixed == 0;
     is_first = nv == 0;
   }
@@ -247,6 +305,18 @@ private:
     if (_solve_tol > 0.0) (void)lslam_pg_set_solve_tolerance(_pg, _solve_tol);
     apply_kernels();
     if (!_priors.empty()) apply_priors();
+    if (!_planes.empty()) apply_plane_priors();
+  }
+  void apply_plane_priors() {
+    bool any = false;
+    for (size_t p = 0; p < _qkind.size(); ++p) any = any || _qkind[p] != LSLAM_PG_KERNEL_NONE;
+    if (lslam_pg_set_plane_priors(_pg, (int32_t)_planes.size(), _qv.data(), _qworld.data(), _qmeas.data(), _qinfo.data(),
+                                  any ? _qkind.data() : nullptr, any ? _qdelta.data() : nullptr) < 0) {
+      const std::string why = lslam_pg_last_error();
+      lslam_pg_destroy(_pg);  // never a device graph without the plane priors it was asked to carry
+      _pg = nullptr;
+      throw std::runtime_error("lslam_pg_set_plane_priors: " + why);
+    }
   }
   EdgeSE3Prior *add_prior(VertexSE3 *v, int type, const double z[7], const double w[36]) {
     if (!v) throw std::invalid_argument("prior: no vertex");
@@ -305,6 +375,9 @@ private:
   std::deque<EdgeSE3Prior> _priors;  // unary constraints: vertex, LSLAM_PG_PRIOR_*, measurement, information, kernel
   std::vector<int32_t> _pv, _ptype, _pkind;
   std::vector<double> _pmeas, _pinfo, _pdelta;
+  std::deque<EdgeSE3Plane> _planes;  // plane priors: vertex, world plane, measured plane, 3x3 information, kernel
+  std::vector<int32_t> _qv, _qkind;
+  std::vector<double> _qworld, _qmeas, _qinfo, _qdelta;
 };
 
 }  // namespace pose_graph

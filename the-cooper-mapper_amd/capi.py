@@ -258,6 +258,25 @@ class LslamScStats(C.Structure):
                 ("describe_launches", C.c_int64), ("query_launches", C.c_int64)]
 
 
+class LslamFloorParams(C.Structure):
+    """lslam_floor_params (include/lslam_c.h)."""
+    _fields_ = [("up", C.c_float * 3), ("sensor_height", C.c_float), ("height_clip_range", C.c_float), ("max_range", C.c_float),
+                ("n_hypotheses", C.c_int32), ("inlier_threshold", C.c_float), ("min_inliers", C.c_int32),
+                ("max_normal_angle_deg", C.c_float), ("refit_iterations", C.c_int32), ("seed", C.c_uint32)]
+
+
+class LslamFloorResult(C.Structure):
+    """lslam_floor_result (include/lslam_c.h)."""
+    _fields_ = [("plane", C.c_double * 4), ("rms_distance", C.c_double), ("n_candidates", C.c_int32), ("n_inliers", C.c_int32),
+                ("best_hypothesis", C.c_int32), ("best_count", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        import numpy as np
+        return dict(plane=np.array(self.plane, np.float64), rms_distance=float(self.rms_distance),
+                    n_candidates=int(self.n_candidates), n_inliers=int(self.n_inliers), best_hypothesis=int(self.best_hypothesis),
+                    best_count=int(self.best_count), status=int(self.status))
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLGATHERV_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32)
 c_double_p = C.POINTER(C.c_double)
@@ -389,6 +408,18 @@ SYMBOLS = {
     "lslam_kfs_scanmatch": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, c_float_p, C.POINTER(LslamOpts),
                                       C.POINTER(LslamStats)]),
     "lslam_kfs_add_to_fmap": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, c_float_p]),
+    "lslam_floor_default_params": (None, [C.POINTER(LslamFloorParams)]),
+    "lslam_sizeof_floor_params": (C.c_size_t, []),
+    "lslam_sizeof_floor_result": (C.c_size_t, []),
+    "lslam_floor_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(LslamFloorParams),
+                                     C.POINTER(LslamFloorResult)]),
+    "lslam_floor_detect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(LslamFloorParams),
+                                            C.POINTER(LslamFloorResult)]),
+    "lslam_floor_detect_keyframes": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.POINTER(LslamFloorParams),
+                                               C.POINTER(LslamFloorResult)]),
+    "lslam_debug_floor_score": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lslam_debug_floor_hypotheses": (C.c_int, [C.c_void_p, c_int32_p, C.c_size_t, C.POINTER(C.c_size_t), c_int32_p, c_float_p,
+                                               c_int32_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "lslam_sizeof_edge_info": (C.c_size_t, []),
     "lslam_match_information": (C.c_int, [C.c_void_p, c_float_p, C.c_int32, C.POINTER(LslamEdgeInfo)]),
     "lslam_keyframe_edge_information": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, C.c_int32, c_float_p, C.c_float, C.c_float,
@@ -530,6 +561,11 @@ SYMBOLS = {
     "lslam_pg_num_priors": (C.c_int32, [C.c_void_p]),
     "lslam_pg_prior_robust": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "lslam_g2o_read_priors": (C.c_int, [C.c_char_p, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p]),
+    "lslam_pg_set_plane_priors": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p,
+                                            c_double_p]),
+    "lslam_pg_num_plane_priors": (C.c_int32, [C.c_void_p]),
+    "lslam_pg_plane_prior_robust": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "lslam_g2o_read_plane_priors": (C.c_int, [C.c_char_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
     "lslam_pg_stream": (C.c_void_p, [C.c_void_p]),
     "lslam_pg_kernel_from_name": (C.c_int, [C.c_char_p]),
     "lslam_icp_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, C.c_int32,
@@ -560,6 +596,8 @@ SYMBOLS = {
 
 COMM_ID_BYTES = 128
 SC_POINT_CHUNK, SC_CAND_TILE, SC_MAX_TOP_K = 256, 64, 32  # LSLAM_SC_* of include/lslam_c.h: the scan-context kernels' shape
+# lslam_floor_result.status (LSLAM_FLOOR_*)
+FLOOR_OK, FLOOR_FEW_CANDIDATES, FLOOR_NO_HYPOTHESIS, FLOOR_FEW_INLIERS, FLOOR_STEEP = 0, 1, 2, 3, 4
 SEARCH_AUTO, SEARCH_LANE, SEARCH_PACKET, SEARCH_GRID = 0, 1, 2, 3
 AB_WIDE_NF_MARGIN, AB_NO_COMPACT = 16, 64  # lslam_opts.ab_switches (LSLAM_AB_*); any other bit is refused
 AB_GRID_GENERAL = 256

@@ -424,6 +424,7 @@ enum CtxSlot : int {
   CTX_SLOT_VOXEL_GRID2,   // lslam_fmap.hip: lslam_voxel_grid2
   CTX_SLOT_ODOM,          // lslam_odom.hip: the hidden node of lslam_odometry_match
   CTX_SLOT_SCANPREP,      // lslam_scanprep.hip
+  CTX_SLOT_FLOOR,         // lslam_floor.hip: the single-cloud floor detection
   CTX_N_SLOTS
 };
 struct CtxSlotEntry {

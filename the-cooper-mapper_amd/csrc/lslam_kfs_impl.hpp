@@ -76,6 +76,45 @@ struct ScState {
   }
 };
 
+// Floor detection (lslam_floor.hip): what its kernels read per cloud of a call, what the host reads back per cloud, and the
+// scratch of a call.  A context owns one (CTX_SLOT_FLOOR: the single-cloud entry points), a store owns one
+// (lslam_floor_detect_keyframes); each is freed with its owner.
+constexpr int FLOOR_NSUM = 11;
+struct FloorJob {
+  const float4 *pts;
+  uint32_t n;
+  uint32_t cand_base;  // the cloud's slice of d_cand_idx / d_cand_pts: [cand_base, cand_base + n)
+  uint32_t tile_base;  // ... of the per-tile arrays: its ceil(n / 1024) tiles
+  uint32_t pad;
+};
+struct FloorOut {
+  int32_t K, best, best_count, pad;
+  double sums[FLOOR_NSUM];
+};
+struct FloorPlane {
+  float4 p32;     // the plane the inlier test reads
+  double p64[4];  // ... and the one distances are taken from
+};
+struct FloorScratch {
+  PinBuf<FloorJob> h_jobs;
+  DevBuf<FloorJob> d_jobs;
+  DevBuf<int32_t> d_tile_cnt, d_tile_off, d_cand_idx, d_triples, d_hstat, d_counts;
+  DevBuf<float4> d_cand_pts, d_planes, d_cloud;
+  PinBuf<float4> h_cloud;  // staging of lslam_floor_detect's host cloud
+  DevBuf<double> d_partials;
+  DevBuf<FloorOut> d_out;
+  PinBuf<FloorOut> h_out;
+  DevBuf<FloorPlane> d_cur;
+  PinBuf<FloorPlane> h_cur;
+  bool tap_valid = false;  // the lists of the last call's first cloud are there (lslam_debug_floor_hypotheses)
+  int32_t tap_K = 0, tap_H = 0;
+  // the shape of the last call's scoring launch, and a second set of counters (lslam_debug_floor_score: the kernel alone, timed)
+  int32_t last_clouds = 0, last_H = 0;
+  uint32_t last_tiles = 0;
+  float last_thr = 0.0f;
+  DevBuf<int32_t> d_counts_again;
+};
+
 }  // namespace lslam
 
 struct lslam_kfs {
@@ -94,6 +133,7 @@ struct lslam_kfs {
   lslam::DevBuf<float4> local[2], indexed[2], filt[4];
   size_t n_local[2] = {0, 0};
   lslam::ScState sc;
+  lslam::FloorScratch floor;
 };
 
 namespace lslam {

@@ -369,26 +369,13 @@ PG_DEV void prior_error(int type, const Pose &x, const Pose &z, double e[6], dou
     for (int c = 0; c < 6; ++c) J[r * 6 + c] = (r < 3 && c < 3) ? R[r * 3 + c] : 0.0;
 }
 
-// One lane per prior.  ROBUST as in edge_record: rho1 scales H and b, rho0 goes to chi2.  A prior on the fixed vertex adds its
-// rho0 to chi2 and nothing to H or b (g2o: an active edge on a fixed vertex).  chi: this rank's compact per-constraint values,
-// the priors' behind the edges'.
+// The record of one unary constraint from its 6-row error, Jacobian and information (a constraint with fewer rows pads with
+// zeros): [rho1 J^T Omega J | -rho1 J^T Omega e | rho0], and rho0 once more into *chi.  fx: the vertex is the fixed one.
 template <bool ROBUST>
-PG_DEV void prior_record(const double *poses, const int32_t *pv, const int32_t *ptype, const double *pmeas,
-                         const double *pinfo, int n_p, int fixed, const int32_t *kind, const double *delta, double *rec,
+PG_DEV void unary_record(const double er[6], const double J[36], const double Om[36], int kd, double dl, bool fx, double *o,
                          double *chi) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n_p) return;
-  const int v = pv[p];
-  const Pose x = load_pose(poses + 7 * v), z = load_pose(pmeas + 7 * p);
-  double er[6], J[36], Om[36];
-  prior_error<true>(ptype[p], x, z, er, J);
-#pragma unroll
-  for (int k = 0; k < 36; ++k) Om[k] = pinfo[(size_t)p * 36 + k];
   double c2 = edge_e2(Om, er), w = 1.0;
-  if (ROBUST) {
-    const int kd = kind[p];
-    robustify(kd, kd != LSLAM_PG_KERNEL_NONE ? delta[p] : 1.0, c2, c2, w);
-  }
+  if (ROBUST) robustify(kd, dl, c2, c2, w);
   double A[36];  // J^T Omega
 #pragma unroll
   for (int r = 0; r < 6; ++r)
@@ -399,8 +386,6 @@ PG_DEV void prior_record(const double *poses, const int32_t *pv, const int32_t *
       for (int k = 0; k < 6; ++k) s += J[k * 6 + r] * Om[k * 6 + c];
       A[r * 6 + c] = s;
     }
-  const bool fx = (v == fixed);
-  double *o = rec + (size_t)p * PREC;
 #pragma unroll
   for (int r = 0; r < 6; ++r) {
 #pragma unroll
@@ -418,7 +403,31 @@ PG_DEV void prior_record(const double *poses, const int32_t *pv, const int32_t *
     o[36 + r] = fx ? 0.0 : -bv;
   }
   o[42] = c2;
-  chi[p] = c2;
+  *chi = c2;
+}
+
+// One lane per prior.  ROBUST as in edge_record: rho1 scales H and b, rho0 goes to chi2.  A prior on the fixed vertex adds its
+// rho0 to chi2 and nothing to H or b (g2o: an active edge on a fixed vertex).  chi: this rank's compact per-constraint values,
+// the priors' behind the edges'.
+template <bool ROBUST>
+PG_DEV void prior_record(const double *poses, const int32_t *pv, const int32_t *ptype, const double *pmeas,
+                         const double *pinfo, int n_p, int fixed, const int32_t *kind, const double *delta, double *rec,
+                         double *chi) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_p) return;
+  const int v = pv[p];
+  const Pose x = load_pose(poses + 7 * v), z = load_pose(pmeas + 7 * p);
+  double er[6], J[36], Om[36];
+  prior_error<true>(ptype[p], x, z, er, J);
+#pragma unroll
+  for (int k = 0; k < 36; ++k) Om[k] = pinfo[(size_t)p * 36 + k];
+  int kd = LSLAM_PG_KERNEL_NONE;
+  double dl = 1.0;
+  if (ROBUST) {
+    kd = kind[p];
+    if (kd != LSLAM_PG_KERNEL_NONE) dl = delta[p];
+  }
+  unary_record<ROBUST>(er, J, Om, kd, dl, v == fixed, rec + (size_t)p * PREC, chi + p);
 }
 
 template <bool ROBUST>
@@ -460,6 +469,94 @@ __global__ void pg_prior_tap_kernel(const double *poses, const int32_t *pv, cons
   e2_out[p] = e2;
   rho_out[p] = rho0;
   w_out[p] = rho1;
+}
+
+// ---- plane priors (lslam_pg_set_plane_priors): a plane known in the graph frame, measured in the sensor frame ---------------
+// hdl_graph_slam's floor constraint in this file's conventions; nothing under the reference pins it, like the rest of this
+// solver.  Per prior 8 doubles: the world plane (n_w, d_w) and the measured plane (n_m, d_m), both normals unit (the host
+// normalises).  With X = (t, R): n_l = R^T n_w, d_l = d_w + n_w.t; a = the unit axis of the smallest |n_m| component (the lowest
+// index among equals), b1 = normalise(n_m x a), b2 = n_m x b1;
+//   e = (b1.n_l, b2.n_l, d_l - d_m),  J rows 0, 1 = [0 | 2 (b_k x n_l)^T], row 2 = [n_l^T | 0]
+// (under X <- X fromVectorMQT(d): n_l -> n_l + 2 n_l x dq, d_l -> d_l + n_l.dt).  Rows 3..5 are zero and the information is the
+// 3x3 padded to 6x6, so the record is unary_record's.
+constexpr int QPL = 8;
+
+template <bool JAC>
+PG_DEV void plane_prior_error(const Pose &x, const double *pl, double e[6], double *J) {
+  double R[9];
+  qrotmat(x.q, R);
+  const double nw[3] = {pl[0], pl[1], pl[2]}, nm[3] = {pl[4], pl[5], pl[6]};
+  double nl[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) nl[c] = (R[c] * nw[0] + R[3 + c] * nw[1]) + R[6 + c] * nw[2];
+  const double dl = pl[3] + ((nw[0] * x.t.x + nw[1] * x.t.y) + nw[2] * x.t.z);
+  int a = 0;
+  double m = fabs(nm[0]);
+  if (fabs(nm[1]) < m) {
+    a = 1;
+    m = fabs(nm[1]);
+  }
+  if (fabs(nm[2]) < m) a = 2;
+  const double ax[3] = {a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0};
+  double b1[3] = {nm[1] * ax[2] - nm[2] * ax[1], nm[2] * ax[0] - nm[0] * ax[2], nm[0] * ax[1] - nm[1] * ax[0]};
+  const double len = sqrt((b1[0] * b1[0] + b1[1] * b1[1]) + b1[2] * b1[2]);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) b1[c] /= len;
+  const double b2[3] = {nm[1] * b1[2] - nm[2] * b1[1], nm[2] * b1[0] - nm[0] * b1[2], nm[0] * b1[1] - nm[1] * b1[0]};
+  e[0] = (b1[0] * nl[0] + b1[1] * nl[1]) + b1[2] * nl[2];
+  e[1] = (b2[0] * nl[0] + b2[1] * nl[1]) + b2[2] * nl[2];
+  e[2] = dl - pl[7];
+  e[3] = 0.0; e[4] = 0.0; e[5] = 0.0;
+  if (!JAC) return;
+#pragma unroll
+  for (int k = 0; k < 36; ++k) J[k] = 0.0;
+  J[0 * 6 + 3] = 2.0 * (b1[1] * nl[2] - b1[2] * nl[1]);
+  J[0 * 6 + 4] = 2.0 * (b1[2] * nl[0] - b1[0] * nl[2]);
+  J[0 * 6 + 5] = 2.0 * (b1[0] * nl[1] - b1[1] * nl[0]);
+  J[1 * 6 + 3] = 2.0 * (b2[1] * nl[2] - b2[2] * nl[1]);
+  J[1 * 6 + 4] = 2.0 * (b2[2] * nl[0] - b2[0] * nl[2]);
+  J[1 * 6 + 5] = 2.0 * (b2[0] * nl[1] - b2[1] * nl[0]);
+  J[2 * 6 + 0] = nl[0];
+  J[2 * 6 + 1] = nl[1];
+  J[2 * 6 + 2] = nl[2];
+}
+
+// One lane per plane prior; the record, the fixed vertex's rule and chi as for prior_record (qinfo: 36 doubles per prior)
+template <bool ROBUST>
+__global__ void pg_plane_prior_kernel(const double *poses, const int32_t *qv, const double *qpl, const double *qinfo, int n_q,
+                                      int fixed, const int32_t *kind, const double *delta, double *rec, double *chi) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_q) return;
+  const int v = qv[p];
+  const Pose x = load_pose(poses + 7 * v);
+  double er[6], J[36], Om[36];
+  plane_prior_error<true>(x, qpl + (size_t)p * QPL, er, J);
+#pragma unroll
+  for (int k = 0; k < 36; ++k) Om[k] = qinfo[(size_t)p * 36 + k];
+  int kd = LSLAM_PG_KERNEL_NONE;
+  double dl = 1.0;
+  if (ROBUST) {
+    kd = kind[p];
+    if (kd != LSLAM_PG_KERNEL_NONE) dl = delta[p];
+  }
+  unary_record<ROBUST>(er, J, Om, kd, dl, v == fixed, rec + (size_t)p * PREC, chi + p);
+}
+// Trial evaluation and tap in one: per plane prior e2, rho0, rho1 at `poses`; any output may be null; kind == nullptr: no kernels
+__global__ void pg_plane_prior_chi2_kernel(const double *poses, const int32_t *qv, const double *qpl, const double *qinfo, int n_q,
+                                           const int32_t *kind, const double *delta, double *e2_out, double *rho_out,
+                                           double *w_out) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_q) return;
+  const Pose x = load_pose(poses + 7 * qv[p]);
+  double er[6];
+  plane_prior_error<false>(x, qpl + (size_t)p * QPL, er, nullptr);
+  const double e2 = edge_e2(qinfo + (size_t)p * 36, er);
+  const int kd = kind ? kind[p] : LSLAM_PG_KERNEL_NONE;
+  double rho0, rho1;
+  robustify(kd, kd != LSLAM_PG_KERNEL_NONE ? delta[p] : 1.0, e2, rho0, rho1);
+  if (e2_out) e2_out[p] = e2;
+  if (rho_out) rho_out[p] = rho0;
+  if (w_out) w_out[p] = rho1;
 }
 
 // fixed-order sum of n doubles into *dst, single block of 1024 (four independent accumulators per thread keep four
@@ -513,6 +610,25 @@ __global__ void pg_assemble_vertex_prior_kernel(const double *rec, const int32_t
     s += rec[(size_t)(code >> 1) * REC + (code & 1) * 42 + k];
   }
   for (int a = p_ptr[v]; a < p_ptr[v + 1]; ++a) s += prec[(size_t)p_adj[a] * PREC + k];
+  if (v == fixed) s = (k < 36 && (k / 6 == k % 6)) ? 1.0 : 0.0;
+  if (k < 36) diag[(size_t)v * 36 + k] = s; else b[(size_t)v * 6 + (k - 36)] = s;
+}
+// ... and with plane priors: behind the vertex's POSE / XYZ priors (p_ptr null: the graph has none), in plane-prior order
+__global__ void pg_assemble_vertex_plane_kernel(const double *rec, const int32_t *v_ptr, const int32_t *v_adj,
+                                                const double *prec, const int32_t *p_ptr, const int32_t *p_adj,
+                                                const double *qrec, const int32_t *q_ptr, const int32_t *q_adj, int n_v,
+                                                int fixed, double *diag, double *b) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int v = t / 42, k = t % 42;
+  if (v >= n_v) return;
+  double s = 0.0;
+  for (int a = v_ptr[v]; a < v_ptr[v + 1]; ++a) {
+    const int code = v_adj[a];
+    s += rec[(size_t)(code >> 1) * REC + (code & 1) * 42 + k];
+  }
+  if (p_ptr)
+    for (int a = p_ptr[v]; a < p_ptr[v + 1]; ++a) s += prec[(size_t)p_adj[a] * PREC + k];
+  for (int a = q_ptr[v]; a < q_ptr[v + 1]; ++a) s += qrec[(size_t)q_adj[a] * PREC + k];
   if (v == fixed) s = (k < 36 && (k / 6 == k % 6)) ? 1.0 : 0.0;
   if (k < 36) diag[(size_t)v * 36 + k] = s; else b[(size_t)v * 6 + (k - 36)] = s;
 }
@@ -1873,6 +1989,16 @@ struct lslam_pg {
   // In a sharded run the system is summed over the ranks, so every prior must be counted once: the rank whose edge range
   // starts at 0 and is not empty carries all of them (a graph without edges: its one range [0, 0) does).
   int local_priors() const { return (e_begin == 0 && (e_end > 0 || n_e == 0)) ? n_p : 0; }
+  // plane priors (lslam_pg_set_plane_priors): a set of their own behind the priors above -- in the per-vertex sums, in d_chi
+  // and in the file lslam_pg_save_g2o writes.  n_q == 0 -- the default -- launches exactly what a graph without them launches.
+  // The host copies are what the caller gave; the device's planes have unit normals, its information is padded to 6x6.
+  int n_q = 0;
+  bool plane_robust = false;
+  std::vector<int32_t> h_qv, h_qkind;
+  std::vector<double> h_qworld, h_qmeas, h_qinfo, h_qdelta;
+  lslam::DevBuf<int32_t> d_qv, d_qkind, d_qptr, d_qadj;
+  lslam::DevBuf<double> d_qpl, d_qinfo, d_qdelta, d_qrec, d_qtap;
+  int local_plane_priors() const { return (e_begin == 0 && (e_end > 0 || n_e == 0)) ? n_q : 0; }
   // shard structures
   lslam::DevBuf<double> d_rec, d_chi;
   lslam::DevBuf<int32_t> d_vptr, d_vadj, d_optr, d_oadj;
@@ -1955,7 +2081,7 @@ int build_shard(lslam_pg *pg, int e_begin, int e_end) {
     oadj[oc[pg->edge_block[e]]++] = le;
   }
   PG_TRY(pg->d_rec.alloc(std::max<size_t>(1, (size_t)ne) * REC));
-  PG_TRY(pg->d_chi.alloc((size_t)ne + (size_t)pg->n_p));  // the priors' values sit behind the edges' (linearize)
+  PG_TRY(pg->d_chi.alloc((size_t)ne + (size_t)pg->n_p + (size_t)pg->n_q));  // the priors' values sit behind the edges', the plane priors' behind those (linearize)
   PG_TRY(dev_upload(pg->d_vptr, vptr));
   PG_TRY(dev_upload(pg->d_vadj, vadj));
   PG_TRY(dev_upload(pg->d_optr, optr));
@@ -1973,13 +2099,24 @@ int linearize(lslam_pg *pg, const double *poses) {
   else if (ne > 0)
     hipLaunchKernelGGL(pg_edge_kernel, dim3((ne + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_ij.p,
                        pg->d_meas.p, pg->d_info.p, pg->e_begin, pg->e_end, pg->fixed, pg->d_rec.p, pg->d_chi.p);
-  const int np = pg->local_priors();
+  const int np = pg->local_priors(), nq = pg->local_plane_priors();
   if (np > 0) {
     const int32_t *kind = pg->prior_robust ? pg->d_pkind.p : nullptr;
     const double *delta = pg->prior_robust ? pg->d_pdelta.p : nullptr;
     hipLaunchKernelGGL(pg->prior_robust ? pg_prior_kernel<true> : pg_prior_kernel<false>, dim3((np + 127) / 128), dim3(128),
                        0, pg->stream, poses, pg->d_pv.p, pg->d_ptype.p, pg->d_pmeas.p, pg->d_pinfo.p, np, pg->fixed, kind,
                        delta, pg->d_prec.p, pg->d_chi.p + ne);
+  }
+  if (nq > 0) {  // plane priors: their records, then ONE assembly that sums edges, priors, plane priors in that order
+    hipLaunchKernelGGL(pg->plane_robust ? pg_plane_prior_kernel<true> : pg_plane_prior_kernel<false>, dim3((nq + 127) / 128),
+                       dim3(128), 0, pg->stream, poses, pg->d_qv.p, pg->d_qpl.p, pg->d_qinfo.p, nq, pg->fixed,
+                       pg->plane_robust ? pg->d_qkind.p : (const int32_t *)nullptr,
+                       pg->plane_robust ? pg->d_qdelta.p : (const double *)nullptr, pg->d_qrec.p, pg->d_chi.p + ne + np);
+    hipLaunchKernelGGL(pg_assemble_vertex_plane_kernel, dim3((pg->n_v * 42 + 255) / 256), dim3(256), 0, pg->stream,
+                       pg->d_rec.p, pg->d_vptr.p, pg->d_vadj.p, pg->d_prec.p, np > 0 ? pg->d_pptr.p : (const int32_t *)nullptr,
+                       pg->d_padj.p, pg->d_qrec.p, pg->d_qptr.p, pg->d_qadj.p, pg->n_v, pg->sharded() ? -1 : pg->fixed,
+                       pg->diag(), pg->b());
+  } else if (np > 0) {
     hipLaunchKernelGGL(pg_assemble_vertex_prior_kernel, dim3((pg->n_v * 42 + 255) / 256), dim3(256), 0, pg->stream,
                        pg->d_rec.p, pg->d_vptr.p, pg->d_vadj.p, pg->d_prec.p, pg->d_pptr.p, pg->d_padj.p, pg->n_v,
                        pg->sharded() ? -1 : pg->fixed, pg->diag(), pg->b());
@@ -1991,7 +2128,7 @@ int linearize(lslam_pg *pg, const double *poses) {
   if (pg->n_off > 0)
     hipLaunchKernelGGL(pg_assemble_off_kernel, dim3((pg->n_off * 36 + 255) / 256), dim3(256), 0, pg->stream,
                        pg->d_rec.p, pg->d_optr.p, pg->d_oadj.p, pg->n_off, pg->off());
-  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne + np, 1, pg->chi());
+  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne + np + nq, 1, pg->chi());
   PG_TRY(hipGetLastError());
   if (pg->sharded()) {
     const int rc = pg->reduce(pg->d_sys.p, pg->core_doubles());
@@ -2021,7 +2158,13 @@ int eval_chi2(lslam_pg *pg, const double *poses, double *out) {
                        dim3(128), 0, pg->stream, poses, pg->d_pv.p, pg->d_ptype.p, pg->d_pmeas.p, pg->d_pinfo.p, np,
                        pg->prior_robust ? pg->d_pkind.p : (const int32_t *)nullptr,
                        pg->prior_robust ? pg->d_pdelta.p : (const double *)nullptr, pg->d_chi.p + ne);
-  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne + np, 1, pg->chi());
+  const int nq = pg->local_plane_priors();
+  if (nq > 0)
+    hipLaunchKernelGGL(pg_plane_prior_chi2_kernel, dim3((nq + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_qv.p, pg->d_qpl.p,
+                       pg->d_qinfo.p, nq, pg->plane_robust ? pg->d_qkind.p : (const int32_t *)nullptr,
+                       pg->plane_robust ? pg->d_qdelta.p : (const double *)nullptr, (double *)nullptr, pg->d_chi.p + ne + np,
+                       (double *)nullptr);
+  hipLaunchKernelGGL(pg_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, pg->stream, pg->d_chi.p, ne + np + nq, 1, pg->chi());
   PG_TRY(hipGetLastError());
   if (pg->sharded()) {
     // chi2 and, next to it, whether this rank's persistent kernels gave way to their launch loops in the solve before:
@@ -3107,8 +3250,8 @@ int lslam_pg_set_priors(lslam_pg *pg, int32_t n_priors, const int32_t *vertex, c
     PG_TRY(dev_upload(pg->d_padj, padj));
     PG_TRY(pg->d_prec.alloc(n * PREC));
   }
-  if ((size_t)(pg->e_end - pg->e_begin) + n > pg->d_chi.cap)  // the priors' chi2 values sit behind the edges'
-    PG_TRY(pg->d_chi.alloc((size_t)(pg->e_end - pg->e_begin) + n));
+  if ((size_t)(pg->e_end - pg->e_begin) + n + (size_t)pg->n_q > pg->d_chi.cap)  // the priors' chi2 values sit behind the edges'
+    PG_TRY(pg->d_chi.alloc((size_t)(pg->e_end - pg->e_begin) + n + (size_t)pg->n_q));
   pg->n_p = (int)n;
   pg->prior_robust = any_kernel;
   pg->h_pv.swap(hv);
@@ -3146,6 +3289,210 @@ int lslam_pg_prior_robust(lslam_pg *pg, const double *poses7, double *e2, double
   if (e2) std::memcpy(e2, h.data(), n * 8);
   if (rho) std::memcpy(rho, h.data() + n, n * 8);
   if (weight) std::memcpy(weight, h.data() + 2 * n, n * 8);
+  return LSLAM_OK;
+}
+
+// ---- plane priors ----------------------------------------------------------------------------------------------------------
+int lslam_pg_set_plane_priors(lslam_pg *pg, int32_t n_priors, const int32_t *vertex, const double *world4, const double *meas4,
+                              const double *info9, const int32_t *kind, const double *delta) {
+  if (!pg || n_priors < 0 || (n_priors > 0 && (!vertex || !world4 || !meas4 || !info9))) {
+    g_pg_err = "plane priors: bad arguments";
+    return LSLAM_ERR_INVALID;
+  }
+  if ((kind == nullptr) != (delta == nullptr)) {
+    g_pg_err = "plane priors: kind and delta are given together, or both NULL";
+    return LSLAM_ERR_INVALID;
+  }
+  PG_TRY(hipSetDevice(pg->device));
+  const size_t n = (size_t)n_priors;
+  std::vector<double> dp(QPL * n), di(36 * n, 0.0), dd(n, 1.0), poses;
+  if (n > 0) {  // the current estimate: a world / measured pair must face the same way under it
+    poses.resize((size_t)pg->n_v * 7);
+    PG_TRY(hipMemcpyAsync(poses.data(), pg->d_poses.p, poses.size() * 8, hipMemcpyDeviceToHost, pg->stream));
+    PG_TRY(hipStreamSynchronize(pg->stream));
+  }
+  bool any_kernel = false;
+  for (size_t p = 0; p < n; ++p) {  // everything is checked before anything changes
+    const std::string at = " (plane prior " + std::to_string(p) + ")";
+    if (vertex[p] < 0 || vertex[p] >= pg->n_v) {
+      g_pg_err = "plane priors: vertex out of range" + at;
+      return LSLAM_ERR_INVALID;
+    }
+    const double *pl[2] = {world4 + 4 * p, meas4 + 4 * p};
+    for (int s = 0; s < 2; ++s) {
+      for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(pl[s][k])) {
+          g_pg_err = std::string("plane priors: ") + (s ? "measured" : "world") + " plane is not finite" + at;
+          return LSLAM_ERR_INVALID;
+        }
+      const double nn = std::sqrt(pl[s][0] * pl[s][0] + pl[s][1] * pl[s][1] + pl[s][2] * pl[s][2]);
+      if (!(nn > 0.0) || !std::isfinite(nn)) {
+        g_pg_err = std::string("plane priors: ") + (s ? "measured" : "world") + " plane has a zero normal" + at;
+        return LSLAM_ERR_INVALID;
+      }
+      // (the plane n.p + d = 0 scaled to a unit normal: d scales with it)
+      for (int k = 0; k < 4; ++k) dp[QPL * p + 4 * s + k] = pl[s][k] / nn;
+    }
+    const double *w = info9 + 9 * p;
+    double big = 0.0;
+    for (int k = 0; k < 9; ++k) {
+      if (!std::isfinite(w[k])) {
+        g_pg_err = "plane priors: information is not finite" + at;
+        return LSLAM_ERR_INVALID;
+      }
+      big = std::max(big, std::fabs(w[k]));
+    }
+    for (int r = 0; r < 3; ++r) {
+      if (w[r * 3 + r] < 0.0) {
+        g_pg_err = "plane priors: information has a negative diagonal entry" + at;
+        return LSLAM_ERR_INVALID;
+      }
+      for (int c = r + 1; c < 3; ++c)
+        if (std::fabs(w[r * 3 + c] - w[c * 3 + r]) > 1e-12 * big) {
+          g_pg_err = "plane priors: information is not symmetric" + at;
+          return LSLAM_ERR_INVALID;
+        }
+    }
+    if (kind) {
+      if (kind[p] < LSLAM_PG_KERNEL_NONE || kind[p] > LSLAM_PG_KERNEL_DCS) {
+        g_pg_err = "plane priors: unknown robust kernel " + std::to_string(kind[p]) + at;
+        return LSLAM_ERR_INVALID;
+      }
+      if (kind[p] != LSLAM_PG_KERNEL_NONE) {
+        if (!std::isfinite(delta[p]) || !(delta[p] > 0.0)) {
+          g_pg_err = "plane priors: delta must be finite and > 0" + at;
+          return LSLAM_ERR_INVALID;
+        }
+        any_kernel = true;
+        dd[p] = delta[p];
+      }
+    }
+    {  // n_l = R^T n_w against n_m
+      const double *x = poses.data() + 7 * (size_t)vertex[p];
+      const double qn = std::sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5] + x[6] * x[6]);
+      const double qx = x[3] / qn, qy = x[4] / qn, qz = x[5] / qn, qw = x[6] / qn;
+      const double R[9] = {1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw),
+                           2 * (qx * qy + qz * qw), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qx * qw),
+                           2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), 1 - 2 * (qx * qx + qy * qy)};
+      const double *nw = dp.data() + QPL * p, *nm = nw + 4;
+      double dot = 0.0;
+      for (int c = 0; c < 3; ++c) dot += (R[c] * nw[0] + R[3 + c] * nw[1] + R[6 + c] * nw[2]) * nm[c];
+      if (!(dot >= 0.0)) {
+        g_pg_err = "plane priors: world and measured normals lie in opposite hemispheres at the current estimate" + at;
+        return LSLAM_ERR_INVALID;
+      }
+    }
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) di[36 * p + r * 6 + c] = w[r * 3 + c];
+  }
+  PG_TRY(hipStreamSynchronize(pg->stream));  // nothing in flight still reads the arrays replaced here
+  std::vector<int32_t> hv(vertex, vertex + n), hk(n, LSLAM_PG_KERNEL_NONE);
+  if (kind) hk.assign(kind, kind + n);
+  // From here on only a device error can stop the call: the graph then has NO plane priors, as for lslam_pg_set_priors
+  pg->n_q = 0;
+  pg->plane_robust = false;
+  pg->h_qv.clear();
+  if (n > 0) {
+    std::vector<int32_t> qptr((size_t)pg->n_v + 1, 0), qadj(n);
+    for (size_t p = 0; p < n; ++p) qptr[(size_t)hv[p] + 1]++;
+    for (int v = 0; v < pg->n_v; ++v) qptr[(size_t)v + 1] += qptr[v];
+    std::vector<int32_t> qc(qptr.begin(), qptr.end() - 1);
+    for (size_t p = 0; p < n; ++p) qadj[qc[hv[p]]++] = (int32_t)p;  // plane-prior order = summation order
+    PG_TRY(dev_upload(pg->d_qv, hv));
+    PG_TRY(dev_upload(pg->d_qpl, dp));
+    PG_TRY(dev_upload(pg->d_qinfo, di));
+    PG_TRY(dev_upload(pg->d_qkind, hk));
+    PG_TRY(dev_upload(pg->d_qdelta, dd));
+    PG_TRY(dev_upload(pg->d_qptr, qptr));
+    PG_TRY(dev_upload(pg->d_qadj, qadj));
+    PG_TRY(pg->d_qrec.alloc(n * PREC));
+  }
+  const size_t chi_need = (size_t)(pg->e_end - pg->e_begin) + (size_t)pg->n_p + n;
+  if (chi_need > pg->d_chi.cap) PG_TRY(pg->d_chi.alloc(chi_need));
+  pg->n_q = (int)n;
+  pg->plane_robust = any_kernel;
+  pg->h_qv.swap(hv);
+  pg->h_qkind.swap(hk);
+  pg->h_qworld.assign(world4, world4 + 4 * n);
+  pg->h_qmeas.assign(meas4, meas4 + 4 * n);
+  pg->h_qinfo.assign(info9, info9 + 9 * n);
+  pg->h_qdelta.swap(dd);
+  return LSLAM_OK;
+}
+
+int32_t lslam_pg_num_plane_priors(const lslam_pg *pg) { return pg ? pg->n_q : 0; }
+
+int lslam_pg_plane_prior_robust(lslam_pg *pg, const double *poses7, double *e2, double *rho, double *weight) {
+  if (!pg) return LSLAM_ERR_INVALID;
+  PG_TRY(hipSetDevice(pg->device));
+  const size_t n = (size_t)pg->n_q;
+  if (n == 0) return LSLAM_OK;
+  const double *poses = pg->d_poses.p;
+  if (poses7) {
+    PG_TRY(pg->d_tap_poses.alloc((size_t)pg->n_v * 7));
+    PG_TRY(hipMemcpyAsync(pg->d_tap_poses.p, poses7, (size_t)pg->n_v * 7 * 8, hipMemcpyHostToDevice, pg->stream));
+    poses = pg->d_tap_poses.p;
+  }
+  PG_TRY(pg->d_qtap.alloc(3 * n));
+  hipLaunchKernelGGL(pg_plane_prior_chi2_kernel, dim3((pg->n_q + 127) / 128), dim3(128), 0, pg->stream, poses, pg->d_qv.p,
+                     pg->d_qpl.p, pg->d_qinfo.p, pg->n_q, pg->plane_robust ? pg->d_qkind.p : (const int32_t *)nullptr,
+                     pg->plane_robust ? pg->d_qdelta.p : (const double *)nullptr, pg->d_qtap.p, pg->d_qtap.p + n,
+                     pg->d_qtap.p + 2 * n);
+  PG_TRY(hipGetLastError());
+  std::vector<double> h(3 * n);
+  PG_TRY(hipMemcpyAsync(h.data(), pg->d_qtap.p, 3 * n * 8, hipMemcpyDeviceToHost, pg->stream));
+  PG_TRY(hipStreamSynchronize(pg->stream));
+  if (e2) std::memcpy(e2, h.data(), n * 8);
+  if (rho) std::memcpy(rho, h.data() + n, n * 8);
+  if (weight) std::memcpy(weight, h.data() + 2 * n, n * 8);
+  return LSLAM_OK;
+}
+
+// The plane priors of a file lslam_pg_save_g2o wrote (host only), in file order; as lslam_g2o_read_priors.
+int lslam_g2o_read_plane_priors(const char *path, int32_t *n_priors, int32_t *vertex, double *world4, double *meas4, double *info9) {
+  if (!path || !n_priors) return LSLAM_ERR_INVALID;
+  std::ifstream ifs(path);
+  if (!ifs) {
+    g_pg_err = std::string("cannot open ") + path;
+    return LSLAM_ERR_INVALID;
+  }
+  std::map<long, int> ids;
+  int nv = 0, np = 0;
+  const int cap = *n_priors;
+  std::string line, tag;
+  while (std::getline(ifs, line)) {
+    std::istringstream ls(line);
+    if (!(ls >> tag)) continue;
+    if (tag == "VERTEX_SE3:QUAT") {
+      long id;
+      if (ls >> id) ids[id] = nv++;
+    } else if (tag == "EDGE_SE3_PRIOR_PLANE") {
+      long v;
+      double m[8], u[6];
+      ls >> v;
+      for (int k = 0; k < 8; ++k) ls >> m[k];
+      for (int k = 0; k < 6; ++k) ls >> u[k];
+      if (!ls) { g_pg_err = "malformed " + tag + " line"; return LSLAM_ERR_INVALID; }
+      auto iv = ids.find(v);
+      if (iv == ids.end()) { g_pg_err = "plane prior refers to an unknown vertex"; return LSLAM_ERR_INVALID; }
+      if (np < cap) {
+        if (vertex) vertex[np] = iv->second;
+        if (world4) for (int k = 0; k < 4; ++k) world4[(size_t)np * 4 + k] = m[k];
+        if (meas4) for (int k = 0; k < 4; ++k) meas4[(size_t)np * 4 + k] = m[4 + k];
+        if (info9) {
+          int q = 0;
+          for (int r = 0; r < 3; ++r)
+            for (int c = r; c < 3; ++c) {
+              info9[(size_t)np * 9 + r * 3 + c] = u[q];
+              info9[(size_t)np * 9 + c * 3 + r] = u[q];
+              ++q;
+            }
+        }
+      }
+      ++np;
+    }
+  }
+  *n_priors = np;
   return LSLAM_OK;
 }
 
@@ -3236,6 +3583,17 @@ int lslam_pg_save_g2o(lslam_pg *pg, const char *path) {
     for (int k = 0; k < (pose ? 7 : 3); ++k) ofs << ' ' << pg->h_pmeas[(size_t)p * 7 + k];
     for (int r = 0; r < d; ++r)
       for (int c = r; c < d; ++c) ofs << ' ' << pg->h_pinfo[(size_t)p * 36 + r * 6 + c];
+    ofs << '\n';
+  }
+  // Plane priors, behind them: this project's OWN tag (no g2o or hdl_graph_slam type reads it) -- vertex, the world plane, the
+  // measured plane (both as given), the 6 upper-triangular information entries.  lslam_g2o_read and lslam_g2o_read_priors
+  // compare whole tags, so they skip these lines; lslam_g2o_read_plane_priors returns them.
+  for (int p = 0; p < pg->n_q; ++p) {
+    ofs << "EDGE_SE3_PRIOR_PLANE " << pg->h_qv[p];
+    for (int k = 0; k < 4; ++k) ofs << ' ' << pg->h_qworld[(size_t)p * 4 + k];
+    for (int k = 0; k < 4; ++k) ofs << ' ' << pg->h_qmeas[(size_t)p * 4 + k];
+    for (int r = 0; r < 3; ++r)
+      for (int c = r; c < 3; ++c) ofs << ' ' << pg->h_qinfo[(size_t)p * 9 + r * 3 + c];
     ofs << '\n';
   }
   return ofs.good() ? LSLAM_OK : LSLAM_ERR_INVALID;

@@ -92,7 +92,9 @@ class Graph:
     def __init__(self, device=0, ctx=None, loop_detector=None, max_keyframes_per_update=10, resident=False,
                  keep_host_clouds=True, store_max_points=0, store_max_keyframes=0, store_slab_points=0, appearance_loops=False,
                  sc_params=None, loop_robust_kernel=None, loop_robust_delta=1.0, edge_information=None, range_sigma=None,
-                 gps_sigma=None, gps_robust_kernel=None, gps_robust_delta=1.0, gps_min_spread=None, imu_orientation_sigma=None):
+                 gps_sigma=None, gps_robust_kernel=None, gps_robust_delta=1.0, gps_min_spread=None, imu_orientation_sigma=None,
+                 floor_sigma=None, floor_params=None, floor_robust_kernel=None, floor_robust_delta=1.0,
+                 floor_world_plane=(0.0, 0.0, 1.0, 0.0), odometry_information=None):
         """``resident=True``: the keyframes' clouds live in a :class:`KeyframeStore` on the loop detector's context --
         ``add_frame`` uploads them once (``kf.store_id``), loop closure and ``get_final_feature_map`` read them there;
         ``keep_host_clouds=False`` then drops the host copies (``kf.corner_cloud`` / ``kf.surf_cloud`` fetch on demand).
@@ -126,7 +128,41 @@ class Graph:
         rebuilt with no fixed vertex.  ``imu_orientation_sigma`` [rad]: ``add_frame(imu_quat=...)`` (x, y, z, w, in the frame
         the fixes are in) becomes a POSE prior with a zero translation block and ``(2 / sigma)^2`` on the quaternion vector
         (half the angle); queued with the fixes when ``gps_sigma`` is set.  ``optimize`` then runs the solver when a pass
-        added loops OR priors.  All of it is off by default."""
+        added loops OR priors.  All of it is off by default.
+        ``floor_sigma=(sigma_normal [rad], sigma_distance [m])`` (not in the reference, which only shows the intent:
+        solver_g2o.h:61-65, :92, graph.cpp:321 "floor coeffs"): on each pass the floor of every new keyframe's surface cloud is
+        detected on the device -- one ``lslam_floor_detect_keyframes`` call over the store with ``resident=True``, one
+        ``lslam_floor_detect`` per cloud on ``ctx`` otherwise -- with ``floor_params`` (:func:`floor.floor_params`' keywords;
+        None: the defaults).  An accepted floor (status OK) is stored as ``kf.floor_coeffs`` (n, d in the sensor frame) and
+        becomes a plane prior (``lslam_pg_set_plane_priors``) against ``floor_world_plane`` -- the floor in the GRAPH frame,
+        z = 0 by default: a graph frame that starts at the first sensor pose has its floor at (0, 0, 1, sensor_height) -- with
+        information ``diag(1/sn^2, 1/sn^2, 1/sd^2)`` and ``floor_robust_kernel`` / ``floor_robust_delta`` (a kerb or a ramp
+        taken for the floor: "Cauchy" rejects it; :meth:`floor_weights`, :meth:`rejected_floors`).  A keyframe whose floor was
+        not found adds nothing and is counted (``floors_not_found``).  Like the other sigmas it has no default.
+        LIMIT of ``floor_robust_kernel`` (and of every kernel here): with the reference's constant odometry information
+        (sigma about 1 m / 0.7 rad) bending the trajectory onto an outlying floor costs less than ANY kernel charges for
+        rejecting it, so no kernel rejects in the default configuration; it does once the edges are worth something --
+        ``odometry_information`` or ``edge_information="hessian"`` (DESIGN, pose-graph section).
+        ``odometry_information`` (6x6, or its 6 diagonal entries, over [translation, rotation]): the information of every
+        odometry edge; None: the reference's constant (graph.cpp:279-288)."""
+        if odometry_information is None:
+            self.odometry_information = ODOMETRY_INFORMATION
+        else:
+            w = np.asarray(odometry_information, np.float64)
+            self.odometry_information = np.diag(w) if w.shape == (6,) else w.reshape(6, 6).copy()
+        self.floor_sigma = None
+        if floor_sigma is not None:
+            sn, sd = (float(v) for v in floor_sigma)
+            if not (sn > 0.0 and sd > 0.0 and np.isfinite(sn) and np.isfinite(sd)):
+                raise ValueError("Graph: floor_sigma is (sigma_normal [rad], sigma_distance [m]), both > 0")
+            self.floor_sigma = (sn, sd)
+        self.floor_params = floor_params
+        self.floor_robust_kernel = floor_robust_kernel if kernel_kind(floor_robust_kernel) else None
+        self.floor_robust_delta = float(floor_robust_delta)
+        self.floor_world_plane = np.array(floor_world_plane, np.float64).reshape(4)
+        self.floors = []            # (keyframe, plane prior index in the solver) of every accepted floor
+        self.floors_not_found = []  # (keyframe, LSLAM_FLOOR_* status) of every keyframe whose floor was not found
+        self.ctx = ctx
         self.gps_sigma = None
         if gps_sigma is not None:
             sxy, sz = (float(v) for v in gps_sigma)
@@ -208,9 +244,9 @@ class Graph:
                 continue
             prev = self.keyframes[-1] if i == 0 else self.keyframe_queue[i - 1]
             relative = np.linalg.inv(prev.odom) @ kf.odom
-            info = ODOMETRY_INFORMATION
+            info = self.odometry_information
             if self.edge_information == "hessian":  # the previous keyframe is the reference, the edge's measurement the pose
-                info = self._hessian_information(ODOMETRY_INFORMATION, [prev.store_id], np.eye(4, dtype=np.float32)[None],
+                info = self._hessian_information(self.odometry_information, [prev.store_id], np.eye(4, dtype=np.float32)[None],
                                                  kf.store_id, relative.astype(np.float32))
             self.solver.add_se3_edge(prev.node, kf.node, relative, info)
         del self.keyframe_queue[:n]
@@ -251,9 +287,10 @@ class Graph:
         self.loops.extend(loops)
         self.keyframes.extend(self.new_keyframes)
         added_priors = self._add_priors(self.new_keyframes)
+        added_floors = self._add_floors(self.new_keyframes)
         self.new_keyframes = []
         iterations = 0
-        if (loops or added_priors) and not self._bookkeeping_only:
+        if (loops or added_priors or added_floors) and not self._bookkeeping_only:
             iterations = self.solver.optimize(max_iterations)
             poses = self.solver.poses()
             from .pose_graph import pose7_to_mat
@@ -328,6 +365,45 @@ class Graph:
     def rejected_fixes(self, threshold=0.1):
         """The keyframes whose fix has a weight below ``threshold``.  Reporting only: nothing is removed from the graph."""
         return [kf for (kf, _), w in zip(self.gps_fixes, self.gps_weights()) if w < threshold]
+
+    # ---- floor planes as plane priors (not in the reference) ----------------------------------------------------------------
+    def _add_floors(self, new_keyframes):
+        """The floors of a pass's new keyframes: detected in one call over the store (resident) or per cloud, the accepted ones
+        added as plane priors.  -> whether any reached the solver."""
+        if self.floor_sigma is None or not new_keyframes:
+            return False
+        from . import floor as floor_mod
+        if self.store is not None:
+            results = self.store.floor_detect([kf.store_id for kf in new_keyframes], self.floor_params)
+        else:
+            ctx = self.ctx or self.loop_detector.scan_match.ctx
+            results = [floor_mod.detect(ctx, kf.surf_cloud, self.floor_params) for kf in new_keyframes]
+        sn, sd = self.floor_sigma
+        info = np.diag([1.0 / (sn * sn), 1.0 / (sn * sn), 1.0 / (sd * sd)])
+        added = False
+        for kf, r in zip(new_keyframes, results):
+            kf.floor_result = r
+            if r["status"] != floor_mod.FLOOR_OK:
+                kf.floor_coeffs = None
+                self.floors_not_found.append((kf, r["status"]))
+                continue
+            kf.floor_coeffs = np.array(r["plane"], np.float64)
+            self.floors.append((kf, self.solver.add_se3_prior_plane_edge(
+                kf.node, kf.floor_coeffs, info, world_plane4=self.floor_world_plane, robust_kernel=self.floor_robust_kernel,
+                robust_delta=self.floor_robust_delta)))
+            added = True
+        return added
+
+    def floor_weights(self):
+        """The robust weight (rho1) of every plane prior in ``self.floors`` at the solver's current estimate; all 1 without
+        ``floor_robust_kernel``."""
+        if not self.floors:
+            return np.zeros(0)
+        return self.solver.plane_prior_robust()["weight"][np.asarray([p for _, p in self.floors], np.int64)]
+
+    def rejected_floors(self, threshold=0.1):
+        """The keyframes whose floor has a weight below ``threshold``.  Reporting only: nothing is removed from the graph."""
+        return [kf for (kf, _), w in zip(self.floors, self.floor_weights()) if w < threshold]
 
     def loop_weights(self):
         """The robust weight (rho1) of every entry of ``self.loops`` at the solver's current estimate, i.e. after the last

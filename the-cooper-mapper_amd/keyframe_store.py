@@ -168,6 +168,17 @@ class KeyframeStore:
         T = np.ascontiguousarray(tf, dtype=np.float32).reshape(16)
         self._check(self.lib.lslam_kfs_add_to_fmap(self.h, int(kid), fmap.h, _fp(T)))
 
+    def floor_detect(self, ids, params=None):
+        """``lslam_floor_detect_keyframes``: the floor of each named keyframe's surface cloud, where it lies -- every keyframe
+        through each stage in one launch, no cloud moved -> one result dict per id (:mod:`.floor`)."""
+        from .capi import LslamFloorResult
+        from .floor import floor_params
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        p = floor_params(params)
+        res = (LslamFloorResult * max(len(ids), 1))()
+        self._check(self.lib.lslam_floor_detect_keyframes(self.h, len(ids), ids.ctypes.data_as(c_int32_p), C.byref(p), res))
+        return [res[i].as_dict() for i in range(len(ids))]
+
     # ---- loop candidates by appearance: scan context (lslam_sc_*) ---------------------------------------------------------
     def sc_setup(self, **params):
         """Install the scan-context parameters (``n_ring``, ``n_sector``, ``max_range``, ``height_offset``, ``up_axis``;

@@ -86,6 +86,7 @@ class PoseGraph:
         self._kind = []   # per edge: LSLAM_PG_KERNEL_* and its delta; applied by _build, so they survive a topology change
         self._delta = []
         self._priors = []  # unary constraints: dicts (vertex, type, meas (7), info (6, 6), kind, delta); applied by _build
+        self._plane_priors = []  # plane priors: dicts (vertex, world (4), meas (4), info (3, 3), kind, delta); applied by _build
         self.fixed = int(fixed)  # the vertex lslam_pg_create pins (g2o: setFixed); -1 pins none
         self.h = None
         self._cb = None
@@ -133,6 +134,72 @@ class PoseGraph:
         self._drop()
         self._priors.append(dict(vertex=int(v), type=int(type_), meas=meas, info=info, kind=kind, delta=float(robust_delta)))
         return len(self._priors) - 1
+
+    def add_se3_prior_plane_edge(self, v, measured_plane4, info3, world_plane4=(0.0, 0.0, 1.0, 0.0), robust_kernel=None,
+                                 robust_delta=1.0):
+        """hdl_graph_slam's floor constraint (not in the reference, which only shows the intent): the plane `world_plane4`
+        = (n, d) of the graph frame was measured as `measured_plane4` in the sensor frame of vertex `v`; `info3` is the 3x3
+        information over (tangent 1, tangent 2, distance) -- include/lslam_c.h, "plane priors".  Returns the plane prior's index."""
+        kind = kernel_kind(robust_kernel)
+        self._drop()
+        self._plane_priors.append(dict(vertex=int(v), world=np.asarray(world_plane4, np.float64).reshape(4).copy(),
+                                       meas=np.asarray(measured_plane4, np.float64).reshape(4).copy(),
+                                       info=np.asarray(info3, np.float64).reshape(3, 3).copy(), kind=kind, delta=float(robust_delta)))
+        return len(self._plane_priors) - 1
+
+    @property
+    def num_plane_priors(self):
+        return int(self.lib.lslam_pg_num_plane_priors(self.h)) if self.h else len(self._plane_priors)
+
+    @staticmethod
+    def _plane_prior_list(priors):
+        """dict(vertex (n), world (n, 4), meas (n, 4), info (n, 3, 3)[, kernels (n), deltas (n or scalar)]) or None -> list"""
+        if priors is None:
+            return []
+        vertex = np.asarray(priors["vertex"]).reshape(-1)
+        n = len(vertex)
+        world = np.asarray(priors["world"], np.float64).reshape(n, 4)
+        meas = np.asarray(priors["meas"], np.float64).reshape(n, 4)
+        info = np.asarray(priors["info"], np.float64).reshape(n, 3, 3)
+        kind, delta = PoseGraph._kernel_lists(priors.get("kernels"), priors.get("deltas"), n)
+        return [dict(vertex=int(vertex[p]), world=world[p].copy(), meas=meas[p].copy(), info=info[p].copy(), kind=kind[p],
+                     delta=float(delta[p])) for p in range(n)]
+
+    def set_plane_priors(self, priors):
+        """Replace the whole set of plane priors (lslam_pg_set_plane_priors); None or an empty set clears.  Checked by the
+        library: on an error nothing changes."""
+        new = self._plane_prior_list(priors)
+        if self.h:
+            self._upload_plane_priors(new)
+        self._plane_priors = new
+
+    def plane_prior_robust(self, poses=None):
+        """Per plane prior at `poses` ((n, 7); None: the current estimate): dict(e2, rho = rho0, weight = rho1)."""
+        self._build()
+        n = len(self._plane_priors)
+        e2, rho, w = np.zeros(n), np.zeros(n), np.zeros(n)
+        p = None
+        if poses is not None:
+            p = np.ascontiguousarray(poses, np.float64)
+            if p.shape != (len(self._nodes), 7):
+                raise ValueError("poses must be (%d, 7)" % len(self._nodes))
+        self._check(self.lib.lslam_pg_plane_prior_robust(self.h, _dp(p) if p is not None else None, _dp(e2), _dp(rho), _dp(w)))
+        return dict(e2=e2, rho=rho, weight=w)
+
+    def _upload_plane_priors(self, priors):
+        n = len(priors)
+        if n == 0:
+            self._check(self.lib.lslam_pg_set_plane_priors(self.h, 0, None, None, None, None, None, None))
+            return
+        v = np.ascontiguousarray([q["vertex"] for q in priors], np.int32)
+        a = np.ascontiguousarray(np.stack([q["world"] for q in priors]), np.float64)
+        m = np.ascontiguousarray(np.stack([q["meas"] for q in priors]), np.float64)
+        w = np.ascontiguousarray(np.stack([q["info"] for q in priors]), np.float64)
+        k = np.ascontiguousarray([q["kind"] for q in priors], np.int32)
+        d = np.ascontiguousarray([q["delta"] for q in priors], np.float64)
+        robust = bool((k != KERNEL_NONE).any())
+        self._check(self.lib.lslam_pg_set_plane_priors(self.h, n, v.ctypes.data_as(c_int32_p), _dp(a), _dp(m), _dp(w),
+                                                       k.ctypes.data_as(c_int32_p) if robust else None, _dp(d) if robust else None))
 
     @property
     def num_priors(self):
@@ -199,17 +266,20 @@ class PoseGraph:
         return st.iterations
 
     # ---- bulk construction / access ---------------------------------------------------
-    def set_graph(self, poses7, ij, meas7, info, fixed=0, kernels=None, deltas=None, priors=None):
+    def set_graph(self, poses7, ij, meas7, info, fixed=0, kernels=None, deltas=None, priors=None, plane_priors=None):
         """Replace the graph; `fixed` is the vertex held at its estimate (default: the first, as add_se3_node; -1: none, for
         graphs whose priors fix the gauge).  `kernels` / `deltas`: per edge, as set_robust_kernels (None: plain edges).
-        `priors`: None or dict(vertex (n), type (n) of PRIOR_XYZ / PRIOR_POSE, meas (n, 7), info (n, 6, 6)[, kernels, deltas])."""
+        `priors`: None or dict(vertex (n), type (n) of PRIOR_XYZ / PRIOR_POSE, meas (n, 7), info (n, 6, 6)[, kernels, deltas]).
+        `plane_priors`: None or dict(vertex (n), world (n, 4), meas (n, 4), info (n, 3, 3)[, kernels, deltas])."""
         new_priors = self._prior_list(priors)
+        new_planes = self._plane_prior_list(plane_priors)
         kind, delta = self._kernel_lists(kernels, deltas, len(np.asarray(ij).reshape(-1, 2)))  # raises before anything is dropped
         if int(fixed) >= len(np.asarray(poses7).reshape(-1, 7)):
             raise ValueError("fixed vertex %d of a graph with %d vertices" % (int(fixed), len(np.asarray(poses7).reshape(-1, 7))))
         self._drop(keep_estimates=False)
         self._kind, self._delta = kind, delta
         self._priors = new_priors
+        self._plane_priors = new_planes
         self._nodes = [p for p in np.asarray(poses7, np.float64).reshape(-1, 7)]
         self._ij = [tuple(int(v) for v in e) for e in np.asarray(ij).reshape(-1, 2)]
         self._meas = [m for m in np.asarray(meas7, np.float64).reshape(-1, 7)]
@@ -273,7 +343,7 @@ class PoseGraph:
     # ---- g2o text format (solver_g2o.cpp:97-100) -----------------------------------------
     def save(self, path):
         """SolverG2O::save: the graph with its current estimates as a .g2o file, priors included (EDGE_SE3_PRIOR /
-        EDGE_SE3_PRIORXYZ lines).  The format has no place for a robust kernel: none is written, and a graph loaded back has
+        EDGE_SE3_PRIORXYZ lines, and this project's own EDGE_SE3_PRIOR_PLANE lines for plane priors).  The format has no place for a robust kernel: none is written, and a graph loaded back has
         plain edges and priors."""
         self._build()
         self._check(self.lib.lslam_pg_save_g2o(self.h, str(path).encode()))
@@ -306,15 +376,25 @@ class PoseGraph:
                                        _dp(pm), _dp(pw))
         if rc < 0:
             raise LslamError(rc, lib.lslam_pg_last_error().decode())
-        return dict(poses=poses, ij=ij, meas=meas, info=info, fixed=fx.value, priors=dict(vertex=pv, type=pt, meas=pm, info=pw))
+        nq = C.c_int32(0)
+        rc = lib.lslam_g2o_read_plane_priors(str(path).encode(), C.byref(nq), None, None, None, None)
+        if rc < 0:
+            raise LslamError(rc, lib.lslam_pg_last_error().decode())
+        qv, qa, qm, qw = np.zeros(nq.value, np.int32), np.zeros((nq.value, 4)), np.zeros((nq.value, 4)), np.zeros((nq.value, 3, 3))
+        rc = lib.lslam_g2o_read_plane_priors(str(path).encode(), C.byref(nq), qv.ctypes.data_as(c_int32_p), _dp(qa), _dp(qm), _dp(qw))
+        if rc < 0:
+            raise LslamError(rc, lib.lslam_pg_last_error().decode())
+        return dict(poses=poses, ij=ij, meas=meas, info=info, fixed=fx.value, priors=dict(vertex=pv, type=pt, meas=pm, info=pw),
+                    plane_priors=dict(vertex=qv, world=qa, meas=qm, info=qw))
 
     def load(self, path):
         """Replace the graph by the one in a .g2o file, its priors included; the file's FIX vertex stays the fixed one.  A
         file without FIX: the first vertex, as add_se3_node -- unless the file holds priors, which then fix the gauge (-1)."""
         g = PoseGraph.read_g2o(path, self.lib)
         has_priors = len(g["priors"]["vertex"]) > 0
+        has_planes = len(g["plane_priors"]["vertex"]) > 0
         self.set_graph(g["poses"], g["ij"], g["meas"], g["info"], fixed=g["fixed"] if g["fixed"] >= 0 or has_priors else 0,
-                       priors=g["priors"] if has_priors else None)
+                       priors=g["priors"] if has_priors else None, plane_priors=g["plane_priors"] if has_planes else None)
         return g
 
     def poses(self):
@@ -467,6 +547,8 @@ class PoseGraph:
                 self._upload_kernels(self._kind, self._delta)
             if self._priors:
                 self._upload_priors(self._priors)
+            if self._plane_priors:
+                self._upload_plane_priors(self._plane_priors)
         except Exception:
             self._drop(keep_estimates=False)
             raise
