@@ -1461,6 +1461,19 @@ uint64_t lslam_debug_grid_lean_launches(lslam_ctx *ctx);
 /* ... of which those whose second pass took ITS lean instantiation (sweep_queue_kernel<256, true, 12, 1, true>; LSLAM_QUEUE_LEAN=0
    in the environment a context is made in keeps the general one) */
 uint64_t lslam_debug_queue_lean_launches(lslam_ctx *ctx);
+/* ... of the lean ones, those that took the instantiation with the in-range fit (sweep_grid_kernel<256, true, *, true>, and
+   sweep_queue_kernel<256, true, 12, 1, true, true> where the second pass is lean; LSLAM_FIT_INRANGE=0 in the environment a
+   context is made in, or a build with -DLSLAM_FIT_INRANGE_DEFAULT=0, keeps `/` and sqrtf in the lean kernels' fit) */
+uint64_t lslam_debug_fit_inrange_launches(lslam_ctx *ctx);
+/* The in-range fit's parts on their own (for the tests).  _ops: for n operand pairs out8[8 i ..] = div_inrange(a, b), a / b,
+ * sqrt_inrange(a), sqrtf(a), the guard's verdict on a and b (an int32 in a float's place: bits 0, 1), the refined reciprocal of
+ * b, the literal the divisions by 5 start from, div_inrange(a, 5).  _fits: one plane fit (is_surf) or line fit with its
+ * coefficient per element, on five neighbours nb_xyzw[20 i ..] and the point x_xyzw[4 i ..], in range and as every other kernel
+ * fits: out_*8[8 i ..] = plane[4] (or A[3], B[0]) and coeff[4]; flags[i]: bits 0 / 1 the coefficient kept (in range / general),
+ * bits 2 / 3 the fit matched, bit 4 the plane fit's guard refused an operand. */
+int lslam_debug_fit_inrange_ops(lslam_ctx *ctx, const float *a, const float *b, size_t n, float *out8);
+int lslam_debug_fit_inrange_fits(lslam_ctx *ctx, const float *nb_xyzw, const float *x_xyzw, size_t n, int32_t is_surf, float *out_inr8, float *out_gen8,
+                                 int32_t *flags);
 /* ... of which those whose first pass read the x-subdivided cell tables (LSLAM_AB_GRID_CUBIC), lean or general */
 uint64_t lslam_debug_grid_fine_launches(lslam_ctx *ctx);
 /* the x-subdivided tables of the resident map: out[0], out[1] sub-cells per cell used (corner, surf; lowered where the table's

@@ -211,6 +211,8 @@ struct lslam_ctx {
   uint64_t sweep_variants[SWEEP_N_VARIANTS] = {0};  // sweep launches per kernel instantiation (lslam_debug_sweep_launches)
   uint64_t grid_lean_launches = 0;                  // ... of SWEEP_VARIANT_GRID's, those that took the lean instantiation (lslam_debug_grid_lean_launches)
   uint64_t queue_lean_launches = 0;                 // ... and those whose second pass took its lean instantiation (lslam_debug_queue_lean_launches)
+  uint64_t fit_inrange_launches = 0;                // ... and the lean first passes that took the instantiation with the in-range fit (lslam_debug_fit_inrange_launches)
+  bool env_fit_inrange = LSLAM_FIT_INRANGE_DEFAULT != 0;  // LSLAM_FIT_INRANGE=0: the lean kernels keep `/` and sqrtf in the fit (to measure it alone); =1 where the build's default is 0
   bool env_queue_lean = true;                       // LSLAM_QUEUE_LEAN=0: the second pass keeps the general kernel where the first is lean (to measure it alone)
   // cell grids over the whole-map trees (lslam_grid.hpp), built the first time the grid search is asked for on a map
   GridDev kc, ks;
@@ -479,18 +481,20 @@ hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, bool g
   if (a.grid) {  // the grid sweep: probe + proof for every point, then the tree search for the points it listed; timed as one
     if (a.nb_total <= 0 || a.n_groups <= 0 || !a.need_cnt) return a.nb_total <= 0 ? hipSuccess : hipErrorInvalidValue;
     const bool lean = grid_sweep_lean_ok(a, jtj_mode) && !general;  // the production loop's launch takes the lean instantiation
+    const bool inr = lean && ctx->env_fit_inrange;  // ... with the in-range fit, in both passes
     hipError_t e;
     if (fine && a.grid == 1 && ctx->kfc.view.cell_start && ctx->kfs.view.cell_start) {
       SweepArgs af = a;
       af.kc = ctx->kfc.view;
       af.ks = ctx->kfs.view;
-      e = launch_sweep_grid(af, jtj_mode, ctx->stream, e0, nullptr, lean, true);
+      e = launch_sweep_grid(af, jtj_mode, ctx->stream, e0, nullptr, lean, true, inr);
       ctx->grid_fine_launches++;
     } else {
-      e = launch_sweep_grid(a, jtj_mode, ctx->stream, e0, nullptr, lean);
+      e = launch_sweep_grid(a, jtj_mode, ctx->stream, e0, nullptr, lean, false, inr);
     }
     ctx->sweep_variants[SWEEP_VARIANT_GRID]++;
     if (lean) ctx->grid_lean_launches++;
+    if (inr) ctx->fit_inrange_launches++;
     if (e != hipSuccess) return e;
     bool planned = false;
     if (a.grid == 2) {  // no trees: the listed points' neighbours come from the wide probe, the queue only runs their residual chain
@@ -507,7 +511,7 @@ hipError_t sweep_launch(lslam_ctx *ctx, const SweepArgs &a, int jtj_mode, bool g
     if (e1) return hipEventRecord(e1, ctx->stream);
     return hipSuccess;
 #endif
-    e = launch_sweep_queue(a, jtj_mode, ctx->stream, e1, pass2, plan, planned, lean2);
+    e = launch_sweep_queue(a, jtj_mode, ctx->stream, e1, pass2, plan, planned, lean2, lean2 && inr);
     ctx->queue_launches++;
     if (lean2) ctx->queue_lean_launches++;
     return e;
@@ -675,6 +679,7 @@ int lslam_ctx_create(int device, lslam_ctx **out) {
   if (const char *v = std::getenv("LSLAM_GRID_CELL_CORNER")) ctx->env_grid_cell_corner = (float)std::atof(v);
   if (const char *v = std::getenv("LSLAM_GRID_XSUB")) ctx->env_grid_xsub = std::max(1, std::min(std::atoi(v), GRID_MAX_XSUB));
   if (const char *v = std::getenv("LSLAM_QUEUE_LEAN")) ctx->env_queue_lean = std::atoi(v) != 0;
+  if (const char *v = std::getenv("LSLAM_FIT_INRANGE")) ctx->env_fit_inrange = std::atoi(v) != 0;
   if (const char *v = std::getenv("LSLAM_DEBUG_CERT_STATS")) ctx->env_debug_cert_stats = std::atoi(v);
   if (const char *v = std::getenv("LSLAM_FORCE_STACK")) {
     if (!std::strcmp(v, "deep")) ctx->env_force_stack = SWEEP_STACK_DEEP;
@@ -768,6 +773,44 @@ void lslam_debug_lazy_trees(lslam_ctx *ctx, uint64_t out[3]) {
 uint64_t lslam_debug_grid_launches(lslam_ctx *ctx) { return ctx ? ctx->sweep_variants[SWEEP_VARIANT_GRID] : 0; }
 uint64_t lslam_debug_grid_lean_launches(lslam_ctx *ctx) { return ctx ? ctx->grid_lean_launches : 0; }
 uint64_t lslam_debug_queue_lean_launches(lslam_ctx *ctx) { return ctx ? ctx->queue_lean_launches : 0; }
+uint64_t lslam_debug_fit_inrange_launches(lslam_ctx *ctx) { return ctx ? ctx->fit_inrange_launches : 0; }
+
+// the in-range fit's parts on host arrays (buffers of their own, freed before returning)
+namespace {
+struct TmpDev {
+  void *p = nullptr;
+  explicit TmpDev(size_t bytes) { if (bytes && hipMalloc(&p, bytes) != hipSuccess) p = nullptr; }
+  ~TmpDev() { if (p) (void)hipFree(p); }
+  TmpDev(const TmpDev &) = delete;
+  TmpDev &operator=(const TmpDev &) = delete;
+};
+}  // namespace
+int lslam_debug_fit_inrange_ops(lslam_ctx *ctx, const float *a, const float *b, size_t n, float *out8) {
+  if (!ctx || !a || !b || !out8 || n == 0 || n > (1u << 24)) return LSLAM_ERR_INVALID;
+  if (hipSetDevice(ctx->device) != hipSuccess) return LSLAM_ERR_HIP;
+  TmpDev da(n * 4), db(n * 4), dout(n * 32);
+  if (!da.p || !db.p || !dout.p) return LSLAM_ERR_HIP;
+  if (hipMemcpy(da.p, a, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(db.p, b, n * 4, hipMemcpyHostToDevice) != hipSuccess) return LSLAM_ERR_HIP;
+  if (launch_fit_inrange_ops((const float *)da.p, (const float *)db.p, (int)n, (float *)dout.p, ctx->stream) != hipSuccess) return LSLAM_ERR_HIP;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return LSLAM_ERR_HIP;
+  if (hipMemcpy(out8, dout.p, n * 32, hipMemcpyDeviceToHost) != hipSuccess) return LSLAM_ERR_HIP;
+  return LSLAM_OK;
+}
+int lslam_debug_fit_inrange_fits(lslam_ctx *ctx, const float *nb_xyzw, const float *x_xyzw, size_t n, int32_t is_surf, float *out_inr8, float *out_gen8,
+                                 int32_t *flags) {
+  if (!ctx || !nb_xyzw || !x_xyzw || !out_inr8 || !out_gen8 || !flags || n == 0 || n > (1u << 22)) return LSLAM_ERR_INVALID;
+  if (hipSetDevice(ctx->device) != hipSuccess) return LSLAM_ERR_HIP;
+  TmpDev dn(n * 80), dx(n * 16), di(n * 32), dg(n * 32), df(n * 4);
+  if (!dn.p || !dx.p || !di.p || !dg.p || !df.p) return LSLAM_ERR_HIP;
+  if (hipMemcpy(dn.p, nb_xyzw, n * 80, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dx.p, x_xyzw, n * 16, hipMemcpyHostToDevice) != hipSuccess) return LSLAM_ERR_HIP;
+  if (launch_fit_inrange_fits((const float4 *)dn.p, (const float4 *)dx.p, (int)n, is_surf, (float *)di.p, (float *)dg.p, (int32_t *)df.p, ctx->stream) != hipSuccess)
+    return LSLAM_ERR_HIP;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return LSLAM_ERR_HIP;
+  if (hipMemcpy(out_inr8, di.p, n * 32, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out_gen8, dg.p, n * 32, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(flags, df.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return LSLAM_ERR_HIP;
+  return LSLAM_OK;
+}
 uint64_t lslam_debug_grid_fine_launches(lslam_ctx *ctx) { return ctx ? ctx->grid_fine_launches : 0; }
 void lslam_debug_grid_fine_info(lslam_ctx *ctx, uint64_t out[4], float *build_ms) {
   const bool have = ctx && ctx->kfc.view.cell_start && ctx->kfs.view.cell_start;

@@ -816,11 +816,86 @@ LSLAM_DEV void eig_sym6_values(const float (&A)[36], float (&evals)[6]) {
   for (int i = 0; i < N; ++i) evals[i] = diag[i] * scale;
 }
 
+// ---------------------------------------------------------------------------
+// The in-range fit ("The in-range fit").  `a / b` and sqrtf(x) compile to a core chain wrapped in range steps:
+//   a / b     v_div_scale_f32 x 2, [v_rcp_f32, 2 fma, mul, 4 fma -- the last of them v_div_fmas_f32], v_div_fixup_f32
+//   sqrtf(x)  x < 2^-96 ? x * 2^32 : x, [v_sqrt_f32, the +-1 ulp residual test], * 2^-16 if scaled, x itself for +-0 / +inf
+// div_inrange / sqrt_inrange are the bracketed chains alone.  From the ISA's definitions of the range steps:
+//   v_div_scale_f32 returns its operand unscaled and clears VCC unless a or b is zero, exp(a) - exp(b) >= 96, b is
+//     denormal, 1 / b is denormal (|b| > 2^126), a / b is denormal (exp(a) - exp(b) <= -126) or a's biased exponent is <= 23
+//     (|a| < 2^-103);
+//   v_div_fmas_f32 is a plain fma while VCC is clear;
+//   v_div_fixup_f32 hands its first operand on with the sign sign(a) ^ sign(b) -- the sign the chain's quotient has --
+//     unless a or b is NaN, infinite or zero, or exp(a) - exp(b) < -150, or the quotient overflows.
+// So for FIT_LO <= |a|, |b| <= FIT_HI (2^-30, 2^30: exp(a) - exp(b) within +-61) div_inrange(a, b) IS the instruction
+// sequence of a / b, same operands, same bits.  A numerator +0 gives the +-0 of a / b as well (every product and residual of
+// the chain is a zero of the right sign), and so does -0 over a negative b; -0 over a positive b gives +0 where a / b gives -0:
+// FitRange refuses every zero numerator.  One more refusal keeps the claim free of what v_rcp_f32 returns within its ulp: for
+// b = +-(2 - 2^-23) 2^m (mantissa all ones) and a a power of two the quotient lies 2^-25 above a rounding tie, and the chain
+// reaches it only from the correctly rounded seed -- from either neighbour it stops on the tie (tools/fit_inrange_ref.cpp
+// finds no other such pair); a / b has the same chain and so the same seed, but FitRange::den refuses such a b all the same, so
+// that div_inrange is the correctly rounded quotient for ANY seed within one ulp.  sqrt_inrange(x) is sqrtf's sequence for 2^-96 <= x < inf (and gives +0 for +0).
+// FitRange is shown the operands of a fit as they come; after the fit `bad` says whether any of them was outside, and the
+// caller -- a whole wavefront, by ballot -- then fits again with `/` and sqrtf.  If none was, every division and square
+// root of the fit returned what `/` and sqrtf return (by induction along the fit: the first one that did not had an
+// operand outside), so the fit's results are the general code's bit for bit.  The tests are comparisons a NaN fails, one
+// v_cmp each into a lane mask.  `low` is for an operand whose upper bound another operand's test implies (the notes at the
+// calls say which: an entry of a column is below its norm, a Householder vector's below beta, ...): with every tested
+// operand in [FIT_LO, FIT_HI] the untested sides stay within [FIT_LO, 8 FIT_HI], exp(a) - exp(b) within +-63, and every
+// intermediate of the fit is finite ("The in-range fit", has the bounds).
+// ---------------------------------------------------------------------------
+constexpr float FIT_LO = 0x1p-30f, FIT_HI = 0x1p30f;
+// what the chain's two refinement steps make of v_rcp_f32(5.0f) -- for the correctly rounded seed 0x3e4ccccd and for both of
+// its neighbours (tools/fit_inrange_ref.cpp works the three out; tests/test_gpu_fit_inrange.py checks it on the device)
+constexpr float FIT_RCP5 = 0x1.99999ap-3f;
+
+struct FitRange {
+  bool bad = false;
+  LSLAM_DEV void low(float a) { bad = bad || !(__builtin_fabsf(a) >= FIT_LO); }
+  LSLAM_DEV void both(float a) { bad = bad || !(__builtin_fabsf(a) >= FIT_LO) || !(__builtin_fabsf(a) <= FIT_HI); }
+  // a denominator's mantissa (its range goes through low / both, or is implied): all ones is refused
+  LSLAM_DEV void den(float b) { bad = bad || (__float_as_uint(b) | 0xff800000u) == 0xffffffffu; }
+};
+// the guard predicate of one operand on its own (the tests' kernel)
+LSLAM_DEV bool fit_inrange_ok(float a) { return __builtin_fabsf(a) >= FIT_LO && __builtin_fabsf(a) <= FIT_HI; }
+LSLAM_DEV bool fit_inrange_den_ok(float b) { return fit_inrange_ok(b) && (__float_as_uint(b) | 0xff800000u) != 0xffffffffu; }
+
+// b and its refined reciprocal: v_rcp_f32 and the chain's two refinement steps, shared by every division by b
+struct FitRcp { float b, r; };
+LSLAM_DEV FitRcp rcp_inrange(float b) {
+  const float r0 = __builtin_amdgcn_rcpf(b);
+  const float e = __builtin_fmaf(-b, r0, 1.0f);
+  return {b, __builtin_fmaf(e, r0, r0)};
+}
+// == a / d.b bit for bit for FIT_LO <= |a|, |d.b| <= FIT_HI, and for a = +0 (see above)
+LSLAM_DEV float div_inrange(float a, const FitRcp &d) {
+  float q = a * d.r;
+  float e = __builtin_fmaf(-d.b, q, a);
+  q = __builtin_fmaf(e, d.r, q);
+  e = __builtin_fmaf(-d.b, q, a);
+  return __builtin_fmaf(e, d.r, q);
+}
+LSLAM_DEV float div_inrange(float a, float b) { return div_inrange(a, rcp_inrange(b)); }
+// == sqrtf(x) bit for bit for 2^-96 <= x < inf, and for x = +0
+LSLAM_DEV float sqrt_inrange(float x) {
+  const float s = __builtin_amdgcn_sqrtf(x);
+  const float sd = __uint_as_float(__float_as_uint(s) - 1u), su = __uint_as_float(__float_as_uint(s) + 1u);
+  const float rd = __builtin_fmaf(-sd, s, x), ru = __builtin_fmaf(-su, s, x);
+  float r = (0.0f >= rd) ? sd : s;
+  r = (0.0f < ru) ? su : r;
+  return r;
+}
+template <bool INR> LSLAM_DEV float fit_sqrt(float x) {
+  if constexpr (INR) return sqrt_inrange(x);
+  else return sqrtf(x);
+}
+
 // ColPivHouseholderQR<Matrix<float,R,C>>::compute + solve (Eigen 3.3,
 // ColPivHouseholderQR.h computeInPlace/_solve_impl; Householder.h
 // makeHouseholder/applyHouseholderOnTheLeft).  A row-major (consumed).
-template <int R, int C>
-LSLAM_DEV void colpiv_qr_solve(float (&qr)[R * C], const float (&b)[R], float (&x)[C]) {
+// INR: the in-range fit (above) -- div_inrange / sqrt_inrange for `/` and sqrtf, their operands shown to *fr
+template <int R, int C, bool INR = false>
+LSLAM_DEV void colpiv_qr_solve(float (&qr)[R * C], const float (&b)[R], float (&x)[C], FitRange *fr = nullptr) {
   constexpr int SIZE = R < C ? R : C;
   float hC[SIZE], nU[C], nD[C], c[R];
   int trans[SIZE], perm[C];
@@ -829,8 +904,9 @@ LSLAM_DEV void colpiv_qr_solve(float (&qr)[R * C], const float (&b)[R], float (&
     float s = 0.0f;
 #pragma unroll
     for (int i = 0; i < R; ++i) s += qr[i * C + k] * qr[i * C + k];
-    nD[k] = sqrtf(s);
+    nD[k] = fit_sqrt<INR>(s);
     nU[k] = nD[k];
+    if constexpr (INR) fr->both(nD[k]);  // (in range: s >= 2^-60, and every entry of the column is within 1.001 FIT_HI)
   }
   float maxn = nU[0];
 #pragma unroll
@@ -874,12 +950,25 @@ LSLAM_DEV void colpiv_qr_solve(float (&qr)[R * C], const float (&b)[R], float (&
 #pragma unroll
         for (int i = k + 1; i < R; ++i) qr[i * C + k] = 0.0f;
       } else {
-        beta = sqrtf(c0 * c0 + tailSqNorm);
+        beta = fit_sqrt<INR>(c0 * c0 + tailSqNorm);
         if (c0 >= 0.0f) beta = -beta;
         const float denom = c0 - beta;
+        if constexpr (INR) {
+          // beta: at most 1.001 x the column's norm; in range, its square root's operand is >= 2^-60.  beta and c0 have
+          // opposite signs, so |denom| = |beta - c0| is within [|beta|, 2.001 |beta|]; the tail's entries are below 1.001 |beta|
+          fr->low(beta); fr->den(beta); fr->den(denom);
+          const FitRcp rd = rcp_inrange(denom);
+#pragma unroll
+          for (int i = k + 1; i < R; ++i) {
+            fr->low(qr[i * C + k]);
+            qr[i * C + k] = div_inrange(qr[i * C + k], rd);
+          }
+          tau = div_inrange(beta - c0, beta);
+        } else {
 #pragma unroll
         for (int i = k + 1; i < R; ++i) qr[i * C + k] = qr[i * C + k] / denom;
         tau = (beta - c0) / beta;
+        }
       }
     }
     hC[k] = tau;
@@ -904,19 +993,31 @@ LSLAM_DEV void colpiv_qr_solve(float (&qr)[R * C], const float (&b)[R], float (&
 #pragma unroll
     for (int j = k + 1; j < C; ++j) {
       if (nU[j] != 0.0f) {
-        float temp = fabsf(qr[k * C + j]) / nU[j];
+        float temp;
+        if constexpr (INR) {
+          // (the entry and both norms of column j are at most 1.001 x its first norm)
+          fr->low(qr[k * C + j]); fr->low(nU[j]); fr->low(nD[j]); fr->den(nU[j]); fr->den(nD[j]);
+          temp = div_inrange(fabsf(qr[k * C + j]), nU[j]);
+        } else {
+          temp = fabsf(qr[k * C + j]) / nU[j];
+        }
         temp = (1.0f + temp) * (1.0f - temp);
         temp = temp < 0.0f ? 0.0f : temp;
-        const float r = nU[j] / nD[j];
+        float r;
+        if constexpr (INR) r = div_inrange(nU[j], nD[j]);
+        else r = nU[j] / nD[j];
         const float temp2 = temp * (r * r);
         if (temp2 <= norm_downdate_threshold) {
           float s = 0.0f;
 #pragma unroll
           for (int i = k + 1; i < R; ++i) s += qr[i * C + j] * qr[i * C + j];
-          nD[j] = sqrtf(s);
+          nD[j] = fit_sqrt<INR>(s);
           nU[j] = nD[j];
+          if constexpr (INR) fr->low(nD[j]);  // (in range: s >= 2^-60)
         } else {
-          nU[j] *= sqrtf(temp);
+          const float st = fit_sqrt<INR>(temp);
+          if constexpr (INR) fr->low(st);  // (in range: temp >= 2^-60; temp <= 1)
+          nU[j] *= st;
         }
       }
     }
@@ -957,7 +1058,12 @@ LSLAM_DEV void colpiv_qr_solve(float (&qr)[R * C], const float (&b)[R], float (&
 #pragma unroll
   for (int i = SIZE - 1; i >= 0; --i) {
     if (i < nonzero_pivots) {
+      if constexpr (INR) {
+        fr->both(c[i]); fr->low(qr[i * C + i]); fr->den(qr[i * C + i]);  // (the diagonal: beta, or the column's own entry where the tail was nothing)
+        c[i] = div_inrange(c[i], qr[i * C + i]);
+      } else {
       c[i] /= qr[i * C + i];
+      }
 #pragma unroll
       for (int r = 0; r < i; ++r) c[r] -= c[i] * qr[r * C + i];
     }
@@ -983,11 +1089,16 @@ LSLAM_DEV void cross3(const float (&a)[3], const float (&b)[3], float (&o)[3]) {
   o[1] = a[2] * b[0] - a[0] * b[2];
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
+template <bool INR = false>
 LSLAM_DEV float norm3(const float (&a)[3]) {
-  return sqrtf((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+  return fit_sqrt<INR>((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
 }
 
 // feature_utils.h:108-154 findLine on the 5 gathered neighbours
+// INR: the in-range fit -- the nine divisions by 5 (eig_sym3 stays as it is).  The two groups guard themselves, each with
+// its own ballot and its own `/ 5.0f` for a wavefront with a numerator outside: a second findLine after the first would have
+// to keep the five neighbours, or their places, through eig_sym3.
+template <bool INR = false>
 LSLAM_DEV bool find_line(const float4 (&nb)[5], float (&A)[3], float (&B)[3]) {
   float c[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -996,7 +1107,18 @@ LSLAM_DEV bool find_line(const float4 (&nb)[5], float (&A)[3], float (&B)[3]) {
     c[1] += nb[j].y;
     c[2] += nb[j].z;
   }
+  const FitRcp five = {5.0f, FIT_RCP5};
+  if constexpr (INR) {
+    FitRange fr;
+    fr.both(c[0]); fr.both(c[1]); fr.both(c[2]);
+    if (__builtin_amdgcn_ballot_w64(fr.bad) != 0) {
+      c[0] /= 5.0f; c[1] /= 5.0f; c[2] /= 5.0f;
+    } else {
+      c[0] = div_inrange(c[0], five); c[1] = div_inrange(c[1], five); c[2] = div_inrange(c[2], five);
+    }
+  } else {
   c[0] /= 5.0f; c[1] /= 5.0f; c[2] /= 5.0f;
+  }
   float M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
@@ -1008,7 +1130,19 @@ LSLAM_DEV bool find_line(const float4 (&nb)[5], float (&A)[3], float (&B)[3]) {
     M[7] += a1 * a2;
     M[8] += a2 * a2;
   }
+  if constexpr (INR) {
+    FitRange fr;
+    fr.both(M[0]); fr.both(M[4]); fr.both(M[8]);
+    fr.low(M[3]); fr.low(M[6]); fr.low(M[7]);  // (|M[i][j]| <= 1.001 sqrt(M[i][i] M[j][j]))
+    if (__builtin_amdgcn_ballot_w64(fr.bad) != 0) {
+      M[0] /= 5.0f; M[3] /= 5.0f; M[6] /= 5.0f; M[4] /= 5.0f; M[7] /= 5.0f; M[8] /= 5.0f;
+    } else {
+      M[0] = div_inrange(M[0], five); M[3] = div_inrange(M[3], five); M[6] = div_inrange(M[6], five);
+      M[4] = div_inrange(M[4], five); M[7] = div_inrange(M[7], five); M[8] = div_inrange(M[8], five);
+    }
+  } else {
   M[0] /= 5.0f; M[3] /= 5.0f; M[6] /= 5.0f; M[4] /= 5.0f; M[7] /= 5.0f; M[8] /= 5.0f;
+  }
   float D[3], V[9];
   eig_sym3(M, D, V);
   if (D[2] > 5 * D[1]) {
@@ -1024,33 +1158,62 @@ LSLAM_DEV bool find_line(const float4 (&nb)[5], float (&A)[3], float (&B)[3]) {
 }
 
 // feature_utils.h:17-26 getLinePointDistance + :63-75 getCornerFeatureCoefficients
+// INR: the in-range fit -- the two norms, then the four divisions; each group guards itself as findLine's do.
+template <bool INR = false>
 LSLAM_DEV bool corner_coeff(const float (&A)[3], const float (&B)[3], const float (&X)[3],
                             float (&coeff)[4]) {
   const float XB[3] = {X[0] - B[0], X[1] - B[1], X[2] - B[2]};
   const float XA[3] = {X[0] - A[0], X[1] - A[1], X[2] - A[2]};
   float n[3];
   cross3(XB, XA, n);
-  const float nn = norm3(n);
+  float nn = norm3<INR>(n);
   const float AB[3] = {A[0] - B[0], A[1] - B[1], A[2] - B[2]};
-  const float lengthAB = norm3(AB);
+  float lengthAB = norm3<INR>(AB);
+  bool inr = INR;
+  if constexpr (INR) {  // (a norm in range: its square root's operand is >= 2^-60; a NaN fails the comparison)
+    FitRange fr;
+    fr.both(nn); fr.both(lengthAB); fr.den(lengthAB);
+    if (__builtin_amdgcn_ballot_w64(fr.bad) != 0) {
+      nn = norm3(n);
+      lengthAB = norm3(AB);
+      inr = false;  // (the divisions' operands are these)
+    }
+  }
   const float BA[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
   const float mn[3] = {-n[0], -n[1], -n[2]};
   float cr[3];
   cross3(mn, BA, cr);
   const float den = nn * lengthAB;
-  const float distance = nn / lengthAB;
+  if constexpr (INR) {
+    FitRange fr;
+    fr.both(den); fr.den(den); fr.den(lengthAB);
+    fr.low(cr[0]); fr.low(cr[1]); fr.low(cr[2]);  // (|cr| <= 2.001 |n| |AB| = 2.001 den)
+    inr = inr && __builtin_amdgcn_ballot_w64(fr.bad) == 0;
+  }
+  float distance, weight;
+  if (INR && inr) {
+    distance = div_inrange(nn, lengthAB);
+    weight = (float)(1.0 - (double)0.9f * fabs((double)distance));
+    const FitRcp rd = rcp_inrange(den);
+    coeff[0] = div_inrange(cr[0], rd) * weight;
+    coeff[1] = div_inrange(cr[1], rd) * weight;
+    coeff[2] = div_inrange(cr[2], rd) * weight;
+  } else {
+  distance = nn / lengthAB;
   // `1 - 0.9f * fabs(distance)` with ::fabs(double) -- the overload the reference's template binds (oracle/lslam_oracle.c,
   // corner_coefficients): evaluated in double, rounded once
-  const float weight = (float)(1.0 - (double)0.9f * fabs((double)distance));
+  weight = (float)(1.0 - (double)0.9f * fabs((double)distance));
   coeff[0] = (cr[0] / den) * weight;
   coeff[1] = (cr[1] / den) * weight;
   coeff[2] = (cr[2] / den) * weight;
+  }
   coeff[3] = distance * weight;
   return (double)weight > 0.1;  // float vs double literal, as in the reference
 }
 
 // feature_utils.h:157-204 findPlane
-LSLAM_DEV bool find_plane(const float4 (&nb)[5], float max_distance, float (&plane)[4]) {
+template <bool INR = false>
+LSLAM_DEV bool find_plane(const float4 (&nb)[5], float max_distance, float (&plane)[4], FitRange *fr = nullptr) {
   float Am[15];
   const float bm[5] = {-1.0f, -1.0f, -1.0f, -1.0f, -1.0f};
   float x[3];
@@ -1064,12 +1227,27 @@ LSLAM_DEV bool find_plane(const float4 (&nb)[5], float max_distance, float (&pla
     Am[j * 3 + 1] = nb[j].y;
     Am[j * 3 + 2] = nb[j].z;
   }
+  if constexpr (INR) {
+    const FitRcp five = {5.0f, FIT_RCP5};
+    fr->low(c[0]); fr->low(c[1]); fr->low(c[2]);  // (at most 5 x the largest coordinate, 2.3 x the column's norm, which the solve tests)
+    c[0] = div_inrange(c[0], five); c[1] = div_inrange(c[1], five); c[2] = div_inrange(c[2], five);
+  } else {
   c[0] /= 5.0f; c[1] /= 5.0f; c[2] /= 5.0f;
-  colpiv_qr_solve<5, 3>(Am, bm, x);
-  const float norm = sqrtf(((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) + 0.0f * 0.0f);
+  }
+  colpiv_qr_solve<5, 3, INR>(Am, bm, x, fr);
+  const float norm = fit_sqrt<INR>(((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]) + 0.0f * 0.0f);
+  if constexpr (INR) {
+    const FitRcp rn = rcp_inrange(norm);
+    fr->both(norm); fr->den(norm);  // (in range: its square root's operand >= 2^-60)
+    fr->low(x[0]); fr->low(x[1]); fr->low(x[2]);  // (|x[i]| <= 1.001 norm)
+    plane[0] = div_inrange(x[0], rn);
+    plane[1] = div_inrange(x[1], rn);
+    plane[2] = div_inrange(x[2], rn);
+  } else {
   plane[0] = x[0] / norm;
   plane[1] = x[1] / norm;
   plane[2] = x[2] / norm;
+  }
   plane[3] = -((plane[0] * c[0] + plane[1] * c[1]) + plane[2] * c[2]);
   bool ok = true;
 #pragma unroll
@@ -1081,9 +1259,15 @@ LSLAM_DEV bool find_plane(const float4 (&nb)[5], float max_distance, float (&pla
 }
 
 // feature_utils.h:97-106 getSurfaceFeatureCoefficients (double literal 0.9)
+// INR: the in-range fit -- |X|; the fp64 weight stays as it is (about 60 double-rate instructions: a v_rsq_f64 with its
+// refinement and a v_rcp_f64 division, rounded once)
+template <bool INR = false>
 LSLAM_DEV bool surf_coeff(const float (&plane)[4], const float (&X)[3], float (&coeff)[4]) {
   const float distance = ((plane[0] * X[0] + plane[1] * X[1]) + plane[2] * X[2]) + plane[3];
-  const float xn = norm3(X);
+  float xn = norm3<INR>(X);
+  if constexpr (INR) {  // (|X| in range: the square root's operand >= 2^-60; a NaN fails the comparison)
+    if (__builtin_amdgcn_ballot_w64(!fit_inrange_ok(xn)) != 0) xn = norm3(X);
+  }
   const float weight = (float)(1 - 0.9 * (double)fabsf(distance) / sqrt((double)xn));
   coeff[0] = plane[0] * weight;
   coeff[1] = plane[1] * weight;

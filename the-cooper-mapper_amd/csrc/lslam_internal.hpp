@@ -296,8 +296,15 @@ inline bool grid_queue_lean_ok(const SweepArgs &a, int jtj_mode) {
   return grid_sweep_lean_ok(a, jtj_mode) && a.grid == 1 && !a.dbg && !a.prev_lb && a.stack_ovf && !a.deep_tree;
 #endif
 }
+#ifndef LSLAM_FIT_INRANGE_DEFAULT
+#define LSLAM_FIT_INRANGE_DEFAULT 1  // 0: the lean kernels keep `/` and sqrtf in the fit unless LSLAM_FIT_INRANGE=1 is in the environment
+#endif
 // fine: a.kc / a.ks are x-subdivided tables (CellGrid::xsub); sweep_grid_kernel<.., FINE>, lean or general
-hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool lean = false, bool fine = false);
+// inrange (with lean): the instantiation with the in-range fit (lslam_device.hpp), here and in launch_sweep_queue
+hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool lean = false, bool fine = false,
+                             bool inrange = false);
+hipError_t launch_fit_inrange_ops(const float *a, const float *b, int n, float *out, hipStream_t s);  // (the tests': lslam_debug_fit_inrange_ops / _fits)
+hipError_t launch_fit_inrange_fits(const float4 *nbs, const float4 *X, int n, int is_surf, float *out_inr, float *out_gen, int32_t *flags, hipStream_t s);
 hipError_t launch_sweep_wide(const SweepArgs &a, hipStream_t s);  // sweep_wide_kernel (its prefix: launch_sweep_plan with_prefix)
 hipError_t launch_knn5_wide(const CellGrid &G, const float4 *q, int nq, float nf_slack, int32_t *idx, float *d2, uint8_t *undecided, hipStream_t s);
 hipError_t launch_knn5_grid(const CellGrid &G, const TreeView &T, const float4 *q, int nq, int32_t *idx, float *d2,
@@ -327,7 +334,7 @@ hipError_t launch_compact_active(const GNState *states, const ProbBlocks *probs,
 // no LiDAR workgroups at all, so count_out = 0 does not mean that the chunk's loops are over)
 hipError_t launch_sweep_plan(const SweepArgs &a, hipStream_t s, const CertPlan &plan, bool with_prefix);
 hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, bool planned = false,
-                              bool lean = false);  // lean: the grid sweep's second pass through its lean instantiation (grid_queue_lean_ok)
+                              bool lean = false, bool inrange = false);  // lean: the grid sweep's second pass through its lean instantiation (grid_queue_lean_ok)
 hipError_t launch_sweep(const SweepArgs &a, int jtj_mode, hipStream_t s,
                         hipEvent_t start = nullptr, hipEvent_t stop = nullptr, int *variant = nullptr, bool *cert_launched = nullptr);
 hipError_t launch_solve(const SolveArgs &a, hipStream_t s);

@@ -66,7 +66,8 @@ __device__ unsigned long long g_pass2_hist[8];  // listed points by the bound th
 // all three needed 96 VGPRs + 92 bytes of scratch per lane).
 // LEAN (with GRIDQ = 1): the production loop's second pass (sweep_queue_kernel<.., LEAN>) -- the caller hands over `a` and
 // jtj_mode with what such a launch never does as constants; here the search reads 12 bytes per leaf slot and nothing is clocked.
-template <int BLOCK, bool OVF, bool CUBES, int LDS_DEPTH, bool PACKET, int CERT = 0, int GRIDQ = 0, bool LEAN = false>
+// INR (with LEAN): the residual chain with the in-range fit (point_residual<.., INR>).
+template <int BLOCK, bool OVF, bool CUBES, int LDS_DEPTH, bool PACKET, int CERT = 0, int GRIDQ = 0, bool LEAN = false, bool INR = false>
 LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, const BlockDesc &bd, const GNState *st,
                           uint32_t *stack_lds, float (*red)[NCOL], float *partial_out, const int prev_valid, const int q_item = -1) {
   constexpr int NWAVE = BLOCK / 64;
@@ -406,7 +407,7 @@ LSLAM_DEV void sweep_body(const SweepArgs &a, const int jtj_mode, const int lb, 
     if (a.dbg) dbg_t1 = __builtin_readcyclecounter();
 
     // (GRIDQ == 2 is launched for a.grid == 2 only: the wide probe's neighbours are positions in the cell-sorted points)
-    point_residual(a, bd, is_surf, (GRIDQ == 2 && a.grid == 2) ? (is_surf ? a.ks.pts : a.kc.pts) : T.pts, q, sel, d, p, sc, row, rb, kept, matched, score);
+    point_residual<false, INR>(a, bd, is_surf, (GRIDQ == 2 && a.grid == 2) ? (is_surf ? a.ks.pts : a.kc.pts) : T.pts, q, sel, d, p, sc, row, rb, kept, matched, score);
   }
 
   if (a.dbg) dbg_t2 = __builtin_readcyclecounter();
@@ -572,9 +573,11 @@ __global__ __launch_bounds__(256) void cert_plan_kernel(SweepArgs a, CertPlan pl
 #ifndef LSLAM_QUEUE_LEAN_OCC
 #define LSLAM_QUEUE_LEAN_OCC 6  // wavefronts per SIMD the lean second pass is compiled for, and workgroups per CU its launch asks for: 80 VGPRs without scratch (5: 82 VGPRs, none either; six workgroups of 26 144 B fit a CU's 160 KB of LDS, seven do not).  The headline, the parent / 5 / 6 taken in turn five times: 1.525 - 1.546 / 1.549 - 1.564 / 1.569 - 1.585e10, medians +1.1 % and +2.5 % ("The lean instantiation of pass 2")
 #endif
-template <int BLOCK, bool OVF, int LDS_DEPTH, int GRIDQ = 0, bool LEAN = false>
+// INR: the lean instantiation with the in-range fit (lslam_device.hpp; LSLAM_FIT_INRANGE=0 keeps `/` and sqrtf).
+template <int BLOCK, bool OVF, int LDS_DEPTH, int GRIDQ = 0, bool LEAN = false, bool INR = false>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LEAN ? LSLAM_QUEUE_LEAN_OCC : (LDS_DEPTH <= 16 ? LSLAM_SHALLOW_OCC : 2)))) void sweep_queue_kernel(const SweepArgs a_in, const int jtj_mode_in, const CertPlan plan) {
   static_assert(!LEAN || GRIDQ == 1, "LEAN is an instantiation of the grid sweep's second pass over trees");
+  static_assert(!INR || LEAN, "the in-range fit is the lean instantiations' alone");
   __shared__ float red[BLOCK / 64][NCOL];
   __shared__ uint32_t stack_lds[2 * LDS_DEPTH * BLOCK];
   __shared__ int next_w;
@@ -657,7 +660,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LEAN ? LS
       const int p0 = pre_lds[k];
       item = a.blocks[fb + k].first + (int)a.need_list[(size_t)(fb + k) * BLOCK + (i - p0)];
     }
-    sweep_body<BLOCK, OVF, false, LDS_DEPTH, false, 2, GRIDQ, LEAN>(a, jtj_mode, fb + c, bd, st, stack_lds, red, a.partials + (size_t)(fb + c) * NCOL, a.prev_valid, item);  // (the certificate sweep's second pass only runs with prev_valid set; the grid sweep's runs in a loop's first sweep too)
+    sweep_body<BLOCK, OVF, false, LDS_DEPTH, false, 2, GRIDQ, LEAN, INR>(a, jtj_mode, fb + c, bd, st, stack_lds, red, a.partials + (size_t)(fb + c) * NCOL, a.prev_valid, item);  // (the certificate sweep's second pass only runs with prev_valid set; the grid sweep's runs in a loop's first sweep too)
     __syncthreads();  // red and the stack columns are free again
   }
 }
@@ -722,6 +725,71 @@ hipError_t launch_sweep(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEven
   return hipGetLastError();
 }
 
+// The in-range fit's parts on their own, for the tests (lslam_debug_fit_inrange_ops / _fits).
+// out[8 i ..]: div_inrange(a, b), a / b, sqrt_inrange(a), sqrtf(a), the guard's verdict on a and b (bits 0, 1), the refined
+// reciprocal of b, FIT_RCP5, div_inrange(a, {5, FIT_RCP5})
+__global__ void fit_inrange_ops_kernel(const float *a, const float *b, int n, float *out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float x = a[i], y = b[i];
+  float *o = out + (size_t)i * 8;
+  o[0] = div_inrange(x, y);
+  o[1] = x / y;
+  o[2] = sqrt_inrange(x);
+  o[3] = sqrtf(x);
+  o[4] = __int_as_float((fit_inrange_ok(x) ? 1 : 0) | (fit_inrange_den_ok(y) ? 2 : 0));
+  o[5] = rcp_inrange(y).r;
+  o[6] = FIT_RCP5;
+  o[7] = div_inrange(x, FitRcp{5.0f, FIT_RCP5});
+}
+// One fit per lane on given neighbours nb[5 i ..] and point X[i], in range and as everybody has it: out_inr / out_gen[8 i ..] =
+// the plane (or A, B's coefficient) and the coefficient; flags[i]: bit 0 / 1 kept by the in-range / the general fit, bit 2 /
+// 3 matched, bit 4 the plane fit's guard refused an operand (the sweep kernels then take the general fit's result)
+__global__ void fit_inrange_fits_kernel(const float4 *nbs, const float4 *X, int n, int is_surf, float *out_inr, float *out_gen, int32_t *flags) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float4 nb[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) nb[j] = nbs[(size_t)i * 5 + j];
+  const float sel[3] = {X[i].x, X[i].y, X[i].z};
+  int f = 0;
+  for (int inr = 0; inr < 2; ++inr) {
+    float r[8] = {0, 0, 0, 0, 0, 0, 0, 0}, coeff[4] = {0, 0, 0, 0};
+    bool matched = false, kept = false;
+    if (is_surf) {
+      float plane[4] = {0, 0, 0, 0};
+      FitRange fr;
+      matched = inr ? find_plane<true>(nb, 0.2f, plane, &fr) : find_plane(nb, 0.2f, plane);
+      if (inr && fr.bad) f |= 16;
+      if (matched) kept = inr ? surf_coeff<true>(plane, sel, coeff) : surf_coeff(plane, sel, coeff);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r[k] = plane[k];
+    } else {
+      float A[3] = {0, 0, 0}, B[3] = {0, 0, 0};
+      matched = inr ? find_line<true>(nb, A, B) : find_line(nb, A, B);
+      if (matched) kept = inr ? corner_coeff<true>(A, B, sel, coeff) : corner_coeff(A, B, sel, coeff);
+      r[0] = A[0]; r[1] = A[1]; r[2] = A[2]; r[3] = B[0];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[4 + k] = coeff[k];
+    float *o = (inr ? out_inr : out_gen) + (size_t)i * 8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = r[k];
+    f |= (kept ? 1 : 0) << (inr ? 0 : 1) | (matched ? 1 : 0) << (inr ? 2 : 3);
+  }
+  flags[i] = f;
+}
+hipError_t launch_fit_inrange_ops(const float *a, const float *b, int n, float *out, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(fit_inrange_ops_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, b, n, out);
+  return hipGetLastError();
+}
+hipError_t launch_fit_inrange_fits(const float4 *nbs, const float4 *X, int n, int is_surf, float *out_inr, float *out_gen, int32_t *flags, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(fit_inrange_fits_kernel, dim3((n + 255) / 256), dim3(256), 0, s, nbs, X, n, is_surf, out_inr, out_gen, flags);
+  return hipGetLastError();
+}
+
 // the planner of a second pass on its own (a map without trees plans BEFORE the wide probe, whose prefix rides in the same launch)
 hipError_t launch_sweep_plan(const SweepArgs &a, hipStream_t s, const CertPlan &plan, bool with_prefix) {
   if (a.n_groups <= 0) return hipSuccess;
@@ -729,7 +797,8 @@ hipError_t launch_sweep_plan(const SweepArgs &a, hipStream_t s, const CertPlan &
   return hipGetLastError();
 }
 
-hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, bool planned, bool lean) {
+hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t stop, int variant, const CertPlan &plan, bool planned, bool lean,
+                              bool inrange) {
   if (a.n_groups <= 0) return hipSuccess;
   // (the lean kernel would compute something else; it exists for the shallow stack, the production loop's, only)
   if (lean && !(grid_queue_lean_ok(a, jtj_mode) && variant == SWEEP_VARIANT_SHALLOW)) return hipErrorInvalidValue;
@@ -743,7 +812,8 @@ hipError_t launch_sweep_queue(const SweepArgs &a, int jtj_mode, hipStream_t s, h
     hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 2>), g, b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
   } else if (lean) {
     const dim3 g((unsigned)std::min<long>(possible, 256 * LSLAM_QUEUE_LEAN_OCC));
-    hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 1, true>), g, b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
+    if (!inrange) hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 1, true>), g, b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
+    else hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 1, true, true>), g, b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
   } else if (variant == SWEEP_VARIANT_SHALLOW) {
     const dim3 g((unsigned)std::min<long>(possible, 256 * 5));
     if (a.grid) hipExtLaunchKernelGGL((sweep_queue_kernel<SWEEP_BLOCK, true, SHALLOW, 1>), g, b, 0, s, nullptr, stop, 0, a, jtj_mode, plan);
@@ -791,8 +861,10 @@ __device__ unsigned long long g_section_clock[12 * 64];  // [section][place]: s_
 // headline (LSLAM_AB_GRID_GENERAL brings the general kernel back; DESIGN 4 has the numbers).
 // FINE: a.kc / a.ks are the x-subdivided tables (CellGrid::xsub > 1, their own cell-sorted points): knn5_grid<.., FINE> clips the
 // bounded probe's rows to sub-cells.  The plain first pass only -- positions in these tables never leave the launch.
-template <int BLOCK, bool LEAN = false, bool FINE = false>
+// INR: the lean instantiation with the in-range fit (lslam_device.hpp; LSLAM_FIT_INRANGE=0 keeps `/` and sqrtf).
+template <int BLOCK, bool LEAN = false, bool FINE = false, bool INR = false>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LEAN ? LSLAM_GRID_LEAN_OCC : LSLAM_GRID_OCC))) void sweep_grid_kernel(SweepArgs a, int jtj_mode) {
+  static_assert(!INR || LEAN, "the in-range fit is the lean instantiations' alone");
   if constexpr (LEAN) {  // what launch_sweep_grid has checked, as constants
     jtj_mode = 1;
     a.flags_out = nullptr;
@@ -940,7 +1012,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LEAN ? LS
   }
   LSLAM_TICK_P(scp, 4);  // the list of pass 2 (one workgroup barrier), the carried state written
   if (has) {
-    if constexpr (LEAN) point_residual<true>(a, bd, is_surf, G.pts, q, sel, d, p, sc, row, rb, kept, matched, score, &five, five_valid);
+    if constexpr (LEAN) point_residual<true, INR>(a, bd, is_surf, G.pts, q, sel, d, p, sc, row, rb, kept, matched, score, &five, five_valid);
     else point_residual(a, bd, is_surf, G.pts, q, sel, d, p, sc, row, rb, kept, matched, score);
   }
   LSLAM_TICK_P(scp, 5);  // the residual chain: five neighbours fetched, findLine / findPlane, coefficient, Jacobian row, score
@@ -1027,7 +1099,7 @@ hipError_t launch_compact_active(const GNState *states, const ProbBlocks *probs,
   return hipGetLastError();
 }
 
-hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool lean, bool fine) {
+hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hipEvent_t start, hipEvent_t stop, bool lean, bool fine, bool inrange) {
   if (a.nb_total <= 0) return hipSuccess;
   if (lean && !grid_sweep_lean_ok(a, jtj_mode)) return hipErrorInvalidValue;  // (the lean kernel would compute something else)
   // fine: a.kc / a.ks are x-subdivided tables, the same table for the lean and the general kernel; otherwise x is read in whole cells
@@ -1035,7 +1107,10 @@ hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hi
   if (a.active_blocks && a.n_active <= 0) return hipSuccess;
   // (active_blocks: the batch's grid sweep over the running scans' workgroups only)
   const dim3 grd(a.active_blocks ? a.n_active : a.nb_total), blk(SWEEP_BLOCK);
-  if (fine && lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, true, true>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);
+  if (inrange && !lean) return hipErrorInvalidValue;
+  if (fine && inrange) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, true, true, true>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);
+  else if (inrange) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, true, false, true>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);
+  else if (fine && lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, true, true>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);
   else if (fine) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, false, true>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);
   else if (lean) hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK, true>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);
   else hipExtLaunchKernelGGL((sweep_grid_kernel<SWEEP_BLOCK>), grd, blk, 0, s, start, stop, 0, a, jtj_mode);

@@ -33,7 +33,8 @@ LSLAM_DEV int cube_tree_of(const CubeGridDev &g, float x, float y, float z) {
 // Shared by the tree sweep (P = the tree's permuted points) and the grid sweep (P = the cell-sorted points).
 // GIVEN (the lean grid sweep): the search has the five points in registers already -- (*given)[3 j ..] = x, y, z of P[p[j]]
 // when `use_given` (wave-uniform; knn5_grid<.., true>) -- and they are not gathered again (findLine / findPlane read x, y, z only).
-template <bool GIVEN = false>
+// INR (the lean kernels): the in-range fit first, the fit as everybody has it only for a wavefront with an operand outside the range.
+template <bool GIVEN = false, bool INR = false>
 LSLAM_DEV void point_residual(const SweepArgs &a, const BlockDesc &bd, const bool is_surf, const float4 *P, const float4 &q,
                               const float (&sel)[3], const float (&d)[5], const int (&p)[5], const float (&sc)[6],
                               float (&row)[6], float &rb, float &kept, float &matched, float &score,
@@ -63,7 +64,28 @@ LSLAM_DEV void point_residual(const SweepArgs &a, const BlockDesc &bd, const boo
 #pragma unroll
       for (int j = 0; j < 5; ++j) nb[j] = P[p[j]];
     }
-    if (!is_surf) {
+    if constexpr (INR) {
+      // the in-range fit (lslam_device.hpp): division and square root without their range steps, the operands tested; one
+      // lane with an operand outside the range and the whole wavefront divides, or fits, again as everybody does (rare; a
+      // ballot is over the lanes that are there, so the branches are uniform)
+      if (!is_surf) {
+        float A[3], B[3];
+        if (find_line<true>(nb, A, B)) {  // (findLine's and the coefficient's divisions guard themselves)
+          flag |= 2u;
+          if (corner_coeff<true>(A, B, sel, coeff)) flag |= 4u;
+        }
+      } else {
+        float plane[4];
+        FitRange fr;
+        bool ok = find_plane<true>(nb, 0.2f, plane, &fr);
+        // (findPlane reads the five to its last statement: they are still here)
+        if (__builtin_amdgcn_ballot_w64(fr.bad) != 0) ok = find_plane(nb, 0.2f, plane);
+        if (ok) {
+          flag |= 2u;
+          if (surf_coeff<true>(plane, sel, coeff)) flag |= 4u;  // (|X| guards itself)
+        }
+      }
+    } else if (!is_surf) {
       float A[3], B[3];
       if (find_line(nb, A, B)) {  // ScanMatch.cpp:105-112
         flag |= 2u;

@@ -152,6 +152,10 @@ class Context:
         """lslam_debug_queue_lean_launches: ... of which with the lean instantiation of the second pass as well."""
         return int(self.lib.lslam_debug_queue_lean_launches(self.h))
 
+    def fit_inrange_launches(self):
+        """lslam_debug_fit_inrange_launches: ... of the lean ones, those with the in-range fit (LSLAM_FIT_INRANGE=0: none)."""
+        return int(self.lib.lslam_debug_fit_inrange_launches(self.h))
+
     def grid_fine_launches(self):
         """lslam_debug_grid_fine_launches: ... of which with the first pass over the x-subdivided cell tables."""
         return int(self.lib.lslam_debug_grid_fine_launches(self.h))
