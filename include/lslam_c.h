@@ -219,6 +219,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed, no entry point gone; six LSLAM_AB_* names retired (bits 1, 2, 4, 8, 32, 128: refused from here on, see lslam_opts.ab_switches). */
 /* still 7: no struct changed; new entry points and an enum (lslam_pg_set_priors, _num_priors, _prior_robust, lslam_g2o_read_priors: unary constraints on pose-graph vertices). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_floor_*, lslam_debug_floor_hypotheses: floor detection; lslam_pg_set_plane_priors, _num_plane_priors, _plane_prior_robust, lslam_g2o_read_plane_priors: plane priors). */
+/* still 7: no struct changed; new entry points and structs of their own (lslam_vis_*, lslam_debug_vis_votes: visibility votes over the keyframe store). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -837,6 +838,103 @@ int lslam_sc_query(lslam_kfs *kfs, int32_t n_query, const int32_t *query_ids, co
  * selection; dist_out / shift_out [n_keyframes]. */
 int lslam_sc_distances(lslam_kfs *kfs, int32_t query_id, float *dist_out, int32_t *shift_out);
 int lslam_sc_info(lslam_kfs *kfs, lslam_sc_stats *out);
+
+/* ---- visibility votes: the final map without moving objects ---------------------------------------------------------------
+ * Not in the reference: its addFeatureCloud only voxel-filters, so a car that stood at a junction for two keyframes stays in the
+ * saved map as a solid block.  The method is the usual one (Removert, ERASOR, OctoMap free space): a point is dynamic when other
+ * keyframes looked through the place where it is.  Each keyframe gets a coarse range image, built from its clouds where they lie
+ * in the store; a query point is projected into each voting keyframe's image and that keyframe votes "free" or "hit"; integer
+ * votes decide, so the result does not depend on any order of summation.  This comment is the specification (restated in numpy
+ * by tests/visibility_ref.py).
+ *
+ * PIXEL of a point p in a keyframe's sensor frame.  up_axis 1 (y up): (a, b, h) = (z, x, y); up_axis 2 (z up): (a, b, h) =
+ * (x, y, z), as lslam_sc_params.  In fp32, every operation rounded on its own (no FMA):
+ *   rho = sqrtf(a*a + b*b);  r = sqrtf((a*a + b*b) + h*h)
+ * The point is OBSERVABLE iff its coordinates are finite, min_range <= r <= max_range (fp32) and, in fp64,
+ *   rowd = (atan2((double)h, (double)rho) - el0) * row_scale   satisfies 0 <= rowd < n_row,
+ * el0 = fov_down_deg * pi / 180 and row_scale = n_row / ((fov_up_deg - fov_down_deg) * pi / 180), both in fp64 from the fp32
+ * parameters, on the host.  Then row = (int)rowd; ang = atan2((double)b, (double)a), plus 2 pi if negative;
+ * col = min((int)(ang * col_scale), n_col - 1), col_scale = n_col / (2 pi) (fp64, on the host).
+ *
+ * RANGE IMAGE of a keyframe: n_row x n_col fp32, row-major, over the corner cloud followed by the surf cloud.  A pixel holds the
+ * minimum r of its observable points, +inf without one (an integer atomic minimum on the bit patterns: positive floats order as
+ * their bits, and a minimum does not depend on arrival order, so images are bit-reproducible).  Images are built lazily -- a call
+ * that needs them first builds every keyframe's that has none, in one launch (behind one that fills them with +inf) -- live in
+ * device slabs that never move and are freed by lslam_kfs_clear / lslam_kfs_destroy.  A store on which lslam_vis_setup was never
+ * called allocates nothing for them.  Parameters that differ from those in force drop the images held.
+ *
+ * VOTE of voter k (keyframe ids[k] at poses[k]: row-major 4x4 fp32, graph <- sensor k) on query point q (graph frame).  The
+ * inverse is formed on the host in fp64 as (R^T, -R^T t), row j of it (R0j, R1j, R2j | -((R0j t0 + R1j t1) + R2j t2)), rounded to
+ * fp32; p = T^-1 q in fp32 as lslam_kfs_debug_local_clouds transforms: ((T0 x + T1 y) + T2 z) + T3.  p not observable: no vote.
+ * Otherwise m = fmaxf(abs_margin, rel_margin * r); the window is the rows row - window .. row + window that lie in [0, n_row) and
+ * the columns (col - window .. col + window) mod n_col.  FREE iff the centre pixel is finite and every finite window pixel v has
+ * v > r + m (one fp32 add); HIT iff some finite window pixel has fabsf(v - r) <= m (one fp32 subtraction).  The two are counted
+ * independently and exclude each other but for a difference v - r above m that rounds onto m.
+ * Per point the calls return n_free | n_hit << 16 (uint32); the point is DYNAMIC iff n_free >= min_free_votes && n_free > n_hit.
+ * The same id may be named more than once (it then votes more than once); n_ids is 0 .. 65535, so neither half can overflow.
+ *
+ * Everything is checked before anything runs -- LSLAM_ERR_INVALID, lslam_last_error names the cause, nothing has changed (the
+ * caller's outputs included) -- for: a null or destroyed store, votes before lslam_vis_setup, a keyframe id out of range, a pose
+ * that is not finite, null arrays with something to read or write, n above 2^31 - 1, n_ids outside 0 .. 65535, a stride under
+ * 16 bytes, and in lslam_vis_setup: n_row outside 1 .. 128, n_col outside 4 .. 4096, fov angles that are not finite, outside
+ * [-90, 90] or not fov_down_deg < fov_up_deg, min_range not positive and finite, max_range not finite or not above min_range,
+ * window outside 0 .. 3, abs_margin / rel_margin negative or not finite, min_free_votes below 1, up_axis neither 1 nor 2. */
+typedef struct lslam_vis_params {
+  int32_t n_row;           /* 16     1 .. 128 */
+  int32_t n_col;           /* 360    4 .. 4096 */
+  float fov_down_deg;      /* -16    the lower ... */
+  float fov_up_deg;        /* 16     ... and upper edge of the image's elevation range, within [-90, 90] */
+  float min_range;         /* 1.0    > 0 [m] */
+  float max_range;         /* 80.0   > min_range [m] */
+  int32_t window;          /* 1      0 .. 3 pixels to every side */
+  float abs_margin;        /* 0.5    >= 0 [m] */
+  float rel_margin;        /* 0.02   >= 0, of the range */
+  int32_t min_free_votes;  /* 2      >= 1 */
+  int32_t up_axis;         /* 1      1: y up, 2: z up */
+} lslam_vis_params;
+typedef struct lslam_vis_stats {
+  lslam_vis_params params;  /* in force (zero before lslam_vis_setup) */
+  int32_t is_set;           /* 1 once lslam_vis_setup succeeded */
+  int64_t n_images;         /* keyframes that have their range image */
+  uint64_t image_bytes;     /* device memory of the image slabs */
+  int64_t image_launches;   /* launches of the image kernel ... */
+  int64_t vote_launches;    /* ... and of the vote kernel (the measurement tap's not counted), since creation */
+} lslam_vis_stats;
+/* Kernel shape, for tests that have to straddle it: query points per workgroup of the vote kernel (one per lane) and voters per
+ * workgroup (grid: point tiles x keyframe chunks). */
+#define LSLAM_VIS_POINT_TILE 256
+#define LSLAM_VIS_KF_CHUNK 16
+/* Writes every byte of *p (the defaults above). */
+void lslam_vis_default_params(lslam_vis_params *p);
+size_t lslam_sizeof_vis_params(void);
+size_t lslam_sizeof_vis_stats(void);
+/* Validates and installs the parameters; NULL: the defaults. */
+int lslam_vis_setup(lslam_kfs *kfs, const lslam_vis_params *params);
+int lslam_vis_info(lslam_kfs *kfs, lslam_vis_stats *out);
+/* Parity tap: keyframe id's range image, downloaded; out[n_row * n_col]. */
+int lslam_vis_range_image(lslam_kfs *kfs, int32_t id, float *out);
+/* The votes of voters ids[n_ids] at poses[n_ids * 16] on n host points (stride_bytes >= 16, {x, y, z} at 0 as elsewhere):
+ * uploaded, voted on, votes_out[n] downloaded.  These are query points of the caller's, not the store's clouds: the store's byte
+ * counters stay. */
+int lslam_vis_votes(lslam_kfs *kfs, int32_t n_ids, const int32_t *ids, const float *poses, const void *points, size_t n,
+                    size_t stride_bytes, uint32_t *votes_out);
+/* The same on points that are in the ctx's device memory, packed {x, y, z, -}; d_votes[n] in device memory.  Waited for. */
+int lslam_vis_votes_device(lslam_kfs *kfs, int32_t n_ids, const int32_t *ids, const float *poses, const float *d_xyzi, size_t n,
+                           uint32_t *d_votes);
+/* The points that are not dynamic, in input order (a stable compaction on the device), into d_out (room for n points, must not
+ * overlap d_xyzi); *n_kept of them. */
+int lslam_vis_filter_device(lslam_kfs *kfs, int32_t n_ids, const int32_t *ids, const float *poses, const float *d_xyzi, size_t n,
+                            float *d_out, size_t *n_kept);
+/* lslam_kfs_add_to_fmap with the filter in front: keyframe id's corner and surf points are moved by T (the fp32 formula above),
+ * voted on by the named voters; the survivors -- still in the sensor frame, in their order -- are compacted on the device and
+ * handed to lslam_fmap_add_feature_cloud's device form with T.  n_removed[0 / 1]: corner / surf points left out.  No cloud
+ * crosses PCIe: the store's byte counters stay. */
+int lslam_vis_add_to_fmap(lslam_kfs *kfs, int32_t id, lslam_fmap *fm, const float T[16], int32_t n_ids, const int32_t *ids,
+                          const float *poses, size_t n_removed[2]);
+/* Measurement tap (tools/bench_visibility.py): enqueues `launches` launches of the vote kernel alone, in the shape of the store's
+ * last lslam_vis_votes call and on its points, voters and poses, voting into a buffer of its own; not waited for (time it with
+ * events on lslam_stream).  LSLAM_ERR_INVALID before such a call has run (or after lslam_kfs_clear / new parameters). */
+int lslam_debug_vis_votes(lslam_kfs *kfs, int32_t launches);
 
 /* pcl::VoxelGrid<PointXYZI>::filter with a cubic leaf on one cloud (LaserMatcher.cpp:289-301,
  * ScanMatch.cpp:362-398 scanMatchLocal): one centroid {x,y,z,intensity} per occupied voxel, in

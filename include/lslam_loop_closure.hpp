@@ -195,6 +195,55 @@ public:
     _err = lslam_last_error();
     return false;
   }
+  // ---- visibility votes: the final map without moving objects (lslam_vis_*) ----
+  // params == nullptr: the defaults.  Other parameters than those in force drop the range images held.
+  bool vis_setup(const lslam_vis_params *params = nullptr) {
+    if (lslam_vis_setup(_h, params) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  bool vis_info(lslam_vis_stats &st) {
+    if (lslam_vis_info(_h, &st) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // keyframe id's range image, n_row x n_col row-major, +inf where nothing was seen (parity tap)
+  bool vis_range_image(int id, std::vector<float> &out) {
+    lslam_vis_stats st;
+    if (!vis_info(st)) return false;
+    out.assign((size_t)std::max(st.params.n_row, 1) * (size_t)std::max(st.params.n_col, 1), 0.0f);
+    if (lslam_vis_range_image(_h, id, out.data()) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // The votes of keyframes ids[k] at poses[16 k ..] (row-major 4x4 float, graph <- sensor) on host points {x, y, z, -}:
+  // votes[i] = n_free | n_hit << 16.
+  bool vis_votes(const std::vector<int32_t> &ids, const std::vector<float> &poses, const std::vector<float> &points,
+                 std::vector<uint32_t> &votes) {
+    votes.assign(points.size() / 4, 0u);
+    if (poses.size() != 16 * ids.size()) { _err = "vis_votes: one 4x4 pose per id"; return false; }
+    if (lslam_vis_votes(_h, (int32_t)ids.size(), ids.data(), poses.data(), points.data(), points.size() / 4, 16, votes.data()) == LSLAM_OK)
+      return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // n points in the ctx's device memory, packed {x, y, z, -}: the ones that are not dynamic, in input order, into d_out (room
+  // for n points); -> how many, -1 when refused.
+  long vis_filter(const std::vector<int32_t> &ids, const std::vector<float> &poses, const float *d_xyzi, size_t n, float *d_out) {
+    size_t kept = 0;
+    if (poses.size() != 16 * ids.size()) { _err = "vis_filter: one 4x4 pose per id"; return -1; }
+    if (lslam_vis_filter_device(_h, (int32_t)ids.size(), ids.data(), poses.data(), d_xyzi, n, d_out, &kept) == LSLAM_OK) return (long)kept;
+    _err = lslam_last_error();
+    return -1;
+  }
+  // lslam_kfs_add_to_fmap with the filter in front; removed[0 / 1]: the corner / surf points left out
+  bool vis_add_to_fmap(int id, lslam_fmap *fm, const float T[16], const std::vector<int32_t> &ids, const std::vector<float> &poses,
+                       size_t removed[2]) {
+    if (poses.size() != 16 * ids.size()) { _err = "vis_add_to_fmap: one 4x4 pose per id"; return false; }
+    if (lslam_vis_add_to_fmap(_h, id, fm, T, (int32_t)ids.size(), ids.data(), poses.data(), removed) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
   const std::string &lastError() const { return _err; }
 
 private:
@@ -537,6 +586,7 @@ public:
       : loop_detector(ctx), _ctx(ctx), _device(device), _max_per_update(max_keyframes_per_update), _keep_host(keep_host_clouds),
         _appearance(appearance_loops) {
     lslam_floor_default_params(&floor_params);
+    lslam_vis_default_params(&dynamic_params);
     if (resident || appearance_loops) {
       store.reset(new KeyframeStore(ctx));
       if (!store->ok()) _err = store->lastError();
@@ -689,6 +739,11 @@ public:
                          int cubeDepth = 121) {
     matched.clear();
     poses.clear();
+    removedPoints.clear();
+    if (remove_dynamic && (!store || ctx != _ctx)) {
+      _err = "Graph: remove_dynamic needs a resident graph and the map on its context";
+      return -1;
+    }
     lslam_fmap *fm = nullptr;
     if (lslam_fmap_create(ctx, cubeWidth, cubeHeight, cubeDepth, &fm) != LSLAM_OK) return fail_final(nullptr);
     lslam_fmap_setup_filter_size(fm, 0.2f, 0.2f, 0.4f);
@@ -727,7 +782,7 @@ public:
         ok = rc == LSLAM_OK;
       }
       if (ok || (bootstrap && !enough)) {
-        if ((stored ? lslam_kfs_add_to_fmap(kf->store, kf->store_id, fm, T)
+        if ((stored ? add_stored(kf, fm, T, true)
                     : lslam_fmap_add_feature_cloud(fm, kf->cornerCloud.data(), kc, kf->surfCloud.data(), ks, 16, T)) < 0)
           return fail_final(fm);
         ++added;
@@ -749,6 +804,7 @@ public:
   // translation, quaternion w, quaternion x y z of the float-cast rotation, index), then getFinalFeatureMap into directory/graph2.
   bool save(const std::string &directory, bool bootstrap = false, int max_iterations = 1000) {
     if (keyframes.empty()) { _err = "Graph::save: no keyframes"; return false; }
+    if (remove_dynamic && !store) { _err = "Graph: remove_dynamic needs a resident graph"; return false; }
     // (the .g2o files carry no kernel: the text format has no place for one)
     const std::string before = directory + "/graph_before.g2o", end = directory + "/graph_end.g2o";
     if (!solve_graph(max_iterations, before.c_str(), end.c_str())) return false;
@@ -760,7 +816,7 @@ public:
       to_float16(kf->estimate, T);
       const float pos[3] = {T[3], T[7], T[11]};
       if (lslam_fmap_update(fm, pos) < 0) return fail_final(fm) >= 0;
-      if ((kf->store ? lslam_kfs_add_to_fmap(kf->store, kf->store_id, fm, T)
+      if ((kf->store ? add_stored(kf, fm, T, false)
                      : lslam_fmap_add_feature_cloud(fm, kf->cornerCloud.data(), kf->cornerCloud.size() / 4, kf->surfCloud.data(),
                                                     kf->surfCloud.size() / 4, 16, T)) < 0)
         return fail_final(fm) >= 0;
@@ -833,6 +889,15 @@ public:
   //   LIMIT: with the reference's constant odometry information (sigma about 1 m / 0.7 rad) bending the trajectory onto an
   //     outlying floor costs less than any kernel charges for rejecting it: a kernel rejects only when the edges are worth
   //     something -- odometry_information below, or edge_information = "hessian".
+  // The final map without moving objects (not in the reference, whose addFeatureCloud only voxel-filters; lslam_vis_*, semantics in
+  // lslam_c.h).  Off by default.  With remove_dynamic on a resident graph, getFinalFeatureMap and the unmatched map of save add a
+  // keyframe through lslam_vis_add_to_fmap: its points, at the pose they are added with, are voted on by every keyframe, itself
+  // included, whose optimised translation lies within 2 * max_range of its own, at its optimised estimate; what the votes call
+  // dynamic -- a car that stood at a junction for two keyframes and drove off -- is left out.  dynamic_params: lslam_vis_setup's
+  // (the defaults unless changed).  removedPoints: (corner, surf) points left out per keyframe getFinalFeatureMap added.
+  bool remove_dynamic = false;
+  lslam_vis_params dynamic_params;
+  std::vector<std::pair<size_t, size_t>> removedPoints;
   double floor_sigma_normal = 0.0, floor_sigma_distance = 0.0;
   lslam_floor_params floor_params;
   std::string floor_robust_kernel = "NONE";
@@ -906,6 +971,30 @@ private:
     _err = lslam_last_error();
     if (fm) lslam_fmap_destroy(fm);
     return -1;
+  }
+  // A stored keyframe's clouds into fm at T; with remove_dynamic through the visibility filter (voters: see remove_dynamic), the
+  // points it left out appended to removedPoints when `record`.  -> the ABI's status.
+  int add_stored(const KeyFrame::Ptr &kf, lslam_fmap *fm, const float T[16], bool record) {
+    if (!remove_dynamic) return lslam_kfs_add_to_fmap(kf->store, kf->store_id, fm, T);
+    int rc = lslam_vis_setup(kf->store, &dynamic_params);
+    if (rc < 0) return rc;
+    const double reach = 2.0 * (double)dynamic_params.max_range;
+    std::vector<int32_t> ids;
+    std::vector<float> poses;
+    for (const auto &o : keyframes) {
+      if (o->store != kf->store) continue;
+      const double dx = o->estimate(0, 3) - kf->estimate(0, 3), dy = o->estimate(1, 3) - kf->estimate(1, 3),
+                   dz = o->estimate(2, 3) - kf->estimate(2, 3);
+      if (std::sqrt(dx * dx + dy * dy + dz * dz) > reach) continue;
+      float P[16];
+      to_float16(o->estimate, P);
+      ids.push_back(o->store_id);
+      poses.insert(poses.end(), P, P + 16);
+    }
+    size_t removed[2] = {0, 0};
+    rc = lslam_vis_add_to_fmap(kf->store, kf->store_id, fm, T, (int32_t)ids.size(), ids.data(), poses.data(), removed);
+    if (rc >= 0 && record) removedPoints.push_back(std::make_pair(removed[0], removed[1]));
+    return rc;
   }
   static void accumulate_pair(double S[18], const double s[3], const double t[3]) {  // lslam_debug_icp_fit's sums
     S[0] += 1.0;

@@ -28,6 +28,7 @@ from .dynamic_feature_map import DynamicFeatureMap
 from . import survey_map
 from .survey_map import SurveyMap
 from . import floor
+from . import visibility
 
-__all__ = ["Comm", "Context", "ScanMatch", "PoseGraph", "FeatureMap", "voxel_grid", "voxel_grid2", "scan_registration", "MultiScanRegistration", "OrganisedScanRegistration", "KeyFrame", "Loop", "LoopDetector", "Graph", "KeyframeUpdater", "LaserOdometry", "DeviceLaserOdometry", "LaserMapping", "LaserMappingLocal", "LaserLocalization", "RelocResult", "yaw_sweep", "grid_positions", "DynamicFeatureMap", "LocalFeatureMap", "KeyframeStore", "survey_map", "SurveyMap", "floor", "LslamError", "LslamOpts", "LslamStats", "LslamMapInfo", "LslamStereoCam",
+__all__ = ["visibility","Comm", "Context", "ScanMatch", "PoseGraph", "FeatureMap", "voxel_grid", "voxel_grid2", "scan_registration", "MultiScanRegistration", "OrganisedScanRegistration", "KeyFrame", "Loop", "LoopDetector", "Graph", "KeyframeUpdater", "LaserOdometry", "DeviceLaserOdometry", "LaserMapping", "LaserMappingLocal", "LaserLocalization", "RelocResult", "yaw_sweep", "grid_positions", "DynamicFeatureMap", "LocalFeatureMap", "KeyframeStore", "survey_map", "SurveyMap", "floor", "LslamError", "LslamOpts", "LslamStats", "LslamMapInfo", "LslamStereoCam",
            "Status", "lib_path", "load_library", "build_library"]

@@ -258,6 +258,19 @@ class LslamScStats(C.Structure):
                 ("describe_launches", C.c_int64), ("query_launches", C.c_int64)]
 
 
+class LslamVisParams(C.Structure):
+    """lslam_vis_params (include/lslam_c.h)."""
+    _fields_ = [("n_row", C.c_int32), ("n_col", C.c_int32), ("fov_down_deg", C.c_float), ("fov_up_deg", C.c_float),
+                ("min_range", C.c_float), ("max_range", C.c_float), ("window", C.c_int32), ("abs_margin", C.c_float),
+                ("rel_margin", C.c_float), ("min_free_votes", C.c_int32), ("up_axis", C.c_int32)]
+
+
+class LslamVisStats(C.Structure):
+    """lslam_vis_stats (include/lslam_c.h)."""
+    _fields_ = [("params", LslamVisParams), ("is_set", C.c_int32), ("n_images", C.c_int64), ("image_bytes", C.c_uint64),
+                ("image_launches", C.c_int64), ("vote_launches", C.c_int64)]
+
+
 class LslamFloorParams(C.Structure):
     """lslam_floor_params (include/lslam_c.h)."""
     _fields_ = [("up", C.c_float * 3), ("sensor_height", C.c_float), ("height_clip_range", C.c_float), ("max_range", C.c_float),
@@ -431,6 +444,20 @@ SYMBOLS = {
                                      c_int32_p]),
     "lslam_sc_distances": (C.c_int, [C.c_void_p, C.c_int32, c_float_p, c_int32_p]),
     "lslam_sc_info": (C.c_int, [C.c_void_p, C.POINTER(LslamScStats)]),
+    "lslam_vis_default_params": (None, [C.POINTER(LslamVisParams)]),
+    "lslam_sizeof_vis_params": (C.c_size_t, []),
+    "lslam_sizeof_vis_stats": (C.c_size_t, []),
+    "lslam_vis_setup": (C.c_int, [C.c_void_p, C.POINTER(LslamVisParams)]),
+    "lslam_vis_info": (C.c_int, [C.c_void_p, C.POINTER(LslamVisStats)]),
+    "lslam_vis_range_image": (C.c_int, [C.c_void_p, C.c_int32, c_float_p]),
+    "lslam_vis_votes": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                  C.POINTER(C.c_uint32)]),
+    "lslam_vis_votes_device": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lslam_vis_filter_device": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.POINTER(C.c_size_t)]),
+    "lslam_vis_add_to_fmap": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, c_float_p, C.c_int32, c_int32_p, c_float_p,
+                                        C.POINTER(C.c_size_t)]),
+    "lslam_debug_vis_votes": (C.c_int, [C.c_void_p, C.c_int32]),
     "lslam_voxel_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, c_float_p,
                                    C.c_size_t, C.POINTER(C.c_size_t)]),
     "lslam_voxel_grid2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, c_float_p,

@@ -287,6 +287,7 @@ int lslam_kfs_clear(lslam_kfs *k) {
   k->held_points = 0;
   k->n_local[0] = k->n_local[1] = 0;
   k->sc.drop();  // the descriptors go with the keyframes; the scan-context parameters stay
+  k->vis.drop();  // ... and so do the range images; the visibility parameters stay
   return LSLAM_OK;
 }
 

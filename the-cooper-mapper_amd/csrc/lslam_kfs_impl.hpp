@@ -115,6 +115,53 @@ struct FloorScratch {
   DevBuf<int32_t> d_counts_again;
 };
 
+// Visibility votes (lslam_vis_*, lslam_vis.hip): a coarse range image per keyframe and the scratch of a vote / filter call.
+// Empty -- no allocation -- until lslam_vis_setup.  Keyframe i's image (n_row * n_col floats) lives in slab i / slab_kf at
+// (i % slab_kf) * stride floats; a slab is never moved or freed before drop(), so images stay where they were built.
+struct VisJob {
+  const float4 *p[2];
+  uint32_t n[2];
+  float *img;
+};
+struct VisState {
+  bool set = false;
+  lslam_vis_params params{};
+  double el0 = 0.0, row_scale = 0.0, col_scale = 0.0;  // fov_down in rad, n_row / fov in rad, n_col / (2 pi): fp64, host
+  size_t stride = 0;    // floats per image
+  size_t slab_kf = 0;   // images per slab
+  size_t imaged = 0;    // keyframes 0 .. imaged-1 have their image
+  std::vector<std::unique_ptr<DevBuf<float>>> slabs;
+  PinBuf<VisJob> h_jobs;
+  DevBuf<VisJob> d_jobs;
+  // a call's scratch: per voter {image, inverse pose} up, the query points, the votes, the compaction's counts
+  PinBuf<float> h_in;
+  DevBuf<float> d_inv;
+  DevBuf<const float *> d_img;
+  PinBuf<const float *> h_img;
+  DevBuf<float4> d_pts, d_keep[2];
+  PinBuf<float4> h_pts;
+  DevBuf<uint32_t> d_votes, d_votes_again, d_block;
+  PinBuf<uint32_t> h_votes, h_count;
+  int64_t image_launches = 0, vote_launches = 0;
+  // the shape of the last lslam_vis_votes call (lslam_debug_vis_votes: the vote kernel alone, timed)
+  size_t last_n = 0;
+  int32_t last_ids = 0;
+
+  float *image(size_t id) const { return slabs[id / slab_kf]->p + (id % slab_kf) * stride; }
+  size_t bytes_held() const {
+    size_t b = 0;
+    for (const auto &s : slabs) b += s->cap * sizeof(float);
+    return b;
+  }
+  // the images go (their slabs are freed); parameters, scratch and counters stay.  The caller has waited for the stream.
+  void drop() {
+    slabs.clear();
+    imaged = 0;
+    last_n = 0;
+    last_ids = 0;
+  }
+};
+
 }  // namespace lslam
 
 struct lslam_kfs {
@@ -134,6 +181,7 @@ struct lslam_kfs {
   size_t n_local[2] = {0, 0};
   lslam::ScState sc;
   lslam::FloorScratch floor;
+  lslam::VisState vis;
 };
 
 namespace lslam {

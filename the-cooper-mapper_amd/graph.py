@@ -94,7 +94,7 @@ class Graph:
                  sc_params=None, loop_robust_kernel=None, loop_robust_delta=1.0, edge_information=None, range_sigma=None,
                  gps_sigma=None, gps_robust_kernel=None, gps_robust_delta=1.0, gps_min_spread=None, imu_orientation_sigma=None,
                  floor_sigma=None, floor_params=None, floor_robust_kernel=None, floor_robust_delta=1.0,
-                 floor_world_plane=(0.0, 0.0, 1.0, 0.0), odometry_information=None):
+                 floor_world_plane=(0.0, 0.0, 1.0, 0.0), odometry_information=None, remove_dynamic=False, dynamic_params=None):
         """``resident=True``: the keyframes' clouds live in a :class:`KeyframeStore` on the loop detector's context --
         ``add_frame`` uploads them once (``kf.store_id``), loop closure and ``get_final_feature_map`` read them there;
         ``keep_host_clouds=False`` then drops the host copies (``kf.corner_cloud`` / ``kf.surf_cloud`` fetch on demand).
@@ -144,7 +144,17 @@ class Graph:
         rejecting it, so no kernel rejects in the default configuration; it does once the edges are worth something --
         ``odometry_information`` or ``edge_information="hessian"`` (DESIGN, pose-graph section).
         ``odometry_information`` (6x6, or its 6 diagonal entries, over [translation, rotation]): the information of every
-        odometry edge; None: the reference's constant (graph.cpp:279-288)."""
+        odometry edge; None: the reference's constant (graph.cpp:279-288).
+        ``remove_dynamic=True`` (not in the reference, whose addFeatureCloud only voxel-filters; needs ``resident=True``): the
+        maps :meth:`get_final_feature_map` and :meth:`save` build leave out the points other keyframes looked through -- a car
+        that stood at a junction for two keyframes and drove off (``lslam_vis_*``, :mod:`.visibility`).  ``dynamic_params``:
+        ``KeyframeStore.vis_setup``'s keywords.  Voters of keyframe j: every keyframe, j included, whose optimised
+        translation lies within ``2 * max_range`` of j's, at its optimised ``estimate``; the keyframe's own points are
+        queried at the pose they are added with.  Off by default."""
+        self.remove_dynamic = bool(remove_dynamic)
+        if self.remove_dynamic and not (resident or appearance_loops):
+            raise ValueError("Graph: remove_dynamic=True needs resident=True")
+        self.dynamic_params = dict(dynamic_params or {})
         if odometry_information is None:
             self.odometry_information = ODOMETRY_INFORMATION
         else:
@@ -202,6 +212,8 @@ class Graph:
             self.store = KeyframeStore(self.loop_detector.scan_match.ctx, store_max_points, store_max_keyframes, store_slab_points)
             if self.appearance_loops:
                 self.store.sc_setup(**(sc_params or {}))
+            if self.remove_dynamic:
+                self.store.vis_setup(**self.dynamic_params)
         self.keyframe_updater = KeyframeUpdater()
         self.keyframes = []
         self.new_keyframes = []
@@ -417,6 +429,26 @@ class Graph:
         w = self.loop_weights()
         return [lp for lp, wk in zip(self.loops, w) if wk < threshold]
 
+    def _voters(self, kf, keyframes):
+        """The keyframes that vote on ``kf``'s points (``remove_dynamic``): those of ``keyframes`` in the store, ``kf`` included,
+        whose optimised translation lies within ``2 * max_range`` of ``kf``'s -> (store ids, 4x4 estimates)."""
+        reach = 2.0 * float(self.store.vis_info()["max_range"])
+        at = np.asarray(kf.estimate, np.float64)[:3, 3]
+        near = [o for o in keyframes if getattr(o, "store", None) is self.store
+                and np.linalg.norm(np.asarray(o.estimate, np.float64)[:3, 3] - at) <= reach]
+        return [o.store_id for o in near], [np.asarray(o.estimate, np.float64) for o in near]
+
+    def _add_stored(self, kf, fm, est, keyframes, removed):
+        """A stored keyframe's clouds into ``fm`` at ``est``; with ``remove_dynamic`` through the visibility filter, the
+        (corner, surf) points it left out appended to ``removed``."""
+        if not self.remove_dynamic:
+            kf.store.add_to_fmap(kf.store_id, fm, est)
+            return
+        if kf.store is not self.store:
+            raise ValueError("Graph: remove_dynamic=True needs every keyframe in the graph's store")
+        ids, poses = self._voters(kf, keyframes)
+        removed.append(kf.store.vis_add_to_fmap(kf.store_id, fm, est, ids, poses))
+
     # graph.cpp:150-199 (driven by Graph::save, :106-147)
     def get_final_feature_map(self, ctx=None, directory=None, cube_dims=(121, 111, 121), bootstrap=False, keyframes=None):
         """``Graph::getFinalFeatureMap``: rebuild the map from the optimised keyframes, one after the other -- keyframe k is
@@ -433,14 +465,19 @@ class Graph:
         bench's ``final_feature_map`` leg times.
 
         Returns a dict: ``map`` (the FeatureMap; the caller closes it), ``matched`` (one bool per keyframe), ``poses`` (the
-        refined 4x4 estimates, float32), ``added`` (keyframes added to the map), ``stats`` (the last lslam_stats)."""
+        refined 4x4 estimates, float32), ``added`` (keyframes added to the map), ``stats`` (the last lslam_stats) and, with
+        ``remove_dynamic``, ``removed`` (the (corner, surf) points left out, one pair per keyframe added)."""
         from .feature_map import FeatureMap, voxel_grid
         ctx = ctx or self.loop_detector.scan_match.ctx
+        if self.remove_dynamic and ctx is not self.store.ctx:
+            raise ValueError("Graph: remove_dynamic=True needs the map on the store's context")
+        removed = []
+        every = self.keyframes if keyframes is None else keyframes
         fm = FeatureMap(ctx, *cube_dims)
         fm.setup_filter_size(0.2, 0.2, 0.4)
         opts = ctx.default_opts()  # lidar_slam::ScanMatch scan_match; (ScanMatch.cpp:21-33)
         matched, poses, added, last = [], [], 0, None
-        for kf in (self.keyframes if keyframes is None else keyframes):
+        for kf in every:
             est = np.asarray(kf.estimate, np.float64).astype(np.float32).reshape(4, 4)  # node->estimate().cast<float>()
             fm.update(est[:3, 3])
             nc, ns = fm.surround_counts()
@@ -462,7 +499,9 @@ class Graph:
                 ok = int(status) == 0
             if ok or (bootstrap and not (nc >= 50 and ns >= 100)):
                 if stored:
-                    kf.store.add_to_fmap(kf.store_id, fm, est)
+                    self._add_stored(kf, fm, est, every, removed)
+                elif self.remove_dynamic:
+                    raise ValueError("Graph: remove_dynamic=True needs every keyframe in the graph's store")
                 else:
                     fm.add_feature_cloud(kf.corner_cloud, kf.surf_cloud, est)
                 added += 1
@@ -470,7 +509,10 @@ class Graph:
             poses.append(np.array(est, np.float32))
         if directory is not None:
             fm.save_cloud_to_files(directory)
-        return {"map": fm, "matched": matched, "poses": poses, "added": added, "stats": last}
+        out = {"map": fm, "matched": matched, "poses": poses, "added": added, "stats": last}
+        if self.remove_dynamic:
+            out["removed"] = removed
+        return out
 
     # graph.cpp:106-147
     def save(self, directory, bootstrap=False, max_iterations=1000):
@@ -501,7 +543,7 @@ class Graph:
                 est = np.asarray(kf.estimate, np.float64).astype(np.float32)
                 fm.update(est[:3, 3])
                 if getattr(kf, "store", None) is not None and kf.store.ctx is ctx:
-                    kf.store.add_to_fmap(kf.store_id, fm, est)
+                    self._add_stored(kf, fm, est, self.keyframes, [])
                 else:
                     fm.add_feature_cloud(kf.corner_cloud, kf.surf_cloud, est)
             os.makedirs(os.path.join(directory, "graph"), exist_ok=True)

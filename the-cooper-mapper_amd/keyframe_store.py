@@ -179,6 +179,40 @@ class KeyframeStore:
         self._check(self.lib.lslam_floor_detect_keyframes(self.h, len(ids), ids.ctypes.data_as(c_int32_p), C.byref(p), res))
         return [res[i].as_dict() for i in range(len(ids))]
 
+    # ---- visibility votes: the final map without moving objects (lslam_vis_*, :mod:`.visibility`) -----------------------------
+    def vis_setup(self, params=None, **kw):
+        """Install the visibility parameters (``n_row``, ``n_col``, ``fov_down_deg``, ``fov_up_deg``, ``min_range``,
+        ``max_range``, ``window``, ``abs_margin``, ``rel_margin``, ``min_free_votes``, ``up_axis``; what is not named keeps its
+        default).  Other parameters than those in force drop the range images held."""
+        from . import visibility
+        visibility.setup(self, params, **kw)
+
+    def vis_info(self):
+        from . import visibility
+        return visibility.info(self)
+
+    def vis_range_image(self, kid):
+        """Keyframe ``kid``'s range image (parity tap) -> (n_row, n_col) float32, +inf where nothing was seen."""
+        from . import visibility
+        return visibility.range_image(self, kid)
+
+    def vis_votes(self, ids, poses, points):
+        """The votes of keyframes ``ids`` at ``poses`` (4x4 each, graph <- sensor) on ``points`` (host array, or a contiguous
+        (n, 4) float32 torch tensor on the device) -> the packed words ``n_free | n_hit << 16``."""
+        from . import visibility
+        return visibility.votes(self, ids, poses, points)
+
+    def vis_filter(self, ids, poses, points):
+        """``points`` without the dynamic ones, in input order, compacted on the device -> (m, 4) float32."""
+        from . import visibility
+        return visibility.filter_points(self, ids, poses, points)
+
+    def vis_add_to_fmap(self, kid, fmap, tf, ids, poses):
+        """:meth:`add_to_fmap` with the filter in front: the keyframe's points at ``tf`` are voted on by keyframes ``ids`` at
+        ``poses``; what is not dynamic is added -> (corner, surf) points left out.  No cloud crosses PCIe."""
+        from . import visibility
+        return visibility.add_to_fmap(self, kid, fmap, tf, ids, poses)
+
     # ---- loop candidates by appearance: scan context (lslam_sc_*) ---------------------------------------------------------
     def sc_setup(self, **params):
         """Install the scan-context parameters (``n_ring``, ``n_sector``, ``max_range``, ``height_offset``, ``up_axis``;
