@@ -1572,6 +1572,11 @@ uint64_t lslam_debug_fit_inrange_launches(lslam_ctx *ctx);
 int lslam_debug_fit_inrange_ops(lslam_ctx *ctx, const float *a, const float *b, size_t n, float *out8);
 int lslam_debug_fit_inrange_fits(lslam_ctx *ctx, const float *nb_xyzw, const float *x_xyzw, size_t n, int32_t is_surf, float *out_inr8, float *out_gen8,
                                  int32_t *flags);
+/* The whole fit of the same elements (for the tests that hold it to float64: tests/fit_ref.py): out_*12[12 i ..] = A[3], B[3], 0, 0,
+ * coeff[4] of a line fit, plane[4], 0, 0, 0, 0, coeff[4] of a plane fit; inputs and flags as lslam_debug_fit_inrange_fits has them.
+ * A fit that did not match leaves its coefficient zero. */
+int lslam_debug_fit_stage(lslam_ctx *ctx, const float *nb_xyzw, const float *x_xyzw, size_t n, int32_t is_surf, float *out_inr12, float *out_gen12,
+                          int32_t *flags);
 /* ... of which those whose first pass read the x-subdivided cell tables (LSLAM_AB_GRID_CUBIC), lean or general */
 uint64_t lslam_debug_grid_fine_launches(lslam_ctx *ctx);
 /* the x-subdivided tables of the resident map: out[0], out[1] sub-cells per cell used (corner, surf; lowered where the table's

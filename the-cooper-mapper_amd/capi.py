@@ -612,6 +612,8 @@ SYMBOLS = {
     "lslam_debug_fit_inrange_ops": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float)]),
     "lslam_debug_fit_inrange_fits": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_int32,
                                      C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "lslam_debug_fit_stage": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.c_int32,
+                              C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "lslam_debug_grid_fine_launches": (C.c_uint64, [C.c_void_p]),
     "lslam_debug_grid_fine_info": (None, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     "lslam_debug_grid_fine_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, c_int32_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32),

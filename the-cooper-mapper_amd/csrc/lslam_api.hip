@@ -811,6 +811,21 @@ int lslam_debug_fit_inrange_fits(lslam_ctx *ctx, const float *nb_xyzw, const flo
     return LSLAM_ERR_HIP;
   return LSLAM_OK;
 }
+int lslam_debug_fit_stage(lslam_ctx *ctx, const float *nb_xyzw, const float *x_xyzw, size_t n, int32_t is_surf, float *out_inr12, float *out_gen12,
+                          int32_t *flags) {
+  if (!ctx || !nb_xyzw || !x_xyzw || !out_inr12 || !out_gen12 || !flags || n == 0 || n > (1u << 22)) return LSLAM_ERR_INVALID;
+  if (hipSetDevice(ctx->device) != hipSuccess) return LSLAM_ERR_HIP;
+  TmpDev dn(n * 80), dx(n * 16), di(n * 48), dg(n * 48), df(n * 4);
+  if (!dn.p || !dx.p || !di.p || !dg.p || !df.p) return LSLAM_ERR_HIP;
+  if (hipMemcpy(dn.p, nb_xyzw, n * 80, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dx.p, x_xyzw, n * 16, hipMemcpyHostToDevice) != hipSuccess) return LSLAM_ERR_HIP;
+  if (launch_fit_stage((const float4 *)dn.p, (const float4 *)dx.p, (int)n, is_surf, (float *)di.p, (float *)dg.p, (int32_t *)df.p, ctx->stream) != hipSuccess)
+    return LSLAM_ERR_HIP;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return LSLAM_ERR_HIP;
+  if (hipMemcpy(out_inr12, di.p, n * 48, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(out_gen12, dg.p, n * 48, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(flags, df.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return LSLAM_ERR_HIP;
+  return LSLAM_OK;
+}
 uint64_t lslam_debug_grid_fine_launches(lslam_ctx *ctx) { return ctx ? ctx->grid_fine_launches : 0; }
 void lslam_debug_grid_fine_info(lslam_ctx *ctx, uint64_t out[4], float *build_ms) {
   const bool have = ctx && ctx->kfc.view.cell_start && ctx->kfs.view.cell_start;

@@ -305,6 +305,7 @@ hipError_t launch_sweep_grid(const SweepArgs &a, int jtj_mode, hipStream_t s, hi
                              bool inrange = false);
 hipError_t launch_fit_inrange_ops(const float *a, const float *b, int n, float *out, hipStream_t s);  // (the tests': lslam_debug_fit_inrange_ops / _fits)
 hipError_t launch_fit_inrange_fits(const float4 *nbs, const float4 *X, int n, int is_surf, float *out_inr, float *out_gen, int32_t *flags, hipStream_t s);
+hipError_t launch_fit_stage(const float4 *nbs, const float4 *X, int n, int is_surf, float *out_inr, float *out_gen, int32_t *flags, hipStream_t s);
 hipError_t launch_sweep_wide(const SweepArgs &a, hipStream_t s);  // sweep_wide_kernel (its prefix: launch_sweep_plan with_prefix)
 hipError_t launch_knn5_wide(const CellGrid &G, const float4 *q, int nq, float nf_slack, int32_t *idx, float *d2, uint8_t *undecided, hipStream_t s);
 hipError_t launch_knn5_grid(const CellGrid &G, const TreeView &T, const float4 *q, int nq, int32_t *idx, float *d2,

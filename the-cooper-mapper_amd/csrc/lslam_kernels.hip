@@ -779,6 +779,51 @@ __global__ void fit_inrange_fits_kernel(const float4 *nbs, const float4 *X, int 
   }
   flags[i] = f;
 }
+// ... and the whole fit (lslam_debug_fit_stage): the same two fits per lane, out_inr / out_gen[12 i ..] = A[3], B[3], 0, 0, coeff[4]
+// of a line, plane[4], 0, 0, 0, 0, coeff[4] of a plane; the same flags
+__global__ void fit_stage_kernel(const float4 *nbs, const float4 *X, int n, int is_surf, float *out_inr, float *out_gen, int32_t *flags) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float4 nb[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) nb[j] = nbs[(size_t)i * 5 + j];
+  const float sel[3] = {X[i].x, X[i].y, X[i].z};
+  int f = 0;
+  for (int inr = 0; inr < 2; ++inr) {
+    float r[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, coeff[4] = {0, 0, 0, 0};
+    bool matched = false, kept = false;
+    if (is_surf) {
+      float plane[4] = {0, 0, 0, 0};
+      FitRange fr;
+      matched = inr ? find_plane<true>(nb, 0.2f, plane, &fr) : find_plane(nb, 0.2f, plane);
+      if (inr && fr.bad) f |= 16;
+      if (matched) kept = inr ? surf_coeff<true>(plane, sel, coeff) : surf_coeff(plane, sel, coeff);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r[k] = plane[k];
+    } else {
+      float A[3] = {0, 0, 0}, B[3] = {0, 0, 0};
+      matched = inr ? find_line<true>(nb, A, B) : find_line(nb, A, B);
+      if (matched) kept = inr ? corner_coeff<true>(A, B, sel, coeff) : corner_coeff(A, B, sel, coeff);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        r[k] = A[k];
+        r[3 + k] = B[k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[8 + k] = coeff[k];
+    float *o = (inr ? out_inr : out_gen) + (size_t)i * 12;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o[k] = r[k];
+    f |= (kept ? 1 : 0) << (inr ? 0 : 1) | (matched ? 1 : 0) << (inr ? 2 : 3);
+  }
+  flags[i] = f;
+}
+hipError_t launch_fit_stage(const float4 *nbs, const float4 *X, int n, int is_surf, float *out_inr, float *out_gen, int32_t *flags, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(fit_stage_kernel, dim3((n + 255) / 256), dim3(256), 0, s, nbs, X, n, is_surf, out_inr, out_gen, flags);
+  return hipGetLastError();
+}
 hipError_t launch_fit_inrange_ops(const float *a, const float *b, int n, float *out, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(fit_inrange_ops_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, b, n, out);

@@ -156,6 +156,21 @@ class Context:
         """lslam_debug_fit_inrange_launches: ... of the lean ones, those with the in-range fit (LSLAM_FIT_INRANGE=0: none)."""
         return int(self.lib.lslam_debug_fit_inrange_launches(self.h))
 
+    def fit_stage(self, nb, x, is_surf):
+        """lslam_debug_fit_stage: one line fit (plane fit when is_surf) with its coefficient per element, on the five
+        neighbours nb (n, 5, 4) and the point x (n, 4), by the in-range instantiation and by the general one ->
+        (out_inr (n, 12), out_gen (n, 12), flags (n,) int32); a row is A[3], B[3], 0, 0, coeff[4] of a line and plane[4], 0,
+        0, 0, 0, coeff[4] of a plane; flags: bits 0 / 1 kept (in range / general), bits 2 / 3 matched, bit 4 the plane fit's
+        guard refused an operand."""
+        nb, x = np.ascontiguousarray(nb, np.float32), np.ascontiguousarray(x, np.float32)
+        n = len(x)
+        if nb.shape != (n, 5, 4) or x.shape != (n, 4):
+            raise ValueError("nb must be (n, 5, 4) and x (n, 4), got %r and %r" % (nb.shape, x.shape))
+        oi, og, fl = np.zeros((n, 12), np.float32), np.zeros((n, 12), np.float32), np.zeros(n, np.int32)
+        self._check(self.lib.lslam_debug_fit_stage(self.h, _fp(nb), _fp(x), n, int(bool(is_surf)), _fp(oi), _fp(og),
+                                                   fl.ctypes.data_as(c_int32_p)))
+        return oi, og, fl
+
     def grid_fine_launches(self):
         """lslam_debug_grid_fine_launches: ... of which with the first pass over the x-subdivided cell tables."""
         return int(self.lib.lslam_debug_grid_fine_launches(self.h))
