@@ -220,6 +220,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed; new entry points and an enum (lslam_pg_set_priors, _num_priors, _prior_robust, lslam_g2o_read_priors: unary constraints on pose-graph vertices). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_floor_*, lslam_debug_floor_hypotheses: floor detection; lslam_pg_set_plane_priors, _num_plane_priors, _plane_prior_robust, lslam_g2o_read_plane_priors: plane priors). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_vis_*, lslam_debug_vis_votes: visibility votes over the keyframe store). */
+/* still 7: no struct changed; new entry points and structs of their own (lslam_mapq_*: map quality, mean map entropy and mean plane variance; lslam_traj_*: trajectory evaluation). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -935,6 +936,129 @@ int lslam_vis_add_to_fmap(lslam_kfs *kfs, int32_t id, lslam_fmap *fm, const floa
  * last lslam_vis_votes call and on its points, voters and poses, voting into a buffer of its own; not waited for (time it with
  * events on lslam_stream).  LSLAM_ERR_INVALID before such a call has run (or after lslam_kfs_clear / new parameters). */
 int lslam_debug_vis_votes(lslam_kfs *kfs, int32_t launches);
+
+/* ---- map quality: mean map entropy and mean plane variance; trajectory evaluation ------------------------------------------
+ * The reference's only accuracy tool is map_evaluation/Evaluation.cpp (lidar pose against GPS: lslam_traj_eval below).  For the
+ * MAP it has none; these are the usual ground-truth-free crispness measures (Droeschel et al. 2014; Razlaw et al. 2015): per
+ * point the covariance of its neighbourhood within a radius, from it the differential entropy of the fitted Gaussian (MME: the
+ * mean) and the variance along the neighbourhood's normal (MPV: the mean).  Lower is crisper.  This comment is the
+ * specification (restated in numpy by tests/map_quality_ref.py).
+ *
+ * INPUTS.  A surface cloud S and a query cloud Q (Q = S when no queries are given), records {x, y, z, -} of fp32.  Non-finite
+ * points of S are dropped.  Non-finite points of Q are counted in n_nonfinite; their outputs are written as for a sparse point.
+ *
+ * Per finite query q:
+ * NEIGHBOURS.  p in S is a neighbour iff, in fp32, (dx*dx + dy*dy) + dz*dz < (float)((double)r * r), d = p - q per axis, the
+ * products summed left to right and nothing contracted (the survey extractor's rule).  A query that is itself in S counts
+ * itself.  k = the number of neighbours.  k < min_neighbors: the point is SPARSE -- counted in n_sparse, its eigenvalues and
+ * entropy are NaN, its count is still k.
+ * SUMS, exact.  Per axis d = (double)p - (double)q (exact) and D = llrint(d * 65536.0), round half to even: units of 2^-16 m,
+ * a quantisation of 15 um whose variance, 2e-11 m^2, lies below every floor used here.  The nine sums  Dx, Dy, Dz, DxDx, DxDy,
+ * DxDz, DyDy, DyDz, DzDz  over the neighbours are int64.  Range: a neighbour has |d| < 8 + 3e-7 per axis (r <= 8 and the fp32
+ * test), so |D| <= 2^19, a product is at most 2^38, and fewer than 2^25 surface points keep every sum below 2^63.  Integer
+ * sums do not depend on the order of summation: results are bit-identical from run to run, for any order of S and for any
+ * launch geometry (the property the visibility votes have).
+ * COVARIANCE, a fixed fp64 sequence, nothing contracted.  Each sum is converted to double (one correctly rounded conversion)
+ * and scaled by 2^-16 (first moments) or 2^-32 (second moments), exactly; with K = (double)k
+ *   mx = sx / K, my = sy / K, mz = sz / K;  a00 = sxx / K - mx * mx,  a01 = sxy / K - mx * my, ... a22 = szz / K - mz * mz
+ * EIGENVALUES.  Ten cyclic sweeps (0,1), (0,2), (1,2) of the Jacobi rotation the survey extractor's normals use (one shared
+ * definition), then the diagonal sorted ascending: l0 <= l1 <= l2.
+ * PLANE VARIANCE  v = max(l0, 0).
+ * ENTROPY  h = 0.5 * ((ln l0' + ln l1') + ln l2') + 4.2568155996140185, lk' = max(lk, lambda_floor); the constant is
+ * 1.5 * ln(2 pi e) as that literal.  The floor keeps an exactly planar or collinear neighbourhood defined.
+ *
+ * AGGREGATES over the DEFINED points (finite and not sparse), exact as well:
+ *   sum_entropy_q32 = sum llrint(h * 2^32),  sum_plane_var_q30 = sum llrint(v * 2^30),  sum_neighbors = sum k,  max_neighbors
+ * and from them mean_entropy = ((double)sum_entropy_q32 / 2^32) / n_defined, mean_plane_variance = ((double)sum_plane_var_q30 /
+ * 2^30) / n_defined, mean_neighbors = (double)sum_neighbors / n_defined; NaN, all three, when n_defined is 0 (the status is still
+ * LSLAM_OK).  (|h| < 38 for lambda_floor >= 1e-12: the entropy sum then stays below 2^63 for every admissible cloud.)
+ *
+ * REFUSED with LSLAM_ERR_INVALID before anything runs, lslam_last_error naming the cause: 2^25 or more surface or query points;
+ * radius not finite or outside (0, 8]; min_neighbors below 3; lambda_floor not finite or not positive; a stride under 12 bytes
+ * or no multiple of 4; a null cloud with points; which outside {0, 1}; a keyframe id out of range; a pose that is not finite. */
+typedef struct lslam_mapq_params {
+  float radius;            /* 0.3    (0, 8] [m] */
+  int32_t min_neighbors;   /* 5      >= 3 */
+  double lambda_floor;     /* 1e-8   > 0 [m^2] */
+  int32_t reserved[4];     /* zero */
+} lslam_mapq_params;
+typedef struct lslam_mapq_stats {
+  int64_t n_surface;           /* finite surface points */
+  int64_t n_query;             /* query points given */
+  int64_t n_nonfinite;         /* ... not finite */
+  int64_t n_sparse;            /* ... finite with fewer than min_neighbors neighbours */
+  int64_t n_defined;           /* ... the others */
+  int64_t sum_entropy_q32;
+  int64_t sum_plane_var_q30;
+  int64_t sum_neighbors;
+  int64_t max_neighbors;
+  double mean_entropy;         /* MME */
+  double mean_plane_variance;  /* MPV [m^2] */
+  double mean_neighbors;
+  /* device time of the call's stages (events on the context's stream): both clouds' sorts by grid cell; the neighbourhood
+   * sums; the per-point tail with the reduction of the aggregates */
+  float ms_sort, ms_kernel, ms_reduce, reserved;
+} lslam_mapq_stats;
+/* Writes every byte of *p (the defaults above). */
+void lslam_mapq_default_params(lslam_mapq_params *p);
+size_t lslam_sizeof_mapq_params(void);
+size_t lslam_sizeof_mapq_stats(void);
+/* Host clouds ({x, y, z} at byte 0 of each record).  queries NULL: the surface queries itself (nq, qstride_bytes ignored).
+ * params NULL: the defaults.  Any output may be NULL: out_lambda3[nq][3] and out_entropy[nq] doubles (NaN where undefined),
+ * out_count[nq] the neighbour counts, in the order of the queries. */
+int lslam_mapq_eval(lslam_ctx *ctx, const void *surface, size_t n, size_t stride_bytes, const void *queries, size_t nq,
+                    size_t qstride_bytes, const lslam_mapq_params *params, lslam_mapq_stats *stats, double *out_lambda3,
+                    double *out_entropy, int32_t *out_count);
+/* The same on clouds that are in the ctx's device memory, packed {x, y, z, -}, with device outputs (or NULL): nothing but the
+ * stats crosses PCIe.  Waited for. */
+int lslam_mapq_eval_device(lslam_ctx *ctx, const float *d_surface, size_t n, const float *d_queries, size_t nq,
+                           const lslam_mapq_params *params, lslam_mapq_stats *stats, double *d_lambda3, double *d_entropy,
+                           int32_t *d_count);
+/* The whole cube map where it lies (which: 0 corner, 1 surf), queried by itself.  An addFeatureCloud begun and not yet committed
+ * is committed first. */
+int lslam_mapq_fmap(lslam_fmap *fm, int32_t which, const lslam_mapq_params *params, lslam_mapq_stats *stats);
+/* The named keyframes' clouds of one type, each moved by its pose (poses16[n_ids * 16]: row-major 4x4 fp32, graph <- sensor;
+ * ((T0 x + T1 y) + T2 z) + T3 per row in fp32 as lslam_kfs_debug_local_clouds transforms) into ONE device cloud, queried by
+ * itself: the form that scores a trajectory -- the same clouds at odometry poses against the same clouds at optimised poses.
+ * No cloud crosses PCIe: the store's byte counters stay.  The same id may be named more than once. */
+int lslam_mapq_keyframes(lslam_kfs *kfs, int32_t n_ids, const int32_t *ids, const float *poses16, int32_t which,
+                         const lslam_mapq_params *params, lslam_mapq_stats *stats);
+
+/* Trajectory evaluation (map_evaluation/Evaluation.cpp:39-150: lidarToMapHandler and process), on the host in fp64; needs no
+ * device and no context.  est_xyz[n_est * 3], ref_xyz[n_ref * 3]; ref_stamp ascending.
+ * ASSOCIATION.  Estimate i is paired with the reference sample nearest in time: scanning from the newest reference backwards
+ * while |t_i - ref_stamp| strictly decreases (:44-51), so a tie goes to the later sample.  (The reference keeps the newest 1000
+ * fixes in a ring and sees only those that arrived before the estimate; here every sample is there for every estimate.)
+ * DIFFERENCES  |dx|, |dy|, |dz| and dist = sqrt((dx*dx + dy*dy) + dz*dz) (:53-58).
+ * MAXIMA over EVERY pair -- the reference updates its maxima (:59-62) before it tests the gate (:64); kept.
+ * GATE.  A pair with dist > gate (the reference's literal: 10 m; 0: no gate) is counted in n_gated and leaves everything else.
+ * STATISTICS over the n_used others, summed in the order of the estimates from zero (:107-131): mean[4] of |dx|, |dy|, |dz|,
+ * dist, mean_dt; var[4] = sum (x - mean)^2 / (n_used - 1) (NaN for n_used < 2; means NaN for n_used = 0).
+ * ALIGNED ATE (not in the reference), with align != 0: the rigid transform (R | t) that best maps the used estimates onto their
+ * references in the least-squares sense -- Kabsch on centred coordinates in fp64, the 3x3 SVD through the Jacobi
+ * eigendecomposition of H^T H, det(R) = +1 enforced (the reflection case) -- then ate_rmse = sqrt(mean |R e + t - r|^2) and
+ * T_align (row-major 4x4).  Fewer than three used pairs, or collinear ones (the second singular value of H, the 3x3 sum of
+ * centred estimate times centred reference, not above 1e-6 of the first): aligned = 0, ate_rmse NaN, T_align the identity.
+ * Without references (n_ref = 0) there are no pairs: n_used = n_gated = 0.
+ * LSLAM_ERR_INVALID: null arrays with something to read, null stats, a gate that is negative or not finite. */
+typedef struct lslam_traj_params {
+  double gate;          /* 10.0   >= 0 [m]; 0: no gate */
+  int32_t align;        /* 0 */
+  int32_t reserved[3];  /* zero */
+} lslam_traj_params;
+typedef struct lslam_traj_stats {
+  int64_t n_used, n_gated;
+  double mean[4], var[4], max[4];  /* |dx|, |dy|, |dz|, dist */
+  double mean_dt;
+  int32_t aligned, reserved;
+  double ate_rmse;
+  double T_align[16];
+} lslam_traj_stats;
+void lslam_traj_default_params(lslam_traj_params *p);
+size_t lslam_sizeof_traj_params(void);
+size_t lslam_sizeof_traj_stats(void);
+int lslam_traj_eval(const double *est_stamp, const double *est_xyz, size_t n_est, const double *ref_stamp, const double *ref_xyz,
+                    size_t n_ref, const lslam_traj_params *params, lslam_traj_stats *stats);
 
 /* pcl::VoxelGrid<PointXYZI>::filter with a cubic leaf on one cloud (LaserMatcher.cpp:289-301,
  * ScanMatch.cpp:362-398 scanMatchLocal): one centroid {x,y,z,intensity} per occupied voxel, in

@@ -77,6 +77,13 @@ public:
   // :378-462
   bool saveCloudToFiles() { return lslam_fmap_save(_fm, _filesDirectory.c_str()) == LSLAM_OK; }
   bool loadCloudFromFiles() { return lslam_fmap_load(_fm, _filesDirectory.c_str()) == LSLAM_OK; }
+  // Not in the reference: mean map entropy and mean plane variance (lslam_mapq_fmap) of the whole map of one feature type
+  // (which: 0 corner, 1 surf) where it lies; params == nullptr: the defaults.  Lower is crisper.
+  lslam_mapq_stats quality(int which = 1, const lslam_mapq_params *params = nullptr) {
+    lslam_mapq_stats st;
+    check(lslam_mapq_fmap(_fm, which, params, &st));
+    return st;
+  }
 
   lslam_fmap *handle() { return _fm; }
 

@@ -244,12 +244,31 @@ public:
     _err = lslam_last_error();
     return false;
   }
+  // ---- map quality (lslam_mapq_keyframes) ----
+  // Mean map entropy and mean plane variance of keyframes ids' clouds of one type (which: 0 corner, 1 surf) put together at
+  // poses[16 k ..] (row-major 4x4 float, graph <- sensor): the score of a trajectory.  params == nullptr: the defaults.
+  bool mapQuality(const std::vector<int32_t> &ids, const std::vector<float> &poses, int which, const lslam_mapq_params *params,
+                  lslam_mapq_stats &stats) {
+    if (poses.size() != 16 * ids.size()) { _err = "mapQuality: one 4x4 pose per id"; return false; }
+    if (lslam_mapq_keyframes(_h, (int32_t)ids.size(), ids.data(), poses.data(), which, params, &stats) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
   const std::string &lastError() const { return _err; }
 
 private:
   lslam_kfs *_h = nullptr;
   std::string _err;
 };
+
+// lslam_traj_eval on vectors (map_evaluation/Evaluation.cpp's statistics, and the rigidly aligned ATE): est_xyz / ref_xyz hold
+// three doubles per stamp, ref_stamp ascends.  params == nullptr: the defaults (gate 10 m, no alignment).  Host code: no device.
+inline bool trajectoryEval(const std::vector<double> &est_stamp, const std::vector<double> &est_xyz, const std::vector<double> &ref_stamp,
+                           const std::vector<double> &ref_xyz, const lslam_traj_params *params, lslam_traj_stats &stats) {
+  if (est_xyz.size() != 3 * est_stamp.size() || ref_xyz.size() != 3 * ref_stamp.size()) return false;
+  return lslam_traj_eval(est_stamp.data(), est_xyz.data(), est_stamp.size(), ref_stamp.data(), ref_xyz.data(), ref_stamp.size(), params,
+                         &stats) == LSLAM_OK;
+}
 
 // pose_graph/keyframe.h
 struct KeyFrame {
@@ -944,6 +963,43 @@ public:
     double R[9], t[3], W[3];
     if (lslam_debug_icp_fit(S, R, t, W, nullptr) < 0) return 0.0;
     return std::sqrt(W[1] > 0.0 ? W[1] : 0.0);  // F^T F of the centred fixes F: its singular values are those of F, squared
+  }
+  // Mean map entropy and mean plane variance (lslam_mapq_*; not in the reference) of the keyframes' clouds of one type (which:
+  // 0 corner, 1 surf) put together at their poses -- odom = false: the optimised estimates; true: the odometry poses they started
+  // from -- so the two calls score what the optimisation did to the MAP, without ground truth: lower is crisper.  A resident
+  // graph evaluates the clouds where they lie in the store; a host graph moves them on the host by the same fp32 formula and
+  // uploads.  which_keyframes == nullptr: `keyframes`.  params == nullptr: the defaults.
+  bool mapQuality(bool odom, int which, const lslam_mapq_params *params, lslam_mapq_stats &stats,
+                  const std::vector<KeyFrame::Ptr> *which_keyframes = nullptr) {
+    const std::vector<KeyFrame::Ptr> &every = which_keyframes ? *which_keyframes : keyframes;
+    if (which < 0 || which > 1) { _err = "mapQuality: which is 0 (corner) or 1 (surf)"; return false; }
+    std::vector<int32_t> ids;
+    std::vector<float> poses(16 * every.size()), cloud;
+    bool stored = (bool)store;
+    for (size_t k = 0; k < every.size(); ++k) {
+      to_float16(odom ? every[k]->odom : every[k]->estimate, &poses[16 * k]);
+      stored = stored && every[k]->store == store->handle();
+      ids.push_back(every[k]->store_id);
+    }
+    if (stored) {
+      if (store->mapQuality(ids, poses, which, params, stats)) return true;
+      _err = store->lastError();
+      return false;
+    }
+    for (size_t k = 0; k < every.size(); ++k) {
+      const std::vector<float> &c = which ? every[k]->surfCloud : every[k]->cornerCloud;
+      const float *T = &poses[16 * k];
+      for (size_t i = 0; i + 3 < c.size(); i += 4) {  // pcl::transformPointCloud, fp32
+        const float x = c[i], y = c[i + 1], z = c[i + 2];
+        cloud.push_back(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);
+        cloud.push_back(((T[4] * x + T[5] * y) + T[6] * z) + T[7]);
+        cloud.push_back(((T[8] * x + T[9] * y) + T[10] * z) + T[11]);
+      }
+    }
+    if (lslam_mapq_eval(_ctx, cloud.data(), cloud.size() / 3, 12, nullptr, 0, 0, params, &stats, nullptr, nullptr, nullptr) == LSLAM_OK)
+      return true;
+    _err = lslam_last_error();
+    return false;
   }
   Mat4d tf_odom2graph;
   int last_iterations = 0;

@@ -271,6 +271,35 @@ class LslamVisStats(C.Structure):
                 ("image_launches", C.c_int64), ("vote_launches", C.c_int64)]
 
 
+class LslamMapqParams(C.Structure):
+    """lslam_mapq_params (include/lslam_c.h)."""
+    _fields_ = [("radius", C.c_float), ("min_neighbors", C.c_int32), ("lambda_floor", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class LslamMapqStats(C.Structure):
+    """lslam_mapq_stats (include/lslam_c.h)."""
+    _fields_ = [("n_surface", C.c_int64), ("n_query", C.c_int64), ("n_nonfinite", C.c_int64), ("n_sparse", C.c_int64),
+                ("n_defined", C.c_int64), ("sum_entropy_q32", C.c_int64), ("sum_plane_var_q30", C.c_int64),
+                ("sum_neighbors", C.c_int64), ("max_neighbors", C.c_int64), ("mean_entropy", C.c_double),
+                ("mean_plane_variance", C.c_double), ("mean_neighbors", C.c_double), ("ms_sort", C.c_float),
+                ("ms_kernel", C.c_float), ("ms_reduce", C.c_float), ("reserved", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+class LslamTrajParams(C.Structure):
+    """lslam_traj_params (include/lslam_c.h)."""
+    _fields_ = [("gate", C.c_double), ("align", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class LslamTrajStats(C.Structure):
+    """lslam_traj_stats (include/lslam_c.h)."""
+    _fields_ = [("n_used", C.c_int64), ("n_gated", C.c_int64), ("mean", C.c_double * 4), ("var", C.c_double * 4),
+                ("max", C.c_double * 4), ("mean_dt", C.c_double), ("aligned", C.c_int32), ("reserved", C.c_int32),
+                ("ate_rmse", C.c_double), ("T_align", C.c_double * 16)]
+
+
 class LslamFloorParams(C.Structure):
     """lslam_floor_params (include/lslam_c.h)."""
     _fields_ = [("up", C.c_float * 3), ("sensor_height", C.c_float), ("height_clip_range", C.c_float), ("max_range", C.c_float),
@@ -458,6 +487,21 @@ SYMBOLS = {
     "lslam_vis_add_to_fmap": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, c_float_p, C.c_int32, c_int32_p, c_float_p,
                                         C.POINTER(C.c_size_t)]),
     "lslam_debug_vis_votes": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lslam_mapq_default_params": (None, [C.POINTER(LslamMapqParams)]),
+    "lslam_sizeof_mapq_params": (C.c_size_t, []),
+    "lslam_sizeof_mapq_stats": (C.c_size_t, []),
+    "lslam_mapq_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                  C.POINTER(LslamMapqParams), C.POINTER(LslamMapqStats), c_double_p, c_double_p, c_int32_p]),
+    "lslam_mapq_eval_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(LslamMapqParams),
+                                         C.POINTER(LslamMapqStats), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lslam_mapq_fmap": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(LslamMapqParams), C.POINTER(LslamMapqStats)]),
+    "lslam_mapq_keyframes": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, C.c_int32, C.POINTER(LslamMapqParams),
+                                       C.POINTER(LslamMapqStats)]),
+    "lslam_traj_default_params": (None, [C.POINTER(LslamTrajParams)]),
+    "lslam_sizeof_traj_params": (C.c_size_t, []),
+    "lslam_sizeof_traj_stats": (C.c_size_t, []),
+    "lslam_traj_eval": (C.c_int, [c_double_p, c_double_p, C.c_size_t, c_double_p, c_double_p, C.c_size_t, C.POINTER(LslamTrajParams),
+                                  C.POINTER(LslamTrajStats)]),
     "lslam_voxel_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, c_float_p,
                                    C.c_size_t, C.POINTER(C.c_size_t)]),
     "lslam_voxel_grid2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, c_float_p,

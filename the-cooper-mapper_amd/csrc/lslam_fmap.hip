@@ -2222,6 +2222,8 @@ int fmap_view(lslam_fmap *fm, FmapView *out) {
   return LSLAM_OK;
 }
 
+lslam_ctx *fmap_ctx(lslam_fmap *fm) { return fm ? fm->ctx : nullptr; }
+
 // the PCD reader of lslam_fmap_load for the paged window of lslam_loc.hip, which reads single cube files
 bool fmap_read_pcd(const char *path, std::vector<float4> &out, std::string &err) { return read_pcd(std::string(path), out, err); }
 // ... and the cube-file writer of lslam_fmap_save for lslam_survey.hip, which saves a map it extracted in the same layout

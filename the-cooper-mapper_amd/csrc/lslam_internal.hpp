@@ -433,6 +433,7 @@ enum CtxSlot : int {
   CTX_SLOT_ODOM,          // lslam_odom.hip: the hidden node of lslam_odometry_match
   CTX_SLOT_SCANPREP,      // lslam_scanprep.hip
   CTX_SLOT_FLOOR,         // lslam_floor.hip: the single-cloud floor detection
+  CTX_SLOT_MAPQ,          // lslam_mapq.hip: the map-quality evaluation's tables, sums and staging
   CTX_N_SLOTS
 };
 struct CtxSlotEntry {
@@ -493,6 +494,7 @@ int fmap_set_clouds(lslam_fmap *fm, const void *corner, size_t n_corner, const v
 int fmap_clear(lslam_fmap *fm);
 int fmap_copy(lslam_fmap *dst, lslam_fmap *src);
 int fmap_view(lslam_fmap *fm, FmapView *out);
+lslam_ctx *fmap_ctx(lslam_fmap *fm);  // the context the map lives on (nullptr for a null map)
 bool fmap_read_pcd(const char *path, std::vector<float4> &out, std::string &err);  // x y z intensity of an ascii or binary PCD
 bool fmap_write_pcd(const char *path, const float4 *p, size_t n);  // one cube file as lslam_fmap_save writes it
 

@@ -239,6 +239,48 @@ int index_cloud(lslam_kfs *k, const float4 *in, size_t n, lslam::DevBuf<float4> 
 
 }  // namespace
 
+namespace lslam {
+
+// The named keyframes' clouds of one type, EVERY one moved by its pose (row-major 4x4 fp32 each), appended in the order named
+// into out (reserved here) -> *total points.  kfs_gather_kernel leaves its candidate 0 as it is, so each launch runs with an
+// empty candidate 0 and up to KFS_MAX_CAND - 1 keyframes behind it; enqueued on the store's stream, not waited for.  The ids
+// have been checked by the caller.
+int kfs_gather_posed(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const float *poses16, int which, DevBuf<float4> &out, size_t *total_out) {
+  size_t total = 0;
+  for (int32_t c = 0; c < n_ids; ++c) total += k->kfs[(size_t)ids[c]].n[which];
+  *total_out = total;
+  if (total > (size_t)INT32_MAX) {
+    lslam::set_error("keyframe store: the named keyframes' clouds hold more than 2^31 points");
+    return LSLAM_ERR_INVALID;
+  }
+  KFS_TRY(out.reserve(total ? total : 1));
+  size_t base = 0;
+  for (int32_t c0 = 0; c0 < n_ids; c0 += KFS_MAX_CAND - 1) {
+    const int m = n_ids - c0 < KFS_MAX_CAND - 1 ? n_ids - c0 : KFS_MAX_CAND - 1;
+    GatherArgs a{};
+    size_t chunk = 0;
+    a.src[0] = nullptr;
+    a.off[0] = 0;
+    for (int j = 0; j < m; ++j) {
+      const KeyframeClouds &kc = k->kfs[(size_t)ids[c0 + j]];
+      a.src[j + 1] = kc.p[which];
+      a.off[j + 1] = (int32_t)chunk;
+      chunk += kc.n[which];
+      std::memcpy(a.T[j + 1], poses16 + 16 * (size_t)(c0 + j), 12 * sizeof(float));
+    }
+    a.off[m + 1] = (int32_t)chunk;
+    a.n_cand = m + 1;
+    a.out = out.p + base;
+    base += chunk;
+    if (!chunk) continue;
+    hipLaunchKernelGGL(kfs_gather_kernel, dim3((unsigned)((chunk + 255) / 256)), dim3(256), 0, k->stream, a);
+    KFS_TRY(hipGetLastError());
+  }
+  return LSLAM_OK;
+}
+
+}  // namespace lslam
+
 extern "C" {
 
 int lslam_kfs_create(lslam_ctx *ctx, size_t max_points_per_type, int32_t max_keyframes, size_t slab_points, lslam_kfs **out) {

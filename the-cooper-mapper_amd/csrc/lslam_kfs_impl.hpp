@@ -201,6 +201,9 @@ inline int check_kfs(lslam_kfs *k, const char *what) {
   return LSLAM_OK;
 }
 
+// lslam_kfs.hip: the named keyframes' clouds of one type, each moved by its pose, as one device cloud (lslam_mapq_keyframes)
+int kfs_gather_posed(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const float *poses16, int which, DevBuf<float4> &out, size_t *total_out);
+
 inline int check_id(const lslam_kfs *k, const char *what, int32_t id) {
   if (id < 0 || (size_t)id >= k->kfs.size()) {
     char b[200];

@@ -32,6 +32,7 @@
 
 #include "../../include/lslam_c.h"
 #include "lslam_internal.hpp"
+#include "lslam_jacobi_dev.hpp"
 
 namespace {
 
@@ -55,7 +56,8 @@ using lslam::DevBuf;
 
 constexpr int SV_BLOCK = 256;
 constexpr int SWEEPS_PER_CHECK = 4;
-constexpr int JACOBI_SWEEPS = 10;  // cyclic sweeps of the 3x3 Jacobi iteration: a fixed count (fp64 converges in five or six)
+using lslam::JACOBI_SWEEPS;
+using lslam::sv_rotate;
 constexpr double GRID_CELL_PAD = 1.0 + 1.0 / 1024.0;  // a radius grid's cell is this much wider than the radius (see SGrid)
 
 inline dim3 blocks_for(size_t n) { return dim3((unsigned)((n + SV_BLOCK - 1) / SV_BLOCK)); }
@@ -217,29 +219,7 @@ __global__ void sv_bbox_kernel(const float4 *pts, int n, uint32_t *box) {
 }
 
 // ---- normals -----------------------------------------------------------------------------------------------------------------
-// One rotation of the cyclic Jacobi iteration on the symmetric 3x3 matrix {app, aqq, apq, arp, arq} (r: the third index) and
-// the eigenvector columns p, q.  Only + - * / sqrt: tests/survey_map_ref.py performs the same operations in the same order.
-__device__ __forceinline__ void sv_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double *vp, double *vq) {
-  if (apq == 0.0) return;
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double root = sqrt(theta * theta + 1.0);
-  const double t = theta >= 0.0 ? 1.0 / (theta + root) : -1.0 / (root - theta);
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  const double h = t * apq;
-  app = app - h;
-  aqq = aqq + h;
-  apq = 0.0;
-  const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-  arp = rp;
-  arq = rq;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double a = c * vp[k] - s * vq[k], b = s * vp[k] + c * vq[k];
-    vp[k] = a;
-    vq[k] = b;
-  }
-}
-
+// (the Jacobi rotation sv_rotate: lslam_jacobi_dev.hpp, shared with lslam_mapq.hip)
 __global__ __launch_bounds__(SV_BLOCK) void sv_normals_kernel(SGrid g, const float4 *query, int nq, float r2, float4 *out, int32_t *count) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nq) return;

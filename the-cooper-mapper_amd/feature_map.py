@@ -141,6 +141,13 @@ class FeatureMap:
         self._check(self.lib.lslam_fmap_get_full_map(self.h, _fp(out), n.value, C.byref(n)))
         return out
 
+    def quality(self, which="surf", **params):
+        """Mean map entropy and mean plane variance of the whole map of one feature type, where it lies
+        (``lslam_mapq_fmap``; :mod:`.map_quality`) -> the stats as a dict.  Keywords: ``radius``, ``min_neighbors``,
+        ``lambda_floor``."""
+        from . import map_quality
+        return map_quality.fmap_quality(self, which, **params)
+
     # ---- FeatureMap.h:378-462 -------------------------------------------------------------
     def save_cloud_to_files(self, directory):
         """saveCloudToFiles: <count>.pcd (binary, x y z intensity) per non-empty cube and type + index.txt."""

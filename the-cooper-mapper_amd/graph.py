@@ -449,6 +449,29 @@ class Graph:
         ids, poses = self._voters(kf, keyframes)
         removed.append(kf.store.vis_add_to_fmap(kf.store_id, fm, est, ids, poses))
 
+    def map_quality(self, poses="estimate", which="surf", keyframes=None, **params):
+        """Mean map entropy and mean plane variance (:mod:`.map_quality`; not in the reference) of the keyframes' clouds of
+        one type put together at their poses -- ``poses="estimate"``: the optimised ``kf.estimate``; ``"odom"``: the odometry
+        poses ``kf.odom`` they started from -- so the two calls score what the optimisation did to the MAP, without ground
+        truth: lower is crisper.  A resident graph evaluates the clouds where they lie in the store
+        (``KeyframeStore.map_quality``); a host graph moves them on the host by the same fp32 formula and uploads
+        (``map_quality.evaluate``).  Keywords: ``radius``, ``min_neighbors``, ``lambda_floor`` -> the stats as a dict."""
+        from . import map_quality
+        if poses not in ("estimate", "odom"):
+            raise ValueError("Graph.map_quality: poses is \"estimate\" or \"odom\"")
+        every = self.keyframes if keyframes is None else keyframes
+        t = map_quality._which(which)
+        T = [np.asarray(kf.estimate if poses == "estimate" else kf.odom, np.float64).astype(np.float32).reshape(4, 4) for kf in every]
+        if self.store is not None and all(getattr(kf, "store", None) is self.store for kf in every):
+            return self.store.map_quality([kf.store_id for kf in every], T, t, **params)
+        clouds = []
+        for kf, M in zip(every, T):
+            c = np.asarray(kf.surf_cloud if t else kf.corner_cloud, np.float32)[:, :3]
+            x, y, z = c[:, 0:1], c[:, 1:2], c[:, 2:3]
+            clouds.append(((M[None, :3, 0] * x + M[None, :3, 1] * y) + M[None, :3, 2] * z) + M[None, :3, 3])
+        cloud = np.concatenate(clouds, axis=0) if clouds else np.zeros((0, 3), np.float32)
+        return map_quality.evaluate(self.ctx or self.loop_detector.scan_match.ctx, cloud, **params)
+
     # graph.cpp:150-199 (driven by Graph::save, :106-147)
     def get_final_feature_map(self, ctx=None, directory=None, cube_dims=(121, 111, 121), bootstrap=False, keyframes=None):
         """``Graph::getFinalFeatureMap``: rebuild the map from the optimised keyframes, one after the other -- keyframe k is

@@ -213,6 +213,13 @@ class KeyframeStore:
         from . import visibility
         return visibility.add_to_fmap(self, kid, fmap, tf, ids, poses)
 
+    def map_quality(self, ids, poses, which="surf", **params):
+        """Mean map entropy and mean plane variance of keyframes ``ids``' clouds of one type put together at ``poses`` (4x4
+        each, graph <- sensor): the score of a trajectory (``lslam_mapq_keyframes``; :mod:`.map_quality`) -> the stats as a
+        dict.  No cloud crosses PCIe.  Keywords: ``radius``, ``min_neighbors``, ``lambda_floor``."""
+        from . import map_quality
+        return map_quality.keyframes_quality(self, ids, poses, which, **params)
+
     # ---- loop candidates by appearance: scan context (lslam_sc_*) ---------------------------------------------------------
     def sc_setup(self, **params):
         """Install the scan-context parameters (``n_ring``, ``n_sector``, ``max_range``, ``height_offset``, ``up_axis``;
