@@ -221,6 +221,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed; new entry points and structs of their own (lslam_floor_*, lslam_debug_floor_hypotheses: floor detection; lslam_pg_set_plane_priors, _num_plane_priors, _plane_prior_robust, lslam_g2o_read_plane_priors: plane priors). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_vis_*, lslam_debug_vis_votes: visibility votes over the keyframe store). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_mapq_*: map quality, mean map entropy and mean plane variance; lslam_traj_*: trajectory evaluation). */
+/* still 7: no struct changed; new entry points and structs of their own (lslam_occ_*, lslam_debug_occ_integrate: the 2D occupancy grid from the keyframe store). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -936,6 +937,130 @@ int lslam_vis_add_to_fmap(lslam_kfs *kfs, int32_t id, lslam_fmap *fm, const floa
  * last lslam_vis_votes call and on its points, voters and poses, voting into a buffer of its own; not waited for (time it with
  * events on lslam_stream).  LSLAM_ERR_INVALID before such a call has run (or after lslam_kfs_clear / new parameters). */
 int lslam_debug_vis_votes(lslam_kfs *kfs, int32_t launches);
+
+/* ---- 2D occupancy grid: ray-cast votes of the keyframes ---------------------------------------------------------------------
+ * Not in the reference: nothing in it produces the map a map_server / move_base stack loads.  Every point of every keyframe is a
+ * ray from the sensor to the point; the cells the ray crosses were seen free, the cell it ends in -- if the point stands at
+ * obstacle height above the keyframe's floor plane -- was seen occupied.  One grid per store; nothing is allocated before
+ * lslam_occ_setup, and the grid itself when it is first needed; lslam_kfs_clear / lslam_kfs_destroy free it (over a clear the
+ * parameters stay, and the next call that needs the grid allocates it again, zeroed).  Every decision is an integer one:
+ * results are reproducible to the bit and do not depend on order, chunking or launch shape.  This comment is the specification
+ * (restated in numpy and Python integers by tests/occupancy_ref.py).
+ *
+ * AXES.  up_axis 1 (y up): (a, b, h) = (z, x, y); up_axis 2 (z up): (a, b, h) = (x, y, z), as lslam_vis_params.  The grid has
+ * `width` cells along a and `height` cells along b; cell (i, j) covers a in origin[0] + [i, i+1) * resolution and b likewise
+ * with j; arrays are row-major with index j * width + i.
+ *
+ * A KEYFRAME'S VOTE takes its id, its pose T (row-major 4x4 fp32, graph <- sensor; only the first three rows are read) and a
+ * plane (n, d) in the sensor frame, n.p + d = 0 on the floor and n pointing up (lslam_floor_result.plane), given as four fp64
+ * and rounded to fp32.  Without a plane (planes NULL, or plane_valid given and 0 for the entry) the fallback (u, sensor_height)
+ * is used, u the unit up axis.  The vote runs over the corner cloud followed by the surf cloud.  Per point p = (x, y, z), in
+ * fp32 with every operation rounded on its own (no FMA):
+ *   GATE    the point takes part iff x, y, z are finite and lo <= (x*x + y*y) + z*z <= hi, lo = min_range * min_range and
+ *           hi = max_range * max_range (one fp32 product each).  No square root.
+ *   HEIGHT  hgt = ((nx*x + ny*y) + nz*z) + d.  OBSTACLE iff obstacle_min <= hgt <= obstacle_max; GROUND iff
+ *           fabsf(hgt) <= ground_band and ground_clears != 0 (the parameter limits make the two exclude each other); any
+ *           other point is ignored: it is no ray.
+ *   END     E = ((T0*x + T1*y) + T2*z) + T3 per row; the ray's origin O is the pose's translation (T3, T7, T11).
+ *   FIXED POINT  s = 256.0 / (double)resolution (one fp64 division, on the host);
+ *           Q(v, r) = floor(((double)v - r) * s), in fp64, nothing contracted; A = (Q(Oa, origin[0]), Q(Ob, origin[1])),
+ *           B = (Q(Ea, origin[0]), Q(Eb, origin[1])).  The ray is DROPPED (counted in rays_dropped, no vote) unless all
+ *           four values lie in [-2^30, 2^30) -- a value that is not finite (E overflowed) does not.  Then they are integers.
+ * CELLS CROSSED.  Cell (i, j) is crossed by the ray iff the open segment A + t (B - A), 0 < t < 1, meets the open square
+ * (256 i, 256 (i+1)) x (256 j, 256 (j+1)); decided exactly in integers.  A ray of zero length (A == B) crosses its own cell
+ * iff A lies in its open interior.  A ray along a grid line crosses nothing; a ray through a lattice corner does not enter the
+ * two cells it only touches.  The END cell is (floor(Ba / 256), floor(Bb / 256)); it need not be crossed (B may lie on a wall).
+ * PER KEYFRAME k, both restricted to the grid:  HIT_k = the end cells of its obstacle rays;  FREE_k = (the crossed cells of its
+ * obstacle rays, each without that ray's own end cell, and all crossed cells of its ground rays) minus HIT_k.  So a keyframe
+ * votes at most once per cell and a hit beats a free: a wall seen at a grazing angle is not erased by the rays along it.
+ * COUNTS.  One uint32 per cell, n_free | n_hit << 16, summed over the keyframes integrated since the last clear (an id named
+ * twice votes twice).  At most 65535 keyframes may be integrated into one grid, so neither half overflows.
+ * VALUES.  One int8 per cell from its count alone, on the device: with H = hit_weight * n_hit and D = H + n_free, the value is
+ * -1 iff n_hit + n_free < min_observations, else (200 * H + D) / (2 * D) in integer division: 0 .. 100, round(100 H / D).
+ *
+ * THE KERNELS' WINDOW.  A keyframe's bits live in a window of the grid that the host derives from the pose: along axis c with
+ * pose row (r0, r1, r2 | t), every E_c lies within t +- L, L = |r| * max_range * (1 + 1e-6) + 1e-6 * ((|r0| + |r1| + |r2|) *
+ * max_range + |t|) + 1e-30 (Cauchy-Schwarz on the gated point, plus a bound on the four fp32 roundings of E); Q is monotone, so the
+ * cells of Q(t - L) .. Q(t + L), clipped to the grid, hold every cell the keyframe can touch -- whatever the pose: it need not
+ * be a rotation.  A cell outside it would make the call fail with LSLAM_ERR_HIP instead of being lost (none can).
+ *
+ * REFUSALS.  Everything is checked before anything runs -- LSLAM_ERR_INVALID, lslam_last_error names the cause, nothing has
+ * changed (the caller's outputs included) -- for: a null or destroyed store, use before lslam_occ_setup, a keyframe id out of
+ * range, a pose (first three rows) or a plane that is read and is not finite in fp32, a plane normal of zero length, null arrays
+ * with something to read or write, n_ids outside 0 .. 65535, an integration that would bring the keyframes integrated above
+ * 65535, and in lslam_occ_setup every limit of the table below (values that are not finite included).  Parameters that differ
+ * from those in force clear the grid. */
+typedef struct lslam_occ_params {
+  double origin[2];        /* 0, 0   graph-frame (a, b) of the corner of cell (0, 0); finite */
+  float resolution;        /* 0.1    metres per cell, >= 0.01 */
+  int32_t width;           /* 0      cells along a ... */
+  int32_t height;          /* 0      ... and along b: each 1 .. 8192, product <= 2^26 (the defaults are refused: set them,
+                                     or let lslam_occ_fit_bounds) */
+  int32_t up_axis;         /* 1      1: y up, 2: z up */
+  float min_range;         /* 1.0    > 0 [m] */
+  float max_range;         /* 40.0   > min_range; max_range / resolution <= 2048 (fp32 division) */
+  float obstacle_min;      /* 0.3    height above the floor [m] ... */
+  float obstacle_max;      /* 2.0    ... obstacle_min < obstacle_max */
+  float ground_band;       /* 0.15   0 <= ground_band < obstacle_min */
+  float sensor_height;     /* 1.8    d of the fallback plane; finite */
+  int32_t ground_clears;   /* 1      0 or 1: ground returns clear the cells their rays cross */
+  int32_t hit_weight;      /* 3      1 .. 16 */
+  int32_t min_observations;/* 1      >= 1 */
+  int32_t reserved;        /* 0      must be 0 */
+} lslam_occ_params;
+typedef struct lslam_occ_stats {
+  lslam_occ_params params;      /* in force (zero before lslam_occ_setup) */
+  int32_t is_set;               /* 1 once lslam_occ_setup succeeded */
+  int32_t n_integrated;         /* keyframe votes summed in the counts since the last clear */
+  int64_t rays_cast;            /* since the last clear: rays_obstacle + rays_ground */
+  int64_t rays_dropped;         /* obstacle or ground points whose ray left the fixed-point range */
+  int64_t rays_obstacle;        /* obstacle rays that voted */
+  int64_t rays_ground;          /* ground rays that voted */
+  uint64_t grid_bytes;          /* device memory of the counts and values */
+  uint64_t scratch_bytes;       /* ... and of the bit planes of a chunk of keyframes */
+  int64_t ray_launches;         /* launches, since creation and without the measurement tap's: the ray kernel, */
+  int64_t merge_launches;       /* the merge of a chunk's bit planes into the counts, */
+  int64_t value_launches;       /* the values from the counts */
+} lslam_occ_stats;
+/* Kernel shape, for tests that have to straddle it: points per workgroup of the ray kernel (whose (ray, column) items are dealt
+ * to its lanes by a prefix sum of the rays' column counts) and keyframes per launch (grid: point tiles x keyframes). */
+#define LSLAM_OCC_RAY_TILE 256
+#define LSLAM_OCC_KF_CHUNK 8
+/* Writes every byte of *p (the defaults above). */
+void lslam_occ_default_params(lslam_occ_params *p);
+size_t lslam_sizeof_occ_params(void);
+size_t lslam_sizeof_occ_stats(void);
+/* Validates and installs the parameters (NULL is refused: width and height have no default).  The same parameters again change
+ * nothing; others clear the grid. */
+int lslam_occ_setup(lslam_kfs *kfs, const lslam_occ_params *params);
+int lslam_occ_info(lslam_kfs *kfs, lslam_occ_stats *out);
+/* Zeroes the counts, n_integrated and the ray counters; the parameters stay. */
+int lslam_occ_clear(lslam_kfs *kfs);
+/* Adds the votes of keyframes ids[n_ids] at poses[n_ids * 16].  planes: n_ids * 4 fp64 or NULL (every keyframe uses the
+ * fallback); plane_valid: n_ids flags or NULL (every plane given is used); an entry whose flag is 0 uses the fallback and its
+ * plane is not read.  No cloud crosses PCIe: the store's byte counters stay.  Waited for. */
+int lslam_occ_integrate(lslam_kfs *kfs, int32_t n_ids, const int32_t *ids, const float *poses, const double *planes,
+                        const int32_t *plane_valid);
+/* Downloads: out[width * height]. */
+int lslam_occ_counts(lslam_kfs *kfs, uint32_t *out);
+int lslam_occ_values(lslam_kfs *kfs, int8_t *out);
+/* The device arrays themselves (either pointer may be NULL); the values are recomputed first if counts changed since.  Waited
+ * for; valid until the next lslam_occ_setup with other parameters, lslam_kfs_clear or lslam_kfs_destroy. */
+int lslam_occ_view(lslam_kfs *kfs, const uint32_t **d_counts, const int8_t **d_values);
+/* Host only, fp64: the smallest grid with origin on multiples of the resolution that holds every pose's position +- max_range.
+ * Reads resolution, max_range and up_axis of *params and writes origin, width and height.  With r = (double)resolution,
+ * m = (double)max_range and, per axis, lo = min O - m, hi = max O + m over the n poses (row-major 4x4 fp32):
+ *   i0 = floor(lo / r), lowered by one while i0 * r > lo, then raised by one while (i0 + 1) * r <= lo;  origin = i0 * r;
+ *   cells = max(1, ceil((hi - origin) / r)), raised by one while origin + cells * r < hi, lowered by one while cells > 1 and
+ *   origin + (cells - 1) * r >= hi  (the products and sums as written, in fp64).
+ * Refused -- *params untouched -- for n < 1, null arguments, a position that is not finite, resolution / max_range / up_axis
+ * outside lslam_occ_setup's limits, or a result that breaks a size limit (the message names the size it would need). */
+int lslam_occ_fit_bounds(int32_t n, const float *poses, lslam_occ_params *params);
+/* Measurement tap (tools/bench_occupancy.py): enqueues, `launches` times, the ray kernel launches of the store's last
+ * lslam_occ_integrate call (every chunk, each behind the memset of its bit planes), on bit planes and counters of its own: the
+ * grid and the stats do not change.  Not waited for (time it with events on lslam_stream).  LSLAM_ERR_INVALID before such a call
+ * with n_ids > 0 has run (or after a clear of the store or new parameters). */
+int lslam_debug_occ_integrate(lslam_kfs *kfs, int32_t launches);
 
 /* ---- map quality: mean map entropy and mean plane variance; trajectory evaluation ------------------------------------------
  * The reference's only accuracy tool is map_evaluation/Evaluation.cpp (lidar pose against GPS: lslam_traj_eval below).  For the

@@ -102,6 +102,35 @@ inline Mat4d pose7_to_mat(const double p[7]) {
   return T;
 }
 
+// The occupancy grid as the stem.pgm / stem.yaml pair map_server loads (byte for byte what the Python occupancy.save_map writes):
+// binary P5, row 0 the largest b, trinary as map_saver writes it -- value >= 65 -> 0, 0 <= value <= 19 -> 254, anything else,
+// unknown included -> 205.  values: width * height, row-major with index j * width + i (KeyframeStore::occValues).
+inline bool saveMap(const std::string &stem, const std::vector<int8_t> &values, const lslam_occ_params &params) {
+  const size_t w = (size_t)params.width, h = (size_t)params.height;
+  if (params.width < 1 || params.height < 1 || values.size() != w * h) return false;
+  const std::string pgm = stem + ".pgm", yaml = stem + ".yaml";
+  const size_t slash = pgm.find_last_of('/');
+  const std::string base = slash == std::string::npos ? pgm : pgm.substr(slash + 1);
+  FILE *f = std::fopen(pgm.c_str(), "wb");
+  if (!f) return false;
+  std::fprintf(f, "P5\n# CREATOR: lslam occupancy %.17g m/pix\n%zu %zu\n255\n", (double)params.resolution, w, h);
+  std::vector<unsigned char> row(w);
+  for (size_t r = 0; r < h; ++r) {
+    const int8_t *v = &values[(h - 1 - r) * w];
+    for (size_t i = 0; i < w; ++i) row[i] = v[i] >= 65 ? 0 : (v[i] >= 0 && v[i] <= 19 ? 254 : 205);
+    std::fwrite(row.data(), 1, w, f);
+  }
+  if (std::fclose(f) != 0) return false;
+  f = std::fopen(yaml.c_str(), "w");
+  if (!f) return false;
+  std::fprintf(f, "# map axes in the graph frame: %s; origin is the corner of cell (0, 0)\n",
+               params.up_axis == 1 ? "a = +z, b = +x (y up)" : "a = +x, b = +y (z up)");
+  std::fprintf(f, "image: %s\nresolution: %.17g\norigin: [%.17g, %.17g, 0.0]\n", base.c_str(), (double)params.resolution, params.origin[0],
+               params.origin[1]);
+  std::fprintf(f, "negate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n");
+  return std::fclose(f) == 0;
+}
+
 // The keyframes' clouds in device memory (lslam_kfs_*).  Not copyable; the store may outlive its ctx (every call is then
 // refused), the destructor frees it either way.
 class KeyframeStore {
@@ -241,6 +270,62 @@ public:
                        size_t removed[2]) {
     if (poses.size() != 16 * ids.size()) { _err = "vis_add_to_fmap: one 4x4 pose per id"; return false; }
     if (lslam_vis_add_to_fmap(_h, id, fm, T, (int32_t)ids.size(), ids.data(), poses.data(), removed) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // ---- 2D occupancy grid: ray-cast votes of the keyframes (lslam_occ_*) ----
+  // width and height have no default: set them, or let occFitBounds.  Other parameters than those in force clear the grid.
+  bool occSetup(const lslam_occ_params &params) {
+    if (lslam_occ_setup(_h, &params) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  bool occInfo(lslam_occ_stats &st) {
+    if (lslam_occ_info(_h, &st) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  bool occClear() {
+    if (lslam_occ_clear(_h) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // origin, width and height of `params` fitted to the poses' positions +- max_range (host only)
+  bool occFitBounds(const std::vector<float> &poses, lslam_occ_params &params) {
+    if (lslam_occ_fit_bounds((int32_t)(poses.size() / 16), poses.data(), &params) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // The votes of keyframes ids[k] at poses[16 k ..] (row-major 4x4 float, graph <- sensor).  planes: empty (every keyframe uses
+  // the fallback plane) or four doubles per id (lslam_floor_result.plane); plane_valid: empty or one flag per id, 0: the fallback.
+  bool occIntegrate(const std::vector<int32_t> &ids, const std::vector<float> &poses, const std::vector<double> &planes = std::vector<double>(),
+                    const std::vector<int32_t> &plane_valid = std::vector<int32_t>()) {
+    if (poses.size() != 16 * ids.size() || (!planes.empty() && planes.size() != 4 * ids.size()) ||
+        (!plane_valid.empty() && plane_valid.size() != ids.size())) {
+      _err = "occIntegrate: one 4x4 pose per id, and no or one plane and flag per id";
+      return false;
+    }
+    if (lslam_occ_integrate(_h, (int32_t)ids.size(), ids.data(), poses.data(), planes.empty() ? nullptr : planes.data(),
+                            plane_valid.empty() || planes.empty() ? nullptr : plane_valid.data()) == LSLAM_OK)
+      return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // n_free | n_hit << 16 per cell, row-major with index j * width + i
+  bool occCounts(std::vector<uint32_t> &out) {
+    lslam_occ_stats st;
+    if (!occInfo(st)) return false;
+    out.assign((size_t)std::max(st.params.width, 1) * (size_t)std::max(st.params.height, 1), 0u);
+    if (lslam_occ_counts(_h, out.data()) == LSLAM_OK) return true;
+    _err = lslam_last_error();
+    return false;
+  }
+  // -1 unknown, else 0 .. 100
+  bool occValues(std::vector<int8_t> &out) {
+    lslam_occ_stats st;
+    if (!occInfo(st)) return false;
+    out.assign((size_t)std::max(st.params.width, 1) * (size_t)std::max(st.params.height, 1), (int8_t)-1);
+    if (lslam_occ_values(_h, out.data()) == LSLAM_OK) return true;
     _err = lslam_last_error();
     return false;
   }
@@ -606,6 +691,7 @@ public:
         _appearance(appearance_loops) {
     lslam_floor_default_params(&floor_params);
     lslam_vis_default_params(&dynamic_params);
+    lslam_occ_default_params(&occupancy_params);
     if (resident || appearance_loops) {
       store.reset(new KeyframeStore(ctx));
       if (!store->ok()) _err = store->lastError();
@@ -821,6 +907,7 @@ public:
   // optimised poses (FeatureMap(121, 111, 121) with its default filter sizes: update + addFeatureCloud per keyframe, no match)
   // into directory/graph, traj_graph.pcd and traj_odom.pcd (ASCII; x y z intensity normal_x normal_y normal_z curvature =
   // translation, quaternion w, quaternion x y z of the float-cast rotation, index), then getFinalFeatureMap into directory/graph2.
+  // With `occupancy` on, also directory/map.pgm and map.yaml (occupancyGrid, saveMap); off: nothing new is written.
   bool save(const std::string &directory, bool bootstrap = false, int max_iterations = 1000) {
     if (keyframes.empty()) { _err = "Graph::save: no keyframes"; return false; }
     if (remove_dynamic && !store) { _err = "Graph: remove_dynamic needs a resident graph"; return false; }
@@ -848,7 +935,14 @@ public:
     }
     std::vector<char> matched;
     std::vector<Mat4d> poses;
-    return getFinalFeatureMap(_ctx, directory + "/graph2", bootstrap, matched, poses, nullptr) >= 0;
+    if (getFinalFeatureMap(_ctx, directory + "/graph2", bootstrap, matched, poses, nullptr) < 0) return false;
+    if (!occupancy) return true;
+    std::vector<int8_t> values;
+    std::vector<uint32_t> counts;
+    lslam_occ_params p;
+    if (!occupancyGrid(values, counts, p)) return false;
+    if (!saveMap(directory + "/map", values, p)) { _err = "Graph::save: cannot write map.pgm / map.yaml"; return false; }
+    return true;
   }
 
   LoopDetector loop_detector;
@@ -916,6 +1010,46 @@ public:
   // (the defaults unless changed).  removedPoints: (corner, surf) points left out per keyframe getFinalFeatureMap added.
   bool remove_dynamic = false;
   lslam_vis_params dynamic_params;
+  // The 2D occupancy grid of the keyframes' ray-cast votes (not in the reference; lslam_occ_*, semantics in lslam_c.h): with
+  // `occupancy` on a resident graph, save also writes directory/map.pgm and map.yaml (saveMap).  occupancy_params: lslam_occ_setup's;
+  // while width or height is 0 the bounds are fitted to the poses (lslam_occ_fit_bounds).  Off by default.
+  bool occupancy = false;
+  lslam_occ_params occupancy_params;
+  // Clears the store's grid and integrates every keyframe at its optimised estimate (odom: at its odometry pose).  With `floor`
+  // each keyframe's floor is detected where its cloud lies (floor_params, with the grid's up axis and sensor_height) and decides
+  // what is an obstacle; a status other than OK falls back to (up axis, sensor_height).  params_out: the parameters in force.
+  bool occupancyGrid(std::vector<int8_t> &values, std::vector<uint32_t> &counts, lslam_occ_params &params_out, bool odom = false,
+                     bool floor = true) {
+    if (!occupancy || !store) { _err = "Graph: occupancy needs the option on and a resident graph"; return false; }
+    if (keyframes.empty()) { _err = "Graph::occupancyGrid: no keyframes"; return false; }
+    std::vector<int32_t> ids;
+    std::vector<float> poses(16 * keyframes.size());
+    for (size_t k = 0; k < keyframes.size(); ++k) {
+      if (keyframes[k]->store != store->handle()) { _err = "Graph::occupancyGrid: every keyframe must be in the graph's store"; return false; }
+      to_float16(odom ? keyframes[k]->odom : keyframes[k]->estimate, &poses[16 * k]);
+      ids.push_back(keyframes[k]->store_id);
+    }
+    lslam_occ_params p = occupancy_params;
+    std::vector<double> planes;
+    std::vector<int32_t> valid;
+    bool good = (p.width > 0 && p.height > 0) || store->occFitBounds(poses, p);
+    if (good && floor) {
+      lslam_floor_params fp = floor_params;
+      fp.up[0] = 0.0f, fp.up[1] = p.up_axis == 1 ? 1.0f : 0.0f, fp.up[2] = p.up_axis == 1 ? 0.0f : 1.0f;
+      fp.sensor_height = p.sensor_height;
+      std::vector<lslam_floor_result> res;
+      good = store->floorDetect(ids, &fp, res);
+      for (size_t k = 0; good && k < res.size(); ++k) {
+        valid.push_back(res[k].status == LSLAM_FLOOR_OK ? 1 : 0);
+        for (int e = 0; e < 4; ++e) planes.push_back(valid.back() ? res[k].plane[e] : 0.0);
+      }
+    }
+    good = good && store->occSetup(p) && store->occClear() && store->occIntegrate(ids, poses, planes, valid) &&
+           store->occValues(values) && store->occCounts(counts);
+    if (!good) { _err = store->lastError(); return false; }
+    params_out = p;
+    return true;
+  }
   std::vector<std::pair<size_t, size_t>> removedPoints;
   double floor_sigma_normal = 0.0, floor_sigma_distance = 0.0;
   lslam_floor_params floor_params;

@@ -29,8 +29,9 @@ from . import survey_map
 from .survey_map import SurveyMap
 from . import floor
 from . import visibility
+from . import occupancy
 from . import map_quality
 from .map_quality import mapq_params, trajectory_eval
 
-__all__ = ["map_quality", "mapq_params", "trajectory_eval", "visibility","Comm", "Context", "ScanMatch", "PoseGraph", "FeatureMap", "voxel_grid", "voxel_grid2", "scan_registration", "MultiScanRegistration", "OrganisedScanRegistration", "KeyFrame", "Loop", "LoopDetector", "Graph", "KeyframeUpdater", "LaserOdometry", "DeviceLaserOdometry", "LaserMapping", "LaserMappingLocal", "LaserLocalization", "RelocResult", "yaw_sweep", "grid_positions", "DynamicFeatureMap", "LocalFeatureMap", "KeyframeStore", "survey_map", "SurveyMap", "floor", "LslamError", "LslamOpts", "LslamStats", "LslamMapInfo", "LslamStereoCam",
+__all__ = ["occupancy", "map_quality", "mapq_params", "trajectory_eval", "visibility","Comm", "Context", "ScanMatch", "PoseGraph", "FeatureMap", "voxel_grid", "voxel_grid2", "scan_registration", "MultiScanRegistration", "OrganisedScanRegistration", "KeyFrame", "Loop", "LoopDetector", "Graph", "KeyframeUpdater", "LaserOdometry", "DeviceLaserOdometry", "LaserMapping", "LaserMappingLocal", "LaserLocalization", "RelocResult", "yaw_sweep", "grid_positions", "DynamicFeatureMap", "LocalFeatureMap", "KeyframeStore", "survey_map", "SurveyMap", "floor", "LslamError", "LslamOpts", "LslamStats", "LslamMapInfo", "LslamStereoCam",
            "Status", "lib_path", "load_library", "build_library"]

@@ -271,6 +271,22 @@ class LslamVisStats(C.Structure):
                 ("image_launches", C.c_int64), ("vote_launches", C.c_int64)]
 
 
+class LslamOccParams(C.Structure):
+    """lslam_occ_params (include/lslam_c.h)."""
+    _fields_ = [("origin", C.c_double * 2), ("resolution", C.c_float), ("width", C.c_int32), ("height", C.c_int32),
+                ("up_axis", C.c_int32), ("min_range", C.c_float), ("max_range", C.c_float), ("obstacle_min", C.c_float),
+                ("obstacle_max", C.c_float), ("ground_band", C.c_float), ("sensor_height", C.c_float),
+                ("ground_clears", C.c_int32), ("hit_weight", C.c_int32), ("min_observations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LslamOccStats(C.Structure):
+    """lslam_occ_stats (include/lslam_c.h)."""
+    _fields_ = [("params", LslamOccParams), ("is_set", C.c_int32), ("n_integrated", C.c_int32), ("rays_cast", C.c_int64),
+                ("rays_dropped", C.c_int64), ("rays_obstacle", C.c_int64), ("rays_ground", C.c_int64), ("grid_bytes", C.c_uint64),
+                ("scratch_bytes", C.c_uint64), ("ray_launches", C.c_int64), ("merge_launches", C.c_int64),
+                ("value_launches", C.c_int64)]
+
+
 class LslamMapqParams(C.Structure):
     """lslam_mapq_params (include/lslam_c.h)."""
     _fields_ = [("radius", C.c_float), ("min_neighbors", C.c_int32), ("lambda_floor", C.c_double), ("reserved", C.c_int32 * 4)]
@@ -487,6 +503,18 @@ SYMBOLS = {
     "lslam_vis_add_to_fmap": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, c_float_p, C.c_int32, c_int32_p, c_float_p,
                                         C.POINTER(C.c_size_t)]),
     "lslam_debug_vis_votes": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lslam_occ_default_params": (None, [C.POINTER(LslamOccParams)]),
+    "lslam_sizeof_occ_params": (C.c_size_t, []),
+    "lslam_sizeof_occ_stats": (C.c_size_t, []),
+    "lslam_occ_setup": (C.c_int, [C.c_void_p, C.POINTER(LslamOccParams)]),
+    "lslam_occ_info": (C.c_int, [C.c_void_p, C.POINTER(LslamOccStats)]),
+    "lslam_occ_clear": (C.c_int, [C.c_void_p]),
+    "lslam_occ_integrate": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_float_p, C.POINTER(C.c_double), c_int32_p]),
+    "lslam_occ_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "lslam_occ_values": (C.c_int, [C.c_void_p, C.POINTER(C.c_int8)]),
+    "lslam_occ_view": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "lslam_occ_fit_bounds": (C.c_int, [C.c_int32, c_float_p, C.POINTER(LslamOccParams)]),
+    "lslam_debug_occ_integrate": (C.c_int, [C.c_void_p, C.c_int32]),
     "lslam_mapq_default_params": (None, [C.POINTER(LslamMapqParams)]),
     "lslam_sizeof_mapq_params": (C.c_size_t, []),
     "lslam_sizeof_mapq_stats": (C.c_size_t, []),

@@ -330,6 +330,7 @@ int lslam_kfs_clear(lslam_kfs *k) {
   k->n_local[0] = k->n_local[1] = 0;
   k->sc.drop();  // the descriptors go with the keyframes; the scan-context parameters stay
   k->vis.drop();  // ... and so do the range images; the visibility parameters stay
+  k->occ.drop();  // ... and the occupancy grid, which was built from these keyframes; its parameters stay
   return LSLAM_OK;
 }
 

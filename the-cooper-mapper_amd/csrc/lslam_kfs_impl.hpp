@@ -162,6 +162,58 @@ struct VisState {
   }
 };
 
+// Occupancy grid (lslam_occ_*, lslam_occ.hip): the counts and values of one grid and the scratch of an integration.  Empty -- no
+// allocation -- until lslam_occ_setup; the grid itself is allocated (zeroed) by the first call that needs it.
+struct OccJob {  // what the ray and merge kernels read per keyframe of a call
+  const float4 *p[2];
+  uint32_t n[2];
+  float T[12];       // the pose's first three rows
+  float plane[4];
+  int32_t ax, ay;    // the ray origin in fixed point (read only when a_ok)
+  int32_t a_ok;      // 0: the origin lies outside the fixed-point range, every ray of the keyframe is dropped
+  int32_t wi0, wj0;  // the window's first cell ...
+  int32_t ww, wh;    // ... and its size in cells (0 x 0: the keyframe cannot touch the grid)
+  uint32_t words;    // uint32 per bit plane: ceil(ww * wh / 32)
+  uint64_t plane_at; // the HIT plane's first word in the chunk's scratch; the FREE plane follows it
+};
+struct OccState {
+  bool set = false;
+  lslam_occ_params params{};
+  double scale = 0.0;  // 256 / resolution: fp64, host
+  int32_t n_integrated = 0;
+  bool values_stale = true;
+  DevBuf<uint32_t> d_counts;
+  DevBuf<int8_t> d_values;
+  // an integration's scratch: the jobs up, the bit planes of one chunk, the four ray counters
+  PinBuf<OccJob> h_jobs;
+  DevBuf<OccJob> d_jobs;
+  DevBuf<uint32_t> d_planes, d_planes_again;
+  DevBuf<unsigned long long> d_stats, d_stats_again;  // [1] dropped, [2] obstacle, [3] ground, [4] cells outside their window
+  PinBuf<unsigned long long> h_stats;
+  int64_t rays[4] = {0, 0, 0, 0};  // cast, dropped, obstacle, ground since the last clear
+  int64_t ray_launches = 0, merge_launches = 0, value_launches = 0;
+  int32_t last_ids = 0;  // the jobs of the last integration are in d_jobs (lslam_debug_occ_integrate)
+
+  size_t cells() const { return (size_t)params.width * (size_t)params.height; }
+  bool held() const { return d_counts.p != nullptr; }
+  size_t grid_bytes() const { return d_counts.cap * sizeof(uint32_t) + d_values.cap; }
+  size_t scratch_bytes() const { return (d_planes.cap + d_planes_again.cap) * sizeof(uint32_t); }
+  void zero_tallies() {
+    n_integrated = 0;
+    values_stale = true;
+    rays[0] = rays[1] = rays[2] = rays[3] = 0;
+  }
+  // the grid and its scratch go; parameters and launch counters stay.  The caller has waited for the stream.
+  void drop() {
+    d_counts.release();
+    d_values.release();
+    d_planes.release();
+    d_planes_again.release();
+    zero_tallies();
+    last_ids = 0;
+  }
+};
+
 }  // namespace lslam
 
 struct lslam_kfs {
@@ -182,6 +234,7 @@ struct lslam_kfs {
   lslam::ScState sc;
   lslam::FloorScratch floor;
   lslam::VisState vis;
+  lslam::OccState occ;
 };
 
 namespace lslam {

@@ -94,7 +94,8 @@ class Graph:
                  sc_params=None, loop_robust_kernel=None, loop_robust_delta=1.0, edge_information=None, range_sigma=None,
                  gps_sigma=None, gps_robust_kernel=None, gps_robust_delta=1.0, gps_min_spread=None, imu_orientation_sigma=None,
                  floor_sigma=None, floor_params=None, floor_robust_kernel=None, floor_robust_delta=1.0,
-                 floor_world_plane=(0.0, 0.0, 1.0, 0.0), odometry_information=None, remove_dynamic=False, dynamic_params=None):
+                 floor_world_plane=(0.0, 0.0, 1.0, 0.0), odometry_information=None, remove_dynamic=False, dynamic_params=None,
+                 occupancy=None):
         """``resident=True``: the keyframes' clouds live in a :class:`KeyframeStore` on the loop detector's context --
         ``add_frame`` uploads them once (``kf.store_id``), loop closure and ``get_final_feature_map`` read them there;
         ``keep_host_clouds=False`` then drops the host copies (``kf.corner_cloud`` / ``kf.surf_cloud`` fetch on demand).
@@ -150,7 +151,14 @@ class Graph:
         that stood at a junction for two keyframes and drove off (``lslam_vis_*``, :mod:`.visibility`).  ``dynamic_params``:
         ``KeyframeStore.vis_setup``'s keywords.  Voters of keyframe j: every keyframe, j included, whose optimised
         translation lies within ``2 * max_range`` of j's, at its optimised ``estimate``; the keyframe's own points are
-        queried at the pose they are added with.  Off by default."""
+        queried at the pose they are added with.  Off by default.
+        ``occupancy=True`` or a dict of ``KeyframeStore.occ_setup``'s keywords (not in the reference; needs ``resident=True``):
+        :meth:`occupancy_grid` is available and :meth:`save` also writes ``map.pgm`` / ``map.yaml``, the 2D occupancy grid a
+        ``map_server`` loads (``lslam_occ_*``, :mod:`.occupancy`).  A dict without ``width`` / ``height`` has the bounds fitted
+        to the poses.  None (the default): nothing changes."""
+        self.occupancy = None if occupancy is None or occupancy is False else ({} if occupancy is True else dict(occupancy))
+        if self.occupancy is not None and not (resident or appearance_loops):
+            raise ValueError("Graph: occupancy needs resident=True")
         self.remove_dynamic = bool(remove_dynamic)
         if self.remove_dynamic and not (resident or appearance_loops):
             raise ValueError("Graph: remove_dynamic=True needs resident=True")
@@ -449,6 +457,44 @@ class Graph:
         ids, poses = self._voters(kf, keyframes)
         removed.append(kf.store.vis_add_to_fmap(kf.store_id, fm, est, ids, poses))
 
+    def occupancy_grid(self, poses="estimate", floor=True, keyframes=None):
+        """The 2D occupancy grid of the keyframes' ray-cast votes (:mod:`.occupancy`; not in the reference), at
+        ``poses="estimate"`` (the optimised ``kf.estimate``) or ``"odom"``.  The bounds are fitted to the poses unless the
+        ``occupancy`` dict gives ``width`` and ``height``; with ``floor`` each keyframe's floor is detected where its cloud lies
+        (``KeyframeStore.floor_detect``) and decides what is an obstacle, a keyframe whose status is not OK falls back to
+        (up axis, ``sensor_height``); the detection runs with the graph's ``floor_params``, or -- without any -- with the
+        grid's up axis and ``sensor_height``.  Clears the store's grid and integrates every keyframe -> dict: ``values`` (height,
+        width) int8, ``counts`` uint32, ``params`` (:class:`LslamOccParams`), ``stats``, ``floors_found``."""
+        from . import floor as floor_mod
+        from . import occupancy as occ
+        if self.occupancy is None:
+            raise ValueError("Graph.occupancy_grid: the graph was created without occupancy")
+        if poses not in ("estimate", "odom"):
+            raise ValueError("Graph.occupancy_grid: poses is \"estimate\" or \"odom\"")
+        every = self.keyframes if keyframes is None else keyframes
+        if not every or not all(getattr(kf, "store", None) is self.store for kf in every):
+            raise ValueError("Graph.occupancy_grid: needs keyframes, every one in the graph's store")
+        T = [np.asarray(kf.estimate if poses == "estimate" else kf.odom, np.float64).astype(np.float32).reshape(4, 4) for kf in every]
+        if "width" in self.occupancy and "height" in self.occupancy:
+            p = occ.occ_params(self.occupancy)
+        else:
+            p = occ.fit_bounds(T, self.occupancy)
+        ids = [kf.store_id for kf in every]
+        planes = valid = None
+        if floor:
+            fp = self.floor_params
+            if fp is None:  # the floor's up direction and height follow the grid's
+                fp = dict(up=(0.0, 1.0, 0.0) if p.up_axis == 1 else (0.0, 0.0, 1.0), sensor_height=p.sensor_height)
+            results = self.store.floor_detect(ids, fp)
+            planes = np.array([r["plane"] for r in results], np.float64).reshape(len(ids), 4)
+            valid = np.array([r["status"] == floor_mod.FLOOR_OK for r in results], np.int32)
+            planes[valid == 0] = 0.0
+        self.store.occ_setup(p)
+        self.store.occ_clear()
+        self.store.occ_integrate(ids, T, planes, valid)
+        return dict(values=self.store.occ_values(), counts=self.store.occ_counts(), params=p, stats=self.store.occ_info(),
+                    floors_found=int(valid.sum()) if valid is not None else 0)
+
     def map_quality(self, poses="estimate", which="surf", keyframes=None, **params):
         """Mean map entropy and mean plane variance (:mod:`.map_quality`; not in the reference) of the keyframes' clouds of
         one type put together at their poses -- ``poses="estimate"``: the optimised ``kf.estimate``; ``"odom"``: the odometry
@@ -544,7 +590,9 @@ class Graph:
         their optimised poses (a ``FeatureMap(121, 111, 121)`` with its default filter sizes: ``update`` + ``addFeatureCloud``
         per keyframe, no match) saved into ``directory/graph``, the trajectory clouds ``traj_graph.pcd`` / ``traj_odom.pcd``,
         then :meth:`get_final_feature_map` into ``directory/graph2``.  Works with and without ``resident``.  -> the dict of
-        :meth:`get_final_feature_map` (its map closed), with ``iterations`` of the final optimisation."""
+        :meth:`get_final_feature_map` (its map closed), with ``iterations`` of the final optimisation.  With ``occupancy``
+        also ``directory/map.pgm`` and ``directory/map.yaml`` (:meth:`occupancy_grid`, ``occupancy.save_map``), and the grid
+        under ``occupancy`` in the result; without it nothing new is written."""
         import os
         from .feature_map import FeatureMap
         from .pose_graph import pose7_to_mat
@@ -579,6 +627,11 @@ class Graph:
         out = self.get_final_feature_map(ctx=ctx, directory=os.path.join(directory, "graph2"), bootstrap=bootstrap)
         out["map"].close()
         out["iterations"] = iterations
+        if self.occupancy is not None:
+            from . import occupancy as occ
+            grid = self.occupancy_grid()
+            occ.save_map(os.path.join(directory, "map"), grid["values"], grid["params"])
+            out["occupancy"] = grid
         return out
 
 

@@ -179,6 +179,46 @@ class KeyframeStore:
         self._check(self.lib.lslam_floor_detect_keyframes(self.h, len(ids), ids.ctypes.data_as(c_int32_p), C.byref(p), res))
         return [res[i].as_dict() for i in range(len(ids))]
 
+    # ---- 2D occupancy grid: ray-cast votes of the keyframes (lslam_occ_*, :mod:`.occupancy`) ----------------------------------
+    def occ_setup(self, params=None, **kw):
+        """Install the grid's parameters (``resolution``, ``origin``, ``width``, ``height``, ``up_axis``, ``min_range``,
+        ``max_range``, ``obstacle_min``, ``obstacle_max``, ``ground_band``, ``sensor_height``, ``ground_clears``,
+        ``hit_weight``, ``min_observations``; ``width`` and ``height`` have no default).  Other parameters than those in force
+        clear the grid."""
+        from . import occupancy
+        occupancy.setup(self, params, **kw)
+
+    def occ_fit_bounds(self, poses, params=None, **kw):
+        """-> the parameters with ``origin``, ``width`` and ``height`` fitted to ``poses`` +- ``max_range`` (host only)."""
+        from . import occupancy
+        return occupancy.fit_bounds(poses, params, **kw)
+
+    def occ_integrate(self, ids, poses, planes=None, plane_valid=None):
+        """Add the votes of keyframes ``ids`` at ``poses`` (4x4 each, graph <- sensor); ``planes``: their floor planes
+        ((n, 4), sensor frame) or None for the fallback, ``plane_valid``: 0 -> the fallback for that keyframe."""
+        from . import occupancy
+        occupancy.integrate(self, ids, poses, planes, plane_valid)
+
+    def occ_counts(self):
+        from . import occupancy
+        return occupancy.counts(self)
+
+    def occ_values(self):
+        from . import occupancy
+        return occupancy.values(self)
+
+    def occ_view(self):
+        from . import occupancy
+        return occupancy.view(self)
+
+    def occ_clear(self):
+        from . import occupancy
+        occupancy.clear(self)
+
+    def occ_info(self):
+        from . import occupancy
+        return occupancy.info(self)
+
     # ---- visibility votes: the final map without moving objects (lslam_vis_*, :mod:`.visibility`) -----------------------------
     def vis_setup(self, params=None, **kw):
         """Install the visibility parameters (``n_row``, ``n_col``, ``fov_down_deg``, ``fov_up_deg``, ``min_range``,
