@@ -1499,6 +1499,7 @@ LSLAM_DEV void colpiv_qr_solve6_wave(float (&col)[6], int lane, float (&x)[6]) {
 // pcl::transformPointCloud with an Isometry3f (transform_utils.h:601-614): p' = R p + t, every row ((T0 x + T1 y) + T2 z) + T3,
 // left to right in fp32 with every product and sum rounded on its own (no FMA, whatever the compiler's flags), intensity kept.
 // T: the rows of [R | t].  The local map's add and the keyframe store's candidate assembly share it: same code, same bits.
+struct Rigid12 { float m[12]; };  // T as a kernel argument
 __device__ __forceinline__ float4 rigid_transform_point(const float *T, const float4 p) {
   float4 q;
   q.x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p.x), __fmul_rn(T[1], p.y)), __fmul_rn(T[2], p.z)), T[3]);

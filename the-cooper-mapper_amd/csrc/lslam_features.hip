@@ -28,17 +28,6 @@
 
 namespace {
 
-#define FX_TRY(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      char _b[400];                                                                      \
-      snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      lslam::set_error(_b);                                                              \
-      return LSLAM_ERR_HIP;                                                              \
-    }                                                                                    \
-  } while (0)
-
 constexpr int FX_BLOCK = 1024;  // a ring of 1 800 points: every point of every region has a thread in the parallel phases
 constexpr int MAXR = 2560;  // points per ring held in LDS
 constexpr int SKEY = 8192;  // sort words of a ring's regions (each region padded to a power of two); later 2 x MAXR x 3 floats of pointClassify
@@ -1207,15 +1196,15 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
     }
   }
   if (n_points == 0) return LSLAM_OK;
-  FX_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = (hipStream_t)lslam_stream(ctx);
   // device scratch and the pinned staging areas are the context's, kept between calls (a sweep arrives every 100 ms); the
   // outputs are WRITTEN to pinned memory by the kernels that make them: sixteen header slots (totals, error), then a slice of
   // n_points per list
   FxCache &cache = *lslam::ctx_slot<FxCache>(ctx, lslam::CTX_SLOT_FEATURES);
   const size_t np4 = n_points * sizeof(float4);
-  FX_TRY(cache.pin.reserve(n_points));
-  FX_TRY(cache.pout.reserve(4 * n_points + 16));
+  LSLAM_TRY(cache.pin.reserve(n_points));
+  LSLAM_TRY(cache.pout.reserve(4 * n_points + 16));
   // pack {x, y, z, intensity-to-copy} (toXYZI, util/pcl_util.h:30-37: the `curvature` field)
   float4 *h = cache.pin.p;
   const char *src = static_cast<const char *>(cloud);
@@ -1232,7 +1221,7 @@ static int extract_features_impl(lslam_ctx *ctx, const void *cloud, size_t n_poi
       h[i] = make_float4(v[0], v[1], v[2], w);
     }
   }
-  FX_TRY(cache.blob.reserve(fx_work_bytes(n_points, n_scans)));
+  LSLAM_TRY(cache.blob.reserve(fx_work_bytes(n_points, n_scans)));
   FxWork w;
   fx_carve(cache.blob.p, n_points, n_scans, w);
   float4 *d_pts = w.pts;
@@ -1293,11 +1282,11 @@ int lslam_multiscan_register(lslam_ctx *ctx, const void *cloud, size_t n_points,
   *n_out = 0;
   for (int r = 0; r < n_rings; ++r) { ranges_out[2 * r] = 0; ranges_out[2 * r + 1] = 0; }
   if (n_points == 0) return LSLAM_OK;
-  FX_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = (hipStream_t)lslam_stream(ctx);
   MsCache &cache = *lslam::ctx_slot<MsCache>(ctx, lslam::CTX_SLOT_MULTISCAN);
   const size_t np4 = n_points * sizeof(float4);
-  FX_TRY(cache.pin.reserve(n_points));
+  LSLAM_TRY(cache.pin.reserve(n_points));
   float4 *h = cache.pin.p;
   const char *src = static_cast<const char *>(cloud);
   for (size_t i = 0; i < n_points; ++i) {
@@ -1311,7 +1300,7 @@ int lslam_multiscan_register(lslam_ctx *ctx, const void *cloud, size_t n_points,
   if (end_ori - start_ori > 3 * M_PI) end_ori -= 2 * M_PI;
   else if (end_ori - start_ori < M_PI) end_ori += 2 * M_PI;
   const size_t bytes = 3 * np4 + 4 * n_points * 4 + 64;
-  FX_TRY(cache.blob.reserve(bytes));
+  LSLAM_TRY(cache.blob.reserve(bytes));
   char *blob = cache.blob.p;
   float4 *d_in = (float4 *)blob, *d_tmp = d_in + n_points, *d_out = d_tmp + n_points;
   int32_t *d_ring = (int32_t *)(d_out + n_points), *d_seg = d_ring + n_points;
@@ -1366,7 +1355,6 @@ int lslam_multiscan_register(lslam_ctx *ctx, const void *cloud, size_t n_points,
 }  // extern "C"
 
 namespace {
-#define SR_TRY(expr) FX_TRY(expr)
 struct SrImu {  // an IMUState on the host; the Angles with the sin / cos they cached when they were made (Angle(float))
   int64_t stamp = 0;
   float roll = 0.f, pitch = 0.f, yaw = 0.f;
@@ -1591,7 +1579,7 @@ int lslam_sreg_process(lslam_sreg *sr, const void *cloud, size_t n_points, size_
     lslam::set_error("lslam_sreg_process: empty cloud or bad stride");
     return LSLAM_ERR_INVALID;
   }
-  SR_TRY(hipSetDevice(sr->device));
+  LSLAM_TRY(hipSetDevice(sr->device));
   hipStream_t s = sr->stream;
   sr->last_valid = false;
   const size_t n = n_points, R = (size_t)sr->n_rings, K = sr->imu.size;
@@ -1600,10 +1588,10 @@ int lslam_sreg_process(lslam_sreg *sr, const void *cloud, size_t n_points, size_
   const size_t o_res = sr_up16(sizeof(SrCtl)), o_ranges = o_res + SR_RES_WORDS * 4, o_hist = o_ranges + sr_up16(2 * R * 4),
                o_states = o_hist + sr_up16(R * 4), o_cloud = o_states + sr_up16(K * sizeof(SrState)),
                in_bytes = o_cloud + n * sizeof(float4);
-  SR_TRY(sr->h_in.reserve(in_bytes));
-  SR_TRY(sr->d_in.reserve(in_bytes));
-  SR_TRY(sr->h_res.reserve(SR_RES_WORDS + 2 * R));
-  SR_TRY(sr->done.reserve(4));
+  LSLAM_TRY(sr->h_in.reserve(in_bytes));
+  LSLAM_TRY(sr->d_in.reserve(in_bytes));
+  LSLAM_TRY(sr->h_res.reserve(SR_RES_WORDS + 2 * R));
+  LSLAM_TRY(sr->done.reserve(4));
   char *hb = sr->h_in.p;
   std::memset(hb, 0, o_cloud);
   SrCtl *hctl = reinterpret_cast<SrCtl *>(hb);
@@ -1649,7 +1637,7 @@ int lslam_sreg_process(lslam_sreg *sr, const void *cloud, size_t n_points, size_
   const size_t np4 = n * sizeof(float4);
   const size_t o_ring = sr_up16(np4), o_seg = o_ring + sr_up16(n * 4), o_ori = o_seg + sr_up16(n * 4), o_rel = o_ori + sr_up16(n * 4),
                o_bmax = o_rel + sr_up16(n * 4), o_fx = o_bmax + sr_up16(nblk * 4);
-  SR_TRY(sr->d_work.reserve(o_fx + fx_work_bytes(n, R)));
+  LSLAM_TRY(sr->d_work.reserve(o_fx + fx_work_bytes(n, R)));
   char *wb = sr->d_work.p, *db = sr->d_in.p;
   float4 *d_tmp = (float4 *)wb;
   int32_t *d_ring = (int32_t *)(wb + o_ring), *d_seg = (int32_t *)(wb + o_seg);
@@ -1658,8 +1646,8 @@ int lslam_sreg_process(lslam_sreg *sr, const void *cloud, size_t n_points, size_
   fx_carve(wb + o_fx, n, R, w);
   uint32_t *d_res = (uint32_t *)(db + o_res);
   int32_t *d_ranges_out = (int32_t *)(db + o_ranges), *d_hist = (int32_t *)(db + o_hist);
-  SR_TRY(lslam::fset_reserve(out, n));
-  SR_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, s));
+  LSLAM_TRY(lslam::fset_reserve(out, n));
+  LSLAM_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, s));
   MsArgs a{};
   a.in = (const float4 *)(db + o_cloud);
   a.n = (int)n;
@@ -1775,9 +1763,9 @@ int lslam_sreg_cloud(lslam_sreg *sr, float *out_xyzc, size_t cap, size_t *n_out,
     lslam::set_error("lslam_sreg_cloud: output buffer too small");
     return LSLAM_ERR_INVALID;
   }
-  SR_TRY(hipSetDevice(sr->device));
-  SR_TRY(hipMemcpyAsync(out_xyzc, sr->d_sorted, sr->last_m * sizeof(float4), hipMemcpyDeviceToHost, sr->stream));
-  SR_TRY(hipStreamSynchronize(sr->stream));
+  LSLAM_TRY(hipSetDevice(sr->device));
+  LSLAM_TRY(hipMemcpyAsync(out_xyzc, sr->d_sorted, sr->last_m * sizeof(float4), hipMemcpyDeviceToHost, sr->stream));
+  LSLAM_TRY(hipStreamSynchronize(sr->stream));
   return LSLAM_OK;
 }
 
@@ -2021,7 +2009,7 @@ int lslam_oreg_process(lslam_oreg *og, const void *cloud, size_t height, size_t 
     lslam::set_error("lslam_oreg_process: bad stride or ring offset");
     return LSLAM_ERR_INVALID;
   }
-  SR_TRY(hipSetDevice(og->device));
+  LSLAM_TRY(hipSetDevice(og->device));
   hipStream_t s = og->stream;
   const size_t H = height, W = width, n = H * W, K = og->imu.size;
   const size_t tiles = (n + OR_TILE - 1) / OR_TILE;
@@ -2029,11 +2017,11 @@ int lslam_oreg_process(lslam_oreg *og, const void *cloud, size_t height, size_t 
   // ---- what goes up, in one block: [result words][ranges][kept cells per row][relTime per column][cells] -----------------------
   const size_t o_ranges = OR_RES_WORDS * 4, o_hist = o_ranges + sr_up16(2 * H * 4), o_rel = o_hist + sr_up16(H * 4),
                o_cloud = o_rel + sr_up16(W * 4), in_bytes = o_cloud + n * sizeof(float4);
-  SR_TRY(og->h_in.reserve(in_bytes));
-  SR_TRY(og->d_in.reserve(in_bytes));
-  SR_TRY(og->h_res.reserve(OR_RES_WORDS + 2 * H));
-  SR_TRY(og->d_work.reserve(sr_up16(tiles * 4) + fx_work_bytes(n, H)));
-  SR_TRY(lslam::fset_reserve(out, n));
+  LSLAM_TRY(og->h_in.reserve(in_bytes));
+  LSLAM_TRY(og->d_in.reserve(in_bytes));
+  LSLAM_TRY(og->h_res.reserve(OR_RES_WORDS + 2 * H));
+  LSLAM_TRY(og->d_work.reserve(sr_up16(tiles * 4) + fx_work_bytes(n, H)));
+  LSLAM_TRY(lslam::fset_reserve(out, n));
   char *hb = og->h_in.p;
   std::memset(hb, 0, o_rel);
   if (og->rel.size() != W) {  // float relTime = scanPeriod * static_cast<double>(col) / width (:111), rounded once
@@ -2064,7 +2052,7 @@ int lslam_oreg_process(lslam_oreg *og, const void *cloud, size_t height, size_t 
   fx_carve(wb + sr_up16(tiles * 4), n, H, w);
   uint32_t *d_res = (uint32_t *)db;
   int32_t *d_ranges_out = (int32_t *)(db + o_ranges);
-  SR_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, s));
+  LSLAM_TRY(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, s));
   OrArgs a{};
   a.cells = (const float4 *)(db + o_cloud);
   a.rel = (const float *)(db + o_rel);
@@ -2144,9 +2132,9 @@ int lslam_oreg_cloud(lslam_oreg *og, float *out_xyzc, size_t cap, size_t *n_out,
     lslam::set_error("lslam_oreg_cloud: output buffer too small");
     return LSLAM_ERR_INVALID;
   }
-  SR_TRY(hipSetDevice(og->device));
-  SR_TRY(hipMemcpyAsync(out_xyzc, og->d_sorted, og->last_m * sizeof(float4), hipMemcpyDeviceToHost, og->stream));
-  SR_TRY(hipStreamSynchronize(og->stream));
+  LSLAM_TRY(hipSetDevice(og->device));
+  LSLAM_TRY(hipMemcpyAsync(out_xyzc, og->d_sorted, og->last_m * sizeof(float4), hipMemcpyDeviceToHost, og->stream));
+  LSLAM_TRY(hipStreamSynchronize(og->stream));
   return LSLAM_OK;
 }
 

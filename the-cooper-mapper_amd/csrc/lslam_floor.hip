@@ -374,8 +374,6 @@ __global__ __launch_bounds__(FLOOR_BLOCK) void floor_reduce_kernel(const FloorJo
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-#define FLOOR_TRY(expr) KFS_TRY(expr)
-
 void refuse(const char *what, const char *why) {
   char b[240];
   snprintf(b, sizeof(b), "%s: %s", what, why);
@@ -467,7 +465,7 @@ int detect_batch(const char *what, hipStream_t s, FloorScratch &F, const std::ve
   if (nj == 0) return LSLAM_OK;
   const int H = P.H;
   size_t total = 0, tiles_total = 0, n_max = 0;
-  FLOOR_TRY(F.h_jobs.reserve(nj));
+  LSLAM_TRY(F.h_jobs.reserve(nj));
   for (int j = 0; j < nj; ++j) {
     if (clouds[j].n >= ((size_t)1 << 31) || total + clouds[j].n >= ((size_t)1 << 31)) return refuse(what, "the clouds hold 2^31 points or more"), LSLAM_ERR_INVALID;
     FloorJob &J = F.h_jobs.p[j];
@@ -480,23 +478,23 @@ int detect_batch(const char *what, hipStream_t s, FloorScratch &F, const std::ve
     if (clouds[j].n > n_max) n_max = clouds[j].n;
   }
   const unsigned tiles_max = (unsigned)((n_max + FLOOR_TILE - 1) / FLOOR_TILE);
-  FLOOR_TRY(F.d_jobs.reserve(nj));
-  FLOOR_TRY(F.d_tile_cnt.reserve(tiles_total));
-  FLOOR_TRY(F.d_tile_off.reserve(tiles_total));
-  FLOOR_TRY(F.d_cand_idx.reserve(total));
-  FLOOR_TRY(F.d_cand_pts.reserve(total));
-  FLOOR_TRY(F.d_triples.reserve((size_t)nj * H * 3));
-  FLOOR_TRY(F.d_planes.reserve((size_t)nj * H));
-  FLOOR_TRY(F.d_hstat.reserve((size_t)nj * H));
-  FLOOR_TRY(F.d_counts.reserve((size_t)nj * H));
-  FLOOR_TRY(F.d_partials.reserve(tiles_total * FLOOR_NSUM));
-  FLOOR_TRY(F.d_out.reserve(nj));
-  FLOOR_TRY(F.h_out.reserve(nj));
-  FLOOR_TRY(F.d_cur.reserve(nj));
-  FLOOR_TRY(F.h_cur.reserve(nj));
-  FLOOR_TRY(hipMemcpyAsync(F.d_jobs.p, F.h_jobs.p, nj * sizeof(FloorJob), hipMemcpyHostToDevice, s));
-  FLOOR_TRY(hipMemsetAsync(F.d_counts.p, 0, (size_t)nj * H * sizeof(int32_t), s));
-  FLOOR_TRY(hipMemsetAsync(F.d_out.p, 0, nj * sizeof(FloorOut), s));
+  LSLAM_TRY(F.d_jobs.reserve(nj));
+  LSLAM_TRY(F.d_tile_cnt.reserve(tiles_total));
+  LSLAM_TRY(F.d_tile_off.reserve(tiles_total));
+  LSLAM_TRY(F.d_cand_idx.reserve(total));
+  LSLAM_TRY(F.d_cand_pts.reserve(total));
+  LSLAM_TRY(F.d_triples.reserve((size_t)nj * H * 3));
+  LSLAM_TRY(F.d_planes.reserve((size_t)nj * H));
+  LSLAM_TRY(F.d_hstat.reserve((size_t)nj * H));
+  LSLAM_TRY(F.d_counts.reserve((size_t)nj * H));
+  LSLAM_TRY(F.d_partials.reserve(tiles_total * FLOOR_NSUM));
+  LSLAM_TRY(F.d_out.reserve(nj));
+  LSLAM_TRY(F.h_out.reserve(nj));
+  LSLAM_TRY(F.d_cur.reserve(nj));
+  LSLAM_TRY(F.h_cur.reserve(nj));
+  LSLAM_TRY(hipMemcpyAsync(F.d_jobs.p, F.h_jobs.p, nj * sizeof(FloorJob), hipMemcpyHostToDevice, s));
+  LSLAM_TRY(hipMemsetAsync(F.d_counts.p, 0, (size_t)nj * H * sizeof(int32_t), s));
+  LSLAM_TRY(hipMemsetAsync(F.d_out.p, 0, nj * sizeof(FloorOut), s));
   if (tiles_max) {
     hipLaunchKernelGGL(floor_mark_kernel, dim3(tiles_max, nj), dim3(FLOOR_BLOCK), 0, s, F.d_jobs.p, P, F.d_tile_cnt.p);
     hipLaunchKernelGGL(floor_scan_kernel, dim3(nj), dim3(FLOOR_BLOCK), 0, s, F.d_jobs.p, F.d_tile_cnt.p, F.d_tile_off.p, F.d_out.p);
@@ -509,7 +507,7 @@ int detect_batch(const char *what, hipStream_t s, FloorScratch &F, const std::ve
     hipLaunchKernelGGL(floor_score_kernel, dim3(tiles_max, (H + FLOOR_HCHUNK - 1) / FLOOR_HCHUNK, nj), dim3(FLOOR_BLOCK), 0, s, F.d_jobs.p,
                        F.d_out.p, F.d_cand_pts.p, F.d_planes.p, F.d_hstat.p, F.d_counts.p, H, P.thr);
   hipLaunchKernelGGL(floor_best_kernel, dim3(nj), dim3(FLOOR_BLOCK), 0, s, F.d_planes.p, F.d_hstat.p, F.d_counts.p, H, F.d_out.p, F.d_cur.p);
-  FLOOR_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
 
   // the passes over the inliers: refit_iterations fits, then the final plane's statistics
   const int need = prm.min_inliers > 3 ? prm.min_inliers : 3;
@@ -517,10 +515,10 @@ int detect_batch(const char *what, hipStream_t s, FloorScratch &F, const std::ve
   for (int pass = 0; pass <= prm.refit_iterations; ++pass) {
     if (tiles_max) hipLaunchKernelGGL(floor_sums_kernel, dim3(tiles_max, nj), dim3(FLOOR_BLOCK), 0, s, F.d_jobs.p, F.d_out.p, F.d_cand_pts.p, F.d_cur.p, P.thr, F.d_partials.p);
     hipLaunchKernelGGL(floor_reduce_kernel, dim3(nj), dim3(FLOOR_BLOCK), 0, s, F.d_jobs.p, F.d_partials.p, F.d_out.p);
-    FLOOR_TRY(hipGetLastError());
-    FLOOR_TRY(hipMemcpyAsync(F.h_out.p, F.d_out.p, nj * sizeof(FloorOut), hipMemcpyDeviceToHost, s));
-    if (pass == 0) FLOOR_TRY(hipMemcpyAsync(F.h_cur.p, F.d_cur.p, nj * sizeof(FloorPlane), hipMemcpyDeviceToHost, s));
-    FLOOR_TRY(hipStreamSynchronize(s));
+    LSLAM_TRY(hipGetLastError());
+    LSLAM_TRY(hipMemcpyAsync(F.h_out.p, F.d_out.p, nj * sizeof(FloorOut), hipMemcpyDeviceToHost, s));
+    if (pass == 0) LSLAM_TRY(hipMemcpyAsync(F.h_cur.p, F.d_cur.p, nj * sizeof(FloorPlane), hipMemcpyDeviceToHost, s));
+    LSLAM_TRY(hipStreamSynchronize(s));
     bool any_live = false;
     for (int j = 0; j < nj; ++j) {
       lslam_floor_result &R = results[j];
@@ -575,7 +573,7 @@ int detect_batch(const char *what, hipStream_t s, FloorScratch &F, const std::ve
     }
     if (!any_live) break;
     // the new planes up (small records, not points); a cloud that has ended keeps its last plane and is not read again
-    FLOOR_TRY(hipMemcpyAsync(F.d_cur.p, F.h_cur.p, nj * sizeof(FloorPlane), hipMemcpyHostToDevice, s));
+    LSLAM_TRY(hipMemcpyAsync(F.d_cur.p, F.h_cur.p, nj * sizeof(FloorPlane), hipMemcpyHostToDevice, s));
   }
   F.tap_valid = true;
   F.tap_K = results[0].n_candidates;
@@ -595,7 +593,7 @@ void clear_results(lslam_floor_result *r, size_t n) {
 
 int check_ctx(lslam_ctx *ctx, const char *what) {
   if (!ctx || !lslam::ctx_alive(ctx)) return refuse(what, "null ctx"), LSLAM_ERR_INVALID;
-  FLOOR_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   return LSLAM_OK;
 }
 
@@ -653,15 +651,15 @@ int lslam_floor_detect(lslam_ctx *ctx, const void *points, size_t n, size_t stri
   clear_results(result, 1);
   FloorScratch &F = *lslam::ctx_slot<FloorScratch>(ctx, lslam::CTX_SLOT_FLOOR);
   hipStream_t s = lslam::ctx_stream(ctx);
-  FLOOR_TRY(F.h_cloud.reserve(n));
-  FLOOR_TRY(F.d_cloud.reserve(n));
+  LSLAM_TRY(F.h_cloud.reserve(n));
+  LSLAM_TRY(F.d_cloud.reserve(n));
   const char *p = static_cast<const char *>(points);
   for (size_t i = 0; i < n; ++i) {  // {x, y, z}; the intensity is not read
     float v[3];
     std::memcpy(v, p + i * stride_bytes, 12);
     F.h_cloud.p[i] = make_float4(v[0], v[1], v[2], 0.0f);
   }
-  if (n) FLOOR_TRY(hipMemcpyAsync(F.d_cloud.p, F.h_cloud.p, n * sizeof(float4), hipMemcpyHostToDevice, s));
+  if (n) LSLAM_TRY(hipMemcpyAsync(F.d_cloud.p, F.h_cloud.p, n * sizeof(float4), hipMemcpyHostToDevice, s));
   const std::vector<Cloud> clouds(1, Cloud{F.d_cloud.p, n});
   rc = detect_batch(what, s, F, clouds, prm, P, result);
   if (rc) (void)hipStreamSynchronize(s);
@@ -700,12 +698,12 @@ int lslam_debug_floor_score(lslam_kfs *k, int32_t launches) {
   if (launches < 0 || F.last_clouds == 0 || F.last_tiles == 0)
     return refuse(what, "a negative count, or no lslam_floor_detect_keyframes call with points has run on this store"), LSLAM_ERR_INVALID;
   const size_t n = (size_t)F.last_clouds * F.last_H;
-  FLOOR_TRY(F.d_counts_again.reserve(n));
-  FLOOR_TRY(hipMemsetAsync(F.d_counts_again.p, 0, n * sizeof(int32_t), k->stream));
+  LSLAM_TRY(F.d_counts_again.reserve(n));
+  LSLAM_TRY(hipMemsetAsync(F.d_counts_again.p, 0, n * sizeof(int32_t), k->stream));
   for (int32_t i = 0; i < launches; ++i)
     hipLaunchKernelGGL(floor_score_kernel, dim3(F.last_tiles, (F.last_H + FLOOR_HCHUNK - 1) / FLOOR_HCHUNK, F.last_clouds), dim3(FLOOR_BLOCK), 0,
                        k->stream, F.d_jobs.p, F.d_out.p, F.d_cand_pts.p, F.d_planes.p, F.d_hstat.p, F.d_counts_again.p, F.last_H, F.last_thr);
-  FLOOR_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   return LSLAM_OK;
 }
 
@@ -725,11 +723,11 @@ int lslam_debug_floor_hypotheses(lslam_ctx *ctx, int32_t *cand_idx, size_t cap_c
     return refuse(what, "output buffer too small"), LSLAM_ERR_INVALID;
   hipStream_t s = lslam::ctx_stream(ctx);
   // (the first cloud of the scratch: its candidate slice and its hypotheses start at 0)
-  if (cand_idx && K) FLOOR_TRY(hipMemcpyAsync(cand_idx, F.d_cand_idx.p, K * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  if (triples) FLOOR_TRY(hipMemcpyAsync(triples, F.d_triples.p, H * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  if (planes) FLOOR_TRY(hipMemcpyAsync(planes, F.d_planes.p, H * sizeof(float4), hipMemcpyDeviceToHost, s));
-  if (counts) FLOOR_TRY(hipMemcpyAsync(counts, F.d_counts.p, H * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  FLOOR_TRY(hipStreamSynchronize(s));
+  if (cand_idx && K) LSLAM_TRY(hipMemcpyAsync(cand_idx, F.d_cand_idx.p, K * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (triples) LSLAM_TRY(hipMemcpyAsync(triples, F.d_triples.p, H * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (planes) LSLAM_TRY(hipMemcpyAsync(planes, F.d_planes.p, H * sizeof(float4), hipMemcpyDeviceToHost, s));
+  if (counts) LSLAM_TRY(hipMemcpyAsync(counts, F.d_counts.p, H * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  LSLAM_TRY(hipStreamSynchronize(s));
   return LSLAM_OK;
 }
 

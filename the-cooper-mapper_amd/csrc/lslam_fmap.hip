@@ -38,19 +38,9 @@
 #include <vector>
 
 #include "lslam_internal.hpp"
+#include "lslam_pointgrid_dev.hpp"
 
 namespace {
-
-#define FM_TRY(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      char _b[400];                                                                      \
-      snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      lslam::set_error(_b);                                                              \
-      return LSLAM_ERR_HIP;                                                              \
-    }                                                                                    \
-  } while (0)
 
 using lslam::DevBuf;
 using lslam::PinBuf;
@@ -79,8 +69,7 @@ __device__ __forceinline__ int32_t cube_of_point(const KeyParams &k, float x, fl
 }
 
 // new points: p' = R p + t (pcl::transformPointCloud), cube of p'
-struct Rigid12 { float m[12]; };  // rows of [R | t], a kernel argument (was a 64-byte upload per call)
-__global__ void fm_transform_kernel(const float4 *in, int n, const Rigid12 Tm, KeyParams k, float4 *out,
+__global__ void fm_transform_kernel(const float4 *in, int n, const lslam::Rigid12 Tm, KeyParams k, float4 *out,
                                     int32_t *cube_out, uint8_t *touched) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -488,10 +477,6 @@ __global__ __launch_bounds__(256) void fm_surround_plan_kernel(const int32_t *va
   if (tid < 7) res[1 + tid] = 0u;  // the box: maxima of ~ordered(x) (the minimum) and of ordered(x)
 }
 
-__device__ __forceinline__ uint32_t fm_ordered_u32(float f) {  // monotone map float -> uint32 (lslam_grid.hip's)
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 // res[0] = points to gather; res[1..3] / res[4..6]: the box (see above)
 __global__ __launch_bounds__(256) void fm_gather_box_kernel(const float4 *pts, const int32_t *src_begin, const int32_t *dst_begin, int n_seg,
                                                             uint32_t *res, int index_in_w, float4 *out) {
@@ -507,30 +492,10 @@ __global__ __launch_bounds__(256) void fm_gather_box_kernel(const float4 *pts, c
     float4 p = pts[src_begin[lo] + (i - dst_begin[lo])];
     if (index_in_w == 1) p.w = __builtin_bit_cast(float, (uint32_t)i);
     out[i] = p;
-    const uint32_t o[3] = {fm_ordered_u32(p.x), fm_ordered_u32(p.y), fm_ordered_u32(p.z)};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      mm[a] = max(mm[a], ~o[a]);
-      mm[3 + a] = max(mm[3 + a], o[a]);
-    }
+    lslam::box_add(mm, p);
     any = true;
   }
-  if (!__syncthreads_or(any)) return;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-    for (int a = 0; a < 6; ++a) mm[a] = max(mm[a], (uint32_t)__shfl_xor((int)mm[a], d, 64));
-  __shared__ uint32_t part[4][6];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 6; ++a) part[wave][a] = mm[a];
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {  // six atomics per workgroup (same-address atomics from a whole grid serialise at the memory side)
-    const int a = threadIdx.x;
-    atomicMax(&res[1 + a], max(max(part[0][a], part[1][a]), max(part[2][a], part[3][a])));
-  }
+  lslam::box_reduce(mm, any, res + 1);
 }
 
 int bits_for(double cells) {
@@ -676,13 +641,13 @@ int run_pipeline(hipStream_t s, Scratch &sc, const float4 *in_pts, const int32_t
   const int n = (int)n_total;
   const int n_cube_bits = kp.single ? 1 : cube_bits(ncube + 1);
   const dim3 blk(256), grd((n + 255) / 256);
-  FM_TRY(sc.err.reserve(4));
+  LSLAM_TRY(sc.err.reserve(4));
   const uint8_t *eff = nullptr;
   if (!kp.single && flags) {
-    FM_TRY(sc.cmin.reserve(3 * (size_t)ncube));
-    FM_TRY(sc.cmax.reserve(3 * (size_t)ncube));
-    FM_TRY(sc.base.reserve(3 * (size_t)ncube));
-    FM_TRY(sc.eff.reserve(ncube));
+    LSLAM_TRY(sc.cmin.reserve(3 * (size_t)ncube));
+    LSLAM_TRY(sc.cmax.reserve(3 * (size_t)ncube));
+    LSLAM_TRY(sc.base.reserve(3 * (size_t)ncube));
+    LSLAM_TRY(sc.eff.reserve(ncube));
     // a map cube's extent is known without reading the points (fm_base_kernel) whenever the caller passes its bound and
     // pcl's "leaf too small" guard cannot fire for an extent of cube_size
     const double cells = (double)kp.cube_size * (double)kp.inv_leaf;
@@ -707,25 +672,25 @@ int run_pipeline(hipStream_t s, Scratch &sc, const float4 *in_pts, const int32_t
       kp.axis_bits = assume_axis_bits;
     } else {
       int32_t max_div = 0;
-      FM_TRY(hipMemcpyAsync(&max_div, sc.err.p + 3, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      FM_TRY(hipStreamSynchronize(s));
+      LSLAM_TRY(hipMemcpyAsync(&max_div, sc.err.p + 3, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      LSLAM_TRY(hipStreamSynchronize(s));
       kp.axis_bits = bits_for((double)max_div + 1.0);
     }
     eff = sc.eff.p;
     }
   } else {
-    FM_TRY(hipMemsetAsync(sc.err.p, 0, 4 * sizeof(int32_t), s));
+    LSLAM_TRY(hipMemsetAsync(sc.err.p, 0, 4 * sizeof(int32_t), s));
     if (!kp.single) kp.axis_bits = 1;
   }
   if (3 * kp.axis_bits + n_cube_bits > 63) {
     lslam::set_error("voxel grid too fine for the 63-bit sort key (leaf too small for this extent)");
     return LSLAM_ERR_INVALID;
   }
-  FM_TRY(sc.k0.reserve(n_total));
-  FM_TRY(sc.k1.reserve(n_total));
-  FM_TRY(sc.i0.reserve(n_total));
-  FM_TRY(sc.i1.reserve(n_total));
-  FM_TRY(sc.pos.reserve(n_total + 1));
+  LSLAM_TRY(sc.k0.reserve(n_total));
+  LSLAM_TRY(sc.k1.reserve(n_total));
+  LSLAM_TRY(sc.i0.reserve(n_total));
+  LSLAM_TRY(sc.i1.reserve(n_total));
+  LSLAM_TRY(sc.pos.reserve(n_total + 1));
   const bool merge = n_sorted > 0 && n_sorted < n_total;
   hipLaunchKernelGGL(fm_key_kernel, grd, blk, 0, s, in_pts, in_cube, n, kp, eff, sc.base.p, sc.k0.p, sc.i0.p, sc.err.p + 1,
                      merge ? sc.k1.p : (uint64_t *)nullptr, merge ? sc.i1.p : (uint32_t *)nullptr);
@@ -735,25 +700,25 @@ int run_pipeline(hipStream_t s, Scratch &sc, const float4 *in_pts, const int32_t
   // here: 60 us against 125 for 157 k keys, 136 against 141 for 587 k); LSLAM_SMALL_SORT=1: lslam_sort.hip for a frame's sorts
   auto sort_pairs = [&](const uint64_t *ki, uint64_t *ko, const uint32_t *vi, uint32_t *vo, size_t cnt, size_t lib_tmp) -> int {
     if (cnt <= lslam::SMALL_SORT_MAX && lslam::env_once().small_sort) {
-      FM_TRY(lslam::small_sort_pairs(s, ki, ko, vi, vo, cnt, (void *)sc.tmp.p));
+      LSLAM_TRY(lslam::small_sort_pairs(s, ki, ko, vi, vo, cnt, (void *)sc.tmp.p));
     } else {
-      FM_TRY(rocprim::radix_sort_pairs((void *)sc.tmp.p, lib_tmp, ki, ko, vi, vo, cnt, 0u, end_bit, s));
+      LSLAM_TRY(rocprim::radix_sort_pairs((void *)sc.tmp.p, lib_tmp, ki, ko, vi, vo, cnt, 0u, end_bit, s));
     }
     return LSLAM_OK;
   };
   size_t tmp_bytes = 0;
-  FM_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, sc.k0.p, sc.k1.p, sc.i0.p, sc.i1.p, n_total, 0u, end_bit, s));
+  LSLAM_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, sc.k0.p, sc.k1.p, sc.i0.p, sc.i1.p, n_total, 0u, end_bit, s));
   size_t tmp2 = 0;
   const HeadOf head_of{sc.k1.p, n, kp.axis_bits, kp.single, eff};
   auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u), head_of);
-  FM_TRY(rocprim::exclusive_scan(nullptr, tmp2, heads, sc.pos.p, 0u, n_total + 1, rocprim::plus<uint32_t>(), s));
+  LSLAM_TRY(rocprim::exclusive_scan(nullptr, tmp2, heads, sc.pos.p, 0u, n_total + 1, rocprim::plus<uint32_t>(), s));
   if (merge) {
     const size_t n_new = n_total - n_sorted;
     size_t tmp3 = 0;
-    FM_TRY(sc.kn.reserve(n_new));
-    FM_TRY(sc.in_.reserve(n_new));
-    FM_TRY(rocprim::radix_sort_pairs(nullptr, tmp3, sc.k0.p + n_sorted, sc.kn.p, sc.i0.p + n_sorted, sc.in_.p, n_new, 0u, end_bit, s));
-    FM_TRY(sc.tmp.reserve(std::max(std::max(std::max(tmp_bytes, tmp2), tmp3), lslam::small_sort_tmp_bytes(n_new))));
+    LSLAM_TRY(sc.kn.reserve(n_new));
+    LSLAM_TRY(sc.in_.reserve(n_new));
+    LSLAM_TRY(rocprim::radix_sort_pairs(nullptr, tmp3, sc.k0.p + n_sorted, sc.kn.p, sc.i0.p + n_sorted, sc.in_.p, n_new, 0u, end_bit, s));
+    LSLAM_TRY(sc.tmp.reserve(std::max(std::max(std::max(tmp_bytes, tmp2), tmp3), lslam::small_sort_tmp_bytes(n_new))));
     {
       const int rc_sort = sort_pairs(sc.k0.p + n_sorted, sc.kn.p, sc.i0.p + n_sorted, sc.in_.p, n_new, tmp3);
       if (rc_sort) return rc_sort;
@@ -764,20 +729,20 @@ int run_pipeline(hipStream_t s, Scratch &sc, const float4 *in_pts, const int32_t
     hipLaunchKernelGGL(fm_merge_kernel, grd, blk, 0, s, (const uint64_t *)sc.k0.p, (int)n_sorted, (const uint64_t *)sc.kn.p,
                        (const uint32_t *)sc.in_.p, (int)n_new, sc.k1.p, sc.i1.p, sc.err.p + 2);
   } else {
-    FM_TRY(sc.tmp.reserve(std::max(std::max(tmp_bytes, tmp2), lslam::small_sort_tmp_bytes(n_total))));
+    LSLAM_TRY(sc.tmp.reserve(std::max(std::max(tmp_bytes, tmp2), lslam::small_sort_tmp_bytes(n_total))));
     const int rc_sort = sort_pairs(sc.k0.p, sc.k1.p, sc.i0.p, sc.i1.p, n_total, tmp_bytes);
     if (rc_sort) return rc_sort;
   }
-  FM_TRY(rocprim::exclusive_scan((void *)sc.tmp.p, tmp2, heads, sc.pos.p, 0u, n_total + 1, rocprim::plus<uint32_t>(), s));
+  LSLAM_TRY(rocprim::exclusive_scan((void *)sc.tmp.p, tmp2, heads, sc.pos.p, 0u, n_total + 1, rocprim::plus<uint32_t>(), s));
   hipLaunchKernelGGL(fm_centroid_kernel, grd, blk, 0, s, in_pts, sc.k1.p, sc.i1.p, head_of, sc.pos.p, n,
                      kp.axis_bits, out_pts, out_cube, sc.err.p);
   if (done) {  // {points out, key-range error, prefix not sorted}: three adjacent words, one copy
-    FM_TRY(hipMemcpyAsync(done, sc.err.p, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    LSLAM_TRY(hipMemcpyAsync(done, sc.err.p, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     return LSLAM_OK;
   }
   int32_t res[3] = {0, 0, 0};
-  FM_TRY(hipMemcpyAsync(res, sc.err.p, sizeof(res), hipMemcpyDeviceToHost, s));
-  FM_TRY(hipStreamSynchronize(s));
+  LSLAM_TRY(hipMemcpyAsync(res, sc.err.p, sizeof(res), hipMemcpyDeviceToHost, s));
+  LSLAM_TRY(hipStreamSynchronize(s));
   const uint32_t total = (uint32_t)res[0];
   const int32_t err = res[1], unsorted = res[2];
   if (unsorted)  // the prefix was not in key order: everything is sorted
@@ -803,8 +768,8 @@ int refresh_segments_device(lslam_fmap *fm, int t) {
   // [begin | end] in ONE buffer of 2 x seg_pad words (seg_pad = ncube rounded up to 4 words: the fill is one aligned launch
   // instead of an aligned part and a tail per array)
   const size_t pad = seg_pad(fm);
-  FM_TRY(fm->seg_begin[t].reserve(2 * pad));
-  FM_TRY(hipMemsetAsync(fm->seg_begin[t].p, 0, sizeof(int32_t) * 2 * pad, s));
+  LSLAM_TRY(fm->seg_begin[t].reserve(2 * pad));
+  LSLAM_TRY(hipMemsetAsync(fm->seg_begin[t].p, 0, sizeof(int32_t) * 2 * pad, s));
   if (fm->n[t])
     hipLaunchKernelGGL(fm_segment_kernel, dim3(((int)fm->n[t] + 255) / 256), dim3(256), 0, s, fm->cube[t].p,
                        (int)fm->n[t], fm->seg_begin[t].p, fm->seg_begin[t].p + pad);
@@ -818,8 +783,8 @@ int refresh_segments(lslam_fmap *fm, int t, bool wait = true) {
   hipStream_t s = fm->stream;
   const size_t pad = seg_pad(fm);
   fm->h_begin[t].resize(2 * pad);
-  FM_TRY(hipMemcpyAsync(fm->h_begin[t].data(), fm->seg_begin[t].p, sizeof(int32_t) * 2 * pad, hipMemcpyDeviceToHost, s));
-  if (wait) FM_TRY(hipStreamSynchronize(s));
+  LSLAM_TRY(hipMemcpyAsync(fm->h_begin[t].data(), fm->seg_begin[t].p, sizeof(int32_t) * 2 * pad, hipMemcpyDeviceToHost, s));
+  if (wait) LSLAM_TRY(hipStreamSynchronize(s));
   fm->seg_current[t] = true;
   return LSLAM_OK;
 }
@@ -840,16 +805,16 @@ int rebuild_begin(lslam_fmap *fm, int t, size_t n_new, bool allow_filter, const 
   const size_t n_old = fm->n[t], n_total = n_old + n_new;
   if (done) done[0] = done[1] = done[2] = 0;
   if (n_total == 0) return LSLAM_OK;
-  FM_TRY(fm->pts[t].grow(n_total, n_old, s));
-  FM_TRY(fm->cube[t].grow(n_total, n_old, s));
+  LSLAM_TRY(fm->pts[t].grow(n_total, n_old, s));
+  LSLAM_TRY(fm->cube[t].grow(n_total, n_old, s));
   if (n_new) {  // (addFeatureCloud's transform writes the new points where they go: nothing to copy then)
     const float4 *src_p = in_tf ? in_tf : fm->in_tf.p;
     const int32_t *src_c = in_cube ? in_cube : fm->in_cube.p;
-    if (src_p != fm->pts[t].p + n_old) FM_TRY(hipMemcpyAsync(fm->pts[t].p + n_old, src_p, n_new * sizeof(float4), hipMemcpyDeviceToDevice, s));
-    if (src_c != fm->cube[t].p + n_old) FM_TRY(hipMemcpyAsync(fm->cube[t].p + n_old, src_c, n_new * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (src_p != fm->pts[t].p + n_old) LSLAM_TRY(hipMemcpyAsync(fm->pts[t].p + n_old, src_p, n_new * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    if (src_c != fm->cube[t].p + n_old) LSLAM_TRY(hipMemcpyAsync(fm->cube[t].p + n_old, src_c, n_new * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   }
-  FM_TRY(fm->pts_alt[t].reserve(n_total));
-  FM_TRY(fm->cube_alt[t].reserve(n_total));
+  LSLAM_TRY(fm->pts_alt[t].reserve(n_total));
+  LSLAM_TRY(fm->cube_alt[t].reserve(n_total));
   KeyParams kp = key_params(fm, fm->leaf[t]);
   size_t n_out = 0;
   int rc = run_pipeline(s, sc, fm->pts[t].p, fm->cube[t].p, n_total, kp, fm->ncube,
@@ -911,11 +876,11 @@ int upload_active(lslam_fmap *fm) {
   if (fm->valid_on_device && fm->valid == fm->valid_uploaded) return LSLAM_OK;
   std::vector<uint8_t> h(fm->ncube, 0);
   for (int32_t c : fm->valid) h[c] = 1;
-  FM_TRY(hipMemcpyAsync(fm->active.p, h.data(), fm->ncube, hipMemcpyHostToDevice, fm->stream));
-  FM_TRY(fm->d_valid.reserve(fm->valid.size() + 1));
+  LSLAM_TRY(hipMemcpyAsync(fm->active.p, h.data(), fm->ncube, hipMemcpyHostToDevice, fm->stream));
+  LSLAM_TRY(fm->d_valid.reserve(fm->valid.size() + 1));
   if (!fm->valid.empty())
-    FM_TRY(hipMemcpyAsync(fm->d_valid.p, fm->valid.data(), fm->valid.size() * sizeof(int32_t), hipMemcpyHostToDevice, fm->stream));
-  FM_TRY(hipStreamSynchronize(fm->stream));  // h is a local
+    LSLAM_TRY(hipMemcpyAsync(fm->d_valid.p, fm->valid.data(), fm->valid.size() * sizeof(int32_t), hipMemcpyHostToDevice, fm->stream));
+  LSLAM_TRY(hipStreamSynchronize(fm->stream));  // h is a local
   fm->valid_uploaded = fm->valid;
   fm->valid_on_device = true;
   return LSLAM_OK;
@@ -926,8 +891,8 @@ int upload_active(lslam_fmap *fm) {
 int pack_input(hipStream_t s, PinBuf<float4> &pin, DevBuf<float4> &dst, const void *src, size_t n, size_t stride_bytes,
                float *mn = nullptr, float *mx = nullptr) {
   // {x,y,z} at offset 0; intensity at offset 12 for 16-byte points, 16 for pcl::PointXYZI (32 bytes)
-  FM_TRY(pin.reserve(n));
-  FM_TRY(dst.reserve(n));
+  LSLAM_TRY(pin.reserve(n));
+  LSLAM_TRY(dst.reserve(n));
   float4 *h = pin.p;
   const char *p = static_cast<const char *>(src);
   const size_t ioff = stride_bytes == 16 ? 12 : 16;
@@ -968,7 +933,7 @@ int pack_input(hipStream_t s, PinBuf<float4> &pin, DevBuf<float4> &dst, const vo
         mx[d] = hi[a][d] > mx[d] ? hi[a][d] : mx[d];
       }
   }
-  FM_TRY(hipMemcpyAsync(dst.p, h, n * sizeof(float4), hipMemcpyHostToDevice, s));
+  LSLAM_TRY(hipMemcpyAsync(dst.p, h, n * sizeof(float4), hipMemcpyHostToDevice, s));
   return LSLAM_OK;
 }
 
@@ -978,7 +943,7 @@ int check_fm(lslam_fmap *fm) {
     lslam::set_error("null feature map, or its ctx was destroyed");
     return LSLAM_ERR_INVALID;
   }
-  FM_TRY(hipSetDevice(lslam::ctx_device(fm->ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(fm->ctx)));
   if (fm->add_pending) return finish_add(fm);  // an addFeatureCloud begun and not yet committed: first of all that
   return LSLAM_OK;
 }
@@ -1011,14 +976,14 @@ int gather_surround(lslam_fmap *fm, int t, int index_in_w, size_t *n_out, int mi
   if (!total) return LSLAM_OK;
   hipStream_t s = fm->stream;
   DevBuf<int32_t> &gs = no_wait ? fm->g_src_t[t] : fm->g_src, &gd = no_wait ? fm->g_dst_t[t] : fm->g_dst;
-  FM_TRY(gs.reserve(src.size()));
-  FM_TRY(gd.reserve(dst.size()));
-  FM_TRY(fm->sur[t].reserve(total));
-  FM_TRY(hipMemcpyAsync(gs.p, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  FM_TRY(hipMemcpyAsync(gd.p, dst.data(), dst.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  LSLAM_TRY(gs.reserve(src.size()));
+  LSLAM_TRY(gd.reserve(dst.size()));
+  LSLAM_TRY(fm->sur[t].reserve(total));
+  LSLAM_TRY(hipMemcpyAsync(gs.p, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  LSLAM_TRY(hipMemcpyAsync(gd.p, dst.data(), dst.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(fm_gather_kernel, dim3(((int)total + 255) / 256), dim3(256), 0, s, fm->pts[t].p, gs.p,
                      gd.p, (int)src.size(), (int)total, index_in_w, fm->sur[t].p);
-  if (!no_wait) FM_TRY(hipStreamSynchronize(s));  // src/dst are locals
+  if (!no_wait) LSLAM_TRY(hipStreamSynchronize(s));  // src/dst are locals
   return LSLAM_OK;
 }
 
@@ -1060,11 +1025,11 @@ int voxel_filter_segments(lslam_ctx *ctx, const float4 *in_pts, const int32_t *i
   size_t &all_set = cache_p->all_set;
   {  // "every segment is filtered": ones, written when the array grows -- not once per call
     const uint8_t *before = all.p;
-    FM_TRY(all.reserve((size_t)nseg));
+    LSLAM_TRY(all.reserve((size_t)nseg));
     if (all.p != before) all_set = 0;
     if (all_set < (size_t)nseg) {
-      FM_TRY(hipMemsetAsync(all.p, 1, all.cap, s));
-      FM_TRY(hipStreamSynchronize(s));  // (once per growth)
+      LSLAM_TRY(hipMemsetAsync(all.p, 1, all.cap, s));
+      LSLAM_TRY(hipStreamSynchronize(s));  // (once per growth)
       all_set = all.cap;
     }
   }
@@ -1108,7 +1073,7 @@ int voxel_filter_window(hipStream_t s, WindowFilter *w, const float4 *in_pts, si
   kp.single = 1;
   kp.axis_bits = axis_bits;
   for (int d = 0; d < 3; ++d) kp.base0[d] = base0[d];
-  FM_TRY(w->oc.reserve(n_total));
+  LSLAM_TRY(w->oc.reserve(n_total));
   size_t m = 0;
   const int rc = run_pipeline(s, w->sc, in_pts, nullptr, n_total, kp, 1, nullptr, out_pts, w->oc.p, &m, 0, done, n_sorted);
   *order = w->sc.i1.p;
@@ -1124,7 +1089,7 @@ int lslam_fmap_create(lslam_ctx *ctx, int32_t w, int32_t h, int32_t d, lslam_fma
     return LSLAM_ERR_INVALID;
   }
   *out = nullptr;
-  FM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   lslam_fmap *fm = new lslam_fmap();
   fm->ctx = ctx;
   fm->stream = (hipStream_t)lslam_stream(ctx);
@@ -1134,9 +1099,9 @@ int lslam_fmap_create(lslam_ctx *ctx, int32_t w, int32_t h, int32_t d, lslam_fma
   fm->origin[0] = (int)std::round((w - 1) / 2.0);
   fm->origin[1] = (int)std::round((h - 1) / 2.0);
   fm->origin[2] = (int)std::round((d - 1) / 2.0);
-  FM_TRY(fm->active.reserve(fm->ncube));
-  FM_TRY(hipMemsetAsync(fm->active.p, 0, fm->ncube, fm->stream));
-  FM_TRY(hipStreamSynchronize(fm->stream));
+  LSLAM_TRY(fm->active.reserve(fm->ncube));
+  LSLAM_TRY(hipMemsetAsync(fm->active.p, 0, fm->ncube, fm->stream));
+  LSLAM_TRY(hipStreamSynchronize(fm->stream));
   *out = fm;
   return LSLAM_OK;
 }
@@ -1207,8 +1172,8 @@ int lslam_fmap_update(lslam_fmap *fm, const float pos[3]) {
     std::vector<int32_t> new_of_old(fm->ncube, -1);
     for (int c = 0; c < fm->ncube; ++c)
       if (content[c] >= 0) new_of_old[content[c]] = c;
-    FM_TRY(fm->d_remap.reserve(fm->ncube));
-    FM_TRY(hipMemcpyAsync(fm->d_remap.p, new_of_old.data(), sizeof(int32_t) * fm->ncube, hipMemcpyHostToDevice, s));
+    LSLAM_TRY(fm->d_remap.reserve(fm->ncube));
+    LSLAM_TRY(hipMemcpyAsync(fm->d_remap.p, new_of_old.data(), sizeof(int32_t) * fm->ncube, hipMemcpyHostToDevice, s));
     for (int t = 0; t < 2; ++t) {
       if (fm->n[t])
         hipLaunchKernelGGL(fm_relabel_kernel, dim3(((int)fm->n[t] + 255) / 256), dim3(256), 0, s, fm->cube[t].p,
@@ -1258,8 +1223,8 @@ static int add_feature_cloud_impl(lslam_fmap *fm, const void *corner, size_t n_c
   hipStream_t s = fm->stream;
   // everything for both feature types is enqueued, then ONE wait: uploads come from pinned staging, the voxel extent of a map
   // cube is bounded (map_axis_bits), the rebuilds' results land in pinned slots
-  FM_TRY(fm->done.reserve(8 + 16));
-  Rigid12 Tm;
+  LSLAM_TRY(fm->done.reserve(8 + 16));
+  lslam::Rigid12 Tm;
   std::memcpy(Tm.m, T, 12 * sizeof(float));
   // which cubes received points matters to the per-cube kd-trees only (lslam_fmap_to_cubemap builds a cube's tree again when
   // its cloud changed): until the first such call every cube counts as changed anyway, and the marks -- a fill, a copy back
@@ -1267,18 +1232,18 @@ static int add_feature_cloud_impl(lslam_fmap *fm, const void *corner, size_t n_c
   const bool track = fm->cube_trees_used;
   const void *src[2] = {corner, surf};
   const size_t cnt[2] = {n_corner, n_surf};
-  FM_TRY(fm->h_touched.reserve(2 * (size_t)fm->ncube));
+  LSLAM_TRY(fm->h_touched.reserve(2 * (size_t)fm->ncube));
   // two chains, two streams -- when both types have something to rebuild
   const bool two = !lslam::env_once().fmap_one_stream && (fm->n[0] + cnt[0]) && (fm->n[1] + cnt[1]);
   if (two) {
     if (!fm->stream2) {  // the context's second stream (the cell grids fork onto it too, never at the same time: one call per context)
       fm->stream2 = lslam::ctx_stream2(fm->ctx);
       if (!fm->stream2) return LSLAM_ERR_HIP;
-      FM_TRY(hipEventCreateWithFlags(&fm->ev_fork, hipEventDisableTiming));
-      FM_TRY(hipEventCreateWithFlags(&fm->ev_join, hipEventDisableTiming));
+      LSLAM_TRY(hipEventCreateWithFlags(&fm->ev_fork, hipEventDisableTiming));
+      LSLAM_TRY(hipEventCreateWithFlags(&fm->ev_join, hipEventDisableTiming));
     }
-    FM_TRY(hipEventRecord(fm->ev_fork, s));  // behind whatever the context's stream still does with the surf arrays
-    FM_TRY(hipStreamWaitEvent(fm->stream2, fm->ev_fork, 0));
+    LSLAM_TRY(hipEventRecord(fm->ev_fork, s));  // behind whatever the context's stream still does with the surf arrays
+    LSLAM_TRY(hipStreamWaitEvent(fm->stream2, fm->ev_fork, 0));
   }
   for (int t = 0; t < 2; ++t) {
     const size_t n = cnt[t];
@@ -1292,24 +1257,24 @@ static int add_feature_cloud_impl(lslam_fmap *fm, const void *corner, size_t n_c
       const float4 *raw = on_device ? static_cast<const float4 *>(src[t]) : fm->in_raw_t[t].p;
       // the transformed points go straight behind the type's current points, where the rebuild wants them (was: a staging
       // array of their own and two device-to-device copies per type)
-      FM_TRY(fm->pts[t].grow(fm->n[t] + n, fm->n[t], st));
-      FM_TRY(fm->cube[t].grow(fm->n[t] + n, fm->n[t], st));
+      LSLAM_TRY(fm->pts[t].grow(fm->n[t] + n, fm->n[t], st));
+      LSLAM_TRY(fm->cube[t].grow(fm->n[t] + n, fm->n[t], st));
       KeyParams kp = key_params(fm, fm->leaf[t]);
       if (track) {
-        FM_TRY(fm->d_touched_t[t].reserve(((size_t)fm->ncube + 15) & ~(size_t)15));
-        FM_TRY(hipMemsetAsync(fm->d_touched_t[t].p, 0, ((size_t)fm->ncube + 15) & ~(size_t)15, st));  // (a whole number of 16-byte words: one fill launch, no tail)
+        LSLAM_TRY(fm->d_touched_t[t].reserve(((size_t)fm->ncube + 15) & ~(size_t)15));
+        LSLAM_TRY(hipMemsetAsync(fm->d_touched_t[t].p, 0, ((size_t)fm->ncube + 15) & ~(size_t)15, st));  // (a whole number of 16-byte words: one fill launch, no tail)
       }
       hipLaunchKernelGGL(fm_transform_kernel, dim3(((int)n + 255) / 256), dim3(256), 0, st, raw, (int)n,
                          Tm, kp, fm->pts[t].p + fm->n[t], fm->cube[t].p + fm->n[t], track ? fm->d_touched_t[t].p : (uint8_t *)nullptr);
-      if (track) FM_TRY(hipMemcpyAsync(fm->h_touched.p + (size_t)t * fm->ncube, fm->d_touched_t[t].p, fm->ncube, hipMemcpyDeviceToHost, st));
+      if (track) LSLAM_TRY(hipMemcpyAsync(fm->h_touched.p + (size_t)t * fm->ncube, fm->d_touched_t[t].p, fm->ncube, hipMemcpyDeviceToHost, st));
     }
     rc = rebuild_begin(fm, t, n, true, nullptr, fm->done.p + 4 * t, fm->pts[t].p + fm->n[t], fm->cube[t].p + fm->n[t], nullptr, true, st,
                        (two && t == 1) ? &fm->sc2 : &fm->sc);
     if (rc) return rc;
   }
   if (two) {
-    FM_TRY(hipEventRecord(fm->ev_join, fm->stream2));
-    FM_TRY(hipStreamWaitEvent(s, fm->ev_join, 0));
+    LSLAM_TRY(hipEventRecord(fm->ev_join, fm->stream2));
+    LSLAM_TRY(hipStreamWaitEvent(s, fm->ev_join, 0));
   }
   fm->add_cnt[0] = cnt[0];
   fm->add_cnt[1] = cnt[1];
@@ -1326,7 +1291,7 @@ int finish_add(lslam_fmap *fm) {
   const size_t *cnt = fm->add_cnt;
   const bool track = fm->add_track;
   int rc = LSLAM_OK;
-  FM_TRY(hipStreamSynchronize(s));
+  LSLAM_TRY(hipStreamSynchronize(s));
   for (int t = 0; t < 2; ++t) {
     const size_t n = cnt[t];
     if (fm->done.p[4 * t + 1] || fm->done.p[4 * t + 2]) {
@@ -1381,9 +1346,9 @@ int lslam_fmap_get_surround(lslam_fmap *fm, float *corner_xyzi, size_t cap_corne
       lslam::set_error("surround buffer too small");
       return LSLAM_ERR_INVALID;
     }
-    if (n) FM_TRY(hipMemcpyAsync(out[t], fm->sur[t].p, n * sizeof(float4), hipMemcpyDeviceToHost, fm->stream));
+    if (n) LSLAM_TRY(hipMemcpyAsync(out[t], fm->sur[t].p, n * sizeof(float4), hipMemcpyDeviceToHost, fm->stream));
   }
-  FM_TRY(hipStreamSynchronize(fm->stream));
+  LSLAM_TRY(hipStreamSynchronize(fm->stream));
   return LSLAM_OK;
 }
 
@@ -1398,51 +1363,42 @@ int lslam_fmap_surround_to_map_counts(lslam_fmap *fm, size_t *n_corner, size_t *
   const int n_valid = (int)fm->valid.size();
   size_t n[2] = {0, 0};
   float lo[2][3], hi[2][3];
-  FM_TRY(fm->sur_res.reserve(16));
-  FM_TRY(fm->done.reserve(8 + 16));
+  LSLAM_TRY(fm->sur_res.reserve(16));
+  LSLAM_TRY(fm->done.reserve(8 + 16));
   uint32_t *h_res = fm->done.p + 8;  // pinned: [2 types][8]
   for (int k = 0; k < 16; ++k) h_res[k] = 0u;
   bool any = false;
   for (int t = 0; t < 2; ++t) {
     if (!fm->n[t] || !n_valid) {  // nothing of this type: its words of the result read "no points"
-      FM_TRY(hipMemsetAsync(fm->sur_res.p + 8 * t, 0, 8 * sizeof(uint32_t), s));
+      LSLAM_TRY(hipMemsetAsync(fm->sur_res.p + 8 * t, 0, 8 * sizeof(uint32_t), s));
       continue;
     }
     rc = refresh_segments_device(fm, t);
     if (rc) return rc;
-    FM_TRY(fm->g_src_t[t].reserve((size_t)n_valid));
-    FM_TRY(fm->g_dst_t[t].reserve((size_t)n_valid));
-    FM_TRY(fm->sur[t].reserve(fm->n[t]));  // (the surround is at most the map)
+    LSLAM_TRY(fm->g_src_t[t].reserve((size_t)n_valid));
+    LSLAM_TRY(fm->g_dst_t[t].reserve((size_t)n_valid));
+    LSLAM_TRY(fm->sur[t].reserve(fm->n[t]));  // (the surround is at most the map)
     hipLaunchKernelGGL(fm_surround_plan_kernel, dim3(1), dim3(256), 0, s, (const int32_t *)fm->d_valid.p, n_valid,
                        (const int32_t *)fm->seg_begin[t].p, (int)seg_pad(fm), fm->g_src_t[t].p, fm->g_dst_t[t].p, fm->sur_res.p + 8 * t);
     const unsigned blocks = (unsigned)std::min<size_t>(512, (fm->n[t] + 255) / 256);
     hipLaunchKernelGGL(fm_gather_box_kernel, dim3(blocks), dim3(256), 0, s, (const float4 *)fm->pts[t].p, (const int32_t *)fm->g_src_t[t].p,
                        (const int32_t *)fm->g_dst_t[t].p, n_valid, fm->sur_res.p + 8 * t, 1, fm->sur[t].p);
-    FM_TRY(hipGetLastError());
+    LSLAM_TRY(hipGetLastError());
     any = true;
   }
   if (any) {  // one copy and the one wait: both types' totals and boxes (a type that was skipped left its words untouched: zeroed below)
-    FM_TRY(hipMemcpyAsync(h_res, fm->sur_res.p, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    FM_TRY(hipStreamSynchronize(s));
+    LSLAM_TRY(hipMemcpyAsync(h_res, fm->sur_res.p, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LSLAM_TRY(hipStreamSynchronize(s));
   }
   for (int t = 0; t < 2; ++t) {
     n[t] = h_res[8 * t];
-    for (int a = 0; a < 3; ++a) {
-      auto back = [](uint32_t o) {  // fm_ordered_u32's inverse
-        const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-        float f;
-        std::memcpy(&f, &u, 4);
-        return f;
-      };
-      lo[t][a] = back(~h_res[8 * t + 1 + a]);
-      hi[t][a] = back(h_res[8 * t + 4 + a]);
-    }
+    lslam::box_back(h_res + 8 * t + 1, lo[t], hi[t]);
   }
   if (n_corner) *n_corner = n[0];
   if (n_surf) *n_surf = n[1];
   if (n[0] == 0 && n[1] == 0) return lslam_map_set(fm->ctx, nullptr, 0, nullptr, 0, 16);
-  FM_TRY(fm->sur[0].reserve(1));
-  FM_TRY(fm->sur[1].reserve(1));
+  LSLAM_TRY(fm->sur[0].reserve(1));
+  LSLAM_TRY(fm->sur[1].reserve(1));
   return lslam::map_set_device(fm->ctx, fm->sur[0].p, n[0], fm->sur[1].p, n[1], lo, hi);
 }
 
@@ -1491,7 +1447,7 @@ int lslam_fmap_to_cubemap(lslam_fmap *fm) {
     fm->cube_tree[t].resize((size_t)fm->ncube);
     fm->dirty[t].resize((size_t)fm->ncube, 1);
   }
-  FM_TRY(hipStreamSynchronize(s));  // both types' segment tables are on the host
+  LSLAM_TRY(hipStreamSynchronize(s));  // both types' segment tables are on the host
   // compaction: too many generations alive means many half-empty arrays -- drop every tree, the active area is
   // rebuilt into one generation below
   if (gens.size() > 12) {
@@ -1544,10 +1500,10 @@ int lslam_fmap_to_cubemap(lslam_fmap *fm) {
       if (!gens[k]) { gi = (int)k; break; }
     if (gi < 0) { gi = (int)gens.size(); gens.push_back(nullptr); }
     gens[(size_t)gi] = g;
-    FM_TRY(g->pts.reserve(total + 16));
+    LSLAM_TRY(g->pts.reserve(total + 16));
     const size_t n_seg = src[0].size() + src[1].size();
-    FM_TRY(fm->g_src.reserve(n_seg));
-    FM_TRY(fm->g_dst.reserve(n_seg));
+    LSLAM_TRY(fm->g_src.reserve(n_seg));
+    LSLAM_TRY(fm->g_dst.reserve(n_seg));
     auto gather = [&]() -> hipError_t {
       size_t seg0 = 0, base = 0;
       for (int t = 0; t < 2; ++t) {
@@ -1564,12 +1520,12 @@ int lslam_fmap_to_cubemap(lslam_fmap *fm) {
       size_t seg0 = 0;
       for (int t = 0; t < 2; ++t) {
         if (src[t].empty()) continue;
-        FM_TRY(hipMemcpyAsync(fm->g_src.p + seg0, src[t].data(), src[t].size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        FM_TRY(hipMemcpyAsync(fm->g_dst.p + seg0, dst[t].data(), dst[t].size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        LSLAM_TRY(hipMemcpyAsync(fm->g_src.p + seg0, src[t].data(), src[t].size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        LSLAM_TRY(hipMemcpyAsync(fm->g_dst.p + seg0, dst[t].data(), dst[t].size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
         seg0 += src[t].size();
       }
     }
-    FM_TRY(gather());  // (src / dst: pageable sources are consumed when hipMemcpyAsync returns, no wait needed)
+    LSLAM_TRY(gather());  // (src / dst: pageable sources are consumed when hipMemcpyAsync returns, no wait needed)
     const auto t2 = now();
     std::vector<lslam::TreeView> built((size_t)T);
     int fallback = 0, max_depth = 0;
@@ -1580,9 +1536,9 @@ int lslam_fmap_to_cubemap(lslam_fmap *fm) {
     for (int attempt = first_attempt; attempt < 3; ++attempt) {
       const size_t mult[3] = {2, 8, 24};
       const size_t cap = ((mult[attempt] * total / 3 + 64 + 8 * (size_t)T) + 7) & ~(size_t)7;
-      FM_TRY(g->nodes.reserve(cap));
-      if (attempt > first_attempt) FM_TRY(gather());  // the failed attempt permuted the points: gather them again
-      FM_TRY(lslam::build_kdforest_device(lslam::ctx_build_pool(fm->ctx, 0), g->pts.p, (int32_t)total, roots_lr.data(), T, g->nodes.p, nullptr,
+      LSLAM_TRY(g->nodes.reserve(cap));
+      if (attempt > first_attempt) LSLAM_TRY(gather());  // the failed attempt permuted the points: gather them again
+      LSLAM_TRY(lslam::build_kdforest_device(lslam::ctx_build_pool(fm->ctx, 0), g->pts.p, (int32_t)total, roots_lr.data(), T, g->nodes.p, nullptr,
                                           (int32_t)cap, s, built.data(), &max_depth, &n_leaves, &fallback));
       if (fallback != 1) {
         fm->forest_attempt0 = attempt;
@@ -1674,13 +1630,13 @@ int lslam_fmap_get_full_map(lslam_fmap *fm, float *out_xyzi, size_t cap, size_t 
   std::vector<float4> h[2];
   std::vector<int32_t> hc[2];
   DevBuf<uint8_t> force;
-  FM_TRY(force.reserve(fm->ncube));
-  FM_TRY(hipMemsetAsync(force.p, 1, fm->ncube, s));  // filter every cube
+  LSLAM_TRY(force.reserve(fm->ncube));
+  LSLAM_TRY(hipMemsetAsync(force.p, 1, fm->ncube, s));  // filter every cube
   for (int t = 0; t < 2; ++t) {
     const size_t n = fm->n[t];
     if (!n) continue;
-    FM_TRY(fm->pts_alt[t].reserve(n));
-    FM_TRY(fm->cube_alt[t].reserve(n));
+    LSLAM_TRY(fm->pts_alt[t].reserve(n));
+    LSLAM_TRY(fm->cube_alt[t].reserve(n));
     KeyParams kp = key_params(fm, fm->leaf[2]);
     size_t m = 0;
     rc = run_pipeline(s, fm->sc, fm->pts[t].p, fm->cube[t].p, n, kp, fm->ncube, force.p, fm->pts_alt[t].p,
@@ -1689,10 +1645,10 @@ int lslam_fmap_get_full_map(lslam_fmap *fm, float *out_xyzi, size_t cap, size_t 
     h[t].resize(m);
     hc[t].resize(m);
     if (m) {
-      FM_TRY(hipMemcpyAsync(h[t].data(), fm->pts_alt[t].p, m * sizeof(float4), hipMemcpyDeviceToHost, s));
-      FM_TRY(hipMemcpyAsync(hc[t].data(), fm->cube_alt[t].p, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      LSLAM_TRY(hipMemcpyAsync(h[t].data(), fm->pts_alt[t].p, m * sizeof(float4), hipMemcpyDeviceToHost, s));
+      LSLAM_TRY(hipMemcpyAsync(hc[t].data(), fm->cube_alt[t].p, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     }
-    FM_TRY(hipStreamSynchronize(s));
+    LSLAM_TRY(hipStreamSynchronize(s));
   }
   const size_t total = h[0].size() + h[1].size();
   if (n_out) *n_out = total;
@@ -1794,9 +1750,9 @@ int lslam_fmap_save(lslam_fmap *fm, const char *directory) {
     rc = refresh_segments(fm, t);
     if (rc) return rc;
     h[t].resize(fm->n[t]);
-    if (fm->n[t]) FM_TRY(hipMemcpyAsync(h[t].data(), fm->pts[t].p, fm->n[t] * sizeof(float4), hipMemcpyDeviceToHost, s));
+    if (fm->n[t]) LSLAM_TRY(hipMemcpyAsync(h[t].data(), fm->pts[t].p, fm->n[t] * sizeof(float4), hipMemcpyDeviceToHost, s));
   }
-  FM_TRY(hipStreamSynchronize(s));
+  LSLAM_TRY(hipStreamSynchronize(s));
   const std::string dir(directory);
   std::ofstream fout(dir + "/index.txt");
   if (!fout) {
@@ -1857,7 +1813,7 @@ int lslam_fmap_load(lslam_fmap *fm, const char *directory) {
   }
   hipStream_t s = fm->stream;
   DevBuf<uint8_t> d_flags;
-  FM_TRY(d_flags.reserve(fm->ncube));
+  LSLAM_TRY(d_flags.reserve(fm->ncube));
   for (int t = 0; t < 2 && rc == LSLAM_OK; ++t) {
     const size_t n = pts[t].size();
     if (hipMemcpyAsync(d_flags.p, loaded[t].data(), fm->ncube, hipMemcpyHostToDevice, s) != hipSuccess) { rc = LSLAM_ERR_HIP; break; }
@@ -1897,7 +1853,7 @@ static int voxel_grid_impl(lslam_ctx *ctx, const void *cloud, size_t n, size_t s
   }
   *n_out = 0;
   if (n == 0) return LSLAM_OK;
-  FM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = (hipStream_t)lslam_stream(ctx);
   VoxelGridCache &cache = *lslam::ctx_slot<VoxelGridCache>(ctx, lslam::CTX_SLOT_VOXEL_GRID);
   DevBuf<float4> &out = cache.out;
@@ -1925,24 +1881,24 @@ static int voxel_grid_impl(lslam_ctx *ctx, const void *cloud, size_t n, size_t s
   if (!(vol <= (long long)INT32_MAX)) {
     // applyFilter: "Leaf size is too small for the input dataset" -> the input is returned unfiltered
     if (n > cap) { lslam::set_error("voxel-grid output buffer too small"); return LSLAM_ERR_INVALID; }
-    FM_TRY(hipStreamSynchronize(s));  // (the upload: nothing else was enqueued)
+    LSLAM_TRY(hipStreamSynchronize(s));  // (the upload: nothing else was enqueued)
     if (out_xyzi) std::memcpy(out_xyzi, cache.in_pin.p, n * sizeof(float4));
     *n_out = n;
     return LSLAM_OK;
   }
-  FM_TRY(out.reserve(n));
-  FM_TRY(oc.reserve(n));
-  FM_TRY(cache.done.reserve(4));
+  LSLAM_TRY(out.reserve(n));
+  LSLAM_TRY(oc.reserve(n));
+  LSLAM_TRY(cache.done.reserve(4));
   // small clouds (a sweep's features): the whole output area comes back behind the count in ONE wait and the m points are
   // copied out of pinned memory; large ones wait for the count first and fetch exactly m points
   const bool one_wait = n * sizeof(float4) <= (size_t)1 << 20;
   size_t m = 0;
   if (one_wait) {
-    FM_TRY(cache.out_pin.reserve(n));
+    LSLAM_TRY(cache.out_pin.reserve(n));
     // (the centroids are written to pinned memory by their kernel: no copy of all n slots behind it)
     rc = run_pipeline(s, sc, cache.in_raw.p, nullptr, n, kp, 1, nullptr, cache.out_pin.p, oc.p, &m, 0, cache.done.p);
     if (rc) return rc;
-    FM_TRY(hipStreamSynchronize(s));
+    LSLAM_TRY(hipStreamSynchronize(s));
     if (cache.done.p[1]) {
       lslam::set_error("voxel index outside its key range (non-finite point?)");
       return LSLAM_ERR_INVALID;
@@ -1982,15 +1938,15 @@ static int voxel_grid2_impl(lslam_ctx *ctx, const void *a, size_t na, const void
   *n_a = *n_b = 0;
   const size_t n = na + nb;
   if (n == 0) return LSLAM_OK;
-  FM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = (hipStream_t)lslam_stream(ctx);
   VoxelGrid2Cache &c = *lslam::ctx_slot<VoxelGrid2Cache>(ctx, lslam::CTX_SLOT_VOXEL_GRID2);
-  FM_TRY(c.in_pin.reserve(n));
-  FM_TRY(c.out_pin.reserve(n));
-  FM_TRY(c.seg_pin.reserve(n));
-  FM_TRY(c.done.reserve(4));
-  FM_TRY(c.in_raw.reserve(n));
-  FM_TRY(c.seg.reserve(n));
+  LSLAM_TRY(c.in_pin.reserve(n));
+  LSLAM_TRY(c.out_pin.reserve(n));
+  LSLAM_TRY(c.seg_pin.reserve(n));
+  LSLAM_TRY(c.done.reserve(4));
+  LSLAM_TRY(c.in_raw.reserve(n));
+  LSLAM_TRY(c.seg.reserve(n));
   const void *src[2] = {a, b};
   const size_t cnt[2] = {na, nb};
   size_t at = 0;
@@ -2010,7 +1966,7 @@ static int voxel_grid2_impl(lslam_ctx *ctx, const void *a, size_t na, const void
     }
     at += cnt[k];
   }
-  FM_TRY(hipMemcpyAsync(c.in_raw.p, c.in_pin.p, n * sizeof(float4), hipMemcpyHostToDevice, s));
+  LSLAM_TRY(hipMemcpyAsync(c.in_raw.p, c.in_pin.p, n * sizeof(float4), hipMemcpyHostToDevice, s));
   // segment 0 for the first cloud's points, 1 for the second's: one launch (two fills were up to four: aligned part + tail each)
   hipLaunchKernelGGL(fm_two_segments_kernel, dim3(((unsigned)n + 255) / 256), dim3(256), 0, s, c.seg.p, (int)na, (int)n);
   size_t m = 0;
@@ -2018,11 +1974,11 @@ static int voxel_grid2_impl(lslam_ctx *ctx, const void *a, size_t na, const void
   // not known on the host yet -- the copies this replaces moved all n slots, 0.8 MB for a sweep's 42 k points)
   int rc = lslam::voxel_filter_segments(ctx, c.in_raw.p, c.seg.p, n, 2, leaf, c.out_pin.p, c.seg_pin.p, &m, true, c.done.p);
   if (rc) return rc;
-  FM_TRY(hipStreamSynchronize(s));
+  LSLAM_TRY(hipStreamSynchronize(s));
   if (c.done.p[1]) {  // the wide key did not hold an extent: once more with the measured one (waits inside)
     rc = lslam::voxel_filter_segments(ctx, c.in_raw.p, c.seg.p, n, 2, leaf, c.out_pin.p, c.seg_pin.p, &m, true, nullptr);
     if (rc) return rc;
-    FM_TRY(hipStreamSynchronize(s));
+    LSLAM_TRY(hipStreamSynchronize(s));
   } else {
     m = c.done.p[0];
   }
@@ -2071,7 +2027,7 @@ int voxel_grid_device(lslam_ctx *ctx, const float4 *d_in, size_t n, const float 
     lslam::set_error("bad voxel-grid arguments");
     return LSLAM_ERR_INVALID;
   }
-  FM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = lslam::ctx_stream(ctx);
   VoxelGridCache &cache = *lslam::ctx_slot<VoxelGridCache>(ctx, lslam::CTX_SLOT_VOXEL_GRID);
   const float inv = 1.0f / leaf;
@@ -2090,17 +2046,17 @@ int voxel_grid_device(lslam_ctx *ctx, const float4 *d_in, size_t n, const float 
   }
   kp.axis_bits = bits_for(cells + 1.0);
   if (!(vol <= (long long)INT32_MAX)) {  // "Leaf size is too small for the input dataset": the input, unfiltered
-    FM_TRY(hipMemcpyAsync(d_out, d_in, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    LSLAM_TRY(hipMemcpyAsync(d_out, d_in, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
     *n_out = n;
     return LSLAM_OK;
   }
-  FM_TRY(cache.oc.reserve(n));
-  FM_TRY(cache.done.reserve(4));
+  LSLAM_TRY(cache.oc.reserve(n));
+  LSLAM_TRY(cache.done.reserve(4));
   size_t m = 0;
   if (n * sizeof(float4) <= (size_t)1 << 20) {  // (lslam_voxel_grid's two forms of the same pipeline)
     const int rc = run_pipeline(s, cache.sc, d_in, nullptr, n, kp, 1, nullptr, d_out, cache.oc.p, &m, 0, cache.done.p);
     if (rc) return rc;
-    FM_TRY(hipStreamSynchronize(s));
+    LSLAM_TRY(hipStreamSynchronize(s));
     if (cache.done.p[1]) {
       lslam::set_error("voxel index outside its key range (non-finite point?)");
       return LSLAM_ERR_INVALID;
@@ -2126,8 +2082,8 @@ int fmap_set_clouds(lslam_fmap *fm, const void *corner, size_t n_corner, const v
   const size_t cnt[2] = {n_corner, n_surf};
   DevBuf<uint8_t> d_flags;
   if (filter) {
-    FM_TRY(d_flags.reserve(fm->ncube));
-    FM_TRY(hipMemsetAsync(d_flags.p, 1, fm->ncube, s));
+    LSLAM_TRY(d_flags.reserve(fm->ncube));
+    LSLAM_TRY(hipMemsetAsync(d_flags.p, 1, fm->ncube, s));
   }
   for (int t = 0; t < 2; ++t) {
     std::vector<float4> pts;
@@ -2151,14 +2107,14 @@ int fmap_set_clouds(lslam_fmap *fm, const void *corner, size_t n_corner, const v
     fm->n[t] = 0;
     fm->seg_current[t] = fm->seg_dev_current[t] = false;
     if (n) {
-      FM_TRY(fm->in_tf.reserve(n));
-      FM_TRY(fm->in_cube.reserve(n));
-      FM_TRY(hipMemcpyAsync(fm->in_tf.p, pts.data(), n * sizeof(float4), hipMemcpyHostToDevice, s));
-      FM_TRY(hipMemcpyAsync(fm->in_cube.p, cube.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+      LSLAM_TRY(fm->in_tf.reserve(n));
+      LSLAM_TRY(fm->in_cube.reserve(n));
+      LSLAM_TRY(hipMemcpyAsync(fm->in_tf.p, pts.data(), n * sizeof(float4), hipMemcpyHostToDevice, s));
+      LSLAM_TRY(hipMemcpyAsync(fm->in_cube.p, cube.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     }
     rc = rebuild(fm, t, n, filter, filter ? d_flags.p : nullptr);
     if (rc) return rc;
-    FM_TRY(hipStreamSynchronize(s));  // (pts / cube are locals)
+    LSLAM_TRY(hipStreamSynchronize(s));  // (pts / cube are locals)
   }
   return LSLAM_OK;
 }
@@ -2192,14 +2148,14 @@ int fmap_copy(lslam_fmap *dst, lslam_fmap *src) {
     dst->n[t] = 0;
     dst->seg_current[t] = dst->seg_dev_current[t] = false;
     if (n) {
-      FM_TRY(dst->pts[t].reserve(n));
-      FM_TRY(dst->cube[t].reserve(n));
-      FM_TRY(hipMemcpyAsync(dst->pts[t].p, src->pts[t].p, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
-      FM_TRY(hipMemcpyAsync(dst->cube[t].p, src->cube[t].p, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+      LSLAM_TRY(dst->pts[t].reserve(n));
+      LSLAM_TRY(dst->cube[t].reserve(n));
+      LSLAM_TRY(hipMemcpyAsync(dst->pts[t].p, src->pts[t].p, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+      LSLAM_TRY(hipMemcpyAsync(dst->cube[t].p, src->cube[t].p, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     }
     dst->n[t] = n;
   }
-  FM_TRY(hipStreamSynchronize(s));
+  LSLAM_TRY(hipStreamSynchronize(s));
   return LSLAM_OK;
 }
 

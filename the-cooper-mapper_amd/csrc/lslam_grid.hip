@@ -9,7 +9,7 @@
 // per frame: four launches per feature type (rocPRIM's radix sort + scan took 25: 140 + 65 us for 587 k points).
 #include "lslam_grid.hpp"
 #include "lslam_internal.hpp"
-
+#include "lslam_pointgrid_dev.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -150,47 +150,6 @@ __global__ __launch_bounds__(256) void grid_rank_kernel(CellGrid G, const float4
   pts[at] = p;
 }
 
-__device__ __forceinline__ uint32_t ordered_u32(float f) {  // monotone map float -> uint32 (for atomicMin / atomicMax)
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__global__ __launch_bounds__(256) void grid_bbox_kernel(const float4 *pts, int n, uint32_t *box /* [6]: min xyz, max xyz (ordered) */) {
-  uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const float4 p = pts[i];
-    const uint32_t v[3] = {ordered_u32(p.x), ordered_u32(p.y), ordered_u32(p.z)};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = min(lo[a], v[a]);
-      hi[a] = max(hi[a], v[a]);
-    }
-  }
-  // wavefront reduction in registers, then six atomics per wavefront (256 lanes on six LDS words serialise)
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], d, 64));
-      hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], d, 64));
-    }
-  __shared__ uint32_t part[4][6];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      part[wave][a] = lo[a];
-      part[wave][3 + a] = hi[a];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {  // six atomics per workgroup: same-address atomics from a whole grid serialise at the memory side
-    const int a = threadIdx.x;
-    uint32_t v = part[0][a];
-    for (int w = 1; w < 4; ++w) v = a < 3 ? min(v, part[w][a]) : max(v, part[w][a]);
-    if (a < 3) atomicMin(&box[a], v); else atomicMax(&box[a], v);
-  }
-}
-
 __global__ __launch_bounds__(256) void grid_unsort_kernel(int n, const float4 *gpts, float4 *out) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
@@ -210,25 +169,17 @@ hipError_t grid_unsort(const CellGrid &G, float4 *out, hipStream_t s) {
 
 // Bounding boxes of two device clouds (nanoflann's root_bbox: componentwise min / max), ONE host round trip for both.
 hipError_t grid_bbox2(const float4 *const pts[2], const int n[2], uint32_t *d_box12, float lo[2][3], float hi[2][3], hipStream_t s) {
-  uint32_t init[12];
-  for (int k = 0; k < 2; ++k)
-    for (int a = 0; a < 6; ++a) init[6 * k + a] = a < 3 ? 0xFFFFFFFFu : 0u;
-  hipError_t e = hipMemcpyAsync(d_box12, init, sizeof(init), hipMemcpyHostToDevice, s);
+  const uint32_t zero[12] = {};
+  uint32_t h[12];
+  hipError_t e = hipMemcpyAsync(d_box12, zero, sizeof(zero), hipMemcpyHostToDevice, s);
   if (e != hipSuccess) return e;
   for (int k = 0; k < 2; ++k)
-    if (n[k] > 0) hipLaunchKernelGGL(grid_bbox_kernel, dim3(std::min((n[k] + 4095) / 4096, 256)), dim3(256), 0, s, pts[k], n[k], d_box12 + 6 * k);
-  uint32_t h[12];
+    if (n[k] > 0) hipLaunchKernelGGL(box_kernel<false>, box_blocks(n[k]), dim3(BOX_BLOCK), 0, s, pts[k], n[k], d_box12 + 6 * k);
   e = hipMemcpyAsync(h, d_box12, sizeof(h), hipMemcpyDeviceToHost, s);
   if (e != hipSuccess) return e;
-  e = hipStreamSynchronize(s);  // (also covers `init`: a local)
+  e = hipStreamSynchronize(s);  // (also covers `zero`: a local)
   if (e != hipSuccess) return e;
-  for (int k = 0; k < 2; ++k)
-    for (int a = 0; a < 6; ++a) {
-      const uint32_t u = (h[6 * k + a] & 0x80000000u) ? (h[6 * k + a] & 0x7FFFFFFFu) : ~h[6 * k + a];
-      float f;
-      std::memcpy(&f, &u, 4);
-      (a < 3 ? lo[k][a] : hi[k][a - 3]) = f;
-    }
+  for (int k = 0; k < 2; ++k) box_back(h + 6 * k, lo[k], hi[k]);
   return hipSuccess;
 }
 

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdio>
+
 #include <string>
 #include <vector>
 
@@ -542,3 +544,21 @@ hipError_t launch_match_information(const float4 *q, int n, int n_corner, const 
 // lslam_scanprep.hip: Morton ordering of the resident scans on the device
 hipError_t scanprep_order(lslam_ctx *ctx, const float4 *h_pts, size_t n, const int32_t *h_seg_off, int nseg, float4 *d_out);
 }  // namespace lslam
+
+// A HIP call that fails ends the calling entry point: its text, HIP's message and the place go to set_error, LSLAM_ERR_HIP
+// comes back.  LSLAM_RC: the same for an internal step that returns a status of its own (which has set the error already).
+#define LSLAM_TRY(expr)                                                                  \
+  do {                                                                                   \
+    hipError_t _e = (expr);                                                              \
+    if (_e != hipSuccess) {                                                              \
+      char _b[400];                                                                      \
+      snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+      lslam::set_error(_b);                                                              \
+      return LSLAM_ERR_HIP;                                                              \
+    }                                                                                    \
+  } while (0)
+#define LSLAM_RC(expr)               \
+  do {                               \
+    const int _rc = (expr);          \
+    if (_rc != LSLAM_OK) return _rc; \
+  } while (0)

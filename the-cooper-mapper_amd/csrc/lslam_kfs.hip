@@ -136,7 +136,7 @@ int add_impl(lslam_kfs *k, const void *corner, size_t n_corner, const void *surf
       return LSLAM_ERR_INVALID;
     }
   hipStream_t s = k->stream;
-  if (host) KFS_TRY(k->h_stage.reserve(n[0] + n[1]));
+  if (host) LSLAM_TRY(k->h_stage.reserve(n[0] + n[1]));
   Placement pl;
   rc = place(k, n, &pl);
   if (rc) return rc;
@@ -221,19 +221,19 @@ int assemble(lslam_kfs *k, const char *what, int32_t n_cand, const int32_t *ids,
     a.n_cand = n_cand;
     k->n_local[t] = total;
     if (!total) continue;
-    KFS_TRY(k->local[t].reserve(total));
+    LSLAM_TRY(k->local[t].reserve(total));
     a.out = k->local[t].p;
     hipLaunchKernelGGL(kfs_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, k->stream, a);
-    KFS_TRY(hipGetLastError());
+    LSLAM_TRY(hipGetLastError());
   }
   return LSLAM_OK;
 }
 
 int index_cloud(lslam_kfs *k, const float4 *in, size_t n, lslam::DevBuf<float4> &out) {
-  KFS_TRY(out.reserve(n ? n : 1));
+  LSLAM_TRY(out.reserve(n ? n : 1));
   if (!n) return LSLAM_OK;
   hipLaunchKernelGGL(kfs_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k->stream, in, (int)n, out.p);
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   return LSLAM_OK;
 }
 
@@ -253,7 +253,7 @@ int kfs_gather_posed(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const floa
     lslam::set_error("keyframe store: the named keyframes' clouds hold more than 2^31 points");
     return LSLAM_ERR_INVALID;
   }
-  KFS_TRY(out.reserve(total ? total : 1));
+  LSLAM_TRY(out.reserve(total ? total : 1));
   size_t base = 0;
   for (int32_t c0 = 0; c0 < n_ids; c0 += KFS_MAX_CAND - 1) {
     const int m = n_ids - c0 < KFS_MAX_CAND - 1 ? n_ids - c0 : KFS_MAX_CAND - 1;
@@ -274,7 +274,7 @@ int kfs_gather_posed(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const floa
     base += chunk;
     if (!chunk) continue;
     hipLaunchKernelGGL(kfs_gather_kernel, dim3((unsigned)((chunk + 255) / 256)), dim3(256), 0, k->stream, a);
-    KFS_TRY(hipGetLastError());
+    LSLAM_TRY(hipGetLastError());
   }
   return LSLAM_OK;
 }
@@ -293,7 +293,7 @@ int lslam_kfs_create(lslam_ctx *ctx, size_t max_points_per_type, int32_t max_key
     lslam::set_error("lslam_kfs_create: negative max_keyframes, or max_points_per_type / slab_points above 2^30");
     return LSLAM_ERR_INVALID;
   }
-  KFS_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   lslam_kfs *k = new lslam_kfs();
   k->ctx = ctx;
   k->stream = lslam::ctx_stream(ctx);
@@ -322,7 +322,7 @@ void lslam_kfs_destroy(lslam_kfs *k) {
 int lslam_kfs_clear(lslam_kfs *k) {
   const int rc = check_kfs(k, "lslam_kfs_clear");
   if (rc) return rc;
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   k->kfs.clear();
   k->slabs.clear();
   k->total[0] = k->total[1] = 0;
@@ -373,8 +373,8 @@ int lslam_kfs_get(lslam_kfs *k, int32_t id, int32_t which, float *out_xyzi, size
     return LSLAM_ERR_INVALID;
   }
   if (n) {
-    KFS_TRY(hipMemcpyAsync(out_xyzi, kc.p[which], n * sizeof(float4), hipMemcpyDeviceToHost, k->stream));
-    KFS_TRY(hipStreamSynchronize(k->stream));
+    LSLAM_TRY(hipMemcpyAsync(out_xyzi, kc.p[which], n * sizeof(float4), hipMemcpyDeviceToHost, k->stream));
+    LSLAM_TRY(hipStreamSynchronize(k->stream));
     k->bytes_down += (uint64_t)n * sizeof(float4);
   }
   return LSLAM_OK;
@@ -438,11 +438,11 @@ int lslam_kfs_debug_local_clouds(lslam_kfs *k, int32_t n_cand, const int32_t *id
       return LSLAM_ERR_INVALID;
     }
     if (k->n_local[t]) {
-      KFS_TRY(hipMemcpyAsync(dst[t], k->local[t].p, k->n_local[t] * sizeof(float4), hipMemcpyDeviceToHost, k->stream));
+      LSLAM_TRY(hipMemcpyAsync(dst[t], k->local[t].p, k->n_local[t] * sizeof(float4), hipMemcpyDeviceToHost, k->stream));
       k->bytes_down += (uint64_t)k->n_local[t] * sizeof(float4);
     }
   }
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   return LSLAM_OK;
 }
 
@@ -468,7 +468,7 @@ int lslam_kfs_loop_match(lslam_kfs *k, int32_t n_cand, const int32_t *ids, const
   }
   const KeyframeClouds nk = k->kfs[(size_t)new_id];
   if (k->n_local[1] == 0) {  // corseMatching, loop_detector.hpp:233-235
-    KFS_TRY(hipStreamSynchronize(k->stream));
+    LSLAM_TRY(hipStreamSynchronize(k->stream));
     return LSLAM_OK;
   }
   // ---- corseMatching: ICP of the new keyframe's surface cloud onto the candidates' (lslam_icp_align) -------------------------
@@ -485,7 +485,7 @@ int lslam_kfs_loop_match(lslam_kfs *k, int32_t n_cand, const int32_t *ids, const
   {
     const float4 *bp[2] = {k->local[0].p, k->local[1].p};
     const int bn[2] = {(int)k->n_local[0], (int)k->n_local[1]};
-    KFS_TRY(lslam::grid_bbox2(bp, bn, k->d_box.p, lo, hi, k->stream));
+    LSLAM_TRY(lslam::grid_bbox2(bp, bn, k->d_box.p, lo, hi, k->stream));
   }
   const float4 *in[4] = {k->local[0].p, k->local[1].p, nk.p[0], nk.p[1]};
   const size_t n_in[4] = {k->n_local[0], k->n_local[1], nk.n[0], nk.n[1]};
@@ -493,7 +493,7 @@ int lslam_kfs_loop_match(lslam_kfs *k, int32_t n_cand, const int32_t *ids, const
   const float leaf[4] = {0.2f, 0.4f, 0.2f, 0.4f};  // ScanMatch.cpp:29-30
   size_t m[4] = {0, 0, 0, 0};
   for (int c = 0; c < 4; ++c) {
-    KFS_TRY(k->filt[c].reserve(n_in[c] ? n_in[c] : 1));
+    LSLAM_TRY(k->filt[c].reserve(n_in[c] ? n_in[c] : 1));
     rc = lslam::voxel_grid_device(k->ctx, in[c], n_in[c], blo[c], bhi[c], leaf[c], k->filt[c].p, &m[c]);
     if (rc) {
       (void)hipStreamSynchronize(k->stream);
@@ -502,7 +502,7 @@ int lslam_kfs_loop_match(lslam_kfs *k, int32_t n_cand, const int32_t *ids, const
   }
   if (stage) *stage = LSLAM_KFS_MATCH_FAILED;
   if (m[0] < 50 || m[1] < 100) {  // ScanMatch.cpp:57-61, before the trees are built (lslam_scanmatch_full)
-    KFS_TRY(hipStreamSynchronize(k->stream));
+    LSLAM_TRY(hipStreamSynchronize(k->stream));
     if (stats) stats->status = LSLAM_TOO_FEW_REF;
     float tw[6];  // the mirrors hand the pose over as a twist and take it back as an isometry, also when nothing ran
     lslam_isometry_to_pose(guess, tw);
@@ -555,14 +555,14 @@ int lslam_keyframe_edge_information(lslam_kfs *k, int32_t n_ref, const int32_t *
   {
     const float4 *bp[2] = {k->local[0].p, k->local[1].p};
     const int bn[2] = {(int)k->n_local[0], (int)k->n_local[1]};
-    KFS_TRY(lslam::grid_bbox2(bp, bn, k->d_box.p, lo, hi, k->stream));
+    LSLAM_TRY(lslam::grid_bbox2(bp, bn, k->d_box.p, lo, hi, k->stream));
   }
   const float4 *in[4] = {k->local[0].p, k->local[1].p, nk.p[0], nk.p[1]};
   const size_t n_in[4] = {k->n_local[0], k->n_local[1], nk.n[0], nk.n[1]};
   const float *blo[4] = {lo[0], lo[1], nk.lo[0], nk.lo[1]}, *bhi[4] = {hi[0], hi[1], nk.hi[0], nk.hi[1]};
   size_t m[4] = {0, 0, 0, 0};
   for (int c = 0; c < 4; ++c) {
-    KFS_TRY(k->filt[c].reserve(n_in[c] ? n_in[c] : 1));
+    LSLAM_TRY(k->filt[c].reserve(n_in[c] ? n_in[c] : 1));
     rc = lslam::voxel_grid_device(k->ctx, in[c], n_in[c], blo[c], bhi[c], leaf[c], k->filt[c].p, &m[c]);
     if (rc) {
       (void)hipStreamSynchronize(k->stream);
@@ -570,7 +570,7 @@ int lslam_keyframe_edge_information(lslam_kfs *k, int32_t n_ref, const int32_t *
     }
   }
   if (m[0] == 0 || m[1] == 0) {  // nothing to match against: *out stays zero
-    KFS_TRY(hipStreamSynchronize(k->stream));
+    LSLAM_TRY(hipStreamSynchronize(k->stream));
     return LSLAM_OK;
   }
   for (int t = 0; t < 2; ++t) {
@@ -601,7 +601,7 @@ int lslam_kfs_scanmatch(lslam_kfs *k, int32_t id, float leaf_corner, float leaf_
   const float leaf[2] = {leaf_corner, leaf_surf};
   size_t m[2] = {0, 0};
   for (int t = 0; t < 2; ++t) {
-    KFS_TRY(k->filt[2 + t].reserve(kc.n[t] ? kc.n[t] : 1));
+    LSLAM_TRY(k->filt[2 + t].reserve(kc.n[t] ? kc.n[t] : 1));
     rc = lslam::voxel_grid_device(k->ctx, kc.p[t], kc.n[t], kc.lo[t], kc.hi[t], leaf[t], k->filt[2 + t].p, &m[t]);
     if (rc) {
       (void)hipStreamSynchronize(k->stream);

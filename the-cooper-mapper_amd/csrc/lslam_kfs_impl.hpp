@@ -10,17 +10,6 @@
 
 #include "lslam_internal.hpp"
 
-#define KFS_TRY(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      char _b[400];                                                                      \
-      snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      lslam::set_error(_b);                                                              \
-      return LSLAM_ERR_HIP;                                                              \
-    }                                                                                    \
-  } while (0)
-
 namespace lslam {
 
 struct Slab {
@@ -250,7 +239,7 @@ inline int check_kfs(lslam_kfs *k, const char *what) {
     set_error("keyframe store: its ctx was destroyed");
     return LSLAM_ERR_INVALID;
   }
-  KFS_TRY(hipSetDevice(ctx_device(k->ctx)));
+  LSLAM_TRY(hipSetDevice(ctx_device(k->ctx)));
   return LSLAM_OK;
 }
 

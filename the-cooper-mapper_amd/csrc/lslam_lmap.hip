@@ -32,58 +32,14 @@
 #include <deque>
 
 #include "lslam_internal.hpp"
+#include "lslam_pointgrid_dev.hpp"
 
 namespace {
-
-#define LM_TRY(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      char _b[400];                                                                      \
-      snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      lslam::set_error(_b);                                                              \
-      return LSLAM_ERR_HIP;                                                              \
-    }                                                                                    \
-  } while (0)
 
 constexpr size_t LM_MAX_POINTS = (size_t)1 << 24;      // per type (the compaction's block offsets are summed per block)
 constexpr size_t LM_DEFAULT_POINTS = (size_t)1 << 20;  // 30 m at 0.1 m per sweep: 300 frames x ~1000 corner / ~2500 surf points
 constexpr int32_t LM_DEFAULT_FRAMES = 4096;
 constexpr int LM_TILE = 1024;  // elements per workgroup of the compaction (4 rounds of 256)
-
-struct Rigid12 { float m[12]; };  // rows of [R | t], a kernel argument
-
-__device__ __forceinline__ uint32_t lm_ordered_u32(float f) {  // monotone map float -> uint32 (lslam_grid.hip's)
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-float lm_ordered_back(uint32_t o) {
-  const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-// mm[0..2] = max of ~ordered (the minimum), mm[3..5] = max of ordered, over the workgroup -> six atomics into res[1..6].
-// Called by every thread of a 256-thread workgroup.
-__device__ __forceinline__ void lm_box_reduce(uint32_t mm[6], bool any, uint32_t *res) {
-  if (!__syncthreads_or(any)) return;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-    for (int a = 0; a < 6; ++a) mm[a] = max(mm[a], (uint32_t)__shfl_xor((int)mm[a], d, 64));
-  __shared__ uint32_t part[4][6];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 6; ++a) part[wave][a] = mm[a];
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int a = threadIdx.x;
-    atomicMax(&res[1 + a], max(max(part[0][a], part[1][a]), max(part[2][a], part[3][a])));
-  }
-}
 
 // One frame's two clouds, both types in one launch (workgroups [0, nb0) work on type 0): p' = R p + t with the operation order of
 // fm_transform_kernel (pcl::transformPointCloud, transform_utils.h:601-614), into the staging of the add, and the clouds' boxes.
@@ -94,7 +50,7 @@ struct TransformArgs {
   int nb0;
   uint32_t *res;  // [2][8]
 };
-__global__ __launch_bounds__(256) void lm_transform_kernel(const TransformArgs a, const Rigid12 Tm) {
+__global__ __launch_bounds__(256) void lm_transform_kernel(const TransformArgs a, const lslam::Rigid12 Tm) {
   const int t = (int)blockIdx.x >= a.nb0 ? 1 : 0;
   const int i = ((int)blockIdx.x - (t ? a.nb0 : 0)) * 256 + (int)threadIdx.x;
   const bool in = i < a.n[t];
@@ -102,14 +58,9 @@ __global__ __launch_bounds__(256) void lm_transform_kernel(const TransformArgs a
   if (in) {
     const float4 q = lslam::rigid_transform_point(Tm.m, a.in[t][i]);
     a.out[t][i] = q;
-    const uint32_t o[3] = {lm_ordered_u32(q.x), lm_ordered_u32(q.y), lm_ordered_u32(q.z)};
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      mm[d] = ~o[d];
-      mm[3 + d] = o[d];
-    }
+    lslam::box_add(mm, q);
   }
-  lm_box_reduce(mm, in, a.res + 8 * t);
+  lslam::box_reduce(mm, in, a.res + 8 * t + 1);
 }
 
 // The commit of an add: the staged frame goes to the tail of its ring (wrapping) and, for the key-ordered window, behind the
@@ -162,17 +113,12 @@ __global__ __launch_bounds__(256) void lm_index_box_kernel(const float4 *filt, c
   bool any = false;
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     float4 p = filt[i];
-    const uint32_t o[3] = {lm_ordered_u32(p.x), lm_ordered_u32(p.y), lm_ordered_u32(p.z)};
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      mm[d] = max(mm[d], ~o[d]);
-      mm[3 + d] = max(mm[3 + d], o[d]);
-    }
+    lslam::box_add(mm, p);
     p.w = __builtin_bit_cast(float, i);
     map_pts[i] = p;
     any = true;
   }
-  lm_box_reduce(mm, any, res);
+  lslam::box_reduce(mm, any, res + 1);
 }
 
 // Eviction from the key-ordered array: a stable compaction of the entries whose frame is still in the queue (seq >= min_seq).
@@ -308,7 +254,7 @@ int check_lm(lslam_lmap *lm, const char *what) {
     lslam::set_error("local map: its ctx was destroyed");
     return LSLAM_ERR_INVALID;
   }
-  LM_TRY(hipSetDevice(lslam::ctx_device(lm->ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(lm->ctx)));
   return LSLAM_OK;
 }
 
@@ -337,9 +283,9 @@ void reset_state(lslam_lmap *lm) {  // LocalFeatureMap as constructed (the leave
 }
 
 int reserve_stage(lslam_lmap *lm, int t, size_t n, bool host) {
-  LM_TRY(lm->d_raw[t].reserve(n));
-  LM_TRY(lm->d_tf[t].reserve(n));
-  if (host) LM_TRY(lm->h_stage[t].reserve(n));
+  LSLAM_TRY(lm->d_raw[t].reserve(n));
+  LSLAM_TRY(lm->d_tf[t].reserve(n));
+  if (host) LSLAM_TRY(lm->h_stage[t].reserve(n));
   return LSLAM_OK;
 }
 
@@ -425,7 +371,7 @@ int add_impl(lslam_lmap *lm, const void *corner, size_t n_corner, const void *su
             h[i] = make_float4(v[0], v[1], v[2], w);
           }
         }
-        LM_TRY(hipMemcpyAsync(lm->d_raw[t].p, h, n_new[t] * sizeof(float4), hipMemcpyHostToDevice, s));
+        LSLAM_TRY(hipMemcpyAsync(lm->d_raw[t].p, h, n_new[t] * sizeof(float4), hipMemcpyHostToDevice, s));
       }
       ta.in[t] = host ? lm->d_raw[t].p : static_cast<const float4 *>(src[t]);
       ta.out[t] = lm->d_tf[t].p;
@@ -433,17 +379,17 @@ int add_impl(lslam_lmap *lm, const void *corner, size_t n_corner, const void *su
     }
     ta.nb0 = (int)((n_new[0] + 255) / 256);
     ta.res = lm->d_res.p;
-    Rigid12 Tm;
+    lslam::Rigid12 Tm;
     for (int k = 0; k < 12; ++k) Tm.m[k] = T_map[k];
-    LM_TRY(hipMemsetAsync(lm->d_res.p, 0, 16 * sizeof(uint32_t), s));
+    LSLAM_TRY(hipMemsetAsync(lm->d_res.p, 0, 16 * sizeof(uint32_t), s));
     hipLaunchKernelGGL(lm_transform_kernel, dim3((unsigned)(ta.nb0 + (int)((n_new[1] + 255) / 256))), dim3(256), 0, s, ta, Tm);
-    LM_TRY(hipGetLastError());
-    LM_TRY(hipMemcpyAsync(h_addbox(lm), lm->d_res.p, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    LM_TRY(hipStreamSynchronize(s));
+    LSLAM_TRY(hipGetLastError());
+    LSLAM_TRY(hipMemcpyAsync(h_addbox(lm), lm->d_res.p, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LSLAM_TRY(hipStreamSynchronize(s));
     for (int t = 0; t < 2; ++t)
       for (int a = 0; a < 3; ++a) {
-        fr.lo[t][a] = n_new[t] ? lm_ordered_back(~h_addbox(lm)[8 * t + 1 + a]) : INFINITY;
-        fr.hi[t][a] = n_new[t] ? lm_ordered_back(h_addbox(lm)[8 * t + 4 + a]) : -INFINITY;
+        fr.lo[t][a] = n_new[t] ? lslam::ordered_back(~h_addbox(lm)[8 * t + 1 + a]) : INFINITY;
+        fr.hi[t][a] = n_new[t] ? lslam::ordered_back(h_addbox(lm)[8 * t + 4 + a]) : -INFINITY;
         if (n_new[t] && !(std::isfinite(fr.lo[t][a]) && std::isfinite(fr.hi[t][a]))) {
           lslam::set_error("lslam_lmap_add_data_frame: a transformed point is not finite");
           return LSLAM_ERR_INVALID;
@@ -536,7 +482,7 @@ int index_box(lslam_lmap *lm, int t, const uint32_t *n_ptr) {
   const unsigned blocks = (unsigned)std::min<size_t>(512, (lm->live[t] + 255) / 256);
   hipLaunchKernelGGL(lm_index_box_kernel, dim3(blocks), dim3(256), 0, lm->stream, (const float4 *)lm->filt[t].p, n_ptr, (uint32_t)lm->cap,
                      lm->mapp[t].p, lm->d_res.p + 16 + 8 * t);
-  LM_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   return LSLAM_OK;
 }
 
@@ -545,7 +491,7 @@ int gather_ring(lslam_lmap *lm, int t, float4 *out) {
   if (!n) return LSLAM_OK;
   hipLaunchKernelGGL(lm_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lm->stream, (const float4 *)lm->ring[t].p,
                      (uint32_t)lm->cap, (uint32_t)(lm->head[t] % lm->cap), n, out);
-  LM_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   return LSLAM_OK;
 }
 
@@ -593,7 +539,7 @@ int ordered_filter(lslam_lmap *lm, int t, bool *took) {
     if (rc) return rc;
     size_t at = 0;
     for (const LFrame &f : lm->frames) {  // (the fall-back path: one fill per frame)
-      if (f.count[t]) LM_TRY(hipMemsetD32Async((hipDeviceptr_t)(lm->xq[t].p + at), (int)f.seq, f.count[t], s));
+      if (f.count[t]) LSLAM_TRY(hipMemsetD32Async((hipDeviceptr_t)(lm->xq[t].p + at), (int)f.seq, f.count[t], s));
       at += f.count[t];
     }
     lm->nx[t] = lm->live[t];
@@ -606,7 +552,7 @@ int ordered_filter(lslam_lmap *lm, int t, bool *took) {
     hipLaunchKernelGGL(lm_live_count_kernel, dim3(tiles), dim3(256), 0, s, (const uint32_t *)lm->xq[t].p, n, min_seq, lm->tile_count.p);
     hipLaunchKernelGGL(lm_compact_kernel, dim3(tiles), dim3(256), 0, s, (const float4 *)lm->xs[t].p, (const uint32_t *)lm->xq[t].p, n, min_seq,
                        (const int32_t *)lm->tile_count.p, lm->xs_alt[t].p, lm->xq_alt[t].p, (uint32_t)lm->cap);
-    LM_TRY(hipGetLastError());
+    LSLAM_TRY(hipGetLastError());
     std::swap(lm->xs[t], lm->xs_alt[t]);
     std::swap(lm->xq[t], lm->xq_alt[t]);
     size_t sorted_live = 0;
@@ -625,7 +571,7 @@ int ordered_filter(lslam_lmap *lm, int t, bool *took) {
   const int n = (int)lm->nx[t];
   hipLaunchKernelGGL(lm_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float4 *)lm->xs[t].p, (const uint32_t *)lm->xq[t].p,
                      order, n, lm->xs_alt[t].p, lm->xq_alt[t].p);
-  LM_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   std::swap(lm->xs[t], lm->xs_alt[t]);
   std::swap(lm->xq[t], lm->xq_alt[t]);
   lm->nx_sorted[t] = lm->nx[t];
@@ -641,7 +587,7 @@ int ensure_surround(lslam_lmap *lm) {
   bool any = false, ordered[2] = {false, false};
   uint32_t *h = h_surres(lm);
   for (int k = 0; k < 16; ++k) h[k] = 0u;
-  LM_TRY(hipMemsetAsync(lm->d_res.p + 16, 0, 16 * sizeof(uint32_t), s));
+  LSLAM_TRY(hipMemsetAsync(lm->d_res.p + 16, 0, 16 * sizeof(uint32_t), s));
   for (int t = 0; t < 2; ++t) {
     if (!lm->live[t]) continue;
     int rc = LSLAM_OK;
@@ -655,8 +601,8 @@ int ensure_surround(lslam_lmap *lm) {
     any = true;
   }
   if (any) {
-    LM_TRY(hipMemcpyAsync(h, lm->d_res.p + 16, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    LM_TRY(hipStreamSynchronize(s));
+    LSLAM_TRY(hipMemcpyAsync(h, lm->d_res.p + 16, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LSLAM_TRY(hipStreamSynchronize(s));
     for (int t = 0; t < 2; ++t) {
       if (!lm->live[t]) continue;
       const uint32_t *done = done_words(lm, t);
@@ -664,20 +610,17 @@ int ensure_surround(lslam_lmap *lm) {
         // the key did not hold the points after all, or the ordered array was not in order: the blocking full re-filter
         // decides, and the ordered array is rebuilt from the ring at the next sweep
         if (ordered[t]) lm->x_valid[t] = false;
-        LM_TRY(hipMemsetAsync(lm->d_res.p + 16 + 8 * t, 0, 8 * sizeof(uint32_t), s));
+        LSLAM_TRY(hipMemsetAsync(lm->d_res.p + 16 + 8 * t, 0, 8 * sizeof(uint32_t), s));
         const int rc = refilter(lm, t, true);
         if (rc) return rc == LSLAM_ERR_HIP ? fail_reset(lm, rc) : rc;
-        LM_TRY(hipMemcpyAsync(h + 8 * t, lm->d_res.p + 16 + 8 * t, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        LM_TRY(hipStreamSynchronize(s));
+        LSLAM_TRY(hipMemcpyAsync(h + 8 * t, lm->d_res.p + 16 + 8 * t, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        LSLAM_TRY(hipStreamSynchronize(s));
       }
     }
   }
   for (int t = 0; t < 2; ++t) {
     lm->n_sur[t] = lm->live[t] ? h[8 * t] : 0;
-    for (int a = 0; a < 3; ++a) {
-      lm->sur_lo[t][a] = lm_ordered_back(~h[8 * t + 1 + a]);
-      lm->sur_hi[t][a] = lm_ordered_back(h[8 * t + 4 + a]);
-    }
+    lslam::box_back(h + 8 * t + 1, lm->sur_lo[t], lm->sur_hi[t]);
   }
   lm->sur_valid = true;
   return LSLAM_OK;
@@ -699,7 +642,7 @@ int lslam_lmap_create(lslam_ctx *ctx, size_t max_points_per_type, int32_t max_fr
     lslam::set_error("lslam_lmap_create: unknown or contradictory flags, negative max_frames, or max_points_per_type above 2^24");
     return LSLAM_ERR_INVALID;
   }
-  LM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   lslam_lmap *lm = new lslam_lmap();
   lm->ctx = ctx;
   lm->stream = lslam::ctx_stream(ctx);
@@ -824,11 +767,11 @@ int lslam_lmap_get_surround(lslam_lmap *lm, float *corner_xyzi, size_t cap_c, si
       return LSLAM_ERR_INVALID;
     }
     if (lm->n_sur[t]) {
-      LM_TRY(hipMemcpyAsync(dst[t], lm->filt[t].p, lm->n_sur[t] * sizeof(float4), hipMemcpyDeviceToHost, lm->stream));
+      LSLAM_TRY(hipMemcpyAsync(dst[t], lm->filt[t].p, lm->n_sur[t] * sizeof(float4), hipMemcpyDeviceToHost, lm->stream));
       any = true;
     }
   }
-  if (any) LM_TRY(hipStreamSynchronize(lm->stream));
+  if (any) LSLAM_TRY(hipStreamSynchronize(lm->stream));
   return LSLAM_OK;
 }
 
@@ -867,10 +810,10 @@ int lslam_lmap_get_frames(lslam_lmap *lm, int32_t cap_frames, int32_t *n_frames,
     if (!dst[t] || !lm->live[t]) continue;
     rc = gather_ring(lm, t, lm->gath[t].p);
     if (rc) return rc;
-    LM_TRY(hipMemcpyAsync(dst[t], lm->gath[t].p, lm->live[t] * sizeof(float4), hipMemcpyDeviceToHost, lm->stream));
+    LSLAM_TRY(hipMemcpyAsync(dst[t], lm->gath[t].p, lm->live[t] * sizeof(float4), hipMemcpyDeviceToHost, lm->stream));
     any = true;
   }
-  if (any) LM_TRY(hipStreamSynchronize(lm->stream));
+  if (any) LSLAM_TRY(hipStreamSynchronize(lm->stream));
   return LSLAM_OK;
 }
 
@@ -886,7 +829,7 @@ int lslam_lmap_stats(lslam_lmap *lm, int64_t *merged, int64_t *resorted, int64_t
 int lslam_lmap_clear(lslam_lmap *lm) {
   const int rc = check_lm(lm, "lslam_lmap_clear");
   if (rc) return rc;
-  LM_TRY(hipStreamSynchronize(lm->stream));
+  LSLAM_TRY(hipStreamSynchronize(lm->stream));
   reset_state(lm);
   return LSLAM_OK;
 }

@@ -3,10 +3,9 @@
 // specification; tests/map_quality_ref.py restates it in numpy.
 //
 // Shape of the work.  The sums are integers (units of 2^-16 m), so any order of summation gives the same bits.
-//   mq_box / mq_key / radix sort / mq_gather   both clouds sorted by the key of their cell in ONE grid over the surface's
-//                                               bounding box, cell = radius * (1 + 1/1024); non-finite points sort behind.  A
-//                                               cell's range is found by binary search in the sorted keys: memory by the
-//                                               points, never by the box
+//   box_kernel / sg_key_kernel / radix sort /  both clouds sorted by the key of their cell in ONE grid over the surface's
+//   sg_gather_kernel                            bounding box, cell = radius * (1 + 1/1024); non-finite points sort behind: the
+//                                               sorted search grid of lslam_pointgrid_dev.hpp, shared with the survey extractor
 //   mq_probe_kernel                            one lane per query, in cell order (neighbouring lanes walk the same rows): the
 //                                               nine rows of three cells around the query, ten integer sums
 //   mq_tail_kernel                             one lane per query: the fp64 covariance, the Jacobi sweeps, three logarithms;
@@ -27,126 +26,28 @@
 #include <string>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include "../../include/lslam_c.h"
 #include "lslam_internal.hpp"
 #include "lslam_jacobi_dev.hpp"
 #include "lslam_kfs_impl.hpp"
+#include "lslam_pointgrid_dev.hpp"
 
 namespace {
 
-#define MQ_TRY(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      char _b[400];                                                                      \
-      snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      lslam::set_error(_b);                                                              \
-      return LSLAM_ERR_HIP;                                                              \
-    }                                                                                    \
-  } while (0)
-#define MQ_RC(expr)                  \
-  do {                               \
-    const int _rc = (expr);          \
-    if (_rc != LSLAM_OK) return _rc; \
-  } while (0)
-
 using lslam::DevBuf;
+using lslam::SGrid;
 
 constexpr int MQ_BLOCK = 256;
 constexpr size_t MQ_MAX_POINTS = (size_t)1 << 25;
-constexpr double GRID_CELL_PAD = 1.0 + 1.0 / 1024.0;  // as the survey extractor's radius grid: the fp32 test passes no |dx| a thousandth above r
 constexpr double ENTROPY_CONST = 4.2568155996140185;  // 1.5 * ln(2 pi e)
 constexpr int NSUM = 9;
 constexpr int NAGG = 6;  // n_defined, n_sparse, sum_entropy_q32, sum_plane_var_q30, sum_neighbors, max_neighbors
 
 inline dim3 blocks_for(size_t n) { return dim3((unsigned)((n + MQ_BLOCK - 1) / MQ_BLOCK)); }
 
-// ---- the grid --------------------------------------------------------------------------------------------------------------
-// Cell coordinate along axis d: floor(((double)x - lo) / cell) clamped into the grid -- monotone, so two coordinates closer than
-// `cell` land in the same or in adjacent cells, also a query's that lies outside the surface's box.
-struct MGrid {
-  double lo[3];
-  double cell;
-  int dim[3];
-};
-__device__ __forceinline__ int mq_cell(const MGrid &g, float x, int d) {
-  const double t = floor(((double)x - g.lo[d]) / g.cell);
-  if (!(t > 0.0)) return 0;
-  if (t >= (double)g.dim[d]) return g.dim[d] - 1;
-  return (int)t;
-}
-__device__ __forceinline__ uint64_t mq_key(const MGrid &g, int x, int y, int z) {
-  return (uint64_t)x + (uint64_t)g.dim[0] * ((uint64_t)y + (uint64_t)g.dim[1] * (uint64_t)z);
-}
-__device__ __forceinline__ bool mq_finite(const float4 &p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
-
-__device__ __forceinline__ uint32_t f2ord(float f) {  // order-preserving unsigned image of a float
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float ord2f(uint32_t u) {
-  const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-  float f;
-  std::memcpy(&f, &b, 4);
-  return f;
-}
-
-// box[0..2] min, [3..5] max (ordered words), box[6] the count, over the finite points
-__global__ __launch_bounds__(MQ_BLOCK) void mq_box_kernel(const float4 *pts, int n, uint32_t *box) {
-  const int i = blockIdx.x * MQ_BLOCK + threadIdx.x;
-  uint32_t lo[3] = {~0u, ~0u, ~0u}, hi[3] = {0u, 0u, 0u};
-  bool ok = false;
-  if (i < n) {
-    const float4 p = pts[i];
-    ok = mq_finite(p);
-    if (ok) {
-      lo[0] = hi[0] = f2ord(p.x);
-      lo[1] = hi[1] = f2ord(p.y);
-      lo[2] = hi[2] = f2ord(p.z);
-    }
-  }
-  const unsigned long long live = __ballot(ok);
-#pragma unroll
-  for (int d = 0; d < 3; ++d)
-    for (int m = 32; m > 0; m >>= 1) {
-      lo[d] = min(lo[d], (uint32_t)__shfl_xor((int)lo[d], m, 64));
-      hi[d] = max(hi[d], (uint32_t)__shfl_xor((int)hi[d], m, 64));
-    }
-  if ((threadIdx.x & 63) == 0 && live) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      atomicMin(box + d, lo[d]);
-      atomicMax(box + 3 + d, hi[d]);
-    }
-    atomicAdd(box + 6, (uint32_t)__popcll(live));
-  }
-}
-
-// key of every point's cell; a non-finite point gets `behind`, a key above every cell's
-__global__ __launch_bounds__(MQ_BLOCK) void mq_key_kernel(const float4 *pts, int n, MGrid g, uint64_t behind, uint64_t *keys, uint32_t *idx) {
-  const int i = blockIdx.x * MQ_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const float4 p = pts[i];
-  keys[i] = mq_finite(p) ? mq_key(g, mq_cell(g, p.x, 0), mq_cell(g, p.y, 1), mq_cell(g, p.z, 2)) : behind;
-  idx[i] = (uint32_t)i;
-}
-__global__ __launch_bounds__(MQ_BLOCK) void mq_gather_kernel(const float4 *pts, const uint32_t *idx, int n, float4 *out) {
-  const int i = blockIdx.x * MQ_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t j = idx[i];
-  const float4 p = pts[j];
-  out[i] = make_float4(p.x, p.y, p.z, __uint_as_float(j));
-}
-
 // ---- the neighbourhood sums --------------------------------------------------------------------------------------------------
 struct ProbeArgs {
-  MGrid g;
-  const uint64_t *skeys;  // [ns] ascending cell keys of the finite surface points
-  const float4 *spts;     // [ns] ... the points in that order
-  int ns;
+  SGrid g;                // the finite surface points in cell order
   const float4 *qpts;     // [nq] finite queries in key order
   int nq;
   float r2;
@@ -154,14 +55,6 @@ struct ProbeArgs {
   long long *sums;        // [NSUM][stride]
   size_t stride;
 };
-__device__ __forceinline__ int mq_lower(const uint64_t *keys, int n, uint64_t key) {  // first position with keys[pos] >= key
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 __device__ __forceinline__ long long shfl_xor_ll(long long v, int m) {
   const int lo = __shfl_xor((int)(v & 0xffffffffll), m, 64), hi = __shfl_xor((int)(v >> 32), m, 64);
   return (long long)(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo);
@@ -171,26 +64,19 @@ __global__ __launch_bounds__(MQ_BLOCK) void mq_probe_kernel(const ProbeArgs a) {
   const int i = blockIdx.x * MQ_BLOCK + threadIdx.x;
   if (i >= a.nq) return;
   const float4 q = a.qpts[i];
-  const int cx = mq_cell(a.g, q.x, 0), cy = mq_cell(a.g, q.y, 1), cz = mq_cell(a.g, q.z, 2);
-  const int x0 = max(cx - 1, 0), x1 = min(cx + 1, a.g.dim[0] - 1);
   int k = 0;
   long long s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, s7 = 0, s8 = 0;
-  for (int z = max(cz - 1, 0); z <= min(cz + 1, a.g.dim[2] - 1); ++z)
-    for (int y = max(cy - 1, 0); y <= min(cy + 1, a.g.dim[1] - 1); ++y) {
-      const int first = mq_lower(a.skeys, a.ns, mq_key(a.g, x0, y, z)), last = mq_lower(a.skeys, a.ns, mq_key(a.g, x1, y, z) + 1);
-      for (int e = first; e < last; ++e) {
-        const float4 p = a.spts[e];
-        const float dx = __fsub_rn(p.x, q.x), dy = __fsub_rn(p.y, q.y), dz = __fsub_rn(p.z, q.z);
-        const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-        if (!(d2 < a.r2)) continue;
-        const int X = (int)rint(((double)p.x - (double)q.x) * 65536.0), Y = (int)rint(((double)p.y - (double)q.y) * 65536.0),
-                  Z = (int)rint(((double)p.z - (double)q.z) * 65536.0);
-        ++k;
-        s0 += X; s1 += Y; s2 += Z;
-        s3 += (long long)X * X; s4 += (long long)X * Y; s5 += (long long)X * Z;
-        s6 += (long long)Y * Y; s7 += (long long)Y * Z; s8 += (long long)Z * Z;
-      }
-    }
+  lslam::sg_probe27(a.g, q, [&](const float4 &p) {
+    const float dx = __fsub_rn(p.x, q.x), dy = __fsub_rn(p.y, q.y), dz = __fsub_rn(p.z, q.z);
+    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    if (!(d2 < a.r2)) return;
+    const int X = (int)rint(((double)p.x - (double)q.x) * 65536.0), Y = (int)rint(((double)p.y - (double)q.y) * 65536.0),
+              Z = (int)rint(((double)p.z - (double)q.z) * 65536.0);
+    ++k;
+    s0 += X; s1 += Y; s2 += Z;
+    s3 += (long long)X * X; s4 += (long long)X * Y; s5 += (long long)X * Z;
+    s6 += (long long)Y * Y; s7 += (long long)Y * Z; s8 += (long long)Z * Z;
+  });
   a.count[i] = k;
   a.sums[i] = s0; a.sums[a.stride + i] = s1; a.sums[2 * a.stride + i] = s2;
   a.sums[3 * a.stride + i] = s3; a.sums[4 * a.stride + i] = s4; a.sums[5 * a.stride + i] = s5;
@@ -229,11 +115,10 @@ __global__ __launch_bounds__(MQ_BLOCK) void mq_tail_kernel(const TailArgs a) {
       const double mx = sx / K, my = sy / K, mz = sz / K;
       double a00 = sxx / K - mx * mx, a01 = sxy / K - mx * my, a02 = sxz / K - mx * mz;
       double a11 = syy / K - my * my, a12 = syz / K - my * mz, a22 = szz / K - mz * mz;
-      double v0[3] = {1.0, 0.0, 0.0}, v1[3] = {0.0, 1.0, 0.0}, v2[3] = {0.0, 0.0, 1.0};  // (the vectors are not used: dead code)
-      for (int it = 0; it < lslam::JACOBI_SWEEPS; ++it) {
-        lslam::sv_rotate(a00, a11, a01, a02, a12, v0, v1);
-        lslam::sv_rotate(a00, a22, a02, a01, a12, v0, v2);
-        lslam::sv_rotate(a11, a22, a12, a01, a02, v1, v2);
+      for (int it = 0; it < lslam::JACOBI_SWEEPS; ++it) {  // (the eigenvalues alone: no vectors)
+        lslam::sv_rotate(a00, a11, a01, a02, a12);
+        lslam::sv_rotate(a00, a22, a02, a01, a12);
+        lslam::sv_rotate(a11, a22, a12, a01, a02);
       }
       l0 = a00; l1 = a11; l2 = a22;
       if (l1 < l0) { const double t = l0; l0 = l1; l1 = t; }
@@ -341,15 +226,12 @@ void empty_stats(lslam_mapq_stats *st) {
   st->mean_entropy = st->mean_plane_variance = st->mean_neighbors = std::numeric_limits<double>::quiet_NaN();
 }
 
-int sort_cloud(Scratch &w, SortBuf &b, hipStream_t s, const float4 *pts, size_t n, const MGrid &g, uint64_t behind, int end_bit) {
-  MQ_TRY(b.k0.reserve(n)); MQ_TRY(b.k1.reserve(n)); MQ_TRY(b.i0.reserve(n)); MQ_TRY(b.i1.reserve(n)); MQ_TRY(b.sorted.reserve(n));
-  hipLaunchKernelGGL(mq_key_kernel, blocks_for(n), dim3(MQ_BLOCK), 0, s, pts, (int)n, g, behind, b.k0.p, b.i0.p);
-  size_t bytes = 0;
-  MQ_TRY(rocprim::radix_sort_pairs(nullptr, bytes, b.k0.p, b.k1.p, b.i0.p, b.i1.p, n, 0u, (unsigned)end_bit, s));
-  MQ_TRY(w.tmp.reserve(bytes));
-  MQ_TRY(rocprim::radix_sort_pairs((void *)w.tmp.p, bytes, b.k0.p, b.k1.p, b.i0.p, b.i1.p, n, 0u, (unsigned)end_bit, s));
-  hipLaunchKernelGGL(mq_gather_kernel, blocks_for(n), dim3(MQ_BLOCK), 0, s, pts, b.i1.p, (int)n, b.sorted.p);
-  MQ_TRY(hipGetLastError());
+int sort_cloud(Scratch &w, SortBuf &b, hipStream_t s, const float4 *pts, size_t n, const SGrid &g, uint64_t behind, int end_bit) {
+  LSLAM_TRY(b.k0.reserve(n)); LSLAM_TRY(b.k1.reserve(n)); LSLAM_TRY(b.i0.reserve(n)); LSLAM_TRY(b.i1.reserve(n)); LSLAM_TRY(b.sorted.reserve(n));
+  hipLaunchKernelGGL(lslam::sg_key_kernel<true>, lslam::sg_blocks(n), dim3(lslam::SG_BLOCK), 0, s, pts, (int)n, g, behind, b.k0.p, b.i0.p);
+  LSLAM_TRY(lslam::sort_pairs(w.tmp, b.k0.p, b.k1.p, b.i0.p, b.i1.p, n, end_bit, s));
+  hipLaunchKernelGGL(lslam::sg_gather_kernel<>, lslam::sg_blocks(n), dim3(lslam::SG_BLOCK), 0, s, pts, b.i1.p, (int)n, b.sorted.p);
+  LSLAM_TRY(hipGetLastError());
   return LSLAM_OK;
 }
 
@@ -361,53 +243,44 @@ int run(lslam_ctx *ctx, const float4 *d_surface, size_t ns_all, const float4 *d_
   if (self) nq_all = ns_all;
   st->n_query = (int64_t)nq_all;
   if (ns_all >= MQ_MAX_POINTS || nq_all >= MQ_MAX_POINTS) return bad("map quality: 2^25 or more points in a cloud");
-  MQ_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = lslam::ctx_stream(ctx);
   Scratch &w = *lslam::ctx_slot<Scratch>(ctx, lslam::CTX_SLOT_MAPQ);
   for (hipEvent_t &e : w.ev)
-    if (!e) MQ_TRY(hipEventCreate(&e));
+    if (!e) LSLAM_TRY(hipEventCreate(&e));
   if (!nq_all) return LSLAM_OK;
   // the surface's bounding box and the finite counts of both clouds: one wait
-  uint32_t box[14] = {~0u, ~0u, ~0u, 0u, 0u, 0u, 0u, ~0u, ~0u, ~0u, 0u, 0u, 0u, 0u};
-  MQ_TRY(w.box.reserve(14));
-  MQ_TRY(hipMemcpyAsync(w.box.p, box, sizeof(box), hipMemcpyHostToDevice, s));
-  if (ns_all) hipLaunchKernelGGL(mq_box_kernel, blocks_for(ns_all), dim3(MQ_BLOCK), 0, s, d_surface, (int)ns_all, w.box.p);
-  if (!self) hipLaunchKernelGGL(mq_box_kernel, blocks_for(nq_all), dim3(MQ_BLOCK), 0, s, d_queries, (int)nq_all, w.box.p + 7);
-  MQ_TRY(hipMemcpyAsync(box, w.box.p, sizeof(box), hipMemcpyDeviceToHost, s));
-  MQ_TRY(hipStreamSynchronize(s));
+  uint32_t box[14] = {};  // per cloud: the six words of a box, the count
+  LSLAM_TRY(w.box.reserve(14));
+  LSLAM_TRY(hipMemcpyAsync(w.box.p, box, sizeof(box), hipMemcpyHostToDevice, s));
+  if (ns_all) hipLaunchKernelGGL(lslam::box_kernel<true>, lslam::box_blocks((int)ns_all), dim3(lslam::BOX_BLOCK), 0, s, d_surface, (int)ns_all, w.box.p);
+  if (!self) hipLaunchKernelGGL(lslam::box_kernel<true>, lslam::box_blocks((int)nq_all), dim3(lslam::BOX_BLOCK), 0, s, d_queries, (int)nq_all, w.box.p + 7);
+  LSLAM_TRY(hipMemcpyAsync(box, w.box.p, sizeof(box), hipMemcpyDeviceToHost, s));
+  LSLAM_TRY(hipStreamSynchronize(s));
   const size_t ns = box[6], nq = self ? ns : box[13];
   st->n_surface = (int64_t)ns;
   st->n_nonfinite = (int64_t)(nq_all - nq);
-  MGrid g{};
-  g.cell = (double)P.radius * GRID_CELL_PAD;
-  uint64_t cells = 1;
-  if (ns) {
-    double ext = 0.0;
-    for (int d = 0; d < 3; ++d) ext = std::max(ext, (double)ord2f(box[3 + d]) - (double)ord2f(box[d]));
-    g.cell = std::max(g.cell, ext / 1048576.0);  // at most 2^20 cells per axis: a key stays inside 60 bits
-  }
-  for (int d = 0; d < 3; ++d) {
-    g.lo[d] = ns ? (double)ord2f(box[d]) : 0.0;
-    g.dim[d] = ns ? (int)std::floor(((double)ord2f(box[3 + d]) - g.lo[d]) / g.cell) + 1 : 1;
-    cells *= (uint64_t)g.dim[d];
-  }
+  float lo[3] = {0.0f, 0.0f, 0.0f}, hi[3] = {0.0f, 0.0f, 0.0f};  // (no finite surface point: one cell)
+  if (ns) lslam::box_back(box, lo, hi);
+  SGrid g{};
+  uint64_t cells = 1;  // itself the key of the non-finite points
   int end_bit = 1;
-  while (end_bit < 64 && (cells >> end_bit)) ++end_bit;  // `cells` itself is the key of the non-finite points
+  lslam::sg_shape(lo, hi, (double)P.radius * lslam::GRID_CELL_PAD, &g, &cells, &end_bit);
   // both clouds sorted by cell
-  MQ_TRY(hipEventRecord(w.ev[0], s));
-  if (ns_all) MQ_RC(sort_cloud(w, w.s, s, d_surface, ns_all, g, cells, end_bit));
-  if (!self) MQ_RC(sort_cloud(w, w.q, s, d_queries, nq_all, g, cells, end_bit));
+  LSLAM_TRY(hipEventRecord(w.ev[0], s));
+  if (ns_all) LSLAM_RC(sort_cloud(w, w.s, s, d_surface, ns_all, g, cells, end_bit));
+  if (!self) LSLAM_RC(sort_cloud(w, w.q, s, d_queries, nq_all, g, cells, end_bit));
   SortBuf &qs = self ? w.s : w.q;
-  MQ_TRY(hipEventRecord(w.ev[1], s));
+  LSLAM_TRY(hipEventRecord(w.ev[1], s));
   // the sums
   const size_t stride = nq ? nq : 1;
-  MQ_TRY(w.count.reserve(stride)); MQ_TRY(w.sums.reserve((size_t)NSUM * stride));
+  LSLAM_TRY(w.count.reserve(stride)); LSLAM_TRY(w.sums.reserve((size_t)NSUM * stride));
   if (nq) {
     ProbeArgs a{};
     a.g = g;
-    a.skeys = w.s.k1.p;
-    a.spts = w.s.sorted.p;
-    a.ns = (int)ns;
+    a.g.keys = w.s.k1.p;
+    a.g.pts = w.s.sorted.p;
+    a.g.n = (int)ns;
     a.qpts = qs.sorted.p;
     a.nq = (int)nq;
     a.r2 = (float)((double)P.radius * (double)P.radius);
@@ -415,12 +288,12 @@ int run(lslam_ctx *ctx, const float4 *d_surface, size_t ns_all, const float4 *d_
     a.sums = w.sums.p;
     a.stride = stride;
     hipLaunchKernelGGL(mq_probe_kernel, blocks_for(nq), dim3(MQ_BLOCK), 0, s, a);
-    MQ_TRY(hipGetLastError());
+    LSLAM_TRY(hipGetLastError());
   }
-  MQ_TRY(hipEventRecord(w.ev[2], s));
+  LSLAM_TRY(hipEventRecord(w.ev[2], s));
   // the tail and the aggregates
   const int blocks = (int)((nq_all + MQ_BLOCK - 1) / MQ_BLOCK);
-  MQ_TRY(w.partials.reserve((size_t)blocks * NAGG)); MQ_TRY(w.agg.reserve(NAGG));
+  LSLAM_TRY(w.partials.reserve((size_t)blocks * NAGG)); LSLAM_TRY(w.agg.reserve(NAGG));
   TailArgs t{};
   t.qpts = qs.sorted.p;
   t.nq = (int)nq;
@@ -436,11 +309,11 @@ int run(lslam_ctx *ctx, const float4 *d_surface, size_t ns_all, const float4 *d_
   t.partials = w.partials.p;
   hipLaunchKernelGGL(mq_tail_kernel, dim3(blocks), dim3(MQ_BLOCK), 0, s, t);
   hipLaunchKernelGGL(mq_final_kernel, dim3(1), dim3(MQ_BLOCK), 0, s, w.partials.p, blocks, w.agg.p);
-  MQ_TRY(hipGetLastError());
-  MQ_TRY(hipEventRecord(w.ev[3], s));
+  LSLAM_TRY(hipGetLastError());
+  LSLAM_TRY(hipEventRecord(w.ev[3], s));
   long long agg[NAGG];
-  MQ_TRY(hipMemcpyAsync(agg, w.agg.p, sizeof(agg), hipMemcpyDeviceToHost, s));
-  MQ_TRY(hipStreamSynchronize(s));
+  LSLAM_TRY(hipMemcpyAsync(agg, w.agg.p, sizeof(agg), hipMemcpyDeviceToHost, s));
+  LSLAM_TRY(hipStreamSynchronize(s));
   st->n_defined = agg[0];
   st->n_sparse = agg[1];
   st->sum_entropy_q32 = agg[2];
@@ -454,7 +327,7 @@ int run(lslam_ctx *ctx, const float4 *d_surface, size_t ns_all, const float4 *d_
     st->mean_neighbors = (double)agg[4] / nd;
   }
   float *ms[3] = {&st->ms_sort, &st->ms_kernel, &st->ms_reduce};
-  for (int k = 0; k < 3; ++k) MQ_TRY(hipEventElapsedTime(ms[k], w.ev[k], w.ev[k + 1]));
+  for (int k = 0; k < 3; ++k) LSLAM_TRY(hipEventElapsedTime(ms[k], w.ev[k], w.ev[k + 1]));
   return LSLAM_OK;
 }
 
@@ -477,8 +350,8 @@ int upload(hipStream_t s, DevBuf<float4> &d, std::vector<float4> &h, const void 
     std::memcpy(v, b + i * stride, 12);
     h[i] = make_float4(v[0], v[1], v[2], 0.0f);
   }
-  MQ_TRY(d.reserve(n ? n : 1));
-  if (n) MQ_TRY(hipMemcpyAsync(d.p, h.data(), n * sizeof(float4), hipMemcpyHostToDevice, s));
+  LSLAM_TRY(d.reserve(n ? n : 1));
+  if (n) LSLAM_TRY(hipMemcpyAsync(d.p, h.data(), n * sizeof(float4), hipMemcpyHostToDevice, s));
   return LSLAM_OK;
 }
 
@@ -498,9 +371,9 @@ size_t lslam_sizeof_mapq_stats(void) { return sizeof(lslam_mapq_stats); }
 
 int lslam_mapq_eval_device(lslam_ctx *ctx, const float *d_surface, size_t n, const float *d_queries, size_t nq, const lslam_mapq_params *params,
                            lslam_mapq_stats *stats, double *d_lambda3, double *d_entropy, int32_t *d_count) {
-  MQ_RC(need_ctx(ctx, "lslam_mapq_eval_device"));
+  LSLAM_RC(need_ctx(ctx, "lslam_mapq_eval_device"));
   lslam_mapq_params P;
-  MQ_RC(check_params(params, &P));
+  LSLAM_RC(check_params(params, &P));
   if (!stats || (n && !d_surface)) return bad("lslam_mapq_eval_device: null stats, or a null surface with points");
   if (d_queries && !nq) {  // an empty query cloud of its own: nothing to evaluate
     empty_stats(stats);
@@ -511,9 +384,9 @@ int lslam_mapq_eval_device(lslam_ctx *ctx, const float *d_surface, size_t n, con
 
 int lslam_mapq_eval(lslam_ctx *ctx, const void *surface, size_t n, size_t stride_bytes, const void *queries, size_t nq, size_t qstride_bytes,
                     const lslam_mapq_params *params, lslam_mapq_stats *stats, double *out_lambda3, double *out_entropy, int32_t *out_count) {
-  MQ_RC(need_ctx(ctx, "lslam_mapq_eval"));
+  LSLAM_RC(need_ctx(ctx, "lslam_mapq_eval"));
   lslam_mapq_params P;
-  MQ_RC(check_params(params, &P));
+  LSLAM_RC(check_params(params, &P));
   if (!stats || (n && !surface)) return bad("lslam_mapq_eval: null stats, or a null surface with points");
   if (!stride_ok(stride_bytes) || (queries && !stride_ok(qstride_bytes))) return bad("lslam_mapq_eval: a stride under 12 bytes or no multiple of 4");
   if (n >= MQ_MAX_POINTS || (queries && nq >= MQ_MAX_POINTS)) return bad("map quality: 2^25 or more points in a cloud");
@@ -521,53 +394,53 @@ int lslam_mapq_eval(lslam_ctx *ctx, const void *surface, size_t n, size_t stride
     empty_stats(stats);
     return LSLAM_OK;
   }
-  MQ_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   hipStream_t s = lslam::ctx_stream(ctx);
   Scratch &w = *lslam::ctx_slot<Scratch>(ctx, lslam::CTX_SLOT_MAPQ);
   std::vector<float4> hs, hq;  // alive until run() has waited
-  MQ_RC(upload(s, w.up_s, hs, surface, n, stride_bytes));
-  if (queries) MQ_RC(upload(s, w.up_q, hq, queries, nq, qstride_bytes));
+  LSLAM_RC(upload(s, w.up_s, hs, surface, n, stride_bytes));
+  if (queries) LSLAM_RC(upload(s, w.up_q, hq, queries, nq, qstride_bytes));
   const size_t m = queries ? nq : n;
-  if (out_lambda3) MQ_TRY(w.l3.reserve(3 * m + 1));
-  if (out_entropy) MQ_TRY(w.h.reserve(m + 1));
-  if (out_count) MQ_TRY(w.ocount.reserve(m + 1));
+  if (out_lambda3) LSLAM_TRY(w.l3.reserve(3 * m + 1));
+  if (out_entropy) LSLAM_TRY(w.h.reserve(m + 1));
+  if (out_count) LSLAM_TRY(w.ocount.reserve(m + 1));
   int rc = run(ctx, w.up_s.p, n, queries ? w.up_q.p : nullptr, nq, P, stats, out_lambda3 ? w.l3.p : nullptr, out_entropy ? w.h.p : nullptr,
                out_count ? w.ocount.p : nullptr);
   if (rc != LSLAM_OK) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
-  if (m && out_lambda3) MQ_TRY(hipMemcpyAsync(out_lambda3, w.l3.p, 3 * m * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (m && out_entropy) MQ_TRY(hipMemcpyAsync(out_entropy, w.h.p, m * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (m && out_count) MQ_TRY(hipMemcpyAsync(out_count, w.ocount.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  MQ_TRY(hipStreamSynchronize(s));
+  if (m && out_lambda3) LSLAM_TRY(hipMemcpyAsync(out_lambda3, w.l3.p, 3 * m * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (m && out_entropy) LSLAM_TRY(hipMemcpyAsync(out_entropy, w.h.p, m * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (m && out_count) LSLAM_TRY(hipMemcpyAsync(out_count, w.ocount.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  LSLAM_TRY(hipStreamSynchronize(s));
   return LSLAM_OK;
 }
 
 int lslam_mapq_fmap(lslam_fmap *fm, int32_t which, const lslam_mapq_params *params, lslam_mapq_stats *stats) {
   lslam_mapq_params P;
-  MQ_RC(check_params(params, &P));
+  LSLAM_RC(check_params(params, &P));
   if (!stats || which < 0 || which > 1) return bad("lslam_mapq_fmap: null stats, or which outside {0, 1}");
   lslam::FmapView v{};
-  MQ_RC(lslam::fmap_view(fm, &v));  // refuses a null map; commits a pending add
+  LSLAM_RC(lslam::fmap_view(fm, &v));  // refuses a null map; commits a pending add
   return run(lslam::fmap_ctx(fm), v.pts[which], v.n[which], nullptr, 0, P, stats, nullptr, nullptr, nullptr);
 }
 
 int lslam_mapq_keyframes(lslam_kfs *kfs, int32_t n_ids, const int32_t *ids, const float *poses16, int32_t which, const lslam_mapq_params *params,
                          lslam_mapq_stats *stats) {
-  MQ_RC(lslam::check_kfs(kfs, "lslam_mapq_keyframes"));
+  LSLAM_RC(lslam::check_kfs(kfs, "lslam_mapq_keyframes"));
   lslam_mapq_params P;
-  MQ_RC(check_params(params, &P));
+  LSLAM_RC(check_params(params, &P));
   if (!stats || which < 0 || which > 1 || n_ids < 0 || (n_ids && (!ids || !poses16)))
     return bad("lslam_mapq_keyframes: null stats, which outside {0, 1}, or keyframes named without ids and poses");
   for (int32_t c = 0; c < n_ids; ++c) {
-    MQ_RC(lslam::check_id(kfs, "lslam_mapq_keyframes", ids[c]));
+    LSLAM_RC(lslam::check_id(kfs, "lslam_mapq_keyframes", ids[c]));
     for (int e = 0; e < 16; ++e)
       if (!std::isfinite(poses16[16 * (size_t)c + e])) return bad("lslam_mapq_keyframes: a pose that is not finite");
   }
   Scratch &w = *lslam::ctx_slot<Scratch>(kfs->ctx, lslam::CTX_SLOT_MAPQ);
   size_t total = 0;
-  MQ_RC(lslam::kfs_gather_posed(kfs, n_ids, ids, poses16, which, w.gathered, &total));
+  LSLAM_RC(lslam::kfs_gather_posed(kfs, n_ids, ids, poses16, which, w.gathered, &total));
   return run(kfs->ctx, w.gathered.p, total, nullptr, 0, P, stats, nullptr, nullptr, nullptr);
 }
 

@@ -355,17 +355,17 @@ int occ_launch_chunk(lslam_kfs *k, int32_t c0, int32_t c1, uint32_t *d_planes, u
   uint32_t most_words;
   occ_chunk_shape(o, c0, c1, &words, &most, &most_words);
   if (!most) return LSLAM_OK;  // no point: no ray, no bit
-  if (words) KFS_TRY(hipMemsetAsync(d_planes, 0, words * sizeof(uint32_t), k->stream));
+  if (words) LSLAM_TRY(hipMemsetAsync(d_planes, 0, words * sizeof(uint32_t), k->stream));
   const dim3 grid((unsigned)((most + OCC_BLOCK - 1) / OCC_BLOCK), (unsigned)(c1 - c0));
   hipLaunchKernelGGL(occ_ray_kernel, grid, dim3(OCC_BLOCK), 0, k->stream, o.d_jobs.p + c0, occ_shape(o), d_planes, d_stats);
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   if (!merge) return LSLAM_OK;
   ++o.ray_launches;
   if (!most_words) return LSLAM_OK;
   const size_t mb = ((size_t)most_words + OCC_BLOCK - 1) / OCC_BLOCK;
   hipLaunchKernelGGL(occ_merge_kernel, dim3((unsigned)(mb < 1024 ? mb : 1024), (unsigned)(c1 - c0)), dim3(OCC_BLOCK), 0, k->stream,
                      o.d_jobs.p + c0, d_planes, o.params.width, o.d_counts.p);
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   ++o.merge_launches;
   return LSLAM_OK;
 }
@@ -381,7 +381,7 @@ int occ_fresh_values(lslam_kfs *k) {
   const size_t n = o.cells(), nb = (n + OCC_BLOCK - 1) / OCC_BLOCK;
   hipLaunchKernelGGL(occ_values_kernel, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(OCC_BLOCK), 0, k->stream, o.d_counts.p, n,
                      (uint32_t)o.params.hit_weight, (uint32_t)o.params.min_observations, o.d_values.p);
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   ++o.value_launches;
   o.values_stale = false;
   return LSLAM_OK;
@@ -428,7 +428,7 @@ int lslam_occ_setup(lslam_kfs *k, const lslam_occ_params *params) {
   if (rc) return rc;
   OccState &o = k->occ;
   if (o.set && std::memcmp(&o.params, &p, sizeof(p)) == 0) return LSLAM_OK;
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   o.drop();
   o.params = p;
   o.scale = 256.0 / (double)p.resolution;
@@ -465,8 +465,8 @@ int lslam_occ_clear(lslam_kfs *k) {
   if (rc) return rc;
   OccState &o = k->occ;
   if (o.held()) {
-    KFS_TRY(hipMemsetAsync(o.d_counts.p, 0, o.cells() * sizeof(uint32_t), k->stream));
-    KFS_TRY(hipStreamSynchronize(k->stream));
+    LSLAM_TRY(hipMemsetAsync(o.d_counts.p, 0, o.cells() * sizeof(uint32_t), k->stream));
+    LSLAM_TRY(hipStreamSynchronize(k->stream));
   }
   o.zero_tallies();
   return LSLAM_OK;
@@ -517,10 +517,10 @@ int lslam_occ_integrate(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const f
   if (!n_ids) return LSLAM_OK;
 
   // the jobs, and every allocation, before anything is enqueued
-  KFS_TRY(o.h_jobs.reserve((size_t)n_ids));
-  KFS_TRY(o.d_jobs.reserve((size_t)n_ids));
-  KFS_TRY(o.d_stats.reserve(OCC_ST_N));
-  KFS_TRY(o.h_stats.reserve(OCC_ST_N));
+  LSLAM_TRY(o.h_jobs.reserve((size_t)n_ids));
+  LSLAM_TRY(o.d_jobs.reserve((size_t)n_ids));
+  LSLAM_TRY(o.d_stats.reserve(OCC_ST_N));
+  LSLAM_TRY(o.h_stats.reserve(OCC_ST_N));
   const lslam_occ_params &p = o.params;
   const int ia = p.up_axis == 1 ? 2 : 0, ib = p.up_axis == 1 ? 0 : 1;
   size_t scratch = 0;
@@ -556,20 +556,20 @@ int lslam_occ_integrate(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const f
     if (at > scratch) scratch = at;
   }
   o.last_ids = 0;
-  KFS_TRY(o.d_planes.reserve(scratch));
+  LSLAM_TRY(o.d_planes.reserve(scratch));
   rc = occ_ensure_grid(k);
   if (rc) return rc;
 
-  KFS_TRY(hipMemsetAsync(o.d_stats.p, 0, OCC_ST_N * sizeof(unsigned long long), k->stream));
-  KFS_TRY(hipMemcpyAsync(o.d_jobs.p, o.h_jobs.p, (size_t)n_ids * sizeof(OccJob), hipMemcpyHostToDevice, k->stream));
+  LSLAM_TRY(hipMemsetAsync(o.d_stats.p, 0, OCC_ST_N * sizeof(unsigned long long), k->stream));
+  LSLAM_TRY(hipMemcpyAsync(o.d_jobs.p, o.h_jobs.p, (size_t)n_ids * sizeof(OccJob), hipMemcpyHostToDevice, k->stream));
   o.n_integrated += n_ids;  // from here on the counts may have changed
   o.values_stale = true;
   for (int32_t c0 = 0; c0 < n_ids; c0 += OCC_CHUNK) {
     rc = occ_launch_chunk(k, c0, c0 + OCC_CHUNK < n_ids ? c0 + OCC_CHUNK : n_ids, o.d_planes.p, o.d_stats.p, true);
     if (rc) return occ_fail(k, rc);
   }
-  KFS_TRY(hipMemcpyAsync(o.h_stats.p, o.d_stats.p, OCC_ST_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, k->stream));
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipMemcpyAsync(o.h_stats.p, o.d_stats.p, OCC_ST_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   o.rays[1] += (int64_t)o.h_stats.p[OCC_ST_DROPPED];
   o.rays[2] += (int64_t)o.h_stats.p[OCC_ST_OBSTACLE];
   o.rays[3] += (int64_t)o.h_stats.p[OCC_ST_GROUND];
@@ -594,8 +594,8 @@ int lslam_occ_counts(lslam_kfs *k, uint32_t *out) {
   rc = occ_ensure_grid(k);
   if (rc) return rc;
   OccState &o = k->occ;
-  KFS_TRY(hipMemcpyAsync(out, o.d_counts.p, o.cells() * sizeof(uint32_t), hipMemcpyDeviceToHost, k->stream));
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipMemcpyAsync(out, o.d_counts.p, o.cells() * sizeof(uint32_t), hipMemcpyDeviceToHost, k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   return LSLAM_OK;
 }
 
@@ -611,8 +611,8 @@ int lslam_occ_values(lslam_kfs *k, int8_t *out) {
   rc = occ_fresh_values(k);
   if (rc) return occ_fail(k, rc);
   OccState &o = k->occ;
-  KFS_TRY(hipMemcpyAsync(out, o.d_values.p, o.cells(), hipMemcpyDeviceToHost, k->stream));
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipMemcpyAsync(out, o.d_values.p, o.cells(), hipMemcpyDeviceToHost, k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   return LSLAM_OK;
 }
 
@@ -625,7 +625,7 @@ int lslam_occ_view(lslam_kfs *k, const uint32_t **d_counts, const int8_t **d_val
     rc = occ_fresh_values(k);
     if (rc) return occ_fail(k, rc);
   }
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   if (d_counts) *d_counts = k->occ.d_counts.p;
   if (d_values) *d_values = k->occ.d_values.p;
   return LSLAM_OK;
@@ -684,9 +684,9 @@ int lslam_debug_occ_integrate(lslam_kfs *k, int32_t launches) {
     lslam::set_error("lslam_debug_occ_integrate: no lslam_occ_integrate call with keyframes has run last, or negative launches");
     return LSLAM_ERR_INVALID;
   }
-  KFS_TRY(o.d_planes_again.reserve(o.d_planes.cap));
-  KFS_TRY(o.d_stats_again.reserve(OCC_ST_N));
-  KFS_TRY(hipMemsetAsync(o.d_stats_again.p, 0, OCC_ST_N * sizeof(unsigned long long), k->stream));
+  LSLAM_TRY(o.d_planes_again.reserve(o.d_planes.cap));
+  LSLAM_TRY(o.d_stats_again.reserve(OCC_ST_N));
+  LSLAM_TRY(hipMemsetAsync(o.d_stats_again.p, 0, OCC_ST_N * sizeof(unsigned long long), k->stream));
   for (int32_t i = 0; i < launches; ++i)
     for (int32_t c0 = 0; c0 < o.last_ids; c0 += OCC_CHUNK) {
       rc = occ_launch_chunk(k, c0, c0 + OCC_CHUNK < o.last_ids ? c0 + OCC_CHUNK : o.last_ids, o.d_planes_again.p, o.d_stats_again.p, false);

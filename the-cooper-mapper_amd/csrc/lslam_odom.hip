@@ -41,17 +41,6 @@ int odometry_match_trees(lslam_ctx *ctx, const void *last_corner, size_t n_lc, c
 
 namespace {
 
-#define OD_TRY(expr)                                                                                           \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess) {                                                                                    \
-      char _b[256];                                                                                            \
-      snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);     \
-      lslam::set_error(_b);                                                                                    \
-      return LSLAM_ERR_HIP;                                                                                    \
-    }                                                                                                          \
-  } while (0)
-
 // ---- hashed cell grids -----------------------------------------------------------------------------------------------------
 constexpr int OH_BITS = 16;
 constexpr uint32_t OH_SIZE = 1u << OH_BITS;
@@ -940,11 +929,11 @@ uint32_t *h_flags_of(lslam_odom *od) { return od->h_state.p->flags; }
 int enqueue_build(lslam_odom *od, int to, const float4 *less_sharp, size_t n_ls, const float4 *less_flat, size_t n_lf, bool to_end,
                   bool gated) {
   Side &S = od->side[to];
-  OD_TRY(S.org[0].reserve(n_ls + 1));
-  OD_TRY(S.org[1].reserve(n_lf + 1));
+  LSLAM_TRY(S.org[0].reserve(n_ls + 1));
+  LSLAM_TRY(S.org[1].reserve(n_lf + 1));
   for (int l = 0; l < 2; ++l) {
-    OD_TRY(S.sorted[l].reserve(n_ls + 1));
-    OD_TRY(S.sorted[2 + l].reserve(n_lf + 1));
+    LSLAM_TRY(S.sorted[l].reserve(n_ls + 1));
+    LSLAM_TRY(S.sorted[2 + l].reserve(n_lf + 1));
   }
   const size_t n = n_ls + n_lf;
   S.n[0] = n_ls;
@@ -960,8 +949,8 @@ int enqueue_build(lslam_odom *od, int to, const float4 *less_sharp, size_t n_ls,
     lslam::set_error("a last cloud of more than 16 777 215 points");
     return LSLAM_ERR_INVALID;
   }
-  OD_TRY(hipMemsetAsync(S.hdr.p, 0, 8, od->stream));
-  OD_TRY(hipMemsetAsync(od->cnt.p, 0, 4 * (size_t)OH_SIZE * 4, od->stream));
+  LSLAM_TRY(hipMemsetAsync(S.hdr.p, 0, 8, od->stream));
+  LSLAM_TRY(hipMemsetAsync(od->cnt.p, 0, 4 * (size_t)OH_SIZE * 4, od->stream));
   pa.gate = (gated || to_end) ? od->d_state.p : nullptr;
   pa.to_end = to_end ? 1 : 0;
   // (an ungated move to the end still reads the pose from d_state: the caller has put it there and marked it done)
@@ -975,7 +964,7 @@ int enqueue_build(lslam_odom *od, int to, const float4 *less_sharp, size_t n_ls,
   for (int k = 0; k < 4; ++k) sa.sorted[k] = S.sorted[k].p;
   sa.gate = pa.gate;
   if (nb) hipLaunchKernelGGL(odom_scatter_kernel, dim3(nb), dim3(256), 0, od->stream, sa);
-  OD_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   return LSLAM_OK;
 }
 
@@ -993,8 +982,8 @@ int enqueue_tail(lslam_odom *od, const TailSpec &t, bool gated) {
   if (rc) return rc;
   if (t.copy_out) {
     const Side &S = od->side[t.to];
-    if (t.n_ls) OD_TRY(hipMemcpyAsync(od->h_last, S.org[0].p, t.n_ls * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
-    if (t.n_lf) OD_TRY(hipMemcpyAsync(od->h_last + t.n_ls, S.org[1].p, t.n_lf * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+    if (t.n_ls) LSLAM_TRY(hipMemcpyAsync(od->h_last, S.org[0].p, t.n_ls * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+    if (t.n_lf) LSLAM_TRY(hipMemcpyAsync(od->h_last + t.n_ls, S.org[1].p, t.n_lf * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
   }
   return LSLAM_OK;
 }
@@ -1012,7 +1001,7 @@ struct LoopSetup {
 int loop_setup(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, const float4 *flat, size_t n_flat, LoopSetup &L) {
   const Side &S = od->side[from];
   const size_t nq = n_sharp + n_flat;
-  OD_TRY(od->ind.reserve(3 * nq + 1));
+  LSLAM_TRY(od->ind.reserve(3 * nq + 1));
   OdomArgs &oa = L.oa;
   oa.oc = S.org[0].p;
   oa.os = S.org[1].p;
@@ -1029,7 +1018,7 @@ int loop_setup(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   oa.coeff = nullptr;
   oa.mode = 2;
   oa.state = od->d_state.p;
-  OD_TRY(od->partials.reserve((size_t)(oa.nb_total ? oa.nb_total : 1) * NCOL));
+  LSLAM_TRY(od->partials.reserve((size_t)(oa.nb_total ? oa.nb_total : 1) * NCOL));
   oa.partials = od->partials.p;
   SearchArgs &sa = L.sa;
   for (int c = 0; c < 2; ++c) {
@@ -1050,8 +1039,8 @@ int loop_setup(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   sa.literal_window = od->literal_window;
   sa.dbg = nullptr;
   if (od->dbg_on) {
-    OD_TRY(od->dbg.reserve(4 * nq + 4));
-    OD_TRY(hipMemsetAsync(od->dbg.p, 0, (4 * nq + 4) * 4, od->stream));
+    LSLAM_TRY(od->dbg.reserve(4 * nq + 4));
+    LSLAM_TRY(hipMemsetAsync(od->dbg.p, 0, (4 * nq + 4) * 4, od->stream));
     sa.dbg = od->dbg.p;
     od->dbg_n = nq;
   }
@@ -1060,7 +1049,7 @@ int loop_setup(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
     ProbBlocks *pb = &od->h_state.p->probs;  // pinned
     pb->first_block = 0;
     pb->n_blocks = oa.nb_total;
-    OD_TRY(hipMemcpyAsync(od->d_probs.p, pb, sizeof(ProbBlocks), hipMemcpyHostToDevice, od->stream));
+    LSLAM_TRY(hipMemcpyAsync(od->d_probs.p, pb, sizeof(ProbBlocks), hipMemcpyHostToDevice, od->stream));
     od->nb_on_device = oa.nb_total;
   }
   SolveArgs &so = L.so;
@@ -1094,9 +1083,9 @@ int loop_setup(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
 // the persistent kernel's exchange slots, every generation filled with the sentinel; enqueued in front of each of its launches
 int loop_slots(lslam_odom *od, LoopSetup &L) {
   const size_t n = (size_t)OGN_GENERATIONS * L.oa.nb_total * NCOL;
-  OD_TRY(od->slots.reserve(n));
+  LSLAM_TRY(od->slots.reserve(n));
   L.ga.slots = od->slots.p;
-  OD_TRY(hipMemsetD32Async((hipDeviceptr_t)od->slots.p, (int)OGN_SENT, n, od->stream));
+  LSLAM_TRY(hipMemsetD32Async((hipDeviceptr_t)od->slots.p, (int)OGN_SENT, n, od->stream));
   return LSLAM_OK;
 }
 
@@ -1108,8 +1097,8 @@ int loop_state_up(lslam_odom *od, const float pose[6], int32_t loop_iter, bool d
   pose_to_Rt_sc(pose, hs->R, hs->t, hs->sc, HostSinCosF());
   hs->loop_iter = loop_iter;
   hs->done = done ? 1 : 0;
-  OD_TRY(hipMemcpyAsync(od->d_state.p, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
-  OD_TRY(hipMemsetAsync(od->d_flags.p, 0, 64, od->stream));
+  LSLAM_TRY(hipMemcpyAsync(od->d_state.p, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
+  LSLAM_TRY(hipMemsetAsync(od->d_flags.p, 0, 64, od->stream));
   return LSLAM_OK;
 }
 
@@ -1130,8 +1119,8 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   const int max_it = od->max_it;
   rc0 = loop_state_up(od, pose, 0, max_it == 0 || oa.nb_total == 0);
   if (rc0) return rc0;
-  if (nq) OD_TRY(hipMemsetAsync(od->ind.p, 0xFF, 3 * nq * sizeof(int32_t), od->stream));
-  OD_TRY(hipEventRecord(od->ev0, od->stream));
+  if (nq) LSLAM_TRY(hipMemsetAsync(od->ind.p, 0xFF, 3 * nq * sizeof(int32_t), od->stream));
+  LSLAM_TRY(hipEventRecord(od->ev0, od->stream));
   // loop_iter advances by one per solve until the loop is done, so the host knows which iterations refresh the
   // correspondences (every fifth, :357,:423); launches behind the end of the loop exit at once
   int launched = 0, n_search = 0;
@@ -1155,13 +1144,13 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
       }
       seg_done += batch;
       launched = seg_done * 5 < max_it ? seg_done * 5 : max_it;
-      OD_TRY(hipGetLastError());
-      OD_TRY(hipEventRecord(od->ev1, od->stream));
+      LSLAM_TRY(hipGetLastError());
+      LSLAM_TRY(hipEventRecord(od->ev1, od->stream));
       int rc = enqueue_tail(od, tail, true);
       if (rc) return rc;
-      OD_TRY(hipMemcpyAsync(hs, od->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
-      OD_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags.p, 64, hipMemcpyDeviceToHost, od->stream));
-      OD_TRY(hipStreamSynchronize(od->stream));
+      LSLAM_TRY(hipMemcpyAsync(hs, od->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
+      LSLAM_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags.p, 64, hipMemcpyDeviceToHost, od->stream));
+      LSLAM_TRY(hipStreamSynchronize(od->stream));
       if (h_flags_of(od)[1] != 0u) {  // an exchange gave up: this match again by launches, and launches from now on
         od->persistent_ok = false;
         return match_loop(od, from, sharp, n_sharp, flat, n_flat, pose, st, searches, tie, tail);
@@ -1181,16 +1170,16 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
         hipLaunchKernelGGL(odom_search_kernel, dim3((unsigned)nq), dim3(64), 0, od->stream, sa);
         ++n_search;
       }
-      OD_TRY(launch_odom_sweep(oa, od->stream));
-      OD_TRY(launch_solve(so, od->stream));
+      LSLAM_TRY(launch_odom_sweep(oa, od->stream));
+      LSLAM_TRY(launch_solve(so, od->stream));
     }
     launched += batch;
-    OD_TRY(hipEventRecord(od->ev1, od->stream));
+    LSLAM_TRY(hipEventRecord(od->ev1, od->stream));
     int rc = enqueue_tail(od, tail, true);
     if (rc) return rc;
-    OD_TRY(hipMemcpyAsync(hs, od->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
-    OD_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags.p, 64, hipMemcpyDeviceToHost, od->stream));
-    OD_TRY(hipStreamSynchronize(od->stream));
+    LSLAM_TRY(hipMemcpyAsync(hs, od->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
+    LSLAM_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags.p, 64, hipMemcpyDeviceToHost, od->stream));
+    LSLAM_TRY(hipStreamSynchronize(od->stream));
     if (hs->done || launched >= max_it) break;
     batch = 10;
   }
@@ -1212,7 +1201,7 @@ int match_loop(lslam_odom *od, int from, const float4 *sharp, size_t n_sharp, co
   st.delta_r = g.delta_r;
   st.delta_t = g.delta_t;
   st.point_residuals = (int64_t)g.sweeps * (int64_t)nq;
-  OD_TRY(hipEventElapsedTime(&st.gpu_ms_total, od->ev0, od->ev1));
+  LSLAM_TRY(hipEventElapsedTime(&st.gpu_ms_total, od->ev0, od->ev1));
   st.status = g.converged ? LSLAM_OK : LSLAM_NOT_CONVERGED;
   if (searches) *searches = (g.loop_iter + 4) / 5 < n_search ? (g.loop_iter + 4) / 5 : n_search;
   *tie = (h_flags_of(od)[0] & 1u) != 0u;
@@ -1239,13 +1228,13 @@ void pack_xyzi(const void *src, size_t n, size_t stride_bytes, float4 *out) {
 int upload_lists(hipStream_t s, lslam_fset *fs, float4 *stage, const void *const src[4], const size_t n[4], size_t stride_bytes) {
   size_t most = 0;
   for (int k = 0; k < 4; ++k) most = n[k] > most ? n[k] : most;
-  OD_TRY(lslam::fset_reserve(fs, most));
+  LSLAM_TRY(lslam::fset_reserve(fs, most));
   size_t off = 0;
   for (int k = 0; k < 4; ++k) {
     fs->counts[k] = n[k];
     if (!n[k]) continue;
     pack_xyzi(src[k], n[k], stride_bytes, stage + off);
-    OD_TRY(hipMemcpyAsync(fs->list(k), stage + off, n[k] * sizeof(float4), hipMemcpyHostToDevice, s));
+    LSLAM_TRY(hipMemcpyAsync(fs->list(k), stage + off, n[k] * sizeof(float4), hipMemcpyHostToDevice, s));
     off += n[k];
   }
   return LSLAM_OK;
@@ -1316,16 +1305,16 @@ int lslam_fset_upload(lslam_ctx *ctx, lslam_fset *fs, const void *sharp, size_t 
     lslam::set_error("bad feature-set upload arguments (clouds need x,y,z,intensity: stride >= 16)");
     return LSLAM_ERR_INVALID;
   }
-  OD_TRY(hipSetDevice(fs->device));
+  LSLAM_TRY(hipSetDevice(fs->device));
   const void *src[4] = {sharp, less_sharp, flat, less_flat};
   const size_t n[4] = {n_sharp, n_less_sharp, n_flat, n_less_flat};
   const size_t total = n_sharp + n_less_sharp + n_flat + n_less_flat;
-  OD_TRY(fs->h_stage.reserve(total + 1));
+  LSLAM_TRY(fs->h_stage.reserve(total + 1));
   hipStream_t s = lslam::ctx_stream(ctx);
   int rc = upload_lists(s, fs, fs->h_stage.p, src, n, stride_bytes);
   const hipError_t e = hipStreamSynchronize(s);
   if (rc) return rc;
-  OD_TRY(e);
+  LSLAM_TRY(e);
   return LSLAM_OK;
 }
 
@@ -1340,10 +1329,10 @@ int lslam_fset_download(lslam_ctx *ctx, const lslam_fset *fs, int32_t which, flo
     lslam::set_error("feature-set download buffer too small");
     return LSLAM_ERR_INVALID;
   }
-  OD_TRY(hipSetDevice(fs->device));
+  LSLAM_TRY(hipSetDevice(fs->device));
   hipStream_t s = lslam::ctx_stream(ctx);
-  OD_TRY(hipMemcpyAsync(out_xyzi, fs->list(which), fs->counts[which] * sizeof(float4), hipMemcpyDeviceToHost, s));
-  OD_TRY(hipStreamSynchronize(s));
+  LSLAM_TRY(hipMemcpyAsync(out_xyzi, fs->list(which), fs->counts[which] * sizeof(float4), hipMemcpyDeviceToHost, s));
+  LSLAM_TRY(hipStreamSynchronize(s));
   return LSLAM_OK;
 }
 
@@ -1410,7 +1399,7 @@ int lslam_debug_odom_step(lslam_odom *od, lslam_fset *fs, const float pose[6], i
     lslam::set_error("bad odometry-step arguments (no queries, or iter outside [0, max_iterations))");
     return LSLAM_ERR_INVALID;
   }
-  OD_TRY(hipSetDevice(od->device));
+  LSLAM_TRY(hipSetDevice(od->device));
   LoopSetup L;
   int rc = loop_setup(od, od->cur, fs->list(0), n_sharp, fs->list(2), n_flat, L);
   if (rc) return rc;
@@ -1434,7 +1423,7 @@ int lslam_debug_odom_step(lslam_odom *od, lslam_fset *fs, const float pose[6], i
   rc = loop_state_up(od, pose, iter, false);
   if (rc) return rc;
   if (search) {
-    OD_TRY(hipMemsetAsync(od->ind.p, 0xFF, 3 * nq * sizeof(int32_t), od->stream));
+    LSLAM_TRY(hipMemsetAsync(od->ind.p, 0xFF, 3 * nq * sizeof(int32_t), od->stream));
     hipLaunchKernelGGL(odom_search_kernel, dim3((unsigned)nq), dim3(64), 0, od->stream, L.sa);
   }
   if (path == 1) {
@@ -1442,26 +1431,26 @@ int lslam_debug_odom_step(lslam_odom *od, lslam_fset *fs, const float pose[6], i
     if (rc) return rc;
     hipLaunchKernelGGL(odom_gn_kernel, dim3((unsigned)L.oa.nb_total), dim3(256), 0, od->stream, L.ga);
   } else {
-    OD_TRY(od->tap_sel.reserve(nq));
-    OD_TRY(od->tap_coeff.reserve(nq));
+    LSLAM_TRY(od->tap_sel.reserve(nq));
+    LSLAM_TRY(od->tap_coeff.reserve(nq));
     L.oa.sel = od->tap_sel.p;
     L.oa.coeff = od->tap_coeff.p;
-    OD_TRY(launch_odom_sweep(L.oa, od->stream));
-    OD_TRY(launch_solve(L.so, od->stream));
+    LSLAM_TRY(launch_odom_sweep(L.oa, od->stream));
+    LSLAM_TRY(launch_solve(L.so, od->stream));
   }
-  OD_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   GNState *hs = &od->h_state.p->state;
-  OD_TRY(hipMemcpyAsync(hs, od->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
-  OD_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags.p, 64, hipMemcpyDeviceToHost, od->stream));
-  if (ind_out) OD_TRY(hipMemcpyAsync(ind_out, od->ind.p, 3 * nq * sizeof(int32_t), hipMemcpyDeviceToHost, od->stream));
+  LSLAM_TRY(hipMemcpyAsync(hs, od->d_state.p, sizeof(GNState), hipMemcpyDeviceToHost, od->stream));
+  LSLAM_TRY(hipMemcpyAsync(h_flags_of(od), od->d_flags.p, 64, hipMemcpyDeviceToHost, od->stream));
+  if (ind_out) LSLAM_TRY(hipMemcpyAsync(ind_out, od->ind.p, 3 * nq * sizeof(int32_t), hipMemcpyDeviceToHost, od->stream));
   std::vector<float4> hsel, hco;
   if (path == 0 && (sel_out || kept_out)) {
     hsel.resize(nq);
-    OD_TRY(hipMemcpyAsync(hsel.data(), od->tap_sel.p, nq * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+    LSLAM_TRY(hipMemcpyAsync(hsel.data(), od->tap_sel.p, nq * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
   }
-  if (path == 0 && coeff_out) OD_TRY(hipMemcpyAsync(coeff_out, od->tap_coeff.p, nq * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+  if (path == 0 && coeff_out) LSLAM_TRY(hipMemcpyAsync(coeff_out, od->tap_coeff.p, nq * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
   od->tap_ind_key[0] = ~0ull;
-  OD_TRY(hipStreamSynchronize(od->stream));
+  LSLAM_TRY(hipStreamSynchronize(od->stream));
   if (path == 1 && h_flags_of(od)[1] != 0u) {
     lslam::set_error("the persistent kernel's exchange gave up");
     return LSLAM_ERR_HIP;
@@ -1527,10 +1516,10 @@ int lslam_odom_last_clouds(lslam_odom *od, float *last_corner, size_t cap_corner
     lslam::set_error("last-cloud buffer too small");
     return LSLAM_ERR_INVALID;
   }
-  OD_TRY(hipSetDevice(od->device));
-  if (last_corner && S.n[0]) OD_TRY(hipMemcpyAsync(last_corner, S.org[0].p, S.n[0] * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
-  if (last_surf && S.n[1]) OD_TRY(hipMemcpyAsync(last_surf, S.org[1].p, S.n[1] * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
-  OD_TRY(hipStreamSynchronize(od->stream));
+  LSLAM_TRY(hipSetDevice(od->device));
+  if (last_corner && S.n[0]) LSLAM_TRY(hipMemcpyAsync(last_corner, S.org[0].p, S.n[0] * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+  if (last_surf && S.n[1]) LSLAM_TRY(hipMemcpyAsync(last_surf, S.org[1].p, S.n[1] * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+  LSLAM_TRY(hipStreamSynchronize(od->stream));
   return LSLAM_OK;
 }
 
@@ -1545,7 +1534,7 @@ int lslam_odom_process(lslam_odom *od, lslam_fset *fs, float transform[6], float
     lslam::set_error("last-cloud buffer too small");
     return LSLAM_ERR_INVALID;
   }
-  OD_TRY(hipSetDevice(od->device));
+  LSLAM_TRY(hipSetDevice(od->device));
   lslam_stats local;
   lslam_stats &st = stats ? *stats : local;
   std::memset(&st, 0, sizeof(st));
@@ -1557,12 +1546,12 @@ int lslam_odom_process(lslam_odom *od, lslam_fset *fs, float transform[6], float
       // buffers that are views right now keep their memory until their turn comes
       for (size_t k = 0; k < od->pub.size(); ++k) {
         if (od->pub[k].p && (int)k != od->pub_next) continue;
-        OD_TRY(od->pub[k].reserve(2 * (n_ls + n_lf) + 1));
+        LSLAM_TRY(od->pub[k].reserve(2 * (n_ls + n_lf) + 1));
       }
     }
     od->h_last = od->pub[od->pub_next].p;
   } else if (want_out) {
-    OD_TRY(od->h_own.reserve(n_ls + n_lf + 1));
+    LSLAM_TRY(od->h_own.reserve(n_ls + n_lf + 1));
     od->h_last = od->h_own.p;
   }
   int status = LSLAM_TOO_FEW_REF;
@@ -1573,10 +1562,10 @@ int lslam_odom_process(lslam_odom *od, lslam_fset *fs, float transform[6], float
     if (rc) return rc;
     if (want_out) {
       const Side &S = od->side[to];
-      if (n_ls) OD_TRY(hipMemcpyAsync(od->h_last, S.org[0].p, n_ls * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
-      if (n_lf) OD_TRY(hipMemcpyAsync(od->h_last + n_ls, S.org[1].p, n_lf * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+      if (n_ls) LSLAM_TRY(hipMemcpyAsync(od->h_last, S.org[0].p, n_ls * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+      if (n_lf) LSLAM_TRY(hipMemcpyAsync(od->h_last + n_ls, S.org[1].p, n_lf * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
     }
-    OD_TRY(hipStreamSynchronize(od->stream));
+    LSLAM_TRY(hipStreamSynchronize(od->stream));
     od->inited = true;
   } else {
     TailSpec tail;
@@ -1597,11 +1586,11 @@ int lslam_odom_process(lslam_odom *od, lslam_fset *fs, float transform[6], float
       if (tie) {
         // an exact distance tie: the same match through kd-trees (nanoflann's own order), from the clouds' host copies
         std::vector<float4> lc(S.n[0]), ls(S.n[1]), sh(n_sharp), fl(n_flat);
-        if (S.n[0]) OD_TRY(hipMemcpyAsync(lc.data(), S.org[0].p, S.n[0] * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
-        if (S.n[1]) OD_TRY(hipMemcpyAsync(ls.data(), S.org[1].p, S.n[1] * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
-        if (n_sharp) OD_TRY(hipMemcpyAsync(sh.data(), fs->list(0), n_sharp * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
-        if (n_flat) OD_TRY(hipMemcpyAsync(fl.data(), fs->list(2), n_flat * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
-        OD_TRY(hipStreamSynchronize(od->stream));
+        if (S.n[0]) LSLAM_TRY(hipMemcpyAsync(lc.data(), S.org[0].p, S.n[0] * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+        if (S.n[1]) LSLAM_TRY(hipMemcpyAsync(ls.data(), S.org[1].p, S.n[1] * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+        if (n_sharp) LSLAM_TRY(hipMemcpyAsync(sh.data(), fs->list(0), n_sharp * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+        if (n_flat) LSLAM_TRY(hipMemcpyAsync(fl.data(), fs->list(2), n_flat * sizeof(float4), hipMemcpyDeviceToHost, od->stream));
+        LSLAM_TRY(hipStreamSynchronize(od->stream));
         for (int i = 0; i < 6; ++i) pose[i] = od->transform[i];
         rc = lslam::odometry_match_trees(od->ctx, lc.data(), lc.size(), ls.data(), ls.size(), sh.data(), sh.size(), fl.data(), fl.size(), 16,
                                          pose, od->max_it, od->dt, od->dr, &st);
@@ -1612,10 +1601,10 @@ int lslam_odom_process(lslam_odom *od, lslam_fset *fs, float transform[6], float
         std::memset(hs, 0, sizeof(GNState));
         for (int i = 0; i < 6; ++i) hs->pose[i] = pose[i];
         hs->done = 1;
-        OD_TRY(hipMemcpyAsync(od->d_state.p, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
+        LSLAM_TRY(hipMemcpyAsync(od->d_state.p, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
         rc = enqueue_tail(od, tail, false);
         if (rc) return rc;
-        OD_TRY(hipStreamSynchronize(od->stream));
+        LSLAM_TRY(hipStreamSynchronize(od->stream));
       }
       for (int i = 0; i < 6; ++i) od->transform[i] = pose[i];
       status = st.status;
@@ -1625,10 +1614,10 @@ int lslam_odom_process(lslam_odom *od, lslam_fset *fs, float transform[6], float
       std::memset(hs, 0, sizeof(GNState));
       for (int i = 0; i < 6; ++i) hs->pose[i] = od->transform[i];
       hs->done = 1;
-      OD_TRY(hipMemcpyAsync(od->d_state.p, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
+      LSLAM_TRY(hipMemcpyAsync(od->d_state.p, hs, sizeof(GNState), hipMemcpyHostToDevice, od->stream));
       int rc = enqueue_tail(od, tail, false);
       if (rc) return rc;
-      OD_TRY(hipStreamSynchronize(od->stream));
+      LSLAM_TRY(hipStreamSynchronize(od->stream));
       st.status = LSLAM_TOO_FEW_REF;
     }
     float T[16], S2[16];
@@ -1707,14 +1696,14 @@ int lslam_odometry_match(lslam_ctx *ctx, const void *last_corner, size_t n_lc, c
     hidden->od = made;
   }
   lslam_odom *od = hidden->od;
-  OD_TRY(hipSetDevice(od->device));
+  LSLAM_TRY(hipSetDevice(od->device));
   od->max_it = max_iterations < 0 ? 0 : max_iterations;
   od->dt = delta_t_abort;
   od->dr = delta_r_abort;
   // the four clouds into the node's own feature set (the last clouds in the less-sharp / less-flat slices), grids, loop
   const void *src[4] = {sharp, last_corner, flat, last_surf};
   const size_t n[4] = {n_sharp, n_lc, n_flat, n_ls};
-  OD_TRY(od->h_up.reserve(n_sharp + n_lc + n_flat + n_ls + 1));
+  LSLAM_TRY(od->h_up.reserve(n_sharp + n_lc + n_flat + n_ls + 1));
   int rc = upload_lists(od->stream, od->own_fs, od->h_up.p, src, n, stride_bytes);
   if (rc) return rc;
   lslam_fset *fs = od->own_fs;

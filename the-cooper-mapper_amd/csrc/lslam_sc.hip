@@ -290,14 +290,14 @@ int sc_describe_pending(lslam_kfs *k) {
   if (sc.slabs_uploaded != sc.slabs.size()) {  // the table of base pointers (the table may move; the slabs do not)
     std::vector<float *> tab(sc.slabs.size());
     for (size_t i = 0; i < tab.size(); ++i) tab[i] = sc.slabs[i]->p;
-    KFS_TRY(hipStreamSynchronize(k->stream));
-    KFS_TRY(sc.d_slabs.reserve(tab.size()));
-    KFS_TRY(hipMemcpy(sc.d_slabs.p, tab.data(), tab.size() * sizeof(float *), hipMemcpyHostToDevice));
+    LSLAM_TRY(hipStreamSynchronize(k->stream));
+    LSLAM_TRY(sc.d_slabs.reserve(tab.size()));
+    LSLAM_TRY(hipMemcpy(sc.d_slabs.p, tab.data(), tab.size() * sizeof(float *), hipMemcpyHostToDevice));
     sc.slabs_uploaded = sc.slabs.size();
   }
   const size_t m = n - sc.described;
-  KFS_TRY(sc.h_jobs.reserve(m));
-  KFS_TRY(sc.d_jobs.reserve(m));
+  LSLAM_TRY(sc.h_jobs.reserve(m));
+  LSLAM_TRY(sc.d_jobs.reserve(m));
   for (size_t i = 0; i < m; ++i) {
     const lslam::KeyframeClouds &kc = k->kfs[sc.described + i];
     ScJob j{};
@@ -307,11 +307,11 @@ int sc_describe_pending(lslam_kfs *k) {
     }
     sc.h_jobs.p[i] = j;
   }
-  KFS_TRY(hipMemcpyAsync(sc.d_jobs.p, sc.h_jobs.p, m * sizeof(ScJob), hipMemcpyHostToDevice, k->stream));
+  LSLAM_TRY(hipMemcpyAsync(sc.d_jobs.p, sc.h_jobs.p, m * sizeof(ScJob), hipMemcpyHostToDevice, k->stream));
   const size_t lds = ((size_t)sc.params.n_ring * sc.params.n_sector + sc.params.n_sector) * sizeof(float);
   hipLaunchKernelGGL(sc_describe_kernel, dim3((unsigned)m), dim3(SC_BLOCK), lds, k->stream, sc.d_jobs.p, (uint32_t)sc.described,
                      sc.d_slabs.p, sc_shape(sc));
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   // (h_jobs is rewritten by the next describe only: every caller waits for the stream before it returns)
   sc.described = n;
   ++sc.describe_launches;
@@ -324,15 +324,15 @@ int sc_launch_query(lslam_kfs *k, int32_t nq, int32_t max_limit, int32_t top_k, 
   ScState &sc = k->sc;
   const uint32_t n_tiles = (uint32_t)max_limit / SC_TILE + 1;
   const size_t lists = (size_t)nq * n_tiles * (size_t)top_k;
-  KFS_TRY(sc.d_tile_key.reserve(lists));
-  KFS_TRY(sc.d_tile_shift.reserve(lists));
+  LSLAM_TRY(sc.d_tile_key.reserve(lists));
+  LSLAM_TRY(sc.d_tile_shift.reserve(lists));
   const size_t form = ((size_t)sc.params.n_ring + 1) * sc.params.n_sector * sizeof(float);
   int cb = 4;
   while (cb > 1 && (size_t)(cb + 1) * form > SC_LDS_BUDGET) cb >>= 1;
   hipLaunchKernelGGL(sc_query_kernel, dim3(n_tiles, (unsigned)nq), dim3(SC_BLOCK), (size_t)(cb + 1) * form, k->stream, sc.d_slabs.p,
                      (uint32_t)sc.stride, (int)sc.params.n_ring, (int)sc.params.n_sector, cb, sc.d_in.p, sc.d_in.p + nq, (int)top_k,
                      n_tiles, sc.d_tile_key.p, sc.d_tile_shift.p, tap_dist, tap_shift, n_tap);
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   ++sc.query_launches;
   *n_tiles_out = n_tiles;
   return LSLAM_OK;
@@ -378,7 +378,7 @@ int lslam_sc_setup(lslam_kfs *k, const lslam_sc_params *params) {
   }
   ScState &sc = k->sc;
   if (sc.set && std::memcmp(&sc.params, &p, sizeof(p)) == 0) return LSLAM_OK;
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   sc.drop();
   sc.params = p;
   sc.ring_scale = (float)p.n_ring / p.max_range;
@@ -404,8 +404,8 @@ int lslam_sc_descriptor(lslam_kfs *k, int32_t id, float *out) {
   ScState &sc = k->sc;
   const float *rec = sc.slabs[(size_t)id / ScState::SC_SLAB_KEYFRAMES]->p + ((size_t)id % ScState::SC_SLAB_KEYFRAMES) * sc.stride;
   const size_t cells = (size_t)sc.params.n_ring * sc.params.n_sector;
-  KFS_TRY(hipMemcpyAsync(out, rec, cells * sizeof(float), hipMemcpyDeviceToHost, k->stream));
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipMemcpyAsync(out, rec, cells * sizeof(float), hipMemcpyDeviceToHost, k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   return LSLAM_OK;
 }
 
@@ -443,9 +443,9 @@ int lslam_sc_query(lslam_kfs *k, int32_t n_query, const int32_t *query_ids, cons
     }
     if (lim > max_limit) max_limit = lim;
   }
-  KFS_TRY(sc.h_io.reserve(2 * nq + 3 * total));
-  KFS_TRY(sc.d_in.reserve(2 * nq));
-  KFS_TRY(sc.d_out.reserve(3 * total));
+  LSLAM_TRY(sc.h_io.reserve(2 * nq + 3 * total));
+  LSLAM_TRY(sc.d_in.reserve(2 * nq));
+  LSLAM_TRY(sc.d_out.reserve(3 * total));
   int32_t *h_in = sc.h_io.p, *h_out = sc.h_io.p + 2 * nq;
   for (size_t q = 0; q < nq; ++q) {
     const int32_t lim = max_cand_id ? max_cand_id[q] : query_ids[q] - 1;
@@ -455,7 +455,7 @@ int lslam_sc_query(lslam_kfs *k, int32_t n_query, const int32_t *query_ids, cons
   }
   rc = sc_describe_pending(k);
   if (rc) return sc_fail(k, rc);
-  KFS_TRY(hipMemcpyAsync(sc.d_in.p, h_in, 2 * nq * sizeof(int32_t), hipMemcpyHostToDevice, k->stream));
+  LSLAM_TRY(hipMemcpyAsync(sc.d_in.p, h_in, 2 * nq * sizeof(int32_t), hipMemcpyHostToDevice, k->stream));
   uint32_t n_tiles = 1;
   if (max_limit >= 0) {
     rc = sc_launch_query(k, n_query, max_limit, top_k, nullptr, nullptr, 0, &n_tiles);
@@ -463,9 +463,9 @@ int lslam_sc_query(lslam_kfs *k, int32_t n_query, const int32_t *query_ids, cons
   }
   hipLaunchKernelGGL(sc_merge_kernel, dim3((unsigned)nq), dim3(SC_BLOCK), 0, k->stream, sc.d_in.p + nq, (int)top_k, n_tiles, (uint32_t)nq,
                      sc.d_tile_key.p, sc.d_tile_shift.p, sc.d_out.p);
-  KFS_TRY(hipGetLastError());
-  KFS_TRY(hipMemcpyAsync(h_out, sc.d_out.p, 3 * total * sizeof(int32_t), hipMemcpyDeviceToHost, k->stream));
-  KFS_TRY(hipStreamSynchronize(k->stream));  // the call's one wait
+  LSLAM_TRY(hipGetLastError());
+  LSLAM_TRY(hipMemcpyAsync(h_out, sc.d_out.p, 3 * total * sizeof(int32_t), hipMemcpyDeviceToHost, k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));  // the call's one wait
   std::memcpy(ids_out, h_out, total * sizeof(int32_t));
   std::memcpy(shift_out, h_out + total, total * sizeof(int32_t));
   std::memcpy(dist_out, h_out + 2 * total, total * sizeof(float));
@@ -485,20 +485,20 @@ int lslam_sc_distances(lslam_kfs *k, int32_t query_id, float *dist_out, int32_t 
   }
   ScState &sc = k->sc;
   const size_t n = k->kfs.size();
-  KFS_TRY(sc.h_io.reserve(2));
-  KFS_TRY(sc.d_in.reserve(2));
-  KFS_TRY(sc.d_tap.reserve(2 * n));
+  LSLAM_TRY(sc.h_io.reserve(2));
+  LSLAM_TRY(sc.d_in.reserve(2));
+  LSLAM_TRY(sc.d_tap.reserve(2 * n));
   rc = sc_describe_pending(k);
   if (rc) return sc_fail(k, rc);
   sc.h_io.p[0] = query_id;
   sc.h_io.p[1] = (int32_t)n - 1;
-  KFS_TRY(hipMemcpyAsync(sc.d_in.p, sc.h_io.p, 2 * sizeof(int32_t), hipMemcpyHostToDevice, k->stream));
+  LSLAM_TRY(hipMemcpyAsync(sc.d_in.p, sc.h_io.p, 2 * sizeof(int32_t), hipMemcpyHostToDevice, k->stream));
   uint32_t n_tiles = 0;
   rc = sc_launch_query(k, 1, (int32_t)n - 1, 1, sc.d_tap.p, reinterpret_cast<int32_t *>(sc.d_tap.p + n), (uint32_t)n, &n_tiles);
   if (rc) return sc_fail(k, rc);
-  KFS_TRY(hipMemcpyAsync(dist_out, sc.d_tap.p, n * sizeof(float), hipMemcpyDeviceToHost, k->stream));
-  KFS_TRY(hipMemcpyAsync(shift_out, sc.d_tap.p + n, n * sizeof(int32_t), hipMemcpyDeviceToHost, k->stream));
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipMemcpyAsync(dist_out, sc.d_tap.p, n * sizeof(float), hipMemcpyDeviceToHost, k->stream));
+  LSLAM_TRY(hipMemcpyAsync(shift_out, sc.d_tap.p + n, n * sizeof(int32_t), hipMemcpyDeviceToHost, k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   return LSLAM_OK;
 }
 

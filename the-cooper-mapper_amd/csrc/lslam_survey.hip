@@ -10,8 +10,9 @@
 // Shape of the work.  The partition runs on the host (one pass over the cloud, a sort of 64-bit words): the cloud never has to
 // fit on the device, a block at a time does.  Everything per block is device work:
 //   sv_vkey / sv_voxel / sv_scatter   VoxelGrid with a minimum count (keys -> radix sort -> one lane per voxel head)
-//   sv_gkey / sv_gather               points sorted into the cells of a search grid (cell >= search radius, 27-cell probe);
+//   sg_key_kernel / sg_gather_kernel  points sorted into the cells of a search grid (cell >= search radius, 27-cell probe);
 //                                     a cell's range is found by binary search in the sorted keys: no table per cell
+//                                     (lslam_pointgrid_dev.hpp, shared with lslam_mapq.hip: same cells, same neighbour sets)
 //   sv_normals                        one lane per query: fp64 sums in ascending (cell, index) order, cyclic Jacobi in fp64
 //   sv_knn                            one wavefront per query: lane t holds the t-th best of a sorted K-list (K <= 64),
 //                                     candidates by rings of cells until the K-th distance is inside the searched rings
@@ -33,24 +34,9 @@
 #include "../../include/lslam_c.h"
 #include "lslam_internal.hpp"
 #include "lslam_jacobi_dev.hpp"
+#include "lslam_pointgrid_dev.hpp"
 
 namespace {
-
-#define SV_TRY(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      char _b[400];                                                                      \
-      snprintf(_b, sizeof(_b), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      lslam::set_error(_b);                                                              \
-      return LSLAM_ERR_HIP;                                                              \
-    }                                                                                    \
-  } while (0)
-#define SV_RC(expr)             \
-  do {                          \
-    const int _rc = (expr);     \
-    if (_rc != LSLAM_OK) return _rc; \
-  } while (0)
 
 using lslam::DevBuf;
 
@@ -58,73 +44,19 @@ constexpr int SV_BLOCK = 256;
 constexpr int SWEEPS_PER_CHECK = 4;
 using lslam::JACOBI_SWEEPS;
 using lslam::sv_rotate;
-constexpr double GRID_CELL_PAD = 1.0 + 1.0 / 1024.0;  // a radius grid's cell is this much wider than the radius (see SGrid)
+using lslam::SGrid;
+using lslam::sg_cell;
+using lslam::sg_key;
+using lslam::sg_lower;
+using lslam::sg_probe27;
 
 inline dim3 blocks_for(size_t n) { return dim3((unsigned)((n + SV_BLOCK - 1) / SV_BLOCK)); }
 
-// ---- search grid -----------------------------------------------------------------------------------------------------------
-// Cell coordinate of x along axis d: floor(((double)x - lo) / cell), clamped into the grid.  In fp64 the map is monotone and
-// two coordinates closer than `cell` land in the same or in adjacent cells; clamping (a monotone map too) keeps that.  A
-// radius search uses cell = r * GRID_CELL_PAD: the fp32 distance test dx*dx + dy*dy + dz*dz < r2 can pass for a |dx| that
-// exceeds r by a few ulp, never by a thousandth.
-struct SGrid {
-  const uint64_t *keys;  // [n] ascending: x + DX * (y + DY * z)
-  const float4 *pts;     // [n] in key order, w = bitcast(original index); equal keys in ascending index
-  int n;
-  int dim[3];
-  double lo[3];
-  double cell;
-};
-
-__device__ __forceinline__ int sg_cell(const SGrid &g, float x, int d) {
-  const double t = floor(((double)x - g.lo[d]) / g.cell);
-  if (!(t > 0.0)) return 0;
-  if (t >= (double)g.dim[d]) return g.dim[d] - 1;
-  return (int)t;
-}
-__device__ __forceinline__ uint64_t sg_key(const SGrid &g, int x, int y, int z) {
-  return (uint64_t)x + (uint64_t)g.dim[0] * ((uint64_t)y + (uint64_t)g.dim[1] * (uint64_t)z);
-}
-__device__ __forceinline__ int sg_lower(const SGrid &g, uint64_t key) {  // first position with keys[pos] >= key
-  int lo = 0, hi = g.n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (g.keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-__global__ void sv_gkey_kernel(const float4 *pts, int n, SGrid g, uint64_t *keys, uint32_t *idx) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float4 p = pts[i];
-  keys[i] = sg_key(g, sg_cell(g, p.x, 0), sg_cell(g, p.y, 1), sg_cell(g, p.z, 2));
-  idx[i] = (uint32_t)i;
-}
-__global__ void sv_gather_kernel(const float4 *pts, const uint32_t *idx, int n, float4 *out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t j = idx[i];
-  const float4 p = pts[j];
-  out[i] = make_float4(p.x, p.y, p.z, __uint_as_float(j));
-}
-
+// ---- search grid: SGrid, sg_cell / sg_key / sg_lower, sg_probe27 of lslam_pointgrid_dev.hpp (shared with lslam_mapq.hip) -------
 // fp32 squared distance as the reference's searches see it: the three products summed left to right, nothing contracted
 __device__ __forceinline__ float sv_d2(const float4 &p, const float4 &q) {
   const float dx = __fsub_rn(p.x, q.x), dy = __fsub_rn(p.y, q.y), dz = __fsub_rn(p.z, q.z);
   return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
-// every point of the grid within the 27 cells around q, in ascending (key, index) order: f(point)
-template <class F>
-__device__ __forceinline__ void sg_probe27(const SGrid &g, const float4 &q, F f) {
-  const int cx = sg_cell(g, q.x, 0), cy = sg_cell(g, q.y, 1), cz = sg_cell(g, q.z, 2);
-  const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
-  for (int z = max(cz - 1, 0); z <= min(cz + 1, g.dim[2] - 1); ++z)
-    for (int y = max(cy - 1, 0); y <= min(cy + 1, g.dim[1] - 1); ++y) {
-      const int a = sg_lower(g, sg_key(g, x0, y, z)), b = sg_lower(g, sg_key(g, x1, y, z) + 1);
-      for (int e = a; e < b; ++e) f(g.pts[e]);
-    }
 }
 
 // ---- VoxelGrid with a minimum count ----------------------------------------------------------------------------------------
@@ -180,42 +112,6 @@ __global__ void sv_scatter_kernel(const T *in, const uint32_t *keep, const uint3
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || !keep[i]) return;
   out[pos[i]] = in[i];
-}
-
-// bounding box of a device cloud: [0..2] min, [3..5] max as order-preserving unsigned words
-__device__ __forceinline__ uint32_t f2ord(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float ord2f(uint32_t u) {
-  const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-  float f;
-  std::memcpy(&f, &b, 4);
-  return f;
-}
-__global__ void sv_bbox_kernel(const float4 *pts, int n, uint32_t *box) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t lo[3] = {~0u, ~0u, ~0u}, hi[3] = {0u, 0u, 0u};
-  if (i < n) {
-    const float4 p = pts[i];
-    lo[0] = hi[0] = f2ord(p.x);
-    lo[1] = hi[1] = f2ord(p.y);
-    lo[2] = hi[2] = f2ord(p.z);
-  }
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    for (int m = 32; m > 0; m >>= 1) {
-      lo[d] = min(lo[d], (uint32_t)__shfl_xor((int)lo[d], m, 64));
-      hi[d] = max(hi[d], (uint32_t)__shfl_xor((int)hi[d], m, 64));
-    }
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      atomicMin(box + d, lo[d]);
-      atomicMax(box + 3 + d, hi[d]);
-    }
-  }
 }
 
 // ---- normals -----------------------------------------------------------------------------------------------------------------
@@ -336,7 +232,7 @@ __global__ void sv_rankkey_kernel(const float4 *normals, int n, uint64_t *keys) 
   if (i >= n) return;
   float c = normals[i].w;
   if (c == 0.0f) c = 0.0f;  // -0 and +0 are equal curvatures
-  keys[i] = ((uint64_t)f2ord(c) << 32) | (uint32_t)i;
+  keys[i] = ((uint64_t)lslam::ordered_u32(c) << 32) | (uint32_t)i;
 }
 __global__ void sv_rank_kernel(const uint64_t *sorted, int n, int32_t *label, int32_t *order) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -488,12 +384,6 @@ __global__ void sv_not_nan_kernel(const float4 *normals, int n, uint32_t *keep) 
 __global__ void sv_zero_tail_kernel(uint32_t *keep, int n) { keep[n] = 0u; }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-int bits_of(double cells) {
-  int b = 1;
-  while (b < 64 && std::ldexp(1.0, b) < cells) ++b;
-  return b;
-}
-
 // scratch of one call: freed when the call returns (a handle keeps only its result)
 struct Work {
   hipStream_t s = nullptr;
@@ -505,47 +395,43 @@ struct Work {
 };
 
 int sort_pairs(Work &w, size_t n, int end_bit) {  // k0, i0 -> k1, i1
-  size_t bytes = 0;
-  SV_TRY(rocprim::radix_sort_pairs(nullptr, bytes, w.k0.p, w.k1.p, w.i0.p, w.i1.p, n, 0u, (unsigned)end_bit, w.s));
-  SV_TRY(w.tmp.reserve(bytes));
-  SV_TRY(rocprim::radix_sort_pairs((void *)w.tmp.p, bytes, w.k0.p, w.k1.p, w.i0.p, w.i1.p, n, 0u, (unsigned)end_bit, w.s));
+  LSLAM_TRY(lslam::sort_pairs(w.tmp, w.k0.p, w.k1.p, w.i0.p, w.i1.p, n, end_bit, w.s));
   return LSLAM_OK;
 }
 // pos = exclusive scan of keep[0 .. n] (n + 1 words, keep[n] = 0) -> *total = pos[n]; waits
 int scan_keep(Work &w, size_t n, size_t *total) {
   size_t bytes = 0;
-  SV_TRY(w.pos.reserve(n + 1));
-  SV_TRY(rocprim::exclusive_scan(nullptr, bytes, w.keep.p, w.pos.p, 0u, n + 1, rocprim::plus<uint32_t>(), w.s));
-  SV_TRY(w.tmp.reserve(bytes));
-  SV_TRY(rocprim::exclusive_scan((void *)w.tmp.p, bytes, w.keep.p, w.pos.p, 0u, n + 1, rocprim::plus<uint32_t>(), w.s));
+  LSLAM_TRY(w.pos.reserve(n + 1));
+  LSLAM_TRY(rocprim::exclusive_scan(nullptr, bytes, w.keep.p, w.pos.p, 0u, n + 1, rocprim::plus<uint32_t>(), w.s));
+  LSLAM_TRY(w.tmp.reserve(bytes));
+  LSLAM_TRY(rocprim::exclusive_scan((void *)w.tmp.p, bytes, w.keep.p, w.pos.p, 0u, n + 1, rocprim::plus<uint32_t>(), w.s));
   uint32_t t = 0;
-  SV_TRY(hipMemcpyAsync(&t, w.pos.p + n, sizeof(t), hipMemcpyDeviceToHost, w.s));
-  SV_TRY(hipStreamSynchronize(w.s));
+  LSLAM_TRY(hipMemcpyAsync(&t, w.pos.p + n, sizeof(t), hipMemcpyDeviceToHost, w.s));
+  LSLAM_TRY(hipStreamSynchronize(w.s));
   *total = t;
   return LSLAM_OK;
 }
 
-int device_bbox(Work &w, const float4 *pts, size_t n, float mn[3], float mx[3]) {
-  SV_TRY(w.box.reserve(6));
-  const uint32_t init[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u};
-  uint32_t got[6];
-  SV_TRY(hipMemcpyAsync(w.box.p, init, sizeof(init), hipMemcpyHostToDevice, w.s));
-  hipLaunchKernelGGL(sv_bbox_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, pts, (int)n, w.box.p);
-  SV_TRY(hipMemcpyAsync(got, w.box.p, sizeof(got), hipMemcpyDeviceToHost, w.s));
-  SV_TRY(hipStreamSynchronize(w.s));
-  for (int d = 0; d < 3; ++d) { mn[d] = ord2f(got[d]); mx[d] = ord2f(got[3 + d]); }
+int device_bbox(Work &w, const float4 *pts, size_t n, float mn[3], float mx[3]) {  // (a non-finite point shows in the box)
+  LSLAM_TRY(w.box.reserve(6));
+  uint32_t got[6] = {};
+  LSLAM_TRY(hipMemcpyAsync(w.box.p, got, sizeof(got), hipMemcpyHostToDevice, w.s));
+  hipLaunchKernelGGL(lslam::box_kernel<false>, lslam::box_blocks((int)n), dim3(lslam::BOX_BLOCK), 0, w.s, pts, (int)n, w.box.p);
+  LSLAM_TRY(hipMemcpyAsync(got, w.box.p, sizeof(got), hipMemcpyDeviceToHost, w.s));
+  LSLAM_TRY(hipStreamSynchronize(w.s));
+  lslam::box_back(got, mn, mx);
   return LSLAM_OK;
 }
 
 // pcl::VoxelGrid with a minimum count of a device cloud (n > 0, finite) into out (reserved here) -> *m points
 int voxel_min(Work &w, const float4 *pts, size_t n, float leaf, int min_points, DevBuf<float4> &out, size_t *m) {
   float mn[3], mx[3];
-  SV_RC(device_bbox(w, pts, n, mn, mx));
+  LSLAM_RC(device_bbox(w, pts, n, mn, mx));
   const float inv = 1.0f / leaf;
   VoxParams v{};
   v.inv_leaf = inv;
   long long vol = 1;
-  double cells = 1.0;
+  uint64_t cells = 1;  // (exact wherever the sort runs: the guard below holds the volume under 2^31)
   for (int d = 0; d < 3; ++d) {
     if (!std::isfinite(mn[d]) || !std::isfinite(mx[d])) {
       lslam::set_error("voxel index outside its key range (non-finite point?)");
@@ -553,31 +439,31 @@ int voxel_min(Work &w, const float4 *pts, size_t n, float leaf, int min_points, 
     }
     v.base[d] = (int32_t)std::floor(mn[d] * inv);
     v.div[d] = (int32_t)std::floor(mx[d] * inv) - v.base[d] + 1;
-    cells *= (double)v.div[d];
+    cells *= (uint64_t)v.div[d];
     vol *= (long long)((mx[d] - mn[d]) * inv) + 1;
   }
-  SV_TRY(out.reserve(n));
+  LSLAM_TRY(out.reserve(n));
   if (!(vol <= (long long)INT32_MAX)) {  // applyFilter: "Leaf size is too small for the input dataset": the input comes back
-    SV_TRY(hipMemcpyAsync(out.p, pts, n * sizeof(float4), hipMemcpyDeviceToDevice, w.s));
-    SV_TRY(hipStreamSynchronize(w.s));
+    LSLAM_TRY(hipMemcpyAsync(out.p, pts, n * sizeof(float4), hipMemcpyDeviceToDevice, w.s));
+    LSLAM_TRY(hipStreamSynchronize(w.s));
     *m = n;
     return LSLAM_OK;
   }
-  SV_TRY(w.k0.reserve(n)); SV_TRY(w.k1.reserve(n)); SV_TRY(w.i0.reserve(n)); SV_TRY(w.i1.reserve(n));
-  SV_TRY(w.keep.reserve(n + 1)); SV_TRY(w.vtmp.reserve(n)); SV_TRY(w.err.reserve(1));
-  SV_TRY(hipMemsetAsync(w.err.p, 0, sizeof(int32_t), w.s));
+  LSLAM_TRY(w.k0.reserve(n)); LSLAM_TRY(w.k1.reserve(n)); LSLAM_TRY(w.i0.reserve(n)); LSLAM_TRY(w.i1.reserve(n));
+  LSLAM_TRY(w.keep.reserve(n + 1)); LSLAM_TRY(w.vtmp.reserve(n)); LSLAM_TRY(w.err.reserve(1));
+  LSLAM_TRY(hipMemsetAsync(w.err.p, 0, sizeof(int32_t), w.s));
   hipLaunchKernelGGL(sv_vkey_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, pts, (int)n, v, w.k0.p, w.i0.p, w.err.p);
-  SV_RC(sort_pairs(w, n, bits_of(cells + 1.0)));
+  LSLAM_RC(sort_pairs(w, n, lslam::key_bits(cells)));
   hipLaunchKernelGGL(sv_voxel_kernel, blocks_for(n + 1), dim3(SV_BLOCK), 0, w.s, pts, w.k1.p, w.i1.p, (int)n, min_points, w.vtmp.p, w.keep.p);
-  SV_RC(scan_keep(w, n, m));
+  LSLAM_RC(scan_keep(w, n, m));
   int32_t err = 0;
-  SV_TRY(hipMemcpy(&err, w.err.p, sizeof(err), hipMemcpyDeviceToHost));
+  LSLAM_TRY(hipMemcpy(&err, w.err.p, sizeof(err), hipMemcpyDeviceToHost));
   if (err) {
     lslam::set_error("voxel index outside its key range (non-finite point?)");
     return LSLAM_ERR_INVALID;
   }
   hipLaunchKernelGGL(sv_scatter_kernel<float4>, blocks_for(n), dim3(SV_BLOCK), 0, w.s, w.vtmp.p, w.keep.p, w.pos.p, (int)n, out.p);
-  SV_TRY(hipStreamSynchronize(w.s));
+  LSLAM_TRY(hipStreamSynchronize(w.s));
   return LSLAM_OK;
 }
 
@@ -589,24 +475,16 @@ struct GridBuf {
 };
 int build_grid(Work &w, GridBuf &gb, const float4 *pts, size_t n, const float lo[3], const float hi[3], double cell) {
   SGrid g{};
-  double ext = 0.0;
-  for (int d = 0; d < 3; ++d) ext = std::max(ext, (double)hi[d] - (double)lo[d]);
-  cell = std::max(cell, ext / 1048576.0);  // at most 2^20 cells per axis: the key stays inside 60 bits
-  if (!(cell > 0.0)) cell = 1.0;
-  double cells = 1.0;
-  for (int d = 0; d < 3; ++d) {
-    g.lo[d] = (double)lo[d];
-    g.dim[d] = (int)std::floor(((double)hi[d] - (double)lo[d]) / cell) + 1;
-    cells *= (double)g.dim[d];
-  }
-  g.cell = cell;
+  uint64_t cells;
+  int end_bit;
+  lslam::sg_shape(lo, hi, cell, &g, &cells, &end_bit);
   g.n = (int)n;
-  SV_TRY(w.k0.reserve(n)); SV_TRY(w.k1.reserve(n)); SV_TRY(w.i0.reserve(n)); SV_TRY(w.i1.reserve(n));
-  SV_TRY(gb.keys.reserve(n)); SV_TRY(gb.pts.reserve(n));
-  hipLaunchKernelGGL(sv_gkey_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, pts, (int)n, g, w.k0.p, w.i0.p);
-  SV_RC(sort_pairs(w, n, bits_of(cells + 1.0)));
-  SV_TRY(hipMemcpyAsync(gb.keys.p, w.k1.p, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, w.s));
-  hipLaunchKernelGGL(sv_gather_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, pts, w.i1.p, (int)n, gb.pts.p);
+  LSLAM_TRY(w.k0.reserve(n)); LSLAM_TRY(w.k1.reserve(n)); LSLAM_TRY(w.i0.reserve(n)); LSLAM_TRY(w.i1.reserve(n));
+  LSLAM_TRY(gb.keys.reserve(n)); LSLAM_TRY(gb.pts.reserve(n));
+  hipLaunchKernelGGL(lslam::sg_key_kernel<false>, lslam::sg_blocks(n), dim3(lslam::SG_BLOCK), 0, w.s, pts, (int)n, g, (uint64_t)0, w.k0.p, w.i0.p);
+  LSLAM_RC(sort_pairs(w, n, end_bit));
+  LSLAM_TRY(hipMemcpyAsync(gb.keys.p, w.k1.p, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, w.s));
+  hipLaunchKernelGGL(lslam::sg_gather_kernel<>, lslam::sg_blocks(n), dim3(lslam::SG_BLOCK), 0, w.s, pts, w.i1.p, (int)n, gb.pts.p);
   g.keys = gb.keys.p;
   g.pts = gb.pts.p;
   gb.view = g;
@@ -617,13 +495,13 @@ inline float radius2(float r) { return (float)((double)r * (double)r); }
 
 int run_normals(Work &w, GridBuf &gb, const float4 *surface, size_t ns, const float lo[3], const float hi[3], const float4 *query,
                 size_t nq, float radius, float4 *out, int32_t *count) {
-  SV_RC(build_grid(w, gb, surface, ns, lo, hi, (double)radius * GRID_CELL_PAD));
+  LSLAM_RC(build_grid(w, gb, surface, ns, lo, hi, (double)radius * lslam::GRID_CELL_PAD));
   hipLaunchKernelGGL(sv_normals_kernel, blocks_for(nq), dim3(SV_BLOCK), 0, w.s, gb.view, query, (int)nq, radius2(radius), out, count);
   return LSLAM_OK;
 }
 
 int run_knn(Work &w, GridBuf &gb, const float4 *pts, size_t n, const float lo[3], const float hi[3], int K, double cell, int32_t *lists) {
-  SV_RC(build_grid(w, gb, pts, n, lo, hi, cell));
+  LSLAM_RC(build_grid(w, gb, pts, n, lo, hi, cell));
   hipLaunchKernelGGL(sv_knn_kernel, dim3((unsigned)((n + SV_BLOCK / 64 - 1) / (SV_BLOCK / 64))), dim3(SV_BLOCK), 0, w.s, gb.view, pts,
                      (int)n, K, lists);
   return LSLAM_OK;
@@ -637,25 +515,25 @@ struct RegionBuf {
 // labels to their fixpoint; then sizes.  planar / seed / counts: optional outputs
 int run_region(Work &w, RegionBuf &rb, const float4 *normals, size_t n, const int32_t *lists, int K, float cos_thr, int cmin, int cmax,
                uint32_t *planar, int32_t *seed, int64_t counts[2], int64_t *sweeps) {
-  SV_TRY(rb.label.reserve(n)); SV_TRY(rb.order.reserve(n)); SV_TRY(rb.size.reserve(n)); SV_TRY(rb.changed.reserve(1));
-  SV_TRY(rb.mask.reserve(n)); SV_TRY(rb.counters.reserve(2));
-  SV_TRY(w.k0.reserve(n)); SV_TRY(w.k1.reserve(n));
+  LSLAM_TRY(rb.label.reserve(n)); LSLAM_TRY(rb.order.reserve(n)); LSLAM_TRY(rb.size.reserve(n)); LSLAM_TRY(rb.changed.reserve(1));
+  LSLAM_TRY(rb.mask.reserve(n)); LSLAM_TRY(rb.counters.reserve(2));
+  LSLAM_TRY(w.k0.reserve(n)); LSLAM_TRY(w.k1.reserve(n));
   hipLaunchKernelGGL(sv_rankkey_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, normals, (int)n, w.k0.p);
   size_t bytes = 0;
-  SV_TRY(rocprim::radix_sort_keys(nullptr, bytes, w.k0.p, w.k1.p, n, 0u, 64u, w.s));
-  SV_TRY(w.tmp.reserve(bytes));
-  SV_TRY(rocprim::radix_sort_keys((void *)w.tmp.p, bytes, w.k0.p, w.k1.p, n, 0u, 64u, w.s));
+  LSLAM_TRY(rocprim::radix_sort_keys(nullptr, bytes, w.k0.p, w.k1.p, n, 0u, 64u, w.s));
+  LSLAM_TRY(w.tmp.reserve(bytes));
+  LSLAM_TRY(rocprim::radix_sort_keys((void *)w.tmp.p, bytes, w.k0.p, w.k1.p, n, 0u, 64u, w.s));
   hipLaunchKernelGGL(sv_rank_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, w.k1.p, (int)n, rb.label.p, rb.order.p);
   hipLaunchKernelGGL(sv_edges_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, normals, lists, (int)n, K, cos_thr, rb.mask.p);
   int64_t launched = 0;
   for (;;) {
-    SV_TRY(hipMemsetAsync(rb.changed.p, 0, sizeof(int32_t), w.s));
+    LSLAM_TRY(hipMemsetAsync(rb.changed.p, 0, sizeof(int32_t), w.s));
     for (int k = 0; k < SWEEPS_PER_CHECK; ++k)
       hipLaunchKernelGGL(sv_sweep_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, lists, rb.mask.p, (int)n, K, rb.label.p, rb.changed.p);
     launched += SWEEPS_PER_CHECK;
     int32_t changed = 0;
-    SV_TRY(hipMemcpyAsync(&changed, rb.changed.p, sizeof(changed), hipMemcpyDeviceToHost, w.s));
-    SV_TRY(hipStreamSynchronize(w.s));
+    LSLAM_TRY(hipMemcpyAsync(&changed, rb.changed.p, sizeof(changed), hipMemcpyDeviceToHost, w.s));
+    LSLAM_TRY(hipStreamSynchronize(w.s));
     if (!changed) break;
     if (launched > (int64_t)n + SWEEPS_PER_CHECK) {  // a label travels at least one edge per launch: cannot happen
       lslam::set_error("region labels did not settle");
@@ -663,15 +541,15 @@ int run_region(Work &w, RegionBuf &rb, const float4 *normals, size_t n, const in
     }
   }
   if (sweeps) *sweeps += launched;
-  SV_TRY(hipMemsetAsync(rb.size.p, 0, n * sizeof(int32_t), w.s));
-  SV_TRY(hipMemsetAsync(rb.counters.p, 0, 2 * sizeof(unsigned long long), w.s));
+  LSLAM_TRY(hipMemsetAsync(rb.size.p, 0, n * sizeof(int32_t), w.s));
+  LSLAM_TRY(hipMemsetAsync(rb.counters.p, 0, 2 * sizeof(unsigned long long), w.s));
   hipLaunchKernelGGL(sv_csize_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, rb.label.p, (int)n, rb.size.p);
   hipLaunchKernelGGL(sv_classify_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, rb.label.p, rb.size.p, rb.order.p, (int)n, cmin, cmax,
                      planar, seed, counts ? rb.counters.p : nullptr);
   if (counts) {
     unsigned long long c[2];
-    SV_TRY(hipMemcpyAsync(c, rb.counters.p, sizeof(c), hipMemcpyDeviceToHost, w.s));
-    SV_TRY(hipStreamSynchronize(w.s));
+    LSLAM_TRY(hipMemcpyAsync(c, rb.counters.p, sizeof(c), hipMemcpyDeviceToHost, w.s));
+    LSLAM_TRY(hipStreamSynchronize(w.s));
     counts[0] += (int64_t)c[0];
     counts[1] += (int64_t)c[1];
   }
@@ -684,18 +562,18 @@ struct BoundaryBuf {
 };
 int run_boundary(Work &w, GridBuf &gb, BoundaryBuf &bb, const float4 *pts, const float4 *normals, size_t n, const float lo[3],
                  const float hi[3], float radius, double thr, uint32_t *flag, double *gap) {
-  SV_RC(build_grid(w, gb, pts, n, lo, hi, (double)radius * GRID_CELL_PAD));
-  SV_TRY(bb.cnt.reserve(n + 1)); SV_TRY(bb.off.reserve(n + 1));
+  LSLAM_RC(build_grid(w, gb, pts, n, lo, hi, (double)radius * lslam::GRID_CELL_PAD));
+  LSLAM_TRY(bb.cnt.reserve(n + 1)); LSLAM_TRY(bb.off.reserve(n + 1));
   const float r2 = radius2(radius);
   hipLaunchKernelGGL(sv_bcount_kernel, blocks_for(n + 1), dim3(SV_BLOCK), 0, w.s, gb.view, pts, (int)n, r2, bb.cnt.p);
   size_t bytes = 0;
-  SV_TRY(rocprim::exclusive_scan(nullptr, bytes, bb.cnt.p, bb.off.p, 0u, n + 1, rocprim::plus<uint32_t>(), w.s));
-  SV_TRY(w.tmp.reserve(bytes));
-  SV_TRY(rocprim::exclusive_scan((void *)w.tmp.p, bytes, bb.cnt.p, bb.off.p, 0u, n + 1, rocprim::plus<uint32_t>(), w.s));
+  LSLAM_TRY(rocprim::exclusive_scan(nullptr, bytes, bb.cnt.p, bb.off.p, 0u, n + 1, rocprim::plus<uint32_t>(), w.s));
+  LSLAM_TRY(w.tmp.reserve(bytes));
+  LSLAM_TRY(rocprim::exclusive_scan((void *)w.tmp.p, bytes, bb.cnt.p, bb.off.p, 0u, n + 1, rocprim::plus<uint32_t>(), w.s));
   uint32_t total = 0;
-  SV_TRY(hipMemcpyAsync(&total, bb.off.p + n, sizeof(total), hipMemcpyDeviceToHost, w.s));
-  SV_TRY(hipStreamSynchronize(w.s));
-  SV_TRY(bb.angles.reserve((size_t)total + 1));
+  LSLAM_TRY(hipMemcpyAsync(&total, bb.off.p + n, sizeof(total), hipMemcpyDeviceToHost, w.s));
+  LSLAM_TRY(hipStreamSynchronize(w.s));
+  LSLAM_TRY(bb.angles.reserve((size_t)total + 1));
   hipLaunchKernelGGL(sv_bgap_kernel, blocks_for(n), dim3(SV_BLOCK), 0, w.s, gb.view, pts, normals, (int)n, r2, bb.off.p, bb.angles.p, thr,
                      flag, gap);
   return LSLAM_OK;
@@ -730,7 +608,7 @@ int begin_call(lslam_ctx *ctx, Work &w, const char *what) {
     lslam::set_error((std::string(what) + ": no context").c_str());
     return LSLAM_ERR_INVALID;
   }
-  SV_TRY(hipSetDevice(lslam::ctx_device(ctx)));
+  LSLAM_TRY(hipSetDevice(lslam::ctx_device(ctx)));
   w.s = lslam::ctx_stream(ctx);
   return LSLAM_OK;
 }
@@ -740,8 +618,8 @@ int bad(const char *what) {
 }
 template <class T>
 int upload(Work &w, DevBuf<T> &d, const T *h, size_t n) {
-  SV_TRY(d.reserve(n ? n : 1));
-  if (n) SV_TRY(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, w.s));
+  LSLAM_TRY(d.reserve(n ? n : 1));
+  if (n) LSLAM_TRY(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, w.s));
   return LSLAM_OK;
 }
 
@@ -773,21 +651,21 @@ int append_features(Work &w, lslam_survey *sv, int t, const float4 *cloud, size_
   if (!n) return LSLAM_OK;
   const lslam_survey_params &P = sv->params;
   size_t m = 0;
-  SV_RC(voxel_min(w, cloud, n, P.feature_leaf, P.feature_min_points, filt, &m));
+  LSLAM_RC(voxel_min(w, cloud, n, P.feature_leaf, P.feature_min_points, filt, &m));
   if (!m) return LSLAM_OK;
   CubeParams cp{};
   cp.cube_size = P.cube_size;
   for (int d = 0; d < 3; ++d) { cp.origin[d] = P.cube_origin[d]; cp.dims[d] = P.cube_dims[d]; }
-  SV_TRY(perm.reserve(m)); SV_TRY(cube.reserve(m)); SV_TRY(w.keep.reserve(m + 1));
+  LSLAM_TRY(perm.reserve(m)); LSLAM_TRY(cube.reserve(m)); LSLAM_TRY(w.keep.reserve(m + 1));
   hipLaunchKernelGGL(sv_cube_kernel, blocks_for(m + 1), dim3(SV_BLOCK), 0, w.s, filt.p, (int)m, cp, perm.p, cube.p, w.keep.p);
   size_t k = 0;
-  SV_RC(scan_keep(w, m, &k));
+  LSLAM_RC(scan_keep(w, m, &k));
   if (!k) return LSLAM_OK;
-  SV_TRY(sv->pts[t].grow(sv->n[t] + k, sv->n[t], w.s));
-  SV_TRY(sv->cube[t].grow(sv->n[t] + k, sv->n[t], w.s));
+  LSLAM_TRY(sv->pts[t].grow(sv->n[t] + k, sv->n[t], w.s));
+  LSLAM_TRY(sv->cube[t].grow(sv->n[t] + k, sv->n[t], w.s));
   hipLaunchKernelGGL(sv_scatter_kernel<float4>, blocks_for(m), dim3(SV_BLOCK), 0, w.s, perm.p, w.keep.p, w.pos.p, (int)m, sv->pts[t].p + sv->n[t]);
   hipLaunchKernelGGL(sv_scatter_kernel<int32_t>, blocks_for(m), dim3(SV_BLOCK), 0, w.s, cube.p, w.keep.p, w.pos.p, (int)m, sv->cube[t].p + sv->n[t]);
-  SV_TRY(hipStreamSynchronize(w.s));
+  LSLAM_TRY(hipStreamSynchronize(w.s));
   sv->n[t] += k;
   return LSLAM_OK;
 }
@@ -806,59 +684,59 @@ int process_block(Work &w, BlockBufs &b, lslam_survey *sv, const float4 *h_block
   lslam_survey_stats &st = sv->st;
   float lo[3], hi[3];
   host_bbox(h_block, n, lo, hi);
-  SV_RC(upload(w, b.block, h_block, n));
+  LSLAM_RC(upload(w, b.block, h_block, n));
   // voxelFilter(block, 0.05, 3)
   size_t nf = 0;
-  SV_RC(voxel_min(w, b.block.p, n, P.filter_leaf, P.filter_min_points, b.filt, &nf));
+  LSLAM_RC(voxel_min(w, b.block.p, n, P.filter_leaf, P.filter_min_points, b.filt, &nf));
   st.filtered_points += (int64_t)nf;
   if (!nf) return LSLAM_OK;
   // normalEstimate(filtered, radius, surface = block)
-  SV_TRY(b.normals.reserve(nf)); SV_TRY(b.count.reserve(nf));
-  SV_RC(run_normals(w, b.grid, b.block.p, n, lo, hi, b.filt.p, nf, P.normal_radius, b.normals.p, b.count.p));
+  LSLAM_TRY(b.normals.reserve(nf)); LSLAM_TRY(b.count.reserve(nf));
+  LSLAM_RC(run_normals(w, b.grid, b.block.p, n, lo, hi, b.filt.p, nf, P.normal_radius, b.normals.p, b.count.p));
   // points with an undefined normal leave here
-  SV_TRY(w.keep.reserve(nf + 1));
+  LSLAM_TRY(w.keep.reserve(nf + 1));
   hipLaunchKernelGGL(sv_not_nan_kernel, blocks_for(nf + 1), dim3(SV_BLOCK), 0, w.s, b.normals.p, (int)nf, w.keep.p);
   size_t m = 0;
-  SV_RC(scan_keep(w, nf, &m));
+  LSLAM_RC(scan_keep(w, nf, &m));
   st.undefined_normals += (int64_t)(nf - m);
   if (!m) return LSLAM_OK;
-  SV_TRY(b.pts2.reserve(m)); SV_TRY(b.normals2.reserve(m));
+  LSLAM_TRY(b.pts2.reserve(m)); LSLAM_TRY(b.normals2.reserve(m));
   hipLaunchKernelGGL(sv_scatter_kernel<float4>, blocks_for(nf), dim3(SV_BLOCK), 0, w.s, b.filt.p, w.keep.p, w.pos.p, (int)nf, b.pts2.p);
   hipLaunchKernelGGL(sv_scatter_kernel<float4>, blocks_for(nf), dim3(SV_BLOCK), 0, w.s, b.normals.p, w.keep.p, w.pos.p, (int)nf, b.normals2.p);
   // plannarEstimate: K-nearest lists, labels, region sizes
   const int K = P.knn_k;
-  SV_TRY(b.lists.reserve(m * (size_t)K)); SV_TRY(b.planar.reserve(m + 1)); SV_TRY(b.bound.reserve(m + 1));
+  LSLAM_TRY(b.lists.reserve(m * (size_t)K)); LSLAM_TRY(b.planar.reserve(m + 1)); LSLAM_TRY(b.bound.reserve(m + 1));
   // (a centroid may round an ulp outside the block's box: the grid clamps)
-  SV_RC(run_knn(w, b.grid, b.pts2.p, m, lo, hi, K, P.knn_cell > 0.f ? (double)P.knn_cell : 4.0 * (double)P.filter_leaf, b.lists.p));
+  LSLAM_RC(run_knn(w, b.grid, b.pts2.p, m, lo, hi, K, P.knn_cell > 0.f ? (double)P.knn_cell : 4.0 * (double)P.filter_leaf, b.lists.p));
   const float cos_thr = (float)std::cos((double)P.smoothness_angle);
   int64_t counts[2] = {0, 0};
-  SV_RC(run_region(w, b.region, b.normals2.p, m, b.lists.p, K, cos_thr, P.cluster_min, P.cluster_max, b.planar.p, nullptr, counts,
+  LSLAM_RC(run_region(w, b.region, b.normals2.p, m, b.lists.p, K, cos_thr, P.cluster_min, P.cluster_max, b.planar.p, nullptr, counts,
                    &st.label_sweeps));
   st.clusters_kept += counts[0];
   st.clusters_dropped += counts[1];
   // boundaryEstimate
-  SV_RC(run_boundary(w, b.grid, b.boundary, b.pts2.p, b.normals2.p, m, lo, hi, P.boundary_radius, P.boundary_angle, b.bound.p, nullptr));
+  LSLAM_RC(run_boundary(w, b.grid, b.boundary, b.pts2.p, b.normals2.p, m, lo, hi, P.boundary_radius, P.boundary_angle, b.bound.p, nullptr));
   // the two feature clouds, in ascending filtered index
   for (int t = 0; t < 2; ++t) {
     uint32_t *flag = t == 0 ? b.bound.p : b.planar.p;
     DevBuf<float4> &sel = t == 0 ? b.bound_pts : b.planar_pts;
-    SV_TRY(w.keep.reserve(m + 1));
-    SV_TRY(hipMemcpyAsync(w.keep.p, flag, m * sizeof(uint32_t), hipMemcpyDeviceToDevice, w.s));
+    LSLAM_TRY(w.keep.reserve(m + 1));
+    LSLAM_TRY(hipMemcpyAsync(w.keep.p, flag, m * sizeof(uint32_t), hipMemcpyDeviceToDevice, w.s));
     hipLaunchKernelGGL(sv_zero_tail_kernel, dim3(1), dim3(1), 0, w.s, w.keep.p, (int)m);
     size_t k = 0;
-    SV_RC(scan_keep(w, m, &k));
+    LSLAM_RC(scan_keep(w, m, &k));
     (t == 0 ? st.boundary_points : st.planar_points) += (int64_t)k;
     if (!k) continue;
-    SV_TRY(sel.reserve(k));
+    LSLAM_TRY(sel.reserve(k));
     hipLaunchKernelGGL(sv_scatter_kernel<float4>, blocks_for(m), dim3(SV_BLOCK), 0, w.s, b.pts2.p, w.keep.p, w.pos.p, (int)m, sel.p);
-    SV_RC(append_features(w, sv, t, sel.p, k, b.feat, b.perm, b.cube));
+    LSLAM_RC(append_features(w, sv, t, sel.p, k, b.feat, b.perm, b.cube));
   }
   return LSLAM_OK;
 }
 
 int extract_impl(lslam_ctx *ctx, const void *cloud, size_t n, size_t stride, lslam_survey *sv) {
   Work w;
-  SV_RC(begin_call(ctx, w, "lslam_survey_extract"));
+  LSLAM_RC(begin_call(ctx, w, "lslam_survey_extract"));
   sv->device = lslam::ctx_device(ctx);
   sv->stream = w.s;
   const lslam_survey_params &P = sv->params;
@@ -908,11 +786,11 @@ int extract_impl(lslam_ctx *ctx, const void *cloud, size_t n, size_t stride, lsl
       st.max_block_points = std::max<int64_t>(st.max_block_points, (int64_t)(e - a));
       block.resize(e - a);
       for (size_t k = a; k < e; ++k) block[k - a] = pts[(size_t)(uint32_t)order[k]];
-      SV_RC(process_block(w, bufs, sv, block.data(), block.size()));
+      LSLAM_RC(process_block(w, bufs, sv, block.data(), block.size()));
     }
     a = e;
   }
-  SV_TRY(hipStreamSynchronize(w.s));
+  LSLAM_TRY(hipStreamSynchronize(w.s));
   st.n_corner = (int64_t)sv->n[0];
   st.n_surf = (int64_t)sv->n[1];
   return LSLAM_OK;
@@ -982,18 +860,18 @@ int lslam_survey_get(lslam_survey *sv, float *corner_xyzi, size_t cap_corner, fl
   if (!sv) return bad("bad lslam_survey_get arguments");
   float *dst[2] = {corner_xyzi, surf_xyzi};
   const size_t cap[2] = {cap_corner, cap_surf};
-  SV_TRY(hipSetDevice(sv->device));
+  LSLAM_TRY(hipSetDevice(sv->device));
   for (int t = 0; t < 2; ++t) {
     if (!dst[t] || !sv->n[t]) continue;
     if (cap[t] < sv->n[t]) return bad("lslam_survey_get: output buffer too small");
-    SV_TRY(hipMemcpy(dst[t], sv->pts[t].p, sv->n[t] * sizeof(float4), hipMemcpyDeviceToHost));
+    LSLAM_TRY(hipMemcpy(dst[t], sv->pts[t].p, sv->n[t] * sizeof(float4), hipMemcpyDeviceToHost));
   }
   return LSLAM_OK;
 }
 
 int lslam_survey_save(lslam_survey *sv, const char *directory) {
   if (!sv || !directory) return bad("bad lslam_survey_save arguments");
-  SV_TRY(hipSetDevice(sv->device));
+  LSLAM_TRY(hipSetDevice(sv->device));
   const lslam_survey_params &P = sv->params;
   const int W = P.cube_dims[0], H = P.cube_dims[1], D = P.cube_dims[2];
   const size_t ncube = (size_t)W * H * D;
@@ -1003,8 +881,8 @@ int lslam_survey_save(lslam_survey *sv, const char *directory) {
     std::vector<float4> h(sv->n[t]);
     std::vector<int32_t> c(sv->n[t]);
     if (sv->n[t]) {
-      SV_TRY(hipMemcpy(h.data(), sv->pts[t].p, sv->n[t] * sizeof(float4), hipMemcpyDeviceToHost));
-      SV_TRY(hipMemcpy(c.data(), sv->cube[t].p, sv->n[t] * sizeof(int32_t), hipMemcpyDeviceToHost));
+      LSLAM_TRY(hipMemcpy(h.data(), sv->pts[t].p, sv->n[t] * sizeof(float4), hipMemcpyDeviceToHost));
+      LSLAM_TRY(hipMemcpy(c.data(), sv->cube[t].p, sv->n[t] * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
     begin[t].assign(ncube + 1, 0);  // a counting sort by cube: block order inside a cube, as pushCornerPoint / pushSurfPoint leave it
     for (size_t i = 0; i < c.size(); ++i) ++begin[t][(size_t)c[i] + 1];
@@ -1046,7 +924,7 @@ int lslam_voxel_grid_min(lslam_ctx *ctx, const void *cloud, size_t n, size_t str
   *n_out = 0;
   if (n == 0) return LSLAM_OK;
   Work w;
-  SV_RC(begin_call(ctx, w, "lslam_voxel_grid_min"));
+  LSLAM_RC(begin_call(ctx, w, "lslam_voxel_grid_min"));
   std::vector<float4> h;
   pack_host(cloud, n, stride_bytes, true, h);
   DevBuf<float4> in, out;
@@ -1068,7 +946,7 @@ int lslam_debug_survey_normals(lslam_ctx *ctx, const float *surface_xyzw, size_t
   if (!ctx || !surface_xyzw || !n_surface || !query_xyzw || !n_query || !(radius > 0.f) || !out_normal || !out_count)
     return bad("bad lslam_debug_survey_normals arguments");
   Work w;
-  SV_RC(begin_call(ctx, w, "lslam_debug_survey_normals"));
+  LSLAM_RC(begin_call(ctx, w, "lslam_debug_survey_normals"));
   float lo[3], hi[3];
   if (!host_bbox((const float4 *)surface_xyzw, n_surface, lo, hi)) return bad("lslam_debug_survey_normals: non-finite surface point");
   DevBuf<float4> surf, query, normals;
@@ -1089,7 +967,7 @@ int lslam_debug_survey_normals(lslam_ctx *ctx, const float *surface_xyzw, size_t
 int lslam_debug_survey_knn(lslam_ctx *ctx, const float *pts_xyzw, size_t n, int32_t k, float cell, int32_t *out_lists) {
   if (!ctx || !pts_xyzw || !n || k < 1 || k > 64 || !out_lists) return bad("bad lslam_debug_survey_knn arguments (k: 1 .. 64)");
   Work w;
-  SV_RC(begin_call(ctx, w, "lslam_debug_survey_knn"));
+  LSLAM_RC(begin_call(ctx, w, "lslam_debug_survey_knn"));
   float lo[3], hi[3];
   if (!host_bbox((const float4 *)pts_xyzw, n, lo, hi)) return bad("lslam_debug_survey_knn: non-finite point");
   double c = (double)cell;
@@ -1117,7 +995,7 @@ int lslam_debug_survey_region(lslam_ctx *ctx, const float *normals_curv, size_t 
   for (size_t i = 0; i < n * (size_t)k; ++i)
     if (lists[i] < -1 || lists[i] >= (int64_t)n) return bad("lslam_debug_survey_region: a list entry is outside the cloud");
   Work w;
-  SV_RC(begin_call(ctx, w, "lslam_debug_survey_region"));
+  LSLAM_RC(begin_call(ctx, w, "lslam_debug_survey_region"));
   DevBuf<float4> normals;
   DevBuf<int32_t> dl, seed;
   RegionBuf rb;
@@ -1138,7 +1016,7 @@ int lslam_debug_survey_boundary(lslam_ctx *ctx, const float *pts_xyzw, const flo
   if (!ctx || !pts_xyzw || !normals_xyzw || !n || !(radius > 0.f) || !out_flags || !out_gaps)
     return bad("bad lslam_debug_survey_boundary arguments");
   Work w;
-  SV_RC(begin_call(ctx, w, "lslam_debug_survey_boundary"));
+  LSLAM_RC(begin_call(ctx, w, "lslam_debug_survey_boundary"));
   float lo[3], hi[3];
   if (!host_bbox((const float4 *)pts_xyzw, n, lo, hi)) return bad("lslam_debug_survey_boundary: non-finite point");
   DevBuf<float4> pts, normals;

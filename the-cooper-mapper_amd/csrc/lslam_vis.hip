@@ -273,8 +273,8 @@ int vis_images_pending(lslam_kfs *k) {
     v.slabs.push_back(std::move(s));
   }
   const size_t m = n - v.imaged;
-  KFS_TRY(v.h_jobs.reserve(m));
-  KFS_TRY(v.d_jobs.reserve(m));
+  LSLAM_TRY(v.h_jobs.reserve(m));
+  LSLAM_TRY(v.d_jobs.reserve(m));
   size_t most = 1;
   for (size_t i = 0; i < m; ++i) {
     const lslam::KeyframeClouds &kc = k->kfs[v.imaged + i];
@@ -287,15 +287,15 @@ int vis_images_pending(lslam_kfs *k) {
     v.h_jobs.p[i] = j;
     if (kc.n[0] + kc.n[1] > most) most = kc.n[0] + kc.n[1];
   }
-  KFS_TRY(hipMemcpyAsync(v.d_jobs.p, v.h_jobs.p, m * sizeof(VisJob), hipMemcpyHostToDevice, k->stream));
+  LSLAM_TRY(hipMemcpyAsync(v.d_jobs.p, v.h_jobs.p, m * sizeof(VisJob), hipMemcpyHostToDevice, k->stream));
   const size_t total = m * v.stride;
   const size_t fill_blocks = (total + VIS_BLOCK - 1) / VIS_BLOCK;
   hipLaunchKernelGGL(vis_fill_kernel, dim3((unsigned)(fill_blocks < 65536 ? fill_blocks : 65536)), dim3(VIS_BLOCK), 0, k->stream,
                      v.d_jobs.p, v.stride, total);
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   hipLaunchKernelGGL(vis_image_kernel, dim3((unsigned)((most + VIS_BLOCK - 1) / VIS_BLOCK), (unsigned)(m < 65535 ? m : 65535)),
                      dim3(VIS_BLOCK), 0, k->stream, v.d_jobs.p, (uint32_t)m, vis_shape(v));
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   // (h_jobs is rewritten by the next build only: every caller waits for the stream before it returns)
   v.imaged = n;
   ++v.image_launches;
@@ -307,10 +307,10 @@ int vis_upload_voters(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const flo
   VisState &v = k->vis;
   if (!n_ids) return LSLAM_OK;
   const size_t m = (size_t)n_ids;
-  KFS_TRY(v.h_in.reserve(12 * m));
-  KFS_TRY(v.d_inv.reserve(12 * m));
-  KFS_TRY(v.h_img.reserve(m));
-  KFS_TRY(v.d_img.reserve(m));
+  LSLAM_TRY(v.h_in.reserve(12 * m));
+  LSLAM_TRY(v.d_inv.reserve(12 * m));
+  LSLAM_TRY(v.h_img.reserve(m));
+  LSLAM_TRY(v.d_img.reserve(m));
   for (size_t i = 0; i < m; ++i) {
     const float *T = poses + 16 * i;
     float *o = v.h_in.p + 12 * i;
@@ -324,8 +324,8 @@ int vis_upload_voters(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const flo
     }
     v.h_img.p[i] = v.image((size_t)ids[i]);
   }
-  KFS_TRY(hipMemcpyAsync(v.d_inv.p, v.h_in.p, 12 * m * sizeof(float), hipMemcpyHostToDevice, k->stream));
-  KFS_TRY(hipMemcpyAsync(v.d_img.p, v.h_img.p, m * sizeof(const float *), hipMemcpyHostToDevice, k->stream));
+  LSLAM_TRY(hipMemcpyAsync(v.d_inv.p, v.h_in.p, 12 * m * sizeof(float), hipMemcpyHostToDevice, k->stream));
+  LSLAM_TRY(hipMemcpyAsync(v.d_img.p, v.h_img.p, m * sizeof(const float *), hipMemcpyHostToDevice, k->stream));
   return LSLAM_OK;
 }
 
@@ -333,7 +333,7 @@ int vis_upload_voters(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const flo
 int vis_launch_votes(lslam_kfs *k, const float4 *d_pts, size_t n, const float *T, int32_t n_ids, uint32_t *d_votes, bool counted) {
   VisState &v = k->vis;
   if (!n) return LSLAM_OK;
-  KFS_TRY(hipMemsetAsync(d_votes, 0, n * sizeof(uint32_t), k->stream));
+  LSLAM_TRY(hipMemsetAsync(d_votes, 0, n * sizeof(uint32_t), k->stream));
   if (!n_ids) return LSLAM_OK;
   VisMove mv{};
   if (T) {
@@ -343,7 +343,7 @@ int vis_launch_votes(lslam_kfs *k, const float4 *d_pts, size_t n, const float *T
   const dim3 grid((unsigned)((n + VIS_BLOCK - 1) / VIS_BLOCK), (unsigned)((n_ids + VIS_CHUNK - 1) / VIS_CHUNK));
   hipLaunchKernelGGL(vis_vote_kernel, grid, dim3(VIS_BLOCK), 0, k->stream, d_pts, (uint32_t)n, mv, v.d_inv.p, v.d_img.p, (uint32_t)n_ids,
                      vis_shape(v), d_votes);
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   if (counted) ++v.vote_launches;
   return LSLAM_OK;
 }
@@ -354,15 +354,15 @@ int vis_launch_compact(lslam_kfs *k, const float4 *src, const uint32_t *d_votes,
   const uint32_t nb = (uint32_t)((n + VIS_BLOCK - 1) / VIS_BLOCK), min_free = (uint32_t)v.params.min_free_votes;
   uint32_t *counts = v.d_block.p + block_at;
   if (!nb) {
-    KFS_TRY(hipMemsetAsync(counts, 0, sizeof(uint32_t), k->stream));
+    LSLAM_TRY(hipMemsetAsync(counts, 0, sizeof(uint32_t), k->stream));
     return LSLAM_OK;
   }
   hipLaunchKernelGGL(vis_count_kernel, dim3(nb), dim3(VIS_BLOCK), 0, k->stream, d_votes, (uint32_t)n, min_free, counts);
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   hipLaunchKernelGGL(vis_scan_kernel, dim3(1), dim3(VIS_BLOCK), 0, k->stream, counts, nb);
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   hipLaunchKernelGGL(vis_scatter_kernel, dim3(nb), dim3(VIS_BLOCK), 0, k->stream, src, d_votes, (uint32_t)n, min_free, counts, out);
-  KFS_TRY(hipGetLastError());
+  LSLAM_TRY(hipGetLastError());
   return LSLAM_OK;
 }
 
@@ -436,7 +436,7 @@ int lslam_vis_setup(lslam_kfs *k, const lslam_vis_params *params) {
   }
   VisState &v = k->vis;
   if (v.set && std::memcmp(&v.params, &p, sizeof(p)) == 0) return LSLAM_OK;
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   v.drop();
   v.params = p;
   v.el0 = (double)p.fov_down_deg * VIS_PI / 180.0;
@@ -482,8 +482,8 @@ int lslam_vis_range_image(lslam_kfs *k, int32_t id, float *out) {
   rc = vis_images_pending(k);
   if (rc) return vis_fail(k, rc);
   VisState &v = k->vis;
-  KFS_TRY(hipMemcpyAsync(out, v.image((size_t)id), v.stride * sizeof(float), hipMemcpyDeviceToHost, k->stream));
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipMemcpyAsync(out, v.image((size_t)id), v.stride * sizeof(float), hipMemcpyDeviceToHost, k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   return LSLAM_OK;
 }
 
@@ -498,10 +498,10 @@ int lslam_vis_votes(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const float
   VisState &v = k->vis;
   v.last_n = 0;
   if (!n) return LSLAM_OK;
-  KFS_TRY(v.h_pts.reserve(n));
-  KFS_TRY(v.d_pts.reserve(n));
-  KFS_TRY(v.d_votes.reserve(n));
-  KFS_TRY(v.h_votes.reserve(n));
+  LSLAM_TRY(v.h_pts.reserve(n));
+  LSLAM_TRY(v.d_pts.reserve(n));
+  LSLAM_TRY(v.d_votes.reserve(n));
+  LSLAM_TRY(v.h_votes.reserve(n));
   const char *src = static_cast<const char *>(points);
   for (size_t i = 0; i < n; ++i) {
     float c[3];
@@ -512,11 +512,11 @@ int lslam_vis_votes(lslam_kfs *k, int32_t n_ids, const int32_t *ids, const float
   if (rc) return vis_fail(k, rc);
   rc = vis_upload_voters(k, n_ids, ids, poses);
   if (rc) return vis_fail(k, rc);
-  KFS_TRY(hipMemcpyAsync(v.d_pts.p, v.h_pts.p, n * sizeof(float4), hipMemcpyHostToDevice, k->stream));
+  LSLAM_TRY(hipMemcpyAsync(v.d_pts.p, v.h_pts.p, n * sizeof(float4), hipMemcpyHostToDevice, k->stream));
   rc = vis_launch_votes(k, v.d_pts.p, n, nullptr, n_ids, v.d_votes.p, true);
   if (rc) return vis_fail(k, rc);
-  KFS_TRY(hipMemcpyAsync(v.h_votes.p, v.d_votes.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, k->stream));
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipMemcpyAsync(v.h_votes.p, v.d_votes.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   std::memcpy(votes_out, v.h_votes.p, n * sizeof(uint32_t));
   v.last_n = n;
   v.last_ids = n_ids;
@@ -539,7 +539,7 @@ int lslam_vis_votes_device(lslam_kfs *k, int32_t n_ids, const int32_t *ids, cons
   if (rc) return vis_fail(k, rc);
   rc = vis_launch_votes(k, reinterpret_cast<const float4 *>(d_xyzi), n, nullptr, n_ids, d_votes, true);
   if (rc) return vis_fail(k, rc);
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   return LSLAM_OK;
 }
 
@@ -555,9 +555,9 @@ int lslam_vis_filter_device(lslam_kfs *k, int32_t n_ids, const int32_t *ids, con
   v.last_n = 0;
   *n_kept = 0;
   if (!n) return LSLAM_OK;
-  KFS_TRY(v.d_votes.reserve(n));
-  KFS_TRY(v.d_block.reserve(vis_blocks(n) + 1));
-  KFS_TRY(v.h_count.reserve(2));
+  LSLAM_TRY(v.d_votes.reserve(n));
+  LSLAM_TRY(v.d_block.reserve(vis_blocks(n) + 1));
+  LSLAM_TRY(v.h_count.reserve(2));
   rc = vis_images_pending(k);
   if (rc) return vis_fail(k, rc);
   rc = vis_upload_voters(k, n_ids, ids, poses);
@@ -567,8 +567,8 @@ int lslam_vis_filter_device(lslam_kfs *k, int32_t n_ids, const int32_t *ids, con
   if (rc) return vis_fail(k, rc);
   rc = vis_launch_compact(k, src, v.d_votes.p, n, 0, reinterpret_cast<float4 *>(d_out));
   if (rc) return vis_fail(k, rc);
-  KFS_TRY(hipMemcpyAsync(v.h_count.p, v.d_block.p + vis_blocks(n), sizeof(uint32_t), hipMemcpyDeviceToHost, k->stream));
-  KFS_TRY(hipStreamSynchronize(k->stream));
+  LSLAM_TRY(hipMemcpyAsync(v.h_count.p, v.d_block.p + vis_blocks(n), sizeof(uint32_t), hipMemcpyDeviceToHost, k->stream));
+  LSLAM_TRY(hipStreamSynchronize(k->stream));
   *n_kept = v.h_count.p[0];
   return LSLAM_OK;
 }
@@ -587,10 +587,10 @@ int lslam_vis_add_to_fmap(lslam_kfs *k, int32_t id, lslam_fmap *fm, const float 
   v.last_n = 0;
   const lslam::KeyframeClouds kc = k->kfs[(size_t)id];
   const size_t nb[2] = {vis_blocks(kc.n[0]), vis_blocks(kc.n[1])};
-  KFS_TRY(v.d_votes.reserve(kc.n[0] + kc.n[1] ? kc.n[0] + kc.n[1] : 1));
-  KFS_TRY(v.d_block.reserve(nb[0] + nb[1] + 2));
-  KFS_TRY(v.h_count.reserve(2));
-  for (int t = 0; t < 2; ++t) KFS_TRY(v.d_keep[t].reserve(kc.n[t] ? kc.n[t] : 1));
+  LSLAM_TRY(v.d_votes.reserve(kc.n[0] + kc.n[1] ? kc.n[0] + kc.n[1] : 1));
+  LSLAM_TRY(v.d_block.reserve(nb[0] + nb[1] + 2));
+  LSLAM_TRY(v.h_count.reserve(2));
+  for (int t = 0; t < 2; ++t) LSLAM_TRY(v.d_keep[t].reserve(kc.n[t] ? kc.n[t] : 1));
   rc = vis_images_pending(k);
   if (rc) return vis_fail(k, rc);
   rc = vis_upload_voters(k, n_ids, ids, poses);
@@ -601,9 +601,9 @@ int lslam_vis_add_to_fmap(lslam_kfs *k, int32_t id, lslam_fmap *fm, const float 
     if (rc) return vis_fail(k, rc);
     rc = vis_launch_compact(k, kc.p[t], v.d_votes.p + vote_at[t], kc.n[t], block_at[t], v.d_keep[t].p);
     if (rc) return vis_fail(k, rc);
-    KFS_TRY(hipMemcpyAsync(v.h_count.p + t, v.d_block.p + block_at[t] + nb[t], sizeof(uint32_t), hipMemcpyDeviceToHost, k->stream));
+    LSLAM_TRY(hipMemcpyAsync(v.h_count.p + t, v.d_block.p + block_at[t] + nb[t], sizeof(uint32_t), hipMemcpyDeviceToHost, k->stream));
   }
-  KFS_TRY(hipStreamSynchronize(k->stream));  // the two counts; the feature map may run on another context's stream
+  LSLAM_TRY(hipStreamSynchronize(k->stream));  // the two counts; the feature map may run on another context's stream
   const size_t kept[2] = {v.h_count.p[0], v.h_count.p[1]};
   if (n_removed) {
     n_removed[0] = kc.n[0] - kept[0];
@@ -622,7 +622,7 @@ int lslam_debug_vis_votes(lslam_kfs *k, int32_t launches) {
     lslam::set_error("lslam_debug_vis_votes: no lslam_vis_votes call with points and voters has run last, or negative launches");
     return LSLAM_ERR_INVALID;
   }
-  KFS_TRY(v.d_votes_again.reserve(v.last_n));
+  LSLAM_TRY(v.d_votes_again.reserve(v.last_n));
   for (int32_t i = 0; i < launches; ++i) {
     rc = vis_launch_votes(k, v.d_pts.p, v.last_n, nullptr, v.last_ids, v.d_votes_again.p, false);
     if (rc) return vis_fail(k, rc);
