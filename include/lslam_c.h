@@ -1187,7 +1187,11 @@ int lslam_traj_eval(const double *est_stamp, const double *est_xyz, size_t n_est
 
 /* pcl::VoxelGrid<PointXYZI>::filter with a cubic leaf on one cloud (LaserMatcher.cpp:289-301,
  * ScanMatch.cpp:362-398 scanMatchLocal): one centroid {x,y,z,intensity} per occupied voxel, in
- * ascending voxel index.  Points of a voxel are summed in input order (PCL: unspecified). */
+ * ascending voxel index.  Points of a voxel are summed in input order (PCL: unspecified), in fp32, and every sum STARTS FROM
+ * ZERO as PCL's does: a field in which all of a voxel's members are -0.0f comes out as +0.0f (0.0f + -0.0f = +0.0f), a lone
+ * point with a -0.0f field included; every other value is unaffected.  Where nothing is filtered -- more voxels than INT_MAX
+ * ("leaf too small": the input comes back as it is), and in the cube map a cube outside the active area -- the points are
+ * handed on bit for bit, -0.0f included.  The same rule holds for every entry that documents itself as this filter. */
 int lslam_voxel_grid(lslam_ctx *ctx, const void *cloud, size_t n, size_t stride_bytes, float leaf,
                      float *out_xyzi, size_t cap, size_t *n_out);
 /* Two clouds with the same leaf in one pass -- prepareFeatureFrame's corner and surface clouds (LaserMatcher.cpp:289-301, two

@@ -83,7 +83,7 @@ def voxel_filter_min(cloud, leaf, min_points):
     idx = ijk[:, 0] + ijk[:, 1] * div[0] + ijk[:, 2] * div[0] * div[1]
     order = np.argsort(idx, kind="stable")
     _, start, count = np.unique(idx[order], return_index=True, return_counts=True)
-    sums = c[order[start]].copy()
+    sums = np.zeros((len(start), c.shape[1]), F) + c[order[start]]  # from zero, as PCL: a lone -0.0f comes out as +0.0f
     for k in range(1, int(count.max())):
         m = count > k
         sums[m] = sums[m] + c[order[start[m] + k]]

@@ -711,7 +711,13 @@ __global__ __launch_bounds__(FX_BLOCK) void fx_ring_voxel_kernel(FxOutArgs a) {
     if (!(u < per && i < n)) continue;
     const unsigned long long vi = key[fx_at(i)] >> 12;
     if (!(i == 0 || vi != (key[fx_at(i - 1)] >> 12))) continue;
-    float4 s = sp[(int)(key[fx_at(i)] & 4095ull)];  // PCL starts from a zero vector: 0 + x = x
+    float4 s = sp[(int)(key[fx_at(i)] & 4095ull)];
+    if (filtered) {  // PCL starts from a zero vector: 0 + x is x for every x but -0.0f (+0.0f then); an unfiltered point stays as it is
+      s.x = __fadd_rn(0.0f, s.x);
+      s.y = __fadd_rn(0.0f, s.y);
+      s.z = __fadd_rn(0.0f, s.z);
+      s.w = __fadd_rn(0.0f, s.w);
+    }
     int m = i + 1;
     for (; m < n && (key[fx_at(m)] >> 12) == vi; ++m) {
       const float4 q = sp[(int)(key[fx_at(m)] & 4095ull)];

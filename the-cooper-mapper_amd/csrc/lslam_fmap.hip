@@ -359,6 +359,14 @@ __global__ __launch_bounds__(256) void fm_centroid_kernel(const float4 *pts, con
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) longest = max(longest, __shfl_xor(longest, d, 64));
   float sx = p.x, sy = p.y, sz = p.z, sw = p.w;
+  // PCL starts a voxel's sums from a zero vector, and 0 + x is x for every x but -0.0f (0.0f + -0.0f = +0.0f): a filtered
+  // voxel's sum starts as 0 + its first member.  A point of a cube that is not filtered is its own output, bit for bit.
+  if (is_head && (head.single || (head.flags != nullptr && head.flags[(int32_t)(k >> (3 * axis_bits))] != 0))) {
+    sx = __fadd_rn(0.0f, sx);
+    sy = __fadd_rn(0.0f, sy);
+    sz = __fadd_rn(0.0f, sz);
+    sw = __fadd_rn(0.0f, sw);
+  }
   for (int m = 1; m <= longest; ++m) {
     const int srcl = min(lane + m, 63);
     const float qx = __shfl(p.x, srcl, 64), qy = __shfl(p.y, srcl, 64), qz = __shfl(p.z, srcl, 64), qw = __shfl(p.w, srcl, 64);
@@ -401,7 +409,7 @@ __global__ __launch_bounds__(256) void fm_centroid_kernel(const float4 *pts, con
   }
   if (!is_head) return;
   const float cnt = (float)(j - i);
-  // PCL starts from a zero vector: 0 + x = x, so the sums above equal its sums
+  // (the sums started from 0 + the first member where the voxel is filtered: they equal PCL's, the sign of a zero included)
   out[pos[i]] = make_float4(__fdiv_rn(sx, cnt), __fdiv_rn(sy, cnt), __fdiv_rn(sz, cnt), __fdiv_rn(sw, cnt));
   cube_out[pos[i]] = (int32_t)(k >> (3 * axis_bits));
 }

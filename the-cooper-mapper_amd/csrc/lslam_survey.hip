@@ -92,7 +92,8 @@ __global__ void sv_voxel_kernel(const float4 *pts, const uint64_t *keys, const u
   const uint64_t k = keys[i];
   if (i > 0 && keys[i - 1] == k) { keep[i] = 0u; return; }
   float4 p = pts[idx[i]];
-  float sx = p.x, sy = p.y, sz = p.z, sw = p.w;
+  // from zero: 0 + x is x for every x but -0.0f, which becomes +0.0f as in PCL's sums (and lslam_voxel_grid's)
+  float sx = __fadd_rn(0.0f, p.x), sy = __fadd_rn(0.0f, p.y), sz = __fadd_rn(0.0f, p.z), sw = __fadd_rn(0.0f, p.w);
   int j = i + 1;
   for (; j < n && keys[j] == k; ++j) {
     p = pts[idx[j]];
