@@ -222,6 +222,7 @@ void lslam_default_opts(lslam_opts *opts);
 /* still 7: no struct changed; new entry points and structs of their own (lslam_vis_*, lslam_debug_vis_votes: visibility votes over the keyframe store). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_mapq_*: map quality, mean map entropy and mean plane variance; lslam_traj_*: trajectory evaluation). */
 /* still 7: no struct changed; new entry points and structs of their own (lslam_occ_*, lslam_debug_occ_integrate: the 2D occupancy grid from the keyframe store). */
+/* still 7: no struct changed; new entry points and structs of their own (lslam_pg_marginals, lslam_pg_relative_covariances: marginal covariances of pose-graph vertices). */
 #define LSLAM_ABI_VERSION 7
 int lslam_abi_version(void);
 size_t lslam_sizeof_opts(void);
@@ -1793,6 +1794,58 @@ int lslam_pg_plane_prior_robust(lslam_pg *pg, const double *poses7, double *e2, 
  * lslam_g2o_read and lslam_g2o_read_priors skip these lines; this reader returns them, in file order (host only), with the
  * two-call pattern and the vertex numbering of lslam_g2o_read_priors. */
 int lslam_g2o_read_plane_priors(const char *path, int32_t *n_priors, int32_t *vertex, double *world4, double *meas4, double *info9);
+
+/* ---- marginal covariances of pose-graph vertices ----------------------------------------------------------------------------
+ * What g2o's computeMarginals offers the reference's solver: selected blocks of H^-1, H being the system lslam_pg_linearize
+ * exports at the CURRENT estimate (robust weights, priors, plane priors and the identity row of the fixed vertex included),
+ * at lambda = 0.  The 6 unit columns of every listed vertex are solved for on the device by a preconditioned CG that works
+ * on PANELS of 60 columns: per iteration the block system is read once per panel, every column keeps its own step lengths,
+ * residual and done flag, a converged column is frozen, and every sum has a fixed order -- a vertex's blocks are THE SAME
+ * BITS whether it is asked for alone or in a long list, first or last, once or twice in the list, now or in a second call.
+ *
+ * COORDINATES: the solver's own increment coordinates -- those dx of lslam_pg_solve is in and an accepted step applies
+ * (X <- X * [dt, dq]): BODY-frame translation [m] first, then the vector part of the unit quaternion, which is HALF the rotation
+ * angle [rad] -- multiply the rotational rows and columns by 2 for an angle covariance.  Blocks are 6x6 row-major.
+ *
+ * cov36[k] is the diagonal block of vertices[k], returned symmetrised, 1/2 (X + X^T), hence bit-symmetric; cross36 (may be
+ * NULL) is [n_q][n_q][36] with cross36[a][b] = Cov(vertices[a], vertices[b]), cross36[b][a] its exact transpose and
+ * cross36[a][a] = cov36[a].  The fixed vertex has zero covariance: its block and its cross blocks are exact zeros (its
+ * block of H^-1 is the identity by construction of the row and is not reported).
+ *
+ * LSLAM_ERR_INVALID, with nothing written and lslam_pg_last_error saying why, for: a vertex out of range; a queried vertex
+ * whose connected component holds neither the fixed vertex nor any unary constraint (no gauge: the block is not defined); a
+ * column that does not reach the tolerance within max_iters (a component held by plane priors alone, for example -- the
+ * message names the vertex); a sharded graph (lslam_pg_set_shard, _set_comm, _set_row_shard); coarse = 1 on a graph too large
+ * for the dense second level.  The graph itself is left as lslam_pg_linearize leaves it and optimises as before. */
+typedef struct {
+  double rel_tol;     /* |r|/|e| per column; 0: the solver's own default (1e-8, lslam_pg_set_solve_tolerance) */
+  int32_t max_iters;  /* 0: 6 n_v, CG's exact-arithmetic bound, but at least 100.  In fp64 block-Jacobi PCG can need several times
+                       * that on a small ill-conditioned graph (a 22-keyframe chain with random rotations: 214 on the device): the
+                       * call then fails with LSLAM_ERR_INVALID and the caller passes a larger cap, or coarse = 1 on a large graph */
+  int32_t coarse;     /* -1: as the graph's solves decide, 0: block-Jacobi only, 1: two-level */
+} lslam_pg_marginal_opts;
+
+typedef struct {
+  int32_t columns, panels, iters_max, iters_sum, coarse_used; /* columns: 6 per DISTINCT vertex asked for, the reference vertex of lslam_pg_relative_covariances included; iters_sum: over the columns solved */
+  double worst_rel_residual;
+} lslam_pg_marginal_stats;
+
+/* opts NULL: {0, 0, -1}; stats may be NULL. */
+int lslam_pg_marginals(lslam_pg *pg, int32_t n_q, const int32_t *vertices, const lslam_pg_marginal_opts *opts,
+                       double *cov36 /* [n_q][36] */, double *cross36 /* NULL, or [n_q][n_q][36] */,
+                       lslam_pg_marginal_stats *stats);
+/* Covariance of the RELATIVE pose X_ref^-1 X_j for j = vertices[k], in the coordinates of an edge error (translation in the
+ * frame of ref, quaternion vector):  S_rel = [J_r J_j] S_(r,j) [J_r J_j]^T  with S_(r,j) the joint 12x12 marginal and J_r, J_j
+ * the Jacobians the solver's own edge has for an edge (ref, j) whose measurement is the current relative pose, evaluated on
+ * the device by the edge's device function; the 6x6 products run on the host in fp64.  Symmetrised; j == ref gives exact
+ * zeros.  Costs the 6 columns of ref once plus 6 per distinct query.  Errors as lslam_pg_marginals. */
+int lslam_pg_relative_covariances(lslam_pg *pg, int32_t ref, int32_t n_q, const int32_t *vertices,
+                                  const lslam_pg_marginal_opts *opts, double *cov36 /* [n_q][36] */,
+                                  lslam_pg_marginal_stats *stats);
+/* Test tap: the six columns of H^-1 of one free vertex as the panel solve left them -- x[6 n_v][6] row-major, every row,
+ * nothing symmetrised or zeroed -- so that a test can form the true residual H x - e.  Errors as lslam_pg_marginals. */
+int lslam_debug_pg_marginal_columns(lslam_pg *pg, int32_t vertex, const lslam_pg_marginal_opts *opts, double *x /* [6 n_v][6] */,
+                                    lslam_pg_marginal_stats *stats);
 
 /* Device handle tap, as lslam_stream: the stream every kernel of this graph runs on (hipStream_t), for harnesses that time a
  * linearisation with events (tools/bench_robust_linearize.py). */

@@ -385,6 +385,9 @@ struct Loop {
   // where the keyframes are not in a store -- what Graph::edge_information = "hessian" builds the edge's match Hessian from
   std::vector<int32_t> ref_ids;
   std::vector<float> rel_T;
+  // Graph::loop_search = "covariance": e^T (Sigma_rel + Omega_loop^-1)^-1 e when the loop was found (has_mahalanobis)
+  bool has_mahalanobis = false;
+  double mahalanobis = 0.0;
 };
 
 // keyframe_updater.hpp:10-60
@@ -416,6 +419,105 @@ private:
   double accum_distance = 0.0;
   int frame_count = 0, frame_id = 0;
 };
+
+// ---- covariance gates (not in the reference): chi-square quantiles and the small dense algebra they need ---------------------
+// the two tabulated values the defaults need; Wilson-Hilferty otherwise: k (1 - 2/(9k) + z_p sqrt(2/(9k)))^3
+inline double normal_quantile(double p) {  // Acklam's rational approximation, then one Halley step on erfc: ~1e-15
+  static const double a[6] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02, 1.383577518672690e+02,
+                              -3.066479806614716e+01, 2.506628277459239e+00};
+  static const double b[5] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02, 6.680131188771972e+01,
+                              -1.328068155288572e+01};
+  static const double c[6] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00, -2.549732539343734e+00,
+                              4.374664141464968e+00, 2.938163982698783e+00};
+  static const double d[4] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00};
+  double x;
+  if (p < 0.02425) {
+    const double q = std::sqrt(-2.0 * std::log(p));
+    x = (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1.0);
+  } else if (p > 1.0 - 0.02425) {
+    const double q = std::sqrt(-2.0 * std::log(1.0 - p));
+    x = -(((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1.0);
+  } else {
+    const double q = p - 0.5, r = q * q;
+    x = (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
+        (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.0);
+  }
+  const double e = 0.5 * std::erfc(-x / std::sqrt(2.0)) - p;
+  const double u = e * std::sqrt(2.0 * 3.141592653589793) * std::exp(x * x / 2.0);
+  return x - u / (1.0 + x * u / 2.0);
+}
+inline double chi2_quantile_wh(double p, int k) {
+  const double a = 2.0 / (9.0 * k);
+  const double t = 1.0 - a + normal_quantile(p) * std::sqrt(a);
+  return k * t * t * t;
+}
+inline double chi2_quantile(double p, int k) {
+  if (p == 0.99 && k == 3) return 11.345;
+  if (p == 0.99 && k == 6) return 16.812;
+  return chi2_quantile_wh(p, k);
+}
+// largest eigenvalue of a symmetric 3x3 (row-major, stride `ld`), closed form
+inline double sym3_lambda_max(const double *A, int ld) {
+  const double a00 = A[0], a11 = A[ld + 1], a22 = A[2 * ld + 2], a01 = A[1], a02 = A[2], a12 = A[ld + 2];
+  const double p1 = a01 * a01 + a02 * a02 + a12 * a12;
+  if (p1 == 0.0) return std::max(a00, std::max(a11, a22));
+  const double q = (a00 + a11 + a22) / 3.0;
+  const double p2 = (a00 - q) * (a00 - q) + (a11 - q) * (a11 - q) + (a22 - q) * (a22 - q) + 2.0 * p1;
+  const double p = std::sqrt(p2 / 6.0);
+  const double b00 = (a00 - q) / p, b11 = (a11 - q) / p, b22 = (a22 - q) / p, b01 = a01 / p, b02 = a02 / p, b12 = a12 / p;
+  const double det = b00 * (b11 * b22 - b12 * b12) - b01 * (b01 * b22 - b12 * b02) + b02 * (b01 * b12 - b11 * b02);
+  const double r = std::min(1.0, std::max(-1.0, det / 2.0));
+  return q + 2.0 * p * std::cos(std::acos(r) / 3.0);
+}
+// x^T S^-1 x for an n x n S (n <= 6), Gaussian elimination with partial pivoting; false when S is singular
+inline bool quadratic_form_inv(const double *S, int n, const double *x, double *out) {
+  double M[6][7];
+  for (int r = 0; r < n; ++r) {
+    for (int c = 0; c < n; ++c) M[r][c] = S[r * n + c];
+    M[r][n] = x[r];
+  }
+  for (int p = 0; p < n; ++p) {
+    int best = p;
+    for (int r = p + 1; r < n; ++r)
+      if (std::fabs(M[r][p]) > std::fabs(M[best][p])) best = r;
+    if (!(std::fabs(M[best][p]) > 0.0)) return false;
+    if (best != p)
+      for (int c = 0; c <= n; ++c) std::swap(M[p][c], M[best][c]);
+    for (int r = p + 1; r < n; ++r) {
+      const double f = M[r][p] / M[p][p];
+      for (int c = p; c <= n; ++c) M[r][c] -= f * M[p][c];
+    }
+  }
+  double y[6];
+  for (int r = n - 1; r >= 0; --r) {
+    double s = M[r][n];
+    for (int c = r + 1; c < n; ++c) s -= M[r][c] * y[c];
+    y[r] = s / M[r][r];
+  }
+  double q = 0.0;
+  for (int r = 0; r < n; ++r) q += x[r] * y[r];
+  *out = q;
+  return true;
+}
+// the solver's edge error of an edge (key1, key2) measured as Z at the given estimates: toVectorMQT(Z^-1 X1^-1 X2)
+inline void edge_error6(const Mat4d &X1, const Mat4d &X2, const Mat4d &Z, double e[6]) {
+  double p[7];
+  mat_to_pose7(inverse(Z) * (inverse(X1) * X2), p);
+  const double n = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]), s = p[6] < 0 ? -1.0 : 1.0;
+  for (int k = 0; k < 3; ++k) {
+    e[k] = p[k];
+    e[3 + k] = s * p[3 + k] / n;
+  }
+}
+// e^T (Sigma_rel + Omega^-1)^-1 e of a verified loop; Omega diagonal (the node's loop information)
+inline bool loop_mahalanobis(const Mat4d &X1, const Mat4d &X2, const Mat4d &Z, const double sigma_rel[36], const double info_diag[6],
+                             double *d2) {
+  double e[6], S[36];
+  edge_error6(X1, X2, Z, e);
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c) S[r * 6 + c] = sigma_rel[r * 6 + c] + (r == c ? 1.0 / info_diag[r] : 0.0);
+  return quadratic_form_inv(S, 6, e, d2);
+}
 
 class LoopDetector {
 public:
@@ -566,6 +668,102 @@ public:
     const KeyFrame::Ptr &kf = keyframes[(size_t)best];
     if (nk->accum_distance - kf->accum_distance < accum_distance_thresh) return false;
     candidates.push_back(kf);
+    return true;
+  }
+
+  // ---- not in the reference: candidates by pose uncertainty (lslam_pg_marginals / lslam_pg_relative_covariances) -------------
+  // find_nearest_candidates with the fixed sqrt(5) m sphere replaced by one sized by the new keyframe's uncertainty and a
+  // Mahalanobis gate per candidate; `pg` holds the keyframes' vertices (KeyFrame::node), the new one's included.
+  //   1. radius = max(sqrt(5), sqrt(chi2_3(p) lambda_max(Sigma_nn,tt))) -- a HEURISTIC proxy: uncertainty against the gauge, not
+  //      against each candidate; it only has to be generous
+  //   2. the old keyframes inside it (this detector's trajectory: y zeroed, as the reference's search) that are
+  //      accum_distance_thresh of travel back; the nearest max_candidates of them
+  //   3. ONE lslam_pg_relative_covariances call gives their exact Sigma_rel; each is gated on d2 = v^T Sigma_rel,tt^-1 v <=
+  //      chi2_3(p), v = R_j^T (t_j - t_new): the relative translation in the candidate's frame, the frame the translation block
+  //      of Sigma_rel (an edge error's coordinates) is in
+  //   4. survivors in order of d2; then the reference's grouping (5 m of accumulated distance around the first, at most 6)
+  // last_gate: (node, d2) of everything step 3 looked at.  false: no candidate, or a backend error (lastError() is set then).
+  struct Gated { int node; double d2; };
+  std::vector<Gated> last_gate;
+  bool find_covariance_candidates(const std::vector<KeyFrame::Ptr> &keyframes, const KeyFrame::Ptr &nk, lslam_pg *pg, double gate_prob,
+                                  int max_candidates, const lslam_pg_marginal_opts *opts, std::vector<KeyFrame::Ptr> &candidates) {
+    last_gate.clear();
+    _err.clear();
+    if (nk->accum_distance - last_loop_accum_distance < last_loop_interval_thresh) return false;
+    const double chi2 = chi2_quantile(gate_prob, 3);
+    double s_nn[36];
+    const int32_t nn = nk->node;
+    if (lslam_pg_marginals(pg, 1, &nn, opts, s_nn, nullptr, nullptr) < 0) {
+      _err = lslam_pg_last_error();
+      return false;
+    }
+    const double radius2 = std::max(5.0, chi2 * std::max(sym3_lambda_max(s_nn, 6), 0.0));
+    const double pos[3] = {nk->estimate(0, 3), 0.0, nk->estimate(2, 3)};
+    const size_t n = _traj.size() / 3;
+    std::vector<double> d2(n);
+    std::vector<size_t> order(n);
+    for (size_t i = 0; i < n; ++i) {
+      const double dx = (double)_traj[3 * i] - pos[0], dy = (double)_traj[3 * i + 1] - pos[1], dz = (double)_traj[3 * i + 2] - pos[2];
+      d2[i] = dx * dx + dy * dy + dz * dz;
+      order[i] = i;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return d2[a] < d2[b]; });
+    std::vector<KeyFrame::Ptr> near;
+    for (size_t k = 0; k < n; ++k) {
+      if (!(d2[order[k]] < radius2) || (int)near.size() >= max_candidates) break;
+      const KeyFrame::Ptr &kf = keyframes[order[k]];
+      if (kf == nk || nk->accum_distance - kf->accum_distance < accum_distance_thresh) continue;
+      near.push_back(kf);
+    }
+    if (near.empty()) return false;
+    std::vector<int32_t> nodes;
+    for (const auto &kf : near) nodes.push_back(kf->node);
+    std::vector<double> s_rel(near.size() * 36);
+    if (lslam_pg_relative_covariances(pg, nn, (int32_t)nodes.size(), nodes.data(), opts, s_rel.data(), nullptr) < 0) {
+      _err = lslam_pg_last_error();
+      return false;
+    }
+    struct Pass { double d2; size_t k; };
+    std::vector<Pass> gated;
+    for (size_t k = 0; k < near.size(); ++k) {
+      const Mat4d &E = near[k]->estimate;
+      const double t[3] = {E(0, 3) - nk->estimate(0, 3), E(1, 3) - nk->estimate(1, 3), E(2, 3) - nk->estimate(2, 3)};
+      double v[3], S[9], m = 0.0;
+      for (int r = 0; r < 3; ++r) {
+        v[r] = E(0, r) * t[0] + E(1, r) * t[1] + E(2, r) * t[2];
+        for (int c = 0; c < 3; ++c) S[r * 3 + c] = s_rel[k * 36 + r * 6 + c];
+      }
+      if (!quadratic_form_inv(S, 3, v, &m)) m = INFINITY;
+      last_gate.push_back(Gated{near[k]->node, m});
+      if (m <= chi2) gated.push_back(Pass{m, k});
+    }
+    std::stable_sort(gated.begin(), gated.end(), [](const Pass &a, const Pass &b) { return a.d2 < b.d2; });
+    double candidate_dist = 0.0;
+    for (const Pass &g : gated) {
+      if (candidates.size() >= 6) break;
+      const KeyFrame::Ptr &kf = near[g.k];
+      if (candidates.empty()) candidate_dist = kf->accum_distance;
+      else if (std::fabs(candidate_dist - kf->accum_distance) > 5.0) continue;
+      candidates.push_back(kf);
+    }
+    return !candidates.empty();
+  }
+  // detect_nearest over find_covariance_candidates; false with lastError() set on a backend error
+  bool detect_covariance(const std::vector<KeyFrame::Ptr> &keyframes, const std::deque<KeyFrame::Ptr> &new_keyframes, lslam_pg *pg,
+                         double gate_prob, int max_candidates, const lslam_pg_marginal_opts *opts, std::vector<Loop::Ptr> &detected_loops) {
+    updateTrajectory(keyframes);
+    for (const auto &nk : new_keyframes) {
+      std::vector<KeyFrame::Ptr> candidates;
+      if (!find_covariance_candidates(keyframes, nk, pg, gate_prob, max_candidates, opts, candidates)) {
+        if (!_err.empty()) return false;
+        continue;
+      }
+      Loop::Ptr loop = matching_nearest(candidates, nk);
+      if (loop) {
+        detected_loops.push_back(loop);
+        loop_count++;
+      }
+    }
     return true;
   }
 
@@ -785,14 +983,34 @@ public:
       _err = "Graph: floor_sigma_normal [rad] and floor_sigma_distance [m] are set together, both > 0";
       return -1;
     }
+    const bool covariance = loop_search == "covariance";
+    if (!covariance && loop_search != "NONE") {
+      _err = "Graph: unknown loop_search " + loop_search + " (NONE, covariance)";
+      return -1;
+    }
+    if (covariance && (!(loop_gate_prob > 0.0 && loop_gate_prob < 1.0) || loop_max_candidates < 1 ||
+                       !(loop_consistency_prob >= 0.0 && loop_consistency_prob < 1.0))) {
+      _err = "Graph: loop_gate_prob in (0, 1), loop_max_candidates >= 1, loop_consistency_prob in [0, 1) (0: record only)";
+      return -1;
+    }
     _edge_failed = false;
     const bool flushed = flush_keyframe_queue();
     if (_edge_failed) return -1;
     if (!flushed) return 0;
     std::vector<Loop::Ptr> found;
     std::deque<KeyFrame::Ptr> nk(new_keyframes.begin(), new_keyframes.end());
+    struct PgGuard {  // the solver graph the covariances are asked of: the vertices and odometry edges just flushed included
+      lslam_pg *pg;
+      ~PgGuard() { lslam_pg_destroy(pg); }
+    } cov{nullptr};
+    if (covariance && !(cov.pg = make_pg())) return -1;
     if (loop_source) loop_source(keyframes, nk, found);
-    else loop_detector.detect_nearest(keyframes, nk, found);
+    else if (covariance) {
+      if (!loop_detector.detect_covariance(keyframes, nk, cov.pg, loop_gate_prob, loop_max_candidates, &covariance_opts, found)) {
+        _err = loop_detector.lastError();
+        return -1;
+      }
+    } else loop_detector.detect_nearest(keyframes, nk, found);
     if (_appearance && !loop_source) {
       std::deque<KeyFrame::Ptr> open;
       for (const auto &k : nk) {
@@ -803,6 +1021,16 @@ public:
       loop_detector.detect_appearance(keyframes, open, found);
     }
     static const double LOOP_INFO[6] = {2, 2, 2, 2, 2, 2};  // graph.cpp:333-339
+    if (covariance) {  // every loop, whichever detector found it: its Mahalanobis distance; dropped only when a probability is set
+      std::vector<Loop::Ptr> keep;
+      for (const auto &lp : found) {
+        if (!loop_consistency(cov.pg, lp->key1, lp->key2, lp->relative_pose, &lp->mahalanobis)) return -1;
+        lp->has_mahalanobis = true;
+        if (loop_consistency_prob > 0.0 && lp->mahalanobis > chi2_quantile(loop_consistency_prob, 6)) _inconsistent.push_back(lp);
+        else keep.push_back(lp);
+      }
+      found.swap(keep);
+    }
     for (const auto &lp : found) {
       double full[36];
       if (hessian) {
@@ -957,6 +1185,27 @@ public:
   // reject it; Cauchy (0.1) and DCS (1) can.  Reporting only: nothing is removed from the graph.
   std::string loop_robust_kernel = "NONE";
   double loop_robust_kernel_size = 1.0;
+  // Covariance-gated loops (not in the reference, whose search is a fixed sqrt(5) m sphere): "NONE" (default: nothing changes)
+  // or "covariance" -- the candidates of a new keyframe are searched inside a radius sized by its pose uncertainty and gated on
+  // the Mahalanobis distance of the relative translation at probability loop_gate_prob, the nearest loop_max_candidates at most
+  // (LoopDetector::find_covariance_candidates; lslam_pg_marginals / lslam_pg_relative_covariances with covariance_opts).  Every
+  // loop found by any detector then carries Loop::mahalanobis = e^T (Sigma_rel + Omega_loop^-1)^-1 e, e the edge error of the
+  // verified relative pose at the current estimates; with loop_consistency_prob > 0 a loop whose value exceeds the chi-square
+  // quantile with 6 degrees of freedom is dropped before it reaches the solver: inconsistentLoops().
+  std::string loop_search = "NONE";
+  double loop_gate_prob = 0.99;
+  int loop_max_candidates = 32;
+  double loop_consistency_prob = 0.0;
+  lslam_pg_marginal_opts covariance_opts = {0.0, 0, -1};
+  const std::vector<Loop::Ptr> &inconsistentLoops() const { return _inconsistent; }
+  // Loop::mahalanobis of a (would-be) loop edge key1 -> key2 at the current estimates, both keyframes in the solver's arrays
+  bool loopConsistency(const KeyFrame::Ptr &key1, const KeyFrame::Ptr &key2, const Mat4d &relative_pose, double *d2) {
+    lslam_pg *pg = make_pg();
+    if (!pg) return false;
+    const bool ok = loop_consistency(pg, key1, key2, relative_pose, d2);
+    lslam_pg_destroy(pg);
+    return ok;
+  }
   // the robust weight of every entry of `loops` after the last optimisation (all 1 without a kernel)
   const std::vector<double> &loopWeights() const { return _loop_weights; }
   // Data-driven edge information (not in the reference, whose InformationEstimator returns the identity): "NONE" (default:
@@ -1389,6 +1638,49 @@ private:
     for (auto &kf : keyframes) kf->estimate = pose7_to_mat(&_poses[7 * (size_t)kf->node]);
     return true;
   }
+  // the graph as it stands as a solver graph (kernels, priors, plane priors), for the covariance calls; null with _err set
+  lslam_pg *make_pg() {
+    lslam_pg *pg = nullptr;
+    if (lslam_pg_create(_device, (int)(_poses.size() / 7), _poses.data(), (int)(_ij.size() / 2), _ij.data(), _meas.data(), _info.data(),
+                        gps_aligned ? -1 : 0, &pg) != LSLAM_OK) {
+      _err = lslam_pg_last_error();
+      return nullptr;
+    }
+    int rc = apply_kernels(pg);
+    if (rc >= 0 && !_pv.empty()) {
+      bool any = false;
+      for (size_t p = 0; p < _pkind.size(); ++p) any = any || _pkind[p] != LSLAM_PG_KERNEL_NONE;
+      rc = lslam_pg_set_priors(pg, (int32_t)_pv.size(), _pv.data(), _ptype.data(), _pmeas.data(), _pinfo.data(),
+                               any ? _pkind.data() : nullptr, any ? _pdelta.data() : nullptr);
+    }
+    if (rc >= 0 && !_qv.empty()) {
+      bool any = false;
+      for (size_t p = 0; p < _qkind.size(); ++p) any = any || _qkind[p] != LSLAM_PG_KERNEL_NONE;
+      rc = lslam_pg_set_plane_priors(pg, (int32_t)_qv.size(), _qv.data(), _qworld.data(), _qmeas.data(), _qinfo.data(),
+                                     any ? _qkind.data() : nullptr, any ? _qdelta.data() : nullptr);
+    }
+    if (rc < 0) {
+      _err = lslam_pg_last_error();
+      lslam_pg_destroy(pg);
+      return nullptr;
+    }
+    return pg;
+  }
+  bool loop_consistency(lslam_pg *pg, const KeyFrame::Ptr &key1, const KeyFrame::Ptr &key2, const Mat4d &relative_pose, double *d2) {
+    static const double LOOP_INFO[6] = {2, 2, 2, 2, 2, 2};
+    double s_rel[36];
+    const int32_t j = key2->node;
+    if (lslam_pg_relative_covariances(pg, key1->node, 1, &j, &covariance_opts, s_rel, nullptr) < 0) {
+      _err = lslam_pg_last_error();
+      return false;
+    }
+    if (!loop_mahalanobis(key1->estimate, key2->estimate, relative_pose, s_rel, LOOP_INFO, d2)) {
+      _err = "Graph: the loop's covariance is singular";
+      return false;
+    }
+    return true;
+  }
+  std::vector<Loop::Ptr> _inconsistent;
   int apply_kernels(lslam_pg *pg) {
     bool any = false;
     for (size_t e = 0; e < _kind.size(); ++e) any = any || _kind[e] != LSLAM_PG_KERNEL_NONE;

@@ -243,6 +243,33 @@ public:
     if (lslam_pg_save_g2o(_pg, filename.c_str()) < 0) throw std::runtime_error(lslam_pg_last_error());
   }
   const lslam_pg_stats &lastStats() const { return _last; }
+  // ---- marginal covariances (g2o: SparseOptimizer::computeMarginals; lslam_pg_marginals in lslam_c.h, which states the
+  // coordinates).  The 6x6 blocks of `vertices` at the current estimate, row-major, 36 doubles each in `cov`; with `cross`
+  // the [n][n] cross blocks as well.  opts: rel_tol / max_iters / coarse, zero-initialised = the defaults with coarse = -1.
+  // Throws std::runtime_error with the library's message (a vertex without a gauge, a column that does not converge).
+  static lslam_pg_marginal_opts defaultMarginalOpts() { lslam_pg_marginal_opts o = {0.0, 0, -1}; return o; }
+  void marginals(const std::vector<int> &vertices, std::vector<double> &cov, std::vector<double> *cross = nullptr,
+                 const lslam_pg_marginal_opts *opts = nullptr) {
+    build();
+    const std::vector<int32_t> v(vertices.begin(), vertices.end());
+    const size_t n = v.size();
+    std::vector<double> c(n * 36), x(cross ? n * n * 36 : 0);
+    if (lslam_pg_marginals(_pg, (int32_t)n, v.data(), opts, c.data(), cross ? x.data() : nullptr, &_marginal_stats) < 0)
+      throw std::runtime_error(std::string("lslam_pg_marginals: ") + lslam_pg_last_error());
+    cov.swap(c);
+    if (cross) cross->swap(x);
+  }
+  // ... and of the relative poses X_ref^-1 X_j, j in `vertices` (lslam_pg_relative_covariances); j == ref: zeros
+  void relativeCovariances(int ref, const std::vector<int> &vertices, std::vector<double> &cov,
+                           const lslam_pg_marginal_opts *opts = nullptr) {
+    build();
+    const std::vector<int32_t> v(vertices.begin(), vertices.end());
+    std::vector<double> c(v.size() * 36);
+    if (lslam_pg_relative_covariances(_pg, ref, (int32_t)v.size(), v.data(), opts, c.data(), &_marginal_stats) < 0)
+      throw std::runtime_error(std::string("lslam_pg_relative_covariances: ") + lslam_pg_last_error());
+    cov.swap(c);
+  }
+  const lslam_pg_marginal_stats &marginalStats() const { return _marginal_stats; }
   // No reference counterpart ("lm_var" factorises: its solves are exact).  rel_tol in (0, 1): the relative residual at which a
   // damped solve's PCG stops from now on; 0 (default) leaves the library's 1e-8.  Looser = an inexact LM: same optimum, another
   // trajectory of iterates (lslam_pg_set_solve_tolerance, include/lslam_c.h).
@@ -364,6 +391,7 @@ private:
   int _device;
   lslam_pg *_pg;
   lslam_pg_stats _last{};
+  lslam_pg_marginal_stats _marginal_stats{};
   double _solve_tol = 0.0;
   std::deque<VertexSE3> _vertices;  // deque: pointers handed out stay valid
   std::deque<EdgeSE3> _edges;

@@ -123,6 +123,17 @@ class LslamPgStats(C.Structure):
     ]
 
 
+class LslamPgMarginalOpts(C.Structure):
+    """lslam_pg_marginal_opts (include/lslam_c.h)."""
+    _fields_ = [("rel_tol", C.c_double), ("max_iters", C.c_int32), ("coarse", C.c_int32)]
+
+
+class LslamPgMarginalStats(C.Structure):
+    """lslam_pg_marginal_stats (include/lslam_c.h)."""
+    _fields_ = [("columns", C.c_int32), ("panels", C.c_int32), ("iters_max", C.c_int32), ("iters_sum", C.c_int32),
+                ("coarse_used", C.c_int32), ("worst_rel_residual", C.c_double)]
+
+
 class LslamOdomStats(C.Structure):
     """lslam_odom_stats (include/lslam_c.h)."""
     _fields_ = [("matched", C.c_int32), ("tree_fallbacks", C.c_int32), ("searches", C.c_int32), ("reserved", C.c_int32),
@@ -665,6 +676,12 @@ SYMBOLS = {
     "lslam_pg_num_plane_priors": (C.c_int32, [C.c_void_p]),
     "lslam_pg_plane_prior_robust": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "lslam_g2o_read_plane_priors": (C.c_int, [C.c_char_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
+    "lslam_pg_marginals": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.POINTER(LslamPgMarginalOpts), c_double_p, c_double_p,
+                                     C.POINTER(LslamPgMarginalStats)]),
+    "lslam_pg_relative_covariances": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_int32_p, C.POINTER(LslamPgMarginalOpts),
+                                                c_double_p, C.POINTER(LslamPgMarginalStats)]),
+    "lslam_debug_pg_marginal_columns": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(LslamPgMarginalOpts), c_double_p,
+                                                  C.POINTER(LslamPgMarginalStats)]),
     "lslam_pg_stream": (C.c_void_p, [C.c_void_p]),
     "lslam_pg_kernel_from_name": (C.c_int, [C.c_char_p]),
     "lslam_icp_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, c_float_p, C.c_int32,

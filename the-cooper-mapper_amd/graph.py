@@ -95,7 +95,8 @@ class Graph:
                  gps_sigma=None, gps_robust_kernel=None, gps_robust_delta=1.0, gps_min_spread=None, imu_orientation_sigma=None,
                  floor_sigma=None, floor_params=None, floor_robust_kernel=None, floor_robust_delta=1.0,
                  floor_world_plane=(0.0, 0.0, 1.0, 0.0), odometry_information=None, remove_dynamic=False, dynamic_params=None,
-                 occupancy=None):
+                 occupancy=None, loop_search=None, loop_gate_prob=0.99, loop_max_candidates=32, loop_consistency_prob=None,
+                 covariance_opts=None):
         """``resident=True``: the keyframes' clouds live in a :class:`KeyframeStore` on the loop detector's context --
         ``add_frame`` uploads them once (``kf.store_id``), loop closure and ``get_final_feature_map`` read them there;
         ``keep_host_clouds=False`` then drops the host copies (``kf.corner_cloud`` / ``kf.surf_cloud`` fetch on demand).
@@ -155,7 +156,24 @@ class Graph:
         ``occupancy=True`` or a dict of ``KeyframeStore.occ_setup``'s keywords (not in the reference; needs ``resident=True``):
         :meth:`occupancy_grid` is available and :meth:`save` also writes ``map.pgm`` / ``map.yaml``, the 2D occupancy grid a
         ``map_server`` loads (``lslam_occ_*``, :mod:`.occupancy`).  A dict without ``width`` / ``height`` has the bounds fitted
-        to the poses.  None (the default): nothing changes."""
+        to the poses.  None (the default): nothing changes.
+        ``loop_search="covariance"`` (not in the reference, whose search is a fixed sqrt(5) m sphere): the candidates of a
+        new keyframe are searched inside a radius sized by its pose uncertainty and gated on the Mahalanobis distance of the
+        relative translation at probability ``loop_gate_prob``, the nearest ``loop_max_candidates`` at most
+        (``LoopDetector.find_covariance_candidates``; ``PoseGraph.marginals`` / ``relative_covariances`` with
+        ``covariance_opts``, e.g. ``dict(max_iters=..., coarse=1)``).  Every loop found by any detector then carries
+        ``loop.mahalanobis`` = e^T (Sigma_rel + Omega_loop^-1)^-1 e, e the edge error of the verified relative pose at the
+        current estimates; with ``loop_consistency_prob`` set, a loop whose value exceeds the chi-square quantile with 6
+        degrees of freedom is dropped before it reaches the solver (:meth:`inconsistent_loops`).  None (the default):
+        nothing changes, bit for bit."""
+        if loop_search not in (None, "covariance"):
+            raise ValueError("Graph: loop_search is None or \"covariance\"")
+        self.loop_search = loop_search
+        self.loop_gate_prob = float(loop_gate_prob)
+        self.loop_max_candidates = int(loop_max_candidates)
+        self.loop_consistency_prob = None if loop_consistency_prob is None else float(loop_consistency_prob)
+        self.covariance_opts = dict(covariance_opts or {})
+        self._inconsistent = []
         self.occupancy = None if occupancy is None or occupancy is False else ({} if occupancy is True else dict(occupancy))
         if self.occupancy is not None and not (resident or appearance_loops):
             raise ValueError("Graph: occupancy needs resident=True")
@@ -290,11 +308,17 @@ class Graph:
         """-> (loops found in this pass, LM iterations run)."""
         if not self.flush_keyframe_queue():
             return [], 0
-        loops = self.loop_detector.detect_nearest(self.keyframes, self.new_keyframes)
+        if self.loop_search == "covariance":
+            loops = self.loop_detector.detect_covariance(self.keyframes, self.new_keyframes, self._covariance_source(),
+                                                         self.loop_gate_prob, self.loop_max_candidates)
+        else:
+            loops = self.loop_detector.detect_nearest(self.keyframes, self.new_keyframes)
         if self.appearance_loops:
             closed = set(id(lp.key2) for lp in loops)
             loops = loops + self.loop_detector.detect_appearance(self.keyframes,
                                                                  [k for k in self.new_keyframes if id(k) not in closed])
+        if self.loop_search == "covariance":
+            loops = self._consistent(loops)
         for lp in loops:
             info = LOOP_INFORMATION
             if self.edge_information == "hessian":
@@ -319,6 +343,42 @@ class Graph:
         last = self.keyframes[-1]
         self.tf_odom2graph = last.estimate @ np.linalg.inv(last.odom)
         return loops, iterations
+
+    # ---- covariance-gated loops (not in the reference) -------------------------------------------------------------------------
+    def _covariance_source(self):
+        """What the covariance search and the consistency test ask: the solver with this graph's options."""
+        g = self
+
+        class _Source:
+            def marginals(self, vertices):
+                return g.solver.marginals(vertices, **g.covariance_opts)
+
+            def relative_covariances(self, ref, vertices):
+                return g.solver.relative_covariances(ref, vertices, **g.covariance_opts)
+        return getattr(self, "covariance_source", None) or _Source()
+
+    def loop_consistency(self, key1, key2, relative_pose, information=None):
+        """``loop_mahalanobis`` of a (would-be) loop edge key1 -> key2 at the current estimates, both keyframes in the solver."""
+        from .loop_closure import loop_mahalanobis
+        s_rel = self._covariance_source().relative_covariances(key1.node, [key2.node])
+        return loop_mahalanobis(key1.estimate, key2.estimate, relative_pose, np.asarray(s_rel)[0],
+                                LOOP_INFORMATION if information is None else information)
+
+    def _consistent(self, loops):
+        """``loop.mahalanobis`` on every loop; the loops that pass ``loop_consistency_prob`` (all, when it is None)."""
+        from .loop_closure import chi2_quantile
+        keep = []
+        for lp in loops:
+            lp.mahalanobis = self.loop_consistency(lp.key1, lp.key2, lp.relative_pose)
+            if self.loop_consistency_prob is not None and lp.mahalanobis > chi2_quantile(self.loop_consistency_prob, 6):
+                self._inconsistent.append(lp)
+            else:
+                keep.append(lp)
+        return keep
+
+    def inconsistent_loops(self):
+        """The verified loops the consistency test kept out of the solver (``loop_consistency_prob``)."""
+        return list(self._inconsistent)
 
     # ---- GPS fixes and IMU orientations as unary constraints (not in the reference) ------------------------------------------
     def _add_priors(self, new_keyframes):

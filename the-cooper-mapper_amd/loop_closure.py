@@ -78,6 +78,55 @@ class Loop:
         self.relative_pose = np.asarray(relative_pose, np.float32).reshape(4, 4)
         self.ref_ids = None if ref_ids is None else [int(i) for i in ref_ids]
         self.rel_T = None if rel_T is None else np.ascontiguousarray(rel_T, np.float32).reshape(-1, 4, 4)
+        self.mahalanobis = None  # Graph(loop_search="covariance"): e^T (Sigma_rel + Omega^-1)^-1 e when the loop was found
+
+
+# chi-square quantiles for the covariance gates: the two tabulated values the defaults need, Wilson-Hilferty otherwise
+CHI2_3_99, CHI2_6_99 = 11.345, 16.812
+
+
+def chi2_quantile_wh(p, k):
+    """Wilson-Hilferty: chi2_k(p) ~ k (1 - 2 / (9 k) + z_p sqrt(2 / (9 k)))^3, z_p the normal quantile.  Within 1 % of the
+    tabulated 0.99 quantiles for k = 3 and 6 (tests/test_loop_covariance_gate.py)."""
+    from statistics import NormalDist
+    if not 0.0 < p < 1.0:
+        raise ValueError("chi2 quantile: the probability must be in (0, 1)")
+    a = 2.0 / (9.0 * k)
+    return k * (1.0 - a + NormalDist().inv_cdf(p) * a ** 0.5) ** 3
+
+
+def chi2_quantile(p, k):
+    if p == 0.99 and k == 3:
+        return CHI2_3_99
+    if p == 0.99 and k == 6:
+        return CHI2_6_99
+    return chi2_quantile_wh(p, k)
+
+
+def edge_error(key1_estimate, key2_estimate, relative_pose):
+    """The solver's edge error of an edge (key1, key2) measured as ``relative_pose`` at the given estimates:
+    toVectorMQT(Z^-1 X1^-1 X2) = [translation, quaternion vector with w >= 0], fp64."""
+    from .pose_graph import mat_to_pose7
+    def inv(T):  # Eigen::Isometry3d::inverse(), [R^T | -R^T t], as the C++ mirror: a verified pose comes out of an fp32 matcher
+        T = np.asarray(T, np.float64)  # and its rotation is orthonormal only to fp32 -- a general inverse differs from this by 1e-7
+        out = np.eye(4)
+        out[:3, :3] = T[:3, :3].T
+        out[:3, 3] = -(T[:3, :3].T @ T[:3, 3])
+        return out
+    E = inv(relative_pose) @ (inv(key1_estimate) @ np.asarray(key2_estimate, np.float64))
+    p = mat_to_pose7(E)
+    q = p[3:] / np.linalg.norm(p[3:])
+    if q[3] < 0:
+        q = -q
+    return np.r_[p[:3], q[:3]]
+
+
+def loop_mahalanobis(key1_estimate, key2_estimate, relative_pose, sigma_rel, information):
+    """e^T (Sigma_rel + Omega^-1)^-1 e for a verified loop: e the edge error of the verified relative pose at the current
+    estimates, Sigma_rel the covariance of X1^-1 X2 (``PoseGraph.relative_covariances``), Omega the loop's information."""
+    e = edge_error(key1_estimate, key2_estimate, relative_pose)
+    S = np.asarray(sigma_rel, np.float64).reshape(6, 6) + np.linalg.inv(np.asarray(information, np.float64).reshape(6, 6))
+    return float(e @ np.linalg.solve(S, e))
 
 
 def transform_cloud(cloud, tf):
@@ -104,6 +153,7 @@ class LoopDetector:
         self.sc_distance_thresh = 0.2
         self.sc_top_k = 4
         self.loop_count = 0
+        self.last_gate = []  # find_covariance_candidates: (keyframe, d2) of every candidate it gated last
         self.last_loop_accum_distance = 0.0
         self._trajectory = np.zeros((0, 4), np.float32)
         self._scan_match = scan_match
@@ -253,6 +303,76 @@ class LoopDetector:
                 continue
             candidates.append(kf)
         return candidates
+
+    # ---- not in the reference: candidates by pose uncertainty (lslam_pg_marginals) --------------------
+    def find_covariance_candidates(self, keyframes, new_keyframe, solver, gate_prob=0.99, max_candidates=32):
+        """:meth:`find_nearest_candidates` with the fixed sqrt(5) m sphere replaced by one sized by the new keyframe's
+        uncertainty and a Mahalanobis gate per candidate.  ``solver``: whatever has ``marginals(vertices)`` and
+        ``relative_covariances(ref, vertices)`` over the keyframes' ``node`` ids (:class:`PoseGraph`), the new keyframe in it.
+          1. radius = max(sqrt(5), sqrt(chi2_3(p) lambda_max(Sigma_nn,tt))) -- a HEURISTIC proxy: Sigma_nn is the new
+             keyframe's uncertainty against the gauge, not against each candidate; it only has to be generous.
+          2. the old keyframes inside it (the detector's trajectory: y zeroed, as the reference's search) that are
+             ``accum_distance_thresh`` of travel back; the nearest ``max_candidates`` of them.
+          3. ONE relative_covariances call gives their exact Sigma_rel; each is gated on d2 = v^T Sigma_rel,tt^-1 v <=
+             chi2_3(p), v = R_j^T (t_j - t_new): the relative translation in the candidate's frame, which is the frame the
+             translation block of Sigma_rel (an edge error's coordinates) is in.
+          4. survivors in order of d2; then the reference's grouping (5 m of accumulated distance around the first, at most 6).
+        -> candidates, and ``self.last_gate`` = [(keyframe, d2)] of everything step 3 looked at."""
+        self.last_gate = []
+        if new_keyframe.accum_distance - self.last_loop_accum_distance < self.last_loop_interval_thresh:
+            return []
+        chi2 = chi2_quantile(gate_prob, 3)
+        s_nn = np.asarray(solver.marginals([new_keyframe.node]), np.float64).reshape(6, 6)
+        lam = float(np.linalg.eigvalsh(s_nn[:3, :3]).max())
+        radius2 = max(5.0, chi2 * max(lam, 0.0))
+        pos = new_keyframe.estimate[:3, 3].astype(np.float64).copy()
+        pos[1] = 0.0
+        t = self._trajectory.astype(np.float64)
+        d = t[:, :3] - pos[None]
+        d2 = (d * d).sum(1)
+        near = []
+        for i in np.argsort(d2, kind="stable"):
+            if not d2[i] < radius2 or len(near) >= max_candidates:
+                break
+            kf = keyframes[int(round(float(t[i, 3])))]
+            if kf is new_keyframe or new_keyframe.accum_distance - kf.accum_distance < self.accum_distance_thresh:
+                continue
+            near.append(kf)
+        if not near:
+            return []
+        s_rel = np.asarray(solver.relative_covariances(new_keyframe.node, [k.node for k in near]), np.float64).reshape(-1, 6, 6)
+        gated = []
+        for kf, S in zip(near, s_rel):
+            v = kf.estimate[:3, :3].T @ (kf.estimate[:3, 3] - new_keyframe.estimate[:3, 3])
+            m = float(v @ np.linalg.solve(S[:3, :3], v))
+            self.last_gate.append((kf, m))
+            if m <= chi2:
+                gated.append((m, len(gated), kf))
+        gated.sort(key=lambda g: g[:2])
+        candidates, candidate_dist = [], 0.0
+        for _m, _k, kf in gated:
+            if len(candidates) >= 6:
+                break
+            if not candidates:
+                candidate_dist = kf.accum_distance
+            elif abs(candidate_dist - kf.accum_distance) > 5.0:
+                continue
+            candidates.append(kf)
+        return candidates
+
+    def detect_covariance(self, keyframes, new_keyframes, solver, gate_prob=0.99, max_candidates=32):
+        """:meth:`detect_nearest` over :meth:`find_covariance_candidates`: the same arguments, plus the solver that already
+        holds the new keyframes' vertices and odometry edges."""
+        self.update_trajectory(keyframes)
+        loops = []
+        for nk in new_keyframes:
+            cand = self.find_covariance_candidates(keyframes, nk, solver, gate_prob, max_candidates)
+            if cand:
+                loop = self.matching_nearest(cand, nk)
+                if loop is not None:
+                    loops.append(loop)
+                    self.loop_count += 1
+        return loops
 
     # ---- :166-230 ---------------------------------------------------------------------------------
     def matching_nearest(self, candidate_keyframes, new_keyframe):

@@ -10,7 +10,8 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import ALLGATHERV_FN, ALLREDUCE_FN, LslamError, LslamPgStats, c_double_p, c_int32_p, load_library
+from .capi import (ALLGATHERV_FN, ALLREDUCE_FN, LslamError, LslamPgMarginalOpts, LslamPgMarginalStats, LslamPgStats, c_double_p,
+                   c_int32_p, load_library)
 
 
 def _dp(a):
@@ -91,6 +92,7 @@ class PoseGraph:
         self.h = None
         self._cb = None
         self.last_stats = None
+        self.marginal_stats = None  # lslam_pg_marginal_stats of the last marginals() / relative_covariances()
 
     # ---- SolverG2O interface ------------------------------------------------------
     def add_se3_node(self, pose):
@@ -505,6 +507,54 @@ class PoseGraph:
         it = C.c_int32()
         self._check(self.lib.lslam_pg_solve(self.h, float(lam), _dp(dx), C.byref(it)))
         return dx, it.value
+
+    # ---- marginal covariances (lslam_pg_marginals, lslam_pg_relative_covariances) ------------------
+    @staticmethod
+    def _marginal_opts(rel_tol=0.0, max_iters=0, coarse=-1):
+        return LslamPgMarginalOpts(float(rel_tol), int(max_iters), int(coarse))
+
+    @staticmethod
+    def _vertex_list(vertices):
+        v = np.ascontiguousarray(np.asarray(vertices).reshape(-1), np.int32)
+        return v, (v.ctypes.data_as(c_int32_p) if len(v) else None)
+
+    def marginals(self, vertices, cross=False, **opts):
+        """Covariance blocks of `vertices` at the current estimate, g2o's computeMarginals: (n, 6, 6), and with `cross` also the
+        (n, n, 6, 6) cross blocks.  Coordinates are the solver's increments (body-frame translation [m], then the quaternion
+        vector = half the angle); the fixed vertex has exact zeros.  `opts`: rel_tol, max_iters, coarse
+        (lslam_pg_marginal_opts).  Raises LslamError for a vertex without a gauge, a column that does not converge, a sharded
+        graph; nothing is returned then.  The call's statistics are in ``marginal_stats``."""
+        self._build()
+        v, vp = self._vertex_list(vertices)
+        n = len(v)
+        cov = np.zeros((n, 6, 6))
+        crs = np.zeros((n, n, 6, 6)) if cross else None
+        o, st = self._marginal_opts(**opts), LslamPgMarginalStats()
+        self._check(self.lib.lslam_pg_marginals(self.h, n, vp, C.byref(o), _dp(cov) if n else None,
+                                                _dp(crs) if cross and n else None, C.byref(st)))
+        self.marginal_stats = st
+        return (cov, crs) if cross else cov
+
+    def relative_covariances(self, ref, vertices, **opts):
+        """Covariance (n, 6, 6) of the relative poses X_ref^-1 X_j, j in `vertices`, in the coordinates of an edge error (ref's
+        frame); j == ref gives exact zeros.  `opts` and errors as ``marginals``."""
+        self._build()
+        v, vp = self._vertex_list(vertices)
+        n = len(v)
+        cov = np.zeros((n, 6, 6))
+        o, st = self._marginal_opts(**opts), LslamPgMarginalStats()
+        self._check(self.lib.lslam_pg_relative_covariances(self.h, int(ref), n, vp, C.byref(o), _dp(cov) if n else None, C.byref(st)))
+        self.marginal_stats = st
+        return cov
+
+    def debug_marginal_columns(self, vertex, **opts):
+        """Test tap (lslam_debug_pg_marginal_columns): the six solved columns of H^-1 of one free vertex, (6 n, 6), raw."""
+        self._build()
+        x = np.zeros((6 * len(self._nodes), 6))
+        o, st = self._marginal_opts(**opts), LslamPgMarginalStats()
+        self._check(self.lib.lslam_debug_pg_marginal_columns(self.h, int(vertex), C.byref(o), _dp(x), C.byref(st)))
+        self.marginal_stats = st
+        return x
 
     # ---- internals ---------------------------------------------------------------------------------
     def _check(self, rc):
