@@ -33,11 +33,25 @@ def transform_associate(Lold, Lnew, Wold):
     return mul(mul(Wold, Linv), Lnew)
 
 
+NO_CUBE = -(2 ** 31)  # what the reference's (int) cast makes of a value that is not a number or does not fit: no valid index
+
+
+def round_half_away(q):
+    """std::round of float32 values -> int64.  The half is added in float64, where q + 0.5 is exact for every float32 q below
+    2^24 (a float32 sum rounds the predecessor of 0.5 up to 1.0: one float per cube wall went to the wrong cube).  A value that
+    is not finite, or beyond the int range, gives NO_CUBE."""
+    q = np.asarray(q, F).astype(np.float64)
+    fits = np.isfinite(q) & (np.abs(q) < 2.0 ** 31 - 1.0)
+    r = np.trunc(np.where(fits, q, 0.0) + np.copysign(0.5, q))
+    return np.where(fits, r, float(NO_CUBE)).astype(np.int64)
+
+
 def cube_index(p, cube_size, origin):
-    """worldToCube (FeatureMap.h:475-487) in float32: round(p / size) + origin, half away from zero as std::round."""
-    q = np.asarray(p, F)[..., :3] / F(cube_size)
-    r = np.where(q >= 0, np.floor(q + F(0.5)), np.ceil(q - F(0.5))).astype(F)
-    return (r + np.asarray(origin, F)).astype(np.int64)
+    """worldToCube (FeatureMap.h:475-487): (int)(std::round(p / size) + origin), the quotient a float32, the rounding half away
+    from zero.  A coordinate that is not finite (or absurdly large) gives NO_CUBE on its axis: isIndexValid fails."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = round_half_away(np.asarray(p, F)[..., :3] / F(cube_size))
+    return np.where(r == NO_CUBE, NO_CUBE, r + np.asarray(origin, np.int64))
 
 
 def read_pcd_xyzi(path):

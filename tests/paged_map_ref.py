@@ -15,14 +15,13 @@ import localization_ref as lr
 F = np.float32
 
 
-def round_half_away(q):
-    q = np.asarray(q, F)
-    return np.where(q >= 0, np.floor(q + F(0.5)), np.ceil(q - F(0.5))).astype(np.int64)
+round_half_away = lr.round_half_away  # std::round of a float32 without a second rounding; not finite -> lr.NO_CUBE
 
 
 def glo_idx(p, cube_size):
     """Glo2GloIdx: (int) round(x / cube_size) per axis, a float quotient."""
-    return round_half_away(np.asarray(p, F)[..., :3] / F(cube_size))
+    with np.errstate(invalid="ignore", over="ignore"):
+        return round_half_away(np.asarray(p, F)[..., :3] / F(cube_size))
 
 
 def parse_index(path):

@@ -1,6 +1,6 @@
 """The paged mode of the localisation node (lslam_pmap_*, csrc/lslam_loc.hip; util/DynamicFeatureMap.h) against its
 restatement (tests/paged_map_ref.py, composed from the CPU oracle) and against the static node over the same files: the
-window's contents and counters step by step, the search tap against an in-cube brute force, single sweeps and the trajectory,
+window's contents and counters step by step, the search tap against the oracle tree of every query's cube, single sweeps and the trajectory,
 staging, refusals, the mirrors and the lifetime of the step's buffers.
 
 The scene: localization_ref's world and sweeps, every sweep cut to 30 m, the map binned into 10 m cubes (133 corner and 297 surf
@@ -86,12 +86,14 @@ def _queries(ref, rng, n=1000):
     return out
 
 
-def _brute_in_cube(ref, t, q):
-    """Five nearest of every query inside its own cube of the window: fp32, accumulated x -> y -> z."""
+def _oracle_in_cube(ref, t, q):
+    """Five nearest of every query inside its own cube of the window: ``oracle.kdtree(cube).knn`` -- nanoflann's traversal, which
+    also decides which of several tied points is returned.  tie: an exact tie among the six nearest (fp32, x -> y -> z)."""
     nq = len(q)
     xyz, d2 = np.zeros((nq, 5, 3), F), np.zeros((nq, 5), F)
     ok, tie = np.zeros(nq, bool), np.zeros(nq, bool)
     g = pm.glo_idx(q, ref.cube_size)
+    trees = {}
     for i in range(nq):
         key = tuple(int(v) for v in g[i])
         if not ref.in_window(key):
@@ -99,12 +101,14 @@ def _brute_in_cube(ref, t, q):
         pts = ref.cubes[t].get(key)
         if pts is None or len(pts) < 5:
             continue
+        if key not in trees:
+            trees[key] = ref.o.kdtree(pts)
+        idx, d = trees[key].knn(q[i:i + 1], 5)
         dx, dy, dz = (q[i, 0] - pts[:, 0]).astype(F), (q[i, 1] - pts[:, 1]).astype(F), (q[i, 2] - pts[:, 2]).astype(F)
-        d = ((dx * dx).astype(F) + (dy * dy).astype(F)).astype(F) + (dz * dz).astype(F)
-        order = np.argsort(d, kind="stable")[:6]
+        b = np.sort(((dx * dx).astype(F) + (dy * dy).astype(F)).astype(F) + (dz * dz).astype(F))[:6]
         ok[i] = True
-        tie[i] = bool(np.any(np.diff(d[order]) == 0))
-        xyz[i], d2[i] = pts[order[:5], :3], d[order[:5]]
+        tie[i] = bool(np.any(np.diff(b) == 0))
+        xyz[i], d2[i] = pts[idx[0], :3], d[0]
     return xyz, d2, ok, tie
 
 
@@ -131,11 +135,12 @@ def _check_window(node, ref, rng, label, first):
     tap = []
     for t, q in enumerate(_queries(ref, rng)):
         xyz, d2, how = node.debug_knn5(t, q)
-        bx, bd, ok, tie = _brute_in_cube(ref, t, q)
+        bx, bd, ok, tie = _oracle_in_cube(ref, t, q)
         assert np.array_equal(how != 0, ok), (label, t)
-        sure = ok & ~tie
-        assert sure.sum() > 0.8 * len(q), (label, t, int(sure.sum()))
-        assert np.array_equal(bits(d2[sure]), bits(bd[sure])) and np.array_equal(bits(xyz[sure]), bits(bx[sure])), (label, t)
+        assert (ok & ~tie).sum() > 0.8 * len(q), (label, t, int((ok & ~tie).sum()))
+        # every answered query, the tied ones included: the oracle tree's five bit for bit, zeros where there is no tree
+        assert np.array_equal(bits(d2), bits(bd)) and np.array_equal(bits(xyz), bits(bx)), (label, t)
+        assert np.all(how[ok & tie] == 2), (label, t)
         tap.append((q, xyz, d2, how))
     print("%s: centre %s entered %s files %d trees %d active %d, surround %d / %d points, tap how %s; step: %d kernels %d filter runs "
           "%d forest builds %d waits %d bytes up; arena %d / %d points %d / %d nodes" %

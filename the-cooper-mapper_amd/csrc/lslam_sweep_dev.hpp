@@ -19,7 +19,10 @@ namespace lslam {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // worldToCube + isIndexValid + toIndex (util/FeatureMap.h:475-487,102-108,146-148)
+// A coordinate that is not a number has no cube: the reference's (int) cast makes INT_MIN of it and isIndexValid fails, the
+// device's conversion makes 0 -- a valid index.  (Infinite and huge values saturate and fail the range test by themselves.)
 LSLAM_DEV int cube_tree_of(const CubeGridDev &g, float x, float y, float z) {
+  if (!(x == x && y == y && z == z)) return -1;
   const int gi = (int)(roundf(x / g.cube_size) + (float)g.origin[0]);
   const int gj = (int)(roundf(y / g.cube_size) + (float)g.origin[1]);
   const int gk = (int)(roundf(z / g.cube_size) + (float)g.origin[2]);

@@ -37,8 +37,9 @@ RANGE_CUT = 30.0
 
 
 def glo_idx(p, cube):
-    q = np.asarray(p, F)[:, :3] / F(cube)
-    return np.where(q >= 0, np.floor(q + F(0.5)), np.ceil(q - F(0.5))).astype(np.int64)
+    # std::round of the float32 quotient; the half is added in float64 (a float32 sum rounds the predecessor of 0.5 up to 1.0)
+    q = (np.asarray(p, F)[:, :3] / F(cube)).astype(np.float64)
+    return np.trunc(q + np.copysign(0.5, q)).astype(np.int64)
 
 
 def write_pcd(path, pts):
